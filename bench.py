@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: images/s of the ViT-B/16 224^2 bf16 CLS-feature forward path on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,11 +15,17 @@ One "step" = one pass of the hot path over one batch of synthetic images already
 BASELINE config 3 = 8 x 256) and ONE all-gather (RCCL over xGMI) reassembles the [N*256,768]
 feature matrix inside the step.  Rank 0 prints ONE JSON line.
 
+A plain run does only what that line's headline needs: set up, W warm-up steps, K timed steps (`ms_per_step` is their
+mean), the outputs of the last timed step if --dump-outputs DIR is given (inputs and weights are seeded: the same
+arguments give the same inputs in every run), the line.  --full adds everything below -- the per-kernel figures and the
+roofline, `full_last_block`, the N > 1 gather figures, the CPU baseline -- each taking passes of its own after the
+timed steps; its timed region also brackets the dominant kernel class with HIP events (--clean-timing: not).
+
 Last block: with a CLS output the library runs the last block's out-projection / norm2 / MLP on the CLS rows only (after
 the last attention every operation is row-wise and x[:, 0] is all `model(x) -> (logits, cls)` returns; the features are
 the bits of the full computation, checked in every run: full_last_block.features_bitwise_equal).  `value` is that
-default; `full_last_block.value` (same run, same K steps) computes every token like the reference; the FLOP counts of
-both are on the line and whole_forward_frac prices the FLOPs actually executed.  --full-last-block times the latter.
+default; with --full, `full_last_block.value` (same run, same K steps) computes every token like the reference; the FLOP
+counts of both are on the line and whole_forward_frac prices the FLOPs actually executed.  --full-last-block times the latter.
 
 roofline: the dominant kernel class (by summed time) of the timed region, timed with HIP events
 recorded by libvdr on the stream the kernels are launched on (vdr_profile_*): achieved = algorithmic
@@ -121,6 +127,35 @@ def cpu_baseline_sam(seconds_target=12.0, max_threads=64):
                       f"{os.cpu_count()} logical CPUs visible"}
 
 
+DUMP_BUDGET = 64 << 20  # bytes of all --dump-outputs files together
+
+
+def dump_outputs(path, feats, out_mode, ocfg):
+    """The [N, D] matrix a caller of the timed path receives, as float32 in its caller's shape: [N, dim] CLS features,
+    [N, tokens, dim] per-patch descriptors, [N, grid, grid, out_chans] encoder maps.  Above DUMP_BUDGET a fixed, seeded
+    sample of whole rows (images) is written, sorted, with the row indices next to it as float64."""
+    import numpy as np
+    import vdr
+    if out_mode == vdr.OUT_CLS:
+        name, shape = "cls_features", (ocfg.dim,)
+    elif out_mode == vdr.OUT_DENSE:
+        name, shape = "dense_descriptors", ((ocfg.img // ocfg.patch) ** 2, ocfg.dim)
+    else:
+        name, shape = "encoder_maps", (ocfg.grid, ocfg.grid, ocfg.out_chans)
+    n, d = feats.shape
+    os.makedirs(path, exist_ok=True)
+    rows = None
+    if n * d * 4 > DUMP_BUDGET:
+        keep = (DUMP_BUDGET - 8 * n) // (4 * d)
+        if keep < 1:
+            raise SystemExit(f"--dump-outputs: one row of {d} values does not fit in {DUMP_BUDGET >> 20} MB")
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        feats = feats[rows.to(feats.device)]
+    np.save(os.path.join(path, f"{name}.npy"), feats.float().cpu().numpy().reshape((feats.shape[0],) + shape))
+    if rows is not None:
+        np.save(os.path.join(path, f"{name}_rows.npy"), rows.double().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -161,8 +196,18 @@ def main():
     ap.add_argument("--dense-dtype", choices=["bf16", "fp32"], default="bf16",
                     help="--out dense: dtype of the gathered per-patch descriptors (BASELINE config 4 states bf16)")
     ap.add_argument("--clean-timing", action="store_true",
-                    help="keep the per-kernel HIP events out of the timed region (roofline from a second pass)")
+                    help="--full: keep the per-kernel HIP events out of the timed region (roofline from a second pass)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, measure and check everything else: the dominant kernel class bracketed "
+                         "with HIP events in the timed region, the per-class table and roofline from a second pass, the FLOP "
+                         "accounting check, `full_last_block`, the N > 1 gather figures and the CPU baseline (off by default: "
+                         "a plain run sets up, warms up, times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32; a fixed, "
+                         f"seeded sample of rows above {DUMP_BUDGET >> 20} MB, with their indices in DIR/<name>_rows.npy)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ  # torchrun / torch.distributed.run
     if a.gpus > 1 and not launched:
@@ -250,41 +295,46 @@ def main():
     for _ in range(a.warmup):
         step()
     sync()
-    # one fully bracketed (untimed) step: which class dominates
-    eng.profile(True)
-    eng.profile_read()
-    step()
-    sync()
-    prof_one = eng.profile_read()
-    dom = max((k for k in prof_one if k in GEMM_CLASSES), key=lambda k: prof_one[k]["ms"])
-    # timed region: ONLY the dominant kernel class is bracketed with HIP events (its launches are
-    # timed live on the stream they run on; 2 events per launch keep the cost negligible)
-    eng.profile(not a.clean_timing, classes=[dom])
-    eng.profile_read()
-    sync()
+    if a.full:
+        # one fully bracketed (untimed) step: which class dominates
+        eng.profile(True)
+        eng.profile_read()
+        step()
+        sync()
+        prof_one = eng.profile_read()
+        dom = max((k for k in prof_one if k in GEMM_CLASSES), key=lambda k: prof_one[k]["ms"])
+        # timed region: ONLY the dominant kernel class is bracketed with HIP events (its launches are
+        # timed live on the stream they run on; 2 events per launch keep the cost negligible)
+        eng.profile(not a.clean_timing, classes=[dom])
+        eng.profile_read()
+        sync()
     t0 = time.perf_counter()
     for _ in range(a.steps):
         step()
     sync()
     dt = time.perf_counter() - t0
-    prof_dom = eng.profile_read()
-    eng.profile(False)
-    # second, untimed pass over the same K steps with EVERY class bracketed: the per-class table is an average over K
-    # steps, like the dominant class (one step alone reads im2col at 0.063 ms where rocprof's average says 0.036)
-    eng.profile(True)
-    eng.profile_read()
-    for _ in range(a.steps):
-        step()
-    sync()
-    prof_all = eng.profile_read()
-    eng.profile(False)
-    if a.clean_timing:
-        prof_dom = {dom: prof_all[dom]}
-    for v in prof_all.values():  # per step
-        v["ms"] /= a.steps
-        v["flops"] /= a.steps
-        v["bytes"] /= a.steps
-        v["launches"] = v["launches"] / a.steps
+    # what the timed path returned in its last step, before any measurement below writes the same buffers again
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, feats, out_mode, ocfg)
+    if a.full:
+        prof_dom = eng.profile_read()
+        eng.profile(False)
+        # second, untimed pass over the same K steps with EVERY class bracketed: the per-class table is an average over K
+        # steps, like the dominant class (one step alone reads im2col at 0.063 ms where rocprof's average says 0.036)
+        eng.profile(True)
+        eng.profile_read()
+        for _ in range(a.steps):
+            step()
+        sync()
+        prof_all = eng.profile_read()
+        eng.profile(False)
+        if a.clean_timing:
+            prof_dom = {dom: prof_all[dom]}
+        for v in prof_all.values():  # per step
+            v["ms"] /= a.steps
+            v["flops"] /= a.steps
+            v["bytes"] /= a.steps
+            v["launches"] = v["launches"] / a.steps
 
     # informational: the same K steps with the batch split over two internal HIP streams (vdr_config.streams = 2,
     # micro_batch = B/2).  Kernels of the two halves overlap (one GEMM's store-heavy epilogue and ramp-down under the
@@ -313,7 +363,7 @@ def main():
     # x[:, 0].  The default (timed above) runs the last block's out-projection / MLP on the CLS rows only -- the same
     # features bit for bit -- and that is an algorithmic saving of this path, so both numbers are on the line.
     full = None
-    if not a.full_last_block and not sam and not dense and world == 1:
+    if a.full and not a.full_last_block and not sam and not dense and world == 1:
         try:
             mf = vdr.load_model(a.model, weights=weights, device=dev, micro_batch=a.micro_batch, streams=a.streams, fp8=a.fp8,
                                 full_last_block=True, fp8_cls_bf16=a.fp8_cls_bf16, resid_fp32=a.resid_fp32,
@@ -336,7 +386,7 @@ def main():
     # N > 1, informational: what the transfers of a step occupy on the side stream, and the same K steps WITHOUT any
     # transfer (the N = 1-equivalent rate of this rank: what the overlap is measured against)
     gather = None
-    if og is not None:
+    if a.full and og is not None:
         step()
         sync()
         gms = og.last_gather_ms()
@@ -356,7 +406,7 @@ def main():
     dt = t.item()
     assert torch.isfinite(feats.float()).all()
 
-    if rank == 0:
+    if rank == 0 and a.full:
         flops_ref = so.flops_per_image(ocfg) if sam else vo.flops_per_image(ocfg)  # every token of every block
         # what this forward executes (sum of the launches' algorithmic FLOPs, booked by the library per launch): equal
         # to flops_ref except for the CLS-rows-only tail of the last block
@@ -364,8 +414,6 @@ def main():
         flops_img = flops_ref if sam else sum(v["flops"] for v in prof_all.values()) / B
         if not (0.85 * flops_ref <= flops_img <= 1.001 * flops_ref):
             raise SystemExit(f"executed FLOPs per image {flops_img:.4g} vs the model's {flops_ref:.4g}: accounting is off")
-        ms = dt / a.steps * 1e3
-        ips = total * a.steps / dt
         kern = {}
         for k, v in prof_all.items():
             e = {"ms_per_step": round(v["ms"], 4), "launches_per_step": v["launches"]}
@@ -408,13 +456,16 @@ def main():
             roof["attention_block"] = {"ms_per_step": round(bms, 3), "TFLOP/s": round(sum(v["flops"] for v in blk) / (bms * 1e-3) / 1e12, 1),
                                        "frac": round(sum(v["flops"] for v in blk) / (bms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
                                        "target_frac": 0.60}
+    if rank == 0:
+        ms = dt / a.steps * 1e3
+        ips = total * a.steps / dt
         out = {"metric": "images/sec, ViT-B/16 224^2 bf16 CLS-feature extraction" if a.model == "vit_base16_224"
                and not a.fp8 and not dense else ("slices/sec, MedSAM ViT-B 1024^2 dense descriptor (64,64,256)" + (" fp8 weights" if a.fp8 else "") if sam
                      else f"images/sec, {a.model}{' fp8 weights' if a.fp8 else ''} {'dense-descriptor' if dense else 'CLS-feature'} extraction"),
                "value": round(ips, 1), "unit": "images/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
                "rccl_ranks": dist.get_world_size() if launched else 1,
                "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-               "dtype": "fp8 (MX e4m3 qkv/fc1/fc2, bf16 elsewhere)" if a.fp8 else "bf16", "data": "synthetic",
+               "dtype": "fp8 (MX e4m3 qkv/fc1/fc2, bf16 elsewhere)" if a.fp8 else "bf16", "data": "synthetic", "full": a.full,
                "config": {"workload": (f"medsam (SAM ViT-B image encoder) {ocfg.img}^2 fp32 in / bf16 compute, batch {B}/GPU -> "
                                        f"[{total},64,64,256] fp32" if sam else
                                        f"{a.model} {ocfg.img}^2 {'MX-fp8 weights' if a.fp8 else 'bf16'}, batch {B}/GPU, {'dense per-patch descriptors' if dense else 'CLS-token extraction'} -> [{total},{D}] {'bf16' if fdt == torch.bfloat16 else 'fp32'}")
@@ -424,12 +475,14 @@ def main():
                           "fp8_cls_bf16": bool(a.fp8_cls_bf16), "resid_fp32": bool(a.resid_fp32), "ln_fin_fused": bool(a.ln_fin_fused),
                           "last_block": "every token" if (a.full_last_block or sam or dense) else
                                         "attention on every token; out-projection / norm2 / MLP on the CLS rows only (bitwise the same features)"},
-               "feature_GBps": round(total * D * feats.element_size() * a.steps / dt / 1e9, 4),
-               "gather": gather,
-               "TFLOPs_per_s": round(flops_img * total * a.steps / dt / 1e12, 1),
-               "roofline": roof, "kernels": kern, "two_stream": two, "full_last_block": full}
-        if not a.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline_sam() if sam else cpu_baseline(a.model)
+               "feature_GBps": round(total * D * feats.element_size() * a.steps / dt / 1e9, 4)}
+        if a.full:
+            out.update({"gather": gather, "TFLOPs_per_s": round(flops_img * total * a.steps / dt / 1e12, 1),
+                        "roofline": roof, "kernels": kern, "two_stream": two, "full_last_block": full})
+            if not a.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline_sam() if sam else cpu_baseline(a.model)
+        elif two is not None:
+            out["two_stream"] = two
         print(json.dumps(out), flush=True)
     if launched:
         dist.barrier()

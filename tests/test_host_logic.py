@@ -141,6 +141,36 @@ def test_bench_plain_multi_gpu_command_line_starts_the_ranks():
     assert '"n_gpus"' not in r.stdout
 
 
+def test_bench_dump_outputs_whole_matrix_or_a_seeded_row_sample(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: the matrix of the last timed step as float32 in its caller's shape while it fits the
+    budget; above it a fixed, seeded sample of whole rows (the same rows in every run) with their indices as float64."""
+    import importlib.util
+    import vdr
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    cfg = vo.CONFIGS["vit_base16_224"]
+    g = torch.Generator().manual_seed(3)
+    cls = torch.randn(6, cfg.dim, generator=g)
+    bench.dump_outputs(str(tmp_path / "cls"), cls, vdr.OUT_CLS, cfg)
+    assert sorted(os.listdir(tmp_path / "cls")) == ["cls_features.npy"]
+    got = np.load(tmp_path / "cls" / "cls_features.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, cls.numpy())
+    n_tok = (cfg.img // cfg.patch) ** 2
+    dense = torch.randn(8, n_tok * cfg.dim, generator=g).to(torch.bfloat16)
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 3 * n_tok * cfg.dim * 4 + 8 * 8)  # room for 3 rows and the index
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), dense, vdr.OUT_DENSE, cfg)
+    vals, rows = np.load(tmp_path / "a" / "dense_descriptors.npy"), np.load(tmp_path / "a" / "dense_descriptors_rows.npy")
+    assert vals.dtype == np.float32 and vals.shape == (3, n_tok, cfg.dim) and rows.dtype == np.float64
+    assert list(rows) == sorted(set(rows)) and 0 <= rows[0] and rows[-1] < 8
+    assert np.array_equal(vals, dense.float()[torch.from_numpy(rows).long()].reshape(3, n_tok, cfg.dim).numpy())
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_BUDGET + 2 * 128
+    for f in ("dense_descriptors.npy", "dense_descriptors_rows.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+
+
 def test_pipeline_roi_host_logic_matches_reference_goldens(golden_dir):
     """vdr.pipeline's host-side box maths (extract_coords / extract_roi / crop_image) vs the reference's own
     functions (tests/golden/prep_roi.npz)."""

@@ -919,3 +919,30 @@ def test_resid_fp32_master_copy_of_the_residual_stream(name, ln_fold):
         got = _engine(cfg, w, ln_fold=ln_fold, resid_fp32=True, micro_batch=mb).forward(x.cuda(), vdr.OUT_CLS)
         assert torch.equal(got, ref_cls), f"micro_batch {mb}"
     assert torch.equal(e32.forward(x.cuda(), vdr.OUT_DENSE), full.forward(x.cuda(), vdr.OUT_DENSE))
+
+
+def test_bench_plain_run_dumps_the_features_of_its_last_timed_step(tmp_path):
+    """A plain `bench.py` run: one JSON line with the headline keys and none of the --full figures, `steps` as asked, and
+    --dump-outputs holding what the timed path returned -- bitwise the same forward on bench.py's seeded inputs."""
+    import json
+    import subprocess
+    import sys
+    import vdr
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "8",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+    assert line["steps"] == 3 and line["full"] is False and line["value"] > 0 and line["ms_per_step"] > 0
+    assert not {"kernels", "roofline", "full_last_block", "cpu_baseline"} & set(line)
+    assert sorted(os.listdir(tmp_path)) == ["cls_features.npy"]
+    got = np.load(tmp_path / "cls_features.npy")
+    ocfg = vo.CONFIGS["vit_base16_224"]
+    assert got.dtype == np.float32 and got.shape == (8, ocfg.dim)
+    model = vdr.load_model("vit_base16_224", weights=vo.make_weights(ocfg, seed=1), device=torch.device("cuda", 0))
+    images = torch.rand(8, 3, ocfg.img, ocfg.img, generator=torch.Generator().manual_seed(1000)).to(torch.bfloat16).cuda()
+    want = torch.empty(8, ocfg.dim, device="cuda")
+    model.engine.forward_into(images, want, vdr.OUT_CLS)
+    torch.cuda.synchronize()
+    assert np.array_equal(got, want.cpu().numpy())

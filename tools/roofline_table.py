@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kernel-class roofline table from one bench.py JSON line (HIP-event timings of the profiled warm-up step):
+"""Per-kernel-class roofline table from one `bench.py --full` JSON line (HIP-event timings of the profiled warm-up step):
    python tools/roofline_table.py profiles/r01_bench_default.json.log > profiles/r01_roofline_table.md"""
 import json
 import sys
