@@ -83,7 +83,7 @@ typedef struct {
   int32_t patch;      /* patch side p (14, 16); 0 for a token model                           */
   int32_t in_chans;   /* 3                                                                    */
   int32_t dim;        /* D                                                                    */
-  int32_t heads;      /* H ; D / H must be 64                                                 */
+  int32_t heads;      /* H ; D / H in {32, 64, 96, 128}; 64 when fp8 = 1 or window > 0        */
   int32_t layers;     /* L                                                                    */
   int32_t mlp_hidden; /* F (GELU: fc1 out; SwiGLU: hidden of w3's input)                      */
   int32_t act;        /* vdr_act                                                              */
@@ -329,7 +329,8 @@ int vdr_op_voxel_sequence(const float* feat, const int64_t* index, const double*
                           int D, void* out, int out_dtype, void* stream);
 
 /* F.scaled_dot_product_attention over a packed qkv activation — the core of
- * nn.MultiheadAttention (models_archs.py:130) / Attention.forward of the ViTs.
+ * nn.MultiheadAttention (models_archs.py:130) / Attention.forward of the ViTs.  Head dim 64; any head dim of
+ * vdr_config.heads: vdr_op_attention_hd.
  *   qkv [batch*seq, 3*H*64] bf16, row = token, columns [q | k | v] each [H, 64]
  *   out [batch*seq, H*64] bf16;  softmax(q k^T / 8) v per (batch, head), no mask.
  *   variant: 0 = library choice; 1 = chunked (online softmax over 128-key chunks), 2 = persistent kernel without,
@@ -337,6 +338,15 @@ int vdr_op_voxel_sequence(const float* feat, const int64_t* index, const double*
  *   produce the same bits for sequences that fit one chunk. */
 int vdr_op_attention(const void* qkv, void* out, int batch, int seq, int heads, int variant,
                      void* stream);
+
+/* The same at head dim dh = head_dim in {32, 64, 96, 128}:
+ *   qkv [batch*seq, 3*H*dh] bf16, columns [q | k | v] each [H, dh];  out [batch*seq, H*dh] bf16;
+ *   softmax(q k^T dh^-0.5) v per (batch, head), no mask, any seq >= 1.
+ *   head_dim 64 is vdr_op_attention (same kernels, same bits, same variants).  32 / 96 / 128 run one kernel (online
+ *   softmax over key chunks) whatever the variant (0..4); a (batch entry, head)'s output does not depend on batch.
+ *   Any other head_dim: VDR_ERR_UNSUPPORTED. */
+int vdr_op_attention_hd(const void* qkv, void* out, int batch, int seq, int heads, int head_dim, int variant,
+                        void* stream);
 
 /* SAM / MedSAM Attention.forward with use_rel_pos (third-party segment_anything ImageEncoderViT, called at
  * tfds_dense_descriptor.py:123): per (window, head) softmax(q k^T dh^-0.5 + q.Rh[qh-kh] + q.Rw[qw-kw]) v.

@@ -597,8 +597,12 @@ static hipError_t launch_nt(const AttnK& k, int batch, hipStream_t s) {
 }
 
 hipError_t launch_attention(const void* qkv, void* out, int batch, int seq, int heads, int variant,
-                            hipStream_t s, void* out_scale, const int* lens, int len_add) {
+                            hipStream_t s, void* out_scale, const int* lens, int len_add, int head_dim) {
   if (batch <= 0 || seq <= 0 || heads <= 0) return hipErrorInvalidValue;
+  if (head_dim != 64) {  // 32 / 96 / 128: attention_hd.hip (one kernel for every variant, no MX-fp8 output)
+    if (out_scale || variant < 0 || variant > 4) return hipErrorInvalidValue;
+    return launch_attention_hd(qkv, out, batch, seq, heads, head_dim, s, lens, len_add);
+  }
   AttnK k;
 #ifdef VDR_TUNING
   k.abl = variant / 10;

@@ -936,9 +936,9 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
                         D, 3 * D, EPI_BIAS)))
         return rc;
       {
-        Scope sc(m, s, VDR_K_ATTENTION, 4.0 * (double)ntok * ntok * 64.0 * H * mb, 2.0 * (double)M * 4 * D);
+        Scope sc(m, s, VDR_K_ATTENTION, 4.0 * (double)ntok * ntok * D * mb, 2.0 * (double)M * 4 * D);
         VDR_KNOB int attn_variant = env_int("VDR_ATTN_VARIANT", 0);  // (tuning builds)
-        VDR_TRY(launch_attention(w.qkv, w.o, mb, ntok, H, attn_variant, s, nullptr, lens, len_add), "attention");
+        VDR_TRY(launch_attention(w.qkv, w.o, mb, ntok, H, attn_variant, s, nullptr, lens, len_add, D / H), "attention");
       }
       if (i == tail_at) {
         *compact = true;
@@ -989,9 +989,9 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
                      nullptr, w.Mp)))
         return rc;
       {
-        Scope sc(m, s, VDR_K_ATTENTION, 4.0 * (double)ntok * ntok * 64.0 * H * mb, 2.0 * (double)M * 4 * D);
+        Scope sc(m, s, VDR_K_ATTENTION, 4.0 * (double)ntok * ntok * D * mb, 2.0 * (double)M * 4 * D);
         VDR_KNOB int attn_variant = env_int("VDR_ATTN_VARIANT", 0);  // (tuning builds)
-        VDR_TRY(launch_attention(w.qkv, w.o, mb, ntok, H, attn_variant, s, nullptr, lens, len_add), "attention");
+        VDR_TRY(launch_attention(w.qkv, w.o, mb, ntok, H, attn_variant, s, nullptr, lens, len_add, D / H), "attention");
       }
       if (i == tail_at) {
         *compact = true;
@@ -1023,9 +1023,9 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
                    nullptr, w.Mp)))
       return rc;
     {
-      Scope sc(m, s, VDR_K_ATTENTION, 4.0 * (double)ntok * ntok * 64.0 * H * mb, 2.0 * (double)M * 4 * D);
+      Scope sc(m, s, VDR_K_ATTENTION, 4.0 * (double)ntok * ntok * D * mb, 2.0 * (double)M * 4 * D);
       VDR_KNOB int attn_variant = env_int("VDR_ATTN_VARIANT", 0);
-      VDR_TRY(launch_attention(w.qkv, w.o, mb, ntok, H, attn_variant, s, nullptr, lens, len_add), "attention");
+      VDR_TRY(launch_attention(w.qkv, w.o, mb, ntok, H, attn_variant, s, nullptr, lens, len_add, D / H), "attention");
     }
     if (i == tail_at) {
       *compact = true;
@@ -1287,7 +1287,14 @@ int vdr_create(const vdr_config* cfg, int device, vdr_handle* out) {
   const vdr_config& c = *cfg;
   if (c.dim <= 0 || c.heads <= 0 || c.layers < 0 || c.mlp_hidden <= 0)
     return fail(nullptr, VDR_ERR_INVALID, "dim/heads/layers/mlp_hidden must be positive");
-  if (c.dim != c.heads * 64) return fail(nullptr, VDR_ERR_UNSUPPORTED, "head dim must be 64 (dim == 64*heads)");
+  {
+    const int dh = c.dim / c.heads;
+    if (c.dim % c.heads || (dh != 32 && dh != 64 && dh != 96 && dh != 128))
+      return fail(nullptr, VDR_ERR_UNSUPPORTED, "head dim must be 32, 64, 96 or 128 (dim == head dim * heads)");
+    // the MX-fp8 attention output and its scales are laid out per 64 channels; the SAM rel-pos tables are [2S-1, 64]
+    if (dh != 64 && c.fp8) return fail(nullptr, VDR_ERR_UNSUPPORTED, "fp8 = 1 needs head dim 64");
+    if (dh != 64 && c.window > 0) return fail(nullptr, VDR_ERR_UNSUPPORTED, "windowed (SAM) attention needs head dim 64");
+  }
   if (c.dim % 64 || c.mlp_hidden % 64 || c.dim > 2048)
     return fail(nullptr, VDR_ERR_UNSUPPORTED, "dim and mlp_hidden must be multiples of 64, dim <= 2048");
   if (c.patch) {
@@ -1889,6 +1896,16 @@ int vdr_op_attention(const void* qkv, void* out, int batch, int seq, int heads, 
   int rc = check_device(nullptr);
   if (rc) return rc;
   OP_TRY(launch_attention(qkv, out, batch, seq, heads, variant, (hipStream_t)stream), "attention");
+  return VDR_OK;
+}
+
+int vdr_op_attention_hd(const void* qkv, void* out, int batch, int seq, int heads, int head_dim, int variant, void* stream) {
+  if (head_dim != 32 && head_dim != 64 && head_dim != 96 && head_dim != 128)
+    return fail(nullptr, VDR_ERR_UNSUPPORTED, "head dim must be 32, 64, 96 or 128");
+  if (!qkv || !out) return fail(nullptr, VDR_ERR_INVALID, "null argument");
+  int rc = check_device(nullptr);
+  if (rc) return rc;
+  OP_TRY(launch_attention(qkv, out, batch, seq, heads, variant, (hipStream_t)stream, nullptr, nullptr, 0, head_dim), "attention");
   return VDR_OK;
 }
 

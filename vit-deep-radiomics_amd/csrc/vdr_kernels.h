@@ -138,8 +138,13 @@ hipError_t launch_layernorm(const LnArgs& a, hipStream_t s);
 //   out_scale != NULL: `out` is written as MX-fp8 (payload [batch*seq][heads*64] bytes + e8m0 scales), the
 //   operand of the fp8 out-projection
 hipError_t launch_attention(const void* qkv, void* out, int batch, int seq, int heads, int variant,
-                            hipStream_t s, void* out_scale = nullptr, const int* lens = nullptr, int len_add = 0);
+                            hipStream_t s, void* out_scale = nullptr, const int* lens = nullptr, int len_add = 0,
+                            int head_dim = 64);
 //   lens != NULL: entry b attends over its first lens[b] + len_add rows only (sequences padded to seq)
+//   head_dim: 64 (attention.hip), or 32 / 96 / 128 (attention_hd.hip: bf16 out only, every variant the same kernel);
+//   qkv [batch*seq, 3*heads*head_dim], out [batch*seq, heads*head_dim]
+hipError_t launch_attention_hd(const void* qkv, void* out, int batch, int seq, int heads, int head_dim, hipStream_t s,
+                               const int* lens, int len_add);
 
 // SAM / MedSAM decomposed relative position bias (attention_relpos.hip)
 //   qkv rows are S*S-token windows (or whole grids) back to back

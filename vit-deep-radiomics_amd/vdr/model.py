@@ -269,9 +269,7 @@ class _CrossAttentionCls:
         W = sd[prefix + ".multihead_attn.in_proj_weight"].float()
         b = sd[prefix + ".multihead_attn.in_proj_bias"].float()
         D = W.shape[1]
-        if D != heads * 64:
-            raise ValueError(f"cross attention needs head dim 64 (dim {D}, heads {heads})")
-        self.D, self.heads = D, heads
+        self.D, self.heads, self.head_dim = D, heads, D // heads  # (nn.MultiheadAttention: heads divides D)
         self.wq, self.bq = W[:D].to(dev, torch.bfloat16).contiguous(), b[:D].to(dev).contiguous()
         self.wkv, self.bkv = W[D:].to(dev, torch.bfloat16).contiguous(), b[D:].to(dev).contiguous()
         self.wo = sd[prefix + ".multihead_attn.out_proj.weight"].to(dev, torch.bfloat16).contiguous()
@@ -285,7 +283,7 @@ class _CrossAttentionCls:
         qkv = torch.zeros((B, Sk, 3 * D), dtype=torch.bfloat16, device=xkv.device)
         qkv[:, :, D:] = ops.linear(xkv.reshape(B * Sk, D).contiguous(), self.wkv, self.bkv).view(B, Sk, 2 * D)
         qkv[:, 0, :D] = q
-        o = ops.attention(qkv.view(B * Sk, 3 * D), B, Sk, self.heads).view(B, Sk, D)[:, 0, :].contiguous()
+        o = ops.attention(qkv.view(B * Sk, 3 * D), B, Sk, self.heads, head_dim=self.head_dim).view(B, Sk, D)[:, 0, :].contiguous()
         return ops.linear(o, self.wo, self.bo).float()
 
 

@@ -125,12 +125,17 @@ def pack_w12(w12: torch.Tensor, b12: torch.Tensor):
     return w12[src].contiguous(), b12[src].contiguous()
 
 
-def attention(qkv: torch.Tensor, batch: int, seq: int, heads: int, variant=0):
+def attention(qkv: torch.Tensor, batch: int, seq: int, heads: int, variant=0, head_dim=64):
+    """softmax(q k^T / sqrt(head_dim)) v per (batch entry, head) over a packed [batch*seq, 3*heads*head_dim] bf16
+    activation (columns [q | k | v], each [heads, head_dim]); head_dim in {32, 64, 96, 128}."""
     lib = L.load()
     assert qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.is_contiguous()
-    assert qkv.shape == (batch * seq, 3 * heads * 64)
-    out = torch.empty((batch * seq, heads * 64), dtype=torch.bfloat16, device=qkv.device)
-    L.check(lib.vdr_op_attention(qkv.data_ptr(), out.data_ptr(), batch, seq, heads, variant, _s(qkv)))
+    assert qkv.shape == (batch * seq, 3 * heads * head_dim)
+    out = torch.empty((batch * seq, heads * head_dim), dtype=torch.bfloat16, device=qkv.device)
+    if head_dim == 64:
+        L.check(lib.vdr_op_attention(qkv.data_ptr(), out.data_ptr(), batch, seq, heads, variant, _s(qkv)))
+    else:
+        L.check(lib.vdr_op_attention_hd(qkv.data_ptr(), out.data_ptr(), batch, seq, heads, head_dim, variant, _s(qkv)))
     return out
 
 
