@@ -348,6 +348,15 @@ int vdr_op_attention(const void* qkv, void* out, int batch, int seq, int heads, 
 int vdr_op_attention_hd(const void* qkv, void* out, int batch, int seq, int heads, int head_dim, int variant,
                         void* stream);
 
+/* The same with per-sequence lengths (the masking vdr_forward_tokens_varlen runs): batch entry b attends over its
+ * first len_b = min(seq, lens[b] + len_add) rows only, as keys; rows past len_b are padding.
+ *   lens  device int32 [batch]; every lens[b] + len_add >= 1
+ *   Rows < len_b of the output do not depend on the padding rows' contents (any bits, NaN and Inf included) nor on
+ *   seq; rows >= len_b are undefined.  With lengths only the one-shot (3) and online (1) kernels run: variants 0, 2
+ *   and 4 take the one-shot kernel at seq <= 288.  head_dim as vdr_op_attention_hd. */
+int vdr_op_attention_varlen(const void* qkv, void* out, int batch, int seq, int heads, int head_dim,
+                            const int32_t* lens, int len_add, int variant, void* stream);
+
 /* SAM / MedSAM Attention.forward with use_rel_pos (third-party segment_anything ImageEncoderViT, called at
  * tfds_dense_descriptor.py:123): per (window, head) softmax(q k^T dh^-0.5 + q.Rh[qh-kh] + q.Rw[qw-kw]) v.
  *   qkv   [batch*S*S, 3*H*64] bf16, `batch` windows (or whole grids) of S x S tokens, row-major (h, w)

@@ -49,6 +49,19 @@ def test_invalid_configs_are_rejected_before_touching_a_device():
     assert lib.vdr_create(None, 0, C.byref(h)) == -1
 
 
+def test_attention_varlen_refuses_bad_arguments_before_touching_a_device():
+    from vdr import _lib
+    lib = _lib.load()
+    buf = (C.c_char * 64)()
+    assert lib.vdr_op_attention_varlen(None, buf, 1, 1, 1, 64, buf, 0, 0, None) == -1  # VDR_ERR_INVALID
+    assert lib.vdr_op_attention_varlen(buf, None, 1, 1, 1, 64, buf, 0, 0, None) == -1
+    assert lib.vdr_op_attention_varlen(buf, buf, 1, 1, 1, 64, None, 0, 0, None) == -1  # lengths are required
+    assert b"null" in lib.vdr_last_error(None)
+    for dh in (0, 16, 48, 63, 256):
+        assert lib.vdr_op_attention_varlen(buf, buf, 1, 1, 1, dh, buf, 0, 0, None) == -7  # VDR_ERR_UNSUPPORTED
+        assert b"head dim" in lib.vdr_last_error(None)
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="only meaningful on a box without a GPU")
 def test_no_gpu_means_loud_failure_not_fallback():
     import vdr
@@ -63,6 +76,7 @@ def test_no_gpu_means_loud_failure_not_fallback():
         vdr.Engine(vdr.VdrConfig())
     buf = (C.c_char * 64)()
     assert lib.vdr_op_attention(buf, buf, 1, 1, 1, 0, None) == -2
+    assert lib.vdr_op_attention_varlen(buf, buf, 1, 1, 1, 64, buf, 0, 0, None) == -2
     assert lib.vdr_op_layernorm(buf, 0, buf, 0, buf, buf, 1, 4, 1e-5, None) == -2
 
 

@@ -144,7 +144,10 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(AttnK p) {
   };
 
   // staging of one key chunk.  The LDS-DMA is an opaque instruction (glds16_raw): hipcc orders nothing after it, the
-  // explicit vmcnt(0) + barrier of stage_wait does.
+  // explicit vmcnt(0) + barrier of stage_wait does.  Rows past the valid length repeat its last row: a 16-key slice that
+  // straddles the length still runs its P.V MFMA, where a masked key's P = 0 times a NaN / Inf padding row would give
+  // NaN (0 x finite = 0).  Without lengths, len == seq.
+  const int last = max(len, 1) - 1;
   auto stage_issue = [&](int kc0) {
     // K: KEYS rows of 128 B, 8 rows per wave-instruction
 #pragma unroll
@@ -153,18 +156,18 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(AttnK p) {
       const int r = piece * 8 + (lane >> 3);
       const int c = (lane & 7) ^ ((r >> 1) & 7);
       int key = kc0 + r;
-      key = key < p.seq ? key : p.seq - 1;
+      key = key < last ? key : last;
       glds16_raw(kb + (int64_t)key * p.ld_qkv + c * 8, sK + piece * 1024);
     }
     // V rows the same way (row-major, chunk ^ (((key >> 1) & 1) << 2)), consumed by ds_read_b64_tr_b16 in process():
-    // no register-staged transpose; rows past the sequence repeat the last key (their P is exp(-inf) = 0)
+    // no register-staged transpose
 #pragma unroll
     for (int q = 0; q < NT; ++q) {
       const int piece = wave * NT + q;
       const int r = piece * 8 + (lane >> 3);
       const int c = (lane & 7) ^ (((r >> 1) & 1) << 2);
       int key = kc0 + r;
-      key = key < p.seq ? key : p.seq - 1;
+      key = key < last ? key : last;
       glds16_raw(vb + (int64_t)key * p.ld_qkv + c * 8, sVt + piece * 1024);
     }
   };

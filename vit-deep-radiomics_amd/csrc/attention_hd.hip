@@ -120,14 +120,16 @@ __global__ __launch_bounds__(256, 2) void attn_hd_kernel(AttnHdK p) {
   constexpr float sc = attn_hd_scale<DH>();
 
   // staging: thread tid moves pieces tid + 256 i (row = piece / CPR, 16-byte column = piece % CPR) of K and of V;
-  // rows past the sequence repeat its last row (masked keys, never read by a valid P)
+  // rows past the valid length repeat its last row: a 16-key slice that straddles the length still runs its P.V MFMA,
+  // where P = 0 times a NaN / Inf padding row would give NaN (0 x finite = 0)
   bf16x8 rk[PPT], rv[PPT];
+  const int last = max(len, 1) - 1;
   auto stage_load = [&](int kc0) {
 #pragma unroll
     for (int i = 0; i < PPT; ++i) {
       const int piece = tid + 256 * i;
       const int r = piece / CPR, c = piece - (piece / CPR) * CPR;
-      const int key = min(kc0 + r, p.seq - 1);
+      const int key = min(kc0 + r, last);
       rk[i] = *reinterpret_cast<const bf16x8*>(kb + (int64_t)key * p.ld_qkv + c * 8);
       rv[i] = *reinterpret_cast<const bf16x8*>(vb + (int64_t)key * p.ld_qkv + c * 8);
     }

@@ -1909,6 +1909,18 @@ int vdr_op_attention_hd(const void* qkv, void* out, int batch, int seq, int head
   return VDR_OK;
 }
 
+int vdr_op_attention_varlen(const void* qkv, void* out, int batch, int seq, int heads, int head_dim, const int32_t* lens,
+                            int len_add, int variant, void* stream) {
+  if (head_dim != 32 && head_dim != 64 && head_dim != 96 && head_dim != 128)
+    return fail(nullptr, VDR_ERR_UNSUPPORTED, "head dim must be 32, 64, 96 or 128");
+  if (!qkv || !out || !lens) return fail(nullptr, VDR_ERR_INVALID, "null argument");
+  int rc = check_device(nullptr);
+  if (rc) return rc;
+  OP_TRY(launch_attention(qkv, out, batch, seq, heads, variant, (hipStream_t)stream, nullptr, lens, len_add, head_dim),
+         "attention");
+  return VDR_OK;
+}
+
 int vdr_op_attention_relpos(const void* qkv, const float* rel_pos_h, const float* rel_pos_w, float* rel, void* out,
                             int batch, int S, int heads, void* stream) {
   if (!qkv || !rel_pos_h || !rel_pos_w || !rel || !out) return fail(nullptr, VDR_ERR_INVALID, "null argument");

@@ -68,6 +68,7 @@ SYMBOLS = {
     "vdr_op_linear_mx": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P]),
     "vdr_op_attention": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "vdr_op_attention_hd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "vdr_op_attention_varlen": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
     "vdr_op_attention_relpos": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "vdr_op_patch_embed": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vdr_profile_enable": (_I, [_P, _I]),

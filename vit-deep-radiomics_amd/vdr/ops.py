@@ -125,14 +125,23 @@ def pack_w12(w12: torch.Tensor, b12: torch.Tensor):
     return w12[src].contiguous(), b12[src].contiguous()
 
 
-def attention(qkv: torch.Tensor, batch: int, seq: int, heads: int, variant=0, head_dim=64):
+def attention(qkv: torch.Tensor, batch: int, seq: int, heads: int, variant=0, head_dim=64, lengths=None, len_add=0):
     """softmax(q k^T / sqrt(head_dim)) v per (batch entry, head) over a packed [batch*seq, 3*heads*head_dim] bf16
-    activation (columns [q | k | v], each [heads, head_dim]); head_dim in {32, 64, 96, 128}."""
+    activation (columns [q | k | v], each [heads, head_dim]); head_dim in {32, 64, 96, 128}.
+    lengths (int [batch]): entry b attends over its first min(seq, lengths[b] + len_add) rows only; the output rows
+    past that length are undefined."""
     lib = L.load()
     assert qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.is_contiguous()
     assert qkv.shape == (batch * seq, 3 * heads * head_dim)
     out = torch.empty((batch * seq, heads * head_dim), dtype=torch.bfloat16, device=qkv.device)
-    if head_dim == 64:
+    if lengths is not None:
+        lens = torch.as_tensor(lengths, dtype=torch.int32)
+        if lens.shape != (batch,) or int(lens.min()) + len_add < 1:
+            raise ValueError("lengths must be [batch] with lengths[b] + len_add >= 1")
+        lens = lens.to(qkv.device).contiguous()
+        L.check(lib.vdr_op_attention_varlen(qkv.data_ptr(), out.data_ptr(), batch, seq, heads, head_dim, lens.data_ptr(),
+                                            len_add, variant, _s(qkv)))
+    elif head_dim == 64:
         L.check(lib.vdr_op_attention(qkv.data_ptr(), out.data_ptr(), batch, seq, heads, variant, _s(qkv)))
     else:
         L.check(lib.vdr_op_attention_hd(qkv.data_ptr(), out.data_ptr(), batch, seq, heads, head_dim, variant, _s(qkv)))
