@@ -259,6 +259,38 @@ int vdr_op_linear_packed(const void* x, const void* Wp, const float* bias, const
                          const float* gamma, void* y, int64_t M, int N, int K, int epilogue, int variant,
                          void* stream);
 
+/* ---- the LayerNorm fold (pre-LN image models; csrc/gemm_kernels.h) ---------------------------------
+ * The forward never materialises norm1 / norm2: the residual GEMMs leave per-row (sum, sum of squares) partials of the
+ * bf16 rows they store, one slot per 64-column group; these become (mean, rstd); the consuming GEMM runs on the folded
+ * weight and applies y = rstd * (x.W'^T - mean * colsum) + tbias in its epilogue.  These entry points run the forward's
+ * own arithmetic and launch code on caller buffers.  All but vdr_ln_fold_weights take device pointers.
+ *
+ * Host only: the fold of one linear (W [N, K], b [N]) behind LayerNorm (gamma, beta [K]), fp32 host arrays in, host
+ * arrays out: wf [N, K] bf16 bits = bf16(gamma . W), colsum[n] = float(sum_k wf[n][k]), tbias[n] = float(sum_k beta[k]
+ * W[n][k] + b[n]).  swiglu = 1: W / b are mlp.w12 in PyTorch order ([x1 | x2]); the outputs come in the gate-pair order
+ * the SwiGLU epilogue reads (ops.pack_w12).  N % 64 == 0 then. */
+int vdr_ln_fold_weights(const float* W, const float* b, const float* gamma, const float* beta, int N, int K, int swiglu,
+                        uint16_t* wf, float* colsum, float* tbias);
+/* Producer: vdr_op_linear with EPI_BIAS_RESID (y = resid + gamma*(xW^T + b), y may alias resid) that also writes the
+ * partials of y's bf16 rows to part [N/64][part_stride][2] fp32.  resid32 / y32 non-NULL: the fp32 residual stream
+ * (read from resid32 [M, N], the fp32 sum written to y32, y = its bf16 rounding; the partials are of y); resid may
+ * then be NULL.  stats non-NULL: the last workgroup of every 64-row block also finalises (mean, rstd) into stats [M][2],
+ * counting with `counters` (uint32, at least ceil(M / 64), zeroed; left zeroed): ring4 variants 26..29 only.
+ * variant 22..29, N % 64 == 0, K % 64 == 0, part_stride >= M. */
+int vdr_op_linear_ln_stats(const void* x, const void* W, const float* bias, const void* resid, const float* gamma, void* y,
+                           const float* resid32, float* y32, int64_t M, int N, int K, int variant, float* part,
+                           int64_t part_stride, float* stats, uint32_t* counters, float eps, void* stream);
+/* Finaliser: part [D/64][part_stride][2] -> stats [rows][2] (mean, rstd), var = E[x^2] - mean^2 in double. */
+int vdr_op_ln_finalize(const float* part, int64_t part_stride, int64_t rows, int D, float eps, float* stats, void* stream);
+/* Consumer: y = epi(rstd * (x.Wf^T - mean * colsum) + tbias) for x [M, K] bf16 (the residual stream), Wf [N, K] bf16,
+ * colsum / tbias fp32 [N].  Exactly one of stats [M][2] (finalised) and part (the producer's partials, finalised
+ * inside the GEMM: variants 22-24 and 26-28, K <= 1024).  epilogue VDR_EPI_BIAS, _GELU or _SWIGLU (Wf / colsum / tbias
+ * in gate-pair order, y [M, N/2]); variant 22..29 or 31 (the 8-phase kernel, where eligible).  x_rows: rows of x and of
+ * stats that are readable (>= M; 0 = M): variant 31 takes a ragged M only when they cover M rounded up to 256. */
+int vdr_op_linear_ln_fold(const void* x, const void* Wf, const float* colsum, const float* tbias, const float* stats,
+                          const float* part, int64_t part_stride, void* y, int64_t M, int N, int K, int64_t x_rows, float eps,
+                          int epilogue, int variant, void* stream);
+
 /* ---- MX-fp8 operators (BASELINE config 5: "DINOv2 ViT-g/14 fp8 weights (CDNA4 fp8 MFMA)") ----------
  * An MX tensor X[rows, K] is an OCP e4m3 payload q[rows, K] (one byte per element) plus e8m0 scales, one per
  * 32 consecutive K elements, in the device layout  s[K/32][rows_pad]  (rows_pad = rows rounded up to 256; inside

@@ -62,6 +62,64 @@ def test_attention_varlen_refuses_bad_arguments_before_touching_a_device():
         assert b"head dim" in lib.vdr_last_error(None)
 
 
+def test_layernorm_fold_ops_refuse_bad_arguments_before_touching_a_device():
+    from vdr import _lib
+    lib = _lib.load()
+    b = (C.c_char * 64)()
+    # producer: x, W, bias, resid, gamma, y, resid32, y32, M, N, K, variant, part, part_stride, stats, counters, eps, stream
+    ok = [b, b, b, b, None, b, None, None, 100, 768, 768, 26, b, 100, None, None, 1e-6, None]
+
+    def prod(**kw):
+        a = list(ok)
+        for i, v in kw.items():
+            a[int(i[1:])] = v
+        return lib.vdr_op_linear_ln_stats(*a)
+    for i in (0, 1, 5, 12):
+        assert prod(**{f"a{i}": None}) == -1, i  # VDR_ERR_INVALID
+    assert b"null" in lib.vdr_last_error(None)
+    assert prod(a3=None) == -1  # no residual at all
+    assert prod(a6=b) == -1  # resid32 without y32
+    assert prod(a14=b) == -1  # stats without counters
+    assert prod(a14=b, a15=b, a11=22) == -1  # in-GEMM finalisation on a ring3 variant
+    for v in (0, 21, 30, 31, 100):
+        assert prod(a11=v) == -1, v
+    for n in (96, 100, 800):
+        assert prod(a9=n) == -1, n  # N % 64
+    assert prod(a10=96) == -1  # K % 64
+    assert prod(a13=99) == -1  # part_stride < M
+    # finaliser: part, part_stride, rows, D, eps, stats, stream
+    assert lib.vdr_op_ln_finalize(None, 100, 100, 768, 1e-6, b, None) == -1
+    assert lib.vdr_op_ln_finalize(b, 100, 100, 768, 1e-6, None, None) == -1
+    for D in (0, 32, 100, 770):
+        assert lib.vdr_op_ln_finalize(b, 100, 100, D, 1e-6, b, None) == -1, D
+    assert lib.vdr_op_ln_finalize(b, 99, 100, 768, 1e-6, b, None) == -1
+    # consumer: x, Wf, colsum, tbias, stats, part, part_stride, y, M, N, K, x_rows, eps, epilogue, variant, stream
+    okc = [b, b, b, b, b, None, 0, b, 100, 768, 768, 0, 1e-6, 0, 26, None]
+
+    def cons(**kw):
+        a = list(okc)
+        for i, v in kw.items():
+            a[int(i[1:])] = v
+        return lib.vdr_op_linear_ln_fold(*a)
+    for i in (0, 1, 2, 3, 7):
+        assert cons(**{f"a{i}": None}) == -1, i
+    assert cons(a4=None) == -1  # neither statistics nor partials
+    assert cons(a5=b, a6=100) == -1  # both
+    assert cons(a13=2) == -1 and cons(a13=4) == -1  # the residual epilogue / unknown
+    for v in (0, 21, 30, 32):
+        assert cons(a14=v) == -1, v
+    assert cons(a10=96) == -1 and cons(a9=100) == -1  # K % 64, N % 64
+    assert cons(a11=50) == -1  # x_rows < M
+    # in-GEMM statistics (partials): never on variants 25 / 29 / 31, nor above 16 groups, nor with a short stride
+    for v in (25, 29, 31):
+        assert cons(a4=None, a5=b, a6=100, a14=v) == -1, v
+    assert cons(a4=None, a5=b, a6=100, a10=1088) == -1
+    assert cons(a4=None, a5=b, a6=99) == -1
+    # host fold: null pointers and a SwiGLU width that is no whole number of gate pairs
+    assert lib.vdr_ln_fold_weights(None, b, b, b, 64, 64, 0, b, b, b) == -1
+    assert lib.vdr_ln_fold_weights(b, b, b, b, 96, 64, 1, b, b, b) == -1
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="only meaningful on a box without a GPU")
 def test_no_gpu_means_loud_failure_not_fallback():
     import vdr
@@ -78,6 +136,8 @@ def test_no_gpu_means_loud_failure_not_fallback():
     assert lib.vdr_op_attention(buf, buf, 1, 1, 1, 0, None) == -2
     assert lib.vdr_op_attention_varlen(buf, buf, 1, 1, 1, 64, buf, 0, 0, None) == -2
     assert lib.vdr_op_layernorm(buf, 0, buf, 0, buf, buf, 1, 4, 1e-5, None) == -2
+    assert lib.vdr_op_ln_finalize(buf, 64, 64, 64, 1e-6, buf, None) == -2
+    assert lib.vdr_op_linear_ln_fold(buf, buf, buf, buf, buf, None, 0, buf, 64, 64, 64, 0, 1e-6, 0, 26, None) == -2
 
 
 def test_product_package_never_imports_the_oracle():

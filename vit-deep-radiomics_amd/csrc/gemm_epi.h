@@ -43,7 +43,7 @@ struct GemmK {
   const float* ln_cpart = nullptr;
   int ln_groups = 0;
   int64_t ln_cstride = 0;
-  float ln_inv_d = 0.0f, ln_eps = 0.0f;
+  float ln_eps = 0.0f;  // (D = 64 * ln_groups)
   int stats_off = 0;
   int ln_fold = 0;  // the consumer-side fold is on (statistics from ln_stats or from ln_cpart)
   float* ln_part;
@@ -53,7 +53,7 @@ struct GemmK {
   float* fin_stats = nullptr;
   uint32_t* fin_cnt = nullptr;
   int fin_groups = 0;
-  float fin_inv_d = 0.0f, fin_eps = 0.0f;
+  float fin_eps = 0.0f;  // (D = 64 * fin_groups)
   int a_rpg;
   int64_t a_gs, a_is;
   int out_f32;

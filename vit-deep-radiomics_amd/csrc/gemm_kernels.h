@@ -175,13 +175,7 @@ VDR_DEV void gemm_ring3_body(const GemmK& p, const int64_t m0, const int n0, cha
         s1 += (double)pv[g].x;
         s2 += (double)pv[g].y;
       }
-    const double mean = s1 * (double)p.ln_inv_d;
-    double var = s2 * (double)p.ln_inv_d - mean * mean;
-    var = var > 0.0 ? var : 0.0;
-    float2 o;
-    o.x = (float)mean;
-    o.y = (float)(1.0 / sqrt(var + (double)p.ln_eps));
-    reinterpret_cast<float2*>(smem + p.stats_off)[tid] = o;
+    reinterpret_cast<float2*>(smem + p.stats_off)[tid] = ln_mean_rstd(s1, s2, p.ln_groups, p.ln_eps);
   }
   retire(0, issued);
   __builtin_amdgcn_s_barrier();
@@ -537,11 +531,7 @@ VDR_DEV void gemm_ring4_body(const GemmK& p, const int64_t m0, const int n0, cha
         s1 += (double)pv[g].x;
         s2 += (double)pv[g].y;
       }
-    const double mean = s1 * (double)p.ln_inv_d;
-    double var = s2 * (double)p.ln_inv_d - mean * mean;
-    var = var > 0.0 ? var : 0.0;
-    my_stats.x = (float)mean;
-    my_stats.y = (float)(1.0 / sqrt(var + (double)p.ln_eps));
+    my_stats = ln_mean_rstd(s1, s2, p.ln_groups, p.ln_eps);
   }
   VDR_GSTAMP(1);  // addresses computed, ring fill issued
   if (nsteps > 2) wait_vmcnt<NB + NA4 + NB>();
@@ -696,13 +686,7 @@ VDR_DEV void finalize_rows_if_last(const GemmK& q, int tm, char* smem) {
             s2 += (double)__uint_as_float((uint32_t)(v[j] >> 32));
           }
       }
-      const double mean = s1 * (double)q.fin_inv_d;
-      double var = s2 * (double)q.fin_inv_d - mean * mean;
-      var = var > 0.0 ? var : 0.0;
-      float2 o;
-      o.x = (float)mean;
-      o.y = (float)(1.0 / sqrt(var + (double)q.fin_eps));
-      *reinterpret_cast<float2*>(q.fin_stats + row * 2) = o;
+      *reinterpret_cast<float2*>(q.fin_stats + row * 2) = ln_mean_rstd(s1, s2, q.fin_groups, q.fin_eps);
     }
     if (threadIdx.x == 0) __hip_atomic_store(q.fin_cnt + tm, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
@@ -909,7 +893,6 @@ static hipError_t launch_cfg(const GemmArgs& a, int epi, hipStream_t s) {
     k.fin_stats = a.fin_stats;
     k.fin_cnt = a.fin_cnt;
     k.fin_groups = a.N / 64;
-    k.fin_inv_d = a.fin_inv_d;
     k.fin_eps = a.fin_eps;
   }
   if (a.ldc >= ((int64_t)1 << 24)) return hipErrorInvalidValue;  // (epilogue_bf16 addresses a wave tile with 32-bit byte offsets)
@@ -920,7 +903,6 @@ static hipError_t launch_cfg(const GemmArgs& a, int epi, hipStream_t s) {
     k.ln_cpart = a.ln_cpart;
     k.ln_groups = a.ln_groups;
     k.ln_cstride = a.ln_cstride;
-    k.ln_inv_d = a.ln_inv_d;
     k.ln_eps = a.ln_eps;
   }
   k.abl = g_gemm_ablation;

@@ -419,7 +419,7 @@ hipError_t launch_gather_rows(const void* x, void* y, int out_bf16, int64_t rows
 // (sum, sumsq) partials per 64-column group -> (mean, rstd) per row.  The sums come from the producing
 // GEMM's epilogue; variance = E[x^2] - mean^2 evaluated in double from the fp32 partials.
 __global__ __launch_bounds__(64) void ln_finalize_kernel(const float* __restrict__ part, int groups, int64_t stride,
-                                                          float* __restrict__ stats, int64_t rows, float inv_d, float eps) {
+                                                          float* __restrict__ stats, int64_t rows, float eps) {
   const int64_t r = (int64_t)blockIdx.x * 64 + threadIdx.x;
   if (r >= rows) return;
   double s1 = 0.0, s2 = 0.0;
@@ -437,20 +437,14 @@ __global__ __launch_bounds__(64) void ln_finalize_kernel(const float* __restrict
         s2 += (double)v[j].y;
       }
   }
-  const double mean = s1 * (double)inv_d;
-  double var = s2 * (double)inv_d - mean * mean;
-  var = var > 0.0 ? var : 0.0;
-  float2 o;
-  o.x = (float)mean;
-  o.y = (float)(1.0 / sqrt(var + (double)eps));
-  *reinterpret_cast<float2*>(stats + r * 2) = o;
+  *reinterpret_cast<float2*>(stats + r * 2) = ln_mean_rstd(s1, s2, groups, eps);
 }
 
 hipError_t launch_ln_finalize(const float* part, int groups, int64_t stride, float* stats, int64_t rows, int D,
                               float eps, hipStream_t s) {
-  if (rows <= 0 || groups <= 0) return hipErrorInvalidValue;
+  if (rows <= 0 || groups <= 0 || D != 64 * groups) return hipErrorInvalidValue;
   hipLaunchKernelGGL(ln_finalize_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, s, part, groups, stride,
-                     stats, rows, 1.0f / (float)D, eps);
+                     stats, rows, eps);
   return hipGetLastError();
 }
 

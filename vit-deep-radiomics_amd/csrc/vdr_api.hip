@@ -242,14 +242,20 @@ bool ln_fusion_wanted(const vdr_model* m) {
   return c.patch && c.pre_ln && !c.input_ln && !c.fp8 && (c.dim % 64) == 0;
 }
 
-// W' = W.diag(gamma) (bf16), colsum, tbias for one linear layer; `perm` (optional) maps packed row -> source row
-int fold_ln(vdr_model* m, const std::vector<float>& W, const std::vector<float>& b, const std::vector<float>& gam,
-            const std::vector<float>& bet, int64_t N, int64_t K, const std::vector<int64_t>* perm, void** wf_dev,
-            float** colsum_dev, float** tbias_dev) {
-  std::vector<uint16_t> wf((size_t)N * K);
-  std::vector<float> cs(N), tb(N);
+// SwiGLU gate pairs: packed row pr of mlp.w12 is source row swiglu_source_row(pr, F) (blocks of 32 x1 rows, then the 32 matching x2 rows:
+// the layout of ops.pack_w12 / vdr_set_weight)
+int64_t swiglu_source_row(int64_t pr, int64_t F) {
+  const int64_t blk = pr / 64, t = pr % 64;
+  return t < 32 ? blk * 32 + t : F + blk * 32 + (t - 32);
+}
+
+// The host arithmetic of the LayerNorm fold for one linear layer: W' = bf16(gamma . W) [N][K], colsum[n] = float(sum_k
+// W'[n][k]) (of the ROUNDED weight: the GEMM multiplies by it), tbias[n] = float(sum_k beta[k] W[n][k] + b[n]); swiglu: rows
+// in the gate-pair order (swiglu_source_row).  Shared by the forward (fold_ln) and vdr_ln_fold_weights.
+void fold_ln_host(const float* W, const float* b, const float* gam, const float* bet, int64_t N, int64_t K, bool swiglu,
+                  uint16_t* wf, float* cs, float* tb) {
   for (int64_t pr = 0; pr < N; ++pr) {
-    const int64_t n = perm ? (*perm)[pr] : pr;
+    const int64_t n = swiglu ? swiglu_source_row(pr, N / 2) : pr;
     const float* w = &W[(size_t)n * K];
     double s = 0.0, t = 0.0;
     for (int64_t k = 0; k < K; ++k) {
@@ -261,6 +267,15 @@ int fold_ln(vdr_model* m, const std::vector<float>& W, const std::vector<float>&
     cs[pr] = (float)s;
     tb[pr] = (float)(t + (double)b[n]);
   }
+}
+
+// fold_ln_host + upload
+int fold_ln(vdr_model* m, const std::vector<float>& W, const std::vector<float>& b, const std::vector<float>& gam,
+            const std::vector<float>& bet, int64_t N, int64_t K, bool swiglu, void** wf_dev, float** colsum_dev,
+            float** tbias_dev) {
+  std::vector<uint16_t> wf((size_t)N * K);
+  std::vector<float> cs(N), tb(N);
+  fold_ln_host(W.data(), b.data(), gam.data(), bet.data(), N, K, swiglu, wf.data(), cs.data(), tb.data());
   if (!*wf_dev) VDR_TRY(hipMalloc(wf_dev, wf.size() * 2 + 256), "hipMalloc(folded weight)");
   if (!*colsum_dev) VDR_TRY(hipMalloc((void**)colsum_dev, (size_t)N * 4 + 256), "hipMalloc(colsum)");
   if (!*tbias_dev) VDR_TRY(hipMalloc((void**)tbias_dev, (size_t)N * 4 + 256), "hipMalloc(tbias)");
@@ -328,20 +343,14 @@ int resolve(vdr_model* m) {
       const std::string p = "blocks." + std::to_string(i) + ".";
       LayerW& L = m->layers[i];
       int rc = fold_ln(m, *host_of(m, p + "attn.qkv.weight"), *host_of(m, p + "attn.qkv.bias"), *host_of(m, p + "norm1.weight"),
-                       *host_of(m, p + "norm1.bias"), 3 * D, D, nullptr, &L.wqkv_f, &L.sqkv, &L.tqkv);
+                       *host_of(m, p + "norm1.bias"), 3 * D, D, false, &L.wqkv_f, &L.sqkv, &L.tqkv);
       if (rc) return rc;
-      if (c.act == VDR_ACT_SWIGLU) {
-        std::vector<int64_t> perm(2 * F);
-        for (int64_t pr = 0; pr < 2 * F; ++pr) {
-          const int64_t blk = pr / 64, t = pr % 64;
-          perm[pr] = t < 32 ? blk * 32 + t : F + blk * 32 + (t - 32);
-        }
+      if (c.act == VDR_ACT_SWIGLU)
         rc = fold_ln(m, *host_of(m, p + "mlp.w12.weight"), *host_of(m, p + "mlp.w12.bias"), *host_of(m, p + "norm2.weight"),
-                     *host_of(m, p + "norm2.bias"), 2 * F, D, &perm, &L.w1_f, &L.s1, &L.t1);
-      } else {
+                     *host_of(m, p + "norm2.bias"), 2 * F, D, true, &L.w1_f, &L.s1, &L.t1);
+      else
         rc = fold_ln(m, *host_of(m, p + "mlp.fc1.weight"), *host_of(m, p + "mlp.fc1.bias"), *host_of(m, p + "norm2.weight"),
-                     *host_of(m, p + "norm2.bias"), F, D, nullptr, &L.w1_f, &L.s1, &L.t1);
-      }
+                     *host_of(m, p + "norm2.bias"), F, D, false, &L.w1_f, &L.s1, &L.t1);
       if (rc) return rc;
     }
   }
@@ -642,9 +651,28 @@ struct LnFold {
   const float* cpart = nullptr;   // consumer: the producers' partials, finalised inside the GEMM (instead of stats)
   int groups = 0;
   int64_t cstride = 0;
-  float inv_d = 0.0f, eps = 0.0f;
+  float eps = 0.0f;
   float* fin_stats = nullptr;     // producer: finalise the statistics of the rows it completes here (see finalize_rows_if_last)
+  uint32_t* fin_cnt = nullptr;    //   with these zeroed counters, one per 64 rows (left zeroed)
 };
+
+// LnFold -> GemmArgs: the one place the fold's fields are filled, for the forward's gemm() and the vdr_op_linear_ln_*
+// entry points alike
+void set_ln_fold(GemmArgs& g, const LnFold& ln) {
+  g.ln_stats = ln.stats;
+  g.colsum = ln.colsum;
+  g.ln_part = ln.part;
+  g.part_stride = ln.part_stride;
+  g.ln_cpart = ln.cpart;
+  g.ln_groups = ln.groups;
+  g.ln_cstride = ln.cstride;
+  g.ln_eps = ln.eps;
+  if (ln.fin_stats && ln.fin_cnt) {
+    g.fin_stats = ln.fin_stats;
+    g.fin_cnt = ln.fin_cnt;
+    g.fin_eps = ln.eps;
+  }
+}
 
 // which GEMM classes take tile variant 31 when the launch is eligible (gemm_8p_eligible): measured per class in the
 // forward; tuning builds: VDR_GEMM_8P = bit mask (1 qkv, 2 fc1), -1 = the default
@@ -680,7 +708,6 @@ int ln_consumer(vdr_model* m, hipStream_t s, int cls, int64_t M, int N, int D, c
     cons->cpart = w.part;
     cons->groups = groups;
     cons->cstride = w.Mp;
-    cons->inv_d = 1.0f / (float)D;
     cons->eps = m->cfg.ln_eps;
     m->stats_fresh = false;
     return VDR_OK;
@@ -701,15 +728,6 @@ int gemm(vdr_model* m, hipStream_t s, int cls, const void* A, const void* W, con
          const float* resid32 = nullptr, float* C32 = nullptr,  // resid_fp32: the fp32 residual stream in / out (same strides)
          int64_t a_rows = 0) {  // rows of A / of the fold's row statistics that are readable (workspace buffers: Mp); 0 = unknown
   GemmArgs g{};
-  g.ln_stats = ln.stats;
-  g.colsum = ln.colsum;
-  g.ln_part = ln.part;
-  g.part_stride = ln.part_stride;
-  g.ln_cpart = ln.cpart;
-  g.ln_groups = ln.groups;
-  g.ln_cstride = ln.cstride;
-  g.ln_inv_d = ln.inv_d;
-  g.ln_eps = ln.eps;
   g.A = A;
   g.W = W;
   g.bias = bias;
@@ -726,6 +744,9 @@ int gemm(vdr_model* m, hipStream_t s, int cls, const void* A, const void* W, con
   g.omap = identity_map();
   g.resid32 = resid32;
   g.C32 = C32;
+  LnFold lnf = ln;
+  lnf.fin_cnt = nullptr;
+  set_ln_fold(g, lnf);
   const double outw = epi == EPI_SWIGLU ? N / 2 : N;
   Scope sc(m, s, cls, 2.0 * M * N * K,
            2.0 * ((double)M * K + (double)N * K + (double)M * outw * (resid32 ? 5 : resid ? 2 : 1)));  // (fp32 in + fp32 out + bf16 out)
@@ -744,10 +765,9 @@ int gemm(vdr_model* m, hipStream_t s, int cls, const void* A, const void* W, con
   bool fin = false;
   if (ln.fin_stats && ln.part && m->fin_cnt && m->cfg.ln_fin_fused && variant >= 26 && variant <= 29 && epi == EPI_BIAS_RESID &&
       (g.M + 63) / 64 <= FIN_ROWS) {
-    g.fin_stats = ln.fin_stats;
-    g.fin_cnt = m->fin_cnt + (size_t)m->cur_aux * FIN_ROWS;
-    g.fin_inv_d = 1.0f / (float)N;
-    g.fin_eps = m->cfg.ln_eps;
+    lnf.fin_cnt = m->fin_cnt + (size_t)m->cur_aux * FIN_ROWS;
+    lnf.eps = m->cfg.ln_eps;
+    set_ln_fold(g, lnf);
     fin = true;
   }
   VDR_TRY(launch_gemm_w(m, g, epi, variant, s), "gemm");
@@ -1751,6 +1771,121 @@ int vdr_op_pack_linear_weight(const void* W, int N, int K, void* packed, void* s
 int vdr_op_linear_packed(const void* x, const void* Wp, const float* bias, const void* resid, const float* gamma, void* y,
                          int64_t M, int N, int K, int epilogue, int variant, void* stream) {
   return op_linear_impl(x, Wp, 1, bias, resid, gamma, y, M, N, K, epilogue, variant, stream);
+}
+
+// ---- the LayerNorm fold at op level: the forward's arithmetic (fold_ln_host, set_ln_fold, launch_gemm, launch_ln_finalize)
+// on caller buffers
+int vdr_ln_fold_weights(const float* W, const float* b, const float* gamma, const float* beta, int N, int K, int swiglu,
+                        uint16_t* wf, float* colsum, float* tbias) {
+  if (!W || !b || !gamma || !beta || !wf || !colsum || !tbias) return fail(nullptr, VDR_ERR_INVALID, "null argument");
+  if (N <= 0 || K <= 0 || (swiglu && (N % 64))) return fail(nullptr, VDR_ERR_INVALID, "N > 0, K > 0 (swiglu: N % 64 == 0) required");
+  fold_ln_host(W, b, gamma, beta, N, K, swiglu != 0, wf, colsum, tbias);
+  return VDR_OK;
+}
+
+static bool ln_variant_ok(int variant, bool allow_31) {
+  return (variant >= 22 && variant <= 29) || (allow_31 && variant == 31);
+}
+
+int vdr_op_linear_ln_stats(const void* x, const void* W, const float* bias, const void* resid, const float* gamma, void* y,
+                           const float* resid32, float* y32, int64_t M, int N, int K, int variant, float* part,
+                           int64_t part_stride, float* stats, uint32_t* counters, float eps, void* stream) {
+  if (!x || !W || !y || !part || (!resid && !resid32)) return fail(nullptr, VDR_ERR_INVALID, "null argument");
+  if ((resid32 != nullptr) != (y32 != nullptr)) return fail(nullptr, VDR_ERR_INVALID, "resid32 and y32 go together");
+  if ((stats != nullptr) != (counters != nullptr)) return fail(nullptr, VDR_ERR_INVALID, "stats and counters go together");
+  if (!ln_variant_ok(variant, false)) return fail(nullptr, VDR_ERR_INVALID, "variant: 22..29");
+  if (stats && variant < 26) return fail(nullptr, VDR_ERR_INVALID, "in-GEMM finalisation: ring4 variants 26..29");
+  if (M <= 0 || N <= 0 || K <= 0 || (N % 64) || (K % 64) || part_stride < M)
+    return fail(nullptr, VDR_ERR_INVALID, "M > 0, N % 64 == 0, K % 64 == 0, part_stride >= M required");
+  int rc = check_device(nullptr);
+  if (rc) return rc;
+  GemmArgs g{};
+  g.A = x;
+  g.W = W;
+  g.bias = bias;
+  g.resid = resid ? resid : y;
+  g.gamma = gamma;
+  g.C = y;
+  g.M = M;
+  g.N = N;
+  g.K = K;
+  g.lda = K;
+  g.ldw = K;
+  g.ldc = N;
+  g.ldr = N;
+  g.omap = identity_map();
+  g.resid32 = resid32;
+  g.C32 = y32;
+  LnFold ln;
+  ln.part = part;
+  ln.part_stride = part_stride;
+  ln.fin_stats = stats;
+  ln.fin_cnt = counters;
+  ln.eps = eps;
+  set_ln_fold(g, ln);
+  const hipError_t e = launch_gemm(g, EPI_BIAS_RESID, variant, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    (void)hipGetLastError();
+    return fail(nullptr, VDR_ERR_INVALID, "gemm: unsupported tile variant or shape for the LayerNorm producer");
+  }
+  OP_TRY(e, "gemm");
+  return VDR_OK;
+}
+
+int vdr_op_ln_finalize(const float* part, int64_t part_stride, int64_t rows, int D, float eps, float* stats, void* stream) {
+  if (!part || !stats) return fail(nullptr, VDR_ERR_INVALID, "null argument");
+  if (rows <= 0 || D <= 0 || (D % 64) || part_stride < rows)
+    return fail(nullptr, VDR_ERR_INVALID, "rows > 0, D % 64 == 0, part_stride >= rows required");
+  int rc = check_device(nullptr);
+  if (rc) return rc;
+  OP_TRY(launch_ln_finalize(part, D / 64, part_stride, stats, rows, D, eps, (hipStream_t)stream), "ln_finalize");
+  return VDR_OK;
+}
+
+int vdr_op_linear_ln_fold(const void* x, const void* Wf, const float* colsum, const float* tbias, const float* stats,
+                          const float* part, int64_t part_stride, void* y, int64_t M, int N, int K, int64_t x_rows, float eps,
+                          int epilogue, int variant, void* stream) {
+  if (!x || !Wf || !colsum || !tbias || !y) return fail(nullptr, VDR_ERR_INVALID, "null argument");
+  if ((stats != nullptr) == (part != nullptr)) return fail(nullptr, VDR_ERR_INVALID, "exactly one of stats and part");
+  if (epilogue != VDR_EPI_BIAS && epilogue != VDR_EPI_BIAS_GELU && epilogue != VDR_EPI_SWIGLU)
+    return fail(nullptr, VDR_ERR_INVALID, "epilogue: bias, GELU or SwiGLU");
+  if (!ln_variant_ok(variant, true)) return fail(nullptr, VDR_ERR_INVALID, "variant: 22..29 or 31");
+  if (M <= 0 || N <= 0 || K <= 0 || (N % 64) || (K % 64) || (x_rows && x_rows < M))
+    return fail(nullptr, VDR_ERR_INVALID, "M > 0, N % 64 == 0, K % 64 == 0, x_rows 0 or >= M required");
+  // (the forward finalises inside the GEMM on ring3 / ring4 variants 22-24, 26-28 only, up to 16 groups)
+  if (part && (variant == 25 || variant >= 29 || K / 64 > 16 || part_stride < M))
+    return fail(nullptr, VDR_ERR_INVALID, "in-GEMM statistics: variants 22-24, 26-28, K <= 1024, part_stride >= M");
+  int rc = check_device(nullptr);
+  if (rc) return rc;
+  GemmArgs g{};
+  g.A = x;
+  g.W = Wf;
+  g.bias = tbias;
+  g.C = y;
+  g.M = M;
+  g.N = N;
+  g.K = K;
+  g.lda = K;
+  g.ldw = K;
+  g.ldc = epilogue == VDR_EPI_SWIGLU ? N / 2 : N;
+  g.ldr = g.ldc;
+  g.omap = identity_map();
+  g.a_rows = x_rows;
+  LnFold ln;
+  ln.stats = stats;
+  ln.colsum = colsum;
+  ln.cpart = part;
+  ln.groups = K / 64;
+  ln.cstride = part_stride;
+  ln.eps = eps;
+  set_ln_fold(g, ln);
+  const hipError_t e = launch_gemm(g, epilogue, variant, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    (void)hipGetLastError();
+    return fail(nullptr, VDR_ERR_INVALID, "gemm: unsupported tile variant or shape for the LayerNorm consumer");
+  }
+  OP_TRY(e, "gemm");
+  return VDR_OK;
 }
 
 size_t vdr_prepare_scratch_bytes(int batch, int h, int w, int channels, int out_side) {

@@ -45,6 +45,22 @@ VDR_DEV float wave_sum(float v) {
   return v;
 }
 
+// LayerNorm statistics of the fold: (sum, sum of squares) over D = 64 * groups columns -> (mean, rstd), one pass in
+// double.  The fp32 partials of bf16 rows are all but exact, so the only error worth naming is that of 1/D: it is divided
+// out exactly here (a float 1/D is off by up to 3e-8 relative, and E[x^2] - mean^2 multiplies that by (mean / sigma)^2: a
+// systematic 5e-4 rstd error at |mean| / sigma = 192, D = 768).  Every finaliser (ln_finalize_kernel, the in-GEMM ring3 /
+// ring4 prologues, finalize_rows_if_last) calls this, so their results are bitwise equal.
+VDR_DEV float2 ln_mean_rstd(double s1, double s2, int groups, float eps) {
+  const double d = 64.0 * (double)groups;
+  const double mean = s1 / d;
+  double var = fma(-mean, mean, s2 / d);
+  var = var > 0.0 ? var : 0.0;
+  float2 o;
+  o.x = (float)mean;
+  o.y = (float)(1.0 / sqrt(var + (double)eps));
+  return o;
+}
+
 VDR_DEV float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 VDR_DEV float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 

@@ -52,6 +52,63 @@ def linear(x, W, bias=None, resid=None, gamma=None, epilogue=L.EPI_BIAS, variant
     return out
 
 
+def ln_fold_weights(W: torch.Tensor, b: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, swiglu: bool = False):
+    """The host fold of one linear behind a LayerNorm (vdr_ln_fold_weights): fp32 CPU W [N, K], b [N], gamma / beta [K]
+    -> (Wf bf16 [N, K], colsum fp32 [N], tbias fp32 [N]), in gate-pair order when swiglu (W / b: mlp.w12 as PyTorch holds it)."""
+    lib = L.load()
+    W, b, gamma, beta = (t.detach().float().contiguous().cpu() for t in (W, b, gamma, beta))
+    N, K = W.shape
+    wf = torch.empty((N, K), dtype=torch.int16)
+    cs = torch.empty(N, dtype=torch.float32)
+    tb = torch.empty(N, dtype=torch.float32)
+    L.check(lib.vdr_ln_fold_weights(W.data_ptr(), b.data_ptr(), gamma.data_ptr(), beta.data_ptr(), N, K, int(swiglu),
+                                    wf.data_ptr(), cs.data_ptr(), tb.data_ptr()))
+    return wf.view(torch.bfloat16), cs, tb
+
+
+def linear_ln_stats(x, W, bias, resid, part, variant, gamma=None, out=None, resid32=None, out32=None, stats=None,
+                    counters=None, eps=1e-6):
+    """The residual linear of the LayerNorm fold (vdr_op_linear_ln_stats): out = resid + gamma * (x W^T + bias) (fp32 stream:
+    resid32 / out32), plus the (sum, sumsq) partials of out's bf16 rows in part [N/64, part_stride, 2]; with stats /
+    counters also (mean, rstd) [M, 2] finalised by the GEMM's last workgroup per row block."""
+    lib = L.load()
+    M, K = x.shape
+    N = W.shape[0]
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    L.check(lib.vdr_op_linear_ln_stats(x.data_ptr(), W.data_ptr(), _p(bias), _p(resid), _p(gamma), out.data_ptr(),
+                                       _p(resid32), _p(out32), M, N, K, variant, part.data_ptr(), part.shape[1],
+                                       _p(stats), _p(counters), float(eps), _s(x)))
+    return out
+
+
+def ln_finalize(part: torch.Tensor, rows: int, eps: float, stats=None):
+    """(sum, sumsq) partials [D/64, stride, 2] -> (mean, rstd) [rows, 2] (vdr_op_ln_finalize)"""
+    lib = L.load()
+    if stats is None:
+        stats = torch.empty((rows, 2), dtype=torch.float32, device=part.device)
+    L.check(lib.vdr_op_ln_finalize(part.data_ptr(), part.shape[1], rows, part.shape[0] * 64, float(eps), stats.data_ptr(),
+                                   _s(part)))
+    return stats
+
+
+def linear_ln_fold(x, Wf, colsum, tbias, variant, epilogue=L.EPI_BIAS, stats=None, part=None, M=None, eps=1e-6, out=None):
+    """The consumer of the LayerNorm fold (vdr_op_linear_ln_fold): epi(rstd (x Wf^T - mean colsum) + tbias) with (mean,
+    rstd) from stats [>= M, 2] or finalised in the GEMM from part.  M defaults to x's rows; x (and stats) may hold more
+    rows than M: they are readable padding (the 8-phase variant reads a ragged last tile whole)."""
+    lib = L.load()
+    rows, K = x.shape
+    M = rows if M is None else M
+    N = Wf.shape[0]
+    if out is None:
+        out = torch.empty((M, N // 2 if epilogue == L.EPI_SWIGLU else N), dtype=torch.bfloat16, device=x.device)
+    x_rows = rows if stats is None else min(rows, stats.shape[0])
+    L.check(lib.vdr_op_linear_ln_fold(x.data_ptr(), Wf.data_ptr(), colsum.data_ptr(), tbias.data_ptr(), _p(stats), _p(part),
+                                      0 if part is None else part.shape[1], out.data_ptr(), M, N, K, x_rows, float(eps),
+                                      epilogue, variant, _s(x)))
+    return out
+
+
 class MxTensor:
     """e4m3 payload [rows, K] (uint8) + e8m0 block scales in the device layout of csrc/mx.hip."""
 
