@@ -71,8 +71,10 @@ typedef enum {
   VDR_OUT_DENSE = 1,       /* [B, n, D]   final-LN(x)[:,1:,:]    (tfds_dense_descriptor.py:130-133) */
   VDR_OUT_PATCH_EMBED = 2, /* [B, n, D]   conv patchify only     (tfds_dense_descriptor.py:128)     */
   VDR_OUT_TOKENS = 3,      /* [B, N, D]   every token after the last block + final LN (if any)      */
-  VDR_OUT_ENCODER = 4      /* [B, g, g, C] SAM neck output, channel-LAST (tfds_dense_descriptor.py:123-126   */
+  VDR_OUT_ENCODER = 4,     /* [B, g, g, C] SAM neck output, channel-LAST (tfds_dense_descriptor.py:123-126   */
                            /*             transposes the reference's [B, C, g, g] to (h, w, C) anyway)     */
+  VDR_OUT_POOLED = 5       /* [B, D]      mean over the patch rows (rows ncls..N-1) of the normalised (or raw)  */
+                           /*             stream: vdr_forward_layers only (vdr_forward refuses it)             */
 } vdr_out_mode;
 
 /* Geometry of one frozen ViT.  Mirrors the constructor arguments the reference
@@ -201,6 +203,32 @@ int vdr_workspace_bytes(vdr_handle h, int batch, int seq, size_t* out);
  *   out    : device, shape by out_mode, dtype out_dtype, C-contiguous, row b = image b */
 int vdr_forward(vdr_handle h, const void* images, int in_dtype, int batch, void* out, int out_mode,
                 int out_dtype, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Features from inside the encoder, several per forward: DINOv2 get_intermediate_layers(x, n, reshape,
+ * return_class_token, norm) and the linear-probe descriptor of create_linear_input (CLS rows of the last blocks and
+ * the mean of the last block's normalised patch tokens, concatenated: [B, 5*D] for 4 blocks).  One output: */
+typedef struct {
+  int32_t layer;     /* block index 0 .. L-1: the residual stream after that block                                */
+  int32_t out_mode;  /* VDR_OUT_CLS [B, D] | VDR_OUT_DENSE [B, n, D] | VDR_OUT_TOKENS [B, N, D] | VDR_OUT_POOLED [B, D] */
+  int32_t out_dtype; /* VDR_F32 | VDR_BF16                                                                        */
+  int32_t norm;      /* 1: through the model's final norm (DINOv2 norm=True); 0: the raw stream the next block reads */
+  int64_t ld;        /* CLS / POOLED: elements between consecutive images' rows (0 = D, else >= D); DENSE / TOKENS: 0 */
+  void* out;         /* device buffer; image b's row(s) start at out + b*ld (CLS/POOLED) or b*rows*D (DENSE/TOKENS)   */
+} vdr_layer_out;
+
+/* One forward of a pre-LN image model (plain ViT, DINOv2: LayerScale, SwiGLU, fp8, fp8_cls_bf16, resid_fp32, no_ln_fold,
+ * micro_batch, streams) that writes all n_outs outputs, in any order; several may name the same layer.  Blocks past the
+ * largest requested layer do not run.  The output of block i is bitwise vdr_forward's on the same weights truncated to
+ * i + 1 blocks (norm = 1; CLS / DENSE / TOKENS): it is the same final-LayerNorm launch on the same stream, written after
+ * the block's last residual GEMM.  norm = 0 copies the raw stream (its fp32 copy with resid_fp32) with one rounding to
+ * out_dtype.  POOLED is the fp32 mean over the n patch rows, in fixed-size chunks and a fixed order (no atomics, the
+ * same bits in any batch), rounded once.  When every output of the last block that runs is CLS, that block runs its
+ * CLS rows only (vdr_config.full_last_block), as vdr_forward does.  Workspace: vdr_workspace_bytes (unchanged).
+ * Refused before the device is touched: SAM (window > 0), token and post-LN models, layers == 0
+ * (VDR_ERR_UNSUPPORTED); null pointers, n_outs <= 0, a layer out of range, an unknown mode, dtype or norm flag, CLS on a
+ * model without a CLS token, ld in (0, D) or negative, a non-zero ld for DENSE / TOKENS (VDR_ERR_INVALID). */
+int vdr_forward_layers(vdr_handle h, const void* images, int in_dtype, int batch, const vdr_layer_out* outs, int n_outs,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* Replaces: TransformerNoduleClassifier.forward up to x[:,0,:]
  * (models_archs.py:141-147): tokens [batch, seq, D] fp32/bf16 on device ->

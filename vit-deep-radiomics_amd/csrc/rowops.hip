@@ -29,6 +29,8 @@ struct LnK {
   int ooff;
   int cls_period;
   int win_ws, win_g;
+  int64_t ldy;  // output row stride in elements
+  int vec_out;  // 1: every output row start is 16-byte (fp32) / 8-byte (bf16) aligned -> vector stores
 };
 
 VDR_DEV int64_t map_row(int64_t r, int rpg, int64_t gs, int off) {
@@ -36,6 +38,57 @@ VDR_DEV int64_t map_row(int64_t r, int rpg, int64_t gs, int off) {
   const int64_t g = r / rpg;
   return g * gs + off + (r - g * rpg);
 }
+
+// One row of D values held by one wave: lane l owns columns k*256 + 4l .. 4l+3 of pass k (zeros past D).  The
+// LayerNorm kernel and the pooled reduction both normalise through these helpers, so their per-row arithmetic is one.
+template <bool IN_BF16, int NP>
+VDR_DEV void row_load(const void* x, int64_t row, int D, int lane, float (&v)[NP][4]) {
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
+    const int c = k * 256 + lane * 4;
+    if (c < D) {
+      if (IN_BF16) {
+        const bf16x4 t = *reinterpret_cast<const bf16x4*>((const bf16_t*)x + row * D + c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[k][e] = (float)t[e];
+      } else {
+        const f32x4 t = *reinterpret_cast<const f32x4*>((const float*)x + row * D + c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[k][e] = t[e];
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[k][e] = 0.0f;
+    }
+  }
+}
+
+// two-pass mean and biased variance of the row in fp32 (wave-wide shuffle sums), rstd = rsqrtf(var + eps)
+template <int NP>
+VDR_DEV void row_mean_rstd(const float (&v)[NP][4], int D, int lane, float eps, float& mean, float& rstd) {
+  float sum = 0.0f;
+#pragma unroll
+  for (int k = 0; k < NP; ++k)
+    if (k * 256 + lane * 4 < D) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) sum += v[k][e];
+    }
+  const float invD = 1.0f / (float)D;
+  mean = wave_sum(sum) * invD;
+  float sq = 0.0f;
+#pragma unroll
+  for (int k = 0; k < NP; ++k)
+    if (k * 256 + lane * 4 < D) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float d = v[k][e] - mean;
+        sq += d * d;
+      }
+    }
+  rstd = rsqrtf(wave_sum(sq) * invD + eps);
+}
+
+VDR_DEV float ln_affine(float v, float mean, float rstd, float g, float b) { return (v - mean) * rstd * g + b; }
 
 template <bool IN_BF16, bool OUT_BF16, int NP>
 __global__ __launch_bounds__(256) void layernorm_kernel(LnK p) {
@@ -54,46 +107,24 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnK p) {
   }
   const bool from_cls = p.cls != nullptr && (r % p.cls_period) == 0;
   float v[NP][4];
-  float sum = 0.0f;
+  if (from_cls) {
 #pragma unroll
-  for (int k = 0; k < NP; ++k) {
-    const int c = k * 256 + lane * 4;
-    if (c < p.D) {
-      if (from_cls) {
+    for (int k = 0; k < NP; ++k) {
+      const int c = k * 256 + lane * 4;
+      if (c < p.D) {
         const f32x4 t = *reinterpret_cast<const f32x4*>(p.cls + c);
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[k][e] = t[e];
-      } else if (IN_BF16) {
-        const bf16x4 t = *reinterpret_cast<const bf16x4*>((const bf16_t*)p.x + ir * p.D + c);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[k][e] = (float)t[e];
       } else {
-        const f32x4 t = *reinterpret_cast<const f32x4*>((const float*)p.x + ir * p.D + c);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[k][e] = t[e];
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) sum += v[k][e];
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[k][e] = 0.0f;
-    }
-  }
-  const float invD = 1.0f / (float)p.D;
-  const float mean = wave_sum(sum) * invD;
-  float sq = 0.0f;
-#pragma unroll
-  for (int k = 0; k < NP; ++k) {
-    const int c = k * 256 + lane * 4;
-    if (c < p.D) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float d = v[k][e] - mean;
-        sq += d * d;
+        for (int e = 0; e < 4; ++e) v[k][e] = 0.0f;
       }
     }
+  } else {
+    row_load<IN_BF16, NP>(p.x, ir, p.D, lane, v);
   }
-  const float rstd = rsqrtf(wave_sum(sq) * invD + p.eps);
+  float mean, rstd;
+  row_mean_rstd<NP>(v, p.D, lane, p.eps, mean, rstd);
 #pragma unroll
   for (int k = 0; k < NP; ++k) {
     const int c = k * 256 + lane * 4;
@@ -102,17 +133,26 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnK p) {
       const f32x4 bt = *reinterpret_cast<const f32x4*>(p.beta + c);
       float o[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (v[k][e] - mean) * rstd * g[e] + bt[e];
+      for (int e = 0; e < 4; ++e) o[e] = ln_affine(v[k][e], mean, rstd, g[e], bt[e]);
+      const int64_t oi = orow * p.ldy + c;
       if (OUT_BF16) {
         bf16x4 ob;
 #pragma unroll
         for (int e = 0; e < 4; ++e) ob[e] = (bf16_t)o[e];
-        *reinterpret_cast<bf16x4*>((bf16_t*)p.y + orow * p.D + c) = ob;
-      } else {
+        if (p.vec_out) {
+          *reinterpret_cast<bf16x4*>((bf16_t*)p.y + oi) = ob;
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) ((bf16_t*)p.y)[oi + e] = ob[e];
+        }
+      } else if (p.vec_out) {
         f32x4 of;
 #pragma unroll
         for (int e = 0; e < 4; ++e) of[e] = o[e];
-        *reinterpret_cast<f32x4*>((float*)p.y + orow * p.D + c) = of;
+        *reinterpret_cast<f32x4*>((float*)p.y + oi) = of;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ((float*)p.y)[oi + e] = o[e];
       }
     }
   }
@@ -135,8 +175,11 @@ static hipError_t ln_dispatch(const LnK& k, hipStream_t s) {
   return hipGetLastError();
 }
 
+// vector stores of 4 elements need every row start aligned to 4 elements
+static int rows_aligned(const void* y, int64_t ldy, int es) { return (ldy % 4) == 0 && ((uintptr_t)y % (4 * es)) == 0; }
+
 hipError_t launch_layernorm(const LnArgs& a, hipStream_t s) {
-  if (a.rows <= 0 || a.D <= 0 || (a.D & 3) || a.D > 2048) return hipErrorInvalidValue;
+  if (a.rows <= 0 || a.D <= 0 || (a.D & 3) || a.D > 2048 || (a.ldy != 0 && a.ldy < a.D)) return hipErrorInvalidValue;
   LnK k;
   k.x = a.x;
   k.y = a.y;
@@ -155,8 +198,175 @@ hipError_t launch_layernorm(const LnArgs& a, hipStream_t s) {
   k.cls_period = a.cls_period > 0 ? a.cls_period : 1;
   k.win_ws = a.win_ws;
   k.win_g = a.win_g;
+  k.ldy = a.ldy ? a.ldy : a.D;
+  k.vec_out = a.ldy == 0 || rows_aligned(a.y, k.ldy, a.out_bf16 ? 2 : 4);
   if (a.in_bf16) return a.out_bf16 ? ln_dispatch<true, true>(k, s) : ln_dispatch<true, false>(k, s);
   return a.out_bf16 ? ln_dispatch<false, true>(k, s) : ln_dispatch<false, false>(k, s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Mean-pooled patch rows (vdr_forward_layers, VDR_OUT_POOLED: DINOv2 create_linear_input's avgpool).  Pass 1: one
+// workgroup per (chunk of POOL_CHUNK patch rows, image); wave w takes rows w, w+4, ... of the chunk in order, normalises
+// each with the LayerNorm kernel's helpers (norm = 1) and adds the fp32 values into per-lane column sums; the next row's
+// loads are issued before the current row's reductions.  The four waves' sums meet in LDS and are added in wave order:
+// part[b][chunk][:].  Pass 2: sum over the chunks in order, times 1/n, one rounding to the output dtype.  The chunking
+// does not depend on the batch, so an image's result is the same in any batch.
+// ---------------------------------------------------------------------------------------------
+struct PoolK {
+  const void* x;
+  const float* gamma;
+  const float* beta;
+  float* part;
+  int ntok, ncls, n, D, chunks;
+  float eps;
+};
+
+template <bool IN_BF16, bool NORM, int NP>
+__global__ __launch_bounds__(256) void pool_rows_kernel(PoolK p) {
+  extern __shared__ __attribute__((aligned(16))) float red[];  // [4][D]: the waves' column sums
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int chunk = blockIdx.x, b = blockIdx.y;
+  const int j0 = chunk * POOL_CHUNK;
+  const int cnt = min(POOL_CHUNK, p.n - j0);  // rows of this chunk (the last one may be ragged)
+  const int64_t row0 = (int64_t)b * p.ntok + p.ncls + j0;
+  float g[NP][4], bt[NP][4], acc[NP][4];
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
+    const int c = k * 256 + lane * 4;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[k][e] = 0.0f;
+    if (NORM && c < p.D) {
+      const f32x4 tg = *reinterpret_cast<const f32x4*>(p.gamma + c);
+      const f32x4 tb = *reinterpret_cast<const f32x4*>(p.beta + c);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        g[k][e] = tg[e];
+        bt[k][e] = tb[e];
+      }
+    }
+  }
+  float v[NP][4], nx[NP][4];
+  int j = wv;
+  if (j < cnt) row_load<IN_BF16, NP>(p.x, row0 + j, p.D, lane, v);
+  for (; j < cnt; j += 4) {
+    const bool more = j + 4 < cnt;
+    if (more) row_load<IN_BF16, NP>(p.x, row0 + j + 4, p.D, lane, nx);
+    if (NORM) {
+      float mean, rstd;
+      row_mean_rstd<NP>(v, p.D, lane, p.eps, mean, rstd);
+#pragma unroll
+      for (int k = 0; k < NP; ++k)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[k][e] += ln_affine(v[k][e], mean, rstd, g[k][e], bt[k][e]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < NP; ++k)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[k][e] += v[k][e];
+    }
+    if (more) {
+#pragma unroll
+      for (int k = 0; k < NP; ++k)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[k][e] = nx[k][e];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
+    const int c = k * 256 + lane * 4;
+    if (c < p.D) {
+      f32x4 t;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) t[e] = acc[k][e];
+      *reinterpret_cast<f32x4*>(&red[wv * p.D + c]) = t;
+    }
+  }
+  __syncthreads();
+  float* dst = p.part + ((int64_t)b * p.chunks + chunk) * p.D;
+  for (int c = threadIdx.x * 4; c < p.D; c += 1024) {
+    f32x4 t = *reinterpret_cast<const f32x4*>(&red[c]);
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+      const f32x4 u = *reinterpret_cast<const f32x4*>(&red[w * p.D + c]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) t[e] += u[e];
+    }
+    *reinterpret_cast<f32x4*>(dst + c) = t;
+  }
+}
+
+template <bool OUT_BF16>
+__global__ __launch_bounds__(256) void pool_finish_kernel(const float* __restrict__ part, int chunks, int D, int batch, float inv_n,
+                                                          void* __restrict__ y, int64_t ldy) {
+  const int d4 = D >> 2;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)batch * d4) return;
+  const int64_t b = idx / d4;
+  const int c = (int)(idx - b * d4) * 4;
+  const float* src = part + b * chunks * (int64_t)D + c;
+  f32x4 t = *reinterpret_cast<const f32x4*>(src);
+  for (int k = 1; k < chunks; ++k) {
+    const f32x4 u = *reinterpret_cast<const f32x4*>(src + (int64_t)k * D);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) t[e] += u[e];
+  }
+  // (scalar stores: y + b*ldy need not be vector-aligned -- a column slice of a wider matrix)
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float o = t[e] * inv_n;
+    if (OUT_BF16)
+      ((bf16_t*)y)[b * ldy + c + e] = (bf16_t)o;
+    else
+      ((float*)y)[b * ldy + c + e] = o;
+  }
+}
+
+template <bool IB, bool NORM>
+static hipError_t pool_dispatch(const PoolK& k, int np, dim3 grid, hipStream_t s) {
+#define VDR_POOL(NP)                                                                         \
+  case NP:                                                                                   \
+    hipLaunchKernelGGL((pool_rows_kernel<IB, NORM, NP>), grid, dim3(256), (size_t)16 * k.D, s, k);          \
+    break;
+  switch (np) {
+    VDR_POOL(1) VDR_POOL(2) VDR_POOL(3) VDR_POOL(4) VDR_POOL(5) VDR_POOL(6) VDR_POOL(7) VDR_POOL(8)
+    default:
+      return hipErrorInvalidValue;
+  }
+#undef VDR_POOL
+  return hipGetLastError();
+}
+
+hipError_t launch_pool_rows(const void* x, int in_bf16, int norm, const float* gamma, const float* beta, float eps, int batch,
+                            int ntok, int ncls, int n, int D, float* part, void* y, int out_bf16, int64_t ldy, hipStream_t s) {
+  if (batch <= 0 || n <= 0 || ncls < 0 || ntok < n + ncls || D <= 0 || (D & 3) || D > 2048 || batch > 65535 ||
+      (ldy != 0 && ldy < D) || (norm && (!gamma || !beta)))
+    return hipErrorInvalidValue;
+  PoolK k;
+  k.x = x;
+  k.gamma = gamma;
+  k.beta = beta;
+  k.part = part;
+  k.ntok = ntok;
+  k.ncls = ncls;
+  k.n = n;
+  k.D = D;
+  k.chunks = (n + POOL_CHUNK - 1) / POOL_CHUNK;
+  k.eps = eps;
+  const dim3 grid((unsigned)k.chunks, (unsigned)batch);
+  const int np = (D + 255) / 256;
+  hipError_t e = in_bf16 ? (norm ? pool_dispatch<true, true>(k, np, grid, s) : pool_dispatch<true, false>(k, np, grid, s))
+                         : (norm ? pool_dispatch<false, true>(k, np, grid, s) : pool_dispatch<false, false>(k, np, grid, s));
+  if (e != hipSuccess) return e;
+  const int64_t total = (int64_t)batch * (D / 4);
+  const float inv_n = 1.0f / (float)n;
+  const int64_t ld = ldy ? ldy : D;
+  if (out_bf16)
+    hipLaunchKernelGGL((pool_finish_kernel<true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, part, k.chunks, D, batch,
+                       inv_n, y, ld);
+  else
+    hipLaunchKernelGGL((pool_finish_kernel<false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, part, k.chunks, D, batch,
+                       inv_n, y, ld);
+  return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -380,39 +590,66 @@ hipError_t launch_assemble_tokens(const void* tok, int in_bf16, const float* cls
   return hipGetLastError();
 }
 
-// y[r][:] = x[imap(r)][:]  (bf16 in; bf16 or fp32 out) — the x[:,0,:] / x[:,1:,:] slice for models
-// without a final norm (post-LN nn.TransformerEncoder, models_archs.py:147)
-template <bool OUT_BF16>
-__global__ __launch_bounds__(256) void gather_rows_kernel(const bf16_t* __restrict__ x, void* __restrict__ y,
-                                                          int64_t rows, int D, int rpg, int64_t gs, int off) {
+// y[r][:] = x[imap(r)][:]  (bf16 or fp32 in; bf16 or fp32 out) — the x[:,0,:] / x[:,1:,:] slice for models
+// without a final norm (post-LN nn.TransformerEncoder, models_archs.py:147), the raw residual stream of
+// vdr_forward_layers (norm = 0), the fp32 copy of the stream (resid_fp32).  Output row stride ldy elements.
+template <bool IN_F32, bool OUT_BF16>
+__global__ __launch_bounds__(256) void gather_rows_kernel(const void* __restrict__ x, void* __restrict__ y,
+                                                          int64_t rows, int D, int rpg, int64_t gs, int off, int64_t ldy,
+                                                          int vec_out) {
   const int d4 = D >> 2;
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= rows * d4) return;
   const int64_t r = idx / d4;
   const int d = (int)(idx - r * d4) * 4;
   const int64_t ir = map_row(r, rpg, gs, off);
-  const bf16x4 a = *reinterpret_cast<const bf16x4*>(x + ir * D + d);
-  if (OUT_BF16) {
-    *reinterpret_cast<bf16x4*>((bf16_t*)y + r * D + d) = a;
+  float v[4];
+  if (IN_F32) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>((const float*)x + ir * D + d);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = a[e];
   } else {
+    const bf16x4 a = *reinterpret_cast<const bf16x4*>((const bf16_t*)x + ir * D + d);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = (float)a[e];
+  }
+  const int64_t oi = r * ldy + d;
+  if (OUT_BF16) {
+    bf16x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = (bf16_t)v[e];
+    if (vec_out) {
+      *reinterpret_cast<bf16x4*>((bf16_t*)y + oi) = o;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ((bf16_t*)y)[oi + e] = o[e];
+    }
+  } else if (vec_out) {
     f32x4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = (float)a[e];
-    *reinterpret_cast<f32x4*>((float*)y + r * D + d) = o;
+    for (int e = 0; e < 4; ++e) o[e] = v[e];
+    *reinterpret_cast<f32x4*>((float*)y + oi) = o;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ((float*)y)[oi + e] = v[e];
   }
 }
 
 hipError_t launch_gather_rows(const void* x, void* y, int out_bf16, int64_t rows, int D, RowMap imap,
-                              hipStream_t s) {
-  if (D & 3) return hipErrorInvalidValue;
+                              hipStream_t s, int in_f32, int64_t ldy) {
+  if ((D & 3) || (ldy != 0 && ldy < D)) return hipErrorInvalidValue;
   const int64_t total = rows * (D / 4);
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (out_bf16)
-    hipLaunchKernelGGL((gather_rows_kernel<true>), grid, block, 0, s, (const bf16_t*)x, y, rows, D, imap.rpg,
-                       imap.gstride, imap.off);
-  else
-    hipLaunchKernelGGL((gather_rows_kernel<false>), grid, block, 0, s, (const bf16_t*)x, y, rows, D, imap.rpg,
-                       imap.gstride, imap.off);
+  const int64_t ld = ldy ? ldy : D;
+  const int vec = ldy == 0 || rows_aligned(y, ld, out_bf16 ? 2 : 4);
+#define VDR_GATHER(F, B)                                                                                                  \
+  hipLaunchKernelGGL((gather_rows_kernel<F, B>), grid, block, 0, s, x, y, rows, D, imap.rpg, imap.gstride, imap.off, ld, vec)
+  if (in_f32) {
+    if (out_bf16) VDR_GATHER(true, true); else VDR_GATHER(true, false);
+  } else {
+    if (out_bf16) VDR_GATHER(false, true); else VDR_GATHER(false, false);
+  }
+#undef VDR_GATHER
   return hipGetLastError();
 }
 

@@ -777,7 +777,7 @@ int gemm(vdr_model* m, hipStream_t s, int cls, const void* A, const void* W, con
 
 int layernorm(vdr_model* m, hipStream_t s, int cls, const void* x, int in_bf16, void* y, int out_bf16,
               const float* gw, const float* gb, int64_t rows, RowMap imap, const float* clsrc = nullptr,
-              int cls_period = 0, int width = 0) {
+              int cls_period = 0, int width = 0, int64_t ldy = 0) {
   LnArgs a{};
   a.x = x;
   a.in_bf16 = in_bf16;
@@ -792,6 +792,7 @@ int layernorm(vdr_model* m, hipStream_t s, int cls, const void* x, int in_bf16, 
   a.omap = identity_map();
   a.cls = clsrc;
   a.cls_period = cls_period;
+  a.ldy = ldy;
   Scope sc(m, s, cls, 0.0, (double)rows * a.D * ((in_bf16 ? 2 : 4) + (out_bf16 ? 2 : 4)));
   VDR_TRY(launch_layernorm(a, s), "layernorm");
   return VDR_OK;
@@ -926,9 +927,68 @@ int block_tail_cls(vdr_model* m, hipStream_t s, const Carve& w, const LayerW& L,
   return gemm(m, s, VDR_K_GEMM_FC2, w.u, L.w2, L.b2, xc, L.ls2, xc, mb, D, F, D, EPI_BIAS_RESID, LnFold(), 0, 0, c32, c32);
 }
 
+// vdr_forward_layers: the outputs to write after each block, and the first image of the micro-batch being run
+struct EmitList {
+  std::vector<std::vector<const vdr_layer_out*>> at;  // [block] -> outputs of that block
+  int last = -1;                                      // last block that runs (the largest requested layer)
+  int b0 = 0;
+};
+
+// Writes every output requested for block i of this micro-batch, on its stream, right after the block's last residual
+// GEMM (and, fp8_cls_bf16, after the copy that puts the CLS rows' bf16 MLP result into w.x: it is enqueued on `s` before
+// this call, so stream order puts these reads behind it).  norm = 1 goes through the final-LayerNorm launch of emit()
+// with the same row maps -- the bits of a model truncated to i + 1 blocks; compact: block i ran its CLS rows only
+// (block_tail_cls) and they sit in w.h / w.xc32.  Every launch is booked as VDR_K_FINAL_LN.
+int emit_layer(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, const EmitList& el, int i, bool compact) {
+  const vdr_config& c = m->cfg;
+  const int D = c.dim, ncls = c.has_cls ? 1 : 0, n = ntok - ncls;
+  for (const vdr_layer_out* o : el.at[i]) {
+    const int ob = o->out_dtype == VDR_BF16;
+    const size_t es = ob ? 2 : 4;
+    // the stream: its fp32 master copy when there is one (resid_fp32), else the bf16 rows
+    const bool f32 = compact ? w.xc32 != nullptr : w.x32 != nullptr;
+    const void* src = compact ? (f32 ? (const void*)w.xc32 : (const void*)w.h) : (f32 ? (const void*)w.x32 : (const void*)w.x);
+    if (o->out_mode == VDR_OUT_POOLED) {
+      const int64_t ld = o->ld ? o->ld : D;
+      char* dst = (char*)o->out + (size_t)el.b0 * ld * es;
+      if (pool_part_bytes(mb, n, D) > (size_t)w.Mp * c.mlp_hidden * 2)
+        return fail(m, VDR_ERR_UNSUPPORTED, "pooled output: partial sums do not fit the MLP activation buffer");
+      Scope sc(m, s, VDR_K_FINAL_LN, 0.0, (double)mb * n * D * (f32 ? 4 : 2) + (double)mb * D * es);
+      // (the partial sums go to the fc1 activation w.u: dead from fc2 of block i to fc1 of block i + 1)
+      VDR_TRY(launch_pool_rows(src, !f32, o->norm, m->normw, m->normb, c.ln_eps, mb, ntok, ncls, n, D, (float*)w.u, dst, ob, ld, s),
+              "pooled rows");
+      continue;
+    }
+    RowMap im = identity_map();
+    int64_t rows = mb, ld = 0;
+    char* dst;
+    if (o->out_mode == VDR_OUT_CLS) {
+      if (!compact) im = RowMap{1, ntok, 0};
+      ld = o->ld ? o->ld : D;
+      dst = (char*)o->out + (size_t)el.b0 * ld * es;
+    } else if (o->out_mode == VDR_OUT_DENSE) {
+      im = RowMap{n, ntok, ncls};
+      rows = (int64_t)mb * n;
+      dst = (char*)o->out + (size_t)el.b0 * n * D * es;
+    } else {
+      rows = (int64_t)mb * ntok;
+      dst = (char*)o->out + (size_t)el.b0 * ntok * D * es;
+    }
+    int rc;
+    if (o->norm) {
+      if ((rc = layernorm(m, s, VDR_K_FINAL_LN, src, !f32, dst, ob, m->normw, m->normb, rows, im, nullptr, 0, 0, ld))) return rc;
+    } else {
+      Scope sc(m, s, VDR_K_FINAL_LN, 0.0, (double)rows * D * ((f32 ? 4 : 2) + es));
+      VDR_TRY(launch_gather_rows(src, dst, ob, rows, D, im, s, f32, ld), "gather_rows");
+    }
+  }
+  return VDR_OK;
+}
+
 // cls_tail: the caller only wants the CLS rows (see block_tail_cls); *compact is set when they were left in w.h [mb, D]
+// el (vdr_forward_layers): blocks 0 .. el->last run, and each block's requested outputs are written after it
 int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, const int* lens = nullptr, int len_add = 0,
-               bool cls_tail = false, bool* compact = nullptr) {
+               bool cls_tail = false, bool* compact = nullptr, const EmitList* el = nullptr) {
   const vdr_config& c = m->cfg;
   const int D = c.dim, F = c.mlp_hidden, H = c.heads;
   const int64_t M = (int64_t)mb * ntok;
@@ -937,7 +997,10 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
   if (compact) *compact = false;
   // (post-LN blocks keep every row: their last operation is a LayerNorm over the block's own output, also row-wise, but
   // the classifier that uses them is not a throughput path)
-  const int tail_at = (cls_tail && compact && c.pre_ln && !c.full_last_block && ntok > 1) ? c.layers - 1 : -1;
+  const int nl = el ? el->last + 1 : c.layers;
+  const int tail_at = (cls_tail && compact && c.pre_ln && !c.full_last_block && ntok > 1) ? nl - 1 : -1;
+  // (a block's outputs; the tail's CLS rows are compact)
+  auto after = [&](int i, bool cmp) { return el ? emit_layer(m, s, w, mb, ntok, *el, i, cmp) : (int)VDR_OK; };
   if (c.fp8) {
     // BASELINE config 5: qkv / fc1 / fc2 on the block-scaled fp8 MFMA.  LayerNorm writes its output as MX-fp8
     // (the qkv / fc1 operand), the attention kernel and the fc1 epilogue write theirs as MX-fp8 (the proj / fc2
@@ -946,7 +1009,7 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
     // vdr_config.fp8_cls_bf16 (image models with a CLS token; not the variable-length token path)
     const int ai = m->cur_aux;
     const bool cls_bf16 = c.fp8_cls_bf16 && c.has_cls && c.patch && ntok > 1 && !lens && ai < (int)m->aux.size() && w.cls_x;
-    for (int i = 0; i < c.layers; ++i) {
+    for (int i = 0; i < nl; ++i) {
       const LayerW& L = m->layers[i];
       {
         Scope sc(m, s, VDR_K_LAYERNORM, 0.0, (double)M * D * 3);
@@ -962,7 +1025,8 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
       }
       if (i == tail_at) {
         *compact = true;
-        return block_tail_cls(m, s, w, L, mb, ntok);
+        if ((rc = block_tail_cls(m, s, w, L, mb, ntok))) return rc;
+        return after(i, true);
       }
       // the out-projection stays bf16: quantising it too measured 0.987 row cosine at 40 blocks (gate 0.99)
       if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, w.o, L.wproj, L.bproj, w.x, L.ls1, w.x, M, D, D, D, EPI_BIAS_RESID))) return rc;
@@ -987,6 +1051,8 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
       if (cls_bf16)  // ... and the bf16 result replaces the MX-fp8 one in the CLS rows
         VDR_TRY(hipMemcpy2DAsync(w.x, (size_t)ntok * D * 2, w.cls_x, (size_t)D * 2, (size_t)D * 2, (size_t)mb, hipMemcpyDeviceToDevice, s),
                 "hipMemcpy2DAsync(CLS rows)");
+      // (the outputs of block i read w.x after that copy: both are on s)
+      if ((rc = after(i, false))) return rc;
     }
     return VDR_OK;
   }
@@ -1000,7 +1066,7 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
     // ring4 consumers to finalise their own rows from the partials need nothing)
     if (!ln_stats_in_gemm(VDR_K_GEMM_QKV, M, 3 * D, D / 64) || !ln_stats_in_gemm(VDR_K_GEMM_FC1, M, sw ? 2 * F : F, D / 64))
       prod.fin_stats = w.stats;
-    for (int i = 0; i < c.layers; ++i) {
+    for (int i = 0; i < nl; ++i) {
       const LayerW& L = m->layers[i];
       LnFold cons;
       if ((rc = ln_consumer(m, s, VDR_K_GEMM_QKV, M, 3 * D, D, w, &cons))) return rc;
@@ -1015,7 +1081,8 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
       }
       if (i == tail_at) {
         *compact = true;
-        return block_tail_cls(m, s, w, L, mb, ntok);
+        if ((rc = block_tail_cls(m, s, w, L, mb, ntok))) return rc;
+        return after(i, true);
       }
       if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, w.o, L.wproj, L.bproj, w.x, L.ls1, w.x, M, D, D, D, EPI_BIAS_RESID, prod, 0, 0, w.x32, w.x32)))
         return rc;
@@ -1026,10 +1093,11 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
         return rc;
       if ((rc = gemm(m, s, VDR_K_GEMM_FC2, w.u, L.w2, L.b2, w.x, L.ls2, w.x, M, D, F, D, EPI_BIAS_RESID, prod, 0, 0, w.x32, w.x32)))
         return rc;
+      if ((rc = after(i, false))) return rc;
     }
     return VDR_OK;
   }
-  for (int i = 0; i < c.layers; ++i) {
+  for (int i = 0; i < nl; ++i) {
     const LayerW& L = m->layers[i];
     const void* attn_in = w.x;
     // (resid_fp32: the explicit LayerNorm reads the fp32 master copy of the stream)
@@ -1049,7 +1117,8 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
     }
     if (i == tail_at) {
       *compact = true;
-      return block_tail_cls(m, s, w, L, mb, ntok);
+      if ((rc = block_tail_cls(m, s, w, L, mb, ntok))) return rc;
+      return after(i, true);
     }
     if (c.pre_ln) {
       if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, w.o, L.wproj, L.bproj, w.x, L.ls1, w.x, M, D, D, D, EPI_BIAS_RESID, LnFold(), 0, 0, w.x32, w.x32)))
@@ -1060,6 +1129,7 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
         return rc;
       if ((rc = gemm(m, s, VDR_K_GEMM_FC2, w.u, L.w2, L.b2, w.x, L.ls2, w.x, M, D, F, D, EPI_BIAS_RESID, LnFold(), 0, 0, w.x32, w.x32)))
         return rc;
+      if ((rc = after(i, false))) return rc;
     } else {
       // nn.TransformerEncoderLayer, norm_first=False: x = LN1(x + SA(x)); x = LN2(x + FF(x))
       if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, w.o, L.wproj, L.bproj, w.x, L.ls1, w.h, M, D, D, D, EPI_BIAS_RESID))) return rc;
@@ -1260,6 +1330,83 @@ int emit(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, int out_
 }
 
 size_t out_row_bytes(const vdr_model* m, int out_dtype) { return (size_t)m->cfg.dim * (out_dtype == VDR_BF16 ? 2 : 4); }
+
+// patch embedding of one micro-batch: the token rows b*ntok + ncls + i of w.x (pos_embed added), or -- pe_out non-null,
+// model.patch_embed(x) -- the caller's [mb, n, D] output
+int embed_patches(vdr_model* m, hipStream_t s, const Carve& w, const char* img, int in_dtype, int mb, char* pe_out, int out_dtype) {
+  const vdr_config& c = m->cfg;
+  const int ntok = m->n_tokens, n = m->n_patches, D = c.dim, ncls = c.has_cls ? 1 : 0;
+  const size_t img_elems = (size_t)c.in_chans * c.img * c.img;
+  const size_t in_es = in_dtype == VDR_BF16 ? 2 : 4;
+  // bf16 images with a patch side of 8 / 16 / 32: the patch GEMM's operand loader gathers 16-byte runs of pixels
+  // straight from the NCHW images (ring4 tile variants) -- no col buffer, no im2col launch.  fp32 images (the loader
+  // is an LDS-DMA: it cannot convert) and p = 14 (runs of 14 pixels are not 16-byte chunks) go through im2col.
+  const int pvar = gemm_variant_for(VDR_K_GEMM_PATCH, (int64_t)mb * n, D);
+  const bool fused_patch = patch_gather_ok(in_dtype, c.patch, pvar, img);
+  const bool pe_only = pe_out != nullptr;
+  if (!fused_patch) {
+    Scope sc(m, s, VDR_K_IM2COL, 0.0, (double)mb * img_elems * in_es + 2.0 * mb * n * m->Kp);
+    VDR_TRY(launch_im2col(img, in_dtype == VDR_BF16, w.u, mb, c.in_chans, c.img, c.patch, m->Kp, s), "im2col");
+  }
+  GemmArgs g{};
+  g.A = fused_patch ? (const void*)img : (const void*)w.u;
+  if (fused_patch) {
+    g.patch_p = c.patch;
+    g.patch_g = c.img / c.patch;
+    g.patch_C = c.in_chans;
+  }
+  g.W = m->w_patch;
+  g.bias = m->b_patch;
+  g.pos = pe_only ? nullptr : m->pos;
+  g.M = (int64_t)mb * n;
+  g.N = D;
+  g.K = m->Kp;
+  g.lda = m->Kp;
+  g.ldw = m->Kp;
+  g.ldc = D;
+  g.ldr = D;
+  if (m->ln_fuse && !pe_only) {
+    g.ln_part = w.part;
+    g.part_stride = w.Mp;
+  }
+  if (pe_only) {
+    // model.patch_embed(x) (tfds_dense_descriptor.py:128): the GEMM epilogue writes the caller's [B, n, D] buffer
+    // directly, bf16 or fp32 (no conversion pass)
+    g.C = pe_out;
+    g.out_f32 = out_dtype != VDR_BF16;
+    g.omap = RowMap{n, n, 0};
+  } else {
+    g.C = w.x;
+    g.omap = RowMap{n, ntok, ncls};
+  }
+  Scope sc(m, s, VDR_K_GEMM_PATCH, 2.0 * g.M * D * c.in_chans * c.patch * c.patch,
+           2.0 * ((double)g.M * m->Kp + (double)D * m->Kp + (double)g.M * D));
+  VDR_TRY(launch_gemm_w(m, g, EPI_PATCH, pvar, s), "patch gemm");
+  return VDR_OK;
+}
+
+// CLS rows, input LayerNorm and the fp32 master copy of the stream: afterwards w.x (w.x32) holds what block 0 reads
+int assemble_stream(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok) {
+  const vdr_config& c = m->cfg;
+  const int D = c.dim;
+  int rc;
+  if (c.has_cls) {
+    Scope sc(m, s, VDR_K_ASSEMBLE, 0.0, (double)mb * D * 2);
+    if (m->ln_fuse)
+      VDR_TRY(launch_cls_rows_stats(m->cls, m->pos, w.x, w.part, w.Mp, mb, ntok, D, s), "cls rows");
+    else
+      VDR_TRY(launch_cls_rows(m->cls, m->pos, w.x, mb, ntok, D, s), "cls rows");
+  }
+  if (c.input_ln) {
+    if ((rc = layernorm(m, s, VDR_K_LAYERNORM, w.x, 1, w.x, 1, m->inw, m->inb, (int64_t)mb * ntok, identity_map())))
+      return rc;
+  }
+  if (w.x32) {  // resid_fp32: the stream's fp32 master copy starts from the assembled tokens (their one bf16 rounding stays)
+    Scope sc(m, s, VDR_K_ASSEMBLE, 0.0, (double)mb * ntok * D * 6);
+    VDR_TRY(launch_gather_rows(w.x, w.x32, 0, (int64_t)mb * ntok, D, identity_map(), s), "residual stream -> fp32");
+  }
+  return VDR_OK;
+}
 
 int check_device(vdr_handle h) {
   int n = 0;
@@ -1541,52 +1688,9 @@ int vdr_forward(vdr_handle m, const void* images, int in_dtype, int batch, void*
     hipStream_t s = ns == 1 ? caller : m->streams[si];
     const Carve w = carve(m, (char*)workspace + si * per_ws, mb_max, ntok);
     const char* img = (const char*)images + (size_t)b0 * img_elems * in_es;
-    // bf16 images with a patch side of 8 / 16 / 32: the patch GEMM's operand loader gathers 16-byte runs of pixels
-    // straight from the NCHW images (ring4 tile variants) -- no col buffer, no im2col launch.  fp32 images (the loader
-    // is an LDS-DMA: it cannot convert) and p = 14 (runs of 14 pixels are not 16-byte chunks) go through im2col.
-    const int pvar = gemm_variant_for(VDR_K_GEMM_PATCH, (int64_t)mb * n, D);
-    const bool fused_patch = patch_gather_ok(in_dtype, c.patch, pvar, img);
     const bool pe_only = out_mode == VDR_OUT_PATCH_EMBED;
-    if (!fused_patch) {
-      Scope sc(m, s, VDR_K_IM2COL, 0.0, (double)mb * img_elems * in_es + 2.0 * mb * n * m->Kp);
-      VDR_TRY(launch_im2col(img, in_dtype == VDR_BF16, w.u, mb, c.in_chans, c.img, c.patch, m->Kp, s), "im2col");
-    }
-    {
-      GemmArgs g{};
-      g.A = fused_patch ? (const void*)img : (const void*)w.u;
-      if (fused_patch) {
-        g.patch_p = c.patch;
-        g.patch_g = c.img / c.patch;
-        g.patch_C = c.in_chans;
-      }
-      g.W = m->w_patch;
-      g.bias = m->b_patch;
-      g.pos = pe_only ? nullptr : m->pos;
-      g.M = (int64_t)mb * n;
-      g.N = D;
-      g.K = m->Kp;
-      g.lda = m->Kp;
-      g.ldw = m->Kp;
-      g.ldc = D;
-      g.ldr = D;
-      if (m->ln_fuse && !pe_only) {
-        g.ln_part = w.part;
-        g.part_stride = w.Mp;
-      }
-      if (pe_only) {
-        // model.patch_embed(x) (tfds_dense_descriptor.py:128): the GEMM epilogue writes the caller's [B, n, D] buffer
-        // directly, bf16 or fp32 (no conversion pass)
-        g.C = (char*)out + (size_t)b0 * n * D * (out_dtype == VDR_BF16 ? 2 : 4);
-        g.out_f32 = out_dtype != VDR_BF16;
-        g.omap = RowMap{n, n, 0};
-      } else {
-        g.C = w.x;
-        g.omap = RowMap{n, ntok, ncls};
-      }
-      Scope sc(m, s, VDR_K_GEMM_PATCH, 2.0 * g.M * D * c.in_chans * c.patch * c.patch,
-               2.0 * ((double)g.M * m->Kp + (double)D * m->Kp + (double)g.M * D));
-      VDR_TRY(launch_gemm_w(m, g, EPI_PATCH, pvar, s), "patch gemm");
-    }
+    char* pe_out = pe_only ? (char*)out + (size_t)b0 * n * D * (out_dtype == VDR_BF16 ? 2 : 4) : nullptr;
+    if ((rc = embed_patches(m, s, w, img, in_dtype, mb, pe_out, out_dtype))) return rc;
     if (pe_only) continue;
     if (c.window > 0) {
       const bool tok = out_mode == VDR_OUT_TOKENS;
@@ -1594,26 +1698,82 @@ int vdr_forward(vdr_handle m, const void* images, int in_dtype, int batch, void*
       if ((rc = run_sam(m, s, w, mb, out_dtype, (char*)out + (size_t)b0 * n * orow_b, tok))) return rc;
       continue;
     }
-    if (c.has_cls) {
-      Scope sc(m, s, VDR_K_ASSEMBLE, 0.0, (double)mb * D * 2);
-      if (m->ln_fuse)
-        VDR_TRY(launch_cls_rows_stats(m->cls, m->pos, w.x, w.part, w.Mp, mb, ntok, D, s), "cls rows");
-      else
-        VDR_TRY(launch_cls_rows(m->cls, m->pos, w.x, mb, ntok, D, s), "cls rows");
-    }
-    if (c.input_ln) {
-      if ((rc = layernorm(m, s, VDR_K_LAYERNORM, w.x, 1, w.x, 1, m->inw, m->inb, (int64_t)mb * ntok, identity_map())))
-        return rc;
-    }
-    if (w.x32) {  // resid_fp32: the stream's fp32 master copy starts from the assembled tokens (their one bf16 rounding stays)
-      Scope sc(m, s, VDR_K_ASSEMBLE, 0.0, (double)mb * ntok * D * 6);
-      VDR_TRY(launch_gather_rows(w.x, w.x32, 0, (int64_t)mb * ntok, D, identity_map(), s), "residual stream -> fp32");
-    }
+    if ((rc = assemble_stream(m, s, w, mb, ntok))) return rc;
     bool compact = false;
     if ((rc = run_blocks(m, s, w, mb, ntok, nullptr, 0, out_mode == VDR_OUT_CLS, &compact))) return rc;
     const int64_t rows_per_img = out_mode == VDR_OUT_CLS ? 1 : (out_mode == VDR_OUT_DENSE ? ntok - ncls : ntok);
     char* o = (char*)out + (size_t)b0 * rows_per_img * out_row_bytes(m, out_dtype);
     if ((rc = emit(m, s, w, mb, ntok, out_mode, out_dtype, o, compact))) return rc;
+  }
+  if (join_streams(m, caller)) return fail(m, VDR_ERR_HIP, "internal stream join failed");
+  return VDR_OK;
+}
+
+int vdr_forward_layers(vdr_handle m, const void* images, int in_dtype, int batch, const vdr_layer_out* outs, int n_outs,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+  // argument checks that need no model first (they also hold for a null handle), then the model's
+  if (!outs || n_outs <= 0) return fail(m, VDR_ERR_INVALID, "null outs or n_outs <= 0");
+  for (int k = 0; k < n_outs; ++k) {
+    const vdr_layer_out& o = outs[k];
+    const std::string at = "outs[" + std::to_string(k) + "]: ";
+    if (!o.out) return fail(m, VDR_ERR_INVALID, at + "null out");
+    if (o.out_mode != VDR_OUT_CLS && o.out_mode != VDR_OUT_DENSE && o.out_mode != VDR_OUT_TOKENS && o.out_mode != VDR_OUT_POOLED)
+      return fail(m, VDR_ERR_INVALID, at + "out_mode must be CLS, DENSE, TOKENS or POOLED");
+    if (o.out_dtype != VDR_F32 && o.out_dtype != VDR_BF16) return fail(m, VDR_ERR_INVALID, at + "out_dtype");
+    if (o.norm != 0 && o.norm != 1) return fail(m, VDR_ERR_INVALID, at + "norm must be 0 or 1");
+    if (o.ld < 0) return fail(m, VDR_ERR_INVALID, at + "negative ld");
+    if (o.ld != 0 && (o.out_mode == VDR_OUT_DENSE || o.out_mode == VDR_OUT_TOKENS))
+      return fail(m, VDR_ERR_INVALID, at + "ld must be 0 for DENSE / TOKENS");
+  }
+  if (!m || !images || !workspace || batch <= 0) return fail(m, VDR_ERR_INVALID, "null/invalid argument");
+  const vdr_config& c = m->cfg;
+  if (!c.patch) return fail(m, VDR_ERR_UNSUPPORTED, "vdr_forward_layers: image models only (token model)");
+  if (c.window > 0) return fail(m, VDR_ERR_UNSUPPORTED, "vdr_forward_layers: not for the SAM encoder (no final norm, a neck)");
+  if (!c.pre_ln) return fail(m, VDR_ERR_UNSUPPORTED, "vdr_forward_layers: pre-LN models only");
+  if (c.layers <= 0) return fail(m, VDR_ERR_UNSUPPORTED, "vdr_forward_layers: the model has no blocks");
+  if (in_dtype != VDR_F32 && in_dtype != VDR_BF16) return fail(m, VDR_ERR_INVALID, "in_dtype");
+  const int D = c.dim;
+  EmitList el;
+  el.at.resize(c.layers);
+  for (int k = 0; k < n_outs; ++k) {
+    const vdr_layer_out& o = outs[k];
+    const std::string at = "outs[" + std::to_string(k) + "]: ";
+    if (o.layer < 0 || o.layer >= c.layers)
+      return fail(m, VDR_ERR_INVALID, at + "layer " + std::to_string(o.layer) + " out of range 0.." + std::to_string(c.layers - 1));
+    if (o.out_mode == VDR_OUT_CLS && !c.has_cls) return fail(m, VDR_ERR_INVALID, at + "model has no cls token");
+    if (o.ld != 0 && o.ld < D) return fail(m, VDR_ERR_INVALID, at + "ld must be 0 or >= D");
+    el.at[o.layer].push_back(&o);
+    if (o.layer > el.last) el.last = o.layer;
+  }
+  bool cls_only = true;  // every output of the last block that runs is CLS: that block may run its CLS rows only
+  for (const vdr_layer_out* o : el.at[el.last]) cls_only = cls_only && o->out_mode == VDR_OUT_CLS;
+  int rc = check_device(m);
+  if (rc) return rc;
+  if (!m->resolved) return fail(m, VDR_ERR_INCOMPLETE, "vdr_finalize has not run since the last vdr_set_weight");
+  DeviceGuard dg(m->device);
+  if (!dg.ok) return fail(m, VDR_ERR_HIP, "hipSetDevice failed");
+  const int mb_max = default_micro_batch(m, batch);
+  const int ntok = m->n_tokens;
+  const int ns = num_streams(m);
+  const size_t per_ws = carve(m, nullptr, mb_max, ntok).total;
+  if (per_ws * ns > workspace_bytes)
+    return fail(m, VDR_ERR_WORKSPACE, "workspace too small: need " + std::to_string(per_ws * ns) + " bytes");
+  hipStream_t caller = (hipStream_t)stream;
+  if (fork_streams(m, caller)) return fail(m, VDR_ERR_HIP, "internal stream setup failed");
+  const size_t img_bytes = (size_t)c.in_chans * c.img * c.img * (in_dtype == VDR_BF16 ? 2 : 4);
+  int chunk = 0;
+  for (int b0 = 0; b0 < batch; b0 += mb_max, ++chunk) {  // (micro-batches and streams as vdr_forward)
+    const int mb = batch - b0 < mb_max ? batch - b0 : mb_max;
+    const int si = chunk % ns;
+    m->cur_aux = si;
+    m->stats_fresh = false;
+    hipStream_t s = ns == 1 ? caller : m->streams[si];
+    const Carve w = carve(m, (char*)workspace + si * per_ws, mb_max, ntok);
+    if ((rc = embed_patches(m, s, w, (const char*)images + (size_t)b0 * img_bytes, in_dtype, mb, nullptr, VDR_F32))) return rc;
+    if ((rc = assemble_stream(m, s, w, mb, ntok))) return rc;
+    el.b0 = b0;
+    bool compact = false;
+    if ((rc = run_blocks(m, s, w, mb, ntok, nullptr, 0, cls_only, &compact, &el))) return rc;
   }
   if (join_streams(m, caller)) return fail(m, VDR_ERR_HIP, "internal stream join failed");
   return VDR_OK;

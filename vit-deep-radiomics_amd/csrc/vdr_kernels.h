@@ -132,6 +132,7 @@ struct LnArgs {
   int cls_period;
   // SAM window partition on the OUTPUT rows (input rows are tokens of a g x g grid, row-major)
   int win_ws = 0, win_g = 0;
+  int64_t ldy = 0;  // elements between consecutive output rows (0 = D): column slices of a wider matrix
 };
 hipError_t launch_layernorm(const LnArgs& a, hipStream_t s);
 
@@ -212,6 +213,15 @@ hipError_t launch_cls_rows_stats(const float* cls, const float* pos, void* x, fl
 
 // y[r] = x[imap(r)], bf16 -> bf16 / fp32
 hipError_t launch_gather_rows(const void* x, void* y, int out_bf16, int64_t rows, int D, RowMap imap,
-                              hipStream_t s);
+                              hipStream_t s, int in_f32 = 0, int64_t ldy = 0);
+
+// Mean over the patch rows of each image, of the final-normalised (norm = 1: LayerNorm with gamma / beta, the arithmetic
+// of the LayerNorm kernel) or raw (norm = 0) residual stream: x rows b*ntok + ncls + j, j < n, of `batch` images ->
+// y + b*ldy [D] (bf16 or fp32).  Two deterministic passes, no atomics: fp32 partial sums per fixed chunk of
+// POOL_CHUNK rows into part [batch][ceil(n / POOL_CHUNK)][D], then their sum in chunk order times 1/n.
+constexpr int POOL_CHUNK = 64;
+inline size_t pool_part_bytes(int batch, int n, int D) { return (size_t)batch * ((n + POOL_CHUNK - 1) / POOL_CHUNK) * D * 4; }
+hipError_t launch_pool_rows(const void* x, int in_bf16, int norm, const float* gamma, const float* beta, float eps, int batch,
+                            int ntok, int ncls, int n, int D, float* part, void* y, int out_bf16, int64_t ldy, hipStream_t s);
 
 }  // namespace vdr

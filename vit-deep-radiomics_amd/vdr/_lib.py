@@ -10,7 +10,7 @@ LIB_PATH = os.path.join(_HERE, "libvdr.so")
 
 VDR_F32, VDR_BF16, VDR_F64, VDR_I16, VDR_U8 = 0, 1, 2, 3, 4
 ACT_GELU, ACT_SWIGLU = 0, 1
-OUT_CLS, OUT_DENSE, OUT_PATCH_EMBED, OUT_TOKENS, OUT_ENCODER = 0, 1, 2, 3, 4
+OUT_CLS, OUT_DENSE, OUT_PATCH_EMBED, OUT_TOKENS, OUT_ENCODER, OUT_POOLED = 0, 1, 2, 3, 4, 5
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_SWIGLU = 0, 1, 2, 3
 K_COUNT = 11
 
@@ -32,6 +32,11 @@ class vdr_config(C.Structure):
                 ("ln_fin_fused", C.c_int32)]
 
 
+class vdr_layer_out(C.Structure):
+    _fields_ = [("layer", C.c_int32), ("out_mode", C.c_int32), ("out_dtype", C.c_int32), ("norm", C.c_int32),
+                ("ld", C.c_int64), ("out", C.c_void_p)]
+
+
 # every symbol include/vdr.h declares: name -> (restype, argtypes)
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SYMBOLS = {
@@ -47,6 +52,7 @@ SYMBOLS = {
     "vdr_weight_name": (C.c_char_p, [_P, _I]),
     "vdr_workspace_bytes": (_I, [_P, _I, _I, C.POINTER(C.c_size_t)]),
     "vdr_forward": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, C.c_size_t, _P]),
+    "vdr_forward_layers": (_I, [_P, _P, _I, _I, C.POINTER(vdr_layer_out), _I, _P, C.c_size_t, _P]),
     "vdr_forward_tokens": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _P, C.c_size_t, _P]),
     "vdr_forward_tokens_varlen": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _I, _P, C.c_size_t, _P]),
     "vdr_op_layernorm": (_I, [_P, _I, _P, _I, _P, _P, _L, _I, _F, _P]),

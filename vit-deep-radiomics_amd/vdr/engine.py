@@ -71,6 +71,18 @@ class VdrConfig:
 _DT = {torch.float32: L.VDR_F32, torch.bfloat16: L.VDR_BF16}
 
 
+@dataclass
+class LayerOut:
+    """One output of Engine.forward_layers (vdr_layer_out): the residual stream after block `layer`, through the final
+    norm (norm=True) or raw.  out: a caller-owned tensor to write (CLS / POOLED: a [B, D] view whose rows may be
+    strided, e.g. a column slice of a wider matrix; DENSE / TOKENS: contiguous), or None to allocate one of `dtype`."""
+    layer: int
+    mode: int = L.OUT_CLS
+    dtype: torch.dtype = torch.float32
+    norm: bool = True
+    out: "torch.Tensor | None" = None
+
+
 def _stream_ptr(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
@@ -183,6 +195,53 @@ class Engine:
         L.check(self.lib.vdr_forward(self.h, images.data_ptr(), _DT[images.dtype], B, out.data_ptr(), out_mode,
                                      _DT[out.dtype], ws.data_ptr(), ws.numel(), _stream_ptr(self.device)), self.h)
         return out
+
+    def forward_layers(self, images: torch.Tensor, specs) -> "list[torch.Tensor]":
+        """One forward, several outputs from inside the encoder (vdr_forward_layers): specs is a sequence of LayerOut;
+        returns their tensors in the same order.  Caller-owned outputs are checked as forward_into checks its buffer,
+        nothing is converted or copied."""
+        cfg = self.cfg
+        if images.dim() != 4 or tuple(images.shape[1:]) != (cfg.in_chans, cfg.img, cfg.img):
+            raise ValueError(f"images must be [B,{cfg.in_chans},{cfg.img},{cfg.img}], got {tuple(images.shape)}")
+        if images.dtype not in _DT:
+            images = images.float()
+        images = images.to(self.device).contiguous()
+        B, D = images.shape[0], cfg.dim
+        specs = list(specs)
+        if not specs:
+            raise ValueError("forward_layers needs at least one LayerOut")
+        arr = (L.vdr_layer_out * len(specs))()
+        outs = []
+        for k, sp in enumerate(specs):
+            rows = {L.OUT_CLS: None, L.OUT_POOLED: None, L.OUT_DENSE: cfg.n_patches, L.OUT_TOKENS: cfg.n_tokens}
+            if sp.mode not in rows:
+                raise ValueError(f"specs[{k}]: mode must be OUT_CLS, OUT_DENSE, OUT_TOKENS or OUT_POOLED, got {sp.mode}")
+            shape = (B, D) if rows[sp.mode] is None else (B, rows[sp.mode], D)
+            out = sp.out
+            if out is None:
+                if sp.dtype not in _DT:
+                    raise TypeError(f"specs[{k}]: dtype must be float32 or bfloat16, got {sp.dtype}")
+                out = torch.empty(shape, dtype=sp.dtype, device=self.device)
+            if out.dtype not in _DT:
+                raise TypeError(f"specs[{k}]: out must be float32 or bfloat16, got {out.dtype}")
+            if out.device != self.device:
+                raise ValueError(f"specs[{k}]: out must live on {self.device}")
+            if tuple(out.shape) != shape:
+                raise ValueError(f"specs[{k}]: out must be {shape}, got {tuple(out.shape)}")
+            ld = 0
+            if rows[sp.mode] is None:  # [B, D] rows b*ld apart
+                if out.stride(1) != 1 or (B > 1 and out.stride(0) < D):
+                    raise ValueError(f"specs[{k}]: out rows must be contiguous and at least D = {D} elements apart")
+                ld = out.stride(0) if B > 1 else D
+            elif not out.is_contiguous():
+                raise ValueError(f"specs[{k}]: out must be contiguous")
+            arr[k].layer, arr[k].out_mode, arr[k].out_dtype = int(sp.layer), int(sp.mode), _DT[out.dtype]
+            arr[k].norm, arr[k].ld, arr[k].out = int(bool(sp.norm)), ld, out.data_ptr()
+            outs.append(out)
+        ws = self._workspace(B)
+        L.check(self.lib.vdr_forward_layers(self.h, images.data_ptr(), _DT[images.dtype], B, arr, len(specs), ws.data_ptr(),
+                                            ws.numel(), _stream_ptr(self.device)), self.h)
+        return outs
 
     def forward_tokens(self, tokens: torch.Tensor, out_mode: int = L.OUT_CLS, out_dtype=torch.float32,
                        lengths=None) -> torch.Tensor:

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .engine import Engine, VdrConfig
+from .engine import Engine, LayerOut, VdrConfig
 
 # geometries BASELINE.json names + the two the reference itself loads
 ARCHS = {
@@ -46,6 +46,27 @@ def from_sam_state_dict(sd):
         k = k[len("image_encoder."):].replace(".mlp.lin1.", ".mlp.fc1.").replace(".mlp.lin2.", ".mlp.fc2.")
         out[k] = v
     return out
+
+
+def intermediate_layer_indices(n, depth: int) -> "list[int]":
+    """The blocks DINOv2's get_intermediate_layers returns (DinoVisionTransformer._get_intermediate_layers_not_chunked):
+    an int n means the last n blocks; a sequence means those block indices, returned in block order (the blocks are
+    visited in order and kept when listed), each once.  Anything DINOv2 would fail on is a ValueError here."""
+    if isinstance(n, bool):
+        raise ValueError("n must be an int or a sequence of block indices")
+    if isinstance(n, (int, np.integer)):
+        if not 1 <= int(n) <= depth:
+            raise ValueError(f"n = {n}: the model has {depth} blocks")
+        return list(range(depth - int(n), depth))
+    idx = [int(i) for i in n]
+    if not idx:
+        raise ValueError("n: no block index given")
+    bad = [i for i in idx if not 0 <= i < depth]
+    if bad:
+        raise ValueError(f"block indices {bad} out of range 0..{depth - 1}")
+    if len(set(idx)) != len(idx):
+        raise ValueError(f"block indices {idx} repeat one")
+    return sorted(idx)
 
 
 class VitDescriptorModel:
@@ -89,6 +110,55 @@ class VitDescriptorModel:
 
     def dense_tokens(self, x: torch.Tensor, out_dtype=torch.bfloat16) -> torch.Tensor:
         return self.engine.forward(x, L.OUT_DENSE, out_dtype)
+
+    def _layers_ok(self, what):
+        if self.cfg.window > 0:
+            raise ValueError(f"{what}: the SAM encoder has no final norm to apply to its blocks' output (and a conv neck); "
+                             "intermediate layers are for ViT / DINOv2 models")
+        if not self.cfg.layers:
+            raise ValueError(f"{what}: the model has no transformer blocks")
+
+    def get_intermediate_layers(self, x: torch.Tensor, n=1, reshape: bool = False, return_class_token: bool = False,
+                                norm: bool = True):
+        """DINOv2's DinoVisionTransformer.get_intermediate_layers: the residual stream after the chosen blocks (n: the
+        last n blocks, or a sequence of block indices), through the final norm when norm=True.  Patch tokens [B, n, D]
+        (reshape=True: [B, D, h, w]); with return_class_token a tuple of (patch, cls) pairs, else a tuple of patch
+        tensors.  fp32.  All of them come out of one forward (vdr_forward_layers)."""
+        self._layers_ok("get_intermediate_layers")
+        if return_class_token and not self.cfg.has_cls:
+            raise ValueError("get_intermediate_layers: return_class_token needs a model with a CLS token")
+        blocks = intermediate_layer_indices(n, self.cfg.layers)
+        specs = []
+        for i in blocks:
+            specs.append(LayerOut(i, L.OUT_DENSE, torch.float32, norm))
+            if return_class_token:
+                specs.append(LayerOut(i, L.OUT_CLS, torch.float32, norm))
+        got = self.engine.forward_layers(x, specs)
+        step = 2 if return_class_token else 1
+        patch = got[::step]
+        if reshape:
+            B, g = patch[0].shape[0], self.cfg.img // self.cfg.patch
+            patch = [t.reshape(B, g, g, -1).permute(0, 3, 1, 2).contiguous() for t in patch]
+        if return_class_token:
+            return tuple(zip(patch, got[1::2]))
+        return tuple(patch)
+
+    def linear_probe_features(self, x: torch.Tensor, n_last_blocks: int = 4, avgpool: bool = True) -> torch.Tensor:
+        """DINOv2's linear-probe descriptor (create_linear_input over get_intermediate_layers(x, n_last_blocks,
+        return_class_token=True)): [B, (n_last_blocks + avgpool) * D] fp32, the normalised CLS rows of the last
+        n_last_blocks blocks in block order, then (avgpool) the mean of the last block's normalised patch tokens.  One
+        forward writes every column slice in place; the patch tokens are never materialised."""
+        self._layers_ok("linear_probe_features")
+        if not self.cfg.has_cls:
+            raise ValueError("linear_probe_features: needs a model with a CLS token")
+        blocks = intermediate_layer_indices(int(n_last_blocks), self.cfg.layers)
+        B, D = x.shape[0], self.cfg.dim
+        out = torch.empty((B, (len(blocks) + int(bool(avgpool))) * D), dtype=torch.float32, device=self.device)
+        specs = [LayerOut(i, L.OUT_CLS, out=out[:, k * D:(k + 1) * D]) for k, i in enumerate(blocks)]
+        if avgpool:
+            specs.append(LayerOut(blocks[-1], L.OUT_POOLED, out=out[:, len(blocks) * D:]))
+        self.engine.forward_layers(x, specs)
+        return out
 
     def __call__(self, x):
         return self.image_encoder(x) if self.cfg.window > 0 else self.forward_features(x)
