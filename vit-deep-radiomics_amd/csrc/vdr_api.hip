@@ -448,13 +448,36 @@ int resolve(vdr_model* m) {
   return VDR_OK;
 }
 
-// every GEMM of the forward goes through here: the weight is swapped for its interleaved copy
-hipError_t launch_gemm_w(vdr_model* m, GemmArgs& g, int epi, int variant, hipStream_t s) {
+// one linear C = epilogue(A . W^T): A [M, K], W [N, K], C [M, N] (EPI_SWIGLU: [M, N / 2]), dense rows, the residual (if
+// any) laid out as C; callers set the rest (bias, resid, gamma, strides, row maps, ...) by field
+GemmArgs linear(const void* A, const void* W, void* C, int64_t M, int N, int K, int epi) {
+  GemmArgs g{};
+  g.A = A;
+  g.W = W;
+  g.C = C;
+  g.M = M;
+  g.N = N;
+  g.K = K;
+  g.lda = K;
+  g.ldw = K;
+  g.ldc = epi == EPI_SWIGLU ? N / 2 : N;
+  g.ldr = g.ldc;
+  g.omap = identity_map();
+  return g;
+}
+
+// the weight's pair-interleaved copy, when resolve() made one
+void use_interleaved(const vdr_model* m, GemmArgs& g) {
   auto it = m->w_il.find(g.W);
   if (it != m->w_il.end()) {
     g.W = it->second;
     g.w_interleaved = 1;
   }
+}
+
+// every GEMM of the forward goes through here: the weight is swapped for its interleaved copy
+hipError_t launch_gemm_w(vdr_model* m, GemmArgs& g, int epi, int variant, hipStream_t s) {
+  use_interleaved(m, g);
   return launch_gemm(g, epi, variant, s);
 }
 
@@ -573,14 +596,16 @@ int join_streams(vdr_model* m, hipStream_t caller) {
 }
 
 // ---- profiler -----------------------------------------------------------------------------------
-struct Scope {
+struct Scope {  // (m = nullptr: an op entry point, nothing is booked)
   vdr_model* m;
   hipStream_t s;
   ProfEvent e;
   bool on;
   Scope(vdr_model* m_, hipStream_t s_, int cls, double flops, double bytes) : m(m_), s(s_) {
+    on = m && m->prof;
+    if (!on) return;
     if (m->prof_as >= 0) cls = m->prof_as;  // (block_tail_cls: its small launches are one class of their own)
-    on = m->prof && ((m->prof_mask >> cls) & 1u);
+    on = (m->prof_mask >> cls) & 1u;
     if (!on) return;
     if (!m->ev_free.empty()) {
       e = m->ev_free.back();
@@ -601,6 +626,15 @@ struct Scope {
     m->ev_used.push_back(e);
   }
 };
+
+// tile-variant families of launch_gemm (gemm.hip, gemm_ring4.hip, gemm_8p.hip)
+bool ring3_variant(int v) { return v >= 22 && v <= 24; }      // ring3: 128x256, 256x256, 128x128 tiles
+constexpr int RING3K_VARIANT = 25;                            // ring3k: 128x128, the K loop split across two wave groups
+bool ring4_variant(int v) { return v >= 26 && v <= 29; }      // ring4: 128x256, 256x256, 128x128, 64x128 tiles
+bool ring4_big_variant(int v) { return v >= 26 && v <= 28; }  //   its tiles of 128 rows and more
+constexpr int VARIANT_8P = 31;                                // 8-phase: 256x256, one persistent workgroup per CU
+// the consumers of the LayerNorm fold that finalise the producers' partials themselves (GemmArgs::ln_cpart)
+bool ln_cpart_variant(int v) { return ring3_variant(v) || ring4_big_variant(v); }
 
 // tile configuration per GEMM class; VDR_GEMM_VARIANT overrides all of them (tuning aid)
 int gemm_variant_for(int cls, int64_t M = 1 << 30, int N = 1 << 30) {
@@ -635,8 +669,30 @@ int gemm_variant_for(int cls, int64_t M = 1 << 30, int N = 1 << 30) {
 
 // im2col-free patchify (GemmArgs::patch_p): bf16 NCHW images, 16-byte aligned, patch side 8 / 16 / 32, a ring4 tile variant
 bool patch_gather_ok(int in_dtype, int patch, int variant, const void* images) {
-  return in_dtype == VDR_BF16 && (patch == 8 || patch == 16 || patch == 32) && variant >= 26 && variant <= 28 &&
+  return in_dtype == VDR_BF16 && (patch == 8 || patch == 16 || patch == 32) && ring4_big_variant(variant) &&
          ((uintptr_t)images & 15) == 0;
+}
+
+// The patch-embedding GEMM of `batch` images [batch, chans, img, img] -> C rows omap(r), r < batch * (img / p)^2: bf16
+// images with a patch side of 8 / 16 / 32 are gathered 16-byte runs at a time by the GEMM's operand loader straight from
+// NCHW (ring4 tile variants: no col buffer, no im2col launch); fp32 images (the loader is an LDS-DMA: it cannot convert)
+// and p = 14 (runs of 14 pixels are not 16-byte chunks) go through im2col into `col`, launched here.  Fills *g (the
+// caller adds bias, pos, omap and what else differs) and *variant.
+hipError_t patch_gemm(vdr_model* m, hipStream_t s, const void* images, int in_dtype, void* col, const void* W, void* C,
+                      int batch, int chans, int img, int p, int D, GemmArgs* g, int* variant) {
+  const int n = (img / p) * (img / p), Kp = round_up(chans * p * p, 64);
+  *variant = gemm_variant_for(VDR_K_GEMM_PATCH, (int64_t)batch * n, D);
+  const bool fused = patch_gather_ok(in_dtype, p, *variant, images);
+  *g = linear(fused ? images : col, W, C, (int64_t)batch * n, D, Kp, EPI_PATCH);
+  if (fused) {
+    g->patch_p = p;
+    g->patch_g = img / p;
+    g->patch_C = chans;
+    return hipSuccess;
+  }
+  const size_t in_es = in_dtype == VDR_BF16 ? 2 : 4;
+  Scope sc(m, s, VDR_K_IM2COL, 0.0, (double)batch * chans * img * img * in_es + 2.0 * batch * n * Kp);
+  return launch_im2col(images, in_dtype == VDR_BF16, col, batch, chans, img, p, Kp, s);
 }
 
 #ifndef VDR_GEMM_8P_DEFAULT
@@ -676,12 +732,15 @@ void set_ln_fold(GemmArgs& g, const LnFold& ln) {
 
 // which GEMM classes take tile variant 31 when the launch is eligible (gemm_8p_eligible): measured per class in the
 // forward; tuning builds: VDR_GEMM_8P = bit mask (1 qkv, 2 fc1), -1 = the default
-bool use_8p(const vdr_model* m, int cls) {
-  (void)m;
+bool use_8p(int cls) {
   VDR_KNOB int mask_env = env_int("VDR_GEMM_8P", -1);
   const int mask = mask_env >= 0 ? mask_env : VDR_GEMM_8P_DEFAULT;
   return (cls == VDR_K_GEMM_QKV && (mask & 1)) || (cls == VDR_K_GEMM_FC1 && (mask & 2));
 }
+
+// whether tile variant 31 takes a launch of this class and shape: gemm() asks this and then gemm_8p_eligible of the
+// launch itself; ln_stats_in_gemm asks this alone
+bool wants_8p(int cls, int64_t M, int N) { return use_8p(cls) && gemm_8p_shape_ok(M, N); }
 
 // Where the (sum, sumsq) partials of the residual stream become (mean, rstd): inside the consuming GEMM when it runs
 // a ring3 variant (22-24; every workgroup finalises its own rows in LDS while its ring fills: no launch), otherwise by
@@ -693,10 +752,11 @@ bool use_8p(const vdr_model* m, int cls) {
 bool ln_stats_in_gemm(int cls, int64_t M, int N, int groups) {
   VDR_KNOB int mode = env_int("VDR_LN_IN_GEMM", -1);
   const int v = gemm_variant_for(cls, M, N);
-  if (mode == 0 || groups > 16 || v < 22 || v == 25 || v > 28) return false;
+  if (mode == 0 || groups > 16 || !ln_cpart_variant(v)) return false;
   if (mode == 1) return true;
   // (a launch the 8-phase kernel takes reads finalised statistics: it has no in-GEMM finalisation)
-  if (use_8p(nullptr, cls) && gemm_8p_shape_ok(M, N)) return false;
+  // (known quirk: predicted from the shape alone, so a launch variant 31 refuses -- SwiGLU fc1 -- gets no finalisation either)
+  if (wants_8p(cls, M, N)) return false;
   return ((M + 127) / 128) * ((N + 255) / 256) <= 2048;
 }
 
@@ -722,55 +782,28 @@ int ln_consumer(vdr_model* m, hipStream_t s, int cls, int64_t M, int N, int D, c
   return VDR_OK;
 }
 
-int gemm(vdr_model* m, hipStream_t s, int cls, const void* A, const void* W, const float* bias, const void* resid,
-         const float* gamma, void* C, int64_t M, int N, int K, int ldc, int epi, const LnFold& ln = LnFold(),
-         int64_t lda = 0, int64_t ldr = 0,  // lda / ldr: row strides of A / resid when they are not K / ldc
-         const float* resid32 = nullptr, float* C32 = nullptr,  // resid_fp32: the fp32 residual stream in / out (same strides)
-         int64_t a_rows = 0) {  // rows of A / of the fold's row statistics that are readable (workspace buffers: Mp); 0 = unknown
-  GemmArgs g{};
-  g.A = A;
-  g.W = W;
-  g.bias = bias;
-  g.resid = resid;
-  g.gamma = gamma;
-  g.C = C;
-  g.M = M;
-  g.N = N;
-  g.K = K;
-  g.lda = lda ? lda : K;
-  g.ldw = K;
-  g.ldc = ldc;
-  g.ldr = ldr ? ldr : ldc;
-  g.omap = identity_map();
-  g.resid32 = resid32;
-  g.C32 = C32;
-  LnFold lnf = ln;
-  lnf.fin_cnt = nullptr;
-  set_ln_fold(g, lnf);
-  const double outw = epi == EPI_SWIGLU ? N / 2 : N;
-  Scope sc(m, s, cls, 2.0 * M * N * K,
-           2.0 * ((double)M * K + (double)N * K + (double)M * outw * (resid32 ? 5 : resid ? 2 : 1)));  // (fp32 in + fp32 out + bf16 out)
-  // Tile variant 31 (gemm_8p.hip) for the write-once linears of large launches (plain weight layout).  The workspace
-  // buffers A points into hold Mp >= M + 256 rows, so a ragged last 256-row tile reads rows that exist; they are never stored.
-  if (use_8p(m, cls) && lda == 0 && a_rows > 0) {
-    g.a_rows = a_rows;
-    if (gemm_8p_eligible(g, epi)) {
-      VDR_TRY(launch_gemm(g, epi, 31, s), "gemm_8p");
-      return VDR_OK;
-    }
-  }
-  const int variant = gemm_variant_for(cls, g.M, N);
+// Every GEMM of the forward but the SAM out-projection: g is the launch as linear() and the caller describe it (a_rows:
+// rows of A / of the fold's row statistics that are readable, the workspace's Mp; 0 = unknown), ln the LayerNorm fold.
+// Books the launch, picks the tile variant and, for a producer of partials, who finalises them.
+int gemm(vdr_model* m, hipStream_t s, int cls, GemmArgs g, int epi, const LnFold& ln = LnFold()) {
+  const int variant = gemm_variant_for(cls, g.M, g.N);
   // a producer of LayerNorm partials on a ring4 tile variant also finalises them (finalize_rows_if_last): the consumer's
   // ln_finalize launch is not needed then (ln_consumer takes m->stats_fresh)
-  bool fin = false;
-  if (ln.fin_stats && ln.part && m->fin_cnt && m->cfg.ln_fin_fused && variant >= 26 && variant <= 29 && epi == EPI_BIAS_RESID &&
-      (g.M + 63) / 64 <= FIN_ROWS) {
-    lnf.fin_cnt = m->fin_cnt + (size_t)m->cur_aux * FIN_ROWS;
-    lnf.eps = m->cfg.ln_eps;
-    set_ln_fold(g, lnf);
-    fin = true;
-  }
-  VDR_TRY(launch_gemm_w(m, g, epi, variant, s), "gemm");
+  const bool fin = ln.fin_stats && ln.part && m->fin_cnt && m->cfg.ln_fin_fused && ring4_variant(variant) && epi == EPI_BIAS_RESID &&
+                   (g.M + 63) / 64 <= FIN_ROWS;
+  LnFold lnf = ln;
+  lnf.fin_cnt = fin ? m->fin_cnt + (size_t)m->cur_aux * FIN_ROWS : nullptr;
+  if (fin) lnf.eps = m->cfg.ln_eps;
+  set_ln_fold(g, lnf);
+  const double outw = epi == EPI_SWIGLU ? g.N / 2 : g.N;
+  Scope sc(m, s, cls, 2.0 * g.M * g.N * g.K,
+           2.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * outw * (g.resid32 ? 5 : g.resid ? 2 : 1)));  // (fp32 in + fp32 out + bf16 out)
+  // Tile variant 31 (gemm_8p.hip) for the write-once linears of large launches (plain weight layout).  The workspace
+  // buffers A points into hold Mp >= M + 256 rows, so a ragged last 256-row tile reads rows that exist; they are never stored.
+  if (g.lda == g.K && g.a_rows > 0 && wants_8p(cls, g.M, g.N) && gemm_8p_eligible(g, epi))
+    VDR_TRY(launch_gemm(g, epi, VARIANT_8P, s), "gemm_8p");
+  else
+    VDR_TRY(launch_gemm_w(m, g, epi, variant, s), "gemm");
   if (ln.part) m->stats_fresh = fin;
   return VDR_OK;
 }
@@ -810,36 +843,18 @@ int mx_variant_for(int cls, int64_t M, int N) {
 
 // one linear on the block-scaled fp8 MFMA: MX operands (aq, as) x (wq, wsc); cs != NULL -> MX output
 int gemm_mx(vdr_model* m, hipStream_t s, int cls, const void* aq, const void* as, const void* wq, const void* wsc,
-            const float* bias, const void* resid, const float* gamma, void* C, void* cs, int64_t M, int N, int K, int ldc,
-            int epi) {
-  GemmArgs g{};
-  g.A = aq;
+            const float* bias, const void* resid, const float* gamma, void* C, void* cs, int64_t M, int N, int K, int epi) {
+  GemmArgs g = linear(aq, wq, C, M, N, K, epi);
   g.a_scale = as;
-  g.W = wq;
   g.w_scale = wsc;
   g.bias = bias;
   g.resid = resid;
   g.gamma = gamma;
-  g.C = C;
   g.c_scale = cs;
-  g.M = M;
-  g.N = N;
-  g.K = K;
-  g.lda = K;
-  g.ldw = K;
-  g.ldc = ldc;
-  g.ldr = ldc;
-  g.omap = identity_map();
   const double outb = cs ? 1.0 : 2.0;
-  Scope sc(m, s, cls, 2.0 * M * N * K, (double)M * K + (double)N * K + (double)M * ldc * (resid ? 2 * outb : outb));
-  {
-    VDR_KNOB int packed = env_int("VDR_MX_PACKED", 1);  // (tuning builds: 0 = the row-major payload, for A/B)
-    auto it = m->w_il.find(g.W);
-    if (packed && it != m->w_il.end()) {
-      g.W = it->second;
-      g.w_interleaved = 1;
-    }
-  }
+  Scope sc(m, s, cls, 2.0 * M * N * K, (double)M * K + (double)N * K + (double)M * g.ldc * (resid ? 2 * outb : outb));
+  VDR_KNOB int packed = env_int("VDR_MX_PACKED", 1);  // (tuning builds: 0 = the row-major payload, for A/B)
+  if (packed) use_interleaved(m, g);
   VDR_TRY(launch_gemm_mx(g, epi, mx_variant_for(cls, M, N), s), "gemm_mx");
   return VDR_OK;
 }
@@ -866,65 +881,74 @@ int cls_mlp_bf16(vdr_model* m, hipStream_t ax, const Carve& w, const LayerW& L, 
   BookAs book(m);
   const vdr_config& c = m->cfg;
   const int D = c.dim, F = c.mlp_hidden;
-  const bool sw = c.act == VDR_ACT_SWIGLU;
-  const int64_t stride = (int64_t)ntok * D;
+  const int e1 = c.act == VDR_ACT_SWIGLU ? EPI_SWIGLU : EPI_BIAS_GELU;
   int rc;
   if ((rc = layernorm(m, ax, VDR_K_LAYERNORM, w.x, 1, w.cls_h, 1, L.n2w, L.n2b, mb, RowMap{1, ntok, 0}))) return rc;
-  if ((rc = gemm(m, ax, VDR_K_GEMM_FC1, w.cls_h, L.w1, L.b1, nullptr, nullptr, w.cls_u, mb, sw ? 2 * F : F, D, F,
-                 sw ? EPI_SWIGLU : EPI_BIAS_GELU)))
-    return rc;
-  return gemm(m, ax, VDR_K_GEMM_FC2, w.cls_u, L.w2, L.b2, w.x, L.ls2, w.cls_x, mb, D, F, D, EPI_BIAS_RESID, LnFold(), 0, stride);
+  GemmArgs fc1 = linear(w.cls_h, L.w1, w.cls_u, mb, e1 == EPI_SWIGLU ? 2 * F : F, D, e1);
+  fc1.bias = L.b1;
+  if ((rc = gemm(m, ax, VDR_K_GEMM_FC1, fc1, e1))) return rc;
+  GemmArgs fc2 = linear(w.cls_u, L.w2, w.cls_x, mb, D, F, EPI_BIAS_RESID);
+  fc2.bias = L.b2;
+  fc2.resid = w.x;
+  fc2.gamma = L.ls2;
+  fc2.ldr = (int64_t)ntok * D;
+  return gemm(m, ax, VDR_K_GEMM_FC2, fc2, EPI_BIAS_RESID);
 }
 
 int block_tail_cls(vdr_model* m, hipStream_t s, const Carve& w, const LayerW& L, int mb, int ntok) {
   BookAs book(m);
   const vdr_config& c = m->cfg;
   const int D = c.dim, F = c.mlp_hidden;
-  const bool sw = c.act == VDR_ACT_SWIGLU;
-  const int64_t stride = (int64_t)ntok * D;
+  const int e1 = c.act == VDR_ACT_SWIGLU ? EPI_SWIGLU : EPI_BIAS_GELU, N1 = e1 == EPI_SWIGLU ? 2 * F : F;
   char* xc = w.h;  // [mb, D] bf16
+  // the out-projection gathers the CLS rows: A and the residual read with a row stride of ntok * D
+  GemmArgs proj = linear(w.o, L.wproj, xc, mb, D, D, EPI_BIAS_RESID);
+  proj.bias = L.bproj;
+  proj.resid = w.x;
+  proj.gamma = L.ls1;
+  proj.lda = proj.ldr = (int64_t)ntok * D;
   int rc;
   if (c.fp8 && !(c.fp8_cls_bf16 && c.has_cls)) {  // (fp8_cls_bf16: the CLS rows' MLP on the bf16 weights -- the explicit-LayerNorm branch below)
     // MX-fp8 linears: norm2 of the compact rows goes out as MX-fp8 behind them in w.h (payload) / w.hs (scales: the
     // layouts depend only on the row count each launch is given), fc1 / fc2 on the block-scaled MFMA at M = mb
     char* hq = w.h + (size_t)round_up(mb, 256) * D * 2;
-    const int N1 = sw ? 2 * F : F;
-    if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, w.o, L.wproj, L.bproj, w.x, L.ls1, xc, mb, D, D, D, EPI_BIAS_RESID, LnFold(), stride, stride)))
-      return rc;
+    if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, proj, EPI_BIAS_RESID))) return rc;
     {
       Scope sc(m, s, VDR_K_LAYERNORM, 0.0, (double)mb * D * 3);
       VDR_TRY(launch_ln_mx(xc, L.n2w, L.n2b, c.ln_eps, mb, D, hq, w.hs, s), "layernorm_mx");
     }
-    if ((rc = gemm_mx(m, s, VDR_K_GEMM_FC1, hq, w.hs, L.w1_q, L.w1_s, L.b1, nullptr, nullptr, w.u, w.us, mb, N1, D, F,
-                      sw ? EPI_SWIGLU : EPI_BIAS_GELU)))
-      return rc;
-    return gemm_mx(m, s, VDR_K_GEMM_FC2, w.u, w.us, L.w2_q, L.w2_s, L.b2, xc, L.ls2, xc, nullptr, mb, D, F, D, EPI_BIAS_RESID);
+    if ((rc = gemm_mx(m, s, VDR_K_GEMM_FC1, hq, w.hs, L.w1_q, L.w1_s, L.b1, nullptr, nullptr, w.u, w.us, mb, N1, D, e1))) return rc;
+    return gemm_mx(m, s, VDR_K_GEMM_FC2, w.u, w.us, L.w2_q, L.w2_s, L.b2, xc, L.ls2, xc, nullptr, mb, D, F, EPI_BIAS_RESID);
   }
-  const float* r32 = w.x32;  // resid_fp32: the CLS rows' fp32 residual comes from x32 (strided) and stays in xc32 (compact)
-  float* c32 = w.x32 ? w.xc32 : nullptr;
+  proj.resid32 = w.x32;  // resid_fp32: the CLS rows' fp32 residual comes from x32 (strided) and stays in xc32 (compact)
+  proj.C32 = w.x32 ? w.xc32 : nullptr;
   if (m->ln_fuse) {
     LnFold prod, cons;
     prod.part = w.part;
     prod.part_stride = w.Mp;
     prod.fin_stats = w.stats;
-    if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, w.o, L.wproj, L.bproj, w.x, L.ls1, xc, mb, D, D, D, EPI_BIAS_RESID, prod, stride, stride, r32, c32)))
-      return rc;
-    if ((rc = ln_consumer(m, s, VDR_K_GEMM_FC1, mb, sw ? 2 * F : F, D, w, &cons))) return rc;
+    if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, proj, EPI_BIAS_RESID, prod))) return rc;
+    if ((rc = ln_consumer(m, s, VDR_K_GEMM_FC1, mb, N1, D, w, &cons))) return rc;
     cons.colsum = L.s1;
-    if ((rc = gemm(m, s, VDR_K_GEMM_FC1, xc, L.w1_f, L.t1, nullptr, nullptr, w.u, mb, sw ? 2 * F : F, D, F,
-                   sw ? EPI_SWIGLU : EPI_BIAS_GELU, cons)))
-      return rc;
+    GemmArgs fc1 = linear(xc, L.w1_f, w.u, mb, N1, D, e1);
+    fc1.bias = L.t1;
+    if ((rc = gemm(m, s, VDR_K_GEMM_FC1, fc1, e1, cons))) return rc;
   } else {
     char* hc = w.h + (size_t)round_up(mb, 256) * D * 2;  // norm2 of the compact rows (w.h holds Mp >= mb * ntok + 256 rows)
-    if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, w.o, L.wproj, L.bproj, w.x, L.ls1, xc, mb, D, D, D, EPI_BIAS_RESID, LnFold(), stride, stride, r32, c32)))
+    if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, proj, EPI_BIAS_RESID))) return rc;
+    const bool f32 = proj.C32 != nullptr;
+    if ((rc = layernorm(m, s, VDR_K_LAYERNORM, f32 ? (const void*)proj.C32 : (const void*)xc, !f32, hc, 1, L.n2w, L.n2b, mb, identity_map())))
       return rc;
-    if ((rc = layernorm(m, s, VDR_K_LAYERNORM, c32 ? (const void*)c32 : (const void*)xc, c32 ? 0 : 1, hc, 1, L.n2w, L.n2b, mb, identity_map())))
-      return rc;
-    if ((rc = gemm(m, s, VDR_K_GEMM_FC1, hc, L.w1, L.b1, nullptr, nullptr, w.u, mb, sw ? 2 * F : F, D, F,
-                   sw ? EPI_SWIGLU : EPI_BIAS_GELU)))
-      return rc;
+    GemmArgs fc1 = linear(hc, L.w1, w.u, mb, N1, D, e1);
+    fc1.bias = L.b1;
+    if ((rc = gemm(m, s, VDR_K_GEMM_FC1, fc1, e1))) return rc;
   }
-  return gemm(m, s, VDR_K_GEMM_FC2, w.u, L.w2, L.b2, xc, L.ls2, xc, mb, D, F, D, EPI_BIAS_RESID, LnFold(), 0, 0, c32, c32);
+  GemmArgs fc2 = linear(w.u, L.w2, xc, mb, D, F, EPI_BIAS_RESID);
+  fc2.bias = L.b2;
+  fc2.resid = xc;
+  fc2.gamma = L.ls2;
+  fc2.resid32 = fc2.C32 = proj.C32;
+  return gemm(m, s, VDR_K_GEMM_FC2, fc2, EPI_BIAS_RESID);
 }
 
 // vdr_forward_layers: the outputs to write after each block, and the first image of the micro-batch being run
@@ -934,54 +958,49 @@ struct EmitList {
   int b0 = 0;
 };
 
-// Writes every output requested for block i of this micro-batch, on its stream, right after the block's last residual
-// GEMM (and, fp8_cls_bf16, after the copy that puts the CLS rows' bf16 MLP result into w.x: it is enqueued on `s` before
-// this call, so stream order puts these reads behind it).  norm = 1 goes through the final-LayerNorm launch of emit()
-// with the same row maps -- the bits of a model truncated to i + 1 blocks; compact: block i ran its CLS rows only
-// (block_tail_cls) and they sit in w.h / w.xc32.  Every launch is booked as VDR_K_FINAL_LN.
-int emit_layer(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, const EmitList& el, int i, bool compact) {
+// Writes one output for images b0 .. b0 + mb - 1 from the residual stream of their micro-batch, on its stream: the rows
+// out_mode selects, through the model's final LayerNorm (norm = 1) or raw, read from the stream's fp32 master copy when
+// there is one (resid_fp32), else from its bf16 rows.  vdr_forward and vdr_forward_tokens write their output after the
+// last block (norm = pre_ln); vdr_forward_layers writes each of block i's right after the block's last residual GEMM (and,
+// fp8_cls_bf16, after the copy that puts the CLS rows' bf16 MLP result into w.x: it is enqueued on `s` before this call,
+// so stream order puts these reads behind it) -- the bits of a model truncated to i + 1 blocks.  compact: the block ran
+// its CLS rows only (block_tail_cls) and they sit in w.h / w.xc32.  Every launch is booked as VDR_K_FINAL_LN.
+int write_output(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, const vdr_layer_out& o, int b0, bool compact) {
   const vdr_config& c = m->cfg;
   const int D = c.dim, ncls = c.has_cls ? 1 : 0, n = ntok - ncls;
-  for (const vdr_layer_out* o : el.at[i]) {
-    const int ob = o->out_dtype == VDR_BF16;
-    const size_t es = ob ? 2 : 4;
-    // the stream: its fp32 master copy when there is one (resid_fp32), else the bf16 rows
-    const bool f32 = compact ? w.xc32 != nullptr : w.x32 != nullptr;
-    const void* src = compact ? (f32 ? (const void*)w.xc32 : (const void*)w.h) : (f32 ? (const void*)w.x32 : (const void*)w.x);
-    if (o->out_mode == VDR_OUT_POOLED) {
-      const int64_t ld = o->ld ? o->ld : D;
-      char* dst = (char*)o->out + (size_t)el.b0 * ld * es;
-      if (pool_part_bytes(mb, n, D) > (size_t)w.Mp * c.mlp_hidden * 2)
-        return fail(m, VDR_ERR_UNSUPPORTED, "pooled output: partial sums do not fit the MLP activation buffer");
-      Scope sc(m, s, VDR_K_FINAL_LN, 0.0, (double)mb * n * D * (f32 ? 4 : 2) + (double)mb * D * es);
-      // (the partial sums go to the fc1 activation w.u: dead from fc2 of block i to fc1 of block i + 1)
-      VDR_TRY(launch_pool_rows(src, !f32, o->norm, m->normw, m->normb, c.ln_eps, mb, ntok, ncls, n, D, (float*)w.u, dst, ob, ld, s),
-              "pooled rows");
-      continue;
-    }
-    RowMap im = identity_map();
-    int64_t rows = mb, ld = 0;
-    char* dst;
-    if (o->out_mode == VDR_OUT_CLS) {
-      if (!compact) im = RowMap{1, ntok, 0};
-      ld = o->ld ? o->ld : D;
-      dst = (char*)o->out + (size_t)el.b0 * ld * es;
-    } else if (o->out_mode == VDR_OUT_DENSE) {
-      im = RowMap{n, ntok, ncls};
-      rows = (int64_t)mb * n;
-      dst = (char*)o->out + (size_t)el.b0 * n * D * es;
-    } else {
-      rows = (int64_t)mb * ntok;
-      dst = (char*)o->out + (size_t)el.b0 * ntok * D * es;
-    }
-    int rc;
-    if (o->norm) {
-      if ((rc = layernorm(m, s, VDR_K_FINAL_LN, src, !f32, dst, ob, m->normw, m->normb, rows, im, nullptr, 0, 0, ld))) return rc;
-    } else {
-      Scope sc(m, s, VDR_K_FINAL_LN, 0.0, (double)rows * D * ((f32 ? 4 : 2) + es));
-      VDR_TRY(launch_gather_rows(src, dst, ob, rows, D, im, s, f32, ld), "gather_rows");
-    }
+  const int ob = o.out_dtype == VDR_BF16;
+  const size_t es = ob ? 2 : 4;
+  const bool f32 = compact ? w.xc32 != nullptr : w.x32 != nullptr;
+  const void* src = compact ? (f32 ? (const void*)w.xc32 : (const void*)w.h) : (f32 ? (const void*)w.x32 : (const void*)w.x);
+  if (o.out_mode == VDR_OUT_POOLED) {
+    const int64_t ld = o.ld ? o.ld : D;
+    char* dst = (char*)o.out + (size_t)b0 * ld * es;
+    if (pool_part_bytes(mb, n, D) > (size_t)w.Mp * c.mlp_hidden * 2)
+      return fail(m, VDR_ERR_UNSUPPORTED, "pooled output: partial sums do not fit the MLP activation buffer");
+    Scope sc(m, s, VDR_K_FINAL_LN, 0.0, (double)mb * n * D * (f32 ? 4 : 2) + (double)mb * D * es);
+    // (the partial sums go to the fc1 activation w.u: dead from fc2 of block i to fc1 of block i + 1)
+    VDR_TRY(launch_pool_rows(src, !f32, o.norm, m->normw, m->normb, c.ln_eps, mb, ntok, ncls, n, D, (float*)w.u, dst, ob, ld, s),
+            "pooled rows");
+    return VDR_OK;
   }
+  RowMap im = identity_map();
+  int64_t rows = mb, ld = 0;
+  char* dst;
+  if (o.out_mode == VDR_OUT_CLS) {
+    if (!compact) im = RowMap{1, ntok, 0};
+    ld = o.ld ? o.ld : D;
+    dst = (char*)o.out + (size_t)b0 * ld * es;
+  } else if (o.out_mode == VDR_OUT_DENSE) {
+    im = RowMap{n, ntok, ncls};
+    rows = (int64_t)mb * n;
+    dst = (char*)o.out + (size_t)b0 * n * D * es;
+  } else {
+    rows = (int64_t)mb * ntok;
+    dst = (char*)o.out + (size_t)b0 * ntok * D * es;
+  }
+  if (o.norm) return layernorm(m, s, VDR_K_FINAL_LN, src, !f32, dst, ob, m->normw, m->normb, rows, im, nullptr, 0, 0, ld);
+  Scope sc(m, s, VDR_K_FINAL_LN, 0.0, (double)rows * D * ((f32 ? 4 : 2) + es));
+  VDR_TRY(launch_gather_rows(src, dst, ob, rows, D, im, s, f32, ld), "gather_rows");
   return VDR_OK;
 }
 
@@ -992,7 +1011,7 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
   const vdr_config& c = m->cfg;
   const int D = c.dim, F = c.mlp_hidden, H = c.heads;
   const int64_t M = (int64_t)mb * ntok;
-  const bool sw = c.act == VDR_ACT_SWIGLU;
+  const int e1 = c.act == VDR_ACT_SWIGLU ? EPI_SWIGLU : EPI_BIAS_GELU, N1 = e1 == EPI_SWIGLU ? 2 * F : F;
   int rc;
   if (compact) *compact = false;
   // (post-LN blocks keep every row: their last operation is a LayerNorm over the block's own output, also row-wise, but
@@ -1000,12 +1019,28 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
   const int nl = el ? el->last + 1 : c.layers;
   const int tail_at = (cls_tail && compact && c.pre_ln && !c.full_last_block && ntok > 1) ? nl - 1 : -1;
   // (a block's outputs; the tail's CLS rows are compact)
-  auto after = [&](int i, bool cmp) { return el ? emit_layer(m, s, w, mb, ntok, *el, i, cmp) : (int)VDR_OK; };
+  auto after = [&](int i, bool cmp) {
+    if (el)
+      for (const vdr_layer_out* o : el->at[i])
+        if (int e = write_output(m, s, w, mb, ntok, *o, el->b0, cmp)) return e;
+    return (int)VDR_OK;
+  };
+  auto attention = [&]() {
+    Scope sc(m, s, VDR_K_ATTENTION, 4.0 * (double)ntok * ntok * D * mb, 2.0 * (double)M * 4 * D);
+    VDR_KNOB int attn_variant = env_int("VDR_ATTN_VARIANT", 0);  // (tuning builds)
+    VDR_TRY(launch_attention(w.qkv, w.o, mb, ntok, H, attn_variant, s, nullptr, lens, len_add, D / H), "attention");
+    return (int)VDR_OK;
+  };
+  // block i == tail_at ends after its attention: the rest of it on the CLS rows, then its outputs
+  auto cls_tail_exit = [&](int i, const LayerW& L) {
+    *compact = true;
+    if (int e = block_tail_cls(m, s, w, L, mb, ntok)) return e;
+    return after(i, true);
+  };
   if (c.fp8) {
     // BASELINE config 5: qkv / fc1 / fc2 on the block-scaled fp8 MFMA.  LayerNorm writes its output as MX-fp8
     // (the qkv / fc1 operand), the attention kernel and the fc1 epilogue write theirs as MX-fp8 (the proj / fc2
     // operands); the residual stream and the attention arithmetic stay bf16 / fp32.
-    const int N1 = sw ? 2 * F : F;
     // vdr_config.fp8_cls_bf16 (image models with a CLS token; not the variable-length token path)
     const int ai = m->cur_aux;
     const bool cls_bf16 = c.fp8_cls_bf16 && c.has_cls && c.patch && ntok > 1 && !lens && ai < (int)m->aux.size() && w.cls_x;
@@ -1015,21 +1050,16 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
         Scope sc(m, s, VDR_K_LAYERNORM, 0.0, (double)M * D * 3);
         VDR_TRY(launch_ln_mx(w.x, L.n1w, L.n1b, c.ln_eps, M, D, w.h, w.hs, s), "layernorm_mx");
       }
-      if ((rc = gemm_mx(m, s, VDR_K_GEMM_QKV, w.h, w.hs, L.qkv_q, L.qkv_s, L.bqkv, nullptr, nullptr, w.qkv, nullptr, M, 3 * D,
-                        D, 3 * D, EPI_BIAS)))
+      if ((rc = gemm_mx(m, s, VDR_K_GEMM_QKV, w.h, w.hs, L.qkv_q, L.qkv_s, L.bqkv, nullptr, nullptr, w.qkv, nullptr, M, 3 * D, D, EPI_BIAS)))
         return rc;
-      {
-        Scope sc(m, s, VDR_K_ATTENTION, 4.0 * (double)ntok * ntok * D * mb, 2.0 * (double)M * 4 * D);
-        VDR_KNOB int attn_variant = env_int("VDR_ATTN_VARIANT", 0);  // (tuning builds)
-        VDR_TRY(launch_attention(w.qkv, w.o, mb, ntok, H, attn_variant, s, nullptr, lens, len_add, D / H), "attention");
-      }
-      if (i == tail_at) {
-        *compact = true;
-        if ((rc = block_tail_cls(m, s, w, L, mb, ntok))) return rc;
-        return after(i, true);
-      }
+      if ((rc = attention())) return rc;
+      if (i == tail_at) return cls_tail_exit(i, L);
       // the out-projection stays bf16: quantising it too measured 0.987 row cosine at 40 blocks (gate 0.99)
-      if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, w.o, L.wproj, L.bproj, w.x, L.ls1, w.x, M, D, D, D, EPI_BIAS_RESID))) return rc;
+      GemmArgs proj = linear(w.o, L.wproj, w.x, M, D, D, EPI_BIAS_RESID);
+      proj.bias = L.bproj;
+      proj.resid = w.x;
+      proj.gamma = L.ls1;
+      if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, proj, EPI_BIAS_RESID))) return rc;
       if (cls_bf16) {
         // fork: the CLS rows' bf16 MLP runs on the side stream under norm2 / fc1 of every row (nothing writes w.x there)
         VDR_TRY(hipEventRecord(m->aux_fork[ai], s), "hipEventRecord");
@@ -1041,12 +1071,10 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
         Scope sc(m, s, VDR_K_LAYERNORM, 0.0, (double)M * D * 3);
         VDR_TRY(launch_ln_mx(w.x, L.n2w, L.n2b, c.ln_eps, M, D, w.h, w.hs, s), "layernorm_mx");
       }
-      if ((rc = gemm_mx(m, s, VDR_K_GEMM_FC1, w.h, w.hs, L.w1_q, L.w1_s, L.b1, nullptr, nullptr, w.u, w.us, M, N1, D, F,
-                        sw ? EPI_SWIGLU : EPI_BIAS_GELU)))
-        return rc;
+      if ((rc = gemm_mx(m, s, VDR_K_GEMM_FC1, w.h, w.hs, L.w1_q, L.w1_s, L.b1, nullptr, nullptr, w.u, w.us, M, N1, D, e1))) return rc;
       // join: fc2 rewrites every row of w.x, the CLS rows' residual reads must be over
       if (cls_bf16) VDR_TRY(hipStreamWaitEvent(s, m->aux_join[ai], 0), "hipStreamWaitEvent");
-      if ((rc = gemm_mx(m, s, VDR_K_GEMM_FC2, w.u, w.us, L.w2_q, L.w2_s, L.b2, w.x, L.ls2, w.x, nullptr, M, D, F, D, EPI_BIAS_RESID)))
+      if ((rc = gemm_mx(m, s, VDR_K_GEMM_FC2, w.u, w.us, L.w2_q, L.w2_s, L.b2, w.x, L.ls2, w.x, nullptr, M, D, F, EPI_BIAS_RESID)))
         return rc;
       if (cls_bf16)  // ... and the bf16 result replaces the MX-fp8 one in the CLS rows
         VDR_TRY(hipMemcpy2DAsync(w.x, (size_t)ntok * D * 2, w.cls_x, (size_t)D * 2, (size_t)D * 2, (size_t)mb, hipMemcpyDeviceToDevice, s),
@@ -1064,80 +1092,80 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
     prod.part_stride = w.Mp;
     // (the producers finalise the statistics where a consumer reads finalised ones; launches small enough for the ring3 /
     // ring4 consumers to finalise their own rows from the partials need nothing)
-    if (!ln_stats_in_gemm(VDR_K_GEMM_QKV, M, 3 * D, D / 64) || !ln_stats_in_gemm(VDR_K_GEMM_FC1, M, sw ? 2 * F : F, D / 64))
+    if (!ln_stats_in_gemm(VDR_K_GEMM_QKV, M, 3 * D, D / 64) || !ln_stats_in_gemm(VDR_K_GEMM_FC1, M, N1, D / 64))
       prod.fin_stats = w.stats;
     for (int i = 0; i < nl; ++i) {
       const LayerW& L = m->layers[i];
       LnFold cons;
       if ((rc = ln_consumer(m, s, VDR_K_GEMM_QKV, M, 3 * D, D, w, &cons))) return rc;
       cons.colsum = L.sqkv;
-      if ((rc = gemm(m, s, VDR_K_GEMM_QKV, w.x, L.wqkv_f, L.tqkv, nullptr, nullptr, w.qkv, M, 3 * D, D, 3 * D, EPI_BIAS, cons, 0, 0, nullptr,
-                     nullptr, w.Mp)))
-        return rc;
-      {
-        Scope sc(m, s, VDR_K_ATTENTION, 4.0 * (double)ntok * ntok * D * mb, 2.0 * (double)M * 4 * D);
-        VDR_KNOB int attn_variant = env_int("VDR_ATTN_VARIANT", 0);  // (tuning builds)
-        VDR_TRY(launch_attention(w.qkv, w.o, mb, ntok, H, attn_variant, s, nullptr, lens, len_add, D / H), "attention");
-      }
-      if (i == tail_at) {
-        *compact = true;
-        if ((rc = block_tail_cls(m, s, w, L, mb, ntok))) return rc;
-        return after(i, true);
-      }
-      if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, w.o, L.wproj, L.bproj, w.x, L.ls1, w.x, M, D, D, D, EPI_BIAS_RESID, prod, 0, 0, w.x32, w.x32)))
-        return rc;
-      if ((rc = ln_consumer(m, s, VDR_K_GEMM_FC1, M, sw ? 2 * F : F, D, w, &cons))) return rc;
+      GemmArgs qkv = linear(w.x, L.wqkv_f, w.qkv, M, 3 * D, D, EPI_BIAS);
+      qkv.bias = L.tqkv;
+      qkv.a_rows = w.Mp;
+      if ((rc = gemm(m, s, VDR_K_GEMM_QKV, qkv, EPI_BIAS, cons))) return rc;
+      if ((rc = attention())) return rc;
+      if (i == tail_at) return cls_tail_exit(i, L);
+      GemmArgs proj = linear(w.o, L.wproj, w.x, M, D, D, EPI_BIAS_RESID);
+      proj.bias = L.bproj;
+      proj.resid = w.x;
+      proj.gamma = L.ls1;
+      proj.resid32 = proj.C32 = w.x32;
+      if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, proj, EPI_BIAS_RESID, prod))) return rc;
+      if ((rc = ln_consumer(m, s, VDR_K_GEMM_FC1, M, N1, D, w, &cons))) return rc;
       cons.colsum = L.s1;
-      if ((rc = gemm(m, s, VDR_K_GEMM_FC1, w.x, L.w1_f, L.t1, nullptr, nullptr, w.u, M, sw ? 2 * F : F, D, F,
-                     sw ? EPI_SWIGLU : EPI_BIAS_GELU, cons, 0, 0, nullptr, nullptr, w.Mp)))
-        return rc;
-      if ((rc = gemm(m, s, VDR_K_GEMM_FC2, w.u, L.w2, L.b2, w.x, L.ls2, w.x, M, D, F, D, EPI_BIAS_RESID, prod, 0, 0, w.x32, w.x32)))
-        return rc;
+      GemmArgs fc1 = linear(w.x, L.w1_f, w.u, M, N1, D, e1);
+      fc1.bias = L.t1;
+      fc1.a_rows = w.Mp;
+      if ((rc = gemm(m, s, VDR_K_GEMM_FC1, fc1, e1, cons))) return rc;
+      GemmArgs fc2 = linear(w.u, L.w2, w.x, M, D, F, EPI_BIAS_RESID);
+      fc2.bias = L.b2;
+      fc2.resid = w.x;
+      fc2.gamma = L.ls2;
+      fc2.resid32 = fc2.C32 = w.x32;
+      if ((rc = gemm(m, s, VDR_K_GEMM_FC2, fc2, EPI_BIAS_RESID, prod))) return rc;
       if ((rc = after(i, false))) return rc;
     }
     return VDR_OK;
   }
   for (int i = 0; i < nl; ++i) {
     const LayerW& L = m->layers[i];
-    const void* attn_in = w.x;
     // (resid_fp32: the explicit LayerNorm reads the fp32 master copy of the stream)
     const void* xin = w.x32 ? (const void*)w.x32 : (const void*)w.x;
     const int xin_bf16 = w.x32 ? 0 : 1;
+    if (c.pre_ln && (rc = layernorm(m, s, VDR_K_LAYERNORM, xin, xin_bf16, w.h, 1, L.n1w, L.n1b, M, identity_map()))) return rc;
+    GemmArgs qkv = linear(c.pre_ln ? w.h : w.x, L.wqkv, w.qkv, M, 3 * D, D, EPI_BIAS);
+    qkv.bias = L.bqkv;
+    qkv.a_rows = w.Mp;
+    if ((rc = gemm(m, s, VDR_K_GEMM_QKV, qkv, EPI_BIAS))) return rc;
+    if ((rc = attention())) return rc;
+    if (i == tail_at) return cls_tail_exit(i, L);
+    // the residual linears: C = x + gamma * (A . W^T + bias), in place (pre-LN, with the fp32 master copy under
+    // resid_fp32) or into w.h (post-LN, the input of the LayerNorm after them)
+    GemmArgs proj = linear(w.o, L.wproj, c.pre_ln ? w.x : w.h, M, D, D, EPI_BIAS_RESID);
+    proj.bias = L.bproj;
+    proj.resid = w.x;
+    proj.gamma = L.ls1;
+    proj.resid32 = proj.C32 = w.x32;
+    GemmArgs fc1 = linear(c.pre_ln ? w.h : w.x, L.w1, w.u, M, N1, D, e1);
+    fc1.bias = L.b1;
+    fc1.a_rows = w.Mp;
+    GemmArgs fc2 = linear(w.u, L.w2, c.pre_ln ? w.x : w.h, M, D, F, EPI_BIAS_RESID);
+    fc2.bias = L.b2;
+    fc2.resid = w.x;
+    fc2.gamma = L.ls2;
+    fc2.resid32 = fc2.C32 = w.x32;
     if (c.pre_ln) {
-      if ((rc = layernorm(m, s, VDR_K_LAYERNORM, xin, xin_bf16, w.h, 1, L.n1w, L.n1b, M, identity_map()))) return rc;
-      attn_in = w.h;
-    }
-    if ((rc = gemm(m, s, VDR_K_GEMM_QKV, attn_in, L.wqkv, L.bqkv, nullptr, nullptr, w.qkv, M, 3 * D, D, 3 * D, EPI_BIAS, LnFold(), 0, 0, nullptr,
-                   nullptr, w.Mp)))
-      return rc;
-    {
-      Scope sc(m, s, VDR_K_ATTENTION, 4.0 * (double)ntok * ntok * D * mb, 2.0 * (double)M * 4 * D);
-      VDR_KNOB int attn_variant = env_int("VDR_ATTN_VARIANT", 0);
-      VDR_TRY(launch_attention(w.qkv, w.o, mb, ntok, H, attn_variant, s, nullptr, lens, len_add, D / H), "attention");
-    }
-    if (i == tail_at) {
-      *compact = true;
-      if ((rc = block_tail_cls(m, s, w, L, mb, ntok))) return rc;
-      return after(i, true);
-    }
-    if (c.pre_ln) {
-      if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, w.o, L.wproj, L.bproj, w.x, L.ls1, w.x, M, D, D, D, EPI_BIAS_RESID, LnFold(), 0, 0, w.x32, w.x32)))
-        return rc;
+      if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, proj, EPI_BIAS_RESID))) return rc;
       if ((rc = layernorm(m, s, VDR_K_LAYERNORM, xin, xin_bf16, w.h, 1, L.n2w, L.n2b, M, identity_map()))) return rc;
-      if ((rc = gemm(m, s, VDR_K_GEMM_FC1, w.h, L.w1, L.b1, nullptr, nullptr, w.u, M, sw ? 2 * F : F, D, F,
-                     sw ? EPI_SWIGLU : EPI_BIAS_GELU, LnFold(), 0, 0, nullptr, nullptr, w.Mp)))
-        return rc;
-      if ((rc = gemm(m, s, VDR_K_GEMM_FC2, w.u, L.w2, L.b2, w.x, L.ls2, w.x, M, D, F, D, EPI_BIAS_RESID, LnFold(), 0, 0, w.x32, w.x32)))
-        return rc;
+      if ((rc = gemm(m, s, VDR_K_GEMM_FC1, fc1, e1))) return rc;
+      if ((rc = gemm(m, s, VDR_K_GEMM_FC2, fc2, EPI_BIAS_RESID))) return rc;
       if ((rc = after(i, false))) return rc;
     } else {
       // nn.TransformerEncoderLayer, norm_first=False: x = LN1(x + SA(x)); x = LN2(x + FF(x))
-      if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, w.o, L.wproj, L.bproj, w.x, L.ls1, w.h, M, D, D, D, EPI_BIAS_RESID))) return rc;
+      if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, proj, EPI_BIAS_RESID))) return rc;
       if ((rc = layernorm(m, s, VDR_K_LAYERNORM, w.h, 1, w.x, 1, L.n1w, L.n1b, M, identity_map()))) return rc;
-      if ((rc = gemm(m, s, VDR_K_GEMM_FC1, w.x, L.w1, L.b1, nullptr, nullptr, w.u, M, sw ? 2 * F : F, D, F,
-                     sw ? EPI_SWIGLU : EPI_BIAS_GELU, LnFold(), 0, 0, nullptr, nullptr, w.Mp)))
-        return rc;
-      if ((rc = gemm(m, s, VDR_K_GEMM_FC2, w.u, L.w2, L.b2, w.x, L.ls2, w.h, M, D, F, D, EPI_BIAS_RESID))) return rc;
+      if ((rc = gemm(m, s, VDR_K_GEMM_FC1, fc1, e1))) return rc;
+      if ((rc = gemm(m, s, VDR_K_GEMM_FC2, fc2, EPI_BIAS_RESID))) return rc;
       if ((rc = layernorm(m, s, VDR_K_LAYERNORM, w.h, 1, w.x, 1, L.n2w, L.n2b, M, identity_map()))) return rc;
     }
   }
@@ -1150,18 +1178,7 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
 // T[(token, head)][j] = q . table[j] for every relative offset j of both axes: one GEMM whose A rows are the
 // per-head q slices of the packed qkv activation (M = tokens * heads, N = relpos_npad(S), K = 64), fp32 out.
 hipError_t relpos_products(const void* qkv, const void* table, float* T, int64_t tokens, int S, int heads, hipStream_t s) {
-  GemmArgs ga{};
-  ga.A = qkv;
-  ga.W = table;
-  ga.C = T;
-  ga.M = tokens * heads;
-  ga.N = relpos_npad(S);
-  ga.K = 64;
-  ga.lda = 64;
-  ga.ldw = 64;
-  ga.ldc = ga.N;
-  ga.ldr = ga.N;
-  ga.omap = identity_map();
+  GemmArgs ga = linear(qkv, table, T, tokens * heads, relpos_npad(S), 64, EPI_BIAS);
   ga.a_rpg = heads;
   ga.a_gs = (int64_t)3 * heads * 64;
   ga.a_is = 64;
@@ -1192,8 +1209,7 @@ int run_sam(vdr_model* m, hipStream_t s, const Carve& w, int mb, int out_dtype, 
         Scope sc(m, s, VDR_K_LAYERNORM, 0.0, (double)M * D * 3);
         VDR_TRY(launch_ln_mx(w.x, L.n1w, L.n1b, c.ln_eps, M, D, hbuf, w.hs, s, glob ? 0 : ws, g, T), "layernorm_mx(window)");
       }
-      if ((rc = gemm_mx(m, s, VDR_K_GEMM_QKV, hbuf, w.hs, L.qkv_q, L.qkv_s, L.bqkv, nullptr, nullptr, w.qkv, nullptr, T, 3 * D, D,
-                        3 * D, EPI_BIAS)))
+      if ((rc = gemm_mx(m, s, VDR_K_GEMM_QKV, hbuf, w.hs, L.qkv_q, L.qkv_s, L.bqkv, nullptr, nullptr, w.qkv, nullptr, T, 3 * D, D, EPI_BIAS)))
         return rc;
     } else {
       LnArgs a{};
@@ -1216,9 +1232,10 @@ int run_sam(vdr_model* m, hipStream_t s, const Carve& w, int mb, int out_dtype, 
         Scope sc(m, s, VDR_K_LAYERNORM, 0.0, (double)M * D * 4);  // (own block: the profiler bracket must close before the GEMM)
         VDR_TRY(launch_layernorm(a, s), "layernorm(window)");
       }
-      if ((rc = gemm(m, s, VDR_K_GEMM_QKV, hbuf, L.wqkv, L.bqkv, nullptr, nullptr, w.qkv, T, 3 * D, D, 3 * D, EPI_BIAS, LnFold(), 0, 0, nullptr,
-                     nullptr, w.Mp)))
-        return rc;
+      GemmArgs qkv = linear(hbuf, L.wqkv, w.qkv, T, 3 * D, D, EPI_BIAS);
+      qkv.bias = L.bqkv;
+      qkv.a_rows = w.Mp;
+      if ((rc = gemm(m, s, VDR_K_GEMM_QKV, qkv, EPI_BIAS))) return rc;
     }
     {
       Scope sc(m, s, VDR_K_ATTENTION, 4.0 * (double)S * S * S * S * 64.0 * H * nb + 2.0 * T * H * relpos_npad(S) * 64,
@@ -1227,20 +1244,10 @@ int run_sam(vdr_model* m, hipStream_t s, const Carve& w, int mb, int out_dtype, 
       VDR_TRY(launch_attention_relpos(w.qkv, w.rel, w.o, nb, S, H, s), "attention_relpos");
     }
     {
-      GemmArgs ga{};
-      ga.A = w.o;
-      ga.W = L.wproj;
+      // (not through gemm(): the profiler books T rows of A, the windowed ones with their padding, but M output rows)
+      GemmArgs ga = linear(w.o, L.wproj, w.x, T, D, D, EPI_BIAS_RESID);
       ga.bias = L.bproj;
       ga.resid = w.x;
-      ga.C = w.x;
-      ga.M = T;
-      ga.N = D;
-      ga.K = D;
-      ga.lda = D;
-      ga.ldw = D;
-      ga.ldc = D;
-      ga.ldr = D;
-      ga.omap = identity_map();
       if (!glob) {
         ga.win_ws = ws;
         ga.win_g = g;
@@ -1258,26 +1265,30 @@ int run_sam(vdr_model* m, hipStream_t s, const Carve& w, int mb, int out_dtype, 
         Scope sc(m, s, VDR_K_LAYERNORM, 0.0, (double)M * D * 3);
         VDR_TRY(launch_ln_mx(w.x, L.n2w, L.n2b, c.ln_eps, M, D, w.hg, w.hs, s), "layernorm_mx");
       }
-      if ((rc = gemm_mx(m, s, VDR_K_GEMM_FC1, w.hg, w.hs, L.w1_q, L.w1_s, L.b1, nullptr, nullptr, w.u, w.us, M, F, D, F,
-                        EPI_BIAS_GELU)))
+      if ((rc = gemm_mx(m, s, VDR_K_GEMM_FC1, w.hg, w.hs, L.w1_q, L.w1_s, L.b1, nullptr, nullptr, w.u, w.us, M, F, D, EPI_BIAS_GELU)))
         return rc;
-      if ((rc = gemm_mx(m, s, VDR_K_GEMM_FC2, w.u, w.us, L.w2_q, L.w2_s, L.b2, w.x, nullptr, w.x, nullptr, M, D, F, D,
-                        EPI_BIAS_RESID)))
+      if ((rc = gemm_mx(m, s, VDR_K_GEMM_FC2, w.u, w.us, L.w2_q, L.w2_s, L.b2, w.x, nullptr, w.x, nullptr, M, D, F, EPI_BIAS_RESID)))
         return rc;
       continue;
     }
+    GemmArgs fc1;
+    LnFold cons;
     if (m->ln_fuse) {
-      LnFold cons;
       if ((rc = ln_consumer(m, s, VDR_K_GEMM_FC1, M, F, D, w, &cons))) return rc;
       cons.colsum = L.s1;
-      if ((rc = gemm(m, s, VDR_K_GEMM_FC1, w.x, L.w1_f, L.t1, nullptr, nullptr, w.u, M, F, D, F, EPI_BIAS_GELU, cons, 0, 0, nullptr, nullptr, w.Mp))) return rc;
+      fc1 = linear(w.x, L.w1_f, w.u, M, F, D, EPI_BIAS_GELU);
+      fc1.bias = L.t1;
     } else {
       if ((rc = layernorm(m, s, VDR_K_LAYERNORM, w.x, 1, w.hg, 1, L.n2w, L.n2b, M, identity_map()))) return rc;
-      if ((rc = gemm(m, s, VDR_K_GEMM_FC1, w.hg, L.w1, L.b1, nullptr, nullptr, w.u, M, F, D, F, EPI_BIAS_GELU, LnFold(), 0, 0, nullptr, nullptr,
-                     w.Mp)))
-        return rc;
+      fc1 = linear(w.hg, L.w1, w.u, M, F, D, EPI_BIAS_GELU);
+      fc1.bias = L.b1;
     }
-    if ((rc = gemm(m, s, VDR_K_GEMM_FC2, w.u, L.w2, L.b2, w.x, nullptr, w.x, M, D, F, D, EPI_BIAS_RESID))) return rc;
+    fc1.a_rows = w.Mp;
+    if ((rc = gemm(m, s, VDR_K_GEMM_FC1, fc1, EPI_BIAS_GELU, cons))) return rc;
+    GemmArgs fc2 = linear(w.u, L.w2, w.x, M, D, F, EPI_BIAS_RESID);
+    fc2.bias = L.b2;
+    fc2.resid = w.x;
+    if ((rc = gemm(m, s, VDR_K_GEMM_FC2, fc2, EPI_BIAS_RESID))) return rc;
   }
   if (tokens_only) {
     Scope sc(m, s, VDR_K_FINAL_LN, 0.0, (double)M * D * 6);
@@ -1285,103 +1296,45 @@ int run_sam(vdr_model* m, hipStream_t s, const Carve& w, int mb, int out_dtype, 
     return VDR_OK;
   }
   // neck: 1x1 conv (no bias) -> LayerNorm2d -> 3x3 conv pad 1 (no bias) -> LayerNorm2d, all on NHWC tokens
-  if ((rc = gemm(m, s, VDR_K_GEMM_PATCH, w.x, m->w_neck0, nullptr, nullptr, nullptr, w.qkv, M, C, D, C, EPI_BIAS))) return rc;
+  if ((rc = gemm(m, s, VDR_K_GEMM_PATCH, linear(w.x, m->w_neck0, w.qkv, M, C, D, EPI_BIAS), EPI_BIAS))) return rc;
   if ((rc = layernorm(m, s, VDR_K_FINAL_LN, w.qkv, 1, w.o, 1, m->neck1w, m->neck1b, M, identity_map(), nullptr, 0, C))) return rc;
   {
     Scope sc(m, s, VDR_K_IM2COL, 0.0, (double)M * C * 2 * 10);
     VDR_TRY(launch_im2col3(w.o, w.u, mb, g, C, s), "im2col3");
   }
-  if ((rc = gemm(m, s, VDR_K_GEMM_PATCH, w.u, m->w_neck2, nullptr, nullptr, nullptr, w.hg, M, C, 9 * C, C, EPI_BIAS))) return rc;
+  if ((rc = gemm(m, s, VDR_K_GEMM_PATCH, linear(w.u, m->w_neck2, w.hg, M, C, 9 * C, EPI_BIAS), EPI_BIAS))) return rc;
   return layernorm(m, s, VDR_K_FINAL_LN, w.hg, 1, out, out_dtype == VDR_BF16, m->neck3w, m->neck3b, M, identity_map(), nullptr,
                    0, C);
 }
-
-// slice (and final-normalise) the token buffer into the caller's output
-int emit(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, int out_mode, int out_dtype, char* out,
-         bool compact = false) {  // compact: the CLS rows are in w.h [mb, D] (block_tail_cls)
-  const vdr_config& c = m->cfg;
-  const int D = c.dim;
-  RowMap im;
-  int64_t rows;
-  const int ncls = c.has_cls ? 1 : 0;
-  if (compact) {
-    const int ob = out_dtype == VDR_BF16;
-    if (w.x32) return layernorm(m, s, VDR_K_FINAL_LN, w.xc32, 0, out, ob, m->normw, m->normb, mb, identity_map());
-    return layernorm(m, s, VDR_K_FINAL_LN, w.h, 1, out, ob, m->normw, m->normb, mb, identity_map());
-  }
-  if (out_mode == VDR_OUT_CLS) {
-    im = RowMap{1, ntok, 0};
-    rows = mb;
-  } else if (out_mode == VDR_OUT_DENSE) {
-    im = RowMap{ntok - ncls, ntok, ncls};
-    rows = (int64_t)mb * (ntok - ncls);
-  } else {
-    im = identity_map();
-    rows = (int64_t)mb * ntok;
-  }
-  const int ob = out_dtype == VDR_BF16;
-  if (c.pre_ln) {
-    if (w.x32) return layernorm(m, s, VDR_K_FINAL_LN, w.x32, 0, out, ob, m->normw, m->normb, rows, im);
-    return layernorm(m, s, VDR_K_FINAL_LN, w.x, 1, out, ob, m->normw, m->normb, rows, im);
-  }
-  Scope sc(m, s, VDR_K_FINAL_LN, 0.0, (double)rows * D * (2 + (ob ? 2 : 4)));
-  VDR_TRY(launch_gather_rows(w.x, out, ob, rows, D, im, s), "gather_rows");
-  return VDR_OK;
-}
-
-size_t out_row_bytes(const vdr_model* m, int out_dtype) { return (size_t)m->cfg.dim * (out_dtype == VDR_BF16 ? 2 : 4); }
 
 // patch embedding of one micro-batch: the token rows b*ntok + ncls + i of w.x (pos_embed added), or -- pe_out non-null,
 // model.patch_embed(x) -- the caller's [mb, n, D] output
 int embed_patches(vdr_model* m, hipStream_t s, const Carve& w, const char* img, int in_dtype, int mb, char* pe_out, int out_dtype) {
   const vdr_config& c = m->cfg;
   const int ntok = m->n_tokens, n = m->n_patches, D = c.dim, ncls = c.has_cls ? 1 : 0;
-  const size_t img_elems = (size_t)c.in_chans * c.img * c.img;
-  const size_t in_es = in_dtype == VDR_BF16 ? 2 : 4;
-  // bf16 images with a patch side of 8 / 16 / 32: the patch GEMM's operand loader gathers 16-byte runs of pixels
-  // straight from the NCHW images (ring4 tile variants) -- no col buffer, no im2col launch.  fp32 images (the loader
-  // is an LDS-DMA: it cannot convert) and p = 14 (runs of 14 pixels are not 16-byte chunks) go through im2col.
-  const int pvar = gemm_variant_for(VDR_K_GEMM_PATCH, (int64_t)mb * n, D);
-  const bool fused_patch = patch_gather_ok(in_dtype, c.patch, pvar, img);
   const bool pe_only = pe_out != nullptr;
-  if (!fused_patch) {
-    Scope sc(m, s, VDR_K_IM2COL, 0.0, (double)mb * img_elems * in_es + 2.0 * mb * n * m->Kp);
-    VDR_TRY(launch_im2col(img, in_dtype == VDR_BF16, w.u, mb, c.in_chans, c.img, c.patch, m->Kp, s), "im2col");
-  }
-  GemmArgs g{};
-  g.A = fused_patch ? (const void*)img : (const void*)w.u;
-  if (fused_patch) {
-    g.patch_p = c.patch;
-    g.patch_g = c.img / c.patch;
-    g.patch_C = c.in_chans;
-  }
-  g.W = m->w_patch;
+  GemmArgs g;
+  int variant;
+  VDR_TRY(patch_gemm(m, s, img, in_dtype, w.u, m->w_patch, pe_only ? (void*)pe_out : (void*)w.x, mb, c.in_chans, c.img, c.patch, D,
+                     &g, &variant),
+          "im2col");
   g.bias = m->b_patch;
-  g.pos = pe_only ? nullptr : m->pos;
-  g.M = (int64_t)mb * n;
-  g.N = D;
-  g.K = m->Kp;
-  g.lda = m->Kp;
-  g.ldw = m->Kp;
-  g.ldc = D;
-  g.ldr = D;
-  if (m->ln_fuse && !pe_only) {
-    g.ln_part = w.part;
-    g.part_stride = w.Mp;
-  }
   if (pe_only) {
     // model.patch_embed(x) (tfds_dense_descriptor.py:128): the GEMM epilogue writes the caller's [B, n, D] buffer
     // directly, bf16 or fp32 (no conversion pass)
-    g.C = pe_out;
     g.out_f32 = out_dtype != VDR_BF16;
     g.omap = RowMap{n, n, 0};
   } else {
-    g.C = w.x;
+    g.pos = m->pos;
     g.omap = RowMap{n, ntok, ncls};
+    if (m->ln_fuse) {
+      g.ln_part = w.part;
+      g.part_stride = w.Mp;
+    }
   }
   Scope sc(m, s, VDR_K_GEMM_PATCH, 2.0 * g.M * D * c.in_chans * c.patch * c.patch,
            2.0 * ((double)g.M * m->Kp + (double)D * m->Kp + (double)g.M * D));
-  VDR_TRY(launch_gemm_w(m, g, EPI_PATCH, pvar, s), "patch gemm");
+  VDR_TRY(launch_gemm_w(m, g, EPI_PATCH, variant, s), "patch gemm");
   return VDR_OK;
 }
 
@@ -1414,6 +1367,37 @@ int check_device(vdr_handle h) {
     (void)hipGetLastError();
     return fail(h, VDR_ERR_NO_DEVICE, "no HIP device visible: libvdr has no CPU path");
   }
+  return VDR_OK;
+}
+
+// The rest of every forward once its arguments are checked: the device, the workspace, then micro-batches of at most
+// default_micro_batch images, micro-batch k on internal stream k % streams (the caller's stream with one) in its own
+// slice of the workspace.  body(s, w, b0, mb) enqueues the micro-batch of images b0 .. b0 + mb - 1.
+template <class Body>
+int run_micro_batches(vdr_model* m, int batch, int ntok, void* workspace, size_t workspace_bytes, void* stream, Body body) {
+  int rc = check_device(m);
+  if (rc) return rc;
+  if (!m->resolved) return fail(m, VDR_ERR_INCOMPLETE, "vdr_finalize has not run since the last vdr_set_weight");
+  DeviceGuard dg(m->device);
+  if (!dg.ok) return fail(m, VDR_ERR_HIP, "hipSetDevice failed");
+  const int mb_max = default_micro_batch(m, batch);
+  const int ns = num_streams(m);
+  const size_t per_ws = carve(m, nullptr, mb_max, ntok).total;
+  if (per_ws * ns > workspace_bytes)
+    return fail(m, VDR_ERR_WORKSPACE, "workspace too small: need " + std::to_string(per_ws * ns) + " bytes");
+  hipStream_t caller = (hipStream_t)stream;
+  if (fork_streams(m, caller)) return fail(m, VDR_ERR_HIP, "internal stream setup failed");
+  int chunk = 0;
+  for (int b0 = 0; b0 < batch; b0 += mb_max, ++chunk) {
+    const int mb = batch - b0 < mb_max ? batch - b0 : mb_max;
+    const int si = chunk % ns;
+    m->cur_aux = si;
+    m->stats_fresh = false;  // (nothing has finalised the statistics of this micro-batch yet)
+    hipStream_t s = ns == 1 ? caller : m->streams[si];
+    const Carve w = carve(m, (char*)workspace + si * per_ws, mb_max, ntok);
+    if ((rc = body(s, w, b0, mb))) return rc;
+  }
+  if (join_streams(m, caller)) return fail(m, VDR_ERR_HIP, "internal stream join failed");
   return VDR_OK;
 }
 
@@ -1663,50 +1647,28 @@ int vdr_forward(vdr_handle m, const void* images, int in_dtype, int batch, void*
   if (out_mode == VDR_OUT_CLS && !c.has_cls) return fail(m, VDR_ERR_INVALID, "model has no cls token");
   if ((out_mode == VDR_OUT_ENCODER) != (c.window > 0 && out_mode != VDR_OUT_PATCH_EMBED && out_mode != VDR_OUT_TOKENS))
     return fail(m, VDR_ERR_INVALID, "VDR_OUT_ENCODER is the output of a SAM encoder (window > 0); other models use CLS/DENSE/TOKENS");
-  int rc = check_device(m);
-  if (rc) return rc;
-  if (!m->resolved) return fail(m, VDR_ERR_INCOMPLETE, "vdr_finalize has not run since the last vdr_set_weight");
-  DeviceGuard dg(m->device);
-  if (!dg.ok) return fail(m, VDR_ERR_HIP, "hipSetDevice failed");
-  const int mb_max = default_micro_batch(m, batch);
   const int ntok = m->n_tokens, n = m->n_patches, D = c.dim;
-  const int ns = num_streams(m);
-  const size_t per_ws = carve(m, nullptr, mb_max, ntok).total;
-  if (per_ws * ns > workspace_bytes)
-    return fail(m, VDR_ERR_WORKSPACE, "workspace too small: need " + std::to_string(per_ws * ns) + " bytes");
-  hipStream_t caller = (hipStream_t)stream;
-  if (fork_streams(m, caller)) return fail(m, VDR_ERR_HIP, "internal stream setup failed");
-  const size_t img_elems = (size_t)c.in_chans * c.img * c.img;
-  const size_t in_es = in_dtype == VDR_BF16 ? 2 : 4;
-  const int ncls = c.has_cls ? 1 : 0;
-  int chunk = 0;
-  for (int b0 = 0; b0 < batch; b0 += mb_max, ++chunk) {
-    const int mb = batch - b0 < mb_max ? batch - b0 : mb_max;
-    const int si = chunk % ns;
-    m->cur_aux = si;
-    m->stats_fresh = false;  // (nothing has finalised the statistics of this micro-batch yet)
-    hipStream_t s = ns == 1 ? caller : m->streams[si];
-    const Carve w = carve(m, (char*)workspace + si * per_ws, mb_max, ntok);
-    const char* img = (const char*)images + (size_t)b0 * img_elems * in_es;
-    const bool pe_only = out_mode == VDR_OUT_PATCH_EMBED;
-    char* pe_out = pe_only ? (char*)out + (size_t)b0 * n * D * (out_dtype == VDR_BF16 ? 2 : 4) : nullptr;
-    if ((rc = embed_patches(m, s, w, img, in_dtype, mb, pe_out, out_dtype))) return rc;
-    if (pe_only) continue;
+  const size_t img_bytes = (size_t)c.in_chans * c.img * c.img * (in_dtype == VDR_BF16 ? 2 : 4);
+  const size_t es = out_dtype == VDR_BF16 ? 2 : 4;
+  vdr_layer_out o{};  // (the output of the last block, as vdr_forward_layers describes one)
+  o.out_mode = out_mode;
+  o.out_dtype = out_dtype;
+  o.norm = c.pre_ln ? 1 : 0;
+  o.out = out;
+  return run_micro_batches(m, batch, ntok, workspace, workspace_bytes, stream, [&](hipStream_t s, const Carve& w, int b0, int mb) {
+    const char* img = (const char*)images + (size_t)b0 * img_bytes;
+    if (out_mode == VDR_OUT_PATCH_EMBED) return embed_patches(m, s, w, img, in_dtype, mb, (char*)out + (size_t)b0 * n * D * es, out_dtype);
+    int rc;
+    if ((rc = embed_patches(m, s, w, img, in_dtype, mb, nullptr, out_dtype))) return rc;
     if (c.window > 0) {
       const bool tok = out_mode == VDR_OUT_TOKENS;
-      const size_t orow_b = tok ? out_row_bytes(m, out_dtype) : (size_t)c.neck_chans * (out_dtype == VDR_BF16 ? 2 : 4);
-      if ((rc = run_sam(m, s, w, mb, out_dtype, (char*)out + (size_t)b0 * n * orow_b, tok))) return rc;
-      continue;
+      return run_sam(m, s, w, mb, out_dtype, (char*)out + (size_t)b0 * n * (tok ? D : c.neck_chans) * es, tok);
     }
     if ((rc = assemble_stream(m, s, w, mb, ntok))) return rc;
     bool compact = false;
     if ((rc = run_blocks(m, s, w, mb, ntok, nullptr, 0, out_mode == VDR_OUT_CLS, &compact))) return rc;
-    const int64_t rows_per_img = out_mode == VDR_OUT_CLS ? 1 : (out_mode == VDR_OUT_DENSE ? ntok - ncls : ntok);
-    char* o = (char*)out + (size_t)b0 * rows_per_img * out_row_bytes(m, out_dtype);
-    if ((rc = emit(m, s, w, mb, ntok, out_mode, out_dtype, o, compact))) return rc;
-  }
-  if (join_streams(m, caller)) return fail(m, VDR_ERR_HIP, "internal stream join failed");
-  return VDR_OK;
+    return write_output(m, s, w, mb, ntok, o, b0, compact);
+  });
 }
 
 int vdr_forward_layers(vdr_handle m, const void* images, int in_dtype, int batch, const vdr_layer_out* outs, int n_outs,
@@ -1747,36 +1709,16 @@ int vdr_forward_layers(vdr_handle m, const void* images, int in_dtype, int batch
   }
   bool cls_only = true;  // every output of the last block that runs is CLS: that block may run its CLS rows only
   for (const vdr_layer_out* o : el.at[el.last]) cls_only = cls_only && o->out_mode == VDR_OUT_CLS;
-  int rc = check_device(m);
-  if (rc) return rc;
-  if (!m->resolved) return fail(m, VDR_ERR_INCOMPLETE, "vdr_finalize has not run since the last vdr_set_weight");
-  DeviceGuard dg(m->device);
-  if (!dg.ok) return fail(m, VDR_ERR_HIP, "hipSetDevice failed");
-  const int mb_max = default_micro_batch(m, batch);
   const int ntok = m->n_tokens;
-  const int ns = num_streams(m);
-  const size_t per_ws = carve(m, nullptr, mb_max, ntok).total;
-  if (per_ws * ns > workspace_bytes)
-    return fail(m, VDR_ERR_WORKSPACE, "workspace too small: need " + std::to_string(per_ws * ns) + " bytes");
-  hipStream_t caller = (hipStream_t)stream;
-  if (fork_streams(m, caller)) return fail(m, VDR_ERR_HIP, "internal stream setup failed");
   const size_t img_bytes = (size_t)c.in_chans * c.img * c.img * (in_dtype == VDR_BF16 ? 2 : 4);
-  int chunk = 0;
-  for (int b0 = 0; b0 < batch; b0 += mb_max, ++chunk) {  // (micro-batches and streams as vdr_forward)
-    const int mb = batch - b0 < mb_max ? batch - b0 : mb_max;
-    const int si = chunk % ns;
-    m->cur_aux = si;
-    m->stats_fresh = false;
-    hipStream_t s = ns == 1 ? caller : m->streams[si];
-    const Carve w = carve(m, (char*)workspace + si * per_ws, mb_max, ntok);
+  return run_micro_batches(m, batch, ntok, workspace, workspace_bytes, stream, [&](hipStream_t s, const Carve& w, int b0, int mb) {
+    int rc;
     if ((rc = embed_patches(m, s, w, (const char*)images + (size_t)b0 * img_bytes, in_dtype, mb, nullptr, VDR_F32))) return rc;
     if ((rc = assemble_stream(m, s, w, mb, ntok))) return rc;
     el.b0 = b0;
     bool compact = false;
-    if ((rc = run_blocks(m, s, w, mb, ntok, nullptr, 0, cls_only, &compact, &el))) return rc;
-  }
-  if (join_streams(m, caller)) return fail(m, VDR_ERR_HIP, "internal stream join failed");
-  return VDR_OK;
+    return run_blocks(m, s, w, mb, ntok, nullptr, 0, cls_only, &compact, &el);
+  });
 }
 
 static int forward_tokens_impl(vdr_handle m, const void* tokens, int in_dtype, int batch, int seq, const int32_t* seq_lens,
@@ -1804,31 +1746,18 @@ static int forward_tokens_impl(vdr_handle m, const void* tokens, int in_dtype, i
   if (out_mode != VDR_OUT_CLS && out_mode != VDR_OUT_TOKENS && out_mode != VDR_OUT_DENSE)
     return fail(m, VDR_ERR_INVALID, "out_mode");
   if (out_mode == VDR_OUT_CLS && !c.has_cls) return fail(m, VDR_ERR_INVALID, "model has no cls token");
-  int rc = check_device(m);
-  if (rc) return rc;
-  if (!m->resolved) return fail(m, VDR_ERR_INCOMPLETE, "vdr_finalize has not run since the last vdr_set_weight");
-  DeviceGuard dg(m->device);
-  if (!dg.ok) return fail(m, VDR_ERR_HIP, "hipSetDevice failed");
   const int ncls = c.has_cls ? 1 : 0;
   const int ntok = seq + ncls, D = c.dim;
-  const int mb_max = default_micro_batch(m, batch);
-  const int ns = num_streams(m);
-  const size_t per_ws = carve(m, nullptr, mb_max, ntok).total;
-  if (per_ws * ns > workspace_bytes)
-    return fail(m, VDR_ERR_WORKSPACE, "workspace too small: need " + std::to_string(per_ws * ns) + " bytes");
-  hipStream_t caller = (hipStream_t)stream;
-  if (fork_streams(m, caller)) return fail(m, VDR_ERR_HIP, "internal stream setup failed");
   const size_t in_es = in_dtype == VDR_BF16 ? 2 : 4;
-  int chunk = 0;
-  for (int b0 = 0; b0 < batch; b0 += mb_max, ++chunk) {
-    const int mb = batch - b0 < mb_max ? batch - b0 : mb_max;
-    const int si = chunk % ns;
-    m->cur_aux = si;
-    m->stats_fresh = false;  // (nothing has finalised the statistics of this micro-batch yet)
-    hipStream_t s = ns == 1 ? caller : m->streams[si];
-    const Carve w = carve(m, (char*)workspace + si * per_ws, mb_max, ntok);
+  vdr_layer_out o{};  // (the output of the last block, as vdr_forward_layers describes one)
+  o.out_mode = out_mode;
+  o.out_dtype = out_dtype;
+  o.norm = c.pre_ln ? 1 : 0;
+  o.out = out;
+  return run_micro_batches(m, batch, ntok, workspace, workspace_bytes, stream, [&](hipStream_t s, const Carve& w, int b0, int mb) {
     const char* tok = (const char*)tokens + (size_t)b0 * seq * D * in_es;
     const int64_t M = (int64_t)mb * ntok;
+    int rc;
     if (c.input_ln) {
       // LayerNorm([cls ; tokens]) straight from the caller's buffer (models_archs.py:143-145)
       const RowMap im = c.has_cls ? RowMap{ntok, seq, -1} : identity_map();
@@ -1840,12 +1769,8 @@ static int forward_tokens_impl(vdr_handle m, const void* tokens, int in_dtype, i
       VDR_TRY(launch_assemble_tokens(tok, in_dtype == VDR_BF16, m->cls, nullptr, w.x, mb, seq, D, ncls, s), "assemble");
     }
     if ((rc = run_blocks(m, s, w, mb, ntok, seq_lens ? seq_lens + b0 : nullptr, ncls))) return rc;
-    const int64_t rows_per = out_mode == VDR_OUT_CLS ? 1 : (out_mode == VDR_OUT_DENSE ? seq : ntok);
-    char* o = (char*)out + (size_t)b0 * rows_per * out_row_bytes(m, out_dtype);
-    if ((rc = emit(m, s, w, mb, ntok, out_mode, out_dtype, o))) return rc;
-  }
-  if (join_streams(m, caller)) return fail(m, VDR_ERR_HIP, "internal stream join failed");
-  return VDR_OK;
+    return write_output(m, s, w, mb, ntok, o, b0, false);
+  });
 }
 
 // ---- single operators -----------------------------------------------------------------------------
@@ -1854,6 +1779,17 @@ static int forward_tokens_impl(vdr_handle m, const void* tokens, int in_dtype, i
     hipError_t _e = (expr);                                                            \
     if (_e != hipSuccess) return fail(nullptr, VDR_ERR_HIP, std::string(what) + ": " + hipGetErrorString(_e)); \
   } while (0)
+
+// an op's GEMM: hipErrorInvalidValue is the caller's tile variant or shape (VDR_ERR_INVALID, `refused`)
+static int op_gemm(const GemmArgs& g, int epilogue, int variant, void* stream, const char* refused) {
+  const hipError_t e = launch_gemm(g, epilogue, variant, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    (void)hipGetLastError();
+    return fail(nullptr, VDR_ERR_INVALID, refused);
+  }
+  OP_TRY(e, "gemm");
+  return VDR_OK;
+}
 
 int vdr_op_layernorm(const void* x, int in_dtype, void* y, int out_dtype, const float* gamma, const float* beta,
                      int64_t rows, int D, float eps, void* stream) {
@@ -1887,31 +1823,14 @@ static int op_linear_impl(const void* x, const void* W, int packed, const float*
 #endif
   int rc = check_device(nullptr);
   if (rc) return rc;
-  GemmArgs g{};
-  g.A = x;
-  g.W = W;
+  GemmArgs g = linear(x, W, y, M, N, K, epilogue);
   g.w_interleaved = packed;
   g.bias = bias;
   g.resid = resid;
   g.gamma = gamma;
-  g.C = y;
-  g.M = M;
-  g.N = N;
-  g.K = K;
-  g.lda = K;
-  g.ldw = K;
-  g.ldc = epilogue == VDR_EPI_SWIGLU ? N / 2 : N;
-  g.ldr = g.ldc;
-  g.omap = identity_map();
   if (variant == 0)  // library default: what the forward itself would pick for this shape
     variant = gemm_variant_for(N >= 2304 ? VDR_K_GEMM_QKV : VDR_K_GEMM_FC1, M, N);
-  const hipError_t e = launch_gemm(g, epilogue, variant, (hipStream_t)stream);
-  if (e == hipErrorInvalidValue) {
-    (void)hipGetLastError();
-    return fail(nullptr, VDR_ERR_INVALID, "gemm: unknown tile variant or unsupported shape");
-  }
-  OP_TRY(e, "gemm");
-  return VDR_OK;
+  return op_gemm(g, epilogue, variant, stream, "gemm: unknown tile variant or unsupported shape");
 }
 
 int vdr_op_linear(const void* x, const void* W, const float* bias, const void* resid, const float* gamma, void* y,
@@ -1944,7 +1863,7 @@ int vdr_ln_fold_weights(const float* W, const float* b, const float* gamma, cons
 }
 
 static bool ln_variant_ok(int variant, bool allow_31) {
-  return (variant >= 22 && variant <= 29) || (allow_31 && variant == 31);
+  return ring3_variant(variant) || variant == RING3K_VARIANT || ring4_variant(variant) || (allow_31 && variant == VARIANT_8P);
 }
 
 int vdr_op_linear_ln_stats(const void* x, const void* W, const float* bias, const void* resid, const float* gamma, void* y,
@@ -1954,26 +1873,15 @@ int vdr_op_linear_ln_stats(const void* x, const void* W, const float* bias, cons
   if ((resid32 != nullptr) != (y32 != nullptr)) return fail(nullptr, VDR_ERR_INVALID, "resid32 and y32 go together");
   if ((stats != nullptr) != (counters != nullptr)) return fail(nullptr, VDR_ERR_INVALID, "stats and counters go together");
   if (!ln_variant_ok(variant, false)) return fail(nullptr, VDR_ERR_INVALID, "variant: 22..29");
-  if (stats && variant < 26) return fail(nullptr, VDR_ERR_INVALID, "in-GEMM finalisation: ring4 variants 26..29");
+  if (stats && !ring4_variant(variant)) return fail(nullptr, VDR_ERR_INVALID, "in-GEMM finalisation: ring4 variants 26..29");
   if (M <= 0 || N <= 0 || K <= 0 || (N % 64) || (K % 64) || part_stride < M)
     return fail(nullptr, VDR_ERR_INVALID, "M > 0, N % 64 == 0, K % 64 == 0, part_stride >= M required");
   int rc = check_device(nullptr);
   if (rc) return rc;
-  GemmArgs g{};
-  g.A = x;
-  g.W = W;
+  GemmArgs g = linear(x, W, y, M, N, K, EPI_BIAS_RESID);
   g.bias = bias;
   g.resid = resid ? resid : y;
   g.gamma = gamma;
-  g.C = y;
-  g.M = M;
-  g.N = N;
-  g.K = K;
-  g.lda = K;
-  g.ldw = K;
-  g.ldc = N;
-  g.ldr = N;
-  g.omap = identity_map();
   g.resid32 = resid32;
   g.C32 = y32;
   LnFold ln;
@@ -1983,13 +1891,7 @@ int vdr_op_linear_ln_stats(const void* x, const void* W, const float* bias, cons
   ln.fin_cnt = counters;
   ln.eps = eps;
   set_ln_fold(g, ln);
-  const hipError_t e = launch_gemm(g, EPI_BIAS_RESID, variant, (hipStream_t)stream);
-  if (e == hipErrorInvalidValue) {
-    (void)hipGetLastError();
-    return fail(nullptr, VDR_ERR_INVALID, "gemm: unsupported tile variant or shape for the LayerNorm producer");
-  }
-  OP_TRY(e, "gemm");
-  return VDR_OK;
+  return op_gemm(g, EPI_BIAS_RESID, variant, stream, "gemm: unsupported tile variant or shape for the LayerNorm producer");
 }
 
 int vdr_op_ln_finalize(const float* part, int64_t part_stride, int64_t rows, int D, float eps, float* stats, void* stream) {
@@ -2013,23 +1915,12 @@ int vdr_op_linear_ln_fold(const void* x, const void* Wf, const float* colsum, co
   if (M <= 0 || N <= 0 || K <= 0 || (N % 64) || (K % 64) || (x_rows && x_rows < M))
     return fail(nullptr, VDR_ERR_INVALID, "M > 0, N % 64 == 0, K % 64 == 0, x_rows 0 or >= M required");
   // (the forward finalises inside the GEMM on ring3 / ring4 variants 22-24, 26-28 only, up to 16 groups)
-  if (part && (variant == 25 || variant >= 29 || K / 64 > 16 || part_stride < M))
+  if (part && (!ln_cpart_variant(variant) || K / 64 > 16 || part_stride < M))
     return fail(nullptr, VDR_ERR_INVALID, "in-GEMM statistics: variants 22-24, 26-28, K <= 1024, part_stride >= M");
   int rc = check_device(nullptr);
   if (rc) return rc;
-  GemmArgs g{};
-  g.A = x;
-  g.W = Wf;
+  GemmArgs g = linear(x, Wf, y, M, N, K, epilogue);
   g.bias = tbias;
-  g.C = y;
-  g.M = M;
-  g.N = N;
-  g.K = K;
-  g.lda = K;
-  g.ldw = K;
-  g.ldc = epilogue == VDR_EPI_SWIGLU ? N / 2 : N;
-  g.ldr = g.ldc;
-  g.omap = identity_map();
   g.a_rows = x_rows;
   LnFold ln;
   ln.stats = stats;
@@ -2039,13 +1930,7 @@ int vdr_op_linear_ln_fold(const void* x, const void* Wf, const float* colsum, co
   ln.cstride = part_stride;
   ln.eps = eps;
   set_ln_fold(g, ln);
-  const hipError_t e = launch_gemm(g, epilogue, variant, (hipStream_t)stream);
-  if (e == hipErrorInvalidValue) {
-    (void)hipGetLastError();
-    return fail(nullptr, VDR_ERR_INVALID, "gemm: unsupported tile variant or shape for the LayerNorm consumer");
-  }
-  OP_TRY(e, "gemm");
-  return VDR_OK;
+  return op_gemm(g, epilogue, variant, stream, "gemm: unsupported tile variant or shape for the LayerNorm consumer");
 }
 
 size_t vdr_prepare_scratch_bytes(int batch, int h, int w, int channels, int out_side) {
@@ -2164,24 +2049,13 @@ int vdr_op_linear_mx(const void* xq, const void* xs, const void* wq, const void*
   if (epilogue == VDR_EPI_BIAS_RESID && !resid) return fail(nullptr, VDR_ERR_INVALID, "EPI_BIAS_RESID needs resid");
   int rc = check_device(nullptr);
   if (rc) return rc;
-  GemmArgs g{};
-  g.A = xq;
+  GemmArgs g = linear(xq, wq, y, M, N, K, epilogue);
   g.a_scale = xs;
-  g.W = wq;
   g.w_scale = ws;
   g.bias = bias;
   g.resid = resid;
   g.gamma = gamma;
-  g.C = y;
   g.c_scale = yscales;
-  g.M = M;
-  g.N = N;
-  g.K = K;
-  g.lda = K;
-  g.ldw = K;
-  g.ldc = epilogue == VDR_EPI_SWIGLU ? N / 2 : N;
-  g.ldr = g.ldc;
-  g.omap = identity_map();
   OP_TRY(launch_gemm_mx(g, epilogue, variant, (hipStream_t)stream), "gemm_mx");
   return VDR_OK;
 }
@@ -2237,29 +2111,12 @@ int vdr_op_patch_embed(const void* images, int in_dtype, const void* W, const fl
   if (p <= 0 || img % p) return fail(nullptr, VDR_ERR_INVALID, "img must be a multiple of p");
   int rc = check_device(nullptr);
   if (rc) return rc;
-  const int g = img / p, n = g * g, Kp = round_up(C * p * p, 64);
-  const int variant = gemm_variant_for(VDR_K_GEMM_PATCH, (int64_t)batch * n, D);
-  const bool fused = patch_gather_ok(in_dtype, p, variant, images);  // (see vdr_forward: no im2col pass, `col` untouched)
-  if (!fused) OP_TRY(launch_im2col(images, in_dtype == VDR_BF16, col, batch, C, img, p, Kp, (hipStream_t)stream), "im2col");
-  GemmArgs a{};
-  a.A = fused ? images : col;
-  if (fused) {
-    a.patch_p = p;
-    a.patch_g = g;
-    a.patch_C = C;
-  }
-  a.W = W;
+  GemmArgs a;
+  int variant;  // (the caller's W as it is; bf16 images with p = 8 / 16 / 32: no im2col pass, `col` untouched)
+  OP_TRY(patch_gemm(nullptr, (hipStream_t)stream, images, in_dtype, col, W, y, batch, C, img, p, D, &a, &variant), "im2col");
   a.bias = bias;
   a.pos = pos;
-  a.C = y;
-  a.M = (int64_t)batch * n;
-  a.N = D;
-  a.K = Kp;
-  a.lda = Kp;
-  a.ldw = Kp;
-  a.ldc = D;
-  a.ldr = D;
-  a.omap = RowMap{n, row_stride, row_offset};
+  a.omap = RowMap{(img / p) * (img / p), row_stride, row_offset};
   OP_TRY(launch_gemm(a, EPI_PATCH, variant, (hipStream_t)stream), "patch gemm");
   return VDR_OK;
 }
