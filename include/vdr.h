@@ -230,6 +230,26 @@ typedef struct {
 int vdr_forward_layers(vdr_handle h, const void* images, int in_dtype, int batch, const vdr_layer_out* outs, int n_outs,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* Attention maps of any block (DINO get_last_selfattention, output_attentions, the per-head CLS heat map): the
+ * normalised softmax(q k^T dh^-0.5) of one block's attention, computed from the block's own qkv activation right after
+ * its attention (vdr_op_attention_probs).  One map: */
+typedef struct {
+  int32_t layer;     /* block 0 .. L-1 whose attention is reported                                  */
+  int32_t q_rows;    /* 1 .. N: the first q_rows query rows (1 = the CLS row, N = the full map)      */
+  int32_t head_mean; /* 0: [B, H, q_rows, N]; 1: [B, q_rows, N], mean over the heads                 */
+  int32_t out_dtype; /* VDR_F32 | VDR_BF16                                                           */
+  void* out;         /* device, contiguous; image b's map starts at out + b * (per-image elements)   */
+} vdr_attn_map;
+
+/* vdr_forward_layers plus n_maps >= 1 attention maps, in one forward.  The outs have exactly vdr_forward_layers' meaning,
+ * checks and bits (n_outs may be 0 with outs NULL).  Blocks past the largest requested layer (outs and maps together) do
+ * not run; a last block whose only requests are maps stops after its attention.  Supported models, workspace and the
+ * VDR_ERR_UNSUPPORTED refusals: those of vdr_forward_layers.  Refused before the device is touched (VDR_ERR_INVALID): null
+ * maps, n_maps <= 0, a null out, q_rows outside [1, N], head_mean not 0 / 1, an unknown dtype, a layer out of range.
+ * The map launches are booked as VDR_K_FINAL_LN. */
+int vdr_forward_attn_maps(vdr_handle h, const void* images, int in_dtype, int batch, const vdr_layer_out* outs, int n_outs,
+                          const vdr_attn_map* maps, int n_maps, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Replaces: TransformerNoduleClassifier.forward up to x[:,0,:]
  * (models_archs.py:141-147): tokens [batch, seq, D] fp32/bf16 on device ->
  * [cls ; tokens] -> (input LN) -> L blocks -> out by out_mode
@@ -416,6 +436,16 @@ int vdr_op_attention_hd(const void* qkv, void* out, int batch, int seq, int head
  *   and 4 take the one-shot kernel at seq <= 288.  head_dim as vdr_op_attention_hd. */
 int vdr_op_attention_varlen(const void* qkv, void* out, int batch, int seq, int heads, int head_dim,
                             const int32_t* lens, int len_add, int variant, void* stream);
+
+/* The attention map of the same qkv: P = softmax(q k^T dh^-0.5) of the first q_rows query rows of every (batch entry,
+ * head), normalised, fp32 or bf16 (out_dtype; bf16 is one rounding of the fp32 value).
+ *   out [batch, H, q_rows, seq] (head_mean = 0) or [batch, q_rows, seq] (head_mean = 1: the mean over the heads)
+ *   s = q.k in fp32 on the bf16 MFMA, t = s * c (c the fp32 dh^-0.5 log2(e) of the attention kernels), m = max t,
+ *   e = exp2(t - m), l = sum e (fp32), p = e * (1 / l) with one correctly rounded division per row; head_mean:
+ *   (sum of p over the heads in head order, fp32) * RN(1 / H).  No atomics: a row's bits depend neither on batch nor
+ *   on the launch.  head_dim in {32, 64, 96, 128} (else VDR_ERR_UNSUPPORTED), 1 <= q_rows <= seq. */
+int vdr_op_attention_probs(const void* qkv, void* out, int batch, int seq, int heads, int head_dim, int q_rows,
+                           int head_mean, int out_dtype, void* stream);
 
 /* SAM / MedSAM Attention.forward with use_rel_pos (third-party segment_anything ImageEncoderViT, called at
  * tfds_dense_descriptor.py:123): per (window, head) softmax(q k^T dh^-0.5 + q.Rh[qh-kh] + q.Rw[qw-kw]) v.

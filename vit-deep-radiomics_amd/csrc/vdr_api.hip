@@ -954,9 +954,26 @@ int block_tail_cls(vdr_model* m, hipStream_t s, const Carve& w, const LayerW& L,
 // vdr_forward_layers: the outputs to write after each block, and the first image of the micro-batch being run
 struct EmitList {
   std::vector<std::vector<const vdr_layer_out*>> at;  // [block] -> outputs of that block
+  std::vector<std::vector<const vdr_attn_map*>> maps; // [block] -> attention maps of that block (vdr_forward_attn_maps)
   int last = -1;                                      // last block that runs (the largest requested layer)
   int b0 = 0;
 };
+
+// Writes one attention map for images b0 .. b0 + mb - 1 from the qkv activation of their micro-batch, right after the
+// block's attention (nothing rewrites w.qkv before the next block's qkv GEMM, later on the same stream).  Booked as
+// VDR_K_FINAL_LN, the class of every output write: three score products per map row, K read per pass.
+int write_attn_map(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, const vdr_attn_map& a, int b0) {
+  const vdr_config& c = m->cfg;
+  const int H = c.heads, D = c.dim;
+  const size_t es = a.out_dtype == VDR_BF16 ? 2 : 4;
+  const size_t per_image = (size_t)(a.head_mean ? 1 : H) * a.q_rows * ntok;
+  char* dst = (char*)a.out + (size_t)b0 * per_image * es;
+  Scope sc(m, s, VDR_K_FINAL_LN, 6.0 * (double)mb * a.q_rows * ntok * D,
+           (double)mb * (3.0 * ntok * D * 2 + (double)a.q_rows * D * 2 + (double)per_image * es));
+  VDR_TRY(launch_attention_probs(w.qkv, dst, mb, ntok, H, D / H, a.q_rows, a.head_mean, a.out_dtype == VDR_BF16, s),
+          "attention_probs");
+  return VDR_OK;
+}
 
 // Writes one output for images b0 .. b0 + mb - 1 from the residual stream of their micro-batch, on its stream: the rows
 // out_mode selects, through the model's final LayerNorm (norm = 1) or raw, read from the stream's fp32 master copy when
@@ -1031,6 +1048,15 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
     VDR_TRY(launch_attention(w.qkv, w.o, mb, ntok, H, attn_variant, s, nullptr, lens, len_add, D / H), "attention");
     return (int)VDR_OK;
   };
+  // vdr_forward_attn_maps: block i's maps, from its qkv, right after its attention
+  auto maps_after_attention = [&](int i) {
+    if (el)
+      for (const vdr_attn_map* a : el->maps[i])
+        if (int e = write_attn_map(m, s, w, mb, ntok, *a, el->b0)) return e;
+    return (int)VDR_OK;
+  };
+  // a last block whose only requests are maps stops after its attention
+  auto maps_only_last = [&](int i) { return el && i == el->last && el->at[i].empty(); };
   // block i == tail_at ends after its attention: the rest of it on the CLS rows, then its outputs
   auto cls_tail_exit = [&](int i, const LayerW& L) {
     *compact = true;
@@ -1053,6 +1079,8 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
       if ((rc = gemm_mx(m, s, VDR_K_GEMM_QKV, w.h, w.hs, L.qkv_q, L.qkv_s, L.bqkv, nullptr, nullptr, w.qkv, nullptr, M, 3 * D, D, EPI_BIAS)))
         return rc;
       if ((rc = attention())) return rc;
+      if ((rc = maps_after_attention(i))) return rc;
+      if (maps_only_last(i)) return VDR_OK;
       if (i == tail_at) return cls_tail_exit(i, L);
       // the out-projection stays bf16: quantising it too measured 0.987 row cosine at 40 blocks (gate 0.99)
       GemmArgs proj = linear(w.o, L.wproj, w.x, M, D, D, EPI_BIAS_RESID);
@@ -1104,6 +1132,8 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
       qkv.a_rows = w.Mp;
       if ((rc = gemm(m, s, VDR_K_GEMM_QKV, qkv, EPI_BIAS, cons))) return rc;
       if ((rc = attention())) return rc;
+      if ((rc = maps_after_attention(i))) return rc;
+      if (maps_only_last(i)) return VDR_OK;
       if (i == tail_at) return cls_tail_exit(i, L);
       GemmArgs proj = linear(w.o, L.wproj, w.x, M, D, D, EPI_BIAS_RESID);
       proj.bias = L.bproj;
@@ -1138,6 +1168,8 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
     qkv.a_rows = w.Mp;
     if ((rc = gemm(m, s, VDR_K_GEMM_QKV, qkv, EPI_BIAS))) return rc;
     if ((rc = attention())) return rc;
+    if ((rc = maps_after_attention(i))) return rc;
+    if (maps_only_last(i)) return VDR_OK;
     if (i == tail_at) return cls_tail_exit(i, L);
     // the residual linears: C = x + gamma * (A . W^T + bias), in place (pre-LN, with the fp32 master copy under
     // resid_fp32) or into w.h (post-LN, the input of the LayerNorm after them)
@@ -1671,10 +1703,40 @@ int vdr_forward(vdr_handle m, const void* images, int in_dtype, int batch, void*
   });
 }
 
+// vdr_forward_layers and vdr_forward_attn_maps (fn: the name the model refusals carry); the callers have checked the
+// outs / maps arrays themselves
+static int forward_layers_impl(const char* fn, vdr_handle m, const void* images, int in_dtype, int batch, const vdr_layer_out* outs,
+                               int n_outs, const vdr_attn_map* maps, int n_maps, void* workspace, size_t workspace_bytes,
+                               void* stream);
+
 int vdr_forward_layers(vdr_handle m, const void* images, int in_dtype, int batch, const vdr_layer_out* outs, int n_outs,
                        void* workspace, size_t workspace_bytes, void* stream) {
   // argument checks that need no model first (they also hold for a null handle), then the model's
   if (!outs || n_outs <= 0) return fail(m, VDR_ERR_INVALID, "null outs or n_outs <= 0");
+  return forward_layers_impl("vdr_forward_layers", m, images, in_dtype, batch, outs, n_outs, nullptr, 0, workspace, workspace_bytes,
+                             stream);
+}
+
+int vdr_forward_attn_maps(vdr_handle m, const void* images, int in_dtype, int batch, const vdr_layer_out* outs, int n_outs,
+                          const vdr_attn_map* maps, int n_maps, void* workspace, size_t workspace_bytes, void* stream) {
+  // the checks that need no model come first, as vdr_forward_layers orders its own
+  if (!maps || n_maps <= 0) return fail(m, VDR_ERR_INVALID, "null maps or n_maps <= 0");
+  for (int k = 0; k < n_maps; ++k) {
+    const vdr_attn_map& a = maps[k];
+    const std::string at = "maps[" + std::to_string(k) + "]: ";
+    if (!a.out) return fail(m, VDR_ERR_INVALID, at + "null out");
+    if (a.q_rows < 1) return fail(m, VDR_ERR_INVALID, at + "q_rows must be >= 1");
+    if (a.head_mean != 0 && a.head_mean != 1) return fail(m, VDR_ERR_INVALID, at + "head_mean must be 0 or 1");
+    if (a.out_dtype != VDR_F32 && a.out_dtype != VDR_BF16) return fail(m, VDR_ERR_INVALID, at + "out_dtype");
+  }
+  if (n_outs < 0 || (n_outs > 0 && !outs)) return fail(m, VDR_ERR_INVALID, "null outs with n_outs > 0, or n_outs < 0");
+  return forward_layers_impl("vdr_forward_attn_maps", m, images, in_dtype, batch, outs, n_outs, maps, n_maps, workspace,
+                             workspace_bytes, stream);
+}
+
+static int forward_layers_impl(const char* fn, vdr_handle m, const void* images, int in_dtype, int batch, const vdr_layer_out* outs,
+                               int n_outs, const vdr_attn_map* maps, int n_maps, void* workspace, size_t workspace_bytes,
+                               void* stream) {
   for (int k = 0; k < n_outs; ++k) {
     const vdr_layer_out& o = outs[k];
     const std::string at = "outs[" + std::to_string(k) + "]: ";
@@ -1689,14 +1751,25 @@ int vdr_forward_layers(vdr_handle m, const void* images, int in_dtype, int batch
   }
   if (!m || !images || !workspace || batch <= 0) return fail(m, VDR_ERR_INVALID, "null/invalid argument");
   const vdr_config& c = m->cfg;
-  if (!c.patch) return fail(m, VDR_ERR_UNSUPPORTED, "vdr_forward_layers: image models only (token model)");
-  if (c.window > 0) return fail(m, VDR_ERR_UNSUPPORTED, "vdr_forward_layers: not for the SAM encoder (no final norm, a neck)");
-  if (!c.pre_ln) return fail(m, VDR_ERR_UNSUPPORTED, "vdr_forward_layers: pre-LN models only");
-  if (c.layers <= 0) return fail(m, VDR_ERR_UNSUPPORTED, "vdr_forward_layers: the model has no blocks");
+  if (!c.patch) return fail(m, VDR_ERR_UNSUPPORTED, std::string(fn) + ": image models only (token model)");
+  if (c.window > 0) return fail(m, VDR_ERR_UNSUPPORTED, std::string(fn) + ": not for the SAM encoder (no final norm, a neck)");
+  if (!c.pre_ln) return fail(m, VDR_ERR_UNSUPPORTED, std::string(fn) + ": pre-LN models only");
+  if (c.layers <= 0) return fail(m, VDR_ERR_UNSUPPORTED, std::string(fn) + ": the model has no blocks");
   if (in_dtype != VDR_F32 && in_dtype != VDR_BF16) return fail(m, VDR_ERR_INVALID, "in_dtype");
   const int D = c.dim;
   EmitList el;
   el.at.resize(c.layers);
+  el.maps.resize(c.layers);
+  for (int k = 0; k < n_maps; ++k) {
+    const vdr_attn_map& a = maps[k];
+    const std::string at = "maps[" + std::to_string(k) + "]: ";
+    if (a.layer < 0 || a.layer >= c.layers)
+      return fail(m, VDR_ERR_INVALID, at + "layer " + std::to_string(a.layer) + " out of range 0.." + std::to_string(c.layers - 1));
+    if (a.q_rows > m->n_tokens)
+      return fail(m, VDR_ERR_INVALID, at + "q_rows " + std::to_string(a.q_rows) + " exceeds the " + std::to_string(m->n_tokens) + " tokens");
+    el.maps[a.layer].push_back(&a);
+    if (a.layer > el.last) el.last = a.layer;
+  }
   for (int k = 0; k < n_outs; ++k) {
     const vdr_layer_out& o = outs[k];
     const std::string at = "outs[" + std::to_string(k) + "]: ";
@@ -2087,6 +2160,22 @@ int vdr_op_attention_varlen(const void* qkv, void* out, int batch, int seq, int 
   if (rc) return rc;
   OP_TRY(launch_attention(qkv, out, batch, seq, heads, variant, (hipStream_t)stream, nullptr, lens, len_add, head_dim),
          "attention");
+  return VDR_OK;
+}
+
+int vdr_op_attention_probs(const void* qkv, void* out, int batch, int seq, int heads, int head_dim, int q_rows, int head_mean,
+                           int out_dtype, void* stream) {
+  if (head_dim != 32 && head_dim != 64 && head_dim != 96 && head_dim != 128)
+    return fail(nullptr, VDR_ERR_UNSUPPORTED, "head dim must be 32, 64, 96 or 128");
+  if (!qkv || !out) return fail(nullptr, VDR_ERR_INVALID, "null argument");
+  if (batch <= 0 || seq <= 0 || heads <= 0) return fail(nullptr, VDR_ERR_INVALID, "bad shape");
+  if (q_rows < 1 || q_rows > seq) return fail(nullptr, VDR_ERR_INVALID, "q_rows must be in [1, seq]");
+  if (head_mean != 0 && head_mean != 1) return fail(nullptr, VDR_ERR_INVALID, "head_mean must be 0 or 1");
+  if (out_dtype != VDR_F32 && out_dtype != VDR_BF16) return fail(nullptr, VDR_ERR_INVALID, "out_dtype");
+  int rc = check_device(nullptr);
+  if (rc) return rc;
+  OP_TRY(launch_attention_probs(qkv, out, batch, seq, heads, head_dim, q_rows, head_mean, out_dtype == VDR_BF16, (hipStream_t)stream),
+         "attention_probs");
   return VDR_OK;
 }
 

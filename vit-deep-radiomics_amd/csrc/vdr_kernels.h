@@ -146,6 +146,11 @@ hipError_t launch_attention(const void* qkv, void* out, int batch, int seq, int 
 //   qkv [batch*seq, 3*heads*head_dim], out [batch*seq, heads*head_dim]
 hipError_t launch_attention_hd(const void* qkv, void* out, int batch, int seq, int heads, int head_dim, hipStream_t s,
                                const int* lens, int len_add);
+// attention maps (attention_probs.hip): softmax(q k^T dh^-1/2) of the first q_rows query rows of every (sequence, head)
+// of the same qkv; out [batch, heads, q_rows, seq] (head_mean = 0) or [batch, q_rows, seq] (1, mean over the heads),
+// fp32 or bf16 (out_bf16).  head_dim 32 / 64 / 96 / 128, 1 <= q_rows <= seq
+hipError_t launch_attention_probs(const void* qkv, void* out, int batch, int seq, int heads, int head_dim, int q_rows,
+                                  int head_mean, int out_bf16, hipStream_t s);
 
 // SAM / MedSAM decomposed relative position bias (attention_relpos.hip)
 //   qkv rows are S*S-token windows (or whole grids) back to back

@@ -37,6 +37,11 @@ class vdr_layer_out(C.Structure):
                 ("ld", C.c_int64), ("out", C.c_void_p)]
 
 
+class vdr_attn_map(C.Structure):
+    _fields_ = [("layer", C.c_int32), ("q_rows", C.c_int32), ("head_mean", C.c_int32), ("out_dtype", C.c_int32),
+                ("out", C.c_void_p)]
+
+
 # every symbol include/vdr.h declares: name -> (restype, argtypes)
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SYMBOLS = {
@@ -53,6 +58,8 @@ SYMBOLS = {
     "vdr_workspace_bytes": (_I, [_P, _I, _I, C.POINTER(C.c_size_t)]),
     "vdr_forward": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, C.c_size_t, _P]),
     "vdr_forward_layers": (_I, [_P, _P, _I, _I, C.POINTER(vdr_layer_out), _I, _P, C.c_size_t, _P]),
+    "vdr_forward_attn_maps": (_I, [_P, _P, _I, _I, C.POINTER(vdr_layer_out), _I, C.POINTER(vdr_attn_map), _I, _P, C.c_size_t,
+                                   _P]),
     "vdr_forward_tokens": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _P, C.c_size_t, _P]),
     "vdr_forward_tokens_varlen": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _I, _P, C.c_size_t, _P]),
     "vdr_op_layernorm": (_I, [_P, _I, _P, _I, _P, _P, _L, _I, _F, _P]),
@@ -79,6 +86,7 @@ SYMBOLS = {
     "vdr_op_attention": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "vdr_op_attention_hd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "vdr_op_attention_varlen": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
+    "vdr_op_attention_probs": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vdr_op_attention_relpos": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "vdr_op_patch_embed": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vdr_profile_enable": (_I, [_P, _I]),

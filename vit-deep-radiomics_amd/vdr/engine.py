@@ -83,6 +83,18 @@ class LayerOut:
     out: "torch.Tensor | None" = None
 
 
+@dataclass
+class AttnMap:
+    """One attention map of Engine.forward_attn_maps (vdr_attn_map): softmax(q k^T / sqrt(dh)) of block `layer`, its first
+    q_rows query rows (1: the CLS row; N: the full map).  [B, H, q_rows, N], or [B, q_rows, N] with head_mean (the mean
+    over the heads).  out: a caller-owned contiguous tensor of that shape, or None to allocate one of `dtype`."""
+    layer: int
+    q_rows: int = 1
+    head_mean: bool = False
+    dtype: torch.dtype = torch.float32
+    out: "torch.Tensor | None" = None
+
+
 def _stream_ptr(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
@@ -206,10 +218,62 @@ class Engine:
         if images.dtype not in _DT:
             images = images.float()
         images = images.to(self.device).contiguous()
-        B, D = images.shape[0], cfg.dim
+        B = images.shape[0]
         specs = list(specs)
         if not specs:
             raise ValueError("forward_layers needs at least one LayerOut")
+        arr, outs = self._layer_outs(specs, B)
+        ws = self._workspace(B)
+        L.check(self.lib.vdr_forward_layers(self.h, images.data_ptr(), _DT[images.dtype], B, arr, len(specs), ws.data_ptr(),
+                                            ws.numel(), _stream_ptr(self.device)), self.h)
+        return outs
+
+    def forward_attn_maps(self, images: torch.Tensor, maps, outs=()):
+        """One forward that writes attention maps (vdr_forward_attn_maps): maps is a sequence of AttnMap, outs an optional
+        sequence of LayerOut (forward_layers' outputs, the same bits).  Returns (feature tensors, map tensors), each in
+        the order given.  Caller-owned buffers are checked, never converted or copied."""
+        cfg = self.cfg
+        if images.dim() != 4 or tuple(images.shape[1:]) != (cfg.in_chans, cfg.img, cfg.img):
+            raise ValueError(f"images must be [B,{cfg.in_chans},{cfg.img},{cfg.img}], got {tuple(images.shape)}")
+        if images.dtype not in _DT:
+            images = images.float()
+        images = images.to(self.device).contiguous()
+        B, N, H = images.shape[0], cfg.n_tokens, cfg.heads
+        maps, specs = list(maps), list(outs)
+        if not maps:
+            raise ValueError("forward_attn_maps needs at least one AttnMap")
+        arr, feats = self._layer_outs(specs, B) if specs else (None, [])
+        marr = (L.vdr_attn_map * len(maps))()
+        got = []
+        for k, mp in enumerate(maps):
+            if not 1 <= int(mp.q_rows) <= N:
+                raise ValueError(f"maps[{k}]: q_rows must be in [1, {N}], got {mp.q_rows}")
+            shape = (B, int(mp.q_rows), N) if mp.head_mean else (B, H, int(mp.q_rows), N)
+            out = mp.out
+            if out is None:
+                if mp.dtype not in _DT:
+                    raise TypeError(f"maps[{k}]: dtype must be float32 or bfloat16, got {mp.dtype}")
+                out = torch.empty(shape, dtype=mp.dtype, device=self.device)
+            if out.dtype not in _DT:
+                raise TypeError(f"maps[{k}]: out must be float32 or bfloat16, got {out.dtype}")
+            if out.device != self.device:
+                raise ValueError(f"maps[{k}]: out must live on {self.device}")
+            if tuple(out.shape) != shape:
+                raise ValueError(f"maps[{k}]: out must be {shape}, got {tuple(out.shape)}")
+            if not out.is_contiguous():
+                raise ValueError(f"maps[{k}]: out must be contiguous")
+            marr[k].layer, marr[k].q_rows, marr[k].head_mean = int(mp.layer), int(mp.q_rows), int(bool(mp.head_mean))
+            marr[k].out_dtype, marr[k].out = _DT[out.dtype], out.data_ptr()
+            got.append(out)
+        ws = self._workspace(B)
+        L.check(self.lib.vdr_forward_attn_maps(self.h, images.data_ptr(), _DT[images.dtype], B, arr, len(specs), marr, len(maps),
+                                               ws.data_ptr(), ws.numel(), _stream_ptr(self.device)), self.h)
+        return feats, got
+
+    def _layer_outs(self, specs, B):
+        """vdr_layer_out array + the output tensors of forward_layers' specs (allocated or checked)."""
+        cfg = self.cfg
+        D = cfg.dim
         arr = (L.vdr_layer_out * len(specs))()
         outs = []
         for k, sp in enumerate(specs):
@@ -238,10 +302,7 @@ class Engine:
             arr[k].layer, arr[k].out_mode, arr[k].out_dtype = int(sp.layer), int(sp.mode), _DT[out.dtype]
             arr[k].norm, arr[k].ld, arr[k].out = int(bool(sp.norm)), ld, out.data_ptr()
             outs.append(out)
-        ws = self._workspace(B)
-        L.check(self.lib.vdr_forward_layers(self.h, images.data_ptr(), _DT[images.dtype], B, arr, len(specs), ws.data_ptr(),
-                                            ws.numel(), _stream_ptr(self.device)), self.h)
-        return outs
+        return arr, outs
 
     def forward_tokens(self, tokens: torch.Tensor, out_mode: int = L.OUT_CLS, out_dtype=torch.float32,
                        lengths=None) -> torch.Tensor:

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .engine import Engine, LayerOut, VdrConfig
+from .engine import AttnMap, Engine, LayerOut, VdrConfig
 
 # geometries BASELINE.json names + the two the reference itself loads
 ARCHS = {
@@ -159,6 +159,50 @@ class VitDescriptorModel:
             specs.append(LayerOut(blocks[-1], L.OUT_POOLED, out=out[:, len(blocks) * D:]))
         self.engine.forward_layers(x, specs)
         return out
+
+    def _maps_ok(self, what, cls_only):
+        if self.cfg.window > 0:
+            raise ValueError(f"{what}: attention maps of the SAM encoder (windowed, relative-position attention) are not "
+                             "available; they are for ViT / DINOv2 models")
+        if not self.cfg.layers:
+            raise ValueError(f"{what}: the model has no transformer blocks")
+        if cls_only and not self.cfg.has_cls:
+            raise ValueError(f"{what}: cls_only needs a model with a CLS token")
+
+    def get_last_selfattention(self, x: torch.Tensor) -> torch.Tensor:
+        """DINO's get_last_selfattention: the softmax attention of the last block, every query row, [B, H, N, N] fp32."""
+        self._maps_ok("get_last_selfattention", False)
+        N = self.cfg.n_tokens
+        _, (att,) = self.engine.forward_attn_maps(x, [AttnMap(self.cfg.layers - 1, N)])
+        return att
+
+    def get_attention_maps(self, x: torch.Tensor, layers=None, cls_only: bool = True, head_mean: bool = False,
+                           reshape: bool = False):
+        """Attention maps of the blocks `layers` (block indices; None: the last block), all from one forward, fp32.
+        cls_only: the CLS query row only, [B, H, N] ([B, N] with head_mean, the mean over the heads); else the full map
+        [B, H, N, N] ([B, N, N]).  reshape (cls_only): the patch key columns only, on the dense-descriptor grid:
+        [B, H, g, g] ([B, g, g]).  An int or None gives one tensor, a sequence a tuple in the order given."""
+        self._maps_ok("get_attention_maps", cls_only)
+        if reshape and not cls_only:
+            raise ValueError("get_attention_maps: reshape needs cls_only")
+        single = layers is None or isinstance(layers, (int, np.integer))
+        idx = [self.cfg.layers - 1] if layers is None else [int(layers)] if single else [int(i) for i in layers]
+        if not idx:
+            raise ValueError("get_attention_maps: no block index given")
+        bad = [i for i in idx if not 0 <= i < self.cfg.layers]
+        if bad:
+            raise ValueError(f"block indices {bad} out of range 0..{self.cfg.layers - 1}")
+        N, ncls = self.cfg.n_tokens, 1 if self.cfg.has_cls else 0
+        _, got = self.engine.forward_attn_maps(x, [AttnMap(i, 1 if cls_only else N, head_mean) for i in idx])
+        res = []
+        for t in got:
+            if cls_only:
+                t = t[:, 0] if head_mean else t[:, :, 0]
+                if reshape:
+                    g = self.cfg.img // self.cfg.patch
+                    t = t[..., ncls:].reshape(*t.shape[:-1], g, g)
+            res.append(t)
+        return res[0] if single else tuple(res)
 
     def __call__(self, x):
         return self.image_encoder(x) if self.cfg.window > 0 else self.forward_features(x)

@@ -205,6 +205,24 @@ def attention(qkv: torch.Tensor, batch: int, seq: int, heads: int, variant=0, he
     return out
 
 
+def attention_probs(qkv: torch.Tensor, batch: int, seq: int, heads: int, head_dim=64, q_rows=None, head_mean=False,
+                    out_dtype=torch.float32):
+    """The attention map of the same packed qkv: softmax(q k^T / sqrt(head_dim)) of the first q_rows query rows (None:
+    all seq) of every (batch entry, head), normalised.  Returns [batch, heads, q_rows, seq], or [batch, q_rows, seq] with
+    head_mean (the mean over the heads); float32 or bfloat16."""
+    lib = L.load()
+    assert qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.is_contiguous()
+    assert qkv.shape == (batch * seq, 3 * heads * head_dim)
+    q_rows = seq if q_rows is None else int(q_rows)
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"out_dtype must be float32 or bfloat16, got {out_dtype}")
+    shape = (batch, q_rows, seq) if head_mean else (batch, heads, q_rows, seq)
+    out = torch.empty(shape, dtype=out_dtype, device=qkv.device)
+    L.check(lib.vdr_op_attention_probs(qkv.data_ptr(), out.data_ptr(), batch, seq, heads, head_dim, q_rows, int(bool(head_mean)),
+                                       L.VDR_BF16 if out_dtype == torch.bfloat16 else L.VDR_F32, _s(qkv)))
+    return out
+
+
 def patch_embed(images, weight, bias, p, pos=None, row_stride=None, row_offset=0, out=None):
     """images [B,C,H,H] fp32/bf16; weight [D,C,p,p] (any float dtype); returns bf16 [B*row_stride, D]."""
     lib = L.load()
