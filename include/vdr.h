@@ -81,7 +81,7 @@ typedef enum {
  * passes to its third-party ViTs (tfds_dense_descriptor.py:87,104) and to
  * nn.TransformerEncoderLayer (models_archs.py:130-135). */
 typedef struct {
-  int32_t img;        /* square input side in pixels (224, 336, 896 ...); 0 for a token model */
+  int32_t img;        /* native square input side in pixels (224, 336, 896 ...: pos_embed's grid; other sizes: vdr_set_input_size); 0 for a token model */
   int32_t patch;      /* patch side p (14, 16); 0 for a token model                           */
   int32_t in_chans;   /* 3                                                                    */
   int32_t dim;        /* D                                                                    */
@@ -185,6 +185,28 @@ int vdr_set_weight(vdr_handle h, const char* name, const float* host, const int6
  * VDR_ERR_INCOMPLETE until it has run. */
 int vdr_finalize(vdr_handle h);
 
+/* Run an image model at another input size, square or rectangular: DINOv2 / transformers interpolate_pos_encoding,
+ * done once per size instead of in every forward.  Load-time class (like vdr_finalize: may allocate and synchronise;
+ * not for the hot path).  After it every image entry point of the handle -- vdr_forward, vdr_forward_layers,
+ * vdr_forward_attn_maps, vdr_workspace_bytes -- takes images [batch, in_chans, height, width]; n = (height / patch) *
+ * (width / patch) patches in (y, x) order, N = n + has_cls tokens.
+ *   has_pos = 1: a device table [N, D] fp32 is built -- the CLS row (when there is one) copied unchanged, the patch rows
+ *   resampled from the loaded pos_embed's (img / patch)^2 grid by vdr_op_interpolate_pos -- and the forward reads it
+ *   wherever it reads pos_embed.  has_pos = 0: geometry only.  height == width == img selects the loaded table itself:
+ *   a handle that went to another size and back gives bitwise the features of one that never moved.  One table is
+ *   kept (no cache of sizes); a later vdr_finalize (weights changed) rebuilds it for the size in force.  The hot-path
+ *   promise (no allocation, no synchronisation in vdr_forward*) holds at any size.  Workspaces must be sized again
+ *   (vdr_workspace_bytes); one sized for a smaller geometry is refused with VDR_ERR_WORKSPACE.
+ * Supported: pre-LN image models without windows (plain ViT, DINOv2; every vdr_config switch) and layers == 0
+ * patch-embedding models.  bf16 images with p in {8, 16, 32} keep the im2col-free gather at square sizes; rectangular
+ * sizes go through im2col.  Not reproduced: DINOv2's older scale_factor + interpolate_offset form and antialiasing.
+ * VDR_ERR_INVALID, before the handle or a device is touched: height <= 0, width <= 0; then a null handle; then a side
+ * that is not a multiple of patch.  VDR_ERR_UNSUPPORTED: SAM / MedSAM (window > 0: its absolute and relative position
+ * tables and the window partition are tied to its grid), token models (patch == 0), post-LN models with blocks.
+ * VDR_ERR_INCOMPLETE: vdr_finalize has not run. */
+int vdr_set_input_size(vdr_handle h, int height, int width);
+int vdr_get_input_size(vdr_handle h, int* height, int* width);   /* (img, img) until the first set */
+
 /* Number of weight tensors the config expects, and the i-th expected name. */
 int vdr_num_weights(vdr_handle h);
 const char* vdr_weight_name(vdr_handle h, int i);
@@ -198,7 +220,7 @@ int vdr_workspace_bytes(vdr_handle h, int batch, int seq, size_t* out);
 /* Replaces: model.image_encoder(x) / model.patch_embed(x)
  * (tfds_dense_descriptor.py:123,128) followed by the CLS / patch-token slice
  * (models_archs.py:147; tfds_dense_descriptor.py:130-133), batched.
- *   images : device, NCHW [batch, in_chans, img, img], dtype in_dtype, values as the
+ *   images : device, NCHW [batch, in_chans, img, img] ([.., height, width] after vdr_set_input_size), dtype in_dtype, values as the
  *            reference feeds them (raw [0,1]; no mean/std normalisation is applied)
  *   out    : device, shape by out_mode, dtype out_dtype, C-contiguous, row b = image b */
 int vdr_forward(vdr_handle h, const void* images, int in_dtype, int batch, void* out, int out_mode,
@@ -456,6 +478,15 @@ int vdr_op_attention_probs(const void* qkv, void* out, int batch, int seq, int h
  *   out   [batch*S*S, H*64] bf16.   S in {4, 7, 10, 14} (one pass) or 64 (online softmax). */
 int vdr_op_attention_relpos(const void* qkv, const float* rel_pos_h, const float* rel_pos_w, float* rel, void* out,
                             int batch, int S, int heads, void* stream);
+
+/* DINOv2 / transformers interpolate_pos_encoding: the patch rows of a learned position table resampled from a
+ * gh0 x gw0 grid to gh x gw (bicubic, A = -0.75, align_corners = False, size = (gh, gw), no antialias, border
+ * indices clamped).  pos, out: device fp32, [gh0*gw0, D] and [gh*gw, D], row-major over (y, x).  No CLS row.
+ * Source coordinate (o + 0.5) * (g0 / g) - 0.5, the cubic-convolution weights and the 16-tap sum are evaluated in
+ * fp64 and rounded to fp32 once: the result is F.interpolate(table.double(), size=(gh, gw), mode="bicubic",
+ * align_corners=False) rounded once (torch's fp32 path rounds the source coordinate to fp32 and differs by a few ulp).
+ * At most 2^20 grid cells either side. */
+int vdr_op_interpolate_pos(const float* pos, int gh0, int gw0, int D, float* out, int gh, int gw, void* stream);
 
 /* nn.Conv2d(in_chans, D, kernel=p, stride=p) + flatten(2).transpose(1,2) — DINOv2 PatchEmbed,
  * the op called at tfds_dense_descriptor.py:128.

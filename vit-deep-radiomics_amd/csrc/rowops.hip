@@ -370,21 +370,21 @@ hipError_t launch_pool_rows(const void* x, int in_bf16, int norm, const float* g
 }
 
 // ---------------------------------------------------------------------------------------------
-// im2col for Conv2d(C, D, kernel=p, stride=p): col[b*n + py*g + px][c*p*p + ky*p + kx]
-// One thread writes 8 consecutive k (one 16-byte store).
+// im2col for Conv2d(C, D, kernel=p, stride=p) over [B, C, H, W] images, gh x gw = (H / p) x (W / p) patches each:
+// col[b*n + py*gw + px][c*p*p + ky*p + kx].  One thread writes 8 consecutive k (one 16-byte store).
 // ---------------------------------------------------------------------------------------------
 template <bool IN_BF16>
 __global__ __launch_bounds__(256) void im2col_kernel(const void* __restrict__ images, bf16_t* __restrict__ col,
-                                                     int64_t total8, int C, int img, int p, int g, int Kp, int fast) {
+                                                     int64_t total8, int C, int H, int W, int p, int gh, int gw, int Kp, int fast) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= total8) return;
   const int k8 = Kp >> 3;
   const int64_t row = idx / k8;
   const int kk = (int)(idx - row * k8) * 8;
-  const int n = g * g;
+  const int n = gh * gw;
   const int64_t b = row / n;
   const int pi = (int)(row - b * n);
-  const int py = pi / g, px = pi - py * g;
+  const int py = pi / gw, px = pi - py * gw;
   const int pp = p * p;
   const int Kreal = C * pp;
   bf16x8 o;
@@ -392,7 +392,7 @@ __global__ __launch_bounds__(256) void im2col_kernel(const void* __restrict__ im
     const int c = kk / pp;
     const int rem = kk - c * pp;
     const int ky = rem / p, kx = rem - ky * p;
-    const int64_t src = ((b * C + c) * img + (py * p + ky)) * (int64_t)img + px * p + kx;
+    const int64_t src = ((b * C + c) * H + (py * p + ky)) * (int64_t)W + px * p + kx;
     if (IN_BF16) {
       o = *reinterpret_cast<const bf16x8*>((const bf16_t*)images + src);
     } else {
@@ -413,7 +413,7 @@ __global__ __launch_bounds__(256) void im2col_kernel(const void* __restrict__ im
         const int c = k / pp;
         const int rem = k - c * pp;
         const int ky = rem / p, kx = rem - ky * p;
-        const int64_t src = ((b * C + c) * img + (py * p + ky)) * (int64_t)img + px * p + kx;
+        const int64_t src = ((b * C + c) * H + (py * p + ky)) * (int64_t)W + px * p + kx;
         val = IN_BF16 ? (float)((const bf16_t*)images)[src] : ((const float*)images)[src];
       }
       o[e] = (bf16_t)val;
@@ -430,17 +430,17 @@ __global__ __launch_bounds__(256) void im2col_kernel(const void* __restrict__ im
 // 2.0 TB/s of pixels + rows in the reference's dinov2 mode; this form: see DESIGN.md §6 f-2.)
 template <bool IN_BF16>
 __global__ __launch_bounds__(256) void im2col_rows_kernel(const void* __restrict__ images, bf16_t* __restrict__ col, int C,
-                                                          int img, int p, int g, int Kp, int tpb, int blocks_per_row) {
+                                                          int H, int W, int p, int gh, int gw, int Kp, int tpb, int blocks_per_row) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int RS = Kp * 2 + 32;
   const int tid = threadIdx.x;
   int bid = blockIdx.x;
   const int xb = bid % blocks_per_row;
   bid /= blocks_per_row;
-  const int py = bid % g;
-  const int b = bid / g;
+  const int py = bid % gh;
+  const int b = bid / gh;
   const int t0 = xb * tpb;
-  const int nt = min(tpb, g - t0);  // patches of this workgroup
+  const int nt = min(tpb, gw - t0);  // patches of this workgroup
   const int pp = p * p, Kreal = C * pp;
   // zero the K padding
   const int padw = (Kp - Kreal) >> 1;  // dwords per row (Kreal and Kp are even)
@@ -450,7 +450,7 @@ __global__ __launch_bounds__(256) void im2col_rows_kernel(const void* __restrict
   }
   // pixels: a thread owns pixel pair j of the workgroup's run (its patch and kx fixed once) and walks the C*p image rows
   const int ppr = (nt * p) >> 1;
-  const int64_t img_base = ((int64_t)b * C * img + py * p) * img + t0 * p;
+  const int64_t img_base = ((int64_t)b * C * H + py * p) * W + t0 * p;
   for (int j = tid; j < ppr; j += 256) {
     const int x = 2 * j;
     const int t = x / p, kx = x - t * p;
@@ -467,56 +467,55 @@ __global__ __launch_bounds__(256) void im2col_rows_kernel(const void* __restrict
       return v;
     };
     for (int c = 0; c < C; ++c) {
-      const int64_t src = img_base + (int64_t)c * img * img + x;
+      const int64_t src = img_base + (int64_t)c * H * W + x;
       char* d = dst + c * pp * 2;
       int ky = 0;
       for (; ky + 7 <= p; ky += 7) {  // 7 rows in flight (p = 14: two rounds)
         bf16x2 v[7];
 #pragma unroll
-        for (int u = 0; u < 7; ++u) v[u] = load(src + (int64_t)(ky + u) * img);
+        for (int u = 0; u < 7; ++u) v[u] = load(src + (int64_t)(ky + u) * W);
 #pragma unroll
         for (int u = 0; u < 7; ++u) *reinterpret_cast<bf16x2*>(d + (ky + u) * p * 2) = v[u];
       }
-      for (; ky < p; ++ky) *reinterpret_cast<bf16x2*>(d + ky * p * 2) = load(src + (int64_t)ky * img);
+      for (; ky < p; ++ky) *reinterpret_cast<bf16x2*>(d + ky * p * 2) = load(src + (int64_t)ky * W);
     }
   }
   __syncthreads();
   const int k8 = Kp >> 3;
-  const int64_t row0 = ((int64_t)b * g + py) * g + t0;
+  const int64_t row0 = ((int64_t)b * gh + py) * gw + t0;
   for (int i = tid; i < nt * k8; i += 256) {
     const int r = i / k8, ch = i - r * k8;
     *reinterpret_cast<bf16x8*>(col + (row0 + r) * Kp + ch * 8) = *reinterpret_cast<const bf16x8*>(smem + r * RS + ch * 16);
   }
 }
 
-hipError_t launch_im2col(const void* images, int in_bf16, void* col, int batch, int C, int img, int p,
+hipError_t launch_im2col(const void* images, int in_bf16, void* col, int batch, int C, int H, int W, int p,
                          int Kp, hipStream_t s) {
-  if (batch <= 0 || p <= 0 || img % p || (Kp & 63) || Kp < C * p * p) return hipErrorInvalidValue;
-  if ((p & 7) && !(p & 1) && !(img & 1) && (((uintptr_t)images) & 7) == 0) {
+  if (batch <= 0 || p <= 0 || H <= 0 || W <= 0 || H % p || W % p || (Kp & 63) || Kp < C * p * p) return hipErrorInvalidValue;
+  const int gh = H / p, gw = W / p;
+  if ((p & 7) && !(p & 1) && !(W & 1) && (((uintptr_t)images) & 7) == 0) {
     // even patch side that is not a multiple of 8: the LDS form
-    const int g = img / p;
-    const int tpb = g < 32 ? g : 32;
-    const int bpr = (g + tpb - 1) / tpb;
+    const int tpb = gw < 32 ? gw : 32;
+    const int bpr = (gw + tpb - 1) / tpb;
     const size_t lds = (size_t)tpb * (Kp * 2 + 32);
     if (lds <= 65536) {
-      const dim3 grid((unsigned)((int64_t)batch * g * bpr)), block(256);
+      const dim3 grid((unsigned)((int64_t)batch * gh * bpr)), block(256);
       if (in_bf16)
-        hipLaunchKernelGGL((im2col_rows_kernel<true>), grid, block, lds, s, images, (bf16_t*)col, C, img, p, g, Kp, tpb, bpr);
+        hipLaunchKernelGGL((im2col_rows_kernel<true>), grid, block, lds, s, images, (bf16_t*)col, C, H, W, p, gh, gw, Kp, tpb, bpr);
       else
-        hipLaunchKernelGGL((im2col_rows_kernel<false>), grid, block, lds, s, images, (bf16_t*)col, C, img, p, g, Kp, tpb, bpr);
+        hipLaunchKernelGGL((im2col_rows_kernel<false>), grid, block, lds, s, images, (bf16_t*)col, C, H, W, p, gh, gw, Kp, tpb, bpr);
       return hipGetLastError();
     }
   }
-  // the fast path reads 8 pixels with vector loads: needs p % 8 == 0 and img % 8 == 0 so that every
+  // the fast path reads 8 pixels with vector loads: needs p % 8 == 0 (and so W % 8 == 0) so that every
   // 8-pixel run starts 16-byte aligned (the image base is assumed 16-byte aligned)
-  const int g = img / p;
-  const int fast = ((p & 7) == 0 && (img & 7) == 0 && (((uintptr_t)images) & 15) == 0) ? 1 : 0;
-  const int64_t total8 = (int64_t)batch * g * g * (Kp / 8);
+  const int fast = ((p & 7) == 0 && (W & 7) == 0 && (((uintptr_t)images) & 15) == 0) ? 1 : 0;
+  const int64_t total8 = (int64_t)batch * gh * gw * (Kp / 8);
   const dim3 grid((unsigned)((total8 + 255) / 256)), block(256);
   if (in_bf16)
-    hipLaunchKernelGGL((im2col_kernel<true>), grid, block, 0, s, images, (bf16_t*)col, total8, C, img, p, g, Kp, fast);
+    hipLaunchKernelGGL((im2col_kernel<true>), grid, block, 0, s, images, (bf16_t*)col, total8, C, H, W, p, gh, gw, Kp, fast);
   else
-    hipLaunchKernelGGL((im2col_kernel<false>), grid, block, 0, s, images, (bf16_t*)col, total8, C, img, p, g, Kp, fast);
+    hipLaunchKernelGGL((im2col_kernel<false>), grid, block, 0, s, images, (bf16_t*)col, total8, C, H, W, p, gh, gw, Kp, fast);
   return hipGetLastError();
 }
 

@@ -81,7 +81,13 @@ struct ProfEvent {
 struct vdr_model {
   vdr_config cfg;
   int device = 0;
-  int n_patches = 0, n_tokens = 0, Kp = 0;
+  int n_patches = 0, n_tokens = 0, Kp = 0;  // patches / tokens per image at the input size in force
+  // vdr_set_input_size: the size in force ((img, img) until the first set) and the position table the forward reads --
+  // the loaded pos_embed (pos0) at the native size, else pos_sized [n_tokens, D]: its CLS row and resampled patch rows
+  int in_h = 0, in_w = 0;
+  const float* pos0 = nullptr;
+  float* pos_sized = nullptr;
+  size_t pos_sized_rows = 0;  // rows pos_sized was allocated for
   std::vector<WSlot> slots;
   std::map<std::string, int> index;
   std::vector<LayerW> layers;
@@ -285,6 +291,31 @@ int fold_ln(vdr_model* m, const std::vector<float>& W, const std::vector<float>&
   return VDR_OK;
 }
 
+// The position table of the input size in force (load-time class: may allocate and synchronise).  The native size reads
+// the loaded table itself; any other size gets [CLS row unchanged ; patch rows resampled from the (img / patch)^2 grid].
+int build_pos_table(vdr_model* m) {
+  const vdr_config& c = m->cfg;
+  m->pos = m->pos0;
+  if (!c.has_pos || !c.patch || (m->in_h == c.img && m->in_w == c.img)) return VDR_OK;
+  const int ncls = c.has_cls ? 1 : 0, D = c.dim, g0 = c.img / c.patch;
+  VDR_TRY(hipSetDevice(m->device), "hipSetDevice");
+  VDR_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");  // (a forward still in flight, on any stream, may read the old table)
+  if (m->pos_sized_rows < (size_t)m->n_tokens) {
+    if (m->pos_sized) VDR_TRY(hipFree(m->pos_sized), "hipFree(pos_embed table)");
+    m->pos_sized = nullptr;
+    m->pos_sized_rows = 0;
+    VDR_TRY(hipMalloc((void**)&m->pos_sized, (size_t)m->n_tokens * D * 4 + 256), "hipMalloc(pos_embed table)");
+    m->pos_sized_rows = (size_t)m->n_tokens;
+  }
+  if (ncls) VDR_TRY(hipMemcpy(m->pos_sized, m->pos0, (size_t)D * 4, hipMemcpyDeviceToDevice), "hipMemcpy(pos_embed CLS row)");
+  VDR_TRY(launch_pos_interp(m->pos0 + (size_t)ncls * D, g0, g0, D, m->pos_sized + (size_t)ncls * D, m->in_h / c.patch,
+                            m->in_w / c.patch, nullptr),
+          "pos_interp");
+  VDR_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
+  m->pos = m->pos_sized;
+  return VDR_OK;
+}
+
 int resolve(vdr_model* m) {
   for (auto& s : m->slots)
     if (!s.set) return fail(m, VDR_ERR_INCOMPLETE, "weight not set: " + s.name);
@@ -296,7 +327,11 @@ int resolve(vdr_model* m) {
   m->w_patch = dev_of(m, "patch_embed.proj.weight");
   m->b_patch = (const float*)dev_of(m, "patch_embed.proj.bias");
   m->cls = (const float*)dev_of(m, "cls_token");
-  m->pos = (const float*)dev_of(m, "pos_embed");
+  m->pos0 = (const float*)dev_of(m, "pos_embed");
+  {
+    const int rc = build_pos_table(m);  // (weights changed: the table of the size in force is rebuilt)
+    if (rc) return rc;
+  }
   m->inw = (const float*)dev_of(m, "input_norm.weight");
   m->inb = (const float*)dev_of(m, "input_norm.bias");
   m->normw = (const float*)dev_of(m, "norm.weight");
@@ -673,26 +708,27 @@ bool patch_gather_ok(int in_dtype, int patch, int variant, const void* images) {
          ((uintptr_t)images & 15) == 0;
 }
 
-// The patch-embedding GEMM of `batch` images [batch, chans, img, img] -> C rows omap(r), r < batch * (img / p)^2: bf16
-// images with a patch side of 8 / 16 / 32 are gathered 16-byte runs at a time by the GEMM's operand loader straight from
-// NCHW (ring4 tile variants: no col buffer, no im2col launch); fp32 images (the loader is an LDS-DMA: it cannot convert)
-// and p = 14 (runs of 14 pixels are not 16-byte chunks) go through im2col into `col`, launched here.  Fills *g (the
-// caller adds bias, pos, omap and what else differs) and *variant.
+// The patch-embedding GEMM of `batch` images [batch, chans, H, W] -> C rows omap(r), r < batch * (H / p) * (W / p), token
+// i of an image being patch (i / gw, i % gw): bf16 images with a patch side of 8 / 16 / 32 on a SQUARE grid are gathered
+// 16-byte runs at a time by the GEMM's operand loader straight from NCHW (ring4 tile variants: no col buffer, no im2col
+// launch); fp32 images (the loader is an LDS-DMA: it cannot convert), p = 14 (runs of 14 pixels are not 16-byte chunks)
+// and rectangular grids (the loader splits a row by one grid side) go through im2col into `col`, launched here.  Fills
+// *g (the caller adds bias, pos, omap and what else differs) and *variant.
 hipError_t patch_gemm(vdr_model* m, hipStream_t s, const void* images, int in_dtype, void* col, const void* W, void* C,
-                      int batch, int chans, int img, int p, int D, GemmArgs* g, int* variant) {
-  const int n = (img / p) * (img / p), Kp = round_up(chans * p * p, 64);
+                      int batch, int chans, int H, int Wd, int p, int D, GemmArgs* g, int* variant) {
+  const int n = (H / p) * (Wd / p), Kp = round_up(chans * p * p, 64);
   *variant = gemm_variant_for(VDR_K_GEMM_PATCH, (int64_t)batch * n, D);
-  const bool fused = patch_gather_ok(in_dtype, p, *variant, images);
+  const bool fused = H == Wd && patch_gather_ok(in_dtype, p, *variant, images);
   *g = linear(fused ? images : col, W, C, (int64_t)batch * n, D, Kp, EPI_PATCH);
   if (fused) {
     g->patch_p = p;
-    g->patch_g = img / p;
+    g->patch_g = H / p;
     g->patch_C = chans;
     return hipSuccess;
   }
   const size_t in_es = in_dtype == VDR_BF16 ? 2 : 4;
-  Scope sc(m, s, VDR_K_IM2COL, 0.0, (double)batch * chans * img * img * in_es + 2.0 * batch * n * Kp);
-  return launch_im2col(images, in_dtype == VDR_BF16, col, batch, chans, img, p, Kp, s);
+  Scope sc(m, s, VDR_K_IM2COL, 0.0, (double)batch * chans * H * Wd * in_es + 2.0 * batch * n * Kp);
+  return launch_im2col(images, in_dtype == VDR_BF16, col, batch, chans, H, Wd, p, Kp, s);
 }
 
 #ifndef VDR_GEMM_8P_DEFAULT
@@ -1347,8 +1383,8 @@ int embed_patches(vdr_model* m, hipStream_t s, const Carve& w, const char* img, 
   const bool pe_only = pe_out != nullptr;
   GemmArgs g;
   int variant;
-  VDR_TRY(patch_gemm(m, s, img, in_dtype, w.u, m->w_patch, pe_only ? (void*)pe_out : (void*)w.x, mb, c.in_chans, c.img, c.patch, D,
-                     &g, &variant),
+  VDR_TRY(patch_gemm(m, s, img, in_dtype, w.u, m->w_patch, pe_only ? (void*)pe_out : (void*)w.x, mb, c.in_chans, m->in_h, m->in_w, c.patch,
+                     D, &g, &variant),
           "im2col");
   g.bias = m->b_patch;
   if (pe_only) {
@@ -1517,6 +1553,7 @@ int vdr_create(const vdr_config* cfg, int device, vdr_handle* out) {
     m->n_patches = g * g;
     m->n_tokens = m->n_patches + (c.has_cls ? 1 : 0);
     m->Kp = round_up(c.in_chans * c.patch * c.patch, 64);
+    m->in_h = m->in_w = c.img;
   }
   build_slots(m.get());
   *out = m.release();
@@ -1542,6 +1579,7 @@ void vdr_destroy(vdr_handle h) {
   for (auto& kv : h->w_il)
     if (kv.second) hipFree(kv.second);
   if (h->fin_cnt) hipFree(h->fin_cnt);
+  if (h->pos_sized) hipFree(h->pos_sized);
   for (auto st : h->streams) hipStreamDestroy(st);
   for (auto st : h->aux) hipStreamDestroy(st);
   for (auto e : h->aux_fork) hipEventDestroy(e);
@@ -1659,6 +1697,50 @@ int vdr_finalize(vdr_handle m) {
   return resolve(m);
 }
 
+int vdr_set_input_size(vdr_handle m, int height, int width) {
+  // the argument checks that need no handle come first (they also hold for a null one)
+  if (height <= 0) return fail(m, VDR_ERR_INVALID, "vdr_set_input_size: height must be positive");
+  if (width <= 0) return fail(m, VDR_ERR_INVALID, "vdr_set_input_size: width must be positive");
+  if (!m) return fail(m, VDR_ERR_INVALID, "vdr_set_input_size: null handle");
+  const vdr_config& c = m->cfg;
+  if (!c.patch) return fail(m, VDR_ERR_UNSUPPORTED, "vdr_set_input_size: image models only (token model)");
+  if (c.window > 0)
+    return fail(m, VDR_ERR_UNSUPPORTED,
+                "vdr_set_input_size: not for the SAM encoder (its position tables and window partition are tied to its grid)");
+  if (!c.pre_ln && c.layers > 0) return fail(m, VDR_ERR_UNSUPPORTED, "vdr_set_input_size: pre-LN models only");
+  if (height % c.patch) return fail(m, VDR_ERR_INVALID, "vdr_set_input_size: height must be a multiple of patch " + std::to_string(c.patch));
+  if (width % c.patch) return fail(m, VDR_ERR_INVALID, "vdr_set_input_size: width must be a multiple of patch " + std::to_string(c.patch));
+  if ((int64_t)(height / c.patch) * (width / c.patch) > (1 << 20))
+    return fail(m, VDR_ERR_INVALID, "vdr_set_input_size: height x width gives more than 2^20 patches");
+  int rc = check_device(m);
+  if (rc) return rc;
+  if (!m->resolved) return fail(m, VDR_ERR_INCOMPLETE, "vdr_set_input_size: vdr_finalize has not run since the last vdr_set_weight");
+  DeviceGuard dg(m->device);
+  if (!dg.ok) return fail(m, VDR_ERR_HIP, "hipSetDevice failed");
+  const int old_h = m->in_h, old_w = m->in_w;
+  auto geometry = [&](int hh, int ww) {
+    m->in_h = hh;
+    m->in_w = ww;
+    m->n_patches = (hh / c.patch) * (ww / c.patch);
+    m->n_tokens = m->n_patches + (c.has_cls ? 1 : 0);
+  };
+  geometry(height, width);
+  if ((rc = build_pos_table(m))) {
+    geometry(old_h, old_w);  // the size in force stays what it was
+    const std::string why = m->err;
+    (void)build_pos_table(m);
+    return fail(m, rc, why);
+  }
+  return VDR_OK;
+}
+
+int vdr_get_input_size(vdr_handle m, int* height, int* width) {
+  if (!m || !height || !width) return fail(m, VDR_ERR_INVALID, "vdr_get_input_size: null argument");
+  *height = m->in_h;
+  *width = m->in_w;
+  return VDR_OK;
+}
+
 int vdr_workspace_bytes(vdr_handle m, int batch, int seq, size_t* out) {
   if (!m || !out || batch <= 0) return fail(m, VDR_ERR_INVALID, "bad argument");
   const int ntok = m->cfg.patch ? m->n_tokens : seq + (m->cfg.has_cls ? 1 : 0);
@@ -1680,7 +1762,7 @@ int vdr_forward(vdr_handle m, const void* images, int in_dtype, int batch, void*
   if ((out_mode == VDR_OUT_ENCODER) != (c.window > 0 && out_mode != VDR_OUT_PATCH_EMBED && out_mode != VDR_OUT_TOKENS))
     return fail(m, VDR_ERR_INVALID, "VDR_OUT_ENCODER is the output of a SAM encoder (window > 0); other models use CLS/DENSE/TOKENS");
   const int ntok = m->n_tokens, n = m->n_patches, D = c.dim;
-  const size_t img_bytes = (size_t)c.in_chans * c.img * c.img * (in_dtype == VDR_BF16 ? 2 : 4);
+  const size_t img_bytes = (size_t)c.in_chans * m->in_h * m->in_w * (in_dtype == VDR_BF16 ? 2 : 4);
   const size_t es = out_dtype == VDR_BF16 ? 2 : 4;
   vdr_layer_out o{};  // (the output of the last block, as vdr_forward_layers describes one)
   o.out_mode = out_mode;
@@ -1783,7 +1865,7 @@ static int forward_layers_impl(const char* fn, vdr_handle m, const void* images,
   bool cls_only = true;  // every output of the last block that runs is CLS: that block may run its CLS rows only
   for (const vdr_layer_out* o : el.at[el.last]) cls_only = cls_only && o->out_mode == VDR_OUT_CLS;
   const int ntok = m->n_tokens;
-  const size_t img_bytes = (size_t)c.in_chans * c.img * c.img * (in_dtype == VDR_BF16 ? 2 : 4);
+  const size_t img_bytes = (size_t)c.in_chans * m->in_h * m->in_w * (in_dtype == VDR_BF16 ? 2 : 4);
   return run_micro_batches(m, batch, ntok, workspace, workspace_bytes, stream, [&](hipStream_t s, const Carve& w, int b0, int mb) {
     int rc;
     if ((rc = embed_patches(m, s, w, (const char*)images + (size_t)b0 * img_bytes, in_dtype, mb, nullptr, VDR_F32))) return rc;
@@ -2194,6 +2276,22 @@ int vdr_op_attention_relpos(const void* qkv, const float* rel_pos_h, const float
   return VDR_OK;
 }
 
+int vdr_op_interpolate_pos(const float* pos, int gh0, int gw0, int D, float* out, int gh, int gw, void* stream) {
+  if (!pos) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_interpolate_pos: pos is null");
+  if (!out) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_interpolate_pos: out is null");
+  if (gh0 <= 0) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_interpolate_pos: gh0 must be positive");
+  if (gw0 <= 0) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_interpolate_pos: gw0 must be positive");
+  if (D <= 0) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_interpolate_pos: D must be positive");
+  if (gh <= 0) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_interpolate_pos: gh must be positive");
+  if (gw <= 0) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_interpolate_pos: gw must be positive");
+  if ((int64_t)gh0 * gw0 > (1 << 20) || (int64_t)gh * gw > (1 << 20))
+    return fail(nullptr, VDR_ERR_INVALID, "vdr_op_interpolate_pos: more than 2^20 grid cells");
+  int rc = check_device(nullptr);
+  if (rc) return rc;
+  OP_TRY(launch_pos_interp(pos, gh0, gw0, D, out, gh, gw, (hipStream_t)stream), "pos_interp");
+  return VDR_OK;
+}
+
 int vdr_op_patch_embed(const void* images, int in_dtype, const void* W, const float* bias, const float* pos, void* col,
                        void* y, int batch, int C, int img, int p, int D, int row_stride, int row_offset, void* stream) {
   if (!images || !W || !col || !y) return fail(nullptr, VDR_ERR_INVALID, "null argument");
@@ -2202,7 +2300,7 @@ int vdr_op_patch_embed(const void* images, int in_dtype, const void* W, const fl
   if (rc) return rc;
   GemmArgs a;
   int variant;  // (the caller's W as it is; bf16 images with p = 8 / 16 / 32: no im2col pass, `col` untouched)
-  OP_TRY(patch_gemm(nullptr, (hipStream_t)stream, images, in_dtype, col, W, y, batch, C, img, p, D, &a, &variant), "im2col");
+  OP_TRY(patch_gemm(nullptr, (hipStream_t)stream, images, in_dtype, col, W, y, batch, C, img, img, p, D, &a, &variant), "im2col");
   a.bias = bias;
   a.pos = pos;
   a.omap = RowMap{(img / p) * (img / p), row_stride, row_offset};

@@ -195,9 +195,14 @@ hipError_t launch_attention_relpos(const void* qkv, const float* T, void* out, i
 // 3x3 / pad 1 im2col over NHWC tokens of a g x g grid: col[r][j*C + c] = y[(y+ky-1, x+kx-1)][c], j = ky*3 + kx
 hipError_t launch_im2col3(const void* y, void* col, int batch, int g, int C, hipStream_t s);
 
-// images NCHW -> col [batch*n, Kp] bf16 with k = c*p*p + ky*p + kx, zero padded to Kp
-hipError_t launch_im2col(const void* images, int in_bf16, void* col, int batch, int C, int img, int p,
+// images NCHW [batch, C, H, W] -> col [batch*n, Kp] bf16, n = (H / p) * (W / p) patches in (py, px) order, with
+// k = c*p*p + ky*p + kx, zero padded to Kp
+hipError_t launch_im2col(const void* images, int in_bf16, void* col, int batch, int C, int H, int W, int p,
                          int Kp, hipStream_t s);
+
+// pos_embed resampling (pos_interp.hip): the patch rows of a position table from a gh0 x gw0 grid to gh x gw, bicubic
+// (A = -0.75, align_corners = False, border taps clamped), fp64 arithmetic, one rounding to fp32
+hipError_t launch_pos_interp(const float* pos, int gh0, int gw0, int D, float* out, int gh, int gw, hipStream_t s);
 
 // x[b*row_stride + 0][:] = cls + pos[0]  (bf16 out)
 hipError_t launch_cls_rows(const float* cls, const float* pos, void* x, int batch, int64_t row_stride,

@@ -53,6 +53,8 @@ SYMBOLS = {
     "vdr_last_error": (C.c_char_p, [_P]),
     "vdr_set_weight": (_I, [_P, C.c_char_p, _P, C.POINTER(_L), _I]),
     "vdr_finalize": (_I, [_P]),
+    "vdr_set_input_size": (_I, [_P, _I, _I]),
+    "vdr_get_input_size": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
     "vdr_num_weights": (_I, [_P]),
     "vdr_weight_name": (C.c_char_p, [_P, _I]),
     "vdr_workspace_bytes": (_I, [_P, _I, _I, C.POINTER(C.c_size_t)]),
@@ -88,6 +90,7 @@ SYMBOLS = {
     "vdr_op_attention_varlen": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
     "vdr_op_attention_probs": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vdr_op_attention_relpos": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "vdr_op_interpolate_pos": (_I, [_P, _I, _I, _I, _P, _I, _I, _P]),
     "vdr_op_patch_embed": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vdr_profile_enable": (_I, [_P, _I]),
     "vdr_profile_mask": (_I, [_P, C.c_uint32]),

@@ -154,6 +154,53 @@ class Engine:
         L.check(self.lib.vdr_finalize(self.h), self.h)
         self._loaded = True
 
+    # ---- input size ----------------------------------------------------------------------------
+    @property
+    def input_size(self) -> "tuple[int, int]":
+        """(height, width) the image entry points take: (img, img) until set_input_size."""
+        return getattr(self, "_size", None) or (self.cfg.img, self.cfg.img)
+
+    @property
+    def grid(self) -> "tuple[int, int]":
+        """Patch grid (gh, gw) at the input size in force; token i of an image is patch (i // gw, i % gw)."""
+        h, w = self.input_size
+        p = self.cfg.patch
+        return (h // p, w // p) if p else (0, 0)
+
+    @property
+    def n_patches(self) -> int:
+        gh, gw = self.grid
+        return gh * gw
+
+    @property
+    def n_tokens(self) -> int:
+        return self.n_patches + (1 if self.cfg.has_cls else 0)
+
+    def set_input_size(self, height: int, width: int):
+        """vdr_set_input_size: run the model on [B, C, height, width] images from now on (sides multiples of patch; square
+        or rectangular).  The learned pos_embed is resampled once, on the device, the way DINOv2 / transformers
+        interpolate_pos_encoding do (bicubic, align_corners=False); (img, img) selects the loaded table again, bit for bit.
+        Load-time class: allocates and synchronises, so call it outside graph capture.  SAM encoders and token models
+        are tied to their geometry: ValueError."""
+        cfg = self.cfg
+        height, width = int(height), int(width)
+        if cfg.window > 0:
+            raise ValueError("set_input_size: the SAM encoder's position tables and window partition are tied to its "
+                             f"{cfg.img}x{cfg.img} input")
+        if not cfg.patch:
+            raise ValueError("set_input_size: a token model has no input size")
+        if height <= 0 or width <= 0 or height % cfg.patch or width % cfg.patch:
+            raise ValueError(f"set_input_size: height and width must be positive multiples of patch {cfg.patch}, "
+                             f"got {height} x {width}")
+        L.check(self.lib.vdr_set_input_size(self.h, height, width), self.h)
+        self._size = (height, width)
+
+    def _check_images(self, images: torch.Tensor):
+        cfg = self.cfg
+        h, w = self.input_size
+        if images.dim() != 4 or tuple(images.shape[1:]) != (cfg.in_chans, h, w):
+            raise ValueError(f"images must be [B,{cfg.in_chans},{h},{w}], got {tuple(images.shape)}")
+
     # ---- workspace ------------------------------------------------------------------------------
     def _workspace(self, batch: int, seq: int = 0) -> torch.Tensor:
         need = C.c_size_t()
@@ -168,16 +215,15 @@ class Engine:
     # ---- hot path --------------------------------------------------------------------------------
     def forward(self, images: torch.Tensor, out_mode: int = L.OUT_CLS, out_dtype=torch.float32) -> torch.Tensor:
         cfg = self.cfg
-        if images.dim() != 4 or images.shape[1] != cfg.in_chans or images.shape[2] != cfg.img or images.shape[3] != cfg.img:
-            raise ValueError(f"images must be [B,{cfg.in_chans},{cfg.img},{cfg.img}], got {tuple(images.shape)}")
+        self._check_images(images)
         if images.dtype not in _DT:
             images = images.float()
         images = images.to(self.device).contiguous()
         B = images.shape[0]
-        n, N, D = cfg.n_patches, cfg.n_tokens, cfg.dim
-        g = cfg.img // cfg.patch
+        n, N, D = self.n_patches, self.n_tokens, cfg.dim
+        gh, gw = self.grid
         shape = {L.OUT_CLS: (B, D), L.OUT_DENSE: (B, n, D), L.OUT_PATCH_EMBED: (B, n, D), L.OUT_TOKENS: (B, N, D),
-                 L.OUT_ENCODER: (B, g, g, cfg.neck_chans)}[out_mode]
+                 L.OUT_ENCODER: (B, gh, gw, cfg.neck_chans)}[out_mode]
         out = torch.empty(shape, dtype=out_dtype, device=self.device)
         ws = self._workspace(B)
         L.check(self.lib.vdr_forward(self.h, images.data_ptr(), _DT[images.dtype], B, out.data_ptr(), out_mode,
@@ -189,8 +235,7 @@ class Engine:
         Nothing is converted or copied here, so everything is checked: a wrong dtype / layout / size is an error, never
         an out-of-bounds write."""
         cfg = self.cfg
-        if images.dim() != 4 or tuple(images.shape[1:]) != (cfg.in_chans, cfg.img, cfg.img):
-            raise ValueError(f"images must be [B,{cfg.in_chans},{cfg.img},{cfg.img}], got {tuple(images.shape)}")
+        self._check_images(images)
         if images.dtype not in _DT or out.dtype not in _DT:
             raise TypeError(f"images / out must be float32 or bfloat16, got {images.dtype} / {out.dtype}")
         if images.device != self.device or out.device != self.device:
@@ -198,9 +243,9 @@ class Engine:
         if not images.is_contiguous() or not out.is_contiguous():
             raise ValueError("images and out must be contiguous")
         B = images.shape[0]
-        g = cfg.img // cfg.patch
-        per_image = {L.OUT_CLS: cfg.dim, L.OUT_DENSE: cfg.n_patches * cfg.dim, L.OUT_PATCH_EMBED: cfg.n_patches * cfg.dim,
-                     L.OUT_TOKENS: cfg.n_tokens * cfg.dim, L.OUT_ENCODER: g * g * cfg.neck_chans}[out_mode]
+        gh, gw = self.grid
+        per_image = {L.OUT_CLS: cfg.dim, L.OUT_DENSE: self.n_patches * cfg.dim, L.OUT_PATCH_EMBED: self.n_patches * cfg.dim,
+                     L.OUT_TOKENS: self.n_tokens * cfg.dim, L.OUT_ENCODER: gh * gw * cfg.neck_chans}[out_mode]
         if out.numel() != B * per_image:
             raise ValueError(f"out has {out.numel()} elements, the forward writes {B} x {per_image}")
         ws = self._workspace(B)
@@ -213,8 +258,7 @@ class Engine:
         returns their tensors in the same order.  Caller-owned outputs are checked as forward_into checks its buffer,
         nothing is converted or copied."""
         cfg = self.cfg
-        if images.dim() != 4 or tuple(images.shape[1:]) != (cfg.in_chans, cfg.img, cfg.img):
-            raise ValueError(f"images must be [B,{cfg.in_chans},{cfg.img},{cfg.img}], got {tuple(images.shape)}")
+        self._check_images(images)
         if images.dtype not in _DT:
             images = images.float()
         images = images.to(self.device).contiguous()
@@ -233,12 +277,11 @@ class Engine:
         sequence of LayerOut (forward_layers' outputs, the same bits).  Returns (feature tensors, map tensors), each in
         the order given.  Caller-owned buffers are checked, never converted or copied."""
         cfg = self.cfg
-        if images.dim() != 4 or tuple(images.shape[1:]) != (cfg.in_chans, cfg.img, cfg.img):
-            raise ValueError(f"images must be [B,{cfg.in_chans},{cfg.img},{cfg.img}], got {tuple(images.shape)}")
+        self._check_images(images)
         if images.dtype not in _DT:
             images = images.float()
         images = images.to(self.device).contiguous()
-        B, N, H = images.shape[0], cfg.n_tokens, cfg.heads
+        B, N, H = images.shape[0], self.n_tokens, cfg.heads
         maps, specs = list(maps), list(outs)
         if not maps:
             raise ValueError("forward_attn_maps needs at least one AttnMap")
@@ -277,7 +320,7 @@ class Engine:
         arr = (L.vdr_layer_out * len(specs))()
         outs = []
         for k, sp in enumerate(specs):
-            rows = {L.OUT_CLS: None, L.OUT_POOLED: None, L.OUT_DENSE: cfg.n_patches, L.OUT_TOKENS: cfg.n_tokens}
+            rows = {L.OUT_CLS: None, L.OUT_POOLED: None, L.OUT_DENSE: self.n_patches, L.OUT_TOKENS: self.n_tokens}
             if sp.mode not in rows:
                 raise ValueError(f"specs[{k}]: mode must be OUT_CLS, OUT_DENSE, OUT_TOKENS or OUT_POOLED, got {sp.mode}")
             shape = (B, D) if rows[sp.mode] is None else (B, rows[sp.mode], D)

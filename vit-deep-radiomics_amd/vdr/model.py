@@ -25,11 +25,15 @@ ARCHS = {
     # reference default for model_name='dinov2': load_dinov2('small') = dinov2_vits14, of which the hot loop runs
     # `model.patch_embed(x)` ONLY, at 896x896 (tfds_dense_descriptor.py:128-133).  So the drop-in for that name is the
     # patch embedding alone: no blocks, no cls / pos / norm -- a real dinov2_vits14 state_dict loads as it is (its
-    # pos_embed is [1, 1370, 384] for 518^2 and would need DINOv2's run-time interpolation for any other use; its
-    # cls_token / mask_token / blocks.* / norm.* keys are ignored here exactly as the reference ignores them).
+    # pos_embed [1, 1370, 384] for 518^2, cls_token / mask_token / blocks.* / norm.* keys are ignored here exactly as
+    # the reference ignores them; the whole encoder of that checkpoint is "dinov2_small14_518" below).
     "dinov2": VdrConfig(896, 14, 3, 384, 6, 0, 1536, pre_ln=False, has_cls=False, has_pos=False),
-    # the whole ViT-S/14 at 896^2 (pos_embed must already be [1, 4097, 384])
+    # the whole ViT-S/14 with a table native to 896^2 (pos_embed [1, 4097, 384]: a checkpoint resized beforehand; it
+    # runs at 896^2 on the loaded table itself and at any other size through set_input_size)
     "dinov2_small14_896": VdrConfig(896, 14, 3, 384, 6, 12, 1536, layerscale=True),
+    # the whole ViT-S/14 at its pre-training size: a real dinov2_vits14 state_dict (pos_embed [1, 1370, 384]) loads as it
+    # is and runs at 224^2, 896^2, ... after set_input_size / with dynamic_size=True (DINOv2's interpolate_pos_encoding)
+    "dinov2_small14_518": VdrConfig(518, 14, 3, 384, 6, 12, 1536, layerscale=True),
     # reference default backbone: sam_model_registry['vit_b'] image encoder (MedSAM checkpoint), 1024x1024
     "medsam": VdrConfig(1024, 16, 3, 768, 12, 12, 3072, has_cls=False, window=14, global_blocks=(2, 5, 8, 11),
                         neck_chans=256),
@@ -72,12 +76,44 @@ def intermediate_layer_indices(n, depth: int) -> "list[int]":
 class VitDescriptorModel:
     """Frozen-ViT feature extractor with the attributes the reference's hot loop dispatches on."""
 
-    def __init__(self, cfg: VdrConfig, weights: "dict[str, torch.Tensor]", model_name: str = "vit", device=None):
+    def __init__(self, cfg: VdrConfig, weights: "dict[str, torch.Tensor]", model_name: str = "vit", device=None,
+                 dynamic_size: bool = False):
+        """dynamic_size=True: every image method first adopts the size of the images it is given (x.shape[-2:]), as
+        DINOv2 and transformers do with interpolate_pos_encoding; the position table is rebuilt only when the size
+        changes.  False (default): other sizes are refused until set_input_size names one."""
+        if dynamic_size and cfg.window > 0:
+            raise ValueError("dynamic_size: the SAM encoder's position tables and window partition are tied to its "
+                             f"{cfg.img}x{cfg.img} input")
         self.cfg = cfg
         self.model_name = model_name  # tfds_dense_descriptor.py:66 assigns this attribute
+        self.dynamic_size = bool(dynamic_size)
         self.engine = Engine(cfg, device)
         self.engine.load_weights(weights)
         self.device = self.engine.device
+
+    # -- input size ------------------------------------------------------------------------------
+    def set_input_size(self, height: int, width: int):
+        """Run on [B, 3, height, width] images from now on (multiples of the patch side; square or rectangular): the
+        learned pos_embed is resampled once on the device (Engine.set_input_size).  ViT / DINOv2 models."""
+        if self.cfg.window > 0:
+            raise ValueError("set_input_size: the SAM encoder's position tables and window partition are tied to its "
+                             f"{self.cfg.img}x{self.cfg.img} input")
+        self.engine.set_input_size(height, width)
+        return self
+
+    @property
+    def input_size(self) -> "tuple[int, int]":
+        return self.engine.input_size
+
+    @property
+    def grid(self) -> "tuple[int, int]":
+        """(gh, gw) of the dense maps at the input size in force."""
+        return self.engine.grid
+
+    def _adopt(self, x):
+        """dynamic_size: take the size of x as the input size (a no-op when it is the one in force)."""
+        if getattr(self, "dynamic_size", False) and x.dim() == 4 and tuple(x.shape[-2:]) != tuple(self.engine.input_size):
+            self.set_input_size(int(x.shape[-2]), int(x.shape[-1]))
 
     # -- nn.Module-style no-ops so reference code such as model.eval().cuda() keeps working
     def eval(self):
@@ -92,23 +128,27 @@ class VitDescriptorModel:
     # -- R2 -------------------------------------------------------------------------------------
     def patch_embed(self, x: torch.Tensor) -> torch.Tensor:
         """DINOv2 PatchEmbed: [B,3,H,W] -> [B,n,D] (tfds_dense_descriptor.py:128)."""
+        self._adopt(x)
         return self.engine.forward(x, L.OUT_PATCH_EMBED, torch.float32)
 
     def image_encoder(self, x: torch.Tensor) -> torch.Tensor:
         """Channel-first dense map [B,D,h,w], the layout tfds_dense_descriptor.py:123-126 squeezes and
         transposes to (h,w,D).  SAM / MedSAM models return the conv-neck output [B,256,64,64]."""
         B = x.shape[0]
-        g = self.cfg.img // self.cfg.patch
         if self.cfg.window > 0:
             return self.engine.forward(x, L.OUT_ENCODER, torch.float32).permute(0, 3, 1, 2)
+        self._adopt(x)
+        gh, gw = self.engine.grid
         dense = self.engine.forward(x, L.OUT_DENSE, torch.float32)
-        return dense.reshape(B, g, g, self.cfg.dim).permute(0, 3, 1, 2)
+        return dense.reshape(B, gh, gw, self.cfg.dim).permute(0, 3, 1, 2)
 
     def forward_features(self, x: torch.Tensor, out_dtype=torch.float32) -> torch.Tensor:
         """[B,3,H,W] -> CLS features [B,D] (the [N,D] matrix embedding_classifier.py consumes)."""
+        self._adopt(x)
         return self.engine.forward(x, L.OUT_CLS, out_dtype)
 
     def dense_tokens(self, x: torch.Tensor, out_dtype=torch.bfloat16) -> torch.Tensor:
+        self._adopt(x)
         return self.engine.forward(x, L.OUT_DENSE, out_dtype)
 
     def _layers_ok(self, what):
@@ -133,12 +173,13 @@ class VitDescriptorModel:
             specs.append(LayerOut(i, L.OUT_DENSE, torch.float32, norm))
             if return_class_token:
                 specs.append(LayerOut(i, L.OUT_CLS, torch.float32, norm))
+        self._adopt(x)
         got = self.engine.forward_layers(x, specs)
         step = 2 if return_class_token else 1
         patch = got[::step]
         if reshape:
-            B, g = patch[0].shape[0], self.cfg.img // self.cfg.patch
-            patch = [t.reshape(B, g, g, -1).permute(0, 3, 1, 2).contiguous() for t in patch]
+            B, (gh, gw) = patch[0].shape[0], self.engine.grid
+            patch = [t.reshape(B, gh, gw, -1).permute(0, 3, 1, 2).contiguous() for t in patch]
         if return_class_token:
             return tuple(zip(patch, got[1::2]))
         return tuple(patch)
@@ -157,6 +198,7 @@ class VitDescriptorModel:
         specs = [LayerOut(i, L.OUT_CLS, out=out[:, k * D:(k + 1) * D]) for k, i in enumerate(blocks)]
         if avgpool:
             specs.append(LayerOut(blocks[-1], L.OUT_POOLED, out=out[:, len(blocks) * D:]))
+        self._adopt(x)
         self.engine.forward_layers(x, specs)
         return out
 
@@ -172,7 +214,8 @@ class VitDescriptorModel:
     def get_last_selfattention(self, x: torch.Tensor) -> torch.Tensor:
         """DINO's get_last_selfattention: the softmax attention of the last block, every query row, [B, H, N, N] fp32."""
         self._maps_ok("get_last_selfattention", False)
-        N = self.cfg.n_tokens
+        self._adopt(x)
+        N = self.engine.n_tokens
         _, (att,) = self.engine.forward_attn_maps(x, [AttnMap(self.cfg.layers - 1, N)])
         return att
 
@@ -192,15 +235,16 @@ class VitDescriptorModel:
         bad = [i for i in idx if not 0 <= i < self.cfg.layers]
         if bad:
             raise ValueError(f"block indices {bad} out of range 0..{self.cfg.layers - 1}")
-        N, ncls = self.cfg.n_tokens, 1 if self.cfg.has_cls else 0
+        self._adopt(x)
+        N, ncls = self.engine.n_tokens, 1 if self.cfg.has_cls else 0
         _, got = self.engine.forward_attn_maps(x, [AttnMap(i, 1 if cls_only else N, head_mean) for i in idx])
         res = []
         for t in got:
             if cls_only:
                 t = t[:, 0] if head_mean else t[:, :, 0]
                 if reshape:
-                    g = self.cfg.img // self.cfg.patch
-                    t = t[..., ncls:].reshape(*t.shape[:-1], g, g)
+                    gh, gw = self.engine.grid
+                    t = t[..., ncls:].reshape(*t.shape[:-1], gh, gw)
             res.append(t)
         return res[0] if single else tuple(res)
 
@@ -210,7 +254,7 @@ class VitDescriptorModel:
 
 def load_model(model_name: str, model_path=None, weights=None, device=None, micro_batch: int = 0, streams: int = 0,
                fp8: int = 0, full_last_block: bool = False, ln_fold: bool = True, fp8_cls_bf16: bool = False,
-               resid_fp32: bool = False, ln_fin_fused: bool = False):
+               resid_fp32: bool = False, ln_fin_fused: bool = False, dynamic_size: bool = False):
     """R1.  model_name: 'dinov2' | 'medsam' (reference names) or any key of ARCHS.
     model_path: a PyTorch state_dict file with the canonical key names; loaded with
     torch.load(weights_only=True).  weights: the same dict passed directly.
@@ -219,7 +263,9 @@ def load_model(model_name: str, model_path=None, weights=None, device=None, micr
     like the reference does before it keeps x[:, 0] (default: the CLS rows only, same bits).  fp8_cls_bf16=True (fp8 models
     with a CLS token): the MLP of the CLS rows runs on the bf16 weights (vdr_config.fp8_cls_bf16).  resid_fp32=True: the
     residual stream keeps an fp32 master copy (vdr_config.resid_fp32; bf16 path of the plain ViTs).  ln_fin_fused=True:
-    the LayerNorm fold's row statistics are finalised inside the residual GEMMs instead of by a launch of their own (A/B)."""
+    the LayerNorm fold's row statistics are finalised inside the residual GEMMs instead of by a launch of their own (A/B).
+    dynamic_size=True (ViT / DINOv2 models): the model runs images of any size whose sides are multiples of the patch
+    side, resampling pos_embed as DINOv2's interpolate_pos_encoding does (VitDescriptorModel.set_input_size)."""
     if model_name not in ARCHS:
         raise KeyError(f"unknown model_name {model_name!r}; known: {sorted(ARCHS)} + 'medsam'")
     cfg = VdrConfig(**{**ARCHS[model_name].__dict__, "micro_batch": micro_batch, "streams": streams,
@@ -232,7 +278,7 @@ def load_model(model_name: str, model_path=None, weights=None, device=None, micr
         weights = torch.load(model_path, map_location="cpu", weights_only=True)
     if model_name == "medsam" and any(k.startswith("image_encoder.") for k in weights):
         weights = from_sam_state_dict(weights)
-    model = VitDescriptorModel(cfg, weights, model_name, device)
+    model = VitDescriptorModel(cfg, weights, model_name, device, dynamic_size=dynamic_size)
     model.model_name = model_name
     return model
 
@@ -274,9 +320,10 @@ def get_dense_descriptor(model, img) -> np.ndarray:
 def extract_dense(model, images: torch.Tensor, encoder: bool = True) -> np.ndarray:
     """Batched counterpart of the reference's per-slice loop (tfds_dense_descriptor.py:271-281):
     [B,3,H,W] -> (B, h, w, D) float32 numpy in one call."""
-    g = model.cfg.img // model.cfg.patch
+    model._adopt(images)
+    gh, gw = model.engine.grid
     f = model.engine.forward(images, L.OUT_DENSE if encoder else L.OUT_PATCH_EMBED, torch.float32)
-    return f.reshape(images.shape[0], g, g, model.cfg.dim).cpu().numpy()
+    return f.reshape(images.shape[0], gh, gw, model.cfg.dim).cpu().numpy()
 
 
 class _DropIn:

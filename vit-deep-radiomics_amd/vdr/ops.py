@@ -245,6 +245,19 @@ def patch_embed(images, weight, bias, p, pos=None, row_stride=None, row_offset=0
     return out
 
 
+def interpolate_pos(pos: torch.Tensor, native_grid, grid) -> torch.Tensor:
+    """pos [gh0*gw0, D] fp32 on the device (the patch rows of a position table, no CLS row) -> [gh*gw, D] fp32: DINOv2 /
+    transformers interpolate_pos_encoding (vdr_op_interpolate_pos: bicubic, align_corners=False, fp64 arithmetic)."""
+    lib = L.load()
+    (gh0, gw0), (gh, gw) = native_grid, grid
+    assert pos.is_cuda and pos.dtype == torch.float32 and pos.is_contiguous() and pos.dim() == 2
+    assert pos.shape[0] == gh0 * gw0
+    D = pos.shape[1]
+    out = torch.empty((gh * gw, D), dtype=torch.float32, device=pos.device)
+    L.check(lib.vdr_op_interpolate_pos(pos.data_ptr(), gh0, gw0, D, out.data_ptr(), gh, gw, _s(pos)))
+    return out
+
+
 def attention_relpos(qkv: torch.Tensor, rel_pos_h: torch.Tensor, rel_pos_w: torch.Tensor, batch: int, S: int, heads: int):
     """SAM attention with decomposed relative position bias over `batch` windows/grids of S x S tokens."""
     lib = L.load()

@@ -66,3 +66,30 @@ def expected_weight_shapes(cfg) -> "dict[str, tuple]":
         s["norm.weight"] = (D,)
         s["norm.bias"] = (D,)
     return s
+
+
+def interpolate_pos_embed(pos_embed, grid, ncls: int = 1, native_grid=None) -> torch.Tensor:
+    """Host statement of what vdr_set_input_size builds on the device (DINOv2 / transformers interpolate_pos_encoding):
+    pos_embed [1, ncls + g0h*g0w, D] (or [ncls + g0h*g0w, D]) -> fp32 [1, ncls + gh*gw, D]; the first ncls rows copied
+    unchanged, the patch rows F.interpolate(size=(gh, gw), mode="bicubic", align_corners=False) evaluated in float64
+    and rounded to fp32 once.  grid == the native grid returns the table itself (as fp32).  native_grid: (g0h, g0w),
+    default the square grid the row count gives.  Use: the expected table in tests, or resizing a checkpoint's
+    pos_embed ahead of time."""
+    t = torch.as_tensor(pos_embed).detach().to(torch.float32)
+    t = t.reshape(-1, t.shape[-1])
+    n0, D = t.shape[0] - ncls, t.shape[1]
+    if native_grid is None:
+        g0 = int(round(n0 ** 0.5))
+        native_grid = (g0, g0)
+    g0h, g0w = int(native_grid[0]), int(native_grid[1])
+    if g0h * g0w != n0:
+        raise ValueError(f"pos_embed has {n0} patch rows, not a {g0h} x {g0w} grid")
+    gh, gw = int(grid[0]), int(grid[1])
+    if gh <= 0 or gw <= 0:
+        raise ValueError(f"grid must be positive, got {gh} x {gw}")
+    if (gh, gw) == (g0h, g0w):
+        return t.reshape(1, -1, D).clone()
+    p = t[ncls:].double().reshape(1, g0h, g0w, D).permute(0, 3, 1, 2)
+    p = torch.nn.functional.interpolate(p, size=(gh, gw), mode="bicubic", align_corners=False)
+    p = p.permute(0, 2, 3, 1).reshape(gh * gw, D).to(torch.float32)
+    return torch.cat([t[:ncls], p], dim=0).reshape(1, -1, D)
