@@ -107,6 +107,10 @@ typedef struct {
                       /* bias in every block; needs has_cls = 0, has_pos = 1, pre_ln = 1               */
   int32_t global_mask;/* bit i set: block i attends over the whole grid (SAM ViT-B: 2,5,8,11 = 0x924)  */
   int32_t neck_chans; /* output channels of the conv neck (256); 1x1 conv, LN2d, 3x3 conv, LN2d        */
+                      /* window in {4, 7, 10, 14}.  img: any multiple of patch; with global blocks the     */
+                      /* grid side img / patch is at most 64 (VDR_ERR_UNSUPPORTED beyond).  The input size */
+                      /* of a SAM encoder is a load-time property, as ImageEncoderViT(img_size=...): a     */
+                      /* checkpoint learned at another size loads through vdr_set_weight (below)           */
   /* BASELINE config 5 ("fp8 weights (CDNA4 fp8 MFMA)"): */
   int32_t fp8;        /* 1: the qkv / fc1 (w12) / fc2 (w3) weights are kept as MX-fp8 (OCP e4m3 + e8m0 scale per 32 K    */
                       /* elements) and run on v_mfma_scale_f32_32x32x64_f8f6f4 with MX-fp8 activations; the            */
@@ -175,7 +179,14 @@ const char* vdr_last_error(vdr_handle h);
  * "blocks.{i}.ls1.gamma", "blocks.{i}.mlp.fc1.weight", "blocks.{i}.mlp.w12.weight",
  * "norm.weight", "input_norm.weight" ...).  `host` points to `numel` contiguous fp32
  * values in HOST memory in the PyTorch layout of that key; the library converts,
- * repacks and uploads (synchronously; this is load time, not the hot path). */
+ * repacks and uploads (synchronously; this is load time, not the hot path).
+ * SAM encoder (window > 0) built at another input size than its checkpoint: "pos_embed" is also taken as
+ * [1, g0, g0, D] and "blocks.{i}.attn.rel_pos_h" / "rel_pos_w" of a GLOBAL block as [2 g0' - 1, 64], for any g0, g0' in
+ * 1..64; vdr_finalize resamples them to the handle's grid g = img / patch once, on the device, as segment_anything
+ * does -- pos_embed by vdr_op_interpolate_pos's arithmetic (bicubic, align_corners = False), the rel-pos tables by
+ * vdr_op_interpolate_rel_pos's (get_rel_pos: linear, align_corners = False) -- before the bf16 rel-pos pack.  Tables
+ * of the handle's own shape are used as loaded (no resampling step).  Window-block tables are [2 window - 1, 64]
+ * whatever the grid.  Every other element-count mismatch is VDR_ERR_INVALID. */
 int vdr_set_weight(vdr_handle h, const char* name, const float* host, const int64_t* shape, int ndim);
 
 /* Replaces: the end of load_state_dict / model.eval() (models_archs.py:32-35, tfds_dense_descriptor.py:89,105).
@@ -202,7 +213,7 @@ int vdr_finalize(vdr_handle h);
  * sizes go through im2col.  Not reproduced: DINOv2's older scale_factor + interpolate_offset form and antialiasing.
  * VDR_ERR_INVALID, before the handle or a device is touched: height <= 0, width <= 0; then a null handle; then a side
  * that is not a multiple of patch.  VDR_ERR_UNSUPPORTED: SAM / MedSAM (window > 0: its absolute and relative position
- * tables and the window partition are tied to its grid), token models (patch == 0), post-LN models with blocks.
+ * tables and the window partition are tied to its grid; its size is vdr_config.img, chosen at vdr_create), token models (patch == 0), post-LN models with blocks.
  * VDR_ERR_INCOMPLETE: vdr_finalize has not run. */
 int vdr_set_input_size(vdr_handle h, int height, int width);
 int vdr_get_input_size(vdr_handle h, int* height, int* width);   /* (img, img) until the first set */
@@ -475,7 +486,9 @@ int vdr_op_attention_probs(const void* qkv, void* out, int batch, int seq, int h
  *   rel_pos_h / rel_pos_w  fp32 [2S-1, 64] (the block's parameters)
  *   rel   device scratch, fp32 [batch*S*S*H*Np + Np*32], Np = 2*roundup(2S-1, 32): the products of q with
  *         every relative-offset row of both tables (one MFMA GEMM) and, behind them, the packed bf16 tables
- *   out   [batch*S*S, H*64] bf16.   S in {4, 7, 10, 14} (one pass) or 64 (online softmax). */
+ *   out   [batch*S*S, H*64] bf16.   Any S in 1..64: {4, 7, 10, 14} one pass and 64 online softmax with compile-time
+ *         key coordinates, every other S the run-time-grid kernel (online softmax over 128-key chunks, ragged last
+ *         chunk).  S > 64: VDR_ERR_UNSUPPORTED (the packed operand holds 127 + 127 rows). */
 int vdr_op_attention_relpos(const void* qkv, const float* rel_pos_h, const float* rel_pos_w, float* rel, void* out,
                             int batch, int S, int heads, void* stream);
 
@@ -487,6 +500,13 @@ int vdr_op_attention_relpos(const void* qkv, const float* rel_pos_h, const float
  * align_corners=False) rounded once (torch's fp32 path rounds the source coordinate to fp32 and differs by a few ulp).
  * At most 2^20 grid cells either side. */
 int vdr_op_interpolate_pos(const float* pos, int gh0, int gw0, int D, float* out, int gh, int gw, void* stream);
+
+/* segment_anything get_rel_pos (also transformers' SamVisionAttention): a relative-position table resampled along its
+ * row axis, per channel -- F.interpolate(table[L0, D] as [1, D, L0], size = L, mode = "linear", align_corners = False).
+ * table, out: device fp32, [L0, D] and [L, D].  src = max((i + 0.5) * L0 / L - 0.5, 0), i0 = trunc(src), the upper
+ * neighbour clamped at the last row, weights (1 - t, t) with t = src - i0; evaluated in fp64 and rounded to fp32 once.
+ * A SAM table for grid side g has L = 2 g - 1 rows.  At most 2^30 elements either side. */
+int vdr_op_interpolate_rel_pos(const float* table, int L0, int D, float* out, int L, void* stream);
 
 /* nn.Conv2d(in_chans, D, kernel=p, stride=p) + flatten(2).transpose(1,2) — DINOv2 PatchEmbed,
  * the op called at tfds_dense_descriptor.py:128.

@@ -3,6 +3,7 @@
 for single kernels): both libraries are dlopen'ed side by side, each gets its own handle with the same weights, and the
 headline forward (bench.py's workload: ViT-B/16 224^2, batch 256, bf16 images, CLS out) alternates between them.
    python tools/ab_forward_libs.py path/to/libA.so path/to/libB.so [--model vit_base16_224] [--batch 256] [--rounds 15] [--steps 10]
+--model medsam: the SAM ViT-B image encoder at 1024^2 (neck output) instead of a plain ViT's CLS features.
 Prints per library the median / min / max ms per step over the rounds, the per-round A - B differences, and whether the
 median difference lies inside the round-to-round spread of either side.  The outputs of the two must be bitwise equal."""
 import argparse
@@ -47,25 +48,33 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     a = ap.parse_args()
     torch.cuda.set_device(0)
-    cfg = vo.CONFIGS[a.model]
-    w = vo.make_weights(cfg, seed=1)
+    sam = a.model == "medsam"
+    if sam:
+        from oracle import sam_oracle as so
+        cfg = so.SAM_VIT_B
+        w = so.make_weights(cfg, seed=1)
+    else:
+        cfg = vo.CONFIGS[a.model]
+        w = vo.make_weights(cfg, seed=1)
+    mode = vdr.OUT_ENCODER if sam else vdr.OUT_CLS
     engines = [engine_on(p, vdr.ARCHS[a.model], w) for p in a.libs]
     x = torch.rand(a.batch, 3, cfg.img, cfg.img).to(torch.bfloat16).cuda()
-    outs = [torch.empty(a.batch, cfg.dim, dtype=torch.float32, device="cuda") for _ in engines]
+    shape = (a.batch, cfg.grid, cfg.grid, cfg.out_chans) if sam else (a.batch, cfg.dim)
+    outs = [torch.empty(shape, dtype=torch.float32, device="cuda") for _ in engines]
     times = [[] for _ in engines]
     for rnd in range(a.rounds + 1):
         order = [0, 1] if rnd & 1 else [1, 0]  # alternate who goes first
         for i in order:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            engines[i].forward_into(x, outs[i], vdr.OUT_CLS)
+            engines[i].forward_into(x, outs[i], mode)
             e0.record()
             for _ in range(a.steps):
-                engines[i].forward_into(x, outs[i], vdr.OUT_CLS)
+                engines[i].forward_into(x, outs[i], mode)
             e1.record()
             torch.cuda.synchronize()
             if rnd:  # round 0 warms up
                 times[i].append(e0.elapsed_time(e1) / a.steps)
-    print(f"{a.model} batch {a.batch} bf16 images, CLS out; {a.rounds} interleaved rounds of {a.steps} steps")
+    print(f"{a.model} batch {a.batch} bf16 images, {'neck' if sam else 'CLS'} out; {a.rounds} interleaved rounds of {a.steps} steps")
     print("outputs bitwise equal:", torch.equal(outs[0], outs[1]))
     med = []
     for p, t in zip(a.libs, times):

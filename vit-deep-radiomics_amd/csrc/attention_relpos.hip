@@ -56,6 +56,8 @@ struct AttnRK {
   int64_t ld_qkv, ld_out;
   int qt_per_block;
   int n_chunks;
+  int g;        // attn_relpos_any_kernel: grid side (seq = g * g) and 1 / g
+  float inv_g;
 };
 
 // Workgroup: 4 waves.  (MULTI with 8 waves = 8 query tiles per workgroup, half the LDS-DMA pieces per wave and half the
@@ -362,9 +364,241 @@ static hipError_t launch_rp(const AttnRK& k, int batch, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------
+// attn_relpos_any_kernel<DB>: global attention over a g x g grid with g a RUN-TIME value in 1..64 (SAM / MedSAM loaded at
+// another input size).  Same data flow as the chunked kernel above -- 128-key chunks of K / V^T in LDS by LDS-DMA, one
+// query tile of 32 rows per wave, online softmax over the chunks, S^T = K.Q^T so that a softmax row is lane-local -- but
+// the key of an accumulator element is no compile-time (kh, kw) any more.  Per wave, the two bias rows of its 32 queries
+//     bh[j][query] = T[qh - j + g-1]          (rel_h of key row j),      j < g
+//     bw[j][query] = T[Npad/2 + qw - j + g-1] (rel_w of key column j)
+// are written to LDS once (j-major: the 32 queries of a j are 32 consecutive banks, the two lane halves of an element sit
+// on different j, at worst a 2-way conflict), and every logit reads bh[key / g] + bw[key % g] there.  key / g is
+// trunc((key + 0.5) / g) in fp32: (key + 0.5) / g is at least 1 / (2g) >= 2^-7 away from an integer and smaller than 2^7,
+// far outside the 2^-16 the two fp32 roundings can move it.  The last chunk is ragged: K / V rows past the sequence
+// repeat the last key (their logits are masked to -inf like the single-pass kernels' padding), and so does their (kh, kw).
+// DB: chunk c+1 streams into a second K / V image under the arithmetic of chunk c (one barrier per chunk); without it a
+// chunk is loaded, waited for and consumed (two barriers), with half the LDS so that a second workgroup fits a CU.
+// LDS: (DB ? 2 : 1) x 32 KB + 1 KB x g.
+template <bool DB>
+__global__ __launch_bounds__(256, 2) void attn_relpos_any_kernel(AttnRK p) {
+  constexpr int NT = 4, KEYS = NT * 32;
+  constexpr int BUF = 2 * KEYS * 128;  // K image + V image
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int hh = lane >> 5;
+  const int l31 = lane & 31;
+  const int swz = (lane >> 1) & 7;
+  typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+  const int tq = (lane & 15) >> 2, tp = lane & 3, dg = (lane >> 4) & 1;
+  const int vkey = 4 * hh + tq;
+  const int vbase = KEYS * 128 + vkey * 128 + 8 * (tp & 1);
+  int vch[2];
+#pragma unroll
+  for (int nd = 0; nd < 2; ++nd) vch[nd] = ((4 * nd + 2 * dg + (tp >> 1)) ^ (((vkey >> 1) & 1) << 2)) * 16;
+
+  const int g = p.g;
+  const int nqt = (p.seq + 31) >> 5;
+  const int nyb = (nqt + p.qt_per_block - 1) / p.qt_per_block;
+  const int vid = nyb > 1 ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
+  const int bh = vid / nyb;
+  const int yb = vid - bh * nyb;
+  const int b = bh / p.heads;
+  const int hd = bh - b * p.heads;
+  const int HD = p.heads * 64;
+  const int npad = 2 * ((2 * g - 1 + 31) / 32 * 32);  // relpos_npad(g)
+  const bf16_t* qb = p.qkv + (int64_t)b * p.seq * p.ld_qkv + hd * 64;
+  const bf16_t* kb = qb + HD;
+  const bf16_t* vb = qb + 2 * HD;
+  bf16_t* ob = p.out + (int64_t)b * p.seq * p.ld_out + hd * 64;
+  constexpr float LOG2E = 1.44269504088896341f;
+
+  // this wave's bias rows: bh at [j][l31], bw behind them
+  float* bias = reinterpret_cast<float*>(smem + (DB ? 2 : 1) * BUF) + wave * (2 * g * 32);
+  const float* bias_h = bias + l31;
+  const float* bias_w = bias + g * 32 + l31;
+
+  const int qt_begin = yb * p.qt_per_block;
+  const int qt_end = min(nqt, qt_begin + p.qt_per_block);
+  const int qt = qt_begin + wave;
+  const bool valid = qt < qt_end;
+
+  f32x16 o[2];
+#pragma unroll
+  for (int nd = 0; nd < 2; ++nd)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) o[nd][e] = 0.0f;
+  float m_run = -INFINITY, l_run = 0.0f;
+  bf16x8 qf[4];
+  {
+    int q = (valid ? qt : qt_begin) * 32 + l31;
+    q = q < p.seq ? q : p.seq - 1;
+    const bf16_t* src = qb + (int64_t)q * p.ld_qkv + hh * 8;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(src + ks * 16);
+    const int qh = q / g, qw = q - qh * g;
+    const float* trow = p.T + (((int64_t)b * p.seq + q) * p.heads + hd) * npad;
+    // lower lane half: the query's rel_h row, upper half: its rel_w row; entry j is src[-j]
+    const float* brow = hh ? trow + npad / 2 + qw + (g - 1) : trow + qh + (g - 1);
+    float* dst = bias + hh * g * 32 + l31;
+    for (int j = 0; j < g; ++j) dst[j * 32] = brow[-j];
+  }
+
+  auto stage_issue = [&](int kc0, char* buf) {
+    char* sK = buf;
+    char* sVt = buf + KEYS * 128;
+#pragma unroll
+    for (int q = 0; q < NT; ++q) {
+      const int piece = wave * NT + q;
+      const int r = piece * 8 + (lane >> 3);
+      const int c = (lane & 7) ^ ((r >> 1) & 7);
+      int key = kc0 + r;
+      key = key < p.seq ? key : p.seq - 1;
+      glds16_raw(kb + (int64_t)key * p.ld_qkv + c * 8, sK + piece * 1024);
+    }
+#pragma unroll
+    for (int q = 0; q < NT; ++q) {
+      const int piece = wave * NT + q;
+      const int r = piece * 8 + (lane >> 3);
+      const int c = (lane & 7) ^ (((r >> 1) & 1) << 2);
+      int key = kc0 + r;
+      key = key < p.seq ? key : p.seq - 1;
+      glds16_raw(vb + (int64_t)key * p.ld_qkv + c * 8, sVt + piece * 1024);
+    }
+  };
+  auto stage_wait = [&]() {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  };
+
+  auto process = [&](int kc0, bool rescale, const char* buf) {
+    const char* sK = buf;
+    const __attribute__((address_space(3))) char* sVtr = (const __attribute__((address_space(3))) char*)buf + vbase;
+    f32x16 s[NT];
+    __builtin_amdgcn_s_setprio(0);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) s[t][e] = 0.0f;
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const bf16x8 kf =
+            *reinterpret_cast<const bf16x8*>(sK + (t * 32 + l31) * 128 + (((2 * ks + hh) ^ swz) * 16));
+        s[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], s[t], 0, 0, 0);
+      }
+    }
+    __builtin_amdgcn_s_setprio(2);
+    // logits = s * dh^-0.5 + bh[key / g] + bw[key % g], the key of element (t, e, half) at run time
+    const int key_lane = kc0 + 4 * hh;
+    const int last = p.seq - 1;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int key = min(key_lane + t * 32 + (e & 3) + 8 * (e >> 2), last);
+        const int kh = (int)(((float)key + 0.5f) * p.inv_g);
+        const int kw = key - kh * g;
+        s[t][e] = fmaf(s[t][e], 0.125f, bias_h[kh * 32] + bias_w[kw * 32]);
+      }
+      if (kc0 + t * 32 + 32 > p.seq) mask_keys(s[t], kc0 + t * 32, hh, p.seq);
+    }
+    float mx = row_max_tiles<NT>(s);
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float m_new = fmaxf(m_run, mx);
+    if (rescale) {
+      const float alpha = fast_exp2((m_run - m_new) * LOG2E);
+      l_run *= alpha;
+#pragma unroll
+      for (int nd = 0; nd < 2; ++nd)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) o[nd][e] *= alpha;
+    }
+    m_run = m_new;
+    const float nmb = -m_new * LOG2E;
+    f32x2 lsum2 = {0.0f, 0.0f};
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        bf16x8 pf;
+        softmax_slice8(s[t], s2, LOG2E, nmb, lsum2, pf);
+#pragma unroll
+        for (int nd = 0; nd < 2; ++nd) {
+          const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(sVtr + (t * 32 + s2 * 16) * 128 + vch[nd]));
+          const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(sVtr + (t * 32 + s2 * 16 + 8) * 128 + vch[nd]));
+          bf16x8 vf;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            vf[j] = lo[j];
+            vf[4 + j] = hi[j];
+          }
+          o[nd] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o[nd], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    l_run += lsum2[0] + lsum2[1];
+  };
+
+  // every ordinary load (q, the bias rows) is retired before the first LDS-DMA piece is issued and "used" right after the
+  // first explicit wait, so that hipcc places no counted vmcnt of its own behind a prefetch (see the chunked kernel above)
+  stage_issue(0, smem);
+  stage_wait();
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) asm volatile("" : "+v"(qf[ks]));
+  for (int c = 0; c < p.n_chunks; ++c) {
+    const bool more = c + 1 < p.n_chunks;
+    if (DB) {
+      if (more) stage_issue((c + 1) * KEYS, smem + ((c + 1) & 1) * BUF);
+      if (valid) process(c * KEYS, c > 0, smem + (c & 1) * BUF);
+      if (more) stage_wait();
+    } else {
+      if (valid) process(c * KEYS, c > 0, smem);
+      if (more) {
+        __syncthreads();  // every wave is done with the image before it is overwritten
+        stage_issue((c + 1) * KEYS, smem);
+        stage_wait();
+      }
+    }
+  }
+  if (valid) {
+    const float l = l_run + __shfl_xor(l_run, 32, 64);
+    const float inv = 1.0f / l;
+    const int q = qt * 32 + l31;
+    store_row64_bf16(ob + (int64_t)(q < p.seq ? q : 0) * p.ld_out, o, inv, hh, q < p.seq);
+  }
+}
+
+// Buffering of attn_relpos_any_kernel by what fits a CU's 160 KB of LDS: up to g = 48 the single-buffered form (32 KB + 1 KB x g)
+// leaves room for a second workgroup, which hides its two barriers per chunk better than a prefetch does (g = 32 / 48, 12 heads,
+// batch 16: 0.168 / 0.763 ms per op against 0.207 / 0.978 double-buffered); beyond, one workgroup fits either way and the
+// prefetch wins (forced at g = 64: 2.79 against 3.34 ms).  DESIGN 4.3b
+static inline bool relpos_any_double_buffered(int g) { return g > 48; }
+
+template <bool DB>
+static hipError_t launch_rp_any(const AttnRK& k, int batch, hipStream_t s) {
+  const size_t lds = (size_t)(DB ? 2 : 1) * 2 * 128 * 128 + (size_t)4 * 2 * k.g * 32 * 4;
+  auto fn = attn_relpos_any_kernel<DB>;
+  static PerDeviceFlag attr;
+  const int dev = current_device_index();
+  if (dev < 0) return hipErrorInvalidDevice;
+  if (!attr.done[dev]) {  // the largest request of any g: 128 KB (DB) / 96 KB
+    hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (DB ? 2 : 1) * 2 * 128 * 128 + 4 * 2 * 64 * 32 * 4);
+    if (e != hipSuccess) return e;
+    attr.done[dev] = true;
+  }
+  const int nqt = (k.seq + 31) / 32;
+  const dim3 grid((unsigned)(batch * k.heads * ((nqt + k.qt_per_block - 1) / k.qt_per_block)));
+  hipLaunchKernelGGL(fn, grid, dim3(256), lds, s, k);
+  return hipGetLastError();
+}
+
 hipError_t launch_attention_relpos(const void* qkv, const float* T, void* out, int batch, int S, int heads,
-                                   hipStream_t s) {
-  if (batch <= 0 || S <= 0 || heads <= 0) return hipErrorInvalidValue;
+                                   hipStream_t s, int any_variant) {
+  if (batch <= 0 || S <= 0 || S > 64 || heads <= 0) return hipErrorInvalidValue;
   AttnRK k;
   k.qkv = (const bf16_t*)qkv;
   k.T = T;
@@ -376,6 +610,14 @@ hipError_t launch_attention_relpos(const void* qkv, const float* T, void* out, i
   const int nqt = (k.seq + 31) / 32;
   k.qt_per_block = nqt;
   k.n_chunks = 1;
+  k.g = S;
+  k.inv_g = 1.0f / (float)S;
+  auto any = [&](bool db) {
+    k.qt_per_block = 4;
+    k.n_chunks = (k.seq + 127) / 128;
+    return db ? launch_rp_any<true>(k, batch, s) : launch_rp_any<false>(k, batch, s);
+  };
+  if (any_variant) return any(any_variant == 2);
   switch (S) {
     case 4:
       return launch_rp<2, 4, false>(k, batch, s);
@@ -390,7 +632,7 @@ hipError_t launch_attention_relpos(const void* qkv, const float* T, void* out, i
       k.n_chunks = (k.seq + 127) / 128;
       return launch_rp<4, 64, true>(k, batch, s);
     default:
-      return hipErrorInvalidValue;  // grid sides outside {4, 7, 10, 14, 64} are not instantiated
+      return any(relpos_any_double_buffered(S));  // every other side up to 64: the run-time-grid kernel
   }
 }
 

@@ -56,7 +56,37 @@ __global__ __launch_bounds__(256) void pos_interp_kernel(const float* __restrict
   out[idx] = (float)acc;
 }
 
+// get_rel_pos of segment_anything (and transformers' SamVisionAttention): a relative-position table [L0][D] resampled to
+// [L][D] rows by F.interpolate(mode="linear", align_corners=False) along the row axis, per channel.  ATen's
+// upsample_linear1d in double:  src = max((i + 0.5) * (L0 / L) - 0.5, 0),  i0 = trunc(src),  i1 = i0 + (i0 < L0 - 1),
+// w1 = src - i0,  out = (1 - w1) * table[i0] + w1 * table[i1], rounded to fp32 once.
+__global__ __launch_bounds__(256) void relpos_interp_kernel(const float* __restrict__ table, float* __restrict__ out, int L0,
+                                                            int D, int L, double scale) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)L * D) return;
+  const int i = (int)(idx / D);
+  const int d = (int)(idx - (int64_t)i * D);
+  double src = ((double)i + 0.5) * scale - 0.5;
+  src = src < 0.0 ? 0.0 : src;
+  int i0 = (int)src;
+  i0 = i0 < L0 - 1 ? i0 : L0 - 1;
+  const int i1 = i0 + (i0 < L0 - 1 ? 1 : 0);
+  double w1 = src - (double)i0;
+  w1 = w1 < 0.0 ? 0.0 : (w1 > 1.0 ? 1.0 : w1);
+  const double w0 = 1.0 - w1;
+  out[idx] = (float)(w0 * (double)table[(int64_t)i0 * D + d] + w1 * (double)table[(int64_t)i1 * D + d]);
+}
+
 }  // namespace
+
+hipError_t launch_relpos_interp(const float* table, int L0, int D, float* out, int L, hipStream_t s) {
+  if (!table || !out || L0 <= 0 || D <= 0 || L <= 0) return hipErrorInvalidValue;
+  const int64_t total = (int64_t)L * D;
+  if (total > ((int64_t)1 << 31)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(relpos_interp_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, table, out, L0, D, L,
+                     (double)L0 / (double)L);
+  return hipGetLastError();
+}
 
 hipError_t launch_pos_interp(const float* pos, int gh0, int gw0, int D, float* out, int gh, int gw, hipStream_t s) {
   if (!pos || !out || gh0 <= 0 || gw0 <= 0 || D <= 0 || gh <= 0 || gw <= 0) return hipErrorInvalidValue;

@@ -54,7 +54,14 @@ struct WSlot {
   void* dev = nullptr;
   bool set = false;
   std::vector<float> host;  // fp32 copy kept until resolve() (LayerNorm folding needs it)
+  // SAM encoder built at another input size than its checkpoint: pos_embed (resample = RS_POS) and the rel-pos tables of
+  // the global blocks (RS_REL) are also taken at their NATIVE shape -- [1, g0, g0, D] / [2 g0 - 1, 64] -- kept in dev_src,
+  // and resampled into dev by resolve().  src_n: g0 / 2 g0 - 1 of the table in dev_src; 0 = dev holds the loaded table.
+  int resample = 0;
+  int64_t src_n = 0;
+  void* dev_src = nullptr;
 };
+enum { RS_NONE = 0, RS_POS = 1, RS_REL = 2 };
 
 struct LayerW {
   const float *n1w, *n1b, *n2w, *n2b, *bqkv, *bproj, *b1, *b2, *ls1, *ls2;
@@ -165,6 +172,7 @@ void build_slots(vdr_model* m) {
   }
   if (c.has_cls) add_slot(m, "cls_token", W_VEC_F32, 1, D);
   if (c.has_pos) add_slot(m, "pos_embed", W_VEC_F32, m->n_tokens, D);
+  if (c.has_pos && c.window > 0) m->slots.back().resample = RS_POS;
   if (c.input_ln) {
     add_slot(m, "input_norm.weight", W_VEC_F32, 1, D);
     add_slot(m, "input_norm.bias", W_VEC_F32, 1, D);
@@ -177,8 +185,11 @@ void build_slots(vdr_model* m) {
     add_slot(m, p + "attn.qkv.bias", W_VEC_F32, 1, 3 * D);
     if (c.window > 0) {
       const int size = ((c.global_mask >> i) & 1) ? c.img / c.patch : c.window;
+      const int rs = ((c.global_mask >> i) & 1) ? RS_REL : RS_NONE;  // (window tables do not depend on the grid)
       add_slot(m, p + "attn.rel_pos_h", W_VEC_F32, 2 * size - 1, 64);
+      m->slots.back().resample = rs;
       add_slot(m, p + "attn.rel_pos_w", W_VEC_F32, 2 * size - 1, 64);
+      m->slots.back().resample = rs;
     }
     add_slot(m, p + "attn.proj.weight", W_MAT_BF16, D, D);
     add_slot(m, p + "attn.proj.bias", W_VEC_F32, 1, D);
@@ -324,6 +335,22 @@ int resolve(vdr_model* m) {
       if (s.host.empty())
         return fail(m, VDR_ERR_INCOMPLETE, "weights changed after the first forward: set every weight again (" + s.name + ")");
   const vdr_config& c = m->cfg;
+  // SAM tables loaded at their native shape: resampled to the handle's grid (segment_anything: bicubic pos_embed as
+  // vdr_op_interpolate_pos, get_rel_pos's linear rule as vdr_op_interpolate_rel_pos); the consumers below (rel-pos pack,
+  // forward) run later on the same (null) stream and resolve() synchronises before it returns
+  for (auto& sl : m->slots) {
+    if (!sl.src_n) continue;
+    VDR_TRY(hipSetDevice(m->device), "hipSetDevice");
+    if (!sl.dev) VDR_TRY(hipMalloc(&sl.dev, (size_t)sl.numel * 4 + 256), "hipMalloc(resampled table)");
+    if (sl.resample == RS_POS) {
+      const int g = c.img / c.patch;
+      VDR_TRY(launch_pos_interp((const float*)sl.dev_src, (int)sl.src_n, (int)sl.src_n, c.dim, (float*)sl.dev, g, g, nullptr),
+              "pos_interp");
+    } else {
+      VDR_TRY(launch_relpos_interp((const float*)sl.dev_src, (int)sl.src_n, 64, (float*)sl.dev, (int)sl.rows, nullptr),
+              "relpos_interp");
+    }
+  }
   m->w_patch = dev_of(m, "patch_embed.proj.weight");
   m->b_patch = (const float*)dev_of(m, "patch_embed.proj.bias");
   m->cls = (const float*)dev_of(m, "cls_token");
@@ -1309,7 +1336,7 @@ int run_sam(vdr_model* m, hipStream_t s, const Carve& w, int mb, int out_dtype, 
       Scope sc(m, s, VDR_K_ATTENTION, 4.0 * (double)S * S * S * S * 64.0 * H * nb + 2.0 * T * H * relpos_npad(S) * 64,
                2.0 * (double)T * 4 * D);
       VDR_TRY(relpos_products(w.qkv, L.reltab, w.rel, T, S, H, s), "relpos");
-      VDR_TRY(launch_attention_relpos(w.qkv, w.rel, w.o, nb, S, H, s), "attention_relpos");
+      VDR_TRY(launch_attention_relpos(w.qkv, w.rel, w.o, nb, S, H, s, glob ? env_int("VDR_RELPOS_ANY", 0) : 0), "attention_relpos");
     }
     {
       // (not through gemm(): the profiler books T rows of A, the windowed ones with their padding, but M output rows)
@@ -1531,13 +1558,16 @@ int vdr_create(const vdr_config* cfg, int device, vdr_handle* out) {
                 "blocks, below the 0.99 gate, and is not shipped)");
   if (c.window > 0) {
     const int g = c.patch ? c.img / c.patch : 0;
-    auto side_ok = [](int v) { return v == 4 || v == 7 || v == 10 || v == 14 || v == 64; };
+    auto side_ok = [](int v) { return v == 4 || v == 7 || v == 10 || v == 14; };
     if (!c.patch || c.has_cls || !c.has_pos || !c.pre_ln || c.input_ln || c.layerscale || c.act != VDR_ACT_GELU)
       return fail(nullptr, VDR_ERR_INVALID, "SAM encoder: needs patch > 0, has_cls = 0, has_pos = 1, pre_ln = 1, GELU, no LayerScale");
     if (c.neck_chans <= 0 || c.neck_chans % 64 || c.neck_chans > 2048)
       return fail(nullptr, VDR_ERR_UNSUPPORTED, "SAM encoder: neck_chans must be a positive multiple of 64");
-    if (!side_ok(c.window) || c.window == 64 || (c.global_mask && !side_ok(g)))
-      return fail(nullptr, VDR_ERR_UNSUPPORTED, "SAM encoder: window side in {4,7,10,14}, grid side of global blocks in {4,7,10,14,64}");
+    if (!side_ok(c.window)) return fail(nullptr, VDR_ERR_UNSUPPORTED, "SAM encoder: window side in {4,7,10,14}");
+    if (c.global_mask && g > 64)
+      return fail(nullptr, VDR_ERR_UNSUPPORTED,
+                  "SAM encoder: the grid side of global blocks (img / patch = " + std::to_string(g) +
+                      ") must be at most 64: the packed rel-pos operand holds 127 + 127 rows");
     if (c.layers > 31) return fail(nullptr, VDR_ERR_UNSUPPORTED, "SAM encoder: at most 31 blocks");
   }
   int rc = check_device(nullptr);
@@ -1563,8 +1593,10 @@ int vdr_create(const vdr_config* cfg, int device, vdr_handle* out) {
 void vdr_destroy(vdr_handle h) {
   if (!h) return;
   DeviceGuard dg(h->device);
-  for (auto& s : h->slots)
+  for (auto& s : h->slots) {
     if (s.dev) hipFree(s.dev);
+    if (s.dev_src) hipFree(s.dev_src);
+  }
   for (auto& L : h->layers) {
     if (L.wqkv_f) hipFree(L.wqkv_f);
     if (L.reltab) hipFree(L.reltab);
@@ -1611,11 +1643,32 @@ int vdr_set_weight(vdr_handle m, const char* name, const float* host, const int6
   WSlot& s = m->slots[it->second];
   int64_t numel = 1;
   for (int i = 0; i < ndim; ++i) numel *= shape[i];
-  if (numel != s.numel)
+  // SAM handle, a table at another (native) grid than the handle's: pos_embed [1, g0, g0, D], rel_pos_h / rel_pos_w of a
+  // global block [2 g0 - 1, 64], g0 in 1..64
+  int64_t src_n = 0;
+  if (numel != s.numel && s.resample == RS_POS && ndim == 4 && shape[0] == 1 && shape[1] == shape[2] && shape[1] >= 1 &&
+      shape[1] <= 64 && shape[3] == m->cfg.dim)
+    src_n = shape[1];
+  if (numel != s.numel && s.resample == RS_REL && ndim == 2 && shape[1] == 64 && shape[0] >= 1 && shape[0] <= 127 &&
+      (shape[0] & 1))
+    src_n = shape[0];
+  if (numel != s.numel && !src_n)
     return fail(m, VDR_ERR_INVALID, std::string(name) + ": expected " + std::to_string(s.numel) + " elements, got " +
                                         std::to_string(numel));
   DeviceGuard dg(m->device);
   if (!dg.ok) return fail(m, VDR_ERR_HIP, "hipSetDevice failed");
+  if (src_n) {  // kept as loaded; vdr_finalize resamples it
+    if (s.dev_src) VDR_TRY(hipFree(s.dev_src), "hipFree(native table)");
+    s.dev_src = nullptr;
+    VDR_TRY(hipMalloc(&s.dev_src, (size_t)numel * 4 + 256), "hipMalloc(native table)");
+    VDR_TRY(hipMemcpy(s.dev_src, host, (size_t)numel * 4, hipMemcpyHostToDevice), "hipMemcpy(native table)");
+    s.host.assign(host, host + numel);
+    s.src_n = src_n;
+    s.set = true;
+    m->resolved = false;
+    return VDR_OK;
+  }
+  s.src_n = 0;
   std::vector<uint16_t> bf;
   std::vector<float> fv;
   const void* src = host;
@@ -2265,6 +2318,8 @@ int vdr_op_attention_relpos(const void* qkv, const float* rel_pos_h, const float
                             int batch, int S, int heads, void* stream) {
   if (!qkv || !rel_pos_h || !rel_pos_w || !rel || !out) return fail(nullptr, VDR_ERR_INVALID, "null argument");
   if (batch <= 0 || S <= 0 || heads <= 0) return fail(nullptr, VDR_ERR_INVALID, "bad shape");
+  if (S > 64)
+    return fail(nullptr, VDR_ERR_UNSUPPORTED, "vdr_op_attention_relpos: S must be at most 64 (the packed rel-pos operand holds 127 + 127 rows)");
   int rc = check_device(nullptr);
   if (rc) return rc;
   const int64_t tokens = (int64_t)batch * S * S;
@@ -2272,7 +2327,21 @@ int vdr_op_attention_relpos(const void* qkv, const float* rel_pos_h, const float
   void* table = rel + tokens * heads * npad;  // packed bf16 tables behind the products
   OP_TRY(launch_relpos_pack(rel_pos_h, rel_pos_w, table, S, (hipStream_t)stream), "relpos_pack");
   OP_TRY(relpos_products(qkv, table, rel, tokens, S, heads, (hipStream_t)stream), "relpos");
-  OP_TRY(launch_attention_relpos(qkv, rel, out, batch, S, heads, (hipStream_t)stream), "attention_relpos");
+  OP_TRY(launch_attention_relpos(qkv, rel, out, batch, S, heads, (hipStream_t)stream, env_int("VDR_RELPOS_ANY", 0)), "attention_relpos");
+  return VDR_OK;
+}
+
+int vdr_op_interpolate_rel_pos(const float* table, int L0, int D, float* out, int L, void* stream) {
+  if (!table) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_interpolate_rel_pos: table is null");
+  if (!out) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_interpolate_rel_pos: out is null");
+  if (L0 <= 0) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_interpolate_rel_pos: L0 must be positive");
+  if (D <= 0) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_interpolate_rel_pos: D must be positive");
+  if (L <= 0) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_interpolate_rel_pos: L must be positive");
+  if ((int64_t)L0 * D > (1 << 30) || (int64_t)L * D > (1 << 30))
+    return fail(nullptr, VDR_ERR_INVALID, "vdr_op_interpolate_rel_pos: more than 2^30 table elements");
+  int rc = check_device(nullptr);
+  if (rc) return rc;
+  OP_TRY(launch_relpos_interp(table, L0, D, out, L, (hipStream_t)stream), "relpos_interp");
   return VDR_OK;
 }
 

@@ -188,9 +188,14 @@ hipError_t launch_affine_cubic(const void* src, int dtype, int H, int W, int64_t
 static inline int relpos_npad(int S) { return 2 * ((2 * S - 1 + 31) / 32 * 32); }
 hipError_t launch_relpos_pack(const float* rel_h, const float* rel_w, void* table, int S, hipStream_t s);
 //   softmax(q k^T / 8 + T[qh - kh + S-1] + T[Npad/2 + qw - kw + S-1]) v per (window, head);
-//   T fp32 [batch*S*S*heads][Npad]; S in {4, 7, 10, 14} single pass, 64 chunked
+//   T fp32 [batch*S*S*heads][Npad]; S in {4, 7, 10, 14} single pass, 64 chunked, every other S <= 64 the run-time-grid
+//   kernel (attn_relpos_any_kernel).  any_variant (tuning / measurements): 1 / 2 force that kernel, single / double
+//   buffered, at any S
 hipError_t launch_attention_relpos(const void* qkv, const float* T, void* out, int batch, int S, int heads,
-                                   hipStream_t s);
+                                   hipStream_t s, int any_variant = 0);
+//   rel-pos table resampling (pos_interp.hip): get_rel_pos of segment_anything, i.e. F.interpolate(mode="linear",
+//   align_corners=False) along the rows of table [L0][D] -> out [L][D]; fp64 arithmetic, one rounding to fp32
+hipError_t launch_relpos_interp(const float* table, int L0, int D, float* out, int L, hipStream_t s);
 
 // 3x3 / pad 1 im2col over NHWC tokens of a g x g grid: col[r][j*C + c] = y[(y+ky-1, x+kx-1)][c], j = ky*3 + kx
 hipError_t launch_im2col3(const void* y, void* col, int batch, int g, int C, hipStream_t s);

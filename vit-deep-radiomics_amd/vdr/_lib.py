@@ -91,6 +91,7 @@ SYMBOLS = {
     "vdr_op_attention_probs": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vdr_op_attention_relpos": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "vdr_op_interpolate_pos": (_I, [_P, _I, _I, _I, _P, _I, _I, _P]),
+    "vdr_op_interpolate_rel_pos": (_I, [_P, _I, _I, _P, _I, _P]),
     "vdr_op_patch_embed": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vdr_profile_enable": (_I, [_P, _I]),
     "vdr_profile_mask": (_I, [_P, C.c_uint32]),

@@ -186,7 +186,7 @@ class Engine:
         height, width = int(height), int(width)
         if cfg.window > 0:
             raise ValueError("set_input_size: the SAM encoder's position tables and window partition are tied to its "
-                             f"{cfg.img}x{cfg.img} input")
+                             f"{cfg.img}x{cfg.img} input; its size is chosen at load time (load_model(..., img_size=...))")
         if not cfg.patch:
             raise ValueError("set_input_size: a token model has no input size")
         if height <= 0 or width <= 0 or height % cfg.patch or width % cfg.patch:

@@ -52,6 +52,21 @@ def from_sam_state_dict(sd):
     return out
 
 
+def sam_input_side(img_size, patch: int) -> int:
+    """The square input side a SAM encoder is built at (load_model's img_size): one int, or an equal (h, w) pair; a
+    positive multiple of the patch side with at most 64 patches a side (the global-attention kernels' limit)."""
+    if isinstance(img_size, (tuple, list)):
+        if len(img_size) != 2 or int(img_size[0]) != int(img_size[1]):
+            raise ValueError(f"img_size: the SAM encoder takes square inputs, got {tuple(img_size)}")
+        img_size = img_size[0]
+    side = int(img_size)
+    if side <= 0 or side % patch:
+        raise ValueError(f"img_size must be a positive multiple of the patch side {patch}, got {side}")
+    if side // patch > 64:
+        raise ValueError(f"img_size {side}: {side // patch} patches a side, the SAM global attention takes at most 64")
+    return side
+
+
 def intermediate_layer_indices(n, depth: int) -> "list[int]":
     """The blocks DINOv2's get_intermediate_layers returns (DinoVisionTransformer._get_intermediate_layers_not_chunked):
     an int n means the last n blocks; a sequence means those block indices, returned in block order (the blocks are
@@ -77,8 +92,9 @@ class VitDescriptorModel:
     """Frozen-ViT feature extractor with the attributes the reference's hot loop dispatches on."""
 
     def __init__(self, cfg: VdrConfig, weights: "dict[str, torch.Tensor]", model_name: str = "vit", device=None,
-                 dynamic_size: bool = False):
-        """dynamic_size=True: every image method first adopts the size of the images it is given (x.shape[-2:]), as
+                 dynamic_size: bool = False, sized: bool = False):
+        """sized=True (SAM encoders built at another side than the reference's 1024, load_model's img_size):
+        get_dense_descriptor prepares a raw slice at cfg.img in one resize.  dynamic_size=True: every image method first adopts the size of the images it is given (x.shape[-2:]), as
         DINOv2 and transformers do with interpolate_pos_encoding; the position table is rebuilt only when the size
         changes.  False (default): other sizes are refused until set_input_size names one."""
         if dynamic_size and cfg.window > 0:
@@ -87,6 +103,7 @@ class VitDescriptorModel:
         self.cfg = cfg
         self.model_name = model_name  # tfds_dense_descriptor.py:66 assigns this attribute
         self.dynamic_size = bool(dynamic_size)
+        self.sized = bool(sized)
         self.engine = Engine(cfg, device)
         self.engine.load_weights(weights)
         self.device = self.engine.device
@@ -133,7 +150,7 @@ class VitDescriptorModel:
 
     def image_encoder(self, x: torch.Tensor) -> torch.Tensor:
         """Channel-first dense map [B,D,h,w], the layout tfds_dense_descriptor.py:123-126 squeezes and
-        transposes to (h,w,D).  SAM / MedSAM models return the conv-neck output [B,256,64,64]."""
+        transposes to (h,w,D).  SAM / MedSAM models return the conv-neck output [B,256,g,g] (g = 64 at 1024^2)."""
         B = x.shape[0]
         if self.cfg.window > 0:
             return self.engine.forward(x, L.OUT_ENCODER, torch.float32).permute(0, 3, 1, 2)
@@ -254,7 +271,7 @@ class VitDescriptorModel:
 
 def load_model(model_name: str, model_path=None, weights=None, device=None, micro_batch: int = 0, streams: int = 0,
                fp8: int = 0, full_last_block: bool = False, ln_fold: bool = True, fp8_cls_bf16: bool = False,
-               resid_fp32: bool = False, ln_fin_fused: bool = False, dynamic_size: bool = False):
+               resid_fp32: bool = False, ln_fin_fused: bool = False, dynamic_size: bool = False, img_size=None):
     """R1.  model_name: 'dinov2' | 'medsam' (reference names) or any key of ARCHS.
     model_path: a PyTorch state_dict file with the canonical key names; loaded with
     torch.load(weights_only=True).  weights: the same dict passed directly.
@@ -265,11 +282,22 @@ def load_model(model_name: str, model_path=None, weights=None, device=None, micr
     residual stream keeps an fp32 master copy (vdr_config.resid_fp32; bf16 path of the plain ViTs).  ln_fin_fused=True:
     the LayerNorm fold's row statistics are finalised inside the residual GEMMs instead of by a launch of their own (A/B).
     dynamic_size=True (ViT / DINOv2 models): the model runs images of any size whose sides are multiples of the patch
-    side, resampling pos_embed as DINOv2's interpolate_pos_encoding does (VitDescriptorModel.set_input_size)."""
+    side, resampling pos_embed as DINOv2's interpolate_pos_encoding does (VitDescriptorModel.set_input_size).
+    img_size (SAM / MedSAM encoders only; default None = the architecture's own 1024): build the encoder at this square
+    input side, as segment_anything's ImageEncoderViT(img_size=...) -- a multiple of the patch side, at most 64 patches a
+    side -- and load the checkpoint's native tables into it: pos_embed [1, 64, 64, D] and the global blocks' rel_pos_h / w
+    [127, 64] are resampled once on the device (bicubic / get_rel_pos's linear rule).  get_dense_descriptor and
+    generate_features then prepare raw slices at that side."""
     if model_name not in ARCHS:
         raise KeyError(f"unknown model_name {model_name!r}; known: {sorted(ARCHS)} + 'medsam'")
-    cfg = VdrConfig(**{**ARCHS[model_name].__dict__, "micro_batch": micro_batch, "streams": streams,
-                       "fp8": int(fp8) or int(ARCHS[model_name].fp8), "full_last_block": bool(full_last_block),
+    arch = ARCHS[model_name]
+    if img_size is not None:
+        if arch.window <= 0:
+            raise ValueError(f"img_size is for SAM / MedSAM encoders; '{model_name}' changes size with set_input_size / "
+                             "dynamic_size")
+        arch = VdrConfig(**{**arch.__dict__, "img": sam_input_side(img_size, arch.patch)})
+    cfg = VdrConfig(**{**arch.__dict__, "micro_batch": micro_batch, "streams": streams,
+                       "fp8": int(fp8) or int(arch.fp8), "full_last_block": bool(full_last_block),
                        "ln_fold": bool(ln_fold), "fp8_cls_bf16": bool(fp8_cls_bf16), "resid_fp32": bool(resid_fp32),
                        "ln_fin_fused": bool(ln_fin_fused)})
     if weights is None:
@@ -278,7 +306,7 @@ def load_model(model_name: str, model_path=None, weights=None, device=None, micr
         weights = torch.load(model_path, map_location="cpu", weights_only=True)
     if model_name == "medsam" and any(k.startswith("image_encoder.") for k in weights):
         weights = from_sam_state_dict(weights)
-    model = VitDescriptorModel(cfg, weights, model_name, device, dynamic_size=dynamic_size)
+    model = VitDescriptorModel(cfg, weights, model_name, device, dynamic_size=dynamic_size, sized=img_size is not None)
     model.model_name = model_name
     return model
 
@@ -304,7 +332,8 @@ def get_dense_descriptor(model, img) -> np.ndarray:
         if t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[2] != 3):
             raise ValueError(f"get_dense_descriptor: a raw (h, w) / (h, w, 3) slice or a prepared (3, {side}, {side}) image, "
                              f"got {tuple(t.shape)}")
-        t = prep.prepare_image(t, device=model.device)  # [1, 3, 1024 | 896, .] float32 on the device
+        # [1, 3, 1024 | 896, .] float32 on the device; a SAM model loaded with img_size: one resize straight to its side
+        t = prep.prepare_image(t, side=side if getattr(model, "sized", False) else None, device=model.device)
         if t.shape[-1] != side:
             raise ValueError(f"prepare_image gives a {t.shape[-1]}^2 image for a {'gray' if torch.as_tensor(img).dim() == 2 else 'colour'} "
                              f"slice, model '{model.model_name}' takes {side}^2 (the reference pairs gray slices with "

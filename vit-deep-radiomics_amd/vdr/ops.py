@@ -258,8 +258,21 @@ def interpolate_pos(pos: torch.Tensor, native_grid, grid) -> torch.Tensor:
     return out
 
 
+def interpolate_rel_pos(table: torch.Tensor, L_out: int) -> torch.Tensor:
+    """table [L0, D] fp32 on the device -> [L_out, D] fp32: segment_anything's get_rel_pos resampling
+    (vdr_op_interpolate_rel_pos: linear, align_corners=False, fp64 arithmetic, one rounding)."""
+    lib = L.load()
+    assert table.is_cuda and table.dtype == torch.float32 and table.is_contiguous() and table.dim() == 2
+    L0, D = table.shape
+    out = torch.empty((int(L_out), D), dtype=torch.float32, device=table.device)
+    L.check(lib.vdr_op_interpolate_rel_pos(table.data_ptr(), L0, D, out.data_ptr(), int(L_out), _s(table)))
+    return out
+
+
 def attention_relpos(qkv: torch.Tensor, rel_pos_h: torch.Tensor, rel_pos_w: torch.Tensor, batch: int, S: int, heads: int):
-    """SAM attention with decomposed relative position bias over `batch` windows/grids of S x S tokens."""
+    """SAM attention with decomposed relative position bias over `batch` windows/grids of S x S tokens, 1 <= S <= 64."""
+    if not 1 <= int(S) <= 64:
+        raise ValueError(f"attention_relpos: S must be in 1..64, got {S}")
     lib = L.load()
     assert qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.is_contiguous()
     assert qkv.shape == (batch * S * S, 3 * heads * 64)

@@ -3,7 +3,7 @@
 Same names, argument meaning and return contracts as the functions they replace; inputs may be numpy arrays
 (uploaded as they are: a 512x512 slice instead of the 12.6 MB resized tensor) or device tensors.
 
-  prepare_image(img)                    src/tfds_dense_descriptor.py:30-48
+  prepare_image(img[, side])            src/tfds_dense_descriptor.py:30-48
   prepare_slices(volume, ...)           the same for all slices of an (H, W, S[, C]) volume in ONE launch
   apply_window_ct(ct, width, level)     src/tfds_dense_descriptor.py:287-302 (windowing_ct :204-237)
   hu_to_rgb_vectorized(hu)              src/visualization_utils.py:128-186
@@ -58,11 +58,13 @@ def prepare_slices(volume, side=None, flip=None, out_dtype=torch.float32, device
     return out
 
 
-def prepare_image(img, device=None) -> torch.Tensor:
-    """R2 input contract: img (h, w) or (h, w, 3) in [0, 1] -> float32 device tensor [1, 3, 1024|896, .]."""
+def prepare_image(img, side=None, device=None) -> torch.Tensor:
+    """R2 input contract: img (h, w) or (h, w, 3) in [0, 1] -> float32 device tensor [1, 3, side, side]; side defaults
+    to the reference's 1024 (gray) / 896 (colour).  Another side is ONE resize of the raw slice to it (a SAM encoder
+    loaded with img_size), not a resize of the 1024^2 image."""
     t = torch.as_tensor(img)
     v = t.unsqueeze(2)  # one-slice volume: (h, w, 1[, 3])
-    return prepare_slices(v, device=device)
+    return prepare_slices(v, side=side, device=device)
 
 
 def apply_window_ct(ct, width, level, device=None) -> torch.Tensor:

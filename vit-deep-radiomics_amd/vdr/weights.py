@@ -93,3 +93,37 @@ def interpolate_pos_embed(pos_embed, grid, ncls: int = 1, native_grid=None) -> t
     p = torch.nn.functional.interpolate(p, size=(gh, gw), mode="bicubic", align_corners=False)
     p = p.permute(0, 2, 3, 1).reshape(gh * gw, D).to(torch.float32)
     return torch.cat([t[:ncls], p], dim=0).reshape(1, -1, D)
+
+
+def interpolate_rel_pos(table, L: int) -> torch.Tensor:
+    """Host statement of what vdr_finalize does to a SAM global block's rel_pos_h / rel_pos_w loaded at another grid
+    (vdr_op_interpolate_rel_pos; segment_anything's get_rel_pos): table [L0, D] -> fp32 [L, D],
+    F.interpolate(mode="linear", align_corners=False) along the row axis, per channel, evaluated in float64 and rounded
+    to fp32 once.  L == L0 returns the table itself (as fp32).  A table for grid side g has L = 2 g - 1 rows."""
+    t = torch.as_tensor(table).detach().to(torch.float32)
+    if t.dim() != 2:
+        raise ValueError(f"rel-pos table must be [L0, D], got {tuple(t.shape)}")
+    L = int(L)
+    if L <= 0:
+        raise ValueError(f"L must be positive, got {L}")
+    if L == t.shape[0]:
+        return t.clone()
+    r = torch.nn.functional.interpolate(t.double().t().unsqueeze(0), size=L, mode="linear", align_corners=False)
+    return r[0].t().contiguous().to(torch.float32)
+
+
+def sam_tables_at(weights, grid: int, global_blocks) -> dict:
+    """The weights a SAM encoder with a grid x grid token grid computes with, from a checkpoint learned at another size: pos_embed
+    [1, g0, g0, D] and the global blocks' rel-pos tables resampled on the host in float64 (interpolate_pos_embed,
+    interpolate_rel_pos) -- what vdr_set_weight + vdr_finalize build on the device.  For tests."""
+    g = int(grid)
+    out = dict(weights)
+    pe = torch.as_tensor(weights["pos_embed"]).float()
+    g0 = int(pe.shape[1])
+    if g0 != g:
+        out["pos_embed"] = interpolate_pos_embed(pe.reshape(1, g0 * g0, -1), (g, g), 0).reshape(1, g, g, -1)
+    for i in global_blocks:
+        for ax in ("h", "w"):
+            k = f"blocks.{i}.attn.rel_pos_{ax}"
+            out[k] = interpolate_rel_pos(weights[k], 2 * g - 1)
+    return out
