@@ -61,8 +61,12 @@ typedef enum {
 
 typedef enum { VDR_F32 = 0, VDR_BF16 = 1, VDR_F64 = 2, VDR_I16 = 3, VDR_U8 = 4 } vdr_dtype; /* F64 / I16 / U8: pre-processing only */
 
-typedef enum { VDR_ACT_GELU = 0, /* exact erf GELU: models_archs.py:133, timm/DINOv2 Mlp */
-               VDR_ACT_SWIGLU = 1 /* DINOv2 ViT-g SwiGLUFFN (w12 / w3)                   */
+typedef enum { VDR_ACT_GELU = 0,   /* exact erf GELU: models_archs.py:133, timm/DINOv2 Mlp */
+               VDR_ACT_SWIGLU = 1, /* DINOv2 ViT-g SwiGLUFFN (w12 / w3)                   */
+               VDR_ACT_QUICK_GELU = 2, /* x sigmoid(1.702 x): OpenAI CLIP vision towers (PubMedCLIP, QuiltNet, PLIP)    */
+               VDR_ACT_GELU_TANH = 3   /* 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))): SigLIP ("gelu_pytorch_tanh") */
+                                       /* both: weights as VDR_ACT_GELU (mlp.fc1 / mlp.fc2); bf16 path only (fp8 = 1 and  */
+                                       /* window > 0 refuse them)                                                         */
 } vdr_act;
 
 /* What vdr_forward writes. */
@@ -95,7 +99,9 @@ typedef struct {
   int32_t has_cls;    /* 1: a learned cls_token row is prepended                              */
   int32_t has_pos;    /* 1: learned pos_embed [1,N,D] is added                                */
   int32_t input_ln;   /* 1: LayerNorm applied to the assembled tokens before block 0          */
-                      /*    (models_archs.py:145)                                             */
+                      /*    (models_archs.py:145; CLIP's pre_layrnorm on an image model,      */
+                      /*    which keeps the LayerNorm fold: the input LayerNorm leaves block  */
+                      /*    0's row statistics)                                               */
   float ln_eps;       /* 1e-6 timm/DINOv2/SAM, 1e-5 torch default (models_archs.py:136)       */
   int32_t micro_batch;/* images per internal pass (0 = library default: the whole batch, split   */
                       /* evenly over `streams`); results do not depend on it                    */
@@ -319,7 +325,15 @@ typedef enum {
                          /*   return their non-NaN operand; csrc/vdr_dev.h).  Inside a block the residual stream carries   */
                          /*   the NaN row on regardless; the classifier heads hand non-finite rows on themselves.          */
   VDR_EPI_BIAS_RESID = 2,/* y = resid + gamma*(xW^T + b)      out_proj / linear2 + residual     */
-  VDR_EPI_SWIGLU = 3     /* y[:, :N/2] = silu(a)*b, (a,b) = split(xW^T + b)  DINOv2 SwiGLUFFN   */
+  VDR_EPI_SWIGLU = 3,    /* y[:, :N/2] = silu(a)*b, (a,b) = split(xW^T + b)  DINOv2 SwiGLUFFN   */
+  /* (4 .. 7 are internal to the library) */
+  VDR_EPI_BIAS_QUICK_GELU = 8, /* y = a sigmoid(1.702 a), a = xW^T + b            CLIP MLP (QuickGELU)                    */
+  VDR_EPI_BIAS_GELU_TANH = 9   /* y = gelu(a, approximate="tanh")                 SigLIP MLP ("gelu_pytorch_tanh")        */
+                         /*   both as a / (1 + 2^(-t log2 e)), t = 1.702 a or 2 sqrt(2/pi) (a + 0.044715 a^3), in fp32 on */
+                         /*   v_exp_f32 / v_rcp_f32 (csrc/vdr_dev.h): within a few fp32 ulp of the exact function before  */
+                         /*   the one bf16 rounding.  NaN propagates; -inf gives NaN (torch's tanh form: -0).  Accepted by  */
+                         /*   vdr_op_linear, vdr_op_linear_packed and vdr_op_linear_ln_fold wherever VDR_EPI_BIAS_GELU is  */
+                         /*   (every tile variant, the 8-phase kernel included); vdr_op_linear_mx does not carry them      */
 } vdr_epilogue;
 
 /* F.linear(x, W, b) (+ fused epilogue) — nn.Linear inside nn.MultiheadAttention /
@@ -479,6 +493,22 @@ int vdr_op_attention_varlen(const void* qkv, void* out, int batch, int seq, int 
  *   on the launch.  head_dim in {32, 64, 96, 128} (else VDR_ERR_UNSUPPORTED), 1 <= q_rows <= seq. */
 int vdr_op_attention_probs(const void* qkv, void* out, int batch, int seq, int heads, int head_dim, int q_rows,
                            int head_mean, int out_dtype, void* stream);
+
+/* One-query attention pooling -- the attention of SigLIP's pooling head (transformers
+ * SiglipMultiheadAttentionPoolingHead: nn.MultiheadAttention with one learned probe as the only query):
+ *   out[b, h*dh + d] = sum_j softmax_j(q_h . k[b, j, h] dh^-0.5) v[b, j, h, d]  over the n tokens j of image b
+ *   q    device fp32 [heads * head_dim]: the probe after the q projection (and its bias), the same for every image; the
+ *        dh^-0.5 scale is applied here
+ *   kv   device bf16, row b * n + j = token j of image b, ldkv elements apart: columns [0, H dh) k, [H dh, 2 H dh) v (one
+ *        GEMM with the k and v rows of in_proj_weight); 16-byte aligned, ldkv % 8 == 0, ldkv >= 2 * heads * head_dim
+ *   out  device bf16 [batch, heads * head_dim]
+ * fp32 arithmetic: the maximum is subtracted, sum p v and sum p are accumulated unnormalised and divided once, one
+ * rounding to bf16.  Each k / v byte is read once (16-byte loads).  The keys are split over the waves of a workgroup and
+ * combined through LDS in a fixed order: no atomics, a row's bits do not depend on batch.
+ * Refused before the device is touched: head_dim not in {32, 64, 96, 128} (VDR_ERR_UNSUPPORTED); null pointers,
+ * batch <= 0, heads <= 0, n < 1, a bad ldkv or alignment (VDR_ERR_INVALID). */
+int vdr_op_attention_pool(const float* q, const void* kv, int64_t ldkv, void* out, int batch, int n, int heads, int head_dim,
+                          void* stream);
 
 /* SAM / MedSAM Attention.forward with use_rel_pos (third-party segment_anything ImageEncoderViT, called at
  * tfds_dense_descriptor.py:123): per (window, head) softmax(q k^T dh^-0.5 + q.Rh[qh-kh] + q.Rw[qw-kw]) v.

@@ -1,5 +1,5 @@
 // Shared by gemm.hip (bf16) and gemm_mx.hip (MX-fp8): the kernel argument block and the fused epilogues
-// (bias, LayerNorm fold, erf-GELU, SwiGLU, residual + LayerScale, position add, window un-partition,
+// (bias, LayerNorm fold, erf-GELU / QuickGELU / tanh-GELU, SwiGLU, residual + LayerScale, position add, window un-partition,
 // LayerNorm partial sums, MX-fp8 re-quantisation of the output) applied to fp32 MFMA accumulators.
 #pragma once
 #include "vdr_dev.h"
@@ -119,6 +119,14 @@ constexpr int epi_base(int e) {
   return e == EPI_BIAS_GELU_MX ? EPI_BIAS_GELU : e == EPI_SWIGLU_MX ? EPI_SWIGLU : e == EPI_BIAS_RESID32 ? EPI_BIAS_RESID : e;
 }
 constexpr bool epi_mx_out(int e) { return e == EPI_BIAS_GELU_MX || e == EPI_SWIGLU_MX; }
+// the activation of an epi_is_act epilogue on a pair of values (bit for bit the scalar forms of vdr_dev.h)
+template <int E>
+VDR_DEV f32x2 epi_act2(f32x2 v) {
+  static_assert(epi_is_act(E), "an activation epilogue");
+  if constexpr (E == EPI_BIAS_QGELU) return quick_gelu2(v);
+  else if constexpr (E == EPI_BIAS_TGELU) return gelu_tanh2(v);
+  else return gelu_erf2(v);
+}
 template <int EPI>
 VDR_DEV int64_t epi_oct(const GemmK& p, float (&v)[8], float (&u)[8], int64_t m, int n, float& sum1, float& sum2,
                         float mu = 0.0f, float rs = 1.0f, const EpiCols& ec = EpiCols()) {
@@ -186,10 +194,10 @@ VDR_DEV int64_t epi_oct(const GemmK& p, float (&v)[8], float (&u)[8], int64_t m,
       v[4 + e] += b1[e];
     }
   }
-  if (E == EPI_BIAS_GELU) {
+  if constexpr (epi_is_act(E)) {
 #pragma unroll
     for (int e = 0; e < 8; e += 2) {
-      const f32x2 g = gelu_erf2(f32x2{v[e], v[e + 1]});
+      const f32x2 g = epi_act2<E>(f32x2{v[e], v[e + 1]});
       v[e] = g[0];
       v[e + 1] = g[1];
     }
@@ -495,7 +503,7 @@ VDR_DEV EpiPre epilogue_bf16_prefetch(const GemmK& p, int64_t m_base, int n_base
 template <int EPI>
 VDR_DEV void epilogue_bf16(const GemmK& p, const Acc16& acc, char* stg, int64_t m_base, int n_base, int lane,
                            const float2* tile_stats, const EpiPre& here) {
-  static_assert(EPI == EPI_BIAS || EPI == EPI_BIAS_GELU, "write-once outputs only");
+  static_assert(EPI == EPI_BIAS || epi_is_act(EPI), "write-once outputs only");
   const int r15 = lane & 15, q4 = lane >> 4;
   const f32x4 (&bias)[4] = here.bias;
   const f32x4 (&csum)[4] = here.csum;
@@ -521,7 +529,7 @@ VDR_DEV void epilogue_bf16(const GemmK& p, const Acc16& acc, char* stg, int64_t 
         const f32x2 a2 = {acc.t[jt][it][e], acc.t[jt][it][e + 1]};
         const f32x2 c2 = {csum[jt][e], csum[jt][e + 1]}, b2 = {bias[jt][e], bias[jt][e + 1]};
         f32x2 v = __builtin_elementwise_fma(f32x2{rs, rs}, a2, __builtin_elementwise_fma(f32x2{nrm, nrm}, c2, b2));
-        if (EPI == EPI_BIAS_GELU) v = gelu_erf2(v);
+        if constexpr (epi_is_act(EPI)) v = epi_act2<EPI>(v);
         o[e] = (bf16_t)v[0];
         o[e + 1] = (bf16_t)v[1];
       }
@@ -765,7 +773,7 @@ VDR_DEV bool epilogue_resid_ok(const GemmK& p) { return !VDR_ABL(p, 8); }
 template <int EPI>
 VDR_DEV void epilogue_tile(const GemmK& p, const Acc16& acc, char* smem, int wave, int64_t m_base, int n_base, int lane,
                            const float2* tile_stats = nullptr) {
-  if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU) {
+  if constexpr (EPI == EPI_BIAS || epi_is_act(EPI)) {
     if (!p.out_f32 && p.win_ws == 0 && !p.ln_part) {
       epilogue_bf16<EPI>(p, acc, smem + wave * 8192, m_base, n_base, lane, tile_stats,
                          epilogue_bf16_prefetch(p, m_base, n_base, lane));

@@ -602,7 +602,7 @@ VDR_DEV void gemm_ring4_body(const GemmK& p, const int64_t m0, const int n0, cha
     for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(acc.t[j][i]));
 #endif
   VDR_GSTAMP(3);  // main loop done (accumulators complete)
-  if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU) {
+  if constexpr (EPI == EPI_BIAS || epi_is_act(EPI)) {
     if (!p.out_f32 && p.win_ws == 0 && !p.ln_part && !p.ln_cpart) {
       // write-once output through the bf16 epilogue: its constants are requested NOW, into the registers the operand
       // fragments have just left, and used after the barrier (see EpiPre)
@@ -985,6 +985,8 @@ static hipError_t launch_cfg(const GemmArgs& a, int epi, hipStream_t s) {
   switch (epi + (PIPE >= 50 && epi_base(epi) == EPI_BIAS_RESID && a.K > a.N ? 100 : 0)) {
     VDR_LAUNCH(EPI_BIAS)
     VDR_LAUNCH(EPI_BIAS_GELU)
+    VDR_LAUNCH(EPI_BIAS_QGELU)
+    VDR_LAUNCH(EPI_BIAS_TGELU)
     VDR_LAUNCH(EPI_BIAS_RESID)
     VDR_LAUNCH_T(EPI_BIAS_RESID, 1)
     VDR_LAUNCH(EPI_BIAS_RESID32)

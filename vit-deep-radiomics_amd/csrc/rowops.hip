@@ -711,6 +711,72 @@ hipError_t launch_cls_rows_stats(const float* cls, const float* pos, void* x, fl
   return hipGetLastError();
 }
 
+// LayerNorm in place over bf16 rows that also leaves the (sum, sumsq) partials of its OUTPUT rows, one slot per (64-column
+// group, row): the input LayerNorm of a model that keeps the LayerNorm fold (CLIP's pre_layrnorm, vdr_config.input_ln).
+// Block 0's folded qkv GEMM reads part [D/64][part_stride][2] exactly as the patch epilogue and cls_rows_stats_kernel
+// leave it for a model without input LayerNorm.  One wave per row, the LayerNorm kernel's helpers (same bits as
+// launch_layernorm on the same row); lane l holds columns 256 k + 4 l .. + 3 of pass k, so a 64-column group is 16
+// neighbouring lanes of one pass: four xor-shuffle adds inside the 16-lane row, lane 0 of the row stores.  The sums are
+// of the bf16 values stored (what the consumer multiplies).  No atomics; a row's bits do not depend on the batch.
+template <int NP>
+__global__ __launch_bounds__(256) void ln_rows_stats_kernel(bf16_t* __restrict__ x, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, float eps, int64_t rows, int D,
+                                                            float* __restrict__ part, int64_t part_stride) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  float v[NP][4];
+  row_load<true, NP>(x, r, D, lane, v);
+  float mean, rstd;
+  row_mean_rstd<NP>(v, D, lane, eps, mean, rstd);
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
+    const int c = k * 256 + lane * 4;
+    float s1 = 0.0f, s2 = 0.0f;
+    if (c < D) {
+      const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + c);
+      const f32x4 bt = *reinterpret_cast<const f32x4*>(beta + c);
+      bf16x4 ob;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        ob[e] = (bf16_t)ln_affine(v[k][e], mean, rstd, g[e], bt[e]);
+        const float q = (float)ob[e];
+        s1 += q;
+        s2 = fmaf(q, q, s2);
+      }
+      *reinterpret_cast<bf16x4*>(x + r * D + c) = ob;
+    }
+    // (every lane takes part in the exchange; D % 64 == 0, so a 16-lane row is inside D or outside it as a whole)
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) {
+      s1 += __shfl_xor(s1, o, 64);
+      s2 += __shfl_xor(s2, o, 64);
+    }
+    if ((lane & 15) == 0 && c < D) {
+      float* dst = part + ((int64_t)(c >> 6) * part_stride + r) * 2;
+      dst[0] = s1;
+      dst[1] = s2;
+    }
+  }
+}
+
+hipError_t launch_ln_rows_stats(void* x, const float* gamma, const float* beta, float eps, int64_t rows, int D, float* part,
+                                int64_t part_stride, hipStream_t s) {
+  if (rows <= 0 || D <= 0 || (D & 63) || D > 2048 || part_stride < rows) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+#define VDR_LNS(NP)                                                                                                          \
+  case NP:                                                                                                                   \
+    hipLaunchKernelGGL((ln_rows_stats_kernel<NP>), grid, block, 0, s, (bf16_t*)x, gamma, beta, eps, rows, D, part, part_stride); \
+    break;
+  switch ((D + 255) / 256) {
+    VDR_LNS(1) VDR_LNS(2) VDR_LNS(3) VDR_LNS(4) VDR_LNS(5) VDR_LNS(6) VDR_LNS(7) VDR_LNS(8)
+    default:
+      return hipErrorInvalidValue;
+  }
+#undef VDR_LNS
+  return hipGetLastError();
+}
+
 // 3x3 / pad 1 im2col over NHWC tokens (the SAM neck's second conv): one thread moves 8 channels (16 B)
 __global__ __launch_bounds__(256) void im2col3_kernel(const bf16_t* __restrict__ y, bf16_t* __restrict__ col,
                                                       int64_t total, int g, int C) {

@@ -253,10 +253,18 @@ int env_int(const char* name, int dflt) {
 #endif
 }
 
+// (input_ln on an image model -- CLIP's pre_layrnorm -- keeps the fold: the input LayerNorm leaves block 0's row
+// statistics itself, launch_ln_rows_stats)
 bool ln_fusion_wanted(const vdr_model* m) {
   const vdr_config& c = m->cfg;
   if (c.no_ln_fold || env_int("VDR_LN_FUSE", 1) == 0) return false;
-  return c.patch && c.pre_ln && !c.input_ln && !c.fp8 && (c.dim % 64) == 0;
+  return c.patch && c.pre_ln && !c.fp8 && (c.dim % 64) == 0;
+}
+
+// the fc1 epilogue of the model's MLP activation
+int fc1_epilogue(const vdr_config& c) {
+  return c.act == VDR_ACT_SWIGLU ? EPI_SWIGLU : c.act == VDR_ACT_QUICK_GELU ? EPI_BIAS_QGELU : c.act == VDR_ACT_GELU_TANH ? EPI_BIAS_TGELU
+                                                                                                                            : EPI_BIAS_GELU;
 }
 
 // SwiGLU gate pairs: packed row pr of mlp.w12 is source row swiglu_source_row(pr, F) (blocks of 32 x1 rows, then the 32 matching x2 rows:
@@ -944,7 +952,7 @@ int cls_mlp_bf16(vdr_model* m, hipStream_t ax, const Carve& w, const LayerW& L, 
   BookAs book(m);
   const vdr_config& c = m->cfg;
   const int D = c.dim, F = c.mlp_hidden;
-  const int e1 = c.act == VDR_ACT_SWIGLU ? EPI_SWIGLU : EPI_BIAS_GELU;
+  const int e1 = fc1_epilogue(c);
   int rc;
   if ((rc = layernorm(m, ax, VDR_K_LAYERNORM, w.x, 1, w.cls_h, 1, L.n2w, L.n2b, mb, RowMap{1, ntok, 0}))) return rc;
   GemmArgs fc1 = linear(w.cls_h, L.w1, w.cls_u, mb, e1 == EPI_SWIGLU ? 2 * F : F, D, e1);
@@ -962,7 +970,7 @@ int block_tail_cls(vdr_model* m, hipStream_t s, const Carve& w, const LayerW& L,
   BookAs book(m);
   const vdr_config& c = m->cfg;
   const int D = c.dim, F = c.mlp_hidden;
-  const int e1 = c.act == VDR_ACT_SWIGLU ? EPI_SWIGLU : EPI_BIAS_GELU, N1 = e1 == EPI_SWIGLU ? 2 * F : F;
+  const int e1 = fc1_epilogue(c), N1 = e1 == EPI_SWIGLU ? 2 * F : F;
   char* xc = w.h;  // [mb, D] bf16
   // the out-projection gathers the CLS rows: A and the residual read with a row stride of ntok * D
   GemmArgs proj = linear(w.o, L.wproj, xc, mb, D, D, EPI_BIAS_RESID);
@@ -1091,7 +1099,7 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
   const vdr_config& c = m->cfg;
   const int D = c.dim, F = c.mlp_hidden, H = c.heads;
   const int64_t M = (int64_t)mb * ntok;
-  const int e1 = c.act == VDR_ACT_SWIGLU ? EPI_SWIGLU : EPI_BIAS_GELU, N1 = e1 == EPI_SWIGLU ? 2 * F : F;
+  const int e1 = fc1_epilogue(c), N1 = e1 == EPI_SWIGLU ? 2 * F : F;
   int rc;
   if (compact) *compact = false;
   // (post-LN blocks keep every row: their last operation is a LayerNorm over the block's own output, also row-wise, but
@@ -1422,7 +1430,7 @@ int embed_patches(vdr_model* m, hipStream_t s, const Carve& w, const char* img, 
   } else {
     g.pos = m->pos;
     g.omap = RowMap{n, ntok, ncls};
-    if (m->ln_fuse) {
+    if (m->ln_fuse && !c.input_ln) {  // (input_ln: the input LayerNorm leaves the statistics, those of the raw rows are not wanted)
       g.ln_part = w.part;
       g.part_stride = w.Mp;
     }
@@ -1440,12 +1448,17 @@ int assemble_stream(vdr_model* m, hipStream_t s, const Carve& w, int mb, int nto
   int rc;
   if (c.has_cls) {
     Scope sc(m, s, VDR_K_ASSEMBLE, 0.0, (double)mb * D * 2);
-    if (m->ln_fuse)
+    if (m->ln_fuse && !c.input_ln)
       VDR_TRY(launch_cls_rows_stats(m->cls, m->pos, w.x, w.part, w.Mp, mb, ntok, D, s), "cls rows");
     else
       VDR_TRY(launch_cls_rows(m->cls, m->pos, w.x, mb, ntok, D, s), "cls rows");
   }
-  if (c.input_ln) {
+  if (c.input_ln && m->ln_fuse) {
+    // in place, and the (sum, sumsq) partials of the normalised rows -- block 0's folded qkv GEMM reads them where the
+    // patch epilogue and the CLS rows leave those of the raw rows in a model without input_ln (here they leave none)
+    Scope sc(m, s, VDR_K_LAYERNORM, 0.0, (double)mb * ntok * D * 4);
+    VDR_TRY(launch_ln_rows_stats(w.x, m->inw, m->inb, c.ln_eps, (int64_t)mb * ntok, D, w.part, w.Mp, s), "input layernorm");
+  } else if (c.input_ln) {
     if ((rc = layernorm(m, s, VDR_K_LAYERNORM, w.x, 1, w.x, 1, m->inw, m->inb, (int64_t)mb * ntok, identity_map())))
       return rc;
   }
@@ -1548,7 +1561,9 @@ int vdr_create(const vdr_config* cfg, int device, vdr_handle* out) {
   } else if (c.has_pos) {
     return fail(nullptr, VDR_ERR_UNSUPPORTED, "token models carry no learned pos_embed");
   }
-  if (c.act != VDR_ACT_GELU && c.act != VDR_ACT_SWIGLU) return fail(nullptr, VDR_ERR_INVALID, "unknown activation");
+  if (c.act < VDR_ACT_GELU || c.act > VDR_ACT_GELU_TANH) return fail(nullptr, VDR_ERR_INVALID, "unknown activation");
+  if (c.fp8 == 1 && (c.act == VDR_ACT_QUICK_GELU || c.act == VDR_ACT_GELU_TANH))
+    return fail(nullptr, VDR_ERR_UNSUPPORTED, "fp8 = 1: the MX-fp8 GEMM carries erf-GELU and SwiGLU only (QuickGELU / tanh-GELU: bf16 path)");
   if (c.fp8 && !c.pre_ln) return fail(nullptr, VDR_ERR_UNSUPPORTED, "fp8 weights: pre-LN models only");
   if (c.fp8_cls_bf16 < 0 || c.fp8_cls_bf16 > 1) return fail(nullptr, VDR_ERR_INVALID, "fp8_cls_bf16 must be 0 or 1");
   if (c.resid_fp32 < 0 || c.resid_fp32 > 1) return fail(nullptr, VDR_ERR_INVALID, "resid_fp32 must be 0 or 1");
@@ -2023,7 +2038,10 @@ int vdr_op_layernorm(const void* x, int in_dtype, void* y, int out_dtype, const 
 static int op_linear_impl(const void* x, const void* W, int packed, const float* bias, const void* resid, const float* gamma,
                           void* y, int64_t M, int N, int K, int epilogue, int variant, void* stream) {
   if (!x || !W || !y) return fail(nullptr, VDR_ERR_INVALID, "null argument");
-  if (epilogue < VDR_EPI_BIAS || epilogue > VDR_EPI_SWIGLU) return fail(nullptr, VDR_ERR_INVALID, "epilogue");
+  // (the public activation values are the internal ones: vdr_kernels.h)
+  static_assert((int)VDR_EPI_BIAS_QUICK_GELU == (int)EPI_BIAS_QGELU && (int)VDR_EPI_BIAS_GELU_TANH == (int)EPI_BIAS_TGELU, "vdr_epilogue");
+  if ((epilogue < VDR_EPI_BIAS || epilogue > VDR_EPI_SWIGLU) && epilogue != VDR_EPI_BIAS_QUICK_GELU && epilogue != VDR_EPI_BIAS_GELU_TANH)
+    return fail(nullptr, VDR_ERR_INVALID, "epilogue");
   if (epilogue == VDR_EPI_BIAS_RESID && !resid) return fail(nullptr, VDR_ERR_INVALID, "resid required");
   if (K % 64 || N % 8) return fail(nullptr, VDR_ERR_UNSUPPORTED, "K % 64 == 0 and N % 8 == 0 required");
 #ifndef VDR_TUNING
@@ -2117,8 +2135,8 @@ int vdr_op_linear_ln_fold(const void* x, const void* Wf, const float* colsum, co
                           int epilogue, int variant, void* stream) {
   if (!x || !Wf || !colsum || !tbias || !y) return fail(nullptr, VDR_ERR_INVALID, "null argument");
   if ((stats != nullptr) == (part != nullptr)) return fail(nullptr, VDR_ERR_INVALID, "exactly one of stats and part");
-  if (epilogue != VDR_EPI_BIAS && epilogue != VDR_EPI_BIAS_GELU && epilogue != VDR_EPI_SWIGLU)
-    return fail(nullptr, VDR_ERR_INVALID, "epilogue: bias, GELU or SwiGLU");
+  if (epilogue != VDR_EPI_BIAS && !epi_is_act(epilogue) && epilogue != VDR_EPI_SWIGLU)
+    return fail(nullptr, VDR_ERR_INVALID, "epilogue: bias, GELU / QuickGELU / tanh-GELU or SwiGLU");
   if (!ln_variant_ok(variant, true)) return fail(nullptr, VDR_ERR_INVALID, "variant: 22..29 or 31");
   if (M <= 0 || N <= 0 || K <= 0 || (N % 64) || (K % 64) || (x_rows && x_rows < M))
     return fail(nullptr, VDR_ERR_INVALID, "M > 0, N % 64 == 0, K % 64 == 0, x_rows 0 or >= M required");
@@ -2311,6 +2329,23 @@ int vdr_op_attention_probs(const void* qkv, void* out, int batch, int seq, int h
   if (rc) return rc;
   OP_TRY(launch_attention_probs(qkv, out, batch, seq, heads, head_dim, q_rows, head_mean, out_dtype == VDR_BF16, (hipStream_t)stream),
          "attention_probs");
+  return VDR_OK;
+}
+
+int vdr_op_attention_pool(const float* q, const void* kv, int64_t ldkv, void* out, int batch, int n, int heads, int head_dim,
+                          void* stream) {
+  if (head_dim != 32 && head_dim != 64 && head_dim != 96 && head_dim != 128)
+    return fail(nullptr, VDR_ERR_UNSUPPORTED, "head dim must be 32, 64, 96 or 128");
+  if (!q || !kv || !out) return fail(nullptr, VDR_ERR_INVALID, "null argument");
+  if (batch <= 0 || heads <= 0) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_attention_pool: batch and heads must be positive");
+  if (n < 1) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_attention_pool: n must be at least 1");
+  if ((int64_t)batch * heads > 0x7fffffff) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_attention_pool: more than 2^31 (image, head) pairs");
+  if (ldkv < (int64_t)2 * heads * head_dim || (ldkv & 7))
+    return fail(nullptr, VDR_ERR_INVALID, "vdr_op_attention_pool: ldkv must be a multiple of 8 and at least 2 * heads * head_dim");
+  if ((uintptr_t)kv & 15) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_attention_pool: kv must be 16-byte aligned");
+  int rc = check_device(nullptr);
+  if (rc) return rc;
+  OP_TRY(launch_attention_pool(q, kv, ldkv, out, batch, n, heads, head_dim, (hipStream_t)stream), "attention_pool");
   return VDR_OK;
 }
 

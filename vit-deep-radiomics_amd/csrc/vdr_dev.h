@@ -112,6 +112,34 @@ VDR_DEV f32x2 gelu_erf2(f32x2 x) {
   return __builtin_elementwise_fma(-a, e, relu);
 }
 
+// The sigmoid-gated activations of the language-supervised towers, both  x sigmoid(t) = x / (1 + 2^(-t log2 e)):
+//   QuickGELU (OpenAI CLIP):         t = 1.702 x
+//   tanh-GELU (SigLIP, "gelu_pytorch_tanh"):  0.5 x (1 + tanh(u)) = x sigmoid(2 u),  t = 2 sqrt(2/pi) (x + 0.044715 x^3)
+// x_sigmoid takes the exponent e2 = -t log2 e ready made.  v_exp_f32 and v_rcp_f32 are good to 1 ulp, the rest is four
+// (QuickGELU: two) correctly rounded fp32 operations: a few 2^-24 relative against the half ulp of 2^-9 of the bf16
+// rounding that follows in every epilogue.  Branch-free; the ends need no clamp: t -> +inf gives 2^-inf = 0, rcp(1) = 1,
+// so x; t -> -inf gives rcp(inf) = 0, so -0 -- also when x^3 overflows (x^2 = inf, e2 = -+inf) -- for every finite x.
+// Cost per value: QuickGELU 3 VALU + v_exp + v_rcp, tanh-GELU 5 VALU + v_exp + v_rcp (erf form: 10 + v_exp).
+// NaN: propagates (NaN in, NaN out), unlike gelu_erf.  -inf gives NaN (-inf * 0), as torch's x * sigmoid(1.702 x) does;
+// torch's tanh form returns -0 there.  +inf gives +inf.
+constexpr float QGELU_E2 = -1.702f * 1.44269504088896341f;                    // -1.702 log2 e
+constexpr float TGELU_E2A = -2.0f * 0.7978845608028654f * 1.44269504088896341f;  // -2 sqrt(2/pi) log2 e
+constexpr float TGELU_E2B = TGELU_E2A * 0.044715f;
+VDR_DEV float x_sigmoid(float x, float e2) { return x * fast_rcp(1.0f + fast_exp2(e2)); }
+VDR_DEV float quick_gelu(float x) { return x_sigmoid(x, x * QGELU_E2); }
+VDR_DEV float gelu_tanh(float x) { return x_sigmoid(x, x * fmaf(x * x, TGELU_E2B, TGELU_E2A)); }
+// The same on pairs, bit for bit (every step is the IEEE operation of the scalar form; the transcendentals are per
+// value): QuickGELU 3 packed (v_pk_mul, v_pk_add, v_pk_mul) + 2 v_exp + 2 v_rcp slots per pair, tanh-GELU 5 packed
+// (v_pk_mul, v_pk_fma, v_pk_mul, v_pk_add, v_pk_mul) + 2 + 2, against erf-GELU's 2 min + 2 max + 7 packed + 2 v_exp.
+VDR_DEV f32x2 x_sigmoid2(f32x2 x, f32x2 e2) {
+  const f32x2 d = f32x2{fast_exp2(e2[0]), fast_exp2(e2[1])} + f32x2{1.0f, 1.0f};
+  return x * f32x2{fast_rcp(d[0]), fast_rcp(d[1])};
+}
+VDR_DEV f32x2 quick_gelu2(f32x2 x) { return x_sigmoid2(x, x * f32x2{QGELU_E2, QGELU_E2}); }
+VDR_DEV f32x2 gelu_tanh2(f32x2 x) {
+  return x_sigmoid2(x, x * __builtin_elementwise_fma(x * x, f32x2{TGELU_E2B, TGELU_E2B}, f32x2{TGELU_E2A, TGELU_E2A}));
+}
+
 // One 16-key slice of a softmax row held in the S^T accumulator layout: P = 2^(s * sc + nmb) for the 8 scores of this
 // lane, their sum added to `lsum2`, P rounded to bf16 as the B operand of O^T += V^T . P^T.  Written on PAIRS of
 // neighbouring accumulator registers so that the scale-and-shift and the row sum are one packed instruction per pair

@@ -47,7 +47,12 @@ enum Epilogue { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_BIAS_RESID = 2, EPI_SWIGLU 
                 // internal to gemm_mx.hip: GELU / SwiGLU with the output re-quantised to MX-fp8
                 EPI_BIAS_GELU_MX = 5, EPI_SWIGLU_MX = 6,
                 // internal to launch_cfg: EPI_BIAS_RESID with the residual stream kept in fp32 (GemmArgs::resid32 / C32)
-                EPI_BIAS_RESID32 = 7 };
+                EPI_BIAS_RESID32 = 7,
+                // EPI_BIAS_GELU with another activation (vdr_dev.h): QuickGELU (CLIP) and tanh-GELU (SigLIP).  The public
+                // vdr_epilogue values are these numbers
+                EPI_BIAS_QGELU = 8, EPI_BIAS_TGELU = 9 };
+// the epilogues "bias, then an elementwise activation, bf16 out": they share every kernel path of EPI_BIAS_GELU
+constexpr bool epi_is_act(int e) { return e == EPI_BIAS_GELU || e == EPI_BIAS_QGELU || e == EPI_BIAS_TGELU; }
 
 struct GemmArgs {
   const void* A;      // [M, K] bf16, row stride lda
@@ -108,7 +113,7 @@ struct GemmArgs {
 
 hipError_t launch_gemm(const GemmArgs& a, int epilogue, int variant, hipStream_t s);
 // whether tile variant 31 (gemm_8p.hip: the 256 x 256 x 64 8-phase kernel, one workgroup per CU) takes this launch: EPI_BIAS /
-// EPI_BIAS_GELU with a plain bf16 output, plain weight layout, N % 256 == 0, K % 128 == 0, M % 256 == 0 or a_rows covering the
+// an activation epilogue (EPI_BIAS_GELU / _QGELU / _TGELU) with a plain bf16 output, plain weight layout, N % 256 == 0, K % 128 == 0, M % 256 == 0 or a_rows covering the
 // last 256-row tile, at least 2 tiles per CU with the last round of workgroups at least 85 % full
 bool gemm_8p_eligible(const GemmArgs& a, int epilogue);
 bool gemm_8p_shape_ok(int64_t M, int N);  // its tile-count rule alone
@@ -151,6 +156,12 @@ hipError_t launch_attention_hd(const void* qkv, void* out, int batch, int seq, i
 // fp32 or bf16 (out_bf16).  head_dim 32 / 64 / 96 / 128, 1 <= q_rows <= seq
 hipError_t launch_attention_probs(const void* qkv, void* out, int batch, int seq, int heads, int head_dim, int q_rows,
                                   int head_mean, int out_bf16, hipStream_t s);
+
+// one-query attention pooling (attention_pool.hip): out[b, h*dh + d] = sum_j softmax_j(q_h . k[b, j, h] dh^-1/2) v[b, j, h, d];
+// q fp32 [heads * head_dim] (one probe for the whole batch), kv bf16 rows b * n + j of ldkv elements, [k | v] columns,
+// out bf16 [batch, heads * head_dim].  head_dim 32 / 64 / 96 / 128, n >= 1, ldkv % 8 == 0, kv 16-byte aligned
+hipError_t launch_attention_pool(const float* q, const void* kv, int64_t ldkv, void* out, int batch, int n, int heads,
+                                 int head_dim, hipStream_t s);
 
 // SAM / MedSAM decomposed relative position bias (attention_relpos.hip)
 //   qkv rows are S*S-token windows (or whole grids) back to back
@@ -225,6 +236,11 @@ hipError_t launch_ln_finalize(const float* part, int groups, int64_t stride, flo
 // x[b*row_stride][:] = cls + pos[0] as launch_cls_rows, plus that row's partial sums
 hipError_t launch_cls_rows_stats(const float* cls, const float* pos, void* x, float* part, int64_t part_stride,
                                  int batch, int64_t row_stride, int D, hipStream_t s);
+
+// x[r] = LN(x[r]) in place over bf16 rows [rows, D], plus the (sum, sumsq) partials of the normalised bf16 rows in the
+// fold's layout part [D/64][part_stride][2] (vdr_config.input_ln with the LayerNorm fold on); D % 64 == 0
+hipError_t launch_ln_rows_stats(void* x, const float* gamma, const float* beta, float eps, int64_t rows, int D, float* part,
+                                int64_t part_stride, hipStream_t s);
 
 // y[r] = x[imap(r)], bf16 -> bf16 / fp32
 hipError_t launch_gather_rows(const void* x, void* y, int out_bf16, int64_t rows, int D, RowMap imap,

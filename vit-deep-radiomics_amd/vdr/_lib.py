@@ -9,9 +9,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvdr.so")
 
 VDR_F32, VDR_BF16, VDR_F64, VDR_I16, VDR_U8 = 0, 1, 2, 3, 4
-ACT_GELU, ACT_SWIGLU = 0, 1
+ACT_GELU, ACT_SWIGLU, ACT_QUICK_GELU, ACT_GELU_TANH = 0, 1, 2, 3
 OUT_CLS, OUT_DENSE, OUT_PATCH_EMBED, OUT_TOKENS, OUT_ENCODER, OUT_POOLED = 0, 1, 2, 3, 4, 5
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_SWIGLU = 0, 1, 2, 3
+EPI_BIAS_QUICK_GELU, EPI_BIAS_GELU_TANH = 8, 9  # (4 .. 7 are internal to the library)
 K_COUNT = 11
 
 
@@ -89,6 +90,7 @@ SYMBOLS = {
     "vdr_op_attention_hd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "vdr_op_attention_varlen": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
     "vdr_op_attention_probs": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "vdr_op_attention_pool": (_I, [_P, _P, _L, _P, _I, _I, _I, _I, _P]),
     "vdr_op_attention_relpos": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "vdr_op_interpolate_pos": (_I, [_P, _I, _I, _I, _P, _I, _I, _P]),
     "vdr_op_interpolate_rel_pos": (_I, [_P, _I, _I, _P, _I, _P]),

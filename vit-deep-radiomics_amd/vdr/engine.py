@@ -21,7 +21,7 @@ class VdrConfig:
     heads: int = 12
     layers: int = 12
     mlp_hidden: int = 3072
-    act: str = "gelu"
+    act: str = "gelu"          # "gelu" (erf) | "swiglu" | "quick_gelu" (CLIP) | "gelu_tanh" (SigLIP)
     pre_ln: bool = True
     layerscale: bool = False
     has_cls: bool = True
@@ -53,7 +53,7 @@ class VdrConfig:
         c = L.vdr_config()
         c.img, c.patch, c.in_chans, c.dim, c.heads, c.layers = self.img, self.patch, self.in_chans, self.dim, self.heads, self.layers
         c.mlp_hidden = self.mlp_hidden
-        c.act = L.ACT_SWIGLU if self.act == "swiglu" else L.ACT_GELU
+        c.act = {"swiglu": L.ACT_SWIGLU, "quick_gelu": L.ACT_QUICK_GELU, "gelu_tanh": L.ACT_GELU_TANH}.get(self.act, L.ACT_GELU)
         c.pre_ln, c.layerscale, c.has_cls, c.has_pos = int(self.pre_ln), int(self.layerscale), int(self.has_cls), int(self.has_pos)
         c.input_ln, c.ln_eps, c.micro_batch = int(self.input_ln), float(self.ln_eps), int(self.micro_batch)
         c.streams = int(self.streams)

@@ -37,6 +37,14 @@ ARCHS = {
     # reference default backbone: sam_model_registry['vit_b'] image encoder (MedSAM checkpoint), 1024x1024
     "medsam": VdrConfig(1024, 16, 3, 768, 12, 12, 3072, has_cls=False, window=14, global_blocks=(2, 5, 8, 11),
                         neck_chans=256),
+    # vision towers of language-supervised models (transformers CLIPVisionModel[WithProjection] / SiglipVisionModel).
+    # OpenAI CLIP and its medical descendants (PubMedCLIP, QuiltNet, PLIP): QuickGELU, pre_layrnorm (input_ln), eps 1e-5
+    "clip_vit_base16_224": VdrConfig(224, 16, 3, 768, 12, 12, 3072, act="quick_gelu", input_ln=True, ln_eps=1e-5),
+    "clip_vit_base32_224": VdrConfig(224, 32, 3, 768, 12, 12, 3072, act="quick_gelu", input_ln=True, ln_eps=1e-5),
+    "clip_vit_large14_336": VdrConfig(336, 14, 3, 1024, 16, 24, 4096, act="quick_gelu", input_ln=True, ln_eps=1e-5),
+    # SigLIP (siglip-base / large-patch16): tanh-GELU, no CLS token, attention-pooling head, eps 1e-6
+    "siglip_base16_224": VdrConfig(224, 16, 3, 768, 12, 12, 3072, act="gelu_tanh", has_cls=False),
+    "siglip_large16_256": VdrConfig(256, 16, 3, 1024, 16, 24, 4096, act="gelu_tanh", has_cls=False),
 }
 
 
@@ -105,8 +113,16 @@ class VitDescriptorModel:
         self.dynamic_size = bool(dynamic_size)
         self.sized = bool(sized)
         self.engine = Engine(cfg, device)
+        # (head.* entries -- a translated CLIP projection / SigLIP pooling head -- are not weights of the encoder)
+        from .weights import split_head_weights
+        weights, head = split_head_weights(weights)
         self.engine.load_weights(weights)
         self.device = self.engine.device
+        self.head = None
+        if "head.visual_projection.weight" in head:
+            self.head = _ClipProjection(head, self.device)
+        elif "head.probe" in head:
+            self.head = _SiglipPoolHead(head, cfg, self.device)
 
     # -- input size ------------------------------------------------------------------------------
     def set_input_size(self, height: int, width: int):
@@ -265,8 +281,84 @@ class VitDescriptorModel:
             res.append(t)
         return res[0] if single else tuple(res)
 
+    def get_image_features(self, x: torch.Tensor, normalize: bool = False) -> torch.Tensor:
+        """The image embedding of a CLIP / SigLIP vision tower, [B, E] fp32 (transformers get_image_features):
+        CLIP: visual_projection(post_layernorm(x[:, 0])) -- CLIPVisionModelWithProjection's image_embeds;
+        SigLIP: the attention-pooling head over the final-LayerNorm tokens -- SiglipVisionModel's pooler_output.
+        normalize=True divides every row by its L2 norm (what the contrastive logits use).  x holds raw [0, 1] values:
+        no mean / std normalisation is applied anywhere in this library (include/vdr.h) -- apply the checkpoint's
+        image_mean / image_std upstream, as transformers' image processor does."""
+        if self.head is None:
+            raise ValueError("get_image_features: the model was loaded without a CLIP visual_projection / SigLIP pooling head")
+        self._adopt(x)
+        f = self.head(self, x)
+        return torch.nn.functional.normalize(f, dim=-1) if normalize else f
+
     def __call__(self, x):
-        return self.image_encoder(x) if self.cfg.window > 0 else self.forward_features(x)
+        if self.cfg.window > 0:
+            return self.image_encoder(x)
+        if isinstance(self.head, _SiglipPoolHead):  # (no CLS token: the pooled feature is SiglipVisionModel's pooler_output)
+            return self.get_image_features(x)
+        return self.forward_features(x)
+
+
+def _pad_rows8(w: torch.Tensor) -> torch.Tensor:
+    """rows zero-padded to a multiple of 8 (the GEMM's N rule), as _MlpHead pads dense2"""
+    n = w.shape[0]
+    out = torch.zeros(((n + 7) // 8 * 8,) + tuple(w.shape[1:]), dtype=w.dtype)
+    out[:n] = w
+    return out
+
+
+class _ClipProjection:
+    """CLIPVisionModelWithProjection's visual_projection (nn.Linear, no bias) on the post-LayerNorm CLS rows, through
+    vdr_op_linear."""
+
+    def __init__(self, head, dev):
+        w = head["head.visual_projection.weight"].float().cpu()
+        self.n = w.shape[0]
+        self.w = _pad_rows8(w).to(dev, torch.bfloat16).contiguous()
+
+    def __call__(self, model, x):
+        from . import ops
+        cls = model.engine.forward(x, L.OUT_CLS, torch.bfloat16)
+        return ops.linear(cls, self.w, None, epilogue=L.EPI_BIAS)[:, : self.n].float()
+
+
+class _SiglipPoolHead:
+    """transformers SiglipMultiheadAttentionPoolingHead in eval mode: one learned probe attends over every token
+    (nn.MultiheadAttention, batch_first), then x + mlp(layernorm(x)) with the tanh-GELU MLP.  The probe's q projection does
+    not depend on the image: computed once here in fp32.  Per call: one k/v GEMM over the final-LayerNorm tokens,
+    vdr_op_attention_pool, the out-projection, LayerNorm, fc1 with the tanh-GELU epilogue, fc2 with the residual epilogue."""
+
+    def __init__(self, head, cfg, dev):
+        W, b = head["head.attention.in_proj_weight"].float().cpu(), head["head.attention.in_proj_bias"].float().cpu()
+        D = W.shape[1]
+        if D != cfg.dim:
+            raise ValueError(f"SigLIP head: in_proj_weight is for width {D}, the model has {cfg.dim}")
+        self.D, self.heads, self.head_dim, self.eps = D, cfg.heads, D // cfg.heads, cfg.ln_eps
+        self.q = (head["head.probe"].float().cpu().reshape(1, D) @ W[:D].t() + b[:D]).reshape(D).to(dev).contiguous()
+        bf = lambda k: head[k].to(dev, torch.bfloat16).contiguous()   # noqa: E731
+        f32 = lambda k: head[k].to(dev, torch.float32).contiguous()  # noqa: E731
+        self.wkv, self.bkv = W[D:].to(dev, torch.bfloat16).contiguous(), b[D:].to(dev).contiguous()
+        self.wo, self.bo = bf("head.attention.out_proj.weight"), f32("head.attention.out_proj.bias")
+        self.lnw, self.lnb = f32("head.layernorm.weight"), f32("head.layernorm.bias")
+        self.w1, self.b1 = bf("head.mlp.fc1.weight"), f32("head.mlp.fc1.bias")
+        self.w2, self.b2 = bf("head.mlp.fc2.weight"), f32("head.mlp.fc2.bias")
+
+    def pooled(self, tokens: torch.Tensor) -> torch.Tensor:
+        """tokens [B, n, D] bf16 (final LayerNorm applied) -> [B, D] fp32"""
+        from . import ops
+        B, n, D = tokens.shape
+        kv = ops.linear(tokens.reshape(B * n, D), self.wkv, self.bkv)                       # [B n, 2D]: k | v
+        o = ops.attention_pool(self.q, kv, B, n, self.heads, self.head_dim)                 # [B, D]
+        a = ops.linear(o, self.wo, self.bo)
+        h = ops.layernorm(a, self.lnw, self.lnb, self.eps)
+        u = ops.linear(h, self.w1, self.b1, epilogue=L.EPI_BIAS_GELU_TANH)
+        return ops.linear(u, self.w2, self.b2, resid=a, epilogue=L.EPI_BIAS_RESID).float()
+
+    def __call__(self, model, x):
+        return self.pooled(model.engine.forward(x, L.OUT_TOKENS, torch.bfloat16))
 
 
 def load_model(model_name: str, model_path=None, weights=None, device=None, micro_batch: int = 0, streams: int = 0,
@@ -274,7 +366,10 @@ def load_model(model_name: str, model_path=None, weights=None, device=None, micr
                resid_fp32: bool = False, ln_fin_fused: bool = False, dynamic_size: bool = False, img_size=None):
     """R1.  model_name: 'dinov2' | 'medsam' (reference names) or any key of ARCHS.
     model_path: a PyTorch state_dict file with the canonical key names; loaded with
-    torch.load(weights_only=True).  weights: the same dict passed directly.
+    torch.load(weights_only=True).  weights: the same dict passed directly.  A transformers CLIPVisionModel
+    [WithProjection] / SiglipVisionModel state_dict (the clip_* / siglip_* entries of ARCHS) is translated on the way in
+    (vdr.weights.from_clip_vision_state_dict / from_siglip_vision_state_dict); its projection / pooling head serves
+    model.get_image_features(x).  Images are raw [0, 1] here as for every model: no mean / std normalisation is applied.
     fp8=True keeps the qkv / fc1 / fc2 weights as MX-fp8 and runs them on the block-scaled fp8 MFMA
     (BASELINE config 5; pre-LN models).  full_last_block=True: `model(x)` computes every token of the last block
     like the reference does before it keeps x[:, 0] (default: the CLS rows only, same bits).  fp8_cls_bf16=True (fp8 models
@@ -306,6 +401,11 @@ def load_model(model_name: str, model_path=None, weights=None, device=None, micr
         weights = torch.load(model_path, map_location="cpu", weights_only=True)
     if model_name == "medsam" and any(k.startswith("image_encoder.") for k in weights):
         weights = from_sam_state_dict(weights)
+    # transformers CLIPVisionModel[WithProjection] / SiglipVisionModel keys (with or without the vision_model. prefix)
+    if any(k.endswith("embeddings.patch_embedding.weight") for k in weights):
+        from .weights import from_clip_vision_state_dict, from_siglip_vision_state_dict
+        clip = any(k.endswith("embeddings.class_embedding") for k in weights)
+        weights = from_clip_vision_state_dict(weights) if clip else from_siglip_vision_state_dict(weights)
     model = VitDescriptorModel(cfg, weights, model_name, device, dynamic_size=dynamic_size, sized=img_size is not None)
     model.model_name = model_name
     return model

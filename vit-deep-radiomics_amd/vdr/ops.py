@@ -205,6 +205,21 @@ def attention(qkv: torch.Tensor, batch: int, seq: int, heads: int, variant=0, he
     return out
 
 
+def attention_pool(q: torch.Tensor, kv: torch.Tensor, batch: int, n: int, heads: int, head_dim: int = 64) -> torch.Tensor:
+    """One-query attention pooling (vdr_op_attention_pool; SigLIP's pooling head): q fp32 [heads * head_dim], the
+    projected probe shared by the batch; kv bf16 [batch * n, >= 2 * heads * head_dim], columns [k | v], rows may be
+    strided (a column slice of a wider matrix).  Returns bf16 [batch, heads * head_dim]:
+    out[b, h] = softmax_j(q_h . k[b, j, h] / sqrt(head_dim)) v[b, j, h].  head_dim in {32, 64, 96, 128}, n >= 1."""
+    lib = L.load()
+    D = heads * head_dim
+    assert q.is_cuda and q.dtype == torch.float32 and q.is_contiguous() and q.numel() == D
+    assert kv.is_cuda and kv.dtype == torch.bfloat16 and kv.dim() == 2 and kv.stride(1) == 1
+    assert kv.shape[0] == batch * n and kv.shape[1] >= 2 * D
+    out = torch.empty((batch, D), dtype=torch.bfloat16, device=kv.device)
+    L.check(lib.vdr_op_attention_pool(q.data_ptr(), kv.data_ptr(), kv.stride(0), out.data_ptr(), batch, n, heads, head_dim, _s(kv)))
+    return out
+
+
 def attention_probs(qkv: torch.Tensor, batch: int, seq: int, heads: int, head_dim=64, q_rows=None, head_mean=False,
                     out_dtype=torch.float32):
     """The attention map of the same packed qkv: softmax(q k^T / sqrt(head_dim)) of the first q_rows query rows (None:

@@ -24,6 +24,65 @@ def from_torch_encoder_state_dict(sd, layers: int):
     return {k: torch.as_tensor(v).detach().to(torch.float32).contiguous() for k, v in out.items()}
 
 
+def _hf_vision_tower(sd, what):
+    """The shared part of the transformers CLIP / SigLIP vision-tower key translation: sd with or without the
+    `vision_model.` prefix -> (canonical tower weights, the stripped dict).  q_proj / k_proj / v_proj are concatenated in
+    that order into attn.qkv (rows [q | k | v], the layout of timm's fused qkv), position_embedding.weight [N, D] becomes
+    pos_embed [1, N, D], post_layernorm the final norm."""
+    sd = {(k[len("vision_model."):] if k.startswith("vision_model.") else k): torch.as_tensor(v).detach().to(torch.float32)
+          for k, v in sd.items() if torch.is_floating_point(torch.as_tensor(v))}
+    if "embeddings.patch_embedding.weight" not in sd:
+        raise KeyError(f"{what}: no embeddings.patch_embedding.weight -- not a transformers vision-tower state_dict")
+    out = {"patch_embed.proj.weight": sd["embeddings.patch_embedding.weight"]}
+    D = out["patch_embed.proj.weight"].shape[0]
+    out["patch_embed.proj.bias"] = sd.get("embeddings.patch_embedding.bias", torch.zeros(D))  # (CLIP's conv has no bias)
+    pos = sd["embeddings.position_embedding.weight"]
+    out["pos_embed"] = pos.reshape(1, pos.shape[0], D)
+    i = 0
+    while f"encoder.layers.{i}.self_attn.q_proj.weight" in sd:
+        s, d = f"encoder.layers.{i}.", f"blocks.{i}."
+        for t in ("weight", "bias"):
+            out[d + "attn.qkv." + t] = torch.cat([sd[s + f"self_attn.{p}_proj.{t}"] for p in ("q", "k", "v")], dim=0)
+            out[d + "attn.proj." + t] = sd[s + "self_attn.out_proj." + t]
+            out[d + "norm1." + t] = sd[s + "layer_norm1." + t]
+            out[d + "norm2." + t] = sd[s + "layer_norm2." + t]
+            out[d + "mlp.fc1." + t] = sd[s + "mlp.fc1." + t]
+            out[d + "mlp.fc2." + t] = sd[s + "mlp.fc2." + t]
+        i += 1
+    for t in ("weight", "bias"):
+        out["norm." + t] = sd["post_layernorm." + t]
+    return out, sd
+
+
+def from_clip_vision_state_dict(sd):
+    """transformers CLIPVisionModel / CLIPVisionModelWithProjection state_dict (OpenAI CLIP and its descendants:
+    PubMedCLIP, QuiltNet, PLIP) -> the canonical names vdr_set_weight understands: class_embedding [D] -> cls_token
+    [1, 1, D], pre_layrnorm -> input_norm, the bias-free patch conv gets a zero bias.  visual_projection.weight [E, D]
+    (when the checkpoint has it) is returned as head.visual_projection.weight: it is not a weight of the encoder."""
+    out, sd = _hf_vision_tower(sd, "from_clip_vision_state_dict")
+    out["cls_token"] = sd["embeddings.class_embedding"].reshape(1, 1, -1)
+    for t in ("weight", "bias"):
+        out["input_norm." + t] = sd["pre_layrnorm." + t]
+    if "visual_projection.weight" in sd:
+        out["head.visual_projection.weight"] = sd["visual_projection.weight"]
+    return {k: v.contiguous() for k, v in out.items()}
+
+
+def from_siglip_vision_state_dict(sd):
+    """transformers SiglipVisionModel state_dict -> the canonical names (no CLS token, no input norm).  The attention-
+    pooling head (head.probe, head.attention.in_proj_weight / in_proj_bias / out_proj.*, head.layernorm.*, head.mlp.fc1 /
+    fc2.*) keeps its names under head.*: it is not a weight of the encoder."""
+    out, sd = _hf_vision_tower(sd, "from_siglip_vision_state_dict")
+    out.update({k: v for k, v in sd.items() if k.startswith("head.")})
+    return {k: v.contiguous() for k, v in out.items()}
+
+
+def split_head_weights(weights):
+    """(encoder weights, head weights): the head.* entries of a translated CLIP / SigLIP state_dict apart from the rest."""
+    enc = {k: v for k, v in weights.items() if not k.startswith("head.")}
+    return enc, {k: v for k, v in weights.items() if k.startswith("head.")}
+
+
 def expected_weight_shapes(cfg) -> "dict[str, tuple]":
     """Names and PyTorch shapes a config expects (same list vdr_weight_name enumerates)."""
     D, Fh = cfg.dim, cfg.mlp_hidden
@@ -50,7 +109,7 @@ def expected_weight_shapes(cfg) -> "dict[str, tuple]":
             s[p + "ls1.gamma"] = (D,)
         s[p + "norm2.weight"] = (D,)
         s[p + "norm2.bias"] = (D,)
-        if cfg.act == "swiglu":
+        if cfg.act == "swiglu":  # ("gelu", "quick_gelu", "gelu_tanh": fc1 / fc2)
             s[p + "mlp.w12.weight"] = (2 * Fh, D)
             s[p + "mlp.w12.bias"] = (2 * Fh,)
             s[p + "mlp.w3.weight"] = (D, Fh)
