@@ -72,12 +72,14 @@ typedef enum { VDR_ACT_GELU = 0,   /* exact erf GELU: models_archs.py:133, timm/
 /* What vdr_forward writes. */
 typedef enum {
   VDR_OUT_CLS = 0,         /* [B, D]      final-LN(x)[:,0,:]     (models_archs.py:147 contract)     */
-  VDR_OUT_DENSE = 1,       /* [B, n, D]   final-LN(x)[:,1:,:]    (tfds_dense_descriptor.py:130-133) */
+  VDR_OUT_DENSE = 1,       /* [B, n, D]   final-LN(x)[:,P:,:]    (tfds_dense_descriptor.py:130-133); P = has_cls +   */
+                           /*             n_register prefix rows: register tokens are discarded with the CLS row   */
   VDR_OUT_PATCH_EMBED = 2, /* [B, n, D]   conv patchify only     (tfds_dense_descriptor.py:128)     */
-  VDR_OUT_TOKENS = 3,      /* [B, N, D]   every token after the last block + final LN (if any)      */
+  VDR_OUT_TOKENS = 3,      /* [B, N, D]   every token after the last block + final LN (if any): N = P + n, rows     */
+                           /*             [cls | registers | patches] (transformers last_hidden_state)             */
   VDR_OUT_ENCODER = 4,     /* [B, g, g, C] SAM neck output, channel-LAST (tfds_dense_descriptor.py:123-126   */
                            /*             transposes the reference's [B, C, g, g] to (h, w, C) anyway)     */
-  VDR_OUT_POOLED = 5       /* [B, D]      mean over the patch rows (rows ncls..N-1) of the normalised (or raw)  */
+  VDR_OUT_POOLED = 5       /* [B, D]      mean over the patch rows (rows P..N-1) of the normalised (or raw)     */
                            /*             stream: vdr_forward_layers only (vdr_forward refuses it)             */
 } vdr_out_mode;
 
@@ -157,6 +159,40 @@ typedef struct {
                       /* (The counters live in the handle, like its internal streams: one forward at a time per handle.)      */
 } vdr_config;
 
+/* Geometry that came after vdr_config was frozen (ABI 8 pins its 100 bytes): register tokens and DINOv3's rotary position
+ * embedding.  Passed beside vdr_config to vdr_create_ext; vdr_create is vdr_create_ext with ext = NULL (no registers, no
+ * RoPE).
+ *
+ * Register tokens (DINOv2-with-registers `dinov2_vit*14_reg`, DINOv3): n_register learned rows "register_tokens"
+ * [1, R, D] sit between the CLS row and the patch rows, so an image is N = P + n token rows with P = has_cls + n_register
+ * prefix rows: [cls | registers | patches].  pos_embed stays [1, has_cls + n, D]: the CLS row gets its position, the
+ * registers get none, the patch rows theirs (DINOv2-with-registers adds pos_embed before it inserts the registers).
+ * Every output mode: VDR_OUT_CLS is row 0; VDR_OUT_TOKENS all N rows; VDR_OUT_DENSE, VDR_OUT_POOLED and the DENSE /
+ * POOLED outputs of vdr_forward_layers take rows P.. only (x_norm_patchtokens; the registers are discarded); attention
+ * maps keep all N key columns and q_rows = 1 is still the CLS row; the CLS-rows-only last block is unchanged.
+ * vdr_set_input_size resamples the patch rows as for any ViT (vdr_op_interpolate_pos).  Stated deviation: upstream's
+ * registers variants resample with antialias = True (another cubic kernel); antialiasing is not reproduced here, so at
+ * sizes other than the native one the position table differs from upstream's.
+ *
+ * rope = 1 (DINOv3, transformers DINOv3ViTModel): no position table (has_pos = 0); in every block, between the qkv GEMM
+ * and the attention, q and k of the PATCH rows are rotated per head by vdr_op_rope2d with the tables of
+ * vdr_op_rope2d_table for the patch grid in force (rebuilt by vdr_finalize / vdr_set_input_size: the model matches
+ * transformers at every size).  Prefix rows and v are not rotated.  Attention maps are computed from the rotated buffer.
+ * The launches are booked as VDR_K_ASSEMBLE.  q and k are rounded to bf16 twice (after the GEMM, after the rotation);
+ * rotating inside the qkv epilogue would remove one rounding and the pass (the partner column lives in another lane's
+ * registers there) -- not done.
+ *
+ * Refused before the device is touched.  VDR_ERR_UNSUPPORTED: n_register > 0 or rope = 1 together with fp8 = 1, window > 0,
+ * patch == 0 or pre_ln = 0; rope = 1 with has_pos = 1; rope = 1 with head dim 96 (the frequency step 4 / 96 is inexact in
+ * fp32 and no checkpoint uses it); n_register > 16.  VDR_ERR_INVALID: n_register > 0 without has_cls; n_register < 0; rope
+ * not 0 / 1; rope = 1 with a non-finite or <= 1 rope_theta; ext->size smaller than the fields below. */
+typedef struct {
+  int32_t size;        /* sizeof(vdr_config_ext) of the caller: later fields are appended after the ones known today */
+  int32_t n_register;  /* 0..16 register tokens between the CLS row and the patch rows (needs has_cls = 1)       */
+  int32_t rope;        /* 0 none | 1 DINOv3 axial 2-D RoPE on q and k of the PATCH rows of every block            */
+  float   rope_theta;  /* DINOv3: 100                                                                             */
+} vdr_config_ext;
+
 typedef struct vdr_model* vdr_handle;
 
 /* ---- lifecycle ------------------------------------------------------------------------ */
@@ -175,6 +211,8 @@ int vdr_device_count(void);
  * (tfds_dense_descriptor.py:70-107) and TransformerNoduleClassifier.__init__
  * (models_archs.py:128-139).  Binds the handle to HIP device `device`. */
 int vdr_create(const vdr_config* cfg, int device, vdr_handle* out);
+/* The same with the extension struct above (NULL: exactly vdr_create). */
+int vdr_create_ext(const vdr_config* cfg, const vdr_config_ext* ext, int device, vdr_handle* out);
 void vdr_destroy(vdr_handle h);
 const char* vdr_last_error(vdr_handle h);
 
@@ -206,7 +244,7 @@ int vdr_finalize(vdr_handle h);
  * done once per size instead of in every forward.  Load-time class (like vdr_finalize: may allocate and synchronise;
  * not for the hot path).  After it every image entry point of the handle -- vdr_forward, vdr_forward_layers,
  * vdr_forward_attn_maps, vdr_workspace_bytes -- takes images [batch, in_chans, height, width]; n = (height / patch) *
- * (width / patch) patches in (y, x) order, N = n + has_cls tokens.
+ * (width / patch) patches in (y, x) order, N = n + has_cls + n_register tokens.
  *   has_pos = 1: a device table [N, D] fp32 is built -- the CLS row (when there is one) copied unchanged, the patch rows
  *   resampled from the loaded pos_embed's (img / patch)^2 grid by vdr_op_interpolate_pos -- and the forward reads it
  *   wherever it reads pos_embed.  has_pos = 0: geometry only.  height == width == img selects the loaded table itself:
@@ -216,7 +254,8 @@ int vdr_finalize(vdr_handle h);
  *   (vdr_workspace_bytes); one sized for a smaller geometry is refused with VDR_ERR_WORKSPACE.
  * Supported: pre-LN image models without windows (plain ViT, DINOv2; every vdr_config switch) and layers == 0
  * patch-embedding models.  bf16 images with p in {8, 16, 32} keep the im2col-free gather at square sizes; rectangular
- * sizes go through im2col.  Not reproduced: DINOv2's older scale_factor + interpolate_offset form and antialiasing.
+ * sizes go through im2col.  Not reproduced: DINOv2's older scale_factor + interpolate_offset form and antialiasing
+ * (DINOv2-with-registers resamples with antialias = True upstream: vdr_config_ext).  rope = 1: the RoPE tables are rebuilt.
  * VDR_ERR_INVALID, before the handle or a device is touched: height <= 0, width <= 0; then a null handle; then a side
  * that is not a multiple of patch.  VDR_ERR_UNSUPPORTED: SAM / MedSAM (window > 0: its absolute and relative position
  * tables and the window partition are tied to its grid; its size is vdr_config.img, chosen at vdr_create), token models (patch == 0), post-LN models with blocks.
@@ -538,6 +577,27 @@ int vdr_op_interpolate_pos(const float* pos, int gh0, int gw0, int D, float* out
  * A SAM table for grid side g has L = 2 g - 1 rows.  At most 2^30 elements either side. */
 int vdr_op_interpolate_rel_pos(const float* table, int L0, int D, float* out, int L, void* stream);
 
+/* DINOv3's axial 2-D rotary position embedding (transformers DINOv3ViTRopePositionEmbedding): the cos / sin tables of a
+ * gh x gw patch grid, device fp32 [gh*gw, head_dim/2] each -- the unique half; the upper half of a head repeats it.
+ * inv_freq[i] = theta^(-4 i / head_dim), i < head_dim/4.  Patch (y, x): cy = 2 (y + 0.5) / gh - 1, cx = 2 (x + 0.5) / gw - 1;
+ * angle[j] = 2 pi cy inv_freq[j] for j < head_dim/4, 2 pi cx inv_freq[j - head_dim/4] above.  Angle, cos and sin are evaluated
+ * in fp64 and rounded to fp32 once (transformers' fp32 table differs by <= 7e-7).  Load-time class.  head_dim in
+ * {32, 64, 128} (else VDR_ERR_UNSUPPORTED); theta finite and > 1, at most 2^20 grid cells (VDR_ERR_INVALID). */
+int vdr_op_rope2d_table(int gh, int gw, int head_dim, float theta, float* cos_out, float* sin_out, void* stream);
+
+/* apply_rotary_pos_emb on the patch rows of a packed qkv activation, in place: qkv [batch*seq, 3*H*dh] bf16, columns
+ * [q | k | v] each [H, dh].  Only rows b*seq + prefix + j (j < seq - prefix) are touched, with table row j, and in them only
+ * the q and k columns; prefix rows and v are neither read nor written.  Per head and j2 < dh/2, with lo = t[j2],
+ * hi = t[j2 + dh/2] (bf16, widened exactly), c = cos[j][j2], s = sin[j][j2], every operation one fp32 rounding, in this
+ * order (no fused multiply-add):
+ *   p1 = lo * c,  p2 = hi * s,  lo' = p1 - p2;    p3 = hi * c,  p4 = lo * s,  hi' = p3 + p4
+ * lo' and hi' are rounded to bf16 once (nearest even) and stored over lo and hi (the rotate_half convention).  One lane:
+ * 8 lo dims and their 8 partners, for q and for k (16-byte accesses); no LDS, no atomics: a row's result does not depend
+ * on batch.  cos / sin: device fp32 [seq - prefix, dh/2] (vdr_op_rope2d_table, or any caller table).  qkv, cos, sin 16-byte
+ * aligned.  head_dim in {32, 64, 128} (else VDR_ERR_UNSUPPORTED). */
+int vdr_op_rope2d(void* qkv, int batch, int seq, int prefix, int heads, int head_dim, const float* cos, const float* sin,
+                  void* stream);
+
 /* nn.Conv2d(in_chans, D, kernel=p, stride=p) + flatten(2).transpose(1,2) — DINOv2 PatchEmbed,
  * the op called at tfds_dense_descriptor.py:128.
  *   images NCHW [batch, C, img, img] in_dtype; W bf16 [D, Kp] (C*p*p columns zero-padded to
@@ -561,7 +621,7 @@ typedef enum {
   VDR_K_GEMM_FC1 = 6,
   VDR_K_GEMM_FC2 = 7,
   VDR_K_FINAL_LN = 8,
-  VDR_K_ASSEMBLE = 9,
+  VDR_K_ASSEMBLE = 9,  /* CLS / register rows, fp32 stream copy, token assembly; the 2-D RoPE launches (vdr_config_ext.rope) */
   VDR_K_CLS_TAIL = 10, /* out-projection, norm2 and MLP of the last block on the CLS rows only (vdr_config.full_last_block) */
   VDR_K_COUNT = 11
 } vdr_kernel_class;

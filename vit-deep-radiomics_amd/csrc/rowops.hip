@@ -519,21 +519,26 @@ hipError_t launch_im2col(const void* images, int in_bf16, void* col, int batch, 
   return hipGetLastError();
 }
 
-// x[b*row_stride][:] = cls + pos[0]
-__global__ __launch_bounds__(256) void cls_rows_kernel(const float* __restrict__ cls, const float* __restrict__ pos,
-                                                       bf16_t* __restrict__ x, int batch, int64_t row_stride, int D) {
+// prefix rows of an image: x[b*row_stride][:] = cls + pos[0]; x[b*row_stride + 1 + r][:] = reg[r] (register tokens, r < P - 1:
+// no position is added to them); one rounding to bf16
+__global__ __launch_bounds__(256) void prefix_rows_kernel(const float* __restrict__ cls, const float* __restrict__ pos,
+                                                          const float* __restrict__ reg, int P, bf16_t* __restrict__ x,
+                                                          int batch, int64_t row_stride, int D) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (int64_t)batch * D) return;
-  const int64_t b = idx / D;
-  const int d = (int)(idx - b * D);
-  const float v = cls[d] + (pos ? pos[d] : 0.0f);
-  x[b * row_stride * D + d] = (bf16_t)v;
+  if (idx >= (int64_t)batch * P * D) return;
+  const int64_t br = idx / D;
+  const int d = (int)(idx - br * D);
+  const int64_t b = br / P;
+  const int p = (int)(br - b * P);
+  const float v = p == 0 ? cls[d] + (pos ? pos[d] : 0.0f) : reg[(int64_t)(p - 1) * D + d];
+  x[(b * row_stride + p) * D + d] = (bf16_t)v;
 }
 
-hipError_t launch_cls_rows(const float* cls, const float* pos, void* x, int batch, int64_t row_stride, int D,
-                           hipStream_t s) {
-  const int64_t total = (int64_t)batch * D;
-  hipLaunchKernelGGL(cls_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, cls, pos,
+hipError_t launch_prefix_rows(const float* cls, const float* pos, const float* reg, int n_reg, void* x, int batch,
+                              int64_t row_stride, int D, hipStream_t s) {
+  if (n_reg < 0 || (n_reg > 0 && !reg) || row_stride < 1 + n_reg) return hipErrorInvalidValue;
+  const int64_t total = (int64_t)batch * (1 + n_reg) * D;
+  hipLaunchKernelGGL(prefix_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, cls, pos, reg, 1 + n_reg,
                      (bf16_t*)x, batch, row_stride, D);
   return hipGetLastError();
 }
@@ -684,14 +689,16 @@ hipError_t launch_ln_finalize(const float* part, int groups, int64_t stride, flo
   return hipGetLastError();
 }
 
-// x[b*row_stride][:] = cls + pos[0], one wave per (image, 64-column group), plus that group's partial sums
-__global__ __launch_bounds__(64) void cls_rows_stats_kernel(const float* __restrict__ cls, const float* __restrict__ pos,
-                                                            bf16_t* __restrict__ x, float* __restrict__ part,
-                                                            int64_t part_stride, int groups, int64_t row_stride, int D) {
-  const int b = blockIdx.x / groups, g = blockIdx.x - b * groups;
+// the prefix rows as prefix_rows_kernel, one wave per (image, prefix row, 64-column group), plus that group's partial sums
+__global__ __launch_bounds__(64) void prefix_rows_stats_kernel(const float* __restrict__ cls, const float* __restrict__ pos,
+                                                               const float* __restrict__ reg, int P, bf16_t* __restrict__ x,
+                                                               float* __restrict__ part, int64_t part_stride, int groups,
+                                                               int64_t row_stride, int D) {
+  const int bp = blockIdx.x / groups, g = blockIdx.x - bp * groups;
+  const int b = bp / P, p = bp - b * P;
   const int d = g * 64 + threadIdx.x;
-  const int64_t row = (int64_t)b * row_stride;
-  const bf16_t o = (bf16_t)(cls[d] + (pos ? pos[d] : 0.0f));
+  const int64_t row = (int64_t)b * row_stride + p;
+  const bf16_t o = (bf16_t)(p == 0 ? cls[d] + (pos ? pos[d] : 0.0f) : reg[(int64_t)(p - 1) * D + d]);
   x[row * D + d] = o;
   const float r = (float)o;
   const float s1 = wave_sum(r), s2 = wave_sum(r * r);
@@ -702,18 +709,18 @@ __global__ __launch_bounds__(64) void cls_rows_stats_kernel(const float* __restr
   }
 }
 
-hipError_t launch_cls_rows_stats(const float* cls, const float* pos, void* x, float* part, int64_t part_stride,
-                                 int batch, int64_t row_stride, int D, hipStream_t s) {
-  if (D & 63) return hipErrorInvalidValue;
+hipError_t launch_prefix_rows_stats(const float* cls, const float* pos, const float* reg, int n_reg, void* x, float* part,
+                                    int64_t part_stride, int batch, int64_t row_stride, int D, hipStream_t s) {
+  if ((D & 63) || n_reg < 0 || (n_reg > 0 && !reg) || row_stride < 1 + n_reg) return hipErrorInvalidValue;
   const int groups = D / 64;
-  hipLaunchKernelGGL(cls_rows_stats_kernel, dim3((unsigned)(batch * groups)), dim3(64), 0, s, cls, pos, (bf16_t*)x, part,
-                     part_stride, groups, row_stride, D);
+  hipLaunchKernelGGL(prefix_rows_stats_kernel, dim3((unsigned)(batch * (1 + n_reg) * groups)), dim3(64), 0, s, cls, pos, reg,
+                     1 + n_reg, (bf16_t*)x, part, part_stride, groups, row_stride, D);
   return hipGetLastError();
 }
 
 // LayerNorm in place over bf16 rows that also leaves the (sum, sumsq) partials of its OUTPUT rows, one slot per (64-column
 // group, row): the input LayerNorm of a model that keeps the LayerNorm fold (CLIP's pre_layrnorm, vdr_config.input_ln).
-// Block 0's folded qkv GEMM reads part [D/64][part_stride][2] exactly as the patch epilogue and cls_rows_stats_kernel
+// Block 0's folded qkv GEMM reads part [D/64][part_stride][2] exactly as the patch epilogue and prefix_rows_stats_kernel
 // leave it for a model without input LayerNorm.  One wave per row, the LayerNorm kernel's helpers (same bits as
 // launch_layernorm on the same row); lane l holds columns 256 k + 4 l .. + 3 of pass k, so a 64-column group is 16
 // neighbouring lanes of one pass: four xor-shuffle adds inside the 16-lane row, lane 0 of the row stores.  The sums are

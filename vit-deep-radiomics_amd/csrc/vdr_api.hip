@@ -95,6 +95,14 @@ struct vdr_model {
   const float* pos0 = nullptr;
   float* pos_sized = nullptr;
   size_t pos_sized_rows = 0;  // rows pos_sized was allocated for
+  // vdr_config_ext: register tokens between the CLS row and the patch rows (pos_sized then holds the per-token-row table
+  // [CLS position ; n_reg zero rows ; patch positions] at every size, the native one included) and DINOv3's 2-D RoPE
+  // (cos / sin [n_patches][head_dim / 2] of the size in force, rebuilt with the position table)
+  int n_reg = 0, rope = 0;
+  float rope_theta = 100.0f;
+  const float* reg = nullptr;
+  float *rope_cos = nullptr, *rope_sin = nullptr;
+  size_t rope_rows = 0;  // patch rows the RoPE tables were allocated for
   std::vector<WSlot> slots;
   std::map<std::string, int> index;
   std::vector<LayerW> layers;
@@ -142,6 +150,9 @@ namespace {
 
 int hip_fail(vdr_handle h, hipError_t e, const char* what);
 
+// rows in front of the patch rows of an image: the CLS token, then the register tokens
+int prefix_rows(const vdr_model* m) { return (m->cfg.has_cls ? 1 : 0) + m->n_reg; }
+
 int fail(vdr_handle h, int code, const std::string& msg) {
   if (h) h->err = msg;
   g_err = msg;
@@ -171,7 +182,9 @@ void build_slots(vdr_model* m) {
     add_slot(m, "patch_embed.proj.bias", W_VEC_F32, 1, D);
   }
   if (c.has_cls) add_slot(m, "cls_token", W_VEC_F32, 1, D);
-  if (c.has_pos) add_slot(m, "pos_embed", W_VEC_F32, m->n_tokens, D);
+  if (m->n_reg) add_slot(m, "register_tokens", W_VEC_F32, m->n_reg, D);
+  // (register tokens carry no position: the table is [cls | patches] whatever their number)
+  if (c.has_pos) add_slot(m, "pos_embed", W_VEC_F32, m->n_patches + (c.has_cls ? 1 : 0), D);
   if (c.has_pos && c.window > 0) m->slots.back().resample = RS_POS;
   if (c.input_ln) {
     add_slot(m, "input_norm.weight", W_VEC_F32, 1, D);
@@ -310,13 +323,40 @@ int fold_ln(vdr_model* m, const std::vector<float>& W, const std::vector<float>&
   return VDR_OK;
 }
 
-// The position table of the input size in force (load-time class: may allocate and synchronise).  The native size reads
-// the loaded table itself; any other size gets [CLS row unchanged ; patch rows resampled from the (img / patch)^2 grid].
+// DINOv3's RoPE tables for the patch grid of the input size in force (load-time class)
+int build_rope_table(vdr_model* m) {
+  const vdr_config& c = m->cfg;
+  const int half = c.dim / c.heads / 2;
+  VDR_TRY(hipSetDevice(m->device), "hipSetDevice");
+  VDR_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");  // (a forward still in flight may read the old tables)
+  if (m->rope_rows < (size_t)m->n_patches) {
+    if (m->rope_cos) VDR_TRY(hipFree(m->rope_cos), "hipFree(RoPE table)");
+    if (m->rope_sin) VDR_TRY(hipFree(m->rope_sin), "hipFree(RoPE table)");
+    m->rope_cos = m->rope_sin = nullptr;
+    m->rope_rows = 0;
+    VDR_TRY(hipMalloc((void**)&m->rope_cos, (size_t)m->n_patches * half * 4 + 256), "hipMalloc(RoPE table)");
+    VDR_TRY(hipMalloc((void**)&m->rope_sin, (size_t)m->n_patches * half * 4 + 256), "hipMalloc(RoPE table)");
+    m->rope_rows = (size_t)m->n_patches;
+  }
+  VDR_TRY(launch_rope2d_table(m->in_h / c.patch, m->in_w / c.patch, 2 * half, m->rope_theta, m->rope_cos, m->rope_sin, nullptr),
+          "rope2d_table");
+  VDR_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
+  return VDR_OK;
+}
+
+// The position tables of the input size in force (load-time class: may allocate and synchronise).  Without register
+// tokens the native size reads the loaded pos_embed itself; any other size gets [CLS row unchanged ; patch rows resampled
+// from the (img / patch)^2 grid].  With register tokens the forward always reads a built table laid out per token row --
+// [CLS row ; n_reg zero rows ; patch rows] -- whose patch rows are the loaded ones at the native size (copied: the same
+// bits however the handle got there) and the resampled ones elsewhere.  RoPE models (no pos_embed) get their cos / sin tables.
 int build_pos_table(vdr_model* m) {
   const vdr_config& c = m->cfg;
   m->pos = m->pos0;
-  if (!c.has_pos || !c.patch || (m->in_h == c.img && m->in_w == c.img)) return VDR_OK;
-  const int ncls = c.has_cls ? 1 : 0, D = c.dim, g0 = c.img / c.patch;
+  if (m->rope && c.patch)
+    if (int rc = build_rope_table(m)) return rc;
+  const bool native = m->in_h == c.img && m->in_w == c.img;
+  if (!c.has_pos || !c.patch || (native && !m->n_reg)) return VDR_OK;
+  const int ncls = c.has_cls ? 1 : 0, P = prefix_rows(m), D = c.dim, g0 = c.img / c.patch;
   VDR_TRY(hipSetDevice(m->device), "hipSetDevice");
   VDR_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");  // (a forward still in flight, on any stream, may read the old table)
   if (m->pos_sized_rows < (size_t)m->n_tokens) {
@@ -327,9 +367,14 @@ int build_pos_table(vdr_model* m) {
     m->pos_sized_rows = (size_t)m->n_tokens;
   }
   if (ncls) VDR_TRY(hipMemcpy(m->pos_sized, m->pos0, (size_t)D * 4, hipMemcpyDeviceToDevice), "hipMemcpy(pos_embed CLS row)");
-  VDR_TRY(launch_pos_interp(m->pos0 + (size_t)ncls * D, g0, g0, D, m->pos_sized + (size_t)ncls * D, m->in_h / c.patch,
-                            m->in_w / c.patch, nullptr),
-          "pos_interp");
+  if (m->n_reg) VDR_TRY(hipMemset(m->pos_sized + (size_t)ncls * D, 0, (size_t)m->n_reg * D * 4), "hipMemset(register rows)");
+  if (native)
+    VDR_TRY(hipMemcpy(m->pos_sized + (size_t)P * D, m->pos0 + (size_t)ncls * D, (size_t)m->n_patches * D * 4, hipMemcpyDeviceToDevice),
+            "hipMemcpy(pos_embed patch rows)");
+  else
+    VDR_TRY(launch_pos_interp(m->pos0 + (size_t)ncls * D, g0, g0, D, m->pos_sized + (size_t)P * D, m->in_h / c.patch,
+                              m->in_w / c.patch, nullptr),
+            "pos_interp");
   VDR_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
   m->pos = m->pos_sized;
   return VDR_OK;
@@ -362,6 +407,7 @@ int resolve(vdr_model* m) {
   m->w_patch = dev_of(m, "patch_embed.proj.weight");
   m->b_patch = (const float*)dev_of(m, "patch_embed.proj.bias");
   m->cls = (const float*)dev_of(m, "cls_token");
+  m->reg = (const float*)dev_of(m, "register_tokens");
   m->pos0 = (const float*)dev_of(m, "pos_embed");
   {
     const int rc = build_pos_table(m);  // (weights changed: the table of the size in force is rebuilt)
@@ -1055,7 +1101,9 @@ int write_attn_map(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok
 // its CLS rows only (block_tail_cls) and they sit in w.h / w.xc32.  Every launch is booked as VDR_K_FINAL_LN.
 int write_output(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, const vdr_layer_out& o, int b0, bool compact) {
   const vdr_config& c = m->cfg;
-  const int D = c.dim, ncls = c.has_cls ? 1 : 0, n = ntok - ncls;
+  // (ncls: the rows in front of the patch rows -- the CLS row and, on an image model, the register tokens, which DENSE
+  // and POOLED discard with it)
+  const int D = c.dim, ncls = c.patch ? prefix_rows(m) : (c.has_cls ? 1 : 0), n = ntok - ncls;
   const int ob = o.out_dtype == VDR_BF16;
   const size_t es = ob ? 2 : 4;
   const bool f32 = compact ? w.xc32 != nullptr : w.x32 != nullptr;
@@ -1114,6 +1162,14 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
     return (int)VDR_OK;
   };
   auto attention = [&]() {
+    if (m->rope) {
+      // DINOv3: q and k of the patch rows rotated in place between the qkv GEMM and everything that reads them (the
+      // attention and, from the same buffer, the attention maps); booked with the token assembly
+      const int P = prefix_rows(m);
+      const double el = (double)mb * (ntok - P) * 2 * D;  // q and k elements
+      Scope sc(m, s, VDR_K_ASSEMBLE, 3.0 * el, 4.0 * el);
+      VDR_TRY(launch_rope2d(w.qkv, mb, ntok, P, H, D / H, m->rope_cos, m->rope_sin, s), "rope2d");
+    }
     Scope sc(m, s, VDR_K_ATTENTION, 4.0 * (double)ntok * ntok * D * mb, 2.0 * (double)M * 4 * D);
     VDR_KNOB int attn_variant = env_int("VDR_ATTN_VARIANT", 0);  // (tuning builds)
     VDR_TRY(launch_attention(w.qkv, w.o, mb, ntok, H, attn_variant, s, nullptr, lens, len_add, D / H), "attention");
@@ -1410,11 +1466,11 @@ int run_sam(vdr_model* m, hipStream_t s, const Carve& w, int mb, int out_dtype, 
                    0, C);
 }
 
-// patch embedding of one micro-batch: the token rows b*ntok + ncls + i of w.x (pos_embed added), or -- pe_out non-null,
+// patch embedding of one micro-batch: the token rows b*ntok + P + i of w.x (P prefix rows; pos_embed added), or -- pe_out non-null,
 // model.patch_embed(x) -- the caller's [mb, n, D] output
 int embed_patches(vdr_model* m, hipStream_t s, const Carve& w, const char* img, int in_dtype, int mb, char* pe_out, int out_dtype) {
   const vdr_config& c = m->cfg;
-  const int ntok = m->n_tokens, n = m->n_patches, D = c.dim, ncls = c.has_cls ? 1 : 0;
+  const int ntok = m->n_tokens, n = m->n_patches, D = c.dim, ncls = prefix_rows(m);
   const bool pe_only = pe_out != nullptr;
   GemmArgs g;
   int variant;
@@ -1441,17 +1497,17 @@ int embed_patches(vdr_model* m, hipStream_t s, const Carve& w, const char* img, 
   return VDR_OK;
 }
 
-// CLS rows, input LayerNorm and the fp32 master copy of the stream: afterwards w.x (w.x32) holds what block 0 reads
+// CLS / register rows, input LayerNorm and the fp32 master copy of the stream: afterwards w.x (w.x32) holds what block 0 reads
 int assemble_stream(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok) {
   const vdr_config& c = m->cfg;
   const int D = c.dim;
   int rc;
   if (c.has_cls) {
-    Scope sc(m, s, VDR_K_ASSEMBLE, 0.0, (double)mb * D * 2);
+    Scope sc(m, s, VDR_K_ASSEMBLE, 0.0, (double)mb * (1 + m->n_reg) * D * 2);
     if (m->ln_fuse && !c.input_ln)
-      VDR_TRY(launch_cls_rows_stats(m->cls, m->pos, w.x, w.part, w.Mp, mb, ntok, D, s), "cls rows");
+      VDR_TRY(launch_prefix_rows_stats(m->cls, m->pos, m->reg, m->n_reg, w.x, w.part, w.Mp, mb, ntok, D, s), "prefix rows");
     else
-      VDR_TRY(launch_cls_rows(m->cls, m->pos, w.x, mb, ntok, D, s), "cls rows");
+      VDR_TRY(launch_prefix_rows(m->cls, m->pos, m->reg, m->n_reg, w.x, mb, ntok, D, s), "prefix rows");
   }
   if (c.input_ln && m->ln_fuse) {
     // in place, and the (sum, sumsq) partials of the normalised rows -- block 0's folded qkv GEMM reads them where the
@@ -1541,9 +1597,20 @@ const char* vdr_kernel_class_name(int k) {
   return (k >= 0 && k < VDR_K_COUNT) ? names[k] : "?";
 }
 
-int vdr_create(const vdr_config* cfg, int device, vdr_handle* out) {
+int vdr_create(const vdr_config* cfg, int device, vdr_handle* out) { return vdr_create_ext(cfg, nullptr, device, out); }
+
+int vdr_create_ext(const vdr_config* cfg, const vdr_config_ext* ext, int device, vdr_handle* out) {
   if (!cfg || !out) return fail(nullptr, VDR_ERR_INVALID, "null argument");
   const vdr_config& c = *cfg;
+  vdr_config_ext x{};  // (null ext: no register tokens, no RoPE -- vdr_create)
+  x.size = (int32_t)sizeof(vdr_config_ext);
+  x.rope_theta = 100.0f;
+  if (ext) {
+    if (ext->size < (int32_t)sizeof(vdr_config_ext))
+      return fail(nullptr, VDR_ERR_INVALID, "vdr_config_ext: size " + std::to_string(ext->size) + " is smaller than the " +
+                                                std::to_string(sizeof(vdr_config_ext)) + " bytes of the fields this library knows");
+    x = *ext;
+  }
   if (c.dim <= 0 || c.heads <= 0 || c.layers < 0 || c.mlp_hidden <= 0)
     return fail(nullptr, VDR_ERR_INVALID, "dim/heads/layers/mlp_hidden must be positive");
   {
@@ -1571,6 +1638,23 @@ int vdr_create(const vdr_config* cfg, int device, vdr_handle* out) {
     return fail(nullptr, VDR_ERR_UNSUPPORTED,
                 "fp8 must be 0 or 1 (a level that also quantised the out-projection measured 0.987 row cosine at 40 "
                 "blocks, below the 0.99 gate, and is not shipped)");
+  if (x.n_register < 0) return fail(nullptr, VDR_ERR_INVALID, "n_register must be >= 0");
+  if (x.rope != 0 && x.rope != 1) return fail(nullptr, VDR_ERR_INVALID, "rope must be 0 or 1");
+  if (x.n_register > 0 && !c.has_cls) return fail(nullptr, VDR_ERR_INVALID, "n_register > 0 needs has_cls = 1 (registers sit behind the CLS row)");
+  if (x.rope && !(std::isfinite(x.rope_theta) && x.rope_theta > 1.0f))
+    return fail(nullptr, VDR_ERR_INVALID, "rope = 1: rope_theta must be finite and > 1 (DINOv3: 100)");
+  if (x.n_register > 0 || x.rope) {
+    const char* what = x.rope ? "rope = 1" : "n_register > 0";
+    if (x.n_register > 16) return fail(nullptr, VDR_ERR_UNSUPPORTED, "n_register must be at most 16");
+    if (c.fp8) return fail(nullptr, VDR_ERR_UNSUPPORTED, std::string(what) + ": bf16 path only (fp8 = 1 is not covered)");
+    if (c.window > 0) return fail(nullptr, VDR_ERR_UNSUPPORTED, std::string(what) + ": not for the SAM encoder (window > 0)");
+    if (!c.patch) return fail(nullptr, VDR_ERR_UNSUPPORTED, std::string(what) + ": image models only (patch == 0 is a token model)");
+    if (!c.pre_ln) return fail(nullptr, VDR_ERR_UNSUPPORTED, std::string(what) + ": pre-LN models only");
+    if (x.rope && c.has_pos)
+      return fail(nullptr, VDR_ERR_UNSUPPORTED, "rope = 1 with has_pos = 1: a RoPE model carries no learned pos_embed");
+    if (x.rope && c.dim / c.heads == 96)
+      return fail(nullptr, VDR_ERR_UNSUPPORTED, "rope = 1: head dim 32, 64 or 128 (96: its frequency step is inexact in fp32 and no checkpoint uses it)");
+  }
   if (c.window > 0) {
     const int g = c.patch ? c.img / c.patch : 0;
     auto side_ok = [](int v) { return v == 4 || v == 7 || v == 10 || v == 14; };
@@ -1593,10 +1677,13 @@ int vdr_create(const vdr_config* cfg, int device, vdr_handle* out) {
   std::unique_ptr<vdr_model> m(new vdr_model());
   m->cfg = c;
   m->device = device;
+  m->n_reg = x.n_register;
+  m->rope = x.rope;
+  m->rope_theta = x.rope_theta;
   if (c.patch) {
     const int g = c.img / c.patch;
     m->n_patches = g * g;
-    m->n_tokens = m->n_patches + (c.has_cls ? 1 : 0);
+    m->n_tokens = m->n_patches + prefix_rows(m.get());
     m->Kp = round_up(c.in_chans * c.patch * c.patch, 64);
     m->in_h = m->in_w = c.img;
   }
@@ -1627,6 +1714,8 @@ void vdr_destroy(vdr_handle h) {
     if (kv.second) hipFree(kv.second);
   if (h->fin_cnt) hipFree(h->fin_cnt);
   if (h->pos_sized) hipFree(h->pos_sized);
+  if (h->rope_cos) hipFree(h->rope_cos);
+  if (h->rope_sin) hipFree(h->rope_sin);
   for (auto st : h->streams) hipStreamDestroy(st);
   for (auto st : h->aux) hipStreamDestroy(st);
   for (auto e : h->aux_fork) hipEventDestroy(e);
@@ -1790,7 +1879,7 @@ int vdr_set_input_size(vdr_handle m, int height, int width) {
     m->in_h = hh;
     m->in_w = ww;
     m->n_patches = (hh / c.patch) * (ww / c.patch);
-    m->n_tokens = m->n_patches + (c.has_cls ? 1 : 0);
+    m->n_tokens = m->n_patches + prefix_rows(m);
   };
   geometry(height, width);
   if ((rc = build_pos_table(m))) {
@@ -2393,6 +2482,34 @@ int vdr_op_interpolate_pos(const float* pos, int gh0, int gw0, int D, float* out
   int rc = check_device(nullptr);
   if (rc) return rc;
   OP_TRY(launch_pos_interp(pos, gh0, gw0, D, out, gh, gw, (hipStream_t)stream), "pos_interp");
+  return VDR_OK;
+}
+
+int vdr_op_rope2d_table(int gh, int gw, int head_dim, float theta, float* cos_out, float* sin_out, void* stream) {
+  if (head_dim != 32 && head_dim != 64 && head_dim != 128)
+    return fail(nullptr, VDR_ERR_UNSUPPORTED, "vdr_op_rope2d_table: head_dim must be 32, 64 or 128");
+  if (!cos_out || !sin_out) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_rope2d_table: null table");
+  if (gh <= 0 || gw <= 0 || (int64_t)gh * gw > (1 << 20))
+    return fail(nullptr, VDR_ERR_INVALID, "vdr_op_rope2d_table: gh, gw must be positive, at most 2^20 grid cells");
+  if (!(std::isfinite(theta) && theta > 1.0f)) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_rope2d_table: theta must be finite and > 1");
+  int rc = check_device(nullptr);
+  if (rc) return rc;
+  OP_TRY(launch_rope2d_table(gh, gw, head_dim, theta, cos_out, sin_out, (hipStream_t)stream), "rope2d_table");
+  return VDR_OK;
+}
+
+int vdr_op_rope2d(void* qkv, int batch, int seq, int prefix, int heads, int head_dim, const float* cos, const float* sin,
+                  void* stream) {
+  if (head_dim != 32 && head_dim != 64 && head_dim != 128)
+    return fail(nullptr, VDR_ERR_UNSUPPORTED, "vdr_op_rope2d: head_dim must be 32, 64 or 128");
+  if (!qkv || !cos || !sin) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_rope2d: null argument");
+  if (batch <= 0 || seq <= 0 || heads <= 0 || prefix < 0 || prefix > seq)
+    return fail(nullptr, VDR_ERR_INVALID, "vdr_op_rope2d: batch, seq, heads must be positive and 0 <= prefix <= seq");
+  if ((((uintptr_t)qkv) | ((uintptr_t)cos) | ((uintptr_t)sin)) & 15)
+    return fail(nullptr, VDR_ERR_INVALID, "vdr_op_rope2d: qkv, cos and sin must be 16-byte aligned");
+  int rc = check_device(nullptr);
+  if (rc) return rc;
+  OP_TRY(launch_rope2d(qkv, batch, seq, prefix, heads, head_dim, cos, sin, (hipStream_t)stream), "rope2d");
   return VDR_OK;
 }
 

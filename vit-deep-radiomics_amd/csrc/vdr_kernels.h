@@ -220,9 +220,17 @@ hipError_t launch_im2col(const void* images, int in_bf16, void* col, int batch, 
 // (A = -0.75, align_corners = False, border taps clamped), fp64 arithmetic, one rounding to fp32
 hipError_t launch_pos_interp(const float* pos, int gh0, int gw0, int D, float* out, int gh, int gw, hipStream_t s);
 
-// x[b*row_stride + 0][:] = cls + pos[0]  (bf16 out)
-hipError_t launch_cls_rows(const float* cls, const float* pos, void* x, int batch, int64_t row_stride,
-                           int D, hipStream_t s);
+// DINOv3 2-D RoPE (rope.hip).  Table: cos / sin [gh*gw][head_dim/2] fp32 of the axial angles, fp64 arithmetic, one rounding
+// (load time).  Rotation: q and k of rows b*seq + prefix + j (j < seq - prefix) of qkv [batch*seq][3*heads*head_dim] bf16 in
+// place, table row j; prefix rows and v untouched.  head_dim in {32, 64, 128}; 16-byte aligned pointers.
+hipError_t launch_rope2d_table(int gh, int gw, int head_dim, float theta, float* cos_out, float* sin_out, hipStream_t s);
+hipError_t launch_rope2d(void* qkv, int batch, int seq, int prefix, int heads, int head_dim, const float* cos_t,
+                         const float* sin_t, hipStream_t s);
+
+// prefix rows of an image model (bf16 out): x[b*row_stride + 0][:] = cls + pos[0]; x[b*row_stride + 1 + r][:] = reg[r],
+// r < n_reg (register tokens: no position; reg may be null when n_reg == 0)
+hipError_t launch_prefix_rows(const float* cls, const float* pos, const float* reg, int n_reg, void* x, int batch,
+                              int64_t row_stride, int D, hipStream_t s);
 
 // token assembly for the token model: x[b*(S+1)+1+i] = tok[b*S+i] (+pos), x[b*(S+1)] = cls (+pos[0]); bf16 out
 hipError_t launch_assemble_tokens(const void* tok, int in_bf16, const float* cls, const float* pos,
@@ -233,9 +241,9 @@ hipError_t launch_assemble_tokens(const void* tok, int in_bf16, const float* cls
 // (mean, rstd)
 hipError_t launch_ln_finalize(const float* part, int groups, int64_t stride, float* stats, int64_t rows, int D,
                               float eps, hipStream_t s);
-// x[b*row_stride][:] = cls + pos[0] as launch_cls_rows, plus that row's partial sums
-hipError_t launch_cls_rows_stats(const float* cls, const float* pos, void* x, float* part, int64_t part_stride,
-                                 int batch, int64_t row_stride, int D, hipStream_t s);
+// as launch_prefix_rows, plus the (sum, sumsq) partials of each of the 1 + n_reg rows it writes
+hipError_t launch_prefix_rows_stats(const float* cls, const float* pos, const float* reg, int n_reg, void* x, float* part,
+                                    int64_t part_stride, int batch, int64_t row_stride, int D, hipStream_t s);
 
 // x[r] = LN(x[r]) in place over bf16 rows [rows, D], plus the (sum, sumsq) partials of the normalised bf16 rows in the
 // fold's layout part [D/64][part_stride][2] (vdr_config.input_ln with the LayerNorm fold on); D % 64 == 0

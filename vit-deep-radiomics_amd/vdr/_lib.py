@@ -33,6 +33,10 @@ class vdr_config(C.Structure):
                 ("ln_fin_fused", C.c_int32)]
 
 
+class vdr_config_ext(C.Structure):
+    _fields_ = [("size", C.c_int32), ("n_register", C.c_int32), ("rope", C.c_int32), ("rope_theta", C.c_float)]
+
+
 class vdr_layer_out(C.Structure):
     _fields_ = [("layer", C.c_int32), ("out_mode", C.c_int32), ("out_dtype", C.c_int32), ("norm", C.c_int32),
                 ("ld", C.c_int64), ("out", C.c_void_p)]
@@ -50,6 +54,7 @@ SYMBOLS = {
     "vdr_tuning_build": (_I, []),
     "vdr_device_count": (_I, []),
     "vdr_create": (_I, [C.POINTER(vdr_config), _I, C.POINTER(_P)]),
+    "vdr_create_ext": (_I, [C.POINTER(vdr_config), C.POINTER(vdr_config_ext), _I, C.POINTER(_P)]),
     "vdr_destroy": (None, [_P]),
     "vdr_last_error": (C.c_char_p, [_P]),
     "vdr_set_weight": (_I, [_P, C.c_char_p, _P, C.POINTER(_L), _I]),
@@ -94,6 +99,8 @@ SYMBOLS = {
     "vdr_op_attention_relpos": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "vdr_op_interpolate_pos": (_I, [_P, _I, _I, _I, _P, _I, _I, _P]),
     "vdr_op_interpolate_rel_pos": (_I, [_P, _I, _I, _P, _I, _P]),
+    "vdr_op_rope2d_table": (_I, [_I, _I, _I, _F, _P, _P, _P]),
+    "vdr_op_rope2d": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "vdr_op_patch_embed": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vdr_profile_enable": (_I, [_P, _I]),
     "vdr_profile_mask": (_I, [_P, C.c_uint32]),

@@ -40,14 +40,23 @@ class VdrConfig:
     fp8_cls_bf16: bool = False  # fp8 = 1: the MLP of the CLS rows on the bf16 weights (vdr_config.fp8_cls_bf16)
     resid_fp32: bool = False  # bf16 path: fp32 master copy of the residual stream (vdr_config.resid_fp32)
     ln_fin_fused: bool = False  # LayerNorm fold: the residual GEMMs finalise the row statistics themselves (vdr_config.ln_fin_fused)
+    # vdr_config_ext (vdr_create_ext): what came after vdr_config was frozen
+    n_register: int = 0        # register tokens between the CLS row and the patch rows (DINOv2-with-registers, DINOv3)
+    rope: bool = False         # DINOv3's axial 2-D RoPE on q / k of the patch rows (no pos_embed: has_pos=False)
+    rope_theta: float = 100.0
 
     @property
     def n_patches(self):
         return (self.img // self.patch) ** 2 if self.patch else 0
 
     @property
+    def n_prefix(self):
+        """rows in front of the patch rows of an image: the CLS token, then the register tokens"""
+        return (1 if self.has_cls else 0) + int(self.n_register)
+
+    @property
     def n_tokens(self):
-        return self.n_patches + (1 if self.has_cls else 0)
+        return self.n_patches + self.n_prefix
 
     def to_c(self) -> L.vdr_config:
         c = L.vdr_config()
@@ -66,6 +75,12 @@ class VdrConfig:
         c.resid_fp32 = int(self.resid_fp32)
         c.ln_fin_fused = int(self.ln_fin_fused)
         return c
+
+    def to_c_ext(self) -> L.vdr_config_ext:
+        e = L.vdr_config_ext()
+        e.size = C.sizeof(L.vdr_config_ext)
+        e.n_register, e.rope, e.rope_theta = int(self.n_register), int(bool(self.rope)), float(self.rope_theta)
+        return e
 
 
 _DT = {torch.float32: L.VDR_F32, torch.bfloat16: L.VDR_BF16}
@@ -111,8 +126,8 @@ class Engine:
         # always an indexed device: torch.device("cuda") means the current one
         self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
         h = C.c_void_p()
-        cc = cfg.to_c()
-        L.check(self.lib.vdr_create(C.byref(cc), self.device.index, C.byref(h)))
+        cc, ce = cfg.to_c(), cfg.to_c_ext()
+        L.check(self.lib.vdr_create_ext(C.byref(cc), C.byref(ce), self.device.index, C.byref(h)))
         self.h = h
         self._ws = None
         self._loaded = False
@@ -174,12 +189,14 @@ class Engine:
 
     @property
     def n_tokens(self) -> int:
-        return self.n_patches + (1 if self.cfg.has_cls else 0)
+        return self.n_patches + self.cfg.n_prefix
 
     def set_input_size(self, height: int, width: int):
         """vdr_set_input_size: run the model on [B, C, height, width] images from now on (sides multiples of patch; square
         or rectangular).  The learned pos_embed is resampled once, on the device, the way DINOv2 / transformers
-        interpolate_pos_encoding do (bicubic, align_corners=False); (img, img) selects the loaded table again, bit for bit.
+        interpolate_pos_encoding do (bicubic, align_corners=False; no antialiasing, which upstream's registers variants
+        use); (img, img) selects the loaded table again, bit for bit.  A RoPE model (DINOv3) has no table: its cos / sin
+        tables are rebuilt for the new grid.
         Load-time class: allocates and synchronises, so call it outside graph capture.  SAM encoders and token models
         are tied to their geometry: ValueError."""
         cfg = self.cfg

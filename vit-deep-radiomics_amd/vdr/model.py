@@ -16,6 +16,8 @@ import torch
 from . import _lib as L
 from .engine import AttnMap, Engine, LayerOut, VdrConfig
 
+_DINOV3 = dict(layerscale=True, has_pos=False, ln_eps=1e-5, n_register=4, rope=True, rope_theta=100.0)
+
 # geometries BASELINE.json names + the two the reference itself loads
 ARCHS = {
     "vit_tiny16_224": VdrConfig(224, 16, 3, 192, 3, 12, 768),
@@ -45,6 +47,19 @@ ARCHS = {
     # SigLIP (siglip-base / large-patch16): tanh-GELU, no CLS token, attention-pooling head, eps 1e-6
     "siglip_base16_224": VdrConfig(224, 16, 3, 768, 12, 12, 3072, act="gelu_tanh", has_cls=False),
     "siglip_large16_256": VdrConfig(256, 16, 3, 1024, 16, 24, 4096, act="gelu_tanh", has_cls=False),
+    # DINOv2-with-registers (hub dinov2_vit*14_reg / transformers Dinov2WithRegistersModel): DINOv2 plus 4 register tokens
+    # between the CLS row and the patch rows; pos_embed [1, 1370, D] for 518^2, other sizes through set_input_size
+    "dinov2_small14_reg_518": VdrConfig(518, 14, 3, 384, 6, 12, 1536, layerscale=True, n_register=4),
+    "dinov2_base14_reg_518": VdrConfig(518, 14, 3, 768, 12, 12, 3072, layerscale=True, n_register=4),
+    "dinov2_large14_reg_518": VdrConfig(518, 14, 3, 1024, 16, 24, 4096, layerscale=True, n_register=4),
+    "dinov2_giant14_reg_518": VdrConfig(518, 14, 3, 1536, 24, 40, 4096, act="swiglu", layerscale=True, n_register=4),
+    # DINOv3 (transformers DINOv3ViTModel): 4 register tokens, no pos_embed, 2-D RoPE on q / k of the patch rows,
+    # LayerScale, eps 1e-5; the "plus" models have the gated (SwiGLU) MLP
+    "dinov3_vits16": VdrConfig(224, 16, 3, 384, 6, 12, 1536, **_DINOV3),
+    "dinov3_vits16plus": VdrConfig(224, 16, 3, 384, 6, 12, 1536, act="swiglu", **_DINOV3),
+    "dinov3_vitb16": VdrConfig(224, 16, 3, 768, 12, 12, 3072, **_DINOV3),
+    "dinov3_vitl16": VdrConfig(224, 16, 3, 1024, 16, 24, 4096, **_DINOV3),
+    "dinov3_vith16plus": VdrConfig(224, 16, 3, 1280, 20, 32, 5120, act="swiglu", **_DINOV3),
 }
 
 
@@ -269,7 +284,7 @@ class VitDescriptorModel:
         if bad:
             raise ValueError(f"block indices {bad} out of range 0..{self.cfg.layers - 1}")
         self._adopt(x)
-        N, ncls = self.engine.n_tokens, 1 if self.cfg.has_cls else 0
+        N, ncls = self.engine.n_tokens, self.cfg.n_prefix  # (reshape drops the CLS and register key columns)
         _, got = self.engine.forward_attn_maps(x, [AttnMap(i, 1 if cls_only else N, head_mean) for i in idx])
         res = []
         for t in got:
@@ -369,7 +384,9 @@ def load_model(model_name: str, model_path=None, weights=None, device=None, micr
     torch.load(weights_only=True).  weights: the same dict passed directly.  A transformers CLIPVisionModel
     [WithProjection] / SiglipVisionModel state_dict (the clip_* / siglip_* entries of ARCHS) is translated on the way in
     (vdr.weights.from_clip_vision_state_dict / from_siglip_vision_state_dict); its projection / pooling head serves
-    model.get_image_features(x).  Images are raw [0, 1] here as for every model: no mean / std normalisation is applied.
+    model.get_image_features(x).  A transformers DINOv3ViTModel / Dinov2Model / Dinov2WithRegistersModel state_dict (the
+    dinov3_* / dinov2_*_reg_* entries) is translated too (from_dinov3_vit_state_dict / from_dinov2_hf_state_dict); hub-format
+    dinov2_vit*14_reg state_dicts (register_tokens [1, 4, D]) load as they are.  Images are raw [0, 1] here as for every model: no mean / std normalisation is applied.
     fp8=True keeps the qkv / fc1 / fc2 weights as MX-fp8 and runs them on the block-scaled fp8 MFMA
     (BASELINE config 5; pre-LN models).  full_last_block=True: `model(x)` computes every token of the last block
     like the reference does before it keeps x[:, 0] (default: the CLS rows only, same bits).  fp8_cls_bf16=True (fp8 models
@@ -406,6 +423,14 @@ def load_model(model_name: str, model_path=None, weights=None, device=None, micr
         from .weights import from_clip_vision_state_dict, from_siglip_vision_state_dict
         clip = any(k.endswith("embeddings.class_embedding") for k in weights)
         weights = from_clip_vision_state_dict(weights) if clip else from_siglip_vision_state_dict(weights)
+    # transformers DINOv3ViTModel keys (embeddings.patch_embeddings.weight, [model.]layer.{i}.*) and Dinov2Model /
+    # Dinov2WithRegistersModel keys (embeddings.patch_embeddings.projection.weight, encoder.layer.{i}.*)
+    if "embeddings.patch_embeddings.weight" in weights:
+        from .weights import from_dinov3_vit_state_dict
+        weights = from_dinov3_vit_state_dict(weights)
+    elif "embeddings.patch_embeddings.projection.weight" in weights and any(".layer_scale1.lambda1" in k for k in weights):
+        from .weights import from_dinov2_hf_state_dict
+        weights = from_dinov2_hf_state_dict(weights)
     model = VitDescriptorModel(cfg, weights, model_name, device, dynamic_size=dynamic_size, sized=img_size is not None)
     model.model_name = model_name
     return model

@@ -273,6 +273,31 @@ def interpolate_pos(pos: torch.Tensor, native_grid, grid) -> torch.Tensor:
     return out
 
 
+def rope2d_table(grid, head_dim: int, theta: float = 100.0, device=None):
+    """DINOv3's axial 2-D RoPE tables of a (gh, gw) patch grid (vdr_op_rope2d_table): (cos, sin), fp32 [gh*gw, head_dim/2]
+    on the device."""
+    lib = L.load()
+    gh, gw = int(grid[0]), int(grid[1])
+    dev = torch.device("cuda") if device is None else device
+    cos = torch.empty((gh * gw, head_dim // 2), dtype=torch.float32, device=dev)
+    sin = torch.empty_like(cos)
+    L.check(lib.vdr_op_rope2d_table(gh, gw, int(head_dim), float(theta), cos.data_ptr(), sin.data_ptr(), _s(cos)))
+    return cos, sin
+
+
+def rope2d(qkv: torch.Tensor, batch: int, seq: int, prefix: int, heads: int, head_dim: int, cos: torch.Tensor,
+           sin: torch.Tensor) -> torch.Tensor:
+    """In place (vdr_op_rope2d): q and k of rows b*seq + prefix + j of the packed qkv [batch*seq, 3*heads*head_dim] bf16
+    rotated with table row j; prefix rows and v untouched.  Returns qkv."""
+    lib = L.load()
+    assert qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.is_contiguous()
+    assert tuple(qkv.shape) == (batch * seq, 3 * heads * head_dim)
+    for t in (cos, sin):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (seq - prefix, head_dim // 2)
+    L.check(lib.vdr_op_rope2d(qkv.data_ptr(), batch, seq, prefix, heads, head_dim, cos.data_ptr(), sin.data_ptr(), _s(qkv)))
+    return qkv
+
+
 def interpolate_rel_pos(table: torch.Tensor, L_out: int) -> torch.Tensor:
     """table [L0, D] fp32 on the device -> [L_out, D] fp32: segment_anything's get_rel_pos resampling
     (vdr_op_interpolate_rel_pos: linear, align_corners=False, fp64 arithmetic, one rounding)."""

@@ -77,6 +77,101 @@ def from_siglip_vision_state_dict(sd):
     return {k: v.contiguous() for k, v in out.items()}
 
 
+def _f32(sd):
+    return {k: torch.as_tensor(v).detach().to(torch.float32) for k, v in sd.items() if torch.is_floating_point(torch.as_tensor(v))}
+
+
+def from_dinov3_vit_state_dict(sd):
+    """transformers DINOv3ViTModel state_dict (layers under `model.layer.{i}.` or `layer.{i}.`) -> the canonical names:
+    q_proj / k_proj / v_proj concatenated into attn.qkv (k_proj has no bias: a zero k bias is supplied), o_proj ->
+    attn.proj, layer_scale{1,2}.lambda1 -> ls{1,2}.gamma, up_proj / down_proj -> mlp.fc1 / fc2 or, gated,
+    cat(gate_proj, up_proj) -> mlp.w12 and down_proj -> mlp.w3 (silu(gate) * up: the SwiGLU epilogue).  mask_token is
+    dropped.  There is no pos_embed: the model is built with has_pos=False, rope=True.  (The key names of the original
+    facebookresearch/dinov3 checkpoints are not handled.)"""
+    sd = _f32(sd)
+    if "embeddings.patch_embeddings.weight" not in sd:
+        raise KeyError("from_dinov3_vit_state_dict: no embeddings.patch_embeddings.weight -- not a transformers DINOv3ViTModel state_dict")
+    pre = "model.layer." if any(k.startswith("model.layer.") for k in sd) else "layer."
+    out = {"patch_embed.proj.weight": sd["embeddings.patch_embeddings.weight"],
+           "patch_embed.proj.bias": sd["embeddings.patch_embeddings.bias"],
+           "cls_token": sd["embeddings.cls_token"].reshape(1, 1, -1)}
+    D = out["patch_embed.proj.weight"].shape[0]
+    if "embeddings.register_tokens" in sd and sd["embeddings.register_tokens"].numel():
+        out["register_tokens"] = sd["embeddings.register_tokens"].reshape(1, -1, D)
+    i = 0
+    while f"{pre}{i}.attention.q_proj.weight" in sd:
+        s, d = f"{pre}{i}.", f"blocks.{i}."
+        att = s + "attention."
+        out[d + "attn.qkv.weight"] = torch.cat([sd[att + f"{p}_proj.weight"] for p in ("q", "k", "v")], dim=0)
+        out[d + "attn.qkv.bias"] = torch.cat([sd.get(att + f"{p}_proj.bias", torch.zeros(D)) for p in ("q", "k", "v")], dim=0)
+        out[d + "attn.proj.weight"] = sd[att + "o_proj.weight"]
+        out[d + "attn.proj.bias"] = sd.get(att + "o_proj.bias", torch.zeros(D))
+        out[d + "ls1.gamma"], out[d + "ls2.gamma"] = sd[s + "layer_scale1.lambda1"], sd[s + "layer_scale2.lambda1"]
+        for n in ("norm1", "norm2"):
+            for t in ("weight", "bias"):
+                out[d + f"{n}.{t}"] = sd[s + f"{n}.{t}"]
+        Fh = sd[s + "mlp.up_proj.weight"].shape[0]
+        bias = lambda k, n: sd.get(s + f"mlp.{k}.bias", torch.zeros(n))  # noqa: E731
+        if s + "mlp.gate_proj.weight" in sd:
+            out[d + "mlp.w12.weight"] = torch.cat([sd[s + "mlp.gate_proj.weight"], sd[s + "mlp.up_proj.weight"]], dim=0)
+            out[d + "mlp.w12.bias"] = torch.cat([bias("gate_proj", Fh), bias("up_proj", Fh)], dim=0)
+            out[d + "mlp.w3.weight"], out[d + "mlp.w3.bias"] = sd[s + "mlp.down_proj.weight"], bias("down_proj", D)
+        else:
+            out[d + "mlp.fc1.weight"], out[d + "mlp.fc1.bias"] = sd[s + "mlp.up_proj.weight"], bias("up_proj", Fh)
+            out[d + "mlp.fc2.weight"], out[d + "mlp.fc2.bias"] = sd[s + "mlp.down_proj.weight"], bias("down_proj", D)
+        i += 1
+    out["norm.weight"], out["norm.bias"] = sd["norm.weight"], sd["norm.bias"]
+    return {k: v.contiguous() for k, v in out.items()}
+
+
+def from_dinov2_hf_state_dict(sd):
+    """transformers Dinov2Model / Dinov2WithRegistersModel state_dict -> the canonical (hub DINOv2) names: query / key /
+    value concatenated into attn.qkv, attention.output.dense -> attn.proj, layer_scale{1,2}.lambda1 -> ls{1,2}.gamma,
+    mlp.fc1 / fc2 or (SwiGLU) mlp.weights_in / weights_out -> mlp.w12 / w3, layernorm -> norm, position_embeddings ->
+    pos_embed [1, 1 + n, D], register_tokens kept [1, R, D] when the model has them.  mask_token is dropped."""
+    sd = _f32(sd)
+    if "embeddings.patch_embeddings.projection.weight" not in sd:
+        raise KeyError("from_dinov2_hf_state_dict: no embeddings.patch_embeddings.projection.weight -- not a transformers "
+                       "Dinov2Model / Dinov2WithRegistersModel state_dict")
+    out = {"patch_embed.proj.weight": sd["embeddings.patch_embeddings.projection.weight"],
+           "patch_embed.proj.bias": sd["embeddings.patch_embeddings.projection.bias"],
+           "cls_token": sd["embeddings.cls_token"].reshape(1, 1, -1),
+           "pos_embed": sd["embeddings.position_embeddings"]}
+    D = out["patch_embed.proj.weight"].shape[0]
+    if "embeddings.register_tokens" in sd and sd["embeddings.register_tokens"].numel():
+        out["register_tokens"] = sd["embeddings.register_tokens"].reshape(1, -1, D)
+    i = 0
+    while f"encoder.layer.{i}.attention.attention.query.weight" in sd:
+        s, d = f"encoder.layer.{i}.", f"blocks.{i}."
+        for t in ("weight", "bias"):
+            out[d + "attn.qkv." + t] = torch.cat([sd[s + f"attention.attention.{p}.{t}"] for p in ("query", "key", "value")], dim=0)
+            out[d + "attn.proj." + t] = sd[s + "attention.output.dense." + t]
+            out[d + "norm1." + t], out[d + "norm2." + t] = sd[s + "norm1." + t], sd[s + "norm2." + t]
+            if s + "mlp.weights_in.weight" in sd:
+                out[d + "mlp.w12." + t], out[d + "mlp.w3." + t] = sd[s + "mlp.weights_in." + t], sd[s + "mlp.weights_out." + t]
+            else:
+                out[d + "mlp.fc1." + t], out[d + "mlp.fc2." + t] = sd[s + "mlp.fc1." + t], sd[s + "mlp.fc2." + t]
+        out[d + "ls1.gamma"], out[d + "ls2.gamma"] = sd[s + "layer_scale1.lambda1"], sd[s + "layer_scale2.lambda1"]
+        i += 1
+    out["norm.weight"], out["norm.bias"] = sd["layernorm.weight"], sd["layernorm.bias"]
+    return {k: v.contiguous() for k, v in out.items()}
+
+
+def rope2d_table(grid, head_dim: int, theta: float = 100.0):
+    """Host statement of vdr_op_rope2d_table (DINOv3's axial 2-D RoPE): (cos, sin), fp32 [gh*gw, head_dim/2] each -- angle,
+    cos and sin evaluated in float64 and rounded once.  Patch (y, x): cy = 2 (y + 0.5) / gh - 1, cx = 2 (x + 0.5) / gw - 1,
+    inv_freq[i] = theta^(-4 i / head_dim); angles [2 pi cy inv_freq | 2 pi cx inv_freq]."""
+    import math
+    gh, gw, q = int(grid[0]), int(grid[1]), int(head_dim) // 4
+    inv = float(theta) ** (-torch.arange(q, dtype=torch.float64) / q)
+    cy = 2.0 * (torch.arange(gh, dtype=torch.float64) + 0.5) / gh - 1.0
+    cx = 2.0 * (torch.arange(gw, dtype=torch.float64) + 0.5) / gw - 1.0
+    ay = (2.0 * math.pi * cy[:, None] * inv[None, :])[:, None, :].expand(gh, gw, q)
+    ax = (2.0 * math.pi * cx[:, None] * inv[None, :])[None, :, :].expand(gh, gw, q)
+    a = torch.cat([ay, ax], dim=-1).reshape(gh * gw, 2 * q)
+    return torch.cos(a).to(torch.float32), torch.sin(a).to(torch.float32)
+
+
 def split_head_weights(weights):
     """(encoder weights, head weights): the head.* entries of a translated CLIP / SigLIP state_dict apart from the rest."""
     enc = {k: v for k, v in weights.items() if not k.startswith("head.")}
@@ -92,8 +187,10 @@ def expected_weight_shapes(cfg) -> "dict[str, tuple]":
         s["patch_embed.proj.bias"] = (D,)
     if cfg.has_cls:
         s["cls_token"] = (1, 1, D)
-    if cfg.has_pos:
-        s["pos_embed"] = (1, cfg.n_tokens, D)
+    if getattr(cfg, "n_register", 0):
+        s["register_tokens"] = (1, cfg.n_register, D)
+    if cfg.has_pos:  # (register tokens carry no position)
+        s["pos_embed"] = (1, cfg.n_patches + (1 if cfg.has_cls else 0), D)
     if cfg.input_ln:
         s["input_norm.weight"] = (D,)
         s["input_norm.bias"] = (D,)
