@@ -927,7 +927,7 @@ int gemm(vdr_model* m, hipStream_t s, int cls, GemmArgs g, int epi, const LnFold
 
 int layernorm(vdr_model* m, hipStream_t s, int cls, const void* x, int in_bf16, void* y, int out_bf16,
               const float* gw, const float* gb, int64_t rows, RowMap imap, const float* clsrc = nullptr,
-              int cls_period = 0, int width = 0, int64_t ldy = 0) {
+              int cls_period = 0, int width = 0, int64_t ldy = 0, int win_ws = 0, int win_g = 0) {
   LnArgs a{};
   a.x = x;
   a.in_bf16 = in_bf16;
@@ -943,12 +943,13 @@ int layernorm(vdr_model* m, hipStream_t s, int cls, const void* x, int in_bf16, 
   a.cls = clsrc;
   a.cls_period = cls_period;
   a.ldy = ldy;
+  a.win_ws = win_ws;  // (SAM window blocks: the output rows in window-partition order)
+  a.win_g = win_g;
   Scope sc(m, s, cls, 0.0, (double)rows * a.D * ((in_bf16 ? 2 : 4) + (out_bf16 ? 2 : 4)));
   VDR_TRY(launch_layernorm(a, s), "layernorm");
   return VDR_OK;
 }
 
-// L transformer blocks over x [M = mb*ntok rows]; leaves the result in w.x
 // tile configuration of the MX-fp8 GEMM per class and shape (VDR_MX_VARIANT overrides)
 int mx_variant_for(int cls, int64_t M, int N) {
   VDR_KNOB int forced = env_int("VDR_MX_VARIANT", -1);
@@ -976,13 +977,98 @@ int gemm_mx(vdr_model* m, hipStream_t s, int cls, const void* aq, const void* as
   return VDR_OK;
 }
 
-// CLS-only tail of the LAST block (VDR_OUT_CLS: `model(x) -> (logits, cls)`, models_archs.py:24-29 -- the reference
-// computes every token of the last block and then keeps x[:, 0]).  After the last attention nothing mixes rows any
-// more: out-projection, norm2, MLP and the final norm are row-wise, so the [mb] CLS rows are all that reaches the output.
-// They are gathered by the out-projection itself (A and the residual are read with a row stride of ntok * D, the
-// result goes to a compact [mb, D] buffer -- the head of w.h, which no later kernel of this forward reads) and the MLP
-// runs on mb rows instead of mb * ntok.  Same kernels, same per-row arithmetic: the CLS features are bitwise those of
-// the full block (test_cls_rows_only_last_block_bitwise).  vdr_config.full_last_block = 1 keeps every row.
+// ---- the transformer block --------------------------------------------------------------------------------------------
+// How a model's linears take their LayerNorm and their operands.  Chosen once per forward (block_path); the two steps of
+// a block that differ between the paths are BlockSteps::norm_linear and BlockSteps::resid_linear, everything else -- the
+// block loop of run_blocks, the CLS tail, the CLS rows' bf16 MLP, the MLP half of a SAM block -- is written once over them.
+enum BlockPath {
+  // BASELINE config 5: qkv / fc1 / fc2 on the block-scaled fp8 MFMA.  LayerNorm writes its output as MX-fp8 (the qkv / fc1
+  // operand), the attention kernel and the fc1 epilogue write theirs as MX-fp8 (the proj / fc2 operands); the residual
+  // stream and the attention arithmetic stay bf16 / fp32.
+  PATH_MX,
+  // LayerNorm never materialised: producers leave (sum, sumsq) partials, a tiny kernel turns them into (mean, rstd), the
+  // consuming GEMM applies them in its epilogue (weights pre-multiplied by gamma).
+  PATH_FOLD,
+  // A LayerNorm kernel in front of the linear (pre-LN), or -- post-LN, nn.TransformerEncoderLayer with norm_first=False:
+  // x = LN1(x + SA(x)); x = LN2(x + FF(x)) -- the linears read the stream itself and the caller runs the LayerNorms.
+  PATH_EXPLICIT
+};
+
+BlockPath block_path(const vdr_model* m) { return m->cfg.fp8 ? PATH_MX : (m->cfg.pre_ln && m->ln_fuse) ? PATH_FOLD : PATH_EXPLICIT; }
+
+// Rows of the residual stream as a step reads or writes them: row r is bf16 row r * step of x (step 0: dense rows; ntok:
+// the CLS row of every image) and, under resid_fp32, of the fp32 master copy x32 (else null)
+struct Rows {
+  void* x;
+  float* x32;
+  int step;
+};
+
+struct BlockSteps {
+  vdr_model* m;
+  hipStream_t s;
+  const Carve& w;
+  const LayerW& L;
+  BlockPath path;
+
+  // LayerNorm (norm1 / norm2) of M rows of the stream, then the linear that reads it (qkv / fc1) into `out`.  h: where the
+  // normalised rows go on the paths that materialise them (MX: the payload, its scales in w.hs); a_rows: as gemm() takes
+  // it.  Strided rows (in.step) are read by the explicit form only.
+  int norm_linear(bool fc1, int64_t M, Rows in, char* h, void* out, int64_t a_rows) const {
+    const vdr_config& c = m->cfg;
+    const int D = c.dim, cls = fc1 ? VDR_K_GEMM_FC1 : VDR_K_GEMM_QKV, epi = fc1 ? fc1_epilogue(c) : EPI_BIAS;
+    const int N = !fc1 ? 3 * D : epi == EPI_SWIGLU ? 2 * c.mlp_hidden : c.mlp_hidden;
+    const float *nw = fc1 ? L.n2w : L.n1w, *nb = fc1 ? L.n2b : L.n1b;
+    int rc;
+    if (path == PATH_MX) {
+      {
+        Scope sc(m, s, VDR_K_LAYERNORM, 0.0, (double)M * D * 3);  // (own block: the profiler bracket must close before the GEMM)
+        VDR_TRY(launch_ln_mx(in.x, nw, nb, c.ln_eps, M, D, h, w.hs, s), "layernorm_mx");
+      }
+      return gemm_mx(m, s, cls, h, w.hs, fc1 ? L.w1_q : L.qkv_q, fc1 ? L.w1_s : L.qkv_s, fc1 ? L.b1 : L.bqkv, nullptr, nullptr, out,
+                     fc1 ? w.us : nullptr, M, N, D, epi);
+    }
+    GemmArgs g;
+    LnFold cons;
+    if (path == PATH_FOLD) {
+      if ((rc = ln_consumer(m, s, cls, M, N, D, w, &cons))) return rc;
+      cons.colsum = fc1 ? L.s1 : L.sqkv;
+      g = linear(in.x, fc1 ? L.w1_f : L.wqkv_f, out, M, N, D, epi);
+      g.bias = fc1 ? L.t1 : L.tqkv;
+    } else {
+      // (resid_fp32: the explicit LayerNorm reads the fp32 master copy of the stream)
+      if (c.pre_ln && (rc = layernorm(m, s, VDR_K_LAYERNORM, in.x32 ? (const void*)in.x32 : in.x, !in.x32, h, 1, nw, nb, M,
+                                      in.step ? RowMap{1, in.step, 0} : identity_map())))
+        return rc;
+      g = linear(c.pre_ln ? h : in.x, fc1 ? L.w1 : L.wqkv, out, M, N, D, epi);
+      g.bias = fc1 ? L.b1 : L.bqkv;
+    }
+    g.a_rows = a_rows;
+    return gemm(m, s, cls, g, epi, cons);
+  }
+
+  // The residual linears (proj / fc2): out = in + gamma * (A . W^T + bias) over M rows, A's rows lda elements apart (0:
+  // dense); in place, into compact rows, or (post-LN) into the input of the LayerNorm behind it.  prod: the fold's
+  // producer side, where a folded consumer reads these rows next (else null).
+  int resid_linear(bool fc2, int64_t M, const void* A, int64_t lda, Rows in, Rows out, const LnFold* prod) const {
+    const vdr_config& c = m->cfg;
+    const int D = c.dim, K = fc2 ? c.mlp_hidden : D, cls = fc2 ? VDR_K_GEMM_FC2 : VDR_K_GEMM_PROJ;
+    const float* gamma = fc2 ? L.ls2 : L.ls1;  // (LayerScale; null without)
+    if (path == PATH_MX && fc2)
+      return gemm_mx(m, s, cls, A, w.us, L.w2_q, L.w2_s, L.b2, in.x, gamma, out.x, nullptr, M, D, K, EPI_BIAS_RESID);
+    // (the out-projection stays bf16 on the MX path: quantising it too measured 0.987 row cosine at 40 blocks, gate 0.99)
+    GemmArgs g = linear(A, fc2 ? L.w2 : L.wproj, out.x, M, D, K, EPI_BIAS_RESID);
+    g.bias = fc2 ? L.b2 : L.bproj;
+    g.resid = in.x;
+    g.gamma = gamma;
+    g.resid32 = in.x32;
+    g.C32 = out.x32;
+    if (lda) g.lda = lda;
+    if (in.step) g.ldr = (int64_t)in.step * D;
+    return gemm(m, s, cls, g, EPI_BIAS_RESID, prod ? *prod : LnFold());
+  }
+};
+
 struct BookAs {  // the profiler books these launches as VDR_K_CLS_TAIL, so that gemm_proj / fc1 / fc2 stay classes of
   vdr_model* m;  // identical full-size launches (their averages are what the rocprofv3 summaries are compared with)
   explicit BookAs(vdr_model* m_) : m(m_) { m->prof_as = VDR_K_CLS_TAIL; }
@@ -992,80 +1078,42 @@ struct BookAs {  // the profiler books these launches as VDR_K_CLS_TAIL, so that
 // vdr_config.fp8_cls_bf16: norm2 -> fc1 / w12 -> activation -> fc2 / w3 + residual of the CLS rows (row b * ntok of the
 // residual stream) on the bf16 weights, enqueued on `ax`; leaves the rows' new residual values in w.cls_x [mb, D].  Reads
 // the residual stream as it is after the out-projection; the caller puts w.cls_x back once the MX-fp8 MLP of every row has
-// written w.x.  Same kernels and per-row arithmetic as the CLS tail of the last block (block_tail_cls, explicit-LayerNorm
-// branch): a row's bits do not depend on which of the two computed it.
+// written w.x.  Same kernels and per-row arithmetic as the CLS tail of the last block (block_tail_cls on the explicit
+// path): a row's bits do not depend on which of the two computed it.
 int cls_mlp_bf16(vdr_model* m, hipStream_t ax, const Carve& w, const LayerW& L, int mb, int ntok) {
   BookAs book(m);
-  const vdr_config& c = m->cfg;
-  const int D = c.dim, F = c.mlp_hidden;
-  const int e1 = fc1_epilogue(c);
-  int rc;
-  if ((rc = layernorm(m, ax, VDR_K_LAYERNORM, w.x, 1, w.cls_h, 1, L.n2w, L.n2b, mb, RowMap{1, ntok, 0}))) return rc;
-  GemmArgs fc1 = linear(w.cls_h, L.w1, w.cls_u, mb, e1 == EPI_SWIGLU ? 2 * F : F, D, e1);
-  fc1.bias = L.b1;
-  if ((rc = gemm(m, ax, VDR_K_GEMM_FC1, fc1, e1))) return rc;
-  GemmArgs fc2 = linear(w.cls_u, L.w2, w.cls_x, mb, D, F, EPI_BIAS_RESID);
-  fc2.bias = L.b2;
-  fc2.resid = w.x;
-  fc2.gamma = L.ls2;
-  fc2.ldr = (int64_t)ntok * D;
-  return gemm(m, ax, VDR_K_GEMM_FC2, fc2, EPI_BIAS_RESID);
+  const BlockSteps b{m, ax, w, L, PATH_EXPLICIT};
+  const Rows cls_rows{w.x, nullptr, ntok};
+  if (int rc = b.norm_linear(true, mb, cls_rows, w.cls_h, w.cls_u, 0)) return rc;
+  return b.resid_linear(true, mb, w.cls_u, 0, cls_rows, Rows{w.cls_x, nullptr, 0}, nullptr);
 }
 
+// CLS-only tail of the LAST block (VDR_OUT_CLS: `model(x) -> (logits, cls)`, models_archs.py:24-29 -- the reference
+// computes every token of the last block and then keeps x[:, 0]).  After the last attention nothing mixes rows any
+// more: out-projection, norm2, MLP and the final norm are row-wise, so the [mb] CLS rows are all that reaches the output.
+// They are gathered by the out-projection itself (A and the residual are read with a row stride of ntok * D, the
+// result goes to a compact [mb, D] buffer -- the head of w.h, which no later kernel of this forward reads) and the MLP
+// runs on mb rows instead of mb * ntok.  Same kernels, same per-row arithmetic: the CLS features are bitwise those of
+// the full block (test_cls_rows_only_last_block_bitwise).  vdr_config.full_last_block = 1 keeps every row.
 int block_tail_cls(vdr_model* m, hipStream_t s, const Carve& w, const LayerW& L, int mb, int ntok) {
   BookAs book(m);
   const vdr_config& c = m->cfg;
-  const int D = c.dim, F = c.mlp_hidden;
-  const int e1 = fc1_epilogue(c), N1 = e1 == EPI_SWIGLU ? 2 * F : F;
-  char* xc = w.h;  // [mb, D] bf16
-  // the out-projection gathers the CLS rows: A and the residual read with a row stride of ntok * D
-  GemmArgs proj = linear(w.o, L.wproj, xc, mb, D, D, EPI_BIAS_RESID);
-  proj.bias = L.bproj;
-  proj.resid = w.x;
-  proj.gamma = L.ls1;
-  proj.lda = proj.ldr = (int64_t)ntok * D;
+  const int D = c.dim;
+  // (fp8_cls_bf16: the CLS rows' MLP on the bf16 weights -- the explicit path)
+  const BlockSteps b{m, s, w, L, c.fp8 && c.fp8_cls_bf16 && c.has_cls ? PATH_EXPLICIT : block_path(m)};
+  // resid_fp32: the CLS rows' fp32 residual comes from x32 (strided) and stays in xc32 (compact)
+  const Rows x{w.x, w.x32, ntok}, xc{w.h, w.x32 ? w.xc32 : nullptr, 0};
+  // norm2 of the compact rows goes behind them in w.h (it holds Mp >= mb * ntok + 256 rows); as MX-fp8 its scales go to
+  // w.hs (the layouts depend only on the row count each launch is given)
+  char* hn = w.h + (size_t)round_up(mb, 256) * D * 2;
+  LnFold prod;  // (the tail's producer always finalises the statistics of its rows)
+  prod.part = w.part;
+  prod.part_stride = w.Mp;
+  prod.fin_stats = w.stats;
   int rc;
-  if (c.fp8 && !(c.fp8_cls_bf16 && c.has_cls)) {  // (fp8_cls_bf16: the CLS rows' MLP on the bf16 weights -- the explicit-LayerNorm branch below)
-    // MX-fp8 linears: norm2 of the compact rows goes out as MX-fp8 behind them in w.h (payload) / w.hs (scales: the
-    // layouts depend only on the row count each launch is given), fc1 / fc2 on the block-scaled MFMA at M = mb
-    char* hq = w.h + (size_t)round_up(mb, 256) * D * 2;
-    if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, proj, EPI_BIAS_RESID))) return rc;
-    {
-      Scope sc(m, s, VDR_K_LAYERNORM, 0.0, (double)mb * D * 3);
-      VDR_TRY(launch_ln_mx(xc, L.n2w, L.n2b, c.ln_eps, mb, D, hq, w.hs, s), "layernorm_mx");
-    }
-    if ((rc = gemm_mx(m, s, VDR_K_GEMM_FC1, hq, w.hs, L.w1_q, L.w1_s, L.b1, nullptr, nullptr, w.u, w.us, mb, N1, D, e1))) return rc;
-    return gemm_mx(m, s, VDR_K_GEMM_FC2, w.u, w.us, L.w2_q, L.w2_s, L.b2, xc, L.ls2, xc, nullptr, mb, D, F, EPI_BIAS_RESID);
-  }
-  proj.resid32 = w.x32;  // resid_fp32: the CLS rows' fp32 residual comes from x32 (strided) and stays in xc32 (compact)
-  proj.C32 = w.x32 ? w.xc32 : nullptr;
-  if (m->ln_fuse) {
-    LnFold prod, cons;
-    prod.part = w.part;
-    prod.part_stride = w.Mp;
-    prod.fin_stats = w.stats;
-    if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, proj, EPI_BIAS_RESID, prod))) return rc;
-    if ((rc = ln_consumer(m, s, VDR_K_GEMM_FC1, mb, N1, D, w, &cons))) return rc;
-    cons.colsum = L.s1;
-    GemmArgs fc1 = linear(xc, L.w1_f, w.u, mb, N1, D, e1);
-    fc1.bias = L.t1;
-    if ((rc = gemm(m, s, VDR_K_GEMM_FC1, fc1, e1, cons))) return rc;
-  } else {
-    char* hc = w.h + (size_t)round_up(mb, 256) * D * 2;  // norm2 of the compact rows (w.h holds Mp >= mb * ntok + 256 rows)
-    if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, proj, EPI_BIAS_RESID))) return rc;
-    const bool f32 = proj.C32 != nullptr;
-    if ((rc = layernorm(m, s, VDR_K_LAYERNORM, f32 ? (const void*)proj.C32 : (const void*)xc, !f32, hc, 1, L.n2w, L.n2b, mb, identity_map())))
-      return rc;
-    GemmArgs fc1 = linear(hc, L.w1, w.u, mb, N1, D, e1);
-    fc1.bias = L.b1;
-    if ((rc = gemm(m, s, VDR_K_GEMM_FC1, fc1, e1))) return rc;
-  }
-  GemmArgs fc2 = linear(w.u, L.w2, xc, mb, D, F, EPI_BIAS_RESID);
-  fc2.bias = L.b2;
-  fc2.resid = xc;
-  fc2.gamma = L.ls2;
-  fc2.resid32 = fc2.C32 = proj.C32;
-  return gemm(m, s, VDR_K_GEMM_FC2, fc2, EPI_BIAS_RESID);
+  if ((rc = b.resid_linear(false, mb, w.o, (int64_t)ntok * D, x, xc, b.path == PATH_FOLD ? &prod : nullptr))) return rc;
+  if ((rc = b.norm_linear(true, mb, xc, hn, w.u, 0))) return rc;
+  return b.resid_linear(true, mb, w.u, 0, xc, xc, nullptr);
 }
 
 // vdr_forward_layers: the outputs to write after each block, and the first image of the micro-batch being run
@@ -1140,20 +1188,28 @@ int write_output(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, 
   return VDR_OK;
 }
 
-// cls_tail: the caller only wants the CLS rows (see block_tail_cls); *compact is set when they were left in w.h [mb, D]
-// el (vdr_forward_layers): blocks 0 .. el->last run, and each block's requested outputs are written after it
-int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, const int* lens = nullptr, int len_add = 0,
-               bool cls_tail = false, bool* compact = nullptr, const EmitList* el = nullptr) {
+// What a forward asks of run_blocks beyond the rows themselves
+struct BlockRun {
+  const int* lens = nullptr;   // variable-length token sequences: the valid keys of each (device pointer), plus len_add
+  int len_add = 0;
+  bool cls_tail = false;       // the caller only wants the CLS rows of the last block (see block_tail_cls)
+  const EmitList* el = nullptr;  // vdr_forward_layers: blocks 0 .. el->last run, each block's requested outputs are written after it
+  bool compact = false;        // out: the last block ran its CLS rows only and left them in w.h [mb, D]
+};
+
+// L transformer blocks over x [M = mb*ntok rows]; leaves the result in w.x (r.compact: the CLS rows of it in w.h)
+int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, BlockRun& r) {
   const vdr_config& c = m->cfg;
   const int D = c.dim, F = c.mlp_hidden, H = c.heads;
   const int64_t M = (int64_t)mb * ntok;
-  const int e1 = fc1_epilogue(c), N1 = e1 == EPI_SWIGLU ? 2 * F : F;
+  const int N1 = fc1_epilogue(c) == EPI_SWIGLU ? 2 * F : F;
+  const EmitList* el = r.el;
   int rc;
-  if (compact) *compact = false;
+  r.compact = false;
   // (post-LN blocks keep every row: their last operation is a LayerNorm over the block's own output, also row-wise, but
   // the classifier that uses them is not a throughput path)
   const int nl = el ? el->last + 1 : c.layers;
-  const int tail_at = (cls_tail && compact && c.pre_ln && !c.full_last_block && ntok > 1) ? nl - 1 : -1;
+  const int tail_at = (r.cls_tail && c.pre_ln && !c.full_last_block && ntok > 1) ? nl - 1 : -1;
   // (a block's outputs; the tail's CLS rows are compact)
   auto after = [&](int i, bool cmp) {
     if (el)
@@ -1172,7 +1228,7 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
     }
     Scope sc(m, s, VDR_K_ATTENTION, 4.0 * (double)ntok * ntok * D * mb, 2.0 * (double)M * 4 * D);
     VDR_KNOB int attn_variant = env_int("VDR_ATTN_VARIANT", 0);  // (tuning builds)
-    VDR_TRY(launch_attention(w.qkv, w.o, mb, ntok, H, attn_variant, s, nullptr, lens, len_add, D / H), "attention");
+    VDR_TRY(launch_attention(w.qkv, w.o, mb, ntok, H, attn_variant, s, nullptr, r.lens, r.len_add, D / H), "attention");
     return (int)VDR_OK;
   };
   // vdr_forward_attn_maps: block i's maps, from its qkv, right after its attention
@@ -1184,149 +1240,55 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, co
   };
   // a last block whose only requests are maps stops after its attention
   auto maps_only_last = [&](int i) { return el && i == el->last && el->at[i].empty(); };
-  // block i == tail_at ends after its attention: the rest of it on the CLS rows, then its outputs
-  auto cls_tail_exit = [&](int i, const LayerW& L) {
-    *compact = true;
-    if (int e = block_tail_cls(m, s, w, L, mb, ntok)) return e;
-    return after(i, true);
-  };
-  if (c.fp8) {
-    // BASELINE config 5: qkv / fc1 / fc2 on the block-scaled fp8 MFMA.  LayerNorm writes its output as MX-fp8
-    // (the qkv / fc1 operand), the attention kernel and the fc1 epilogue write theirs as MX-fp8 (the proj / fc2
-    // operands); the residual stream and the attention arithmetic stay bf16 / fp32.
-    // vdr_config.fp8_cls_bf16 (image models with a CLS token; not the variable-length token path)
-    const int ai = m->cur_aux;
-    const bool cls_bf16 = c.fp8_cls_bf16 && c.has_cls && c.patch && ntok > 1 && !lens && ai < (int)m->aux.size() && w.cls_x;
-    for (int i = 0; i < nl; ++i) {
-      const LayerW& L = m->layers[i];
-      {
-        Scope sc(m, s, VDR_K_LAYERNORM, 0.0, (double)M * D * 3);
-        VDR_TRY(launch_ln_mx(w.x, L.n1w, L.n1b, c.ln_eps, M, D, w.h, w.hs, s), "layernorm_mx");
-      }
-      if ((rc = gemm_mx(m, s, VDR_K_GEMM_QKV, w.h, w.hs, L.qkv_q, L.qkv_s, L.bqkv, nullptr, nullptr, w.qkv, nullptr, M, 3 * D, D, EPI_BIAS)))
-        return rc;
-      if ((rc = attention())) return rc;
-      if ((rc = maps_after_attention(i))) return rc;
-      if (maps_only_last(i)) return VDR_OK;
-      if (i == tail_at) return cls_tail_exit(i, L);
-      // the out-projection stays bf16: quantising it too measured 0.987 row cosine at 40 blocks (gate 0.99)
-      GemmArgs proj = linear(w.o, L.wproj, w.x, M, D, D, EPI_BIAS_RESID);
-      proj.bias = L.bproj;
-      proj.resid = w.x;
-      proj.gamma = L.ls1;
-      if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, proj, EPI_BIAS_RESID))) return rc;
-      if (cls_bf16) {
-        // fork: the CLS rows' bf16 MLP runs on the side stream under norm2 / fc1 of every row (nothing writes w.x there)
-        VDR_TRY(hipEventRecord(m->aux_fork[ai], s), "hipEventRecord");
-        VDR_TRY(hipStreamWaitEvent(m->aux[ai], m->aux_fork[ai], 0), "hipStreamWaitEvent");
-        if ((rc = cls_mlp_bf16(m, m->aux[ai], w, L, mb, ntok))) return rc;
-        VDR_TRY(hipEventRecord(m->aux_join[ai], m->aux[ai]), "hipEventRecord");
-      }
-      {
-        Scope sc(m, s, VDR_K_LAYERNORM, 0.0, (double)M * D * 3);
-        VDR_TRY(launch_ln_mx(w.x, L.n2w, L.n2b, c.ln_eps, M, D, w.h, w.hs, s), "layernorm_mx");
-      }
-      if ((rc = gemm_mx(m, s, VDR_K_GEMM_FC1, w.h, w.hs, L.w1_q, L.w1_s, L.b1, nullptr, nullptr, w.u, w.us, M, N1, D, e1))) return rc;
-      // join: fc2 rewrites every row of w.x, the CLS rows' residual reads must be over
-      if (cls_bf16) VDR_TRY(hipStreamWaitEvent(s, m->aux_join[ai], 0), "hipStreamWaitEvent");
-      if ((rc = gemm_mx(m, s, VDR_K_GEMM_FC2, w.u, w.us, L.w2_q, L.w2_s, L.b2, w.x, L.ls2, w.x, nullptr, M, D, F, EPI_BIAS_RESID)))
-        return rc;
-      if (cls_bf16)  // ... and the bf16 result replaces the MX-fp8 one in the CLS rows
-        VDR_TRY(hipMemcpy2DAsync(w.x, (size_t)ntok * D * 2, w.cls_x, (size_t)D * 2, (size_t)D * 2, (size_t)mb, hipMemcpyDeviceToDevice, s),
-                "hipMemcpy2DAsync(CLS rows)");
-      // (the outputs of block i read w.x after that copy: both are on s)
-      if ((rc = after(i, false))) return rc;
-    }
-    return VDR_OK;
-  }
-  if (c.pre_ln && m->ln_fuse) {
-    // LayerNorm never materialised: producers leave (sum, sumsq) partials, a tiny kernel turns them into
-    // (mean, rstd), the consuming GEMM applies them in its epilogue (weights pre-multiplied by gamma).
-    LnFold prod;
-    prod.part = w.part;
-    prod.part_stride = w.Mp;
-    // (the producers finalise the statistics where a consumer reads finalised ones; launches small enough for the ring3 /
-    // ring4 consumers to finalise their own rows from the partials need nothing)
+  const BlockPath path = block_path(m);
+  // The fold's producers (proj, fc2) leave the partials and finalise the statistics where a consumer reads finalised ones;
+  // launches small enough for the ring3 / ring4 consumers to finalise their own rows from the partials need nothing.
+  LnFold fold_prod;
+  if (path == PATH_FOLD) {
+    fold_prod.part = w.part;
+    fold_prod.part_stride = w.Mp;
     if (!ln_stats_in_gemm(VDR_K_GEMM_QKV, M, 3 * D, D / 64) || !ln_stats_in_gemm(VDR_K_GEMM_FC1, M, N1, D / 64))
-      prod.fin_stats = w.stats;
-    for (int i = 0; i < nl; ++i) {
-      const LayerW& L = m->layers[i];
-      LnFold cons;
-      if ((rc = ln_consumer(m, s, VDR_K_GEMM_QKV, M, 3 * D, D, w, &cons))) return rc;
-      cons.colsum = L.sqkv;
-      GemmArgs qkv = linear(w.x, L.wqkv_f, w.qkv, M, 3 * D, D, EPI_BIAS);
-      qkv.bias = L.tqkv;
-      qkv.a_rows = w.Mp;
-      if ((rc = gemm(m, s, VDR_K_GEMM_QKV, qkv, EPI_BIAS, cons))) return rc;
-      if ((rc = attention())) return rc;
-      if ((rc = maps_after_attention(i))) return rc;
-      if (maps_only_last(i)) return VDR_OK;
-      if (i == tail_at) return cls_tail_exit(i, L);
-      GemmArgs proj = linear(w.o, L.wproj, w.x, M, D, D, EPI_BIAS_RESID);
-      proj.bias = L.bproj;
-      proj.resid = w.x;
-      proj.gamma = L.ls1;
-      proj.resid32 = proj.C32 = w.x32;
-      if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, proj, EPI_BIAS_RESID, prod))) return rc;
-      if ((rc = ln_consumer(m, s, VDR_K_GEMM_FC1, M, N1, D, w, &cons))) return rc;
-      cons.colsum = L.s1;
-      GemmArgs fc1 = linear(w.x, L.w1_f, w.u, M, N1, D, e1);
-      fc1.bias = L.t1;
-      fc1.a_rows = w.Mp;
-      if ((rc = gemm(m, s, VDR_K_GEMM_FC1, fc1, e1, cons))) return rc;
-      GemmArgs fc2 = linear(w.u, L.w2, w.x, M, D, F, EPI_BIAS_RESID);
-      fc2.bias = L.b2;
-      fc2.resid = w.x;
-      fc2.gamma = L.ls2;
-      fc2.resid32 = fc2.C32 = w.x32;
-      if ((rc = gemm(m, s, VDR_K_GEMM_FC2, fc2, EPI_BIAS_RESID, prod))) return rc;
-      if ((rc = after(i, false))) return rc;
-    }
-    return VDR_OK;
+      fold_prod.fin_stats = w.stats;
   }
+  const LnFold* prod = path == PATH_FOLD ? &fold_prod : nullptr;
+  // the stream, in place (with its fp32 master copy under resid_fp32); post-LN: the residual linears write w.h, the input
+  // of the LayerNorm that follows each of them back into w.x
+  const Rows x{w.x, w.x32, 0}, sum = c.pre_ln ? x : Rows{w.h, nullptr, 0};
+  // vdr_config.fp8_cls_bf16 (image models with a CLS token; not the variable-length token path): the CLS rows' bf16 MLP
+  // runs on the side stream ai under norm2 / fc1 of every row
+  const int ai = m->cur_aux;
+  const bool cls_bf16 = path == PATH_MX && c.fp8_cls_bf16 && c.has_cls && c.patch && ntok > 1 && !r.lens && ai < (int)m->aux.size() && w.cls_x;
   for (int i = 0; i < nl; ++i) {
     const LayerW& L = m->layers[i];
-    // (resid_fp32: the explicit LayerNorm reads the fp32 master copy of the stream)
-    const void* xin = w.x32 ? (const void*)w.x32 : (const void*)w.x;
-    const int xin_bf16 = w.x32 ? 0 : 1;
-    if (c.pre_ln && (rc = layernorm(m, s, VDR_K_LAYERNORM, xin, xin_bf16, w.h, 1, L.n1w, L.n1b, M, identity_map()))) return rc;
-    GemmArgs qkv = linear(c.pre_ln ? w.h : w.x, L.wqkv, w.qkv, M, 3 * D, D, EPI_BIAS);
-    qkv.bias = L.bqkv;
-    qkv.a_rows = w.Mp;
-    if ((rc = gemm(m, s, VDR_K_GEMM_QKV, qkv, EPI_BIAS))) return rc;
+    const BlockSteps b{m, s, w, L, path};
+    if ((rc = b.norm_linear(false, M, x, w.h, w.qkv, w.Mp))) return rc;
     if ((rc = attention())) return rc;
     if ((rc = maps_after_attention(i))) return rc;
     if (maps_only_last(i)) return VDR_OK;
-    if (i == tail_at) return cls_tail_exit(i, L);
-    // the residual linears: C = x + gamma * (A . W^T + bias), in place (pre-LN, with the fp32 master copy under
-    // resid_fp32) or into w.h (post-LN, the input of the LayerNorm after them)
-    GemmArgs proj = linear(w.o, L.wproj, c.pre_ln ? w.x : w.h, M, D, D, EPI_BIAS_RESID);
-    proj.bias = L.bproj;
-    proj.resid = w.x;
-    proj.gamma = L.ls1;
-    proj.resid32 = proj.C32 = w.x32;
-    GemmArgs fc1 = linear(c.pre_ln ? w.h : w.x, L.w1, w.u, M, N1, D, e1);
-    fc1.bias = L.b1;
-    fc1.a_rows = w.Mp;
-    GemmArgs fc2 = linear(w.u, L.w2, c.pre_ln ? w.x : w.h, M, D, F, EPI_BIAS_RESID);
-    fc2.bias = L.b2;
-    fc2.resid = w.x;
-    fc2.gamma = L.ls2;
-    fc2.resid32 = fc2.C32 = w.x32;
-    if (c.pre_ln) {
-      if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, proj, EPI_BIAS_RESID))) return rc;
-      if ((rc = layernorm(m, s, VDR_K_LAYERNORM, xin, xin_bf16, w.h, 1, L.n2w, L.n2b, M, identity_map()))) return rc;
-      if ((rc = gemm(m, s, VDR_K_GEMM_FC1, fc1, e1))) return rc;
-      if ((rc = gemm(m, s, VDR_K_GEMM_FC2, fc2, EPI_BIAS_RESID))) return rc;
-      if ((rc = after(i, false))) return rc;
-    } else {
-      // nn.TransformerEncoderLayer, norm_first=False: x = LN1(x + SA(x)); x = LN2(x + FF(x))
-      if ((rc = gemm(m, s, VDR_K_GEMM_PROJ, proj, EPI_BIAS_RESID))) return rc;
-      if ((rc = layernorm(m, s, VDR_K_LAYERNORM, w.h, 1, w.x, 1, L.n1w, L.n1b, M, identity_map()))) return rc;
-      if ((rc = gemm(m, s, VDR_K_GEMM_FC1, fc1, e1))) return rc;
-      if ((rc = gemm(m, s, VDR_K_GEMM_FC2, fc2, EPI_BIAS_RESID))) return rc;
-      if ((rc = layernorm(m, s, VDR_K_LAYERNORM, w.h, 1, w.x, 1, L.n2w, L.n2b, M, identity_map()))) return rc;
+    if (i == tail_at) {  // the block ends after its attention: the rest of it on the CLS rows, then its outputs
+      r.compact = true;
+      if ((rc = block_tail_cls(m, s, w, L, mb, ntok))) return rc;
+      return after(i, true);
     }
+    if ((rc = b.resid_linear(false, M, w.o, 0, x, sum, prod))) return rc;
+    if (!c.pre_ln && (rc = layernorm(m, s, VDR_K_LAYERNORM, w.h, 1, w.x, 1, L.n1w, L.n1b, M, identity_map()))) return rc;
+    if (cls_bf16) {
+      // fork: nothing writes w.x between here and fc2
+      VDR_TRY(hipEventRecord(m->aux_fork[ai], s), "hipEventRecord");
+      VDR_TRY(hipStreamWaitEvent(m->aux[ai], m->aux_fork[ai], 0), "hipStreamWaitEvent");
+      if ((rc = cls_mlp_bf16(m, m->aux[ai], w, L, mb, ntok))) return rc;
+      VDR_TRY(hipEventRecord(m->aux_join[ai], m->aux[ai]), "hipEventRecord");
+    }
+    if ((rc = b.norm_linear(true, M, x, w.h, w.u, w.Mp))) return rc;
+    // join: fc2 rewrites every row of w.x, the CLS rows' residual reads must be over
+    if (cls_bf16) VDR_TRY(hipStreamWaitEvent(s, m->aux_join[ai], 0), "hipStreamWaitEvent");
+    if ((rc = b.resid_linear(true, M, w.u, 0, x, sum, prod))) return rc;
+    if (!c.pre_ln && (rc = layernorm(m, s, VDR_K_LAYERNORM, w.h, 1, w.x, 1, L.n2w, L.n2b, M, identity_map()))) return rc;
+    if (cls_bf16)  // ... and the bf16 result replaces the MX-fp8 one in the CLS rows
+      VDR_TRY(hipMemcpy2DAsync(w.x, (size_t)ntok * D * 2, w.cls_x, (size_t)D * 2, (size_t)D * 2, (size_t)mb, hipMemcpyDeviceToDevice, s),
+              "hipMemcpy2DAsync(CLS rows)");
+    // (the outputs of block i read w.x after that copy: both are on s)
+    if ((rc = after(i, false))) return rc;
   }
   return VDR_OK;
 }
@@ -1347,7 +1309,7 @@ hipError_t relpos_products(const void* qkv, const void* table, float* T, int64_t
 
 int run_sam(vdr_model* m, hipStream_t s, const Carve& w, int mb, int out_dtype, char* out, bool tokens_only) {
   const vdr_config& c = m->cfg;
-  const int D = c.dim, F = c.mlp_hidden, H = c.heads, C = c.neck_chans;
+  const int D = c.dim, H = c.heads, C = c.neck_chans;
   const int g = c.img / c.patch, n = g * g, ws = c.window, nw = (g + ws - 1) / ws, wtok = nw * nw * ws * ws;
   const int64_t M = (int64_t)mb * n;
   int rc;
@@ -1356,6 +1318,8 @@ int run_sam(vdr_model* m, hipStream_t s, const Carve& w, int mb, int out_dtype, 
   // padding rows of the windowed MX activation are zero payload (memset above) under zeroed, i.e. finite, scales
   const bool fp8 = c.fp8 != 0;
   if (fp8) VDR_TRY(hipMemsetAsync(w.hs, 0, mx_scale_bytes(w.Mp, D), s), "memset(window padding scales)");
+  const BlockPath path = block_path(m);
+  const Rows x{w.x, w.x32, 0};
   for (int i = 0; i < c.layers; ++i) {
     const LayerW& L = m->layers[i];
     const bool glob = (c.global_mask >> i) & 1;
@@ -1371,26 +1335,9 @@ int run_sam(vdr_model* m, hipStream_t s, const Carve& w, int mb, int out_dtype, 
       if ((rc = gemm_mx(m, s, VDR_K_GEMM_QKV, hbuf, w.hs, L.qkv_q, L.qkv_s, L.bqkv, nullptr, nullptr, w.qkv, nullptr, T, 3 * D, D, EPI_BIAS)))
         return rc;
     } else {
-      LnArgs a{};
-      a.x = w.x;
-      a.in_bf16 = 1;
-      a.y = hbuf;
-      a.out_bf16 = 1;
-      a.gamma = L.n1w;
-      a.beta = L.n1b;
-      a.rows = M;
-      a.D = D;
-      a.eps = c.ln_eps;
-      a.imap = identity_map();
-      a.omap = identity_map();
-      if (!glob) {
-        a.win_ws = ws;
-        a.win_g = g;
-      }
-      {
-        Scope sc(m, s, VDR_K_LAYERNORM, 0.0, (double)M * D * 4);  // (own block: the profiler bracket must close before the GEMM)
-        VDR_TRY(launch_layernorm(a, s), "layernorm(window)");
-      }
+      if ((rc = layernorm(m, s, VDR_K_LAYERNORM, w.x, 1, hbuf, 1, L.n1w, L.n1b, M, identity_map(), nullptr, 0, 0, 0, glob ? 0 : ws,
+                          glob ? 0 : g)))
+        return rc;
       GemmArgs qkv = linear(hbuf, L.wqkv, w.qkv, T, 3 * D, D, EPI_BIAS);
       qkv.bias = L.bqkv;
       qkv.a_rows = w.Mp;
@@ -1419,35 +1366,10 @@ int run_sam(vdr_model* m, hipStream_t s, const Carve& w, int mb, int out_dtype, 
       VDR_TRY(launch_gemm_w(m, ga, EPI_BIAS_RESID, gemm_variant_for(VDR_K_GEMM_PROJ, ga.M, ga.N), s), "proj gemm");
       m->stats_fresh = false;  // (window un-partition scatters the rows: their statistics are finalised by ln_consumer's launch)
     }
-    if (fp8) {
-      {
-        Scope sc(m, s, VDR_K_LAYERNORM, 0.0, (double)M * D * 3);
-        VDR_TRY(launch_ln_mx(w.x, L.n2w, L.n2b, c.ln_eps, M, D, w.hg, w.hs, s), "layernorm_mx");
-      }
-      if ((rc = gemm_mx(m, s, VDR_K_GEMM_FC1, w.hg, w.hs, L.w1_q, L.w1_s, L.b1, nullptr, nullptr, w.u, w.us, M, F, D, EPI_BIAS_GELU)))
-        return rc;
-      if ((rc = gemm_mx(m, s, VDR_K_GEMM_FC2, w.u, w.us, L.w2_q, L.w2_s, L.b2, w.x, nullptr, w.x, nullptr, M, D, F, EPI_BIAS_RESID)))
-        return rc;
-      continue;
-    }
-    GemmArgs fc1;
-    LnFold cons;
-    if (m->ln_fuse) {
-      if ((rc = ln_consumer(m, s, VDR_K_GEMM_FC1, M, F, D, w, &cons))) return rc;
-      cons.colsum = L.s1;
-      fc1 = linear(w.x, L.w1_f, w.u, M, F, D, EPI_BIAS_GELU);
-      fc1.bias = L.t1;
-    } else {
-      if ((rc = layernorm(m, s, VDR_K_LAYERNORM, w.x, 1, w.hg, 1, L.n2w, L.n2b, M, identity_map()))) return rc;
-      fc1 = linear(w.hg, L.w1, w.u, M, F, D, EPI_BIAS_GELU);
-      fc1.bias = L.b1;
-    }
-    fc1.a_rows = w.Mp;
-    if ((rc = gemm(m, s, VDR_K_GEMM_FC1, fc1, EPI_BIAS_GELU, cons))) return rc;
-    GemmArgs fc2 = linear(w.u, L.w2, w.x, M, D, F, EPI_BIAS_RESID);
-    fc2.bias = L.b2;
-    fc2.resid = w.x;
-    if ((rc = gemm(m, s, VDR_K_GEMM_FC2, fc2, EPI_BIAS_RESID))) return rc;
+    // the MLP half is the plain block's (GELU, no LayerScale); fc2 produces no partials: the next block's qkv is not folded
+    const BlockSteps b{m, s, w, L, path};
+    if ((rc = b.norm_linear(true, M, x, w.hg, w.u, w.Mp))) return rc;
+    if ((rc = b.resid_linear(true, M, w.u, 0, x, x, nullptr))) return rc;
   }
   if (tokens_only) {
     Scope sc(m, s, VDR_K_FINAL_LN, 0.0, (double)M * D * 6);
@@ -1936,43 +1858,15 @@ int vdr_forward(vdr_handle m, const void* images, int in_dtype, int batch, void*
       return run_sam(m, s, w, mb, out_dtype, (char*)out + (size_t)b0 * n * (tok ? D : c.neck_chans) * es, tok);
     }
     if ((rc = assemble_stream(m, s, w, mb, ntok))) return rc;
-    bool compact = false;
-    if ((rc = run_blocks(m, s, w, mb, ntok, nullptr, 0, out_mode == VDR_OUT_CLS, &compact))) return rc;
-    return write_output(m, s, w, mb, ntok, o, b0, compact);
+    BlockRun r;
+    r.cls_tail = out_mode == VDR_OUT_CLS;
+    if ((rc = run_blocks(m, s, w, mb, ntok, r))) return rc;
+    return write_output(m, s, w, mb, ntok, o, b0, r.compact);
   });
 }
 
 // vdr_forward_layers and vdr_forward_attn_maps (fn: the name the model refusals carry); the callers have checked the
 // outs / maps arrays themselves
-static int forward_layers_impl(const char* fn, vdr_handle m, const void* images, int in_dtype, int batch, const vdr_layer_out* outs,
-                               int n_outs, const vdr_attn_map* maps, int n_maps, void* workspace, size_t workspace_bytes,
-                               void* stream);
-
-int vdr_forward_layers(vdr_handle m, const void* images, int in_dtype, int batch, const vdr_layer_out* outs, int n_outs,
-                       void* workspace, size_t workspace_bytes, void* stream) {
-  // argument checks that need no model first (they also hold for a null handle), then the model's
-  if (!outs || n_outs <= 0) return fail(m, VDR_ERR_INVALID, "null outs or n_outs <= 0");
-  return forward_layers_impl("vdr_forward_layers", m, images, in_dtype, batch, outs, n_outs, nullptr, 0, workspace, workspace_bytes,
-                             stream);
-}
-
-int vdr_forward_attn_maps(vdr_handle m, const void* images, int in_dtype, int batch, const vdr_layer_out* outs, int n_outs,
-                          const vdr_attn_map* maps, int n_maps, void* workspace, size_t workspace_bytes, void* stream) {
-  // the checks that need no model come first, as vdr_forward_layers orders its own
-  if (!maps || n_maps <= 0) return fail(m, VDR_ERR_INVALID, "null maps or n_maps <= 0");
-  for (int k = 0; k < n_maps; ++k) {
-    const vdr_attn_map& a = maps[k];
-    const std::string at = "maps[" + std::to_string(k) + "]: ";
-    if (!a.out) return fail(m, VDR_ERR_INVALID, at + "null out");
-    if (a.q_rows < 1) return fail(m, VDR_ERR_INVALID, at + "q_rows must be >= 1");
-    if (a.head_mean != 0 && a.head_mean != 1) return fail(m, VDR_ERR_INVALID, at + "head_mean must be 0 or 1");
-    if (a.out_dtype != VDR_F32 && a.out_dtype != VDR_BF16) return fail(m, VDR_ERR_INVALID, at + "out_dtype");
-  }
-  if (n_outs < 0 || (n_outs > 0 && !outs)) return fail(m, VDR_ERR_INVALID, "null outs with n_outs > 0, or n_outs < 0");
-  return forward_layers_impl("vdr_forward_attn_maps", m, images, in_dtype, batch, outs, n_outs, maps, n_maps, workspace,
-                             workspace_bytes, stream);
-}
-
 static int forward_layers_impl(const char* fn, vdr_handle m, const void* images, int in_dtype, int batch, const vdr_layer_out* outs,
                                int n_outs, const vdr_attn_map* maps, int n_maps, void* workspace, size_t workspace_bytes,
                                void* stream) {
@@ -2028,24 +1922,36 @@ static int forward_layers_impl(const char* fn, vdr_handle m, const void* images,
     if ((rc = embed_patches(m, s, w, (const char*)images + (size_t)b0 * img_bytes, in_dtype, mb, nullptr, VDR_F32))) return rc;
     if ((rc = assemble_stream(m, s, w, mb, ntok))) return rc;
     el.b0 = b0;
-    bool compact = false;
-    return run_blocks(m, s, w, mb, ntok, nullptr, 0, cls_only, &compact, &el);
+    BlockRun r;
+    r.cls_tail = cls_only;
+    r.el = &el;
+    return run_blocks(m, s, w, mb, ntok, r);
   });
 }
 
-static int forward_tokens_impl(vdr_handle m, const void* tokens, int in_dtype, int batch, int seq, const int32_t* seq_lens,
-                               void* out, int out_mode, int out_dtype, void* workspace, size_t workspace_bytes, void* stream);
-
-int vdr_forward_tokens(vdr_handle m, const void* tokens, int in_dtype, int batch, int seq, void* out, int out_mode,
-                       int out_dtype, void* workspace, size_t workspace_bytes, void* stream) {
-  return forward_tokens_impl(m, tokens, in_dtype, batch, seq, nullptr, out, out_mode, out_dtype, workspace, workspace_bytes, stream);
+int vdr_forward_layers(vdr_handle m, const void* images, int in_dtype, int batch, const vdr_layer_out* outs, int n_outs,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+  // argument checks that need no model first (they also hold for a null handle), then the model's
+  if (!outs || n_outs <= 0) return fail(m, VDR_ERR_INVALID, "null outs or n_outs <= 0");
+  return forward_layers_impl("vdr_forward_layers", m, images, in_dtype, batch, outs, n_outs, nullptr, 0, workspace, workspace_bytes,
+                             stream);
 }
 
-int vdr_forward_tokens_varlen(vdr_handle m, const void* tokens, int in_dtype, int batch, int max_seq, const int32_t* seq_lens,
-                              void* out, int out_mode, int out_dtype, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!seq_lens) return fail(m, VDR_ERR_INVALID, "seq_lens is null");
-  return forward_tokens_impl(m, tokens, in_dtype, batch, max_seq, seq_lens, out, out_mode, out_dtype, workspace, workspace_bytes,
-                             stream);
+int vdr_forward_attn_maps(vdr_handle m, const void* images, int in_dtype, int batch, const vdr_layer_out* outs, int n_outs,
+                          const vdr_attn_map* maps, int n_maps, void* workspace, size_t workspace_bytes, void* stream) {
+  // the checks that need no model come first, as vdr_forward_layers orders its own
+  if (!maps || n_maps <= 0) return fail(m, VDR_ERR_INVALID, "null maps or n_maps <= 0");
+  for (int k = 0; k < n_maps; ++k) {
+    const vdr_attn_map& a = maps[k];
+    const std::string at = "maps[" + std::to_string(k) + "]: ";
+    if (!a.out) return fail(m, VDR_ERR_INVALID, at + "null out");
+    if (a.q_rows < 1) return fail(m, VDR_ERR_INVALID, at + "q_rows must be >= 1");
+    if (a.head_mean != 0 && a.head_mean != 1) return fail(m, VDR_ERR_INVALID, at + "head_mean must be 0 or 1");
+    if (a.out_dtype != VDR_F32 && a.out_dtype != VDR_BF16) return fail(m, VDR_ERR_INVALID, at + "out_dtype");
+  }
+  if (n_outs < 0 || (n_outs > 0 && !outs)) return fail(m, VDR_ERR_INVALID, "null outs with n_outs > 0, or n_outs < 0");
+  return forward_layers_impl("vdr_forward_attn_maps", m, images, in_dtype, batch, outs, n_outs, maps, n_maps, workspace,
+                             workspace_bytes, stream);
 }
 
 static int forward_tokens_impl(vdr_handle m, const void* tokens, int in_dtype, int batch, int seq, const int32_t* seq_lens,
@@ -2080,9 +1986,24 @@ static int forward_tokens_impl(vdr_handle m, const void* tokens, int in_dtype, i
       Scope sc(m, s, VDR_K_ASSEMBLE, 0.0, (double)M * D * (in_es + 2));
       VDR_TRY(launch_assemble_tokens(tok, in_dtype == VDR_BF16, m->cls, nullptr, w.x, mb, seq, D, ncls, s), "assemble");
     }
-    if ((rc = run_blocks(m, s, w, mb, ntok, seq_lens ? seq_lens + b0 : nullptr, ncls))) return rc;
+    BlockRun r;
+    r.lens = seq_lens ? seq_lens + b0 : nullptr;
+    r.len_add = ncls;
+    if ((rc = run_blocks(m, s, w, mb, ntok, r))) return rc;
     return write_output(m, s, w, mb, ntok, o, b0, false);
   });
+}
+
+int vdr_forward_tokens(vdr_handle m, const void* tokens, int in_dtype, int batch, int seq, void* out, int out_mode,
+                       int out_dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  return forward_tokens_impl(m, tokens, in_dtype, batch, seq, nullptr, out, out_mode, out_dtype, workspace, workspace_bytes, stream);
+}
+
+int vdr_forward_tokens_varlen(vdr_handle m, const void* tokens, int in_dtype, int batch, int max_seq, const int32_t* seq_lens,
+                              void* out, int out_mode, int out_dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!seq_lens) return fail(m, VDR_ERR_INVALID, "seq_lens is null");
+  return forward_tokens_impl(m, tokens, in_dtype, batch, max_seq, seq_lens, out, out_mode, out_dtype, workspace, workspace_bytes,
+                             stream);
 }
 
 // ---- single operators -----------------------------------------------------------------------------
