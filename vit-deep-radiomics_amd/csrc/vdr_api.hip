@@ -1,7 +1,9 @@
 // C ABI of libvdr.so (include/vdr.h): handle, weight packing, forward orchestration, profiler.
-// Host code only; every kernel lives in gemm.hip / attention.hip / rowops.hip.
+// Host code only; every kernel lives in one of the other .hip files of this directory, behind the launch functions of
+// vdr_kernels.h.
 #include <hip/hip_runtime.h>
 
+#include <cassert>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -9,6 +11,8 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/vdr.h"
@@ -44,6 +48,67 @@ struct DeviceGuard {
 };
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// ---- owners: what a handle holds on the device frees itself with the handle (vdr_destroy is `delete`) ------------------------
+// Device memory.  Move-only; alloc() is the only allocation of this file and adds the tail pad every buffer carries
+// (operand loaders read whole lines past the last element).  Which buffer is (re)allocated when is reserve()'s policy.
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p_(std::exchange(o.p_, nullptr)), cap_(std::exchange(o.cap_, 0)) {}
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    std::swap(p_, o.p_);
+    std::swap(cap_, o.cap_);
+    return *this;
+  }
+  ~DevBuf() { (void)free(); }
+  explicit operator bool() const { return p_ != nullptr; }
+  void* get() const { return p_; }
+  template <class T>
+  T* as() const {
+    return static_cast<T*>(p_);
+  }
+  size_t capacity() const { return cap_; }  // bytes asked for (without the pad)
+  hipError_t alloc(size_t bytes) {          // (of an empty buffer)
+    const hipError_t e = hipMalloc(&p_, bytes + 256);
+    if (e != hipSuccess) p_ = nullptr;
+    cap_ = p_ ? bytes : 0;
+    return e;
+  }
+  hipError_t free() {
+    const hipError_t e = p_ ? hipFree(p_) : hipSuccess;
+    p_ = nullptr;
+    cap_ = 0;
+    return e;
+  }
+
+ private:
+  void* p_ = nullptr;
+  size_t cap_ = 0;
+};
+
+// Streams and events: hipStream_t / hipEvent_t are pointers to opaque structs, so unique_ptr owns them as they are
+struct StreamDeleter {
+  void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); }
+};
+struct EventDeleter {
+  void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); }
+};
+using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, StreamDeleter>;
+using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, EventDeleter>;
+
+hipError_t make_stream(Stream& out) {
+  hipStream_t s = nullptr;
+  const hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+  if (e == hipSuccess) out.reset(s);
+  return e;
+}
+hipError_t make_event(Event& out, unsigned flags) {
+  hipEvent_t ev = nullptr;
+  const hipError_t e = hipEventCreateWithFlags(&ev, flags);
+  if (e == hipSuccess) out.reset(ev);
+  return e;
+}
+
 enum WKind { W_VEC_F32, W_MAT_BF16, W_PATCH_BF16, W_W12_BF16, W_W12_BIAS, W_CONV3_BF16 };
 
 struct WSlot {
@@ -51,7 +116,10 @@ struct WSlot {
   WKind kind;
   int64_t numel;      // expected fp32 elements from the caller
   int64_t rows, cols; // logical matrix shape for MAT kinds
-  void* dev = nullptr;
+  DevBuf dev;
+  // where resolve() publishes dev: a field of the vdr_model or of one of its layers (typed by the slot's kind)
+  const float** dst_f = nullptr;
+  const void** dst_v = nullptr;
   bool set = false;
   std::vector<float> host;  // fp32 copy kept until resolve() (LayerNorm folding needs it)
   // SAM encoder built at another input size than its checkpoint: pos_embed (resample = RS_POS) and the rel-pos tables of
@@ -59,28 +127,35 @@ struct WSlot {
   // and resampled into dev by resolve().  src_n: g0 / 2 g0 - 1 of the table in dev_src; 0 = dev holds the loaded table.
   int resample = 0;
   int64_t src_n = 0;
-  void* dev_src = nullptr;
+  DevBuf dev_src;
 };
 enum { RS_NONE = 0, RS_POS = 1, RS_REL = 2 };
 
+// the slots (indices into vdr_model::slots) one LayerNorm fold reads: a linear layer's weight and bias, the LayerNorm's
+struct FoldIn {
+  int w = -1, b = -1, gamma = -1, beta = -1;
+};
+
 struct LayerW {
-  const float *n1w, *n1b, *n2w, *n2b, *bqkv, *bproj, *b1, *b2, *ls1, *ls2;
-  const void *wqkv, *wproj, *w1, *w2;
-  // LayerNorm folded into the consuming GEMM (pre-LN image models): W' = W.diag(gamma) in bf16,
-  // colsum[n] = sum_k W'[n][k], tbias[n] = sum_k beta[k] W[n][k] + b[n]
+  // the loaded weights (set by resolve() from the slots; a weight the config lacks stays null)
+  const float *n1w = nullptr, *n1b = nullptr, *n2w = nullptr, *n2b = nullptr, *bqkv = nullptr, *bproj = nullptr, *b1 = nullptr,
+              *b2 = nullptr, *ls1 = nullptr, *ls2 = nullptr;
+  const void *wqkv = nullptr, *wproj = nullptr, *w1 = nullptr, *w2 = nullptr;
   const float *relh = nullptr, *relw = nullptr;  // SAM decomposed relative position tables
-  void* reltab = nullptr;  // both tables packed as one [relpos_npad(S)][64] bf16 GEMM operand
-  void *wqkv_f = nullptr, *w1_f = nullptr;
+  DevBuf reltab;  // both tables packed as one [relpos_npad(S)][64] bf16 GEMM operand
+  // LayerNorm folded into the consuming GEMM (pre-LN image models): W' = W.diag(gamma) in bf16 (wqkv_f, w1_f),
+  // colsum[n] = sum_k W'[n][k] (sqkv, s1), tbias[n] = sum_k beta[k] W[n][k] + b[n] (tqkv, t1)
+  FoldIn fold_qkv, fold_fc1;
+  DevBuf wqkv_f, w1_f, sqkv, tqkv, s1, t1;
   // fp8 path: MX-fp8 copies (payload, scales) of the qkv / fc1 (w12) / fc2 (w3) weights
-  void *qkv_q = nullptr, *qkv_s = nullptr, *w1_q = nullptr, *w1_s = nullptr, *w2_q = nullptr, *w2_s = nullptr;
-  float *sqkv = nullptr, *tqkv = nullptr, *s1 = nullptr, *t1 = nullptr;
+  DevBuf qkv_q, qkv_s, w1_q, w1_s, w2_q, w2_s;
 };
 
 constexpr int FIN_ROWS = 1 << 16;  // finalisation counters per stream: blocks of >= 64 tile rows, i.e. launches of up to 4 M rows
 
 struct ProfEvent {
-  int cls;
-  hipEvent_t a, b;
+  int cls = 0;
+  Event a, b;
 };
 
 }  // namespace
@@ -93,19 +168,17 @@ struct vdr_model {
   // the loaded pos_embed (pos0) at the native size, else pos_sized [n_tokens, D]: its CLS row and resampled patch rows
   int in_h = 0, in_w = 0;
   const float* pos0 = nullptr;
-  float* pos_sized = nullptr;
-  size_t pos_sized_rows = 0;  // rows pos_sized was allocated for
+  DevBuf pos_sized;  // (grows only)
   // vdr_config_ext: register tokens between the CLS row and the patch rows (pos_sized then holds the per-token-row table
   // [CLS position ; n_reg zero rows ; patch positions] at every size, the native one included) and DINOv3's 2-D RoPE
   // (cos / sin [n_patches][head_dim / 2] of the size in force, rebuilt with the position table)
   int n_reg = 0, rope = 0;
   float rope_theta = 100.0f;
   const float* reg = nullptr;
-  float *rope_cos = nullptr, *rope_sin = nullptr;
-  size_t rope_rows = 0;  // patch rows the RoPE tables were allocated for
+  DevBuf rope_cos, rope_sin;  // (grow only)
   std::vector<WSlot> slots;
   std::map<std::string, int> index;
-  std::vector<LayerW> layers;
+  std::vector<LayerW> layers;  // sized by vdr_create_ext and never resized: the slots point into it
   const void* w_patch = nullptr;
   const void *w_neck0 = nullptr, *w_neck2 = nullptr;
   const float *neck1w = nullptr, *neck1b = nullptr, *neck3w = nullptr, *neck3b = nullptr;
@@ -115,21 +188,21 @@ struct vdr_model {
   bool ln_fuse = false;
   // GEMM weights in the pair-interleaved layout the operand loader wants (gemm_kernels.h), keyed by the row-major
   // device copy they were packed from; built by resolve()
-  std::map<const void*, void*> w_il;
+  std::map<const void*, DevBuf> w_il;
   std::string err;
   // internal streams (cfg.streams > 1)
-  std::vector<hipStream_t> streams;
-  hipEvent_t ev_fork = nullptr;
-  std::vector<hipEvent_t> ev_join;
+  std::vector<Stream> streams;
+  Event ev_fork;
+  std::vector<Event> ev_join;
   // fp8_cls_bf16: one side stream (+ fork / join events) per stream a forward can run on, created by vdr_finalize; the CLS
   // rows' bf16 MLP of a block runs there under the MX-fp8 GEMMs of the other rows
-  std::vector<hipStream_t> aux;
-  std::vector<hipEvent_t> aux_fork, aux_join;
+  std::vector<Stream> aux;
+  std::vector<Event> aux_fork, aux_join;
   int cur_aux = 0;  // index of the stream run_blocks is being called for (set by the forward's micro-batch loop)
   // producer-side LayerNorm finalisation (GemmArgs::fin_stats): zeroed counters, one per block of tile rows and per stream
   // a forward can run on (FIN_ROWS each; the kernels leave them zeroed); stats_fresh: the (mean, rstd) buffer of the
   // workspace in use already holds the statistics of the stream's current contents (set by gemm(), taken by ln_consumer())
-  uint32_t* fin_cnt = nullptr;
+  DevBuf fin_cnt;
   bool stats_fresh = false;
   // profiler
   bool prof = false;
@@ -150,6 +223,9 @@ namespace {
 
 int hip_fail(vdr_handle h, hipError_t e, const char* what);
 
+// the head dims the attention kernels are built for
+bool head_dim_ok(int dh) { return dh == 32 || dh == 64 || dh == 96 || dh == 128; }
+
 // rows in front of the patch rows of an image: the CLS token, then the register tokens
 int prefix_rows(const vdr_model* m) { return (m->cfg.has_cls ? 1 : 0) + m->n_reg; }
 
@@ -163,83 +239,108 @@ int hip_fail(vdr_handle h, hipError_t e, const char* what) {
   return fail(h, VDR_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
-void add_slot(vdr_model* m, const std::string& name, WKind kind, int64_t rows, int64_t cols) {
-  WSlot s;
+// (Re)allocation policies of a handle's buffers.  IF_EMPTY: every load-time copy -- its size is fixed by the config, a
+// reload writes into the buffer it has.  GROW: the tables of the input size in force.  REPLACE: a table kept at the shape
+// it was loaded with.
+enum AllocPolicy { IF_EMPTY, GROW, REPLACE };
+
+int reserve(vdr_model* m, DevBuf& b, size_t bytes, AllocPolicy how, const char* what) {
+  if (b && (how == IF_EMPTY || (how == GROW && b.capacity() >= bytes))) return VDR_OK;
+  if (b) VDR_TRY(b.free(), ("hipFree(" + std::string(what) + ")").c_str());
+  VDR_TRY(b.alloc(bytes), ("hipMalloc(" + std::string(what) + ")").c_str());
+  return VDR_OK;
+}
+
+// appends the slot of one weight the config wants
+WSlot& new_slot(vdr_model* m, const std::string& name, WKind kind, int64_t rows, int64_t cols) {
+  m->index[name] = (int)m->slots.size();
+  m->slots.emplace_back();
+  WSlot& s = m->slots.back();
   s.name = name;
   s.kind = kind;
   s.rows = rows;
   s.cols = cols;
   s.numel = rows * cols;
-  m->index[name] = (int)m->slots.size();
-  m->slots.push_back(s);
+  return s;
+}
+// One weight the config wants, and the field of *m (or of m->layers[i]) that resolve() points at its device copy: the fp32
+// kinds (vectors, tables) through a const float*, the bf16 kinds (matrices) through a const void*.  Returns the slot's index.
+// (The overloads give the typing; the asserts are a developer check only and vanish under NDEBUG.)
+bool fp32_kind(WKind k) { return k == W_VEC_F32 || k == W_W12_BIAS; }
+int add_slot(vdr_model* m, const std::string& name, WKind kind, int64_t rows, int64_t cols, const float** dst) {
+  assert(fp32_kind(kind));
+  new_slot(m, name, kind, rows, cols).dst_f = dst;
+  return (int)m->slots.size() - 1;
+}
+int add_slot(vdr_model* m, const std::string& name, WKind kind, int64_t rows, int64_t cols, const void** dst) {
+  assert(!fp32_kind(kind));
+  new_slot(m, name, kind, rows, cols).dst_v = dst;
+  return (int)m->slots.size() - 1;
 }
 
+// The only place a weight name is spelled.  The ORDER of the slots is observable (vdr_weight_name).
 void build_slots(vdr_model* m) {
   const vdr_config& c = m->cfg;
   const int D = c.dim, F = c.mlp_hidden;
   if (c.patch) {
-    add_slot(m, "patch_embed.proj.weight", W_PATCH_BF16, D, (int64_t)c.in_chans * c.patch * c.patch);
-    add_slot(m, "patch_embed.proj.bias", W_VEC_F32, 1, D);
+    add_slot(m, "patch_embed.proj.weight", W_PATCH_BF16, D, (int64_t)c.in_chans * c.patch * c.patch, &m->w_patch);
+    add_slot(m, "patch_embed.proj.bias", W_VEC_F32, 1, D, &m->b_patch);
   }
-  if (c.has_cls) add_slot(m, "cls_token", W_VEC_F32, 1, D);
-  if (m->n_reg) add_slot(m, "register_tokens", W_VEC_F32, m->n_reg, D);
+  if (c.has_cls) add_slot(m, "cls_token", W_VEC_F32, 1, D, &m->cls);
+  if (m->n_reg) add_slot(m, "register_tokens", W_VEC_F32, m->n_reg, D, &m->reg);
   // (register tokens carry no position: the table is [cls | patches] whatever their number)
-  if (c.has_pos) add_slot(m, "pos_embed", W_VEC_F32, m->n_patches + (c.has_cls ? 1 : 0), D);
+  if (c.has_pos) add_slot(m, "pos_embed", W_VEC_F32, m->n_patches + (c.has_cls ? 1 : 0), D, &m->pos0);
   if (c.has_pos && c.window > 0) m->slots.back().resample = RS_POS;
   if (c.input_ln) {
-    add_slot(m, "input_norm.weight", W_VEC_F32, 1, D);
-    add_slot(m, "input_norm.bias", W_VEC_F32, 1, D);
+    add_slot(m, "input_norm.weight", W_VEC_F32, 1, D, &m->inw);
+    add_slot(m, "input_norm.bias", W_VEC_F32, 1, D, &m->inb);
   }
   for (int i = 0; i < c.layers; ++i) {
     const std::string p = "blocks." + std::to_string(i) + ".";
-    add_slot(m, p + "norm1.weight", W_VEC_F32, 1, D);
-    add_slot(m, p + "norm1.bias", W_VEC_F32, 1, D);
-    add_slot(m, p + "attn.qkv.weight", W_MAT_BF16, 3 * D, D);
-    add_slot(m, p + "attn.qkv.bias", W_VEC_F32, 1, 3 * D);
+    LayerW& L = m->layers[i];
+    L.fold_qkv.gamma = add_slot(m, p + "norm1.weight", W_VEC_F32, 1, D, &L.n1w);
+    L.fold_qkv.beta = add_slot(m, p + "norm1.bias", W_VEC_F32, 1, D, &L.n1b);
+    L.fold_qkv.w = add_slot(m, p + "attn.qkv.weight", W_MAT_BF16, 3 * D, D, &L.wqkv);
+    L.fold_qkv.b = add_slot(m, p + "attn.qkv.bias", W_VEC_F32, 1, 3 * D, &L.bqkv);
     if (c.window > 0) {
       const int size = ((c.global_mask >> i) & 1) ? c.img / c.patch : c.window;
       const int rs = ((c.global_mask >> i) & 1) ? RS_REL : RS_NONE;  // (window tables do not depend on the grid)
-      add_slot(m, p + "attn.rel_pos_h", W_VEC_F32, 2 * size - 1, 64);
+      add_slot(m, p + "attn.rel_pos_h", W_VEC_F32, 2 * size - 1, 64, &L.relh);
       m->slots.back().resample = rs;
-      add_slot(m, p + "attn.rel_pos_w", W_VEC_F32, 2 * size - 1, 64);
+      add_slot(m, p + "attn.rel_pos_w", W_VEC_F32, 2 * size - 1, 64, &L.relw);
       m->slots.back().resample = rs;
     }
-    add_slot(m, p + "attn.proj.weight", W_MAT_BF16, D, D);
-    add_slot(m, p + "attn.proj.bias", W_VEC_F32, 1, D);
-    if (c.layerscale) add_slot(m, p + "ls1.gamma", W_VEC_F32, 1, D);
-    add_slot(m, p + "norm2.weight", W_VEC_F32, 1, D);
-    add_slot(m, p + "norm2.bias", W_VEC_F32, 1, D);
+    add_slot(m, p + "attn.proj.weight", W_MAT_BF16, D, D, &L.wproj);
+    add_slot(m, p + "attn.proj.bias", W_VEC_F32, 1, D, &L.bproj);
+    if (c.layerscale) add_slot(m, p + "ls1.gamma", W_VEC_F32, 1, D, &L.ls1);
+    L.fold_fc1.gamma = add_slot(m, p + "norm2.weight", W_VEC_F32, 1, D, &L.n2w);
+    L.fold_fc1.beta = add_slot(m, p + "norm2.bias", W_VEC_F32, 1, D, &L.n2b);
     if (c.act == VDR_ACT_SWIGLU) {
-      add_slot(m, p + "mlp.w12.weight", W_W12_BF16, 2 * F, D);
-      add_slot(m, p + "mlp.w12.bias", W_W12_BIAS, 1, 2 * F);
-      add_slot(m, p + "mlp.w3.weight", W_MAT_BF16, D, F);
-      add_slot(m, p + "mlp.w3.bias", W_VEC_F32, 1, D);
+      L.fold_fc1.w = add_slot(m, p + "mlp.w12.weight", W_W12_BF16, 2 * F, D, &L.w1);
+      L.fold_fc1.b = add_slot(m, p + "mlp.w12.bias", W_W12_BIAS, 1, 2 * F, &L.b1);
+      add_slot(m, p + "mlp.w3.weight", W_MAT_BF16, D, F, &L.w2);
+      add_slot(m, p + "mlp.w3.bias", W_VEC_F32, 1, D, &L.b2);
     } else {
-      add_slot(m, p + "mlp.fc1.weight", W_MAT_BF16, F, D);
-      add_slot(m, p + "mlp.fc1.bias", W_VEC_F32, 1, F);
-      add_slot(m, p + "mlp.fc2.weight", W_MAT_BF16, D, F);
-      add_slot(m, p + "mlp.fc2.bias", W_VEC_F32, 1, D);
+      L.fold_fc1.w = add_slot(m, p + "mlp.fc1.weight", W_MAT_BF16, F, D, &L.w1);
+      L.fold_fc1.b = add_slot(m, p + "mlp.fc1.bias", W_VEC_F32, 1, F, &L.b1);
+      add_slot(m, p + "mlp.fc2.weight", W_MAT_BF16, D, F, &L.w2);
+      add_slot(m, p + "mlp.fc2.bias", W_VEC_F32, 1, D, &L.b2);
     }
-    if (c.layerscale) add_slot(m, p + "ls2.gamma", W_VEC_F32, 1, D);
+    if (c.layerscale) add_slot(m, p + "ls2.gamma", W_VEC_F32, 1, D, &L.ls2);
   }
   if (c.pre_ln && c.window == 0) {
-    add_slot(m, "norm.weight", W_VEC_F32, 1, D);
-    add_slot(m, "norm.bias", W_VEC_F32, 1, D);
+    add_slot(m, "norm.weight", W_VEC_F32, 1, D, &m->normw);
+    add_slot(m, "norm.bias", W_VEC_F32, 1, D, &m->normb);
   }
   if (c.window > 0) {
     const int C = c.neck_chans;
-    add_slot(m, "neck.0.weight", W_MAT_BF16, C, D);
-    add_slot(m, "neck.1.weight", W_VEC_F32, 1, C);
-    add_slot(m, "neck.1.bias", W_VEC_F32, 1, C);
-    add_slot(m, "neck.2.weight", W_CONV3_BF16, C, (int64_t)C * 9);
-    add_slot(m, "neck.3.weight", W_VEC_F32, 1, C);
-    add_slot(m, "neck.3.bias", W_VEC_F32, 1, C);
+    add_slot(m, "neck.0.weight", W_MAT_BF16, C, D, &m->w_neck0);
+    add_slot(m, "neck.1.weight", W_VEC_F32, 1, C, &m->neck1w);
+    add_slot(m, "neck.1.bias", W_VEC_F32, 1, C, &m->neck1b);
+    add_slot(m, "neck.2.weight", W_CONV3_BF16, C, (int64_t)C * 9, &m->w_neck2);
+    add_slot(m, "neck.3.weight", W_VEC_F32, 1, C, &m->neck3w);
+    add_slot(m, "neck.3.bias", W_VEC_F32, 1, C, &m->neck3b);
   }
-}
-
-const void* dev_of(vdr_model* m, const std::string& name) {
-  auto it = m->index.find(name);
-  return it == m->index.end() ? nullptr : m->slots[it->second].dev;
 }
 
 float bf16_to_f32(uint16_t h) {
@@ -247,11 +348,6 @@ float bf16_to_f32(uint16_t h) {
   float f;
   std::memcpy(&f, &u, 4);
   return f;
-}
-
-const std::vector<float>* host_of(vdr_model* m, const std::string& name) {
-  auto it = m->index.find(name);
-  return it == m->index.end() ? nullptr : &m->slots[it->second].host;
 }
 
 // tuning knobs are read from the environment in tuning builds only (-DVDR_TUNING, `make tuning`); the shipped library
@@ -308,18 +404,19 @@ void fold_ln_host(const float* W, const float* b, const float* gam, const float*
 }
 
 // fold_ln_host + upload
-int fold_ln(vdr_model* m, const std::vector<float>& W, const std::vector<float>& b, const std::vector<float>& gam,
-            const std::vector<float>& bet, int64_t N, int64_t K, bool swiglu, void** wf_dev, float** colsum_dev,
-            float** tbias_dev) {
+int fold_ln(vdr_model* m, const FoldIn& in, int64_t N, int64_t K, bool swiglu, DevBuf& wf_dev, DevBuf& colsum_dev,
+            DevBuf& tbias_dev) {
+  auto host = [&](int slot) { return m->slots[slot].host.data(); };
   std::vector<uint16_t> wf((size_t)N * K);
   std::vector<float> cs(N), tb(N);
-  fold_ln_host(W.data(), b.data(), gam.data(), bet.data(), N, K, swiglu, wf.data(), cs.data(), tb.data());
-  if (!*wf_dev) VDR_TRY(hipMalloc(wf_dev, wf.size() * 2 + 256), "hipMalloc(folded weight)");
-  if (!*colsum_dev) VDR_TRY(hipMalloc((void**)colsum_dev, (size_t)N * 4 + 256), "hipMalloc(colsum)");
-  if (!*tbias_dev) VDR_TRY(hipMalloc((void**)tbias_dev, (size_t)N * 4 + 256), "hipMalloc(tbias)");
-  VDR_TRY(hipMemcpy(*wf_dev, wf.data(), wf.size() * 2, hipMemcpyHostToDevice), "hipMemcpy(folded weight)");
-  VDR_TRY(hipMemcpy(*colsum_dev, cs.data(), (size_t)N * 4, hipMemcpyHostToDevice), "hipMemcpy(colsum)");
-  VDR_TRY(hipMemcpy(*tbias_dev, tb.data(), (size_t)N * 4, hipMemcpyHostToDevice), "hipMemcpy(tbias)");
+  fold_ln_host(host(in.w), host(in.b), host(in.gamma), host(in.beta), N, K, swiglu, wf.data(), cs.data(), tb.data());
+  int rc;
+  if ((rc = reserve(m, wf_dev, wf.size() * 2, IF_EMPTY, "folded weight"))) return rc;
+  if ((rc = reserve(m, colsum_dev, (size_t)N * 4, IF_EMPTY, "colsum"))) return rc;
+  if ((rc = reserve(m, tbias_dev, (size_t)N * 4, IF_EMPTY, "tbias"))) return rc;
+  VDR_TRY(hipMemcpy(wf_dev.get(), wf.data(), wf.size() * 2, hipMemcpyHostToDevice), "hipMemcpy(folded weight)");
+  VDR_TRY(hipMemcpy(colsum_dev.get(), cs.data(), (size_t)N * 4, hipMemcpyHostToDevice), "hipMemcpy(colsum)");
+  VDR_TRY(hipMemcpy(tbias_dev.get(), tb.data(), (size_t)N * 4, hipMemcpyHostToDevice), "hipMemcpy(tbias)");
   return VDR_OK;
 }
 
@@ -327,18 +424,13 @@ int fold_ln(vdr_model* m, const std::vector<float>& W, const std::vector<float>&
 int build_rope_table(vdr_model* m) {
   const vdr_config& c = m->cfg;
   const int half = c.dim / c.heads / 2;
-  VDR_TRY(hipSetDevice(m->device), "hipSetDevice");
   VDR_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");  // (a forward still in flight may read the old tables)
-  if (m->rope_rows < (size_t)m->n_patches) {
-    if (m->rope_cos) VDR_TRY(hipFree(m->rope_cos), "hipFree(RoPE table)");
-    if (m->rope_sin) VDR_TRY(hipFree(m->rope_sin), "hipFree(RoPE table)");
-    m->rope_cos = m->rope_sin = nullptr;
-    m->rope_rows = 0;
-    VDR_TRY(hipMalloc((void**)&m->rope_cos, (size_t)m->n_patches * half * 4 + 256), "hipMalloc(RoPE table)");
-    VDR_TRY(hipMalloc((void**)&m->rope_sin, (size_t)m->n_patches * half * 4 + 256), "hipMalloc(RoPE table)");
-    m->rope_rows = (size_t)m->n_patches;
-  }
-  VDR_TRY(launch_rope2d_table(m->in_h / c.patch, m->in_w / c.patch, 2 * half, m->rope_theta, m->rope_cos, m->rope_sin, nullptr),
+  const size_t bytes = (size_t)m->n_patches * half * 4;
+  int rc;
+  if ((rc = reserve(m, m->rope_cos, bytes, GROW, "RoPE table"))) return rc;
+  if ((rc = reserve(m, m->rope_sin, bytes, GROW, "RoPE table"))) return rc;
+  VDR_TRY(launch_rope2d_table(m->in_h / c.patch, m->in_w / c.patch, 2 * half, m->rope_theta, m->rope_cos.as<float>(),
+                              m->rope_sin.as<float>(), nullptr),
           "rope2d_table");
   VDR_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
   return VDR_OK;
@@ -357,29 +449,38 @@ int build_pos_table(vdr_model* m) {
   const bool native = m->in_h == c.img && m->in_w == c.img;
   if (!c.has_pos || !c.patch || (native && !m->n_reg)) return VDR_OK;
   const int ncls = c.has_cls ? 1 : 0, P = prefix_rows(m), D = c.dim, g0 = c.img / c.patch;
-  VDR_TRY(hipSetDevice(m->device), "hipSetDevice");
   VDR_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");  // (a forward still in flight, on any stream, may read the old table)
-  if (m->pos_sized_rows < (size_t)m->n_tokens) {
-    if (m->pos_sized) VDR_TRY(hipFree(m->pos_sized), "hipFree(pos_embed table)");
-    m->pos_sized = nullptr;
-    m->pos_sized_rows = 0;
-    VDR_TRY(hipMalloc((void**)&m->pos_sized, (size_t)m->n_tokens * D * 4 + 256), "hipMalloc(pos_embed table)");
-    m->pos_sized_rows = (size_t)m->n_tokens;
-  }
-  if (ncls) VDR_TRY(hipMemcpy(m->pos_sized, m->pos0, (size_t)D * 4, hipMemcpyDeviceToDevice), "hipMemcpy(pos_embed CLS row)");
-  if (m->n_reg) VDR_TRY(hipMemset(m->pos_sized + (size_t)ncls * D, 0, (size_t)m->n_reg * D * 4), "hipMemset(register rows)");
+  if (int rc = reserve(m, m->pos_sized, (size_t)m->n_tokens * D * 4, GROW, "pos_embed table")) return rc;
+  float* sized = m->pos_sized.as<float>();
+  if (ncls) VDR_TRY(hipMemcpy(sized, m->pos0, (size_t)D * 4, hipMemcpyDeviceToDevice), "hipMemcpy(pos_embed CLS row)");
+  if (m->n_reg) VDR_TRY(hipMemset(sized + (size_t)ncls * D, 0, (size_t)m->n_reg * D * 4), "hipMemset(register rows)");
   if (native)
-    VDR_TRY(hipMemcpy(m->pos_sized + (size_t)P * D, m->pos0 + (size_t)ncls * D, (size_t)m->n_patches * D * 4, hipMemcpyDeviceToDevice),
+    VDR_TRY(hipMemcpy(sized + (size_t)P * D, m->pos0 + (size_t)ncls * D, (size_t)m->n_patches * D * 4, hipMemcpyDeviceToDevice),
             "hipMemcpy(pos_embed patch rows)");
   else
-    VDR_TRY(launch_pos_interp(m->pos0 + (size_t)ncls * D, g0, g0, D, m->pos_sized + (size_t)P * D, m->in_h / c.patch,
-                              m->in_w / c.patch, nullptr),
+    VDR_TRY(launch_pos_interp(m->pos0 + (size_t)ncls * D, g0, g0, D, sized + (size_t)P * D, m->in_h / c.patch, m->in_w / c.patch,
+                              nullptr),
             "pos_interp");
   VDR_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
-  m->pos = m->pos_sized;
+  m->pos = sized;
   return VDR_OK;
 }
 
+int num_streams(const vdr_model* m) { return m->cfg.streams > 1 ? (m->cfg.streams > 8 ? 8 : m->cfg.streams) : 1; }
+
+// the pair-interleaved copy of GEMM weight w [N][K] bf16 (whole-line operand loads, gemm_kernels.h), kept in w_il under w
+int interleave(vdr_model* m, const void* w, int N, int K, const char* what_buf, const char* what_launch) {
+  auto it = m->w_il.find(w);
+  if (it == m->w_il.end()) {
+    DevBuf b;
+    if (int rc = reserve(m, b, (size_t)N * K * 2, IF_EMPTY, what_buf)) return rc;
+    it = m->w_il.emplace(w, std::move(b)).first;
+  }
+  VDR_TRY(launch_w_interleave(w, it->second.get(), N, K, K, nullptr), what_launch);
+  return VDR_OK;
+}
+
+// vdr_finalize: everything the forward reads is derived from the loaded weights here (the caller holds the DeviceGuard)
 int resolve(vdr_model* m) {
   for (auto& s : m->slots)
     if (!s.set) return fail(m, VDR_ERR_INCOMPLETE, "weight not set: " + s.name);
@@ -388,146 +489,74 @@ int resolve(vdr_model* m) {
       if (s.host.empty())
         return fail(m, VDR_ERR_INCOMPLETE, "weights changed after the first forward: set every weight again (" + s.name + ")");
   const vdr_config& c = m->cfg;
-  // SAM tables loaded at their native shape: resampled to the handle's grid (segment_anything: bicubic pos_embed as
-  // vdr_op_interpolate_pos, get_rel_pos's linear rule as vdr_op_interpolate_rel_pos); the consumers below (rel-pos pack,
-  // forward) run later on the same (null) stream and resolve() synchronises before it returns
+  const int D = c.dim, F = c.mlp_hidden, N1 = c.act == VDR_ACT_SWIGLU ? 2 * F : F;
+  int rc;
   for (auto& sl : m->slots) {
-    if (!sl.src_n) continue;
-    VDR_TRY(hipSetDevice(m->device), "hipSetDevice");
-    if (!sl.dev) VDR_TRY(hipMalloc(&sl.dev, (size_t)sl.numel * 4 + 256), "hipMalloc(resampled table)");
-    if (sl.resample == RS_POS) {
-      const int g = c.img / c.patch;
-      VDR_TRY(launch_pos_interp((const float*)sl.dev_src, (int)sl.src_n, (int)sl.src_n, c.dim, (float*)sl.dev, g, g, nullptr),
-              "pos_interp");
-    } else {
-      VDR_TRY(launch_relpos_interp((const float*)sl.dev_src, (int)sl.src_n, 64, (float*)sl.dev, (int)sl.rows, nullptr),
-              "relpos_interp");
+    // SAM tables loaded at their native shape: resampled to the handle's grid (segment_anything: bicubic pos_embed as
+    // vdr_op_interpolate_pos, get_rel_pos's linear rule as vdr_op_interpolate_rel_pos); the consumers below (rel-pos pack,
+    // forward) run later on the same (null) stream and resolve() synchronises before it returns
+    if (sl.src_n) {
+      if ((rc = reserve(m, sl.dev, (size_t)sl.numel * 4, IF_EMPTY, "resampled table"))) return rc;
+      if (sl.resample == RS_POS) {
+        const int g = c.img / c.patch;
+        VDR_TRY(launch_pos_interp(sl.dev_src.as<float>(), (int)sl.src_n, (int)sl.src_n, c.dim, sl.dev.as<float>(), g, g, nullptr),
+                "pos_interp");
+      } else {
+        VDR_TRY(launch_relpos_interp(sl.dev_src.as<float>(), (int)sl.src_n, 64, sl.dev.as<float>(), (int)sl.rows, nullptr),
+                "relpos_interp");
+      }
     }
+    if (sl.dst_f) *sl.dst_f = sl.dev.as<float>();
+    if (sl.dst_v) *sl.dst_v = sl.dev.get();
   }
-  m->w_patch = dev_of(m, "patch_embed.proj.weight");
-  m->b_patch = (const float*)dev_of(m, "patch_embed.proj.bias");
-  m->cls = (const float*)dev_of(m, "cls_token");
-  m->reg = (const float*)dev_of(m, "register_tokens");
-  m->pos0 = (const float*)dev_of(m, "pos_embed");
-  {
-    const int rc = build_pos_table(m);  // (weights changed: the table of the size in force is rebuilt)
-    if (rc) return rc;
-  }
-  m->inw = (const float*)dev_of(m, "input_norm.weight");
-  m->inb = (const float*)dev_of(m, "input_norm.bias");
-  m->normw = (const float*)dev_of(m, "norm.weight");
-  m->normb = (const float*)dev_of(m, "norm.bias");
-  m->w_neck0 = dev_of(m, "neck.0.weight");
-  m->w_neck2 = dev_of(m, "neck.2.weight");
-  m->neck1w = (const float*)dev_of(m, "neck.1.weight");
-  m->neck1b = (const float*)dev_of(m, "neck.1.bias");
-  m->neck3w = (const float*)dev_of(m, "neck.3.weight");
-  m->neck3b = (const float*)dev_of(m, "neck.3.bias");
-  m->layers.resize(c.layers);
-  for (int i = 0; i < c.layers; ++i) {
-    const std::string p = "blocks." + std::to_string(i) + ".";
-    LayerW& L = m->layers[i];
-    L.n1w = (const float*)dev_of(m, p + "norm1.weight");
-    L.n1b = (const float*)dev_of(m, p + "norm1.bias");
-    L.n2w = (const float*)dev_of(m, p + "norm2.weight");
-    L.n2b = (const float*)dev_of(m, p + "norm2.bias");
-    L.wqkv = dev_of(m, p + "attn.qkv.weight");
-    L.bqkv = (const float*)dev_of(m, p + "attn.qkv.bias");
-    L.wproj = dev_of(m, p + "attn.proj.weight");
-    L.bproj = (const float*)dev_of(m, p + "attn.proj.bias");
-    L.relh = (const float*)dev_of(m, p + "attn.rel_pos_h");
-    L.relw = (const float*)dev_of(m, p + "attn.rel_pos_w");
-    L.ls1 = (const float*)dev_of(m, p + "ls1.gamma");
-    L.ls2 = (const float*)dev_of(m, p + "ls2.gamma");
-    if (c.act == VDR_ACT_SWIGLU) {
-      L.w1 = dev_of(m, p + "mlp.w12.weight");
-      L.b1 = (const float*)dev_of(m, p + "mlp.w12.bias");
-      L.w2 = dev_of(m, p + "mlp.w3.weight");
-      L.b2 = (const float*)dev_of(m, p + "mlp.w3.bias");
-    } else {
-      L.w1 = dev_of(m, p + "mlp.fc1.weight");
-      L.b1 = (const float*)dev_of(m, p + "mlp.fc1.bias");
-      L.w2 = dev_of(m, p + "mlp.fc2.weight");
-      L.b2 = (const float*)dev_of(m, p + "mlp.fc2.bias");
-    }
-  }
+  if ((rc = build_pos_table(m))) return rc;  // (weights changed: the table of the size in force is rebuilt)
   m->ln_fuse = ln_fusion_wanted(m);
   if (m->ln_fuse) {
-    VDR_TRY(hipSetDevice(m->device), "hipSetDevice");
-    const int64_t D = c.dim, F = c.mlp_hidden;
-    for (int i = 0; i < c.layers; ++i) {
-      const std::string p = "blocks." + std::to_string(i) + ".";
-      LayerW& L = m->layers[i];
-      int rc = fold_ln(m, *host_of(m, p + "attn.qkv.weight"), *host_of(m, p + "attn.qkv.bias"), *host_of(m, p + "norm1.weight"),
-                       *host_of(m, p + "norm1.bias"), 3 * D, D, false, &L.wqkv_f, &L.sqkv, &L.tqkv);
-      if (rc) return rc;
-      if (c.act == VDR_ACT_SWIGLU)
-        rc = fold_ln(m, *host_of(m, p + "mlp.w12.weight"), *host_of(m, p + "mlp.w12.bias"), *host_of(m, p + "norm2.weight"),
-                     *host_of(m, p + "norm2.bias"), 2 * F, D, true, &L.w1_f, &L.s1, &L.t1);
-      else
-        rc = fold_ln(m, *host_of(m, p + "mlp.fc1.weight"), *host_of(m, p + "mlp.fc1.bias"), *host_of(m, p + "norm2.weight"),
-                     *host_of(m, p + "norm2.bias"), F, D, false, &L.w1_f, &L.s1, &L.t1);
-      if (rc) return rc;
+    for (LayerW& L : m->layers) {
+      if ((rc = fold_ln(m, L.fold_qkv, 3 * D, D, false, L.wqkv_f, L.sqkv, L.tqkv))) return rc;
+      if ((rc = fold_ln(m, L.fold_fc1, N1, D, c.act == VDR_ACT_SWIGLU, L.w1_f, L.s1, L.t1))) return rc;
     }
   }
   if (c.fp8) {
-    VDR_TRY(hipSetDevice(m->device), "hipSetDevice");
-    const int D = c.dim, F = c.mlp_hidden;
-    const int N1 = c.act == VDR_ACT_SWIGLU ? 2 * F : F;
-    auto quant = [&](const void* wdev, int N, int K, void** q, void** sc) -> int {
-      if (!*q) VDR_TRY(hipMalloc(q, (size_t)N * K + 256), "hipMalloc(fp8 weight)");
-      if (!*sc) VDR_TRY(hipMalloc(sc, mx_scale_bytes(N, K) + 256), "hipMalloc(fp8 weight scales)");
-      VDR_TRY(hipMemset(*sc, 0, mx_scale_bytes(N, K)), "hipMemset(fp8 weight scales)");
-      VDR_TRY(launch_mx_quant(wdev, N, K, K, *q, *sc, nullptr), "mx_quant(weight)");
-      return VDR_OK;
-    };
-    // the e4m3 payloads go to the packed (pair-interleaved) layout too: as bytes, [N][K] fp8 is [N][K/2] bf16, and a
-    // 32-element bf16 block is one 64-element MX unit
-    auto pack8 = [&](void* q, int N, int K) -> int {
-      void*& dst = m->w_il[q];
-      if (!dst) VDR_TRY(hipMalloc(&dst, (size_t)N * K + 256), "hipMalloc(interleaved fp8 weight)");
-      VDR_TRY(launch_w_interleave(q, dst, N, K / 2, K / 2, nullptr), "w_interleave(fp8)");
-      return VDR_OK;
-    };
-    for (int i = 0; i < c.layers; ++i) {
-      LayerW& L = m->layers[i];
+    // MX-fp8 copy of a weight; the e4m3 payload goes to the packed (pair-interleaved) layout too: as bytes, [N][K] fp8 is
+    // [N][K/2] bf16, and a 32-element bf16 block is one 64-element MX unit
+    auto quant = [&](const void* wdev, int N, int K, DevBuf& q, DevBuf& sc) -> int {
       int rc;
-      if ((rc = quant(L.wqkv, 3 * D, D, &L.qkv_q, &L.qkv_s)) || (rc = pack8(L.qkv_q, 3 * D, D))) return rc;
-      if ((rc = quant(L.w1, N1, D, &L.w1_q, &L.w1_s)) || (rc = pack8(L.w1_q, N1, D))) return rc;
-      if ((rc = quant(L.w2, D, F, &L.w2_q, &L.w2_s)) || (rc = pack8(L.w2_q, D, F))) return rc;
-    }
+      if ((rc = reserve(m, q, (size_t)N * K, IF_EMPTY, "fp8 weight")) ||
+          (rc = reserve(m, sc, mx_scale_bytes(N, K), IF_EMPTY, "fp8 weight scales")))
+        return rc;
+      VDR_TRY(hipMemset(sc.get(), 0, mx_scale_bytes(N, K)), "hipMemset(fp8 weight scales)");
+      VDR_TRY(launch_mx_quant(wdev, N, K, K, q.get(), sc.get(), nullptr), "mx_quant(weight)");
+      return interleave(m, q.get(), N, K / 2, "interleaved fp8 weight", "w_interleave(fp8)");
+    };
+    for (LayerW& L : m->layers)
+      if ((rc = quant(L.wqkv, 3 * D, D, L.qkv_q, L.qkv_s)) || (rc = quant(L.w1, N1, D, L.w1_q, L.w1_s)) ||
+          (rc = quant(L.w2, D, F, L.w2_q, L.w2_s)))
+        return rc;
     VDR_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
   }
   if (c.window > 0) {
-    VDR_TRY(hipSetDevice(m->device), "hipSetDevice");
     const int g = c.img / c.patch;
     for (int i = 0; i < c.layers; ++i) {
       LayerW& L = m->layers[i];
       const int S = (c.global_mask >> i) & 1 ? g : c.window;
-      if (!L.reltab) VDR_TRY(hipMalloc(&L.reltab, (size_t)relpos_npad(S) * 64 * 2 + 256), "hipMalloc(rel-pos table)");
-      VDR_TRY(launch_relpos_pack(L.relh, L.relw, L.reltab, S, nullptr), "relpos_pack");
+      if ((rc = reserve(m, L.reltab, (size_t)relpos_npad(S) * 64 * 2, IF_EMPTY, "rel-pos table"))) return rc;
+      VDR_TRY(launch_relpos_pack(L.relh, L.relw, L.reltab.get(), S, nullptr), "relpos_pack");
     }
     VDR_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
   }
   {
-    // pair-interleaved copies of every GEMM weight (whole-line operand loads, gemm_kernels.h)
-    VDR_TRY(hipSetDevice(m->device), "hipSetDevice");
-    const int D = c.dim, F = c.mlp_hidden;
-    const int N1 = c.act == VDR_ACT_SWIGLU ? 2 * F : F;
+    // pair-interleaved copies of every GEMM weight the forward multiplies by
     auto pack = [&](const void* w, int N, int K) -> int {
       if (!w || (N & 1) || (K & 31)) return VDR_OK;
-      void*& dst = m->w_il[w];
-      if (!dst) VDR_TRY(hipMalloc(&dst, (size_t)N * K * 2 + 256), "hipMalloc(interleaved weight)");
-      VDR_TRY(launch_w_interleave(w, dst, N, K, K, nullptr), "w_interleave");
-      return VDR_OK;
+      return interleave(m, w, N, K, "interleaved weight", "w_interleave");
     };
-    int rc = VDR_OK;
     if (c.patch && (rc = pack(m->w_patch, D, m->Kp))) return rc;
     for (int i = 0; i < c.layers && !c.fp8; ++i) {
       const LayerW& L = m->layers[i];
-      if ((rc = pack(L.wqkv, 3 * D, D)) || (rc = pack(L.wqkv_f, 3 * D, D))) return rc;  // (SAM blocks use the unfolded qkv)
+      if ((rc = pack(L.wqkv, 3 * D, D)) || (rc = pack(L.wqkv_f.get(), 3 * D, D))) return rc;  // (SAM blocks use the unfolded qkv)
       if ((rc = pack(L.wproj, D, D))) return rc;
-      if ((rc = pack(L.w1, N1, D)) || (rc = pack(L.w1_f, N1, D))) return rc;
+      if ((rc = pack(L.w1, N1, D)) || (rc = pack(L.w1_f.get(), N1, D))) return rc;
       if ((rc = pack(L.w2, D, F))) return rc;
     }
     if (c.fp8)  // the out-projection stays bf16 on the fp8 path
@@ -536,16 +565,15 @@ int resolve(vdr_model* m) {
     if (c.fp8 && c.fp8_cls_bf16 && c.has_cls) {  // the CLS rows' MLP runs on the bf16 weights
       for (int i = 0; i < c.layers; ++i)
         if ((rc = pack(m->layers[i].w1, N1, D)) || (rc = pack(m->layers[i].w2, D, F))) return rc;
-      const size_t ns = (size_t)(c.streams > 1 ? (c.streams > 8 ? 8 : c.streams) : 1);
-      while (m->aux.size() < ns) {
-        hipStream_t st;
-        hipEvent_t ea, eb;
-        VDR_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreate(CLS side stream)");
-        VDR_TRY(hipEventCreateWithFlags(&ea, hipEventDisableTiming), "hipEventCreate");
-        VDR_TRY(hipEventCreateWithFlags(&eb, hipEventDisableTiming), "hipEventCreate");
-        m->aux.push_back(st);
-        m->aux_fork.push_back(ea);
-        m->aux_join.push_back(eb);
+      while (m->aux.size() < (size_t)num_streams(m)) {
+        Stream st;
+        Event ea, eb;
+        VDR_TRY(make_stream(st), "hipStreamCreate(CLS side stream)");
+        VDR_TRY(make_event(ea, hipEventDisableTiming), "hipEventCreate");
+        VDR_TRY(make_event(eb, hipEventDisableTiming), "hipEventCreate");
+        m->aux.push_back(std::move(st));
+        m->aux_fork.push_back(std::move(ea));
+        m->aux_join.push_back(std::move(eb));
       }
     }
     if (c.window > 0) {
@@ -554,9 +582,9 @@ int resolve(vdr_model* m) {
     }
     VDR_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
   }
-  if (!m->fin_cnt) {
-    VDR_TRY(hipMalloc(&m->fin_cnt, (size_t)8 * FIN_ROWS * 4), "hipMalloc(LayerNorm finalisation counters)");
-    VDR_TRY(hipMemset(m->fin_cnt, 0, (size_t)8 * FIN_ROWS * 4), "hipMemset");
+  if (!m->fin_cnt) {  // (once per handle: the kernels leave the counters zeroed, so a reload skips the memset and the sync)
+    if ((rc = reserve(m, m->fin_cnt, (size_t)8 * FIN_ROWS * 4, IF_EMPTY, "LayerNorm finalisation counters"))) return rc;
+    VDR_TRY(hipMemset(m->fin_cnt.get(), 0, (size_t)8 * FIN_ROWS * 4), "hipMemset");
     VDR_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
   }
   for (auto& sl : m->slots) std::vector<float>().swap(sl.host);  // host copies are no longer needed
@@ -586,7 +614,7 @@ GemmArgs linear(const void* A, const void* W, void* C, int64_t M, int N, int K, 
 void use_interleaved(const vdr_model* m, GemmArgs& g) {
   auto it = m->w_il.find(g.W);
   if (it != m->w_il.end()) {
-    g.W = it->second;
+    g.W = it->second.get();
     g.w_interleaved = 1;
   }
 }
@@ -673,8 +701,6 @@ Carve carve(const vdr_model* m, char* base, int mb, int ntok) {
   return w;
 }
 
-int num_streams(const vdr_model* m) { return m->cfg.streams > 1 ? (m->cfg.streams > 8 ? 8 : m->cfg.streams) : 1; }
-
 int default_micro_batch(const vdr_model* m, int batch) {
   if (m->cfg.micro_batch > 0) return m->cfg.micro_batch < batch ? m->cfg.micro_batch : batch;
   const int ns = num_streams(m);
@@ -689,14 +715,14 @@ int fork_streams(vdr_model* m, hipStream_t caller) {
     m->streams.resize(ns);
     m->ev_join.resize(ns);
     for (int i = 0; i < ns; ++i) {
-      if (hipStreamCreateWithFlags(&m->streams[i], hipStreamNonBlocking) != hipSuccess) return VDR_ERR_HIP;
-      if (hipEventCreateWithFlags(&m->ev_join[i], hipEventDisableTiming) != hipSuccess) return VDR_ERR_HIP;
+      if (make_stream(m->streams[i]) != hipSuccess) return VDR_ERR_HIP;
+      if (make_event(m->ev_join[i], hipEventDisableTiming) != hipSuccess) return VDR_ERR_HIP;
     }
-    if (hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming) != hipSuccess) return VDR_ERR_HIP;
+    if (make_event(m->ev_fork, hipEventDisableTiming) != hipSuccess) return VDR_ERR_HIP;
   }
-  if (hipEventRecord(m->ev_fork, caller) != hipSuccess) return VDR_ERR_HIP;
+  if (hipEventRecord(m->ev_fork.get(), caller) != hipSuccess) return VDR_ERR_HIP;
   for (int i = 0; i < ns; ++i)
-    if (hipStreamWaitEvent(m->streams[i], m->ev_fork, 0) != hipSuccess) return VDR_ERR_HIP;
+    if (hipStreamWaitEvent(m->streams[i].get(), m->ev_fork.get(), 0) != hipSuccess) return VDR_ERR_HIP;
   return VDR_OK;
 }
 
@@ -705,8 +731,8 @@ int join_streams(vdr_model* m, hipStream_t caller) {
   const int ns = num_streams(m);
   if (ns == 1) return VDR_OK;
   for (int i = 0; i < ns; ++i) {
-    if (hipEventRecord(m->ev_join[i], m->streams[i]) != hipSuccess) return VDR_ERR_HIP;
-    if (hipStreamWaitEvent(caller, m->ev_join[i], 0) != hipSuccess) return VDR_ERR_HIP;
+    if (hipEventRecord(m->ev_join[i].get(), m->streams[i].get()) != hipSuccess) return VDR_ERR_HIP;
+    if (hipStreamWaitEvent(caller, m->ev_join[i].get(), 0) != hipSuccess) return VDR_ERR_HIP;
   }
   return VDR_OK;
 }
@@ -724,22 +750,22 @@ struct Scope {  // (m = nullptr: an op entry point, nothing is booked)
     on = (m->prof_mask >> cls) & 1u;
     if (!on) return;
     if (!m->ev_free.empty()) {
-      e = m->ev_free.back();
+      e = std::move(m->ev_free.back());
       m->ev_free.pop_back();
     } else {
-      hipEventCreate(&e.a);
-      hipEventCreate(&e.b);
+      (void)make_event(e.a, hipEventDefault);
+      (void)make_event(e.b, hipEventDefault);
     }
     e.cls = cls;
     m->p_flops[cls] += flops;
     m->p_bytes[cls] += bytes;
     m->p_launch[cls] += 1;
-    hipEventRecord(e.a, s);
+    hipEventRecord(e.a.get(), s);
   }
   ~Scope() {
     if (!on) return;
-    hipEventRecord(e.b, s);
-    m->ev_used.push_back(e);
+    hipEventRecord(e.b.get(), s);
+    m->ev_used.push_back(std::move(e));
   }
 };
 
@@ -909,7 +935,7 @@ int gemm(vdr_model* m, hipStream_t s, int cls, GemmArgs g, int epi, const LnFold
   const bool fin = ln.fin_stats && ln.part && m->fin_cnt && m->cfg.ln_fin_fused && ring4_variant(variant) && epi == EPI_BIAS_RESID &&
                    (g.M + 63) / 64 <= FIN_ROWS;
   LnFold lnf = ln;
-  lnf.fin_cnt = fin ? m->fin_cnt + (size_t)m->cur_aux * FIN_ROWS : nullptr;
+  lnf.fin_cnt = fin ? m->fin_cnt.as<uint32_t>() + (size_t)m->cur_aux * FIN_ROWS : nullptr;
   if (fin) lnf.eps = m->cfg.ln_eps;
   set_ln_fold(g, lnf);
   const double outw = epi == EPI_SWIGLU ? g.N / 2 : g.N;
@@ -1025,16 +1051,16 @@ struct BlockSteps {
         Scope sc(m, s, VDR_K_LAYERNORM, 0.0, (double)M * D * 3);  // (own block: the profiler bracket must close before the GEMM)
         VDR_TRY(launch_ln_mx(in.x, nw, nb, c.ln_eps, M, D, h, w.hs, s), "layernorm_mx");
       }
-      return gemm_mx(m, s, cls, h, w.hs, fc1 ? L.w1_q : L.qkv_q, fc1 ? L.w1_s : L.qkv_s, fc1 ? L.b1 : L.bqkv, nullptr, nullptr, out,
+      return gemm_mx(m, s, cls, h, w.hs, (fc1 ? L.w1_q : L.qkv_q).get(), (fc1 ? L.w1_s : L.qkv_s).get(), fc1 ? L.b1 : L.bqkv, nullptr, nullptr, out,
                      fc1 ? w.us : nullptr, M, N, D, epi);
     }
     GemmArgs g;
     LnFold cons;
     if (path == PATH_FOLD) {
       if ((rc = ln_consumer(m, s, cls, M, N, D, w, &cons))) return rc;
-      cons.colsum = fc1 ? L.s1 : L.sqkv;
-      g = linear(in.x, fc1 ? L.w1_f : L.wqkv_f, out, M, N, D, epi);
-      g.bias = fc1 ? L.t1 : L.tqkv;
+      cons.colsum = (fc1 ? L.s1 : L.sqkv).as<float>();
+      g = linear(in.x, (fc1 ? L.w1_f : L.wqkv_f).get(), out, M, N, D, epi);
+      g.bias = (fc1 ? L.t1 : L.tqkv).as<float>();
     } else {
       // (resid_fp32: the explicit LayerNorm reads the fp32 master copy of the stream)
       if (c.pre_ln && (rc = layernorm(m, s, VDR_K_LAYERNORM, in.x32 ? (const void*)in.x32 : in.x, !in.x32, h, 1, nw, nb, M,
@@ -1055,7 +1081,7 @@ struct BlockSteps {
     const int D = c.dim, K = fc2 ? c.mlp_hidden : D, cls = fc2 ? VDR_K_GEMM_FC2 : VDR_K_GEMM_PROJ;
     const float* gamma = fc2 ? L.ls2 : L.ls1;  // (LayerScale; null without)
     if (path == PATH_MX && fc2)
-      return gemm_mx(m, s, cls, A, w.us, L.w2_q, L.w2_s, L.b2, in.x, gamma, out.x, nullptr, M, D, K, EPI_BIAS_RESID);
+      return gemm_mx(m, s, cls, A, w.us, L.w2_q.get(), L.w2_s.get(), L.b2, in.x, gamma, out.x, nullptr, M, D, K, EPI_BIAS_RESID);
     // (the out-projection stays bf16 on the MX path: quantising it too measured 0.987 row cosine at 40 blocks, gate 0.99)
     GemmArgs g = linear(A, fc2 ? L.w2 : L.wproj, out.x, M, D, K, EPI_BIAS_RESID);
     g.bias = fc2 ? L.b2 : L.bproj;
@@ -1224,7 +1250,7 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, Bl
       const int P = prefix_rows(m);
       const double el = (double)mb * (ntok - P) * 2 * D;  // q and k elements
       Scope sc(m, s, VDR_K_ASSEMBLE, 3.0 * el, 4.0 * el);
-      VDR_TRY(launch_rope2d(w.qkv, mb, ntok, P, H, D / H, m->rope_cos, m->rope_sin, s), "rope2d");
+      VDR_TRY(launch_rope2d(w.qkv, mb, ntok, P, H, D / H, m->rope_cos.as<float>(), m->rope_sin.as<float>(), s), "rope2d");
     }
     Scope sc(m, s, VDR_K_ATTENTION, 4.0 * (double)ntok * ntok * D * mb, 2.0 * (double)M * 4 * D);
     VDR_KNOB int attn_variant = env_int("VDR_ATTN_VARIANT", 0);  // (tuning builds)
@@ -1274,14 +1300,14 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, Bl
     if (!c.pre_ln && (rc = layernorm(m, s, VDR_K_LAYERNORM, w.h, 1, w.x, 1, L.n1w, L.n1b, M, identity_map()))) return rc;
     if (cls_bf16) {
       // fork: nothing writes w.x between here and fc2
-      VDR_TRY(hipEventRecord(m->aux_fork[ai], s), "hipEventRecord");
-      VDR_TRY(hipStreamWaitEvent(m->aux[ai], m->aux_fork[ai], 0), "hipStreamWaitEvent");
-      if ((rc = cls_mlp_bf16(m, m->aux[ai], w, L, mb, ntok))) return rc;
-      VDR_TRY(hipEventRecord(m->aux_join[ai], m->aux[ai]), "hipEventRecord");
+      VDR_TRY(hipEventRecord(m->aux_fork[ai].get(), s), "hipEventRecord");
+      VDR_TRY(hipStreamWaitEvent(m->aux[ai].get(), m->aux_fork[ai].get(), 0), "hipStreamWaitEvent");
+      if ((rc = cls_mlp_bf16(m, m->aux[ai].get(), w, L, mb, ntok))) return rc;
+      VDR_TRY(hipEventRecord(m->aux_join[ai].get(), m->aux[ai].get()), "hipEventRecord");
     }
     if ((rc = b.norm_linear(true, M, x, w.h, w.u, w.Mp))) return rc;
     // join: fc2 rewrites every row of w.x, the CLS rows' residual reads must be over
-    if (cls_bf16) VDR_TRY(hipStreamWaitEvent(s, m->aux_join[ai], 0), "hipStreamWaitEvent");
+    if (cls_bf16) VDR_TRY(hipStreamWaitEvent(s, m->aux_join[ai].get(), 0), "hipStreamWaitEvent");
     if ((rc = b.resid_linear(true, M, w.u, 0, x, sum, prod))) return rc;
     if (!c.pre_ln && (rc = layernorm(m, s, VDR_K_LAYERNORM, w.h, 1, w.x, 1, L.n2w, L.n2b, M, identity_map()))) return rc;
     if (cls_bf16)  // ... and the bf16 result replaces the MX-fp8 one in the CLS rows
@@ -1332,7 +1358,7 @@ int run_sam(vdr_model* m, hipStream_t s, const Carve& w, int mb, int out_dtype, 
         Scope sc(m, s, VDR_K_LAYERNORM, 0.0, (double)M * D * 3);
         VDR_TRY(launch_ln_mx(w.x, L.n1w, L.n1b, c.ln_eps, M, D, hbuf, w.hs, s, glob ? 0 : ws, g, T), "layernorm_mx(window)");
       }
-      if ((rc = gemm_mx(m, s, VDR_K_GEMM_QKV, hbuf, w.hs, L.qkv_q, L.qkv_s, L.bqkv, nullptr, nullptr, w.qkv, nullptr, T, 3 * D, D, EPI_BIAS)))
+      if ((rc = gemm_mx(m, s, VDR_K_GEMM_QKV, hbuf, w.hs, L.qkv_q.get(), L.qkv_s.get(), L.bqkv, nullptr, nullptr, w.qkv, nullptr, T, 3 * D, D, EPI_BIAS)))
         return rc;
     } else {
       if ((rc = layernorm(m, s, VDR_K_LAYERNORM, w.x, 1, hbuf, 1, L.n1w, L.n1b, M, identity_map(), nullptr, 0, 0, 0, glob ? 0 : ws,
@@ -1346,7 +1372,7 @@ int run_sam(vdr_model* m, hipStream_t s, const Carve& w, int mb, int out_dtype, 
     {
       Scope sc(m, s, VDR_K_ATTENTION, 4.0 * (double)S * S * S * S * 64.0 * H * nb + 2.0 * T * H * relpos_npad(S) * 64,
                2.0 * (double)T * 4 * D);
-      VDR_TRY(relpos_products(w.qkv, L.reltab, w.rel, T, S, H, s), "relpos");
+      VDR_TRY(relpos_products(w.qkv, L.reltab.get(), w.rel, T, S, H, s), "relpos");
       VDR_TRY(launch_attention_relpos(w.qkv, w.rel, w.o, nb, S, H, s, glob ? env_int("VDR_RELPOS_ANY", 0) : 0), "attention_relpos");
     }
     {
@@ -1479,7 +1505,7 @@ int run_micro_batches(vdr_model* m, int batch, int ntok, void* workspace, size_t
     const int si = chunk % ns;
     m->cur_aux = si;
     m->stats_fresh = false;  // (nothing has finalised the statistics of this micro-batch yet)
-    hipStream_t s = ns == 1 ? caller : m->streams[si];
+    hipStream_t s = ns == 1 ? caller : m->streams[si].get();
     const Carve w = carve(m, (char*)workspace + si * per_ws, mb_max, ntok);
     if ((rc = body(s, w, b0, mb))) return rc;
   }
@@ -1537,7 +1563,7 @@ int vdr_create_ext(const vdr_config* cfg, const vdr_config_ext* ext, int device,
     return fail(nullptr, VDR_ERR_INVALID, "dim/heads/layers/mlp_hidden must be positive");
   {
     const int dh = c.dim / c.heads;
-    if (c.dim % c.heads || (dh != 32 && dh != 64 && dh != 96 && dh != 128))
+    if (c.dim % c.heads || !head_dim_ok(dh))
       return fail(nullptr, VDR_ERR_UNSUPPORTED, "head dim must be 32, 64, 96 or 128 (dim == head dim * heads)");
     // the MX-fp8 attention output and its scales are laid out per 64 channels; the SAM rel-pos tables are [2S-1, 64]
     if (dh != 64 && c.fp8) return fail(nullptr, VDR_ERR_UNSUPPORTED, "fp8 = 1 needs head dim 64");
@@ -1609,6 +1635,7 @@ int vdr_create_ext(const vdr_config* cfg, const vdr_config_ext* ext, int device,
     m->Kp = round_up(c.in_chans * c.patch * c.patch, 64);
     m->in_h = m->in_w = c.img;
   }
+  m->layers.resize(c.layers);  // (before build_slots: the slots point into it)
   build_slots(m.get());
   *out = m.release();
   return VDR_OK;
@@ -1617,42 +1644,7 @@ int vdr_create_ext(const vdr_config* cfg, const vdr_config_ext* ext, int device,
 void vdr_destroy(vdr_handle h) {
   if (!h) return;
   DeviceGuard dg(h->device);
-  for (auto& s : h->slots) {
-    if (s.dev) hipFree(s.dev);
-    if (s.dev_src) hipFree(s.dev_src);
-  }
-  for (auto& L : h->layers) {
-    if (L.wqkv_f) hipFree(L.wqkv_f);
-    if (L.reltab) hipFree(L.reltab);
-    for (void* q : {L.qkv_q, L.qkv_s, L.w1_q, L.w1_s, L.w2_q, L.w2_s})
-      if (q) hipFree(q);
-    if (L.w1_f) hipFree(L.w1_f);
-    if (L.sqkv) hipFree(L.sqkv);
-    if (L.tqkv) hipFree(L.tqkv);
-    if (L.s1) hipFree(L.s1);
-    if (L.t1) hipFree(L.t1);
-  }
-  for (auto& kv : h->w_il)
-    if (kv.second) hipFree(kv.second);
-  if (h->fin_cnt) hipFree(h->fin_cnt);
-  if (h->pos_sized) hipFree(h->pos_sized);
-  if (h->rope_cos) hipFree(h->rope_cos);
-  if (h->rope_sin) hipFree(h->rope_sin);
-  for (auto st : h->streams) hipStreamDestroy(st);
-  for (auto st : h->aux) hipStreamDestroy(st);
-  for (auto e : h->aux_fork) hipEventDestroy(e);
-  for (auto e : h->aux_join) hipEventDestroy(e);
-  for (auto e : h->ev_join) hipEventDestroy(e);
-  if (h->ev_fork) hipEventDestroy(h->ev_fork);
-  for (auto& e : h->ev_used) {
-    hipEventDestroy(e.a);
-    hipEventDestroy(e.b);
-  }
-  for (auto& e : h->ev_free) {
-    hipEventDestroy(e.a);
-    hipEventDestroy(e.b);
-  }
-  delete h;
+  delete h;  // (every device buffer, stream and event is a member that frees itself)
 }
 
 int vdr_num_weights(vdr_handle h) { return h ? (int)h->slots.size() : 0; }
@@ -1684,10 +1676,8 @@ int vdr_set_weight(vdr_handle m, const char* name, const float* host, const int6
   DeviceGuard dg(m->device);
   if (!dg.ok) return fail(m, VDR_ERR_HIP, "hipSetDevice failed");
   if (src_n) {  // kept as loaded; vdr_finalize resamples it
-    if (s.dev_src) VDR_TRY(hipFree(s.dev_src), "hipFree(native table)");
-    s.dev_src = nullptr;
-    VDR_TRY(hipMalloc(&s.dev_src, (size_t)numel * 4 + 256), "hipMalloc(native table)");
-    VDR_TRY(hipMemcpy(s.dev_src, host, (size_t)numel * 4, hipMemcpyHostToDevice), "hipMemcpy(native table)");
+    if (int rc = reserve(m, s.dev_src, (size_t)numel * 4, REPLACE, "native table")) return rc;
+    VDR_TRY(hipMemcpy(s.dev_src.get(), host, (size_t)numel * 4, hipMemcpyHostToDevice), "hipMemcpy(native table)");
     s.host.assign(host, host + numel);
     s.src_n = src_n;
     s.set = true;
@@ -1721,14 +1711,12 @@ int vdr_set_weight(vdr_handle m, const char* name, const float* host, const int6
       break;
     }
     case W_W12_BF16: {
-      // SwiGLU: interleave x1/x2 rows in blocks of 32 so one wave tile holds a gate pair:
-      // packed row 64*blk + t = (t < 32 ? x1[32*blk + t] : x2[32*blk + t - 32])
+      // SwiGLU: interleave x1/x2 rows in blocks of 32 so one wave tile holds a gate pair (swiglu_source_row)
       if (F % 32) return fail(m, VDR_ERR_UNSUPPORTED, "SwiGLU hidden must be a multiple of 32");
       const int64_t K = s.cols;
       bf.resize(numel);
       for (int64_t pr = 0; pr < 2 * F; ++pr) {
-        const int64_t blk = pr / 64, t = pr % 64;
-        const int64_t srow = t < 32 ? blk * 32 + t : F + blk * 32 + (t - 32);
+        const int64_t srow = swiglu_source_row(pr, F);
         for (int64_t k = 0; k < K; ++k) bf[pr * K + k] = f32_to_bf16(host[srow * K + k]);
       }
       src = bf.data();
@@ -1749,18 +1737,15 @@ int vdr_set_weight(vdr_handle m, const char* name, const float* host, const int6
     }
     case W_W12_BIAS: {
       fv.resize(numel);
-      for (int64_t pr = 0; pr < 2 * F; ++pr) {
-        const int64_t blk = pr / 64, t = pr % 64;
-        fv[pr] = host[t < 32 ? blk * 32 + t : F + blk * 32 + (t - 32)];
-      }
+      for (int64_t pr = 0; pr < 2 * F; ++pr) fv[pr] = host[swiglu_source_row(pr, F)];
       src = fv.data();
       bytes = (size_t)numel * 4;
       break;
     }
   }
   s.host.assign(host, host + numel);
-  if (!s.dev) VDR_TRY(hipMalloc(&s.dev, bytes + 256), "hipMalloc(weight)");
-  VDR_TRY(hipMemcpy(s.dev, src, bytes, hipMemcpyHostToDevice), "hipMemcpy(weight)");
+  if (int rc = reserve(m, s.dev, bytes, IF_EMPTY, "weight")) return rc;
+  VDR_TRY(hipMemcpy(s.dev.get(), src, bytes, hipMemcpyHostToDevice), "hipMemcpy(weight)");
   s.set = true;
   m->resolved = false;
   return VDR_OK;
@@ -2013,6 +1998,15 @@ int vdr_forward_tokens_varlen(vdr_handle m, const void* tokens, int in_dtype, in
     if (_e != hipSuccess) return fail(nullptr, VDR_ERR_HIP, std::string(what) + ": " + hipGetErrorString(_e)); \
   } while (0)
 
+// an op that is one launch, as the LAST statement of its entry point: RETURNS FROM THE CALLER with the device check's
+// refusal, with VDR_ERR_HIP "<what>: <HIP's text>" if the launch fails, else with VDR_OK
+#define RUN_OP(launch, what)                       \
+  do {                                             \
+    if (int rc = check_device(nullptr)) return rc; \
+    OP_TRY(launch, what);                          \
+    return VDR_OK;                                 \
+  } while (0)
+
 // an op's GEMM: hipErrorInvalidValue is the caller's tile variant or shape (VDR_ERR_INVALID, `refused`)
 static int op_gemm(const GemmArgs& g, int epilogue, int variant, void* stream, const char* refused) {
   const hipError_t e = launch_gemm(g, epilogue, variant, (hipStream_t)stream);
@@ -2027,8 +2021,7 @@ static int op_gemm(const GemmArgs& g, int epilogue, int variant, void* stream, c
 int vdr_op_layernorm(const void* x, int in_dtype, void* y, int out_dtype, const float* gamma, const float* beta,
                      int64_t rows, int D, float eps, void* stream) {
   if (!x || !y || !gamma || !beta) return fail(nullptr, VDR_ERR_INVALID, "null argument");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
+  if (int rc = check_device(nullptr)) return rc;
   LnArgs a{};
   a.x = x;
   a.in_bf16 = in_dtype == VDR_BF16;
@@ -2057,8 +2050,7 @@ static int op_linear_impl(const void* x, const void* W, int packed, const float*
 #ifndef VDR_TUNING
   if (variant < 0 || variant >= 100) return fail(nullptr, VDR_ERR_INVALID, "variant");  // (ablation encodings: tuning builds only)
 #endif
-  int rc = check_device(nullptr);
-  if (rc) return rc;
+  if (int rc = check_device(nullptr)) return rc;
   GemmArgs g = linear(x, W, y, M, N, K, epilogue);
   g.w_interleaved = packed;
   g.bias = bias;
@@ -2077,10 +2069,8 @@ int vdr_op_linear(const void* x, const void* W, const float* bias, const void* r
 int vdr_op_pack_linear_weight(const void* W, int N, int K, void* packed, void* stream) {
   if (!W || !packed) return fail(nullptr, VDR_ERR_INVALID, "null argument");
   if (N <= 0 || (N & 1) || K <= 0 || (K & 31)) return fail(nullptr, VDR_ERR_UNSUPPORTED, "N even and K % 32 == 0 required");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
-  OP_TRY(launch_w_interleave(W, packed, N, K, K, (hipStream_t)stream), "w_interleave");
-  return VDR_OK;
+  RUN_OP(launch_w_interleave(W, packed, N, K, K, (hipStream_t)stream),
+         "w_interleave");
 }
 
 int vdr_op_linear_packed(const void* x, const void* Wp, const float* bias, const void* resid, const float* gamma, void* y,
@@ -2112,8 +2102,7 @@ int vdr_op_linear_ln_stats(const void* x, const void* W, const float* bias, cons
   if (stats && !ring4_variant(variant)) return fail(nullptr, VDR_ERR_INVALID, "in-GEMM finalisation: ring4 variants 26..29");
   if (M <= 0 || N <= 0 || K <= 0 || (N % 64) || (K % 64) || part_stride < M)
     return fail(nullptr, VDR_ERR_INVALID, "M > 0, N % 64 == 0, K % 64 == 0, part_stride >= M required");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
+  if (int rc = check_device(nullptr)) return rc;
   GemmArgs g = linear(x, W, y, M, N, K, EPI_BIAS_RESID);
   g.bias = bias;
   g.resid = resid ? resid : y;
@@ -2134,10 +2123,8 @@ int vdr_op_ln_finalize(const float* part, int64_t part_stride, int64_t rows, int
   if (!part || !stats) return fail(nullptr, VDR_ERR_INVALID, "null argument");
   if (rows <= 0 || D <= 0 || (D % 64) || part_stride < rows)
     return fail(nullptr, VDR_ERR_INVALID, "rows > 0, D % 64 == 0, part_stride >= rows required");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
-  OP_TRY(launch_ln_finalize(part, D / 64, part_stride, stats, rows, D, eps, (hipStream_t)stream), "ln_finalize");
-  return VDR_OK;
+  RUN_OP(launch_ln_finalize(part, D / 64, part_stride, stats, rows, D, eps, (hipStream_t)stream),
+         "ln_finalize");
 }
 
 int vdr_op_linear_ln_fold(const void* x, const void* Wf, const float* colsum, const float* tbias, const float* stats,
@@ -2153,8 +2140,7 @@ int vdr_op_linear_ln_fold(const void* x, const void* Wf, const float* colsum, co
   // (the forward finalises inside the GEMM on ring3 / ring4 variants 22-24, 26-28 only, up to 16 groups)
   if (part && (!ln_cpart_variant(variant) || K / 64 > 16 || part_stride < M))
     return fail(nullptr, VDR_ERR_INVALID, "in-GEMM statistics: variants 22-24, 26-28, K <= 1024, part_stride >= M");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
+  if (int rc = check_device(nullptr)) return rc;
   GemmArgs g = linear(x, Wf, y, M, N, K, epilogue);
   g.bias = tbias;
   g.a_rows = x_rows;
@@ -2182,40 +2168,31 @@ int vdr_op_prepare_image(const void* src, int src_dtype, int batch, int h, int w
   if (out_dtype != VDR_F32 && out_dtype != VDR_BF16) return fail(nullptr, VDR_ERR_UNSUPPORTED, "prepare_image: fp32 or bf16 output");
   if (prepare_scratch_bytes(batch, h, w, channels, out_side) && !scratch)
     return fail(nullptr, VDR_ERR_INVALID, "prepare_image: down-scaling needs the scratch buffer");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
-  OP_TRY(launch_prepare(src, src_dtype == VDR_F32, batch, h, w, channels, stride_b, stride_y, stride_x, stride_c, flip, out_side,
-                        out, out_dtype == VDR_BF16, (float*)scratch, (hipStream_t)stream),
+  RUN_OP(launch_prepare(src, src_dtype == VDR_F32, batch, h, w, channels, stride_b, stride_y, stride_x, stride_c, flip,
+                        out_side, out, out_dtype == VDR_BF16, (float*)scratch, (hipStream_t)stream),
          "prepare_image");
-  return VDR_OK;
 }
 
 int vdr_op_window_ct(const void* ct, int in_dtype, int64_t n, double width, double level, float* out, void* stream) {
   if (!ct || !out) return fail(nullptr, VDR_ERR_INVALID, "null argument");
   if (in_dtype != VDR_F32 && in_dtype != VDR_I16) return fail(nullptr, VDR_ERR_UNSUPPORTED, "window_ct: fp32 or int16 input");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
-  OP_TRY(launch_window_ct(ct, in_dtype == VDR_I16, n, width, level, out, (hipStream_t)stream), "window_ct");
-  return VDR_OK;
+  RUN_OP(launch_window_ct(ct, in_dtype == VDR_I16, n, width, level, out, (hipStream_t)stream),
+         "window_ct");
 }
 
 int vdr_op_hu_to_rgb(const void* hu, int in_dtype, int64_t n, void* rgb, void* stream) {
   if (!hu || !rgb) return fail(nullptr, VDR_ERR_INVALID, "null argument");
   const int dt = in_dtype == VDR_F32 ? 0 : in_dtype == VDR_I16 ? 1 : in_dtype == VDR_F64 ? 2 : -1;
   if (dt < 0) return fail(nullptr, VDR_ERR_UNSUPPORTED, "hu_to_rgb: fp32, int16 or fp64 input");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
-  OP_TRY(launch_hu_to_rgb(hu, dt, n, rgb, (hipStream_t)stream), "hu_to_rgb");
-  return VDR_OK;
+  RUN_OP(launch_hu_to_rgb(hu, dt, n, rgb, (hipStream_t)stream),
+         "hu_to_rgb");
 }
 
 int vdr_op_crop_hwc(const float* src, float* dst, int batch, int H, int W, int C, int y0, int x0, int crop_h, int crop_w,
                     void* stream) {
   if (!src || !dst) return fail(nullptr, VDR_ERR_INVALID, "null argument");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
-  OP_TRY(launch_crop_hwc(src, dst, batch, H, W, C, y0, x0, crop_h, crop_w, (hipStream_t)stream), "crop_hwc");
-  return VDR_OK;
+  RUN_OP(launch_crop_hwc(src, dst, batch, H, W, C, y0, x0, crop_h, crop_w, (hipStream_t)stream),
+         "crop_hwc");
 }
 
 int vdr_op_voxel_sequence(const float* feat, const int64_t* index, const double* xyz, const double* expo, int64_t n, int D,
@@ -2225,10 +2202,8 @@ int vdr_op_voxel_sequence(const float* feat, const int64_t* index, const double*
   if (!feat || !index || !xyz || !expo || !out) return fail(nullptr, VDR_ERR_INVALID, "null argument");
   const int dt = out_dtype == VDR_F32 ? 0 : out_dtype == VDR_BF16 ? 1 : out_dtype == VDR_F64 ? 2 : -1;
   if (dt < 0) return fail(nullptr, VDR_ERR_UNSUPPORTED, "voxel_sequence: fp32, bf16 or fp64 output");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
-  OP_TRY(launch_voxel_sequence(feat, index, xyz, expo, n, D, out, dt, (hipStream_t)stream), "voxel_sequence");
-  return VDR_OK;
+  RUN_OP(launch_voxel_sequence(feat, index, xyz, expo, n, D, out, dt, (hipStream_t)stream),
+         "voxel_sequence");
 }
 
 size_t vdr_affine_cubic_scratch_bytes(int h, int w, int64_t planes) {
@@ -2244,38 +2219,29 @@ int vdr_op_affine_cubic(const void* src, int dtype, int h, int w, int64_t planes
   if (dt < 0) return fail(nullptr, VDR_ERR_UNSUPPORTED, "affine_cubic: fp64, fp32 or uint8 (boolean mask) volume");
   if ((int64_t)(h + 24) * (w + 24) * planes >= ((int64_t)1 << 31) * 256)
     return fail(nullptr, VDR_ERR_UNSUPPORTED, "affine_cubic: volume too large for one launch");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
-  OP_TRY(launch_affine_cubic(src, dt, h, w, planes, matrix, offset, out, clip01, (double*)scratch, (hipStream_t)stream),
+  RUN_OP(launch_affine_cubic(src, dt, h, w, planes, matrix, offset, out, clip01, (double*)scratch, (hipStream_t)stream),
          "affine_cubic");
-  return VDR_OK;
 }
 
 size_t vdr_mx_scale_bytes(int64_t rows, int K) { return rows > 0 && K > 0 ? mx_scale_bytes(rows, K) : 0; }
 
 int vdr_op_mx_quantize(const void* x, int64_t rows, int K, void* q, void* scales, void* stream) {
   if (!x || !q || !scales) return fail(nullptr, VDR_ERR_INVALID, "null argument");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
-  OP_TRY(launch_mx_quant(x, rows, K, K, q, scales, (hipStream_t)stream), "mx_quantize");
-  return VDR_OK;
+  RUN_OP(launch_mx_quant(x, rows, K, K, q, scales, (hipStream_t)stream),
+         "mx_quantize");
 }
 
 int vdr_op_mx_dequantize(const void* q, const void* scales, int64_t rows, int K, float* y, void* stream) {
   if (!q || !scales || !y) return fail(nullptr, VDR_ERR_INVALID, "null argument");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
-  OP_TRY(launch_mx_dequant(q, scales, rows, K, y, (hipStream_t)stream), "mx_dequantize");
-  return VDR_OK;
+  RUN_OP(launch_mx_dequant(q, scales, rows, K, y, (hipStream_t)stream),
+         "mx_dequantize");
 }
 
 int vdr_op_layernorm_mx(const void* x, const float* gamma, const float* beta, float eps, int64_t rows, int D, void* q,
                         void* scales, void* stream) {
   if (!x || !gamma || !beta || !q || !scales) return fail(nullptr, VDR_ERR_INVALID, "null argument");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
-  OP_TRY(launch_ln_mx(x, gamma, beta, eps, rows, D, q, scales, (hipStream_t)stream), "layernorm_mx");
-  return VDR_OK;
+  RUN_OP(launch_ln_mx(x, gamma, beta, eps, rows, D, q, scales, (hipStream_t)stream),
+         "layernorm_mx");
 }
 
 int vdr_op_linear_mx(const void* xq, const void* xs, const void* wq, const void* ws, const float* bias, const void* resid,
@@ -2283,8 +2249,7 @@ int vdr_op_linear_mx(const void* xq, const void* xs, const void* wq, const void*
                      void* stream) {
   if (!xq || !xs || !wq || !ws || !y) return fail(nullptr, VDR_ERR_INVALID, "null argument");
   if (epilogue == VDR_EPI_BIAS_RESID && !resid) return fail(nullptr, VDR_ERR_INVALID, "EPI_BIAS_RESID needs resid");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
+  if (int rc = check_device(nullptr)) return rc;
   GemmArgs g = linear(xq, wq, y, M, N, K, epilogue);
   g.a_scale = xs;
   g.w_scale = ws;
@@ -2298,54 +2263,41 @@ int vdr_op_linear_mx(const void* xq, const void* xs, const void* wq, const void*
 
 int vdr_op_attention(const void* qkv, void* out, int batch, int seq, int heads, int variant, void* stream) {
   if (!qkv || !out) return fail(nullptr, VDR_ERR_INVALID, "null argument");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
-  OP_TRY(launch_attention(qkv, out, batch, seq, heads, variant, (hipStream_t)stream), "attention");
-  return VDR_OK;
+  RUN_OP(launch_attention(qkv, out, batch, seq, heads, variant, (hipStream_t)stream),
+         "attention");
 }
 
 int vdr_op_attention_hd(const void* qkv, void* out, int batch, int seq, int heads, int head_dim, int variant, void* stream) {
-  if (head_dim != 32 && head_dim != 64 && head_dim != 96 && head_dim != 128)
-    return fail(nullptr, VDR_ERR_UNSUPPORTED, "head dim must be 32, 64, 96 or 128");
+  if (!head_dim_ok(head_dim)) return fail(nullptr, VDR_ERR_UNSUPPORTED, "head dim must be 32, 64, 96 or 128");
   if (!qkv || !out) return fail(nullptr, VDR_ERR_INVALID, "null argument");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
-  OP_TRY(launch_attention(qkv, out, batch, seq, heads, variant, (hipStream_t)stream, nullptr, nullptr, 0, head_dim), "attention");
-  return VDR_OK;
+  RUN_OP(launch_attention(qkv, out, batch, seq, heads, variant, (hipStream_t)stream, nullptr, nullptr, 0, head_dim),
+         "attention");
 }
 
 int vdr_op_attention_varlen(const void* qkv, void* out, int batch, int seq, int heads, int head_dim, const int32_t* lens,
                             int len_add, int variant, void* stream) {
-  if (head_dim != 32 && head_dim != 64 && head_dim != 96 && head_dim != 128)
-    return fail(nullptr, VDR_ERR_UNSUPPORTED, "head dim must be 32, 64, 96 or 128");
+  if (!head_dim_ok(head_dim)) return fail(nullptr, VDR_ERR_UNSUPPORTED, "head dim must be 32, 64, 96 or 128");
   if (!qkv || !out || !lens) return fail(nullptr, VDR_ERR_INVALID, "null argument");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
-  OP_TRY(launch_attention(qkv, out, batch, seq, heads, variant, (hipStream_t)stream, nullptr, lens, len_add, head_dim),
+  RUN_OP(launch_attention(qkv, out, batch, seq, heads, variant, (hipStream_t)stream, nullptr, lens, len_add, head_dim),
          "attention");
-  return VDR_OK;
 }
 
 int vdr_op_attention_probs(const void* qkv, void* out, int batch, int seq, int heads, int head_dim, int q_rows, int head_mean,
                            int out_dtype, void* stream) {
-  if (head_dim != 32 && head_dim != 64 && head_dim != 96 && head_dim != 128)
-    return fail(nullptr, VDR_ERR_UNSUPPORTED, "head dim must be 32, 64, 96 or 128");
+  if (!head_dim_ok(head_dim)) return fail(nullptr, VDR_ERR_UNSUPPORTED, "head dim must be 32, 64, 96 or 128");
   if (!qkv || !out) return fail(nullptr, VDR_ERR_INVALID, "null argument");
   if (batch <= 0 || seq <= 0 || heads <= 0) return fail(nullptr, VDR_ERR_INVALID, "bad shape");
   if (q_rows < 1 || q_rows > seq) return fail(nullptr, VDR_ERR_INVALID, "q_rows must be in [1, seq]");
   if (head_mean != 0 && head_mean != 1) return fail(nullptr, VDR_ERR_INVALID, "head_mean must be 0 or 1");
   if (out_dtype != VDR_F32 && out_dtype != VDR_BF16) return fail(nullptr, VDR_ERR_INVALID, "out_dtype");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
-  OP_TRY(launch_attention_probs(qkv, out, batch, seq, heads, head_dim, q_rows, head_mean, out_dtype == VDR_BF16, (hipStream_t)stream),
+  RUN_OP(launch_attention_probs(qkv, out, batch, seq, heads, head_dim, q_rows, head_mean, out_dtype == VDR_BF16,
+                                (hipStream_t)stream),
          "attention_probs");
-  return VDR_OK;
 }
 
 int vdr_op_attention_pool(const float* q, const void* kv, int64_t ldkv, void* out, int batch, int n, int heads, int head_dim,
                           void* stream) {
-  if (head_dim != 32 && head_dim != 64 && head_dim != 96 && head_dim != 128)
-    return fail(nullptr, VDR_ERR_UNSUPPORTED, "head dim must be 32, 64, 96 or 128");
+  if (!head_dim_ok(head_dim)) return fail(nullptr, VDR_ERR_UNSUPPORTED, "head dim must be 32, 64, 96 or 128");
   if (!q || !kv || !out) return fail(nullptr, VDR_ERR_INVALID, "null argument");
   if (batch <= 0 || heads <= 0) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_attention_pool: batch and heads must be positive");
   if (n < 1) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_attention_pool: n must be at least 1");
@@ -2353,10 +2305,8 @@ int vdr_op_attention_pool(const float* q, const void* kv, int64_t ldkv, void* ou
   if (ldkv < (int64_t)2 * heads * head_dim || (ldkv & 7))
     return fail(nullptr, VDR_ERR_INVALID, "vdr_op_attention_pool: ldkv must be a multiple of 8 and at least 2 * heads * head_dim");
   if ((uintptr_t)kv & 15) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_attention_pool: kv must be 16-byte aligned");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
-  OP_TRY(launch_attention_pool(q, kv, ldkv, out, batch, n, heads, head_dim, (hipStream_t)stream), "attention_pool");
-  return VDR_OK;
+  RUN_OP(launch_attention_pool(q, kv, ldkv, out, batch, n, heads, head_dim, (hipStream_t)stream),
+         "attention_pool");
 }
 
 int vdr_op_attention_relpos(const void* qkv, const float* rel_pos_h, const float* rel_pos_w, float* rel, void* out,
@@ -2365,8 +2315,7 @@ int vdr_op_attention_relpos(const void* qkv, const float* rel_pos_h, const float
   if (batch <= 0 || S <= 0 || heads <= 0) return fail(nullptr, VDR_ERR_INVALID, "bad shape");
   if (S > 64)
     return fail(nullptr, VDR_ERR_UNSUPPORTED, "vdr_op_attention_relpos: S must be at most 64 (the packed rel-pos operand holds 127 + 127 rows)");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
+  if (int rc = check_device(nullptr)) return rc;
   const int64_t tokens = (int64_t)batch * S * S;
   const int npad = relpos_npad(S);
   void* table = rel + tokens * heads * npad;  // packed bf16 tables behind the products
@@ -2384,10 +2333,8 @@ int vdr_op_interpolate_rel_pos(const float* table, int L0, int D, float* out, in
   if (L <= 0) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_interpolate_rel_pos: L must be positive");
   if ((int64_t)L0 * D > (1 << 30) || (int64_t)L * D > (1 << 30))
     return fail(nullptr, VDR_ERR_INVALID, "vdr_op_interpolate_rel_pos: more than 2^30 table elements");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
-  OP_TRY(launch_relpos_interp(table, L0, D, out, L, (hipStream_t)stream), "relpos_interp");
-  return VDR_OK;
+  RUN_OP(launch_relpos_interp(table, L0, D, out, L, (hipStream_t)stream),
+         "relpos_interp");
 }
 
 int vdr_op_interpolate_pos(const float* pos, int gh0, int gw0, int D, float* out, int gh, int gw, void* stream) {
@@ -2400,10 +2347,8 @@ int vdr_op_interpolate_pos(const float* pos, int gh0, int gw0, int D, float* out
   if (gw <= 0) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_interpolate_pos: gw must be positive");
   if ((int64_t)gh0 * gw0 > (1 << 20) || (int64_t)gh * gw > (1 << 20))
     return fail(nullptr, VDR_ERR_INVALID, "vdr_op_interpolate_pos: more than 2^20 grid cells");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
-  OP_TRY(launch_pos_interp(pos, gh0, gw0, D, out, gh, gw, (hipStream_t)stream), "pos_interp");
-  return VDR_OK;
+  RUN_OP(launch_pos_interp(pos, gh0, gw0, D, out, gh, gw, (hipStream_t)stream),
+         "pos_interp");
 }
 
 int vdr_op_rope2d_table(int gh, int gw, int head_dim, float theta, float* cos_out, float* sin_out, void* stream) {
@@ -2413,10 +2358,8 @@ int vdr_op_rope2d_table(int gh, int gw, int head_dim, float theta, float* cos_ou
   if (gh <= 0 || gw <= 0 || (int64_t)gh * gw > (1 << 20))
     return fail(nullptr, VDR_ERR_INVALID, "vdr_op_rope2d_table: gh, gw must be positive, at most 2^20 grid cells");
   if (!(std::isfinite(theta) && theta > 1.0f)) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_rope2d_table: theta must be finite and > 1");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
-  OP_TRY(launch_rope2d_table(gh, gw, head_dim, theta, cos_out, sin_out, (hipStream_t)stream), "rope2d_table");
-  return VDR_OK;
+  RUN_OP(launch_rope2d_table(gh, gw, head_dim, theta, cos_out, sin_out, (hipStream_t)stream),
+         "rope2d_table");
 }
 
 int vdr_op_rope2d(void* qkv, int batch, int seq, int prefix, int heads, int head_dim, const float* cos, const float* sin,
@@ -2428,18 +2371,15 @@ int vdr_op_rope2d(void* qkv, int batch, int seq, int prefix, int heads, int head
     return fail(nullptr, VDR_ERR_INVALID, "vdr_op_rope2d: batch, seq, heads must be positive and 0 <= prefix <= seq");
   if ((((uintptr_t)qkv) | ((uintptr_t)cos) | ((uintptr_t)sin)) & 15)
     return fail(nullptr, VDR_ERR_INVALID, "vdr_op_rope2d: qkv, cos and sin must be 16-byte aligned");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
-  OP_TRY(launch_rope2d(qkv, batch, seq, prefix, heads, head_dim, cos, sin, (hipStream_t)stream), "rope2d");
-  return VDR_OK;
+  RUN_OP(launch_rope2d(qkv, batch, seq, prefix, heads, head_dim, cos, sin, (hipStream_t)stream),
+         "rope2d");
 }
 
 int vdr_op_patch_embed(const void* images, int in_dtype, const void* W, const float* bias, const float* pos, void* col,
                        void* y, int batch, int C, int img, int p, int D, int row_stride, int row_offset, void* stream) {
   if (!images || !W || !col || !y) return fail(nullptr, VDR_ERR_INVALID, "null argument");
   if (p <= 0 || img % p) return fail(nullptr, VDR_ERR_INVALID, "img must be a multiple of p");
-  int rc = check_device(nullptr);
-  if (rc) return rc;
+  if (int rc = check_device(nullptr)) return rc;
   GemmArgs a;
   int variant;  // (the caller's W as it is; bf16 images with p = 8 / 16 / 32: no im2col pass, `col` untouched)
   OP_TRY(patch_gemm(nullptr, (hipStream_t)stream, images, in_dtype, col, W, y, batch, C, img, img, p, D, &a, &variant), "im2col");
@@ -2466,14 +2406,15 @@ int vdr_profile_mask(vdr_handle m, uint32_t class_mask) {
 int vdr_profile_read(vdr_handle m, double* ms, int64_t* launches, double* flops, double* bytes, int n) {
   if (!m || !ms || n < VDR_K_COUNT) return fail(m, VDR_ERR_INVALID, "bad argument");
   for (int k = 0; k < VDR_K_COUNT; ++k) ms[k] = 0.0;
-  for (auto& e : m->ev_used) {
-    VDR_TRY(hipEventSynchronize(e.b), "hipEventSynchronize");
+  std::vector<ProfEvent> used;
+  used.swap(m->ev_used);  // (an early return below drops the pairs not yet read; none is left behind moved-from)
+  for (auto& e : used) {
+    VDR_TRY(hipEventSynchronize(e.b.get()), "hipEventSynchronize");
     float t = 0.0f;
-    VDR_TRY(hipEventElapsedTime(&t, e.a, e.b), "hipEventElapsedTime");
+    VDR_TRY(hipEventElapsedTime(&t, e.a.get(), e.b.get()), "hipEventElapsedTime");
     ms[e.cls] += t;
-    m->ev_free.push_back(e);
+    m->ev_free.push_back(std::move(e));
   }
-  m->ev_used.clear();
   for (int k = 0; k < VDR_K_COUNT; ++k) {
     if (launches) launches[k] = m->p_launch[k];
     if (flops) flops[k] = m->p_flops[k];
