@@ -2,12 +2,14 @@
 """Whole-forward A/B of two builds of libvdr.so in ONE process, interleaved rounds on one device (as tools/ab_libs.py does
 for single kernels): both libraries are dlopen'ed side by side, each gets its own handle with the same weights, and the
 headline forward (bench.py's workload: ViT-B/16 224^2, batch 256, bf16 images, CLS out) alternates between them.
-   python tools/ab_forward_libs.py path/to/libA.so path/to/libB.so [--model vit_base16_224] [--batch 256] [--rounds 15] [--steps 10]
+   python tools/ab_forward_libs.py path/to/libA.so path/to/libB.so [--model vit_base16_224] [--batch 256] [--rounds 15] [--steps 10] [--fp8]
 --model medsam: the SAM ViT-B image encoder at 1024^2 (neck output) instead of a plain ViT's CLS features.
+--fp8: qkv / fc1 / fc2 as MX-fp8 (vdr_config.fp8 = 1).
 Prints per library the median / min / max ms per step over the rounds, the per-round A - B differences, and whether the
 median difference lies inside the round-to-round spread of either side.  The outputs of the two must be bitwise equal."""
 import argparse
 import ctypes as C
+import dataclasses
 import os
 import sys
 
@@ -46,6 +48,7 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--fp8", action="store_true")
     a = ap.parse_args()
     torch.cuda.set_device(0)
     sam = a.model == "medsam"
@@ -57,7 +60,8 @@ def main():
         cfg = vo.CONFIGS[a.model]
         w = vo.make_weights(cfg, seed=1)
     mode = vdr.OUT_ENCODER if sam else vdr.OUT_CLS
-    engines = [engine_on(p, vdr.ARCHS[a.model], w) for p in a.libs]
+    arch = dataclasses.replace(vdr.ARCHS[a.model], fp8=1) if a.fp8 else vdr.ARCHS[a.model]
+    engines = [engine_on(p, arch, w) for p in a.libs]
     x = torch.rand(a.batch, 3, cfg.img, cfg.img).to(torch.bfloat16).cuda()
     shape = (a.batch, cfg.grid, cfg.grid, cfg.out_chans) if sam else (a.batch, cfg.dim)
     outs = [torch.empty(shape, dtype=torch.float32, device="cuda") for _ in engines]
@@ -74,7 +78,7 @@ def main():
             torch.cuda.synchronize()
             if rnd:  # round 0 warms up
                 times[i].append(e0.elapsed_time(e1) / a.steps)
-    print(f"{a.model} batch {a.batch} bf16 images, {'neck' if sam else 'CLS'} out; {a.rounds} interleaved rounds of {a.steps} steps")
+    print(f"{a.model}{' MX-fp8' if a.fp8 else ''} batch {a.batch} bf16 images, {'neck' if sam else 'CLS'} out; {a.rounds} interleaved rounds of {a.steps} steps")
     print("outputs bitwise equal:", torch.equal(outs[0], outs[1]))
     med = []
     for p, t in zip(a.libs, times):

@@ -5,6 +5,7 @@
 // time (s_memrealtime), how many run at once, and the mean duration of each phase.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -DVDR_GEMM_STAMPS -I vit-deep-radiomics_amd/csrc tools/micro/gemm_stamps.hip -o tools/micro/gemm_stamps
 //   tools/micro/gemm_stamps [shape = fc1 | fc2 | qkv | proj]
+#include "gemm_launch.hip"
 #include "gemm.hip"
 #include "gemm_ring4.hip"
 #include <algorithm>

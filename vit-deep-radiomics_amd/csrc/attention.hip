@@ -564,14 +564,10 @@ template <int NT, bool LOADER>
 static hipError_t launch_persist(const AttnK& k, int batch, hipStream_t s) {
   constexpr size_t lds = 2 * (size_t)(2 * NT * 32 * 128);
   auto fn = attn_persist_kernel<NT, LOADER>;
-  static PerDeviceFlag attr;  // per instantiation and device: raised once, not per launch
+  static KernelState st;  // per instantiation and device: the LDS limit is raised once, not per launch
   const int dev = current_device_index();
   if (dev < 0) return hipErrorInvalidDevice;
-  if (!attr.done[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    attr.done[dev] = true;
-  }
+  if (hipError_t e = raise_lds_limit(st, (const void*)fn, dev, lds)) return e;
   int n_cu = device_cu_count(dev);
   if (n_cu <= 0) n_cu = 256;
   const int n_items = batch * k.heads;
@@ -585,14 +581,10 @@ static hipError_t launch_nt(const AttnK& k, int batch, hipStream_t s) {
   constexpr size_t image = 2 * (size_t)NT * 32 * 128;       // K image + V image
   const size_t lds = image;
   auto fn = attn_kernel<NT>;
-  static PerDeviceFlag attr;  // per instantiation and device: raised once, not per launch
+  static KernelState st;  // per instantiation and device: the LDS limit is raised once, not per launch
   const int dev = current_device_index();
   if (dev < 0) return hipErrorInvalidDevice;
-  if (image > 65536 && !attr.done[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)image);
-    if (e != hipSuccess) return e;
-    attr.done[dev] = true;
-  }
+  if (hipError_t e = raise_lds_limit(st, (const void*)fn, dev, lds)) return e;
   const int nqt = (k.seq + 31) / 32;
   const dim3 grid((unsigned)(batch * k.heads * ((nqt + k.qt_per_block - 1) / k.qt_per_block)));
   hipLaunchKernelGGL(fn, grid, dim3(256), lds, s, k);

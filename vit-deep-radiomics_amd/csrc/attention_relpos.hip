@@ -350,14 +350,10 @@ template <int NT, int S, bool MULTI>
 static hipError_t launch_rp(const AttnRK& k, int batch, hipStream_t s) {
   constexpr size_t lds = (MULTI ? 2 : 1) * 2 * (size_t)NT * 32 * 128;  // (K image + V image) x 1 or 2 buffers
   auto fn = attn_relpos_kernel<NT, S, MULTI>;
-  static PerDeviceFlag attr;  // per instantiation and device: raised once, not per launch
+  static KernelState st;  // per instantiation and device: the LDS limit is raised once, not per launch
   const int dev = current_device_index();
   if (dev < 0) return hipErrorInvalidDevice;
-  if (lds > 65536 && !attr.done[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    attr.done[dev] = true;
-  }
+  if (hipError_t e = raise_lds_limit(st, (const void*)fn, dev, lds)) return e;
   const int nqt = (k.seq + 31) / 32;
   const dim3 grid((unsigned)(batch * k.heads * ((nqt + k.qt_per_block - 1) / k.qt_per_block)));
   hipLaunchKernelGGL(fn, grid, dim3(256), lds, s, k);
@@ -581,15 +577,11 @@ template <bool DB>
 static hipError_t launch_rp_any(const AttnRK& k, int batch, hipStream_t s) {
   const size_t lds = (size_t)(DB ? 2 : 1) * 2 * 128 * 128 + (size_t)4 * 2 * k.g * 32 * 4;
   auto fn = attn_relpos_any_kernel<DB>;
-  static PerDeviceFlag attr;
+  static KernelState st;
   const int dev = current_device_index();
   if (dev < 0) return hipErrorInvalidDevice;
-  if (!attr.done[dev]) {  // the largest request of any g: 128 KB (DB) / 96 KB
-    hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (DB ? 2 : 1) * 2 * 128 * 128 + 4 * 2 * 64 * 32 * 4);
-    if (e != hipSuccess) return e;
-    attr.done[dev] = true;
-  }
+  // raised once, to the largest request of any g: 128 KB (DB) / 96 KB
+  if (hipError_t e = raise_lds_limit(st, (const void*)fn, dev, (size_t)(DB ? 2 : 1) * 2 * 128 * 128 + (size_t)4 * 2 * 64 * 32 * 4)) return e;
   const int nqt = (k.seq + 31) / 32;
   const dim3 grid((unsigned)(batch * k.heads * ((nqt + k.qt_per_block - 1) / k.qt_per_block)));
   hipLaunchKernelGGL(fn, grid, dim3(256), lds, s, k);

@@ -1,5 +1,6 @@
 // bf16 MFMA GEMM with fused epilogues for gfx950:  C[M,N] = epi(A[M,K] . W[N,K]^T)   -- entry point, the ring3 tile
-// variants and the weight packer.  Kernels live in gemm_kernels.h; the ring4 variants are instantiated in gemm_ring4.hip.
+// variants and the weight packer.  Kernels live in gemm_kernels.h; the ring4 variants are instantiated in gemm_ring4.hip
+// (so that the two halves compile in parallel); the argument checks and the launch shape are gemm_launch.hip's.
 //
 // Replaces the nn.Linear calls under nn.MultiheadAttention / nn.TransformerEncoderLayer
 // (reference src/models_archs.py:130-135) and attn.qkv / attn.proj / mlp.fc1 / mlp.fc2 of the
@@ -9,7 +10,7 @@
 
 namespace vdr {
 
-hipError_t launch_gemm_ring4(const GemmArgs& a, int epilogue, int variant, hipStream_t s);  // gemm_ring4.hip
+hipError_t launch_gemm_ring4(const GemmLaunch& L, hipStream_t s);                           // gemm_ring4.hip
 hipError_t launch_gemm_8p(const GemmArgs& a, int epilogue, hipStream_t s);                   // gemm_8p.hip
 
 // [N][K] (row stride ld) -> pair-interleaved [N/2][K/32][2][32]; one 16-byte chunk per thread
@@ -34,35 +35,10 @@ hipError_t launch_w_interleave(const void* src, void* dst, int N, int K, int64_t
 }
 
 hipError_t launch_gemm(const GemmArgs& a, int epilogue, int variant, hipStream_t s) {
-  if (a.K <= 0 || (a.K & 63) || (a.N & 7) || a.M <= 0) return hipErrorInvalidValue;
-  if (epilogue == EPI_SWIGLU && (a.N & 63)) return hipErrorInvalidValue;
-#ifdef VDR_TUNING
-  g_gemm_gn = variant >= 1000 ? variant / 1000 - 1 : -1;  // tools/: (gn + 1) * 1000 + v forces the column-group width gn
-  variant %= 1000;
-  g_gemm_ablation = variant / 100;  // tools/: 1xx no epilogue, 4xx no global loads after the ring fill, 8xx no stores
-  variant %= 100;
-#endif
-  if (a.out_f32 && epilogue != EPI_BIAS && epilogue != EPI_PATCH) return hipErrorInvalidValue;
-  if (a.ln_part && (a.N & 63)) return hipErrorInvalidValue;
-  switch (variant) {
-    case 22:
-      return launch_cfg<2, 4, 33>(a, epilogue, s);  // ring3: 128x256, 8 waves, 3 x 24 KB, 2 WG/CU
-    case 23:
-      return launch_cfg<4, 4, 33>(a, epilogue, s);  // ring3: 256x256, 16 waves, 3 x 32 KB
-    case 24:
-      return launch_cfg<2, 2, 33>(a, epilogue, s);  // ring3: 128x128, 4 waves, 3 x 16 KB, 3 WG/CU
-    case 25:
-      return launch_cfg<2, 2, 43>(a, epilogue, s);  // ring3k: 128x128 tile, 8 waves = 2 K-groups x (2x2), 3 x 32 KB
-    case 26:
-    case 27:
-    case 28:
-    case 29:
-      return launch_gemm_ring4(a, epilogue, variant, s);
-    case 31:
-      return launch_gemm_8p(a, epilogue, s);  // 8-phase: 256x256 tile, 8 waves, one persistent workgroup per CU, plain W layout
-    default:
-      return hipErrorInvalidValue;  // (variants 0-21, the earlier rungs of the ladder in DESIGN.md, are no longer built; 30, the persistent stream kernel of round 3, lives in tools/micro/)
-  }
+  GemmLaunch L;
+  if (hipError_t e = build_gemm_launch(a, epilogue, variant, &L)) return e;  // every refusal but variant 31's own
+  if (L.row->family == TILE_8P) return launch_gemm_8p(a, epilogue, s);
+  return L.row->family == TILE_RING4 ? launch_gemm_ring4(L, s) : launch_tiles<22, 23, 24, 25>(L, s);
 }
 
 }  // namespace vdr

@@ -77,24 +77,30 @@ hipError_t launch_gemm_8p(const GemmArgs& a, int epi, hipStream_t s) {
   if (!gemm_8p_eligible(a, epi)) return hipErrorInvalidValue;
   const int dev = current_device_index();
   if (dev < 0) return hipErrorInvalidDevice;
-  static float* zeros[VDR_MAX_DEVICES] = {};  // a zero bias of the largest N seen (bias == NULL), per device
-  static int zeros_n[VDR_MAX_DEVICES] = {};
   const float* bias = a.bias;
   if (!bias) {
+    // a zero bias of at least N entries (bias == NULL), per device.  (load-time path in practice: every Linear of the models has a
+    // bias; kept correct for vdr_op_linear callers.)  It grows by doubling under a lock, and an outgrown buffer stays allocated:
+    // another thread may hold its pointer between this block and its launch (all of them together are smaller than the last)
+    static std::mutex mu;
+    static float* zeros[VDR_MAX_DEVICES] = {};
+    static int zeros_n[VDR_MAX_DEVICES] = {};
+    std::lock_guard<std::mutex> lock(mu);
     if (zeros_n[dev] < a.N) {
-      // (load-time path in practice: every Linear of the models has a bias; kept correct for vdr_op_linear callers)
-      if (zeros[dev]) (void)hipFree(zeros[dev]);
-      hipError_t e = hipMalloc(&zeros[dev], (size_t)a.N * 4);
+      int n = zeros_n[dev] ? zeros_n[dev] : 256;
+      while (n < a.N) n *= 2;
+      float* z = nullptr;
+      hipError_t e = hipMalloc(&z, (size_t)n * 4);
+      if (e == hipSuccess) e = hipMemset(z, 0, (size_t)n * 4);
       if (e != hipSuccess) return e;
-      e = hipMemset(zeros[dev], 0, (size_t)a.N * 4);
-      if (e != hipSuccess) return e;
-      zeros_n[dev] = a.N;
+      zeros[dev] = z;
+      zeros_n[dev] = n;
     }
     bias = zeros[dev];
   }
   G8 g{(const bf16_t*)a.A, (const bf16_t*)a.W, bias, a.colsum, a.ln_stats, (bf16_t*)a.C, (int)a.M, a.N, a.K,
        (int)a.lda, (int)a.ldw, (int)a.ldc, a.N / 256, (int)(((a.M + 255) / 256) * (a.N / 256)), 0};
-  g.nt_store = (double)a.M * (double)a.ldc * 2.0 >= 128e6 ? 1 : 0;  // as launch_cfg: outputs larger than half the Infinity Cache
+  g.nt_store = output_exceeds_cache(a.M, a.ldc) ? 1 : 0;
   int n_cu = device_cu_count(dev);
   if (n_cu <= 0) n_cu = 256;
   const int grid = n_cu & ~7;

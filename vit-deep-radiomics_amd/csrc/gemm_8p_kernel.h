@@ -415,12 +415,8 @@ __global__ __launch_bounds__(512) void gemm_8p_kernel(G8 p) {
 template <int EPI, bool FOLD>
 hipError_t launch_8p_instance(const G8& g, int grid, int dev, hipStream_t s) {
   auto fn = gemm_8p_kernel<EPI, FOLD>;
-  static PerDeviceFlag attr;
-  if (!attr.done[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
-    if (e != hipSuccess) return e;
-    attr.done[dev] = true;
-  }
+  static KernelState st;
+  if (hipError_t e = raise_lds_limit(st, (const void*)fn, dev, LDS_TOTAL)) return e;
   hipLaunchKernelGGL(fn, dim3(grid), dim3(512), LDS_TOTAL, s, g);
   return hipGetLastError();
 }

@@ -1,6 +1,6 @@
 // bf16 MFMA GEMM kernels with fused epilogues for gfx950:  C[M,N] = epi(A[M,K] . W[N,K]^T)
-// (kernel templates + the launch helper; instantiated per tile variant by gemm.hip and gemm_ring4.hip so the library
-// builds in parallel)
+// (kernel templates + the kernel selection; instantiated per tile variant by gemm.hip and gemm_ring4.hip, two files so
+// that the library builds in parallel; from a GemmArgs to a launch: gemm_launch.hip)
 //
 // Replaces the nn.Linear calls under nn.MultiheadAttention / nn.TransformerEncoderLayer
 // (reference src/models_archs.py:130-135) and attn.qkv / attn.proj / mlp.fc1 / mlp.fc2 of the
@@ -21,10 +21,10 @@
 //      L2-resident source, 2 workgroups x 8 waves per CU): 66 GB/s per CU for half lines, 112 GB/s for whole lines.
 //      Weights are packed once at load (w_interleave_kernel), so this costs nothing per forward.
 #pragma once
-#include <cstdlib>
 #include <type_traits>
+#include <utility>
 
-#include "gemm_epi.h"
+#include "gemm_launch.h"
 
 namespace vdr {
 
@@ -770,235 +770,43 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, 4) void gemm_ring4p_kernel(G
   }
 }
 
-// PIPE: 3x = ring3 with x LDS slots, 4x = ring3k with x super-slots, 50 = ring4
-template <int WAVES_M, int WAVES_N, int PIPE, int E, int TAG = 0>
-static auto launch_pick() -> void (*)(GemmK) {
-  if constexpr (PIPE >= 50)
-    return gemm_ring4_kernel<WAVES_M, WAVES_N, E, TAG>;
-  else if constexpr (PIPE >= 40)
-    return gemm_ring3k_kernel<PIPE - 40, E>;
+// Kernel selection, all of the launch path that is templated: (row of the tile-variant table, epilogue, TAG, persistent
+// form) -> the kernel instantiation and its per-device launch state; a null fn where there is none.  A new tile variant
+// is one row of TILE_VARIANTS (vdr_kernels.h) and its id in the launch_tiles<...> list of gemm.hip or gemm_ring4.hip.
+template <TileFamily F, int WAVES_M, int WAVES_N, int DEPTH, int E, bool PERSISTENT, int TAG = 0>
+static GemmKernel kernel_instance(bool tag1) {
+  // the residual epilogues of ring4 have a second symbol, TAG 1 (GemmLaunch::tag1)
+  if constexpr (TAG == 0 && F == TILE_RING4 && epi_base(E) == EPI_BIAS_RESID)
+    if (tag1) return kernel_instance<F, WAVES_M, WAVES_N, DEPTH, E, PERSISTENT, 1>(false);
+  static KernelState st;
+  // the persistent form exists for the residual epilogue of ring4 (tuning builds: for every epilogue, variant 2xx)
+  if constexpr (PERSISTENT && F == TILE_RING4 && (VDR_TUNING_BUILD || epi_base(E) == EPI_BIAS_RESID))
+    return {gemm_ring4p_kernel<WAVES_M, WAVES_N, E, TAG>, &st};
+  else if constexpr (PERSISTENT)
+    return {};
+  else if constexpr (F == TILE_RING4)
+    return {gemm_ring4_kernel<WAVES_M, WAVES_N, E, TAG>, &st};
+  else if constexpr (F == TILE_RING3K)
+    return {gemm_ring3k_kernel<DEPTH, E>, &st};
   else
-    return gemm_ring3_kernel<WAVES_M, WAVES_N, PIPE - 30, E>;
+    return {gemm_ring3_kernel<WAVES_M, WAVES_N, DEPTH, E>, &st};
 }
 
-#ifdef VDR_GEMM_STAMPS
-inline unsigned long long* g_gemm_stamps = nullptr;  // tools/micro/gemm_stamps.hip
-#endif
-// the persistent form exists for the residual epilogue of ring4 (tuning builds: for every epilogue, variant 2xx)
-template <int WAVES_M, int WAVES_N, int PIPE, int E, int TAG = 0>
-static auto launch_pick_persistent() -> void (*)(GemmK) {
-#ifdef VDR_TUNING
-  if constexpr (PIPE >= 50) return gemm_ring4p_kernel<WAVES_M, WAVES_N, E, TAG>;
-#else
-  if constexpr (PIPE >= 50 && epi_base(E) == EPI_BIAS_RESID) return gemm_ring4p_kernel<WAVES_M, WAVES_N, E, TAG>;
-#endif
-  return launch_pick<WAVES_M, WAVES_N, PIPE, E, TAG>();
+// row ID, epilogue `epi` out of the list ES
+using GemmEpilogues = std::integer_sequence<int, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_QGELU, EPI_BIAS_TGELU, EPI_BIAS_RESID, EPI_BIAS_RESID32, EPI_SWIGLU, EPI_PATCH>;
+template <int ID, bool PERSISTENT, int... ES>
+static GemmKernel select_kernel(int epi, bool tag1, std::integer_sequence<int, ES...>) {
+  constexpr TileVariant R = *tile_variant(ID);
+  GemmKernel kn;
+  ((epi == ES ? (void)(kn = kernel_instance<R.family, R.waves_m, R.waves_n, R.depth, ES, PERSISTENT>(tag1)) : (void)0), ...);
+  return kn;
 }
 
-inline int g_gemm_ablation = 0;  // tuning builds only (variant / 100 of vdr_op_linear)
-inline int g_gemm_gn = -1;       // tuning builds only: column-group width override (variant / 1000 - 1)
-
-// integer tuning knob from the environment: read in tuning builds (-DVDR_TUNING, `make tuning`) only; the shipped
-// library has no environment dependence
-static inline int tuning_env(const char* name, int dflt) {
-#ifdef VDR_TUNING
-  const char* e = getenv(name);
-  return e && *e ? atoi(e) : dflt;
-#else
-  (void)name;
-  return dflt;
-#endif
-}
-
-template <int WAVES_M, int WAVES_N, int PIPE>
-static hipError_t launch_cfg(const GemmArgs& a, int epi, hipStream_t s) {
-  constexpr int BM = WAVES_M * 64, BN = WAVES_N * 64;
-  constexpr int NWV = PIPE >= 40 && PIPE < 50 ? 8 : WAVES_M * WAVES_N;
-  GemmK k;
-  k.A = (const bf16_t*)a.A;
-  k.W = (const bf16_t*)a.W;
-  k.w_il = a.w_interleaved;
-  k.bias = a.bias;
-  k.resid = (const bf16_t*)a.resid;
-  k.resid32 = a.resid32;
-  k.C32 = a.C32;
-  if (a.resid32 || a.C32) {  // the fp32 residual stream: its own instantiation of the residual kernels
-    if (epi != EPI_BIAS_RESID || !a.resid32 || !a.C32 || a.win_ws || (PIPE >= 40 && PIPE < 50)) return hipErrorInvalidValue;
-    epi = EPI_BIAS_RESID32;
-  }
-  k.gamma = a.gamma;
-  k.pos = a.pos;
-  k.C = (bf16_t*)a.C;
-  k.M = a.M;
-  k.N = a.N;
-  k.K = a.K;
-  k.lda = a.lda;
-  k.ldw = a.ldw;
-  k.ldc = a.ldc;
-  k.ldr = a.ldr;
-  k.rpg = a.omap.rpg;
-  k.gstride = a.omap.gstride;
-  k.off = a.omap.off;
-  const int64_t tiles_m = (a.M + BM - 1) / BM;
-  k.tiles_n = (a.N + BN - 1) / BN;
-  k.tiles_m = (int)tiles_m;
-  {
-    // column-group width: tiles are walked in groups of gn tile columns (tile_of) so that a group's W panels (BN x K
-    // bf16 each) stay in the XCD's 4 MB L2 next to the A row panels in flight.  Measured:
-    //   per launch, M = 50432, interleaved rounds (tools/kbench.py --variants (gn+1)*1000+26): qkv (9 columns, panel
-    //   393 KB) 0.192 ms row-major, 0.174 / 0.171 / 0.175 / 0.176 for gn = 2 / 3 / 4 / 5; fc1 (12 columns) 0.276
-    //   row-major, 0.266 / 0.265 / 0.266 for gn = 2 / 4 / 5, 0.275 for 6;
-    //   whole forward, same device (tools/ab_forward.py): ViT-B (K = 768) 10.54 ms row-major, 10.37 / 10.40 / 10.40 for
-    //   gn = 3 / 4 / 5; ViT-L/14 (K = 1024) 26.91 row-major, 26.47 / 26.64 for gn = 2 / 3; ViT-g/14 (K = 1536, 32 tile
-    //   columns in w12) 22.79 row-major, 20.09 / 20.07 for gn = 2 / 3 (-12 %).
-    // Rule: about 1.7 MB of W per group, i.e. gn = 4 / 3 / 2 for K = 768 / 1024 / 1536.  (Round 1 grouped only when W
-    // as a whole exceeded the L2; with the whole-line operand loads the L2 misses weigh more and qkv gains too.)
-    // K >= 3072 panels (>= 1.6 MB) give gn = 1: row-major, which is all a 3-column fc2 can use anyway.
-    VDR_KNOB int gn_env = tuning_env("VDR_GEMM_GN", -1);
-    const size_t panel = (size_t)BN * a.K * 2;
-    int gn = (int)((1700u << 10) / panel);
-    if (gn < 2 || gn >= k.tiles_n) gn = 0;  // a single column at a time re-reads A once per column: never better than row-major
-    k.gn = g_gemm_gn >= 0 ? g_gemm_gn : gn_env >= 0 ? gn_env : gn;
-  }
-  const int64_t nwg = tiles_m * k.tiles_n;
-  if (nwg <= 0 || nwg > 0x7fffffff) return hipErrorInvalidValue;
-  k.nwg = (int)nwg;
-  k.win_ws = a.win_ws;
-  k.win_g = a.win_g;
-  k.a_rpg = a.a_rpg;
-  k.a_gs = a.a_gs;
-  k.a_is = a.a_is;
-  k.out_f32 = a.out_f32;
-  if (a.patch_p) {
-    const int P = a.patch_p;
-    if (epi != EPI_PATCH || PIPE != 50 || (P != 8 && P != 16 && P != 32) || a.patch_g <= 0 || a.patch_C <= 0 || a.K != a.patch_C * P * P ||
-        a.M % ((int64_t)a.patch_g * a.patch_g) || a.a_rpg || ((uintptr_t)a.A & 15))
-      return hipErrorInvalidValue;
-    k.pg_ps = P == 8 ? 3 : P == 16 ? 4 : 5;
-    k.pg_g = a.patch_g;
-    k.pg_C = a.patch_C;
-  }
-  {
-    VDR_KNOB int nt_env = tuning_env("VDR_GEMM_NT", -1);
-    const bool big = (double)a.M * (double)a.ldc * 2.0 >= 128e6 && !a.resid;  // write-once output larger than half the Infinity Cache
-    k.nt_store = nt_env >= 0 ? nt_env : (big ? 1 : 0);
-  }
-  k.ln_stats = a.ln_stats;
-  k.colsum = a.colsum;
-  k.ln_part = a.ln_part;
-  k.part_stride = a.part_stride;
-  k.ln_fold = a.ln_stats || a.ln_cpart;
-  if (a.fin_stats) {  // producer-side finalisation: ring4 kernels, residual epilogue, rows stored where they are computed
-    if (PIPE < 50 || epi_base(epi) != EPI_BIAS_RESID || !a.ln_part || !a.fin_cnt || a.win_ws || (a.N & 63)) return hipErrorInvalidValue;
-    k.fin_stats = a.fin_stats;
-    k.fin_cnt = a.fin_cnt;
-    k.fin_groups = a.N / 64;
-    k.fin_eps = a.fin_eps;
-  }
-  if (a.ldc >= ((int64_t)1 << 24)) return hipErrorInvalidValue;  // (epilogue_bf16 addresses a wave tile with 32-bit byte offsets)
-  // (the residual epilogue, epilogue_resid: bf16 in place or out of place, no consumer-side fold, 32-bit row numbers)
-  if (epi_base(epi) == EPI_BIAS_RESID && (k.ln_fold || a.out_f32 || a.M >= ((int64_t)1 << 31))) return hipErrorInvalidValue;
-  if (a.ln_cpart) {
-    if ((PIPE >= 40 && PIPE < 50) || a.ln_groups < 1 || a.ln_groups > 16 || a.ln_stats) return hipErrorInvalidValue;
-    k.ln_cpart = a.ln_cpart;
-    k.ln_groups = a.ln_groups;
-    k.ln_cstride = a.ln_cstride;
-    k.ln_eps = a.ln_eps;
-  }
-  k.abl = g_gemm_ablation;
-#ifdef VDR_GEMM_STAMPS
-  k.stamps = g_gemm_stamps;
-#endif
-  if (PIPE >= 50 && a.a_rpg) return hipErrorInvalidValue;  // the two-stride A gather stays on ring3
-
-  dim3 grid((unsigned)k.nwg), block(NWV * 64);
-  const int dev = current_device_index();
-  if (dev < 0) return hipErrorInvalidDevice;
-  bool persistent = PIPE >= 50 && epi_base(epi) == EPI_BIAS_RESID;  // (see gemm_ring4p_kernel)
-#ifdef VDR_TUNING
-  {
-    VDR_KNOB int pers_env = tuning_env("VDR_GEMM_PERSISTENT", -1);
-    if (pers_env >= 0) persistent = persistent && pers_env;
-    if (pers_env == 2 && PIPE >= 50) persistent = true;  // every epilogue (experiments)
-    if ((k.abl & 2) && PIPE >= 50) persistent = true;
-  }
-#endif
-  const size_t staging = (size_t)WAVES_M * WAVES_N * 32 * 272;  // epilogue images (ring3 / ring4: one per wave)
-  size_t lds;
-  if (PIPE >= 50) {
-    lds = (size_t)2 * BM * 128 + (size_t)3 * BN * 64;
-    const size_t need = staging + (a.ln_cpart ? (size_t)BM * 8 : 0);
-    if (need > lds) lds = need;
-  } else if (PIPE >= 40) {
-    lds = (size_t)(BM + BN) * 64 * 2 * (PIPE - 40);
-    if (lds < (size_t)65536 + 4 * 32 * 272) lds = (size_t)65536 + 4 * 32 * 272;  // K reduction + staging
-  } else {
-    lds = (size_t)(BM + BN) * 64 * (PIPE - 30);
-    if (lds < staging) lds = staging;
-    if (a.ln_cpart) {  // (mean, rstd) of the tile's BM rows, behind the ring / staging area
-      k.stats_off = (int)lds;
-      lds += (size_t)BM * 8;
-    }
-  }
-#ifdef VDR_TUNING
-  {  // tools/: extra dynamic LDS per workgroup (e.g. 40000 on ring4: one workgroup per CU instead of two)
-    const int pad = tuning_env("VDR_GEMM_LDS_PAD", 0);
-    if (pad > 0) lds += (size_t)pad;
-  }
-#endif
-#define VDR_LAUNCH(E) VDR_LAUNCH_T(E, 0)
-#define VDR_LAUNCH_T(E, T)                                                                             \
-  case E + 100 * T: {                                                                                  \
-    auto fn = launch_pick<WAVES_M, WAVES_N, PIPE, E, T>();                                             \
-    if (persistent && launch_pick_persistent<WAVES_M, WAVES_N, PIPE, E, T>() != fn) {                  \
-      auto pfn = launch_pick_persistent<WAVES_M, WAVES_N, PIPE, E, T>();                               \
-      static int slots_dev[VDR_MAX_DEVICES] = {}; /* workgroups of this instantiation the chip holds at once */ \
-      int& slots = slots_dev[dev];                                                                     \
-      if (!slots) {                                                                                    \
-        int per_cu = 0;                                                                                \
-        const int n_cu = device_cu_count(dev);                                                         \
-        if (n_cu <= 0 ||                                                                               \
-            hipFuncSetAttribute((const void*)pfn, hipFuncAttributeMaxDynamicSharedMemorySize,          \
-                                (int)(lds > 65536 ? lds : 65536)) != hipSuccess ||                     \
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)pfn, (int)block.x, lds) != hipSuccess || \
-            per_cu <= 0)                                                                               \
-          return hipErrorUnknown;                                                                      \
-        slots = per_cu * n_cu;                                                                         \
-      }                                                                                                \
-      if (k.nwg > slots) {                                                                             \
-        fn = pfn;                                                                                      \
-        grid = dim3((unsigned)slots);                                                                  \
-      }                                                                                                \
-    }                                                                                                  \
-    static size_t lds_set[VDR_MAX_DEVICES][2] = {}; /* per kernel and device: the attribute is raised once, not per launch */ \
-    size_t& lset = lds_set[dev][grid.x != (unsigned)k.nwg];                                            \
-    if (lds > 65536 && lds > lset) {                                                                   \
-      hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                         (int)lds);                                                    \
-      if (e != hipSuccess) return e;                                                                   \
-      lset = lds;                                                                                      \
-    }                                                                                                  \
-    hipLaunchKernelGGL(fn, grid, block, lds, s, k);                                                    \
-    break;                                                                                             \
-  }
-  // (the residual GEMM with K > N -- fc2 -- launches the TAG 1 symbol of the same code: profiles tell it from the out-projection)
-  switch (epi + (PIPE >= 50 && epi_base(epi) == EPI_BIAS_RESID && a.K > a.N ? 100 : 0)) {
-    VDR_LAUNCH(EPI_BIAS)
-    VDR_LAUNCH(EPI_BIAS_GELU)
-    VDR_LAUNCH(EPI_BIAS_QGELU)
-    VDR_LAUNCH(EPI_BIAS_TGELU)
-    VDR_LAUNCH(EPI_BIAS_RESID)
-    VDR_LAUNCH_T(EPI_BIAS_RESID, 1)
-    VDR_LAUNCH(EPI_BIAS_RESID32)
-    VDR_LAUNCH_T(EPI_BIAS_RESID32, 1)
-    VDR_LAUNCH(EPI_SWIGLU)
-    VDR_LAUNCH(EPI_PATCH)
-    default:
-      return hipErrorInvalidValue;
-  }
-#undef VDR_LAUNCH
-#undef VDR_LAUNCH_T
-  return hipGetLastError();
+template <int... IDS>  // the launch of L on the kernels of its row, one of IDS
+static hipError_t launch_tiles(const GemmLaunch& L, hipStream_t s) {
+  GemmKernel plain, persistent;
+  ((L.row->id == IDS ? (void)(plain = select_kernel<IDS, false>(L.epi, L.tag1, GemmEpilogues()), persistent = select_kernel<IDS, true>(L.epi, L.tag1, GemmEpilogues())) : (void)0), ...);
+  return launch_built(L, plain, persistent, s);
 }
 
 }  // namespace vdr

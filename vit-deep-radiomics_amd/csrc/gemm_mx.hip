@@ -11,9 +11,8 @@
 // i.e. exactly the two ds_read_b128 the bf16 kernel issues for its two k-steps, concatenated.  The scales of a
 // unit (2 blocks x 64 rows of A and of W per wave) arrive by ONE extra 4-byte global_load_lds per wave into a
 // wave-private 256-byte region of the slot; a lane fetches the pair for its two row tiles with one ds_read_u16.
-#include <cstdlib>
 
-#include "gemm_epi.h"
+#include "gemm_launch.h"
 
 namespace vdr {
 
@@ -50,7 +49,7 @@ VDR_DEV void gemm_mx_body(const GemmK& p, char* smem) {
 
   const int wg = xcd_remap(blockIdx.x, p.nwg);
   int tm, tn;
-  tile_of(p, wg, tm, tn);  // column groups of gn tile columns (launch_mx_cfg), as in the bf16 kernels
+  tile_of(p, wg, tm, tn);  // column groups of gn tile columns (build_mx_launch), as in the bf16 kernels
   const int64_t m0 = (int64_t)tm * BM;
   const int n0 = tn * BN;
 
@@ -215,101 +214,27 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64, 4) void gemm_mx_kernel(GemmK
   gemm_mx_body<WAVES_M, WAVES_N, NST, EPI>(p, smem);
 }
 
-template <int WAVES_M, int WAVES_N, int NST>
-static hipError_t launch_mx_cfg(const GemmArgs& a, int epi, hipStream_t s) {
-  constexpr int BM = WAVES_M * 64, BN = WAVES_N * 64, NW = WAVES_M * WAVES_N;
-  GemmK k{};
-  k.A = (const bf16_t*)a.A;
-  k.W = (const bf16_t*)a.W;
-  k.w_il = a.w_interleaved;
-  k.bias = a.bias;
-  k.resid = (const bf16_t*)a.resid;
-  k.gamma = a.gamma;
-  k.pos = a.pos;
-  k.C = (bf16_t*)a.C;
-  k.M = a.M;
-  k.N = a.N;
-  k.K = a.K;
-  k.lda = a.lda;
-  k.ldw = a.ldw;
-  k.ldc = a.ldc;
-  k.ldr = a.ldr;
-  k.rpg = a.omap.rpg;
-  k.gstride = a.omap.gstride;
-  k.off = a.omap.off;
-  const int64_t tiles_m = (a.M + BM - 1) / BM;
-  k.tiles_n = (a.N + BN - 1) / BN;
-  k.tiles_m = (int)tiles_m;
-  {
-    // tile order: about 1.7 MB of W payload per column group (gemm_kernels.h, launch_cfg; an e4m3 panel is BN x K bytes)
-    int gn = (int)((1700u << 10) / ((size_t)BN * a.K));
-    if (gn < 2 || gn >= k.tiles_n) gn = 0;
-    k.gn = gn;
-#ifdef VDR_TUNING
-    if (const char* e = getenv("VDR_MX_GN")) k.gn = atoi(e);
-#endif
-  }
-  const int64_t nwg = tiles_m * k.tiles_n;
-  if (nwg <= 0 || nwg > 0x7fffffff) return hipErrorInvalidValue;
-  k.nwg = (int)nwg;
-  k.ln_part = a.ln_part;
-  k.part_stride = a.part_stride;
-  k.sA = (const uint8_t*)a.a_scale;
-  k.sW = (const uint8_t*)a.w_scale;
-  k.sa_rows = mx_rows_pad(a.M);
-  k.sw_rows = mx_rows_pad(a.N);
-  k.sC = (uint8_t*)a.c_scale;
-  k.sc_rows = mx_rows_pad(a.M);
-  const size_t ring = (size_t)NST * ((size_t)(BM + BN) * 64 + (size_t)NW * 256);
-  const size_t stg = (size_t)NW * 32 * 272;
-  const size_t lds = ring > stg ? ring : stg;
-  const dim3 grid((unsigned)nwg), block(NW * 64);
-  const int dev = current_device_index();
-  if (dev < 0) return hipErrorInvalidDevice;
-#define VDR_LAUNCH_MX(E)                                                                                          \
-  case E: {                                                                                                       \
-    auto fn = gemm_mx_kernel<WAVES_M, WAVES_N, NST, E>;                                                           \
-    static PerDeviceFlag attr; /* per instantiation and device: lds is a compile-time constant of it */           \
-    if (lds > 65536 && !attr.done[dev]) {                                                                         \
-      hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);  \
-      if (e != hipSuccess) return e;                                                                              \
-      attr.done[dev] = true;                                                                                      \
-    }                                                                                                             \
-    hipLaunchKernelGGL(fn, grid, block, lds, s, k);                                                               \
-    break;                                                                                                        \
-  }
-  switch (epi) {
-    VDR_LAUNCH_MX(EPI_BIAS)
-    VDR_LAUNCH_MX(EPI_BIAS_GELU)
-    VDR_LAUNCH_MX(EPI_BIAS_RESID)
-    VDR_LAUNCH_MX(EPI_SWIGLU)
-    VDR_LAUNCH_MX(EPI_BIAS_GELU_MX)
-    VDR_LAUNCH_MX(EPI_SWIGLU_MX)
-    default:
-      return hipErrorInvalidValue;
-  }
-#undef VDR_LAUNCH_MX
-  return hipGetLastError();
+// kernel selection: MX row ID of TILE_VARIANTS, epilogue `epi` out of the list ES
+template <int ID, int E>
+static KernelState mx_state;
+template <int ID, int... ES>
+static GemmKernel mx_select(int epi) {
+  constexpr TileVariant R = *tile_variant(ID, true);
+  GemmKernel kn;
+  ((epi == ES ? (void)(kn = {gemm_mx_kernel<R.waves_m, R.waves_n, R.depth, ES>, &mx_state<ID, ES>}) : (void)0), ...);
+  return kn;
+}
+template <int... IDS>
+static hipError_t launch_mx_tiles(const GemmLaunch& L, hipStream_t s) {
+  GemmKernel kn;
+  ((L.row->id == IDS ? (void)(kn = mx_select<IDS, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_SWIGLU, EPI_BIAS_GELU_MX, EPI_SWIGLU_MX>(L.epi)) : (void)0), ...);
+  return launch_built(L, kn, GemmKernel(), s);
 }
 
 hipError_t launch_gemm_mx(const GemmArgs& a, int epilogue, int variant, hipStream_t s) {
-  if (a.K <= 0 || (a.K & 63) || (a.N & 63) || a.M <= 0 || !a.a_scale || !a.w_scale) return hipErrorInvalidValue;
-  if (a.ln_stats || a.win_ws || a.a_rpg || a.out_f32 || a.M >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-  if (a.c_scale) {  // MX output
-    if (epilogue == EPI_BIAS_GELU) epilogue = EPI_BIAS_GELU_MX;
-    else if (epilogue == EPI_SWIGLU) epilogue = EPI_SWIGLU_MX;
-    else return hipErrorInvalidValue;
-  }
-  switch (variant) {
-    case 0:
-      return launch_mx_cfg<2, 4, 3>(a, epilogue, s);  // 128x256, 8 waves, 3 x 26 KB, 2 workgroups per CU
-    case 1:
-      return launch_mx_cfg<4, 4, 3>(a, epilogue, s);  // 256x256, 16 waves, 3 x 36 KB
-    case 2:
-      return launch_mx_cfg<2, 2, 3>(a, epilogue, s);  // 128x128, 4 waves, 3 x 17 KB, 3 workgroups per CU
-    default:
-      return hipErrorInvalidValue;
-  }
+  GemmLaunch L;
+  if (hipError_t e = build_mx_launch(a, epilogue, variant, &L)) return e;
+  return launch_mx_tiles<0, 1, 2>(L, s);
 }
 
 }  // namespace vdr

@@ -769,14 +769,12 @@ struct Scope {  // (m = nullptr: an op entry point, nothing is booked)
   }
 };
 
-// tile-variant families of launch_gemm (gemm.hip, gemm_ring4.hip, gemm_8p.hip)
-bool ring3_variant(int v) { return v >= 22 && v <= 24; }      // ring3: 128x256, 256x256, 128x128 tiles
-constexpr int RING3K_VARIANT = 25;                            // ring3k: 128x128, the K loop split across two wave groups
-bool ring4_variant(int v) { return v >= 26 && v <= 29; }      // ring4: 128x256, 256x256, 128x128, 64x128 tiles
-bool ring4_big_variant(int v) { return v >= 26 && v <= 28; }  //   its tiles of 128 rows and more
-constexpr int VARIANT_8P = 31;                                // 8-phase: 256x256, one persistent workgroup per CU
+// questions about a tile variant of launch_gemm: lookups in the one table of them (TILE_VARIANTS, vdr_kernels.h)
+bool variant_is(int v, TileFamily f) { const TileVariant* r = tile_variant(v); return r && r->family == f; }
+bool ring4_variant(int v) { return variant_is(v, TILE_RING4); }
+bool ring4_big_variant(int v) { return ring4_variant(v) && tile_variant(v)->bm() >= 128; }  // the forward gives the patch gather and the in-GEMM statistics to these only
 // the consumers of the LayerNorm fold that finalise the producers' partials themselves (GemmArgs::ln_cpart)
-bool ln_cpart_variant(int v) { return ring3_variant(v) || ring4_big_variant(v); }
+bool ln_cpart_variant(int v) { return variant_is(v, TILE_RING3) || ring4_big_variant(v); }
 
 // tile configuration per GEMM class; VDR_GEMM_VARIANT overrides all of them (tuning aid)
 int gemm_variant_for(int cls, int64_t M = 1 << 30, int N = 1 << 30) {
@@ -1330,7 +1328,8 @@ hipError_t relpos_products(const void* qkv, const void* table, float* T, int64_t
   ga.a_gs = (int64_t)3 * heads * 64;
   ga.a_is = 64;
   ga.out_f32 = 1;
-  return launch_gemm(ga, EPI_BIAS, ga.N <= 128 ? 24 : 22, s);  // ring3: 128x128 tiles for the 64-column window table, 128x256 for the global one
+  // ring3 (the two-stride A gather): 128x128 tiles for the 64-column window table, 128x256 for the global one
+  return launch_gemm(ga, EPI_BIAS, ga.N <= 128 ? VARIANT_RING3_128x128 : VARIANT_RING3_128x256, s);
 }
 
 int run_sam(vdr_model* m, hipStream_t s, const Carve& w, int mb, int out_dtype, char* out, bool tokens_only) {
@@ -2089,7 +2088,7 @@ int vdr_ln_fold_weights(const float* W, const float* b, const float* gamma, cons
 }
 
 static bool ln_variant_ok(int variant, bool allow_31) {
-  return ring3_variant(variant) || variant == RING3K_VARIANT || ring4_variant(variant) || (allow_31 && variant == VARIANT_8P);
+  return tile_variant(variant) && (allow_31 || variant != VARIANT_8P);
 }
 
 int vdr_op_linear_ln_stats(const void* x, const void* W, const float* bias, const void* resid, const float* gamma, void* y,

@@ -3,12 +3,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+#include <mutex>
+
 // tuning knobs (-DVDR_TUNING builds read VDR_* environment variables): re-read on every call there, so that one
 // process can alternate settings between forwards (interleaved A/B, tools/ab_forward.py); constants in the shipped build
 #ifdef VDR_TUNING
 #define VDR_KNOB const
+constexpr bool VDR_TUNING_BUILD = true;
 #else
 #define VDR_KNOB static const
+constexpr bool VDR_TUNING_BUILD = false;
 #endif
 
 namespace vdr {
@@ -22,9 +27,6 @@ static inline int current_device_index() {
   int d = -1;
   return hipGetDevice(&d) == hipSuccess && d >= 0 && d < VDR_MAX_DEVICES ? d : -1;
 }
-struct PerDeviceFlag {
-  bool done[VDR_MAX_DEVICES] = {};
-};
 static inline int device_cu_count(int dev) {  // 0 on failure
   static int n[VDR_MAX_DEVICES] = {};
   if (dev < 0 || dev >= VDR_MAX_DEVICES) return 0;
@@ -34,6 +36,85 @@ static inline int device_cu_count(int dev) {  // 0 on failure
   }
   return n[dev];
 }
+// That state, one object per kernel instantiation (a static of its launcher).  Two host threads may launch the same kernel
+// at once: steady state is one atomic load; first use takes a lock (the attribute) or asks for the same occupancy twice.
+struct KernelState {
+  std::atomic<int> lds_limit[VDR_MAX_DEVICES] = {};  // what hipFuncAttributeMaxDynamicSharedMemorySize was raised to (0: never)
+  std::atomic<int> slots[VDR_MAX_DEVICES] = {};      // persistent kernels: workgroups of it the chip holds at once (0: not asked yet)
+};
+// Before a launch with `lds` bytes of dynamic LDS: above 64 KB the kernel has to opt in, once per device -- and again when
+// a larger size arrives for the same kernel.  No call at or below 64 KB, none at steady state.
+static inline hipError_t raise_lds_limit(KernelState& st, const void* fn, int dev, size_t lds) {
+  if (lds <= 65536 || (int)lds <= st.lds_limit[dev].load(std::memory_order_acquire)) return hipSuccess;
+  static std::mutex first_use;
+  std::lock_guard<std::mutex> lock(first_use);
+  if ((int)lds <= st.lds_limit[dev].load(std::memory_order_relaxed)) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e == hipSuccess) st.lds_limit[dev].store((int)lds, std::memory_order_release);
+  return e;
+}
+// workgroups of `block` threads and `lds` bytes of a persistent kernel that the device holds at once; 0 on failure
+static inline int persistent_slots(KernelState& st, const void* fn, int dev, int block, size_t lds) {
+  int slots = st.slots[dev].load(std::memory_order_relaxed), per_cu = 0;
+  const int n_cu = slots ? 0 : device_cu_count(dev);
+  if (slots || n_cu <= 0 || raise_lds_limit(st, fn, dev, lds) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, lds) != hipSuccess || per_cu <= 0)
+    return slots;
+  st.slots[dev].store(per_cu * n_cu, std::memory_order_relaxed);
+  return per_cu * n_cu;
+}
+
+// ---- the tile variants of launch_gemm and launch_gemm_mx: one row each, read by the launch code (gemm_launch.hip), by the
+// kernel selection (gemm_kernels.h, gemm_mx.hip) and by the forward's variant choice (vdr_api.hip)
+// families: ring3, ring3k (its K loop split across two wave groups of the workgroup) and ring4 (both operands staged in whole
+// 128-B lines) of gemm_kernels.h, the 8-phase kernel (gemm_8p.hip), MX-fp8 operands (gemm_mx.hip: launch_gemm_mx's numbers)
+enum TileFamily { TILE_RING3, TILE_RING3K, TILE_RING4, TILE_8P, TILE_MX };
+// what a GemmArgs may ask of a variant (the launch refuses the rest)
+enum TileCap : unsigned {
+  CAP_LN_CPART = 1,     // finalises the LayerNorm partials of its rows itself (GemmArgs::ln_cpart)
+  CAP_FIN_STATS = 2,    // producer-side finalisation behind the residual epilogue (GemmArgs::fin_stats)
+  CAP_PATCH = 4,        // im2col-free patchify in the operand loader (GemmArgs::patch_p)
+  CAP_A_RPG = 8,        // A rows gathered with two strides (GemmArgs::a_rpg)
+  CAP_RESID32 = 16,     // the fp32 residual stream (GemmArgs::resid32 / C32)
+  CAP_PERSISTENT = 32,  // has a persistent form (gemm_ring4p_kernel)
+  RING3_CAPS = CAP_LN_CPART | CAP_A_RPG | CAP_RESID32,
+  RING4_CAPS = CAP_LN_CPART | CAP_FIN_STATS | CAP_PATCH | CAP_RESID32 | CAP_PERSISTENT,
+};
+
+struct TileVariant {
+  int id;
+  TileFamily family;
+  int waves_m, waves_n;  // a wave owns 64 x 64 of the tile (8-phase: 128 x 64)
+  int depth;             // ring depth: LDS slots (ring3, MX), super-slots (ring3k), W slots (ring4), K-tile buffers (8-phase)
+  unsigned caps;
+  constexpr bool can(unsigned c) const { return (caps & c) == c; }
+  constexpr int bm() const { return waves_m * (family == TILE_8P ? 128 : 64); }
+  constexpr int bn() const { return waves_n * 64; }
+  constexpr int block() const { return waves_m * waves_n * 64 * (family == TILE_RING3K ? 2 : 1); }  // threads (ring3k: two K-groups of waves)
+};
+
+// (variants 0-21, the earlier rungs of the ladder in DESIGN.md, are no longer built; 30, the persistent stream kernel of round 3, lives in tools/micro/)
+constexpr TileVariant TILE_VARIANTS[] = {
+    {22, TILE_RING3, 2, 4, 3, RING3_CAPS},  // 128x256, 8 waves, 3 x 24 KB, 2 WG/CU
+    {23, TILE_RING3, 4, 4, 3, RING3_CAPS},  // 256x256, 16 waves, 3 x 32 KB
+    {24, TILE_RING3, 2, 2, 3, RING3_CAPS},  // 128x128, 4 waves, 3 x 16 KB, 3 WG/CU
+    {25, TILE_RING3K, 2, 2, 3, CAP_A_RPG},  // 128x128 tile, 8 waves = 2 K-groups x (2x2), 3 x 32 KB
+    {26, TILE_RING4, 2, 4, 3, RING4_CAPS},  // 128x256, 8 waves, 2 x 16 KB (A) + 3 x 16 KB (W), 2 WG/CU
+    {27, TILE_RING4, 4, 4, 3, RING4_CAPS},  // 256x256, 16 waves, 2 x 32 KB + 3 x 16 KB
+    {28, TILE_RING4, 2, 2, 3, RING4_CAPS},  // 128x128, 4 waves, 2 x 16 KB + 3 x 8 KB, 2 WG/CU
+    {29, TILE_RING4, 1, 2, 3, RING4_CAPS},  // 64x128, 2 waves, 2 x 8 KB + 3 x 8 KB: launches of a few hundred rows x 768 columns
+    {31, TILE_8P, 2, 4, 2, 0},              // 256x256 tile, 8 waves, one persistent workgroup per CU, plain W layout
+    // launch_gemm_mx's own numbering
+    {0, TILE_MX, 2, 4, 3, 0},  // 128x256, 8 waves, 3 x 26 KB, 2 workgroups per CU
+    {1, TILE_MX, 4, 4, 3, 0},  // 256x256, 16 waves, 3 x 36 KB
+    {2, TILE_MX, 2, 2, 3, 0},  // 128x128, 4 waves, 3 x 17 KB, 3 workgroups per CU
+};
+constexpr const TileVariant* tile_variant(int id, bool mx = false) {  // null: no such variant
+  for (const TileVariant& r : TILE_VARIANTS)
+    if (r.id == id && (r.family == TILE_MX) == mx) return &r;
+  return nullptr;
+}
+constexpr int VARIANT_RING3_128x256 = 22, VARIANT_RING3_128x128 = 24, VARIANT_8P = 31;  // the variants other code names
 
 // row r of a compact [R, *] view  <->  row (r / rpg) * gstride + off + (r % rpg) of a token buffer
 struct RowMap {
@@ -46,7 +127,7 @@ static inline RowMap identity_map() { return RowMap{1 << 30, 0, 0}; }
 enum Epilogue { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_BIAS_RESID = 2, EPI_SWIGLU = 3, EPI_PATCH = 4,
                 // internal to gemm_mx.hip: GELU / SwiGLU with the output re-quantised to MX-fp8
                 EPI_BIAS_GELU_MX = 5, EPI_SWIGLU_MX = 6,
-                // internal to launch_cfg: EPI_BIAS_RESID with the residual stream kept in fp32 (GemmArgs::resid32 / C32)
+                // internal to build_gemm_launch: EPI_BIAS_RESID with the residual stream kept in fp32 (GemmArgs::resid32 / C32)
                 EPI_BIAS_RESID32 = 7,
                 // EPI_BIAS_GELU with another activation (vdr_dev.h): QuickGELU (CLIP) and tanh-GELU (SigLIP).  The public
                 // vdr_epilogue values are these numbers
