@@ -561,6 +561,44 @@ int vdr_op_attention_pool(const float* q, const void* kv, int64_t ldkv, void* ou
 int vdr_op_attention_relpos(const void* qkv, const float* rel_pos_h, const float* rel_pos_w, float* rel, void* out,
                             int batch, int S, int heads, void* stream);
 
+/* ---- the window path of a SAM / MedSAM block and the neck's 3 x 3 convolution, step by step -----------------------------
+ * segment_anything Block.forward: norm1, window_partition, attention, window_unpartition, the residual add; Neck: the
+ * second Conv2d (3 x 3, padding 1).  Each entry point is the argument builder and the launcher vdr_forward itself runs
+ * for that step (csrc/vdr_api.hip: sam_ln_args, sam_ln_mx, sam_proj_args, launch_im2col3), on caller buffers.
+ * Geometry: `batch` images of g x g tokens, row b*g*g + y*g + x ("token order"); ws x ws windows, nw = ceil(g / ws) a side,
+ * the last window of a row / column padded when ws does not divide g (g < ws: one partly filled window).  "Windowed
+ * order" is window_partition's: row ((b*nw + y/ws)*nw + x/ws)*ws*ws + (y%ws)*ws + x%ws, wrows = batch*nw*nw*ws*ws rows in
+ * all; rows whose (y, x) falls outside the grid are padding rows.
+ * Refused before the device is touched: null pointers ("null argument"), batch < 1, g < 1, ws < 1 ("bad shape"), 2^31 or
+ * more windowed rows, a pointer that is not 16-byte aligned (VDR_ERR_INVALID); the width constraints named below
+ * (VDR_ERR_UNSUPPORTED). */
+
+/* norm1 + window_partition: x bf16 [batch*g*g, D], token order -> y bf16 [wrows, D], windowed order; gamma / beta fp32 [D].
+ * Row arithmetic and bits of vdr_op_layernorm.  Padding rows of y are NOT written: the caller zeroes them (vdr_forward: one
+ * memset per forward).  D % 4 == 0, D <= 2048. */
+int vdr_op_layernorm_window(const void* x, void* y, const float* gamma, const float* beta, int batch, int g, int ws, int D,
+                            float eps, void* stream);
+/* The same with MX-fp8 output (vdr_op_layernorm_mx's arithmetic): payload q [wrows, D] bytes, scales the array of an MX
+ * tensor of wrows rows (vdr_mx_scale_bytes(wrows, D); row r of the WINDOWED order owns the bytes the layout above gives
+ * row r).  Payload and scale bytes of padding rows, and the scale bytes of rows wrows .. rows_pad - 1, are not written.
+ * D % 32 == 0, D <= 2048. */
+int vdr_op_layernorm_mx_window(const void* x, const float* gamma, const float* beta, float eps, int batch, int g, int ws, int D,
+                               void* q, void* scales, void* stream);
+/* attn.proj + window_unpartition + the residual add: y[t] = resid[t] + x[m] . W^T + bias for every windowed row m that is
+ * no padding row, t its token-order row.
+ *   x [wrows, K] bf16, windowed order (padding rows are multiplied but dropped: any bits, NaN included);  W [N, K] bf16
+ *   (PyTorch layout, as vdr_op_linear);  bias fp32 [N] or NULL;  resid, y bf16 [batch*g*g, N], token order; y may be resid
+ *   variant: 0 = the tile variant vdr_forward picks for this out-projection, or 22..29
+ *   part non-NULL (N % 64 == 0, part_stride >= batch*g*g): the LayerNorm partials of y's rows as vdr_op_linear_ln_stats
+ *   writes them, part [N/64][part_stride][2] fp32, indexed by the TOKEN-order row; rows >= batch*g*g are not written.
+ * K % 64 == 0, N % 8 == 0.  A valid row's bits are those of vdr_op_linear (VDR_EPI_BIAS_RESID) on the same variant. */
+int vdr_op_linear_window(const void* x, const void* W, const float* bias, const void* resid, void* y, int batch, int g, int ws,
+                         int N, int K, int variant, float* part, int64_t part_stride, void* stream);
+/* The neck's 3 x 3 / padding 1 im2col: x bf16 [batch*g*g, C] (NHWC tokens) -> col bf16 [batch*g*g, 9*C], tap-major:
+ * col[r][(ky*3 + kx)*C + c] = x[(b, y + ky - 1, x + kx - 1)][c], zero outside the image's own grid -- the operand layout
+ * "neck.2.weight" is packed for ([C_out][(ky*3 + kx)*C_in + c]).  Pure data movement.  C % 8 == 0. */
+int vdr_op_im2col3(const void* x, void* col, int batch, int g, int C, void* stream);
+
 /* DINOv2 / transformers interpolate_pos_encoding: the patch rows of a learned position table resampled from a
  * gh0 x gw0 grid to gh x gw (bicubic, A = -0.75, align_corners = False, size = (gh, gw), no antialias, border
  * indices clamped).  pos, out: device fp32, [gh0*gw0, D] and [gh*gw, D], row-major over (y, x).  No CLS row.

@@ -1,7 +1,8 @@
 """CPU: what launch_gemm / launch_gemm_mx refuse, and the launch shape they derive for what they accept.
 
 The refusals between a GemmArgs and a kernel keep a wrong launch from becoming a wrong result or a fault, and most of
-them cannot be reached from the public ops (a_rpg, patch_p, win_ws, out_f32, resid32, fin_stats, the 2^24 / 2^31 limits);
+them cannot be reached from the public ops (a_rpg, patch_p, out_f32, resid32, fin_stats, the 2^24 / 2^31 limits; win_ws is
+reachable since vdr_op_linear_window, whose own checks come first: tests/test_sam_ops_cpu.py, tests/test_sam_ops_gpu.py);
 the launch shape (tile counts, column-group width, non-temporal stores, LDS bytes, block size, persistent form) cannot be
 seen in any output.  tests/gemm_launch_cases.cpp calls the launchers with dummy buffers on a machine without a GPU -- an
 accepted launch ends in hipErrorInvalidDevice (101) after every check has run, a refused one in hipErrorInvalidValue (1)

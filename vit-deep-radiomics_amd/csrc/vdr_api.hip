@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <string>
@@ -949,9 +950,16 @@ int gemm(vdr_model* m, hipStream_t s, int cls, GemmArgs g, int epi, const LnFold
   return VDR_OK;
 }
 
+// one LayerNorm launch of the forward, booked under kernel class `cls`
+int layernorm(vdr_model* m, hipStream_t s, int cls, const LnArgs& a) {
+  Scope sc(m, s, cls, 0.0, (double)a.rows * a.D * ((a.in_bf16 ? 2 : 4) + (a.out_bf16 ? 2 : 4)));
+  VDR_TRY(launch_layernorm(a, s), "layernorm");
+  return VDR_OK;
+}
+
 int layernorm(vdr_model* m, hipStream_t s, int cls, const void* x, int in_bf16, void* y, int out_bf16,
               const float* gw, const float* gb, int64_t rows, RowMap imap, const float* clsrc = nullptr,
-              int cls_period = 0, int width = 0, int64_t ldy = 0, int win_ws = 0, int win_g = 0) {
+              int cls_period = 0, int width = 0, int64_t ldy = 0) {
   LnArgs a{};
   a.x = x;
   a.in_bf16 = in_bf16;
@@ -967,11 +975,7 @@ int layernorm(vdr_model* m, hipStream_t s, int cls, const void* x, int in_bf16, 
   a.cls = clsrc;
   a.cls_period = cls_period;
   a.ldy = ldy;
-  a.win_ws = win_ws;  // (SAM window blocks: the output rows in window-partition order)
-  a.win_g = win_g;
-  Scope sc(m, s, cls, 0.0, (double)rows * a.D * ((in_bf16 ? 2 : 4) + (out_bf16 ? 2 : 4)));
-  VDR_TRY(launch_layernorm(a, s), "layernorm");
-  return VDR_OK;
+  return layernorm(m, s, cls, a);
 }
 
 // tile configuration of the MX-fp8 GEMM per class and shape (VDR_MX_VARIANT overrides)
@@ -1332,6 +1336,58 @@ hipError_t relpos_products(const void* qkv, const void* table, float* T, int64_t
   return launch_gemm(ga, EPI_BIAS, ga.N <= 128 ? VARIANT_RING3_128x128 : VARIANT_RING3_128x256, s);
 }
 
+// ---- the window steps of a SAM block, built in one place for run_sam and for the vdr_op_*_window entry points ----------
+// `batch` grids of g x g tokens in ws x ws windows, nw = ceil(g / ws) a side, the border windows padded: rows of the
+// window-partition order per grid (ws = 0, a global block: the grid itself)
+int64_t sam_window_rows(int g, int ws) {
+  if (ws <= 0) return (int64_t)g * g;
+  const int64_t nw = (g + ws - 1) / ws;
+  return nw * nw * ws * ws;
+}
+
+// norm1: tokens x [batch * g * g, D] bf16 -> y bf16, in window-partition order (padding rows are not written) or, ws = 0, as they are
+LnArgs sam_ln_args(const void* x, void* y, const float* gw, const float* gb, float eps, int batch, int g, int ws, int D) {
+  LnArgs a{};
+  a.x = x;
+  a.in_bf16 = 1;
+  a.y = y;
+  a.out_bf16 = 1;
+  a.gamma = gw;
+  a.beta = gb;
+  a.rows = (int64_t)batch * g * g;
+  a.D = D;
+  a.eps = eps;
+  a.imap = identity_map();
+  a.omap = identity_map();
+  a.win_ws = ws;
+  a.win_g = ws ? g : 0;
+  return a;
+}
+
+// the same with MX-fp8 output: the scale array is that of a tensor of batch * sam_window_rows(g, ws) rows
+hipError_t sam_ln_mx(const void* x, const float* gw, const float* gb, float eps, int batch, int g, int ws, int D, void* q,
+                     void* scales, hipStream_t s) {
+  return launch_ln_mx(x, gw, gb, eps, (int64_t)batch * g * g, D, q, scales, s, ws, g, batch * sam_window_rows(g, ws));
+}
+
+// the out-projection: y[unpart(r)] = resid[unpart(r)] + a[r] . W^T + bias over the batch * sam_window_rows(g, ws) rows of a
+// (padding rows dropped; ws = 0: unpart is the identity), y may be resid; part non-null: the LayerNorm partials of y's rows
+GemmArgs sam_proj_args(const void* a, const void* W, const float* bias, const void* resid, void* y, int batch, int g, int ws,
+                       int N, int K, float* part, int64_t part_stride) {
+  GemmArgs ga = linear(a, W, y, batch * sam_window_rows(g, ws), N, K, EPI_BIAS_RESID);
+  ga.bias = bias;
+  ga.resid = resid;
+  if (ws) {
+    ga.win_ws = ws;
+    ga.win_g = g;
+  }
+  if (part) {
+    ga.ln_part = part;
+    ga.part_stride = part_stride;
+  }
+  return ga;
+}
+
 int run_sam(vdr_model* m, hipStream_t s, const Carve& w, int mb, int out_dtype, char* out, bool tokens_only) {
   const vdr_config& c = m->cfg;
   const int D = c.dim, H = c.heads, C = c.neck_chans;
@@ -1355,14 +1411,12 @@ int run_sam(vdr_model* m, hipStream_t s, const Carve& w, int mb, int out_dtype, 
     if (fp8) {
       {
         Scope sc(m, s, VDR_K_LAYERNORM, 0.0, (double)M * D * 3);
-        VDR_TRY(launch_ln_mx(w.x, L.n1w, L.n1b, c.ln_eps, M, D, hbuf, w.hs, s, glob ? 0 : ws, g, T), "layernorm_mx(window)");
+        VDR_TRY(sam_ln_mx(w.x, L.n1w, L.n1b, c.ln_eps, mb, g, glob ? 0 : ws, D, hbuf, w.hs, s), "layernorm_mx(window)");
       }
       if ((rc = gemm_mx(m, s, VDR_K_GEMM_QKV, hbuf, w.hs, L.qkv_q.get(), L.qkv_s.get(), L.bqkv, nullptr, nullptr, w.qkv, nullptr, T, 3 * D, D, EPI_BIAS)))
         return rc;
     } else {
-      if ((rc = layernorm(m, s, VDR_K_LAYERNORM, w.x, 1, hbuf, 1, L.n1w, L.n1b, M, identity_map(), nullptr, 0, 0, 0, glob ? 0 : ws,
-                          glob ? 0 : g)))
-        return rc;
+      if ((rc = layernorm(m, s, VDR_K_LAYERNORM, sam_ln_args(w.x, hbuf, L.n1w, L.n1b, c.ln_eps, mb, g, glob ? 0 : ws, D)))) return rc;
       GemmArgs qkv = linear(hbuf, L.wqkv, w.qkv, T, 3 * D, D, EPI_BIAS);
       qkv.bias = L.bqkv;
       qkv.a_rows = w.Mp;
@@ -1376,17 +1430,7 @@ int run_sam(vdr_model* m, hipStream_t s, const Carve& w, int mb, int out_dtype, 
     }
     {
       // (not through gemm(): the profiler books T rows of A, the windowed ones with their padding, but M output rows)
-      GemmArgs ga = linear(w.o, L.wproj, w.x, T, D, D, EPI_BIAS_RESID);
-      ga.bias = L.bproj;
-      ga.resid = w.x;
-      if (!glob) {
-        ga.win_ws = ws;
-        ga.win_g = g;
-      }
-      if (m->ln_fuse) {
-        ga.ln_part = w.part;
-        ga.part_stride = w.Mp;
-      }
+      GemmArgs ga = sam_proj_args(w.o, L.wproj, L.bproj, w.x, w.x, mb, g, glob ? 0 : ws, D, D, m->ln_fuse ? w.part : nullptr, w.Mp);
       Scope sc(m, s, VDR_K_GEMM_PROJ, 2.0 * T * D * D, 2.0 * ((double)T * D + (double)D * D + 2.0 * M * D));
       VDR_TRY(launch_gemm_w(m, ga, EPI_BIAS_RESID, gemm_variant_for(VDR_K_GEMM_PROJ, ga.M, ga.N), s), "proj gemm");
       m->stats_fresh = false;  // (window un-partition scatters the rows: their statistics are finalised by ln_consumer's launch)
@@ -2322,6 +2366,68 @@ int vdr_op_attention_relpos(const void* qkv, const float* rel_pos_h, const float
   OP_TRY(relpos_products(qkv, table, rel, tokens, S, heads, (hipStream_t)stream), "relpos");
   OP_TRY(launch_attention_relpos(qkv, rel, out, batch, S, heads, (hipStream_t)stream, env_int("VDR_RELPOS_ANY", 0)), "attention_relpos");
   return VDR_OK;
+}
+
+// ---- the SAM window path at op level: run_sam's own argument builders (sam_ln_args, sam_ln_mx, sam_proj_args) and launchers
+// on caller buffers
+static bool aligned16(std::initializer_list<const void*> ps) {
+  uintptr_t u = 0;
+  for (const void* q : ps) u |= (uintptr_t)q;
+  return (u & 15) == 0;
+}
+// the kernels index rows with 32-bit arithmetic (g * g, the windowed row number)
+static bool window_rows_ok(int batch, int g, int ws) {
+  return g <= 32768 && ws <= 32768 && (int64_t)batch * sam_window_rows(g, ws) < ((int64_t)1 << 31);
+}
+
+int vdr_op_layernorm_window(const void* x, void* y, const float* gamma, const float* beta, int batch, int g, int ws, int D,
+                            float eps, void* stream) {
+  if (!x || !y || !gamma || !beta) return fail(nullptr, VDR_ERR_INVALID, "null argument");
+  if (batch < 1 || g < 1 || ws < 1) return fail(nullptr, VDR_ERR_INVALID, "bad shape");
+  if (!window_rows_ok(batch, g, ws)) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_layernorm_window: more than 2^31 windowed rows");
+  if (D <= 0 || (D & 3) || D > 2048)
+    return fail(nullptr, VDR_ERR_UNSUPPORTED, "vdr_op_layernorm_window: D must be a positive multiple of 4, at most 2048");
+  if (!aligned16({x, y, gamma, beta}))
+    return fail(nullptr, VDR_ERR_INVALID, "vdr_op_layernorm_window: x, y, gamma and beta must be 16-byte aligned");
+  RUN_OP(launch_layernorm(sam_ln_args(x, y, gamma, beta, eps, batch, g, ws, D), (hipStream_t)stream), "layernorm");
+}
+
+int vdr_op_layernorm_mx_window(const void* x, const float* gamma, const float* beta, float eps, int batch, int g, int ws, int D,
+                               void* q, void* scales, void* stream) {
+  if (!x || !gamma || !beta || !q || !scales) return fail(nullptr, VDR_ERR_INVALID, "null argument");
+  if (batch < 1 || g < 1 || ws < 1) return fail(nullptr, VDR_ERR_INVALID, "bad shape");
+  if (!window_rows_ok(batch, g, ws)) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_layernorm_mx_window: more than 2^31 windowed rows");
+  if (D <= 0 || (D & 31) || D > 2048)
+    return fail(nullptr, VDR_ERR_UNSUPPORTED, "vdr_op_layernorm_mx_window: D must be a positive multiple of 32, at most 2048");
+  if (!aligned16({x, gamma, beta, q}))
+    return fail(nullptr, VDR_ERR_INVALID, "vdr_op_layernorm_mx_window: x, gamma, beta and q must be 16-byte aligned");
+  RUN_OP(sam_ln_mx(x, gamma, beta, eps, batch, g, ws, D, q, scales, (hipStream_t)stream), "layernorm_mx");
+}
+
+int vdr_op_linear_window(const void* x, const void* W, const float* bias, const void* resid, void* y, int batch, int g, int ws,
+                         int N, int K, int variant, float* part, int64_t part_stride, void* stream) {
+  if (!x || !W || !resid || !y) return fail(nullptr, VDR_ERR_INVALID, "null argument");
+  if (batch < 1 || g < 1 || ws < 1) return fail(nullptr, VDR_ERR_INVALID, "bad shape");
+  if (!window_rows_ok(batch, g, ws)) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_linear_window: more than 2^31 windowed rows");
+  if (N <= 0 || K <= 0 || K % 64 || N % 8) return fail(nullptr, VDR_ERR_UNSUPPORTED, "K % 64 == 0 and N % 8 == 0 required");
+  if (variant != 0 && !ln_variant_ok(variant, false)) return fail(nullptr, VDR_ERR_INVALID, "variant: 0 or 22..29");
+  if (part && (N % 64 || part_stride < (int64_t)batch * g * g))
+    return fail(nullptr, VDR_ERR_INVALID, "vdr_op_linear_window: part needs N % 64 == 0 and part_stride >= batch * g * g");
+  if (!aligned16({x, W, bias, resid, y, part}))
+    return fail(nullptr, VDR_ERR_INVALID, "vdr_op_linear_window: x, W, bias, resid, y and part must be 16-byte aligned");
+  if (int rc = check_device(nullptr)) return rc;
+  const GemmArgs ga = sam_proj_args(x, W, bias, resid, y, batch, g, ws, N, K, part, part_stride);
+  if (variant == 0) variant = gemm_variant_for(VDR_K_GEMM_PROJ, ga.M, ga.N);  // (what run_sam launches the out-projection on)
+  return op_gemm(ga, EPI_BIAS_RESID, variant, stream, "gemm: unknown tile variant or unsupported shape");
+}
+
+int vdr_op_im2col3(const void* x, void* col, int batch, int g, int C, void* stream) {
+  if (!x || !col) return fail(nullptr, VDR_ERR_INVALID, "null argument");
+  if (batch < 1 || g < 1) return fail(nullptr, VDR_ERR_INVALID, "bad shape");
+  if (!window_rows_ok(batch, g, 0)) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_im2col3: more than 2^31 rows");
+  if (C <= 0 || (C & 7)) return fail(nullptr, VDR_ERR_UNSUPPORTED, "vdr_op_im2col3: C must be a positive multiple of 8");
+  if (!aligned16({x, col})) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_im2col3: x and col must be 16-byte aligned");
+  RUN_OP(launch_im2col3(x, col, batch, g, C, (hipStream_t)stream), "im2col3");
 }
 
 int vdr_op_interpolate_rel_pos(const float* table, int L0, int D, float* out, int L, void* stream) {

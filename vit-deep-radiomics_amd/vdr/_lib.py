@@ -97,6 +97,10 @@ SYMBOLS = {
     "vdr_op_attention_probs": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vdr_op_attention_pool": (_I, [_P, _P, _L, _P, _I, _I, _I, _I, _P]),
     "vdr_op_attention_relpos": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "vdr_op_layernorm_window": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "vdr_op_layernorm_mx_window": (_I, [_P, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P]),
+    "vdr_op_linear_window": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
+    "vdr_op_im2col3": (_I, [_P, _P, _I, _I, _I, _P]),
     "vdr_op_interpolate_pos": (_I, [_P, _I, _I, _I, _P, _I, _I, _P]),
     "vdr_op_interpolate_rel_pos": (_I, [_P, _I, _I, _P, _I, _P]),
     "vdr_op_rope2d_table": (_I, [_I, _I, _I, _F, _P, _P, _P]),

@@ -324,3 +324,72 @@ def attention_relpos(qkv: torch.Tensor, rel_pos_h: torch.Tensor, rel_pos_w: torc
                                         rel_pos_w.float().contiguous().data_ptr(), rel.data_ptr(), out.data_ptr(), batch, S,
                                         heads, _s(qkv)))
     return out
+
+
+def window_rows(batch: int, g: int, ws: int) -> int:
+    """Rows of the window-partition order of `batch` g x g grids in ws x ws windows (border windows padded)."""
+    nw = -(-g // ws)
+    return batch * nw * nw * ws * ws
+
+
+def layernorm_window(x: torch.Tensor, gamma, beta, eps: float, batch: int, g: int, ws: int, out=None) -> torch.Tensor:
+    """norm1 + window_partition of a SAM block (vdr_op_layernorm_window): x bf16 [batch*g*g, D] in token order -> bf16
+    [window_rows, D] in segment_anything's window_partition order.  Padding rows are not written: `out` (default: zeros)
+    keeps what it held there."""
+    lib = L.load()
+    assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and x.shape[0] == batch * g * g
+    D = x.shape[1]
+    if out is None:
+        out = torch.zeros((window_rows(batch, g, ws), D), dtype=torch.bfloat16, device=x.device)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (window_rows(batch, g, ws), D)
+    L.check(lib.vdr_op_layernorm_window(x.data_ptr(), out.data_ptr(), gamma.data_ptr(), beta.data_ptr(), batch, g, ws, D,
+                                        float(eps), _s(x)))
+    return out
+
+
+def layernorm_mx_window(x: torch.Tensor, gamma, beta, eps: float, batch: int, g: int, ws: int, out: MxTensor = None) -> MxTensor:
+    """The same with MX-fp8 output (vdr_op_layernorm_mx_window): an MxTensor of window_rows rows; padding rows of the
+    payload and the scales are not written (default `out`: zeroed, as the forward zeroes them)."""
+    lib = L.load()
+    assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and x.shape[0] == batch * g * g
+    D = x.shape[1]
+    rows = window_rows(batch, g, ws)
+    if out is None:
+        out = MxTensor.empty(rows, D, x.device)
+        out.q.zero_()
+    assert tuple(out.q.shape) == (rows, D) and out.scales.numel() == int(lib.vdr_mx_scale_bytes(rows, D))
+    L.check(lib.vdr_op_layernorm_mx_window(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps), batch, g, ws, D,
+                                           out.q.data_ptr(), out.scales.data_ptr(), _s(x)))
+    return out
+
+
+def linear_window(x: torch.Tensor, W: torch.Tensor, bias, resid: torch.Tensor, batch: int, g: int, ws: int, variant=0,
+                  out=None, part=None) -> torch.Tensor:
+    """attn.proj + window_unpartition + residual of a SAM block (vdr_op_linear_window): x bf16 [window_rows, K] in
+    windowed order, W bf16 [N, K], bias fp32 [N] or None, resid bf16 [batch*g*g, N] in token order -> out (default: a new
+    tensor; may be resid) = resid + unpartition(x W^T + bias).  part fp32 [N/64, stride, 2]: the LayerNorm partials of
+    out's rows, by token-order row."""
+    lib = L.load()
+    assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and W.dtype == torch.bfloat16 and W.is_contiguous()
+    N, K = W.shape
+    assert tuple(x.shape) == (window_rows(batch, g, ws), K)
+    assert resid.dtype == torch.bfloat16 and resid.is_contiguous() and tuple(resid.shape) == (batch * g * g, N)
+    if out is None:
+        out = torch.empty_like(resid)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (batch * g * g, N)
+    L.check(lib.vdr_op_linear_window(x.data_ptr(), W.data_ptr(), _p(bias), resid.data_ptr(), out.data_ptr(), batch, g, ws, N, K,
+                                     variant, _p(part), 0 if part is None else part.shape[1], _s(x)))
+    return out
+
+
+def im2col3(x: torch.Tensor, batch: int, g: int, out=None) -> torch.Tensor:
+    """The SAM neck's 3 x 3 / padding 1 im2col (vdr_op_im2col3): x bf16 [batch*g*g, C] NHWC tokens -> bf16
+    [batch*g*g, 9*C], tap-major (column (ky*3 + kx)*C + c)."""
+    lib = L.load()
+    assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and x.shape[0] == batch * g * g
+    C_ = x.shape[1]
+    if out is None:
+        out = torch.empty((batch * g * g, 9 * C_), dtype=torch.bfloat16, device=x.device)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (batch * g * g, 9 * C_)
+    L.check(lib.vdr_op_im2col3(x.data_ptr(), out.data_ptr(), batch, g, C_, _s(x)))
+    return out
