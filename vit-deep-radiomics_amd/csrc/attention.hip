@@ -16,8 +16,7 @@
 //                        permuted key order the accumulator registers hold)
 // so P never touches LDS.  seq <= 288 runs as one chunk (no rescale); longer sequences run an
 // online softmax over 128-key chunks with one query tile per wave.
-#include "vdr_dev.h"
-#include "vdr_kernels.h"
+#include "attention_tile.h"
 
 namespace vdr {
 
@@ -89,40 +88,21 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(AttnK p) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int hh = lane >> 5;
-  const int l31 = lane & 31;
-  const int swz = (lane >> 1) & 7;
-  // transposed V read: lane 4q+p of a 16-lane group addresses key row q, d columns 4p..4p+3 of a 4 x 16 block and
-  // receives d column (lane & 15) of the 4 keys (groups: d half (lane >> 4) & 1, key offset 4 hh)
-  typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-  const int tq = (lane & 15) >> 2, tp = lane & 3, dg = (lane >> 4) & 1;
-  const int vkey = 4 * hh + tq;
-  const __attribute__((address_space(3))) char* sVtr =
-      (const __attribute__((address_space(3))) char*)sVt + vkey * 128 + 8 * (tp & 1);
-  int vch[2];
-#pragma unroll
-  for (int nd = 0; nd < 2; ++nd) vch[nd] = ((4 * nd + 2 * dg + (tp >> 1)) ^ (((vkey >> 1) & 1) << 2)) * 16;
+  const AttnLane ln = attn_lane(lane);
+  const lds_cptr sVtr = (lds_cptr)sVt + ln.vrow;
 
-  // 1-D grid of (image, head) x query blocks, query block fastest, walked in XCD-contiguous order: the query blocks of
-  // one (image, head) run next to each other on ONE XCD and find its K / V in that L2.  (As a 2-D grid with the query
-  // block on y they were a whole grid row apart: every block re-read K / V from HBM -- ViT-L/14@336, 5 query blocks
-  // per head: 0.83 GB per launch at 5.2 TB/s.)
   const int nqt = (p.seq + 31) >> 5;
-  const int nyb = (nqt + p.qt_per_block - 1) / p.qt_per_block;
-  const int vid = nyb > 1 ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
-  const int bh = vid / nyb;
-  const int yb = vid - bh * nyb;
-  const int b = bh / p.heads;
-  const int hd = bh - b * p.heads;
+  const AttnItem it = attn_item((nqt + p.qt_per_block - 1) / p.qt_per_block, p.heads);
+  const int b = it.b, hd = it.hd;
   const int HD = p.heads * 64;
   const bf16_t* qb = p.qkv + (int64_t)b * p.seq * p.ld_qkv + hd * 64;
   const int len = p.lens ? min(p.seq, p.lens[b] + p.len_add) : p.seq;  // valid keys of this sequence
   const bf16_t* kb = qb + HD;
   const bf16_t* vb = qb + 2 * HD;
 
-  const int qt_begin = yb * p.qt_per_block;
+  const int qt_begin = it.yb * p.qt_per_block;
   const int qt_end = min(nqt, qt_begin + p.qt_per_block);
-  const float sc = 0.125f * 1.44269504088896341f;  // 1/sqrt(64) * log2(e)
+  constexpr float sc = attn_scale_log2e<64>();
 
   // per-wave running state (multi-chunk mode: exactly one query tile per wave)
   f32x16 o[2];
@@ -130,116 +110,48 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(AttnK p) {
   bf16x8 qf[4];
 
   auto load_q = [&](int qt) {
-    int q = qt * 32 + l31;
+    int q = qt * 32 + ln.l31;
     q = q < p.seq ? q : p.seq - 1;
-    const bf16_t* src = qb + (int64_t)q * p.ld_qkv + hh * 8;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(src + ks * 16);
-#pragma unroll
-    for (int nd = 0; nd < 2; ++nd)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) o[nd][e] = 0.0f;
+    load_q_frags(qb + (int64_t)q * p.ld_qkv + ln.hh * 8, qf);
+    zero_tiles(o);
     m_run = -INFINITY;
     l_run = 0.0f;
   };
 
-  // staging of one key chunk.  The LDS-DMA is an opaque instruction (glds16_raw): hipcc orders nothing after it, the
-  // explicit vmcnt(0) + barrier of stage_wait does.  Rows past the valid length repeat its last row: a 16-key slice that
-  // straddles the length still runs its P.V MFMA, where a masked key's P = 0 times a NaN / Inf padding row would give
-  // NaN (0 x finite = 0).  Without lengths, len == seq.
-  const int last = max(len, 1) - 1;
-  auto stage_issue = [&](int kc0) {
-    // K: KEYS rows of 128 B, 8 rows per wave-instruction
-#pragma unroll
-    for (int q = 0; q < NT; ++q) {
-      const int piece = wave * NT + q;  // 0 .. 4*NT-1, rows piece*8 .. +7
-      const int r = piece * 8 + (lane >> 3);
-      const int c = (lane & 7) ^ ((r >> 1) & 7);
-      int key = kc0 + r;
-      key = key < last ? key : last;
-      glds16_raw(kb + (int64_t)key * p.ld_qkv + c * 8, sK + piece * 1024);
-    }
-    // V rows the same way (row-major, chunk ^ (((key >> 1) & 1) << 2)), consumed by ds_read_b64_tr_b16 in process():
-    // no register-staged transpose
-#pragma unroll
-    for (int q = 0; q < NT; ++q) {
-      const int piece = wave * NT + q;
-      const int r = piece * 8 + (lane >> 3);
-      const int c = (lane & 7) ^ (((r >> 1) & 1) << 2);
-      int key = kc0 + r;
-      key = key < last ? key : last;
-      glds16_raw(vb + (int64_t)key * p.ld_qkv + c * 8, sVt + piece * 1024);
-    }
-  };
-  auto stage_wait = [&]() {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  };
+  const int last = max(len, 1) - 1;  // (without lengths, len == seq)
+  auto stage_issue = [&](int kc0) { stage_kv_chunk<NT>(kb, vb, p.ld_qkv, kc0, last, sK, sVt, wave, lane); };
 
   auto process = [&](int kc0, bool rescale) {
     f32x16 s[NT];
-    __builtin_amdgcn_s_setprio(0);  // (low for the K.Q^T MFMAs, high for the vector-heavy rest: see attn_persist_kernel)
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) s[t][e] = 0.0f;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const bf16x8 kf =
-            *reinterpret_cast<const bf16x8*>(sK + (t * 32 + l31) * 128 + (((2 * ks + hh) ^ swz) * 16));
-        s[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], s[t], 0, 0, 0);
-      }
-    }
-    __builtin_amdgcn_s_setprio(2);
+    zero_tiles(s);
+    qk_tiles(sK, ln, qf, s);
     // mask keys >= seq (only tiles that straddle or lie beyond the end)
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-      if (kc0 + t * 32 + 32 > len) mask_keys(s[t], kc0 + t * 32, hh, len);
+      if (kc0 + t * 32 + 32 > len) mask_keys(s[t], kc0 + t * 32, ln.hh, len);
     }
     float mx = row_max_tiles<NT>(s);
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
     const float m_new = fmaxf(m_run, mx);
-    if (rescale) {
-      const float alpha = fast_exp2((m_run - m_new) * sc);
-      l_run *= alpha;
-#pragma unroll
-      for (int nd = 0; nd < 2; ++nd)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) o[nd][e] *= alpha;
-    }
+    if (rescale) online_rescale(m_run, m_new, sc, l_run, o);
     m_run = m_new;
     const float mb = m_new * sc;
-    f32x2 lsum2 = {0.0f, 0.0f};  // fp32 row sum, (even, odd) elements (same order in the persistent kernel: bitwise equal)
+    f32x2 lsum2 = {0.0f, 0.0f};
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
         if (kc0 + t * 32 + s2 * 16 >= len) continue;  // fully masked slice (wave-uniform): P = 0, nothing to add
-        bf16x8 pf;
-        softmax_slice8(s[t], s2, sc, -mb, lsum2, pf);
-#pragma unroll
-        for (int nd = 0; nd < 2; ++nd) {
-          const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(sVtr + (t * 32 + s2 * 16) * 128 + vch[nd]));
-          const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(sVtr + (t * 32 + s2 * 16 + 8) * 128 + vch[nd]));
-          bf16x8 vf;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            vf[j] = lo[j];
-            vf[4 + j] = hi[j];
-          }
-          o[nd] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o[nd], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);  // keep the exp/cvt of later key slices from being hoisted (VGPR cap)
+        pv_slice(s[t], s2, sc, -mb, lsum2, sVtr + (t * 32 + s2 * 16) * 128, 128, ln.vch, o);
       }
     }
     l_run += lsum2[0] + lsum2[1];
   };
 
   auto store = [&](int qt) {
-    const float l = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = 1.0f / l;
-    const int q = qt * 32 + l31;
-    attn_store_row(p, o, inv, q < p.seq, (int64_t)b * p.seq + (q < p.seq ? q : 0), hd, hh);
+    const float inv = finish_row(l_run);
+    const int q = qt * 32 + ln.l31;
+    attn_store_row(p, o, inv, q < p.seq, (int64_t)b * p.seq + (q < p.seq ? q : 0), hd, ln.hh);
   };
 
   if (p.n_chunks == 1) {
@@ -297,17 +209,14 @@ __global__ __launch_bounds__(LOADER ? 512 : 448, 2) void attn_persist_kernel(Att
   const int swz = (lane >> 1) & 7;
   const int HD = p.heads * 64;
   const int nqt = (p.seq + 31) >> 5;
-  const float sc = 0.125f * 1.44269504088896341f;
+  constexpr float sc = attn_scale_log2e<64>();
 #ifdef VDR_ATTN_STAMPS
   unsigned long long st[16] = {};  // tools/micro/attn_stamps.hip: s_memtime at the phase boundaries of the current item
 #endif
 
-  // ---- staging of one item: K and V rows straight into LDS by global_load_lds, no registers -------
-  //   K: 16-B chunk ^ ((key >> 1) & 7)            (ds_read_b128 row reads of the 32x32x16 operand)
-  //   V: 16-B chunk ^ (((key >> 1) & 1) << 2)     (ds_read_b64_tr_b16 blocks of 4 keys x 16 d: the two even / odd keys
-  //                                                of a block land in different halves of their 32 banks)
-  // V stays row-major: the transposed read hands every lane V[key0 .. key0+3][d] -- the P.V operand -- so the
-  // register-staged transpose (32 VGPRs and 16 ds_write_b32 per thread and item) of the first version is gone.
+  // ---- staging of one item: K and V rows straight into LDS by global_load_lds, no registers, in the swizzled images
+  // of attention_tile.h (AttnLane, stage_kv_chunk: same layout, pieces dealt to 7 waves or to the loader).  The
+  // register-staged V transpose of the first version cost 32 VGPRs and 16 ds_write_b32 per thread and item.
   auto stage_issue = [&](int item, char* buf) {
     const int b = item / p.heads;
     const int hd = item - b * p.heads;
@@ -351,15 +260,13 @@ __global__ __launch_bounds__(LOADER ? 512 : 448, 2) void attn_persist_kernel(Att
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   };
 
-  // Q fragments of this wave's query tile (B operand of S^T = K.Q^T): 4 x 16 B straight from global
+  // Q fragments of this wave's query tile
   auto load_q = [&](int item, int qt, bf16x8 (&q)[4]) {
     const int b = item / p.heads;
     const int hd = item - b * p.heads;
     int qr = qt * 32 + l31;
     qr = qr < p.seq ? qr : p.seq - 1;
-    const bf16_t* src = p.qkv + ((int64_t)b * p.seq + qr) * p.ld_qkv + hd * 64 + hh * 8;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) q[ks] = *reinterpret_cast<const bf16x8*>(src + ks * 16);
+    load_q_frags(p.qkv + ((int64_t)b * p.seq + qr) * p.ld_qkv + hd * 64 + hh * 8, q);
   };
 
   // compute: one 32-query tile of an item against the staged K / V^T.  Fragment reads run one step
@@ -384,13 +291,11 @@ __global__ __launch_bounds__(LOADER ? 512 : 448, 2) void attn_persist_kernel(Att
     const int b = item / p.heads;
     const int hd = item - b * p.heads;
     const char* sK = buf + l31 * 128;
-    // transposed V read: lane 4q+p of its 16-lane group addresses key row q, d columns 4p..4p+3 of a 4 x 16 block and
-    // receives d column (lane & 15) of the 4 keys; groups: d half (lane >> 4) & 1, key offset 4 hh
-    typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+    // AttnLane's transposed-read constants, spelled out per item: taken from the struct (or with the MFMA join as a
+    // function) this kernel's instruction order changes, and it is the one whose schedule was tuned by hand
     const int tq = (lane & 15) >> 2, tp = lane & 3, dg = (lane >> 4) & 1;
     const int vkey = 4 * hh + tq;  // + 16 it (+ 8 for the high half): multiples of 8 keep (key >> 1) & 1
-    const __attribute__((address_space(3))) char* sV =
-        (const __attribute__((address_space(3))) char*)(buf + KEYS * 128) + vkey * 128 + 8 * (tp & 1);
+    const lds_cptr sV = (lds_cptr)(buf + KEYS * 128) + vkey * 128 + 8 * (tp & 1);
     int vch[2];
 #pragma unroll
     for (int nd = 0; nd < 2; ++nd) vch[nd] = ((4 * nd + 2 * dg + (tp >> 1)) ^ (((vkey >> 1) & 1) << 2)) * 16;
@@ -578,17 +483,8 @@ static hipError_t launch_persist(const AttnK& k, int batch, hipStream_t s) {
 
 template <int NT>
 static hipError_t launch_nt(const AttnK& k, int batch, hipStream_t s) {
-  constexpr size_t image = 2 * (size_t)NT * 32 * 128;       // K image + V image
-  const size_t lds = image;
-  auto fn = attn_kernel<NT>;
-  static KernelState st;  // per instantiation and device: the LDS limit is raised once, not per launch
-  const int dev = current_device_index();
-  if (dev < 0) return hipErrorInvalidDevice;
-  if (hipError_t e = raise_lds_limit(st, (const void*)fn, dev, lds)) return e;
-  const int nqt = (k.seq + 31) / 32;
-  const dim3 grid((unsigned)(batch * k.heads * ((nqt + k.qt_per_block - 1) / k.qt_per_block)));
-  hipLaunchKernelGGL(fn, grid, dim3(256), lds, s, k);
-  return hipGetLastError();
+  constexpr size_t lds = 2 * (size_t)NT * 32 * 128;  // K image + V image
+  return launch_query_blocks<attn_kernel<NT>>(lds, lds, k, batch, s);
 }
 
 hipError_t launch_attention(const void* qkv, void* out, int batch, int seq, int heads, int variant,
@@ -626,16 +522,13 @@ hipError_t launch_attention(const void* qkv, void* out, int batch, int seq, int 
   }
   k.qt_per_block = nqt;
   k.n_chunks = 1;
-  if ((variant == 2 || variant == 4 || variant == 0) && !lens) {  // (per-sequence lengths: one-shot kernel only)
-    // persistent warp-specialised kernel (needs a few items per workgroup to pay off)
-    if (variant == 4 && seq > 128 && seq <= 224) return launch_persist<7, true>(k, batch, s);
-    if (variant == 0 && seq > 128 && seq <= 224 && batch * heads >= 512) return launch_persist<7, true>(k, batch, s);  // nqt <= 7 compute waves
-    if (seq > 128 && seq <= 224 && batch * heads >= 512) return launch_persist<7, false>(k, batch, s);
-    if (variant == 2) {
-      if (seq <= 128) return launch_persist<4, false>(k, batch, s);
-      if (seq <= 224) return launch_persist<7, false>(k, batch, s);
-    }
-  }
+  // One chunk.  The persistent kernels give every item the launch's one length (so: not with per-sequence lengths) and
+  // serve at most 7 query tiles.  With its loader wave (NT 7: 129..224 keys) the kernel is variant 4, and the library's
+  // choice once there are a few items per workgroup to pay for it; without it, variant 2, which also has an NT 4 form.
+  const bool nt7 = seq > 128 && seq <= 224;
+  if (!lens && nt7 && (variant == 4 || (variant == 0 && batch * heads >= 512))) return launch_persist<7, true>(k, batch, s);
+  if (!lens && variant == 2 && seq <= 224) return nt7 ? launch_persist<7, false>(k, batch, s) : launch_persist<4, false>(k, batch, s);
+  // one-shot
   if (seq <= 64) return launch_nt<2>(k, batch, s);
   if (seq <= 128) return launch_nt<4>(k, batch, s);
   if (seq <= 224) return launch_nt<7>(k, batch, s);

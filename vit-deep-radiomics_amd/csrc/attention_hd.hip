@@ -22,8 +22,7 @@
 // and 16-key slices that lie wholly past it are skipped (wave-uniform), so a valid row's bits depend neither on the
 // padding rows' contents nor on how far the sequence is padded.  Nothing depends on batch * heads: the grid grows,
 // the arithmetic of a (sequence, head) does not.
-#include "vdr_dev.h"
-#include "vdr_kernels.h"
+#include "attention_tile.h"
 
 namespace vdr {
 
@@ -35,13 +34,6 @@ struct AttnHdK {
   const int* lens;  // non-null: valid length of batch entry b = min(seq, lens[b] + len_add)
   int len_add;
 };
-
-// dh^-1/2 * log2(e)
-template <int DH>
-constexpr float attn_hd_scale() {
-  return DH == 32 ? 0.17677669529663688f * 1.44269504088896341f
-                  : DH == 96 ? 0.10206207261596575f * 1.44269504088896341f : 0.08838834764831845f * 1.44269504088896341f;
-}
 
 template <int DH>
 struct HdShape {
@@ -100,28 +92,22 @@ __global__ __launch_bounds__(256, 2) void attn_hd_kernel(AttnHdK p) {
   const int hh = lane >> 5;
   const int l31 = lane & 31;
 
-  // grid: (sequence, head) x blocks of 4 query tiles, block fastest, XCD-contiguous (the blocks of one (sequence, head)
-  // share an L2 and its K / V)
+  // grid: (sequence, head) x blocks of 4 query tiles
   const int nqt = (p.seq + 31) >> 5;
-  const int nqb = (nqt + 3) >> 2;
-  const int vid = nqb > 1 ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
-  const int bh = vid / nqb;
-  const int qblk = vid - bh * nqb;
-  const int b = bh / p.heads;
-  const int hd = bh - b * p.heads;
+  const AttnItem it = attn_item((nqt + 3) >> 2, p.heads);
+  const int b = it.b, hd = it.hd;
   const int HD = p.heads * DH;
   const bf16_t* qb = p.qkv + (int64_t)b * p.seq * p.ld_qkv + hd * DH;
   const bf16_t* kb = qb + HD;
   const bf16_t* vb = qb + 2 * HD;
   const int len = p.lens ? min(p.seq, p.lens[b] + p.len_add) : p.seq;
   const int n_chunks = (len + KC - 1) / KC;  // chunks wholly past the length are never staged
-  const int qt = qblk * 4 + wave;
+  const int qt = it.yb * 4 + wave;
   const bool active = qt < nqt;  // wave-uniform
-  constexpr float sc = attn_hd_scale<DH>();
+  constexpr float sc = attn_scale_log2e<DH>();
 
   // staging: thread tid moves pieces tid + 256 i (row = piece / CPR, 16-byte column = piece % CPR) of K and of V;
-  // rows past the valid length repeat its last row: a 16-key slice that straddles the length still runs its P.V MFMA,
-  // where P = 0 times a NaN / Inf padding row would give NaN (0 x finite = 0)
+  // rows past the valid length repeat its last row (the padding rule of stage_kv_chunk)
   bf16x8 rk[PPT], rv[PPT];
   const int last = max(len, 1) - 1;
   auto stage_load = [&](int kc0) {
@@ -144,35 +130,25 @@ __global__ __launch_bounds__(256, 2) void attn_hd_kernel(AttnHdK p) {
     }
   };
 
-  // Q fragments (B operand of S^T = K.Q^T): lane (query l31, hh) holds dims 16 ks + 8 hh .. +7
   bf16x8 qf[KS];
-  {
-    const int q = min(qt * 32 + l31, p.seq - 1);
-    const bf16_t* src = qb + (int64_t)q * p.ld_qkv + hh * 8;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(src + ks * 16);
-  }
+  load_q_frags(qb + (int64_t)min(qt * 32 + l31, p.seq - 1) * p.ld_qkv + hh * 8, qf);
   f32x16 o[ND];
-#pragma unroll
-  for (int nd = 0; nd < ND; ++nd)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) o[nd][e] = 0.0f;
+  zero_tiles(o);
   float m_run = -INFINITY, l_run = 0.0f;
 
-  // transposed V read: lane 4q+t of its 16-lane group addresses key row q, dims 4t..4t+3 of a 4-key x 16-dim block and
-  // receives dim (lane & 15) of the 4 keys; groups: dim half (lane >> 4) & 1 of the 32-dim block, key offset 4 hh
-  typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+  // transposed V read with AttnLane's lane roles, on this file's padded, unswizzled V image
   const int tq = (lane & 15) >> 2, tp = lane & 3, dg = (lane >> 4) & 1;
-  const __attribute__((address_space(3))) char* sVr =
-      (const __attribute__((address_space(3))) char*)sV + (4 * hh + tq) * VSTR + (16 * dg + 4 * tp) * 2;
+  const lds_cptr sVr = (lds_cptr)sV + (4 * hh + tq) * VSTR + (16 * dg + 4 * tp) * 2;
+  int vcol[ND];  // byte column of 32-dim block nd
+#pragma unroll
+  for (int nd = 0; nd < ND; ++nd) vcol[nd] = nd * 64;
   const char* sKr = sK + l31 * KSTR + hh * 16;
 
   auto process = [&](int kc0, bool rescale) {
     f32x16 s[NT];
+    zero_tiles(s);
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) s[t][e] = 0.0f;
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         const bf16x8 kf = *reinterpret_cast<const bf16x8*>(sKr + t * 32 * KSTR + ks * 32);
@@ -185,14 +161,7 @@ __global__ __launch_bounds__(256, 2) void attn_hd_kernel(AttnHdK p) {
     float mx = row_max_tiles<NT>(s);
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
     const float m_new = fmaxf(m_run, mx);
-    if (rescale) {
-      const float alpha = fast_exp2((m_run - m_new) * sc);
-      l_run *= alpha;
-#pragma unroll
-      for (int nd = 0; nd < ND; ++nd)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) o[nd][e] *= alpha;
-    }
+    if (rescale) online_rescale(m_run, m_new, sc, l_run, o);
     m_run = m_new;
     const float mb = m_new * sc;
     f32x2 lsum2 = {0.0f, 0.0f};
@@ -201,22 +170,7 @@ __global__ __launch_bounds__(256, 2) void attn_hd_kernel(AttnHdK p) {
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
         if (kc0 + t * 32 + s2 * 16 >= len) continue;  // wholly masked slice (wave-uniform): P = 0
-        bf16x8 pf;
-        softmax_slice8(s[t], s2, sc, -mb, lsum2, pf);
-#pragma unroll
-        for (int nd = 0; nd < ND; ++nd) {
-          const int row = t * 32 + s2 * 16;
-          const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(sVr + row * VSTR + nd * 64));
-          const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(sVr + (row + 8) * VSTR + nd * 64));
-          bf16x8 vf;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            vf[j] = lo[j];
-            vf[4 + j] = hi[j];
-          }
-          o[nd] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o[nd], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);  // (keeps the exp / convert of later slices from being hoisted: VGPR cap)
+        pv_slice(s[t], s2, sc, -mb, lsum2, sVr + (t * 32 + s2 * 16) * VSTR, VSTR, vcol, o);
       }
     }
     l_run += lsum2[0] + lsum2[1];
@@ -231,8 +185,7 @@ __global__ __launch_bounds__(256, 2) void attn_hd_kernel(AttnHdK p) {
     if (active) process(c * KC, c > 0);
   }
   if (!active) return;
-  const float l = l_run + __shfl_xor(l_run, 32, 64);
-  const float inv = 1.0f / l;
+  const float inv = finish_row(l_run);
   const int q = qt * 32 + l31;
   bf16_t* dst = p.out + ((int64_t)b * p.seq + (q < p.seq ? q : 0)) * p.ld_out + hd * DH;
 #pragma unroll

@@ -19,8 +19,7 @@
 //   3. S = Q.K^T (the same fragments as the A / B operands swapped: key on the lane): p = e * r, and one store
 //      instruction writes 32 consecutive keys of two query rows -- whole 128-byte lines of an fp32 map
 // The MFMA's fp32 sum over k does not depend on which operand is A, so pass 3's scores are pass 1's, bit for bit.
-#include "vdr_dev.h"
-#include "vdr_kernels.h"
+#include "attention_tile.h"
 
 namespace vdr {
 
@@ -32,18 +31,10 @@ struct AttnProbsK {
   float inv_heads;  // RN(1 / heads)
 };
 
-// dh^-1/2 * log2(e), the products attention.hip (dh 64) and attention_hd.hip (attn_hd_scale) use
-template <int DH>
-constexpr float probs_scale() {
-  return DH == 64 ? 0.125f * 1.44269504088896341f
-                  : DH == 32 ? 0.17677669529663688f * 1.44269504088896341f
-                             : DH == 96 ? 0.10206207261596575f * 1.44269504088896341f : 0.08838834764831845f * 1.44269504088896341f;
-}
-
 template <int DH, bool MEAN, bool BF16>
 __global__ __launch_bounds__(256) void attn_probs_kernel(AttnProbsK p) {
   constexpr int KS = DH / 16;  // 16-deep k steps of one 32 x 32 score tile
-  constexpr float sc = probs_scale<DH>();
+  constexpr float sc = attn_scale_log2e<DH>();  // (a constant: untouched by this file's -ffp-contract=off)
   extern __shared__ float2 smr[];  // [wave][head of the loop][32 queries] (m, r)
 
   const int tid = threadIdx.x;

@@ -14,8 +14,7 @@
 //                   added to the logits from registers: the key of accumulator element (t, e, half) is a
 //                   compile-time constant, so kh = key / S and kw = key % S index register arrays statically.
 //                   MULTI (S = 64): online softmax over 128-key chunks = two grid rows per chunk.
-#include "vdr_dev.h"
-#include "vdr_kernels.h"
+#include "attention_tile.h"
 
 namespace vdr {
 
@@ -76,35 +75,20 @@ __global__ __launch_bounds__(256, 2) void attn_relpos_kernel(AttnRK p) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int hh = lane >> 5;
-  const int l31 = lane & 31;
-  const int swz = (lane >> 1) & 7;
-  // transposed V read (see attention.hip): lane 4q+p of a 16-lane group addresses key row q, d columns 4p..4p+3
-  typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-  const int tq = (lane & 15) >> 2, tp = lane & 3, dg = (lane >> 4) & 1;
-  const int vkey = 4 * hh + tq;
-  const int vbase = KEYS * 128 + vkey * 128 + 8 * (tp & 1);  // byte offset of this lane's V address inside a buffer
-  int vch[2];
-#pragma unroll
-  for (int nd = 0; nd < 2; ++nd) vch[nd] = ((4 * nd + 2 * dg + (tp >> 1)) ^ (((vkey >> 1) & 1) << 2)) * 16;
+  const AttnLane ln = attn_lane(lane);
+  const int hh = ln.hh, l31 = ln.l31;
+  const int vbase = KEYS * 128 + ln.vrow;  // byte offset of this lane's V address inside a buffer
 
-  // 1-D grid of (window or grid, head) x query blocks in XCD-contiguous order (see attention.hip: attn_kernel).  The
-  // 32 query blocks of one global-attention head now share their XCD's L2 for its 1 MB of K / V instead of each
-  // streaming it from HBM: 6.4 GB per launch at B = 16 before.
   const int nqt = (p.seq + 31) >> 5;
-  const int nyb = (nqt + p.qt_per_block - 1) / p.qt_per_block;
-  const int vid = nyb > 1 ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
-  const int bh = vid / nyb;
-  const int yb = vid - bh * nyb;
-  const int b = bh / p.heads;
-  const int hd = bh - b * p.heads;
+  const AttnItem it = attn_item((nqt + p.qt_per_block - 1) / p.qt_per_block, p.heads);
+  const int b = it.b, hd = it.hd;
   const int HD = p.heads * 64;
   const bf16_t* qb = p.qkv + (int64_t)b * p.seq * p.ld_qkv + hd * 64;
   const bf16_t* kb = qb + HD;
   const bf16_t* vb = qb + 2 * HD;
   bf16_t* ob = p.out + (int64_t)b * p.seq * p.ld_out + hd * 64;
 
-  const int qt_begin = yb * p.qt_per_block;
+  const int qt_begin = it.yb * p.qt_per_block;
   const int qt_end = min(nqt, qt_begin + p.qt_per_block);
   constexpr float LOG2E = 1.44269504088896341f;
 
@@ -124,9 +108,7 @@ __global__ __launch_bounds__(256, 2) void attn_relpos_kernel(AttnRK p) {
   auto load_q = [&](int qt) {
     int q = qt * 32 + l31;
     q = q < p.seq ? q : p.seq - 1;
-    const bf16_t* src = qb + (int64_t)q * p.ld_qkv + hh * 8;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(src + ks * 16);
+    load_q_frags(qb + (int64_t)q * p.ld_qkv + hh * 8, qf);
     const int qh = q / S, qw = q - qh * S;
     const float* trow = p.T + (((int64_t)b * p.seq + q) * p.heads + hd) * NPAD;
     relrow = trow + qh + (S - 1);  // rel_h[kh] = relrow[-kh]
@@ -140,10 +122,7 @@ __global__ __launch_bounds__(256, 2) void attn_relpos_kernel(AttnRK p) {
 #pragma unroll
       for (int j = 0; j < NRH; ++j) relh[j] = relrow[-j];
     }
-#pragma unroll
-    for (int nd = 0; nd < 2; ++nd)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) o[nd][e] = 0.0f;
+    zero_tiles(o);
     m_run = -INFINITY;
     l_run = 0.0f;
   };
@@ -170,52 +149,23 @@ __global__ __launch_bounds__(256, 2) void attn_relpos_kernel(AttnRK p) {
       for (int q = 0; q < PPW; ++q) glds16_raw(kc + HD, voff[q], sVt + (wave * PPW + q) * 1024);
       return;
     }
-#pragma unroll
-    for (int q = 0; q < NT; ++q) {
-      const int piece = wave * NT + q;
-      const int r = piece * 8 + (lane >> 3);
-      const int c = (lane & 7) ^ ((r >> 1) & 7);
-      int key = kc0 + r;
-      key = key < p.seq ? key : p.seq - 1;
-      glds16_raw(kb + (int64_t)key * p.ld_qkv + c * 8, sK + piece * 1024);
-    }
-    // V rows the same way (row-major, chunk ^ (((key >> 1) & 1) << 2)): consumed by ds_read_b64_tr_b16 below, so no
-    // register-staged transpose; rows past the sequence repeat the last key (their P is exp(-inf) = 0)
-#pragma unroll
-    for (int q = 0; q < NT; ++q) {
-      const int piece = wave * NT + q;
-      const int r = piece * 8 + (lane >> 3);
-      const int c = (lane & 7) ^ (((r >> 1) & 1) << 2);
-      int key = kc0 + r;
-      key = key < p.seq ? key : p.seq - 1;
-      glds16_raw(vb + (int64_t)key * p.ld_qkv + c * 8, sVt + piece * 1024);
-    }
-  };
-  auto stage_wait = [&]() {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    stage_kv_chunk<NT>(kb, vb, p.ld_qkv, kc0, p.seq - 1, sK, sVt, wave, lane);
   };
 
   auto process = [&](int kc0, bool rescale, const char* buf) {
     const char* sK = buf;
-    const __attribute__((address_space(3))) char* sVtr = (const __attribute__((address_space(3))) char*)buf + vbase;
+    const lds_cptr sVtr = (lds_cptr)buf + vbase;
     f32x16 s[NT];
-    __builtin_amdgcn_s_setprio(0);  // (low for the K.Q^T MFMAs, high for the vector-heavy rest: attention.hip, attn_persist_kernel)
+    // MULTI: the first MFMA takes 8 rel_w[kw] as its C operand (registers that never change: no per-element add, no
+    // copy) and the rest add q.k on top; 8 rel_h[kh] is constant over a tile (grid row t >> 1 of the chunk) and enters
+    // the row maximum and the exp2 offset below.  logits = (acc + 8 rel_h) / 8, the 1/8 folded into the exp2 scale.
+    if constexpr (MULTI) {
 #pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      // MULTI: the first MFMA takes 8 rel_w[kw] as its C operand (registers that never change: no per-element add, no
-      // copy) and the rest add q.k on top; 8 rel_h[kh] is constant over a tile (grid row t >> 1 of the chunk) and enters
-      // the row maximum and the exp2 offset below.  logits = (acc + 8 rel_h) / 8, the 1/8 folded into the exp2 scale.
-#pragma unroll
-      for (int e = 0; e < 16; ++e) s[t][e] = 0.0f;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const bf16x8 kf =
-            *reinterpret_cast<const bf16x8*>(sK + (t * 32 + l31) * 128 + (((2 * ks + hh) ^ swz) * 16));
-        s[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], (MULTI && ks == 0) ? rw8[t & 1] : s[t], 0, 0, 0);
-      }
+      for (int t = 0; t < NT; ++t) s[t] = rw8[t & 1];
+    } else {
+      zero_tiles(s);
     }
-    __builtin_amdgcn_s_setprio(2);
+    qk_tiles(sK, ln, qf, s);
     // windows: logits = s * dh^-0.5 + rel_h[kh] + rel_w[kw]; the key of element (t, e, half) is static
     if constexpr (!MULTI) {
 #pragma unroll
@@ -251,14 +201,7 @@ __global__ __launch_bounds__(256, 2) void attn_relpos_kernel(AttnRK p) {
     }
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
     const float m_new = fmaxf(m_run, mx);
-    if (rescale) {
-      const float alpha = fast_exp2((m_run - m_new) * SC);
-      l_run *= alpha;
-#pragma unroll
-      for (int nd = 0; nd < 2; ++nd)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) o[nd][e] *= alpha;
-    }
+    if (rescale) online_rescale(m_run, m_new, SC, l_run, o);
     m_run = m_new;
     const float mb = m_new * SC;
     float crow[2];  // exp2 offset of a tile: -max (+ 8 rel_h of its grid row), scaled
@@ -271,29 +214,14 @@ __global__ __launch_bounds__(256, 2) void attn_relpos_kernel(AttnRK p) {
     for (int t = 0; t < NT; ++t) {
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
-        bf16x8 pf;
-        softmax_slice8(s[t], s2, SC, crow[MULTI ? t >> 1 : 0], lsum2, pf);  // packed pairs: vdr_dev.h
-#pragma unroll
-        for (int nd = 0; nd < 2; ++nd) {
-          const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(sVtr + (t * 32 + s2 * 16) * 128 + vch[nd]));
-          const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(sVtr + (t * 32 + s2 * 16 + 8) * 128 + vch[nd]));
-          bf16x8 vf;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            vf[j] = lo[j];
-            vf[4 + j] = hi[j];
-          }
-          o[nd] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o[nd], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
+        pv_slice(s[t], s2, SC, crow[MULTI ? t >> 1 : 0], lsum2, sVtr + (t * 32 + s2 * 16) * 128, 128, ln.vch, o);
       }
     }
     l_run += lsum2[0] + lsum2[1];
   };
 
   auto store = [&](int qt) {
-    const float l = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = 1.0f / l;
+    const float inv = finish_row(l_run);
     const int q = qt * 32 + l31;
     store_row64_bf16(ob + (int64_t)(q < p.seq ? q : 0) * p.ld_out, o, inv, hh, q < p.seq);
   };
@@ -349,15 +277,7 @@ __global__ __launch_bounds__(256, 2) void attn_relpos_kernel(AttnRK p) {
 template <int NT, int S, bool MULTI>
 static hipError_t launch_rp(const AttnRK& k, int batch, hipStream_t s) {
   constexpr size_t lds = (MULTI ? 2 : 1) * 2 * (size_t)NT * 32 * 128;  // (K image + V image) x 1 or 2 buffers
-  auto fn = attn_relpos_kernel<NT, S, MULTI>;
-  static KernelState st;  // per instantiation and device: the LDS limit is raised once, not per launch
-  const int dev = current_device_index();
-  if (dev < 0) return hipErrorInvalidDevice;
-  if (hipError_t e = raise_lds_limit(st, (const void*)fn, dev, lds)) return e;
-  const int nqt = (k.seq + 31) / 32;
-  const dim3 grid((unsigned)(batch * k.heads * ((nqt + k.qt_per_block - 1) / k.qt_per_block)));
-  hipLaunchKernelGGL(fn, grid, dim3(256), lds, s, k);
-  return hipGetLastError();
+  return launch_query_blocks<attn_relpos_kernel<NT, S, MULTI>>(lds, lds, k, batch, s);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -384,25 +304,14 @@ __global__ __launch_bounds__(256, 2) void attn_relpos_any_kernel(AttnRK p) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int hh = lane >> 5;
-  const int l31 = lane & 31;
-  const int swz = (lane >> 1) & 7;
-  typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-  const int tq = (lane & 15) >> 2, tp = lane & 3, dg = (lane >> 4) & 1;
-  const int vkey = 4 * hh + tq;
-  const int vbase = KEYS * 128 + vkey * 128 + 8 * (tp & 1);
-  int vch[2];
-#pragma unroll
-  for (int nd = 0; nd < 2; ++nd) vch[nd] = ((4 * nd + 2 * dg + (tp >> 1)) ^ (((vkey >> 1) & 1) << 2)) * 16;
+  const AttnLane ln = attn_lane(lane);
+  const int hh = ln.hh, l31 = ln.l31;
+  const int vbase = KEYS * 128 + ln.vrow;
 
   const int g = p.g;
   const int nqt = (p.seq + 31) >> 5;
-  const int nyb = (nqt + p.qt_per_block - 1) / p.qt_per_block;
-  const int vid = nyb > 1 ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
-  const int bh = vid / nyb;
-  const int yb = vid - bh * nyb;
-  const int b = bh / p.heads;
-  const int hd = bh - b * p.heads;
+  const AttnItem it = attn_item((nqt + p.qt_per_block - 1) / p.qt_per_block, p.heads);
+  const int b = it.b, hd = it.hd;
   const int HD = p.heads * 64;
   const int npad = 2 * ((2 * g - 1 + 31) / 32 * 32);  // relpos_npad(g)
   const bf16_t* qb = p.qkv + (int64_t)b * p.seq * p.ld_qkv + hd * 64;
@@ -416,24 +325,19 @@ __global__ __launch_bounds__(256, 2) void attn_relpos_any_kernel(AttnRK p) {
   const float* bias_h = bias + l31;
   const float* bias_w = bias + g * 32 + l31;
 
-  const int qt_begin = yb * p.qt_per_block;
+  const int qt_begin = it.yb * p.qt_per_block;
   const int qt_end = min(nqt, qt_begin + p.qt_per_block);
   const int qt = qt_begin + wave;
   const bool valid = qt < qt_end;
 
   f32x16 o[2];
-#pragma unroll
-  for (int nd = 0; nd < 2; ++nd)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) o[nd][e] = 0.0f;
+  zero_tiles(o);
   float m_run = -INFINITY, l_run = 0.0f;
   bf16x8 qf[4];
   {
     int q = (valid ? qt : qt_begin) * 32 + l31;
     q = q < p.seq ? q : p.seq - 1;
-    const bf16_t* src = qb + (int64_t)q * p.ld_qkv + hh * 8;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(src + ks * 16);
+    load_q_frags(qb + (int64_t)q * p.ld_qkv + hh * 8, qf);
     const int qh = q / g, qw = q - qh * g;
     const float* trow = p.T + (((int64_t)b * p.seq + q) * p.heads + hd) * npad;
     // lower lane half: the query's rel_h row, upper half: its rel_w row; entry j is src[-j]
@@ -443,49 +347,15 @@ __global__ __launch_bounds__(256, 2) void attn_relpos_any_kernel(AttnRK p) {
   }
 
   auto stage_issue = [&](int kc0, char* buf) {
-    char* sK = buf;
-    char* sVt = buf + KEYS * 128;
-#pragma unroll
-    for (int q = 0; q < NT; ++q) {
-      const int piece = wave * NT + q;
-      const int r = piece * 8 + (lane >> 3);
-      const int c = (lane & 7) ^ ((r >> 1) & 7);
-      int key = kc0 + r;
-      key = key < p.seq ? key : p.seq - 1;
-      glds16_raw(kb + (int64_t)key * p.ld_qkv + c * 8, sK + piece * 1024);
-    }
-#pragma unroll
-    for (int q = 0; q < NT; ++q) {
-      const int piece = wave * NT + q;
-      const int r = piece * 8 + (lane >> 3);
-      const int c = (lane & 7) ^ (((r >> 1) & 1) << 2);
-      int key = kc0 + r;
-      key = key < p.seq ? key : p.seq - 1;
-      glds16_raw(vb + (int64_t)key * p.ld_qkv + c * 8, sVt + piece * 1024);
-    }
-  };
-  auto stage_wait = [&]() {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    stage_kv_chunk<NT>(kb, vb, p.ld_qkv, kc0, p.seq - 1, buf, buf + KEYS * 128, wave, lane);
   };
 
   auto process = [&](int kc0, bool rescale, const char* buf) {
     const char* sK = buf;
-    const __attribute__((address_space(3))) char* sVtr = (const __attribute__((address_space(3))) char*)buf + vbase;
+    const lds_cptr sVtr = (lds_cptr)buf + vbase;
     f32x16 s[NT];
-    __builtin_amdgcn_s_setprio(0);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) s[t][e] = 0.0f;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const bf16x8 kf =
-            *reinterpret_cast<const bf16x8*>(sK + (t * 32 + l31) * 128 + (((2 * ks + hh) ^ swz) * 16));
-        s[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], s[t], 0, 0, 0);
-      }
-    }
-    __builtin_amdgcn_s_setprio(2);
+    zero_tiles(s);
+    qk_tiles(sK, ln, qf, s);
     // logits = s * dh^-0.5 + bh[key / g] + bw[key % g], the key of element (t, e, half) at run time
     const int key_lane = kc0 + 4 * hh;
     const int last = p.seq - 1;
@@ -503,14 +373,7 @@ __global__ __launch_bounds__(256, 2) void attn_relpos_any_kernel(AttnRK p) {
     float mx = row_max_tiles<NT>(s);
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
     const float m_new = fmaxf(m_run, mx);
-    if (rescale) {
-      const float alpha = fast_exp2((m_run - m_new) * LOG2E);
-      l_run *= alpha;
-#pragma unroll
-      for (int nd = 0; nd < 2; ++nd)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) o[nd][e] *= alpha;
-    }
+    if (rescale) online_rescale(m_run, m_new, LOG2E, l_run, o);
     m_run = m_new;
     const float nmb = -m_new * LOG2E;
     f32x2 lsum2 = {0.0f, 0.0f};
@@ -518,21 +381,7 @@ __global__ __launch_bounds__(256, 2) void attn_relpos_any_kernel(AttnRK p) {
     for (int t = 0; t < NT; ++t) {
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
-        bf16x8 pf;
-        softmax_slice8(s[t], s2, LOG2E, nmb, lsum2, pf);
-#pragma unroll
-        for (int nd = 0; nd < 2; ++nd) {
-          const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(sVtr + (t * 32 + s2 * 16) * 128 + vch[nd]));
-          const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(sVtr + (t * 32 + s2 * 16 + 8) * 128 + vch[nd]));
-          bf16x8 vf;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            vf[j] = lo[j];
-            vf[4 + j] = hi[j];
-          }
-          o[nd] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o[nd], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
+        pv_slice(s[t], s2, LOG2E, nmb, lsum2, sVtr + (t * 32 + s2 * 16) * 128, 128, ln.vch, o);
       }
     }
     l_run += lsum2[0] + lsum2[1];
@@ -560,8 +409,7 @@ __global__ __launch_bounds__(256, 2) void attn_relpos_any_kernel(AttnRK p) {
     }
   }
   if (valid) {
-    const float l = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = 1.0f / l;
+    const float inv = finish_row(l_run);
     const int q = qt * 32 + l31;
     store_row64_bf16(ob + (int64_t)(q < p.seq ? q : 0) * p.ld_out, o, inv, hh, q < p.seq);
   }
@@ -573,19 +421,16 @@ __global__ __launch_bounds__(256, 2) void attn_relpos_any_kernel(AttnRK p) {
 // prefetch wins (forced at g = 64: 2.79 against 3.34 ms).  DESIGN 4.3b
 static inline bool relpos_any_double_buffered(int g) { return g > 48; }
 
+// LDS of attn_relpos_any_kernel at grid side g: the K / V images + 4 waves x 2 bias rows x g x 32 floats
+template <bool DB>
+static constexpr size_t relpos_any_lds(int g) {
+  return (size_t)(DB ? 2 : 1) * 2 * 128 * 128 + (size_t)4 * 2 * g * 32 * 4;
+}
+
 template <bool DB>
 static hipError_t launch_rp_any(const AttnRK& k, int batch, hipStream_t s) {
-  const size_t lds = (size_t)(DB ? 2 : 1) * 2 * 128 * 128 + (size_t)4 * 2 * k.g * 32 * 4;
-  auto fn = attn_relpos_any_kernel<DB>;
-  static KernelState st;
-  const int dev = current_device_index();
-  if (dev < 0) return hipErrorInvalidDevice;
-  // raised once, to the largest request of any g: 128 KB (DB) / 96 KB
-  if (hipError_t e = raise_lds_limit(st, (const void*)fn, dev, (size_t)(DB ? 2 : 1) * 2 * 128 * 128 + (size_t)4 * 2 * 64 * 32 * 4)) return e;
-  const int nqt = (k.seq + 31) / 32;
-  const dim3 grid((unsigned)(batch * k.heads * ((nqt + k.qt_per_block - 1) / k.qt_per_block)));
-  hipLaunchKernelGGL(fn, grid, dim3(256), lds, s, k);
-  return hipGetLastError();
+  // the limit is raised once, to the largest request of any g: 128 KB (DB) / 96 KB
+  return launch_query_blocks<attn_relpos_any_kernel<DB>>(relpos_any_lds<DB>(k.g), relpos_any_lds<DB>(64), k, batch, s);
 }
 
 hipError_t launch_attention_relpos(const void* qkv, const float* T, void* out, int batch, int S, int heads,
