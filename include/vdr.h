@@ -263,6 +263,32 @@ int vdr_finalize(vdr_handle h);
 int vdr_set_input_size(vdr_handle h, int height, int width);
 int vdr_get_input_size(vdr_handle h, int* height, int* width);   /* (img, img) until the first set */
 
+/* Run an image model with its frozen patch convolution at a stride below its kernel -- Conv2d(kernel = patch, stride) --
+ * for a finer descriptor grid from the same pixels ("Deep ViT Features as Dense Visual Descriptors", dino-vit-features'
+ * ViTExtractor(stride=...)): ViT-B/16 on 512^2 at stride 8 gives 63 x 63 patches.  Load-time class, like
+ * vdr_set_input_size (may allocate and synchronise), callable before or after it in any order.  The grid in force is
+ *   gh x gw = ((height - patch) / stride + 1) x ((width - patch) / stride + 1)
+ * for the input size in force, patch (y, x) covering pixels [y*stride, y*stride + patch) x [x*stride, x*stride + patch);
+ * n = gh * gw, N = n + has_cls + n_register in every image entry point (vdr_forward's every out_mode,
+ * vdr_forward_layers, vdr_forward_attn_maps' q_rows, POOLED's divisor, vdr_workspace_bytes: the col buffer grows with n).
+ * The size rule of vdr_set_input_size (sides multiples of patch) is unchanged and makes (side - patch) % stride == 0.
+ *   has_pos = 1: the patch rows of the position table are resampled from the loaded (img / patch)^2 grid to gh x gw by
+ *   vdr_op_interpolate_pos' rule (bicubic, align_corners = False, size = (gh, gw), fp64, one rounding), the CLS row is
+ *   copied, register tokens get none.  Stated deviation: dino-vit-features resamples with the older scale_factor +
+ *   0.1-offset form, which is not reproduced (the deviation vdr_set_input_size states for DINOv2).
+ *   stride == patch restores the non-overlapping path (the im2col-free gather included): a handle that went to another
+ *   stride and back gives bitwise the features of one that never moved.  stride < patch: the images go through the
+ *   overlapping im2col (csrc/patch_stride.hip) into the workspace's col buffer, the patch GEMM reads it unchanged.
+ * The hot-path promise (no allocation, no synchronisation in vdr_forward*) holds at any stride.
+ * Supported: what vdr_set_input_size supports (pre-LN image models without windows, every vdr_config switch, layers == 0
+ * patch-embedding models, CLIP / SigLIP towers, register tokens).
+ * VDR_ERR_INVALID, before the handle or a device is touched: stride <= 0; then a null handle; then stride > patch or
+ * patch % stride != 0.  VDR_ERR_UNSUPPORTED: SAM / MedSAM (window > 0), token models (patch == 0), post-LN models with
+ * blocks, rope = 1 (DINOv3's patch coordinates have no upstream definition for overlapping patches to check against).
+ * VDR_ERR_INCOMPLETE: vdr_finalize has not run.  A workspace sized for a smaller geometry: VDR_ERR_WORKSPACE. */
+int vdr_set_patch_stride(vdr_handle h, int stride);
+int vdr_get_patch_stride(vdr_handle h, int* stride);   /* patch until the first set */
+
 /* Number of weight tensors the config expects, and the i-th expected name. */
 int vdr_num_weights(vdr_handle h);
 const char* vdr_weight_name(vdr_handle h, int i);
@@ -646,6 +672,16 @@ int vdr_op_rope2d(void* qkv, int batch, int seq, int prefix, int heads, int head
 int vdr_op_patch_embed(const void* images, int in_dtype, const void* W, const float* bias,
                        const float* pos, void* col, void* y, int batch, int C, int img, int p, int D,
                        int row_stride, int row_offset, void* stream);
+
+/* The same for nn.Conv2d(in_chans, D, kernel=p, stride=stride), stride | p, over [batch, C, H, Wd] images, (H - p) and
+ * (Wd - p) multiples of stride: n = ((H - p) / stride + 1) * ((Wd - p) / stride + 1) overlapping patches in (y, x) order.
+ * stride < p: col (batch*n*Kp bf16) is always written -- col[b*n + i][c*p*p + ky*p + kx] = the pixel rounded once to bf16,
+ * columns C*p*p .. Kp-1 zero -- by the overlapping im2col of csrc/patch_stride.hip (LDS form: p even, stride >= 2, Wd a
+ * multiple of 8 (p % 8 == 0) or 2, images 16-byte aligned; else one thread per 16-byte chunk).  stride == p:
+ * vdr_op_patch_embed's paths (rectangular sizes through im2col). */
+int vdr_op_patch_embed_strided(const void* images, int in_dtype, const void* W, const float* bias, const float* pos, void* col,
+                               void* y, int batch, int C, int H, int Wd, int p, int stride, int D, int row_stride, int row_offset,
+                               void* stream);
 /* ---- measurement ------------------------------------------------------------------------ */
 
 /* Kernel classes timed by the built-in HIP-event profiler. */

@@ -168,6 +168,9 @@ struct vdr_model {
   // vdr_set_input_size: the size in force ((img, img) until the first set) and the position table the forward reads --
   // the loaded pos_embed (pos0) at the native size, else pos_sized [n_tokens, D]: its CLS row and resampled patch rows
   int in_h = 0, in_w = 0;
+  // vdr_set_patch_stride: the stride of the patch convolution in force (patch until the first set); the grid in force is
+  // grid_h() x grid_w() overlapping patches, n_patches / n_tokens follow it
+  int stride = 0;
   const float* pos0 = nullptr;
   DevBuf pos_sized;  // (grows only)
   // vdr_config_ext: register tokens between the CLS row and the patch rows (pos_sized then holds the per-token-row table
@@ -229,6 +232,19 @@ bool head_dim_ok(int dh) { return dh == 32 || dh == 64 || dh == 96 || dh == 128;
 
 // rows in front of the patch rows of an image: the CLS token, then the register tokens
 int prefix_rows(const vdr_model* m) { return (m->cfg.has_cls ? 1 : 0) + m->n_reg; }
+
+// the patch grid in force of an image model: Conv2d(kernel = patch, stride = stride) over in_h x in_w pixels
+int grid_h(const vdr_model* m) { return (m->in_h - m->cfg.patch) / m->stride + 1; }
+int grid_w(const vdr_model* m) { return (m->in_w - m->cfg.patch) / m->stride + 1; }
+
+// input size and patch stride in force, and the patch / token counts that follow from them
+void set_geometry(vdr_model* m, int height, int width, int stride) {
+  m->in_h = height;
+  m->in_w = width;
+  m->stride = stride;
+  m->n_patches = grid_h(m) * grid_w(m);
+  m->n_tokens = m->n_patches + prefix_rows(m);
+}
 
 int fail(vdr_handle h, int code, const std::string& msg) {
   if (h) h->err = msg;
@@ -430,16 +446,16 @@ int build_rope_table(vdr_model* m) {
   int rc;
   if ((rc = reserve(m, m->rope_cos, bytes, GROW, "RoPE table"))) return rc;
   if ((rc = reserve(m, m->rope_sin, bytes, GROW, "RoPE table"))) return rc;
-  VDR_TRY(launch_rope2d_table(m->in_h / c.patch, m->in_w / c.patch, 2 * half, m->rope_theta, m->rope_cos.as<float>(),
+  VDR_TRY(launch_rope2d_table(grid_h(m), grid_w(m), 2 * half, m->rope_theta, m->rope_cos.as<float>(),
                               m->rope_sin.as<float>(), nullptr),
           "rope2d_table");
   VDR_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
   return VDR_OK;
 }
 
-// The position tables of the input size in force (load-time class: may allocate and synchronise).  Without register
-// tokens the native size reads the loaded pos_embed itself; any other size gets [CLS row unchanged ; patch rows resampled
-// from the (img / patch)^2 grid].  With register tokens the forward always reads a built table laid out per token row --
+// The position tables of the input size and patch stride in force (load-time class: may allocate and synchronise).  Without
+// register tokens the native geometry (size img x img at stride patch) reads the loaded pos_embed itself; any other gets
+// [CLS row unchanged ; patch rows resampled from the (img / patch)^2 grid to the grid in force].  With register tokens the forward always reads a built table laid out per token row --
 // [CLS row ; n_reg zero rows ; patch rows] -- whose patch rows are the loaded ones at the native size (copied: the same
 // bits however the handle got there) and the resampled ones elsewhere.  RoPE models (no pos_embed) get their cos / sin tables.
 int build_pos_table(vdr_model* m) {
@@ -447,7 +463,7 @@ int build_pos_table(vdr_model* m) {
   m->pos = m->pos0;
   if (m->rope && c.patch)
     if (int rc = build_rope_table(m)) return rc;
-  const bool native = m->in_h == c.img && m->in_w == c.img;
+  const bool native = m->in_h == c.img && m->in_w == c.img && m->stride == c.patch;
   if (!c.has_pos || !c.patch || (native && !m->n_reg)) return VDR_OK;
   const int ncls = c.has_cls ? 1 : 0, P = prefix_rows(m), D = c.dim, g0 = c.img / c.patch;
   VDR_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");  // (a forward still in flight, on any stream, may read the old table)
@@ -459,11 +475,24 @@ int build_pos_table(vdr_model* m) {
     VDR_TRY(hipMemcpy(sized + (size_t)P * D, m->pos0 + (size_t)ncls * D, (size_t)m->n_patches * D * 4, hipMemcpyDeviceToDevice),
             "hipMemcpy(pos_embed patch rows)");
   else
-    VDR_TRY(launch_pos_interp(m->pos0 + (size_t)ncls * D, g0, g0, D, sized + (size_t)P * D, m->in_h / c.patch, m->in_w / c.patch,
-                              nullptr),
+    VDR_TRY(launch_pos_interp(m->pos0 + (size_t)ncls * D, g0, g0, D, sized + (size_t)P * D, grid_h(m), grid_w(m), nullptr),
             "pos_interp");
   VDR_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
   m->pos = sized;
+  return VDR_OK;
+}
+
+// vdr_set_input_size / vdr_set_patch_stride once their arguments are checked (the caller holds the DeviceGuard): the new
+// geometry and its position tables; on failure the geometry in force stays what it was
+int change_geometry(vdr_model* m, int height, int width, int stride) {
+  const int old_h = m->in_h, old_w = m->in_w, old_s = m->stride;
+  set_geometry(m, height, width, stride);
+  if (int rc = build_pos_table(m)) {
+    set_geometry(m, old_h, old_w, old_s);
+    const std::string why = m->err;
+    (void)build_pos_table(m);
+    return fail(m, rc, why);
+  }
   return VDR_OK;
 }
 
@@ -814,17 +843,19 @@ bool patch_gather_ok(int in_dtype, int patch, int variant, const void* images) {
          ((uintptr_t)images & 15) == 0;
 }
 
-// The patch-embedding GEMM of `batch` images [batch, chans, H, W] -> C rows omap(r), r < batch * (H / p) * (W / p), token
-// i of an image being patch (i / gw, i % gw): bf16 images with a patch side of 8 / 16 / 32 on a SQUARE grid are gathered
+// The patch-embedding GEMM of `batch` images [batch, chans, H, W] at patch stride `stride` (p: no overlap) -> C rows omap(r),
+// r < batch * gh * gw with gh x gw = ((H - p) / stride + 1) x ((W - p) / stride + 1), token i of an image being patch
+// (i / gw, i % gw): at stride p bf16 images with a patch side of 8 / 16 / 32 on a SQUARE grid are gathered
 // 16-byte runs at a time by the GEMM's operand loader straight from NCHW (ring4 tile variants: no col buffer, no im2col
 // launch); fp32 images (the loader is an LDS-DMA: it cannot convert), p = 14 (runs of 14 pixels are not 16-byte chunks)
-// and rectangular grids (the loader splits a row by one grid side) go through im2col into `col`, launched here.  Fills
+// and rectangular grids (the loader splits a row by one grid side) go through im2col into `col`, launched here, and so does
+// every stride below p (the overlapping im2col of patch_stride.hip).  Fills
 // *g (the caller adds bias, pos, omap and what else differs) and *variant.
 hipError_t patch_gemm(vdr_model* m, hipStream_t s, const void* images, int in_dtype, void* col, const void* W, void* C,
-                      int batch, int chans, int H, int Wd, int p, int D, GemmArgs* g, int* variant) {
-  const int n = (H / p) * (Wd / p), Kp = round_up(chans * p * p, 64);
+                      int batch, int chans, int H, int Wd, int p, int stride, int D, GemmArgs* g, int* variant) {
+  const int n = ((H - p) / stride + 1) * ((Wd - p) / stride + 1), Kp = round_up(chans * p * p, 64);
   *variant = gemm_variant_for(VDR_K_GEMM_PATCH, (int64_t)batch * n, D);
-  const bool fused = H == Wd && patch_gather_ok(in_dtype, p, *variant, images);
+  const bool fused = stride == p && H == Wd && patch_gather_ok(in_dtype, p, *variant, images);
   *g = linear(fused ? images : col, W, C, (int64_t)batch * n, D, Kp, EPI_PATCH);
   if (fused) {
     g->patch_p = p;
@@ -834,6 +865,7 @@ hipError_t patch_gemm(vdr_model* m, hipStream_t s, const void* images, int in_dt
   }
   const size_t in_es = in_dtype == VDR_BF16 ? 2 : 4;
   Scope sc(m, s, VDR_K_IM2COL, 0.0, (double)batch * chans * H * Wd * in_es + 2.0 * batch * n * Kp);
+  if (stride != p) return launch_im2col_strided(images, in_dtype == VDR_BF16, col, batch, chans, H, Wd, p, stride, Kp, s);
   return launch_im2col(images, in_dtype == VDR_BF16, col, batch, chans, H, Wd, p, Kp, s);
 }
 
@@ -1466,7 +1498,7 @@ int embed_patches(vdr_model* m, hipStream_t s, const Carve& w, const char* img, 
   GemmArgs g;
   int variant;
   VDR_TRY(patch_gemm(m, s, img, in_dtype, w.u, m->w_patch, pe_only ? (void*)pe_out : (void*)w.x, mb, c.in_chans, m->in_h, m->in_w, c.patch,
-                     D, &g, &variant),
+                     m->stride, D, &g, &variant),
           "im2col");
   g.bias = m->b_patch;
   if (pe_only) {
@@ -1672,11 +1704,8 @@ int vdr_create_ext(const vdr_config* cfg, const vdr_config_ext* ext, int device,
   m->rope = x.rope;
   m->rope_theta = x.rope_theta;
   if (c.patch) {
-    const int g = c.img / c.patch;
-    m->n_patches = g * g;
-    m->n_tokens = m->n_patches + prefix_rows(m.get());
+    set_geometry(m.get(), c.img, c.img, c.patch);
     m->Kp = round_up(c.in_chans * c.patch * c.patch, 64);
-    m->in_h = m->in_w = c.img;
   }
   m->layers.resize(c.layers);  // (before build_slots: the slots point into it)
   build_slots(m.get());
@@ -1817,27 +1846,44 @@ int vdr_set_input_size(vdr_handle m, int height, int width) {
   if (!c.pre_ln && c.layers > 0) return fail(m, VDR_ERR_UNSUPPORTED, "vdr_set_input_size: pre-LN models only");
   if (height % c.patch) return fail(m, VDR_ERR_INVALID, "vdr_set_input_size: height must be a multiple of patch " + std::to_string(c.patch));
   if (width % c.patch) return fail(m, VDR_ERR_INVALID, "vdr_set_input_size: width must be a multiple of patch " + std::to_string(c.patch));
-  if ((int64_t)(height / c.patch) * (width / c.patch) > (1 << 20))
+  if ((int64_t)((height - c.patch) / m->stride + 1) * ((width - c.patch) / m->stride + 1) > (1 << 20))
     return fail(m, VDR_ERR_INVALID, "vdr_set_input_size: height x width gives more than 2^20 patches");
   int rc = check_device(m);
   if (rc) return rc;
   if (!m->resolved) return fail(m, VDR_ERR_INCOMPLETE, "vdr_set_input_size: vdr_finalize has not run since the last vdr_set_weight");
   DeviceGuard dg(m->device);
   if (!dg.ok) return fail(m, VDR_ERR_HIP, "hipSetDevice failed");
-  const int old_h = m->in_h, old_w = m->in_w;
-  auto geometry = [&](int hh, int ww) {
-    m->in_h = hh;
-    m->in_w = ww;
-    m->n_patches = (hh / c.patch) * (ww / c.patch);
-    m->n_tokens = m->n_patches + prefix_rows(m);
-  };
-  geometry(height, width);
-  if ((rc = build_pos_table(m))) {
-    geometry(old_h, old_w);  // the size in force stays what it was
-    const std::string why = m->err;
-    (void)build_pos_table(m);
-    return fail(m, rc, why);
-  }
+  return change_geometry(m, height, width, m->stride);
+}
+
+int vdr_set_patch_stride(vdr_handle m, int stride) {
+  // the argument check that needs no handle comes first (it also holds for a null one)
+  if (stride <= 0) return fail(m, VDR_ERR_INVALID, "vdr_set_patch_stride: stride must be positive");
+  if (!m) return fail(m, VDR_ERR_INVALID, "vdr_set_patch_stride: null handle");
+  const vdr_config& c = m->cfg;
+  if (c.patch && (stride > c.patch || c.patch % stride))
+    return fail(m, VDR_ERR_INVALID, "vdr_set_patch_stride: stride must divide patch " + std::to_string(c.patch));
+  if (c.window > 0)
+    return fail(m, VDR_ERR_UNSUPPORTED,
+                "vdr_set_patch_stride: not for the SAM encoder (its position tables and window partition are tied to its grid)");
+  if (!c.patch) return fail(m, VDR_ERR_UNSUPPORTED, "vdr_set_patch_stride: image models only (token model)");
+  if (!c.pre_ln && c.layers > 0) return fail(m, VDR_ERR_UNSUPPORTED, "vdr_set_patch_stride: pre-LN models only");
+  if (m->rope)
+    return fail(m, VDR_ERR_UNSUPPORTED,
+                "vdr_set_patch_stride: not for rope = 1 (DINOv3's patch coordinates are defined for non-overlapping patches only)");
+  if ((int64_t)((m->in_h - c.patch) / stride + 1) * ((m->in_w - c.patch) / stride + 1) > (1 << 20))
+    return fail(m, VDR_ERR_INVALID, "vdr_set_patch_stride: the input size in force gives more than 2^20 patches at this stride");
+  int rc = check_device(m);
+  if (rc) return rc;
+  if (!m->resolved) return fail(m, VDR_ERR_INCOMPLETE, "vdr_set_patch_stride: vdr_finalize has not run since the last vdr_set_weight");
+  DeviceGuard dg(m->device);
+  if (!dg.ok) return fail(m, VDR_ERR_HIP, "hipSetDevice failed");
+  return change_geometry(m, m->in_h, m->in_w, stride);
+}
+
+int vdr_get_patch_stride(vdr_handle m, int* stride) {
+  if (!m || !stride) return fail(m, VDR_ERR_INVALID, "vdr_get_patch_stride: null argument");
+  *stride = m->stride;
   return VDR_OK;
 }
 
@@ -2487,10 +2533,33 @@ int vdr_op_patch_embed(const void* images, int in_dtype, const void* W, const fl
   if (int rc = check_device(nullptr)) return rc;
   GemmArgs a;
   int variant;  // (the caller's W as it is; bf16 images with p = 8 / 16 / 32: no im2col pass, `col` untouched)
-  OP_TRY(patch_gemm(nullptr, (hipStream_t)stream, images, in_dtype, col, W, y, batch, C, img, img, p, D, &a, &variant), "im2col");
+  OP_TRY(patch_gemm(nullptr, (hipStream_t)stream, images, in_dtype, col, W, y, batch, C, img, img, p, p, D, &a, &variant), "im2col");
   a.bias = bias;
   a.pos = pos;
   a.omap = RowMap{(img / p) * (img / p), row_stride, row_offset};
+  OP_TRY(launch_gemm(a, EPI_PATCH, variant, (hipStream_t)stream), "patch gemm");
+  return VDR_OK;
+}
+
+int vdr_op_patch_embed_strided(const void* images, int in_dtype, const void* W, const float* bias, const float* pos, void* col,
+                               void* y, int batch, int C, int H, int Wd, int p, int stride, int D, int row_stride, int row_offset,
+                               void* stream) {
+  if (!images || !W || !col || !y) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_patch_embed_strided: null argument");
+  if (in_dtype != VDR_F32 && in_dtype != VDR_BF16) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_patch_embed_strided: in_dtype");
+  if (batch <= 0 || C <= 0 || D <= 0 || p <= 0) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_patch_embed_strided: batch, C, D and p must be positive");
+  if (stride <= 0 || stride > p || p % stride)
+    return fail(nullptr, VDR_ERR_INVALID, "vdr_op_patch_embed_strided: stride must be positive and divide p");
+  if (H < p || Wd < p || (H - p) % stride || (Wd - p) % stride)
+    return fail(nullptr, VDR_ERR_INVALID, "vdr_op_patch_embed_strided: (H - p) and (W - p) must be non-negative multiples of stride");
+  const int64_t n = (int64_t)((H - p) / stride + 1) * ((Wd - p) / stride + 1);
+  if (n > (1 << 20) || n * batch > INT32_MAX) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_patch_embed_strided: more than 2^20 patches per image or 2^31 rows");
+  if (int rc = check_device(nullptr)) return rc;
+  GemmArgs a;
+  int variant;  // (stride == p: vdr_op_patch_embed's paths, rectangular sizes through im2col)
+  OP_TRY(patch_gemm(nullptr, (hipStream_t)stream, images, in_dtype, col, W, y, batch, C, H, Wd, p, stride, D, &a, &variant), "im2col");
+  a.bias = bias;
+  a.pos = pos;
+  a.omap = RowMap{(int)n, row_stride, row_offset};
   OP_TRY(launch_gemm(a, EPI_PATCH, variant, (hipStream_t)stream), "patch gemm");
   return VDR_OK;
 }

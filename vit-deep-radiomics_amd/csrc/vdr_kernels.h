@@ -296,6 +296,10 @@ hipError_t launch_im2col3(const void* y, void* col, int batch, int g, int C, hip
 // k = c*p*p + ky*p + kx, zero padded to Kp
 hipError_t launch_im2col(const void* images, int in_bf16, void* col, int batch, int C, int H, int W, int p,
                          int Kp, hipStream_t s);
+// the same for Conv2d(kernel=p, stride=s), s | p (patch_stride.hip): n = ((H - p) / s + 1) * ((W - p) / s + 1) overlapping
+// patches, patch (py, px) starting at pixel (py*s, px*s); s == p is launch_im2col
+hipError_t launch_im2col_strided(const void* images, int in_bf16, void* col, int batch, int C, int H, int W, int p, int s,
+                                 int Kp, hipStream_t st);
 
 // pos_embed resampling (pos_interp.hip): the patch rows of a position table from a gh0 x gw0 grid to gh x gw, bicubic
 // (A = -0.75, align_corners = False, border taps clamped), fp64 arithmetic, one rounding to fp32

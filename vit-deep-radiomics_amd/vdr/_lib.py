@@ -61,6 +61,8 @@ SYMBOLS = {
     "vdr_finalize": (_I, [_P]),
     "vdr_set_input_size": (_I, [_P, _I, _I]),
     "vdr_get_input_size": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
+    "vdr_set_patch_stride": (_I, [_P, _I]),
+    "vdr_get_patch_stride": (_I, [_P, C.POINTER(_I)]),
     "vdr_num_weights": (_I, [_P]),
     "vdr_weight_name": (C.c_char_p, [_P, _I]),
     "vdr_workspace_bytes": (_I, [_P, _I, _I, C.POINTER(C.c_size_t)]),
@@ -106,6 +108,7 @@ SYMBOLS = {
     "vdr_op_rope2d_table": (_I, [_I, _I, _I, _F, _P, _P, _P]),
     "vdr_op_rope2d": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "vdr_op_patch_embed": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "vdr_op_patch_embed_strided": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vdr_profile_enable": (_I, [_P, _I]),
     "vdr_profile_mask": (_I, [_P, C.c_uint32]),
     "vdr_profile_read": (_I, [_P, C.POINTER(C.c_double), C.POINTER(_L), C.POINTER(C.c_double),

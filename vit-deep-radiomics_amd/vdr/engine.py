@@ -176,11 +176,17 @@ class Engine:
         return getattr(self, "_size", None) or (self.cfg.img, self.cfg.img)
 
     @property
+    def patch_stride(self) -> int:
+        """Stride of the patch convolution in force: patch until set_patch_stride."""
+        return getattr(self, "_stride", None) or self.cfg.patch
+
+    @property
     def grid(self) -> "tuple[int, int]":
-        """Patch grid (gh, gw) at the input size in force; token i of an image is patch (i // gw, i % gw)."""
+        """Patch grid (gh, gw) at the input size and patch stride in force -- ((side - patch) // stride + 1 per side; side //
+        patch at the default stride); token i of an image is patch (i // gw, i % gw)."""
         h, w = self.input_size
-        p = self.cfg.patch
-        return (h // p, w // p) if p else (0, 0)
+        p, s = self.cfg.patch, self.patch_stride
+        return ((h - p) // s + 1, (w - p) // s + 1) if p else (0, 0)
 
     @property
     def n_patches(self) -> int:
@@ -211,6 +217,27 @@ class Engine:
                              f"got {height} x {width}")
         L.check(self.lib.vdr_set_input_size(self.h, height, width), self.h)
         self._size = (height, width)
+
+    def set_patch_stride(self, stride: int):
+        """vdr_set_patch_stride: run the frozen patch convolution at `stride` <= patch (a divisor of patch) from now on, for
+        a ((H - patch) // stride + 1) x ((W - patch) // stride + 1) grid of overlapping patches from the same pixels
+        (dino-vit-features' ViTExtractor(stride=...)).  pos_embed's patch rows are resampled to that grid as
+        set_input_size resamples them; stride == patch restores the default path, bit for bit.  Load-time class, in any
+        order with set_input_size; the stride stays in force across later sizes.  SAM encoders, token models and RoPE
+        (DINOv3) models: ValueError."""
+        cfg = self.cfg
+        stride = int(stride)
+        if cfg.window > 0:
+            raise ValueError("set_patch_stride: the SAM encoder's position tables and window partition are tied to its grid")
+        if not cfg.patch:
+            raise ValueError("set_patch_stride: a token model has no patch convolution")
+        if cfg.rope:
+            raise ValueError("set_patch_stride: not for RoPE models (DINOv3's patch coordinates are defined for "
+                             "non-overlapping patches only)")
+        if stride <= 0 or stride > cfg.patch or cfg.patch % stride:
+            raise ValueError(f"set_patch_stride: stride must be a positive divisor of patch {cfg.patch}, got {stride}")
+        L.check(self.lib.vdr_set_patch_stride(self.h, stride), self.h)
+        self._stride = stride
 
     def _check_images(self, images: torch.Tensor):
         cfg = self.cfg

@@ -149,13 +149,29 @@ class VitDescriptorModel:
         self.engine.set_input_size(height, width)
         return self
 
+    def set_patch_stride(self, stride: int):
+        """Run the frozen patch convolution at `stride` (a divisor of the patch side) from now on: every dense output --
+        patch_embed, image_encoder, dense_tokens, get_intermediate_layers(reshape=True), get_attention_maps(reshape=True),
+        get_dense_descriptor, extract_dense, pipeline.generate_features -- comes on the finer
+        ((H - patch) // stride + 1) x ((W - patch) // stride + 1) grid of overlapping patches (Engine.set_patch_stride;
+        dino-vit-features' ViTExtractor(stride=...)).  The stride stays in force across input sizes (dynamic_size
+        included); stride == patch restores the default.  ViT / DINOv2 / CLIP / SigLIP models."""
+        if self.cfg.window > 0:
+            raise ValueError("set_patch_stride: the SAM encoder's position tables and window partition are tied to its grid")
+        self.engine.set_patch_stride(stride)
+        return self
+
     @property
     def input_size(self) -> "tuple[int, int]":
         return self.engine.input_size
 
     @property
+    def patch_stride(self) -> int:
+        return self.engine.patch_stride
+
+    @property
     def grid(self) -> "tuple[int, int]":
-        """(gh, gw) of the dense maps at the input size in force."""
+        """(gh, gw) of the dense maps at the input size and patch stride in force."""
         return self.engine.grid
 
     def _adopt(self, x):
@@ -378,7 +394,8 @@ class _SiglipPoolHead:
 
 def load_model(model_name: str, model_path=None, weights=None, device=None, micro_batch: int = 0, streams: int = 0,
                fp8: int = 0, full_last_block: bool = False, ln_fold: bool = True, fp8_cls_bf16: bool = False,
-               resid_fp32: bool = False, ln_fin_fused: bool = False, dynamic_size: bool = False, img_size=None):
+               resid_fp32: bool = False, ln_fin_fused: bool = False, dynamic_size: bool = False, img_size=None,
+               stride=None):
     """R1.  model_name: 'dinov2' | 'medsam' (reference names) or any key of ARCHS.
     model_path: a PyTorch state_dict file with the canonical key names; loaded with
     torch.load(weights_only=True).  weights: the same dict passed directly.  A transformers CLIPVisionModel
@@ -399,7 +416,9 @@ def load_model(model_name: str, model_path=None, weights=None, device=None, micr
     input side, as segment_anything's ImageEncoderViT(img_size=...) -- a multiple of the patch side, at most 64 patches a
     side -- and load the checkpoint's native tables into it: pos_embed [1, 64, 64, D] and the global blocks' rel_pos_h / w
     [127, 64] are resampled once on the device (bicubic / get_rel_pos's linear rule).  get_dense_descriptor and
-    generate_features then prepare raw slices at that side."""
+    generate_features then prepare raw slices at that side.
+    stride (default None = the patch side): run the patch convolution at this stride, a divisor of the patch side, for a
+    finer dense grid (VitDescriptorModel.set_patch_stride); not for SAM / MedSAM and DINOv3 models."""
     if model_name not in ARCHS:
         raise KeyError(f"unknown model_name {model_name!r}; known: {sorted(ARCHS)} + 'medsam'")
     arch = ARCHS[model_name]
@@ -433,6 +452,8 @@ def load_model(model_name: str, model_path=None, weights=None, device=None, micr
         weights = from_dinov2_hf_state_dict(weights)
     model = VitDescriptorModel(cfg, weights, model_name, device, dynamic_size=dynamic_size, sized=img_size is not None)
     model.model_name = model_name
+    if stride is not None:
+        model.set_patch_stride(stride)
     return model
 
 
@@ -466,9 +487,9 @@ def get_dense_descriptor(model, img) -> np.ndarray:
     if model.model_name == "medsam":
         f = model.image_encoder(t).cpu().numpy()
         return np.transpose(np.squeeze(f), (1, 2, 0))
-    f = np.squeeze(model.patch_embed(t).cpu().numpy())
-    s = int(np.sqrt(f.shape[0]))
-    return f.reshape(s, s, f.shape[1])
+    f = model.patch_embed(t).cpu().numpy()
+    gh, gw = model.engine.grid
+    return f.reshape(gh, gw, f.shape[-1])
 
 
 def extract_dense(model, images: torch.Tensor, encoder: bool = True) -> np.ndarray:

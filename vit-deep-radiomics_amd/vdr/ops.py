@@ -260,6 +260,28 @@ def patch_embed(images, weight, bias, p, pos=None, row_stride=None, row_offset=0
     return out
 
 
+def patch_embed_strided(images, weight, bias, p, stride, pos=None, row_stride=None, row_offset=0, return_col=False):
+    """Conv2d(kernel=p, stride=stride) patch embedding (vdr_op_patch_embed_strided): images [B,C,H,W] fp32/bf16, (H - p) and
+    (W - p) multiples of stride; weight [D,C,p,p]; returns bf16 [B*row_stride, D] (and, return_col, the col matrix
+    [B*n, Kp] the GEMM read: written whenever stride < p)."""
+    lib = L.load()
+    B, Cc, H, W = images.shape
+    D = weight.shape[0]
+    n = ((H - p) // stride + 1) * ((W - p) // stride + 1)
+    K = Cc * p * p
+    Kp = (K + 63) // 64 * 64
+    Wp = torch.zeros((D, Kp), dtype=torch.bfloat16, device=images.device)
+    Wp[:, :K] = weight.reshape(D, K).to(torch.bfloat16)
+    col = torch.full((B * n * Kp + 4096,), float("nan"), dtype=torch.bfloat16, device=images.device)
+    row_stride = n if row_stride is None else row_stride
+    out = torch.zeros((B * row_stride, D), dtype=torch.bfloat16, device=images.device)
+    images = images.contiguous()
+    L.check(lib.vdr_op_patch_embed_strided(images.data_ptr(), 1 if images.dtype == torch.bfloat16 else 0, Wp.data_ptr(),
+                                           _p(bias), _p(pos), col.data_ptr(), out.data_ptr(), B, Cc, H, W, p, stride, D,
+                                           row_stride, row_offset, _s(images)))
+    return (out, col[:B * n * Kp].view(B * n, Kp)) if return_col else out
+
+
 def interpolate_pos(pos: torch.Tensor, native_grid, grid) -> torch.Tensor:
     """pos [gh0*gw0, D] fp32 on the device (the patch rows of a position table, no CLS row) -> [gh*gw, D] fp32: DINOv2 /
     transformers interpolate_pos_encoding (vdr_op_interpolate_pos: bicubic, align_corners=False, fp64 arithmetic)."""

@@ -129,8 +129,8 @@ def generate_features(model, img_3d, mask_3d, flip=None, max_batch=16):
         if medsam:
             maps = model.engine.forward(x, L.OUT_ENCODER, torch.float32)          # [b, g, g, C] channel-last
         else:
-            g = model.cfg.img // model.cfg.patch
-            maps = model.engine.forward(x, L.OUT_PATCH_EMBED, torch.float32).reshape(s1 - s0, g, g, model.cfg.dim)
+            gh, gw = model.engine.grid  # (img / patch a side by default; finer after set_patch_stride)
+            maps = model.engine.forward(x, L.OUT_PATCH_EMBED, torch.float32).reshape(s1 - s0, gh, gw, model.cfg.dim)
         if rb is None:  # the boxes depend on the (cropped) union mask only: once per volume, not once per slice
             rb = roi_box(maps.shape[1:3], bigger_c)
             mb = roi_box(mask_c.shape[0:2], bigger_c)
