@@ -354,6 +354,43 @@ typedef struct {
 int vdr_forward_attn_maps(vdr_handle h, const void* images, int in_dtype, int batch, const vdr_layer_out* outs, int n_outs,
                           const vdr_attn_map* maps, int n_maps, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Facet descriptors ("Deep ViT Features as Dense Visual Descriptors", ViTExtractor.extract_descriptors(x, layer, facet,
+ * bin, include_cls)): the keys, queries or values of one block's attention, or the residual stream after it, optionally
+ * log-binned.  With P prefix rows (CLS + registers), n = gh * gw patch rows, N = P + n:
+ *   QUERY | KEY | VALUE of block i: the output of its qkv linear, bias included, heads concatenated -- columns [0, D),
+ *     [D, 2D), [2D, 3D) of the [B*N, 3D] bf16 activation the attention kernels read -- BEFORE the 2-D RoPE rotation of a
+ *     vdr_config_ext.rope model (what a forward hook on attn.qkv sees) and before any dh^-0.5 scale.
+ *   TOKEN of block i: the raw residual stream after it, bitwise a vdr_layer_out with norm = 0 in VDR_OUT_DENSE
+ *     (all_rows = 0) or VDR_OUT_TOKENS (all_rows = 1) mode at the same dtype.
+ *   hierarchy = 0: [B, n, D] (all_rows = 1: [B, N, D], rows as VDR_OUT_TOKENS orders them), one rounding to out_dtype.
+ *   hierarchy = h in 1..3: vdr_op_log_bin of the n patch rows on the gh x gw grid, [B, n, (1 + 8h) * D]; all_rows must be 0. */
+enum { VDR_FACET_TOKEN = 0, VDR_FACET_QUERY = 1, VDR_FACET_KEY = 2, VDR_FACET_VALUE = 3 };
+typedef struct {
+  int32_t layer;     /* block 0 .. L-1                                                               */
+  int32_t facet;     /* VDR_FACET_TOKEN | QUERY | KEY | VALUE                                        */
+  int32_t hierarchy; /* 0: no binning; 1..3: log-binned                                              */
+  int32_t all_rows;  /* 0: the n patch rows; 1: all N rows (hierarchy must be 0)                     */
+  int32_t out_dtype; /* VDR_F32 | VDR_BF16                                                           */
+  void* out;         /* device, contiguous; image b's rows start at out + b * (per-image elements)   */
+} vdr_facet_out;
+
+/* vdr_forward_attn_maps plus n_facets >= 1 facets, in one forward.  outs and maps keep exactly their meaning, checks and
+ * bits; either may be empty (NULL, 0).  Facets may name any blocks in any order, several per block.  q / k / v facets of
+ * block i are written right after its qkv GEMM, before the rotation and the attention: unbinned as a strided row gather,
+ * binned by the log-bin kernel reading the qkv activation in place, its level means in the (then dead) fc1 activation
+ * buffer.  A TOKEN facet is written where the block's outs are.  Blocks past the largest requested layer do not run; a
+ * last block whose only requests are q / k / v facets stops after its qkv GEMM (with maps: after its attention); a TOKEN
+ * facet needs every row of its block, so the CLS-rows-only last block does not apply then.  Facet launches are booked as
+ * VDR_K_FINAL_LN.  Supported models, workspace and VDR_ERR_UNSUPPORTED refusals: those of vdr_forward_layers, plus a
+ * hierarchy whose level means ((h - 1) * micro-batch * n * D fp32) do not fit the fc1 activation buffer, or with D % 8 != 0
+ * (both refused before anything is launched or written).  fp8 handles are
+ * allowed: their qkv activation is the same bf16 [q | k | v] image the attention reads (the MX GEMM writes bf16 there).
+ * Refused before the device is touched (VDR_ERR_INVALID): null facets, n_facets <= 0, a null out, a layer out of range,
+ * an unknown facet or dtype, hierarchy outside 0..3, all_rows not 0 / 1 or set together with a hierarchy. */
+int vdr_forward_facets(vdr_handle h, const void* images, int in_dtype, int batch, const vdr_layer_out* outs, int n_outs,
+                       const vdr_attn_map* maps, int n_maps, const vdr_facet_out* facets, int n_facets, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* Replaces: TransformerNoduleClassifier.forward up to x[:,0,:]
  * (models_archs.py:141-147): tokens [batch, seq, D] fp32/bf16 on device ->
  * [cls ; tokens] -> (input LN) -> L blocks -> out by out_mode
@@ -682,6 +719,19 @@ int vdr_op_patch_embed(const void* images, int in_dtype, const void* W, const fl
 int vdr_op_patch_embed_strided(const void* images, int in_dtype, const void* W, const float* bias, const float* pos, void* col,
                                void* y, int batch, int C, int H, int Wd, int p, int stride, int D, int row_stride, int row_offset,
                                void* stream);
+/* Log-binning of a dense descriptor map (csrc/log_bin.hip).  F[b, y, x, c] on a gh x gw grid, C channels, hierarchy h:
+ *   A_k = mean of F over the 3^k x 3^k window centred at (y, x) intersected with the grid (divided by the in-grid count);
+ *   bins: k = 0 .. h-1, dy in (-3^k, 0, +3^k), dx likewise, (0, 0) skipped for k >= 1 -- 1 + 8h bins;
+ *   out[b, y*gw + x, j*C + c] = A_k[b, clamp(y + dy, 0, gh-1), clamp(x + dx, 0, gw-1), c], bin-major, [batch, gh*gw, (1+8h)*C].
+ * x points at the first patch row's first channel; consecutive patch rows are ld elements apart, images image_stride
+ * elements apart (in_dtype VDR_BF16 | VDR_F32).  Window sums are fixed-order fp32 additions without atomics (a value's
+ * bits do not depend on the batch position or the launch), the mean is one IEEE fp32 division sum / count, bf16 output is
+ * one rounding of that, level-0 bins are exact copies.  work: fp32 scratch of (h-1)*batch*gh*gw*C elements (NULL allowed
+ * when h == 1).  Refused before the device is touched: VDR_ERR_INVALID for C % 8 != 0, ld < C, null pointers,
+ * non-positive sizes, pointers or rows (ld, image_stride) that are not 16-byte aligned; VDR_ERR_UNSUPPORTED for a
+ * hierarchy outside 1..3. */
+int vdr_op_log_bin(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int batch, int gh, int gw, int C,
+                   int hierarchy, float* work, void* out, int out_dtype, void* stream);
 /* ---- measurement ------------------------------------------------------------------------ */
 
 /* Kernel classes timed by the built-in HIP-event profiler. */

@@ -596,11 +596,12 @@ hipError_t launch_assemble_tokens(const void* tok, int in_bf16, const float* cls
 
 // y[r][:] = x[imap(r)][:]  (bf16 or fp32 in; bf16 or fp32 out) — the x[:,0,:] / x[:,1:,:] slice for models
 // without a final norm (post-LN nn.TransformerEncoder, models_archs.py:147), the raw residual stream of
-// vdr_forward_layers (norm = 0), the fp32 copy of the stream (resid_fp32).  Output row stride ldy elements.
+// vdr_forward_layers (norm = 0), the fp32 copy of the stream (resid_fp32), a q / k / v facet out of the qkv activation
+// (ldx = 3D).  Input row stride ldx, output row stride ldy elements.
 template <bool IN_F32, bool OUT_BF16>
 __global__ __launch_bounds__(256) void gather_rows_kernel(const void* __restrict__ x, void* __restrict__ y,
-                                                          int64_t rows, int D, int rpg, int64_t gs, int off, int64_t ldy,
-                                                          int vec_out) {
+                                                          int64_t rows, int D, int rpg, int64_t gs, int off, int64_t ldx,
+                                                          int64_t ldy, int vec_out) {
   const int d4 = D >> 2;
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= rows * d4) return;
@@ -609,11 +610,11 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const void* __restrict
   const int64_t ir = map_row(r, rpg, gs, off);
   float v[4];
   if (IN_F32) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>((const float*)x + ir * D + d);
+    const f32x4 a = *reinterpret_cast<const f32x4*>((const float*)x + ir * ldx + d);
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = a[e];
   } else {
-    const bf16x4 a = *reinterpret_cast<const bf16x4*>((const bf16_t*)x + ir * D + d);
+    const bf16x4 a = *reinterpret_cast<const bf16x4*>((const bf16_t*)x + ir * ldx + d);
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = (float)a[e];
   }
@@ -640,14 +641,14 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const void* __restrict
 }
 
 hipError_t launch_gather_rows(const void* x, void* y, int out_bf16, int64_t rows, int D, RowMap imap,
-                              hipStream_t s, int in_f32, int64_t ldy) {
-  if ((D & 3) || (ldy != 0 && ldy < D)) return hipErrorInvalidValue;
+                              hipStream_t s, int in_f32, int64_t ldy, int64_t ldx) {
+  if ((D & 3) || (ldy != 0 && ldy < D) || (ldx != 0 && (ldx < D || (ldx & 3)))) return hipErrorInvalidValue;
   const int64_t total = rows * (D / 4);
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
   const int64_t ld = ldy ? ldy : D;
   const int vec = ldy == 0 || rows_aligned(y, ld, out_bf16 ? 2 : 4);
 #define VDR_GATHER(F, B)                                                                                                  \
-  hipLaunchKernelGGL((gather_rows_kernel<F, B>), grid, block, 0, s, x, y, rows, D, imap.rpg, imap.gstride, imap.off, ld, vec)
+  hipLaunchKernelGGL((gather_rows_kernel<F, B>), grid, block, 0, s, x, y, rows, D, imap.rpg, imap.gstride, imap.off, ldx ? ldx : (int64_t)D, ld, vec)
   if (in_f32) {
     if (out_bf16) VDR_GATHER(true, true); else VDR_GATHER(true, false);
   } else {

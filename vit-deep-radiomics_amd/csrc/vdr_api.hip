@@ -1180,6 +1180,7 @@ int block_tail_cls(vdr_model* m, hipStream_t s, const Carve& w, const LayerW& L,
 struct EmitList {
   std::vector<std::vector<const vdr_layer_out*>> at;  // [block] -> outputs of that block
   std::vector<std::vector<const vdr_attn_map*>> maps; // [block] -> attention maps of that block (vdr_forward_attn_maps)
+  std::vector<std::vector<const vdr_facet_out*>> facets;  // [block] -> facets of that block (vdr_forward_facets)
   int last = -1;                                      // last block that runs (the largest requested layer)
   int b0 = 0;
 };
@@ -1248,6 +1249,48 @@ int write_output(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, 
   return VDR_OK;
 }
 
+// Writes one facet (vdr_forward_facets) for images b0 .. b0 + mb - 1.  q / k / v: from the qkv activation of their
+// micro-batch, right after the block's qkv GEMM (before the RoPE rotation and the attention); TOKEN: from the residual
+// stream after the block, where write_output runs -- unbinned THROUGH write_output (the bits of a norm = 0 layer output).
+// Binned: the log-bin kernel reads the patch rows where they lie; its level means go to the fc1 activation w.u, dead from
+// fc2 of block i - 1 to fc1 of block i and from fc2 of block i on (as the pooled output's partial sums).  Booked as
+// VDR_K_FINAL_LN.
+int write_facet(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, const vdr_facet_out& f, int b0) {
+  const vdr_config& c = m->cfg;
+  const int D = c.dim, P = prefix_rows(m), n = ntok - P, h = f.hierarchy;
+  const int ob = f.out_dtype == VDR_BF16;
+  const size_t es = ob ? 2 : 4;
+  const bool token = f.facet == VDR_FACET_TOKEN;
+  if (token && !h) {
+    vdr_layer_out o{};
+    o.layer = f.layer;
+    o.out_mode = f.all_rows ? VDR_OUT_TOKENS : VDR_OUT_DENSE;
+    o.out_dtype = f.out_dtype;
+    o.out = f.out;
+    return write_output(m, s, w, mb, ntok, o, b0, false);
+  }
+  // the source rows: the stream (its fp32 master copy under resid_fp32), or the facet's columns of the qkv activation
+  const bool f32 = token && w.x32 != nullptr;
+  const int64_t ld = token ? D : 3 * D;
+  const size_t ies = f32 ? 4 : 2;
+  const char* src = token ? (f32 ? (const char*)w.x32 : (const char*)w.x) : (const char*)w.qkv + (size_t)(f.facet - VDR_FACET_QUERY) * D * 2;
+  if (!h) {
+    const int64_t rpi = f.all_rows ? ntok : n;
+    char* dst = (char*)f.out + (size_t)b0 * rpi * D * es;
+    Scope sc(m, s, VDR_K_FINAL_LN, 0.0, (double)mb * rpi * D * (2 + es));
+    VDR_TRY(launch_gather_rows(src, dst, ob, (int64_t)mb * rpi, D, f.all_rows ? identity_map() : RowMap{n, ntok, P}, s, 0, 0, ld),
+            "gather_rows(facet)");
+    return VDR_OK;
+  }
+  // (forward_layers_impl has checked that the level means fit w.u and that D % 8 == 0)
+  const int bins = 1 + 8 * h;
+  char* dst = (char*)f.out + (size_t)b0 * n * bins * D * es;
+  Scope sc(m, s, VDR_K_FINAL_LN, 0.0, (double)mb * n * D * (ies + (double)bins * es));
+  VDR_TRY(launch_log_bin(src + (size_t)P * ld * ies, !f32, ld, (int64_t)ntok * ld, mb, grid_h(m), grid_w(m), D, h, (float*)w.u, dst, ob, s),
+          "log_bin");
+  return VDR_OK;
+}
+
 // What a forward asks of run_blocks beyond the rows themselves
 struct BlockRun {
   const int* lens = nullptr;   // variable-length token sequences: the valid keys of each (device pointer), plus len_add
@@ -1275,7 +1318,25 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, Bl
     if (el)
       for (const vdr_layer_out* o : el->at[i])
         if (int e = write_output(m, s, w, mb, ntok, *o, el->b0, cmp)) return e;
+    // (TOKEN facets: a block that has one runs every row -- forward_layers_impl keeps the CLS tail off it)
+    if (el && !cmp)
+      for (const vdr_facet_out* f : el->facets[i])
+        if (f->facet == VDR_FACET_TOKEN)
+          if (int e = write_facet(m, s, w, mb, ntok, *f, el->b0)) return e;
     return (int)VDR_OK;
+  };
+  // vdr_forward_facets: block i's q / k / v facets, from its qkv, right after the qkv GEMM (before rope and attention)
+  auto facets_after_qkv = [&](int i) {
+    if (el)
+      for (const vdr_facet_out* f : el->facets[i])
+        if (f->facet != VDR_FACET_TOKEN)
+          if (int e = write_facet(m, s, w, mb, ntok, *f, el->b0)) return e;
+    return (int)VDR_OK;
+  };
+  auto has_token_facet = [&](int i) {
+    for (const vdr_facet_out* f : el->facets[i])
+      if (f->facet == VDR_FACET_TOKEN) return true;
+    return false;
   };
   auto attention = [&]() {
     if (m->rope) {
@@ -1299,7 +1360,7 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, Bl
     return (int)VDR_OK;
   };
   // a last block whose only requests are maps stops after its attention
-  auto maps_only_last = [&](int i) { return el && i == el->last && el->at[i].empty(); };
+  auto maps_only_last = [&](int i) { return el && i == el->last && el->at[i].empty() && !has_token_facet(i); };
   const BlockPath path = block_path(m);
   // The fold's producers (proj, fc2) leave the partials and finalise the statistics where a consumer reads finalised ones;
   // launches small enough for the ring3 / ring4 consumers to finalise their own rows from the partials need nothing.
@@ -1322,6 +1383,9 @@ int run_blocks(vdr_model* m, hipStream_t s, const Carve& w, int mb, int ntok, Bl
     const LayerW& L = m->layers[i];
     const BlockSteps b{m, s, w, L, path};
     if ((rc = b.norm_linear(false, M, x, w.h, w.qkv, w.Mp))) return rc;
+    if ((rc = facets_after_qkv(i))) return rc;
+    // a last block whose only requests are q / k / v facets stops after its qkv GEMM
+    if (maps_only_last(i) && el->maps[i].empty()) return VDR_OK;
     if ((rc = attention())) return rc;
     if ((rc = maps_after_attention(i))) return rc;
     if (maps_only_last(i)) return VDR_OK;
@@ -1942,8 +2006,8 @@ int vdr_forward(vdr_handle m, const void* images, int in_dtype, int batch, void*
 // vdr_forward_layers and vdr_forward_attn_maps (fn: the name the model refusals carry); the callers have checked the
 // outs / maps arrays themselves
 static int forward_layers_impl(const char* fn, vdr_handle m, const void* images, int in_dtype, int batch, const vdr_layer_out* outs,
-                               int n_outs, const vdr_attn_map* maps, int n_maps, void* workspace, size_t workspace_bytes,
-                               void* stream) {
+                               int n_outs, const vdr_attn_map* maps, int n_maps, const vdr_facet_out* facets, int n_facets,
+                               void* workspace, size_t workspace_bytes, void* stream) {
   for (int k = 0; k < n_outs; ++k) {
     const vdr_layer_out& o = outs[k];
     const std::string at = "outs[" + std::to_string(k) + "]: ";
@@ -1967,6 +2031,15 @@ static int forward_layers_impl(const char* fn, vdr_handle m, const void* images,
   EmitList el;
   el.at.resize(c.layers);
   el.maps.resize(c.layers);
+  el.facets.resize(c.layers);
+  for (int k = 0; k < n_facets; ++k) {
+    const vdr_facet_out& f = facets[k];
+    if (f.layer < 0 || f.layer >= c.layers)
+      return fail(m, VDR_ERR_INVALID, "facets[" + std::to_string(k) + "]: layer " + std::to_string(f.layer) + " out of range 0.." +
+                                          std::to_string(c.layers - 1));
+    el.facets[f.layer].push_back(&f);
+    if (f.layer > el.last) el.last = f.layer;
+  }
   for (int k = 0; k < n_maps; ++k) {
     const vdr_attn_map& a = maps[k];
     const std::string at = "maps[" + std::to_string(k) + "]: ";
@@ -1987,8 +2060,23 @@ static int forward_layers_impl(const char* fn, vdr_handle m, const void* images,
     el.at[o.layer].push_back(&o);
     if (o.layer > el.last) el.last = o.layer;
   }
+  // binned facets, before anything is launched: 16-byte chunks of D channels, and the level means of the largest
+  // micro-batch -- (h - 1) * mb * n * D fp32 -- inside the fc1 activation buffer (carve: Mp * mlp_hidden bf16)
+  {
+    const int mb = default_micro_batch(m, batch);
+    const size_t u_bytes = (size_t)carve(m, nullptr, mb, m->n_tokens).Mp * c.mlp_hidden * 2;
+    for (int k = 0; k < n_facets; ++k) {
+      const int h = facets[k].hierarchy;
+      if (!h) continue;
+      const std::string at = "facets[" + std::to_string(k) + "]: ";
+      if (D % 8) return fail(m, VDR_ERR_UNSUPPORTED, at + "log-binning needs dim % 8 == 0");
+      if ((size_t)(h - 1) * mb * m->n_patches * D * 4 > u_bytes)
+        return fail(m, VDR_ERR_UNSUPPORTED, at + "the level means of hierarchy " + std::to_string(h) + " do not fit the MLP activation buffer");
+    }
+  }
   bool cls_only = true;  // every output of the last block that runs is CLS: that block may run its CLS rows only
   for (const vdr_layer_out* o : el.at[el.last]) cls_only = cls_only && o->out_mode == VDR_OUT_CLS;
+  for (const vdr_facet_out* f : el.facets[el.last]) cls_only = cls_only && f->facet != VDR_FACET_TOKEN;  // (the stream's every row)
   const int ntok = m->n_tokens;
   const size_t img_bytes = (size_t)c.in_chans * m->in_h * m->in_w * (in_dtype == VDR_BF16 ? 2 : 4);
   return run_micro_batches(m, batch, ntok, workspace, workspace_bytes, stream, [&](hipStream_t s, const Carve& w, int b0, int mb) {
@@ -2007,14 +2095,12 @@ int vdr_forward_layers(vdr_handle m, const void* images, int in_dtype, int batch
                        void* workspace, size_t workspace_bytes, void* stream) {
   // argument checks that need no model first (they also hold for a null handle), then the model's
   if (!outs || n_outs <= 0) return fail(m, VDR_ERR_INVALID, "null outs or n_outs <= 0");
-  return forward_layers_impl("vdr_forward_layers", m, images, in_dtype, batch, outs, n_outs, nullptr, 0, workspace, workspace_bytes,
-                             stream);
+  return forward_layers_impl("vdr_forward_layers", m, images, in_dtype, batch, outs, n_outs, nullptr, 0, nullptr, 0, workspace,
+                             workspace_bytes, stream);
 }
 
-int vdr_forward_attn_maps(vdr_handle m, const void* images, int in_dtype, int batch, const vdr_layer_out* outs, int n_outs,
-                          const vdr_attn_map* maps, int n_maps, void* workspace, size_t workspace_bytes, void* stream) {
-  // the checks that need no model come first, as vdr_forward_layers orders its own
-  if (!maps || n_maps <= 0) return fail(m, VDR_ERR_INVALID, "null maps or n_maps <= 0");
+// the per-map checks that need no model (vdr_forward_attn_maps, vdr_forward_facets)
+static int check_maps(vdr_handle m, const vdr_attn_map* maps, int n_maps) {
   for (int k = 0; k < n_maps; ++k) {
     const vdr_attn_map& a = maps[k];
     const std::string at = "maps[" + std::to_string(k) + "]: ";
@@ -2023,8 +2109,37 @@ int vdr_forward_attn_maps(vdr_handle m, const void* images, int in_dtype, int ba
     if (a.head_mean != 0 && a.head_mean != 1) return fail(m, VDR_ERR_INVALID, at + "head_mean must be 0 or 1");
     if (a.out_dtype != VDR_F32 && a.out_dtype != VDR_BF16) return fail(m, VDR_ERR_INVALID, at + "out_dtype");
   }
+  return VDR_OK;
+}
+
+int vdr_forward_attn_maps(vdr_handle m, const void* images, int in_dtype, int batch, const vdr_layer_out* outs, int n_outs,
+                          const vdr_attn_map* maps, int n_maps, void* workspace, size_t workspace_bytes, void* stream) {
+  // the checks that need no model come first, as vdr_forward_layers orders its own
+  if (!maps || n_maps <= 0) return fail(m, VDR_ERR_INVALID, "null maps or n_maps <= 0");
+  if (int rc = check_maps(m, maps, n_maps)) return rc;
   if (n_outs < 0 || (n_outs > 0 && !outs)) return fail(m, VDR_ERR_INVALID, "null outs with n_outs > 0, or n_outs < 0");
-  return forward_layers_impl("vdr_forward_attn_maps", m, images, in_dtype, batch, outs, n_outs, maps, n_maps, workspace,
+  return forward_layers_impl("vdr_forward_attn_maps", m, images, in_dtype, batch, outs, n_outs, maps, n_maps, nullptr, 0, workspace,
+                             workspace_bytes, stream);
+}
+
+int vdr_forward_facets(vdr_handle m, const void* images, int in_dtype, int batch, const vdr_layer_out* outs, int n_outs,
+                       const vdr_attn_map* maps, int n_maps, const vdr_facet_out* facets, int n_facets, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+  if (!facets || n_facets <= 0) return fail(m, VDR_ERR_INVALID, "null facets or n_facets <= 0");
+  for (int k = 0; k < n_facets; ++k) {
+    const vdr_facet_out& f = facets[k];
+    const std::string at = "facets[" + std::to_string(k) + "]: ";
+    if (!f.out) return fail(m, VDR_ERR_INVALID, at + "null out");
+    if (f.facet < VDR_FACET_TOKEN || f.facet > VDR_FACET_VALUE) return fail(m, VDR_ERR_INVALID, at + "facet must be TOKEN, QUERY, KEY or VALUE");
+    if (f.hierarchy < 0 || f.hierarchy > 3) return fail(m, VDR_ERR_INVALID, at + "hierarchy must be 0 (no binning) or 1..3");
+    if (f.all_rows != 0 && f.all_rows != 1) return fail(m, VDR_ERR_INVALID, at + "all_rows must be 0 or 1");
+    if (f.all_rows && f.hierarchy) return fail(m, VDR_ERR_INVALID, at + "a binned facet takes the patch rows only (all_rows = 0)");
+    if (f.out_dtype != VDR_F32 && f.out_dtype != VDR_BF16) return fail(m, VDR_ERR_INVALID, at + "out_dtype");
+  }
+  if (n_outs < 0 || (n_outs > 0 && !outs)) return fail(m, VDR_ERR_INVALID, "null outs with n_outs > 0, or n_outs < 0");
+  if (n_maps < 0 || (n_maps > 0 && !maps)) return fail(m, VDR_ERR_INVALID, "null maps with n_maps > 0, or n_maps < 0");
+  if (int rc = check_maps(m, maps, n_maps)) return rc;
+  return forward_layers_impl("vdr_forward_facets", m, images, in_dtype, batch, outs, n_outs, maps, n_maps, facets, n_facets, workspace,
                              workspace_bytes, stream);
 }
 
@@ -2562,6 +2677,24 @@ int vdr_op_patch_embed_strided(const void* images, int in_dtype, const void* W, 
   a.omap = RowMap{(int)n, row_stride, row_offset};
   OP_TRY(launch_gemm(a, EPI_PATCH, variant, (hipStream_t)stream), "patch gemm");
   return VDR_OK;
+}
+
+int vdr_op_log_bin(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int batch, int gh, int gw, int C, int hierarchy,
+                   float* work, void* out, int out_dtype, void* stream) {
+  if ((in_dtype != VDR_F32 && in_dtype != VDR_BF16) || (out_dtype != VDR_F32 && out_dtype != VDR_BF16))
+    return fail(nullptr, VDR_ERR_INVALID, "log_bin: dtype");
+  if (!x || !out || batch <= 0 || gh <= 0 || gw <= 0 || C <= 0) return fail(nullptr, VDR_ERR_INVALID, "log_bin: null pointer or non-positive size");
+  if (hierarchy < 1 || hierarchy > 3) return fail(nullptr, VDR_ERR_UNSUPPORTED, "log_bin: hierarchy must be 1, 2 or 3");
+  if (C % 8 != 0) return fail(nullptr, VDR_ERR_INVALID, "log_bin: C must be a multiple of 8");
+  if (ld < C || image_stride < 0) return fail(nullptr, VDR_ERR_INVALID, "log_bin: ld must be >= C, image_stride >= 0");
+  if (hierarchy > 1 && !work) return fail(nullptr, VDR_ERR_INVALID, "log_bin: null work with hierarchy > 1");
+  const int64_t per16 = in_dtype == VDR_BF16 ? 8 : 4;  // elements of a 16-byte chunk
+  if (!aligned16({x, out, work}) || ld % per16 || image_stride % per16)
+    return fail(nullptr, VDR_ERR_INVALID, "log_bin: x, work, out and every row (ld, image_stride) must be 16-byte aligned");
+  if ((int64_t)batch * gh * gw > INT32_MAX) return fail(nullptr, VDR_ERR_INVALID, "log_bin: batch * gh * gw exceeds 2^31 - 1");
+  RUN_OP(launch_log_bin(x, in_dtype == VDR_BF16, ld, image_stride, batch, gh, gw, C, hierarchy, work, out, out_dtype == VDR_BF16,
+                        (hipStream_t)stream),
+         "log_bin");
 }
 
 // ---- profiler ---------------------------------------------------------------------------------------

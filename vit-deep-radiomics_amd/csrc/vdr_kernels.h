@@ -301,6 +301,12 @@ hipError_t launch_im2col(const void* images, int in_bf16, void* col, int batch, 
 hipError_t launch_im2col_strided(const void* images, int in_bf16, void* col, int batch, int C, int H, int W, int p, int s,
                                  int Kp, hipStream_t st);
 
+// Log-binned descriptors (log_bin.hip): out [batch, gh*gw, (1 + 8*hierarchy)*C] from F read in place (patch rows ld
+// elements apart, images image_stride apart, bf16 or fp32); work: fp32 [(hierarchy-1)*batch*gh*gw*C] for the level means
+// (three or fewer box-sum launches in front of the copy).  C % 8 == 0; x, work, out and every row 16-byte aligned.
+hipError_t launch_log_bin(const void* x, int in_bf16, int64_t ld, int64_t image_stride, int batch, int gh, int gw, int C,
+                          int hierarchy, float* work, void* out, int out_bf16, hipStream_t st);
+
 // pos_embed resampling (pos_interp.hip): the patch rows of a position table from a gh0 x gw0 grid to gh x gw, bicubic
 // (A = -0.75, align_corners = False, border taps clamped), fp64 arithmetic, one rounding to fp32
 hipError_t launch_pos_interp(const float* pos, int gh0, int gw0, int D, float* out, int gh, int gw, hipStream_t s);
@@ -337,7 +343,7 @@ hipError_t launch_ln_rows_stats(void* x, const float* gamma, const float* beta, 
 
 // y[r] = x[imap(r)], bf16 -> bf16 / fp32
 hipError_t launch_gather_rows(const void* x, void* y, int out_bf16, int64_t rows, int D, RowMap imap,
-                              hipStream_t s, int in_f32 = 0, int64_t ldy = 0);
+                              hipStream_t s, int in_f32 = 0, int64_t ldy = 0, int64_t ldx = 0);
 
 // Mean over the patch rows of each image, of the final-normalised (norm = 1: LayerNorm with gamma / beta, the arithmetic
 // of the LayerNorm kernel) or raw (norm = 0) residual stream: x rows b*ntok + ncls + j, j < n, of `batch` images ->

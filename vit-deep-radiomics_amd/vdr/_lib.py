@@ -47,6 +47,15 @@ class vdr_attn_map(C.Structure):
                 ("out", C.c_void_p)]
 
 
+FACET_TOKEN, FACET_QUERY, FACET_KEY, FACET_VALUE = 0, 1, 2, 3
+FACETS = {"token": FACET_TOKEN, "query": FACET_QUERY, "key": FACET_KEY, "value": FACET_VALUE}
+
+
+class vdr_facet_out(C.Structure):
+    _fields_ = [("layer", C.c_int32), ("facet", C.c_int32), ("hierarchy", C.c_int32), ("all_rows", C.c_int32),
+                ("out_dtype", C.c_int32), ("out", C.c_void_p)]
+
+
 # every symbol include/vdr.h declares: name -> (restype, argtypes)
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SYMBOLS = {
@@ -70,6 +79,8 @@ SYMBOLS = {
     "vdr_forward_layers": (_I, [_P, _P, _I, _I, C.POINTER(vdr_layer_out), _I, _P, C.c_size_t, _P]),
     "vdr_forward_attn_maps": (_I, [_P, _P, _I, _I, C.POINTER(vdr_layer_out), _I, C.POINTER(vdr_attn_map), _I, _P, C.c_size_t,
                                    _P]),
+    "vdr_forward_facets": (_I, [_P, _P, _I, _I, C.POINTER(vdr_layer_out), _I, C.POINTER(vdr_attn_map), _I,
+                                C.POINTER(vdr_facet_out), _I, _P, C.c_size_t, _P]),
     "vdr_forward_tokens": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _P, C.c_size_t, _P]),
     "vdr_forward_tokens_varlen": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _I, _P, C.c_size_t, _P]),
     "vdr_op_layernorm": (_I, [_P, _I, _P, _I, _P, _P, _L, _I, _F, _P]),
@@ -109,6 +120,7 @@ SYMBOLS = {
     "vdr_op_rope2d": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "vdr_op_patch_embed": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vdr_op_patch_embed_strided": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "vdr_op_log_bin": (_I, [_P, _I, _L, _L, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "vdr_profile_enable": (_I, [_P, _I]),
     "vdr_profile_mask": (_I, [_P, C.c_uint32]),
     "vdr_profile_read": (_I, [_P, C.POINTER(C.c_double), C.POINTER(_L), C.POINTER(C.c_double),

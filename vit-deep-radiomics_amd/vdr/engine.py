@@ -110,6 +110,51 @@ class AttnMap:
     out: "torch.Tensor | None" = None
 
 
+@dataclass
+class FacetOut:
+    """One facet descriptor of Engine.forward_descriptors (vdr_facet_out): the "key" / "query" / "value" of block `layer`'s
+    attention (the qkv linear's output, before RoPE and scaling) or its "token" (the raw residual stream after the block).
+    hierarchy 0: [B, n, D] patch rows, or [B, N, D] with all_rows; hierarchy 1..3: log-binned, [B, n, (1 + 8*hierarchy)*D]
+    (patch rows only).  out: a caller-owned contiguous tensor of that shape, or None to allocate one of `dtype`."""
+    layer: int
+    facet: "str | int" = "key"
+    hierarchy: int = 0
+    all_rows: bool = False
+    dtype: torch.dtype = torch.float32
+    out: "torch.Tensor | None" = None
+
+
+def facet_code(facet) -> int:
+    """"token" | "query" | "key" | "value" (or the VDR_FACET_* code) -> the code; ValueError for anything else."""
+    if isinstance(facet, str) and facet in L.FACETS:
+        return L.FACETS[facet]
+    if isinstance(facet, int) and not isinstance(facet, bool) and facet in L.FACETS.values():
+        return facet
+    raise ValueError(f"facet must be one of {sorted(L.FACETS)}, got {facet!r}")
+
+
+def check_facet(facet, hierarchy: int, all_rows: bool) -> int:
+    """The refusals of a facet request that need no device (ValueError); returns the facet code."""
+    code = facet_code(facet)
+    if not 0 <= int(hierarchy) <= 3:
+        raise ValueError(f"hierarchy must be 1, 2 or 3 (0: no binning), got {hierarchy}")
+    if hierarchy and all_rows:
+        raise ValueError("a log-binned descriptor takes the patch rows only: bin with include_cls / all_rows is refused")
+    return code
+
+
+def check_descriptor_model(cfg) -> None:
+    """Facet descriptors are for pre-LN image models with blocks (vdr_forward_layers' models): ValueError otherwise."""
+    if cfg.window > 0:
+        raise ValueError("facet descriptors: not for the SAM encoder")
+    if not cfg.patch:
+        raise ValueError("facet descriptors: image models only (token model)")
+    if cfg.layers <= 0:
+        raise ValueError("facet descriptors: the model has no blocks")
+    if not cfg.pre_ln:
+        raise ValueError("facet descriptors: pre-LN models only")
+
+
 def _stream_ptr(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
@@ -330,6 +375,15 @@ class Engine:
         if not maps:
             raise ValueError("forward_attn_maps needs at least one AttnMap")
         arr, feats = self._layer_outs(specs, B) if specs else (None, [])
+        marr, got = self._attn_maps(maps, B)
+        ws = self._workspace(B)
+        L.check(self.lib.vdr_forward_attn_maps(self.h, images.data_ptr(), _DT[images.dtype], B, arr, len(specs), marr, len(maps),
+                                               ws.data_ptr(), ws.numel(), _stream_ptr(self.device)), self.h)
+        return feats, got
+
+    def _attn_maps(self, maps, B):
+        """vdr_attn_map array + the map tensors of forward_attn_maps' maps (allocated or checked)."""
+        N, H = self.n_tokens, self.cfg.heads
         marr = (L.vdr_attn_map * len(maps))()
         got = []
         for k, mp in enumerate(maps):
@@ -352,10 +406,63 @@ class Engine:
             marr[k].layer, marr[k].q_rows, marr[k].head_mean = int(mp.layer), int(mp.q_rows), int(bool(mp.head_mean))
             marr[k].out_dtype, marr[k].out = _DT[out.dtype], out.data_ptr()
             got.append(out)
+        return marr, got
+
+    def _facet_outs(self, facets, B):
+        """vdr_facet_out array + the output tensors of forward_descriptors' facets (allocated or checked)."""
+        n, N, D = self.n_patches, self.n_tokens, self.cfg.dim
+        arr = (L.vdr_facet_out * len(facets))()
+        got = []
+        for k, f in enumerate(facets):
+            code = check_facet(f.facet, f.hierarchy, f.all_rows)
+            if not 0 <= int(f.layer) < self.cfg.layers:
+                raise ValueError(f"facets[{k}]: layer {f.layer} out of range 0..{self.cfg.layers - 1}")
+            h = int(f.hierarchy)
+            shape = (B, n, (1 + 8 * h) * D) if h else (B, N if f.all_rows else n, D)
+            out = f.out
+            if out is None:
+                if f.dtype not in _DT:
+                    raise TypeError(f"facets[{k}]: dtype must be float32 or bfloat16, got {f.dtype}")
+                out = torch.empty(shape, dtype=f.dtype, device=self.device)
+            if out.dtype not in _DT:
+                raise TypeError(f"facets[{k}]: out must be float32 or bfloat16, got {out.dtype}")
+            if out.device != self.device:
+                raise ValueError(f"facets[{k}]: out must live on {self.device}")
+            if tuple(out.shape) != shape:
+                raise ValueError(f"facets[{k}]: out must be {shape}, got {tuple(out.shape)}")
+            if not out.is_contiguous():
+                raise ValueError(f"facets[{k}]: out must be contiguous")
+            arr[k].layer, arr[k].facet, arr[k].hierarchy, arr[k].all_rows = int(f.layer), code, h, int(bool(f.all_rows))
+            arr[k].out_dtype, arr[k].out = _DT[out.dtype], out.data_ptr()
+            got.append(out)
+        return arr, got
+
+    def forward_descriptors(self, images: torch.Tensor, facets, outs=(), maps=()):
+        """One forward that writes facet descriptors (vdr_forward_facets): facets is a sequence of FacetOut, outs / maps
+        optional sequences of LayerOut / AttnMap (forward_layers' and forward_attn_maps' outputs, the same bits).  Returns
+        (facet tensors, feature tensors, map tensors), each in the order given.  A last block whose only requests are
+        key / query / value facets stops after its qkv GEMM.  Caller-owned buffers are checked, never converted or copied;
+        the refusals that need no device (unknown facet, hierarchy outside 0..3, binning with all_rows, SAM / token /
+        post-LN / block-less models) are ValueError."""
+        cfg = self.cfg
+        facets, specs, maps = list(facets), list(outs), list(maps)
+        if not facets:
+            raise ValueError("forward_descriptors needs at least one FacetOut")
+        for f in facets:
+            check_facet(f.facet, f.hierarchy, f.all_rows)
+        check_descriptor_model(cfg)
+        self._check_images(images)
+        if images.dtype not in _DT:
+            images = images.float()
+        images = images.to(self.device).contiguous()
+        B = images.shape[0]
+        farr, fgot = self._facet_outs(facets, B)
+        arr, feats = self._layer_outs(specs, B) if specs else (None, [])
+        marr, mgot = self._attn_maps(maps, B) if maps else (None, [])
         ws = self._workspace(B)
-        L.check(self.lib.vdr_forward_attn_maps(self.h, images.data_ptr(), _DT[images.dtype], B, arr, len(specs), marr, len(maps),
-                                               ws.data_ptr(), ws.numel(), _stream_ptr(self.device)), self.h)
-        return feats, got
+        L.check(self.lib.vdr_forward_facets(self.h, images.data_ptr(), _DT[images.dtype], B, arr, len(specs), marr, len(maps),
+                                            farr, len(facets), ws.data_ptr(), ws.numel(), _stream_ptr(self.device)), self.h)
+        return fgot, feats, mgot
 
     def _layer_outs(self, specs, B):
         """vdr_layer_out array + the output tensors of forward_layers' specs (allocated or checked)."""

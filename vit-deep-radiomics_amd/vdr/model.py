@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .engine import AttnMap, Engine, LayerOut, VdrConfig
+from .engine import AttnMap, Engine, FacetOut, LayerOut, VdrConfig, check_descriptor_model, check_facet
 
 _DINOV3 = dict(layerscale=True, has_pos=False, ln_eps=1e-5, n_register=4, rope=True, rope_theta=100.0)
 
@@ -312,6 +312,39 @@ class VitDescriptorModel:
             res.append(t)
         return res[0] if single else tuple(res)
 
+    def extract_descriptors(self, x: torch.Tensor, layer=None, facet: str = "key", bin: bool = False, include_cls: bool = False,
+                            hierarchy: int = 2, reshape: bool = False) -> torch.Tensor:
+        """dino-vit-features' ViTExtractor.extract_descriptors: the `facet` ("key" | "query" | "value": block `layer`'s qkv
+        linear output, bias included, heads concatenated, before RoPE and before the dh^-0.5 scale; "token": the raw
+        residual stream after the block) of block `layer` (None: the last block) as [B, 1, t, d] fp32.  t = the n patch
+        rows (include_cls: all N rows, prefix rows first), d = D; bin=True log-bins the patch rows on the grid in force
+        (vdr.ops.log_bin at `hierarchy`, 1..3): d = (1 + 8*hierarchy) * D, refused with include_cls as upstream asserts.
+        reshape=True (not with include_cls): [B, gh, gw, d] channel-last, as get_dense_descriptor lays its maps out.
+        One forward (vdr_forward_facets); a key / query / value request of the last block stops after that block's qkv
+        GEMM.  Refusals (ValueError, before any device work): unknown facet, bin with include_cls, hierarchy outside
+        1..3, reshape with include_cls, a layer out of range, SAM / token / post-LN / block-less models."""
+        h = self._descriptor_args(layer, facet, bin, include_cls, hierarchy)
+        if reshape and include_cls:
+            raise ValueError("extract_descriptors: reshape needs include_cls=False (the prefix rows have no grid position)")
+        i = self.cfg.layers - 1 if layer is None else int(layer)
+        self._adopt(x)
+        (got,), _, _ = self.engine.forward_descriptors(x, [FacetOut(i, facet, h, bool(include_cls), torch.float32)])
+        if reshape:
+            gh, gw = self.engine.grid
+            return got.reshape(got.shape[0], gh, gw, got.shape[-1])
+        return got.unsqueeze(1)
+
+    def _descriptor_args(self, layer, facet, bin, include_cls, hierarchy) -> int:
+        """The device-free refusals of a descriptor request; returns the hierarchy to ask for (0 without binning)."""
+        check_descriptor_model(self.cfg)
+        if bin and not 1 <= int(hierarchy) <= 3:
+            raise ValueError(f"hierarchy must be 1, 2 or 3, got {hierarchy}")
+        h = int(hierarchy) if bin else 0
+        check_facet(facet, h, bool(include_cls))
+        if layer is not None and not 0 <= int(layer) < self.cfg.layers:
+            raise ValueError(f"layer {layer} out of range 0..{self.cfg.layers - 1}")
+        return h
+
     def get_image_features(self, x: torch.Tensor, normalize: bool = False) -> torch.Tensor:
         """The image embedding of a CLIP / SigLIP vision tower, [B, E] fp32 (transformers get_image_features):
         CLIP: visual_projection(post_layernorm(x[:, 0])) -- CLIPVisionModelWithProjection's image_embeds;
@@ -457,15 +490,22 @@ def load_model(model_name: str, model_path=None, weights=None, device=None, micr
     return model
 
 
-def get_dense_descriptor(model, img) -> np.ndarray:
+def get_dense_descriptor(model, img, layer=None, facet=None, bin: bool = False, hierarchy: int = 2) -> np.ndarray:
     """R2: the reference's function (tfds_dense_descriptor.py:110-139), same argument, same result layout.
     img: the RAW slice exactly as the reference passes it -- (h, w) gray or (h, w, 3) colour, values in [0, 1]; it is
     prepared here as `prepare_image` does (tfds_dense_descriptor.py:30-48: gray2rgb + resize to 1024^2 for gray,
     resize to 896^2 for colour, CHW, float32, on the device: vdr.prep.prepare_image) and run through
     `model.image_encoder` ('medsam') or `model.patch_embed` (anything else), returning (h, w, D) float32 numpy.
     Also accepted, for callers that prepared the image themselves: a (3, S, S) or (1, 3, S, S) array / tensor with S
-    the model's input side (taken as it is)."""
+    the model's input side (taken as it is).
+    facet ("key" | "query" | "value" | "token"; None: the reference's path above, untouched): the map is
+    model.extract_descriptors(t, layer, facet, bin, hierarchy=hierarchy, reshape=True) instead -- (h, w, D), or
+    (h, w, (1 + 8*hierarchy)*D) with bin=True."""
     from . import prep
+    if facet is not None:
+        model._descriptor_args(layer, facet, bin, False, hierarchy)  # (refusals before any device work)
+    elif layer is not None or bin:
+        raise ValueError("get_dense_descriptor: layer / bin need a facet")
     t = torch.as_tensor(img)
     side = model.cfg.img
     prepared = t.dim() == 4 or (t.dim() == 3 and t.shape[0] == 3 and tuple(t.shape[1:]) == (side, side))
@@ -484,6 +524,8 @@ def get_dense_descriptor(model, img) -> np.ndarray:
             raise ValueError(f"prepare_image gives a {t.shape[-1]}^2 image for a {'gray' if torch.as_tensor(img).dim() == 2 else 'colour'} "
                              f"slice, model '{model.model_name}' takes {side}^2 (the reference pairs gray slices with "
                              "'medsam' and colour slices with 'dinov2')")
+    if facet is not None:
+        return model.extract_descriptors(t, layer, facet, bin, False, hierarchy, reshape=True)[0].cpu().numpy()
     if model.model_name == "medsam":
         f = model.image_encoder(t).cpu().numpy()
         return np.transpose(np.squeeze(f), (1, 2, 0))
@@ -492,9 +534,15 @@ def get_dense_descriptor(model, img) -> np.ndarray:
     return f.reshape(gh, gw, f.shape[-1])
 
 
-def extract_dense(model, images: torch.Tensor, encoder: bool = True) -> np.ndarray:
+def extract_dense(model, images: torch.Tensor, encoder: bool = True, layer=None, facet=None, bin: bool = False,
+                  hierarchy: int = 2) -> np.ndarray:
     """Batched counterpart of the reference's per-slice loop (tfds_dense_descriptor.py:271-281):
-    [B,3,H,W] -> (B, h, w, D) float32 numpy in one call."""
+    [B,3,H,W] -> (B, h, w, D) float32 numpy in one call.  facet (None: that path, untouched): the facet descriptors of
+    VitDescriptorModel.extract_descriptors(..., reshape=True) instead, (B, h, w, d)."""
+    if facet is not None:
+        return model.extract_descriptors(images, layer, facet, bin, False, hierarchy, reshape=True).cpu().numpy()
+    if layer is not None or bin:
+        raise ValueError("extract_dense: layer / bin need a facet")
     model._adopt(images)
     gh, gw = model.engine.grid
     f = model.engine.forward(images, L.OUT_DENSE if encoder else L.OUT_PATCH_EMBED, torch.float32)

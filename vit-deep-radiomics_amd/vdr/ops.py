@@ -238,6 +238,41 @@ def attention_probs(qkv: torch.Tensor, batch: int, seq: int, heads: int, head_di
     return out
 
 
+def log_bin(x: torch.Tensor, gh: int, gw: int, hierarchy: int = 2, out_dtype=torch.float32, out=None) -> torch.Tensor:
+    """Log-binning of a dense descriptor map (vdr_op_log_bin): x [B, gh*gw, C] bf16 or fp32 -- contiguous, or a view whose
+    last dimension is contiguous, such as the key columns and patch rows buf[:, P:, C:2*C] of a [B, P + n, 3C] qkv
+    activation, read in place -- -> [B, gh*gw, (1 + 8*hierarchy)*C]: per patch its own descriptor, its 8 neighbours, and
+    for k = 1 .. hierarchy-1 the 8 neighbours at 3^k spacing of the 3^k x 3^k window means (edges clamped, windows cut to
+    the grid).  fp32 sums, one IEEE division, one rounding to out_dtype; level-0 bins are copies."""
+    lib = L.load()
+    if not (x.is_cuda and x.dim() == 3 and x.dtype in (torch.float32, torch.bfloat16)):
+        raise TypeError("log_bin: x must be a [B, gh*gw, C] float32 or bfloat16 tensor on the HIP device")
+    B, n, Cc = x.shape
+    if n != int(gh) * int(gw):
+        raise ValueError(f"log_bin: x has {n} rows, the grid {gh} x {gw}")
+    if Cc > 1 and x.stride(2) != 1:
+        raise ValueError("log_bin: the channels of x must be contiguous")
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"out_dtype must be float32 or bfloat16, got {out_dtype}")
+    h = int(hierarchy)
+    if not 1 <= h <= 3:
+        raise ValueError(f"log_bin: hierarchy must be 1, 2 or 3, got {hierarchy}")
+    ld = x.stride(1) if n > 1 else Cc
+    image_stride = x.stride(0) if B > 1 else n * ld
+    bins = 1 + 8 * h
+    shape = (B, n, bins * Cc)
+    if out is None:
+        out = torch.empty(shape, dtype=out_dtype, device=x.device)
+    elif out.dtype not in (torch.float32, torch.bfloat16) or out.device != x.device or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"log_bin: out must be a contiguous float32 or bfloat16 tensor of shape {shape} on {x.device}, got "
+                         f"{out.dtype} {tuple(out.shape)} on {out.device}")
+    work = torch.empty((max(h - 1, 0) * B * n * Cc,), dtype=torch.float32, device=x.device) if h > 1 else None
+    L.check(lib.vdr_op_log_bin(x.data_ptr(), L.VDR_BF16 if x.dtype == torch.bfloat16 else L.VDR_F32, ld, image_stride, B, int(gh),
+                               int(gw), Cc, h, _p(work), out.data_ptr(), L.VDR_BF16 if out.dtype == torch.bfloat16 else L.VDR_F32,
+                               _s(x)))
+    return out
+
+
 def patch_embed(images, weight, bias, p, pos=None, row_stride=None, row_offset=0, out=None):
     """images [B,C,H,H] fp32/bf16; weight [D,C,p,p] (any float dtype); returns bf16 [B*row_stride, D]."""
     lib = L.load()

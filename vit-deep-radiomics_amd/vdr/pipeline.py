@@ -76,7 +76,7 @@ def crop_maps(maps: torch.Tensor, box) -> torch.Tensor:
 
 
 # ---- tfds_dense_descriptor.py:242-284 -----------------------------------------------------------------------
-def generate_features(model, img_3d, mask_3d, flip=None, max_batch=16):
+def generate_features(model, img_3d, mask_3d, flip=None, max_batch=16, descriptor=None):
     """Feature map of every slice, cropped to the nodule region.
 
     img_3d  (H, W, S) CT/PET volume in [0, 1] ('medsam') or (H, W, S, 3) ('dinov2'); mask_3d (H, W, S) bool.
@@ -88,7 +88,19 @@ def generate_features(model, img_3d, mask_3d, flip=None, max_batch=16):
     `generate_features(model, *flip_image(img_3d, mask_3d, flip))` (tfds_dense_descriptor.py:463-467): the mask is
     flipped first, every box (volume crop, ROI of the feature maps, ROI of the masks -- asymmetric margins and all) is
     derived from the FLIPPED mask, and the pixels are read from the mirrored window of the unflipped volume with the
-    reversal folded into the resize gather (no flipped copy of the volume is made)."""
+    reversal folded into the resize gather (no flipped copy of the volume is made).
+
+    descriptor (None: the reference's maps, as above): a dict of VitDescriptorModel.extract_descriptors' keywords --
+    layer, facet, bin, hierarchy -- for facet descriptors instead (ViT / DINOv2 / CLIP models): the per-slice maps are
+    (h', w', d) with d = D, or (1 + 8*hierarchy)*D with bin=True; the ROI crop works on that channel count."""
+    desc = None
+    if descriptor is not None:
+        unknown = set(descriptor) - {"layer", "facet", "bin", "hierarchy"}
+        if unknown:
+            raise ValueError(f"descriptor: unknown keys {sorted(unknown)} (layer, facet, bin, hierarchy)")
+        desc = {"layer": descriptor.get("layer"), "facet": descriptor.get("facet", "key"), "bin": bool(descriptor.get("bin", False)),
+                "hierarchy": int(descriptor.get("hierarchy", 2))}
+        model._descriptor_args(desc["layer"], desc["facet"], desc["bin"], False, desc["hierarchy"])  # (before any device work)
     if flip not in (None, "horizontal", "vertical"):
         raise ValueError(f"flip must be None, 'horizontal' or 'vertical', got {flip!r}")
     mask_np = mask_3d.cpu().numpy() if isinstance(mask_3d, torch.Tensor) else np.asarray(mask_3d)
@@ -126,7 +138,9 @@ def generate_features(model, img_3d, mask_3d, flip=None, max_batch=16):
         # for bit); written as bf16 here they are half the bytes, and for p = 16 (MedSAM) the GEMM gathers them straight
         # from the images (no im2col pass)
         x = prep.prepare_slices(vol[:, :, s0:s1], side=model.cfg.img, flip=flip, out_dtype=torch.bfloat16, device=model.device)
-        if medsam:
+        if desc is not None:
+            maps = model.extract_descriptors(x, reshape=True, **desc)             # [b, gh, gw, d] channel-last
+        elif medsam:
             maps = model.engine.forward(x, L.OUT_ENCODER, torch.float32)          # [b, g, g, C] channel-last
         else:
             gh, gw = model.engine.grid  # (img / patch a side by default; finer after set_patch_stride)
