@@ -732,6 +732,31 @@ int vdr_op_patch_embed_strided(const void* images, int in_dtype, const void* W, 
  * hierarchy outside 1..3. */
 int vdr_op_log_bin(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int batch, int gh, int gw, int C,
                    int hierarchy, float* work, void* out, int out_dtype, void* stream);
+
+/* Cosine nearest neighbours between two descriptor maps (csrc/nn_cosine.hip): for each of `pairs` problems, every row of
+ * X_p against every row of Y_p, without the tx x ty similarity matrix ever being written.
+ *   X_p = [tx, d] bf16, rows ldx elements apart, starting at x + p * x_stride; Y_p = [ty, d] bf16 with ldy and y_stride
+ *   likewise.  A stride of 0 is allowed (one map matched against many).
+ * Definition:
+ *   ss(v)     = sum_c v_c^2 in fp32 (products of bf16 values are exact in fp32; fixed summation order, no atomics);
+ *   rn(v)     = 1.0f / fmaxf(sqrtf(ss(v)), 1e-8f), correctly rounded sqrtf and division;
+ *   sim(i, j) = (dot(x_i, y_j) * rn(x_i)) * rn(y_j), in this association; dot is accumulated in fp32 by bf16 MFMAs;
+ *   row_sim[p, i] = max_j sim(i, j), row_idx[p, i] the lowest j that attains it        ([pairs, tx] fp32 / int32);
+ *   col_sim[p, j] = max_i sim(i, j), col_idx[p, j] the lowest i that attains it        ([pairs, ty] fp32 / int32).
+ * Comparisons are > on the value, then < on the index.  Inputs are finite by contract; a zero row has sim = 0 against
+ * everything.  Results are bitwise reproducible from run to run, and a pair's result does not depend on `pairs` or on its
+ * position in the batch.
+ * col_sim == NULL && col_idx == NULL skips the column side.  work: vdr_nn_cosine_work_bytes(pairs, tx, ty) bytes of device
+ * scratch (row norms and the partial maxima), 16-byte aligned.
+ * Refused before the device is touched: VDR_ERR_UNSUPPORTED for d % 32 != 0; VDR_ERR_INVALID for a null x, y, work, row_sim
+ * or row_idx, exactly one of col_sim / col_idx null, non-positive pairs, tx, ty or d, ldx < d or ldy < d, negative
+ * strides, pointers or strides (ldx, ldy, x_stride, y_stride) that are not 16-byte aligned, pairs * max(tx, ty) above
+ * 2^31 - 1. */
+size_t vdr_nn_cosine_work_bytes(int pairs, int tx, int ty);
+int vdr_op_nn_cosine(const void* x, int64_t ldx, int64_t x_stride, int tx,
+                     const void* y, int64_t ldy, int64_t y_stride, int ty,
+                     int pairs, int d, void* work,
+                     float* row_sim, int32_t* row_idx, float* col_sim, int32_t* col_idx, void* stream);
 /* ---- measurement ------------------------------------------------------------------------ */
 
 /* Kernel classes timed by the built-in HIP-event profiler. */

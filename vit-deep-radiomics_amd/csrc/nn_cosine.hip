@@ -1,0 +1,421 @@
+// Cosine nearest neighbours between two descriptor maps for gfx950 (include/vdr.h, vdr_op_nn_cosine): for `pairs`
+// problems X_p [tx, d], Y_p [ty, d] (bf16 rows ldx / ldy elements apart, pairs x_stride / y_stride apart, 0 allowed)
+//   sim(i, j)  = (dot(x_i, y_j) * rn(x_i)) * rn(y_j),   rn(v) = 1 / max(sqrt(sum v^2), 1e-8)
+//   row_sim[i] = max_j sim(i, j), row_idx[i] the lowest j that attains it; col_sim / col_idx likewise over i.
+// The tx x ty similarity matrix is never written: it exists one 128 x 128 tile at a time in MFMA accumulators.
+//
+// Three launches, no atomics:
+//   nn_rnorm_kernel    rn of every row of X and Y into `work`: one wave per row, 16-byte loads, each lane sums its chunks in
+//                      chunk order, then a fixed xor butterfly.  sqrt and the division are the IEEE ones.
+//   nn_cosine_kernel   256 threads; one work item = (pair, split of Y's tiles, 128-row panel of X).  It walks its 128-row
+//                      tiles of Y; per tile a K loop over d in steps of 64 stages both operands global -> LDS (LDS-DMA,
+//                      two buffers: step s + 1 is in flight under the MFMAs of step s).  Wave (wr, wc) owns the 64 x 64
+//                      sub-tile at (64 wr, 64 wc) as 2 x 2 mfma_f32_32x32x16_bf16 accumulators: X is the A operand, Y the
+//                      B operand, so a lane holds ONE column j (l & 31) and 16 rows i ((e & 3) + 8 (e >> 2) + 4 (l >> 5)).
+//                      Epilogue per tile, in that layout: scale, mask the ragged rows / columns with -inf, fold every
+//                      element into the lane's running row best (kept across the tiles), reduce the tile's column best
+//                      over registers, lane halves and the two row waves (LDS), write it as a partial (value, index).
+//                      At the end of the item the row best is reduced over the 32 lanes and the two column waves and
+//                      written as a partial too.
+//   nn_finish_kernel   folds the row partials over the splits and the column partials over the panels, ascending.
+// Every fold uses one comparison -- greater value, then lower index -- which is a total order on (value, index) pairs
+// with distinct indices: the result is the same whatever the grouping, so it depends neither on the split count (a
+// launch heuristic) nor on `pairs`.  dot is the MFMA's fp32 accumulation in k order; both are fixed.
+//
+// LDS image of a staged operand tile: [128 rows][64 bf16] = 128-B rows, 16-B chunk c of row r at slot c ^ ((r >> 1) & 7)
+// (the K image of attention_tile.h: conflict-free ds_read_b128 fragment reads).  The DMA writes linearly, so the swizzle
+// is applied to the per-lane SOURCE address.  Rows past the end of a map repeat its last row (finite values, masked in the
+// epilogue).  d % 64 == 32: the last step runs 2 of its 4 MFMA k-steps; its unused chunks re-read chunks 0..3 (nothing
+// past the end of a row is touched).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "vdr_dev.h"
+#include "vdr_kernels.h"
+
+namespace vdr {
+namespace {
+
+constexpr int NN_T = 128;                   // tile side (rows of X per panel, rows of Y per tile)
+constexpr int NN_OPER = NN_T * 128;         // bytes of one staged operand tile
+constexpr int NN_RN = 4 * NN_OPER;          // s_rn [2][256] float: tile parity x (rn of the tile's Y rows | of the panel's X rows)
+constexpr int NN_COL = NN_RN + 2048;        // column exchange: value [128], index [128]
+constexpr int NN_ROW = NN_COL + 1024;       // row exchange: value [2][128], index [2][128]
+constexpr int NN_LDS = NN_ROW + 2048;
+constexpr int NN_TARGET_ITEMS = 512;        // work items the split of Y's tiles aims for (two workgroups per CU)
+
+struct NnArgs {
+  const bf16_t *x, *y;
+  int64_t ldx, xs, ldy, ys;
+  int tx, ty, d, npanels, ntiles, nsplit, tx_pad, ty_pad, do_cols;
+  int split_base, split_rem;  // tiles per split: ntiles / nsplit, and the first ntiles % nsplit splits take one more
+  float *rnx, *rny;      // [pairs][tx_pad], [pairs][ty_pad]
+  float* colv;           // [pairs][npanels][ty_pad]
+  int32_t* coli;
+  float* rowv;           // [pairs][nsplit][tx_pad]
+  int32_t* rowi;
+};
+
+VDR_DEV bool nn_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+__global__ __launch_bounds__(256) void nn_rnorm_kernel(NnArgs a, int pairs) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t nx = (int64_t)pairs * a.tx, ny = (int64_t)pairs * a.ty;
+  if (row >= nx + ny) return;
+  const bool is_x = row < nx;
+  const int64_t r = is_x ? row : row - nx;
+  const int t = is_x ? a.tx : a.ty;
+  const int64_t p = r / t;
+  const int i = (int)(r - p * t);
+  const bf16_t* src = is_x ? a.x + p * a.xs + (int64_t)i * a.ldx : a.y + p * a.ys + (int64_t)i * a.ldy;
+  float ss = 0.0f;
+  for (int c = lane * 8; c < a.d; c += 512) {
+    const bf16x8 v = *reinterpret_cast<const bf16x8*>(src + c);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float f = (float)v[e];
+      ss += f * f;
+    }
+  }
+  ss = wave_sum(ss);
+  if (lane == 0) {
+    const float rn = __fdiv_rn(1.0f, fmaxf(__fsqrt_rn(ss), 1e-8f));
+    if (is_x) a.rnx[p * a.tx_pad + i] = rn; else a.rny[p * a.ty_pad + i] = rn;
+  }
+}
+
+// the staged step has landed, for every wave: the DMAs are opaque to hipcc, so the wait is spelled out
+VDR_DEV void nn_wait() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+}
+
+// one K step of (panel, tile jt) into staging buffer `buf`: 4 + 4 DMA instructions per wave, 8 rows x 128 B each
+VDR_DEV void nn_stage(const NnArgs& a, const bf16_t* xp, const bf16_t* yp, int64_t p, int panel, int jt, int kk, char* smem,
+                      int buf, int wave, int lane) {
+  const int k0 = kk * 64;
+  const bool shortk = a.d - k0 < 64;
+  char* sx = smem + buf * 2 * NN_OPER;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int piece = wave * 4 + q;
+    const int r = piece * 8 + (lane >> 3);
+    int c = (lane & 7) ^ ((r >> 1) & 7);
+    c = shortk ? c & 3 : c;
+    const int xr = min(panel * NN_T + r, a.tx - 1), yr = min(jt * NN_T + r, a.ty - 1);
+    glds16_raw(xp + (int64_t)xr * a.ldx + k0 + c * 8, sx + piece * 1024);
+    glds16_raw(yp + (int64_t)yr * a.ldy + k0 + c * 8, sx + NN_OPER + piece * 1024);
+  }
+  if (kk == 0 && wave == 0) {  // the tile's rn values ride on the same wait: lanes 0..31 Y's, 32..63 the panel's
+    const float* src = lane < 32 ? a.rny + p * a.ty_pad + jt * NN_T + lane * 4 : a.rnx + p * a.tx_pad + panel * NN_T + (lane - 32) * 4;
+    glds16_raw(src, smem + NN_RN + (jt & 1) * 1024);
+  }
+}
+
+template <int KS0, int KS1>
+VDR_DEV void nn_mfma(const char* sx, int wr, int wc, int l31, int hh, f32x16 (&acc)[2][2]) {
+  const int swz = (l31 >> 1) & 7;
+#pragma unroll
+  for (int ks = KS0; ks < KS1; ++ks) {
+    const int off = ((2 * ks + hh) ^ swz) * 16;
+    bf16x8 af[2], bf[2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m) af[m] = *reinterpret_cast<const bf16x8*>(sx + (wr * 64 + m * 32 + l31) * 128 + off);
+#pragma unroll
+    for (int n = 0; n < 2; ++n) bf[n] = *reinterpret_cast<const bf16x8*>(sx + NN_OPER + (wc * 64 + n * 32 + l31) * 128 + off);
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[m], bf[n], acc[m][n], 0, 0, 0);
+  }
+}
+
+__global__ __launch_bounds__(256, 2) void nn_cosine_kernel(NnArgs a) {
+  extern __shared__ __attribute__((aligned(1024))) char smem[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l31 = lane & 31, hh = lane >> 5;
+  const int wr = wave >> 1, wc = wave & 1;
+  // (pair, split, panel), panel fastest, in XCD-contiguous order: the panels that read the same tiles of Y_p run next to
+  // each other on one XCD and meet in its L2
+  const int vid = xcd_remap(blockIdx.x, gridDim.x);
+  const int ps = vid / a.npanels, panel = vid - ps * a.npanels;
+  const int p = ps / a.nsplit, split = ps - p * a.nsplit;
+  const int jt0 = split * a.split_base + min(split, a.split_rem), jt1 = jt0 + a.split_base + (split < a.split_rem);
+  const bf16_t* xp = a.x + (int64_t)p * a.xs;
+  const bf16_t* yp = a.y + (int64_t)p * a.ys;
+  const int nk = (a.d + 63) >> 6;
+
+  float rbv[2][16];
+  int rbi[2][16];
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      rbv[m][e] = -INFINITY;
+      rbi[m][e] = INT32_MAX;
+    }
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[m][n][e] = 0.0f;
+  }
+  float* s_rn = reinterpret_cast<float*>(smem + NN_RN);
+  float* s_colv = reinterpret_cast<float*>(smem + NN_COL);
+  int* s_coli = reinterpret_cast<int*>(smem + NN_COL + 512);
+  float* s_rowv = reinterpret_cast<float*>(smem + NN_ROW);
+  int* s_rowi = reinterpret_cast<int*>(smem + NN_ROW + 1024);
+
+  // One loop over the K steps of all tiles, step s + 1 staged under the MFMAs of step s (pass s = -1 only stages step 0):
+  // the step after a tile's last one is the first of the next tile.  (jt, kk) is the step in the MFMAs, (njt, nkk) the
+  // one being staged; it goes into the other buffer, which every wave finished reading before the barrier that ended
+  // the previous pass.
+  const int nsteps = (jt1 - jt0) * nk;
+  int jt = jt0, kk = -1, buf = 1;
+#pragma clang loop unroll(disable)
+  for (int s = -1; s < nsteps; ++s) {
+    int njt = jt, nkk = kk + 1;
+    if (nkk == nk) {
+      nkk = 0;
+      ++njt;
+    }
+    if (s + 1 < nsteps) nn_stage(a, xp, yp, p, panel, njt, nkk, smem, buf ^ 1, wave, lane);
+    if (s >= 0) {
+      const char* sx = smem + buf * 2 * NN_OPER;
+      nn_mfma<0, 2>(sx, wr, wc, l31, hh, acc);
+      if (a.d - kk * 64 >= 64) nn_mfma<2, 4>(sx, wr, wc, l31, hh, acc);
+      if (kk + 1 == nk) {
+        // ---- epilogue of tile jt
+        const float* rn = s_rn + (jt & 1) * 256;
+        float rny[2], cbv[2];
+        int gcol[2], cbi[2];
+        bool cok[2];
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+          rny[n] = rn[wc * 64 + n * 32 + l31];
+          gcol[n] = jt * NN_T + wc * 64 + n * 32 + l31;
+          cok[n] = gcol[n] < a.ty;
+          cbv[n] = -INFINITY;
+          cbi[n] = INT32_MAX;
+        }
+        // rows of the panel this lane may count, as (constant < per-lane threshold) with the threshold made opaque here:
+        // written as `grow < tx` the 32 lane masks are loop invariants that hipcc keeps in SGPR pairs and spills (mask_keys)
+        int rthr = a.tx - panel * NN_T - wr * 64 - 4 * hh;
+        asm volatile("" : "+v"(rthr));
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const int rloc = wr * 64 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+            const int grow = panel * NN_T + rloc;
+            const bool rok = m * 32 + (e & 3) + 8 * (e >> 2) < rthr;
+            const float rnx = rn[128 + rloc];
+#pragma unroll
+            for (int n = 0; n < 2; ++n) {
+              const float v = (acc[m][n][e] * rnx) * rny[n];
+              acc[m][n][e] = 0.0f;
+              // (ascending j within the lane, ascending i within the column: a strict > keeps the lowest index)
+              const float vr = cok[n] ? v : -INFINITY;
+              if (vr > rbv[m][e]) {
+                rbv[m][e] = vr;
+                rbi[m][e] = gcol[n];
+              }
+              const float vc = rok ? v : -INFINITY;
+              if (vc > cbv[n]) {
+                cbv[n] = vc;
+                cbi[n] = grow;
+              }
+            }
+          }
+        if (a.do_cols) {
+#pragma unroll
+          for (int n = 0; n < 2; ++n) {
+            const float ov = __shfl_xor(cbv[n], 32, 64);
+            const int oi = __shfl_xor(cbi[n], 32, 64);
+            if (nn_better(ov, oi, cbv[n], cbi[n])) {
+              cbv[n] = ov;
+              cbi[n] = oi;
+            }
+            if (wr == 1 && hh == 0) {
+              s_colv[wc * 64 + n * 32 + l31] = cbv[n];
+              s_coli[wc * 64 + n * 32 + l31] = cbi[n];
+            }
+          }
+          __syncthreads();
+          if (wr == 0 && hh == 0) {
+            const int64_t base = ((int64_t)p * a.npanels + panel) * a.ty_pad;
+#pragma unroll
+            for (int n = 0; n < 2; ++n) {
+              const float ov = s_colv[wc * 64 + n * 32 + l31];
+              const int oi = s_coli[wc * 64 + n * 32 + l31];
+              if (nn_better(ov, oi, cbv[n], cbi[n])) {
+                cbv[n] = ov;
+                cbi[n] = oi;
+              }
+              if (cok[n]) {
+                a.colv[base + gcol[n]] = cbv[n];
+                a.coli[base + gcol[n]] = cbi[n];
+              }
+            }
+          }
+        }
+      }
+    }
+    nn_wait();
+    buf ^= 1;
+    jt = njt;
+    kk = nkk;
+  }
+  // ---- row best of the item: over the 32 lanes of a half wave, then over the two column waves
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      float v = rbv[m][e];
+      int i = rbi[m][e];
+#pragma unroll
+      for (int o = 1; o < 32; o <<= 1) {
+        const float ov = __shfl_xor(v, o, 64);
+        const int oi = __shfl_xor(i, o, 64);
+        if (nn_better(ov, oi, v, i)) {
+          v = ov;
+          i = oi;
+        }
+      }
+      if (l31 == 0) {
+        const int rloc = wr * 64 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+        s_rowv[wc * 128 + rloc] = v;
+        s_rowi[wc * 128 + rloc] = i;
+      }
+    }
+  __syncthreads();
+  if (threadIdx.x < 128) {
+    const int t = threadIdx.x;
+    float v = s_rowv[t];
+    int i = s_rowi[t];
+    if (nn_better(s_rowv[128 + t], s_rowi[128 + t], v, i)) {
+      v = s_rowv[128 + t];
+      i = s_rowi[128 + t];
+    }
+    // (rows past tx land in the padding of the partial and are never read)
+    const int64_t o = ((int64_t)p * a.nsplit + split) * a.tx_pad + panel * NN_T + t;
+    a.rowv[o] = v;
+    a.rowi[o] = i;
+  }
+}
+
+__global__ __launch_bounds__(256) void nn_finish_kernel(NnArgs a, int pairs, float* row_sim, int32_t* row_idx, float* col_sim,
+                                                        int32_t* col_idx) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t nx = (int64_t)pairs * a.tx, ny = a.do_cols ? (int64_t)pairs * a.ty : 0;
+  if (idx < nx) {
+    const int64_t p = idx / a.tx;
+    const int i = (int)(idx - p * a.tx);
+    const float* pv = a.rowv + p * a.nsplit * a.tx_pad + i;
+    const int32_t* pi = a.rowi + p * a.nsplit * a.tx_pad + i;
+    float v = pv[0];
+    int b = pi[0];
+    for (int s = 1; s < a.nsplit; ++s) {
+      const float ov = pv[(int64_t)s * a.tx_pad];
+      const int oi = pi[(int64_t)s * a.tx_pad];
+      if (nn_better(ov, oi, v, b)) {
+        v = ov;
+        b = oi;
+      }
+    }
+    row_sim[idx] = v;
+    row_idx[idx] = b;
+  } else if (idx - nx < ny) {
+    const int64_t c = idx - nx, p = c / a.ty;
+    const int j = (int)(c - p * a.ty);
+    const float* pv = a.colv + p * a.npanels * a.ty_pad + j;
+    const int32_t* pi = a.coli + p * a.npanels * a.ty_pad + j;
+    float v = pv[0];
+    int b = pi[0];
+    for (int s = 1; s < a.npanels; ++s) {
+      const float ov = pv[(int64_t)s * a.ty_pad];
+      const int oi = pi[(int64_t)s * a.ty_pad];
+      if (nn_better(ov, oi, v, b)) {
+        v = ov;
+        b = oi;
+      }
+    }
+    col_sim[c] = v;
+    col_idx[c] = b;
+  }
+}
+
+// the sections of `work`, in 4-byte elements; each a multiple of 128 elements, so every section starts 16-byte aligned
+struct NnLayout {
+  int64_t npanels, ntiles, tx_pad, ty_pad, rn_x, rn_y, col, row;
+};
+NnLayout nn_layout(int pairs, int tx, int ty) {
+  NnLayout l;
+  l.npanels = (tx + NN_T - 1) / NN_T;
+  l.ntiles = (ty + NN_T - 1) / NN_T;
+  l.tx_pad = l.npanels * NN_T;
+  l.ty_pad = l.ntiles * NN_T;
+  l.rn_x = (int64_t)pairs * l.tx_pad;
+  l.rn_y = (int64_t)pairs * l.ty_pad;
+  l.col = (int64_t)pairs * l.npanels * l.ty_pad;
+  // pairs * nsplit * tx_pad with nsplit <= max(1, NN_TARGET_ITEMS / (pairs * npanels)): never more than this, and monotone
+  const int64_t items = (int64_t)pairs * l.npanels;
+  l.row = (items > NN_TARGET_ITEMS ? items : NN_TARGET_ITEMS) * NN_T;
+  return l;
+}
+
+}  // namespace
+
+size_t nn_cosine_work_bytes(int pairs, int tx, int ty) {
+  if (pairs <= 0 || tx <= 0 || ty <= 0) return 0;
+  const NnLayout l = nn_layout(pairs, tx, ty);
+  return (size_t)(l.rn_x + l.rn_y + 2 * l.col + 2 * l.row) * 4;
+}
+
+hipError_t launch_nn_cosine(const void* x, int64_t ldx, int64_t x_stride, int tx, const void* y, int64_t ldy, int64_t y_stride,
+                            int ty, int pairs, int d, void* work, float* row_sim, int32_t* row_idx, float* col_sim,
+                            int32_t* col_idx, hipStream_t st) {
+  if (!x || !y || !work || !row_sim || !row_idx || (!col_sim) != (!col_idx) || pairs <= 0 || tx <= 0 || ty <= 0 || d <= 0 ||
+      (d & 31) || ldx < d || ldy < d || x_stride < 0 || y_stride < 0)
+    return hipErrorInvalidValue;
+  if ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)work) & 15) || ((ldx | ldy | x_stride | y_stride) & 7)) return hipErrorInvalidValue;
+  if ((int64_t)pairs * (tx > ty ? tx : ty) > INT32_MAX) return hipErrorInvalidValue;
+  const NnLayout l = nn_layout(pairs, tx, ty);
+  NnArgs a;
+  a.x = (const bf16_t*)x;
+  a.y = (const bf16_t*)y;
+  a.ldx = ldx, a.xs = x_stride, a.ldy = ldy, a.ys = y_stride;
+  a.tx = tx, a.ty = ty, a.d = d;
+  a.npanels = (int)l.npanels, a.ntiles = (int)l.ntiles, a.tx_pad = (int)l.tx_pad, a.ty_pad = (int)l.ty_pad;
+  const int64_t items = (int64_t)pairs * l.npanels;
+  int64_t nsplit = NN_TARGET_ITEMS / items;
+  nsplit = nsplit < 1 ? 1 : nsplit > l.ntiles ? l.ntiles : nsplit;
+  a.nsplit = (int)nsplit;
+  a.split_base = (int)(l.ntiles / nsplit), a.split_rem = (int)(l.ntiles % nsplit);
+  a.do_cols = col_sim != nullptr;
+  float* w = (float*)work;
+  a.rnx = w;
+  a.rny = a.rnx + l.rn_x;
+  a.colv = a.rny + l.rn_y;
+  a.coli = (int32_t*)(a.colv + l.col);
+  a.rowv = (float*)(a.coli + l.col);
+  a.rowi = (int32_t*)(a.rowv + l.row);
+  if (items * nsplit > INT32_MAX) return hipErrorInvalidValue;
+
+  static KernelState ks;
+  const int dev = current_device_index();
+  if (dev < 0) return hipErrorInvalidDevice;
+  if (hipError_t e = raise_lds_limit(ks, (const void*)nn_cosine_kernel, dev, NN_LDS)) return e;
+  const int64_t rows = (int64_t)pairs * tx + (int64_t)pairs * ty;
+  hipLaunchKernelGGL(nn_rnorm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, a, pairs);
+  if (hipError_t e = hipGetLastError()) return e;
+  hipLaunchKernelGGL(nn_cosine_kernel, dim3((unsigned)(items * nsplit)), dim3(256), NN_LDS, st, a);
+  if (hipError_t e = hipGetLastError()) return e;
+  const int64_t outs = (int64_t)pairs * tx + (a.do_cols ? (int64_t)pairs * ty : 0);
+  hipLaunchKernelGGL(nn_finish_kernel, dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, st, a, pairs, row_sim, row_idx, col_sim,
+                     col_idx);
+  return hipGetLastError();
+}
+
+}  // namespace vdr

@@ -2697,6 +2697,25 @@ int vdr_op_log_bin(const void* x, int in_dtype, int64_t ld, int64_t image_stride
          "log_bin");
 }
 
+size_t vdr_nn_cosine_work_bytes(int pairs, int tx, int ty) { return nn_cosine_work_bytes(pairs, tx, ty); }
+
+int vdr_op_nn_cosine(const void* x, int64_t ldx, int64_t x_stride, int tx, const void* y, int64_t ldy, int64_t y_stride, int ty,
+                     int pairs, int d, void* work, float* row_sim, int32_t* row_idx, float* col_sim, int32_t* col_idx,
+                     void* stream) {
+  if (!x || !y || !work || !row_sim || !row_idx) return fail(nullptr, VDR_ERR_INVALID, "nn_cosine: null x, y, work, row_sim or row_idx");
+  if (!col_sim != !col_idx) return fail(nullptr, VDR_ERR_INVALID, "nn_cosine: col_sim and col_idx must both be given or both be null");
+  if (pairs <= 0 || tx <= 0 || ty <= 0 || d <= 0) return fail(nullptr, VDR_ERR_INVALID, "nn_cosine: pairs, tx, ty and d must be positive");
+  if (d % 32 != 0) return fail(nullptr, VDR_ERR_UNSUPPORTED, "nn_cosine: d must be a multiple of 32");
+  if (ldx < d || ldy < d || x_stride < 0 || y_stride < 0)
+    return fail(nullptr, VDR_ERR_INVALID, "nn_cosine: ldx and ldy must be >= d, the pair strides >= 0");
+  if (!aligned16({x, y, work, row_sim, row_idx, col_sim, col_idx}) || ldx % 8 || ldy % 8 || x_stride % 8 || y_stride % 8)
+    return fail(nullptr, VDR_ERR_INVALID, "nn_cosine: pointers, rows (ldx, ldy) and pair strides must be 16-byte aligned");
+  if ((int64_t)pairs * (tx > ty ? tx : ty) > INT32_MAX) return fail(nullptr, VDR_ERR_INVALID, "nn_cosine: pairs * max(tx, ty) exceeds 2^31 - 1");
+  RUN_OP(launch_nn_cosine(x, ldx, x_stride, tx, y, ldy, y_stride, ty, pairs, d, work, row_sim, row_idx, col_sim, col_idx,
+                          (hipStream_t)stream),
+         "nn_cosine");
+}
+
 // ---- profiler ---------------------------------------------------------------------------------------
 int vdr_profile_enable(vdr_handle m, int on) {
   if (!m) return fail(m, VDR_ERR_INVALID, "null handle");

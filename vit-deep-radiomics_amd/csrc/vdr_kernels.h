@@ -307,6 +307,15 @@ hipError_t launch_im2col_strided(const void* images, int in_bf16, void* col, int
 hipError_t launch_log_bin(const void* x, int in_bf16, int64_t ld, int64_t image_stride, int batch, int gh, int gw, int C,
                           int hierarchy, float* work, void* out, int out_bf16, hipStream_t st);
 
+// Cosine nearest neighbours of two descriptor maps (nn_cosine.hip; the definition is vdr_op_nn_cosine's in include/vdr.h):
+// X_p [tx, d], Y_p [ty, d] bf16, rows ldx / ldy elements apart, pairs x_stride / y_stride apart (0: one map against many).
+// d % 32 == 0; pointers, row and pair strides 16-byte aligned; work: nn_cosine_work_bytes(pairs, tx, ty) bytes.  col_sim and
+// col_idx both null: the column side is skipped.  Three launches (row norms, the fused tile kernel, the fold of partials).
+size_t nn_cosine_work_bytes(int pairs, int tx, int ty);
+hipError_t launch_nn_cosine(const void* x, int64_t ldx, int64_t x_stride, int tx, const void* y, int64_t ldy, int64_t y_stride,
+                            int ty, int pairs, int d, void* work, float* row_sim, int32_t* row_idx, float* col_sim,
+                            int32_t* col_idx, hipStream_t st);
+
 // pos_embed resampling (pos_interp.hip): the patch rows of a position table from a gh0 x gw0 grid to gh x gw, bicubic
 // (A = -0.75, align_corners = False, border taps clamped), fp64 arithmetic, one rounding to fp32
 hipError_t launch_pos_interp(const float* pos, int gh0, int gw0, int D, float* out, int gh, int gw, hipStream_t s);

@@ -10,6 +10,8 @@ methods runs in libvdr.so on the MI355X.  There is no CPU fallback.
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
+
 import numpy as np
 import torch
 
@@ -109,6 +111,49 @@ def intermediate_layer_indices(n, depth: int) -> "list[int]":
     if len(set(idx)) != len(idx):
         raise ValueError(f"block indices {idx} repeat one")
     return sorted(idx)
+
+
+@dataclass
+class Correspondences:
+    """Result of VitDescriptorModel.find_correspondences for B image pairs on a gh x gw grid of t = gh * gw patches.
+    nn12 [B, t] int32: for every patch of image 1 its cosine-nearest patch of image 2, sim12 [B, t] fp32 that similarity;
+    nn21 / sim21 the reverse.  saliency1 / saliency2 [B, t] fp32: the last block's CLS attention over the patch columns,
+    mean over the heads, min-max normalised per image.  mask [B, t] bool: best buddies (nn21[nn12[i]] == i) whose two
+    patches are both salient (> thresh).  grid = (gh, gw); stride and patch place a grid index in the image."""
+    nn12: torch.Tensor
+    sim12: torch.Tensor
+    nn21: torch.Tensor
+    sim21: torch.Tensor
+    saliency1: torch.Tensor
+    saliency2: torch.Tensor
+    mask: torch.Tensor
+    grid: "tuple[int, int]"
+    stride: int
+    patch: int
+
+    def points(self, b: int, num_pairs=None):
+        """The correspondences of pair b as two [k, 2] float tensors of (y, x) pixel centres (image 1, image 2), patch
+        (gy, gx) at gy * stride + patch / 2: the masked positions in order of descending sim12 (ties: ascending
+        position), cut to num_pairs."""
+        idx = torch.nonzero(self.mask[b], as_tuple=False).flatten()
+        order = torch.sort(self.sim12[b][idx], descending=True, stable=True).indices
+        idx = idx[order]
+        if num_pairs is not None:
+            idx = idx[: int(num_pairs)]
+        gw = self.grid[1]
+
+        def centres(i):
+            i = i.long()
+            y, x = torch.div(i, gw, rounding_mode="floor"), i % gw
+            return torch.stack((y, x), dim=1).float() * self.stride + self.patch / 2
+
+        return centres(idx), centres(self.nn12[b][idx])
+
+
+def minmax_normalise(a: torch.Tensor) -> torch.Tensor:
+    """(a - min) / (max - min) over the last dimension (a constant row gives zeros)"""
+    lo, hi = a.min(dim=-1, keepdim=True).values, a.max(dim=-1, keepdim=True).values
+    return (a - lo) / (hi - lo).clamp_min(torch.finfo(a.dtype).tiny)
 
 
 class VitDescriptorModel:
@@ -333,6 +378,38 @@ class VitDescriptorModel:
             gh, gw = self.engine.grid
             return got.reshape(got.shape[0], gh, gw, got.shape[-1])
         return got.unsqueeze(1)
+
+    def find_correspondences(self, x1: torch.Tensor, x2: torch.Tensor, layer=None, facet: str = "key", bin: bool = True,
+                             hierarchy: int = 2, thresh: float = 0.05) -> Correspondences:
+        """dino-vit-features' point correspondences: mutual cosine nearest neighbours ("best buddies") between the
+        descriptors of x1[b] and x2[b], x1 and x2 [B, 3, H, W] of one shape, kept where both patches are salient.
+        One forward over cat([x1, x2]) (vdr_forward_facets) writes the bf16 `facet` descriptors of block `layer` (None: the
+        last block; upstream uses block 9 of 12), log-binned at `hierarchy` when bin, and the head-mean CLS attention of the
+        last block; vdr.ops.nn_cosine then matches the two halves of that one buffer in place -- the t x t similarity
+        matrix is never materialised.  The input size, patch stride and dynamic_size in force apply.  Deviations from
+        upstream: the saliency averages all heads (upstream: four chosen heads of dino_vits8), and Correspondences.points
+        ranks by similarity (upstream: k-means over the buddies' descriptors, ranked by saliency).  Refusals (ValueError,
+        before any device work): extract_descriptors' (unknown facet, hierarchy outside 1..3, a layer out of range, SAM /
+        token / post-LN / block-less models), a model without a CLS token, x1 and x2 of different shapes."""
+        h = self._descriptor_args(layer, facet, bin, False, hierarchy)
+        if not self.cfg.has_cls:
+            raise ValueError("find_correspondences: the saliency is the CLS row's attention; the model has no CLS token")
+        if x1.dim() != 4 or tuple(x1.shape) != tuple(x2.shape):
+            raise ValueError(f"find_correspondences: x1 and x2 must be [B, 3, H, W] of the same shape, got {tuple(x1.shape)} "
+                             f"and {tuple(x2.shape)}")
+        from . import ops
+        i = self.cfg.layers - 1 if layer is None else int(layer)
+        self._adopt(x1)
+        B = x1.shape[0]
+        both = torch.cat([x1.to(self.device), x2.to(self.device)])
+        (desc,), _, (att,) = self.engine.forward_descriptors(both, [FacetOut(i, facet, h, False, torch.bfloat16)],
+                                                             maps=[AttnMap(self.cfg.layers - 1, 1, True)])
+        sim12, nn12, sim21, nn21 = ops.nn_cosine(desc[:B], desc[B:])
+        sal = minmax_normalise(att[:, 0, self.cfg.n_prefix:])
+        sal1, sal2 = sal[:B], sal[B:]
+        mask = ops.best_buddies(nn12, nn21) & (sal1 > thresh) & (torch.gather(sal2, 1, nn12.long()) > thresh)
+        return Correspondences(nn12, sim12, nn21, sim21, sal1, sal2, mask, tuple(self.engine.grid), int(self.engine.patch_stride),
+                               int(self.cfg.patch))
 
     def _descriptor_args(self, layer, facet, bin, include_cls, hierarchy) -> int:
         """The device-free refusals of a descriptor request; returns the hierarchy to ask for (0 without binning)."""

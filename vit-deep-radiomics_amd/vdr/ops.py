@@ -273,6 +273,69 @@ def log_bin(x: torch.Tensor, gh: int, gw: int, hierarchy: int = 2, out_dtype=tor
     return out
 
 
+def _nn_operand(t: torch.Tensor, name: str):
+    """(tensor, row stride, pair stride) of one nn_cosine operand, read where it lies when it can be"""
+    if t.dtype != torch.bfloat16:
+        t = t.to(torch.bfloat16)  # (fp32: rounded once; a new contiguous tensor)
+    P, n, d = t.shape
+    ok = (d == 1 or t.stride(2) == 1) and (n == 1 or (t.stride(1) >= d and t.stride(1) % 8 == 0)) and \
+        (P == 1 or (t.stride(0) >= 0 and t.stride(0) % 8 == 0)) and t.data_ptr() % 16 == 0
+    if not ok:
+        if d > 1 and t.stride(2) != 1:
+            raise ValueError(f"nn_cosine: the channels of {name} must be contiguous")
+        t = t.contiguous()
+    return t, (t.stride(1) if n > 1 else d), (t.stride(0) if P > 1 else 0)
+
+
+def nn_cosine(x: torch.Tensor, y: torch.Tensor, mutual: bool = True):
+    """Cosine nearest neighbours between descriptor maps (vdr_op_nn_cosine): x [P, tx, d], y [P, ty, d] on the device, bf16
+    -- contiguous, or views with contiguous channels (column slices of a wider buffer, rows behind a prefix, a batch stride
+    of 0 from expand(): one map against many), read in place.  fp32 inputs are rounded once to bf16 first.  d must be a
+    multiple of 32.  Returns (row_sim [P, tx] fp32, row_idx [P, tx] int32, col_sim [P, ty], col_idx [P, ty]):
+    row_sim[p, i] = max_j cos(x[p, i], y[p, j]) and row_idx the lowest j attaining it, col_* the same over i for every j;
+    col_sim and col_idx are None when mutual=False (the column side is then not computed).  The [tx, ty] similarity matrix
+    is never materialised.  The exact arithmetic is stated in include/vdr.h."""
+    for t, name in ((x, "x"), (y, "y")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"nn_cosine: {name} must be a [P, t, d] float32 or bfloat16 tensor")
+        if not t.is_cuda:
+            raise TypeError(f"nn_cosine: {name} must live on the HIP device")
+    if x.device != y.device:
+        raise ValueError("nn_cosine: x and y must be on the same device")
+    if x.shape[0] != y.shape[0] or x.shape[2] != y.shape[2]:
+        raise ValueError(f"nn_cosine: x {tuple(x.shape)} and y {tuple(y.shape)} must agree in P and d")
+    P, tx, d = x.shape
+    ty = y.shape[1]
+    if min(P, tx, ty, d) <= 0:
+        raise ValueError("nn_cosine: empty operand")
+    if d % 32:
+        raise ValueError(f"nn_cosine: d must be a multiple of 32, got {d}")
+    if P * max(tx, ty) > 2 ** 31 - 1:
+        raise ValueError("nn_cosine: P * max(tx, ty) exceeds 2^31 - 1")
+    lib = L.load()
+    x, ldx, xs = _nn_operand(x, "x")
+    y, ldy, ys = _nn_operand(y, "y")
+    dev = x.device
+    work = torch.empty((lib.vdr_nn_cosine_work_bytes(P, tx, ty),), dtype=torch.uint8, device=dev)
+    row_sim = torch.empty((P, tx), dtype=torch.float32, device=dev)
+    row_idx = torch.empty((P, tx), dtype=torch.int32, device=dev)
+    col_sim = torch.empty((P, ty), dtype=torch.float32, device=dev) if mutual else None
+    col_idx = torch.empty((P, ty), dtype=torch.int32, device=dev) if mutual else None
+    L.check(lib.vdr_op_nn_cosine(x.data_ptr(), ldx, xs, tx, y.data_ptr(), ldy, ys, ty, P, d, work.data_ptr(), row_sim.data_ptr(),
+                                 row_idx.data_ptr(), _p(col_sim), _p(col_idx), _s(x)))
+    return row_sim, row_idx, col_sim, col_idx
+
+
+def best_buddies(row_idx: torch.Tensor, col_idx: torch.Tensor) -> torch.Tensor:
+    """Mutual nearest neighbours: row_idx [P, tx] (for every row of x its nearest row of y), col_idx [P, ty] (the reverse)
+    -> bool [P, tx], col_idx[p, row_idx[p, i]] == i.  Pure torch; CPU tensors work too."""
+    if row_idx.dim() != 2 or col_idx.dim() != 2 or row_idx.shape[0] != col_idx.shape[0]:
+        raise ValueError(f"best_buddies: row_idx [P, tx] and col_idx [P, ty] expected, got {tuple(row_idx.shape)} and "
+                         f"{tuple(col_idx.shape)}")
+    back = torch.gather(col_idx.long(), 1, row_idx.long())
+    return back == torch.arange(row_idx.shape[1], device=row_idx.device).unsqueeze(0)
+
+
 def patch_embed(images, weight, bias, p, pos=None, row_stride=None, row_offset=0, out=None):
     """images [B,C,H,H] fp32/bf16; weight [D,C,p,p] (any float dtype); returns bf16 [B*row_stride, D]."""
     lib = L.load()
