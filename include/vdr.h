@@ -757,6 +757,44 @@ int vdr_op_nn_cosine(const void* x, int64_t ldx, int64_t x_stride, int tx,
                      const void* y, int64_t ldy, int64_t y_stride, int ty,
                      int pairs, int d, void* work,
                      float* row_sim, int32_t* row_idx, float* col_sim, int32_t* col_idx, void* stream);
+
+/* PCA of dense descriptor maps (csrc/pca.hip): the column mean, the centred covariance and the projection on given
+ * components.  The eigen-decomposition between the last two is the caller's (vdr.pca.fit: torch.linalg.eigh in float64).
+ * Operand, shared by the three entry points: `problems` problems, each `imgs` images of t rows of d channels, R = imgs * t
+ *   rows per problem; rows ld elements apart, images image_stride elements apart, image q of problem p is image
+ *   p * imgs + q counted from x; in_dtype VDR_BF16 or VDR_F32.  Per-image PCA of a batch B is problems = B, imgs = 1; joint
+ *   PCA is problems = 1, imgs = B.  A view into a wider buffer (a key facet inside the qkv activation, ld = 3D) is read in
+ *   place.  work: vdr_pca_work_bytes(problems, imgs, t, d) bytes of device scratch, 16-byte aligned, enough for any of the
+ *   three.  Rows are cut into chunks of VDR_COV_CHUNK rows; the chunk length is part of the definition, not a launch
+ *   heuristic.  No atomics; results are bitwise reproducible, and a problem's result depends neither on `problems` nor on
+ *   its position in the batch.
+ * vdr_op_col_mean:  mean[p, c] = S / float(R), one IEEE division, S the fp32 sum of column c in this order: inside a chunk
+ *   sixteen interleaved sums (rows r, r + 16, r + 32, ... of the chunk, ascending), folded in ascending r; then the chunk sums
+ *   in ascending chunk order.                                                                      mean [problems, d] fp32
+ * vdr_op_covariance:  z[r, c] = bf16_rn(float(x[r, c]) - mean[p, c]): the subtraction in fp32 BEFORE the one rounding to
+ *   bf16, so a map with a large channel mean keeps its variance.  cov[p, c1, c2] = (sum_r z[r, c1] * z[r, c2]) / float(R - 1)
+ *   (the n - 1 of sklearn), one IEEE division; the products (exact in fp32) are accumulated in fp32 by bf16 MFMAs over
+ *   16 rows at a time, rows ascending within a chunk, and the chunk sums are folded in ascending chunk order.  cov is written
+ *   whole and is exactly symmetric (c1 <= c2 is computed, both entries are written from it).  `mean` is an input: any
+ *   vector may be passed.  R >= 2.                                                               cov [problems, d, d] fp32
+ * vdr_op_pca_project:  proj[p, r, j] = sum_c (float(x[r, c]) - mean[p, c]) * comps[p, j, c], all in fp32 (no bf16 rounding;
+ *   separate multiply and add): lane l of 64 sums its channels 8l .. 8l + 7, 512 + 8l .., ... ascending, then the 64 lane
+ *   sums are folded by an xor butterfly (distance 32, 16, ... 1).  minmax[p] = (min, max) over the problem's whole [R, k]
+ *   block -- one range for all components.  scale != 0: proj = (proj - min) / (max - min), one IEEE subtraction and one
+ *   IEEE division per element, when max != min; left as it is otherwise.  k = 1..8.
+ *                                      comps [problems, k, d] fp32, proj [problems, R, k] fp32, minmax [problems, 2] fp32
+ * Refused before the device is touched: VDR_ERR_UNSUPPORTED for d % 32 != 0, d > 2048, k outside 1..8; VDR_ERR_INVALID for
+ * an in_dtype other than the two, null pointers, non-positive problems, imgs, t or d, R < 2 (covariance), ld < d, a negative
+ * image_stride, pointers or strides (ld, image_stride) that are not 16-byte aligned, problems * R above 2^31 - 1. */
+#define VDR_COV_CHUNK 1024
+size_t vdr_pca_work_bytes(int problems, int imgs, int t, int d);
+int vdr_op_col_mean(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int imgs, int t, int d,
+                    void* work, float* mean, void* stream);
+int vdr_op_covariance(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int imgs, int t, int d,
+                      const float* mean, void* work, float* cov, void* stream);
+int vdr_op_pca_project(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int imgs, int t, int d,
+                       const float* mean, const float* comps, int k, int scale, void* work, float* proj, float* minmax,
+                       void* stream);
 /* ---- measurement ------------------------------------------------------------------------ */
 
 /* Kernel classes timed by the built-in HIP-event profiler. */

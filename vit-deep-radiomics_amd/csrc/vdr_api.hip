@@ -2716,6 +2716,56 @@ int vdr_op_nn_cosine(const void* x, int64_t ldx, int64_t x_stride, int tx, const
          "nn_cosine");
 }
 
+size_t vdr_pca_work_bytes(int problems, int imgs, int t, int d) { return pca_work_bytes(problems, imgs, t, d); }
+
+// the operand checks shared by the three PCA ops (include/vdr.h); `outs`: the op's other pointers
+static int pca_operand(const char* op, const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int imgs,
+                       int t, int d, std::initializer_list<const void*> outs) {
+  static thread_local char msg[160];
+  const auto refuse = [&](int code, const char* what) {
+    snprintf(msg, sizeof msg, "%s: %s", op, what);
+    return fail(nullptr, code, msg);
+  };
+  if (in_dtype != VDR_F32 && in_dtype != VDR_BF16) return refuse(VDR_ERR_INVALID, "in_dtype must be VDR_F32 or VDR_BF16");
+  bool null = !x;
+  for (const void* q : outs) null = null || !q;
+  if (null) return refuse(VDR_ERR_INVALID, "null pointer");
+  if (problems <= 0 || imgs <= 0 || t <= 0 || d <= 0) return refuse(VDR_ERR_INVALID, "problems, imgs, t and d must be positive");
+  if (d % 32 != 0 || d > 2048) return refuse(VDR_ERR_UNSUPPORTED, "d must be a multiple of 32, at most 2048");
+  if (ld < d || image_stride < 0) return refuse(VDR_ERR_INVALID, "ld must be >= d, image_stride >= 0");
+  const int64_t per16 = in_dtype == VDR_BF16 ? 8 : 4;  // elements of a 16-byte chunk
+  if (!aligned16({x}) || !aligned16(outs) || ld % per16 || image_stride % per16)
+    return refuse(VDR_ERR_INVALID, "pointers, rows (ld) and images (image_stride) must be 16-byte aligned");
+  const int64_t R = (int64_t)imgs * t;  // (each factor is a positive int: no overflow; R is bounded before the next product)
+  if (R > INT32_MAX || R * problems > INT32_MAX) return refuse(VDR_ERR_INVALID, "problems * R exceeds 2^31 - 1");
+  return VDR_OK;
+}
+
+int vdr_op_col_mean(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int imgs, int t, int d, void* work,
+                    float* mean, void* stream) {
+  if (int rc = pca_operand("col_mean", x, in_dtype, ld, image_stride, problems, imgs, t, d, {work, mean})) return rc;
+  RUN_OP(launch_col_mean(x, in_dtype == VDR_BF16, ld, image_stride, problems, imgs, t, d, work, mean, (hipStream_t)stream), "col_mean");
+}
+
+int vdr_op_covariance(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int imgs, int t, int d,
+                      const float* mean, void* work, float* cov, void* stream) {
+  if (int rc = pca_operand("covariance", x, in_dtype, ld, image_stride, problems, imgs, t, d, {mean, work, cov})) return rc;
+  if ((int64_t)imgs * t < 2) return fail(nullptr, VDR_ERR_INVALID, "covariance: needs R = imgs * t >= 2 rows");
+  RUN_OP(launch_covariance(x, in_dtype == VDR_BF16, ld, image_stride, problems, imgs, t, d, mean, work, cov, (hipStream_t)stream),
+         "covariance");
+}
+
+int vdr_op_pca_project(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int imgs, int t, int d,
+                       const float* mean, const float* comps, int k, int scale, void* work, float* proj, float* minmax,
+                       void* stream) {
+  if (int rc = pca_operand("pca_project", x, in_dtype, ld, image_stride, problems, imgs, t, d, {mean, comps, work, proj, minmax}))
+    return rc;
+  if (k < 1 || k > 8) return fail(nullptr, VDR_ERR_UNSUPPORTED, "pca_project: k must be 1..8");
+  RUN_OP(launch_pca_project(x, in_dtype == VDR_BF16, ld, image_stride, problems, imgs, t, d, mean, comps, k, scale, work, proj,
+                            minmax, (hipStream_t)stream),
+         "pca_project");
+}
+
 // ---- profiler ---------------------------------------------------------------------------------------
 int vdr_profile_enable(vdr_handle m, int on) {
   if (!m) return fail(m, VDR_ERR_INVALID, "null handle");

@@ -316,6 +316,19 @@ hipError_t launch_nn_cosine(const void* x, int64_t ldx, int64_t x_stride, int tx
                             int ty, int pairs, int d, void* work, float* row_sim, int32_t* row_idx, float* col_sim,
                             int32_t* col_idx, hipStream_t st);
 
+// PCA of dense descriptor maps (pca.hip; the definitions are vdr_op_col_mean's, vdr_op_covariance's and vdr_op_pca_project's
+// in include/vdr.h): `problems` problems of `imgs` images of t rows of d channels, bf16 or fp32, rows ld and images
+// image_stride elements apart.  d % 32 == 0, d <= 2048; pointers and strides 16-byte aligned; work: pca_work_bytes(...)
+// bytes.  Two launches each (partials, fold); the projection a third when it rescales.
+size_t pca_work_bytes(int problems, int imgs, int t, int d);
+hipError_t launch_col_mean(const void* x, int in_bf16, int64_t ld, int64_t image_stride, int problems, int imgs, int t, int d,
+                           void* work, float* mean, hipStream_t st);
+hipError_t launch_covariance(const void* x, int in_bf16, int64_t ld, int64_t image_stride, int problems, int imgs, int t, int d,
+                             const float* mean, void* work, float* cov, hipStream_t st);
+hipError_t launch_pca_project(const void* x, int in_bf16, int64_t ld, int64_t image_stride, int problems, int imgs, int t, int d,
+                              const float* mean, const float* comps, int k, int scale, void* work, float* proj, float* minmax,
+                              hipStream_t st);
+
 // pos_embed resampling (pos_interp.hip): the patch rows of a position table from a gh0 x gw0 grid to gh x gw, bicubic
 // (A = -0.75, align_corners = False, border taps clamped), fp64 arithmetic, one rounding to fp32
 hipError_t launch_pos_interp(const float* pos, int gh0, int gw0, int D, float* out, int gh, int gw, hipStream_t s);

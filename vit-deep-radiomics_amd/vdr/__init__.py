@@ -8,4 +8,5 @@ from ._lib import (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GELU_TANH, EPI_BIAS_QUICK_G
 from .engine import AttnMap, Engine, FacetOut, LayerOut, VdrConfig  # noqa: F401
 from .model import (ARCHS, Correspondences, TransformerNoduleBimodalClassifier, TransformerNoduleClassifier, VitDescriptorModel, extract_dense, get_dense_descriptor,  # noqa: F401
                     load_model)
-from . import pipeline, prep  # noqa: F401,E402
+from . import pca, pipeline, prep  # noqa: F401,E402
+from .pca import Pca, pca_colorize  # noqa: F401,E402

@@ -411,6 +411,47 @@ class VitDescriptorModel:
         return Correspondences(nn12, sim12, nn21, sim21, sal1, sal2, mask, tuple(self.engine.grid), int(self.engine.patch_stride),
                                int(self.cfg.patch))
 
+    def pca_descriptors(self, x: torch.Tensor, n_components: int = 3, layer=None, facet=None, joint: bool = False,
+                        remove_bg: bool = False) -> torch.Tensor:
+        """The reference's pca_colorize (visualization_utils.py:49-69) of every image's dense descriptors, on the device:
+        [B, 3, H, W] -> [B, gh, gw, n_components] fp32, the leading principal components of each image's map (joint=True:
+        of all B maps together, as dino-vit-features' joint PCA), min-max scaled over a problem's whole block;
+        remove_bg=True applies the Otsu cut on channel 0 per problem.  One forward, one fit, one projection: facet=None
+        takes the model's own dense descriptor (what get_dense_descriptor returns: the SAM neck output for 'medsam',
+        patch_embed otherwise), a facet ("key" | "query" | "value" | "token") block `layer`'s bf16 descriptors
+        (vdr_forward_facets); vdr.pca.fit and the projection read that buffer in place.  The input size, patch stride and
+        dynamic_size in force apply.  Refusals (ValueError, before any device work): extract_descriptors' own;
+        n_components outside 1..8; a layer without a facet; a descriptor width that is not a multiple of 32 or exceeds
+        2048.  Log-binned descriptors are not offered: at ViT-B width bin=True gives (1 + 8 * hierarchy) * 768 > 2048
+        channels, whose PCA would need the t x t Gram side."""
+        from . import pca
+        if facet is not None:
+            self._descriptor_args(layer, facet, False, False, 2)
+        elif layer is not None:
+            raise ValueError("pca_descriptors: layer needs a facet")
+        if not 1 <= int(n_components) <= 8:
+            raise ValueError(f"pca_descriptors: n_components must be 1..8, got {n_components}")
+        d = self.cfg.neck_chans if facet is None and self.cfg.window > 0 else self.cfg.dim
+        if d % 32 or d > 2048:
+            raise ValueError(f"pca_descriptors: {d} descriptor channels; the covariance kernel takes multiples of 32 up to 2048 "
+                             "(which also excludes log-binned descriptors, bin=True, at ViT-B width)")
+        if x.dim() != 4:
+            raise ValueError(f"pca_descriptors: x must be [B, 3, H, W], got {tuple(x.shape)}")
+        if facet is None and self.cfg.window > 0:
+            desc = self.engine.forward(x, L.OUT_ENCODER, torch.float32)  # [B, g, g, C], channel-last
+            gh, gw = int(desc.shape[1]), int(desc.shape[2])
+        else:
+            self._adopt(x)
+            if facet is None:
+                desc = self.engine.forward(x, L.OUT_PATCH_EMBED, torch.float32)
+            else:
+                i = self.cfg.layers - 1 if layer is None else int(layer)
+                (desc,), _, _ = self.engine.forward_descriptors(x, [FacetOut(i, facet, 0, False, torch.bfloat16)])
+            gh, gw = self.engine.grid
+        B = desc.shape[0]
+        rgb = pca._colorize_maps(desc.reshape(B, gh * gw, desc.shape[-1]), int(n_components), joint, remove_bg)
+        return rgb.reshape(B, gh, gw, rgb.shape[-1])
+
     def _descriptor_args(self, layer, facet, bin, include_cls, hierarchy) -> int:
         """The device-free refusals of a descriptor request; returns the hierarchy to ask for (0 without binning)."""
         check_descriptor_model(self.cfg)

@@ -336,6 +336,105 @@ def best_buddies(row_idx: torch.Tensor, col_idx: torch.Tensor) -> torch.Tensor:
     return back == torch.arange(row_idx.shape[1], device=row_idx.device).unsqueeze(0)
 
 
+def _pca_operand(x: torch.Tensor, op: str, joint: bool):
+    """The host-side refusals of a PCA operand and its description for the library: (tensor, in_dtype, ld, image_stride,
+    problems, imgs, t, d).  x [P, t, d] bf16 / fp32, read where it lies when its channels are contiguous and its rows and
+    images 16-byte aligned (a column slice of a wider buffer, rows behind a prefix); copied once otherwise."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{op}: x must be a [P, t, d] float32 or bfloat16 tensor")
+    if not x.is_cuda:
+        raise TypeError(f"{op}: x must live on the HIP device")
+    P, t, d = x.shape
+    if min(P, t, d) <= 0:
+        raise ValueError(f"{op}: empty operand")
+    if d % 32 or d > 2048:
+        raise ValueError(f"{op}: d must be a multiple of 32, at most 2048, got {d}")
+    if P * t > 2 ** 31 - 1:
+        raise ValueError(f"{op}: P * t exceeds 2^31 - 1")
+    per16 = 8 if x.dtype == torch.bfloat16 else 4
+    ok = x.stride(2) == 1 and (t == 1 or (x.stride(1) >= d and x.stride(1) % per16 == 0)) and \
+        (P == 1 or (x.stride(0) >= 0 and x.stride(0) % per16 == 0)) and x.data_ptr() % 16 == 0
+    if not ok:
+        x = x.contiguous()
+    ld = x.stride(1) if t > 1 else d
+    stride = x.stride(0) if P > 1 else 0
+    problems, imgs = (1, P) if joint else (P, 1)
+    return x, (L.VDR_BF16 if x.dtype == torch.bfloat16 else L.VDR_F32), ld, stride, problems, imgs, t, d
+
+
+def _pca_work(lib, problems, imgs, t, d, dev):
+    return torch.empty((lib.vdr_pca_work_bytes(problems, imgs, t, d),), dtype=torch.uint8, device=dev)
+
+
+def _pca_vector(v, name: str, op: str, shape, dev):
+    if not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or tuple(v.shape) != tuple(shape):
+        raise ValueError(f"{op}: {name} must be a float32 tensor of shape {tuple(shape)}, got "
+                         f"{tuple(v.shape) if isinstance(v, torch.Tensor) else type(v).__name__}")
+    if v.device != dev:
+        raise ValueError(f"{op}: {name} must be on x's device")
+    return v.contiguous()
+
+
+def col_mean(x: torch.Tensor, joint: bool = False) -> torch.Tensor:
+    """Column means of descriptor maps (vdr_op_col_mean): x [P, t, d] bf16 / fp32 on the device -> [P, d] fp32, one mean
+    per image, or [1, d] with joint=True (the P * t rows of all images as one problem).  fp32 sums in a fixed order, one
+    IEEE division (include/vdr.h).  d must be a multiple of 32, at most 2048."""
+    x, dt, ld, stride, problems, imgs, t, d = _pca_operand(x, "col_mean", joint)
+    lib = L.load()
+    work = _pca_work(lib, problems, imgs, t, d, x.device)
+    mean = torch.empty((problems, d), dtype=torch.float32, device=x.device)
+    L.check(lib.vdr_op_col_mean(x.data_ptr(), dt, ld, stride, problems, imgs, t, d, work.data_ptr(), mean.data_ptr(), _s(x)))
+    return mean
+
+
+def covariance(x: torch.Tensor, mean=None, joint: bool = False):
+    """Centred covariance of descriptor maps (vdr_op_covariance): x [P, t, d] bf16 / fp32 on the device -> (mean [P, d],
+    cov [P, d, d]) fp32 -- [1, d] and [1, d, d] with joint=True.  mean=None: col_mean(x, joint); any other [problems, d]
+    fp32 vector is taken as it is.  z = bf16(float(x) - mean), cov = z^T z / (R - 1) accumulated in fp32 by bf16 MFMAs in
+    chunks of 1024 rows; exactly symmetric (include/vdr.h).  Needs R >= 2 rows per problem."""
+    x, dt, ld, stride, problems, imgs, t, d = _pca_operand(x, "covariance", joint)
+    if imgs * t < 2:
+        raise ValueError("covariance: needs at least 2 rows per problem")
+    lib = L.load()
+    work = _pca_work(lib, problems, imgs, t, d, x.device)
+    if mean is None:
+        mean = torch.empty((problems, d), dtype=torch.float32, device=x.device)
+        L.check(lib.vdr_op_col_mean(x.data_ptr(), dt, ld, stride, problems, imgs, t, d, work.data_ptr(), mean.data_ptr(), _s(x)))
+    else:
+        mean = _pca_vector(mean, "mean", "covariance", (problems, d), x.device)
+    cov = torch.empty((problems, d, d), dtype=torch.float32, device=x.device)
+    L.check(lib.vdr_op_covariance(x.data_ptr(), dt, ld, stride, problems, imgs, t, d, mean.data_ptr(), work.data_ptr(),
+                                  cov.data_ptr(), _s(x)))
+    return mean, cov
+
+
+def pca_project(x: torch.Tensor, mean: torch.Tensor, components: torch.Tensor, scale: bool = False):
+    """Projection of descriptor maps on given components (vdr_op_pca_project): x [P, t, d] bf16 / fp32 on the device, mean
+    [problems, d] and components [problems, k, d] fp32, k = 1..8; problems = P projects every image with its own mean and
+    components, problems = 1 (with P > 1) all P * t rows with the one set (joint).  Returns (proj [problems, R, k] fp32,
+    minmax [problems, 2] fp32), R = t or P * t: proj = (x - mean) . components^T in fp32, minmax the range of a
+    problem's whole block; scale=True rescales proj to (proj - min) / (max - min) where max != min (include/vdr.h)."""
+    if not isinstance(components, torch.Tensor) or components.dim() != 3:
+        raise ValueError("pca_project: components must be a [problems, k, d] float32 tensor")
+    problems, k = int(components.shape[0]), int(components.shape[1])
+    if not 1 <= k <= 8:
+        raise ValueError(f"pca_project: k must be 1..8, got {k}")
+    if not isinstance(x, torch.Tensor) or x.dim() != 3:
+        raise TypeError("pca_project: x must be a [P, t, d] float32 or bfloat16 tensor")
+    if problems not in (1, x.shape[0]):
+        raise ValueError(f"pca_project: {problems} sets of components for {x.shape[0]} images (one per image, or one for all)")
+    x, dt, ld, stride, problems, imgs, t, d = _pca_operand(x, "pca_project", problems == 1 and x.shape[0] > 1)
+    mean = _pca_vector(mean, "mean", "pca_project", (problems, d), x.device)
+    components = _pca_vector(components, "components", "pca_project", (problems, k, d), x.device)
+    lib = L.load()
+    work = _pca_work(lib, problems, imgs, t, d, x.device)
+    proj = torch.empty((problems, imgs * t, k), dtype=torch.float32, device=x.device)
+    minmax = torch.empty((problems, 2), dtype=torch.float32, device=x.device)
+    L.check(lib.vdr_op_pca_project(x.data_ptr(), dt, ld, stride, problems, imgs, t, d, mean.data_ptr(), components.data_ptr(), k,
+                                   int(bool(scale)), work.data_ptr(), proj.data_ptr(), minmax.data_ptr(), _s(x)))
+    return proj, minmax
+
+
 def patch_embed(images, weight, bias, p, pos=None, row_stride=None, row_offset=0, out=None):
     """images [B,C,H,H] fp32/bf16; weight [D,C,p,p] (any float dtype); returns bf16 [B*row_stride, D]."""
     lib = L.load()
