@@ -795,6 +795,72 @@ int vdr_op_covariance(const void* x, int in_dtype, int64_t ld, int64_t image_str
 int vdr_op_pca_project(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int imgs, int t, int d,
                        const float* mean, const float* comps, int k, int scale, void* work, float* proj, float* minmax,
                        void* stream);
+/* The t x t Gram side of the PCA and a top-k eigensolver on the device (csrc/pca.hip, csrc/pca_topk.hip): what
+ * vdr.pca.fit(solver="subspace") runs instead of the caller's eigh.  Operand of vdr_op_col_mean_any, vdr_op_gram and
+ * vdr_op_pca_back_project: `problems` maps of t rows of d channels (per image only: the operand above with imgs = 1), rows ld and
+ * maps image_stride elements apart, in_dtype VDR_BF16 or VDR_F32; d % 32 == 0 with NO upper bound on d.  work:
+ * vdr_pca_topk_work_bytes(problems, t, d, k) bytes of device scratch, 16-byte aligned, enough for any op of this block on
+ * a t x d operand (k = 8 covers every k) and for vdr_op_sym_topk on matrices of side n = t (side d when d <= 2048 is
+ * covered too when the call passes t = max(t, d)).  No atomics; results are bitwise reproducible, and a problem's result depends
+ * neither on `problems`, nor on its position in the batch, nor on the grid.
+ * vdr_op_col_mean_any:  vdr_op_col_mean's definition, kernels and bits (imgs = 1) at any d.
+ * vdr_op_gram:  z[r, c] = bf16_rn(float(x[r, c]) - mean[p, c]), the covariance's centring rule;
+ *   gram[p, r1, r2] = (sum_c z[r1, c] * z[r2, c]) / float(t - 1), one IEEE division.  The columns are cut into chunks of
+ *   VDR_GRAM_CHUNK columns -- the chunk length is part of the definition --; inside a chunk the products (exact in fp32) are
+ *   accumulated in fp32 by bf16 MFMAs over 16 columns at a time, columns ascending; the chunk sums are folded in ascending
+ *   chunk order.  gram is written whole and is exactly symmetric (r1 <= r2 is computed, both entries are written from it).
+ *   2 <= t <= 4096.  Scratch: one 128 x 128 fp32 tile per (pair of 128-row tiles, chunk).           gram [problems, t, t] fp32
+ * vdr_op_pca_back_project:  the step from eigenvectors u of the Gram matrix to components:
+ *   c[p, j, :] = sum_r u[p, j, r] * (float(x[r, :]) - mean[p, :]), fp32, separate multiply and add, in col_mean's order:
+ *   inside a chunk of VDR_COV_CHUNK rows sixteen interleaved sums (rows r, r + 16, ... ascending) folded in ascending r,
+ *   then the chunk sums in ascending chunk order.  Each component is then divided by its norm: the squared norm is
+ *   accumulated in float64 (thread i of 256 sums columns i, i + 256, ... ascending, then a binary tree over the threads),
+ *   comps = float(double(c) / sqrt(ss)).  A component whose values[p, j] <= 0 or whose norm is 0 is written as zeros.
+ *   k = 1..8.                               u [problems, k, t] fp32, values [problems, k] fp32, comps [problems, k, d] fp32
+ * vdr_op_sym_topk:  the k largest eigenpairs of symmetric positive semi-definite fp32 matrices a [problems, n, n] (symmetric
+ *   by contract: the product is formed as sum_c a[c, r] V[c, :]), n = 2..4096, k = 1..min(8, n).  Block subspace iteration
+ *   with a Rayleigh-Ritz step on b = min(16, n) columns; per iteration:
+ *     W = A V in fp32 FMAs (no bf16): the contraction is cut into slabs of VDR_TOPK_SLAB rows, inside a slab one FMA chain
+ *       per entry, rows ascending; the slab sums are folded in ascending slab order;
+ *     H = V^T W in float64, symmetrised; its Ritz pairs (theta_j, y_j) by a cyclic Jacobi (round-robin order; sweeps until no off-diagonal entry exceeds
+ *       2^-52 of the largest diagonal one, 10 at most),
+ *       sorted descending; residuals res_j = ||W y_j - theta_j V y_j||_2 in float64;
+ *     done when res_j <= tol * theta_1 for the k leading pairs, or after max_iter iterations;
+ *     else V = orthonormalised columns W y_j / theta_j (rounded to fp32, Gram matrix in float64, Cholesky).  A column whose
+ *       Ritz value is not above 2^-40 theta_1 or whose Cholesky pivot is not above 2^-30 of its diagonal is dropped (zero
+ *       from then on): a matrix of rank r < k returns k - r zero vectors with value 0.
+ *   Start block, fixed: for n <= 16 the first n columns of the identity; else V0[r, c] = +1 / -1 by bit 0 of the hash
+ *     h = (r * 0x9E3779B1) ^ (c * 0x85EBCA6B); h ^= h >> 15; h *= 0x2C1B3C6D; h ^= h >> 12; h *= 0x297A2D39; h ^= h >> 15
+ *     (uint32 arithmetic; bit set: -1), orthonormalised as above.  A problem's iterates are a property of the problem alone.
+ *   Outputs: values [problems, k] fp32 descending; vectors [problems, k, n] fp32, V y_j divided by its float64 norm, the entry of
+ *     largest magnitude positive (lowest index on a tie); iters [problems] int32, the iterations (A V products) used;
+ *     resid [problems] fp32 = max_j res_j / theta_1 at exit: a problem that ran into max_iter is told by resid > tol.
+ *   No host synchronisation: max_iter iterations are enqueued, every launch returns at once for a finished problem.
+ *   VDR_TOPK_TOL / VDR_TOPK_MAX_ITER: the defaults of vdr.ops.sym_topk and vdr.pca.fit, measured (profiles/pca_topk_bench.txt).
+ *     tol: with tol = 0 the residual stops falling at 3e-8 .. 8.2e-8 of theta_1 on planted spectra of n = 200 .. 4096 (no
+ *     growth with n: no fp32 chain is longer than a slab); four times the worst, 3.3e-7.  max_iter: the golden sklearn maps
+ *     need 3 - 4 iterations, ViT-B/16 key facets 27 - 42, their log-binned 729 x 13 056 map 73; twice that, 146.
+ *     Left out of that rule on purpose: the synthetic white-noise maps of the README's PCA table, whose spectrum does not
+ *     fall (80 - 94 iterations at 196 x 768, 142 at 729 x 768, 218 at 3969 x 768, so the rule would give 436 or more): they
+ *     run into max_iter at the covariance sizes and vdr.pca.fit decomposes them by eigh, which README reports as losses.
+ * Refused before the device is touched: VDR_ERR_UNSUPPORTED for d % 32 != 0, t outside 2..4096 (gram), n outside 2..4096,
+ * k outside 1..8 (or above n); VDR_ERR_INVALID for an in_dtype other than the two, null pointers, non-positive problems, t
+ * or d, ld < d, a negative image_stride, pointers or strides that are not 16-byte aligned, problems * t above 2^31 - 1, a
+ * negative or NaN tol, max_iter < 1. */
+#define VDR_GRAM_CHUNK 256
+#define VDR_TOPK_SLAB 128
+#define VDR_TOPK_TOL 3.3e-7f
+#define VDR_TOPK_MAX_ITER 146
+size_t vdr_pca_topk_work_bytes(int problems, int t, int d, int k);
+int vdr_op_col_mean_any(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int t, int d, void* work,
+                        float* mean, void* stream);
+int vdr_op_gram(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int t, int d, const float* mean,
+                void* work, float* gram, void* stream);
+int vdr_op_pca_back_project(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int t, int d,
+                            const float* mean, const float* u, const float* values, int k, void* work, float* comps,
+                            void* stream);
+int vdr_op_sym_topk(const float* a, int problems, int n, int k, float tol, int max_iter, void* work, float* values,
+                    float* vectors, int32_t* iters, float* resid, void* stream);
 /* ---- measurement ------------------------------------------------------------------------ */
 
 /* Kernel classes timed by the built-in HIP-event profiler. */

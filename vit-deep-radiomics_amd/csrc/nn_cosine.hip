@@ -31,14 +31,15 @@
 
 #include <cstdint>
 
+#include "tile128.h"
 #include "vdr_dev.h"
 #include "vdr_kernels.h"
 
 namespace vdr {
 namespace {
 
-constexpr int NN_T = 128;                   // tile side (rows of X per panel, rows of Y per tile)
-constexpr int NN_OPER = NN_T * 128;         // bytes of one staged operand tile
+constexpr int NN_T = T128;                  // tile side (rows of X per panel, rows of Y per tile): the shared tile of tile128.h
+constexpr int NN_OPER = T128_OPER;          // bytes of one staged operand tile
 constexpr int NN_RN = 4 * NN_OPER;          // s_rn [2][256] float: tile parity x (rn of the tile's Y rows | of the panel's X rows)
 constexpr int NN_COL = NN_RN + 2048;        // column exchange: value [128], index [128]
 constexpr int NN_ROW = NN_COL + 1024;       // row exchange: value [2][128], index [2][128]
@@ -114,24 +115,6 @@ VDR_DEV void nn_stage(const NnArgs& a, const bf16_t* xp, const bf16_t* yp, int64
   }
 }
 
-template <int KS0, int KS1>
-VDR_DEV void nn_mfma(const char* sx, int wr, int wc, int l31, int hh, f32x16 (&acc)[2][2]) {
-  const int swz = (l31 >> 1) & 7;
-#pragma unroll
-  for (int ks = KS0; ks < KS1; ++ks) {
-    const int off = ((2 * ks + hh) ^ swz) * 16;
-    bf16x8 af[2], bf[2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m) af[m] = *reinterpret_cast<const bf16x8*>(sx + (wr * 64 + m * 32 + l31) * 128 + off);
-#pragma unroll
-    for (int n = 0; n < 2; ++n) bf[n] = *reinterpret_cast<const bf16x8*>(sx + NN_OPER + (wc * 64 + n * 32 + l31) * 128 + off);
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[m], bf[n], acc[m][n], 0, 0, 0);
-  }
-}
-
 __global__ __launch_bounds__(256, 2) void nn_cosine_kernel(NnArgs a) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l31 = lane & 31, hh = lane >> 5;
@@ -183,8 +166,8 @@ __global__ __launch_bounds__(256, 2) void nn_cosine_kernel(NnArgs a) {
     if (s + 1 < nsteps) nn_stage(a, xp, yp, p, panel, njt, nkk, smem, buf ^ 1, wave, lane);
     if (s >= 0) {
       const char* sx = smem + buf * 2 * NN_OPER;
-      nn_mfma<0, 2>(sx, wr, wc, l31, hh, acc);
-      if (a.d - kk * 64 >= 64) nn_mfma<2, 4>(sx, wr, wc, l31, hh, acc);
+      t128_mfma<0, 2>(sx, wr, wc, l31, hh, acc);
+      if (a.d - kk * 64 >= 64) t128_mfma<2, 4>(sx, wr, wc, l31, hh, acc);
       if (kk + 1 == nk) {
         // ---- epilogue of tile jt
         const float* rn = s_rn + (jt & 1) * 256;

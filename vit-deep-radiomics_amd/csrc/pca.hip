@@ -23,11 +23,22 @@
 //                16-byte chunks lane, lane + 64, ... in chunk order into k fp32 sums, then the xor butterfly.  The
 //                workgroup's min / max go to `work`; pca_minmax_kernel folds them per problem (min and max are exact in any
 //                order), pca_scale_kernel rescales in place when asked.
+//   gram         (vdr_op_gram, the t x t side for t < d)  pca_gram_kernel: one work item = (problem, pair ti <= tj of
+//                128-ROW tiles, chunk of VDR_GRAM_CHUNK columns).  The product contracts over the contiguous index, so the
+//                tile is nn_cosine.hip's (tile128.h): both operands are [128 rows][64 bf16] images of a 64-column step, read
+//                with ds_read_b128.  Staged through registers like the covariance (the centring again rules the LDS-DMA out):
+//                a thread owns 16-byte chunk tid & 7 of rows (tid >> 3) + 32 j of each tile and the 8 means of its columns.
+//                The partial goes to `work` in the covariance's layout and pca_cov_finish_kernel folds it (matrix side t,
+//                divisor t - 1).  The mean at any d is pca_mean_kernel's (launch_col_mean_any: the same launches, the same bits).
+//   back_project (vdr_op_pca_back_project)  pca_back_kernel: the weighted sibling of pca_mean_kernel, one workgroup =
+//                (problem, 1024-row chunk, 128 columns), k weighted sums per column; pca_back_finish_kernel folds the
+//                chunks ascending and normalises each component with a float64 norm.
 // No atomics anywhere; nothing depends on `problems`, on the grid or on a launch heuristic.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "tile128.h"
 #include "vdr_dev.h"
 #include "vdr_kernels.h"
 #include "../../include/vdr.h"
@@ -290,6 +301,182 @@ __global__ __launch_bounds__(256) void pca_cov_finish_kernel(PcaArgs a, float* c
   c[(int64_t)gj * a.d + gi] = v;
 }
 
+// ---- Gram (t x t) -----------------------------------------------------------------------------------
+constexpr int GRAM_CHUNK = VDR_GRAM_CHUNK;  // columns per chunk: a constant of the definition
+constexpr int GRAM_STEP = 64;               // columns staged per step
+static_assert(GRAM_CHUNK % GRAM_STEP == 0, "a chunk is whole steps");
+
+// a.nt / a.npairs: 128-row tiles over t and their pairs; a.nchunks: column chunks over d
+template <bool BF16>
+__global__ __launch_bounds__(256) void pca_gram_kernel(PcaArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, hh = lane >> 5;
+  const int wr = wave >> 1, wc = wave & 1;
+  int id = blockIdx.x;
+  const int chunk = id % a.nchunks;
+  id /= a.nchunks;
+  const int pair = id % a.npairs, p = id / a.npairs;
+  int ti = 0, rem = pair;
+  while (rem >= a.nt - ti) {
+    rem -= a.nt - ti;
+    ++ti;
+  }
+  const int tj = ti + rem;
+  const bool diag = ti == tj;
+
+  // staging role: 16-byte chunk ch of the 64-column step, rows rl, rl + 32, rl + 64, rl + 96 of each tile
+  const int ch = tid & 7, rl = tid >> 3;
+  const int c0 = chunk * GRAM_CHUNK;
+  const int c1 = c0 + GRAM_CHUNK < a.d ? c0 + GRAM_CHUNK : a.d;
+  const int nsteps = (c1 - c0 + GRAM_STEP - 1) / GRAM_STEP;
+  bool rok[2][4];
+  int64_t roff[2][4];
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int r = (s ? tj : ti) * T128 + rl + 32 * j;
+      rok[s][j] = r < a.t && !(s == 1 && diag);
+      roff[s][j] = rok[s][j] ? pca_row(a, p, r) : 0;
+    }
+
+  PcaRaw<BF16> raw[2][4];
+  float mu[8], mu_next[8];
+  const auto fetch = [&](int step) {
+    const int col = c0 + step * GRAM_STEP + ch * 8;
+    const bool cok = col < c1;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) mu_next[e] = cok ? a.mean[(int64_t)p * a.d + col + e] : 0.0f;
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (rok[s][j] && cok) raw[s][j].load(a.x, roff[s][j] + col);
+        else raw[s][j].zero();
+      }
+  };
+  // (a row past t or a column past the chunk was fetched as zeros and has a zero mean: it is staged as zero)
+  const auto stage = [&]() {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) mu[e] = mu_next[e];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int src = s == 1 && diag ? 0 : s;  // a diagonal pair stages the one tile as both operands
+        bf16x8 z;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) z[e] = (bf16_t)(rok[src][j] ? raw[src][j].get(e) - mu[e] : 0.0f);
+        *reinterpret_cast<bf16x8*>(smem + s * T128_OPER + t128_off(rl + 32 * j, ch)) = z;
+      }
+  };
+
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[m][n][e] = 0.0f;
+
+  fetch(0);
+#pragma clang loop unroll(disable)
+  for (int step = 0; step < nsteps; ++step) {
+    __syncthreads();  // every wave has read the previous step
+    stage();
+    __syncthreads();
+    if (step + 1 < nsteps) fetch(step + 1);
+    t128_mfma<0, 4>(smem, wr, wc, l31, hh, acc);
+  }
+
+  float* part = a.part + (((int64_t)p * a.npairs + pair) * a.nchunks + chunk) * (PCA_T * PCA_T);
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int row = wr * 64 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+        part[row * PCA_T + wc * 64 + n * 32 + l31] = acc[m][n][e];
+      }
+}
+
+// ---- back-projection (Gram eigenvectors -> components) ----------------------------------------------
+// part[((p * nchunks + chunk) * k + j) * d + c] = sum over the chunk's rows of u[p, j, r] * (float(x[r, c]) - mean[p, c])
+__global__ __launch_bounds__(256) void pca_back_kernel(PcaArgs a, const float* u, int k) {
+  __shared__ float s[16][PCA_T];
+  const int ncg = a.nt;
+  int id = blockIdx.x;
+  const int cg = id % ncg;
+  id /= ncg;
+  const int chunk = id % a.nchunks, p = id / a.nchunks;
+  const int ch = threadIdx.x & 15, rl = threadIdx.x >> 4;
+  const int col = cg * PCA_T + ch * 8;
+  const bool cok = col < a.d;
+  const int64_t r0 = (int64_t)chunk * PCA_CHUNK;
+  const int64_t r1 = r0 + PCA_CHUNK < a.R ? r0 + PCA_CHUNK : a.R;
+  float mu[8], acc[8][8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) mu[e] = cok ? a.mean[(int64_t)p * a.d + col + e] : 0.0f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[j][e] = 0.0f;
+  if (cok)
+    for (int64_t r = r0 + rl; r < r1; r += 16) {
+      float v[8];
+      pca_load8(a, pca_row(a, p, r) + col, v);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] -= mu[e];
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (j < k) {
+          const float w = u[((int64_t)p * k + j) * a.R + r];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[j][e] += w * v[e];
+        }
+    }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    if (j >= k) break;  // (uniform)
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s[rl][ch * 8 + e] = acc[j][e];
+    __syncthreads();
+    if (threadIdx.x < PCA_T && cg * PCA_T + (int)threadIdx.x < a.d) {
+      float sum = s[0][threadIdx.x];
+#pragma unroll
+      for (int q = 1; q < 16; ++q) sum += s[q][threadIdx.x];
+      a.part[(((int64_t)p * a.nchunks + chunk) * k + j) * a.d + cg * PCA_T + threadIdx.x] = sum;
+    }
+  }
+}
+
+// one workgroup per (problem, component): chunk sums folded ascending, the squared norm in float64 (a thread's columns
+// tid, tid + 256, ... ascending, then a fixed binary tree over the 256 threads), one float64 division per element
+__global__ __launch_bounds__(256) void pca_back_finish_kernel(PcaArgs a, const float* values, int k, float* comps) {
+  __shared__ double s[256];
+  const int p = blockIdx.x / k, j = blockIdx.x - p * k;
+  float* out = comps + ((int64_t)p * k + j) * a.d;
+  double ss = 0.0;
+  for (int c = threadIdx.x; c < a.d; c += 256) {
+    const float* src = a.part + ((int64_t)p * a.nchunks * k + j) * a.d + c;
+    float sum = src[0];
+    for (int q = 1; q < a.nchunks; ++q) sum += src[(int64_t)q * k * a.d];
+    out[c] = sum;
+    ss += (double)sum * (double)sum;
+  }
+  s[threadIdx.x] = ss;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
+    __syncthreads();
+  }
+  const double norm = sqrt(s[0]);
+  const bool live = values[(int64_t)p * k + j] > 0.0f && norm > 0.0;
+  for (int c = threadIdx.x; c < a.d; c += 256) out[c] = live ? (float)((double)out[c] / norm) : 0.0f;
+}
+
 // ---- projection -------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void pca_project_kernel(PcaArgs a, const float* comps, int k, int nblocks, float* proj) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -382,8 +569,8 @@ int64_t pca_chunks(int64_t R) { return (R + PCA_CHUNK - 1) / PCA_CHUNK; }
 int64_t pca_proj_blocks(int64_t R) { return (R + PCA_PROJ_ROWS - 1) / PCA_PROJ_ROWS; }
 
 bool pca_args(PcaArgs& a, const void* x, int in_bf16, int64_t ld, int64_t image_stride, int problems, int imgs, int t, int d,
-              void* work) {
-  if (!x || !work || problems <= 0 || imgs <= 0 || t <= 0 || d <= 0 || (d & 31) || d > 2048 || ld < d || image_stride < 0)
+              void* work, int dmax = 2048) {
+  if (!x || !work || problems <= 0 || imgs <= 0 || t <= 0 || d <= 0 || (d & 31) || d > dmax || ld < d || image_stride < 0)
     return false;
   const int64_t per16 = in_bf16 ? 8 : 4;
   if ((((uintptr_t)x | (uintptr_t)work) & 15) || ld % per16 || image_stride % per16) return false;
@@ -463,6 +650,66 @@ hipError_t launch_pca_project(const void* x, int in_bf16, int64_t ld, int64_t im
     if (hipError_t e = hipGetLastError()) return e;
   }
   return hipSuccess;
+}
+
+static int64_t gram_chunks(int d) { return (d + GRAM_CHUNK - 1) / GRAM_CHUNK; }
+
+size_t pca_topk_side_work_bytes(int problems, int t, int d, int k) {
+  if (problems <= 0 || t <= 0 || d <= 0 || k <= 0) return 0;
+  const int64_t nt = (t + T128 - 1) / T128;
+  const int64_t mean = pca_chunks(t) * d, gram = nt * (nt + 1) / 2 * gram_chunks(d) * (PCA_T * PCA_T), back = pca_chunks(t) * k * d;
+  int64_t n = mean > gram ? mean : gram;
+  n = n > back ? n : back;
+  return (size_t)((n * problems * 4 + 15) & ~(int64_t)15);
+}
+
+hipError_t launch_col_mean_any(const void* x, int in_bf16, int64_t ld, int64_t image_stride, int problems, int t, int d, void* work,
+                               float* mean, hipStream_t st) {
+  PcaArgs a;
+  if (!mean || !pca_args(a, x, in_bf16, ld, image_stride, problems, 1, t, d, work, INT32_MAX & ~31)) return hipErrorInvalidValue;
+  const int64_t grid = (int64_t)problems * a.nchunks * a.nt;
+  if (grid > INT32_MAX) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pca_mean_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
+  if (hipError_t e = hipGetLastError()) return e;
+  hipLaunchKernelGGL(pca_mean_finish_kernel, dim3((unsigned)(((int64_t)problems * d + 255) / 256)), dim3(256), 0, st, a, problems, mean);
+  return hipGetLastError();
+}
+
+hipError_t launch_gram(const void* x, int in_bf16, int64_t ld, int64_t image_stride, int problems, int t, int d, const float* mean,
+                       void* work, float* gram, hipStream_t st) {
+  PcaArgs a;
+  if (!mean || !gram || t < 2 || t > 4096 || !pca_args(a, x, in_bf16, ld, image_stride, problems, 1, t, d, work, INT32_MAX & ~31))
+    return hipErrorInvalidValue;
+  a.mean = mean;
+  a.nt = (t + T128 - 1) / T128;
+  a.npairs = a.nt * (a.nt + 1) / 2;
+  a.nchunks = (int)gram_chunks(d);
+  const int64_t items = (int64_t)problems * a.npairs * a.nchunks;
+  const int64_t fin = (int64_t)problems * a.npairs * (PCA_T * PCA_T / 256);
+  if (items > INT32_MAX || fin > INT32_MAX) return hipErrorInvalidValue;
+  if (in_bf16) hipLaunchKernelGGL(pca_gram_kernel<true>, dim3((unsigned)items), dim3(256), 2 * T128_OPER, st, a);
+  else hipLaunchKernelGGL(pca_gram_kernel<false>, dim3((unsigned)items), dim3(256), 2 * T128_OPER, st, a);
+  if (hipError_t e = hipGetLastError()) return e;
+  PcaArgs f = a;  // the fold of the covariance, on a t x t matrix: side t, divisor R - 1 = t - 1
+  f.d = t;
+  hipLaunchKernelGGL(pca_cov_finish_kernel, dim3((unsigned)fin), dim3(256), 0, st, f, gram);
+  return hipGetLastError();
+}
+
+hipError_t launch_pca_back_project(const void* x, int in_bf16, int64_t ld, int64_t image_stride, int problems, int t, int d,
+                                   const float* mean, const float* u, const float* values, int k, void* work, float* comps,
+                                   hipStream_t st) {
+  PcaArgs a;
+  if (!mean || !u || !values || !comps || k < 1 || k > 8 ||
+      !pca_args(a, x, in_bf16, ld, image_stride, problems, 1, t, d, work, INT32_MAX & ~31))
+    return hipErrorInvalidValue;
+  a.mean = mean;
+  const int64_t grid = (int64_t)problems * a.nchunks * a.nt;
+  if (grid > INT32_MAX) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pca_back_kernel, dim3((unsigned)grid), dim3(256), 0, st, a, u, k);
+  if (hipError_t e = hipGetLastError()) return e;
+  hipLaunchKernelGGL(pca_back_finish_kernel, dim3((unsigned)(problems * k)), dim3(256), 0, st, a, values, k, comps);
+  return hipGetLastError();
 }
 
 }  // namespace vdr

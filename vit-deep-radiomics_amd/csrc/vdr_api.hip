@@ -2766,6 +2766,68 @@ int vdr_op_pca_project(const void* x, int in_dtype, int64_t ld, int64_t image_st
          "pca_project");
 }
 
+// the Gram side and the top-k solver (include/vdr.h): the operand checks of the PCA ops without the d <= 2048 limit
+static int pca_topk_operand(const char* op, const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int t, int d,
+                            std::initializer_list<const void*> outs) {
+  static thread_local char msg[160];
+  const auto refuse = [&](int code, const char* what) {
+    snprintf(msg, sizeof msg, "%s: %s", op, what);
+    return fail(nullptr, code, msg);
+  };
+  if (in_dtype != VDR_F32 && in_dtype != VDR_BF16) return refuse(VDR_ERR_INVALID, "in_dtype must be VDR_F32 or VDR_BF16");
+  bool null = !x;
+  for (const void* q : outs) null = null || !q;
+  if (null) return refuse(VDR_ERR_INVALID, "null pointer");
+  if (problems <= 0 || t <= 0 || d <= 0) return refuse(VDR_ERR_INVALID, "problems, t and d must be positive");
+  if (d % 32 != 0) return refuse(VDR_ERR_UNSUPPORTED, "d must be a multiple of 32");
+  if (ld < d || image_stride < 0) return refuse(VDR_ERR_INVALID, "ld must be >= d, image_stride >= 0");
+  const int64_t per16 = in_dtype == VDR_BF16 ? 8 : 4;  // elements of a 16-byte chunk
+  if (!aligned16({x}) || !aligned16(outs) || ld % per16 || image_stride % per16)
+    return refuse(VDR_ERR_INVALID, "pointers, rows (ld) and images (image_stride) must be 16-byte aligned");
+  if ((int64_t)t * problems > INT32_MAX) return refuse(VDR_ERR_INVALID, "problems * t exceeds 2^31 - 1");
+  return VDR_OK;
+}
+
+size_t vdr_pca_topk_work_bytes(int problems, int t, int d, int k) {
+  const size_t side = pca_topk_side_work_bytes(problems, t, d, k), solver = sym_topk_work_bytes(problems, t);
+  return side > solver ? side : solver;
+}
+
+int vdr_op_col_mean_any(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int t, int d, void* work,
+                        float* mean, void* stream) {
+  if (int rc = pca_topk_operand("col_mean_any", x, in_dtype, ld, image_stride, problems, t, d, {work, mean})) return rc;
+  RUN_OP(launch_col_mean_any(x, in_dtype == VDR_BF16, ld, image_stride, problems, t, d, work, mean, (hipStream_t)stream), "col_mean_any");
+}
+
+int vdr_op_gram(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int t, int d, const float* mean,
+                void* work, float* gram, void* stream) {
+  if (int rc = pca_topk_operand("gram", x, in_dtype, ld, image_stride, problems, t, d, {mean, work, gram})) return rc;
+  if (t < 2 || t > 4096) return fail(nullptr, VDR_ERR_UNSUPPORTED, "gram: t must be 2..4096");
+  RUN_OP(launch_gram(x, in_dtype == VDR_BF16, ld, image_stride, problems, t, d, mean, work, gram, (hipStream_t)stream), "gram");
+}
+
+int vdr_op_pca_back_project(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int t, int d,
+                            const float* mean, const float* u, const float* values, int k, void* work, float* comps, void* stream) {
+  if (int rc = pca_topk_operand("pca_back_project", x, in_dtype, ld, image_stride, problems, t, d, {mean, u, values, work, comps}))
+    return rc;
+  if (k < 1 || k > 8) return fail(nullptr, VDR_ERR_UNSUPPORTED, "pca_back_project: k must be 1..8");
+  RUN_OP(launch_pca_back_project(x, in_dtype == VDR_BF16, ld, image_stride, problems, t, d, mean, u, values, k, work, comps,
+                                 (hipStream_t)stream),
+         "pca_back_project");
+}
+
+int vdr_op_sym_topk(const float* a, int problems, int n, int k, float tol, int max_iter, void* work, float* values, float* vectors,
+                    int32_t* iters, float* resid, void* stream) {
+  if (!a || !work || !values || !vectors || !iters || !resid) return fail(nullptr, VDR_ERR_INVALID, "sym_topk: null pointer");
+  if (problems <= 0) return fail(nullptr, VDR_ERR_INVALID, "sym_topk: problems must be positive");
+  if (n < 2 || n > 4096) return fail(nullptr, VDR_ERR_UNSUPPORTED, "sym_topk: n must be 2..4096");
+  if (k < 1 || k > 8 || k > n) return fail(nullptr, VDR_ERR_UNSUPPORTED, "sym_topk: k must be 1..min(8, n)");
+  if (!(tol >= 0.0f) || max_iter < 1) return fail(nullptr, VDR_ERR_INVALID, "sym_topk: tol must be >= 0, max_iter >= 1");
+  if (!aligned16({a, work, values, vectors, iters, resid}))
+    return fail(nullptr, VDR_ERR_INVALID, "sym_topk: pointers must be 16-byte aligned");
+  RUN_OP(launch_sym_topk(a, problems, n, k, tol, max_iter, work, values, vectors, iters, resid, (hipStream_t)stream), "sym_topk");
+}
+
 // ---- profiler ---------------------------------------------------------------------------------------
 int vdr_profile_enable(vdr_handle m, int on) {
   if (!m) return fail(m, VDR_ERR_INVALID, "null handle");

@@ -329,6 +329,21 @@ hipError_t launch_pca_project(const void* x, int in_bf16, int64_t ld, int64_t im
                               const float* mean, const float* comps, int k, int scale, void* work, float* proj, float* minmax,
                               hipStream_t st);
 
+// The Gram side and the top-k solver (pca.hip, pca_topk.hip; the definitions are vdr_op_gram's, vdr_op_pca_back_project's and
+// vdr_op_sym_topk's in include/vdr.h).  Per image only (imgs = 1); d % 32 == 0 with no upper bound, 2 <= t <= 4096.
+// launch_col_mean_any: launch_col_mean's kernels and bits at any d.
+size_t pca_topk_side_work_bytes(int problems, int t, int d, int k);
+hipError_t launch_col_mean_any(const void* x, int in_bf16, int64_t ld, int64_t image_stride, int problems, int t, int d, void* work,
+                               float* mean, hipStream_t st);
+hipError_t launch_gram(const void* x, int in_bf16, int64_t ld, int64_t image_stride, int problems, int t, int d, const float* mean,
+                       void* work, float* gram, hipStream_t st);
+hipError_t launch_pca_back_project(const void* x, int in_bf16, int64_t ld, int64_t image_stride, int problems, int t, int d,
+                                   const float* mean, const float* u, const float* values, int k, void* work, float* comps,
+                                   hipStream_t st);
+size_t sym_topk_work_bytes(int problems, int n);
+hipError_t launch_sym_topk(const float* a, int problems, int n, int k, float tol, int max_iter, void* work, float* values,
+                           float* vectors, int32_t* iters, float* resid, hipStream_t st);
+
 // pos_embed resampling (pos_interp.hip): the patch rows of a position table from a gh0 x gw0 grid to gh x gw, bicubic
 // (A = -0.75, align_corners = False, border taps clamped), fp64 arithmetic, one rounding to fp32
 hipError_t launch_pos_interp(const float* pos, int gh0, int gw0, int D, float* out, int gh, int gw, hipStream_t s);

@@ -422,34 +422,57 @@ class VitDescriptorModel:
         (vdr_forward_facets); vdr.pca.fit and the projection read that buffer in place.  The input size, patch stride and
         dynamic_size in force apply.  Refusals (ValueError, before any device work): extract_descriptors' own;
         n_components outside 1..8; a layer without a facet; a descriptor width that is not a multiple of 32 or exceeds
-        2048.  Log-binned descriptors are not offered: at ViT-B width bin=True gives (1 + 8 * hierarchy) * 768 > 2048
-        channels, whose PCA would need the t x t Gram side."""
+        2048.  Log-binned descriptors (at ViT-B width bin=True gives (1 + 8 * hierarchy) * 768 > 2048 channels) and the
+        library's own top-k solver are keywords of pca_descriptor_maps; this signature stays as it was."""
+        return self.pca_descriptor_maps(x, n_components, layer, facet, joint, remove_bg)
+
+    def pca_descriptor_maps(self, x: torch.Tensor, n_components: int = 3, layer=None, facet=None, joint: bool = False,
+                            remove_bg: bool = False, bin: bool = False, hierarchy: int = 2, solver: str = "eigh") -> torch.Tensor:
+        """pca_descriptors with the log-binning of extract_descriptors and the solver of vdr.pca.fit as keywords (the
+        defaults are pca_descriptors, bit for bit).  bin=True (needs a facet): the PCA of the facet's descriptors log-binned
+        at `hierarchy` (1..3), (1 + 8 * hierarchy) * D channels.  solver="subspace": the library's top-k solver on the
+        smaller side -- a map with fewer rows than channels goes through the t x t Gram matrix, which is what admits more
+        than 2048 channels (per image only, at most 4096 patches per image); beyond 2048 channels the colours are the fit's own scores
+        (Pca.scores), up to 2048 the projection kernel's as on the covariance side.
+        Further refusals (ValueError, before any device work): bin without a facet, an unknown solver, and with
+        solver="subspace" a joint PCA of more than 2048 channels, more than 4096 patches per image on the Gram side,
+        n_components above rows - 1."""
         from . import pca
+        if solver not in pca.SOLVERS:
+            raise ValueError(f"pca_descriptors: solver must be one of {pca.SOLVERS}, got {solver!r}")
+        h = 0
         if facet is not None:
-            self._descriptor_args(layer, facet, False, False, 2)
+            h = self._descriptor_args(layer, facet, bool(bin), False, hierarchy)
         elif layer is not None:
             raise ValueError("pca_descriptors: layer needs a facet")
+        elif bin:
+            raise ValueError("pca_descriptors: bin needs a facet")
         if not 1 <= int(n_components) <= 8:
             raise ValueError(f"pca_descriptors: n_components must be 1..8, got {n_components}")
         d = self.cfg.neck_chans if facet is None and self.cfg.window > 0 else self.cfg.dim
-        if d % 32 or d > 2048:
+        d *= 1 + 8 * h
+        if d % 32 or (d > 2048 and solver == "eigh"):
             raise ValueError(f"pca_descriptors: {d} descriptor channels; the covariance kernel takes multiples of 32 up to 2048 "
                              "(which also excludes log-binned descriptors, bin=True, at ViT-B width)")
         if x.dim() != 4:
             raise ValueError(f"pca_descriptors: x must be [B, 3, H, W], got {tuple(x.shape)}")
         if facet is None and self.cfg.window > 0:
+            if solver == "subspace":  # (fit's refusals, ahead of the forward: the SAM grid is fixed by the configuration)
+                pca._check_subspace(int(x.shape[0]), (self.cfg.img // self.cfg.patch) ** 2, d, int(n_components), joint)
             desc = self.engine.forward(x, L.OUT_ENCODER, torch.float32)  # [B, g, g, C], channel-last
             gh, gw = int(desc.shape[1]), int(desc.shape[2])
         else:
             self._adopt(x)
+            gh, gw = self.engine.grid
+            if solver == "subspace":  # (fit's refusals, ahead of the forward)
+                pca._check_subspace(int(x.shape[0]), gh * gw, d, int(n_components), joint)
             if facet is None:
                 desc = self.engine.forward(x, L.OUT_PATCH_EMBED, torch.float32)
             else:
                 i = self.cfg.layers - 1 if layer is None else int(layer)
-                (desc,), _, _ = self.engine.forward_descriptors(x, [FacetOut(i, facet, 0, False, torch.bfloat16)])
-            gh, gw = self.engine.grid
+                (desc,), _, _ = self.engine.forward_descriptors(x, [FacetOut(i, facet, h, False, torch.bfloat16)])
         B = desc.shape[0]
-        rgb = pca._colorize_maps(desc.reshape(B, gh * gw, desc.shape[-1]), int(n_components), joint, remove_bg)
+        rgb = pca._colorize_maps(desc.reshape(B, gh * gw, desc.shape[-1]), int(n_components), joint, remove_bg, solver)
         return rgb.reshape(B, gh, gw, rgb.shape[-1])
 
     def _descriptor_args(self, layer, facet, bin, include_cls, hierarchy) -> int:

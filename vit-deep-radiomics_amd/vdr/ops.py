@@ -435,6 +435,123 @@ def pca_project(x: torch.Tensor, mean: torch.Tensor, components: torch.Tensor, s
     return proj, minmax
 
 
+TOPK_TOL = 3.3e-7    # VDR_TOPK_TOL (include/vdr.h)
+TOPK_MAX_ITER = 146  # VDR_TOPK_MAX_ITER
+
+
+def _topk_operand(x: torch.Tensor, op: str):
+    """_pca_operand's refusals for the per-image Gram side: any d % 32 == 0, no upper bound -> (tensor, in_dtype, ld,
+    image_stride, problems, t, d)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{op}: x must be a [P, t, d] float32 or bfloat16 tensor")
+    if not x.is_cuda:
+        raise TypeError(f"{op}: x must live on the HIP device")
+    P, t, d = x.shape
+    if min(P, t, d) <= 0:
+        raise ValueError(f"{op}: empty operand")
+    if d % 32:
+        raise ValueError(f"{op}: d must be a multiple of 32, got {d}")
+    if P * t > 2 ** 31 - 1:
+        raise ValueError(f"{op}: P * t exceeds 2^31 - 1")
+    per16 = 8 if x.dtype == torch.bfloat16 else 4
+    ok = x.stride(2) == 1 and (t == 1 or (x.stride(1) >= d and x.stride(1) % per16 == 0)) and \
+        (P == 1 or (x.stride(0) >= 0 and x.stride(0) % per16 == 0)) and x.data_ptr() % 16 == 0
+    if not ok:
+        x = x.contiguous()
+    ld = x.stride(1) if t > 1 else d
+    stride = x.stride(0) if P > 1 else 0
+    return x, (L.VDR_BF16 if x.dtype == torch.bfloat16 else L.VDR_F32), ld, stride, P, t, d
+
+
+def _topk_work(lib, problems, t, d, k, dev):
+    return torch.empty((lib.vdr_pca_topk_work_bytes(problems, t, d, k),), dtype=torch.uint8, device=dev)
+
+
+def col_mean_any(x: torch.Tensor) -> torch.Tensor:
+    """col_mean per image at any width (vdr_op_col_mean_any): x [P, t, d] bf16 / fp32 on the device -> [P, d] fp32, bit for
+    bit col_mean's result where d <= 2048."""
+    x, dt, ld, stride, P, t, d = _topk_operand(x, "col_mean_any")
+    lib = L.load()
+    work = _topk_work(lib, P, t, d, 1, x.device)
+    mean = torch.empty((P, d), dtype=torch.float32, device=x.device)
+    L.check(lib.vdr_op_col_mean_any(x.data_ptr(), dt, ld, stride, P, t, d, work.data_ptr(), mean.data_ptr(), _s(x)))
+    return mean
+
+
+def gram(x: torch.Tensor, mean=None):
+    """Centred Gram matrices of descriptor maps (vdr_op_gram), the t x t side of the PCA for t < d: x [P, t, d] bf16 / fp32
+    on the device -> (mean [P, d], gram [P, t, t]) fp32, per image.  mean=None: col_mean_any(x); any other [P, d] fp32 vector is
+    taken as it is.  z = bf16(float(x) - mean), gram = z z^T / (t - 1) accumulated in fp32 by bf16 MFMAs in chunks of 256
+    columns; exactly symmetric (include/vdr.h).  d % 32 == 0 with no upper bound, 2 <= t <= 4096."""
+    x, dt, ld, stride, P, t, d = _topk_operand(x, "gram")
+    if not 2 <= t <= 4096:
+        raise ValueError(f"gram: t must be 2..4096 rows per image, got {t}")
+    lib = L.load()
+    work = _topk_work(lib, P, t, d, 1, x.device)
+    if mean is None:
+        mean = torch.empty((P, d), dtype=torch.float32, device=x.device)
+        L.check(lib.vdr_op_col_mean_any(x.data_ptr(), dt, ld, stride, P, t, d, work.data_ptr(), mean.data_ptr(), _s(x)))
+    else:
+        mean = _pca_vector(mean, "mean", "gram", (P, d), x.device)
+    g = torch.empty((P, t, t), dtype=torch.float32, device=x.device)
+    L.check(lib.vdr_op_gram(x.data_ptr(), dt, ld, stride, P, t, d, mean.data_ptr(), work.data_ptr(), g.data_ptr(), _s(x)))
+    return mean, g
+
+
+def sym_topk(a: torch.Tensor, k: int, tol: float = TOPK_TOL, max_iter: int = TOPK_MAX_ITER):
+    """The k largest eigenpairs of symmetric positive semi-definite matrices (vdr_op_sym_topk): a [P, n, n] fp32 on the
+    device, n = 2..4096, k = 1..min(8, n) -> (values [P, k] fp32 descending, vectors [P, k, n] fp32 of unit length with the
+    entry of largest magnitude positive, iters [P] int32, resid [P] fp32).  Block subspace iteration with a Rayleigh-Ritz
+    step on 16 columns, all on the device, no host synchronisation; a problem is done when its k leading residuals are at or
+    below tol * theta_1.  resid > tol tells a problem that ran into max_iter (include/vdr.h)."""
+    if not isinstance(a, torch.Tensor) or a.dim() != 3 or a.shape[1] != a.shape[2] or a.dtype != torch.float32:
+        raise TypeError("sym_topk: a must be a [P, n, n] float32 tensor")
+    if not a.is_cuda:
+        raise TypeError("sym_topk: a must live on the HIP device")
+    P, n = int(a.shape[0]), int(a.shape[1])
+    if P <= 0:
+        raise ValueError("sym_topk: empty operand")
+    if not 2 <= n <= 4096:
+        raise ValueError(f"sym_topk: n must be 2..4096, got {n}")
+    k = int(k)
+    if not 1 <= k <= min(8, n):
+        raise ValueError(f"sym_topk: k must be 1..min(8, n) = 1..{min(8, n)}, got {k}")
+    if not float(tol) >= 0.0 or int(max_iter) < 1:
+        raise ValueError(f"sym_topk: tol must be >= 0 and max_iter >= 1, got {tol} and {max_iter}")
+    a = a.contiguous()
+    lib = L.load()
+    work = _topk_work(lib, P, n, 32, 1, a.device)
+    values = torch.empty((P, k), dtype=torch.float32, device=a.device)
+    vectors = torch.empty((P, k, n), dtype=torch.float32, device=a.device)
+    iters = torch.empty((P,), dtype=torch.int32, device=a.device)
+    resid = torch.empty((P,), dtype=torch.float32, device=a.device)
+    L.check(lib.vdr_op_sym_topk(a.data_ptr(), P, n, k, float(tol), int(max_iter), work.data_ptr(), values.data_ptr(),
+                                vectors.data_ptr(), iters.data_ptr(), resid.data_ptr(), _s(a)))
+    return values, vectors, iters, resid
+
+
+def pca_back_project(x: torch.Tensor, mean: torch.Tensor, u: torch.Tensor, values: torch.Tensor) -> torch.Tensor:
+    """From eigenvectors of the Gram matrix to principal components (vdr_op_pca_back_project): x [P, t, d] bf16 / fp32 on the
+    device, mean [P, d], u [P, k, t], values [P, k] fp32 -> components [P, k, d] fp32,
+    c[p, j] = sum_r u[p, j, r] * (float(x[r]) - mean[p]) in fp32 in col_mean's row order, divided by its float64 norm; a
+    component with values[p, j] <= 0 comes back as zeros (include/vdr.h).  k = 1..8, any d % 32 == 0."""
+    if not isinstance(u, torch.Tensor) or u.dim() != 3:
+        raise ValueError("pca_back_project: u must be a [P, k, t] float32 tensor")
+    k = int(u.shape[1])
+    if not 1 <= k <= 8:
+        raise ValueError(f"pca_back_project: k must be 1..8, got {k}")
+    x, dt, ld, stride, P, t, d = _topk_operand(x, "pca_back_project")
+    mean = _pca_vector(mean, "mean", "pca_back_project", (P, d), x.device)
+    u = _pca_vector(u, "u", "pca_back_project", (P, k, t), x.device)
+    values = _pca_vector(values, "values", "pca_back_project", (P, k), x.device)
+    lib = L.load()
+    work = _topk_work(lib, P, t, d, k, x.device)
+    comps = torch.empty((P, k, d), dtype=torch.float32, device=x.device)
+    L.check(lib.vdr_op_pca_back_project(x.data_ptr(), dt, ld, stride, P, t, d, mean.data_ptr(), u.data_ptr(), values.data_ptr(), k,
+                                        work.data_ptr(), comps.data_ptr(), _s(x)))
+    return comps
+
+
 def patch_embed(images, weight, bias, p, pos=None, row_stride=None, row_offset=0, out=None):
     """images [B,C,H,H] fp32/bf16; weight [D,C,p,p] (any float dtype); returns bf16 [B*row_stride, D]."""
     lib = L.load()
