@@ -39,21 +39,32 @@ def e4m3_decode_table() -> np.ndarray:
     return out
 
 
-def scale_exponent(amax: torch.Tensor) -> torch.Tensor:
-    """e = ceil(log2(amax / 448)) computed on the fp32 bit pattern exactly as the kernel does."""
-    t = (amax.to(torch.float32) * np.float32(1.0 / 448.0)).contiguous()
+def scale_exponent(amax: torch.Tensor, ignore_nan: bool = False) -> torch.Tensor:
+    """e = ceil(log2(amax / 448)) computed on the fp32 bit pattern exactly as the kernel does.  ignore_nan: a NaN maximum
+    counts as 0 (an all-NaN block under fmaxf); by default it reads as 2^128 and clamps to 126."""
+    amax = amax.to(torch.float32)
+    if ignore_nan:
+        amax = torch.where(torch.isnan(amax), torch.zeros_like(amax), amax)
+    t = (amax * np.float32(1.0 / 448.0)).contiguous()
     bits = t.view(torch.int32)
     e = ((bits >> 23) & 255) - 127 + ((bits & 0x7FFFFF) != 0).to(torch.int32)
     return e.clamp(-126, 126)
 
 
-def mx_quantize(x: torch.Tensor):
-    """x [..., K] (K % 32 == 0) -> (payload float8_e4m3fn [..., K], exponent int32 [..., K/32])."""
+def mx_quantize(x: torch.Tensor, ignore_nan: bool = False):
+    """x [..., K] (K % 32 == 0) -> (payload float8_e4m3fn [..., K], exponent int32 [..., K/32]).
+
+    ignore_nan: the block maximum skips NaN elements, as the kernels' fmaxf does (csrc/mx.hip): the NaN element itself
+    still converts to the e4m3 NaN, the rest of its block is quantised as if it were absent.  Default: amax propagates
+    the NaN and the whole block is scaled by 2^126."""
     x = x.to(torch.float32)
     K = x.shape[-1]
     assert K % BLOCK == 0
     xb = x.reshape(*x.shape[:-1], K // BLOCK, BLOCK)
-    e = scale_exponent(xb.abs().amax(dim=-1))
+    a = xb.abs()
+    if ignore_nan:
+        a = torch.where(torch.isnan(a), torch.zeros_like(a), a)
+    e = scale_exponent(a.amax(dim=-1), ignore_nan)
     inv = torch.ldexp(torch.ones_like(xb[..., 0]), -e)
     q = (xb * inv[..., None]).to(torch.float8_e4m3fn)
     return q.reshape(x.shape), e

@@ -44,17 +44,8 @@ def token_to_window(batch, g, ws):
     return inv
 
 
-def mx_rows_pad(rows):
-    return (rows + 255) // 256 * 256
-
-
-def mx_scale_offsets(rows_total, rows, K):
-    """Byte offsets, [len(rows), K / 32], of the e8m0 scales of the given rows inside the scale array of an MX tensor of
-    rows_total rows (include/vdr.h: s[K/32][rows_pad], rows_pad = rows_total rounded up to 256; inside every 64-row group
-    rows are stored as (r, r + 32) pairs)."""
-    rows = torch.as_tensor(rows, dtype=torch.int64)
-    slot = (rows & ~63) + 2 * (rows & 31) + ((rows >> 5) & 1)
-    return torch.arange(K // 32)[None, :] * mx_rows_pad(rows_total) + slot[:, None]
+# the byte offsets of an MX tensor's scales: restated once, in oracle/mx_designs.py
+from oracle.mx_designs import mx_rows_pad, mx_scale_offsets  # noqa: E402,F401
 
 
 def token_code_rows(tokens, D):

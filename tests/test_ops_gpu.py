@@ -577,7 +577,7 @@ def test_linear_mx_epilogues_vs_dequantised_reference(epi):
 def test_layernorm_mx_vs_oracle(rows, D):
     """LayerNorm with MX output: dequantised result within half an e4m3 ulp (2^-4 relative to the block
     maximum) of the fp32 LayerNorm, and bitwise the oracle quantiser applied to the kernel's own fp32 result
-    on all but rounding-boundary elements."""
+    on all but rounding-boundary elements.  (Statistical; byte-exact on designed rows: tests/test_mx_exact_gpu.py.)"""
     from vdr import ops
 
     g = torch.Generator().manual_seed(rows + D)
@@ -598,7 +598,8 @@ def test_layernorm_mx_vs_oracle(rows, D):
 @pytest.mark.parametrize("variant", [0, 1, 2])
 def test_linear_mx_output_requantised(epi, variant):
     """fc1 epilogue writing MX-fp8 directly (the fc2 operand): dequantised output = oracle quantiser applied to
-    the exact epilogue result, up to elements whose fp32 value sits on a rounding boundary."""
+    the exact epilogue result, up to elements whose fp32 value sits on a rounding boundary.  (Statistical; byte-exact
+    on designed operands: tests/test_mx_exact_gpu.py.)"""
     from vdr import ops, _lib as L
 
     M, N, K = 333, 512, 768

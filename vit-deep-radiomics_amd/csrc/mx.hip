@@ -12,6 +12,21 @@
 //
 // Quantiser (restated on the CPU by the test suite): per block, e = ceil(log2(amax / 448)) clamped to
 // [-126, 126], scale byte = e + 127, payload = RNE_e4m3(x * 2^-e)  (|x| 2^-e <= 448: never saturates).
+//
+// Edge behaviour, pinned byte for byte by tests/test_mx_exact_gpu.py:
+//   exponent   amax * fl(1 / 448) in fp32 gives the exact ceiling for every bf16 maximum: 448 * 2^k has exponent k, one
+//              bf16 step above it (450 * 2^k) k + 1
+//   clamp      a maximum below 448 * 2^-126 (zero blocks, bf16-subnormal inputs) keeps the scale 2^-126 (byte 1): such
+//              inputs are multiplied by 2^126 and land on the e4m3 grid like any other; no input reaches the upper clamp
+//              except Inf
+//   subnormals scaled values below 2^-6 round to nearest even on the subnormal grid m * 2^-9; 2^-10 and below flush to a
+//              signed zero, anything above 2^-10 rounds up to 2^-9; -0 stays -0
+//   NaN        the block maximum is taken with fmaxf, which drops a NaN: the NaN element becomes the e4m3 NaN (it
+//              dequantises to NaN), the rest of its block is quantised as if the NaN were 0; a block of NaN only has byte 1
+//   Inf        the maximum is Inf, the exponent clamps to 126 (byte 253); Inf * 2^-126 = Inf converts to the e4m3 NaN
+//              (e4m3fn has no infinity), the rest of the block (|x| < 2^116) flushes to signed zeros
+// The same holds for ln_mx_kernel below and for the MX-out epilogue of gemm_epi.h (a NaN in a LayerNorm row makes its
+// mean, hence the whole row, NaN).
 #include "vdr_dev.h"
 #include "vdr_kernels.h"
 

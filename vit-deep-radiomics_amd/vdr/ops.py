@@ -133,38 +133,51 @@ class MxTensor:
         return y
 
 
-def mx_quantize(x: torch.Tensor) -> MxTensor:
-    """bf16 [rows, K] -> MX-fp8 (block 32 along K)."""
+def _mx_out(out, rows: int, K: int, device) -> MxTensor:
+    if out is None:
+        return MxTensor.empty(rows, K, device)
+    assert tuple(out.q.shape) == (rows, K) and out.q.is_contiguous() and out.q.dtype == torch.uint8
+    assert out.scales.numel() == int(L.load().vdr_mx_scale_bytes(rows, K)) and out.scales.is_contiguous()
+    return out
+
+
+def mx_quantize(x: torch.Tensor, out: MxTensor = None) -> MxTensor:
+    """bf16 [rows, K] -> MX-fp8 (block 32 along K); `out`: write into this MxTensor (scale bytes of no valid row keep
+    what they hold)."""
     lib = L.load()
     assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and x.shape[1] % 32 == 0
     rows, K = x.shape
-    t = MxTensor.empty(rows, K, x.device)
+    t = _mx_out(out, rows, K, x.device)
     L.check(lib.vdr_op_mx_quantize(x.data_ptr(), rows, K, t.q.data_ptr(), t.scales.data_ptr(), _s(x)))
     return t
 
 
-def layernorm_mx(x: torch.Tensor, gamma, beta, eps: float) -> MxTensor:
+def layernorm_mx(x: torch.Tensor, gamma, beta, eps: float, out: MxTensor = None) -> MxTensor:
     lib = L.load()
     assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous()
     rows, D = x.shape
-    t = MxTensor.empty(rows, D, x.device)
+    t = _mx_out(out, rows, D, x.device)
     L.check(lib.vdr_op_layernorm_mx(x.data_ptr(), gamma.float().contiguous().data_ptr(), beta.float().contiguous().data_ptr(),
                                     float(eps), rows, D, t.q.data_ptr(), t.scales.data_ptr(), _s(x)))
     return t
 
 
-def linear_mx(x: MxTensor, W: MxTensor, bias=None, resid=None, gamma=None, epilogue=L.EPI_BIAS, variant=0, mx_out=False):
-    """MX x [M,K] . MX W [N,K]^T on the block-scaled fp8 MFMA; returns bf16 [M,N] or (mx_out) an MxTensor."""
+def linear_mx(x: MxTensor, W: MxTensor, bias=None, resid=None, gamma=None, epilogue=L.EPI_BIAS, variant=0, mx_out=False,
+              out=None):
+    """MX x [M,K] . MX W [N,K]^T on the block-scaled fp8 MFMA; returns bf16 [M,N] or (mx_out) an MxTensor.  `out`: the
+    tensor (mx_out: MxTensor) to write into; it may be `resid` itself, as in the forward."""
     lib = L.load()
     M, K = x.shape
     N = W.shape[0]
     assert W.shape[1] == K
     No = N // 2 if epilogue == L.EPI_SWIGLU else N
     if mx_out:
-        out = MxTensor.empty(M, No, x.q.device)
+        out = _mx_out(out, M, No, x.q.device)
         yp, ysp = out.q.data_ptr(), out.scales.data_ptr()
     else:
-        out = torch.empty((M, No), dtype=torch.bfloat16, device=x.q.device)
+        if out is None:
+            out = torch.empty((M, No), dtype=torch.bfloat16, device=x.q.device)
+        assert tuple(out.shape) == (M, No) and out.dtype == torch.bfloat16 and out.is_contiguous()
         yp, ysp = out.data_ptr(), None
     L.check(lib.vdr_op_linear_mx(x.q.data_ptr(), x.scales.data_ptr(), W.q.data_ptr(), W.scales.data_ptr(), _p(bias),
                                  _p(resid), _p(gamma), yp, ysp, M, N, K, epilogue, variant, _s(x.q)))
