@@ -861,6 +861,51 @@ int vdr_op_pca_back_project(const void* x, int in_dtype, int64_t ld, int64_t ima
                             void* stream);
 int vdr_op_sym_topk(const float* a, int problems, int n, int k, float tol, int max_iter, void* work, float* values,
                     float* vectors, int32_t* iters, float* resid, void* stream);
+/* Lloyd's k-means over dense descriptor maps (csrc/kmeans.hip): the assignment step and the update step.  The loop, the
+ * initialisation and the restarts are the caller's (vdr.kmeans.fit).
+ * Operand of both: `problems` problems, each `imgs` images of t rows of d bf16 channels, R = imgs * t rows per problem; rows
+ *   ld elements apart, images image_stride elements apart, problems problem_stride elements apart: image q of problem p
+ *   starts at x + p * problem_stride + q * image_stride.  problem_stride = imgs * image_stride is the PCA ops' operand;
+ *   problem_stride = 0 is one map under `problems` sets of centroids (restarts).  A view into a wider buffer is read in
+ *   place.  k = 1..1024 clusters, k <= R; centroids [problems, k, d] fp32.
+ *   active: NULL, or [problems] int32 -- a problem whose entry is 0 is skipped by every launch and none of its outputs is
+ *   touched (a converged problem in a loop enqueued without host synchronisation).  `active` may be the `changed` array
+ *   itself.  work: vdr_kmeans_work_bytes(problems, imgs, t, d, k) bytes of device scratch, 16-byte aligned, enough for
+ *   either op.  No atomics; results are bitwise reproducible, and a problem's result depends neither on `problems` nor on
+ *   its position in the batch.  Inputs are finite by contract.
+ * vdr_op_kmeans_assign:  with x_i the rows and c_j the centroids,
+ *   c_hi = bf16_rn(c), c_lo = bf16_rn(c - float(c_hi)) per element (the subtraction is exact; what hi + lo leaves of c is at
+ *     most 2^-17 |c|);
+ *   s(i, j) = dot(x_i, c_hi_j) + dot(x_i, c_lo_j): ONE fp32 accumulation by bf16 MFMAs (the products are exact in fp32) over
+ *     16 channels at a time, channels ascending, per 16 channels the products with c_hi and then those with c_lo;
+ *   cc_j = sum_c c_jc^2 of the fp32 centroid, each square rounded to fp32; lane l of 64 sums the channels 8l .. 8l + 7,
+ *     512 + 8l .., ... ascending, then the 64 lane sums are folded by an xor butterfly (distance 32, 16, ... 1); xx_i the
+ *     same over the row's channels (its squares are exact);
+ *   h(i, j) = cc_j - 2 s(i, j), one rounding;  labels[p, i] = argmin_j h(i, j): comparison < on the value, then < on the
+ *     index;  min_dist[p, i] = max(xx_i + h(i, label), 0);
+ *   inertia[p] = sum_i min_dist[p, i] in col_mean's order (inside a chunk of VDR_COV_CHUNK rows sixteen interleaved sums,
+ *     rows r, r + 16, ... ascending, folded in ascending r; then the chunk sums ascending);
+ *   changed[p] = the number of rows whose label differs from the value found in labels[p, i] before the call: labels is read
+ *     and written, the caller initialises it (to -1: every row counts).
+ *   The R x k matrix is never written.  labels [problems, R] int32, min_dist [problems, R] fp32, inertia [problems] fp32,
+ *   changed [problems] int32.
+ * vdr_op_kmeans_update:  counts[p, j] = the number of rows with labels[p, i] == j (labels outside 0..k-1 are in no cluster);
+ *   sum[p, j, :] = sum over those rows of float(x_i), accumulated in fp32 by bf16 MFMAs against a one-hot operand (0 / 1:
+ *   exact) over 16 rows at a time, rows ascending within a chunk of VDR_KMEANS_CHUNK rows; the chunk sums are folded in
+ *   ascending chunk order.  The chunk length is part of the definition, not a launch heuristic.
+ *   centroids[p, j, :] = sum / float(counts), one IEEE division; a cluster with counts == 0 keeps its centroid's bits
+ *   (centroids is read and written).                          centroids [problems, k, d] fp32, counts [problems, k] int32
+ * Refused before the device is touched: VDR_ERR_UNSUPPORTED for d % 32 != 0 or k outside 1..1024; VDR_ERR_INVALID for null
+ * pointers (active excepted), non-positive problems, imgs, t or d, k > R, ld < d, negative strides, pointers or strides
+ * (ld, image_stride, problem_stride) that are not 16-byte aligned, problems * R above 2^31 - 1. */
+#define VDR_KMEANS_CHUNK 256
+size_t vdr_kmeans_work_bytes(int problems, int imgs, int t, int d, int k);
+int vdr_op_kmeans_assign(const void* x, int64_t ld, int64_t image_stride, int64_t problem_stride, int problems, int imgs, int t,
+                         int d, int k, const float* centroids, const int32_t* active, void* work, int32_t* labels,
+                         float* min_dist, float* inertia, int32_t* changed, void* stream);
+int vdr_op_kmeans_update(const void* x, int64_t ld, int64_t image_stride, int64_t problem_stride, int problems, int imgs, int t,
+                         int d, int k, const int32_t* labels, const int32_t* active, void* work, float* centroids,
+                         int32_t* counts, void* stream);
 /* ---- measurement ------------------------------------------------------------------------ */
 
 /* Kernel classes timed by the built-in HIP-event profiler. */

@@ -18,7 +18,7 @@
 //                chunk / R and columns past d are staged as zeros (every lane always reads: EXEC stays all ones).  The
 //                item's 128 x 128 partial goes to `work`; pca_cov_finish_kernel folds the chunks ascending, divides once,
 //                and writes (c1, c2) and (c2, c1) from the same value; of a diagonal tile only c1 <= c2 is read.
-//                LDS image: plain 256-byte rows, 16-byte chunk ch of row r at slot ch ^ (((r & 3) << 2) | ((r >> 2) & 3)).
+//                LDS image and the transposed read: tile_tr.h (shared with the update kernel of kmeans.hip).
 //   pca_project  pca_project_kernel: components and mean in LDS, one wave per row (16 rows per wave): a lane multiplies its
 //                16-byte chunks lane, lane + 64, ... in chunk order into k fp32 sums, then the xor butterfly.  The
 //                workgroup's min / max go to `work`; pca_minmax_kernel folds them per problem (min and max are exact in any
@@ -39,6 +39,7 @@
 #include <cstdint>
 
 #include "tile128.h"
+#include "tile_tr.h"
 #include "vdr_dev.h"
 #include "vdr_kernels.h"
 #include "../../include/vdr.h"
@@ -46,13 +47,10 @@
 namespace vdr {
 namespace {
 
-typedef __attribute__((address_space(3))) bf16x4 pca_lds_bf16x4;
-typedef const __attribute__((address_space(3))) char* pca_lds_cptr;
-
 constexpr int PCA_CHUNK = VDR_COV_CHUNK;    // rows per chunk: a constant of the definition
 constexpr int PCA_T = 128;                  // columns of a tile
-constexpr int PCA_STEP = 64;                // rows staged per step
-constexpr int PCA_IMG = PCA_STEP * 256;     // bytes of one staged tile
+constexpr int PCA_STEP = TR_STEP;           // rows staged per step (tile_tr.h)
+constexpr int PCA_IMG = TR_IMG;             // bytes of one staged tile
 constexpr int PCA_PROJ_ROWS = 64;           // rows of one projection workgroup
 static_assert(PCA_CHUNK % PCA_STEP == 0, "a chunk is whole steps");
 
@@ -130,9 +128,6 @@ __global__ __launch_bounds__(256) void pca_mean_finish_kernel(PcaArgs a, int pro
 }
 
 // ---- covariance -------------------------------------------------------------------------------------
-// byte offset of 16-byte chunk ch (0..15) of row `row` in a staged [rows][128 x bf16] tile
-VDR_DEV int pca_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
-
 template <bool BF16>
 struct PcaRaw;
 template <>
@@ -158,22 +153,6 @@ struct PcaRaw<false> {
   }
   __device__ __forceinline__ float get(int e) const { return e < 4 ? lo[e] : hi[e - 4]; }
 };
-
-// the operand of one 16-row k-step for the 32 columns at cb: column cb + (lane & 31), rows 4hh..4hh+3 | 8+4hh..8+4hh+3
-VDR_DEV bf16x8 pca_tr_read(pca_lds_cptr img, int ks, int cb, int lane) {
-  const int hh = lane >> 5, dg = (lane >> 4) & 1, tq = (lane & 15) >> 2, tp = lane & 3;
-  const int row = ks * 16 + 4 * hh + tq;
-  const int ch = (cb >> 3) + 2 * dg + (tp >> 1);
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((pca_lds_bf16x4*)(img + pca_off(row, ch) + 8 * (tp & 1)));
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((pca_lds_bf16x4*)(img + pca_off(row + 8, ch) + 8 * (tp & 1)));
-  bf16x8 f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    f[j] = lo[j];
-    f[4 + j] = hi[j];
-  }
-  return f;
-}
 
 template <bool BF16>
 __global__ __launch_bounds__(256) void pca_cov_kernel(PcaArgs a) {
@@ -229,7 +208,7 @@ __global__ __launch_bounds__(256) void pca_cov_kernel(PcaArgs a) {
         bf16x8 z;
 #pragma unroll
         for (int e = 0; e < 8; ++e) z[e] = (bf16_t)(rok && cok[s] ? raw[s][j].get(e) - mu[s][e] : 0.0f);
-        *reinterpret_cast<bf16x8*>(smem + s * PCA_IMG + pca_off(rl + 16 * j, ch)) = z;
+        *reinterpret_cast<bf16x8*>(smem + s * PCA_IMG + tr_off(rl + 16 * j, ch)) = z;
       }
     }
   };
@@ -242,8 +221,8 @@ __global__ __launch_bounds__(256) void pca_cov_kernel(PcaArgs a) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[m][n][e] = 0.0f;
 
-  const pca_lds_cptr imgA = (pca_lds_cptr)smem;
-  const pca_lds_cptr imgB = imgA + (diag ? 0 : PCA_IMG);
+  const tr_lds_cptr imgA = (tr_lds_cptr)smem;
+  const tr_lds_cptr imgB = imgA + (diag ? 0 : PCA_IMG);
   fetch(0);
 #pragma clang loop unroll(disable)
   for (int step = 0; step < nsteps; ++step) {
@@ -255,9 +234,9 @@ __global__ __launch_bounds__(256) void pca_cov_kernel(PcaArgs a) {
     for (int ks = 0; ks < PCA_STEP / 16; ++ks) {
       bf16x8 af[2], bf[2];
 #pragma unroll
-      for (int m = 0; m < 2; ++m) af[m] = pca_tr_read(imgA, ks, wr * 64 + m * 32, lane);
+      for (int m = 0; m < 2; ++m) af[m] = tr_read(imgA, ks, wr * 64 + m * 32, lane);
 #pragma unroll
-      for (int n = 0; n < 2; ++n) bf[n] = pca_tr_read(imgB, ks, wc * 64 + n * 32, lane);
+      for (int n = 0; n < 2; ++n) bf[n] = tr_read(imgB, ks, wc * 64 + n * 32, lane);
 #pragma unroll
       for (int m = 0; m < 2; ++m)
 #pragma unroll

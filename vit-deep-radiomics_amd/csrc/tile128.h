@@ -36,4 +36,30 @@ VDR_DEV void t128_mfma(const char* sx, int wr, int wc, int l31, int hh, f32x16 (
   }
 }
 
+// the four MFMA k-steps of a staged 64-column step with ONE A image against TWO B images accumulated into the same tile
+// (kmeans.hip: X against the hi and the lo half of the centroids): per 16-column k-step the products with b0, then those with b1
+VDR_DEV void t128_mfma_a2b(const char* sa, const char* sb0, const char* sb1, int wr, int wc, int l31, int hh, f32x16 (&acc)[2][2]) {
+  const int swz = (l31 >> 1) & 7;
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    const int off = ((2 * ks + hh) ^ swz) * 16;
+    bf16x8 af[2], b0[2], b1[2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m) af[m] = *reinterpret_cast<const bf16x8*>(sa + (wr * 64 + m * 32 + l31) * 128 + off);
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+      b0[n] = *reinterpret_cast<const bf16x8*>(sb0 + (wc * 64 + n * 32 + l31) * 128 + off);
+      b1[n] = *reinterpret_cast<const bf16x8*>(sb1 + (wc * 64 + n * 32 + l31) * 128 + off);
+    }
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[m], b0[n], acc[m][n], 0, 0, 0);
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[m], b1[n], acc[m][n], 0, 0, 0);
+  }
+}
+
 }  // namespace vdr

@@ -2828,6 +2828,53 @@ int vdr_op_sym_topk(const float* a, int problems, int n, int k, float tol, int m
   RUN_OP(launch_sym_topk(a, problems, n, k, tol, max_iter, work, values, vectors, iters, resid, (hipStream_t)stream), "sym_topk");
 }
 
+size_t vdr_kmeans_work_bytes(int problems, int imgs, int t, int d, int k) { return kmeans_work_bytes(problems, imgs, t, d, k); }
+
+// the operand checks shared by the two k-means ops (include/vdr.h); `ptrs`: the op's other required pointers
+static int kmeans_operand(const char* op, const void* x, int64_t ld, int64_t image_stride, int64_t problem_stride, int problems,
+                          int imgs, int t, int d, int k, const void* active, std::initializer_list<const void*> ptrs) {
+  static thread_local char msg[160];
+  const auto refuse = [&](int code, const char* what) {
+    snprintf(msg, sizeof msg, "%s: %s", op, what);
+    return fail(nullptr, code, msg);
+  };
+  bool null = !x;
+  for (const void* q : ptrs) null = null || !q;
+  if (null) return refuse(VDR_ERR_INVALID, "null pointer");
+  if (problems <= 0 || imgs <= 0 || t <= 0 || d <= 0) return refuse(VDR_ERR_INVALID, "problems, imgs, t and d must be positive");
+  if (d % 32 != 0) return refuse(VDR_ERR_UNSUPPORTED, "d must be a multiple of 32");
+  if (k < 1 || k > 1024) return refuse(VDR_ERR_UNSUPPORTED, "k must be 1..1024");
+  if (ld < d || image_stride < 0 || problem_stride < 0) return refuse(VDR_ERR_INVALID, "ld must be >= d, the strides >= 0");
+  if (!aligned16({x, active}) || !aligned16(ptrs) || ld % 8 || image_stride % 8 || problem_stride % 8)
+    return refuse(VDR_ERR_INVALID, "pointers, rows (ld), images and problems (the strides) must be 16-byte aligned");
+  const int64_t R = (int64_t)imgs * t;  // (each factor is a positive int: no overflow; R is bounded before the next product)
+  if (R > INT32_MAX || R * problems > INT32_MAX) return refuse(VDR_ERR_INVALID, "problems * R exceeds 2^31 - 1");
+  if (k > R) return refuse(VDR_ERR_INVALID, "k exceeds the R = imgs * t rows of a problem");
+  return VDR_OK;
+}
+
+int vdr_op_kmeans_assign(const void* x, int64_t ld, int64_t image_stride, int64_t problem_stride, int problems, int imgs, int t,
+                         int d, int k, const float* centroids, const int32_t* active, void* work, int32_t* labels, float* min_dist,
+                         float* inertia, int32_t* changed, void* stream) {
+  if (int rc = kmeans_operand("kmeans_assign", x, ld, image_stride, problem_stride, problems, imgs, t, d, k, active,
+                              {centroids, work, labels, min_dist, inertia, changed}))
+    return rc;
+  RUN_OP(launch_kmeans_assign(x, ld, image_stride, problem_stride, problems, imgs, t, d, k, centroids, active, work, labels,
+                              min_dist, inertia, changed, (hipStream_t)stream),
+         "kmeans_assign");
+}
+
+int vdr_op_kmeans_update(const void* x, int64_t ld, int64_t image_stride, int64_t problem_stride, int problems, int imgs, int t,
+                         int d, int k, const int32_t* labels, const int32_t* active, void* work, float* centroids, int32_t* counts,
+                         void* stream) {
+  if (int rc = kmeans_operand("kmeans_update", x, ld, image_stride, problem_stride, problems, imgs, t, d, k, active,
+                              {labels, work, centroids, counts}))
+    return rc;
+  RUN_OP(launch_kmeans_update(x, ld, image_stride, problem_stride, problems, imgs, t, d, k, labels, active, work, centroids, counts,
+                              (hipStream_t)stream),
+         "kmeans_update");
+}
+
 // ---- profiler ---------------------------------------------------------------------------------------
 int vdr_profile_enable(vdr_handle m, int on) {
   if (!m) return fail(m, VDR_ERR_INVALID, "null handle");

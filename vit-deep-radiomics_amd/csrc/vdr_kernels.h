@@ -344,6 +344,19 @@ size_t sym_topk_work_bytes(int problems, int n);
 hipError_t launch_sym_topk(const float* a, int problems, int n, int k, float tol, int max_iter, void* work, float* values,
                            float* vectors, int32_t* iters, float* resid, hipStream_t st);
 
+// Lloyd's k-means over bf16 descriptor maps (kmeans.hip; the definitions are vdr_op_kmeans_assign's and vdr_op_kmeans_update's
+// in include/vdr.h): `problems` problems of `imgs` images of t rows of d channels, rows ld, images image_stride and problems
+// problem_stride elements apart.  d % 32 == 0, 1 <= k <= min(1024, R); pointers and strides 16-byte aligned; active: null or
+// [problems] flags (0: the problem is skipped); work: kmeans_work_bytes(...) bytes.  Assign: three launches (norms, the fused
+// tile kernel, inertia / changed); update: two (partial sums, fold and division).
+size_t kmeans_work_bytes(int problems, int imgs, int t, int d, int k);
+hipError_t launch_kmeans_assign(const void* x, int64_t ld, int64_t image_stride, int64_t problem_stride, int problems, int imgs,
+                                int t, int d, int k, const float* centroids, const int32_t* active, void* work, int32_t* labels,
+                                float* min_dist, float* inertia, int32_t* changed, hipStream_t st);
+hipError_t launch_kmeans_update(const void* x, int64_t ld, int64_t image_stride, int64_t problem_stride, int problems, int imgs,
+                                int t, int d, int k, const int32_t* labels, const int32_t* active, void* work, float* centroids,
+                                int32_t* counts, hipStream_t st);
+
 // pos_embed resampling (pos_interp.hip): the patch rows of a position table from a gh0 x gw0 grid to gh x gw, bicubic
 // (A = -0.75, align_corners = False, border taps clamped), fp64 arithmetic, one rounding to fp32
 hipError_t launch_pos_interp(const float* pos, int gh0, int gw0, int D, float* out, int gh, int gw, hipStream_t s);

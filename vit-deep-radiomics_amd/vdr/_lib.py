@@ -132,6 +132,9 @@ SYMBOLS = {
     "vdr_op_gram": (_I, [_P, _I, _L, _L, _I, _I, _I, _P, _P, _P, _P]),
     "vdr_op_pca_back_project": (_I, [_P, _I, _L, _L, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P]),
     "vdr_op_sym_topk": (_I, [_P, _I, _I, _I, C.c_float, _I, _P, _P, _P, _P, _P, _P]),
+    "vdr_kmeans_work_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
+    "vdr_op_kmeans_assign": (_I, [_P, _L, _L, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vdr_op_kmeans_update": (_I, [_P, _L, _L, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vdr_profile_enable": (_I, [_P, _I]),
     "vdr_profile_mask": (_I, [_P, C.c_uint32]),
     "vdr_profile_read": (_I, [_P, C.POINTER(C.c_double), C.POINTER(_L), C.POINTER(C.c_double),

@@ -119,7 +119,9 @@ class Correspondences:
     nn12 [B, t] int32: for every patch of image 1 its cosine-nearest patch of image 2, sim12 [B, t] fp32 that similarity;
     nn21 / sim21 the reverse.  saliency1 / saliency2 [B, t] fp32: the last block's CLS attention over the patch columns,
     mean over the heads, min-max normalised per image.  mask [B, t] bool: best buddies (nn21[nn12[i]] == i) whose two
-    patches are both salient (> thresh).  grid = (gh, gw); stride and patch place a grid index in the image."""
+    patches are both salient (> thresh).  grid = (gh, gw); stride and patch place a grid index in the image.
+    desc1 / desc2 [B, t, d] bf16: the descriptors that were matched, kept with find_correspondences(keep_descriptors=True)
+    (None otherwise); points(select="kmeans") needs them."""
     nn12: torch.Tensor
     sim12: torch.Tensor
     nn21: torch.Tensor
@@ -130,16 +132,47 @@ class Correspondences:
     grid: "tuple[int, int]"
     stride: int
     patch: int
+    desc1: torch.Tensor = None
+    desc2: torch.Tensor = None
 
-    def points(self, b: int, num_pairs=None):
-        """The correspondences of pair b as two [k, 2] float tensors of (y, x) pixel centres (image 1, image 2), patch
-        (gy, gx) at gy * stride + patch / 2: the masked positions in order of descending sim12 (ties: ascending
-        position), cut to num_pairs."""
+    def buddy_descriptors(self, b: int):
+        """(positions [n_bb] of the masked buddies of pair b in image 1, ascending; their [n_bb, 2d] bf16 descriptors: the
+        L2-normalised (fp32, norm clamped at 1e-12) descriptor of the patch and of its buddy, each rounded once to bf16,
+        side by side)"""
+        if self.desc1 is None or self.desc2 is None:
+            raise ValueError("Correspondences: the descriptors were not kept; call find_correspondences(keep_descriptors=True)")
         idx = torch.nonzero(self.mask[b], as_tuple=False).flatten()
-        order = torch.sort(self.sim12[b][idx], descending=True, stable=True).indices
-        idx = idx[order]
-        if num_pairs is not None:
-            idx = idx[: int(num_pairs)]
+        d1 = self.desc1[b][idx].float()
+        d2 = self.desc2[b][self.nn12[b][idx].long()].float()
+        norm = torch.nn.functional.normalize
+        return idx, torch.cat([norm(d1, dim=-1, eps=1e-12).to(torch.bfloat16), norm(d2, dim=-1, eps=1e-12).to(torch.bfloat16)], dim=-1)
+
+    def points(self, b: int, num_pairs=None, select: str = "similarity"):
+        """The correspondences of pair b as two [k, 2] float tensors of (y, x) pixel centres (image 1, image 2), patch
+        (gy, gx) at gy * stride + patch / 2.
+        select="similarity": the masked positions in order of descending sim12 (ties: ascending position), cut to num_pairs.
+        select="kmeans" (dino-vit-features' selection; needs num_pairs and the kept descriptors): the masked buddies'
+        descriptors (buddy_descriptors) are clustered by vdr.kmeans.fit(k=min(num_pairs, n_bb), init="maximin"); from every
+        non-empty cluster the buddy with the largest rank saliency1 * saliency2[nn12] is taken (lowest position on a tie),
+        and the chosen ones come in descending order of that rank (ties: ascending position)."""
+        if select not in ("similarity", "kmeans"):
+            raise ValueError(f"points: select must be 'similarity' or 'kmeans', got {select!r}")
+        if select == "kmeans":
+            if num_pairs is None or int(num_pairs) < 1:
+                raise ValueError("points: select='kmeans' needs num_pairs >= 1")
+            idx, desc = self.buddy_descriptors(b)
+            if idx.numel():
+                from . import kmeans
+                k = min(int(num_pairs), int(idx.numel()), 1024)
+                labels = kmeans.fit(desc, k, init="maximin").labels[0]
+                rank = self.saliency1[b][idx] * self.saliency2[b][self.nn12[b][idx].long()]
+                idx = idx[select_by_cluster(labels, rank, k)]
+        else:
+            idx = torch.nonzero(self.mask[b], as_tuple=False).flatten()
+            order = torch.sort(self.sim12[b][idx], descending=True, stable=True).indices
+            idx = idx[order]
+            if num_pairs is not None:
+                idx = idx[: int(num_pairs)]
         gw = self.grid[1]
 
         def centres(i):
@@ -148,6 +181,32 @@ class Correspondences:
             return torch.stack((y, x), dim=1).float() * self.stride + self.patch / 2
 
         return centres(idx), centres(self.nn12[b][idx])
+
+
+def select_by_cluster(labels: torch.Tensor, rank: torch.Tensor, k: int) -> torch.Tensor:
+    """labels [n] in 0..k-1, rank [n] -> the positions (int64) of the top-ranked member of every non-empty cluster, the lowest
+    position on a tie, in descending order of rank (ties: ascending position).  Pure torch; CPU tensors work too."""
+    n = labels.shape[0]
+    pos = torch.arange(n, device=labels.device)
+    member = labels.long().unsqueeze(0) == torch.arange(k, device=labels.device).unsqueeze(1)  # [k, n]
+    best = torch.where(member, rank.unsqueeze(0), torch.full_like(rank, float("-inf")).unsqueeze(0)).max(dim=1, keepdim=True).values
+    first = torch.where(member & (rank.unsqueeze(0) == best), pos, n).min(dim=1).values
+    chosen = first[first < n]
+    chosen = chosen.sort().values
+    return chosen[torch.sort(rank[chosen], descending=True, stable=True).indices]
+
+
+@dataclass
+class Cosegmentation:
+    """Result of VitDescriptorModel.cosegment for B images on a gh x gw grid.  labels [B, gh, gw] int32: every patch's cluster
+    of the one joint k-means over all B maps; salient [k] bool: the clusters voted salient; masks [B, gh, gw] bool: the
+    patches in a salient cluster; saliency [B, gh, gw] fp32: the last block's CLS attention, head mean, min-max normalised
+    per image; kmeans: the fit (vdr.kmeans.KMeans, one problem)."""
+    labels: torch.Tensor
+    salient: torch.Tensor
+    masks: torch.Tensor
+    saliency: torch.Tensor
+    kmeans: object
 
 
 def minmax_normalise(a: torch.Tensor) -> torch.Tensor:
@@ -380,7 +439,7 @@ class VitDescriptorModel:
         return got.unsqueeze(1)
 
     def find_correspondences(self, x1: torch.Tensor, x2: torch.Tensor, layer=None, facet: str = "key", bin: bool = True,
-                             hierarchy: int = 2, thresh: float = 0.05) -> Correspondences:
+                             hierarchy: int = 2, thresh: float = 0.05, keep_descriptors: bool = False) -> Correspondences:
         """dino-vit-features' point correspondences: mutual cosine nearest neighbours ("best buddies") between the
         descriptors of x1[b] and x2[b], x1 and x2 [B, 3, H, W] of one shape, kept where both patches are salient.
         One forward over cat([x1, x2]) (vdr_forward_facets) writes the bf16 `facet` descriptors of block `layer` (None: the
@@ -388,7 +447,9 @@ class VitDescriptorModel:
         last block; vdr.ops.nn_cosine then matches the two halves of that one buffer in place -- the t x t similarity
         matrix is never materialised.  The input size, patch stride and dynamic_size in force apply.  Deviations from
         upstream: the saliency averages all heads (upstream: four chosen heads of dino_vits8), and Correspondences.points
-        ranks by similarity (upstream: k-means over the buddies' descriptors, ranked by saliency).  Refusals (ValueError,
+        ranks by similarity unless asked for upstream's selection (select="kmeans": k-means over the buddies' descriptors,
+        ranked by saliency; it needs keep_descriptors=True, which keeps views of the descriptor buffer in the result).
+        Refusals (ValueError,
         before any device work): extract_descriptors' (unknown facet, hierarchy outside 1..3, a layer out of range, SAM /
         token / post-LN / block-less models), a model without a CLS token, x1 and x2 of different shapes."""
         h = self._descriptor_args(layer, facet, bin, False, hierarchy)
@@ -408,8 +469,52 @@ class VitDescriptorModel:
         sal = minmax_normalise(att[:, 0, self.cfg.n_prefix:])
         sal1, sal2 = sal[:B], sal[B:]
         mask = ops.best_buddies(nn12, nn21) & (sal1 > thresh) & (torch.gather(sal2, 1, nn12.long()) > thresh)
-        return Correspondences(nn12, sim12, nn21, sim21, sal1, sal2, mask, tuple(self.engine.grid), int(self.engine.patch_stride),
-                               int(self.cfg.patch))
+        res = Correspondences(nn12, sim12, nn21, sim21, sal1, sal2, mask, tuple(self.engine.grid), int(self.engine.patch_stride),
+                              int(self.cfg.patch))
+        if keep_descriptors:
+            res.desc1, res.desc2 = desc[:B], desc[B:]
+        return res
+
+    def cosegment(self, x: torch.Tensor, k=None, layer=None, facet: str = "key", bin: bool = False, hierarchy: int = 2,
+                  thresh: float = 0.065, votes_percentage: float = 75, elbow: float = 0.975, **fit_kwargs) -> Cosegmentation:
+        """dino-vit-features' co-segmentation of the B images x [B, 3, H, W]: one forward (vdr_forward_facets) gives the bf16
+        `facet` descriptors of block `layer` (None: the last block), log-binned at `hierarchy` when bin, and the head-mean
+        CLS attention of the last block, min-max normalised per image as in find_correspondences; the rows are L2-normalised
+        in fp32 and rounded once to bf16; ONE joint k-means over all B maps (vdr.kmeans.fit(joint=True); k=None: the elbow
+        sweep vdr.kmeans.elbow(ratio=elbow)); then the saliency vote (vdr.kmeans.vote): a cluster is salient when in at least
+        votes_percentage % of the images the mean saliency of its patches exceeds thresh.  fit_kwargs go to the fit (init,
+        n_init, max_iter, sync_every, seed).  The input size, patch stride and dynamic_size in force apply.
+        Deviations from upstream: no GrabCut refinement of the masks, no subsampling of the descriptors before the
+        clustering, no part co-segmentation (the second k-means over the foreground); the saliency averages all heads; the
+        k-means is this library's Lloyd with a deterministic maximin start (upstream: faiss with random restarts); the elbow
+        rule is upstream's as remembered (vdr.kmeans.elbow), not pinned against its code.
+        Refusals (ValueError, before any device work): find_correspondences' own, k outside 1..1024 or above B * t."""
+        h = self._descriptor_args(layer, facet, bin, False, hierarchy)
+        if not self.cfg.has_cls:
+            raise ValueError("cosegment: the saliency is the CLS row's attention; the model has no CLS token")
+        if x.dim() != 4:
+            raise ValueError(f"cosegment: x must be [B, 3, H, W], got {tuple(x.shape)}")
+        if k is not None and (isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 1024):
+            raise ValueError(f"cosegment: k must be None or an integer in 1..1024, got {k!r}")
+        from . import kmeans
+        i = self.cfg.layers - 1 if layer is None else int(layer)
+        self._adopt(x)
+        B = x.shape[0]
+        gh, gw = self.engine.grid
+        if k is not None and int(k) > B * gh * gw:
+            raise ValueError(f"cosegment: k = {k} exceeds the {B * gh * gw} patches of the {B} images")
+        (desc,), _, (att,) = self.engine.forward_descriptors(x.to(self.device), [FacetOut(i, facet, h, False, torch.bfloat16)],
+                                                             maps=[AttnMap(self.cfg.layers - 1, 1, True)])
+        sal = minmax_normalise(att[:, 0, self.cfg.n_prefix:])
+        rows = torch.nn.functional.normalize(desc.float(), dim=-1, eps=1e-12).to(torch.bfloat16)
+        if k is None:
+            fit = kmeans.elbow(rows, ratio=float(elbow), joint=True, **fit_kwargs)
+        else:
+            fit = kmeans.fit(rows, int(k), joint=True, **fit_kwargs)
+        labels = fit.labels.reshape(B, gh * gw)
+        salient = kmeans.vote(labels, sal, fit.k, float(thresh), float(votes_percentage))
+        masks = salient[labels.long()]
+        return Cosegmentation(labels.reshape(B, gh, gw), salient, masks.reshape(B, gh, gw), sal.reshape(B, gh, gw), fit)
 
     def pca_descriptors(self, x: torch.Tensor, n_components: int = 3, layer=None, facet=None, joint: bool = False,
                         remove_bg: bool = False) -> torch.Tensor:

@@ -565,6 +565,138 @@ def pca_back_project(x: torch.Tensor, mean: torch.Tensor, u: torch.Tensor, value
     return comps
 
 
+KMEANS_CHUNK = 256  # VDR_KMEANS_CHUNK (include/vdr.h)
+KMEANS_MAX_K = 1024
+
+
+class KmeansOperand:
+    """A descriptor map as the two k-means ops read it: the bf16 tensor kept alive, its strides in elements and its shape
+    (problems, imgs, t, d); R = imgs * t rows per problem.  Built once per fit by kmeans_operand."""
+
+    def __init__(self, x, ld, image_stride, problem_stride, problems, imgs, t, d):
+        self.x, self.ld, self.image_stride, self.problem_stride = x, ld, image_stride, problem_stride
+        self.problems, self.imgs, self.t, self.d = problems, imgs, t, d
+        self.R = imgs * t
+
+    def work(self, k: int) -> torch.Tensor:
+        n = L.load().vdr_kmeans_work_bytes(self.problems, self.imgs, self.t, self.d, int(k))
+        return torch.empty((n,), dtype=torch.uint8, device=self.x.device)
+
+
+def kmeans_operand(x: torch.Tensor, joint: bool = False, op: str = "kmeans") -> KmeansOperand:
+    """The host-side refusals of a k-means operand and its description for the library.  x [P, t, d]: one problem per image,
+    or the P * t rows of all images as one problem with joint=True; x [problems, imgs, t, d]: as it says (an expand()ed
+    leading dimension, stride 0, is one map under many sets of centroids).  bf16, or fp32 rounded once to bf16; read where
+    it lies when its channels are contiguous and its rows, images and problems 16-byte aligned (a column slice of a wider
+    buffer, rows behind a prefix), copied once otherwise.  d must be a multiple of 32."""
+    if isinstance(x, KmeansOperand):
+        return x
+    if not isinstance(x, torch.Tensor) or x.dim() not in (3, 4) or x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{op}: x must be a [P, t, d] or [problems, imgs, t, d] float32 or bfloat16 tensor")
+    if not x.is_cuda:
+        raise TypeError(f"{op}: x must live on the HIP device")
+    if x.dim() == 3:
+        x = x.unsqueeze(0) if joint else x.unsqueeze(1)
+    elif joint:
+        raise ValueError(f"{op}: joint=True goes with a [P, t, d] operand")
+    problems, imgs, t, d = x.shape
+    if min(problems, imgs, t, d) <= 0:
+        raise ValueError(f"{op}: empty operand")
+    if d % 32:
+        raise ValueError(f"{op}: d must be a multiple of 32, got {d}")
+    if problems * imgs * t > 2 ** 31 - 1:
+        raise ValueError(f"{op}: problems * imgs * t exceeds 2^31 - 1")
+    if x.dtype != torch.bfloat16:
+        x = x.to(torch.bfloat16)  # (fp32: rounded once)
+    ok = x.stride(3) == 1 and (t == 1 or (x.stride(2) >= d and x.stride(2) % 8 == 0)) and \
+        (imgs == 1 or (x.stride(1) >= 0 and x.stride(1) % 8 == 0)) and \
+        (problems == 1 or (x.stride(0) >= 0 and x.stride(0) % 8 == 0)) and x.data_ptr() % 16 == 0
+    if not ok:
+        x = x.contiguous()
+    return KmeansOperand(x, x.stride(2) if t > 1 else d, x.stride(1) if imgs > 1 else 0, x.stride(0) if problems > 1 else 0,
+                         problems, imgs, t, d)
+
+
+def _kmeans_k(o: KmeansOperand, centroids, op: str) -> int:
+    if not isinstance(centroids, torch.Tensor) or centroids.dim() != 3 or centroids.dtype != torch.float32 or \
+            centroids.shape[0] != o.problems or centroids.shape[2] != o.d:
+        raise ValueError(f"{op}: centroids must be a float32 tensor of shape ({o.problems}, k, {o.d}), got "
+                         f"{tuple(centroids.shape) if isinstance(centroids, torch.Tensor) else type(centroids).__name__}")
+    if centroids.device != o.x.device or not centroids.is_contiguous():
+        raise ValueError(f"{op}: centroids must be contiguous and on x's device")
+    k = int(centroids.shape[1])
+    if not 1 <= k <= KMEANS_MAX_K:
+        raise ValueError(f"{op}: k must be 1..{KMEANS_MAX_K}, got {k}")
+    if k > o.R:
+        raise ValueError(f"{op}: k = {k} exceeds the {o.R} rows of a problem")
+    return k
+
+
+def _kmeans_ints(v, name: str, op: str, shape, dev):
+    if not isinstance(v, torch.Tensor) or v.dtype != torch.int32 or tuple(v.shape) != tuple(shape) or v.device != dev or \
+            not v.is_contiguous():
+        raise ValueError(f"{op}: {name} must be a contiguous int32 tensor of shape {tuple(shape)} on x's device")
+    return v
+
+
+def kmeans_assign(x, centroids: torch.Tensor, labels=None, joint: bool = False, active=None, out=None, work=None):
+    """The assignment step of Lloyd's k-means (vdr_op_kmeans_assign): x as kmeans_operand takes it, centroids [problems, k, d]
+    fp32.  Returns (labels [problems, R] int32, min_dist [problems, R] fp32, inertia [problems] fp32, changed [problems]
+    int32): the nearest centroid of every row by h = cc - 2 x.c with the centroid split into two bf16 operands, the lowest
+    index on a tie; changed counts the rows whose label differs from the one passed in `labels` (None: every row counts;
+    a given tensor is updated in place and returned).  active [problems] int32: problems whose flag is 0 are left
+    untouched.  out: (min_dist, inertia, changed) to write into.  The R x k matrix is never materialised; the exact
+    arithmetic is stated in include/vdr.h."""
+    o = kmeans_operand(x, joint, "kmeans_assign")
+    k = _kmeans_k(o, centroids, "kmeans_assign")
+    dev = o.x.device
+    if labels is None:
+        labels = torch.full((o.problems, o.R), -1, dtype=torch.int32, device=dev)
+    else:
+        _kmeans_ints(labels, "labels", "kmeans_assign", (o.problems, o.R), dev)
+    if active is not None:
+        _kmeans_ints(active, "active", "kmeans_assign", (o.problems,), dev)
+    if out is None:
+        min_dist = torch.empty((o.problems, o.R), dtype=torch.float32, device=dev)
+        inertia = torch.empty((o.problems,), dtype=torch.float32, device=dev)
+        changed = torch.empty((o.problems,), dtype=torch.int32, device=dev)
+    else:
+        min_dist, inertia, changed = out
+    lib = L.load()
+    if work is None:
+        work = o.work(k)
+    L.check(lib.vdr_op_kmeans_assign(o.x.data_ptr(), o.ld, o.image_stride, o.problem_stride, o.problems, o.imgs, o.t, o.d, k,
+                                     centroids.data_ptr(), _p(active), work.data_ptr(), labels.data_ptr(), min_dist.data_ptr(),
+                                     inertia.data_ptr(), changed.data_ptr(), _s(o.x)))
+    return labels, min_dist, inertia, changed
+
+
+def kmeans_update(x, labels: torch.Tensor, centroids: torch.Tensor, joint: bool = False, active=None, inplace: bool = False,
+                  counts=None, work=None):
+    """The update step of Lloyd's k-means (vdr_op_kmeans_update): x as kmeans_operand takes it, labels [problems, R] int32,
+    centroids [problems, k, d] fp32 (the previous ones).  Returns (centroids, counts [problems, k] int32): every centroid
+    the fp32 sum of its rows -- bf16 MFMAs against a one-hot operand built on chip, in chunks of 256 rows -- divided once
+    by its count; an empty cluster keeps its previous centroid's bits.  inplace=True writes into `centroids` itself.
+    active [problems] int32: problems whose flag is 0 are left untouched (include/vdr.h)."""
+    o = kmeans_operand(x, joint, "kmeans_update")
+    k = _kmeans_k(o, centroids, "kmeans_update")
+    dev = o.x.device
+    _kmeans_ints(labels, "labels", "kmeans_update", (o.problems, o.R), dev)
+    if active is not None:
+        _kmeans_ints(active, "active", "kmeans_update", (o.problems,), dev)
+    if not inplace:
+        centroids = centroids.clone()
+    if counts is None:
+        counts = torch.zeros((o.problems, k), dtype=torch.int32, device=dev)
+    lib = L.load()
+    if work is None:
+        work = o.work(k)
+    L.check(lib.vdr_op_kmeans_update(o.x.data_ptr(), o.ld, o.image_stride, o.problem_stride, o.problems, o.imgs, o.t, o.d, k,
+                                     labels.data_ptr(), _p(active), work.data_ptr(), centroids.data_ptr(), counts.data_ptr(),
+                                     _s(o.x)))
+    return centroids, counts
+
+
 def patch_embed(images, weight, bias, p, pos=None, row_stride=None, row_offset=0, out=None):
     """images [B,C,H,H] fp32/bf16; weight [D,C,p,p] (any float dtype); returns bf16 [B*row_stride, D]."""
     lib = L.load()
