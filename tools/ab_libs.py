@@ -1,17 +1,22 @@
 #!/usr/bin/env python3
 """Kernel-level A/B of two builds of libvdr.so in ONE process, interleaved rounds (guide rule 24): both libraries are
 dlopen'ed side by side and the attention ops / vdr_op_linear_packed are called through ctypes on the same tensors.
-   python tools/ab_libs.py path/to/libA.so[:variant] path/to/libB.so[:variant] [attention|gemm]
+   python tools/ab_libs.py path/to/libA.so[:variant] path/to/libB.so[:variant] [attention|gemm|descriptors]
 (":variant" = the tile variant handed to vdr_op_linear_packed by that side, e.g. the same library twice as lib.so:0 lib.so:31)
 attention: first a bitwise pass (torch.equal of the two libraries' outputs) over the smallest shapes that reach every
 instantiation of the fused attention kernels, then the timing; exit status 1 if any output differs.  For the spread of
-the timing run a copy of library A against it (a second path: the same path is the same handle)."""
+the timing run a copy of library A against it (a second path: the same path is the same handle).
+descriptors: the same two passes for the descriptor-analysis ops (nn_cosine, the PCA ops, the Gram side, k-means): bitwise on the
+smallest shapes that reach every path (the shapes of the exact tests), every element of every output compared; timed on the shapes of
+tools/correspondence_bench.py, pca_bench.py, pca_topk_bench.py and kmeans_bench.py."""
 import ctypes as C
 import sys
 
 import torch
 
-_P, _I = C.c_void_p, C.c_int
+_P, _I, _L = C.c_void_p, C.c_int, C.c_int64
+F32, BF16 = 0, 1  # vdr_dtype
+GRAM_CHUNK = 256  # VDR_GRAM_CHUNK
 
 
 def load(path):
@@ -22,6 +27,20 @@ def load(path):
     lib.vdr_op_attention_relpos.argtypes = [_P, _P, _P, _P, _P, _I, _I, _I, _P]
     lib.vdr_op_linear_packed.argtypes = [_P] * 6 + [C.c_int64, _I, _I, _I, _I, _P]
     lib.vdr_op_pack_linear_weight.argtypes = [_P, _I, _I, _P, _P]
+    for f, n in (("vdr_nn_cosine_work_bytes", 3), ("vdr_pca_work_bytes", 4), ("vdr_pca_topk_work_bytes", 4), ("vdr_kmeans_work_bytes", 5)):
+        getattr(lib, f).argtypes, getattr(lib, f).restype = [_I] * n, C.c_size_t
+    lib.vdr_op_nn_cosine.argtypes = [_P, _L, _L, _I, _P, _L, _L, _I, _I, _I] + [_P] * 6
+    pca = [_P, _I, _L, _L, _I, _I, _I, _I]  # x, in_dtype, ld, image_stride, problems, imgs, t, d
+    lib.vdr_op_col_mean.argtypes = pca + [_P, _P, _P]
+    lib.vdr_op_covariance.argtypes = pca + [_P, _P, _P, _P]
+    lib.vdr_op_pca_project.argtypes = pca + [_P, _P, _I, _I, _P, _P, _P, _P]
+    side = [_P, _I, _L, _L, _I, _I, _I]     # x, in_dtype, ld, image_stride, problems, t, d
+    lib.vdr_op_col_mean_any.argtypes = side + [_P, _P, _P]
+    lib.vdr_op_gram.argtypes = side + [_P, _P, _P, _P]
+    lib.vdr_op_pca_back_project.argtypes = side + [_P, _P, _P, _I, _P, _P, _P]
+    km = [_P, _L, _L, _L, _I, _I, _I, _I, _I]  # x, ld, image_stride, problem_stride, problems, imgs, t, d, k
+    lib.vdr_op_kmeans_assign.argtypes = km + [_P] * 8
+    lib.vdr_op_kmeans_update.argtypes = km + [_P] * 6
     return lib
 
 
@@ -73,6 +92,181 @@ def attention_equal(libs, st):
     return bad
 
 
+# ---- descriptor ops -------------------------------------------------------------------------------------------------
+# A case is (name, run(lib, keep=None) -> outputs): run calls the ops and returns every output tensor.  keep is None (the bitwise
+# pass): fresh outputs, floats prefilled with NaN, int32 with INT32_MIN, the scratch with 0xFF bytes; outputs that an op also reads
+# (labels, centroids) start from the value the op's contract asks for instead.  keep is a list (the timing): the buffers are made
+# on the first call, kept in it and shared by both libraries, and nothing is prefilled again.
+_INT_FILL = -2 ** 31
+
+
+class _Bufs:
+    def __init__(self, keep):
+        self.keep, self.i = keep, 0
+
+    def get(self, make):
+        if self.keep is None:
+            return make()
+        if self.i == len(self.keep):
+            self.keep.append(make())
+        self.i += 1
+        return self.keep[self.i - 1]
+
+    def out(self, *shape, dtype=torch.float32, value=None):
+        if value is None:
+            value = float("nan") if dtype.is_floating_point else _INT_FILL
+        return self.get(lambda: torch.full(shape, value, device="cuda", dtype=dtype))
+
+    def work(self, nbytes):
+        return self.get(lambda: torch.full((nbytes,), 255, device="cuda", dtype=torch.uint8))
+
+
+def _map(P, rows, d, ld, bf16, seed):
+    """[P, rows, ld] with a channel offset (the centring has something to remove); the ld - d padding columns are NaN"""
+    gen = torch.Generator(device="cuda").manual_seed(seed)
+    x = torch.full((P, rows, ld), float("nan"), device="cuda")
+    x[..., :d] = torch.randn(P, rows, d, device="cuda", generator=gen) * 2 + torch.randn(d, device="cuda", generator=gen)
+    return x.to(torch.bfloat16 if bf16 else torch.float32)
+
+
+def nn_case(st, P, tx, ty, d, cols=True, pad=0):
+    gen = torch.Generator(device="cuda").manual_seed(tx + ty + d)
+    x = torch.randn(P, tx, d + pad, device="cuda", generator=gen).bfloat16()
+    y = torch.randn(P, ty, d + pad, device="cuda", generator=gen).bfloat16()
+
+    def run(lib, keep=None):
+        o = _Bufs(keep)
+        work = o.work(lib.vdr_nn_cosine_work_bytes(P, tx, ty))
+        rs, ri = o.out(P, tx), o.out(P, tx, dtype=torch.int32)
+        cs, ci = (o.out(P, ty), o.out(P, ty, dtype=torch.int32)) if cols else (None, None)
+        assert lib.vdr_op_nn_cosine(x.data_ptr(), d + pad, tx * (d + pad), tx, y.data_ptr(), d + pad, ty * (d + pad), ty, P, d, work.data_ptr(),
+                                    rs.data_ptr(), ri.data_ptr(), cs.data_ptr() if cols else None, ci.data_ptr() if cols else None, st) == 0
+        return [rs, ri] + ([cs, ci] if cols else [])
+    return f"nn_cosine P{P} tx{tx} ty{ty} d{d} cols{int(cols)}", run
+
+
+def pca_case(st, P, imgs, t, d, bf16, ops=("mean", "cov", "proj"), pad=0):
+    """col_mean -> covariance -> pca_project (k = 3, scaled) on `P` problems of `imgs` images; `ops` picks what is (re)run"""
+    ld, R = d + pad, imgs * t
+    x = _map(P * imgs, t, d, ld, bf16, t + d + imgs)
+    comps = torch.randn(P, 3, d, device="cuda", generator=torch.Generator(device="cuda").manual_seed(d))
+    mean0 = x[..., :d].float().reshape(P, R, d).mean(1).contiguous()  # the ops after col_mean read this one when col_mean is not run
+
+    def run(lib, keep=None):
+        a = (x.data_ptr(), BF16 if bf16 else F32, ld, t * ld, P, imgs, t, d)
+        o = _Bufs(keep)
+        work = o.work(lib.vdr_pca_work_bytes(P, imgs, t, d))
+        outs, mean = [], mean0
+        if "mean" in ops:
+            mean = o.out(P, d)
+            assert lib.vdr_op_col_mean(*a, work.data_ptr(), mean.data_ptr(), st) == 0
+            outs.append(mean)
+        if "cov" in ops and R >= 2:
+            cov = o.out(P, d, d)
+            assert lib.vdr_op_covariance(*a, mean.data_ptr(), work.data_ptr(), cov.data_ptr(), st) == 0
+            outs.append(cov)
+        if "proj" in ops:
+            proj, mm = o.out(P, R, 3), o.out(P, 2)
+            assert lib.vdr_op_pca_project(*a, mean.data_ptr(), comps.data_ptr(), 3, 1, work.data_ptr(), proj.data_ptr(), mm.data_ptr(), st) == 0
+            outs += [proj, mm]
+        return outs
+    return f"pca {'+'.join(ops)} P{P} imgs{imgs} t{t} d{d} {'bf16' if bf16 else 'fp32'}", run
+
+
+def gram_case(st, P, t, d, bf16, ops=("mean", "gram", "back"), pad=0):
+    """col_mean_any -> gram -> pca_back_project (k = 3; the last component's value is 0: written as zeros)"""
+    ld = d + pad
+    x = _map(P, t, d, ld, bf16, t + d)
+    gen = torch.Generator(device="cuda").manual_seed(t)
+    u = torch.randn(P, 3, t, device="cuda", generator=gen)
+    values = torch.tensor([[2.0, 1.0, 0.0]] * P, device="cuda")
+    mean0 = x[..., :d].float().mean(1).contiguous()
+
+    def run(lib, keep=None):
+        a = (x.data_ptr(), BF16 if bf16 else F32, ld, t * ld, P, t, d)
+        o = _Bufs(keep)
+        work = o.work(lib.vdr_pca_topk_work_bytes(P, t, d, 8))
+        outs, mean = [], mean0
+        if "mean" in ops:
+            mean = o.out(P, d)
+            assert lib.vdr_op_col_mean_any(*a, work.data_ptr(), mean.data_ptr(), st) == 0
+            outs.append(mean)
+        if "gram" in ops:
+            g = o.out(P, t, t)
+            assert lib.vdr_op_gram(*a, mean.data_ptr(), work.data_ptr(), g.data_ptr(), st) == 0
+            outs.append(g)
+        if "back" in ops:
+            comps = o.out(P, 3, d)
+            assert lib.vdr_op_pca_back_project(*a, mean.data_ptr(), u.data_ptr(), values.data_ptr(), 3, work.data_ptr(), comps.data_ptr(), st) == 0
+            outs.append(comps)
+        return outs
+    return f"gram {'+'.join(ops)} P{P} t{t} d{d} {'bf16' if bf16 else 'fp32'}", run
+
+
+def kmeans_case(st, P, imgs, t, d, k, ops=("assign", "update")):
+    """assign from labels = -1 (every row counts as changed), update from the centroids the assign read; the update alone runs on
+    labels r % k"""
+    R = imgs * t
+    gen = torch.Generator(device="cuda").manual_seed(R + d + k)
+    x = torch.randn(P, R, d, device="cuda", generator=gen).bfloat16()
+    c0 = x[:, :k].float().contiguous()
+    lab0 = (torch.arange(R, device="cuda", dtype=torch.int32) % k).repeat(P, 1).contiguous()
+
+    def run(lib, keep=None):
+        a = (x.data_ptr(), d, t * d, R * d, P, imgs, t, d, k)
+        o = _Bufs(keep)
+        work = o.work(lib.vdr_kmeans_work_bytes(P, imgs, t, d, k))
+        outs, labels = [], lab0
+        if "assign" in ops:
+            labels = o.out(P, R, dtype=torch.int32, value=-1)
+            md, inertia, changed = o.out(P, R), o.out(P), o.out(P, dtype=torch.int32)
+            assert lib.vdr_op_kmeans_assign(*a, c0.data_ptr(), None, work.data_ptr(), labels.data_ptr(), md.data_ptr(), inertia.data_ptr(),
+                                            changed.data_ptr(), st) == 0
+            outs += [labels, md, inertia, changed]
+        if "update" in ops:
+            cent, counts = o.get(c0.clone), o.out(P, k, dtype=torch.int32)
+            assert lib.vdr_op_kmeans_update(*a, labels.data_ptr(), None, work.data_ptr(), cent.data_ptr(), counts.data_ptr(), st) == 0
+            outs += [cent, counts]
+        return outs
+    return f"kmeans {'+'.join(ops)} P{P} imgs{imgs} t{t} d{d} k{k}", run
+
+
+def descriptors_equal(libs, st):
+    """the shapes of the exact tests (tests/test_nn_cosine_gpu.py, test_pca_gpu.py, test_pca_topk_gpu.py, test_kmeans_gpu.py)"""
+    cases = [nn_case(st, 2, tx, ty, d, cols, pad=8) for (tx, ty) in ((1, 1), (127, 129), (130, 257)) for d in (32, 96, 448) for cols in (True, False)]
+    cases += [nn_case(st, 520, 17, 19, 32)]  # more work items than the split aims for: one split
+    cases += [pca_case(st, 2, imgs, t, d, bf16, pad=32) for t in (2, 16, 17, 1025, 2049) for d in (32, 160, 288) for bf16 in (True, False)
+              for imgs in (1, 2)]
+    cases += [gram_case(st, 2, t, d, bf16, pad=32) for t in (17, 129, 300) for d in (96, GRAM_CHUNK + 32) for bf16 in (True, False)]
+    cases += [kmeans_case(st, 2, 1, R, d, k) for R in (1, 129, 300) for k in (1, 127, 130) if k <= R for d in (96, 416)]
+    bad = 0
+    for name, run in cases:
+        outs = [run(lib) for lib in libs]
+        torch.cuda.synchronize()
+        notes = []  # per output that fails: its index, elements left undefined by A / B, elements whose bits differ
+        for i, (a, b) in enumerate(zip(*outs)):
+            undef = [int((torch.isnan(t) if t.dtype.is_floating_point else t == _INT_FILL).sum()) for t in (a, b)]
+            diff = int((a.view(torch.int32) != b.view(torch.int32)).sum())
+            if undef[0] or undef[1] or diff:
+                notes.append(f"out{i} undefined {undef[0]}/{undef[1]} differ {diff} of {a.numel()}")
+        same = len(outs[0]) == len(outs[1]) and not notes
+        bad += not same
+        print(f"equal {name:52s}: {same}" + "".join("  [" + n + "]" for n in notes), flush=True)
+    print(f"bitwise pass: {len(cases)} cases, {bad} differ", flush=True)
+    return bad
+
+
+def descriptors_timed(st):
+    timed = [nn_case(st, P, t, t, d) for (P, t, d) in ((64, 196, 768), (64, 196, 13056), (32, 729, 13056), (1, 3969, 13056), (8, 3969, 13056))]
+    for (P, t, d, bf16) in ((64, 196, 768, True), (16, 729, 768, True), (16, 4096, 256, False), (1, 3969, 768, True)):
+        for joint in ((False, True) if P > 1 else (False,)):
+            timed += [pca_case(st, 1 if joint else P, P if joint else 1, t, d, bf16, (op,)) for op in ("mean", "cov", "proj")]
+    timed += [gram_case(st, 1, t, 13056, True, (op,)) for t in (196, 729) for op in ("mean", "gram", "back")]
+    for (P, imgs, t, d, k) in ((1, 8, 196, 768, 10), (1, 8, 729, 768, 10), (8, 1, 196, 13056, 10), (1, 1, 150, 26112, 10)):
+        timed += [kmeans_case(st, P, imgs, t, d, k, (op,)) for op in ("assign", "update")]
+    return timed
+
+
 def main():
     specs = [a.split(":") for a in sys.argv[1:3]]
     libs = [load(sp[0]) for sp in specs]
@@ -89,6 +283,12 @@ def main():
             out = torch.empty(shape, device="cuda", dtype=torch.bfloat16)
             for li, lib in enumerate(libs):
                 cases.append((f"{name} lib{'AB'[li]}", lambda lib=lib, call=call, out=out: call(lib, out)))
+    elif what == "descriptors":
+        bad = descriptors_equal(libs, st)
+        for name, run in descriptors_timed(st):
+            keep = []
+            for li, lib in enumerate(libs):
+                cases.append((f"{name} lib{'AB'[li]}", lambda lib=lib, run=run, keep=keep: 0 if run(lib, keep) is not None else 1))
     else:
         M = 50432
         for name, N, K, epi in (("qkv", 2304, 768, 0), ("fc1", 3072, 768, 1)):

@@ -2,25 +2,21 @@
 // Operand of both: `problems` problems of `imgs` images of t rows of d bf16 channels, rows ld elements apart, images
 // image_stride apart, problems problem_stride apart (0: one map under many sets of centroids); R = imgs * t rows per problem.
 //
-//   assign   km_norms_kernel    xx of every row and cc of every centroid into `work`: one wave per row, 16-byte chunks, each
-//                               lane sums its chunks in chunk order, then the xor butterfly (nn_cosine.hip's row norm).
+// Tile, accumulator layout, LDS images, the register-staged pipeline and every reduction: desc_tile.h.
+//   assign   km_norms_kernel    xx of every row and cc of every centroid into `work` (row_sumsq: one wave per row).
 //            km_assign_kernel   256 threads; one work item = (problem, 128-row panel of X).  It walks the 128-centroid tiles;
-//                               per tile a loop over d in steps of 64 stages three [128 rows][64 bf16] LDS images (tile128.h):
-//                               the panel's X rows, c_hi and c_lo of the tile's centroids -- split from the fp32 values in the
-//                               staging pass itself, so the operands go through registers (the next step's loads are in
-//                               flight under the MFMAs of the current one), not the LDS-DMA.  Wave (wr, wc) owns the 64 x 64
-//                               sub-tile as 2 x 2 mfma_f32_32x32x16_bf16 accumulators: X is the A operand, the centroids the B
+//                               per tile a loop over d in steps of 64 stages three "t128" images: the panel's X rows, c_hi
+//                               and c_lo of the tile's centroids -- split from the fp32 values in the staging pass itself, so
+//                               the operands go through registers, not the LDS-DMA.  X is the A operand, the centroids the B
 //                               operand, so a lane holds ONE centroid j and 16 rows i.  Epilogue per tile, in that layout:
 //                               h = cc_j - 2 s, centroids past k masked, every element folded into the lane's running row
-//                               best (kept across the tiles).  At the end of the item the row best is reduced over the 32
-//                               lanes and the two column waves; label, min_dist and a changed flag per row are written.  The
-//                               R x k matrix is never written.
+//                               best (kept across the tiles).  At the end of the item the row best is reduced (its own copy of
+//                               row_best_reduce); label, min_dist and a changed flag per row are written.  The R x k matrix is never written.
 //            km_assign_finish_kernel  one workgroup per problem: inertia in col_mean's order, the changed flags counted.
 //   update   km_update_kernel   256 threads; one work item = (problem, 128-cluster tile, 128-column tile, chunk of
-//                               VDR_KMEANS_CHUNK rows): the covariance kernel of pca.hip with a one-hot operand.  A thread
-//                               owns one 16-byte column chunk of the X tile and the same chunk (8 clusters) of the one-hot
-//                               image, which it builds in LDS from the labels of its rows; both MFMA operands are read with
-//                               ds_read_b64_tr_b16 (tile_tr.h).  The item's partial sums go to `work`.
+//                               VDR_KMEANS_CHUNK rows): onehot^T X on the "tr" image.  A thread owns one 16-byte column
+//                               chunk of the X tile and the same chunk (8 clusters) of the one-hot image, which it builds in
+//                               LDS from the labels of its rows.  The item's partial sums go to `work`.
 //            km_update_finish_kernel  one workgroup per (problem, cluster): counts the cluster's rows (integers), folds the
 //                               chunk sums ascending and divides once; an empty cluster's centroid is not touched.
 // Every kernel returns at once for a problem whose `active` flag is 0.  No atomics anywhere; nothing depends on `problems`,
@@ -29,8 +25,7 @@
 
 #include <cstdint>
 
-#include "tile128.h"
-#include "tile_tr.h"
+#include "desc_tile.h"
 #include "vdr_dev.h"
 #include "vdr_kernels.h"
 #include "../../include/vdr.h"
@@ -59,13 +54,9 @@ struct KmArgs {
 
 VDR_DEV bool km_on(const KmArgs& a, int64_t p) { return !a.active || a.active[p] != 0; }
 
-// element offset of row r (0 .. R-1) of problem p
-VDR_DEV int64_t km_row(const KmArgs& a, int64_t p, int64_t r) {
-  const int64_t q = r / a.t;
-  return p * a.ps + q * a.is + (r - q * a.t) * a.ld;
-}
-
-VDR_DEV bool km_better(float v, int i, float bv, int bi) { return v < bv || (v == bv && i < bi); }
+struct KmBetter {  // lower value, then lower index
+  __device__ __forceinline__ bool operator()(float v, int i, float bv, int bi) const { return v < bv || (v == bv && i < bi); }
+};
 
 // ---- assign ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void km_norms_kernel(KmArgs a, int problems) {
@@ -73,34 +64,15 @@ __global__ __launch_bounds__(256) void km_norms_kernel(KmArgs a, int problems) {
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int64_t nx = (int64_t)problems * a.R, nc = (int64_t)problems * a.k;
   if (row >= nx + nc) return;
-  float ss = 0.0f;
   if (row < nx) {
     const int64_t p = row / a.R, r = row - p * a.R;
     if (!km_on(a, p)) return;
-    const bf16_t* src = a.x + km_row(a, p, r);
-    for (int c = lane * 8; c < a.d; c += 512) {
-      const bf16x8 v = *reinterpret_cast<const bf16x8*>(src + c);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float f = (float)v[e];
-        ss += f * f;
-      }
-    }
-    ss = wave_sum(ss);
+    const float ss = row_sumsq(a.x + desc_row(a, p * a.ps, r), a.d, lane);
     if (lane == 0) a.xx[row] = ss;
   } else {
     const int64_t cr = row - nx, p = cr / a.k;
     if (!km_on(a, p)) return;
-    const float* src = a.cent + cr * a.d;
-    for (int c = lane * 8; c < a.d; c += 512) {
-      const f32x4 lo = *reinterpret_cast<const f32x4*>(src + c);
-      const f32x4 hi = *reinterpret_cast<const f32x4*>(src + c + 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) ss += lo[e] * lo[e];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) ss += hi[e] * hi[e];
-    }
-    ss = wave_sum(ss);
+    const float ss = row_sumsq(a.cent + cr * a.d, a.d, lane);
     if (lane == 0) a.cc[cr] = ss;
   }
 }
@@ -121,24 +93,20 @@ __global__ __launch_bounds__(256) void km_assign_kernel(KmArgs a, int32_t* label
   for (int j = 0; j < 4; ++j) {
     const int64_t r = (int64_t)panel * KM_T + rl + 32 * j;
     rok[j] = r < a.R;
-    roff[j] = rok[j] ? km_row(a, p, r) : 0;
+    roff[j] = rok[j] ? desc_row(a, p * a.ps, r) : 0;
   }
 
   float rbv[2][16];
   int rbi[2][16];
   f32x16 acc[2][2];
+  acc_zero(acc);
 #pragma unroll
-  for (int m = 0; m < 2; ++m) {
+  for (int m = 0; m < 2; ++m)
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       rbv[m][e] = INFINITY;
       rbi[m][e] = INT32_MAX;
     }
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[m][n][e] = 0.0f;
-  }
 
   char* sx = smem;
   char* shi = smem + T128_OPER;
@@ -155,55 +123,36 @@ __global__ __launch_bounds__(256) void km_assign_kernel(KmArgs a, int32_t* label
       cok[j] = c < a.k;
       crow[j] = cent + (int64_t)(cok[j] ? c : 0) * a.d;
     }
-    bf16x8 rx[4];
-    f32x4 rc[4][2];
+    RawChunk<true> rx[4];
+    RawChunk<false> rc[4];
     // (a row past R, a centroid past k or a column past d is fetched as zeros and staged as zeros)
     const auto fetch = [&](int step) {
       const int col = step * 64 + ch * 8;
       const bool colok = col < a.d;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        if (rok[j] && colok) {
-          rx[j] = *reinterpret_cast<const bf16x8*>(a.x + roff[j] + col);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) rx[j][e] = (bf16_t)0.0f;
-        }
-        if (cok[j] && colok) {
-          rc[j][0] = *reinterpret_cast<const f32x4*>(crow[j] + col);
-          rc[j][1] = *reinterpret_cast<const f32x4*>(crow[j] + col + 4);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) rc[j][0][e] = rc[j][1][e] = 0.0f;
-        }
+        raw_fill(rx[j], rok[j] && colok, a.x, roff[j] + col);
+        raw_fill(rc[j], cok[j] && colok, crow[j], col);
       }
     };
-    const auto stage = [&]() {
+    const auto stage = [&](int) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         bf16x8 h, l;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const float c = rc[j][e >> 2][e & 3];
+          const float c = rc[j].get(e);
           h[e] = (bf16_t)c;
           l[e] = (bf16_t)(c - (float)h[e]);
         }
         const int off = t128_off(rl + 32 * j, ch);
-        *reinterpret_cast<bf16x8*>(sx + off) = rx[j];
+        *reinterpret_cast<bf16x8*>(sx + off) = rx[j].v;
         *reinterpret_cast<bf16x8*>(shi + off) = h;
         *reinterpret_cast<bf16x8*>(slo + off) = l;
       }
     };
 
-    fetch(0);
-#pragma clang loop unroll(disable)
-    for (int step = 0; step < nk; ++step) {
-      __syncthreads();  // every wave has read the previous step
-      stage();
-      __syncthreads();
-      if (step + 1 < nk) fetch(step + 1);
-      t128_mfma_a2b(sx, shi, slo, wr, wc, l31, hh, acc);
-    }
+    staged_steps(nk, fetch, stage, [&]() { t128_mfma_a2b(sx, shi, slo, wr, wc, l31, hh, acc); });
 
     // ---- epilogue of tile jt
     float ccv[2];
@@ -211,7 +160,7 @@ __global__ __launch_bounds__(256) void km_assign_kernel(KmArgs a, int32_t* label
     bool jok[2];
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
-      gcol[n] = jt * KM_T + wc * 64 + n * 32 + l31;
+      gcol[n] = jt * KM_T + acc_col(wc, n, l31);
       jok[n] = gcol[n] < a.k;
       ccv[n] = jok[n] ? a.cc[(int64_t)p * a.k + gcol[n]] : 0.0f;
     }
@@ -231,9 +180,11 @@ __global__ __launch_bounds__(256) void km_assign_kernel(KmArgs a, int32_t* label
         }
   }
 
-  // ---- row best of the item: over the 32 lanes of a half wave, then over the two column waves
+  // ---- row best of the item: row_best_reduce spelled out -- through the helper the whole kernel is scheduled differently and the
+  // d = 13056 assign is 1.3 % slower: over the 32 lanes of a half wave, then over the two column waves
   float* s_rowv = reinterpret_cast<float*>(smem + KM_ROW);
   int* s_rowi = reinterpret_cast<int*>(smem + KM_ROW + 1024);
+  const KmBetter better;
 #pragma unroll
   for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -244,22 +195,21 @@ __global__ __launch_bounds__(256) void km_assign_kernel(KmArgs a, int32_t* label
       for (int o = 1; o < 32; o <<= 1) {
         const float ov = __shfl_xor(v, o, 64);
         const int oi = __shfl_xor(i, o, 64);
-        if (km_better(ov, oi, v, i)) {
+        if (better(ov, oi, v, i)) {
           v = ov;
           i = oi;
         }
       }
       if (l31 == 0) {
-        const int rloc = wr * 64 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-        s_rowv[wc * 128 + rloc] = v;
-        s_rowi[wc * 128 + rloc] = i;
+        s_rowv[wc * 128 + acc_row(wr, m, e, hh)] = v;
+        s_rowi[wc * 128 + acc_row(wr, m, e, hh)] = i;
       }
     }
   __syncthreads();
   if (tid < 128) {
     float v = s_rowv[tid];
     int i = s_rowi[tid];
-    if (km_better(s_rowv[128 + tid], s_rowi[128 + tid], v, i)) {
+    if (better(s_rowv[128 + tid], s_rowi[128 + tid], v, i)) {
       v = s_rowv[128 + tid];
       i = s_rowi[128 + tid];
     }
@@ -285,7 +235,6 @@ __global__ __launch_bounds__(256) void km_assign_finish_kernel(KmArgs a, const f
   const int32_t* chg = a.chg + (int64_t)p * a.R;
   int cnt = 0;
   for (int64_t r = tid; r < a.R; r += 256) cnt += chg[r];
-  s_cnt[tid] = cnt;
   const int64_t nchunks = (a.R + KM_SUM_CHUNK - 1) / KM_SUM_CHUNK;
   const int cs = tid >> 4, rl = tid & 15;
   float total = 0.0f;
@@ -297,12 +246,7 @@ __global__ __launch_bounds__(256) void km_assign_finish_kernel(KmArgs a, const f
     __syncthreads();
     s_part[cs][rl] = sum;
     __syncthreads();
-    if (tid < 16) {
-      float f = s_part[tid][0];
-#pragma unroll
-      for (int j = 1; j < 16; ++j) f += s_part[tid][j];
-      s_chunk[tid] = f;
-    }
+    if (tid < 16) s_chunk[tid] = fold_chunks(s_part[tid], 16, 1);
     __syncthreads();
     if (tid == 0) {
       const int n = nchunks - c0 < 16 ? (int)(nchunks - c0) : 16;
@@ -311,14 +255,10 @@ __global__ __launch_bounds__(256) void km_assign_finish_kernel(KmArgs a, const f
       for (; j < n; ++j) total += s_chunk[j];
     }
   }
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) s_cnt[tid] += s_cnt[tid + o];
-    __syncthreads();
-  }
+  cnt = block_reduce_256(s_cnt, tid, cnt, [](int x, int y) { return x + y; });
   if (tid == 0) {
     inertia[p] = total;
-    changed[p] = s_cnt[0];
+    changed[p] = cnt;
   }
 }
 
@@ -346,7 +286,7 @@ __global__ __launch_bounds__(256) void km_update_kernel(KmArgs a, const int32_t*
   const int nsteps = (int)((r1 - r0 + TR_STEP - 1) / TR_STEP);
   const int32_t* lab = labels + (int64_t)p * a.R;
 
-  bf16x8 raw[4];
+  RawChunk<true> raw[4];
   int rlab[4];
   // (a row past the chunk has label -1 and zeros: it is in no cluster)
   const auto fetch = [&](int step) {
@@ -355,15 +295,10 @@ __global__ __launch_bounds__(256) void km_update_kernel(KmArgs a, const int32_t*
       const int64_t r = r0 + step * TR_STEP + rl + 16 * j;
       const bool rok = r < r1;
       rlab[j] = rok ? lab[r] : -1;
-      if (rok && cok) {
-        raw[j] = *reinterpret_cast<const bf16x8*>(a.x + km_row(a, p, r) + col);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) raw[j][e] = (bf16_t)0.0f;
-      }
+      raw_fill(raw[j], rok && cok, a.x, desc_row(a, p * a.ps, r) + col);
     }
   };
-  const auto stage = [&]() {
+  const auto stage = [&](int) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       bf16x8 oh;
@@ -371,52 +306,29 @@ __global__ __launch_bounds__(256) void km_update_kernel(KmArgs a, const int32_t*
       for (int e = 0; e < 8; ++e) oh[e] = (bf16_t)(rlab[j] == c0 + e ? 1.0f : 0.0f);
       const int off = tr_off(rl + 16 * j, ch);
       *reinterpret_cast<bf16x8*>(smem + off) = oh;
-      *reinterpret_cast<bf16x8*>(smem + TR_IMG + off) = raw[j];
+      *reinterpret_cast<bf16x8*>(smem + TR_IMG + off) = raw[j].v;
     }
   };
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[m][n][e] = 0.0f;
-
+  acc_zero(acc);
   const tr_lds_cptr imgA = (tr_lds_cptr)smem;
   const tr_lds_cptr imgB = imgA + TR_IMG;
+  // staged_steps spelled out: through the helper this kernel drops to 104 VGPRs and a third wave per SIMD, and a refactor leaves
+  // the occupancy as it was
   fetch(0);
 #pragma clang loop unroll(disable)
   for (int step = 0; step < nsteps; ++step) {
     __syncthreads();  // every wave has read the previous step
-    stage();
+    stage(step);
     __syncthreads();
     if (step + 1 < nsteps) fetch(step + 1);
-#pragma unroll
-    for (int ks = 0; ks < TR_STEP / 16; ++ks) {
-      bf16x8 af[2], bf[2];
-#pragma unroll
-      for (int m = 0; m < 2; ++m) af[m] = tr_read(imgA, ks, wr * 64 + m * 32, lane);
-#pragma unroll
-      for (int n = 0; n < 2; ++n) bf[n] = tr_read(imgB, ks, wc * 64 + n * 32, lane);
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[m], bf[n], acc[m][n], 0, 0, 0);
-    }
+    tr_mfma(imgA, imgB, wr, wc, lane, acc);
   }
 
-  float* part = a.part + ((int64_t)p * a.nchunks + chunk) * a.k * a.d;
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int j = kt * KM_T + wr * 64 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-        const int c = ct * 128 + wc * 64 + n * 32 + l31;
-        if (j < a.k && c < a.d) part[(int64_t)j * a.d + c] = acc[m][n][e];
-      }
+  // the tile's clusters < k and columns < d of part[p][chunk][k][d]
+  float* part = a.part + (((int64_t)p * a.nchunks + chunk) * a.k + kt * KM_T) * a.d + ct * 128;
+  acc_store<true>(part, a.d, a.k - kt * KM_T, a.d - ct * 128, wr, wc, l31, hh, acc);
 }
 
 __global__ __launch_bounds__(256) void km_update_finish_kernel(KmArgs a, const int32_t* labels, float* centroids, int32_t* counts) {
@@ -426,22 +338,13 @@ __global__ __launch_bounds__(256) void km_update_finish_kernel(KmArgs a, const i
   const int32_t* lab = labels + (int64_t)p * a.R;
   int cnt = 0;
   for (int64_t r = tid; r < a.R; r += 256) cnt += lab[r] == j;
-  s_cnt[tid] = cnt;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) s_cnt[tid] += s_cnt[tid + o];
-    __syncthreads();
-  }
-  cnt = s_cnt[0];
+  cnt = block_reduce_256(s_cnt, tid, cnt, [](int x, int y) { return x + y; });
   if (tid == 0) counts[(int64_t)p * a.k + j] = cnt;
   if (cnt == 0) return;  // an empty cluster keeps its centroid's bits
   const float n = (float)cnt;
   float* out = centroids + ((int64_t)p * a.k + j) * a.d;
   for (int c = tid; c < a.d; c += 256) {
-    const float* src = a.part + ((int64_t)p * a.nchunks * a.k + j) * a.d + c;
-    float sum = src[0];
-    for (int q = 1; q < a.nchunks; ++q) sum += src[(int64_t)q * a.k * a.d];
-    out[c] = __fdiv_rn(sum, n);
+    out[c] = __fdiv_rn(fold_chunks(a.part + ((int64_t)p * a.nchunks * a.k + j) * a.d + c, a.nchunks, (int64_t)a.k * a.d), n);
   }
 }
 

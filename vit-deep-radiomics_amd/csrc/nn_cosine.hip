@@ -5,25 +5,22 @@
 // The tx x ty similarity matrix is never written: it exists one 128 x 128 tile at a time in MFMA accumulators.
 //
 // Three launches, no atomics:
-//   nn_rnorm_kernel    rn of every row of X and Y into `work`: one wave per row, 16-byte loads, each lane sums its chunks in
-//                      chunk order, then a fixed xor butterfly.  sqrt and the division are the IEEE ones.
+//   nn_rnorm_kernel    rn of every row of X and Y into `work` (row_sumsq: one wave per row).  sqrt and the division are the
+//                      IEEE ones.
 //   nn_cosine_kernel   256 threads; one work item = (pair, split of Y's tiles, 128-row panel of X).  It walks its 128-row
 //                      tiles of Y; per tile a K loop over d in steps of 64 stages both operands global -> LDS (LDS-DMA,
-//                      two buffers: step s + 1 is in flight under the MFMAs of step s).  Wave (wr, wc) owns the 64 x 64
-//                      sub-tile at (64 wr, 64 wc) as 2 x 2 mfma_f32_32x32x16_bf16 accumulators: X is the A operand, Y the
-//                      B operand, so a lane holds ONE column j (l & 31) and 16 rows i ((e & 3) + 8 (e >> 2) + 4 (l >> 5)).
+//                      two buffers: step s + 1 is in flight under the MFMAs of step s).  X is the A operand, Y the B
+//                      operand of the tile of desc_tile.h, so a lane holds ONE column j and 16 rows i.
 //                      Epilogue per tile, in that layout: scale, mask the ragged rows / columns with -inf, fold every
 //                      element into the lane's running row best (kept across the tiles), reduce the tile's column best
 //                      over registers, lane halves and the two row waves (LDS), write it as a partial (value, index).
-//                      At the end of the item the row best is reduced over the 32 lanes and the two column waves and
-//                      written as a partial too.
+//                      At the end of the item row_best_reduce; the row best is written as a partial too.
 //   nn_finish_kernel   folds the row partials over the splits and the column partials over the panels, ascending.
 // Every fold uses one comparison -- greater value, then lower index -- which is a total order on (value, index) pairs
 // with distinct indices: the result is the same whatever the grouping, so it depends neither on the split count (a
 // launch heuristic) nor on `pairs`.  dot is the MFMA's fp32 accumulation in k order; both are fixed.
 //
-// LDS image of a staged operand tile: [128 rows][64 bf16] = 128-B rows, 16-B chunk c of row r at slot c ^ ((r >> 1) & 7)
-// (the K image of attention_tile.h: conflict-free ds_read_b128 fragment reads).  The DMA writes linearly, so the swizzle
+// LDS image of a staged operand tile: the "t128" image of desc_tile.h.  The DMA writes linearly, so the swizzle
 // is applied to the per-lane SOURCE address.  Rows past the end of a map repeat its last row (finite values, masked in the
 // epilogue).  d % 64 == 32: the last step runs 2 of its 4 MFMA k-steps; its unused chunks re-read chunks 0..3 (nothing
 // past the end of a row is touched).
@@ -31,14 +28,14 @@
 
 #include <cstdint>
 
-#include "tile128.h"
+#include "desc_tile.h"
 #include "vdr_dev.h"
 #include "vdr_kernels.h"
 
 namespace vdr {
 namespace {
 
-constexpr int NN_T = T128;                  // tile side (rows of X per panel, rows of Y per tile): the shared tile of tile128.h
+constexpr int NN_T = T128;                  // tile side (rows of X per panel, rows of Y per tile)
 constexpr int NN_OPER = T128_OPER;          // bytes of one staged operand tile
 constexpr int NN_RN = 4 * NN_OPER;          // s_rn [2][256] float: tile parity x (rn of the tile's Y rows | of the panel's X rows)
 constexpr int NN_COL = NN_RN + 2048;        // column exchange: value [128], index [128]
@@ -58,7 +55,10 @@ struct NnArgs {
   int32_t* rowi;
 };
 
-VDR_DEV bool nn_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+struct NnBetter {  // greater value, then lower index
+  __device__ __forceinline__ bool operator()(float v, int i, float bv, int bi) const { return v > bv || (v == bv && i < bi); }
+};
+constexpr NnBetter nn_better;
 
 __global__ __launch_bounds__(256) void nn_rnorm_kernel(NnArgs a, int pairs) {
   const int lane = threadIdx.x & 63;
@@ -71,16 +71,7 @@ __global__ __launch_bounds__(256) void nn_rnorm_kernel(NnArgs a, int pairs) {
   const int64_t p = r / t;
   const int i = (int)(r - p * t);
   const bf16_t* src = is_x ? a.x + p * a.xs + (int64_t)i * a.ldx : a.y + p * a.ys + (int64_t)i * a.ldy;
-  float ss = 0.0f;
-  for (int c = lane * 8; c < a.d; c += 512) {
-    const bf16x8 v = *reinterpret_cast<const bf16x8*>(src + c);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float f = (float)v[e];
-      ss += f * f;
-    }
-  }
-  ss = wave_sum(ss);
+  const float ss = row_sumsq(src, a.d, lane);
   if (lane == 0) {
     const float rn = __fdiv_rn(1.0f, fmaxf(__fsqrt_rn(ss), 1e-8f));
     if (is_x) a.rnx[p * a.tx_pad + i] = rn; else a.rny[p * a.ty_pad + i] = rn;
@@ -132,23 +123,17 @@ __global__ __launch_bounds__(256, 2) void nn_cosine_kernel(NnArgs a) {
   float rbv[2][16];
   int rbi[2][16];
   f32x16 acc[2][2];
+  acc_zero(acc);
 #pragma unroll
-  for (int m = 0; m < 2; ++m) {
+  for (int m = 0; m < 2; ++m)
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       rbv[m][e] = -INFINITY;
       rbi[m][e] = INT32_MAX;
     }
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[m][n][e] = 0.0f;
-  }
   float* s_rn = reinterpret_cast<float*>(smem + NN_RN);
   float* s_colv = reinterpret_cast<float*>(smem + NN_COL);
   int* s_coli = reinterpret_cast<int*>(smem + NN_COL + 512);
-  float* s_rowv = reinterpret_cast<float*>(smem + NN_ROW);
-  int* s_rowi = reinterpret_cast<int*>(smem + NN_ROW + 1024);
 
   // One loop over the K steps of all tiles, step s + 1 staged under the MFMAs of step s (pass s = -1 only stages step 0):
   // the step after a tile's last one is the first of the next tile.  (jt, kk) is the step in the MFMAs, (njt, nkk) the
@@ -176,8 +161,8 @@ __global__ __launch_bounds__(256, 2) void nn_cosine_kernel(NnArgs a) {
         bool cok[2];
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
-          rny[n] = rn[wc * 64 + n * 32 + l31];
-          gcol[n] = jt * NN_T + wc * 64 + n * 32 + l31;
+          rny[n] = rn[acc_col(wc, n, l31)];
+          gcol[n] = jt * NN_T + wc * 64 + n * 32 + l31;  // acc_col spelled out: through the helper, two more SGPRs spill
           cok[n] = gcol[n] < a.ty;
           cbv[n] = -INFINITY;
           cbi[n] = INT32_MAX;
@@ -190,9 +175,9 @@ __global__ __launch_bounds__(256, 2) void nn_cosine_kernel(NnArgs a) {
         for (int m = 0; m < 2; ++m)
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
-            const int rloc = wr * 64 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+            const int rloc = acc_row(wr, m, e, hh);
             const int grow = panel * NN_T + rloc;
-            const bool rok = m * 32 + (e & 3) + 8 * (e >> 2) < rthr;
+            const bool rok = acc_row(0, m, e, 0) < rthr;
             const float rnx = rn[128 + rloc];
 #pragma unroll
             for (int n = 0; n < 2; ++n) {
@@ -221,8 +206,8 @@ __global__ __launch_bounds__(256, 2) void nn_cosine_kernel(NnArgs a) {
               cbi[n] = oi;
             }
             if (wr == 1 && hh == 0) {
-              s_colv[wc * 64 + n * 32 + l31] = cbv[n];
-              s_coli[wc * 64 + n * 32 + l31] = cbi[n];
+              s_colv[acc_col(wc, n, l31)] = cbv[n];
+              s_coli[acc_col(wc, n, l31)] = cbi[n];
             }
           }
           __syncthreads();
@@ -230,8 +215,8 @@ __global__ __launch_bounds__(256, 2) void nn_cosine_kernel(NnArgs a) {
             const int64_t base = ((int64_t)p * a.npanels + panel) * a.ty_pad;
 #pragma unroll
             for (int n = 0; n < 2; ++n) {
-              const float ov = s_colv[wc * 64 + n * 32 + l31];
-              const int oi = s_coli[wc * 64 + n * 32 + l31];
+              const float ov = s_colv[acc_col(wc, n, l31)];
+              const int oi = s_coli[acc_col(wc, n, l31)];
               if (nn_better(ov, oi, cbv[n], cbi[n])) {
                 cbv[n] = ov;
                 cbi[n] = oi;
@@ -250,41 +235,15 @@ __global__ __launch_bounds__(256, 2) void nn_cosine_kernel(NnArgs a) {
     jt = njt;
     kk = nkk;
   }
-  // ---- row best of the item: over the 32 lanes of a half wave, then over the two column waves
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      float v = rbv[m][e];
-      int i = rbi[m][e];
-#pragma unroll
-      for (int o = 1; o < 32; o <<= 1) {
-        const float ov = __shfl_xor(v, o, 64);
-        const int oi = __shfl_xor(i, o, 64);
-        if (nn_better(ov, oi, v, i)) {
-          v = ov;
-          i = oi;
-        }
-      }
-      if (l31 == 0) {
-        const int rloc = wr * 64 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-        s_rowv[wc * 128 + rloc] = v;
-        s_rowi[wc * 128 + rloc] = i;
-      }
-    }
-  __syncthreads();
-  if (threadIdx.x < 128) {
-    const int t = threadIdx.x;
-    float v = s_rowv[t];
-    int i = s_rowi[t];
-    if (nn_better(s_rowv[128 + t], s_rowi[128 + t], v, i)) {
-      v = s_rowv[128 + t];
-      i = s_rowi[128 + t];
-    }
+  // ---- row best of the item
+  const int t = threadIdx.x;
+  const RowBest b = row_best_reduce(rbv, rbi, reinterpret_cast<float*>(smem + NN_ROW), reinterpret_cast<int*>(smem + NN_ROW + 1024), t,
+                                    nn_better);
+  if (t < 128) {
     // (rows past tx land in the padding of the partial and are never read)
     const int64_t o = ((int64_t)p * a.nsplit + split) * a.tx_pad + panel * NN_T + t;
-    a.rowv[o] = v;
-    a.rowi[o] = i;
+    a.rowv[o] = b.v;
+    a.rowi[o] = b.i;
   }
 }
 

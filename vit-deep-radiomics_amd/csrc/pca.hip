@@ -8,38 +8,30 @@
 //   covariance   pca_cov_kernel: 256 threads, one work item = (problem, pair ci <= cj of 128-column tiles, 1024-row chunk).
 //                The centring (fp32 subtraction, ONE rounding to bf16) rules out the LDS-DMA: every thread owns one fixed
 //                16-byte column chunk of each tile, keeps its 8 + 8 means in registers, loads the next 64-row step into
-//                registers under the MFMAs of the current one, and writes the centred bf16 values into a
-//                [64 rows][128 x bf16] LDS image per tile.  The product contracts over the ROW index of that image, so both
-//                MFMA operands -- "a column of Z over 8 consecutive rows" -- are read with ds_read_b64_tr_b16: lane 4q + p of
-//                a 16-lane group addresses row q, columns 4p .. 4p+3 of a 4-row x 16-column block and receives column
-//                (lane & 15) of the 4 rows.  A lane's 8 k-values are rows 4hh .. 4hh+3 and 8 + 4hh .. 8 + 4hh+3 of a 16-row
-//                k-step (hh = lane >> 5) -- the same permutation on both operands, so the MFMA sums the right products.
-//                Wave (wr, wc) owns the 64 x 64 sub-tile as 2 x 2 mfma_f32_32x32x16_bf16 accumulators.  Rows past the
-//                chunk / R and columns past d are staged as zeros (every lane always reads: EXEC stays all ones).  The
-//                item's 128 x 128 partial goes to `work`; pca_cov_finish_kernel folds the chunks ascending, divides once,
-//                and writes (c1, c2) and (c2, c1) from the same value; of a diagonal tile only c1 <= c2 is read.
-//                LDS image and the transposed read: tile_tr.h (shared with the update kernel of kmeans.hip).
+//                registers under the MFMAs of the current one, and writes the centred bf16 values into the row-contracting
+//                "tr" image of desc_tile.h (tile, accumulator layout, pipeline and transposed read: there).  Rows past the
+//                chunk / R and columns past d are staged as zeros.  The item's 128 x 128 partial goes to `work`;
+//                pca_cov_finish_kernel folds the chunks ascending, divides once, and writes (c1, c2) and (c2, c1) from the
+//                same value; of a diagonal tile only c1 <= c2 is read.
 //   pca_project  pca_project_kernel: components and mean in LDS, one wave per row (16 rows per wave): a lane multiplies its
 //                16-byte chunks lane, lane + 64, ... in chunk order into k fp32 sums, then the xor butterfly.  The
 //                workgroup's min / max go to `work`; pca_minmax_kernel folds them per problem (min and max are exact in any
 //                order), pca_scale_kernel rescales in place when asked.
 //   gram         (vdr_op_gram, the t x t side for t < d)  pca_gram_kernel: one work item = (problem, pair ti <= tj of
 //                128-ROW tiles, chunk of VDR_GRAM_CHUNK columns).  The product contracts over the contiguous index, so the
-//                tile is nn_cosine.hip's (tile128.h): both operands are [128 rows][64 bf16] images of a 64-column step, read
-//                with ds_read_b128.  Staged through registers like the covariance (the centring again rules the LDS-DMA out):
+//                tile is nn_cosine.hip's "t128" image of desc_tile.h, staged through registers like the covariance:
 //                a thread owns 16-byte chunk tid & 7 of rows (tid >> 3) + 32 j of each tile and the 8 means of its columns.
 //                The partial goes to `work` in the covariance's layout and pca_cov_finish_kernel folds it (matrix side t,
 //                divisor t - 1).  The mean at any d is pca_mean_kernel's (launch_col_mean_any: the same launches, the same bits).
-//   back_project (vdr_op_pca_back_project)  pca_back_kernel: the weighted sibling of pca_mean_kernel, one workgroup =
-//                (problem, 1024-row chunk, 128 columns), k weighted sums per column; pca_back_finish_kernel folds the
+//   back_project (vdr_op_pca_back_project)  pca_back_kernel: pca_mean_kernel's workgroup and fold with k weighted sums per
+//                column; pca_back_finish_kernel folds the
 //                chunks ascending and normalises each component with a float64 norm.
 // No atomics anywhere; nothing depends on `problems`, on the grid or on a launch heuristic.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
-#include "tile128.h"
-#include "tile_tr.h"
+#include "desc_tile.h"
 #include "vdr_dev.h"
 #include "vdr_kernels.h"
 #include "../../include/vdr.h"
@@ -63,11 +55,8 @@ struct PcaArgs {
   float* part;  // scratch
 };
 
-// element offset of row r (0 .. R-1) of problem p
-VDR_DEV int64_t pca_row(const PcaArgs& a, int p, int64_t r) {
-  const int64_t q = r / a.t;
-  return ((int64_t)p * a.imgs + q) * a.is + (r - q * a.t) * a.ld;
-}
+// first element of problem p: the problems lie one after another
+VDR_DEV int64_t pca_base(const PcaArgs& a, int p) { return (int64_t)p * a.imgs * a.is; }
 
 VDR_DEV void pca_load8(const PcaArgs& a, int64_t off, float (&v)[8]) {
   if (a.in_bf16) {
@@ -101,19 +90,11 @@ __global__ __launch_bounds__(256) void pca_mean_kernel(PcaArgs a) {
   if (col < a.d)
     for (int64_t r = r0 + rl; r < r1; r += 16) {
       float v[8];
-      pca_load8(a, pca_row(a, p, r) + col, v);
+      pca_load8(a, desc_row(a, pca_base(a, p), r) + col, v);
 #pragma unroll
       for (int e = 0; e < 8; ++e) acc[e] += v[e];
     }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) s[rl][ch * 8 + e] = acc[e];
-  __syncthreads();
-  if (threadIdx.x < PCA_T && cg * PCA_T + (int)threadIdx.x < a.d) {
-    float sum = s[0][threadIdx.x];
-#pragma unroll
-    for (int j = 1; j < 16; ++j) sum += s[j][threadIdx.x];
-    a.part[((int64_t)p * a.nchunks + chunk) * a.d + cg * PCA_T + threadIdx.x] = sum;
-  }
+  fold_row_lanes(s, threadIdx.x, acc, a.d - cg * PCA_T, a.part + ((int64_t)p * a.nchunks + chunk) * a.d + cg * PCA_T);
 }
 
 __global__ __launch_bounds__(256) void pca_mean_finish_kernel(PcaArgs a, int problems, float* mean) {
@@ -121,39 +102,14 @@ __global__ __launch_bounds__(256) void pca_mean_finish_kernel(PcaArgs a, int pro
   if (idx >= (int64_t)problems * a.d) return;
   const int64_t p = idx / a.d;
   const int c = (int)(idx - p * a.d);
-  const float* src = a.part + p * a.nchunks * a.d + c;
-  float sum = src[0];
-  for (int k = 1; k < a.nchunks; ++k) sum += src[(int64_t)k * a.d];
-  mean[idx] = __fdiv_rn(sum, (float)a.R);
+  mean[idx] = __fdiv_rn(fold_chunks(a.part + p * a.nchunks * a.d + c, a.nchunks, a.d), (float)a.R);
 }
 
 // ---- covariance -------------------------------------------------------------------------------------
-template <bool BF16>
-struct PcaRaw;
-template <>
-struct PcaRaw<true> {
-  bf16x8 v;
-  __device__ __forceinline__ void zero() {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (bf16_t)0.0f;
-  }
-  __device__ __forceinline__ void load(const void* x, int64_t off) { v = *reinterpret_cast<const bf16x8*>((const bf16_t*)x + off); }
-  __device__ __forceinline__ float get(int e) const { return (float)v[e]; }
-};
-template <>
-struct PcaRaw<false> {
-  f32x4 lo, hi;
-  __device__ __forceinline__ void zero() {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) lo[e] = hi[e] = 0.0f;
-  }
-  __device__ __forceinline__ void load(const void* x, int64_t off) {
-    lo = *reinterpret_cast<const f32x4*>((const float*)x + off);
-    hi = *reinterpret_cast<const f32x4*>((const float*)x + off + 4);
-  }
-  __device__ __forceinline__ float get(int e) const { return e < 4 ? lo[e] : hi[e - 4]; }
-};
-
+// This kernel spells the pieces of desc_tile.h out (pair decode, row addressing, zero-or-load, zeroing, pipeline, transposed-read
+// MFMA step, partial store) and takes only the raw chunk type from it: on the shared pieces it measured 0.2 - 0.6 us (up to 1.2 %)
+// slower than its parent on the bf16 workloads, outside the A/A spread; the pipeline helper alone costs three more waits per pass.
+// As written its assembly is the parent's, line for line (profiles/descriptor_tile_refactor_ab.txt).
 template <bool BF16>
 __global__ __launch_bounds__(256) void pca_cov_kernel(PcaArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -185,12 +141,13 @@ __global__ __launch_bounds__(256) void pca_cov_kernel(PcaArgs a) {
   const int64_t r1 = r0 + PCA_CHUNK < a.R ? r0 + PCA_CHUNK : a.R;
   const int nsteps = (int)((r1 - r0 + PCA_STEP - 1) / PCA_STEP);
 
-  PcaRaw<BF16> raw[2][4];
+  RawChunk<BF16> raw[2][4];
   const auto fetch = [&](int step) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int64_t r = r0 + step * PCA_STEP + rl + 16 * j;
-      const int64_t off = r < r1 ? pca_row(a, p, r) : 0;
+      const int64_t q = r / a.t;
+      const int64_t off = r < r1 ? ((int64_t)p * a.imgs + q) * a.is + (r - q * a.t) * a.ld : 0;
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         if (r < r1 && cok[s]) raw[s][j].load(a.x, off + col[s]);
@@ -262,19 +219,13 @@ __global__ __launch_bounds__(256) void pca_cov_finish_kernel(PcaArgs a, float* c
   const int idx = (id % BLOCKS) * 256 + threadIdx.x;
   id /= BLOCKS;
   const int pair = id % a.npairs, p = id / a.npairs;
-  int ci = 0, rem = pair;
-  while (rem >= a.nt - ci) {
-    rem -= a.nt - ci;
-    ++ci;
-  }
-  const int cj = ci + rem;
+  int ci, cj;
+  tri_pair(pair, a.nt, ci, cj);
   const int i = idx >> 7, j = idx & 127;
   const int gi = ci * PCA_T + i, gj = cj * PCA_T + j;
   if (gi >= a.d || gj >= a.d || (ci == cj && i > j)) return;
   const float* src = a.part + ((int64_t)p * a.npairs + pair) * a.nchunks * (PCA_T * PCA_T) + idx;
-  float sum = src[0];
-  for (int k = 1; k < a.nchunks; ++k) sum += src[(int64_t)k * (PCA_T * PCA_T)];
-  const float v = __fdiv_rn(sum, (float)(a.R - 1));
+  const float v = __fdiv_rn(fold_chunks(src, a.nchunks, PCA_T * PCA_T), (float)(a.R - 1));
   float* c = cov + (int64_t)p * a.d * a.d;
   c[(int64_t)gi * a.d + gj] = v;
   c[(int64_t)gj * a.d + gi] = v;
@@ -295,12 +246,8 @@ __global__ __launch_bounds__(256) void pca_gram_kernel(PcaArgs a) {
   const int chunk = id % a.nchunks;
   id /= a.nchunks;
   const int pair = id % a.npairs, p = id / a.npairs;
-  int ti = 0, rem = pair;
-  while (rem >= a.nt - ti) {
-    rem -= a.nt - ti;
-    ++ti;
-  }
-  const int tj = ti + rem;
+  int ti, tj;
+  tri_pair(pair, a.nt, ti, tj);
   const bool diag = ti == tj;
 
   // staging role: 16-byte chunk ch of the 64-column step, rows rl, rl + 32, rl + 64, rl + 96 of each tile
@@ -316,10 +263,10 @@ __global__ __launch_bounds__(256) void pca_gram_kernel(PcaArgs a) {
     for (int j = 0; j < 4; ++j) {
       const int r = (s ? tj : ti) * T128 + rl + 32 * j;
       rok[s][j] = r < a.t && !(s == 1 && diag);
-      roff[s][j] = rok[s][j] ? pca_row(a, p, r) : 0;
+      roff[s][j] = rok[s][j] ? desc_row(a, pca_base(a, p), r) : 0;
     }
 
-  PcaRaw<BF16> raw[2][4];
+  RawChunk<BF16> raw[2][4];
   float mu[8], mu_next[8];
   const auto fetch = [&](int step) {
     const int col = c0 + step * GRAM_STEP + ch * 8;
@@ -329,13 +276,10 @@ __global__ __launch_bounds__(256) void pca_gram_kernel(PcaArgs a) {
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (rok[s][j] && cok) raw[s][j].load(a.x, roff[s][j] + col);
-        else raw[s][j].zero();
-      }
+      for (int j = 0; j < 4; ++j) raw_fill(raw[s][j], rok[s][j] && cok, a.x, roff[s][j] + col);
   };
   // (a row past t or a column past the chunk was fetched as zeros and has a zero mean: it is staged as zero)
-  const auto stage = [&]() {
+  const auto stage = [&](int) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) mu[e] = mu_next[e];
 #pragma unroll
@@ -351,33 +295,9 @@ __global__ __launch_bounds__(256) void pca_gram_kernel(PcaArgs a) {
   };
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[m][n][e] = 0.0f;
-
-  fetch(0);
-#pragma clang loop unroll(disable)
-  for (int step = 0; step < nsteps; ++step) {
-    __syncthreads();  // every wave has read the previous step
-    stage();
-    __syncthreads();
-    if (step + 1 < nsteps) fetch(step + 1);
-    t128_mfma<0, 4>(smem, wr, wc, l31, hh, acc);
-  }
-
-  float* part = a.part + (((int64_t)p * a.npairs + pair) * a.nchunks + chunk) * (PCA_T * PCA_T);
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = wr * 64 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-        part[row * PCA_T + wc * 64 + n * 32 + l31] = acc[m][n][e];
-      }
+  acc_zero(acc);
+  staged_steps(nsteps, fetch, stage, [&]() { t128_mfma<0, 4>(smem, wr, wc, l31, hh, acc); });
+  acc_store<false>(a.part + (((int64_t)p * a.npairs + pair) * a.nchunks + chunk) * (PCA_T * PCA_T), PCA_T, PCA_T, PCA_T, wr, wc, l31, hh, acc);
 }
 
 // ---- back-projection (Gram eigenvectors -> components) ----------------------------------------------
@@ -404,7 +324,7 @@ __global__ __launch_bounds__(256) void pca_back_kernel(PcaArgs a, const float* u
   if (cok)
     for (int64_t r = r0 + rl; r < r1; r += 16) {
       float v[8];
-      pca_load8(a, pca_row(a, p, r) + col, v);
+      pca_load8(a, desc_row(a, pca_base(a, p), r) + col, v);
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] -= mu[e];
 #pragma unroll
@@ -418,16 +338,8 @@ __global__ __launch_bounds__(256) void pca_back_kernel(PcaArgs a, const float* u
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     if (j >= k) break;  // (uniform)
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 8; ++e) s[rl][ch * 8 + e] = acc[j][e];
-    __syncthreads();
-    if (threadIdx.x < PCA_T && cg * PCA_T + (int)threadIdx.x < a.d) {
-      float sum = s[0][threadIdx.x];
-#pragma unroll
-      for (int q = 1; q < 16; ++q) sum += s[q][threadIdx.x];
-      a.part[(((int64_t)p * a.nchunks + chunk) * k + j) * a.d + cg * PCA_T + threadIdx.x] = sum;
-    }
+    __syncthreads();  // every thread has read the previous component
+    fold_row_lanes(s, threadIdx.x, acc[j], a.d - cg * PCA_T, a.part + (((int64_t)p * a.nchunks + chunk) * k + j) * a.d + cg * PCA_T);
   }
 }
 
@@ -439,19 +351,11 @@ __global__ __launch_bounds__(256) void pca_back_finish_kernel(PcaArgs a, const f
   float* out = comps + ((int64_t)p * k + j) * a.d;
   double ss = 0.0;
   for (int c = threadIdx.x; c < a.d; c += 256) {
-    const float* src = a.part + ((int64_t)p * a.nchunks * k + j) * a.d + c;
-    float sum = src[0];
-    for (int q = 1; q < a.nchunks; ++q) sum += src[(int64_t)q * k * a.d];
+    const float sum = fold_chunks(a.part + ((int64_t)p * a.nchunks * k + j) * a.d + c, a.nchunks, (int64_t)k * a.d);
     out[c] = sum;
     ss += (double)sum * (double)sum;
   }
-  s[threadIdx.x] = ss;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
-    __syncthreads();
-  }
-  const double norm = sqrt(s[0]);
+  const double norm = sqrt(block_reduce_256(s, (int)threadIdx.x, ss, [](double x, double y) { return x + y; }));
   const bool live = values[(int64_t)p * k + j] > 0.0f && norm > 0.0;
   for (int c = threadIdx.x; c < a.d; c += 256) out[c] = live ? (float)((double)out[c] / norm) : 0.0f;
 }
@@ -474,7 +378,7 @@ __global__ __launch_bounds__(256) void pca_project_kernel(PcaArgs a, const float
   for (int i = 0; i < PCA_PROJ_ROWS / 4; ++i) {
     const int64_t r = rbase + i;
     if (r >= a.R) break;  // (wave-uniform)
-    const int64_t off = pca_row(a, p, r);
+    const int64_t off = desc_row(a, pca_base(a, p), r);
     float acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     for (int c = lane * 8; c < a.d; c += 512) {
       float v[8];
@@ -513,26 +417,21 @@ __global__ __launch_bounds__(256) void pca_project_kernel(PcaArgs a, const float
 }
 
 __global__ __launch_bounds__(256) void pca_minmax_kernel(const float* part, int nblocks, float* minmax) {
-  __shared__ float s[2][256];
+  struct MinMax {
+    float lo, hi;
+  };
+  __shared__ MinMax s[256];
   const int p = blockIdx.x;
   float lo = INFINITY, hi = -INFINITY;
   for (int b = threadIdx.x; b < nblocks; b += 256) {
     lo = fminf(lo, part[((int64_t)p * nblocks + b) * 2]);
     hi = fmaxf(hi, part[((int64_t)p * nblocks + b) * 2 + 1]);
   }
-  s[0][threadIdx.x] = lo;
-  s[1][threadIdx.x] = hi;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      s[0][threadIdx.x] = fminf(s[0][threadIdx.x], s[0][threadIdx.x + o]);
-      s[1][threadIdx.x] = fmaxf(s[1][threadIdx.x], s[1][threadIdx.x + o]);
-    }
-    __syncthreads();
-  }
+  const MinMax mm = block_reduce_256(s, (int)threadIdx.x, MinMax{lo, hi},
+                                     [](MinMax x, MinMax y) { return MinMax{fminf(x.lo, y.lo), fmaxf(x.hi, y.hi)}; });
   if (threadIdx.x == 0) {
-    minmax[2 * p] = s[0][0];
-    minmax[2 * p + 1] = s[1][0];
+    minmax[2 * p] = mm.lo;
+    minmax[2 * p + 1] = mm.hi;
   }
 }
 
@@ -577,16 +476,21 @@ size_t pca_work_bytes(int problems, int imgs, int t, int d) {
   return (size_t)((n * problems * 4 + 15) & ~(int64_t)15);
 }
 
-hipError_t launch_col_mean(const void* x, int in_bf16, int64_t ld, int64_t image_stride, int problems, int imgs, int t, int d,
-                           void* work, float* mean, hipStream_t st) {
+static hipError_t col_mean(const void* x, int in_bf16, int64_t ld, int64_t image_stride, int problems, int imgs, int t, int d,
+                           int dmax, void* work, float* mean, hipStream_t st) {
   PcaArgs a;
-  if (!mean || !pca_args(a, x, in_bf16, ld, image_stride, problems, imgs, t, d, work)) return hipErrorInvalidValue;
+  if (!mean || !pca_args(a, x, in_bf16, ld, image_stride, problems, imgs, t, d, work, dmax)) return hipErrorInvalidValue;
   const int64_t grid = (int64_t)problems * a.nchunks * a.nt;
   if (grid > INT32_MAX) return hipErrorInvalidValue;
   hipLaunchKernelGGL(pca_mean_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
   if (hipError_t e = hipGetLastError()) return e;
   hipLaunchKernelGGL(pca_mean_finish_kernel, dim3((unsigned)(((int64_t)problems * d + 255) / 256)), dim3(256), 0, st, a, problems, mean);
   return hipGetLastError();
+}
+
+hipError_t launch_col_mean(const void* x, int in_bf16, int64_t ld, int64_t image_stride, int problems, int imgs, int t, int d,
+                           void* work, float* mean, hipStream_t st) {
+  return col_mean(x, in_bf16, ld, image_stride, problems, imgs, t, d, 2048, work, mean, st);
 }
 
 hipError_t launch_covariance(const void* x, int in_bf16, int64_t ld, int64_t image_stride, int problems, int imgs, int t, int d,
@@ -644,14 +548,7 @@ size_t pca_topk_side_work_bytes(int problems, int t, int d, int k) {
 
 hipError_t launch_col_mean_any(const void* x, int in_bf16, int64_t ld, int64_t image_stride, int problems, int t, int d, void* work,
                                float* mean, hipStream_t st) {
-  PcaArgs a;
-  if (!mean || !pca_args(a, x, in_bf16, ld, image_stride, problems, 1, t, d, work, INT32_MAX & ~31)) return hipErrorInvalidValue;
-  const int64_t grid = (int64_t)problems * a.nchunks * a.nt;
-  if (grid > INT32_MAX) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(pca_mean_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
-  if (hipError_t e = hipGetLastError()) return e;
-  hipLaunchKernelGGL(pca_mean_finish_kernel, dim3((unsigned)(((int64_t)problems * d + 255) / 256)), dim3(256), 0, st, a, problems, mean);
-  return hipGetLastError();
+  return col_mean(x, in_bf16, ld, image_stride, problems, 1, t, d, INT32_MAX & ~31, work, mean, st);
 }
 
 hipError_t launch_gram(const void* x, int in_bf16, int64_t ld, int64_t image_stride, int problems, int t, int d, const float* mean,
