@@ -758,6 +758,41 @@ int vdr_op_nn_cosine(const void* x, int64_t ldx, int64_t x_stride, int tx,
                      int pairs, int d, void* work,
                      float* row_sim, int32_t* row_idx, float* col_sim, int32_t* col_idx, void* stream);
 
+/* Thresholded affinity graph of a descriptor map, one bit per pair (csrc/affinity.hip): for each of `pairs` problems the
+ * graph B[i, j] = cos(x_i, x_j) > tau over the rows of X_p, without the t x t matrix of scores ever being written.
+ *   X_p = [t, d] bf16, rows ldx elements apart, starting at x + p * x_stride (0 allowed).
+ * Definition:
+ *   ss, rn    = vdr_op_nn_cosine's: rn(v) = 1.0f / fmaxf(sqrtf(ss(v)), 1e-8f), correctly rounded sqrtf and division;
+ *   sim(i, j) = dot(x_i, x_j) * (rn(x_i) * rn(x_j)): the two norms are multiplied FIRST (one rounding), then the dot product by
+ *               that (one rounding); dot is accumulated in fp32 by bf16 MFMAs in ascending k.  Every step commutes in
+ *               (i, j), so sim(i, j) == sim(j, i) bit for bit (vdr_op_nn_cosine's (dot * rn_i) * rn_j does not promise that);
+ *   B[i, j]   = sim(i, j) > tau, an fp32 comparison, strict; exclude_diag != 0 clears B[i, i].
+ *   bits[p][i][j >> 5] bit (j & 31) = B[i, j]; rows are `pitch` words apart, pitch = ceil(t / 32) rounded up to a multiple of 4
+ *   (16-byte rows); the bits of columns >= t and the padding words are written 0.  Every word is written once, by one thread:
+ *   no atomics; a problem's bits do not depend on `pairs` or on its position.  Inputs are finite by contract; a zero row has
+ *   sim = 0 against everything.
+ * work: vdr_affinity_work_bytes(pairs, t) bytes of device scratch (the row norms), 16-byte aligned.
+ * Refused before the device is touched: VDR_ERR_UNSUPPORTED for d % 32 != 0; VDR_ERR_INVALID for a null x, work or bits,
+ * non-positive pairs, t or d, ldx < d, x_stride < 0, pointers or strides that are not 16-byte aligned, pairs * t above
+ * 2^31 - 1, a pitch other than the one above, a NaN tau.
+ *
+ * vdr_op_bits_matvec: the product of that graph with nv columns,
+ *   y[p, i, c] = sum over j with B[i, j] of v[p, j, c],   v, y = [pairs][t][nv] fp32, 1 <= nv <= 8,
+ *   degree[p, i] = number of set bits of row i (int32, exact; NULL skips it).
+ * Summation order (part of the definition): per row and column 64 partial sums s_0 .. s_63 (the lanes of one wave); s_l adds,
+ * starting from 0.0f, the v[j] of the set bits of words l, l + 64, l + 128, ... in ascending word order and ascending bit order
+ * within a word; the 64 sums are folded by the xor butterfly s_l += s_(l ^ 32), then ^ 16, 8, 4, 2, 1 (every lane ends with the
+ * total).  (The kernel adds 0.0f for a clear bit instead of skipping it: a sum that starts at +0.0f is never -0.0f, so that
+ * changes no bit; a non-finite v[j] behind a clear bit stays out.)  Bits of columns >= t are ignored.  The result depends on
+ * (t, nv, inputs) only.
+ * Refused: VDR_ERR_UNSUPPORTED for nv outside 1 .. 8; VDR_ERR_INVALID for null bits, v or y, non-positive pairs or t, bits not
+ * 16-byte aligned, v / y / degree not 4-byte aligned, pairs * t above 2^31 - 1, a wrong pitch. */
+size_t vdr_affinity_work_bytes(int pairs, int t);
+int vdr_op_affinity_bits(const void* x, int64_t ldx, int64_t x_stride, int t, int pairs, int d, float tau, int exclude_diag,
+                         void* work, uint32_t* bits, int pitch, void* stream);
+int vdr_op_bits_matvec(const uint32_t* bits, int pitch, int t, int pairs, const float* v, int nv, float* y, int32_t* degree,
+                       void* stream);
+
 /* PCA of dense descriptor maps (csrc/pca.hip): the column mean, the centred covariance and the projection on given
  * components.  The eigen-decomposition between the last two is the caller's (vdr.pca.fit: torch.linalg.eigh in float64).
  * Operand, shared by the three entry points: `problems` problems, each `imgs` images of t rows of d channels, R = imgs * t

@@ -2716,6 +2716,34 @@ int vdr_op_nn_cosine(const void* x, int64_t ldx, int64_t x_stride, int tx, const
          "nn_cosine");
 }
 
+size_t vdr_affinity_work_bytes(int pairs, int t) { return affinity_work_bytes(pairs, t); }
+
+int vdr_op_affinity_bits(const void* x, int64_t ldx, int64_t x_stride, int t, int pairs, int d, float tau, int exclude_diag,
+                         void* work, uint32_t* bits, int pitch, void* stream) {
+  if (!x || !work || !bits) return fail(nullptr, VDR_ERR_INVALID, "affinity_bits: null x, work or bits");
+  if (pairs <= 0 || t <= 0 || d <= 0) return fail(nullptr, VDR_ERR_INVALID, "affinity_bits: pairs, t and d must be positive");
+  if (d % 32 != 0) return fail(nullptr, VDR_ERR_UNSUPPORTED, "affinity_bits: d must be a multiple of 32");
+  if (ldx < d || x_stride < 0) return fail(nullptr, VDR_ERR_INVALID, "affinity_bits: ldx must be >= d, x_stride >= 0");
+  if (!aligned16({x, work, bits}) || ldx % 8 || x_stride % 8)
+    return fail(nullptr, VDR_ERR_INVALID, "affinity_bits: pointers, rows (ldx) and x_stride must be 16-byte aligned");
+  if ((int64_t)pairs * t > INT32_MAX) return fail(nullptr, VDR_ERR_INVALID, "affinity_bits: pairs * t exceeds 2^31 - 1");
+  if (pitch != affinity_pitch(t)) return fail(nullptr, VDR_ERR_INVALID, "affinity_bits: pitch must be ceil(t / 32) rounded up to a multiple of 4");
+  if (!(tau == tau)) return fail(nullptr, VDR_ERR_INVALID, "affinity_bits: tau is NaN");
+  RUN_OP(launch_affinity_bits(x, ldx, x_stride, t, pairs, d, tau, exclude_diag, work, bits, pitch, (hipStream_t)stream), "affinity_bits");
+}
+
+int vdr_op_bits_matvec(const uint32_t* bits, int pitch, int t, int pairs, const float* v, int nv, float* y, int32_t* degree,
+                       void* stream) {
+  if (!bits || !v || !y) return fail(nullptr, VDR_ERR_INVALID, "bits_matvec: null bits, v or y");
+  if (pairs <= 0 || t <= 0) return fail(nullptr, VDR_ERR_INVALID, "bits_matvec: pairs and t must be positive");
+  if (nv < 1 || nv > 8) return fail(nullptr, VDR_ERR_UNSUPPORTED, "bits_matvec: nv must be 1 .. 8");
+  if (!aligned16({bits}) || ((uintptr_t)v | (uintptr_t)y | (uintptr_t)degree) % 4)
+    return fail(nullptr, VDR_ERR_INVALID, "bits_matvec: bits must be 16-byte aligned, v, y and degree 4-byte aligned");
+  if ((int64_t)pairs * t > INT32_MAX) return fail(nullptr, VDR_ERR_INVALID, "bits_matvec: pairs * t exceeds 2^31 - 1");
+  if (pitch != affinity_pitch(t)) return fail(nullptr, VDR_ERR_INVALID, "bits_matvec: pitch must be ceil(t / 32) rounded up to a multiple of 4");
+  RUN_OP(launch_bits_matvec(bits, pitch, t, pairs, v, nv, y, degree, (hipStream_t)stream), "bits_matvec");
+}
+
 size_t vdr_pca_work_bytes(int problems, int imgs, int t, int d) { return pca_work_bytes(problems, imgs, t, d); }
 
 // the operand checks shared by the three PCA ops (include/vdr.h); `outs`: the op's other pointers

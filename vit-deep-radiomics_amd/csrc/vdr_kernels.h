@@ -316,6 +316,17 @@ hipError_t launch_nn_cosine(const void* x, int64_t ldx, int64_t x_stride, int tx
                             int ty, int pairs, int d, void* work, float* row_sim, int32_t* row_idx, float* col_sim,
                             int32_t* col_idx, hipStream_t st);
 
+// Thresholded affinity graphs of descriptor maps, one bit per pair (affinity.hip; the definitions are vdr_op_affinity_bits' and
+// vdr_op_bits_matvec's in include/vdr.h): X_p [t, d] bf16, rows ldx elements apart, problems x_stride apart (0 allowed);
+// d % 32 == 0; pointers and strides 16-byte aligned; work: affinity_work_bytes(pairs, t) bytes; bits [pairs][t][pitch] with
+// pitch == affinity_pitch(t).  Two launches (row norms, the fused tile kernel); the matvec is one.
+int affinity_pitch(int t);
+size_t affinity_work_bytes(int pairs, int t);
+hipError_t launch_affinity_bits(const void* x, int64_t ldx, int64_t x_stride, int t, int pairs, int d, float tau, int exclude_diag,
+                                void* work, uint32_t* bits, int pitch, hipStream_t st);
+hipError_t launch_bits_matvec(const uint32_t* bits, int pitch, int t, int pairs, const float* v, int nv, float* y, int32_t* degree,
+                              hipStream_t st);
+
 // PCA of dense descriptor maps (pca.hip; the definitions are vdr_op_col_mean's, vdr_op_covariance's and vdr_op_pca_project's
 // in include/vdr.h): `problems` problems of `imgs` images of t rows of d channels, bf16 or fp32, rows ld and images
 // image_stride elements apart.  d % 32 == 0, d <= 2048; pointers and strides 16-byte aligned; work: pca_work_bytes(...)

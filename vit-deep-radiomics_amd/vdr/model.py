@@ -516,6 +516,48 @@ class VitDescriptorModel:
         masks = salient[labels.long()]
         return Cosegmentation(labels.reshape(B, gh, gw), salient, masks.reshape(B, gh, gw), sal.reshape(B, gh, gw), fit)
 
+    def _affinity_graph(self, x, what, layer, facet, bin, hierarchy, tau):
+        """one forward for the bf16 `facet` descriptors of x, then their thresholded affinity graph, read in place"""
+        h = self._descriptor_args(layer, facet, bin, False, hierarchy)
+        if x.dim() != 4:
+            raise ValueError(f"{what}: x must be [B, 3, H, W], got {tuple(x.shape)}")
+        if tau != tau:
+            raise ValueError(f"{what}: tau is NaN")
+        from . import ops
+        i = self.cfg.layers - 1 if layer is None else int(layer)
+        self._adopt(x)
+        (desc,), _, _ = self.engine.forward_descriptors(x.to(self.device), [FacetOut(i, facet, h, False, torch.bfloat16)])
+        return ops.affinity_bits(desc, tau=tau)
+
+    def tokencut(self, x: torch.Tensor, layer=None, facet: str = "key", bin: bool = False, tau: float = 0.2, eps: float = 1e-5,
+                 hierarchy: int = 2):
+        """TokenCut (Wang et al., CVPR 2022) on every image of x [B, 3, H, W]: one forward (vdr_forward_facets) writes the bf16
+        `facet` descriptors of block `layer` (None: the last block), log-binned at `hierarchy` when bin;
+        vdr.ops.affinity_bits builds the graph cos > tau of each map from that buffer in place, one bit per pair;
+        vdr.spectral.tokencut takes the Fiedler vector of (D - W) y = lambda D y, W = eps + (1 - eps) B, splits it at its
+        mean and returns the seed's connected component and box (vdr.TokenCut, with the graph in .bits; pixel_box() for pixels).  No mask, no second
+        image, no k.  The input size, patch stride and dynamic_size in force apply.  Written from the paper as remembered;
+        parity with its code is not pinned.  Refusals (ValueError, before any device work): extract_descriptors', a NaN tau."""
+        from . import spectral
+        bits = self._affinity_graph(x, "tokencut", layer, facet, bin, hierarchy, float(tau))
+        return spectral.tokencut(bits, tuple(self.engine.grid), eps=float(eps), stride=int(self.engine.patch_stride),
+                                 patch=int(self.cfg.patch))
+
+    def lost(self, x: torch.Tensor, layer=None, facet: str = "key", k: int = 100, bin: bool = False, hierarchy: int = 2,
+             tau: float = 0.0):
+        """LOST (Simeoni et al., BMVC 2021) on every image of x [B, 3, H, W]: the graph cos > 0 of the bf16 `facet` descriptors
+        (one forward, vdr.ops.affinity_bits in place), the lowest-degree patch as the seed, the k lowest-degree patches
+        adjacent to it as the expansion set, the seed's connected component of that set and its box (vdr.Lost).  tau: the
+        threshold of the graph, LOST's 0 by default; descriptors that share a large common component (every cosine positive:
+        a complete graph, every degree equal) need a higher one to say anything.  Deviation: LOST compares raw dot products
+        with >= 0; here it is cosines > tau.  Refusals as
+        tokencut's, and k < 1."""
+        from . import spectral
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or int(k) < 1:
+            raise ValueError(f"lost: k must be a positive integer, got {k!r}")
+        bits = self._affinity_graph(x, "lost", layer, facet, bin, hierarchy, float(tau))
+        return spectral.lost(bits, tuple(self.engine.grid), k=int(k), stride=int(self.engine.patch_stride), patch=int(self.cfg.patch))
+
     def pca_descriptors(self, x: torch.Tensor, n_components: int = 3, layer=None, facet=None, joint: bool = False,
                         remove_bg: bool = False) -> torch.Tensor:
         """The reference's pca_colorize (visualization_utils.py:49-69) of every image's dense descriptors, on the device:

@@ -286,8 +286,8 @@ def log_bin(x: torch.Tensor, gh: int, gw: int, hierarchy: int = 2, out_dtype=tor
     return out
 
 
-def _nn_operand(t: torch.Tensor, name: str):
-    """(tensor, row stride, pair stride) of one nn_cosine operand, read where it lies when it can be"""
+def _nn_operand(t: torch.Tensor, name: str, op: str = "nn_cosine"):
+    """(tensor, row stride, pair stride) of one nn_cosine / affinity_bits operand, read where it lies when it can be"""
     if t.dtype != torch.bfloat16:
         t = t.to(torch.bfloat16)  # (fp32: rounded once; a new contiguous tensor)
     P, n, d = t.shape
@@ -295,7 +295,7 @@ def _nn_operand(t: torch.Tensor, name: str):
         (P == 1 or (t.stride(0) >= 0 and t.stride(0) % 8 == 0)) and t.data_ptr() % 16 == 0
     if not ok:
         if d > 1 and t.stride(2) != 1:
-            raise ValueError(f"nn_cosine: the channels of {name} must be contiguous")
+            raise ValueError(f"{op}: the channels of {name} must be contiguous")
         t = t.contiguous()
     return t, (t.stride(1) if n > 1 else d), (t.stride(0) if P > 1 else 0)
 
@@ -337,6 +337,95 @@ def nn_cosine(x: torch.Tensor, y: torch.Tensor, mutual: bool = True):
     L.check(lib.vdr_op_nn_cosine(x.data_ptr(), ldx, xs, tx, y.data_ptr(), ldy, ys, ty, P, d, work.data_ptr(), row_sim.data_ptr(),
                                  row_idx.data_ptr(), _p(col_sim), _p(col_idx), _s(x)))
     return row_sim, row_idx, col_sim, col_idx
+
+
+def bits_pitch(t: int) -> int:
+    """int32 words per row of a bit-packed [t, t] graph: ceil(t / 32) rounded up to a multiple of 4 (16-byte rows)"""
+    return (int(t) + 127) // 128 * 4
+
+
+def affinity_bits(x: torch.Tensor, tau: float = 0.2, exclude_diag: bool = False) -> torch.Tensor:
+    """Thresholded affinity graph of descriptor maps (vdr_op_affinity_bits): x [P, t, d] on the device, bf16 -- contiguous, or
+    a view with contiguous channels, read in place as nn_cosine reads its operands; fp32 is rounded once to bf16 first.  d
+    must be a multiple of 32.  Returns bits [P, t, bits_pitch(t)] int32: bit (j & 31) of bits[p, i, j >> 5] is
+    cos(x[p, i], x[p, j]) > tau (the diagonal cleared with exclude_diag); bits of columns >= t and the padding words are 0.
+    The graph is symmetric bit for bit; the [t, t] matrix of scores is never materialised.  The exact arithmetic is stated in
+    include/vdr.h."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("affinity_bits: x must be a [P, t, d] float32 or bfloat16 tensor")
+    if not x.is_cuda:
+        raise TypeError("affinity_bits: x must live on the HIP device")
+    P, t, d = x.shape
+    if min(P, t, d) <= 0:
+        raise ValueError("affinity_bits: empty operand")
+    if d % 32:
+        raise ValueError(f"affinity_bits: d must be a multiple of 32, got {d}")
+    if P * t > 2 ** 31 - 1:
+        raise ValueError("affinity_bits: P * t exceeds 2^31 - 1")
+    tau = float(tau)
+    if tau != tau:
+        raise ValueError("affinity_bits: tau is NaN")
+    lib = L.load()
+    x, ldx, xs = _nn_operand(x, "x", "affinity_bits")
+    pitch = bits_pitch(t)
+    work = torch.empty((lib.vdr_affinity_work_bytes(P, t),), dtype=torch.uint8, device=x.device)
+    bits = torch.empty((P, t, pitch), dtype=torch.int32, device=x.device)
+    L.check(lib.vdr_op_affinity_bits(x.data_ptr(), ldx, xs, t, P, d, tau, int(bool(exclude_diag)), work.data_ptr(), bits.data_ptr(),
+                                     pitch, _s(x)))
+    return bits
+
+
+def _check_bits(bits: torch.Tensor, op: str):
+    if not isinstance(bits, torch.Tensor) or bits.dim() != 3 or bits.dtype != torch.int32:
+        raise TypeError(f"{op}: bits must be a [P, t, pitch] int32 tensor")
+    if bits.shape[0] <= 0 or bits.shape[1] <= 0 or bits.shape[2] != bits_pitch(bits.shape[1]):
+        raise ValueError(f"{op}: bits {tuple(bits.shape)} is not [P, t, bits_pitch(t)]")
+
+
+def bits_matvec(bits: torch.Tensor, v: torch.Tensor, degree: bool = False):
+    """The product of a bit-packed graph with 1 .. 8 columns (vdr_op_bits_matvec): bits [P, t, pitch] int32 from
+    affinity_bits, v [P, t, nv] (or [P, t]) fp32 -> y of v's shape, y[p, i, c] = sum over j with B[p, i, j] of v[p, j, c], in
+    the fixed fp32 order stated in include/vdr.h.  degree=True returns (y, deg [P, t] int32), the exact row popcounts."""
+    _check_bits(bits, "bits_matvec")
+    if not bits.is_cuda:
+        raise TypeError("bits_matvec: bits must live on the HIP device")
+    P, t, pitch = bits.shape
+    if not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or v.dim() not in (2, 3) or v.device != bits.device:
+        raise TypeError("bits_matvec: v must be a [P, t, nv] or [P, t] float32 tensor on the device of bits")
+    flat = v.dim() == 2
+    v3 = v.unsqueeze(2) if flat else v
+    if v3.shape[0] != P or v3.shape[1] != t or not 1 <= v3.shape[2] <= 8:
+        raise ValueError(f"bits_matvec: v {tuple(v.shape)} does not match bits {tuple(bits.shape)} with 1 <= nv <= 8")
+    nv = v3.shape[2]
+    bits, v3 = bits.contiguous(), v3.contiguous()
+    y = torch.empty((P, t, nv), dtype=torch.float32, device=bits.device)
+    deg = torch.empty((P, t), dtype=torch.int32, device=bits.device) if degree else None
+    L.check(L.load().vdr_op_bits_matvec(bits.data_ptr(), pitch, t, P, v3.data_ptr(), nv, y.data_ptr(), _p(deg), _s(bits)))
+    y = y[:, :, 0] if flat else y
+    return (y, deg) if degree else y
+
+
+def pack_bits(b: torch.Tensor) -> torch.Tensor:
+    """bool [P, t, t] -> bits [P, t, bits_pitch(t)] int32 in affinity_bits' layout.  Plain torch: for tests and small maps."""
+    if b.dim() != 3 or b.shape[1] != b.shape[2]:
+        raise ValueError(f"pack_bits: a [P, t, t] tensor expected, got {tuple(b.shape)}")
+    P, t, _ = b.shape
+    pitch = bits_pitch(t)
+    full = torch.zeros((P, t, pitch * 32), dtype=torch.int64, device=b.device)
+    full[:, :, :t] = b.to(torch.int64)
+    words = (full.view(P, t, pitch, 32) << torch.arange(32, device=b.device, dtype=torch.int64)).sum(-1)
+    return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
+
+
+def unpack_bits(bits: torch.Tensor, t: int) -> torch.Tensor:
+    """bits [P, t, pitch] int32 -> bool [P, t, t], B[p, i, j] = bit (j & 31) of bits[p, i, j >> 5].  Plain torch, on the
+    device of bits: for tests and small maps."""
+    _check_bits(bits, "unpack_bits")
+    if int(t) != bits.shape[1]:
+        raise ValueError(f"unpack_bits: t = {t} but bits has {bits.shape[1]} rows")
+    sh = torch.arange(32, device=bits.device, dtype=torch.int64)
+    b = ((bits.to(torch.int64).unsqueeze(-1) >> sh) & 1).to(torch.bool)
+    return b.reshape(bits.shape[0], bits.shape[1], -1)[:, :, :t]
 
 
 def best_buddies(row_idx: torch.Tensor, col_idx: torch.Tensor) -> torch.Tensor:
