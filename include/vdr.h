@@ -941,6 +941,37 @@ int vdr_op_kmeans_assign(const void* x, int64_t ld, int64_t image_stride, int64_
 int vdr_op_kmeans_update(const void* x, int64_t ld, int64_t image_stride, int64_t problem_stride, int problems, int imgs, int t,
                          int d, int k, const int32_t* labels, const int32_t* active, void* work, float* centroids,
                          int32_t* counts, void* stream);
+/* Squared Mahalanobis distances of dense descriptor rows under a Gaussian (csrc/mahalanobis.hip): the score side of the
+ * Gaussian-of-features anomaly methods (vdr.anomaly).  The fit -- mean, covariance, eigen-decomposition, whitening rows -- is
+ * the caller's (vdr.anomaly.whitening).
+ * Operand: the k-means ops' -- `problems` problems, each `imgs` images of t rows of d bf16 channels, R = imgs * t rows per
+ *   problem; rows ld, images image_stride, problems problem_stride elements apart (0: one map under `problems` models); a view
+ *   into a wider buffer is read in place.  The model of problem p: mean + p * mean_stride, [d] fp32, and
+ *   whiten + p * whiten_stride, [k][d] fp32 contiguous; a model stride of 0 is one model under every problem.
+ *   k = 1..VDR_MAHALANOBIS_MAX_K whitening rows, below, equal to or above d: the op squares whatever rows it is given.
+ * For row x_i of problem p:
+ *   z = float(x_i) - mean, one fp32 rounding per channel (the subtraction BEFORE any rounding to bf16);
+ *   z_hi = bf16_rn(z), z_lo = bf16_rn(z - float(z_hi)) per channel (the subtraction is exact);
+ *   for whitening row w_j: w_hi = bf16_rn(w_j), w_lo = bf16_rn(w_j - float(w_hi));
+ *   y_j = ONE fp32 accumulation by bf16 MFMAs (the products are exact in fp32) over 16 channels at a time, channels ascending,
+ *     per 16 channels the products z_hi.w_hi, then z_hi.w_lo, then z_lo.w_hi; z_lo.w_lo is dropped on purpose (it is below
+ *     2^-16 of the leading product, at the level of the fp32 accumulation's own rounding);
+ *   d2[p, i] = sum_j y_j * y_j, each square rounded to fp32 before it is added, in this order: 64 partial sums s_(w, l),
+ *     w = 0, 1 and l = 0..31, where s_(w, l) adds, starting from 0.0f, the squares of the j with j mod 32 = l and
+ *     (j / 64) mod 2 = w in ascending j; T_w = the 32 sums s_(w, .) folded by the xor butterfly s_l += s_(l ^ 1), then ^ 2, 4, 8,
+ *     16 (every lane ends with the total); d2 = T_0 + T_1.  The j are counted up to the next multiple of 128 above k - 1: a j >= k
+ *     adds +0.0f, which changes no bit.
+ *   The order depends on (k, d, inputs) only -- not on `problems`, the problem's position in the batch, R, the grid or a
+ *   launch heuristic.  No atomics, no scratch; the R x k matrix of the y is never written.  A non-finite value in row i reaches
+ *   d2[p, i] alone; rows past R, whitening rows past k and channels past d are never read.      d2 [problems, R] fp32
+ * Refused before the device is touched: VDR_ERR_UNSUPPORTED for d % 32 != 0 or k outside 1..VDR_MAHALANOBIS_MAX_K;
+ * VDR_ERR_INVALID for null pointers, non-positive problems, imgs, t or d, ld < d, negative strides, a non-zero mean_stride
+ * below d or whiten_stride below k * d, x / mean / whiten or strides (ld, image_stride, problem_stride, mean_stride,
+ * whiten_stride) that are not 16-byte aligned, d2 not 4-byte aligned, problems * R above 2^31 - 1. */
+#define VDR_MAHALANOBIS_MAX_K 2048
+int vdr_op_mahalanobis(const void* x, int64_t ld, int64_t image_stride, int64_t problem_stride, int problems, int imgs, int t,
+                       int d, const float* mean, int64_t mean_stride, const float* whiten, int64_t whiten_stride, int k,
+                       float* d2, void* stream);
 /* ---- measurement ------------------------------------------------------------------------ */
 
 /* Kernel classes timed by the built-in HIP-event profiler. */

@@ -1,4 +1,4 @@
-// The tile core of the descriptor-analysis kernels (nn_cosine.hip, pca.hip, kmeans.hip): one 128 x 128 fp32 tile per workgroup
+// The tile core of the descriptor-analysis kernels (nn_cosine.hip, pca.hip, kmeans.hip, mahalanobis.hip): one 128 x 128 fp32 tile per workgroup
 // of 4 waves, wave (wr, wc) = (wave >> 1, wave & 1) owning the 64 x 64 sub-tile at (64 wr, 64 wc) as 2 x 2
 // mfma_f32_32x32x16_bf16 accumulators.  Every piece that fixes the BITS of a result -- the accumulator layout, the k order of
 // the MFMA steps, the comparator folds, the ascending sums -- is written once here; the kernels keep what is theirs (centring,
@@ -94,6 +94,41 @@ VDR_DEV void t128_mfma_a2b(const char* sa, const char* sb0, const char* sb1, int
     for (int m = 0; m < 2; ++m)
 #pragma unroll
       for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[m], b1[n], acc[m][n], 0, 0, 0);
+  }
+}
+
+// the four MFMA k-steps of a staged 64-column step with TWO A images against TWO B images accumulated into the same tile
+// (mahalanobis.hip: the hi and the lo half of the centred rows against those of the whitening rows): per 16-column k-step the
+// products a0 b0, then a0 b1, then a1 b0; a1 b1 is not taken
+VDR_DEV void t128_mfma_2a2b(const char* sa0, const char* sa1, const char* sb0, const char* sb1, int wr, int wc, int l31, int hh,
+                            f32x16 (&acc)[2][2]) {
+  const int swz = (l31 >> 1) & 7;
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    const int off = ((2 * ks + hh) ^ swz) * 16;
+    bf16x8 a0[2], a1[2], b0[2], b1[2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      a0[m] = *reinterpret_cast<const bf16x8*>(sa0 + (wr * 64 + m * 32 + l31) * 128 + off);
+      a1[m] = *reinterpret_cast<const bf16x8*>(sa1 + (wr * 64 + m * 32 + l31) * 128 + off);
+    }
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+      b0[n] = *reinterpret_cast<const bf16x8*>(sb0 + (wc * 64 + n * 32 + l31) * 128 + off);
+      b1[n] = *reinterpret_cast<const bf16x8*>(sb1 + (wc * 64 + n * 32 + l31) * 128 + off);
+    }
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[m], b0[n], acc[m][n], 0, 0, 0);
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[m], b1[n], acc[m][n], 0, 0, 0);
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[m], b0[n], acc[m][n], 0, 0, 0);
   }
 }
 

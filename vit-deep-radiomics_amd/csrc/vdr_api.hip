@@ -2903,6 +2903,29 @@ int vdr_op_kmeans_update(const void* x, int64_t ld, int64_t image_stride, int64_
          "kmeans_update");
 }
 
+int vdr_op_mahalanobis(const void* x, int64_t ld, int64_t image_stride, int64_t problem_stride, int problems, int imgs, int t, int d,
+                       const float* mean, int64_t mean_stride, const float* whiten, int64_t whiten_stride, int k, float* d2,
+                       void* stream) {
+  if (!x || !mean || !whiten || !d2) return fail(nullptr, VDR_ERR_INVALID, "mahalanobis: null x, mean, whiten or d2");
+  if (problems <= 0 || imgs <= 0 || t <= 0 || d <= 0)
+    return fail(nullptr, VDR_ERR_INVALID, "mahalanobis: problems, imgs, t and d must be positive");
+  if (d % 32 != 0) return fail(nullptr, VDR_ERR_UNSUPPORTED, "mahalanobis: d must be a multiple of 32");
+  if (k < 1 || k > VDR_MAHALANOBIS_MAX_K) return fail(nullptr, VDR_ERR_UNSUPPORTED, "mahalanobis: k must be 1..2048");
+  if (ld < d || image_stride < 0 || problem_stride < 0)
+    return fail(nullptr, VDR_ERR_INVALID, "mahalanobis: ld must be >= d, the strides >= 0");
+  if ((mean_stride != 0 && mean_stride < d) || (whiten_stride != 0 && whiten_stride < (int64_t)k * d))
+    return fail(nullptr, VDR_ERR_INVALID, "mahalanobis: mean_stride must be 0 or >= d, whiten_stride 0 or >= k * d");
+  if (!aligned16({x, mean, whiten}) || (uintptr_t)d2 % 4 || ld % 8 || image_stride % 8 || problem_stride % 8 || mean_stride % 4 ||
+      whiten_stride % 4)
+    return fail(nullptr, VDR_ERR_INVALID,
+                "mahalanobis: x, mean, whiten, rows (ld), images, problems and the model strides must be 16-byte aligned, d2 4-byte aligned");
+  const int64_t R = (int64_t)imgs * t;  // (each factor is a positive int: no overflow; R is bounded before the next product)
+  if (R > INT32_MAX || R * problems > INT32_MAX) return fail(nullptr, VDR_ERR_INVALID, "mahalanobis: problems * R exceeds 2^31 - 1");
+  RUN_OP(launch_mahalanobis(x, ld, image_stride, problem_stride, problems, imgs, t, d, mean, mean_stride, whiten, whiten_stride, k, d2,
+                            (hipStream_t)stream),
+         "mahalanobis");
+}
+
 // ---- profiler ---------------------------------------------------------------------------------------
 int vdr_profile_enable(vdr_handle m, int on) {
   if (!m) return fail(m, VDR_ERR_INVALID, "null handle");

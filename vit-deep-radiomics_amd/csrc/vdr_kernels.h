@@ -368,6 +368,14 @@ hipError_t launch_kmeans_update(const void* x, int64_t ld, int64_t image_stride,
                                 int t, int d, int k, const int32_t* labels, const int32_t* active, void* work, float* centroids,
                                 int32_t* counts, hipStream_t st);
 
+// Squared Mahalanobis distances of bf16 descriptor rows (mahalanobis.hip; the definition is vdr_op_mahalanobis' in
+// include/vdr.h): the k-means operand; the model of problem p at mean + p * mean_stride ([d] fp32) and whiten + p * whiten_stride
+// ([k][d] fp32), a stride of 0 shares it.  d % 32 == 0, 1 <= k <= VDR_MAHALANOBIS_MAX_K; x, mean, whiten and the strides 16-byte
+// aligned; d2 [problems][R] fp32.  One launch, no scratch.
+hipError_t launch_mahalanobis(const void* x, int64_t ld, int64_t image_stride, int64_t problem_stride, int problems, int imgs,
+                              int t, int d, const float* mean, int64_t mean_stride, const float* whiten, int64_t whiten_stride,
+                              int k, float* d2, hipStream_t st);
+
 // pos_embed resampling (pos_interp.hip): the patch rows of a position table from a gh0 x gw0 grid to gh x gw, bicubic
 // (A = -0.75, align_corners = False, border taps clamped), fp64 arithmetic, one rounding to fp32
 hipError_t launch_pos_interp(const float* pos, int gh0, int gw0, int D, float* out, int gh, int gw, hipStream_t s);

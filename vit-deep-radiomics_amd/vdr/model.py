@@ -558,6 +558,64 @@ class VitDescriptorModel:
         bits = self._affinity_graph(x, "lost", layer, facet, bin, hierarchy, float(tau))
         return spectral.lost(bits, tuple(self.engine.grid), k=int(k), stride=int(self.engine.patch_stride), patch=int(self.cfg.patch))
 
+    def _anomaly_args(self, what, layer, facet, bin, hierarchy):
+        """the device-free refusals shared by fit_anomaly and anomaly_map; returns (hierarchy to ask for, block, channels)"""
+        h = self._descriptor_args(layer, facet, bin, False, hierarchy)
+        d = self.cfg.dim * (1 + 8 * h)
+        if d % 32:
+            raise ValueError(f"{what}: {d} descriptor channels; the Mahalanobis kernel takes multiples of 32")
+        return h, (self.cfg.layers - 1 if layer is None else int(layer)), d
+
+    def fit_anomaly(self, batches, layer=None, facet: str = "key", bin: bool = False, per_position: bool = False,
+                    shrinkage: float = 0.01, ridge: float = 0.0, n_components=None, hierarchy: int = 2):
+        """Fit the Gaussian of normal descriptors (vdr.anomaly): `batches` is an iterable of [B, 3, H, W] images of normal
+        cases; per batch ONE forward (vdr_forward_facets) for the bf16 `facet` descriptors of block `layer` (None: the last),
+        log-binned at `hierarchy` when bin, and ONE vdr.ops.covariance call on that buffer in place; the batches are merged in
+        float64 (GaussianAccumulator).  per_position=False: one Gaussian over all patches (Rippel et al.);
+        per_position=True: one per patch position (PaDiM), every batch then on the same grid.  shrinkage / ridge /
+        n_components: vdr.anomaly.whitening.  Returns a vdr.anomaly.Gaussian that remembers the grid.  The input size, patch
+        stride and dynamic_size in force apply.  Refusals (ValueError, before any device work): extract_descriptors' own, a
+        descriptor wider than the covariance kernel's 2048 channels; and a per-position batch on another grid than the first."""
+        from . import anomaly
+        h, i, d = self._anomaly_args("fit_anomaly", layer, facet, bin, hierarchy)
+        if d > 2048:
+            raise ValueError(f"fit_anomaly: {d} descriptor channels; the covariance kernel takes at most 2048")
+        acc = anomaly.GaussianAccumulator(per_position)
+        for x in batches:
+            if x.dim() != 4:
+                raise ValueError(f"fit_anomaly: every batch must be [B, 3, H, W], got {tuple(x.shape)}")
+            self._adopt(x)
+            grid = tuple(self.engine.grid)
+            if acc.grid is None:
+                acc.grid = grid
+            elif per_position and grid != acc.grid:
+                raise ValueError(f"fit_anomaly: a per-position fit needs one grid; got {grid} after {acc.grid}")
+            (desc,), _, _ = self.engine.forward_descriptors(x.to(self.device), [FacetOut(i, facet, h, False, torch.bfloat16)])
+            acc.add(desc)
+        return acc.finish(shrinkage, ridge, n_components)
+
+    def anomaly_map(self, x: torch.Tensor, gaussian, layer=None, facet: str = "key", bin: bool = False, hierarchy: int = 2):
+        """The anomaly map of x [B, 3, H, W] under a fitted vdr.anomaly.Gaussian: ONE forward for the bf16 `facet` descriptors
+        (the arguments of the fit) and ONE vdr.ops.mahalanobis call on that buffer in place -> vdr.anomaly.AnomalyMap
+        (d2 [B, gh, gw], score [B], upsample()).  The input size, patch stride and dynamic_size in force apply.  Refusals
+        (ValueError): extract_descriptors' own, a model of another channel count, a per-position model on another grid."""
+        from . import anomaly
+        h, i, d = self._anomaly_args("anomaly_map", layer, facet, bin, hierarchy)
+        if not isinstance(gaussian, anomaly.Gaussian):
+            raise TypeError("anomaly_map: gaussian must be a vdr.anomaly.Gaussian (fit_anomaly)")
+        if int(gaussian.mean.shape[1]) != d:
+            raise ValueError(f"anomaly_map: the Gaussian has {int(gaussian.mean.shape[1])} channels, the descriptors {d}")
+        if x.dim() != 4:
+            raise ValueError(f"anomaly_map: x must be [B, 3, H, W], got {tuple(x.shape)}")
+        self._adopt(x)
+        gh, gw = self.engine.grid
+        if gaussian.per_position and (gaussian.grid is not None and tuple(gaussian.grid) != (gh, gw)
+                                      or int(gaussian.mean.shape[0]) != gh * gw):
+            raise ValueError(f"anomaly_map: the per-position Gaussian was fitted on the grid {gaussian.grid}, the input gives "
+                             f"{(gh, gw)}")
+        (desc,), _, _ = self.engine.forward_descriptors(x.to(self.device), [FacetOut(i, facet, h, False, torch.bfloat16)])
+        return anomaly.AnomalyMap(gaussian.score(desc).reshape(desc.shape[0], gh, gw))
+
     def pca_descriptors(self, x: torch.Tensor, n_components: int = 3, layer=None, facet=None, joint: bool = False,
                         remove_bg: bool = False) -> torch.Tensor:
         """The reference's pca_colorize (visualization_utils.py:49-69) of every image's dense descriptors, on the device:

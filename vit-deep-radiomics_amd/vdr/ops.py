@@ -786,6 +786,56 @@ def kmeans_update(x, labels: torch.Tensor, centroids: torch.Tensor, joint: bool 
     return centroids, counts
 
 
+MAHALANOBIS_MAX_K = 2048  # VDR_MAHALANOBIS_MAX_K (include/vdr.h)
+
+
+def _mahalanobis_model(v, name: str, inner, problems: int, dev):
+    """A model tensor [problems, *inner] fp32 whose inner block is contiguous; its problem stride in elements (0 for an
+    expand()ed leading dimension: one model under every problem)."""
+    shape = (problems,) + tuple(inner)
+    if not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or tuple(v.shape) != shape:
+        raise ValueError(f"mahalanobis: {name} must be a float32 tensor of shape {shape}, got "
+                         f"{tuple(v.shape) if isinstance(v, torch.Tensor) else type(v).__name__}")
+    if v.device != dev:
+        raise ValueError(f"mahalanobis: {name} must be on x's device")
+    n = 1
+    for s in inner:
+        n *= s
+    stride = v.stride(0) if problems > 1 else n
+    if not v[0].is_contiguous() or (stride != 0 and stride < n) or stride % 4 or v.data_ptr() % 16:
+        v = v.contiguous()
+        stride = n
+    return v, stride
+
+
+def mahalanobis(x, mean: torch.Tensor, whiten: torch.Tensor, joint: bool = False, out=None) -> torch.Tensor:
+    """Squared Mahalanobis distances of descriptor rows (vdr_op_mahalanobis): x as kmeans_operand takes it ([P, t, d], one
+    problem per image or joint=True; or [problems, imgs, t, d]; bf16 read in place, fp32 rounded once to bf16), mean
+    [problems, d] fp32, whiten [problems, k, d] fp32 with contiguous [k, d] blocks, 1 <= k <= 2048 -- an expand()ed leading
+    dimension (stride 0) is one model under every problem.  Returns d2 [problems, R] fp32, d2_i = sum_j (w_j . (x_i - mean))^2:
+    the centred row and the whitening rows are each split into two bf16 operands, three of the four products are taken, and the
+    squares are summed in one fixed order; the R x k matrix is never materialised.  out: a [problems, R] fp32 tensor with
+    contiguous rows to write into.  The exact arithmetic is stated in include/vdr.h."""
+    o = kmeans_operand(x, joint, "mahalanobis")
+    dev = o.x.device
+    if not isinstance(whiten, torch.Tensor) or whiten.dim() != 3:
+        raise ValueError(f"mahalanobis: whiten must be a float32 tensor of shape ({o.problems}, k, {o.d})")
+    k = int(whiten.shape[1])
+    if not 1 <= k <= MAHALANOBIS_MAX_K:
+        raise ValueError(f"mahalanobis: k must be 1..{MAHALANOBIS_MAX_K}, got {k}")
+    mean, ms = _mahalanobis_model(mean, "mean", (o.d,), o.problems, dev)
+    whiten, ws = _mahalanobis_model(whiten, "whiten", (k, o.d), o.problems, dev)
+    if out is None:
+        out = torch.empty((o.problems, o.R), dtype=torch.float32, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (o.problems, o.R) or \
+            out.device != dev or not out.is_contiguous():
+        raise ValueError(f"mahalanobis: out must be a contiguous float32 tensor of shape ({o.problems}, {o.R}) on x's device")
+    lib = L.load()
+    L.check(lib.vdr_op_mahalanobis(o.x.data_ptr(), o.ld, o.image_stride, o.problem_stride, o.problems, o.imgs, o.t, o.d,
+                                   mean.data_ptr(), ms, whiten.data_ptr(), ws, k, out.data_ptr(), _s(o.x)))
+    return out
+
+
 def patch_embed(images, weight, bias, p, pos=None, row_stride=None, row_offset=0, out=None):
     """images [B,C,H,H] fp32/bf16; weight [D,C,p,p] (any float dtype); returns bf16 [B*row_stride, D]."""
     lib = L.load()
