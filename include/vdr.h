@@ -972,6 +972,58 @@ int vdr_op_kmeans_update(const void* x, int64_t ld, int64_t image_stride, int64_
 int vdr_op_mahalanobis(const void* x, int64_t ld, int64_t image_stride, int64_t problem_stride, int problems, int imgs, int t,
                        int d, const float* mean, int64_t mean_stride, const float* whiten, int64_t whiten_stride, int k,
                        float* d2, void* stream);
+/* Joint bilateral upsampling of a dense descriptor map to pixel resolution, guided by the image the descriptors came from
+ * (csrc/upsample.hip; Kopf et al. 2007, the parameter-free filter of FeatUp's JBU up-sampler).
+ * Inputs:
+ *   F      [batch, gh, gw, C] features, f_dtype VDR_BF16 or VDR_F32 (fp32 is rounded ONCE to bf16 when it is staged; below F means
+ *          that bf16 value), read in place: patch (i, j) of image b starts at f + b * image_stride + (i * gw + j) * ld elements.
+ *          A key facet inside a qkv activation has ld = 3C.  C % 8 == 0.
+ *   G      [batch, Cg, H, W] guide, guide_dtype VDR_F32 or VDR_BF16, contiguous NCHW, Cg = 1..4: the image batch itself.
+ *   p, s   patch and stride of the grid, s | p, H = p + (gh - 1) s, W = p + (gw - 1) s.
+ *   r      radius 1..3;  cs = 1 / (2 sigma_s^2 s^2), cr = 1 / (2 sigma_r^2): computed by the caller in double and rounded once to
+ *          fp32 (sigma = inf gives 0);  m [batch, gh, gw] fp32 confidences >= 0, NULL = 1 everywhere.
+ *   box    y0 <= Y < y1, x0 <= X < x1 in pixels, inside the image; out [batch, y1 - y0, x1 - x0, C] channel-last, out_dtype
+ *          VDR_BF16 or VDR_F32.
+ * vdr_op_guide_lowres (the first launch of vdr_op_upsample_guided; on its own it fills the whole grid):
+ *   g_lr[b, g, i, j] = S / float(p * p), one IEEE division, S the fp32 sum, starting from 0.0f, of float(G[b, g, i s + ky, j s + kx])
+ *   in ascending (ky, kx) order, ky outer.                                     work = g_lr [batch, Cg, gh, gw] fp32
+ *   vdr_op_upsample_guided writes only the g_lr of the patches its box can reach (the nearest patches of the box, r further
+ *   each way, inside the grid); the rest of work is not touched.
+ * vdr_op_upsample_guided, for pixel (Y, X) of image b:
+ *   nearest patch  i0 = clamp(floor_div(2Y + 1 - p + s, 2s), 0, gh - 1), j0 likewise from X: integer arithmetic, floor division
+ *     (the numerator can be negative).  p and s of equal parity: no ties; p even and s odd: a tie goes to the upper index.
+ *   window         the positions q = (i0 + a, j0 + b), a, b = -r..r, that lie inside the grid; positions outside do not exist
+ *     (no clamped duplicates).
+ *   weight of q = (i, j), every step ONE fp32 operation (no contraction):
+ *     dy = (2Y + 1 - p - 2 s i) / 2, dx likewise from X and j (exact);  ts = -(dy * dy + dx * dx) * cs (the sum is exact);
+ *     dist2 = sum over g ascending of d_g * d_g, d_g = float(G[b, g, Y, X]) - g_lr[b, g, i, j], starting from 0.0f;
+ *     tr = -dist2 * cr;  t = ts + tr;
+ *     w = 0 when t < -64 (no subnormal reaches a weight or its lo half); else w = expf(t) * m[b, i, j] -- expf is the device
+ *     math library's (OCML __ocml_exp_f32: documented maximum error 1 ulp), the product one rounding (none when m is NULL).
+ *   sum            w_hi = bf16_rn(w), w_lo = bf16_rn(w - float(w_hi)) (the subtraction is exact);
+ *     acc[c] = sum over q of (w_hi[q] + w_lo[q]) * F[q, c]: ONE fp32 accumulation by bf16 MFMAs (the products are exact in
+ *     fp32) over 16 window slots at a time, slot (a + r)(2r + 1) + (b + r) ascending, per 16 slots the products with w_hi and
+ *     then those with w_lo; slots outside the grid and past the window hold zero weights AND zero descriptors (nothing from
+ *     outside the map is ever staged: not other columns of a wider buffer, not rows past the grid, not the next image);
+ *     Z = sum over q of w[q] (the fp32 w), starting from 0.0f, in ascending (a, b) order, a outer;
+ *     out[b, Y - y0, X - x0, c] = acc[c] / Z, one IEEE division, one rounding to out_dtype;  Z == 0: out = F[b, i0, j0, c],
+ *     one rounding to out_dtype.
+ *   No atomics, no scratch beyond work; bitwise reproducible.  A pixel's bits depend on its own image, the parameters and
+ *   (p, s, gh, gw) only -- not on the batch, the position in the batch or the box: the tiles are the cells of the image's patch
+ *   grid (the pixels that share a nearest patch), and the output of a box equals that region of the full-image output bit for
+ *   bit.  Contract: the features inside the map, the guide and the confidences are finite.
+ * work: vdr_upsample_work_bytes(batch, Cg, gh, gw) bytes of device scratch, 16-byte aligned.
+ * Refused before the device is touched: VDR_ERR_UNSUPPORTED for a radius outside 1..3 or Cg outside 1..4; VDR_ERR_INVALID for a
+ * dtype other than the two, null pointers (m excepted), C % 8 != 0, ld < C, a negative image_stride, features / work / out or
+ * strides (ld, image_stride) that are not 16-byte aligned, a guide or m not aligned to its element, non-positive sizes, s not
+ * a divisor of p, H, W that do not match (p, s, gh, gw), an empty box or one outside the image, a box of more than 2^31 - 1
+ * pixels, negative or non-finite cs / cr.  Device offsets are 64-bit. */
+size_t vdr_upsample_work_bytes(int batch, int Cg, int gh, int gw);
+int vdr_op_guide_lowres(const void* guide, int guide_dtype, int batch, int Cg, int H, int W, int p, int s, void* work,
+                        void* stream);
+int vdr_op_upsample_guided(const void* f, int f_dtype, int64_t ld, int64_t image_stride, int batch, int gh, int gw, int C,
+                           const void* guide, int guide_dtype, int Cg, int H, int W, int p, int s, int radius, float cs, float cr,
+                           const float* conf, int y0, int x0, int y1, int x1, void* work, void* out, int out_dtype, void* stream);
 /* ---- measurement ------------------------------------------------------------------------ */
 
 /* Kernel classes timed by the built-in HIP-event profiler. */

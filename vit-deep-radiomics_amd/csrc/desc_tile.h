@@ -1,4 +1,4 @@
-// The tile core of the descriptor-analysis kernels (nn_cosine.hip, pca.hip, kmeans.hip, mahalanobis.hip): one 128 x 128 fp32 tile per workgroup
+// The tile core of the descriptor-analysis kernels (nn_cosine.hip, pca.hip, kmeans.hip, mahalanobis.hip, upsample.hip): one 128 x 128 fp32 tile per workgroup
 // of 4 waves, wave (wr, wc) = (wave >> 1, wave & 1) owning the 64 x 64 sub-tile at (64 wr, 64 wc) as 2 x 2
 // mfma_f32_32x32x16_bf16 accumulators.  Every piece that fixes the BITS of a result -- the accumulator layout, the k order of
 // the MFMA steps, the comparator folds, the ascending sums -- is written once here; the kernels keep what is theirs (centring,
@@ -171,6 +171,33 @@ VDR_DEV void tr_mfma(tr_lds_cptr imgA, tr_lds_cptr imgB, int wr, int wc, int lan
     for (int m = 0; m < 2; ++m)
 #pragma unroll
       for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[m], bf[n], acc[m][n], 0, 0, 0);
+  }
+}
+
+// the first NKS MFMA k-steps of a staged step with TWO A images against ONE B image accumulated into the same tile
+// (upsample.hip: the hi and the lo half of the weights against the window's descriptors; its window fills NKS * 16 rows): per
+// 16-row k-step the products with a0, then those with a1
+template <int NKS>
+VDR_DEV void tr_mfma_2a(tr_lds_cptr imgA0, tr_lds_cptr imgA1, tr_lds_cptr imgB, int wr, int wc, int lane, f32x16 (&acc)[2][2]) {
+  static_assert(NKS >= 1 && NKS <= TR_STEP / 16, "k-steps of one staged step");
+#pragma unroll
+  for (int ks = 0; ks < NKS; ++ks) {
+    bf16x8 a0[2], a1[2], bf[2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      a0[m] = tr_read(imgA0, ks, wr * 64 + m * 32, lane);
+      a1[m] = tr_read(imgA1, ks, wr * 64 + m * 32, lane);
+    }
+#pragma unroll
+    for (int n = 0; n < 2; ++n) bf[n] = tr_read(imgB, ks, wc * 64 + n * 32, lane);
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[m], bf[n], acc[m][n], 0, 0, 0);
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[m], bf[n], acc[m][n], 0, 0, 0);
   }
 }
 

@@ -2926,6 +2926,67 @@ int vdr_op_mahalanobis(const void* x, int64_t ld, int64_t image_stride, int64_t 
          "mahalanobis");
 }
 
+size_t vdr_upsample_work_bytes(int batch, int Cg, int gh, int gw) { return upsample_work_bytes(batch, Cg, gh, gw); }
+
+// the guide and the geometry shared by the two upsampling ops (include/vdr.h); sets gh, gw
+static int upsample_guide(const char* op, const void* guide, int guide_dtype, int batch, int Cg, int H, int W, int p, int s,
+                          int* gh, int* gw) {
+  static thread_local char msg[160];
+  const auto refuse = [&](int code, const char* what) {
+    snprintf(msg, sizeof msg, "%s: %s", op, what);
+    return fail(nullptr, code, msg);
+  };
+  if (guide_dtype != VDR_F32 && guide_dtype != VDR_BF16) return refuse(VDR_ERR_INVALID, "guide_dtype must be VDR_F32 or VDR_BF16");
+  if (!guide) return refuse(VDR_ERR_INVALID, "null guide");
+  if (Cg < 1 || Cg > 4) return refuse(VDR_ERR_UNSUPPORTED, "the guide must have 1..4 channels");
+  if (batch <= 0 || p <= 0 || s <= 0 || H <= 0 || W <= 0) return refuse(VDR_ERR_INVALID, "batch, patch, stride, H and W must be positive");
+  if (p > 4096 || H > (1 << 24) || W > (1 << 24)) return refuse(VDR_ERR_INVALID, "patch above 4096 or a side above 2^24");
+  if (p % s) return refuse(VDR_ERR_INVALID, "stride must divide patch");
+  if (H < p || W < p || (H - p) % s || (W - p) % s)
+    return refuse(VDR_ERR_INVALID, "H and W must be patch + (gh - 1) stride and patch + (gw - 1) stride");
+  if ((uintptr_t)guide % (guide_dtype == VDR_BF16 ? 2 : 4)) return refuse(VDR_ERR_INVALID, "guide is not aligned to its element");
+  *gh = (H - p) / s + 1;
+  *gw = (W - p) / s + 1;
+  if ((int64_t)batch * Cg * *gh * *gw > INT32_MAX) return refuse(VDR_ERR_INVALID, "batch * Cg * gh * gw exceeds 2^31 - 1");
+  return VDR_OK;
+}
+
+int vdr_op_guide_lowres(const void* guide, int guide_dtype, int batch, int Cg, int H, int W, int p, int s, void* work, void* stream) {
+  int gh, gw;
+  if (int rc = upsample_guide("guide_lowres", guide, guide_dtype, batch, Cg, H, W, p, s, &gh, &gw)) return rc;
+  if (!work || !aligned16({work})) return fail(nullptr, VDR_ERR_INVALID, "guide_lowres: work must be non-null and 16-byte aligned");
+  RUN_OP(launch_guide_lowres(guide, guide_dtype == VDR_BF16, batch, Cg, H, W, p, s, gh, gw, (float*)work, (hipStream_t)stream),
+         "guide_lowres");
+}
+
+int vdr_op_upsample_guided(const void* f, int f_dtype, int64_t ld, int64_t image_stride, int batch, int gh, int gw, int C,
+                           const void* guide, int guide_dtype, int Cg, int H, int W, int p, int s, int radius, float cs, float cr,
+                           const float* conf, int y0, int x0, int y1, int x1, void* work, void* out, int out_dtype, void* stream) {
+  if ((f_dtype != VDR_F32 && f_dtype != VDR_BF16) || (out_dtype != VDR_F32 && out_dtype != VDR_BF16))
+    return fail(nullptr, VDR_ERR_INVALID, "upsample_guided: dtype");
+  if (!f || !work || !out) return fail(nullptr, VDR_ERR_INVALID, "upsample_guided: null features, work or out");
+  if (radius < 1 || radius > 3) return fail(nullptr, VDR_ERR_UNSUPPORTED, "upsample_guided: radius must be 1, 2 or 3");
+  int ggh, ggw;
+  if (int rc = upsample_guide("upsample_guided", guide, guide_dtype, batch, Cg, H, W, p, s, &ggh, &ggw)) return rc;
+  if (gh != ggh || gw != ggw)
+    return fail(nullptr, VDR_ERR_INVALID, "upsample_guided: H and W must be patch + (gh - 1) stride and patch + (gw - 1) stride");
+  if (C <= 0 || C % 8 != 0) return fail(nullptr, VDR_ERR_INVALID, "upsample_guided: C must be a positive multiple of 8");
+  if (ld < C || image_stride < 0) return fail(nullptr, VDR_ERR_INVALID, "upsample_guided: ld must be >= C, image_stride >= 0");
+  const int64_t per16 = f_dtype == VDR_BF16 ? 8 : 4;  // elements of a 16-byte chunk
+  if (!aligned16({f, work, out}) || ld % per16 || image_stride % per16 || (uintptr_t)conf % 4)
+    return fail(nullptr, VDR_ERR_INVALID,
+                "upsample_guided: features, work, out and every row (ld, image_stride) must be 16-byte aligned, confidence 4-byte aligned");
+  if (y0 < 0 || x0 < 0 || y1 > H || x1 > W || y0 >= y1 || x0 >= x1)
+    return fail(nullptr, VDR_ERR_INVALID, "upsample_guided: the box must be non-empty and inside the image");
+  if ((int64_t)(y1 - y0) * (x1 - x0) > INT32_MAX)
+    return fail(nullptr, VDR_ERR_INVALID, "upsample_guided: the box has more than 2^31 - 1 pixels");
+  if (!(cs >= 0.0f) || !(cr >= 0.0f) || cs > 3.0e38f || cr > 3.0e38f)
+    return fail(nullptr, VDR_ERR_INVALID, "upsample_guided: cs and cr must be finite and >= 0");
+  RUN_OP(launch_upsample_guided(f, f_dtype == VDR_BF16, ld, image_stride, batch, gh, gw, C, guide, guide_dtype == VDR_BF16, Cg, H, W, p,
+                                s, radius, cs, cr, conf, y0, x0, y1, x1, (float*)work, out, out_dtype == VDR_BF16, (hipStream_t)stream),
+         "upsample_guided");
+}
+
 // ---- profiler ---------------------------------------------------------------------------------------
 int vdr_profile_enable(vdr_handle m, int on) {
   if (!m) return fail(m, VDR_ERR_INVALID, "null handle");

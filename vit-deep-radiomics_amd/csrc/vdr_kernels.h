@@ -376,6 +376,19 @@ hipError_t launch_mahalanobis(const void* x, int64_t ld, int64_t image_stride, i
                               int t, int d, const float* mean, int64_t mean_stride, const float* whiten, int64_t whiten_stride,
                               int k, float* d2, hipStream_t st);
 
+// Joint bilateral upsampling of descriptor maps (upsample.hip; the definitions are vdr_op_guide_lowres' and
+// vdr_op_upsample_guided's in include/vdr.h): features [batch][gh][gw][C] read through ld / image_stride, guide
+// [batch][Cg][H][W] contiguous, H = p + (gh - 1) s, box [y0, y1) x [x0, x1) inside the image, out [batch][y1 - y0][x1 - x0][C].
+// C % 8 == 0, radius 1..3, Cg 1..4, s | p; features and strides 16-byte aligned; work: upsample_work_bytes(...) bytes.  Two
+// launches: the low-resolution guide of the patches the box reaches, then the tile kernel.
+size_t upsample_work_bytes(int batch, int Cg, int gh, int gw);
+hipError_t launch_guide_lowres(const void* guide, bool guide_bf16, int batch, int Cg, int H, int W, int p, int s, int gh, int gw,
+                               float* work, hipStream_t st);
+hipError_t launch_upsample_guided(const void* f, bool f_bf16, int64_t ld, int64_t image_stride, int batch, int gh, int gw, int C,
+                                  const void* guide, bool guide_bf16, int Cg, int H, int W, int p, int s, int radius, float cs,
+                                  float cr, const float* conf, int y0, int x0, int y1, int x1, float* work, void* out, bool out_bf16,
+                                  hipStream_t st);
+
 // pos_embed resampling (pos_interp.hip): the patch rows of a position table from a gh0 x gw0 grid to gh x gw, bicubic
 // (A = -0.75, align_corners = False, border taps clamped), fp64 arithmetic, one rounding to fp32
 hipError_t launch_pos_interp(const float* pos, int gh0, int gw0, int D, float* out, int gh, int gw, hipStream_t s);

@@ -139,6 +139,10 @@ SYMBOLS = {
     "vdr_op_kmeans_assign": (_I, [_P, _L, _L, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vdr_op_kmeans_update": (_I, [_P, _L, _L, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vdr_op_mahalanobis": (_I, [_P, _L, _L, _L, _I, _I, _I, _I, _P, _L, _P, _L, _I, _P, _P]),
+    "vdr_upsample_work_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "vdr_op_guide_lowres": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "vdr_op_upsample_guided": (_I, [_P, _I, _L, _L, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P, _I, _I, _I, _I,
+                                    _P, _P, _I, _P]),
     "vdr_profile_enable": (_I, [_P, _I]),
     "vdr_profile_mask": (_I, [_P, C.c_uint32]),
     "vdr_profile_read": (_I, [_P, C.POINTER(C.c_double), C.POINTER(_L), C.POINTER(C.c_double),

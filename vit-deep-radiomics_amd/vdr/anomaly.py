@@ -192,3 +192,28 @@ class AnomalyMap:
         pixels when sigma > 0 (PaDiM: 4)"""
         up = torch.nn.functional.interpolate(self.d2.unsqueeze(1), size=tuple(size), mode="bilinear", align_corners=False).squeeze(1)
         return gaussian_blur(up, sigma) if sigma > 0 else up
+
+    def upsample_guided(self, x: torch.Tensor, box=None, patch=None, stride=None, radius: int = 2, sigma_spatial: float = 1.0,
+                        sigma_range: float = 0.1) -> torch.Tensor:
+        """the map at the pixels of `box` = (y0, x0, y1, x1) of the images x [B, Cg, H, W] the map was computed from (None: the
+        whole image), by joint bilateral upsampling guided by x (vdr.upsample.guided): [B, h, w] fp32 whose edges follow the
+        image's instead of the patch borders.  patch / stride: the grid's geometry; None takes non-overlapping patches of
+        H // gh pixels.  The filter is linear in the map, so d2 enters as three bf16 channels hi + mid + lo (24 significant
+        bits: nothing of the fp32 distances is lost to the op's bf16 operand) that are added up again."""
+        from . import upsample
+        if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[0] != self.d2.shape[0]:
+            raise ValueError(f"upsample_guided: x must be the [B, Cg, H, W] images of the map, B = {self.d2.shape[0]}")
+        gh, gw = int(self.d2.shape[1]), int(self.d2.shape[2])
+        if patch is None:
+            if x.shape[2] % gh or x.shape[3] % gw or x.shape[2] // gh != x.shape[3] // gw:
+                raise ValueError(f"upsample_guided: a {x.shape[2]} x {x.shape[3]} image over a {gh} x {gw} grid of overlapping or "
+                                 "non-square patches needs patch and stride")
+            patch = x.shape[2] // gh
+        stride = patch if stride is None else stride
+        d2 = self.d2.float()
+        hi = d2.to(torch.bfloat16).float()
+        mid = (d2 - hi).to(torch.bfloat16).float()
+        lo = (d2 - hi - mid).to(torch.bfloat16).float()
+        up = upsample.guided(torch.stack((hi, mid, lo), dim=-1), x.to(d2.device), patch, stride, radius=radius,
+                             sigma_spatial=sigma_spatial, sigma_range=sigma_range, box=box, out_dtype=torch.float32)
+        return up[..., 0] + up[..., 1] + up[..., 2]

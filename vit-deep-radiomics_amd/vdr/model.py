@@ -438,6 +438,54 @@ class VitDescriptorModel:
             return got.reshape(got.shape[0], gh, gw, got.shape[-1])
         return got.unsqueeze(1)
 
+    def upsample_descriptors(self, x: torch.Tensor, layer=None, facet="key", bin: bool = False, hierarchy: int = 2, box=None,
+                             radius: int = 2, sigma_spatial: float = 1.0, sigma_range: float = 0.1,
+                             out_dtype=torch.bfloat16) -> torch.Tensor:
+        """Dense descriptors at PIXEL resolution by joint bilateral upsampling guided by x itself (vdr.upsample,
+        csrc/upsample.hip): [B, 3, H, W] -> [B, h', w', d] over `box` = (y0, x0, y1, x1) in pixels (None: the whole image), at a
+        cost that does not depend on the transformer -- the alternative to a larger input or a finer patch stride.  ONE
+        forward_descriptors call for the bf16 `facet` descriptors of block `layer` (extract_descriptors' arguments, bin and
+        hierarchy included) and ONE vdr.ops.upsample_guided call on that buffer in place.  facet=None takes the model's own
+        dense descriptor in fp32 (the SAM neck output for 'medsam', patch_embed otherwise; rounded once to bf16 by the op).
+        sigma_spatial is in grid units (patch strides), sigma_range in units of x.  The input size, patch stride and
+        dynamic_size in force apply.  Refusals (ValueError, before any device work): extract_descriptors' own, a layer or bin
+        without a facet, and the op's (radius outside 1..3, a box outside the image, non-positive sigmas)."""
+        from . import ops
+        h = 0
+        if facet is not None:
+            h = self._descriptor_args(layer, facet, bool(bin), False, hierarchy)
+        elif layer is not None or bin:
+            raise ValueError("upsample_descriptors: layer and bin need a facet")
+        if not isinstance(x, torch.Tensor) or x.dim() != 4:
+            raise ValueError(f"upsample_descriptors: x must be [B, 3, H, W], got {tuple(getattr(x, 'shape', ()))}")
+        if not 1 <= int(radius) <= ops.UPSAMPLE_MAX_RADIUS:
+            raise ValueError(f"upsample_descriptors: radius must be 1..{ops.UPSAMPLE_MAX_RADIUS}, got {radius}")
+        if out_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"upsample_descriptors: out_dtype must be float32 or bfloat16, got {out_dtype}")
+        ops.upsample_coefficients(1, sigma_spatial, sigma_range)
+        H, W = int(x.shape[-2]), int(x.shape[-1])
+        if box is not None:
+            y0, x0, y1, x1 = (int(v) for v in box)
+            if not (0 <= y0 < y1 <= H and 0 <= x0 < x1 <= W):
+                raise ValueError(f"upsample_descriptors: box {tuple(box)} must be non-empty and inside the {H} x {W} image")
+        guide = x if x.dtype in (torch.float32, torch.bfloat16) else x.float()
+        guide = guide.to(self.device)
+        if self.cfg.window > 0:
+            desc = self.engine.forward(x, L.OUT_ENCODER, torch.float32)  # [B, g, g, C], channel-last
+            p = s = self.cfg.patch
+        else:
+            self._adopt(x)
+            gh, gw = self.engine.grid
+            p, s = int(self.cfg.patch), int(self.engine.patch_stride)
+            if facet is None:
+                desc = self.engine.forward(x, L.OUT_PATCH_EMBED, torch.float32)
+            else:
+                i = self.cfg.layers - 1 if layer is None else int(layer)
+                (desc,), _, _ = self.engine.forward_descriptors(x, [FacetOut(i, facet, h, False, torch.bfloat16)])
+            desc = desc.reshape(desc.shape[0], gh, gw, desc.shape[-1])
+        return ops.upsample_guided(desc, guide, p, s, radius=int(radius), sigma_spatial=sigma_spatial, sigma_range=sigma_range,
+                                   box=box, out_dtype=out_dtype)
+
     def find_correspondences(self, x1: torch.Tensor, x2: torch.Tensor, layer=None, facet: str = "key", bin: bool = True,
                              hierarchy: int = 2, thresh: float = 0.05, keep_descriptors: bool = False) -> Correspondences:
         """dino-vit-features' point correspondences: mutual cosine nearest neighbours ("best buddies") between the

@@ -836,6 +836,128 @@ def mahalanobis(x, mean: torch.Tensor, whiten: torch.Tensor, joint: bool = False
     return out
 
 
+UPSAMPLE_MAX_RADIUS = 3
+UPSAMPLE_MAX_GUIDE_CHANNELS = 4
+
+
+def _dt(t):
+    return L.VDR_BF16 if t.dtype == torch.bfloat16 else L.VDR_F32
+
+
+def _upsample_guide(guide, patch, stride, op: str):
+    """(B, Cg, H, W, p, s, gh, gw) of a guide batch under a patch grid, or the ValueError / TypeError of a bad one"""
+    if not isinstance(guide, torch.Tensor) or guide.dim() != 4 or guide.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{op}: guide must be a [B, Cg, H, W] float32 or bfloat16 tensor")
+    p, s = int(patch), int(stride)
+    if p <= 0 or s <= 0 or p % s:
+        raise ValueError(f"{op}: stride must be positive and divide patch, got patch {patch}, stride {stride}")
+    B, Cg, H, W = guide.shape
+    if B <= 0:
+        raise ValueError(f"{op}: empty batch")
+    if not 1 <= Cg <= UPSAMPLE_MAX_GUIDE_CHANNELS:
+        raise ValueError(f"{op}: the guide must have 1..{UPSAMPLE_MAX_GUIDE_CHANNELS} channels, got {Cg}")
+    if H < p or W < p or (H - p) % s or (W - p) % s:
+        raise ValueError(f"{op}: a {H} x {W} guide is no patch + (g - 1) * stride grid of patch {p}, stride {s}")
+    return B, Cg, H, W, p, s, (H - p) // s + 1, (W - p) // s + 1
+
+
+def upsample_coefficients(stride: int, sigma_spatial: float, sigma_range: float):
+    """(cs, cr) = (1 / (2 sigma_s^2 s^2), 1 / (2 sigma_r^2)) in double; sigma = inf gives 0.  The op rounds them once to fp32."""
+    ss, sr = float(sigma_spatial), float(sigma_range)
+    if not ss > 0.0 or not sr > 0.0:  # (NaN fails both)
+        raise ValueError(f"upsample_guided: sigma_spatial and sigma_range must be > 0 (inf allowed), got {sigma_spatial}, {sigma_range}")
+    cs = 0.0 if ss == float("inf") else 1.0 / (2.0 * ss * ss * float(stride) * float(stride))
+    cr = 0.0 if sr == float("inf") else 1.0 / (2.0 * sr * sr)
+    if cs > 3.0e38 or cr > 3.0e38:
+        raise ValueError("upsample_guided: a sigma so small that its coefficient overflows fp32")
+    return cs, cr
+
+
+def guide_lowres(guide: torch.Tensor, patch: int, stride: int) -> torch.Tensor:
+    """The low-resolution guide of upsample_guided alone (vdr_op_guide_lowres): guide [B, Cg, H, W] fp32 or bf16 -> [B, Cg, gh,
+    gw] fp32, the mean of the guide over each patch's p x p footprint (fp32 sum in ascending (ky, kx), one IEEE division)."""
+    B, Cg, H, W, p, s, gh, gw = _upsample_guide(guide, patch, stride, "guide_lowres")
+    if not guide.is_cuda:
+        raise TypeError("guide_lowres: guide must live on the HIP device")
+    lib = L.load()
+    guide = guide.contiguous()
+    work = torch.empty((lib.vdr_upsample_work_bytes(B, Cg, gh, gw) // 4,), dtype=torch.float32, device=guide.device)
+    L.check(lib.vdr_op_guide_lowres(guide.data_ptr(), _dt(guide), B, Cg, H, W, p, s, work.data_ptr(), _s(guide)))
+    return work[:B * Cg * gh * gw].view(B, Cg, gh, gw)
+
+
+def upsample_guided(features: torch.Tensor, guide: torch.Tensor, patch: int, stride: int, radius: int = 2,
+                    sigma_spatial: float = 1.0, sigma_range: float = 0.1, confidence=None, box=None, out_dtype=None, out=None,
+                    work=None) -> torch.Tensor:
+    """Joint bilateral upsampling of a descriptor map to pixel resolution (vdr_op_upsample_guided): features [B, gh, gw, C]
+    bf16 or fp32 (rounded once to bf16) -- contiguous, or a view with contiguous channels whose patch rows are evenly spaced
+    (the key columns of a qkv activation: read in place) --, guide [B, Cg, H, W] fp32 or bf16, the image batch the features
+    came from, H = patch + (gh - 1) * stride.  sigma_spatial is in patch-grid units (strides), sigma_range in guide units;
+    confidence [B, gh, gw] fp32 >= 0 scales each patch's weight.  box = (y0, x0, y1, x1), half-open, in pixels (None: the
+    whole image).  Returns [B, y1 - y0, x1 - x0, C] in out_dtype (default: the features' dtype); a box's output equals that
+    region of the full output bit for bit.  The exact arithmetic is stated in include/vdr.h."""
+    op = "upsample_guided"
+    if not isinstance(features, torch.Tensor) or features.dim() != 4 or features.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{op}: features must be a [B, gh, gw, C] float32 or bfloat16 tensor")
+    B, Cg, H, W, p, s, gh, gw = _upsample_guide(guide, patch, stride, op)
+    if tuple(features.shape[:3]) != (B, gh, gw):
+        raise ValueError(f"{op}: features {tuple(features.shape)} do not lie on the {B} x {gh} x {gw} grid of the guide")
+    Cc = features.shape[3]
+    if Cc <= 0 or Cc % 8:
+        raise ValueError(f"{op}: C must be a positive multiple of 8, got {Cc}")
+    r = int(radius)
+    if not 1 <= r <= UPSAMPLE_MAX_RADIUS:
+        raise ValueError(f"{op}: radius must be 1..{UPSAMPLE_MAX_RADIUS}, got {radius}")
+    cs, cr = upsample_coefficients(s, sigma_spatial, sigma_range)
+    if box is None:
+        box = (0, 0, H, W)
+    y0, x0, y1, x1 = (int(v) for v in box)
+    if not (0 <= y0 < y1 <= H and 0 <= x0 < x1 <= W):
+        raise ValueError(f"{op}: box {tuple(box)} must be non-empty and inside the {H} x {W} image")
+    if out_dtype is None:
+        out_dtype = features.dtype
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"out_dtype must be float32 or bfloat16, got {out_dtype}")
+    if confidence is not None and (not isinstance(confidence, torch.Tensor) or confidence.dtype != torch.float32 or
+                                   tuple(confidence.shape) != (B, gh, gw)):
+        raise ValueError(f"{op}: confidence must be a float32 tensor of shape ({B}, {gh}, {gw})")
+    if Cc > 1 and features.stride(3) != 1:
+        raise ValueError(f"{op}: the channels of features must be contiguous")
+    if not features.is_cuda or not guide.is_cuda or (confidence is not None and not confidence.is_cuda):
+        raise TypeError(f"{op}: features, guide and confidence must live on the HIP device")
+    if guide.device != features.device or (confidence is not None and confidence.device != features.device):
+        raise ValueError(f"{op}: features, guide and confidence must be on the same device")
+    per16 = 8 if features.dtype == torch.bfloat16 else 4
+    ld = features.stride(2) if gw > 1 else features.stride(1) if gh > 1 else Cc
+    if gh > 1 and features.stride(1) != gw * ld:
+        ld = -1  # (patch rows not evenly spaced: a copy)
+    image_stride = features.stride(0) if B > 1 else 0
+    if ld < Cc or ld % per16 or image_stride < 0 or image_stride % per16 or features.data_ptr() % 16:
+        features = features.contiguous()
+        ld, image_stride = Cc, gh * gw * Cc
+    lib = L.load()
+    dev = features.device
+    guide = guide.contiguous()
+    if confidence is not None:
+        confidence = confidence.contiguous()
+    shape = (B, y1 - y0, x1 - x0, Cc)
+    if out is None:
+        out = torch.empty(shape, dtype=out_dtype, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.dtype != out_dtype or tuple(out.shape) != shape or out.device != dev or \
+            not out.is_contiguous():
+        raise ValueError(f"{op}: out must be a contiguous {out_dtype} tensor of shape {shape} on the features' device")
+    need = lib.vdr_upsample_work_bytes(B, Cg, gh, gw)
+    if work is None:
+        work = torch.empty((need // 4,), dtype=torch.float32, device=dev)
+    elif not isinstance(work, torch.Tensor) or work.dtype != torch.float32 or work.device != dev or not work.is_contiguous() or \
+            work.numel() * 4 < need:
+        raise ValueError(f"{op}: work must be a contiguous float32 tensor of at least {need // 4} elements on the features' device")
+    L.check(lib.vdr_op_upsample_guided(features.data_ptr(), _dt(features), ld, image_stride, B, gh, gw, Cc, guide.data_ptr(),
+                                       _dt(guide), Cg, H, W, p, s, r, cs, cr, _p(confidence), y0, x0, y1, x1, work.data_ptr(),
+                                       out.data_ptr(), _dt(out), _s(features)))
+    return out
+
+
 def patch_embed(images, weight, bias, p, pos=None, row_stride=None, row_offset=0, out=None):
     """images [B,C,H,H] fp32/bf16; weight [D,C,p,p] (any float dtype); returns bf16 [B*row_stride, D]."""
     lib = L.load()

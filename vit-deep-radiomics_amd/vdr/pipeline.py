@@ -92,12 +92,26 @@ def generate_features(model, img_3d, mask_3d, flip=None, max_batch=16, descripto
 
     descriptor (None: the reference's maps, as above): a dict of VitDescriptorModel.extract_descriptors' keywords --
     layer, facet, bin, hierarchy -- for facet descriptors instead (ViT / DINOv2 / CLIP models): the per-slice maps are
-    (h', w', d) with d = D, or (1 + 8*hierarchy)*D with bin=True; the ROI crop works on that channel count."""
-    desc = None
+    (h', w', d) with d = D, or (1 + 8*hierarchy)*D with bin=True; the ROI crop works on that channel count.
+    descriptor["upsample"] (a dict of radius, sigma_spatial, sigma_range; {} for the defaults): the descriptors come at PIXEL
+    resolution by guided upsampling (VitDescriptorModel.upsample_descriptors, guided by the prepared slice itself).  The ROI
+    box of the feature maps is then taken in pixel coordinates of the prepared slice and only that box is upsampled; the mask
+    crops are taken from the mask resampled (nearest) to the prepared slice under the same box, so the feature crops and the
+    mask crops have the same height and width.  Without the key the function is what it was."""
+    desc = up = None
     if descriptor is not None:
-        unknown = set(descriptor) - {"layer", "facet", "bin", "hierarchy"}
+        unknown = set(descriptor) - {"layer", "facet", "bin", "hierarchy", "upsample"}
         if unknown:
-            raise ValueError(f"descriptor: unknown keys {sorted(unknown)} (layer, facet, bin, hierarchy)")
+            raise ValueError(f"descriptor: unknown keys {sorted(unknown)} (layer, facet, bin, hierarchy, upsample)")
+        if descriptor.get("upsample") is not None:
+            up = dict(descriptor["upsample"])
+            unknown = set(up) - {"radius", "sigma_spatial", "sigma_range"}
+            if unknown:
+                raise ValueError(f"descriptor['upsample']: unknown keys {sorted(unknown)} (radius, sigma_spatial, sigma_range)")
+            from . import ops
+            if not 1 <= int(up.get("radius", 2)) <= ops.UPSAMPLE_MAX_RADIUS:
+                raise ValueError(f"descriptor['upsample']: radius must be 1..{ops.UPSAMPLE_MAX_RADIUS}, got {up['radius']}")
+            ops.upsample_coefficients(1, up.get("sigma_spatial", 1.0), up.get("sigma_range", 0.1))
         desc = {"layer": descriptor.get("layer"), "facet": descriptor.get("facet", "key"), "bin": bool(descriptor.get("bin", False)),
                 "hierarchy": int(descriptor.get("hierarchy", 2))}
         model._descriptor_args(desc["layer"], desc["facet"], desc["bin"], False, desc["hierarchy"])  # (before any device work)
@@ -138,6 +152,21 @@ def generate_features(model, img_3d, mask_3d, flip=None, max_batch=16, descripto
         # for bit); written as bf16 here they are half the bytes, and for p = 16 (MedSAM) the GEMM gathers them straight
         # from the images (no im2col pass)
         x = prep.prepare_slices(vol[:, :, s0:s1], side=model.cfg.img, flip=flip, out_dtype=torch.bfloat16, device=model.device)
+        if up is not None:
+            if rb is None:  # (pixel coordinates of the prepared slice; the masks resampled to it, nearest)
+                side_hw = tuple(int(v) for v in x.shape[-2:])
+                rb = mb = roi_box(side_hw, bigger_c)
+                ry = (np.arange(side_hw[0]) * mask_c.shape[0]) // side_hw[0]
+                rx = (np.arange(side_hw[1]) * mask_c.shape[1]) // side_hw[1]
+                mask_c = mask_c[ry][:, rx]
+            by0, by1, bx0, bx1 = crop_box(x.shape[-2:], *rb)
+            if by1 <= by0 or bx1 <= bx0:
+                raise ValueError(f"generate_features: the ROI box {rb} lies outside the prepared slice")
+            crops = model.upsample_descriptors(x, box=(by0, bx0, by1, bx1), out_dtype=torch.float32, **desc, **up)
+            host = torch.empty(crops.shape, dtype=crops.dtype, pin_memory=True)
+            host.copy_(crops, non_blocking=True)
+            pending.append((host, s0, s1))
+            continue
         if desc is not None:
             maps = model.extract_descriptors(x, reshape=True, **desc)             # [b, gh, gw, d] channel-last
         elif medsam:
