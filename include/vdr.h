@@ -296,7 +296,17 @@ const char* vdr_weight_name(vdr_handle h, int i);
 /* ---- the hot path ----------------------------------------------------------------------- */
 
 /* Bytes of device workspace vdr_forward / vdr_forward_tokens need for `batch`
- * images (token models: `batch` sequences of `seq` tokens, seq ignored otherwise). */
+ * images (token models: `batch` sequences of `seq` tokens, seq ignored otherwise).
+ * The workspace contract, of every entry point that takes (workspace, workspace_bytes) -- vdr_forward, vdr_forward_layers,
+ * vdr_forward_attn_maps, vdr_forward_facets, vdr_forward_tokens, vdr_forward_tokens_varlen:
+ *   - the contents of `workspace` on entry are irrelevant: any bits, NaN under every element type included, give the
+ *     same outputs bit for bit (nothing is read before the call has written it);
+ *   - the call reads and writes device memory only inside [workspace, workspace + vdr_workspace_bytes), its inputs,
+ *     its outputs and the handle's own weights; the padding rows its kernels read lie inside that range;
+ *   - the contents on return are unspecified, and nothing is kept in it between calls;
+ *   - workspace_bytes below vdr_workspace_bytes: VDR_ERR_WORKSPACE, and neither the workspace nor any output has been
+ *     written.
+ * tests/test_workspace_contract_gpu.py holds every kind of forward to this between canary guards. */
 int vdr_workspace_bytes(vdr_handle h, int batch, int seq, size_t* out);
 
 /* Replaces: model.image_encoder(x) / model.patch_embed(x)
@@ -415,7 +425,9 @@ int vdr_forward_tokens_varlen(vdr_handle h, const void* tokens, int in_dtype, in
 
 /* F.layer_norm(x, (D,), gamma, beta, eps)  — nn.LayerNorm at models_archs.py:136,145 and
  * norm1/norm2/norm of the ViT blocks.  x [rows, D] in_dtype -> y [rows, D] out_dtype;
- * gamma/beta fp32 [D]. */
+ * gamma/beta fp32 [D].  rows >= 1 (else VDR_ERR_INVALID); D a positive multiple of 4, at most 2048 (else
+ * VDR_ERR_UNSUPPORTED).  Alignment (a lane moves 4 elements per access): x and y to 4 elements of their type -- 8 bytes
+ * for bf16, 16 for fp32 -- gamma and beta to 16 bytes; anything else is VDR_ERR_INVALID before the device is touched. */
 int vdr_op_layernorm(const void* x, int in_dtype, void* y, int out_dtype, const float* gamma,
                      const float* beta, int64_t rows, int D, float eps, void* stream);
 
@@ -443,7 +455,10 @@ typedef enum {
  *   x [M, K] bf16, W [N, K] bf16 (PyTorch layout), bias fp32 [N] or NULL,
  *   resid [M, N] bf16 (EPI_BIAS_RESID; may alias y), gamma fp32 [N] or NULL (LayerScale),
  *   y [M, N] bf16 (EPI_SWIGLU: [M, N/2]).  K % 64 == 0, N % 8 == 0.
- *   `variant` selects the tile configuration (0 = library default). */
+ *   `variant` selects the tile configuration (0 = library default).
+ *   Alignment: x, W, bias, resid, gamma and y each to 16 bytes (16-byte operand loads of x and W, f32x4 loads of bias and
+ *   gamma, bf16x8 loads of resid and stores of y; with K % 64 == 0 and N % 8 == 0 every row then is).  A pointer off
+ *   that boundary is VDR_ERR_INVALID before the device is touched; the same for vdr_op_linear_packed. */
 int vdr_op_linear(const void* x, const void* W, const float* bias, const void* resid,
                   const float* gamma, void* y, int64_t M, int N, int K, int epilogue, int variant,
                   void* stream);
@@ -564,7 +579,8 @@ int vdr_op_voxel_sequence(const float* feat, const int64_t* index, const double*
  *   out [batch*seq, H*64] bf16;  softmax(q k^T / 8) v per (batch, head), no mask.
  *   variant: 0 = library choice; 1 = chunked (online softmax over 128-key chunks), 2 = persistent kernel without,
  *   4 = with its loader wave (sequences of 129..224 tokens), 3 = one workgroup per (batch, head).  All variants
- *   produce the same bits for sequences that fit one chunk. */
+ *   produce the same bits for sequences that fit one chunk.
+ *   batch, seq or heads <= 0: VDR_ERR_INVALID (also vdr_op_attention_hd and vdr_op_attention_varlen). */
 int vdr_op_attention(const void* qkv, void* out, int batch, int seq, int heads, int variant,
                      void* stream);
 

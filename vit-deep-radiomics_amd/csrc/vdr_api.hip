@@ -2222,9 +2222,22 @@ static int op_gemm(const GemmArgs& g, int epilogue, int variant, void* stream, c
   return VDR_OK;
 }
 
+// every pointer of the argument list on a 16-byte boundary (null: an absent optional argument)
+static bool aligned16(std::initializer_list<const void*> ps) {
+  uintptr_t u = 0;
+  for (const void* q : ps) u |= (uintptr_t)q;
+  return (u & 15) == 0;
+}
+
 int vdr_op_layernorm(const void* x, int in_dtype, void* y, int out_dtype, const float* gamma, const float* beta,
                      int64_t rows, int D, float eps, void* stream) {
   if (!x || !y || !gamma || !beta) return fail(nullptr, VDR_ERR_INVALID, "null argument");
+  if (rows <= 0) return fail(nullptr, VDR_ERR_INVALID, "vdr_op_layernorm: rows must be positive");
+  if (D <= 0 || (D & 3) || D > 2048)
+    return fail(nullptr, VDR_ERR_UNSUPPORTED, "vdr_op_layernorm: D must be a positive multiple of 4, at most 2048");
+  // a lane moves 4 elements per access: 8 bytes of bf16, 16 of fp32 (x, y); gamma and beta as f32x4
+  if (((uintptr_t)x & (in_dtype == VDR_BF16 ? 7 : 15)) || ((uintptr_t)y & (out_dtype == VDR_BF16 ? 7 : 15)) || !aligned16({gamma, beta}))
+    return fail(nullptr, VDR_ERR_INVALID, "vdr_op_layernorm: x / y must be aligned to 4 elements, gamma and beta to 16 bytes");
   if (int rc = check_device(nullptr)) return rc;
   LnArgs a{};
   a.x = x;
@@ -2254,6 +2267,9 @@ static int op_linear_impl(const void* x, const void* W, int packed, const float*
 #ifndef VDR_TUNING
   if (variant < 0 || variant >= 100) return fail(nullptr, VDR_ERR_INVALID, "variant");  // (ablation encodings: tuning builds only)
 #endif
+  // 16-byte operand loads (x, W), f32x4 bias / gamma, bf16x8 residual loads and output stores
+  if (!aligned16({x, W, bias, resid, gamma, y}))
+    return fail(nullptr, VDR_ERR_INVALID, "vdr_op_linear: x, W, bias, resid, gamma and y must be 16-byte aligned");
   if (int rc = check_device(nullptr)) return rc;
   GemmArgs g = linear(x, W, y, M, N, K, epilogue);
   g.w_interleaved = packed;
@@ -2467,6 +2483,7 @@ int vdr_op_linear_mx(const void* xq, const void* xs, const void* wq, const void*
 
 int vdr_op_attention(const void* qkv, void* out, int batch, int seq, int heads, int variant, void* stream) {
   if (!qkv || !out) return fail(nullptr, VDR_ERR_INVALID, "null argument");
+  if (batch <= 0 || seq <= 0 || heads <= 0) return fail(nullptr, VDR_ERR_INVALID, "bad shape");
   RUN_OP(launch_attention(qkv, out, batch, seq, heads, variant, (hipStream_t)stream),
          "attention");
 }
@@ -2474,6 +2491,7 @@ int vdr_op_attention(const void* qkv, void* out, int batch, int seq, int heads, 
 int vdr_op_attention_hd(const void* qkv, void* out, int batch, int seq, int heads, int head_dim, int variant, void* stream) {
   if (!head_dim_ok(head_dim)) return fail(nullptr, VDR_ERR_UNSUPPORTED, "head dim must be 32, 64, 96 or 128");
   if (!qkv || !out) return fail(nullptr, VDR_ERR_INVALID, "null argument");
+  if (batch <= 0 || seq <= 0 || heads <= 0) return fail(nullptr, VDR_ERR_INVALID, "bad shape");
   RUN_OP(launch_attention(qkv, out, batch, seq, heads, variant, (hipStream_t)stream, nullptr, nullptr, 0, head_dim),
          "attention");
 }
@@ -2482,6 +2500,7 @@ int vdr_op_attention_varlen(const void* qkv, void* out, int batch, int seq, int 
                             int len_add, int variant, void* stream) {
   if (!head_dim_ok(head_dim)) return fail(nullptr, VDR_ERR_UNSUPPORTED, "head dim must be 32, 64, 96 or 128");
   if (!qkv || !out || !lens) return fail(nullptr, VDR_ERR_INVALID, "null argument");
+  if (batch <= 0 || seq <= 0 || heads <= 0) return fail(nullptr, VDR_ERR_INVALID, "bad shape");
   RUN_OP(launch_attention(qkv, out, batch, seq, heads, variant, (hipStream_t)stream, nullptr, lens, len_add, head_dim),
          "attention");
 }
@@ -2531,11 +2550,6 @@ int vdr_op_attention_relpos(const void* qkv, const float* rel_pos_h, const float
 
 // ---- the SAM window path at op level: run_sam's own argument builders (sam_ln_args, sam_ln_mx, sam_proj_args) and launchers
 // on caller buffers
-static bool aligned16(std::initializer_list<const void*> ps) {
-  uintptr_t u = 0;
-  for (const void* q : ps) u |= (uintptr_t)q;
-  return (u & 15) == 0;
-}
 // the kernels index rows with 32-bit arithmetic (g * g, the windowed row number)
 static bool window_rows_ok(int batch, int g, int ws) {
   return g <= 32768 && ws <= 32768 && (int64_t)batch * sam_window_rows(g, ws) < ((int64_t)1 << 31);

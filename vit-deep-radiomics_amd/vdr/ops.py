@@ -15,12 +15,17 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
-def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, out_dtype=torch.bfloat16):
+def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, out_dtype=torch.bfloat16, out=None):
+    """`out`: write into this caller-owned tensor instead of a fresh one (x's shape, out_dtype, contiguous)."""
     lib = L.load()
     assert x.is_cuda and x.is_contiguous() and x.dtype in (torch.float32, torch.bfloat16)
     D = x.shape[-1]
     rows = x.numel() // D
-    y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    if out is None:
+        y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    else:
+        assert tuple(out.shape) == tuple(x.shape) and out.is_contiguous() and out.dtype == out_dtype and out.device == x.device
+        y = out
     L.check(lib.vdr_op_layernorm(x.data_ptr(), 1 if x.dtype == torch.bfloat16 else 0, y.data_ptr(),
                                  1 if out_dtype == torch.bfloat16 else 0, gamma.data_ptr(), beta.data_ptr(), rows, D,
                                  float(eps), _s(x)))
