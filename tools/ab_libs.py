@@ -10,38 +10,22 @@ descriptors: the same two passes for the descriptor-analysis ops (nn_cosine, the
 smallest shapes that reach every path (the shapes of the exact tests), every element of every output compared; timed on the shapes of
 tools/correspondence_bench.py, pca_bench.py, pca_topk_bench.py and kmeans_bench.py."""
 import ctypes as C
+import os
 import sys
 
 import torch
 
-_P, _I, _L = C.c_void_p, C.c_int, C.c_int64
-F32, BF16 = 0, 1  # vdr_dtype
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "vit-deep-radiomics_amd"))
+from vdr import _lib  # noqa: E402
+
+F32, BF16 = _lib.VDR_F32, _lib.VDR_BF16
 GRAM_CHUNK = 256  # VDR_GRAM_CHUNK
 
 
 def load(path):
-    lib = C.CDLL(path)
-    lib.vdr_op_attention.argtypes = [_P, _P, _I, _I, _I, _I, _P]
-    lib.vdr_op_attention_hd.argtypes = [_P, _P, _I, _I, _I, _I, _I, _P]
-    lib.vdr_op_attention_varlen.argtypes = [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]
-    lib.vdr_op_attention_relpos.argtypes = [_P, _P, _P, _P, _P, _I, _I, _I, _P]
-    lib.vdr_op_linear_packed.argtypes = [_P] * 6 + [C.c_int64, _I, _I, _I, _I, _P]
-    lib.vdr_op_pack_linear_weight.argtypes = [_P, _I, _I, _P, _P]
-    for f, n in (("vdr_nn_cosine_work_bytes", 3), ("vdr_pca_work_bytes", 4), ("vdr_pca_topk_work_bytes", 4), ("vdr_kmeans_work_bytes", 5)):
-        getattr(lib, f).argtypes, getattr(lib, f).restype = [_I] * n, C.c_size_t
-    lib.vdr_op_nn_cosine.argtypes = [_P, _L, _L, _I, _P, _L, _L, _I, _I, _I] + [_P] * 6
-    pca = [_P, _I, _L, _L, _I, _I, _I, _I]  # x, in_dtype, ld, image_stride, problems, imgs, t, d
-    lib.vdr_op_col_mean.argtypes = pca + [_P, _P, _P]
-    lib.vdr_op_covariance.argtypes = pca + [_P, _P, _P, _P]
-    lib.vdr_op_pca_project.argtypes = pca + [_P, _P, _I, _I, _P, _P, _P, _P]
-    side = [_P, _I, _L, _L, _I, _I, _I]     # x, in_dtype, ld, image_stride, problems, t, d
-    lib.vdr_op_col_mean_any.argtypes = side + [_P, _P, _P]
-    lib.vdr_op_gram.argtypes = side + [_P, _P, _P, _P]
-    lib.vdr_op_pca_back_project.argtypes = side + [_P, _P, _P, _I, _P, _P, _P]
-    km = [_P, _L, _L, _L, _I, _I, _I, _I, _I]  # x, ld, image_stride, problem_stride, problems, imgs, t, d, k
-    lib.vdr_op_kmeans_assign.argtypes = km + [_P] * 8
-    lib.vdr_op_kmeans_update.argtypes = km + [_P] * 6
-    return lib
+    """the signatures of vdr/_lib.py on the library at `path`; one built before an entry point existed simply lacks it"""
+    return _lib.bind(C.CDLL(path), skip_missing=True)
 
 
 def attn_case(st, B, N, H, variant=0, dh=64, lens=None):

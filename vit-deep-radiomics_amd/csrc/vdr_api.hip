@@ -2196,6 +2196,10 @@ int vdr_forward_tokens_varlen(vdr_handle m, const void* tokens, int in_dtype, in
 }
 
 // ---- single operators -----------------------------------------------------------------------------
+// An entry point refuses what it cannot run (VDR_ERR_INVALID / VDR_ERR_UNSUPPORTED, vdr_last_error(NULL) = "<op>: <what>")
+// BEFORE check_device, so every refusal is reachable without a GPU; then RUN_OP launches.  The descriptor ops (nn_cosine,
+// affinity_bits, the PCA three, the Gram side, k-means, mahalanobis) describe their map as a DescOperand and share
+// check_desc_operand; each adds only what it alone asks.  There is no kernel and no launch of its own in this file.
 #define OP_TRY(expr, what)                                                             \
   do {                                                                                 \
     hipError_t _e = (expr);                                                            \
@@ -2227,6 +2231,50 @@ static bool aligned16(std::initializer_list<const void*> ps) {
   uintptr_t u = 0;
   for (const void* q : ps) u |= (uintptr_t)q;
   return (u & 15) == 0;
+}
+
+// an op's refusal "<op>: <what>" as its return value
+static int refuse(const char* op, int code, const std::string& what) { return fail(nullptr, code, std::string(op) + ": " + what); }
+
+// A descriptor map as the descriptor ops take it (include/vdr.h): `problems` problems of `imgs` images of `t` rows of `d`
+// channels, the rows `ld`, the images `image_stride`, the problems `problem_stride` elements apart.  An op without an image
+// level passes imgs = 1 and image_stride = 0, one without a problem stride 0, a bf16-only op in_dtype = VDR_BF16.
+struct DescOperand {
+  const void* x;
+  int in_dtype;
+  int64_t ld, image_stride, problem_stride;
+  int problems, imgs, t, d;
+};
+// what the op's signature calls the sizes, the row stride, the other strides and the row count of all problems
+struct DescNames {
+  const char *sizes, *ld, *strides, *rows;
+};
+static const DescNames PCA_NAMES = {"problems, imgs, t and d", "ld", "image_stride", "problems * R"};
+static const DescNames GRAM_NAMES = {"problems, t and d", "ld", "image_stride", "problems * t"};
+static const DescNames KMEANS_NAMES = {"problems, imgs, t and d", "ld", "the strides", "problems * R"};
+static const DescNames NN_NAMES = {"pairs, tx, ty and d", "ldx and ldy", "the pair strides", "pairs * max(tx, ty)"};
+static const DescNames AFFINITY_NAMES = {"pairs, t and d", "ldx", "x_stride", "pairs * t"};
+
+// THE operand check of the descriptor ops, in one fixed order: dtype, null pointers, positive sizes, d % 32 (and d <= max_d
+// where max_d > 0), ld >= d and strides >= 0, 16-byte alignment of x, of `required16` (the op's other pointers that must be
+// non-null and 16-byte aligned), of the rows and of both strides, problems * imgs * t <= 2^31 - 1.  What only one op asks
+// (k ranges, optional or 4-byte pointers, pitch, ...) stays in that op, after this.
+static int check_desc_operand(const char* op, const DescOperand& o, const DescNames& n, int max_d,
+                              std::initializer_list<const void*> required16) {
+  if (o.in_dtype != VDR_F32 && o.in_dtype != VDR_BF16) return refuse(op, VDR_ERR_INVALID, "in_dtype must be VDR_F32 or VDR_BF16");
+  bool null = !o.x;
+  for (const void* q : required16) null = null || !q;
+  if (null) return refuse(op, VDR_ERR_INVALID, "null pointer");
+  if (o.problems <= 0 || o.imgs <= 0 || o.t <= 0 || o.d <= 0) return refuse(op, VDR_ERR_INVALID, std::string(n.sizes) + " must be positive");
+  if (o.d % 32 != 0 || (max_d > 0 && o.d > max_d))
+    return refuse(op, VDR_ERR_UNSUPPORTED, "d must be a multiple of 32" + (max_d > 0 ? ", at most " + std::to_string(max_d) : std::string()));
+  if (o.ld < o.d || o.image_stride < 0 || o.problem_stride < 0) return refuse(op, VDR_ERR_INVALID, std::string(n.ld) + " must be >= d, " + n.strides + " >= 0");
+  const int64_t per16 = o.in_dtype == VDR_BF16 ? 8 : 4;  // elements of a 16-byte chunk
+  if (!aligned16({o.x}) || !aligned16(required16) || o.ld % per16 || o.image_stride % per16 || o.problem_stride % per16)
+    return refuse(op, VDR_ERR_INVALID, std::string("pointers, rows (") + n.ld + ") and " + n.strides + " must be 16-byte aligned");
+  const int64_t R = (int64_t)o.imgs * o.t;  // (each factor is a positive int: no overflow; R is bounded before the next product)
+  if (R > INT32_MAX || R * o.problems > INT32_MAX) return refuse(op, VDR_ERR_INVALID, std::string(n.rows) + " exceeds 2^31 - 1");
+  return VDR_OK;
 }
 
 int vdr_op_layernorm(const void* x, int in_dtype, void* y, int out_dtype, const float* gamma, const float* beta,
@@ -2716,15 +2764,11 @@ size_t vdr_nn_cosine_work_bytes(int pairs, int tx, int ty) { return nn_cosine_wo
 int vdr_op_nn_cosine(const void* x, int64_t ldx, int64_t x_stride, int tx, const void* y, int64_t ldy, int64_t y_stride, int ty,
                      int pairs, int d, void* work, float* row_sim, int32_t* row_idx, float* col_sim, int32_t* col_idx,
                      void* stream) {
-  if (!x || !y || !work || !row_sim || !row_idx) return fail(nullptr, VDR_ERR_INVALID, "nn_cosine: null x, y, work, row_sim or row_idx");
-  if (!col_sim != !col_idx) return fail(nullptr, VDR_ERR_INVALID, "nn_cosine: col_sim and col_idx must both be given or both be null");
-  if (pairs <= 0 || tx <= 0 || ty <= 0 || d <= 0) return fail(nullptr, VDR_ERR_INVALID, "nn_cosine: pairs, tx, ty and d must be positive");
-  if (d % 32 != 0) return fail(nullptr, VDR_ERR_UNSUPPORTED, "nn_cosine: d must be a multiple of 32");
-  if (ldx < d || ldy < d || x_stride < 0 || y_stride < 0)
-    return fail(nullptr, VDR_ERR_INVALID, "nn_cosine: ldx and ldy must be >= d, the pair strides >= 0");
-  if (!aligned16({x, y, work, row_sim, row_idx, col_sim, col_idx}) || ldx % 8 || ldy % 8 || x_stride % 8 || y_stride % 8)
-    return fail(nullptr, VDR_ERR_INVALID, "nn_cosine: pointers, rows (ldx, ldy) and pair strides must be 16-byte aligned");
-  if ((int64_t)pairs * (tx > ty ? tx : ty) > INT32_MAX) return fail(nullptr, VDR_ERR_INVALID, "nn_cosine: pairs * max(tx, ty) exceeds 2^31 - 1");
+  if (int rc = check_desc_operand("nn_cosine", {x, VDR_BF16, ldx, 0, x_stride, pairs, 1, tx, d}, NN_NAMES, 0, {work, row_sim, row_idx}))
+    return rc;
+  if (int rc = check_desc_operand("nn_cosine", {y, VDR_BF16, ldy, 0, y_stride, pairs, 1, ty, d}, NN_NAMES, 0, {})) return rc;
+  if (!col_sim != !col_idx) return refuse("nn_cosine", VDR_ERR_INVALID, "col_sim and col_idx must both be given or both be null");
+  if (!aligned16({col_sim, col_idx})) return refuse("nn_cosine", VDR_ERR_INVALID, "col_sim and col_idx must be 16-byte aligned");
   RUN_OP(launch_nn_cosine(x, ldx, x_stride, tx, y, ldy, y_stride, ty, pairs, d, work, row_sim, row_idx, col_sim, col_idx,
                           (hipStream_t)stream),
          "nn_cosine");
@@ -2734,13 +2778,8 @@ size_t vdr_affinity_work_bytes(int pairs, int t) { return affinity_work_bytes(pa
 
 int vdr_op_affinity_bits(const void* x, int64_t ldx, int64_t x_stride, int t, int pairs, int d, float tau, int exclude_diag,
                          void* work, uint32_t* bits, int pitch, void* stream) {
-  if (!x || !work || !bits) return fail(nullptr, VDR_ERR_INVALID, "affinity_bits: null x, work or bits");
-  if (pairs <= 0 || t <= 0 || d <= 0) return fail(nullptr, VDR_ERR_INVALID, "affinity_bits: pairs, t and d must be positive");
-  if (d % 32 != 0) return fail(nullptr, VDR_ERR_UNSUPPORTED, "affinity_bits: d must be a multiple of 32");
-  if (ldx < d || x_stride < 0) return fail(nullptr, VDR_ERR_INVALID, "affinity_bits: ldx must be >= d, x_stride >= 0");
-  if (!aligned16({x, work, bits}) || ldx % 8 || x_stride % 8)
-    return fail(nullptr, VDR_ERR_INVALID, "affinity_bits: pointers, rows (ldx) and x_stride must be 16-byte aligned");
-  if ((int64_t)pairs * t > INT32_MAX) return fail(nullptr, VDR_ERR_INVALID, "affinity_bits: pairs * t exceeds 2^31 - 1");
+  if (int rc = check_desc_operand("affinity_bits", {x, VDR_BF16, ldx, 0, x_stride, pairs, 1, t, d}, AFFINITY_NAMES, 0, {work, bits}))
+    return rc;
   if (pitch != affinity_pitch(t)) return fail(nullptr, VDR_ERR_INVALID, "affinity_bits: pitch must be ceil(t / 32) rounded up to a multiple of 4");
   if (!(tau == tau)) return fail(nullptr, VDR_ERR_INVALID, "affinity_bits: tau is NaN");
   RUN_OP(launch_affinity_bits(x, ldx, x_stride, t, pairs, d, tau, exclude_diag, work, bits, pitch, (hipStream_t)stream), "affinity_bits");
@@ -2760,38 +2799,15 @@ int vdr_op_bits_matvec(const uint32_t* bits, int pitch, int t, int pairs, const 
 
 size_t vdr_pca_work_bytes(int problems, int imgs, int t, int d) { return pca_work_bytes(problems, imgs, t, d); }
 
-// the operand checks shared by the three PCA ops (include/vdr.h); `outs`: the op's other pointers
-static int pca_operand(const char* op, const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int imgs,
-                       int t, int d, std::initializer_list<const void*> outs) {
-  static thread_local char msg[160];
-  const auto refuse = [&](int code, const char* what) {
-    snprintf(msg, sizeof msg, "%s: %s", op, what);
-    return fail(nullptr, code, msg);
-  };
-  if (in_dtype != VDR_F32 && in_dtype != VDR_BF16) return refuse(VDR_ERR_INVALID, "in_dtype must be VDR_F32 or VDR_BF16");
-  bool null = !x;
-  for (const void* q : outs) null = null || !q;
-  if (null) return refuse(VDR_ERR_INVALID, "null pointer");
-  if (problems <= 0 || imgs <= 0 || t <= 0 || d <= 0) return refuse(VDR_ERR_INVALID, "problems, imgs, t and d must be positive");
-  if (d % 32 != 0 || d > 2048) return refuse(VDR_ERR_UNSUPPORTED, "d must be a multiple of 32, at most 2048");
-  if (ld < d || image_stride < 0) return refuse(VDR_ERR_INVALID, "ld must be >= d, image_stride >= 0");
-  const int64_t per16 = in_dtype == VDR_BF16 ? 8 : 4;  // elements of a 16-byte chunk
-  if (!aligned16({x}) || !aligned16(outs) || ld % per16 || image_stride % per16)
-    return refuse(VDR_ERR_INVALID, "pointers, rows (ld) and images (image_stride) must be 16-byte aligned");
-  const int64_t R = (int64_t)imgs * t;  // (each factor is a positive int: no overflow; R is bounded before the next product)
-  if (R > INT32_MAX || R * problems > INT32_MAX) return refuse(VDR_ERR_INVALID, "problems * R exceeds 2^31 - 1");
-  return VDR_OK;
-}
-
 int vdr_op_col_mean(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int imgs, int t, int d, void* work,
                     float* mean, void* stream) {
-  if (int rc = pca_operand("col_mean", x, in_dtype, ld, image_stride, problems, imgs, t, d, {work, mean})) return rc;
+  if (int rc = check_desc_operand("col_mean", {x, in_dtype, ld, image_stride, 0, problems, imgs, t, d}, PCA_NAMES, 2048, {work, mean})) return rc;
   RUN_OP(launch_col_mean(x, in_dtype == VDR_BF16, ld, image_stride, problems, imgs, t, d, work, mean, (hipStream_t)stream), "col_mean");
 }
 
 int vdr_op_covariance(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int imgs, int t, int d,
                       const float* mean, void* work, float* cov, void* stream) {
-  if (int rc = pca_operand("covariance", x, in_dtype, ld, image_stride, problems, imgs, t, d, {mean, work, cov})) return rc;
+  if (int rc = check_desc_operand("covariance", {x, in_dtype, ld, image_stride, 0, problems, imgs, t, d}, PCA_NAMES, 2048, {mean, work, cov})) return rc;
   if ((int64_t)imgs * t < 2) return fail(nullptr, VDR_ERR_INVALID, "covariance: needs R = imgs * t >= 2 rows");
   RUN_OP(launch_covariance(x, in_dtype == VDR_BF16, ld, image_stride, problems, imgs, t, d, mean, work, cov, (hipStream_t)stream),
          "covariance");
@@ -2800,34 +2816,13 @@ int vdr_op_covariance(const void* x, int in_dtype, int64_t ld, int64_t image_str
 int vdr_op_pca_project(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int imgs, int t, int d,
                        const float* mean, const float* comps, int k, int scale, void* work, float* proj, float* minmax,
                        void* stream) {
-  if (int rc = pca_operand("pca_project", x, in_dtype, ld, image_stride, problems, imgs, t, d, {mean, comps, work, proj, minmax}))
+  if (int rc = check_desc_operand("pca_project", {x, in_dtype, ld, image_stride, 0, problems, imgs, t, d}, PCA_NAMES, 2048,
+                                  {mean, comps, work, proj, minmax}))
     return rc;
   if (k < 1 || k > 8) return fail(nullptr, VDR_ERR_UNSUPPORTED, "pca_project: k must be 1..8");
   RUN_OP(launch_pca_project(x, in_dtype == VDR_BF16, ld, image_stride, problems, imgs, t, d, mean, comps, k, scale, work, proj,
                             minmax, (hipStream_t)stream),
          "pca_project");
-}
-
-// the Gram side and the top-k solver (include/vdr.h): the operand checks of the PCA ops without the d <= 2048 limit
-static int pca_topk_operand(const char* op, const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int t, int d,
-                            std::initializer_list<const void*> outs) {
-  static thread_local char msg[160];
-  const auto refuse = [&](int code, const char* what) {
-    snprintf(msg, sizeof msg, "%s: %s", op, what);
-    return fail(nullptr, code, msg);
-  };
-  if (in_dtype != VDR_F32 && in_dtype != VDR_BF16) return refuse(VDR_ERR_INVALID, "in_dtype must be VDR_F32 or VDR_BF16");
-  bool null = !x;
-  for (const void* q : outs) null = null || !q;
-  if (null) return refuse(VDR_ERR_INVALID, "null pointer");
-  if (problems <= 0 || t <= 0 || d <= 0) return refuse(VDR_ERR_INVALID, "problems, t and d must be positive");
-  if (d % 32 != 0) return refuse(VDR_ERR_UNSUPPORTED, "d must be a multiple of 32");
-  if (ld < d || image_stride < 0) return refuse(VDR_ERR_INVALID, "ld must be >= d, image_stride >= 0");
-  const int64_t per16 = in_dtype == VDR_BF16 ? 8 : 4;  // elements of a 16-byte chunk
-  if (!aligned16({x}) || !aligned16(outs) || ld % per16 || image_stride % per16)
-    return refuse(VDR_ERR_INVALID, "pointers, rows (ld) and images (image_stride) must be 16-byte aligned");
-  if ((int64_t)t * problems > INT32_MAX) return refuse(VDR_ERR_INVALID, "problems * t exceeds 2^31 - 1");
-  return VDR_OK;
 }
 
 size_t vdr_pca_topk_work_bytes(int problems, int t, int d, int k) {
@@ -2837,20 +2832,21 @@ size_t vdr_pca_topk_work_bytes(int problems, int t, int d, int k) {
 
 int vdr_op_col_mean_any(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int t, int d, void* work,
                         float* mean, void* stream) {
-  if (int rc = pca_topk_operand("col_mean_any", x, in_dtype, ld, image_stride, problems, t, d, {work, mean})) return rc;
+  if (int rc = check_desc_operand("col_mean_any", {x, in_dtype, ld, image_stride, 0, problems, 1, t, d}, GRAM_NAMES, 0, {work, mean})) return rc;
   RUN_OP(launch_col_mean_any(x, in_dtype == VDR_BF16, ld, image_stride, problems, t, d, work, mean, (hipStream_t)stream), "col_mean_any");
 }
 
 int vdr_op_gram(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int t, int d, const float* mean,
                 void* work, float* gram, void* stream) {
-  if (int rc = pca_topk_operand("gram", x, in_dtype, ld, image_stride, problems, t, d, {mean, work, gram})) return rc;
+  if (int rc = check_desc_operand("gram", {x, in_dtype, ld, image_stride, 0, problems, 1, t, d}, GRAM_NAMES, 0, {mean, work, gram})) return rc;
   if (t < 2 || t > 4096) return fail(nullptr, VDR_ERR_UNSUPPORTED, "gram: t must be 2..4096");
   RUN_OP(launch_gram(x, in_dtype == VDR_BF16, ld, image_stride, problems, t, d, mean, work, gram, (hipStream_t)stream), "gram");
 }
 
 int vdr_op_pca_back_project(const void* x, int in_dtype, int64_t ld, int64_t image_stride, int problems, int t, int d,
                             const float* mean, const float* u, const float* values, int k, void* work, float* comps, void* stream) {
-  if (int rc = pca_topk_operand("pca_back_project", x, in_dtype, ld, image_stride, problems, t, d, {mean, u, values, work, comps}))
+  if (int rc = check_desc_operand("pca_back_project", {x, in_dtype, ld, image_stride, 0, problems, 1, t, d}, GRAM_NAMES, 0,
+                                  {mean, u, values, work, comps}))
     return rc;
   if (k < 1 || k > 8) return fail(nullptr, VDR_ERR_UNSUPPORTED, "pca_back_project: k must be 1..8");
   RUN_OP(launch_pca_back_project(x, in_dtype == VDR_BF16, ld, image_stride, problems, t, d, mean, u, values, k, work, comps,
@@ -2872,35 +2868,21 @@ int vdr_op_sym_topk(const float* a, int problems, int n, int k, float tol, int m
 
 size_t vdr_kmeans_work_bytes(int problems, int imgs, int t, int d, int k) { return kmeans_work_bytes(problems, imgs, t, d, k); }
 
-// the operand checks shared by the two k-means ops (include/vdr.h); `ptrs`: the op's other required pointers
-static int kmeans_operand(const char* op, const void* x, int64_t ld, int64_t image_stride, int64_t problem_stride, int problems,
-                          int imgs, int t, int d, int k, const void* active, std::initializer_list<const void*> ptrs) {
-  static thread_local char msg[160];
-  const auto refuse = [&](int code, const char* what) {
-    snprintf(msg, sizeof msg, "%s: %s", op, what);
-    return fail(nullptr, code, msg);
-  };
-  bool null = !x;
-  for (const void* q : ptrs) null = null || !q;
-  if (null) return refuse(VDR_ERR_INVALID, "null pointer");
-  if (problems <= 0 || imgs <= 0 || t <= 0 || d <= 0) return refuse(VDR_ERR_INVALID, "problems, imgs, t and d must be positive");
-  if (d % 32 != 0) return refuse(VDR_ERR_UNSUPPORTED, "d must be a multiple of 32");
-  if (k < 1 || k > 1024) return refuse(VDR_ERR_UNSUPPORTED, "k must be 1..1024");
-  if (ld < d || image_stride < 0 || problem_stride < 0) return refuse(VDR_ERR_INVALID, "ld must be >= d, the strides >= 0");
-  if (!aligned16({x, active}) || !aligned16(ptrs) || ld % 8 || image_stride % 8 || problem_stride % 8)
-    return refuse(VDR_ERR_INVALID, "pointers, rows (ld), images and problems (the strides) must be 16-byte aligned");
-  const int64_t R = (int64_t)imgs * t;  // (each factor is a positive int: no overflow; R is bounded before the next product)
-  if (R > INT32_MAX || R * problems > INT32_MAX) return refuse(VDR_ERR_INVALID, "problems * R exceeds 2^31 - 1");
-  if (k > R) return refuse(VDR_ERR_INVALID, "k exceeds the R = imgs * t rows of a problem");
+// what the two k-means ops ask beyond the operand check (include/vdr.h)
+static int kmeans_own(const char* op, int imgs, int t, int k, const void* active) {
+  if (k < 1 || k > 1024) return refuse(op, VDR_ERR_UNSUPPORTED, "k must be 1..1024");
+  if (!aligned16({active})) return refuse(op, VDR_ERR_INVALID, "active must be 16-byte aligned");
+  if (k > (int64_t)imgs * t) return refuse(op, VDR_ERR_INVALID, "k exceeds the R = imgs * t rows of a problem");
   return VDR_OK;
 }
 
 int vdr_op_kmeans_assign(const void* x, int64_t ld, int64_t image_stride, int64_t problem_stride, int problems, int imgs, int t,
                          int d, int k, const float* centroids, const int32_t* active, void* work, int32_t* labels, float* min_dist,
                          float* inertia, int32_t* changed, void* stream) {
-  if (int rc = kmeans_operand("kmeans_assign", x, ld, image_stride, problem_stride, problems, imgs, t, d, k, active,
-                              {centroids, work, labels, min_dist, inertia, changed}))
+  if (int rc = check_desc_operand("kmeans_assign", {x, VDR_BF16, ld, image_stride, problem_stride, problems, imgs, t, d}, KMEANS_NAMES, 0,
+                                  {centroids, work, labels, min_dist, inertia, changed}))
     return rc;
+  if (int rc = kmeans_own("kmeans_assign", imgs, t, k, active)) return rc;
   RUN_OP(launch_kmeans_assign(x, ld, image_stride, problem_stride, problems, imgs, t, d, k, centroids, active, work, labels,
                               min_dist, inertia, changed, (hipStream_t)stream),
          "kmeans_assign");
@@ -2909,9 +2891,10 @@ int vdr_op_kmeans_assign(const void* x, int64_t ld, int64_t image_stride, int64_
 int vdr_op_kmeans_update(const void* x, int64_t ld, int64_t image_stride, int64_t problem_stride, int problems, int imgs, int t,
                          int d, int k, const int32_t* labels, const int32_t* active, void* work, float* centroids, int32_t* counts,
                          void* stream) {
-  if (int rc = kmeans_operand("kmeans_update", x, ld, image_stride, problem_stride, problems, imgs, t, d, k, active,
-                              {labels, work, centroids, counts}))
+  if (int rc = check_desc_operand("kmeans_update", {x, VDR_BF16, ld, image_stride, problem_stride, problems, imgs, t, d}, KMEANS_NAMES, 0,
+                                  {labels, work, centroids, counts}))
     return rc;
+  if (int rc = kmeans_own("kmeans_update", imgs, t, k, active)) return rc;
   RUN_OP(launch_kmeans_update(x, ld, image_stride, problem_stride, problems, imgs, t, d, k, labels, active, work, centroids, counts,
                               (hipStream_t)stream),
          "kmeans_update");
@@ -2920,21 +2903,15 @@ int vdr_op_kmeans_update(const void* x, int64_t ld, int64_t image_stride, int64_
 int vdr_op_mahalanobis(const void* x, int64_t ld, int64_t image_stride, int64_t problem_stride, int problems, int imgs, int t, int d,
                        const float* mean, int64_t mean_stride, const float* whiten, int64_t whiten_stride, int k, float* d2,
                        void* stream) {
-  if (!x || !mean || !whiten || !d2) return fail(nullptr, VDR_ERR_INVALID, "mahalanobis: null x, mean, whiten or d2");
-  if (problems <= 0 || imgs <= 0 || t <= 0 || d <= 0)
-    return fail(nullptr, VDR_ERR_INVALID, "mahalanobis: problems, imgs, t and d must be positive");
-  if (d % 32 != 0) return fail(nullptr, VDR_ERR_UNSUPPORTED, "mahalanobis: d must be a multiple of 32");
-  if (k < 1 || k > VDR_MAHALANOBIS_MAX_K) return fail(nullptr, VDR_ERR_UNSUPPORTED, "mahalanobis: k must be 1..2048");
-  if (ld < d || image_stride < 0 || problem_stride < 0)
-    return fail(nullptr, VDR_ERR_INVALID, "mahalanobis: ld must be >= d, the strides >= 0");
+  if (int rc = check_desc_operand("mahalanobis", {x, VDR_BF16, ld, image_stride, problem_stride, problems, imgs, t, d}, KMEANS_NAMES, 0,
+                                  {mean, whiten}))
+    return rc;
+  if (!d2) return refuse("mahalanobis", VDR_ERR_INVALID, "null pointer");
+  if (k < 1 || k > VDR_MAHALANOBIS_MAX_K) return refuse("mahalanobis", VDR_ERR_UNSUPPORTED, "k must be 1..2048");
   if ((mean_stride != 0 && mean_stride < d) || (whiten_stride != 0 && whiten_stride < (int64_t)k * d))
-    return fail(nullptr, VDR_ERR_INVALID, "mahalanobis: mean_stride must be 0 or >= d, whiten_stride 0 or >= k * d");
-  if (!aligned16({x, mean, whiten}) || (uintptr_t)d2 % 4 || ld % 8 || image_stride % 8 || problem_stride % 8 || mean_stride % 4 ||
-      whiten_stride % 4)
-    return fail(nullptr, VDR_ERR_INVALID,
-                "mahalanobis: x, mean, whiten, rows (ld), images, problems and the model strides must be 16-byte aligned, d2 4-byte aligned");
-  const int64_t R = (int64_t)imgs * t;  // (each factor is a positive int: no overflow; R is bounded before the next product)
-  if (R > INT32_MAX || R * problems > INT32_MAX) return fail(nullptr, VDR_ERR_INVALID, "mahalanobis: problems * R exceeds 2^31 - 1");
+    return refuse("mahalanobis", VDR_ERR_INVALID, "mean_stride must be 0 or >= d, whiten_stride 0 or >= k * d");
+  if ((uintptr_t)d2 % 4 || mean_stride % 4 || whiten_stride % 4)
+    return refuse("mahalanobis", VDR_ERR_INVALID, "the model strides (mean_stride, whiten_stride) must be 16-byte aligned, d2 4-byte aligned");
   RUN_OP(launch_mahalanobis(x, ld, image_stride, problem_stride, problems, imgs, t, d, mean, mean_stride, whiten, whiten_stride, k, d2,
                             (hipStream_t)stream),
          "mahalanobis");
@@ -2945,11 +2922,7 @@ size_t vdr_upsample_work_bytes(int batch, int Cg, int gh, int gw) { return upsam
 // the guide and the geometry shared by the two upsampling ops (include/vdr.h); sets gh, gw
 static int upsample_guide(const char* op, const void* guide, int guide_dtype, int batch, int Cg, int H, int W, int p, int s,
                           int* gh, int* gw) {
-  static thread_local char msg[160];
-  const auto refuse = [&](int code, const char* what) {
-    snprintf(msg, sizeof msg, "%s: %s", op, what);
-    return fail(nullptr, code, msg);
-  };
+  const auto refuse = [op](int code, const char* what) { return ::refuse(op, code, what); };
   if (guide_dtype != VDR_F32 && guide_dtype != VDR_BF16) return refuse(VDR_ERR_INVALID, "guide_dtype must be VDR_F32 or VDR_BF16");
   if (!guide) return refuse(VDR_ERR_INVALID, "null guide");
   if (Cg < 1 || Cg > 4) return refuse(VDR_ERR_UNSUPPORTED, "the guide must have 1..4 channels");

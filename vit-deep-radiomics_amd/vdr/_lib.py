@@ -153,6 +153,21 @@ SYMBOLS = {
 _lib = None
 
 
+def bind(lib: C.CDLL, skip_missing: bool = False) -> C.CDLL:
+    """Set restype / argtypes of every SYMBOLS entry on `lib`.  A symbol the library does not export is an AttributeError, or
+    is left out with skip_missing (tools that open a library older than the table)."""
+    for name, (res, args) in SYMBOLS.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            if skip_missing:
+                continue
+            raise
+        fn.restype = res
+        fn.argtypes = args
+    return lib
+
+
 def load() -> C.CDLL:
     """dlopen libvdr.so and bind every declared symbol.  torch is imported first so that the HIP
     runtime already mapped by PyTorch-ROCm (same SONAME libamdhip64.so.7) is the one libvdr uses:
@@ -164,11 +179,7 @@ def load() -> C.CDLL:
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "or `make -C vit-deep-radiomics_amd/csrc`. There is no CPU fallback.")
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
-        fn = getattr(lib, name)  # AttributeError if the library does not export it
-        fn.restype = res
-        fn.argtypes = args
+    lib = bind(C.CDLL(LIB_PATH))  # AttributeError if the library does not export a symbol
     if lib.vdr_abi_version() != 8:
         raise ImportError("libvdr ABI version mismatch")
     _lib = lib

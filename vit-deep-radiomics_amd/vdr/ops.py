@@ -291,18 +291,68 @@ def log_bin(x: torch.Tensor, gh: int, gw: int, hierarchy: int = 2, out_dtype=tor
     return out
 
 
-def _nn_operand(t: torch.Tensor, name: str, op: str = "nn_cosine"):
-    """(tensor, row stride, pair stride) of one nn_cosine / affinity_bits operand, read where it lies when it can be"""
-    if t.dtype != torch.bfloat16:
-        t = t.to(torch.bfloat16)  # (fp32: rounded once; a new contiguous tensor)
-    P, n, d = t.shape
-    ok = (d == 1 or t.stride(2) == 1) and (n == 1 or (t.stride(1) >= d and t.stride(1) % 8 == 0)) and \
-        (P == 1 or (t.stride(0) >= 0 and t.stride(0) % 8 == 0)) and t.data_ptr() % 16 == 0
+class DescOperand:
+    """A descriptor map as the descriptor ops read it (the host side of check_desc_operand, csrc/vdr_api.hip): the tensor kept
+    alive, its dtype code, its strides in elements and its shape (problems, imgs, t, d); R = imgs * t rows per problem.  Built
+    by desc_operand; k-means builds it once per fit."""
+
+    def __init__(self, x, ld, image_stride, problem_stride, problems, imgs, t, d):
+        self.x, self.dtype = x, (L.VDR_BF16 if x.dtype == torch.bfloat16 else L.VDR_F32)
+        self.ld, self.image_stride, self.problem_stride = ld, image_stride, problem_stride
+        self.problems, self.imgs, self.t, self.d = problems, imgs, t, d
+        self.R = imgs * t
+
+    @property
+    def stride(self):
+        """of a [P, t, d] operand: the stride of its one level above the rows, images (joint) or problems"""
+        return self.image_stride if self.imgs > 1 else self.problem_stride
+
+    def work(self, k: int) -> torch.Tensor:
+        """the scratch of the two k-means ops for k centroids"""
+        n = L.load().vdr_kmeans_work_bytes(self.problems, self.imgs, self.t, self.d, int(k))
+        return torch.empty((n,), dtype=torch.uint8, device=self.x.device)
+
+
+def desc_operand(x, op: str, name: str = "x", joint: bool = False, keep_fp32: bool = False, max_d=None, four_d: bool = False,
+                 refuse_strided_channels: bool = False) -> DescOperand:
+    """The host-side refusals of a descriptor operand and its description for the library, for every descriptor op.  x
+    [P, t, d] bf16 / fp32 on the device: one problem per image, or the P * t rows of all images as one problem with joint=True.
+    It is read where it lies when its channels are contiguous and its rows, images and problems 16-byte aligned (a column
+    slice of a wider buffer, rows behind a prefix, a stride of 0 from expand()), and copied once otherwise.  d must be a
+    multiple of 32.  What the families differ in:
+      keep_fp32                fp32 stays fp32 (PCA, the Gram side); otherwise it is rounded once to bf16
+      max_d                    the widest d taken (PCA: 2048)
+      four_d                   [problems, imgs, t, d] is taken as it says, and a DescOperand is passed through (k-means, Mahalanobis)
+      refuse_strided_channels  channels that are not contiguous are a ValueError, not a copy (nn_cosine, affinity_bits)"""
+    if four_d and isinstance(x, DescOperand):
+        return x
+    if not isinstance(x, torch.Tensor) or x.dim() not in ((3, 4) if four_d else (3,)) or x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{op}: {name} must be a [P, t, d] {'or [problems, imgs, t, d] ' if four_d else ''}float32 or bfloat16 tensor")
+    if not x.is_cuda:
+        raise TypeError(f"{op}: {name} must live on the HIP device")
+    if x.dim() == 3:
+        x = x.unsqueeze(0) if joint else x.unsqueeze(1)
+    elif joint:
+        raise ValueError(f"{op}: joint=True goes with a [P, t, d] operand")
+    problems, imgs, t, d = x.shape
+    if min(problems, imgs, t, d) <= 0:
+        raise ValueError(f"{op}: empty operand")
+    if d % 32 or (max_d and d > max_d):
+        raise ValueError(f"{op}: d must be a multiple of 32{f', at most {max_d}' if max_d else ''}, got {d}")
+    if problems * imgs * t > 2 ** 31 - 1:
+        raise ValueError(f"{op}: problems * imgs * t exceeds 2^31 - 1")
+    if x.dtype != torch.bfloat16 and not keep_fp32:
+        x = x.to(torch.bfloat16)  # (fp32: rounded once)
+    per16 = 8 if x.dtype == torch.bfloat16 else 4  # elements of a 16-byte chunk
+    ok = x.stride(3) == 1 and (t == 1 or (x.stride(2) >= d and x.stride(2) % per16 == 0)) and \
+        (imgs == 1 or (x.stride(1) >= 0 and x.stride(1) % per16 == 0)) and \
+        (problems == 1 or (x.stride(0) >= 0 and x.stride(0) % per16 == 0)) and x.data_ptr() % 16 == 0
     if not ok:
-        if d > 1 and t.stride(2) != 1:
+        if refuse_strided_channels and x.stride(3) != 1:
             raise ValueError(f"{op}: the channels of {name} must be contiguous")
-        t = t.contiguous()
-    return t, (t.stride(1) if n > 1 else d), (t.stride(0) if P > 1 else 0)
+        x = x.contiguous()
+    return DescOperand(x, x.stride(2) if t > 1 else d, x.stride(1) if imgs > 1 else 0, x.stride(0) if problems > 1 else 0,
+                       problems, imgs, t, d)
 
 
 def nn_cosine(x: torch.Tensor, y: torch.Tensor, mutual: bool = True):
@@ -313,34 +363,22 @@ def nn_cosine(x: torch.Tensor, y: torch.Tensor, mutual: bool = True):
     row_sim[p, i] = max_j cos(x[p, i], y[p, j]) and row_idx the lowest j attaining it, col_* the same over i for every j;
     col_sim and col_idx are None when mutual=False (the column side is then not computed).  The [tx, ty] similarity matrix
     is never materialised.  The exact arithmetic is stated in include/vdr.h."""
-    for t, name in ((x, "x"), (y, "y")):
-        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.dtype not in (torch.float32, torch.bfloat16):
-            raise TypeError(f"nn_cosine: {name} must be a [P, t, d] float32 or bfloat16 tensor")
-        if not t.is_cuda:
-            raise TypeError(f"nn_cosine: {name} must live on the HIP device")
-    if x.device != y.device:
+    ox = desc_operand(x, "nn_cosine", "x", refuse_strided_channels=True)
+    oy = desc_operand(y, "nn_cosine", "y", refuse_strided_channels=True)
+    if ox.x.device != oy.x.device:
         raise ValueError("nn_cosine: x and y must be on the same device")
-    if x.shape[0] != y.shape[0] or x.shape[2] != y.shape[2]:
+    if ox.problems != oy.problems or ox.d != oy.d:
         raise ValueError(f"nn_cosine: x {tuple(x.shape)} and y {tuple(y.shape)} must agree in P and d")
-    P, tx, d = x.shape
-    ty = y.shape[1]
-    if min(P, tx, ty, d) <= 0:
-        raise ValueError("nn_cosine: empty operand")
-    if d % 32:
-        raise ValueError(f"nn_cosine: d must be a multiple of 32, got {d}")
-    if P * max(tx, ty) > 2 ** 31 - 1:
-        raise ValueError("nn_cosine: P * max(tx, ty) exceeds 2^31 - 1")
+    P, tx, ty, d = ox.problems, ox.t, oy.t, ox.d
     lib = L.load()
-    x, ldx, xs = _nn_operand(x, "x")
-    y, ldy, ys = _nn_operand(y, "y")
     dev = x.device
     work = torch.empty((lib.vdr_nn_cosine_work_bytes(P, tx, ty),), dtype=torch.uint8, device=dev)
     row_sim = torch.empty((P, tx), dtype=torch.float32, device=dev)
     row_idx = torch.empty((P, tx), dtype=torch.int32, device=dev)
     col_sim = torch.empty((P, ty), dtype=torch.float32, device=dev) if mutual else None
     col_idx = torch.empty((P, ty), dtype=torch.int32, device=dev) if mutual else None
-    L.check(lib.vdr_op_nn_cosine(x.data_ptr(), ldx, xs, tx, y.data_ptr(), ldy, ys, ty, P, d, work.data_ptr(), row_sim.data_ptr(),
-                                 row_idx.data_ptr(), _p(col_sim), _p(col_idx), _s(x)))
+    L.check(lib.vdr_op_nn_cosine(ox.x.data_ptr(), ox.ld, ox.stride, tx, oy.x.data_ptr(), oy.ld, oy.stride, ty, P, d, work.data_ptr(),
+                                 row_sim.data_ptr(), row_idx.data_ptr(), _p(col_sim), _p(col_idx), _s(ox.x)))
     return row_sim, row_idx, col_sim, col_idx
 
 
@@ -356,26 +394,16 @@ def affinity_bits(x: torch.Tensor, tau: float = 0.2, exclude_diag: bool = False)
     cos(x[p, i], x[p, j]) > tau (the diagonal cleared with exclude_diag); bits of columns >= t and the padding words are 0.
     The graph is symmetric bit for bit; the [t, t] matrix of scores is never materialised.  The exact arithmetic is stated in
     include/vdr.h."""
-    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError("affinity_bits: x must be a [P, t, d] float32 or bfloat16 tensor")
-    if not x.is_cuda:
-        raise TypeError("affinity_bits: x must live on the HIP device")
-    P, t, d = x.shape
-    if min(P, t, d) <= 0:
-        raise ValueError("affinity_bits: empty operand")
-    if d % 32:
-        raise ValueError(f"affinity_bits: d must be a multiple of 32, got {d}")
-    if P * t > 2 ** 31 - 1:
-        raise ValueError("affinity_bits: P * t exceeds 2^31 - 1")
+    o = desc_operand(x, "affinity_bits", refuse_strided_channels=True)
+    x, P, t, d = o.x, o.problems, o.t, o.d
     tau = float(tau)
     if tau != tau:
         raise ValueError("affinity_bits: tau is NaN")
     lib = L.load()
-    x, ldx, xs = _nn_operand(x, "x", "affinity_bits")
     pitch = bits_pitch(t)
     work = torch.empty((lib.vdr_affinity_work_bytes(P, t),), dtype=torch.uint8, device=x.device)
     bits = torch.empty((P, t, pitch), dtype=torch.int32, device=x.device)
-    L.check(lib.vdr_op_affinity_bits(x.data_ptr(), ldx, xs, t, P, d, tau, int(bool(exclude_diag)), work.data_ptr(), bits.data_ptr(),
+    L.check(lib.vdr_op_affinity_bits(x.data_ptr(), o.ld, o.stride, t, P, d, tau, int(bool(exclude_diag)), work.data_ptr(), bits.data_ptr(),
                                      pitch, _s(x)))
     return bits
 
@@ -443,30 +471,10 @@ def best_buddies(row_idx: torch.Tensor, col_idx: torch.Tensor) -> torch.Tensor:
     return back == torch.arange(row_idx.shape[1], device=row_idx.device).unsqueeze(0)
 
 
-def _pca_operand(x: torch.Tensor, op: str, joint: bool):
-    """The host-side refusals of a PCA operand and its description for the library: (tensor, in_dtype, ld, image_stride,
-    problems, imgs, t, d).  x [P, t, d] bf16 / fp32, read where it lies when its channels are contiguous and its rows and
-    images 16-byte aligned (a column slice of a wider buffer, rows behind a prefix); copied once otherwise."""
-    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"{op}: x must be a [P, t, d] float32 or bfloat16 tensor")
-    if not x.is_cuda:
-        raise TypeError(f"{op}: x must live on the HIP device")
-    P, t, d = x.shape
-    if min(P, t, d) <= 0:
-        raise ValueError(f"{op}: empty operand")
-    if d % 32 or d > 2048:
-        raise ValueError(f"{op}: d must be a multiple of 32, at most 2048, got {d}")
-    if P * t > 2 ** 31 - 1:
-        raise ValueError(f"{op}: P * t exceeds 2^31 - 1")
-    per16 = 8 if x.dtype == torch.bfloat16 else 4
-    ok = x.stride(2) == 1 and (t == 1 or (x.stride(1) >= d and x.stride(1) % per16 == 0)) and \
-        (P == 1 or (x.stride(0) >= 0 and x.stride(0) % per16 == 0)) and x.data_ptr() % 16 == 0
-    if not ok:
-        x = x.contiguous()
-    ld = x.stride(1) if t > 1 else d
-    stride = x.stride(0) if P > 1 else 0
-    problems, imgs = (1, P) if joint else (P, 1)
-    return x, (L.VDR_BF16 if x.dtype == torch.bfloat16 else L.VDR_F32), ld, stride, problems, imgs, t, d
+def _pca_operand(x, op: str, joint: bool):
+    """a PCA operand: the input's dtype is kept, d <= 2048 -> (tensor, in_dtype, ld, image_stride, problems, imgs, t, d)"""
+    o = desc_operand(x, op, joint=joint, keep_fp32=True, max_d=2048)
+    return o.x, o.dtype, o.ld, o.stride, o.problems, o.imgs, o.t, o.d
 
 
 def _pca_work(lib, problems, imgs, t, d, dev):
@@ -546,28 +554,11 @@ TOPK_TOL = 3.3e-7    # VDR_TOPK_TOL (include/vdr.h)
 TOPK_MAX_ITER = 146  # VDR_TOPK_MAX_ITER
 
 
-def _topk_operand(x: torch.Tensor, op: str):
-    """_pca_operand's refusals for the per-image Gram side: any d % 32 == 0, no upper bound -> (tensor, in_dtype, ld,
-    image_stride, problems, t, d)."""
-    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"{op}: x must be a [P, t, d] float32 or bfloat16 tensor")
-    if not x.is_cuda:
-        raise TypeError(f"{op}: x must live on the HIP device")
-    P, t, d = x.shape
-    if min(P, t, d) <= 0:
-        raise ValueError(f"{op}: empty operand")
-    if d % 32:
-        raise ValueError(f"{op}: d must be a multiple of 32, got {d}")
-    if P * t > 2 ** 31 - 1:
-        raise ValueError(f"{op}: P * t exceeds 2^31 - 1")
-    per16 = 8 if x.dtype == torch.bfloat16 else 4
-    ok = x.stride(2) == 1 and (t == 1 or (x.stride(1) >= d and x.stride(1) % per16 == 0)) and \
-        (P == 1 or (x.stride(0) >= 0 and x.stride(0) % per16 == 0)) and x.data_ptr() % 16 == 0
-    if not ok:
-        x = x.contiguous()
-    ld = x.stride(1) if t > 1 else d
-    stride = x.stride(0) if P > 1 else 0
-    return x, (L.VDR_BF16 if x.dtype == torch.bfloat16 else L.VDR_F32), ld, stride, P, t, d
+def _topk_operand(x, op: str):
+    """an operand of the per-image Gram side: the input's dtype is kept, any d % 32 == 0 -> (tensor, in_dtype, ld, image_stride,
+    problems, t, d)"""
+    o = desc_operand(x, op, keep_fp32=True)
+    return o.x, o.dtype, o.ld, o.stride, o.problems, o.t, o.d
 
 
 def _topk_work(lib, problems, t, d, k, dev):
@@ -663,52 +654,13 @@ KMEANS_CHUNK = 256  # VDR_KMEANS_CHUNK (include/vdr.h)
 KMEANS_MAX_K = 1024
 
 
-class KmeansOperand:
-    """A descriptor map as the two k-means ops read it: the bf16 tensor kept alive, its strides in elements and its shape
-    (problems, imgs, t, d); R = imgs * t rows per problem.  Built once per fit by kmeans_operand."""
-
-    def __init__(self, x, ld, image_stride, problem_stride, problems, imgs, t, d):
-        self.x, self.ld, self.image_stride, self.problem_stride = x, ld, image_stride, problem_stride
-        self.problems, self.imgs, self.t, self.d = problems, imgs, t, d
-        self.R = imgs * t
-
-    def work(self, k: int) -> torch.Tensor:
-        n = L.load().vdr_kmeans_work_bytes(self.problems, self.imgs, self.t, self.d, int(k))
-        return torch.empty((n,), dtype=torch.uint8, device=self.x.device)
+KmeansOperand = DescOperand  # (the name the k-means family and its callers know it by)
 
 
-def kmeans_operand(x: torch.Tensor, joint: bool = False, op: str = "kmeans") -> KmeansOperand:
-    """The host-side refusals of a k-means operand and its description for the library.  x [P, t, d]: one problem per image,
-    or the P * t rows of all images as one problem with joint=True; x [problems, imgs, t, d]: as it says (an expand()ed
-    leading dimension, stride 0, is one map under many sets of centroids).  bf16, or fp32 rounded once to bf16; read where
-    it lies when its channels are contiguous and its rows, images and problems 16-byte aligned (a column slice of a wider
-    buffer, rows behind a prefix), copied once otherwise.  d must be a multiple of 32."""
-    if isinstance(x, KmeansOperand):
-        return x
-    if not isinstance(x, torch.Tensor) or x.dim() not in (3, 4) or x.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"{op}: x must be a [P, t, d] or [problems, imgs, t, d] float32 or bfloat16 tensor")
-    if not x.is_cuda:
-        raise TypeError(f"{op}: x must live on the HIP device")
-    if x.dim() == 3:
-        x = x.unsqueeze(0) if joint else x.unsqueeze(1)
-    elif joint:
-        raise ValueError(f"{op}: joint=True goes with a [P, t, d] operand")
-    problems, imgs, t, d = x.shape
-    if min(problems, imgs, t, d) <= 0:
-        raise ValueError(f"{op}: empty operand")
-    if d % 32:
-        raise ValueError(f"{op}: d must be a multiple of 32, got {d}")
-    if problems * imgs * t > 2 ** 31 - 1:
-        raise ValueError(f"{op}: problems * imgs * t exceeds 2^31 - 1")
-    if x.dtype != torch.bfloat16:
-        x = x.to(torch.bfloat16)  # (fp32: rounded once)
-    ok = x.stride(3) == 1 and (t == 1 or (x.stride(2) >= d and x.stride(2) % 8 == 0)) and \
-        (imgs == 1 or (x.stride(1) >= 0 and x.stride(1) % 8 == 0)) and \
-        (problems == 1 or (x.stride(0) >= 0 and x.stride(0) % 8 == 0)) and x.data_ptr() % 16 == 0
-    if not ok:
-        x = x.contiguous()
-    return KmeansOperand(x, x.stride(2) if t > 1 else d, x.stride(1) if imgs > 1 else 0, x.stride(0) if problems > 1 else 0,
-                         problems, imgs, t, d)
+def kmeans_operand(x, joint: bool = False, op: str = "kmeans") -> DescOperand:
+    """The operand of the k-means ops and of mahalanobis: desc_operand with x [problems, imgs, t, d] taken as it says (an
+    expand()ed leading dimension, stride 0, is one map under many sets of centroids) and fp32 rounded once to bf16."""
+    return desc_operand(x, op, joint=joint, four_d=True)
 
 
 def _kmeans_k(o: KmeansOperand, centroids, op: str) -> int:
