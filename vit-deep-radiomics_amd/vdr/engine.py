@@ -3,6 +3,7 @@ the current HIP stream and (elsewhere) torch.distributed; all compute is in libv
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 
 import numpy as np
@@ -155,6 +156,35 @@ def check_descriptor_model(cfg) -> None:
         raise ValueError("facet descriptors: pre-LN models only")
 
 
+def check_input_size(cfg, height, width) -> "tuple[int, int]":
+    """The refusals of set_input_size that need no device (ValueError); returns (height, width) as ints."""
+    height, width = int(height), int(width)
+    if cfg.window > 0:
+        raise ValueError("set_input_size: the SAM encoder's position tables and window partition are tied to its "
+                         f"{cfg.img}x{cfg.img} input; its size is chosen at load time (load_model(..., img_size=...))")
+    if not cfg.patch:
+        raise ValueError("set_input_size: a token model has no input size")
+    if height <= 0 or width <= 0 or height % cfg.patch or width % cfg.patch:
+        raise ValueError(f"set_input_size: height and width must be positive multiples of patch {cfg.patch}, "
+                         f"got {height} x {width}")
+    return height, width
+
+
+def check_patch_stride(cfg, stride) -> int:
+    """The refusals of set_patch_stride that need no device (ValueError); returns the stride as an int."""
+    stride = int(stride)
+    if cfg.window > 0:
+        raise ValueError("set_patch_stride: the SAM encoder's position tables and window partition are tied to its grid")
+    if not cfg.patch:
+        raise ValueError("set_patch_stride: a token model has no patch convolution")
+    if cfg.rope:
+        raise ValueError("set_patch_stride: not for RoPE models (DINOv3's patch coordinates are defined for "
+                         "non-overlapping patches only)")
+    if stride <= 0 or stride > cfg.patch or cfg.patch % stride:
+        raise ValueError(f"set_patch_stride: stride must be a positive divisor of patch {cfg.patch}, got {stride}")
+    return stride
+
+
 def _stream_ptr(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
@@ -250,16 +280,7 @@ class Engine:
         tables are rebuilt for the new grid.
         Load-time class: allocates and synchronises, so call it outside graph capture.  SAM encoders and token models
         are tied to their geometry: ValueError."""
-        cfg = self.cfg
-        height, width = int(height), int(width)
-        if cfg.window > 0:
-            raise ValueError("set_input_size: the SAM encoder's position tables and window partition are tied to its "
-                             f"{cfg.img}x{cfg.img} input; its size is chosen at load time (load_model(..., img_size=...))")
-        if not cfg.patch:
-            raise ValueError("set_input_size: a token model has no input size")
-        if height <= 0 or width <= 0 or height % cfg.patch or width % cfg.patch:
-            raise ValueError(f"set_input_size: height and width must be positive multiples of patch {cfg.patch}, "
-                             f"got {height} x {width}")
+        height, width = check_input_size(self.cfg, height, width)
         L.check(self.lib.vdr_set_input_size(self.h, height, width), self.h)
         self._size = (height, width)
 
@@ -270,17 +291,7 @@ class Engine:
         set_input_size resamples them; stride == patch restores the default path, bit for bit.  Load-time class, in any
         order with set_input_size; the stride stays in force across later sizes.  SAM encoders, token models and RoPE
         (DINOv3) models: ValueError."""
-        cfg = self.cfg
-        stride = int(stride)
-        if cfg.window > 0:
-            raise ValueError("set_patch_stride: the SAM encoder's position tables and window partition are tied to its grid")
-        if not cfg.patch:
-            raise ValueError("set_patch_stride: a token model has no patch convolution")
-        if cfg.rope:
-            raise ValueError("set_patch_stride: not for RoPE models (DINOv3's patch coordinates are defined for "
-                             "non-overlapping patches only)")
-        if stride <= 0 or stride > cfg.patch or cfg.patch % stride:
-            raise ValueError(f"set_patch_stride: stride must be a positive divisor of patch {cfg.patch}, got {stride}")
+        stride = check_patch_stride(self.cfg, stride)
         L.check(self.lib.vdr_set_patch_stride(self.h, stride), self.h)
         self._stride = stride
 
@@ -289,6 +300,15 @@ class Engine:
         h, w = self.input_size
         if images.dim() != 4 or tuple(images.shape[1:]) != (cfg.in_chans, h, w):
             raise ValueError(f"images must be [B,{cfg.in_chans},{h},{w}], got {tuple(images.shape)}")
+
+    def _adopt_images(self, images: torch.Tensor) -> torch.Tensor:
+        """The images of a converting entry point as the library reads them: checked against the size in force, converted to
+        float32 unless they are float32 / bfloat16, moved to the engine's device, made contiguous -- a tensor that needs none
+        of it is passed on itself, no copy.  forward_into converts nothing and shares the shape check only."""
+        self._check_images(images)
+        if images.dtype not in _DT:
+            images = images.float()
+        return images.to(self.device).contiguous()
 
     # ---- workspace ------------------------------------------------------------------------------
     def _workspace(self, batch: int, seq: int = 0) -> torch.Tensor:
@@ -301,29 +321,56 @@ class Engine:
             self._ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
         return self._ws
 
-    # ---- hot path --------------------------------------------------------------------------------
-    def forward(self, images: torch.Tensor, out_mode: int = L.OUT_CLS, out_dtype=torch.float32) -> torch.Tensor:
-        cfg = self.cfg
-        self._check_images(images)
-        if images.dtype not in _DT:
-            images = images.float()
-        images = images.to(self.device).contiguous()
-        B = images.shape[0]
-        n, N, D = self.n_patches, self.n_tokens, cfg.dim
-        gh, gw = self.grid
-        shape = {L.OUT_CLS: (B, D), L.OUT_DENSE: (B, n, D), L.OUT_PATCH_EMBED: (B, n, D), L.OUT_TOKENS: (B, N, D),
-                 L.OUT_ENCODER: (B, gh, gw, cfg.neck_chans)}[out_mode]
-        out = torch.empty(shape, dtype=out_dtype, device=self.device)
-        ws = self._workspace(B)
-        L.check(self.lib.vdr_forward(self.h, images.data_ptr(), _DT[images.dtype], B, out.data_ptr(), out_mode,
-                                     _DT[out_dtype], ws.data_ptr(), ws.numel(), _stream_ptr(self.device)), self.h)
+    def _run(self, entry, x: torch.Tensor, *args, seq: int = 0):
+        """The tail of every forward: entry(handle, x, its dtype, batch, *args, workspace, its size, the current stream),
+        checked.  args: what the C entry point takes between `batch` and `workspace`."""
+        B = x.shape[0]
+        ws = self._workspace(B, seq)
+        L.check(entry(self.h, x.data_ptr(), _DT[x.dtype], B, *args, ws.data_ptr(), ws.numel(), _stream_ptr(self.device)), self.h)
+
+    def _out(self, where: str, out, dtype, shape, strided_rows: bool = False) -> torch.Tensor:
+        """The output buffer of one struct entry (`where`: "specs[0]", "maps[2]", ...): the caller's `out`, checked -- nothing
+        is converted or copied -- or, for None, a fresh one of `dtype`.  strided_rows (shape [B, D]): the rows may lie apart,
+        e.g. a column slice of a wider matrix; every other buffer is contiguous."""
+        if out is None:
+            if dtype not in _DT:
+                raise TypeError(f"{where}: dtype must be float32 or bfloat16, got {dtype}")
+            out = torch.empty(shape, dtype=dtype, device=self.device)
+        if out.dtype not in _DT:
+            raise TypeError(f"{where}: out must be float32 or bfloat16, got {out.dtype}")
+        if out.device != self.device:
+            raise ValueError(f"{where}: out must live on {self.device}")
+        if tuple(out.shape) != shape:
+            raise ValueError(f"{where}: out must be {shape}, got {tuple(out.shape)}")
+        if strided_rows:
+            B, D = shape
+            if out.stride(1) != 1 or (B > 1 and out.stride(0) < D):
+                raise ValueError(f"{where}: out rows must be contiguous and at least D = {D} elements apart")
+        elif not out.is_contiguous():
+            raise ValueError(f"{where}: out must be contiguous")
         return out
+
+    # ---- hot path --------------------------------------------------------------------------------
+    def _out_shape(self, out_mode: int, B: int) -> tuple:
+        """what vdr_forward writes for B images (KeyError: no such out_mode)"""
+        n, N, D = self.n_patches, self.n_tokens, self.cfg.dim
+        gh, gw = self.grid
+        return {L.OUT_CLS: (B, D), L.OUT_DENSE: (B, n, D), L.OUT_PATCH_EMBED: (B, n, D), L.OUT_TOKENS: (B, N, D),
+                L.OUT_ENCODER: (B, gh, gw, self.cfg.neck_chans)}[out_mode]
+
+    def _forward_into(self, images: torch.Tensor, out: torch.Tensor, out_mode: int) -> torch.Tensor:
+        self._run(self.lib.vdr_forward, images, out.data_ptr(), out_mode, _DT[out.dtype])
+        return out
+
+    def forward(self, images: torch.Tensor, out_mode: int = L.OUT_CLS, out_dtype=torch.float32) -> torch.Tensor:
+        images = self._adopt_images(images)
+        out = torch.empty(self._out_shape(out_mode, images.shape[0]), dtype=out_dtype, device=self.device)
+        return self._forward_into(images, out, out_mode)
 
     def forward_into(self, images: torch.Tensor, out: torch.Tensor, out_mode: int = L.OUT_CLS):
         """As forward(), writing into a caller-owned buffer (e.g. this rank's slice of the all-gather buffer).
         Nothing is converted or copied here, so everything is checked: a wrong dtype / layout / size is an error, never
         an out-of-bounds write."""
-        cfg = self.cfg
         self._check_images(images)
         if images.dtype not in _DT or out.dtype not in _DT:
             raise TypeError(f"images / out must be float32 or bfloat16, got {images.dtype} / {out.dtype}")
@@ -332,110 +379,36 @@ class Engine:
         if not images.is_contiguous() or not out.is_contiguous():
             raise ValueError("images and out must be contiguous")
         B = images.shape[0]
-        gh, gw = self.grid
-        per_image = {L.OUT_CLS: cfg.dim, L.OUT_DENSE: self.n_patches * cfg.dim, L.OUT_PATCH_EMBED: self.n_patches * cfg.dim,
-                     L.OUT_TOKENS: self.n_tokens * cfg.dim, L.OUT_ENCODER: gh * gw * cfg.neck_chans}[out_mode]
-        if out.numel() != B * per_image:
+        per_image = math.prod(self._out_shape(out_mode, 1))
+        if out.numel() != B * per_image:  # (the element count, not the shape: callers hand in flat slices of a wider buffer)
             raise ValueError(f"out has {out.numel()} elements, the forward writes {B} x {per_image}")
-        ws = self._workspace(B)
-        L.check(self.lib.vdr_forward(self.h, images.data_ptr(), _DT[images.dtype], B, out.data_ptr(), out_mode,
-                                     _DT[out.dtype], ws.data_ptr(), ws.numel(), _stream_ptr(self.device)), self.h)
-        return out
+        return self._forward_into(images, out, out_mode)
 
     def forward_layers(self, images: torch.Tensor, specs) -> "list[torch.Tensor]":
         """One forward, several outputs from inside the encoder (vdr_forward_layers): specs is a sequence of LayerOut;
         returns their tensors in the same order.  Caller-owned outputs are checked as forward_into checks its buffer,
         nothing is converted or copied."""
-        cfg = self.cfg
-        self._check_images(images)
-        if images.dtype not in _DT:
-            images = images.float()
-        images = images.to(self.device).contiguous()
-        B = images.shape[0]
+        images = self._adopt_images(images)
         specs = list(specs)
         if not specs:
             raise ValueError("forward_layers needs at least one LayerOut")
-        arr, outs = self._layer_outs(specs, B)
-        ws = self._workspace(B)
-        L.check(self.lib.vdr_forward_layers(self.h, images.data_ptr(), _DT[images.dtype], B, arr, len(specs), ws.data_ptr(),
-                                            ws.numel(), _stream_ptr(self.device)), self.h)
+        arr, outs = self._layer_outs(specs, images.shape[0])
+        self._run(self.lib.vdr_forward_layers, images, arr, len(specs))
         return outs
 
     def forward_attn_maps(self, images: torch.Tensor, maps, outs=()):
         """One forward that writes attention maps (vdr_forward_attn_maps): maps is a sequence of AttnMap, outs an optional
         sequence of LayerOut (forward_layers' outputs, the same bits).  Returns (feature tensors, map tensors), each in
         the order given.  Caller-owned buffers are checked, never converted or copied."""
-        cfg = self.cfg
-        self._check_images(images)
-        if images.dtype not in _DT:
-            images = images.float()
-        images = images.to(self.device).contiguous()
-        B, N, H = images.shape[0], self.n_tokens, cfg.heads
+        images = self._adopt_images(images)
+        B = images.shape[0]
         maps, specs = list(maps), list(outs)
         if not maps:
             raise ValueError("forward_attn_maps needs at least one AttnMap")
-        arr, feats = self._layer_outs(specs, B) if specs else (None, [])
+        arr, feats = self._layer_outs(specs, B)
         marr, got = self._attn_maps(maps, B)
-        ws = self._workspace(B)
-        L.check(self.lib.vdr_forward_attn_maps(self.h, images.data_ptr(), _DT[images.dtype], B, arr, len(specs), marr, len(maps),
-                                               ws.data_ptr(), ws.numel(), _stream_ptr(self.device)), self.h)
+        self._run(self.lib.vdr_forward_attn_maps, images, arr, len(specs), marr, len(maps))
         return feats, got
-
-    def _attn_maps(self, maps, B):
-        """vdr_attn_map array + the map tensors of forward_attn_maps' maps (allocated or checked)."""
-        N, H = self.n_tokens, self.cfg.heads
-        marr = (L.vdr_attn_map * len(maps))()
-        got = []
-        for k, mp in enumerate(maps):
-            if not 1 <= int(mp.q_rows) <= N:
-                raise ValueError(f"maps[{k}]: q_rows must be in [1, {N}], got {mp.q_rows}")
-            shape = (B, int(mp.q_rows), N) if mp.head_mean else (B, H, int(mp.q_rows), N)
-            out = mp.out
-            if out is None:
-                if mp.dtype not in _DT:
-                    raise TypeError(f"maps[{k}]: dtype must be float32 or bfloat16, got {mp.dtype}")
-                out = torch.empty(shape, dtype=mp.dtype, device=self.device)
-            if out.dtype not in _DT:
-                raise TypeError(f"maps[{k}]: out must be float32 or bfloat16, got {out.dtype}")
-            if out.device != self.device:
-                raise ValueError(f"maps[{k}]: out must live on {self.device}")
-            if tuple(out.shape) != shape:
-                raise ValueError(f"maps[{k}]: out must be {shape}, got {tuple(out.shape)}")
-            if not out.is_contiguous():
-                raise ValueError(f"maps[{k}]: out must be contiguous")
-            marr[k].layer, marr[k].q_rows, marr[k].head_mean = int(mp.layer), int(mp.q_rows), int(bool(mp.head_mean))
-            marr[k].out_dtype, marr[k].out = _DT[out.dtype], out.data_ptr()
-            got.append(out)
-        return marr, got
-
-    def _facet_outs(self, facets, B):
-        """vdr_facet_out array + the output tensors of forward_descriptors' facets (allocated or checked)."""
-        n, N, D = self.n_patches, self.n_tokens, self.cfg.dim
-        arr = (L.vdr_facet_out * len(facets))()
-        got = []
-        for k, f in enumerate(facets):
-            code = check_facet(f.facet, f.hierarchy, f.all_rows)
-            if not 0 <= int(f.layer) < self.cfg.layers:
-                raise ValueError(f"facets[{k}]: layer {f.layer} out of range 0..{self.cfg.layers - 1}")
-            h = int(f.hierarchy)
-            shape = (B, n, (1 + 8 * h) * D) if h else (B, N if f.all_rows else n, D)
-            out = f.out
-            if out is None:
-                if f.dtype not in _DT:
-                    raise TypeError(f"facets[{k}]: dtype must be float32 or bfloat16, got {f.dtype}")
-                out = torch.empty(shape, dtype=f.dtype, device=self.device)
-            if out.dtype not in _DT:
-                raise TypeError(f"facets[{k}]: out must be float32 or bfloat16, got {out.dtype}")
-            if out.device != self.device:
-                raise ValueError(f"facets[{k}]: out must live on {self.device}")
-            if tuple(out.shape) != shape:
-                raise ValueError(f"facets[{k}]: out must be {shape}, got {tuple(out.shape)}")
-            if not out.is_contiguous():
-                raise ValueError(f"facets[{k}]: out must be contiguous")
-            arr[k].layer, arr[k].facet, arr[k].hierarchy, arr[k].all_rows = int(f.layer), code, h, int(bool(f.all_rows))
-            arr[k].out_dtype, arr[k].out = _DT[out.dtype], out.data_ptr()
-            got.append(out)
-        return arr, got
 
     def forward_descriptors(self, images: torch.Tensor, facets, outs=(), maps=()):
         """One forward that writes facet descriptors (vdr_forward_facets): facets is a sequence of FacetOut, outs / maps
@@ -444,59 +417,66 @@ class Engine:
         key / query / value facets stops after its qkv GEMM.  Caller-owned buffers are checked, never converted or copied;
         the refusals that need no device (unknown facet, hierarchy outside 0..3, binning with all_rows, SAM / token /
         post-LN / block-less models) are ValueError."""
-        cfg = self.cfg
         facets, specs, maps = list(facets), list(outs), list(maps)
         if not facets:
             raise ValueError("forward_descriptors needs at least one FacetOut")
         for f in facets:
             check_facet(f.facet, f.hierarchy, f.all_rows)
-        check_descriptor_model(cfg)
-        self._check_images(images)
-        if images.dtype not in _DT:
-            images = images.float()
-        images = images.to(self.device).contiguous()
+        check_descriptor_model(self.cfg)
+        images = self._adopt_images(images)
         B = images.shape[0]
         farr, fgot = self._facet_outs(facets, B)
-        arr, feats = self._layer_outs(specs, B) if specs else (None, [])
-        marr, mgot = self._attn_maps(maps, B) if maps else (None, [])
-        ws = self._workspace(B)
-        L.check(self.lib.vdr_forward_facets(self.h, images.data_ptr(), _DT[images.dtype], B, arr, len(specs), marr, len(maps),
-                                            farr, len(facets), ws.data_ptr(), ws.numel(), _stream_ptr(self.device)), self.h)
+        arr, feats = self._layer_outs(specs, B)
+        marr, mgot = self._attn_maps(maps, B)
+        self._run(self.lib.vdr_forward_facets, images, arr, len(specs), marr, len(maps), farr, len(facets))
         return fgot, feats, mgot
 
+    # vdr_layer_out / vdr_attn_map / vdr_facet_out arrays (None: no entry) + their tensors: what shape, which struct fields
     def _layer_outs(self, specs, B):
-        """vdr_layer_out array + the output tensors of forward_layers' specs (allocated or checked)."""
-        cfg = self.cfg
-        D = cfg.dim
-        arr = (L.vdr_layer_out * len(specs))()
-        outs = []
+        if not specs:
+            return None, []
+        D = self.cfg.dim
+        rows = {L.OUT_CLS: None, L.OUT_POOLED: None, L.OUT_DENSE: self.n_patches, L.OUT_TOKENS: self.n_tokens}
+        arr, outs = (L.vdr_layer_out * len(specs))(), []
         for k, sp in enumerate(specs):
-            rows = {L.OUT_CLS: None, L.OUT_POOLED: None, L.OUT_DENSE: self.n_patches, L.OUT_TOKENS: self.n_tokens}
             if sp.mode not in rows:
                 raise ValueError(f"specs[{k}]: mode must be OUT_CLS, OUT_DENSE, OUT_TOKENS or OUT_POOLED, got {sp.mode}")
-            shape = (B, D) if rows[sp.mode] is None else (B, rows[sp.mode], D)
-            out = sp.out
-            if out is None:
-                if sp.dtype not in _DT:
-                    raise TypeError(f"specs[{k}]: dtype must be float32 or bfloat16, got {sp.dtype}")
-                out = torch.empty(shape, dtype=sp.dtype, device=self.device)
-            if out.dtype not in _DT:
-                raise TypeError(f"specs[{k}]: out must be float32 or bfloat16, got {out.dtype}")
-            if out.device != self.device:
-                raise ValueError(f"specs[{k}]: out must live on {self.device}")
-            if tuple(out.shape) != shape:
-                raise ValueError(f"specs[{k}]: out must be {shape}, got {tuple(out.shape)}")
-            ld = 0
-            if rows[sp.mode] is None:  # [B, D] rows b*ld apart
-                if out.stride(1) != 1 or (B > 1 and out.stride(0) < D):
-                    raise ValueError(f"specs[{k}]: out rows must be contiguous and at least D = {D} elements apart")
-                ld = out.stride(0) if B > 1 else D
-            elif not out.is_contiguous():
-                raise ValueError(f"specs[{k}]: out must be contiguous")
+            r = rows[sp.mode]  # None: [B, D] rows b*ld apart
+            out = self._out(f"specs[{k}]", sp.out, sp.dtype, (B, D) if r is None else (B, r, D), strided_rows=r is None)
+            ld = 0 if r is not None else out.stride(0) if B > 1 else D
             arr[k].layer, arr[k].out_mode, arr[k].out_dtype = int(sp.layer), int(sp.mode), _DT[out.dtype]
             arr[k].norm, arr[k].ld, arr[k].out = int(bool(sp.norm)), ld, out.data_ptr()
             outs.append(out)
         return arr, outs
+
+    def _attn_maps(self, maps, B):
+        if not maps:
+            return None, []
+        N, H = self.n_tokens, self.cfg.heads
+        marr, got = (L.vdr_attn_map * len(maps))(), []
+        for k, mp in enumerate(maps):
+            q = int(mp.q_rows)
+            if not 1 <= q <= N:
+                raise ValueError(f"maps[{k}]: q_rows must be in [1, {N}], got {mp.q_rows}")
+            out = self._out(f"maps[{k}]", mp.out, mp.dtype, (B, q, N) if mp.head_mean else (B, H, q, N))
+            marr[k].layer, marr[k].q_rows, marr[k].head_mean = int(mp.layer), q, int(bool(mp.head_mean))
+            marr[k].out_dtype, marr[k].out = _DT[out.dtype], out.data_ptr()
+            got.append(out)
+        return marr, got
+
+    def _facet_outs(self, facets, B):
+        n, N, D = self.n_patches, self.n_tokens, self.cfg.dim
+        arr, got = (L.vdr_facet_out * len(facets))(), []
+        for k, f in enumerate(facets):
+            code = check_facet(f.facet, f.hierarchy, f.all_rows)
+            if not 0 <= int(f.layer) < self.cfg.layers:
+                raise ValueError(f"facets[{k}]: layer {f.layer} out of range 0..{self.cfg.layers - 1}")
+            h = int(f.hierarchy)
+            out = self._out(f"facets[{k}]", f.out, f.dtype, (B, n, (1 + 8 * h) * D) if h else (B, N if f.all_rows else n, D))
+            arr[k].layer, arr[k].facet, arr[k].hierarchy, arr[k].all_rows = int(f.layer), code, h, int(bool(f.all_rows))
+            arr[k].out_dtype, arr[k].out = _DT[out.dtype], out.data_ptr()
+            got.append(out)
+        return arr, got
 
     def forward_tokens(self, tokens: torch.Tensor, out_mode: int = L.OUT_CLS, out_dtype=torch.float32,
                        lengths=None) -> torch.Tensor:
@@ -511,18 +491,15 @@ class Engine:
         c = 1 if cfg.has_cls else 0
         shape = {L.OUT_CLS: (B, D), L.OUT_DENSE: (B, S, D), L.OUT_TOKENS: (B, S + c, D)}[out_mode]
         out = torch.empty(shape, dtype=out_dtype, device=self.device)
-        ws = self._workspace(B, S)
+        tail = (out.data_ptr(), out_mode, _DT[out_dtype])
         if lengths is None:
-            L.check(self.lib.vdr_forward_tokens(self.h, tokens.data_ptr(), _DT[tokens.dtype], B, S, out.data_ptr(), out_mode,
-                                                _DT[out_dtype], ws.data_ptr(), ws.numel(), _stream_ptr(self.device)), self.h)
+            self._run(self.lib.vdr_forward_tokens, tokens, S, *tail, seq=S)
             return out
         lens = torch.as_tensor(lengths, dtype=torch.int32)
         if lens.shape != (B,) or int(lens.min()) < 1 or int(lens.max()) > S:
             raise ValueError(f"lengths must be [B] with 1 <= length <= {S}")
         lens = lens.to(self.device).contiguous()
-        L.check(self.lib.vdr_forward_tokens_varlen(self.h, tokens.data_ptr(), _DT[tokens.dtype], B, S, lens.data_ptr(),
-                                                   out.data_ptr(), out_mode, _DT[out_dtype], ws.data_ptr(), ws.numel(),
-                                                   _stream_ptr(self.device)), self.h)
+        self._run(self.lib.vdr_forward_tokens_varlen, tokens, S, lens.data_ptr(), *tail, seq=S)
         return out
 
     # ---- profiler ---------------------------------------------------------------------------------

@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .engine import AttnMap, Engine, FacetOut, LayerOut, VdrConfig, check_descriptor_model, check_facet
+from .engine import (AttnMap, Engine, FacetOut, LayerOut, VdrConfig, check_descriptor_model, check_facet, check_input_size,
+                     check_patch_stride)
 
 _DINOV3 = dict(layerscale=True, has_pos=False, ln_eps=1e-5, n_register=4, rope=True, rope_theta=100.0)
 
@@ -92,6 +93,34 @@ def sam_input_side(img_size, patch: int) -> int:
     return side
 
 
+def block_indices(idx, depth: int, what: str) -> "list[int]":
+    """A sequence of block indices as ints, in the order given; an empty one or an index outside 0..depth-1: ValueError."""
+    idx = [int(i) for i in idx]
+    if not idx:
+        raise ValueError(f"{what}: no block index given")
+    bad = [i for i in idx if not 0 <= i < depth]
+    if bad:
+        raise ValueError(f"block indices {bad} out of range 0..{depth - 1}")
+    return idx
+
+
+def check_batch(what: str, x) -> None:
+    """The one wording of "x is no image batch" (ValueError); the size is the engine's to check."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError(f"{what}: x must be [B, 3, H, W], got {tuple(getattr(x, 'shape', ()))}")
+
+
+def facet_args(model, what: str, layer, facet, bin, hierarchy, sentence: str) -> int:
+    """The descriptor arguments of a method that also takes facet=None (the model's own dense descriptor, which has no block to
+    choose and nothing to bin: a layer or bin is refused with `sentence`); a facet: model._descriptor_args' refusals.  Returns the
+    hierarchy to ask for."""
+    if facet is not None:
+        return model._descriptor_args(layer, facet, bool(bin), False, hierarchy)
+    if layer is not None or bin:
+        raise ValueError(f"{what}: {sentence}")
+    return 0
+
+
 def intermediate_layer_indices(n, depth: int) -> "list[int]":
     """The blocks DINOv2's get_intermediate_layers returns (DinoVisionTransformer._get_intermediate_layers_not_chunked):
     an int n means the last n blocks; a sequence means those block indices, returned in block order (the blocks are
@@ -102,12 +131,7 @@ def intermediate_layer_indices(n, depth: int) -> "list[int]":
         if not 1 <= int(n) <= depth:
             raise ValueError(f"n = {n}: the model has {depth} blocks")
         return list(range(depth - int(n), depth))
-    idx = [int(i) for i in n]
-    if not idx:
-        raise ValueError("n: no block index given")
-    bad = [i for i in idx if not 0 <= i < depth]
-    if bad:
-        raise ValueError(f"block indices {bad} out of range 0..{depth - 1}")
+    idx = block_indices(n, depth, "n")
     if len(set(idx)) != len(idx):
         raise ValueError(f"block indices {idx} repeat one")
     return sorted(idx)
@@ -247,9 +271,7 @@ class VitDescriptorModel:
     def set_input_size(self, height: int, width: int):
         """Run on [B, 3, height, width] images from now on (multiples of the patch side; square or rectangular): the
         learned pos_embed is resampled once on the device (Engine.set_input_size).  ViT / DINOv2 models."""
-        if self.cfg.window > 0:
-            raise ValueError("set_input_size: the SAM encoder's position tables and window partition are tied to its "
-                             f"{self.cfg.img}x{self.cfg.img} input")
+        check_input_size(self.cfg, height, width)  # (the engine's refusals, for a model that has no engine yet)
         self.engine.set_input_size(height, width)
         return self
 
@@ -260,8 +282,7 @@ class VitDescriptorModel:
         ((H - patch) // stride + 1) x ((W - patch) // stride + 1) grid of overlapping patches (Engine.set_patch_stride;
         dino-vit-features' ViTExtractor(stride=...)).  The stride stays in force across input sizes (dynamic_size
         included); stride == patch restores the default.  ViT / DINOv2 / CLIP / SigLIP models."""
-        if self.cfg.window > 0:
-            raise ValueError("set_patch_stride: the SAM encoder's position tables and window partition are tied to its grid")
+        check_patch_stride(self.cfg, stride)  # (as above)
         self.engine.set_patch_stride(stride)
         return self
 
@@ -282,6 +303,36 @@ class VitDescriptorModel:
         """dynamic_size: take the size of x as the input size (a no-op when it is the one in force)."""
         if getattr(self, "dynamic_size", False) and x.dim() == 4 and tuple(x.shape[-2:]) != tuple(self.engine.input_size):
             self.set_input_size(int(x.shape[-2]), int(x.shape[-1]))
+
+    def _descriptors(self, x, layer, facet, h, all_rows=False, dtype=torch.bfloat16, saliency=False):
+        """The descriptor request of every analysis, for arguments _descriptor_args has passed and a checked [B, 3, H, W]
+        batch: the size of x adopted, then ONE forward_descriptors call for the `facet` descriptors of block `layer` (None: the
+        last) at hierarchy `h` -> the [B, t, d] buffer.  saliency=True: the same forward also writes the last block's CLS
+        attention, mean over the heads; returns (buffer, that attention over the patch columns, min-max normalised per image,
+        [B, n] fp32)."""
+        i = self.cfg.layers - 1 if layer is None else int(layer)
+        self._adopt(x)
+        maps = [AttnMap(self.cfg.layers - 1, 1, True)] if saliency else []
+        (desc,), _, att = self.engine.forward_descriptors(x, [FacetOut(i, facet, h, bool(all_rows), dtype)], maps=maps)
+        return (desc, minmax_normalise(att[0][:, 0, self.cfg.n_prefix:])) if saliency else desc
+
+    def _saliency_ok(self, what):
+        if not self.cfg.has_cls:
+            raise ValueError(f"{what}: the saliency is the CLS row's attention; the model has no CLS token")
+
+    def _dense_map(self, x, layer=None, facet=None, h=0, dtype=torch.float32, mode=None) -> torch.Tensor:
+        """The dense map of x as [B, gh, gw, d], channel-last, from one forward.  facet=None: the model's own dense descriptor
+        in fp32 -- the SAM neck output for a windowed model, patch_embed otherwise (mode: another out_mode on the patch grid
+        instead, extract_dense's OUT_DENSE); a facet: _descriptors' buffer in `dtype`, viewed on the grid in force."""
+        self._adopt(x)
+        if facet is not None:
+            rows = self._descriptors(x, layer, facet, h, dtype=dtype)
+        elif mode is None and self.cfg.window > 0:
+            return self.engine.forward(x, L.OUT_ENCODER, torch.float32)  # [B, g, g, C], channel-last already
+        else:
+            rows = self.engine.forward(x, L.OUT_PATCH_EMBED if mode is None else mode, torch.float32)
+        gh, gw = self.engine.grid
+        return rows.reshape(rows.shape[0], gh, gw, rows.shape[-1])
 
     # -- nn.Module-style no-ops so reference code such as model.eval().cuda() keeps working
     def eval(self):
@@ -397,12 +448,8 @@ class VitDescriptorModel:
         if reshape and not cls_only:
             raise ValueError("get_attention_maps: reshape needs cls_only")
         single = layers is None or isinstance(layers, (int, np.integer))
-        idx = [self.cfg.layers - 1] if layers is None else [int(layers)] if single else [int(i) for i in layers]
-        if not idx:
-            raise ValueError("get_attention_maps: no block index given")
-        bad = [i for i in idx if not 0 <= i < self.cfg.layers]
-        if bad:
-            raise ValueError(f"block indices {bad} out of range 0..{self.cfg.layers - 1}")
+        idx = block_indices([self.cfg.layers - 1] if layers is None else [layers] if single else layers, self.cfg.layers,
+                            "get_attention_maps")
         self._adopt(x)
         N, ncls = self.engine.n_tokens, self.cfg.n_prefix  # (reshape drops the CLS and register key columns)
         _, got = self.engine.forward_attn_maps(x, [AttnMap(i, 1 if cls_only else N, head_mean) for i in idx])
@@ -430,13 +477,9 @@ class VitDescriptorModel:
         h = self._descriptor_args(layer, facet, bin, include_cls, hierarchy)
         if reshape and include_cls:
             raise ValueError("extract_descriptors: reshape needs include_cls=False (the prefix rows have no grid position)")
-        i = self.cfg.layers - 1 if layer is None else int(layer)
-        self._adopt(x)
-        (got,), _, _ = self.engine.forward_descriptors(x, [FacetOut(i, facet, h, bool(include_cls), torch.float32)])
         if reshape:
-            gh, gw = self.engine.grid
-            return got.reshape(got.shape[0], gh, gw, got.shape[-1])
-        return got.unsqueeze(1)
+            return self._dense_map(x, layer, facet, h, torch.float32)
+        return self._descriptors(x, layer, facet, h, include_cls, torch.float32).unsqueeze(1)
 
     def upsample_descriptors(self, x: torch.Tensor, layer=None, facet="key", bin: bool = False, hierarchy: int = 2, box=None,
                              radius: int = 2, sigma_spatial: float = 1.0, sigma_range: float = 0.1,
@@ -451,13 +494,8 @@ class VitDescriptorModel:
         dynamic_size in force apply.  Refusals (ValueError, before any device work): extract_descriptors' own, a layer or bin
         without a facet, and the op's (radius outside 1..3, a box outside the image, non-positive sigmas)."""
         from . import ops
-        h = 0
-        if facet is not None:
-            h = self._descriptor_args(layer, facet, bool(bin), False, hierarchy)
-        elif layer is not None or bin:
-            raise ValueError("upsample_descriptors: layer and bin need a facet")
-        if not isinstance(x, torch.Tensor) or x.dim() != 4:
-            raise ValueError(f"upsample_descriptors: x must be [B, 3, H, W], got {tuple(getattr(x, 'shape', ()))}")
+        h = facet_args(self, "upsample_descriptors", layer, facet, bin, hierarchy, "layer and bin need a facet")
+        check_batch("upsample_descriptors", x)
         if not 1 <= int(radius) <= ops.UPSAMPLE_MAX_RADIUS:
             raise ValueError(f"upsample_descriptors: radius must be 1..{ops.UPSAMPLE_MAX_RADIUS}, got {radius}")
         if out_dtype not in (torch.float32, torch.bfloat16):
@@ -470,19 +508,8 @@ class VitDescriptorModel:
                 raise ValueError(f"upsample_descriptors: box {tuple(box)} must be non-empty and inside the {H} x {W} image")
         guide = x if x.dtype in (torch.float32, torch.bfloat16) else x.float()
         guide = guide.to(self.device)
-        if self.cfg.window > 0:
-            desc = self.engine.forward(x, L.OUT_ENCODER, torch.float32)  # [B, g, g, C], channel-last
-            p = s = self.cfg.patch
-        else:
-            self._adopt(x)
-            gh, gw = self.engine.grid
-            p, s = int(self.cfg.patch), int(self.engine.patch_stride)
-            if facet is None:
-                desc = self.engine.forward(x, L.OUT_PATCH_EMBED, torch.float32)
-            else:
-                i = self.cfg.layers - 1 if layer is None else int(layer)
-                (desc,), _, _ = self.engine.forward_descriptors(x, [FacetOut(i, facet, h, False, torch.bfloat16)])
-            desc = desc.reshape(desc.shape[0], gh, gw, desc.shape[-1])
+        desc = self._dense_map(x, layer, facet, h, torch.bfloat16)
+        p, s = int(self.cfg.patch), int(self.engine.patch_stride)  # (a SAM encoder has no other stride than its patch side)
         return ops.upsample_guided(desc, guide, p, s, radius=int(radius), sigma_spatial=sigma_spatial, sigma_range=sigma_range,
                                    box=box, out_dtype=out_dtype)
 
@@ -501,20 +528,14 @@ class VitDescriptorModel:
         before any device work): extract_descriptors' (unknown facet, hierarchy outside 1..3, a layer out of range, SAM /
         token / post-LN / block-less models), a model without a CLS token, x1 and x2 of different shapes."""
         h = self._descriptor_args(layer, facet, bin, False, hierarchy)
-        if not self.cfg.has_cls:
-            raise ValueError("find_correspondences: the saliency is the CLS row's attention; the model has no CLS token")
+        self._saliency_ok("find_correspondences")
         if x1.dim() != 4 or tuple(x1.shape) != tuple(x2.shape):
             raise ValueError(f"find_correspondences: x1 and x2 must be [B, 3, H, W] of the same shape, got {tuple(x1.shape)} "
                              f"and {tuple(x2.shape)}")
         from . import ops
-        i = self.cfg.layers - 1 if layer is None else int(layer)
-        self._adopt(x1)
         B = x1.shape[0]
-        both = torch.cat([x1.to(self.device), x2.to(self.device)])
-        (desc,), _, (att,) = self.engine.forward_descriptors(both, [FacetOut(i, facet, h, False, torch.bfloat16)],
-                                                             maps=[AttnMap(self.cfg.layers - 1, 1, True)])
+        desc, sal = self._descriptors(torch.cat([x1.to(self.device), x2.to(self.device)]), layer, facet, h, saliency=True)
         sim12, nn12, sim21, nn21 = ops.nn_cosine(desc[:B], desc[B:])
-        sal = minmax_normalise(att[:, 0, self.cfg.n_prefix:])
         sal1, sal2 = sal[:B], sal[B:]
         mask = ops.best_buddies(nn12, nn21) & (sal1 > thresh) & (torch.gather(sal2, 1, nn12.long()) > thresh)
         res = Correspondences(nn12, sim12, nn21, sim21, sal1, sal2, mask, tuple(self.engine.grid), int(self.engine.patch_stride),
@@ -538,22 +559,17 @@ class VitDescriptorModel:
         rule is upstream's as remembered (vdr.kmeans.elbow), not pinned against its code.
         Refusals (ValueError, before any device work): find_correspondences' own, k outside 1..1024 or above B * t."""
         h = self._descriptor_args(layer, facet, bin, False, hierarchy)
-        if not self.cfg.has_cls:
-            raise ValueError("cosegment: the saliency is the CLS row's attention; the model has no CLS token")
-        if x.dim() != 4:
-            raise ValueError(f"cosegment: x must be [B, 3, H, W], got {tuple(x.shape)}")
+        self._saliency_ok("cosegment")
+        check_batch("cosegment", x)
         if k is not None and (isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 1024):
             raise ValueError(f"cosegment: k must be None or an integer in 1..1024, got {k!r}")
         from . import kmeans
-        i = self.cfg.layers - 1 if layer is None else int(layer)
         self._adopt(x)
         B = x.shape[0]
         gh, gw = self.engine.grid
         if k is not None and int(k) > B * gh * gw:
             raise ValueError(f"cosegment: k = {k} exceeds the {B * gh * gw} patches of the {B} images")
-        (desc,), _, (att,) = self.engine.forward_descriptors(x.to(self.device), [FacetOut(i, facet, h, False, torch.bfloat16)],
-                                                             maps=[AttnMap(self.cfg.layers - 1, 1, True)])
-        sal = minmax_normalise(att[:, 0, self.cfg.n_prefix:])
+        desc, sal = self._descriptors(x, layer, facet, h, saliency=True)
         rows = torch.nn.functional.normalize(desc.float(), dim=-1, eps=1e-12).to(torch.bfloat16)
         if k is None:
             fit = kmeans.elbow(rows, ratio=float(elbow), joint=True, **fit_kwargs)
@@ -567,15 +583,11 @@ class VitDescriptorModel:
     def _affinity_graph(self, x, what, layer, facet, bin, hierarchy, tau):
         """one forward for the bf16 `facet` descriptors of x, then their thresholded affinity graph, read in place"""
         h = self._descriptor_args(layer, facet, bin, False, hierarchy)
-        if x.dim() != 4:
-            raise ValueError(f"{what}: x must be [B, 3, H, W], got {tuple(x.shape)}")
+        check_batch(what, x)
         if tau != tau:
             raise ValueError(f"{what}: tau is NaN")
         from . import ops
-        i = self.cfg.layers - 1 if layer is None else int(layer)
-        self._adopt(x)
-        (desc,), _, _ = self.engine.forward_descriptors(x.to(self.device), [FacetOut(i, facet, h, False, torch.bfloat16)])
-        return ops.affinity_bits(desc, tau=tau)
+        return ops.affinity_bits(self._descriptors(x, layer, facet, h), tau=tau)
 
     def tokencut(self, x: torch.Tensor, layer=None, facet: str = "key", bin: bool = False, tau: float = 0.2, eps: float = 1e-5,
                  hierarchy: int = 2):
@@ -607,12 +619,12 @@ class VitDescriptorModel:
         return spectral.lost(bits, tuple(self.engine.grid), k=int(k), stride=int(self.engine.patch_stride), patch=int(self.cfg.patch))
 
     def _anomaly_args(self, what, layer, facet, bin, hierarchy):
-        """the device-free refusals shared by fit_anomaly and anomaly_map; returns (hierarchy to ask for, block, channels)"""
+        """the device-free refusals shared by fit_anomaly and anomaly_map; returns (hierarchy to ask for, channels)"""
         h = self._descriptor_args(layer, facet, bin, False, hierarchy)
         d = self.cfg.dim * (1 + 8 * h)
         if d % 32:
             raise ValueError(f"{what}: {d} descriptor channels; the Mahalanobis kernel takes multiples of 32")
-        return h, (self.cfg.layers - 1 if layer is None else int(layer)), d
+        return h, d
 
     def fit_anomaly(self, batches, layer=None, facet: str = "key", bin: bool = False, per_position: bool = False,
                     shrinkage: float = 0.01, ridge: float = 0.0, n_components=None, hierarchy: int = 2):
@@ -625,7 +637,7 @@ class VitDescriptorModel:
         stride and dynamic_size in force apply.  Refusals (ValueError, before any device work): extract_descriptors' own, a
         descriptor wider than the covariance kernel's 2048 channels; and a per-position batch on another grid than the first."""
         from . import anomaly
-        h, i, d = self._anomaly_args("fit_anomaly", layer, facet, bin, hierarchy)
+        h, d = self._anomaly_args("fit_anomaly", layer, facet, bin, hierarchy)
         if d > 2048:
             raise ValueError(f"fit_anomaly: {d} descriptor channels; the covariance kernel takes at most 2048")
         acc = anomaly.GaussianAccumulator(per_position)
@@ -638,8 +650,7 @@ class VitDescriptorModel:
                 acc.grid = grid
             elif per_position and grid != acc.grid:
                 raise ValueError(f"fit_anomaly: a per-position fit needs one grid; got {grid} after {acc.grid}")
-            (desc,), _, _ = self.engine.forward_descriptors(x.to(self.device), [FacetOut(i, facet, h, False, torch.bfloat16)])
-            acc.add(desc)
+            acc.add(self._descriptors(x, layer, facet, h))
         return acc.finish(shrinkage, ridge, n_components)
 
     def anomaly_map(self, x: torch.Tensor, gaussian, layer=None, facet: str = "key", bin: bool = False, hierarchy: int = 2):
@@ -648,20 +659,19 @@ class VitDescriptorModel:
         (d2 [B, gh, gw], score [B], upsample()).  The input size, patch stride and dynamic_size in force apply.  Refusals
         (ValueError): extract_descriptors' own, a model of another channel count, a per-position model on another grid."""
         from . import anomaly
-        h, i, d = self._anomaly_args("anomaly_map", layer, facet, bin, hierarchy)
+        h, d = self._anomaly_args("anomaly_map", layer, facet, bin, hierarchy)
         if not isinstance(gaussian, anomaly.Gaussian):
             raise TypeError("anomaly_map: gaussian must be a vdr.anomaly.Gaussian (fit_anomaly)")
         if int(gaussian.mean.shape[1]) != d:
             raise ValueError(f"anomaly_map: the Gaussian has {int(gaussian.mean.shape[1])} channels, the descriptors {d}")
-        if x.dim() != 4:
-            raise ValueError(f"anomaly_map: x must be [B, 3, H, W], got {tuple(x.shape)}")
+        check_batch("anomaly_map", x)
         self._adopt(x)
         gh, gw = self.engine.grid
         if gaussian.per_position and (gaussian.grid is not None and tuple(gaussian.grid) != (gh, gw)
                                       or int(gaussian.mean.shape[0]) != gh * gw):
             raise ValueError(f"anomaly_map: the per-position Gaussian was fitted on the grid {gaussian.grid}, the input gives "
                              f"{(gh, gw)}")
-        (desc,), _, _ = self.engine.forward_descriptors(x.to(self.device), [FacetOut(i, facet, h, False, torch.bfloat16)])
+        desc = self._descriptors(x, layer, facet, h)
         return anomaly.AnomalyMap(gaussian.score(desc).reshape(desc.shape[0], gh, gw))
 
     def pca_descriptors(self, x: torch.Tensor, n_components: int = 3, layer=None, facet=None, joint: bool = False,
@@ -693,13 +703,8 @@ class VitDescriptorModel:
         from . import pca
         if solver not in pca.SOLVERS:
             raise ValueError(f"pca_descriptors: solver must be one of {pca.SOLVERS}, got {solver!r}")
-        h = 0
-        if facet is not None:
-            h = self._descriptor_args(layer, facet, bool(bin), False, hierarchy)
-        elif layer is not None:
-            raise ValueError("pca_descriptors: layer needs a facet")
-        elif bin:
-            raise ValueError("pca_descriptors: bin needs a facet")
+        h = facet_args(self, "pca_descriptors", layer, facet, bin, hierarchy,
+                       f"{'layer' if layer is not None else 'bin'} needs a facet")
         if not 1 <= int(n_components) <= 8:
             raise ValueError(f"pca_descriptors: n_components must be 1..8, got {n_components}")
         d = self.cfg.neck_chans if facet is None and self.cfg.window > 0 else self.cfg.dim
@@ -707,24 +712,12 @@ class VitDescriptorModel:
         if d % 32 or (d > 2048 and solver == "eigh"):
             raise ValueError(f"pca_descriptors: {d} descriptor channels; the covariance kernel takes multiples of 32 up to 2048 "
                              "(which also excludes log-binned descriptors, bin=True, at ViT-B width)")
-        if x.dim() != 4:
-            raise ValueError(f"pca_descriptors: x must be [B, 3, H, W], got {tuple(x.shape)}")
-        if facet is None and self.cfg.window > 0:
-            if solver == "subspace":  # (fit's refusals, ahead of the forward: the SAM grid is fixed by the configuration)
-                pca._check_subspace(int(x.shape[0]), (self.cfg.img // self.cfg.patch) ** 2, d, int(n_components), joint)
-            desc = self.engine.forward(x, L.OUT_ENCODER, torch.float32)  # [B, g, g, C], channel-last
-            gh, gw = int(desc.shape[1]), int(desc.shape[2])
-        else:
+        check_batch("pca_descriptors", x)
+        if solver == "subspace":  # (fit's refusals, ahead of the forward; a SAM encoder's grid is its configuration's)
             self._adopt(x)
-            gh, gw = self.engine.grid
-            if solver == "subspace":  # (fit's refusals, ahead of the forward)
-                pca._check_subspace(int(x.shape[0]), gh * gw, d, int(n_components), joint)
-            if facet is None:
-                desc = self.engine.forward(x, L.OUT_PATCH_EMBED, torch.float32)
-            else:
-                i = self.cfg.layers - 1 if layer is None else int(layer)
-                (desc,), _, _ = self.engine.forward_descriptors(x, [FacetOut(i, facet, h, False, torch.bfloat16)])
-        B = desc.shape[0]
+            pca._check_subspace(int(x.shape[0]), self.engine.n_patches, d, int(n_components), joint)
+        desc = self._dense_map(x, layer, facet, h, torch.bfloat16)
+        B, gh, gw = desc.shape[:3]
         rgb = pca._colorize_maps(desc.reshape(B, gh * gw, desc.shape[-1]), int(n_components), joint, remove_bg, solver)
         return rgb.reshape(B, gh, gw, rgb.shape[-1])
 
@@ -761,7 +754,7 @@ class VitDescriptorModel:
 
 
 def _pad_rows8(w: torch.Tensor) -> torch.Tensor:
-    """rows zero-padded to a multiple of 8 (the GEMM's N rule), as _MlpHead pads dense2"""
+    """rows zero-padded to a multiple of 8 (the GEMM's N rule): a weight matrix, or its bias"""
     n = w.shape[0]
     out = torch.zeros(((n + 7) // 8 * 8,) + tuple(w.shape[1:]), dtype=w.dtype)
     out[:n] = w
@@ -896,10 +889,7 @@ def get_dense_descriptor(model, img, layer=None, facet=None, bin: bool = False, 
     model.extract_descriptors(t, layer, facet, bin, hierarchy=hierarchy, reshape=True) instead -- (h, w, D), or
     (h, w, (1 + 8*hierarchy)*D) with bin=True."""
     from . import prep
-    if facet is not None:
-        model._descriptor_args(layer, facet, bin, False, hierarchy)  # (refusals before any device work)
-    elif layer is not None or bin:
-        raise ValueError("get_dense_descriptor: layer / bin need a facet")
+    facet_args(model, "get_dense_descriptor", layer, facet, bin, hierarchy, "layer / bin need a facet")  # (before any device work)
     t = torch.as_tensor(img)
     side = model.cfg.img
     prepared = t.dim() == 4 or (t.dim() == 3 and t.shape[0] == 3 and tuple(t.shape[1:]) == (side, side))
@@ -935,12 +925,8 @@ def extract_dense(model, images: torch.Tensor, encoder: bool = True, layer=None,
     VitDescriptorModel.extract_descriptors(..., reshape=True) instead, (B, h, w, d)."""
     if facet is not None:
         return model.extract_descriptors(images, layer, facet, bin, False, hierarchy, reshape=True).cpu().numpy()
-    if layer is not None or bin:
-        raise ValueError("extract_dense: layer / bin need a facet")
-    model._adopt(images)
-    gh, gw = model.engine.grid
-    f = model.engine.forward(images, L.OUT_DENSE if encoder else L.OUT_PATCH_EMBED, torch.float32)
-    return f.reshape(images.shape[0], gh, gw, model.cfg.dim).cpu().numpy()
+    facet_args(model, "extract_dense", layer, facet, bin, hierarchy, "layer / bin need a facet")
+    return model._dense_map(images, mode=L.OUT_DENSE if encoder else L.OUT_PATCH_EMBED).cpu().numpy()
 
 
 class _DropIn:
@@ -1017,12 +1003,7 @@ class _MlpHead:
         self.b1 = sd[prefix + ".dense1.bias"].to(dev, torch.float32).contiguous()
         w2, b2 = sd[prefix + ".dense2.weight"].float().cpu(), sd[prefix + ".dense2.bias"].float().cpu()
         self.n = w2.shape[0]
-        npad = (self.n + 7) // 8 * 8
-        wp = torch.zeros((npad, w2.shape[1]), dtype=torch.float32)
-        wp[: self.n] = w2
-        bp = torch.zeros((npad,), dtype=torch.float32)
-        bp[: self.n] = b2
-        self.w2, self.b2 = wp.to(dev, torch.bfloat16).contiguous(), bp.to(dev)
+        self.w2, self.b2 = _pad_rows8(w2).to(dev, torch.bfloat16).contiguous(), _pad_rows8(b2).to(dev)
 
     def __call__(self, x):
         from . import ops

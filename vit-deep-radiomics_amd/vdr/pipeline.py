@@ -142,7 +142,6 @@ def generate_features(model, img_3d, mask_3d, flip=None, max_batch=16, descripto
     if vol.dtype not in (torch.float32, torch.float64):
         vol = vol.to(torch.float32)
     S = vol.shape[2]
-    medsam = model.model_name == "medsam"
     features_list, mask_list = [], []
     rb = mb = None
     pending = []
@@ -169,11 +168,8 @@ def generate_features(model, img_3d, mask_3d, flip=None, max_batch=16, descripto
             continue
         if desc is not None:
             maps = model.extract_descriptors(x, reshape=True, **desc)             # [b, gh, gw, d] channel-last
-        elif medsam:
-            maps = model.engine.forward(x, L.OUT_ENCODER, torch.float32)          # [b, g, g, C] channel-last
-        else:
-            gh, gw = model.engine.grid  # (img / patch a side by default; finer after set_patch_stride)
-            maps = model.engine.forward(x, L.OUT_PATCH_EMBED, torch.float32).reshape(s1 - s0, gh, gw, model.cfg.dim)
+        else:  # the model's own: a SAM encoder's neck output [b, g, g, C], else patch_embed on the grid in force
+            maps = model._dense_map(x)
         if rb is None:  # the boxes depend on the (cropped) union mask only: once per volume, not once per slice
             rb = roi_box(maps.shape[1:3], bigger_c)
             mb = roi_box(mask_c.shape[0:2], bigger_c)
