@@ -774,6 +774,43 @@ int vdr_op_nn_cosine(const void* x, int64_t ldx, int64_t x_stride, int tx,
                      int pairs, int d, void* work,
                      float* row_sim, int32_t* row_idx, float* col_sim, int32_t* col_idx, void* stream);
 
+/* Windowed correlation of two descriptor maps that live on ONE gh x gw grid (csrc/local_corr.hip): for each of `pairs`
+ * problems, every patch of X_p against the patches of Y_p at most `radius` grid steps away in y and in x -- the search for
+ * adjacent slices or a follow-up scan, where a structure moves by a few patches.  t = gh * gw, row i = qy * gw + qx.
+ *   X_p = [t, d] bf16 (the queries), rows ldx elements apart, starting at x + p * x_stride; Y_p = [t, d] bf16 (the
+ *   candidates) with ldy and y_stride likewise.  A stride of 0 is allowed.  The operand rules are vdr_op_nn_cosine's.
+ * Definition, with W = 2 * radius + 1; slot w = (dy + radius) * W + (dx + radius) holds the displacement (dy, dx), dy and dx
+ * in [-radius, radius]; the candidate of slot w for query i = (qy, qx) is j = (qy + dy) * gw + (qx + dx):
+ *   ss, rn, dot = vdr_op_nn_cosine's: ss(v) = sum_c v_c^2 in fp32, rn(v) = 1.0f / fmaxf(sqrtf(ss(v)), 1e-8f) with correctly
+ *               rounded sqrtf and division, dot accumulated in fp32 by bf16 MFMAs in ascending k;
+ *   sim(i, j)   = (dot(x_i, y_j) * rn(x_i)) * rn(y_j), in this association: the bits are vdr_op_nn_cosine's sim(i, j);
+ *                 with transposed != 0 it is (dot(x_i, y_j) * rn(y_j)) * rn(x_i) instead, the candidate's norm first: the
+ *                 bits of vdr_op_nn_cosine's sim(j, i) for the operands exchanged -- the two multiplications do not
+ *                 commute in fp32, and the reverse direction of a match (queries Y, candidates X) must not depend on
+ *                 which of the two searches, the global or the windowed, produced it;
+ *   cost[p, i, w]  = sim(i, j) when (qy + dy, qx + dx) is inside the grid, -inf otherwise      ([pairs, t, W * W] fp32);
+ *   best_sim[p, i] = the maximum of cost[p, i, :] over the in-grid slots                        ([pairs, t] fp32);
+ *   best_idx[p, i] = the lowest j that attains it (slots ascend with j: also the lowest slot)   ([pairs, t] int32).
+ * Comparisons are > on the value, then < on the index.  Inputs are finite by contract.  No atomics; every entry of cost
+ * has exactly one writer; a problem's bits depend on (gh, gw, radius, d, inputs) only -- not on `pairs`, on its position in
+ * the batch or on a launch heuristic.  A window that covers the grid (radius >= max(gh, gw) - 1) gives best_sim / best_idx
+ * equal to vdr_op_nn_cosine's row_sim / row_idx bit for bit, and with transposed != 0 equal to the col_sim / col_idx of
+ * vdr_op_nn_cosine(y, x).
+ * cost == NULL: only the best pair is wanted.  best_sim == NULL && best_idx == NULL: only the cost volume.  At least one
+ * output must be given.  work: vdr_local_correlation_work_bytes(pairs, gh, gw, radius) bytes of device scratch (the row
+ * norms, and room for the cost rows the best pair is folded from when cost == NULL), 16-byte aligned; it is written before
+ * it is read.
+ * Refused before the device is touched, in this order: VDR_ERR_INVALID for a null x, y or work, non-positive pairs, gh,
+ * gw or d; VDR_ERR_UNSUPPORTED for d % 32 != 0; VDR_ERR_INVALID for ldx < d or ldy < d, negative strides, pointers or
+ * strides that are not 16-byte aligned, pairs * t above 2^31 - 1, gh * gw above 2^31 - 1; VDR_ERR_UNSUPPORTED for a radius
+ * outside 1 .. VDR_LOCAL_CORR_MAX_RADIUS; VDR_ERR_INVALID for no output at all, exactly one of best_sim / best_idx null,
+ * outputs that are not 16-byte aligned, pairs * t * W * W above 2^31 - 1. */
+#define VDR_LOCAL_CORR_MAX_RADIUS 8
+size_t vdr_local_correlation_work_bytes(int pairs, int gh, int gw, int radius);
+int vdr_op_local_correlation(const void* x, int64_t ldx, int64_t x_stride, const void* y, int64_t ldy, int64_t y_stride,
+                             int pairs, int gh, int gw, int d, int radius, int transposed, void* work,
+                             float* cost, float* best_sim, int32_t* best_idx, void* stream);
+
 /* Thresholded affinity graph of a descriptor map, one bit per pair (csrc/affinity.hip): for each of `pairs` problems the
  * graph B[i, j] = cos(x_i, x_j) > tau over the rows of X_p, without the t x t matrix of scores ever being written.
  *   X_p = [t, d] bf16, rows ldx elements apart, starting at x + p * x_stride (0 allowed).

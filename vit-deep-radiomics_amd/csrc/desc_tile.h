@@ -336,6 +336,11 @@ struct RowBest {
   float v;
   int i;
 };
+// the comparison of the cosine matches (nn_cosine.hip, local_corr.hip): greater value, then lower index
+struct NnBetter {
+  __device__ __forceinline__ bool operator()(float v, int i, float bv, int bi) const { return v > bv || (v == bv && i < bi); }
+};
+constexpr NnBetter nn_better;
 template <class Better>
 VDR_DEV RowBest row_best_reduce(const float (&rbv)[2][16], const int (&rbi)[2][16], float* s_rowv, int* s_rowi, int tid, Better better) {
   const int wave = tid >> 6, wr = wave >> 1, wc = wave & 1, l31 = tid & 31, hh = (tid >> 5) & 1;

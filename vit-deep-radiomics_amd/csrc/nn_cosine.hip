@@ -55,11 +55,6 @@ struct NnArgs {
   int32_t* rowi;
 };
 
-struct NnBetter {  // greater value, then lower index
-  __device__ __forceinline__ bool operator()(float v, int i, float bv, int bi) const { return v > bv || (v == bv && i < bi); }
-};
-constexpr NnBetter nn_better;
-
 __global__ __launch_bounds__(256) void nn_rnorm_kernel(NnArgs a, int pairs) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);

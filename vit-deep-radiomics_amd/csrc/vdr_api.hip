@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/vdr.h"
+#include "local_corr_map.h"
 #include "vdr_kernels.h"
 
 using namespace vdr;
@@ -2253,6 +2254,7 @@ static const DescNames PCA_NAMES = {"problems, imgs, t and d", "ld", "image_stri
 static const DescNames GRAM_NAMES = {"problems, t and d", "ld", "image_stride", "problems * t"};
 static const DescNames KMEANS_NAMES = {"problems, imgs, t and d", "ld", "the strides", "problems * R"};
 static const DescNames NN_NAMES = {"pairs, tx, ty and d", "ldx and ldy", "the pair strides", "pairs * max(tx, ty)"};
+static const DescNames LOCAL_NAMES = {"pairs, gh, gw and d", "ldx and ldy", "the pair strides", "pairs * gh * gw"};
 static const DescNames AFFINITY_NAMES = {"pairs, t and d", "ldx", "x_stride", "pairs * t"};
 
 // THE operand check of the descriptor ops, in one fixed order: dtype, null pointers, positive sizes, d % 32 (and d <= max_d
@@ -2772,6 +2774,33 @@ int vdr_op_nn_cosine(const void* x, int64_t ldx, int64_t x_stride, int tx, const
   RUN_OP(launch_nn_cosine(x, ldx, x_stride, tx, y, ldy, y_stride, ty, pairs, d, work, row_sim, row_idx, col_sim, col_idx,
                           (hipStream_t)stream),
          "nn_cosine");
+}
+
+size_t vdr_local_correlation_work_bytes(int pairs, int gh, int gw, int radius) {
+  return local_correlation_work_bytes(pairs, gh, gw, radius);
+}
+
+int vdr_op_local_correlation(const void* x, int64_t ldx, int64_t x_stride, const void* y, int64_t ldy, int64_t y_stride, int pairs,
+                             int gh, int gw, int d, int radius, int transposed, void* work, float* cost, float* best_sim,
+                             int32_t* best_idx, void* stream) {
+  static_assert(VDR_LOCAL_CORR_MAX_RADIUS == LC_MAX_RADIUS, "include/vdr.h and local_corr_map.h");
+  const char* op = "local_correlation";
+  // t as check_desc_operand takes it: 0 for a grid that is not positive (its refusal), capped where gh * gw overflows (ours, below)
+  const int64_t t64 = gh > 0 && gw > 0 ? (int64_t)gh * gw : 0;
+  const int t = (int)(t64 > INT32_MAX ? INT32_MAX : t64);
+  if (int rc = check_desc_operand(op, {x, VDR_BF16, ldx, 0, x_stride, pairs, 1, t, d}, LOCAL_NAMES, 0, {work})) return rc;
+  if (int rc = check_desc_operand(op, {y, VDR_BF16, ldy, 0, y_stride, pairs, 1, t, d}, LOCAL_NAMES, 0, {})) return rc;
+  if (t64 > INT32_MAX) return refuse(op, VDR_ERR_INVALID, "gh * gw exceeds 2^31 - 1");
+  if (radius < 1 || radius > VDR_LOCAL_CORR_MAX_RADIUS)
+    return refuse(op, VDR_ERR_UNSUPPORTED, "radius must be 1 .. " + std::to_string(VDR_LOCAL_CORR_MAX_RADIUS));
+  if (!cost && !best_sim && !best_idx) return refuse(op, VDR_ERR_INVALID, "no output: give cost, or best_sim and best_idx, or all three");
+  if (!best_sim != !best_idx) return refuse(op, VDR_ERR_INVALID, "best_sim and best_idx must both be given or both be null");
+  if (!aligned16({cost, best_sim, best_idx})) return refuse(op, VDR_ERR_INVALID, "cost, best_sim and best_idx must be 16-byte aligned");
+  const int64_t WW = (int64_t)(2 * radius + 1) * (2 * radius + 1);
+  if ((int64_t)pairs * t > INT32_MAX / WW) return refuse(op, VDR_ERR_INVALID, "pairs * gh * gw * (2 radius + 1)^2 exceeds 2^31 - 1");
+  RUN_OP(launch_local_correlation(x, ldx, x_stride, y, ldy, y_stride, pairs, gh, gw, d, radius, transposed, work, cost, best_sim,
+                                  best_idx, (hipStream_t)stream),
+         "local_correlation");
 }
 
 size_t vdr_affinity_work_bytes(int pairs, int t) { return affinity_work_bytes(pairs, t); }

@@ -316,6 +316,15 @@ hipError_t launch_nn_cosine(const void* x, int64_t ldx, int64_t x_stride, int tx
                             int ty, int pairs, int d, void* work, float* row_sim, int32_t* row_idx, float* col_sim,
                             int32_t* col_idx, hipStream_t st);
 
+// Windowed correlation of two descriptor maps on one gh x gw grid (local_corr.hip; the definition is
+// vdr_op_local_correlation's in include/vdr.h): operands as launch_nn_cosine's with tx = ty = gh * gw; radius 1 .. 8.
+// cost [pairs][t][(2r+1)^2] fp32 and / or (best_sim, best_idx) [pairs][t]; work: local_correlation_work_bytes(...) bytes.
+// Two launches (row norms, the tile kernel), a third (the fold over the window) when the best pair is asked for.
+size_t local_correlation_work_bytes(int pairs, int gh, int gw, int radius);
+hipError_t launch_local_correlation(const void* x, int64_t ldx, int64_t x_stride, const void* y, int64_t ldy, int64_t y_stride,
+                                    int pairs, int gh, int gw, int d, int radius, int transposed, void* work, float* cost,
+                                    float* best_sim, int32_t* best_idx, hipStream_t st);
+
 // Thresholded affinity graphs of descriptor maps, one bit per pair (affinity.hip; the definitions are vdr_op_affinity_bits' and
 // vdr_op_bits_matvec's in include/vdr.h): X_p [t, d] bf16, rows ldx elements apart, problems x_stride apart (0 allowed);
 // d % 32 == 0; pointers and strides 16-byte aligned; work: affinity_work_bytes(pairs, t) bytes; bits [pairs][t][pitch] with

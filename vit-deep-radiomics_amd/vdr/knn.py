@@ -2,7 +2,9 @@
 DINOv2's evaluation beside the linear probe) and of DINO's label propagation between slices.
 
 Plain torch: no kernel is involved, CPU and device tensors both work.  The neighbours themselves -- (value, index) lists,
-best first -- come from the caller; this library has a top-1 kernel (vdr.ops.nn_cosine) and no top-k kernel yet.  The
+best first -- come from the caller: vdr.local.topk makes them from the cost volume of a windowed correlation
+(vdr.ops.local_correlation; label propagation between slices is VitDescriptorModel.propagate_labels); for a search over ALL
+candidates this library has a top-1 kernel (vdr.ops.nn_cosine) and no top-k kernel yet.  The
 definition of the scores such a kernel has to return, its float64 restatement and scikit-learn's answers on planted
 clusters are in tests/knn_ref.py and tests/golden/README_knn.md."""
 from __future__ import annotations

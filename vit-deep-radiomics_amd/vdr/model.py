@@ -145,7 +145,11 @@ class Correspondences:
     mean over the heads, min-max normalised per image.  mask [B, t] bool: best buddies (nn21[nn12[i]] == i) whose two
     patches are both salient (> thresh).  grid = (gh, gw); stride and patch place a grid index in the image.
     desc1 / desc2 [B, t, d] bf16: the descriptors that were matched, kept with find_correspondences(keep_descriptors=True)
-    (None otherwise); points(select="kmeans") needs them."""
+    (None otherwise); points(select="kmeans") needs them.
+    radius: None for the global match; r for find_correspondences(radius=r), where both directions were searched inside the
+    (2r + 1) x (2r + 1) window around every patch's own grid position (vdr.ops.local_correlation).  cost12 [B, t, (2r + 1)^2]
+    fp32: the cost volume of the 1 -> 2 direction, kept with keep_cost=True (None otherwise); vdr.local.topk and
+    vdr.local.soft_displacement take it."""
     nn12: torch.Tensor
     sim12: torch.Tensor
     nn21: torch.Tensor
@@ -158,6 +162,21 @@ class Correspondences:
     patch: int
     desc1: torch.Tensor = None
     desc2: torch.Tensor = None
+    # (set by find_correspondences; plain attributes, not dataclass fields: the constructor and the field list stay what they were)
+    radius = None
+    cost12 = None
+
+    def displacement(self) -> torch.Tensor:
+        """[B, gh, gw, 2] int32: how far every patch of image 1 moved to its match nn12 in image 2, (dy, dx) in patches"""
+        gh, gw = self.grid
+        i = torch.arange(gh * gw, device=self.nn12.device).unsqueeze(0)
+        j = self.nn12.long()
+        dy = torch.div(j, gw, rounding_mode="floor") - torch.div(i, gw, rounding_mode="floor")
+        return torch.stack((dy, j % gw - i % gw), dim=-1).to(torch.int32).reshape(-1, gh, gw, 2)
+
+    def pixel_displacement(self) -> torch.Tensor:
+        """displacement() in pixels: times the patch stride"""
+        return self.displacement() * int(self.stride)
 
     def buddy_descriptors(self, b: int):
         """(positions [n_bb] of the masked buddies of pair b in image 1, ascending; their [n_bb, 2d] bf16 descriptors: the
@@ -218,6 +237,20 @@ def select_by_cluster(labels: torch.Tensor, rank: torch.Tensor, k: int) -> torch
     chosen = first[first < n]
     chosen = chosen.sort().values
     return chosen[torch.sort(rank[chosen], descending=True, stable=True).indices]
+
+
+@dataclass
+class Propagation:
+    """Result of VitDescriptorModel.propagate_labels for B (source, target) slice pairs on a gh x gw grid.  scores
+    [B, gh, gw, n_classes] fp32: every target patch's class scores, the softmax-weighted vote of its k best source patches
+    inside the window (they sum to 1); labels [B, gh, gw] int64: the class of the largest score, the lowest on a tie;
+    idx [B, t, k] int32 / val [B, t, k] fp32: those source patches and their similarities, best first."""
+    scores: torch.Tensor
+    labels: torch.Tensor
+    idx: torch.Tensor
+    val: torch.Tensor
+    grid: "tuple[int, int]"
+    radius: int
 
 
 @dataclass
@@ -514,7 +547,8 @@ class VitDescriptorModel:
                                    box=box, out_dtype=out_dtype)
 
     def find_correspondences(self, x1: torch.Tensor, x2: torch.Tensor, layer=None, facet: str = "key", bin: bool = True,
-                             hierarchy: int = 2, thresh: float = 0.05, keep_descriptors: bool = False) -> Correspondences:
+                             hierarchy: int = 2, thresh: float = 0.05, keep_descriptors: bool = False, radius=None,
+                             keep_cost: bool = False) -> Correspondences:
         """dino-vit-features' point correspondences: mutual cosine nearest neighbours ("best buddies") between the
         descriptors of x1[b] and x2[b], x1 and x2 [B, 3, H, W] of one shape, kept where both patches are salient.
         One forward over cat([x1, x2]) (vdr_forward_facets) writes the bf16 `facet` descriptors of block `layer` (None: the
@@ -524,25 +558,91 @@ class VitDescriptorModel:
         upstream: the saliency averages all heads (upstream: four chosen heads of dino_vits8), and Correspondences.points
         ranks by similarity unless asked for upstream's selection (select="kmeans": k-means over the buddies' descriptors,
         ranked by saliency; it needs keep_descriptors=True, which keeps views of the descriptor buffer in the result).
+        radius=r (1..8): both directions are searched inside the (2r + 1) x (2r + 1) window around a patch's own grid position
+        instead -- two vdr.ops.local_correlation calls on the same two halves; for adjacent slices and follow-up scans, where
+        nothing moves far and a look-alike on the other side of the image is no match.  keep_cost=True (with a radius) keeps
+        the 1 -> 2 cost volume in the result.  radius=None is the global match.
         Refusals (ValueError,
         before any device work): extract_descriptors' (unknown facet, hierarchy outside 1..3, a layer out of range, SAM /
-        token / post-LN / block-less models), a model without a CLS token, x1 and x2 of different shapes."""
+        token / post-LN / block-less models), a model without a CLS token, x1 and x2 of different shapes, a radius outside
+        1..8, keep_cost without a radius."""
+        from . import ops
         h = self._descriptor_args(layer, facet, bin, False, hierarchy)
         self._saliency_ok("find_correspondences")
         if x1.dim() != 4 or tuple(x1.shape) != tuple(x2.shape):
             raise ValueError(f"find_correspondences: x1 and x2 must be [B, 3, H, W] of the same shape, got {tuple(x1.shape)} "
                              f"and {tuple(x2.shape)}")
-        from . import ops
+        if radius is not None:
+            radius = ops.check_local_radius("find_correspondences", radius)
+        elif keep_cost:
+            raise ValueError("find_correspondences: keep_cost needs a radius (the global match writes no cost volume)")
         B = x1.shape[0]
         desc, sal = self._descriptors(torch.cat([x1.to(self.device), x2.to(self.device)]), layer, facet, h, saliency=True)
-        sim12, nn12, sim21, nn21 = ops.nn_cosine(desc[:B], desc[B:])
+        cost12 = None
+        if radius is None:
+            sim12, nn12, sim21, nn21 = ops.nn_cosine(desc[:B], desc[B:])
+        else:
+            grid = tuple(self.engine.grid)
+            cost12, sim12, nn12 = ops.local_correlation(desc[:B], desc[B:], grid, radius, cost=bool(keep_cost))
+            _, sim21, nn21 = ops.local_correlation(desc[B:], desc[:B], grid, radius, cost=False, transposed=True)
         sal1, sal2 = sal[:B], sal[B:]
         mask = ops.best_buddies(nn12, nn21) & (sal1 > thresh) & (torch.gather(sal2, 1, nn12.long()) > thresh)
         res = Correspondences(nn12, sim12, nn21, sim21, sal1, sal2, mask, tuple(self.engine.grid), int(self.engine.patch_stride),
                               int(self.cfg.patch))
         if keep_descriptors:
             res.desc1, res.desc2 = desc[:B], desc[B:]
+        res.radius, res.cost12 = radius, cost12
         return res
+
+    def propagate_labels(self, x_src: torch.Tensor, labels_src: torch.Tensor, x_dst: torch.Tensor, n_classes: int, radius: int = 4,
+                         k: int = 5, temperature: float = 0.1, layer=None, facet: str = "key", bin: bool = False,
+                         hierarchy: int = 2) -> Propagation:
+        """DINO's label propagation for one source slice per target slice: every patch of x_dst[b] takes the softmax-weighted
+        vote (exp(sim / temperature), normalised) of its k most similar patches of x_src[b] among those at most `radius` grid
+        steps from its own position; labels_src [B, gh, gw] integer holds their classes in 0..n_classes-1.  x_src and x_dst are
+        [B, 3, H, W] of one shape.  One forward over cat([x_dst, x_src]) writes the bf16 `facet` descriptors (extract_descriptors'
+        arguments); one vdr.ops.local_correlation call with the target patches as queries and the source patches as
+        candidates writes the [B, t, (2 radius + 1)^2] cost volume -- never a t x t matrix --; vdr.local.topk and
+        vdr.knn.vote(weights="softmax") do the rest.  A volume is swept by looping over this, the result's labels becoming
+        the next call's labels_src.  No saliency is involved, so the model needs no CLS token.  Several source slices per
+        target and soft (probability) labels are not supported.  The input size, patch stride and dynamic_size in force
+        apply.  Refusals (ValueError, before any device work): extract_descriptors' own, shapes of x_src / x_dst / labels_src
+        that do not agree with each other or with the grid in force, a radius outside 1..8, k above vdr.local.max_k(grid,
+        radius), labels outside 0..n_classes-1, a temperature that is not positive."""
+        from . import knn, local, ops
+        h = self._descriptor_args(layer, facet, bin, False, hierarchy)
+        check_batch("propagate_labels", x_src)
+        if not isinstance(x_dst, torch.Tensor) or tuple(x_src.shape) != tuple(x_dst.shape):
+            raise ValueError(f"propagate_labels: x_src and x_dst must be [B, 3, H, W] of the same shape, got {tuple(x_src.shape)} "
+                             f"and {tuple(getattr(x_dst, 'shape', ()))}")
+        radius = ops.check_local_radius("propagate_labels", radius)
+        if int(n_classes) < 1:
+            raise ValueError(f"propagate_labels: n_classes must be positive, got {n_classes}")
+        if not float(temperature) > 0:
+            raise ValueError(f"propagate_labels: temperature must be positive, got {temperature}")
+        B, (gh, gw) = x_src.shape[0], self.engine.grid
+        if getattr(self, "dynamic_size", False):  # (the grid the forward will adopt, without adopting it here)
+            p, s = int(self.cfg.patch), int(self.engine.patch_stride)
+            gh, gw = (int(x_src.shape[-2]) - p) // s + 1, (int(x_src.shape[-1]) - p) // s + 1
+        elif tuple(x_src.shape[-2:]) != tuple(self.engine.input_size):
+            raise ValueError(f"propagate_labels: the images are {tuple(x_src.shape[-2:])}, the input size in force "
+                             f"{tuple(self.engine.input_size)}")
+        if not isinstance(labels_src, torch.Tensor) or labels_src.dtype.is_floating_point or labels_src.dtype == torch.bool or \
+                tuple(labels_src.shape) != (B, gh, gw):
+            raise ValueError(f"propagate_labels: labels_src must be an integer tensor of shape {(B, gh, gw)} (the grid in force), got "
+                             f"{getattr(labels_src, 'dtype', type(labels_src).__name__)} {tuple(getattr(labels_src, 'shape', ()))}")
+        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= local.max_k((gh, gw), radius):
+            raise ValueError(f"propagate_labels: k must be 1..{local.max_k((gh, gw), radius)} (the in-grid candidates of a corner patch "
+                             f"of a {gh} x {gw} grid at radius {radius}), got {k!r}")
+        if labels_src.numel() and (int(labels_src.min()) < 0 or int(labels_src.max()) >= int(n_classes)):
+            raise ValueError(f"propagate_labels: labels_src must lie in 0..{int(n_classes) - 1}")
+        desc = self._descriptors(torch.cat([x_dst.to(self.device), x_src.to(self.device)]), layer, facet, h)
+        cost, _, _ = ops.local_correlation(desc[:B], desc[B:], (gh, gw), radius, best=False)
+        idx, val = local.topk(cost, (gh, gw), int(k))
+        scores = knn.vote(idx, val, labels_src.to(self.device).reshape(B, gh * gw), int(n_classes), weights="softmax",
+                          temperature=float(temperature))
+        return Propagation(scores.reshape(B, gh, gw, int(n_classes)), knn.lowest_argmax(scores).reshape(B, gh, gw), idx, val,
+                           (int(gh), int(gw)), radius)
 
     def cosegment(self, x: torch.Tensor, k=None, layer=None, facet: str = "key", bin: bool = False, hierarchy: int = 2,
                   thresh: float = 0.065, votes_percentage: float = 75, elbow: float = 0.975, **fit_kwargs) -> Cosegmentation:

@@ -382,6 +382,55 @@ def nn_cosine(x: torch.Tensor, y: torch.Tensor, mutual: bool = True):
     return row_sim, row_idx, col_sim, col_idx
 
 
+LOCAL_CORR_MAX_RADIUS = 8  # VDR_LOCAL_CORR_MAX_RADIUS (include/vdr.h)
+
+
+def check_local_radius(op: str, radius) -> int:
+    """The one wording of "no such window" (ValueError); returns the radius as an int."""
+    if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= LOCAL_CORR_MAX_RADIUS:
+        raise ValueError(f"{op}: radius must be an integer in 1..{LOCAL_CORR_MAX_RADIUS}, got {radius!r}")
+    return int(radius)
+
+
+def local_correlation(x: torch.Tensor, y: torch.Tensor, grid, radius: int, cost: bool = True, best: bool = True,
+                      transposed: bool = False):
+    """Windowed correlation of two descriptor maps on one grid (vdr_op_local_correlation): x [P, t, d] the queries, y
+    [P, t, d] the candidates, t = gh * gw for grid = (gh, gw); operands as nn_cosine takes them (bf16 read in place through
+    views with contiguous channels, a batch stride of 0 from expand(), fp32 rounded once to bf16; d a multiple of 32).
+    Every patch is compared with the patches at most `radius` (1..8) grid steps away in y and in x, W = 2 * radius + 1:
+    returns (cost [P, t, W * W] fp32, best_sim [P, t] fp32, best_idx [P, t] int32).  Slot (dy + radius) * W + (dx + radius)
+    of cost[p, i] is the cosine of x[p, i] and the candidate at displacement (dy, dx) -- vdr.local.offsets(radius) lists
+    them --, -inf where that falls outside the grid; best_sim is the maximum over the window and best_idx the lowest
+    candidate index that attains it.  cost=False / best=False skip that output (None in its place); one of them must be
+    asked for.  The similarities have nn_cosine's bits; transposed=True multiplies by the candidate's norm first, which gives
+    the reverse direction of a match -- local_correlation(y, x, transposed=True) beside local_correlation(x, y) -- the bits
+    of nn_cosine(x, y)'s column side.  The exact arithmetic is stated in include/vdr.h."""
+    ox = desc_operand(x, "local_correlation", "x", refuse_strided_channels=True)
+    oy = desc_operand(y, "local_correlation", "y", refuse_strided_channels=True)
+    if ox.x.device != oy.x.device:
+        raise ValueError("local_correlation: x and y must be on the same device")
+    if ox.problems != oy.problems or ox.d != oy.d or ox.t != oy.t:
+        raise ValueError(f"local_correlation: x {tuple(x.shape)} and y {tuple(y.shape)} must agree in P, t and d")
+    gh, gw = (int(v) for v in grid)
+    if gh <= 0 or gw <= 0 or gh * gw != ox.t:
+        raise ValueError(f"local_correlation: x has {ox.t} rows, the grid {gh} x {gw}")
+    r = check_local_radius("local_correlation", radius)
+    if not cost and not best:
+        raise ValueError("local_correlation: no output asked for (cost=False and best=False)")
+    P, t, d, WW = ox.problems, ox.t, ox.d, (2 * r + 1) ** 2
+    if P * t * WW > 2 ** 31 - 1:
+        raise ValueError("local_correlation: P * t * (2 radius + 1)^2 exceeds 2^31 - 1")
+    lib = L.load()
+    dev = ox.x.device
+    work = torch.empty((lib.vdr_local_correlation_work_bytes(P, gh, gw, r),), dtype=torch.uint8, device=dev)
+    c = torch.empty((P, t, WW), dtype=torch.float32, device=dev) if cost else None
+    best_sim = torch.empty((P, t), dtype=torch.float32, device=dev) if best else None
+    best_idx = torch.empty((P, t), dtype=torch.int32, device=dev) if best else None
+    L.check(lib.vdr_op_local_correlation(ox.x.data_ptr(), ox.ld, ox.stride, oy.x.data_ptr(), oy.ld, oy.stride, P, gh, gw, d, r,
+                                         int(bool(transposed)), work.data_ptr(), _p(c), _p(best_sim), _p(best_idx), _s(ox.x)))
+    return c, best_sim, best_idx
+
+
 def bits_pitch(t: int) -> int:
     """int32 words per row of a bit-packed [t, t] graph: ceil(t / 32) rounded up to a multiple of 4 (16-byte rows)"""
     return (int(t) + 127) // 128 * 4
