@@ -6,7 +6,8 @@ Designed inputs (nn_cosine_ref.designed: exactly 16 entries of +-1 per row, rn =
 ragged tiles, more than one panel and tile), d in {32, 96, 448} (one short K step, a short last step, an odd number of steps
 through the two staging buffers), P in {1, 3}, exclude_diag both ways, tau in {0.2, 0, 1/16} -- the last two a strict > on a
 score that is attained.  Random inputs: symmetry bit for bit, and agreement with the float64 graph outside the band of the
-entry-wise fp32 bound around tau, the band holding at most 1 % of the entries.  bits_matvec: integer-valued V (every order
+entry-wise fp32 bound around tau, the band holding at most 1 % of the entries; one problem alone (its column tiles split into
+runs) against the same problem among 300 (unsplit), word for word.  bits_matvec: integer-valued V (every order
 exact) bit for bit, degree exact, random V within t u (B |V|), and independence of P bitwise."""
 import numpy as np
 import pytest
@@ -148,6 +149,21 @@ def test_random_inputs_match_outside_the_band(ops, shape):
     assert 0.02 < got.mean() < 0.98  # a graph with both kinds of entries
     assert np.array_equal(got[clear], (s > tau)[clear]), int((got[clear] != (s > tau)[clear]).sum())
     assert got[:, np.arange(t), np.arange(t)].all()
+
+
+def test_few_problems_take_the_split_path_and_many_the_unsplit_one(ops):
+    """t = 130 is 2 panels x 2 column tiles.  One problem alone is 2 work items, so each panel's tiles are cut into 2 runs; 300
+    problems are 600 items, above what the split aims for, so every panel walks both tiles in one run.  The split only decides
+    which workgroup computes a word: the bits of the problem alone equal its bits as each of the 300, word for word."""
+    t, d = 130, 96
+    x, _, _ = _random(t, d)
+    one = x[:1].cuda()
+    alone = ops.affinity_bits(one, tau=0.2)
+    share = float(ops.unpack_bits(alone, t).float().mean())
+    assert 0.02 < share < 0.98, share  # a graph with both kinds of entries
+    many = ops.affinity_bits(one.repeat(300, 1, 1), tau=0.2)
+    assert many.shape == (300, t, sref.pitch(t))
+    assert torch.equal(many, alone.expand_as(many)), torch.nonzero(many != alone)[:4].tolist()
 
 
 MV_CASES = tuple((t, 32) for t in TS) + ((2100, 32), (300, 448))

@@ -6,9 +6,10 @@ dlopen'ed side by side and the attention ops / vdr_op_linear_packed are called t
 attention: first a bitwise pass (torch.equal of the two libraries' outputs) over the smallest shapes that reach every
 instantiation of the fused attention kernels, then the timing; exit status 1 if any output differs.  For the spread of
 the timing run a copy of library A against it (a second path: the same path is the same handle).
-descriptors: the same two passes for the descriptor-analysis ops (nn_cosine, the PCA ops, the Gram side, k-means): bitwise on the
-smallest shapes that reach every path (the shapes of the exact tests), every element of every output compared; timed on the shapes of
-tools/correspondence_bench.py, pca_bench.py, pca_topk_bench.py and kmeans_bench.py."""
+descriptors: the same two passes for the descriptor-analysis ops (nn_cosine, affinity_bits, local_correlation, the PCA ops, the
+Gram side, k-means, mahalanobis): bitwise on the smallest shapes that reach every path (the shapes of the exact tests), every element of
+every output compared; timed on the shapes of tools/correspondence_bench.py, spectral_bench.py (the affinity shapes),
+local_correlation_bench.py, pca_bench.py, pca_topk_bench.py and kmeans_bench.py."""
 import ctypes as C
 import os
 import sys
@@ -215,10 +216,68 @@ def kmeans_case(st, P, imgs, t, d, k, ops=("assign", "update")):
     return f"kmeans {'+'.join(ops)} P{P} imgs{imgs} t{t} d{d} k{k}", run
 
 
+def affinity_case(st, P, t, d, diag, pad=0, tau=0.05):
+    """random rows: the cosines spread around 0 by 1 / sqrt(d), so tau = 0.05 sets a good share of the bits at every d; the
+    padding columns of the rows are NaN"""
+    ld = d + pad
+    x = torch.full((P, t, ld), float("nan"), device="cuda")
+    x[..., :d] = torch.randn(P, t, d, device="cuda", generator=torch.Generator(device="cuda").manual_seed(t + d))
+    x = x.bfloat16()
+    pitch = (t + 127) // 128 * 4
+
+    def run(lib, keep=None):
+        o = _Bufs(keep)
+        work = o.work(lib.vdr_affinity_work_bytes(P, t))
+        bits = o.out(P, t, pitch, dtype=torch.int32)
+        assert lib.vdr_op_affinity_bits(x.data_ptr(), ld, t * ld, t, P, d, tau, diag, work.data_ptr(), bits.data_ptr(), pitch, st) == 0
+        return [bits.view(torch.uint8)]
+    return f"affinity P{P} t{t} d{d} diag{diag} pad{pad}", run
+
+
+def local_case(st, P, grid, r, d, outs="cost+best", transposed=0, y_shared=False):
+    """cost only, best only or both; y_shared: one Y map under every problem (problem stride 0)"""
+    gh, gw = grid
+    t, WW = gh * gw, (2 * r + 1) ** 2
+    gen = torch.Generator(device="cuda").manual_seed(t + d + r)
+    x = torch.randn(P, t, d, device="cuda", generator=gen).bfloat16()
+    y = torch.randn(1 if y_shared else P, t, d, device="cuda", generator=gen).bfloat16()
+
+    def run(lib, keep=None):
+        o = _Bufs(keep)
+        work = o.work(lib.vdr_local_correlation_work_bytes(P, gh, gw, r))
+        cost = o.out(P, t, WW) if "cost" in outs else None
+        bs, bi = (o.out(P, t), o.out(P, t, dtype=torch.int32)) if "best" in outs else (None, None)
+        assert lib.vdr_op_local_correlation(x.data_ptr(), d, t * d, y.data_ptr(), d, 0 if y_shared else t * d, P, gh, gw, d, r, transposed,
+                                            work.data_ptr(), cost.data_ptr() if cost is not None else None,
+                                            bs.data_ptr() if bs is not None else None, bi.data_ptr() if bi is not None else None, st) == 0
+        return [v for v in (cost, bs, bi) if v is not None]
+    return f"local_corr P{P} {gh}x{gw} r{r} d{d} {outs}{' transposed' if transposed else ''}{' y_shared' if y_shared else ''}", run
+
+
+def mahalanobis_case(st, P, t, d, k):
+    gen = torch.Generator(device="cuda").manual_seed(t + d + k)
+    x = torch.randn(P, t, d, device="cuda", generator=gen).bfloat16()
+    mean = torch.randn(P, d, device="cuda", generator=gen)
+    whiten = torch.randn(P, k, d, device="cuda", generator=gen) / d ** 0.5
+
+    def run(lib, keep=None):
+        d2 = _Bufs(keep).out(P, t)
+        assert lib.vdr_op_mahalanobis(x.data_ptr(), d, t * d, t * d, P, 1, t, d, mean.data_ptr(), d, whiten.data_ptr(), k * d, k, d2.data_ptr(), st) == 0
+        return [d2]
+    return f"mahalanobis P{P} t{t} d{d} k{k}", run
+
+
 def descriptors_equal(libs, st):
-    """the shapes of the exact tests (tests/test_nn_cosine_gpu.py, test_pca_gpu.py, test_pca_topk_gpu.py, test_kmeans_gpu.py)"""
+    """the shapes of the exact tests (tests/test_nn_cosine_gpu.py, test_affinity_gpu.py, test_local_correlation_gpu.py, test_pca_gpu.py,
+    test_pca_topk_gpu.py, test_kmeans_gpu.py)"""
     cases = [nn_case(st, 2, tx, ty, d, cols, pad=8) for (tx, ty) in ((1, 1), (127, 129), (130, 257)) for d in (32, 96, 448) for cols in (True, False)]
     cases += [nn_case(st, 520, 17, 19, 32)]  # more work items than the split aims for: one split
+    cases += [affinity_case(st, 2, t, d, diag) for t in (1, 33, 129, 300) for d in (32, 96, 448) for diag in (0, 1)]
+    cases += [affinity_case(st, 2, 129, 96, 1, pad=32), affinity_case(st, 300, 130, 96, 1)]  # padded rows; 600 items: one run
+    cases += [local_case(st, 2, grid, r, d, outs) for grid in ((1, 1), (5, 7), (9, 17), (17, 33)) for r in (1, 8) for d in (32, 96)
+              for outs in ("cost", "best", "cost+best")]
+    cases += [local_case(st, 2, (9, 17), 3, 96, transposed=1), local_case(st, 3, (9, 17), 3, 96, y_shared=True)]
+    cases += [mahalanobis_case(st, 2, t, 96, k) for t in (129, 300) for k in (1, 130)]
     cases += [pca_case(st, 2, imgs, t, d, bf16, pad=32) for t in (2, 16, 17, 1025, 2049) for d in (32, 160, 288) for bf16 in (True, False)
               for imgs in (1, 2)]
     cases += [gram_case(st, 2, t, d, bf16, pad=32) for t in (17, 129, 300) for d in (96, GRAM_CHUNK + 32) for bf16 in (True, False)]
@@ -229,7 +288,8 @@ def descriptors_equal(libs, st):
         torch.cuda.synchronize()
         notes = []  # per output that fails: its index, elements left undefined by A / B, elements whose bits differ
         for i, (a, b) in enumerate(zip(*outs)):
-            undef = [int((torch.isnan(t) if t.dtype.is_floating_point else t == _INT_FILL).sum()) for t in (a, b)]
+            # (uint8: the affinity words as bytes -- in a bit field every pattern is a value, the fill included)
+            undef = [0 if t.dtype == torch.uint8 else int((torch.isnan(t) if t.dtype.is_floating_point else t == _INT_FILL).sum()) for t in (a, b)]
             diff = int((a.view(torch.int32) != b.view(torch.int32)).sum())
             if undef[0] or undef[1] or diff:
                 notes.append(f"out{i} undefined {undef[0]}/{undef[1]} differ {diff} of {a.numel()}")
@@ -242,6 +302,11 @@ def descriptors_equal(libs, st):
 
 def descriptors_timed(st):
     timed = [nn_case(st, P, t, t, d) for (P, t, d) in ((64, 196, 768), (64, 196, 13056), (32, 729, 13056), (1, 3969, 13056), (8, 3969, 13056))]
+    timed += [affinity_case(st, P, t, d, 1, tau=0.2) for (P, t, d) in ((64, 196, 768), (32, 729, 768), (1, 3969, 768), (1, 3969, 13056), (8, 3969, 768))]
+    timed += [local_case(st, P, grid, r, d) for (P, grid, d, r) in ((64, (14, 14), 768, 2), (32, (27, 27), 768, 4), (1, (63, 63), 768, 4),
+                                                                    (8, (63, 63), 768, 4), (1, (63, 63), 768, 8), (8, (63, 63), 768, 8),
+                                                                    (1, (63, 63), 13056, 4))]
+    timed += [mahalanobis_case(st, 8, 3969, 768, 100)]
     for (P, t, d, bf16) in ((64, 196, 768, True), (16, 729, 768, True), (16, 4096, 256, False), (1, 3969, 768, True)):
         for joint in ((False, True) if P > 1 else (False,)):
             timed += [pca_case(st, 1 if joint else P, P if joint else 1, t, d, bf16, (op,)) for op in ("mean", "cov", "proj")]

@@ -1,6 +1,6 @@
 // Thresholded patch-affinity graphs of dense descriptor maps for gfx950 (include/vdr.h, vdr_op_affinity_bits and
 // vdr_op_bits_matvec): for `pairs` problems X_p [t, d] (bf16 rows ldx elements apart, problems x_stride apart, 0 allowed)
-//   sim(i, j) = dot(x_i, x_j) * (rn(x_i) * rn(x_j)),   rn(v) = 1 / max(sqrt(sum v^2), 1e-8)   (nn_cosine's rn)
+//   sim(i, j) = dot(x_i, x_j) * (rn(x_i) * rn(x_j)),   rn(v) = 1 / max(sqrt(sum v^2), 1e-8)   (cosine_rn of desc_tile.h)
 //   B[i, j]   = sim(i, j) > tau, the diagonal cleared with exclude_diag
 // written one BIT per pair: bit (j & 31) of word bits[p][i][j >> 5], rows `pitch` = 4 ceil(t / 128) words apart.  The two norms
 // are multiplied FIRST: fp32 multiplication commutes, dot(i, j) and dot(j, i) are the same products summed in the same k order,
@@ -8,10 +8,13 @@
 // time in MFMA accumulators, and the epilogue folds the tile into 4 words per row.
 //
 // Launches, no atomics:
-//   aff_rnorm_kernel      rn of every row into `work` (row_sumsq: one wave per row; IEEE sqrt and division).
-//   affinity_bits_kernel  256 threads; one work item = (problem, run of 128-column tiles, 128-row panel), nn_cosine_kernel's
-//                         loop: per tile a K loop over d in steps of 64 stages the panel's rows (A operand) and the tile's rows
-//                         (B operand) global -> LDS by LDS-DMA, two buffers, step s + 1 in flight under the MFMAs of step s.
+//   aff_rnorm_kernel      rn of every row into `work` (row_sumsq: one wave per row; cosine_rn of desc_tile.h).
+//   affinity_bits_kernel  256 threads; one work item = (problem, run of 128-column tiles, 128-row panel; run_split of
+//                         desc_tile.h), nn_cosine_kernel's loop: per tile a K loop over d in steps of 64 stages the panel's
+//                         rows (A operand) and the tile's rows (B operand) global -> LDS by LDS-DMA, two buffers, step s + 1
+//                         in flight under the MFMAs of step s.  Like nn_cosine_kernel it keeps its own copy of dma_steps /
+//                         t128_dma_stage of desc_tile.h (1 - 3 % slower through the helpers); the source chunk a
+//                         lane copies (t128_dma_chunk) and the wait (dma_wait) are the header's.
 //                         Epilogue per tile: a lane holds ONE column and 16 rows per accumulator (desc_tile.h), so the wave
 //                         ballot of `sim > tau` for element e of acc[m][n] is 32 columns of row acc_row(wr, m, e, 0) in its low
 //                         half and the same 32 columns of row acc_row(wr, m, e, 1) in its high half: two finished words.  Word
@@ -37,10 +40,8 @@ namespace vdr {
 namespace {
 
 constexpr int AF_T = T128;
-constexpr int AF_OPER = T128_OPER;
-constexpr int AF_RN = 4 * AF_OPER;          // s_rn [2][256] float: tile parity x (rn of the tile's rows | of the panel's rows)
+constexpr int AF_RN = 4 * T128_OPER;        // s_rn [2][256] float: tile parity x (rn of the tile's rows | of the panel's rows)
 constexpr int AF_LDS = AF_RN + 2048;
-constexpr int AF_TARGET_ITEMS = 512;        // work items the split of the column tiles aims for (two workgroups per CU)
 
 struct AffArgs {
   const bf16_t* x;
@@ -52,6 +53,8 @@ struct AffArgs {
   uint32_t* bits;   // [pairs][t][pitch]
 };
 
+// rn of every row into `work`.  The kernel's own one-sided copy of cosine_rnorm_kernel (nn_cosine.hip): through the two-sided
+// kernel the op ran 0.2 - 5.8 us (0.3 - 2.6 %) slower at an A/A spread of 0.1 - 0.6 %
 __global__ __launch_bounds__(256) void aff_rnorm_kernel(AffArgs a, int pairs) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -59,13 +62,7 @@ __global__ __launch_bounds__(256) void aff_rnorm_kernel(AffArgs a, int pairs) {
   const int64_t p = row / a.t;
   const int i = (int)(row - p * a.t);
   const float ss = row_sumsq(a.x + p * a.xs + (int64_t)i * a.ldx, a.d, lane);
-  if (lane == 0) a.rn[p * a.t_pad + i] = __fdiv_rn(1.0f, fmaxf(__fsqrt_rn(ss), 1e-8f));
-}
-
-// the staged step has landed, for every wave: the DMAs are opaque to hipcc, so the wait is spelled out
-VDR_DEV void aff_wait() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
+  if (lane == 0) a.rn[p * a.t_pad + i] = cosine_rn(ss);
 }
 
 // one K step of (panel, tile jt) into staging buffer `buf`: 4 + 4 DMA instructions per wave, 8 rows x 128 B each
@@ -73,16 +70,15 @@ VDR_DEV void aff_stage(const AffArgs& a, const bf16_t* xp, int64_t p, int panel,
                        int lane) {
   const int k0 = kk * 64;
   const bool shortk = a.d - k0 < 64;
-  char* sx = smem + buf * 2 * AF_OPER;
+  char* sx = smem + buf * 2 * T128_OPER;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int piece = wave * 4 + q;
     const int r = piece * 8 + (lane >> 3);
-    int c = (lane & 7) ^ ((r >> 1) & 7);
-    c = shortk ? c & 3 : c;
+    const int c = t128_dma_chunk(lane, r, shortk);
     const int xr = min(panel * AF_T + r, a.t - 1), yr = min(jt * AF_T + r, a.t - 1);
     glds16_raw(xp + (int64_t)xr * a.ldx + k0 + c * 8, sx + piece * 1024);
-    glds16_raw(xp + (int64_t)yr * a.ldx + k0 + c * 8, sx + AF_OPER + piece * 1024);
+    glds16_raw(xp + (int64_t)yr * a.ldx + k0 + c * 8, sx + T128_OPER + piece * 1024);
   }
   if (kk == 0 && wave == 0) {  // the tile's rn values ride on the same wait: lanes 0..31 the tile's, 32..63 the panel's
     const float* src = a.rn + p * a.t_pad + (lane < 32 ? jt * AF_T + lane * 4 : panel * AF_T + (lane - 32) * 4);
@@ -99,9 +95,9 @@ __global__ __launch_bounds__(256, 2) void affinity_bits_kernel(AffArgs a) {
   const int vid = xcd_remap(blockIdx.x, gridDim.x);
   const int ps = vid / a.npanels, panel = vid - ps * a.npanels;
   const int p = ps / a.nsplit, split = ps - p * a.nsplit;
-  const int jt0 = split * a.split_base + min(split, a.split_rem), jt1 = jt0 + a.split_base + (split < a.split_rem);
+  int jt0, jt1;
+  run_tiles(split, a.split_base, a.split_rem, jt0, jt1);
   const bf16_t* xp = a.x + (int64_t)p * a.xs;
-  const int nk = (a.d + 63) >> 6;
 
   f32x16 acc[2][2];
   acc_zero(acc);
@@ -110,7 +106,8 @@ __global__ __launch_bounds__(256, 2) void affinity_bits_kernel(AffArgs a) {
   const int srow = panel * AF_T + acc_row(wr, (lane >> 4) & 1, lane & 15, hh);
   uint32_t* const dst = a.bits + ((int64_t)p * a.t + min(srow, a.t - 1)) * a.pitch + wc * 2;
 
-  // One loop over the K steps of all tiles, step s + 1 staged under the MFMAs of step s (nn_cosine_kernel's loop)
+  // dma_steps of desc_tile.h, spelled out
+  const int nk = (a.d + 63) >> 6;
   const int nsteps = (jt1 - jt0) * nk;
   int jt = jt0, kk = -1, buf = 1;
 #pragma clang loop unroll(disable)
@@ -122,7 +119,7 @@ __global__ __launch_bounds__(256, 2) void affinity_bits_kernel(AffArgs a) {
     }
     if (s + 1 < nsteps) aff_stage(a, xp, p, panel, njt, nkk, smem, buf ^ 1, wave, lane);
     if (s >= 0) {
-      const char* sx = smem + buf * 2 * AF_OPER;
+      const char* sx = smem + buf * 2 * T128_OPER;
       t128_mfma<0, 2>(sx, wr, wc, l31, hh, acc);
       if (a.d - kk * 64 >= 64) t128_mfma<2, 4>(sx, wr, wc, l31, hh, acc);
       if (kk + 1 == nk) {
@@ -167,7 +164,7 @@ __global__ __launch_bounds__(256, 2) void affinity_bits_kernel(AffArgs a) {
         }
       }
     }
-    aff_wait();
+    dma_wait();
     buf ^= 1;
     jt = njt;
     kk = nkk;
@@ -277,9 +274,9 @@ size_t affinity_work_bytes(int pairs, int t) {
 
 hipError_t launch_affinity_bits(const void* x, int64_t ldx, int64_t x_stride, int t, int pairs, int d, float tau, int exclude_diag,
                                 void* work, uint32_t* bits, int pitch, hipStream_t st) {
-  if (!x || !work || !bits || pairs <= 0 || t <= 0 || d <= 0 || (d & 31) || ldx < d || x_stride < 0 || pitch != affinity_pitch(t))
+  if (!cos_operand_ok(x, ldx, x_stride, t, d) || !work || !bits || (((uintptr_t)work | (uintptr_t)bits) & 15) || pairs <= 0 ||
+      pitch != affinity_pitch(t))
     return hipErrorInvalidValue;
-  if ((((uintptr_t)x | (uintptr_t)work | (uintptr_t)bits) & 15) || ((ldx | x_stride) & 7)) return hipErrorInvalidValue;
   if ((int64_t)pairs * t > INT32_MAX) return hipErrorInvalidValue;
   AffArgs a;
   a.x = (const bf16_t*)x;
@@ -291,22 +288,19 @@ hipError_t launch_affinity_bits(const void* x, int64_t ldx, int64_t x_stride, in
   a.exclude_diag = exclude_diag != 0;
   a.tau = tau;
   const int64_t items = (int64_t)pairs * a.npanels;
-  int64_t nsplit = AF_TARGET_ITEMS / items;
-  nsplit = nsplit < 1 ? 1 : nsplit > a.npanels ? a.npanels : nsplit;
-  a.nsplit = (int)nsplit;
-  a.split_base = (int)(a.npanels / nsplit), a.split_rem = (int)(a.npanels % nsplit);
+  const RunSplit run = run_split(items, a.npanels);
+  a.nsplit = run.nsplit, a.split_base = run.base, a.split_rem = run.rem;
   a.rn = (float*)work;
   a.bits = bits;
-  if (items * nsplit > INT32_MAX) return hipErrorInvalidValue;
+  if (items * a.nsplit > INT32_MAX) return hipErrorInvalidValue;
 
   static KernelState ks;
   const int dev = current_device_index();
   if (dev < 0) return hipErrorInvalidDevice;
   if (hipError_t e = raise_lds_limit(ks, (const void*)affinity_bits_kernel, dev, AF_LDS)) return e;
-  const int64_t rows = (int64_t)pairs * t;
-  hipLaunchKernelGGL(aff_rnorm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, a, pairs);
+  hipLaunchKernelGGL(aff_rnorm_kernel, dim3((unsigned)(((int64_t)pairs * t + 3) / 4)), dim3(256), 0, st, a, pairs);
   if (hipError_t e = hipGetLastError()) return e;
-  hipLaunchKernelGGL(affinity_bits_kernel, dim3((unsigned)(items * nsplit)), dim3(256), AF_LDS, st, a);
+  hipLaunchKernelGGL(affinity_bits_kernel, dim3((unsigned)(items * a.nsplit)), dim3(256), AF_LDS, st, a);
   return hipGetLastError();
 }
 

@@ -1,8 +1,10 @@
-// The tile core of the descriptor-analysis kernels (nn_cosine.hip, pca.hip, kmeans.hip, mahalanobis.hip, upsample.hip): one 128 x 128 fp32 tile per workgroup
+// The tile core of the descriptor-analysis kernels (nn_cosine.hip, affinity.hip, local_corr.hip, pca.hip, kmeans.hip,
+// mahalanobis.hip, upsample.hip): one 128 x 128 fp32 tile per workgroup
 // of 4 waves, wave (wr, wc) = (wave >> 1, wave & 1) owning the 64 x 64 sub-tile at (64 wr, 64 wc) as 2 x 2
 // mfma_f32_32x32x16_bf16 accumulators.  Every piece that fixes the BITS of a result -- the accumulator layout, the k order of
-// the MFMA steps, the comparator folds, the ascending sums -- is written once here; the kernels keep what is theirs (centring,
-// hi/lo split, one-hot build, epilogues, masks, work layouts) and their own loops.
+// the MFMA steps, the comparator folds, the ascending sums, the cosine row norm -- is written once here, and so are the two
+// pipelines that feed the tile (staged_steps through registers, dma_steps by LDS-DMA); the kernels keep what is theirs
+// (centring, hi/lo split, one-hot build, source rows, epilogues, masks, work layouts).
 //   Accumulator layout: element e of acc[m][n] of lane (hh = lane >> 5, l31 = lane & 31) is tile row acc_row(wr, m, e, hh),
 //   tile column acc_col(wc, n, l31): a lane holds ONE column of the B operand and 16 rows of the A operand.
 //   Two LDS images of a staged operand step, by the index the product contracts over:
@@ -251,6 +253,92 @@ VDR_DEV void raw_fill(RawChunk<BF16>& c, bool ok, const void* x, int64_t off) {
   else c.zero();
 }
 
+// ---- staging by LDS-DMA: the cosine kernels ---------------------------------------------------------------
+// nn_cosine.hip, affinity.hip and local_corr.hip multiply raw bf16 rows, so their operands go global -> LDS directly.  All
+// three take dma_wait and t128_dma_chunk; local_corr_kernel runs on t128_dma_stage and dma_steps, nn_cosine_kernel and
+// affinity_bits_kernel keep spelled-out copies of those two (1 - 3 % slower through them: DESIGN 4.6t) -- a change to either
+// is a change to all three, and a new kernel starts from the helpers.
+// the staged step has landed, for every wave: the DMAs are opaque to hipcc, so the wait is spelled out
+VDR_DEV void dma_wait() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+}
+
+// One K step (64 channels from kk * 64) of both operands into the staging buffer at sx, the A image first: 4 + 4 DMA
+// instructions per wave, 8 rows x 128 B each.  The DMA writes linearly, so the swizzle of the t128 image is applied to the
+// per-lane SOURCE chunk.  A lane stages tile rows t128_dma_row(wave, lane, q), q = 0..3, of each operand; xo[q] / yo[q] are
+// the element offsets of their source rows: always valid rows (the kernels clamp; what a clamped row contributes is dropped
+// in their epilogues).  d % 64 == 32: the last step's unused chunks re-read chunks 0..3, nothing past the end of a row is touched.
+VDR_DEV int t128_dma_row(int wave, int lane, int q) { return (wave * 4 + q) * 8 + (lane >> 3); }
+// the 16-byte chunk of the source row's K step that this lane copies for tile row r: the swizzle, and in a short last step
+// (d % 64 == 32) chunks 0..3 again
+VDR_DEV int t128_dma_chunk(int lane, int r, bool shortk) {
+  const int c = (lane & 7) ^ ((r >> 1) & 7);
+  return shortk ? c & 3 : c;
+}
+VDR_DEV void t128_dma_stage(const bf16_t* xp, const bf16_t* yp, const int64_t (&xo)[4], const int64_t (&yo)[4], int d, int kk, char* sx,
+                            int wave, int lane) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int col = kk * 64 + t128_dma_chunk(lane, t128_dma_row(wave, lane, q), d - kk * 64 < 64) * 8;
+    glds16_raw(xp + xo[q] + col, sx + (wave * 4 + q) * 1024);
+    glds16_raw(yp + yo[q] + col, sx + T128_OPER + (wave * 4 + q) * 1024);
+  }
+}
+
+// One loop over the nk K steps of tiles jt0 .. jt1-1 through two staging buffers of 2 T128_OPER bytes at smem: step s + 1 is
+// staged under the MFMAs of step s (pass s = -1 only stages step 0); the step after a tile's last one is the first of the next
+// tile.  (jt, kk) is the step in the MFMAs, (njt, nkk) the one being staged; it goes into the other buffer, which every wave
+// finished reading before the barrier that ended the previous pass.  stage(tile, k, buffer) issues the DMAs, epilogue(tile)
+// consumes acc after the tile's last step (and zeroes it if another tile follows).
+template <class Stage, class Epilogue>
+VDR_DEV void dma_steps(int jt0, int jt1, int d, char* smem, int wr, int wc, int l31, int hh, f32x16 (&acc)[2][2], Stage stage,
+                       Epilogue epilogue) {
+  const int nk = (d + 63) >> 6;
+  const int nsteps = (jt1 - jt0) * nk;
+  int jt = jt0, kk = -1, buf = 1;
+#pragma clang loop unroll(disable)
+  for (int s = -1; s < nsteps; ++s) {
+    int njt = jt, nkk = kk + 1;
+    if (nkk == nk) {
+      nkk = 0;
+      ++njt;
+    }
+    if (s + 1 < nsteps) stage(njt, nkk, smem + (buf ^ 1) * 2 * T128_OPER);
+    if (s >= 0) {
+      const char* sx = smem + buf * 2 * T128_OPER;
+      t128_mfma<0, 2>(sx, wr, wc, l31, hh, acc);
+      if (d - kk * 64 >= 64) t128_mfma<2, 4>(sx, wr, wc, l31, hh, acc);
+      if (kk + 1 == nk) epilogue(jt);
+    }
+    dma_wait();
+    buf ^= 1;
+    jt = njt;
+    kk = nkk;
+  }
+}
+
+// the launch-side check of one operand: t rows of d channels, d a multiple of 32 within the row, 16-byte aligned rows
+inline bool cos_operand_ok(const void* x, int64_t ld, int64_t ps, int64_t t, int d) {
+  return x && t > 0 && d > 0 && !(d & 31) && ld >= d && ps >= 0 && !((uintptr_t)x & 15) && !((ld | ps) & 7);
+}
+
+// The column tiles of a (problem, panel) cut into runs so that a launch has about COS_TARGET_ITEMS work items (two workgroups
+// per CU): run `split` takes `base` tiles, the first `rem` runs one more.  Only decides which workgroup computes a tile.
+constexpr int COS_TARGET_ITEMS = 512;
+struct RunSplit {
+  int nsplit, base, rem;
+};
+inline RunSplit run_split(int64_t items, int64_t ntiles) {
+  int64_t n = COS_TARGET_ITEMS / items;
+  n = n < 1 ? 1 : n > ntiles ? ntiles : n;
+  return {(int)n, (int)(ntiles / n), (int)(ntiles % n)};
+}
+VDR_DEV void run_tiles(int split, int base, int rem, int& jt0, int& jt1) {
+  jt0 = split * base + min(split, rem);
+  jt1 = jt0 + base + (split < rem);
+}
+
 // ---- addressing -------------------------------------------------------------------------------------
 // element offset of row r (0 .. R-1) of a problem that starts at element `base`: its images of a.t rows are a.is apart, rows a.ld
 template <class Args>
@@ -294,6 +382,9 @@ VDR_DEV float row_sumsq(const float* src, int d, int lane) {
   }
   return wave_sum(ss);
 }
+
+// rn(v) = 1 / max(sqrt(sum v^2), 1e-8) of the cosine kernels, IEEE sqrt and division: the one place it is written
+VDR_DEV float cosine_rn(float ss) { return __fdiv_rn(1.0f, fmaxf(__fsqrt_rn(ss), 1e-8f)); }
 
 // src[0] + src[stride] + ... + src[(n - 1) stride], ascending: the definition of every chunked sum's bits
 VDR_DEV float fold_chunks(const float* src, int n, int64_t stride) {

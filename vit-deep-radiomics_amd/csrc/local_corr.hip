@@ -6,12 +6,12 @@
 // (`transposed`: the association of the reverse direction, (dot * rn(y_j)) * rn(x_i), the bits of nn_cosine's column side).
 //
 // Three launches, no atomics:
-//   lc_rnorm_kernel    rn of every row of X and Y into `work`; nn_rnorm_kernel's arithmetic restated (row_sumsq: one wave per
-//                      row, IEEE sqrt and division), as aff_rnorm_kernel restates it.
+//   cosine_rnorm_kernel  (nn_cosine.hip) rn of every row of X and Y into `work`: nn_cosine's, by the same kernel.
 //   local_corr_kernel  256 threads; one work item = (pair, panel of 8 x 16 queries, tile of 128 halo candidates), the mapping
-//                      of local_corr_map.h.  nn_cosine_kernel's K loop with gathered source rows: per step of 64 channels both
-//                      operands go global -> LDS by LDS-DMA into the t128 image of desc_tile.h, two buffers, step s + 1 in
-//                      flight under the MFMAs of step s.  The per-lane source rows are the mapping's `src`: positions outside
+//                      of local_corr_map.h.  nn_cosine_kernel's K loop (dma_steps of desc_tile.h, over one tile) with gathered
+//                      source rows (t128_dma_stage): per step of 64 channels both operands go global -> LDS by LDS-DMA into
+//                      the t128 image, two buffers, step s + 1 in flight under the MFMAs of step s.  The per-lane source rows
+//                      are the mapping's `src`: positions outside
 //                      the grid, past the ragged panel or past the halo load a clamped (valid) row, whose finite values are
 //                      dropped in the epilogue.  Epilogue: a lane holds ONE candidate and 16 query rows per accumulator; for
 //                      every element whose candidate falls in the query's window (lc_slot) it stores sim -- or -inf for a
@@ -34,8 +34,7 @@
 namespace vdr {
 namespace {
 
-constexpr int LC_OPER = T128_OPER;     // bytes of one staged operand tile
-constexpr int LC_RN = 4 * LC_OPER;     // s_rn [256] float: rn of the tile's candidates | of the panel's queries
+constexpr int LC_RN = 4 * T128_OPER;    // s_rn [256] float: rn of the tile's candidates | of the panel's queries
 constexpr int LC_LDS = LC_RN + 1024;
 static_assert(LC_TILE == T128, "the panel and the halo tile are operands of the t128 image");
 
@@ -49,26 +48,6 @@ struct LcArgs {
   float* cost;       // [pairs][t][W * W]: the caller's, or the scratch copy in `work`
 };
 
-__global__ __launch_bounds__(256) void lc_rnorm_kernel(LcArgs a, int pairs) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t n = (int64_t)pairs * a.t;
-  if (row >= 2 * n) return;
-  const bool is_x = row < n;
-  const int64_t r = is_x ? row : row - n;
-  const int64_t p = r / a.t;
-  const int i = (int)(r - p * a.t);
-  const bf16_t* src = is_x ? a.x + p * a.xs + (int64_t)i * a.ldx : a.y + p * a.ys + (int64_t)i * a.ldy;
-  const float ss = row_sumsq(src, a.d, lane);
-  if (lane == 0) (is_x ? a.rnx : a.rny)[p * a.t_pad + i] = __fdiv_rn(1.0f, fmaxf(__fsqrt_rn(ss), 1e-8f));
-}
-
-// the staged step has landed, for every wave: the DMAs are opaque to hipcc, so the wait is spelled out
-VDR_DEV void lc_wait() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-}
-
 __global__ __launch_bounds__(256, 2) void local_corr_kernel(LcArgs a) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l31 = lane & 31, hh = lane >> 5;
@@ -80,18 +59,17 @@ __global__ __launch_bounds__(256, 2) void local_corr_kernel(LcArgs a) {
   const int p = pp / a.g.npanels, panel = pp - p * a.g.npanels;
   const bf16_t* xp = a.x + (int64_t)p * a.xs;
   const bf16_t* yp = a.y + (int64_t)p * a.ys;
-  const int nk = (a.d + 63) >> 6;
   float* s_rn = reinterpret_cast<float*>(smem + LC_RN);
 
   // the rows this lane stages, fixed over the K loop: 4 of the panel and 4 of the tile (element offsets of clamped rows)
   int64_t xo[4], yo[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const int r = (wave * 4 + q) * 8 + (lane >> 3);
+    const int r = t128_dma_row(wave, lane, q);
     xo[q] = (int64_t)lc_map(a.g, panel, tile, 0, r).src * a.ldx;
     yo[q] = (int64_t)lc_map(a.g, panel, tile, 1, r).src * a.ldy;
   }
-  {  // rn of the item's 128 candidates and 128 queries, gathered through the same mapping; visible after the first lc_wait
+  {  // rn of the item's 128 candidates and 128 queries, gathered through the same mapping; visible after the first dma_wait
     const int t = threadIdx.x, side = t < 128 ? 1 : 0, r = t & 127;
     const int src = lc_map(a.g, panel, tile, side, r).src;
     s_rn[t] = (side ? a.rny : a.rnx)[(int64_t)p * a.t_pad + src];
@@ -99,33 +77,10 @@ __global__ __launch_bounds__(256, 2) void local_corr_kernel(LcArgs a) {
 
   f32x16 acc[2][2];
   acc_zero(acc);
-  // nn_cosine_kernel's loop over one tile: step s + 1 staged under the MFMAs of step s (pass s = -1 only stages step 0) into
-  // the other buffer, which every wave finished reading before the barrier that ended the previous pass
-  int buf = 1;
-#pragma clang loop unroll(disable)
-  for (int s = -1; s < nk; ++s) {
-    if (s + 1 < nk) {
-      const int k0 = (s + 1) * 64;
-      const bool shortk = a.d - k0 < 64;
-      char* sx = smem + (buf ^ 1) * 2 * LC_OPER;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int piece = wave * 4 + q;
-        const int r = piece * 8 + (lane >> 3);
-        int c = (lane & 7) ^ ((r >> 1) & 7);
-        c = shortk ? c & 3 : c;
-        glds16_raw(xp + xo[q] + k0 + c * 8, sx + piece * 1024);
-        glds16_raw(yp + yo[q] + k0 + c * 8, sx + LC_OPER + piece * 1024);
-      }
-    }
-    if (s >= 0) {
-      const char* sx = smem + buf * 2 * LC_OPER;
-      t128_mfma<0, 2>(sx, wr, wc, l31, hh, acc);
-      if (a.d - s * 64 >= 64) t128_mfma<2, 4>(sx, wr, wc, l31, hh, acc);
-    }
-    lc_wait();
-    buf ^= 1;
-  }
+  // one tile.  Its epilogue follows the loop instead of being handed in: inside the loop its lane masks are loop invariants
+  // kept in SGPR pairs, and the kernel goes to 256 VGPRs, 68 + 12 spills, 52 bytes of scratch and occupancy 2
+  dma_steps(0, 1, a.d, smem, wr, wc, l31, hh, acc,
+            [&](int, int kk, char* sx) { t128_dma_stage(xp, yp, xo, yo, a.d, kk, sx, wave, lane); }, [](int) {});
 
   // ---- epilogue: this lane's two candidates against its 32 queries
   float rny[2];
@@ -216,11 +171,10 @@ size_t local_correlation_work_bytes(int pairs, int gh, int gw, int radius) {
 hipError_t launch_local_correlation(const void* x, int64_t ldx, int64_t x_stride, const void* y, int64_t ldy, int64_t y_stride,
                                     int pairs, int gh, int gw, int d, int radius, int transposed, void* work, float* cost,
                                     float* best_sim, int32_t* best_idx, hipStream_t st) {
-  if (!x || !y || !work || (!best_sim) != (!best_idx) || (!cost && !best_sim) || pairs <= 0 || gh <= 0 || gw <= 0 || d <= 0 ||
-      (d & 31) || ldx < d || ldy < d || x_stride < 0 || y_stride < 0 || radius < 1 || radius > LC_MAX_RADIUS)
-    return hipErrorInvalidValue;
-  if ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)work) & 15) || ((ldx | ldy | x_stride | y_stride) & 7)) return hipErrorInvalidValue;
   const int64_t t = (int64_t)gh * gw, WW = (int64_t)(2 * radius + 1) * (2 * radius + 1);
+  if (gh <= 0 || gw <= 0 || !cos_operand_ok(x, ldx, x_stride, t, d) || !cos_operand_ok(y, ldy, y_stride, t, d) || !work ||
+      ((uintptr_t)work & 15) || (!best_sim) != (!best_idx) || (!cost && !best_sim) || pairs <= 0 || radius < 1 || radius > LC_MAX_RADIUS)
+    return hipErrorInvalidValue;
   if (t > INT32_MAX || (int64_t)pairs * t > INT32_MAX / WW) return hipErrorInvalidValue;  // pairs * t * W * W <= 2^31 - 1
   const LcLayout l = lc_layout(pairs, gh, gw, radius);
   LcArgs a;
@@ -242,8 +196,8 @@ hipError_t launch_local_correlation(const void* x, int64_t ldx, int64_t x_stride
   if (dev < 0) return hipErrorInvalidDevice;
   if (hipError_t e = raise_lds_limit(ks, (const void*)local_corr_kernel, dev, LC_LDS)) return e;
   const int64_t rows = (int64_t)pairs * t;
-  hipLaunchKernelGGL(lc_rnorm_kernel, dim3((unsigned)((2 * rows + 3) / 4)), dim3(256), 0, st, a, pairs);
-  if (hipError_t e = hipGetLastError()) return e;
+  if (hipError_t e = launch_cosine_rnorm({a.x, ldx, x_stride, a.t, a.t_pad, a.rnx}, {a.y, ldy, y_stride, a.t, a.t_pad, a.rny}, d, pairs, st))
+    return e;
   hipLaunchKernelGGL(local_corr_kernel, dim3((unsigned)items), dim3(256), LC_LDS, st, a);
   if (hipError_t e = hipGetLastError()) return e;
   if (best_sim) {

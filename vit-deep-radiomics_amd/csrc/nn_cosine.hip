@@ -5,12 +5,14 @@
 // The tx x ty similarity matrix is never written: it exists one 128 x 128 tile at a time in MFMA accumulators.
 //
 // Three launches, no atomics:
-//   nn_rnorm_kernel    rn of every row of X and Y into `work` (row_sumsq: one wave per row).  sqrt and the division are the
-//                      IEEE ones.
-//   nn_cosine_kernel   256 threads; one work item = (pair, split of Y's tiles, 128-row panel of X).  It walks its 128-row
-//                      tiles of Y; per tile a K loop over d in steps of 64 stages both operands global -> LDS (LDS-DMA,
-//                      two buffers: step s + 1 is in flight under the MFMAs of step s).  X is the A operand, Y the B
-//                      operand of the tile of desc_tile.h, so a lane holds ONE column j and 16 rows i.
+//   cosine_rnorm_kernel  rn (cosine_rn of desc_tile.h) of every row of X and Y into `work`: one wave per row.  Also the
+//                      row norms of local_corr.hip (launch_cosine_rnorm, vdr_kernels.h).
+//   nn_cosine_kernel   256 threads; one work item = (pair, run of Y's tiles, 128-row panel of X; run_split of desc_tile.h).
+//                      It walks its 128-row tiles of Y; per tile a K loop over d in steps of 64 stages both operands
+//                      global -> LDS (LDS-DMA, two buffers: step s + 1 is in flight under the MFMAs of step s).  The loop
+//                      and the staging are the kernel's own copy of dma_steps / t128_dma_stage of desc_tile.h: through
+//                      the helpers it ran up to 3 % slower.  X is the A operand, Y the B operand of the
+//                      tile of desc_tile.h, so a lane holds ONE column j and 16 rows i.
 //                      Epilogue per tile, in that layout: scale, mask the ragged rows / columns with -inf, fold every
 //                      element into the lane's running row best (kept across the tiles), reduce the tile's column best
 //                      over registers, lane halves and the two row waves (LDS), write it as a partial (value, index).
@@ -20,10 +22,8 @@
 // with distinct indices: the result is the same whatever the grouping, so it depends neither on the split count (a
 // launch heuristic) nor on `pairs`.  dot is the MFMA's fp32 accumulation in k order; both are fixed.
 //
-// LDS image of a staged operand tile: the "t128" image of desc_tile.h.  The DMA writes linearly, so the swizzle
-// is applied to the per-lane SOURCE address.  Rows past the end of a map repeat its last row (finite values, masked in the
-// epilogue).  d % 64 == 32: the last step runs 2 of its 4 MFMA k-steps; its unused chunks re-read chunks 0..3 (nothing
-// past the end of a row is touched).
+// Rows past the end of a map repeat its last row (finite values, masked in the epilogue); the image, the source chunk a
+// lane copies (swizzle, short last step of d % 64 == 32: t128_dma_chunk) and the wait (dma_wait) are desc_tile.h's.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -36,13 +36,12 @@ namespace vdr {
 namespace {
 
 constexpr int NN_T = T128;                  // tile side (rows of X per panel, rows of Y per tile)
-constexpr int NN_OPER = T128_OPER;          // bytes of one staged operand tile
-constexpr int NN_RN = 4 * NN_OPER;          // s_rn [2][256] float: tile parity x (rn of the tile's Y rows | of the panel's X rows)
+constexpr int NN_RN = 4 * T128_OPER;        // s_rn [2][256] float: tile parity x (rn of the tile's Y rows | of the panel's X rows)
 constexpr int NN_COL = NN_RN + 2048;        // column exchange: value [128], index [128]
 constexpr int NN_ROW = NN_COL + 1024;       // row exchange: value [2][128], index [2][128]
 constexpr int NN_LDS = NN_ROW + 2048;
-constexpr int NN_TARGET_ITEMS = 512;        // work items the split of Y's tiles aims for (two workgroups per CU)
 
+// (flat, in this order: with the fields regrouped by side nn_cosine_kernel spills 150 SGPRs instead of 142)
 struct NnArgs {
   const bf16_t *x, *y;
   int64_t ldx, xs, ldy, ys;
@@ -55,28 +54,17 @@ struct NnArgs {
   int32_t* rowi;
 };
 
-__global__ __launch_bounds__(256) void nn_rnorm_kernel(NnArgs a, int pairs) {
+__global__ __launch_bounds__(256) void cosine_rnorm_kernel(CosSide X, CosSide Y, int d, int pairs) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t nx = (int64_t)pairs * a.tx, ny = (int64_t)pairs * a.ty;
-  if (row >= nx + ny) return;
-  const bool is_x = row < nx;
-  const int64_t r = is_x ? row : row - nx;
-  const int t = is_x ? a.tx : a.ty;
-  const int64_t p = r / t;
-  const int i = (int)(r - p * t);
-  const bf16_t* src = is_x ? a.x + p * a.xs + (int64_t)i * a.ldx : a.y + p * a.ys + (int64_t)i * a.ldy;
-  const float ss = row_sumsq(src, a.d, lane);
-  if (lane == 0) {
-    const float rn = __fdiv_rn(1.0f, fmaxf(__fsqrt_rn(ss), 1e-8f));
-    if (is_x) a.rnx[p * a.tx_pad + i] = rn; else a.rny[p * a.ty_pad + i] = rn;
-  }
-}
-
-// the staged step has landed, for every wave: the DMAs are opaque to hipcc, so the wait is spelled out
-VDR_DEV void nn_wait() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
+  const int64_t nx = (int64_t)pairs * X.t;
+  if (row >= nx + (int64_t)pairs * Y.t) return;
+  const CosSide s = row < nx ? X : Y;
+  const int64_t r = row < nx ? row : row - nx;
+  const int64_t p = r / s.t;
+  const int i = (int)(r - p * s.t);
+  const float ss = row_sumsq((const bf16_t*)s.x + p * s.ps + (int64_t)i * s.ld, d, lane);
+  if (lane == 0) s.rn[p * s.t_pad + i] = cosine_rn(ss);
 }
 
 // one K step of (panel, tile jt) into staging buffer `buf`: 4 + 4 DMA instructions per wave, 8 rows x 128 B each
@@ -84,16 +72,15 @@ VDR_DEV void nn_stage(const NnArgs& a, const bf16_t* xp, const bf16_t* yp, int64
                       int buf, int wave, int lane) {
   const int k0 = kk * 64;
   const bool shortk = a.d - k0 < 64;
-  char* sx = smem + buf * 2 * NN_OPER;
+  char* sx = smem + buf * 2 * T128_OPER;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int piece = wave * 4 + q;
     const int r = piece * 8 + (lane >> 3);
-    int c = (lane & 7) ^ ((r >> 1) & 7);
-    c = shortk ? c & 3 : c;
+    const int c = t128_dma_chunk(lane, r, shortk);
     const int xr = min(panel * NN_T + r, a.tx - 1), yr = min(jt * NN_T + r, a.ty - 1);
     glds16_raw(xp + (int64_t)xr * a.ldx + k0 + c * 8, sx + piece * 1024);
-    glds16_raw(yp + (int64_t)yr * a.ldy + k0 + c * 8, sx + NN_OPER + piece * 1024);
+    glds16_raw(yp + (int64_t)yr * a.ldy + k0 + c * 8, sx + T128_OPER + piece * 1024);
   }
   if (kk == 0 && wave == 0) {  // the tile's rn values ride on the same wait: lanes 0..31 Y's, 32..63 the panel's
     const float* src = lane < 32 ? a.rny + p * a.ty_pad + jt * NN_T + lane * 4 : a.rnx + p * a.tx_pad + panel * NN_T + (lane - 32) * 4;
@@ -110,10 +97,10 @@ __global__ __launch_bounds__(256, 2) void nn_cosine_kernel(NnArgs a) {
   const int vid = xcd_remap(blockIdx.x, gridDim.x);
   const int ps = vid / a.npanels, panel = vid - ps * a.npanels;
   const int p = ps / a.nsplit, split = ps - p * a.nsplit;
-  const int jt0 = split * a.split_base + min(split, a.split_rem), jt1 = jt0 + a.split_base + (split < a.split_rem);
+  int jt0, jt1;
+  run_tiles(split, a.split_base, a.split_rem, jt0, jt1);
   const bf16_t* xp = a.x + (int64_t)p * a.xs;
   const bf16_t* yp = a.y + (int64_t)p * a.ys;
-  const int nk = (a.d + 63) >> 6;
 
   float rbv[2][16];
   int rbi[2][16];
@@ -130,10 +117,8 @@ __global__ __launch_bounds__(256, 2) void nn_cosine_kernel(NnArgs a) {
   float* s_colv = reinterpret_cast<float*>(smem + NN_COL);
   int* s_coli = reinterpret_cast<int*>(smem + NN_COL + 512);
 
-  // One loop over the K steps of all tiles, step s + 1 staged under the MFMAs of step s (pass s = -1 only stages step 0):
-  // the step after a tile's last one is the first of the next tile.  (jt, kk) is the step in the MFMAs, (njt, nkk) the
-  // one being staged; it goes into the other buffer, which every wave finished reading before the barrier that ended
-  // the previous pass.
+  // dma_steps of desc_tile.h, spelled out (see there for the counters and the buffers)
+  const int nk = (a.d + 63) >> 6;
   const int nsteps = (jt1 - jt0) * nk;
   int jt = jt0, kk = -1, buf = 1;
 #pragma clang loop unroll(disable)
@@ -145,7 +130,7 @@ __global__ __launch_bounds__(256, 2) void nn_cosine_kernel(NnArgs a) {
     }
     if (s + 1 < nsteps) nn_stage(a, xp, yp, p, panel, njt, nkk, smem, buf ^ 1, wave, lane);
     if (s >= 0) {
-      const char* sx = smem + buf * 2 * NN_OPER;
+      const char* sx = smem + buf * 2 * T128_OPER;
       t128_mfma<0, 2>(sx, wr, wc, l31, hh, acc);
       if (a.d - kk * 64 >= 64) t128_mfma<2, 4>(sx, wr, wc, l31, hh, acc);
       if (kk + 1 == nk) {
@@ -225,7 +210,7 @@ __global__ __launch_bounds__(256, 2) void nn_cosine_kernel(NnArgs a) {
         }
       }
     }
-    nn_wait();
+    dma_wait();
     buf ^= 1;
     jt = njt;
     kk = nkk;
@@ -296,13 +281,19 @@ NnLayout nn_layout(int pairs, int tx, int ty) {
   l.rn_x = (int64_t)pairs * l.tx_pad;
   l.rn_y = (int64_t)pairs * l.ty_pad;
   l.col = (int64_t)pairs * l.npanels * l.ty_pad;
-  // pairs * nsplit * tx_pad with nsplit <= max(1, NN_TARGET_ITEMS / (pairs * npanels)): never more than this, and monotone
+  // pairs * nsplit * tx_pad with nsplit <= max(1, COS_TARGET_ITEMS / (pairs * npanels)): never more than this, and monotone
   const int64_t items = (int64_t)pairs * l.npanels;
-  l.row = (items > NN_TARGET_ITEMS ? items : NN_TARGET_ITEMS) * NN_T;
+  l.row = (items > COS_TARGET_ITEMS ? items : COS_TARGET_ITEMS) * NN_T;
   return l;
 }
 
 }  // namespace
+
+hipError_t launch_cosine_rnorm(const CosSide& X, const CosSide& Y, int d, int pairs, hipStream_t st) {
+  const int64_t rows = (int64_t)pairs * X.t + (int64_t)pairs * Y.t;
+  hipLaunchKernelGGL(cosine_rnorm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, X, Y, d, pairs);
+  return hipGetLastError();
+}
 
 size_t nn_cosine_work_bytes(int pairs, int tx, int ty) {
   if (pairs <= 0 || tx <= 0 || ty <= 0) return 0;
@@ -313,10 +304,9 @@ size_t nn_cosine_work_bytes(int pairs, int tx, int ty) {
 hipError_t launch_nn_cosine(const void* x, int64_t ldx, int64_t x_stride, int tx, const void* y, int64_t ldy, int64_t y_stride,
                             int ty, int pairs, int d, void* work, float* row_sim, int32_t* row_idx, float* col_sim,
                             int32_t* col_idx, hipStream_t st) {
-  if (!x || !y || !work || !row_sim || !row_idx || (!col_sim) != (!col_idx) || pairs <= 0 || tx <= 0 || ty <= 0 || d <= 0 ||
-      (d & 31) || ldx < d || ldy < d || x_stride < 0 || y_stride < 0)
+  if (!cos_operand_ok(x, ldx, x_stride, tx, d) || !cos_operand_ok(y, ldy, y_stride, ty, d) || !work || ((uintptr_t)work & 15) ||
+      !row_sim || !row_idx || (!col_sim) != (!col_idx) || pairs <= 0)
     return hipErrorInvalidValue;
-  if ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)work) & 15) || ((ldx | ldy | x_stride | y_stride) & 7)) return hipErrorInvalidValue;
   if ((int64_t)pairs * (tx > ty ? tx : ty) > INT32_MAX) return hipErrorInvalidValue;
   const NnLayout l = nn_layout(pairs, tx, ty);
   NnArgs a;
@@ -326,28 +316,24 @@ hipError_t launch_nn_cosine(const void* x, int64_t ldx, int64_t x_stride, int tx
   a.tx = tx, a.ty = ty, a.d = d;
   a.npanels = (int)l.npanels, a.ntiles = (int)l.ntiles, a.tx_pad = (int)l.tx_pad, a.ty_pad = (int)l.ty_pad;
   const int64_t items = (int64_t)pairs * l.npanels;
-  int64_t nsplit = NN_TARGET_ITEMS / items;
-  nsplit = nsplit < 1 ? 1 : nsplit > l.ntiles ? l.ntiles : nsplit;
-  a.nsplit = (int)nsplit;
-  a.split_base = (int)(l.ntiles / nsplit), a.split_rem = (int)(l.ntiles % nsplit);
+  const RunSplit run = run_split(items, l.ntiles);
+  a.nsplit = run.nsplit, a.split_base = run.base, a.split_rem = run.rem;
   a.do_cols = col_sim != nullptr;
-  float* w = (float*)work;
-  a.rnx = w;
+  a.rnx = (float*)work;
   a.rny = a.rnx + l.rn_x;
   a.colv = a.rny + l.rn_y;
   a.coli = (int32_t*)(a.colv + l.col);
   a.rowv = (float*)(a.coli + l.col);
   a.rowi = (int32_t*)(a.rowv + l.row);
-  if (items * nsplit > INT32_MAX) return hipErrorInvalidValue;
+  if (items * a.nsplit > INT32_MAX) return hipErrorInvalidValue;
 
   static KernelState ks;
   const int dev = current_device_index();
   if (dev < 0) return hipErrorInvalidDevice;
   if (hipError_t e = raise_lds_limit(ks, (const void*)nn_cosine_kernel, dev, NN_LDS)) return e;
-  const int64_t rows = (int64_t)pairs * tx + (int64_t)pairs * ty;
-  hipLaunchKernelGGL(nn_rnorm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, a, pairs);
-  if (hipError_t e = hipGetLastError()) return e;
-  hipLaunchKernelGGL(nn_cosine_kernel, dim3((unsigned)(items * nsplit)), dim3(256), NN_LDS, st, a);
+  if (hipError_t e = launch_cosine_rnorm({a.x, ldx, x_stride, tx, a.tx_pad, a.rnx}, {a.y, ldy, y_stride, ty, a.ty_pad, a.rny}, d, pairs, st))
+    return e;
+  hipLaunchKernelGGL(nn_cosine_kernel, dim3((unsigned)(items * a.nsplit)), dim3(256), NN_LDS, st, a);
   if (hipError_t e = hipGetLastError()) return e;
   const int64_t outs = (int64_t)pairs * tx + (a.do_cols ? (int64_t)pairs * ty : 0);
   hipLaunchKernelGGL(nn_finish_kernel, dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, st, a, pairs, row_sim, row_idx, col_sim,

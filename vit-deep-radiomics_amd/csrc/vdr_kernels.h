@@ -307,6 +307,18 @@ hipError_t launch_im2col_strided(const void* images, int in_bf16, void* col, int
 hipError_t launch_log_bin(const void* x, int in_bf16, int64_t ld, int64_t image_stride, int batch, int gh, int gw, int C,
                           int hierarchy, float* work, void* out, int out_bf16, hipStream_t st);
 
+// The row norms of the two-sided cosine ops (the kernel is in nn_cosine.hip; local_corr.hip launches it too):
+// rn(v) = 1 / max(sqrt(sum v^2), 1e-8), IEEE sqrt and division, of every row of side X, then of side Y, in one launch of one
+// wave per row.  A side is `pairs` maps of t bf16 rows of d channels, rows ld elements apart, problems ps apart (0 allowed);
+// rn is [pairs][t_pad].  t == 0 (a CosSide{}): no such side.
+struct CosSide {
+  const void* x = nullptr;
+  int64_t ld = 0, ps = 0;
+  int t = 0, t_pad = 0;
+  float* rn = nullptr;
+};
+hipError_t launch_cosine_rnorm(const CosSide& X, const CosSide& Y, int d, int pairs, hipStream_t st);
+
 // Cosine nearest neighbours of two descriptor maps (nn_cosine.hip; the definition is vdr_op_nn_cosine's in include/vdr.h):
 // X_p [tx, d], Y_p [ty, d] bf16, rows ldx / ldy elements apart, pairs x_stride / y_stride apart (0: one map against many).
 // d % 32 == 0; pointers, row and pair strides 16-byte aligned; work: nn_cosine_work_bytes(pairs, tx, ty) bytes.  col_sim and
