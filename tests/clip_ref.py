@@ -9,7 +9,9 @@ tests/golden/clip_hf_tiny.npz / siglip_hf_tiny.npz (tests/test_clip_cpu.py: <= 2
 emulate=True rounds to bf16 where the HIP path stores bf16 (as vit_oracle's emulate_bf16=True does).
 """
 import math
+import os
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -32,6 +34,24 @@ def tiny_cfg(g, family: str) -> vo.VitCfg:
 def golden_state_dict(g) -> dict:
     """the transformers state_dict a golden holds under sd.<key>"""
     return {k[3:]: torch.from_numpy(g[k]) for k in g.files if k.startswith("sd.")}
+
+
+def tiny_model(golden_dir, family, **kw):
+    """(golden, VitCfg, translated weights, model) of a tiny golden, loaded through load_model's key detection"""
+    import vdr
+    import handle_configs as hc
+    g = np.load(os.path.join(golden_dir, family + "_hf_tiny.npz"), allow_pickle=False)
+    cfg = tiny_cfg(g, family)
+    sd = golden_state_dict(g)
+    name = f"_{family}_tiny_test"
+    vdr.ARCHS[name] = hc.vit_config(cfg)
+    try:
+        model = vdr.load_model(name, weights=sd, **kw)  # transformers keys: translated on the way in
+    finally:
+        del vdr.ARCHS[name]
+    from vdr import weights as W
+    w = (W.from_clip_vision_state_dict if family == "clip" else W.from_siglip_vision_state_dict)(sd)
+    return g, cfg, w, model
 
 
 def make_weights(cfg: vo.VitCfg, family: str, seed: int, scale: float = 0.02, proj: int = 512) -> dict:

@@ -15,6 +15,7 @@ import torch
 
 import nn_cosine_ref as nref
 import spectral_ref as sref
+from fixtures import ops  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -22,12 +23,6 @@ TS = (1, 5, 31, 32, 33, 64, 65, 127, 128, 129, 257, 300)
 DIMS = (32, 96, 448)
 PAIRS = 3
 TAUS = (0.2, 0.0, 1.0 / 16.0)
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from vdr import ops
-    return ops
 
 
 _CACHE = {}

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import mahalanobis_ref as mr
+from fixtures import lib  # noqa: F401
 
 GOLDENS = ("anomaly_sk_600x32", "anomaly_sk_1200x96", "anomaly_sk_1000x256")
 POS = "anomaly_sk_pos_2x3x40x32"
@@ -30,12 +31,6 @@ def _load(golden_dir, name):
     c = np.load(os.path.join(golden_dir, name + "_cov.npz"))
     d = int(name.split("x")[-1])
     return z, {"emp": _untriu(c["emp_cov_triu"], d), "shr": _untriu(c["shr_cov_triu"], d)}
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from vdr import _lib
-    return _lib.load()
 
 
 @pytest.mark.parametrize("name", GOLDENS)

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import handle_configs as hc
+from handle_configs import TINY
 import mahalanobis_ref as mr
 from oracle import vit_oracle as vo
 
@@ -25,7 +26,6 @@ FIT_WORST = 1.57e-3  # README_anomaly.md: the worst relative distance of fit_gau
 FIT_GATE = 10 * FIT_WORST  # three global maps, first device run (anomaly_sk_1000x256, empirical covariance)
 POS_WORST = 9.36e-3  # the same of the per-position case: 40 rows per Gaussian of 32 channels, a fit ten times as ill-conditioned
 POS_GATE = 10 * POS_WORST
-TINY = vo.VitCfg(32, 8, 3, 64, 1, 2, 128)
 
 
 @pytest.fixture(scope="module")
@@ -132,13 +132,8 @@ def test_memory_bank(anomaly):
 
 @pytest.fixture(scope="module")
 def model():
-    import vdr
-    name = "_anomaly_tiny"
-    vdr.ARCHS[name] = hc.vit_config(TINY)
-    try:
-        yield vdr.load_model(name, weights=vo.make_weights(TINY, seed=21, scale=0.05))
-    finally:
-        del vdr.ARCHS[name]
+    with hc.registered_model("_anomaly_tiny") as m:
+        yield m
 
 
 @pytest.fixture(scope="module")

@@ -17,6 +17,7 @@ to 128 tokens, <7,false> to 224), 4 the one with it (<7,true>, 129..224 tokens),
 import pytest
 import torch
 
+from fixtures import ops  # noqa: F401
 from oracle import attn_designs as ad
 
 pytestmark = pytest.mark.gpu
@@ -25,14 +26,6 @@ N64 = [1, 5, 32, 33, 64, 65, 128, 129, 197, 224, 225, 288, 289, 577, 1024]
 NHD = [1, 5, 32, 33, 63, 64, 65, 127, 128, 129, 197, 224, 225, 288, 289, 577, 1024]  # + key-chunk edges KC +- 1
 PAD_VALUES = (0.0, 1000.0, float("nan"), float("inf"), float("-inf"))
 LENGTHS = [1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 224, 225, 288, 289, 513]
-
-
-@pytest.fixture(scope="module")
-def ops():
-    import vdr  # noqa: F401
-    from vdr import ops as _ops
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return _ops
 
 
 def _variants(dh):

@@ -9,19 +9,15 @@ import math
 import pytest
 import torch
 
+import handle_configs as hc
+from attn_maps_ref import LOG2E, block_input, fp32_bounds, softmax64
+from fixtures import ops  # noqa: F401
 from oracle import vit_oracle as vo
 
 pytestmark = pytest.mark.gpu
 
 DHS = (32, 64, 96, 128)
 SEQS = (1, 5, 31, 32, 33, 63, 64, 65, 127, 128, 129, 197, 257, 577, 1025)
-LOG2E = 1.4426950408889634
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from vdr import ops
-    return ops
 
 
 def _qkv(B, N, H, dh, q, k, v):
@@ -119,28 +115,6 @@ def _random_qkv(gen, B, N, H, dh, amp):
     return q, k, v
 
 
-def _softmax64(q, k, dh):
-    return torch.softmax(q.double() @ k.double().transpose(-1, -2) / math.sqrt(dh), dim=-1)
-
-
-def _fp32_bounds(q, k, dh, N):
-    """Entry-wise relative and |sum p - 1| bounds of the fp32 arithmetic against float64 of the same bf16 values.
-    u = 2^-24.  The products q_i k_i of bf16 values are exact in fp32; their fp32 sum errs by at most
-    (dh - 1) u sum_i |q_i k_i| <= dh u A (A = max over rows and keys of sum |q_i k_i|).  c = RN(RN(dh^-1/2) RN(log2 e)) is
-    within 3u of dh^-1/2 log2 e, t = RN(s c) adds u |t|: |dt| <= c dh u A + 4 u T (T = max |t|); the same for m, and
-    t - m adds u 2T: the exponent errs by at most E = 2 (c dh u A + 4 u T) + 2 u T.  v_exp_f32 is within 2 ulp (2^-22
-    relative), so e is within ln2 E + 2^-22 relative.  l sums N such terms in fp32: N u more; r = RN(1/l) and p = RN(e r)
-    add 2u.  So |p / p64 - 1| <= 2 (ln2 E + 2^-22) + (N + 2) u (the e error enters through e and l), and the row sum,
-    N roundings of p more, |sum p - 1| <= that + N u.  Doubled for margin."""
-    u = 2.0 ** -24
-    c = LOG2E / math.sqrt(dh)
-    A = float((q.abs() @ k.abs().transpose(-1, -2)).max())
-    T = A * c
-    E = 2 * (c * dh * u * A + 4 * u * T) + 2 * u * T
-    rel = 2 * (math.log(2) * E + 2.0 ** -22) + (N + 2) * u
-    return 2 * rel, 2 * (rel + N * u)
-
-
 @pytest.mark.parametrize("dh", DHS)
 @pytest.mark.parametrize("N", (5, 65, 197, 577, 1025))
 def test_random_rows_against_a_float64_softmax(ops, dh, N):
@@ -148,8 +122,8 @@ def test_random_rows_against_a_float64_softmax(ops, dh, N):
     B, H = 2, 3
     q, k, v = _random_qkv(gen, B, N, H, dh, amp=2.0)
     qkv = _qkv(B, N, H, dh, q, k, v)
-    ref = _softmax64(q, k, dh)
-    rel_b, sum_b = _fp32_bounds(q, k, dh, N)
+    ref = softmax64(q, k, dh)
+    rel_b, sum_b = fp32_bounds(q, k, dh, N)
     got = ops.attention_probs(qkv, B, N, H, dh, N, False, torch.float32).cpu().double()
     rel = ((got - ref).abs() / ref).max().item()
     assert rel <= rel_b, (rel, rel_b)
@@ -203,20 +177,6 @@ def test_invariance_batch_repeat_and_cls_row(ops, dh):
 
 # ---- inside the forward --------------------------------------------------------------------------------------------
 
-def _vc(cfg, **kw):
-    import vdr
-    return vdr.VdrConfig(img=cfg.img, patch=cfg.patch, in_chans=cfg.in_chans, dim=cfg.dim, heads=cfg.heads, layers=cfg.layers,
-                         mlp_hidden=cfg.mlp_hidden, act=cfg.act, pre_ln=cfg.pre_ln, layerscale=cfg.layerscale,
-                         has_cls=cfg.has_cls, has_pos=cfg.has_pos, input_ln=cfg.input_ln, ln_eps=cfg.ln_eps, **kw)
-
-
-def _engine(cfg, w, **kw):
-    import vdr
-    e = vdr.Engine(_vc(cfg, **kw))
-    e.load_weights(w)
-    return e
-
-
 VIT3 = vo.VitCfg(64, 16, 3, 128, 2, 3, 512)  # dh 64, N = 17
 PATHS = {"fold": dict(), "no_ln_fold": dict(ln_fold=False), "fp8": dict(fp8=1), "resid_fp32": dict(resid_fp32=True),
          "fp8_cls_bf16": dict(fp8=1, fp8_cls_bf16=True)}
@@ -241,7 +201,7 @@ def test_zeroed_heads_are_exactly_uniform_inside_the_forward(path):
     dh = cfg.dim // cfg.heads
     w["blocks.1.attn.qkv.weight"][dh:2 * dh] = 0
     w["blocks.1.attn.qkv.bias"][dh:2 * dh] = 0
-    e = _engine(cfg, w, **PATHS[path])
+    e = hc.engine(cfg, w, **PATHS[path])
     N = cfg.n_tokens
     x = vo.make_images(cfg, 3, seed=2).cuda()
     _, (full, cls) = e.forward_attn_maps(x, [vdr.AttnMap(1, N), vdr.AttnMap(1, 1, dtype=torch.bfloat16)])
@@ -249,12 +209,6 @@ def test_zeroed_heads_are_exactly_uniform_inside_the_forward(path):
     assert torch.all(full[:, 1].cpu() == r)
     assert torch.all(cls[:, 1].cpu() == r.to(torch.bfloat16))
     assert (full[:, 0] - r.cuda()).abs().max() > 0.05
-
-
-def _block_input(e, x, layer):
-    """the raw residual stream block `layer` reads, fp32 [B, N, D], from the library's own output"""
-    import vdr
-    return e.forward_layers(x, [vdr.LayerOut(layer - 1, vdr.OUT_TOKENS, torch.float32, norm=False)])[0]
 
 
 @pytest.mark.parametrize("dh", (32, 64, 96, 128))
@@ -270,7 +224,7 @@ def test_maps_match_a_recompute_on_the_explicit_layernorm_path(ops, dh):
     D = dh * 2
     cfg = vo.VitCfg(64, 16, 3, D, 2, 3, 2 * D)
     w = _peaked(cfg, 7 + dh, math.sqrt(1200.0 / D))  # scores of about 3 nats spread at every width
-    e = _engine(cfg, w, ln_fold=False)
+    e = hc.engine(cfg, w, ln_fold=False)
     N, H = cfg.n_tokens, cfg.heads
     x = vo.make_images(cfg, 3, seed=9).cuda()
     c = LOG2E / math.sqrt(dh)
@@ -278,7 +232,7 @@ def test_maps_match_a_recompute_on_the_explicit_layernorm_path(ops, dh):
     bounds = {}
     for layer in (1, 2):
         _, (got,) = e.forward_attn_maps(x, [vdr.AttnMap(layer, N)])
-        xin = _block_input(e, x, layer).reshape(-1, D).to(torch.bfloat16).contiguous()
+        xin = block_input(e, x, layer).reshape(-1, D).to(torch.bfloat16).contiguous()
         h = ops.layernorm(xin, w[f"blocks.{layer}.norm1.weight"].cuda(), w[f"blocks.{layer}.norm1.bias"].cuda(), cfg.ln_eps,
                           torch.bfloat16).double()
         W = w[f"blocks.{layer}.attn.qkv.weight"].to(torch.bfloat16).double().cuda()
@@ -296,8 +250,8 @@ def test_maps_match_a_recompute_on_the_explicit_layernorm_path(ops, dh):
         q, k = qk[:, :, 0].transpose(1, 2), qk[:, :, 1].transpose(1, 2)
         dq, dk = uq[:, :, 0].transpose(1, 2), uq[:, :, 1].transpose(1, 2)
         ds = dq @ k.abs().transpose(-1, -2) + q.abs() @ dk.transpose(-1, -2) + dq @ dk.transpose(-1, -2)
-        ref = _softmax64(q, k, dh)
-        rel_b, _ = _fp32_bounds(q.cpu(), k.cpu(), dh, N)
+        ref = softmax64(q, k, dh)
+        rel_b, _ = fp32_bounds(q.cpu(), k.cpu(), dh, N)
         # log2 p_k = t_k - log2 sum_j 2^t_j moves by at most c (ds_k + max_j ds_j)
         dmax = ds.max(-1, keepdim=True).values
         bound = ref * (torch.exp2(c * (ds + dmax)) - 1) + ref * rel_b + 1e-7
@@ -318,7 +272,7 @@ def test_features_are_bitwise_those_of_forward_layers(path):
     import vdr
     cfg = VIT3
     w = _peaked(cfg, 3, 2.0)
-    e = _engine(cfg, w, **PATHS[path])
+    e = hc.engine(cfg, w, **PATHS[path])
     x = vo.make_images(cfg, 4, seed=1).cuda()
     specs = [vdr.LayerOut(0, vdr.OUT_TOKENS, norm=False), vdr.LayerOut(1, vdr.OUT_DENSE, torch.bfloat16),
              vdr.LayerOut(2, vdr.OUT_CLS), vdr.LayerOut(2, vdr.OUT_POOLED)]
@@ -337,12 +291,12 @@ def test_maps_do_not_depend_on_how_the_batch_is_run():
     N = cfg.n_tokens
     x = vo.make_images(cfg, 7, seed=3).cuda()
     req = [vdr.AttnMap(0, N), vdr.AttnMap(1, 1, True), vdr.AttnMap(2, 5, False, torch.bfloat16)]
-    ref = _engine(cfg, w).forward_attn_maps(x, req)[1]
+    ref = hc.engine(cfg, w).forward_attn_maps(x, req)[1]
     for kw in (dict(micro_batch=3), dict(micro_batch=2, streams=3), dict(micro_batch=1, streams=2)):
-        got = _engine(cfg, w, **kw).forward_attn_maps(x, req)[1]
+        got = hc.engine(cfg, w, **kw).forward_attn_maps(x, req)[1]
         for a, b in zip(got, ref):
             assert torch.equal(a, b), kw
-    e = _engine(cfg, w)
+    e = hc.engine(cfg, w)
     sub = e.forward_attn_maps(x[2:5].contiguous(), req)[1]
     for a, b in zip(sub, ref):
         assert torch.equal(a, b[2:5])
@@ -360,7 +314,7 @@ def test_last_block_map_with_cls_only_outputs(path):
     import vdr
     cfg = VIT3
     w = _peaked(cfg, 6, 4.0)
-    e = _engine(cfg, w, **PATHS[path])
+    e = hc.engine(cfg, w, **PATHS[path])
     N, L = cfg.n_tokens, cfg.layers
     x = vo.make_images(cfg, 3, seed=5).cuda()
     req = [vdr.AttnMap(L - 1, N), vdr.AttnMap(L - 1, 1, True)]
@@ -381,7 +335,7 @@ def test_last_block_map_with_cls_only_outputs(path):
 def test_model_level_checks_of_layer_and_q_rows():
     import vdr
     cfg = VIT3
-    e = _engine(cfg, _peaked(cfg, 1, 1.0))
+    e = hc.engine(cfg, _peaked(cfg, 1, 1.0))
     x = vo.make_images(cfg, 1, seed=0).cuda()
     lib = vdr.load()
     for bad in (vdr.AttnMap(3), vdr.AttnMap(-1)):
@@ -396,7 +350,7 @@ def test_python_methods_shapes_and_layouts():
     import vdr
     cfg = VIT3
     w = _peaked(cfg, 8, 4.0)
-    m = vdr.VitDescriptorModel(_vc(cfg), w)
+    m = vdr.VitDescriptorModel(hc.vit_config(cfg), w)
     B, H, N, g = 2, cfg.heads, cfg.n_tokens, cfg.img // cfg.patch
     x = vo.make_images(cfg, B, seed=6).cuda()
     last = m.get_last_selfattention(x)

@@ -16,23 +16,12 @@ import pytest
 import torch
 
 import clip_ref as cr
+from fixtures import ops  # noqa: F401
+from ops_checks import BF16_EPS, bf
 
 pytestmark = pytest.mark.gpu
 
-BF16_EPS = 2.0 ** -8
 KINDS = {"quick_gelu": "EPI_BIAS_QUICK_GELU", "gelu_tanh": "EPI_BIAS_GELU_TANH"}
-
-
-@pytest.fixture(scope="module")
-def ops():
-    import vdr  # noqa: F401
-    from vdr import ops as _ops
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return _ops
-
-
-def _bf(x):
-    return x.to(torch.bfloat16)
 
 
 def _epi(kind):
@@ -50,7 +39,7 @@ EPI_SHAPES = [(256 * 64, 2048, 256, (22, 26, 31)), (2048, 3072, 768, (22, 26, 27
 @pytest.mark.parametrize("M,N,K,variants", EPI_SHAPES)
 def test_linear_activation_epilogue_one_ulp_and_flip_share(ops, kind, M, N, K, variants):
     x, W, b = cr.epilogue_test_inputs(M, N, K, seed=M + N + K)
-    xd, Wd, bd = _bf(x).cuda(), _bf(W).cuda(), b.cuda()
+    xd, Wd, bd = bf(x).cuda(), bf(W).cuda(), b.cuda()
     assert torch.equal(xd.float().cpu(), x) and torch.equal(Wd.float().cpu(), W)  # the grids are bf16-exact
     pre = cr.exact_preactivation(xd.float(), Wd.float(), bd)       # float64 on the device, exact
     exact = cr.exact_activation_fp64(pre, kind)
@@ -82,7 +71,7 @@ def test_activation_tail_sweep_and_non_finite_inputs(ops, kind):
     vals = torch.cat([torch.linspace(-12, 12, 4096 - 16), torch.tensor([0.0, -0.0, 1e-30, -1e-30, 65504.0, -65504.0, 1e20, -1e20,
                                                                          3e38, -3e38, fmax, -fmax, 1e-36, -1e-36, 30.0, -30.0])])
     N = vals.numel()
-    y = ops.linear(_bf(torch.zeros(4, K)).cuda(), _bf(torch.zeros(N, K)).cuda(), vals.cuda(), epilogue=_epi(kind)).cpu()
+    y = ops.linear(bf(torch.zeros(4, K)).cuda(), bf(torch.zeros(N, K)).cuda(), vals.cuda(), epilogue=_epi(kind)).cpu()
     assert torch.isfinite(y.float()).all(), "finite x must give a finite result"
     exact = cr.exact_activation_fp64(vals, kind).expand(4, N)
     dist = cr.bf16_ulp_distance(y, exact)
@@ -90,11 +79,11 @@ def test_activation_tail_sweep_and_non_finite_inputs(ops, kind):
     ok = (dist <= 1) | (exact.abs() <= vals.double().abs().expand(4, N) * 2.0 ** -125)
     assert ok.all(), (kind, vals[(~ok)[0]][:5])
     big = vals.abs() >= 1e20
-    assert torch.equal(y[0][big & (vals > 0)].float(), _bf(vals[big & (vals > 0)]).float())
+    assert torch.equal(y[0][big & (vals > 0)].float(), bf(vals[big & (vals > 0)]).float())
     neg = y[0][big & (vals < 0)].float()
     assert (neg == 0).all() and torch.signbit(neg).all()
     sp = torch.tensor([float("nan"), float("inf"), float("-inf")] + [0.0] * 5)
-    z = ops.linear(_bf(torch.zeros(2, K)).cuda(), _bf(torch.zeros(8, K)).cuda(), sp.cuda(), epilogue=_epi(kind)).float().cpu()[0]
+    z = ops.linear(bf(torch.zeros(2, K)).cuda(), bf(torch.zeros(8, K)).cuda(), sp.cuda(), epilogue=_epi(kind)).float().cpu()[0]
     assert torch.isnan(z[0]) and z[1] == float("inf") and torch.isnan(z[2])  # NaN propagates; +inf -> +inf; -inf -> NaN (-inf * 0)
 
 
@@ -104,7 +93,7 @@ def test_ln_fold_consumer_with_the_new_epilogues(ops, kind):
     the activation of float64 F.linear(F.layer_norm(x)) to the tolerance the erf-GELU consumer is held to."""
     g = torch.Generator().manual_seed(17)
     M, D, N, eps = 256 * 64, 768, 3072, 1e-5   # 64 x 12 = 768 tiles, three full rounds: the 8-phase kernel takes it
-    x = _bf(torch.randn(M, D, generator=g) * 1.3 + 0.2).cuda()
+    x = bf(torch.randn(M, D, generator=g) * 1.3 + 0.2).cuda()
     W = torch.randn(N, D, generator=g) * 0.05
     b = torch.randn(N, generator=g) * 0.1
     gamma, beta = 1 + 0.1 * torch.randn(D, generator=g), 0.1 * torch.randn(D, generator=g)
@@ -127,7 +116,7 @@ def test_ln_fold_consumer_with_the_new_epilogues(ops, kind):
     assert (err <= bound).all()
     # and the unfolded path (explicit LayerNorm, then vdr_op_linear) agrees with it to bf16 noise
     h = ops.layernorm(x, gamma.cuda(), beta.cuda(), eps)
-    plain = ops.linear(h, _bf(W).cuda(), b.cuda(), epilogue=_epi(kind))
+    plain = ops.linear(h, bf(W).cuda(), b.cuda(), epilogue=_epi(kind))
     rel = ((plain.double() - outs[22].double()).norm() / outs[22].double().norm()).item()
     print(f"{kind}: folded vs explicit LayerNorm + linear: rel L2 {rel:.3e}")
     assert rel <= 8e-3
@@ -155,11 +144,11 @@ def test_attention_pool_all_keys_equal_gives_the_mean_exactly(ops, dh):
     for n in POOL_N:
         B = 2
         q = torch.randn(D, generator=g)
-        k = _bf(torch.randn(B, 1, D, generator=g)).expand(B, n, D)
+        k = bf(torch.randn(B, 1, D, generator=g)).expand(B, n, D)
         v = torch.randint(-8, 9, (B, n, D), generator=g).float()
-        kv = torch.cat([_bf(k), _bf(v)], dim=-1).reshape(B * n, 2 * D).contiguous().cuda()
+        kv = torch.cat([bf(k), bf(v)], dim=-1).reshape(B * n, 2 * D).contiguous().cuda()
         out = ops.attention_pool(q.cuda(), kv, B, n, H, dh).cpu()
-        want = _bf(v.sum(1) / float(n))  # fp32 division of an exact integer sum, then one rounding
+        want = bf(v.sum(1) / float(n))  # fp32 division of an exact integer sum, then one rounding
         assert torch.equal(out.view(torch.int16), want.view(torch.int16)), (dh, n)
 
 
@@ -174,9 +163,9 @@ def test_attention_pool_one_dominant_key_gives_its_value_row_exactly(ops, dh):
     for n in POOL_N:
         q = torch.zeros(H, dh)
         q[:, 0] = 16.0                                   # score = 16 k[0] / sqrt(dh): k[0] = 64 sqrt(dh)/4 ... below
-        k = _bf(torch.randn(B, n, H, dh, generator=g) * 0.5)
+        k = bf(torch.randn(B, n, H, dh, generator=g) * 0.5)
         k[..., 0] = 0.0
-        v = _bf(torch.randn(B, n, H, dh, generator=g) * 3)
+        v = bf(torch.randn(B, n, H, dh, generator=g) * 3)
         win = torch.zeros(B, H, dtype=torch.long)
         for b in range(B):
             for h in range(H):
@@ -200,7 +189,7 @@ def test_attention_pool_random_against_fp32_reference_and_batch_invariance(ops, 
     for n in POOL_N:
         B = 16
         q = torch.randn(D, generator=g) * 1.5
-        wide = _bf(torch.randn(B * n, 2 * D + 64, generator=g)).cuda()  # ldkv = 2D + 64: the k | v columns of a wider matrix
+        wide = bf(torch.randn(B * n, 2 * D + 64, generator=g)).cuda()  # ldkv = 2D + 64: the k | v columns of a wider matrix
         kv = wide[:, : 2 * D]
         out = ops.attention_pool(q.cuda(), kv, B, n, H, dh)
         ref = _pool_ref(q.cuda(), kv, B, n, H, dh)

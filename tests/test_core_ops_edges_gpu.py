@@ -19,6 +19,8 @@ import torch
 
 import core_ops_designs as cd
 import memguard as mg
+from fixtures import ops  # noqa: F401
+from ops_checks import BF16_EPS, bf
 
 pytestmark = pytest.mark.gpu
 
@@ -27,21 +29,8 @@ VARIANTS = [22, 23, 24, 25, 26, 27, 28, 29]
 SHAPES = [(1, 8, 64), (7, 72, 64), (65, 136, 128), (129, 264, 192), (257, 520, 64)]
 SWIGLU_SHAPES = [(1, 64, 64), (7, 128, 64), (129, 320, 128), (257, 576, 192)]
 GUARD_ROWS = 8
-BF16_EPS = 2.0 ** -8
 DT_PAIRS = [(torch.bfloat16, torch.bfloat16), (torch.bfloat16, torch.float32), (torch.float32, torch.bfloat16),
             (torch.float32, torch.float32)]
-
-
-@pytest.fixture(scope="module")
-def ops():
-    import vdr  # noqa: F401
-    from vdr import ops as _ops
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return _ops
-
-
-def _bf(t):
-    return t.to(torch.bfloat16)
 
 
 def _bits(t):
@@ -54,7 +43,7 @@ class Linear:
 
     def __init__(self, ops, x, W, bias, epi, variant, packed, resid=None, gamma=None, inplace=False):
         self.ops, self.epi, self.variant, self.packed, self.inplace = ops, epi, variant, packed, inplace
-        self.x, self.W, self.bias, self.resid, self.gamma = _bf(x), _bf(W), bias, None if resid is None else _bf(resid), gamma
+        self.x, self.W, self.bias, self.resid, self.gamma = bf(x), bf(W), bias, None if resid is None else bf(resid), gamma
         from vdr import EPI_SWIGLU
         self.n_out = W.shape[0] // 2 if epi == EPI_SWIGLU else W.shape[0]
 
@@ -99,10 +88,10 @@ def _close(got, ref, atol, what):
 
 def _random_case(M, N, K, seed):
     g = torch.Generator().manual_seed(seed)
-    x = _bf(torch.randn(M, K, generator=g)).float()
-    W = _bf(torch.randn(N, K, generator=g) * 0.08).float()
+    x = bf(torch.randn(M, K, generator=g)).float()
+    W = bf(torch.randn(N, K, generator=g) * 0.08).float()
     b = torch.randn(N, generator=g) * 0.1
-    r = _bf(torch.randn(M, N, generator=g)).float()
+    r = bf(torch.randn(M, N, generator=g)).float()
     gamma = 1 + 0.2 * torch.randn(N, generator=g)
     return x, W, b, r, gamma
 
@@ -237,7 +226,7 @@ def test_rcp_of_one_is_one(ops):
     x = torch.zeros(4, K)
     W = torch.zeros(64, K)
     b = torch.cat([torch.full((32,), 32.0), torch.ones(32)])
-    y = ops.linear(_bf(x).cuda(), _bf(W).cuda(), b.cuda(), epilogue=vdr.EPI_SWIGLU)
+    y = ops.linear(bf(x).cuda(), bf(W).cuda(), b.cuda(), epilogue=vdr.EPI_SWIGLU)
     print("silu(32) * 1 on the device:", y[0, 0].item())
     assert torch.equal(y.float().cpu(), torch.full((4, 32), 32.0))
 

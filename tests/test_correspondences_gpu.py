@@ -10,23 +10,17 @@ import pytest
 import torch
 
 import handle_configs as hc
+from handle_configs import TINY
 import nn_cosine_ref as nref
 from oracle import vit_oracle as vo
 
 pytestmark = pytest.mark.gpu
 
-TINY = vo.VitCfg(32, 8, 3, 64, 1, 2, 128)
-
 
 @pytest.fixture(scope="module")
 def model():
-    import vdr
-    name = "_corr_tiny"
-    vdr.ARCHS[name] = hc.vit_config(TINY)
-    try:
-        yield vdr.load_model(name, weights=vo.make_weights(TINY, seed=21, scale=0.05))
-    finally:
-        del vdr.ARCHS[name]
+    with hc.registered_model("_corr_tiny") as m:
+        yield m
 
 
 @pytest.fixture(scope="module")

@@ -10,6 +10,8 @@ import os
 import pytest
 import torch
 
+from fixtures import lib  # noqa: F401
+
 # old text -> new text, without the "<op>: " both start with (the list of DESIGN.md §4.6q).  Conditions that two copies worded
 # differently and now share one wording:
 REWORDED = {
@@ -32,12 +34,6 @@ OWN_ALIGNMENT = {
     "d2": "the model strides (mean_stride, whiten_stride) must be 16-byte aligned, d2 4-byte aligned",
 }
 INVALID, UNSUPPORTED, NO_DEVICE = -1, -7, -2
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from vdr import _lib
-    return _lib.load()
 
 
 @pytest.fixture(scope="module")

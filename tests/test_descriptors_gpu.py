@@ -11,7 +11,6 @@ the golden): block 0 (gate 7.0e-3) query 3.1e-3 / 3.5e-3, key 3.4e-3 / 3.6e-3, v
 DINOv3 tiny, pre-rotation keys: 3.5e-3 / 3.7e-3 (block 0), 4.6e-3 / 4.9e-3 (block 1); min row cosine 0.99997.
 Everything else is bitwise: a facet is a copy of rows the forward computes anyway, and its log-bin is vdr_op_log_bin of
 those rows."""
-import math
 import os
 
 import numpy as np
@@ -21,45 +20,13 @@ import torch
 import descriptor_ref as dref
 import dinov3_ref as dr
 import handle_configs as hc
+from handle_configs import P16, TINY  # the vit_hf_tiny / vit_hf_facets network; test_model_gpu.SMALL["p16_d128"]
+from model_gates import check_parity, gate_l2, rel_l2
 from oracle import vit_oracle as vo
 
 pytestmark = pytest.mark.gpu
 
-TINY = vo.VitCfg(32, 8, 3, 64, 1, 2, 128)   # the vit_hf_tiny / vit_hf_facets network: 4 x 4 grid, N = 17
-P16 = vo.VitCfg(64, 16, 3, 128, 2, 3, 512)  # tests/test_model_gpu.py SMALL["p16_d128"]
 FACETS = ("query", "key", "value", "token")
-
-
-def _rel_l2(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def _min_cos(a, b):
-    a, b = a.double().reshape(-1, a.shape[-1]), b.double().reshape(-1, b.shape[-1])
-    return torch.nn.functional.cosine_similarity(a, b, dim=-1).min().item()
-
-
-def gate_l2(layers):  # tests/test_model_gpu.py
-    return 4e-3 + 3e-3 * math.sqrt(max(layers, 1))
-
-
-def _gate(got, ref, ref_emul, l2_fp32, l2_emul, what):  # tests/test_model_gpu.py
-    got = got.float().cpu()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    assert torch.isfinite(got).all(), what
-    r32, re, c = _rel_l2(got, ref), _rel_l2(got, ref_emul), _min_cos(got, ref)
-    print(f"{what}: relL2 vs fp32 {r32:.3e}  vs bf16-emulated {re:.3e}  (emulated vs fp32 {_rel_l2(ref_emul, ref):.3e})  min cos {c:.6f}")
-    assert c >= 0.999, f"{what}: min cosine {c}"
-    assert r32 <= l2_fp32, f"{what}: rel L2 vs fp32 {r32}"
-    assert re <= l2_emul, f"{what}: rel L2 vs bf16-emulating restatement {re}"
-
-
-def _engine(cfg, w, **kw):
-    import vdr
-    e = vdr.Engine(hc.vit_config(cfg, **kw))
-    e.load_weights(w)
-    return e
 
 
 def _tiny():
@@ -79,12 +46,13 @@ def test_hf_golden_every_facet_of_both_layers(golden_dir):
     g = np.load(os.path.join(golden_dir, "vit_hf_facets.npz"), allow_pickle=False)
     w, x = _tiny()
     emu = dref.facets(dref.plain(TINY), w, x, emulate=True)
-    e = _engine(TINY, w)
+    e = hc.engine(TINY, w)
     req = [vdr.FacetOut(i, f, all_rows=True) for i in range(TINY.layers) for f in FACETS]
     got, _, _ = e.forward_descriptors(x.cuda(), req)
     for r, t in zip(req, got):
         gl = gate_l2(r.layer + 1)
-        _gate(t, torch.from_numpy(g[f"{r.facet}.{r.layer}"]), emu[r.facet][r.layer], gl, gl, f"vit_hf_facets {r.facet}.{r.layer}")
+        check_parity(t, torch.from_numpy(g[f"{r.facet}.{r.layer}"]), f"vit_hf_facets {r.facet}.{r.layer}", gl,
+                     emu[r.facet][r.layer])
 
 
 # ---- 2. token == forward_layers(norm=False) ------------------------------------------------------------------------------
@@ -93,7 +61,7 @@ def test_token_facet_is_the_raw_layer_output_bitwise(kw):
     import vdr
     w = vo.make_weights(P16, seed=3, scale=0.05)
     x = vo.make_images(P16, 3, seed=4).cuda()
-    e = _engine(P16, w, **kw)
+    e = hc.engine(P16, w, **kw)
     for dt in (torch.float32, torch.bfloat16):
         for i in range(P16.layers):
             want = e.forward_layers(x, [vdr.LayerOut(i, vdr.OUT_DENSE, dt, False), vdr.LayerOut(i, vdr.OUT_TOKENS, dt, False)])
@@ -108,7 +76,7 @@ def test_binned_facet_is_log_bin_of_the_unbinned_bf16_facet(size):
     import vdr
     from vdr import ops
     w, _ = _tiny()
-    e = _engine(TINY, w)
+    e = hc.engine(TINY, w)
     if size:
         e.set_input_size(*size)
     H, W = e.input_size
@@ -130,7 +98,7 @@ def test_one_call_with_outs_maps_and_facets_equals_the_separate_calls():
     import vdr
     w = vo.make_weights(P16, seed=3, scale=0.05)
     x = vo.make_images(P16, 4, seed=4).cuda()
-    e = _engine(P16, w)
+    e = hc.engine(P16, w)
     N = P16.n_tokens
     outs = [vdr.LayerOut(2, vdr.OUT_CLS), vdr.LayerOut(0, vdr.OUT_DENSE, torch.bfloat16, False), vdr.LayerOut(1, vdr.OUT_POOLED)]
     maps = [vdr.AttnMap(1, N, True), vdr.AttnMap(2, 1)]
@@ -154,7 +122,7 @@ def test_key_only_last_block_stops_after_its_qkv_gemm(path):
     import vdr
     w = vo.make_weights(P16, seed=3, scale=0.05)
     x = vo.make_images(P16, 4, seed=4).cuda()
-    e = _engine(P16, w, **{"fold": {}, "nofold": dict(ln_fold=False), "fp8": dict(fp8=1)}[path])
+    e = hc.engine(P16, w, **{"fold": {}, "nofold": dict(ln_fold=False), "fp8": dict(fp8=1)}[path])
     L = P16.layers
     e.profile(True)
     (key,), _, _ = e.forward_descriptors(x, [vdr.FacetOut(L - 1, "key")])
@@ -185,9 +153,9 @@ def test_micro_batches_write_their_own_rows():
     x = vo.make_images(P16, 3, seed=4).cuda()
     req = [vdr.FacetOut(2, "key", 2), vdr.FacetOut(1, "value", all_rows=True), vdr.FacetOut(2, "token", 3, dtype=torch.bfloat16),
            vdr.FacetOut(0, "query", dtype=torch.bfloat16), vdr.FacetOut(1, "token")]
-    want, _, _ = _engine(P16, w).forward_descriptors(x, req)
+    want, _, _ = hc.engine(P16, w).forward_descriptors(x, req)
     for kw in (dict(micro_batch=2), dict(micro_batch=1, streams=2)):
-        got, _, _ = _engine(P16, w, **kw).forward_descriptors(x, req)
+        got, _, _ = hc.engine(P16, w, **kw).forward_descriptors(x, req)
         for a, b in zip(got, want):
             assert torch.equal(a, b), kw
 
@@ -208,7 +176,7 @@ def test_register_rows_are_prefix_rows():
         assert rows.shape == (2, n, 64) and allr.shape == (2, n + 5, 64)
         assert torch.equal(rows, allr[:, 5:])
         assert torch.equal(binned[:, :, 4 * 64:5 * 64], rows)
-        _gate(allr, ref[f][1], emu[f][1], gate_l2(2), gate_l2(2), f"registers {f}.1")
+        check_parity(allr, ref[f][1], f"registers {f}.1", gate_l2(2), emu[f][1])
 
 
 # ---- 8. DINOv3: before the rotation --------------------------------------------------------------------------------------
@@ -228,7 +196,7 @@ def test_dinov3_key_facet_is_taken_before_the_rotation():
     got, _, got_maps = e.forward_descriptors(x.cuda(), req, maps=maps)
     for r, t in zip(req, got):
         gl = gate_l2(r.layer + 1)
-        _gate(t, ref[r.facet][r.layer], emu[r.facet][r.layer], gl, gl, f"dinov3 {r.facet}.{r.layer} (pre-rotation)")
+        check_parity(t, ref[r.facet][r.layer], f"dinov3 {r.facet}.{r.layer} (pre-rotation)", gl, emu[r.facet][r.layer])
     for a, b in zip(got_maps, want_maps):
         assert torch.equal(a, b)
     # (the rotated keys are a different tensor: the gate would not hold against them)
@@ -236,7 +204,7 @@ def test_dinov3_key_facet_is_taken_before_the_rotation():
     cos, sin = dr.rope_table(e.grid, dh, rc.rope_theta)
     k0 = ref["key"][0][:, P:].reshape(2, -1, rc.vit.heads, dh).transpose(1, 2)
     rot = dr.rotate(k0, cos, sin).transpose(1, 2).reshape(2, -1, rc.vit.dim)
-    assert _rel_l2(got[0][:, P:].float().cpu(), rot) > 10 * gate_l2(1)
+    assert rel_l2(got[0][:, P:].float().cpu(), rot) > 10 * gate_l2(1)
 
 
 # ---- 9. patch stride -----------------------------------------------------------------------------------------------------
@@ -308,7 +276,7 @@ def test_level_means_that_do_not_fit_are_refused_before_the_first_launch():
     cfg = vo.VitCfg(64, 16, 3, 128, 2, 2, 128)
     w = vo.make_weights(cfg, seed=3, scale=0.05)
     x = vo.make_images(cfg, 64, seed=4).cuda()
-    e = _engine(cfg, w)
+    e = hc.engine(cfg, w)
     first = torch.full((64, cfg.n_patches, cfg.dim), -5.0, device="cuda")
     feat = torch.full((64, cfg.dim), -5.0, device="cuda")
     with pytest.raises(vdr.VdrError, match="do not fit") as ei:

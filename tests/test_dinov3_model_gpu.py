@@ -3,11 +3,10 @@ models (tests/golden/dinov3_hf_tiny.npz, dinov3_hf_gated_hd64.npz, dinov2reg_hf_
 prefix-row semantics of every output mode, and one full-size model of each family on seeded weights against the fp32
 restatement (tests/dinov3_ref.py).
 
-Gates: those of tests/test_model_gpu.py as tests/test_clip_model_gpu.py applies them -- per-row cosine >= 0.999 and rel L2
+Gates: those of tests/model_gates.py as tests/test_clip_model_gpu.py applies them -- per-row cosine >= 0.999 and rel L2
 <= gate(L) = 4e-3 + 3e-3 sqrt(L) against fp32 arithmetic and against the restatement with bf16 rounding emulated at the
 device's store points (for DINOv3 that includes the bf16 qkv before the rotation and the bf16 q / k after it).
 """
-import math
 import os
 
 import numpy as np
@@ -15,36 +14,12 @@ import pytest
 import torch
 
 import dinov3_ref as dr
+from model_gates import check_parity, gate_l2, min_cos, rel_l2
 from oracle import vit_oracle as vo
 
 pytestmark = pytest.mark.gpu
 
 GOLDENS = {"dinov3_hf_tiny": "dinov3", "dinov3_hf_gated_hd64": "dinov3", "dinov2reg_hf_tiny": "dinov2reg"}
-
-
-def _rel_l2(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def _min_cos(a, b):
-    a, b = a.double().reshape(-1, a.shape[-1]), b.double().reshape(-1, b.shape[-1])
-    return torch.nn.functional.cosine_similarity(a, b, dim=-1).min().item()
-
-
-def gate_l2(layers):  # tests/test_model_gpu.py
-    return 4e-3 + 3e-3 * math.sqrt(max(layers, 1))
-
-
-def _gate(got, ref, ref_emul, gate, what):  # tests/test_model_gpu.py
-    got = got.float().cpu()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    assert torch.isfinite(got).all(), what
-    r32, re, c = _rel_l2(got, ref), _rel_l2(got, ref_emul), _min_cos(got, ref)
-    print(f"{what}: relL2 vs fp32 {r32:.3e}  vs bf16-emulated {re:.3e}  (gate {gate:.3e})  min cos {c:.6f}")
-    assert c >= 0.999, f"{what}: min cosine {c}"
-    assert r32 <= gate, f"{what}: rel L2 vs fp32 {r32}"
-    assert re <= gate, f"{what}: rel L2 vs bf16-emulating restatement {re}"
 
 
 def _tiny(golden_dir, name, **kw):
@@ -80,12 +55,13 @@ def test_tiny_models_against_the_transformers_vectors(golden_dir, name):
         tok = m.engine.forward(xd, vdr.OUT_TOKENS)
         n = m.engine.n_patches
         assert tok.shape == (x.shape[0], P + n, D) and m.engine.n_tokens == P + n
-        _gate(tok, hf, emu["tokens"], gate_l2(L), f"{name}{tag} tokens (last_hidden_state)")
+        check_parity(tok, hf, f"{name}{tag} tokens (last_hidden_state)", gate_l2(L), emu["tokens"])
         cls = m(xd)
-        _gate(cls, torch.from_numpy(g["pooler_output" + tag]), emu["cls"], gate_l2(L), f"{name}{tag} cls (pooler_output)")
+        check_parity(cls, torch.from_numpy(g["pooler_output" + tag]), f"{name}{tag} cls (pooler_output)", gate_l2(L),
+                     emu["cls"])
         dense = m.engine.forward(xd, vdr.OUT_DENSE)
         assert dense.shape == (x.shape[0], n, D)
-        _gate(dense, hf[:, P:], emu["dense"], gate_l2(L), f"{name}{tag} dense (patch rows)")
+        check_parity(dense, hf[:, P:], f"{name}{tag} dense (patch rows)", gate_l2(L), emu["dense"])
         return tok
 
     native = run("")
@@ -97,7 +73,8 @@ def test_tiny_models_against_the_transformers_vectors(golden_dir, name):
         m.set_input_size(2 * rc.vit.img, rc.vit.img)
         x2 = torch.rand(2, 3, 2 * rc.vit.img, rc.vit.img, generator=torch.Generator().manual_seed(4))
         tok2 = m.engine.forward(x2.cuda(), vdr.OUT_TOKENS)
-        _gate(tok2, dr.forward(rc, w, x2)["tokens"], dr.forward(rc, w, x2, emulate=True)["tokens"], gate_l2(L), f"{name} 2:1 tokens")
+        check_parity(tok2, dr.forward(rc, w, x2)["tokens"], f"{name} 2:1 tokens", gate_l2(L),
+                     dr.forward(rc, w, x2, emulate=True)["tokens"])
     m.set_input_size(rc.vit.img, rc.vit.img)
     assert torch.equal(m.engine.forward(torch.from_numpy(g["x"]).cuda(), vdr.OUT_TOKENS), native), "back at the native size: the same bits"
 
@@ -107,12 +84,13 @@ def test_dynamic_size_follows_the_images(golden_dir):
     g, rc, w, m = _tiny(golden_dir, "dinov3_hf_tiny", dynamic_size=True)
     x2 = torch.from_numpy(g["x_64x32"])
     emu = dr.forward(rc, w, x2, emulate=True)
-    _gate(m(x2.cuda()), torch.from_numpy(g["pooler_output_64x32"]), emu["cls"], gate_l2(rc.vit.layers), "dynamic_size 64x32 cls")
+    check_parity(m(x2.cuda()), torch.from_numpy(g["pooler_output_64x32"]), "dynamic_size 64x32 cls", gate_l2(rc.vit.layers),
+                 emu["cls"])
     assert m.input_size == (64, 32)
     d = vdr.extract_dense(m, torch.from_numpy(g["x"]).cuda())
     assert d.shape == (3, 4, 4, rc.vit.dim) and m.input_size == (32, 32)
-    _gate(torch.from_numpy(d).reshape(3, 16, -1), torch.from_numpy(g["last_hidden_state"])[:, rc.n_prefix:],
-          dr.forward(rc, w, torch.from_numpy(g["x"]), emulate=True)["dense"], gate_l2(rc.vit.layers), "extract_dense")
+    check_parity(torch.from_numpy(d).reshape(3, 16, -1), torch.from_numpy(g["last_hidden_state"])[:, rc.n_prefix:],
+                 "extract_dense", gate_l2(rc.vit.layers), dr.forward(rc, w, torch.from_numpy(g["x"]), emulate=True)["dense"])
 
 
 # ---- prefix rows in every output mode ----------------------------------------------------------------------------------
@@ -172,9 +150,10 @@ def test_layers_and_attention_maps_agree_with_the_restatement(golden_dir, name):
     for i in range(c.layers):
         normed = vo.layer_norm(ref["layers"][i], w["norm.weight"], w["norm.bias"], c.ln_eps)
         normed_e = vo.layer_norm(emu["layers"][i], w["norm.weight"], w["norm.bias"], c.ln_eps)
-        _gate(outs[i][0], normed[:, P:], normed_e[:, P:], gate_l2(i + 1), f"{name} block {i} patch tokens (norm)")
-        _gate(outs[i][1], normed[:, 0], normed_e[:, 0], gate_l2(i + 1), f"{name} block {i} cls (norm)")
-        _gate(raws[i], ref["layers"][i][:, P:], emu["layers"][i][:, P:], gate_l2(i + 1), f"{name} block {i} patch tokens (raw)")
+        check_parity(outs[i][0], normed[:, P:], f"{name} block {i} patch tokens (norm)", gate_l2(i + 1), normed_e[:, P:])
+        check_parity(outs[i][1], normed[:, 0], f"{name} block {i} cls (norm)", gate_l2(i + 1), normed_e[:, 0])
+        check_parity(raws[i], ref["layers"][i][:, P:], f"{name} block {i} patch tokens (raw)", gate_l2(i + 1),
+                     emu["layers"][i][:, P:])
     # the maps come from the ROTATED q / k (DINOv3): the coarse check of tests/test_clip_model_gpu.py -- bf16 q / k behind
     # an activation that carries the forward's rel-L2: |dp| <= 0.1 p + 2e-3
     N = m.engine.n_tokens
@@ -205,10 +184,10 @@ def test_layernorm_fold_on_and_off(golden_dir, name):
     plain = plain_m.engine.forward(x.cuda(), vdr.OUT_TOKENS)
     assert not torch.equal(fused, plain)  # two different code paths really ran
     gt = gate_l2(c.layers)
-    r_f, r_p = _rel_l2(fused.cpu(), ref), _rel_l2(plain.cpu(), ref)
-    print(f"{name} LN fold: fused {r_f:.3e}  explicit {r_p:.3e}  fused-vs-explicit {_rel_l2(fused.cpu(), plain.cpu()):.3e}  (gate {gt:.3e})")
+    r_f, r_p = rel_l2(fused.cpu(), ref), rel_l2(plain.cpu(), ref)
+    print(f"{name} LN fold: fused {r_f:.3e}  explicit {r_p:.3e}  fused-vs-explicit {rel_l2(fused.cpu(), plain.cpu()):.3e}  (gate {gt:.3e})")
     assert r_f <= gt and r_p <= gt
-    assert _min_cos(fused.cpu(), ref) >= 0.999 and _min_cos(plain.cpu(), ref) >= 0.999
+    assert min_cos(fused.cpu(), ref) >= 0.999 and min_cos(plain.cpu(), ref) >= 0.999
     for mdl, per_block in ((fused_m, False), (plain_m, True)):
         mdl.engine.profile(True)
         mdl.engine.forward(x.cuda(), vdr.OUT_TOKENS)
@@ -241,9 +220,5 @@ def test_full_size_models_batch_8(arch):
     assert torch.equal(tok[7], tok[1]), "duplicate images must give bitwise equal rows"
     for got, want, what in ((tok, ref["tokens"], "tokens"), (m(xd), ref["cls"], "cls"),
                             (m.engine.forward(xd, vdr.OUT_DENSE), ref["dense"], "dense")):
-        got = got.float().cpu()
-        assert torch.isfinite(got).all()
-        r, c = _rel_l2(got, want), _min_cos(got, want)
-        print(f"{arch} L=12 {what}: relL2 vs fp32 restatement {r:.3e} (gate {gate_l2(12):.3e})  min row cosine {c:.6f}")
-        assert c >= 0.999 and r <= gate_l2(12), (what, r, c)
+        check_parity(got, want, f"{arch} L=12 {what}", gate_l2(12))
     assert torch.equal(m.engine.forward(xd, vdr.OUT_DENSE), tok[:, 5:])

@@ -10,52 +10,14 @@ permutation permutes the rows, and a row does not depend on the batch it travels
   config 5  DINOv2 ViT-g/14 224^2, 40 blocks, SwiGLU + LayerScale, bf16 and MX-fp8 weights (fp8 = 1)
   MedSAM    SAM ViT-B image encoder, 12 blocks at 1024^2 (tfds_dense_descriptor.py:93-107, 122-126)
 """
-import math
-
 import pytest
 import torch
 
+from model_gates import (check_batch_properties, check_parity, gate_l2, gate_l2_fp8, inject_outlier_channels, min_cos,
+                         rel_l2)
 from oracle import vit_oracle as vo
 
 pytestmark = pytest.mark.gpu
-
-
-def _rel_l2(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def _min_cos(a, b):
-    a, b = a.double().reshape(-1, a.shape[-1]), b.double().reshape(-1, b.shape[-1])
-    return torch.nn.functional.cosine_similarity(a, b, dim=-1).min().item()
-
-
-def gate_l2(layers):  # tests/test_model_gpu.py: bf16 path vs the fp32 oracle
-    return 4e-3 + 3e-3 * math.sqrt(layers)
-
-
-def _check(got, ref, gate, min_cos, what):
-    got = got.float().cpu().reshape(ref.shape)
-    assert torch.isfinite(got).all(), what
-    r, c = _rel_l2(got, ref), _min_cos(got, ref)
-    print(f"{what}: relL2 vs fp32 oracle {r:.3e} (gate {gate:.3e})  min row cosine {c:.6f} (gate {min_cos})")
-    assert c >= min_cos, f"{what}: min cosine {c}"
-    assert r <= gate, f"{what}: rel L2 {r} > {gate}"
-
-
-def _properties(e, x, mode, out_dtype, small=3):
-    """x [B, ...] on the device with x[B-1] == x[1]."""
-    import vdr  # noqa: F401
-    B = x.shape[0]
-    out = e.forward(x, mode, out_dtype)
-    assert torch.isfinite(out.float()).all()
-    assert torch.equal(out[B - 1], out[1]), "duplicate images must give bitwise equal rows"
-    g = torch.Generator().manual_seed(B)
-    perm = torch.randperm(B, generator=g).cuda()
-    assert torch.equal(e.forward(x[perm].contiguous(), mode, out_dtype), out[perm]), "batch permutation equivariance"
-    lo = B // 2
-    assert torch.equal(e.forward(x[lo:lo + small].contiguous(), mode, out_dtype), out[lo:lo + small]), "a row depends on its batch"
-    return out
 
 
 def test_config4_vit_large14_336_full_depth_and_full_batch():
@@ -70,13 +32,13 @@ def test_config4_vit_large14_336_full_depth_and_full_batch():
     xd = x.cuda().to(torch.bfloat16)
     dense = e.forward(xd, vdr.OUT_DENSE, torch.bfloat16)          # config 4's output: [B, 576, 1024] bf16
     assert dense.shape == (2, 576, 1024) and dense.dtype == torch.bfloat16
-    _check(dense, ref["dense"], gate_l2(24) + 2e-3, 0.999, "ViT-L/14@336 L=24 dense (bf16 out)")  # + the output rounding
-    _check(e.forward(xd, vdr.OUT_CLS), ref["cls"], gate_l2(24), 0.999, "ViT-L/14@336 L=24 cls")
+    check_parity(dense, ref["dense"], "ViT-L/14@336 L=24 dense (bf16 out)", gate_l2(24) + 2e-3)  # + the output rounding
+    check_parity(e.forward(xd, vdr.OUT_CLS), ref["cls"], "ViT-L/14@336 L=24 cls", gate_l2(24))
     # full per-GPU batch of config 4 (512 / 8 GPUs = 64 images)
     g = torch.Generator().manual_seed(1)
     xb = torch.rand(64, 3, cfg.img, cfg.img, generator=g).to(torch.bfloat16).cuda()
     xb[63] = xb[1]
-    out = _properties(e, xb, vdr.OUT_DENSE, torch.bfloat16)
+    out = check_batch_properties(lambda t: e.forward(t, vdr.OUT_DENSE, torch.bfloat16), xb)
     assert out.shape == (64, 576, 1024)
 
 
@@ -92,15 +54,15 @@ def test_config5_dinov2_giant14_full_depth_and_full_batch(fp8):
     ref = vo.forward_images(cfg, w, x)
     m = vdr.load_model("dinov2_giant14_224", weights=w, fp8=fp8)
     e = m.engine
-    gate, cos = (4e-2 + 4e-2 * math.sqrt(40), 0.99) if fp8 else (gate_l2(40), 0.999)
+    gate, cos = (gate_l2_fp8(40), 0.99) if fp8 else (gate_l2(40), 0.999)
     tag = "MX-fp8 weights" if fp8 else "bf16"
-    _check(e.forward(x.cuda(), vdr.OUT_CLS), ref["cls"], gate, cos, f"DINOv2 ViT-g/14 L=40 {tag} cls")
-    _check(e.forward(x.cuda(), vdr.OUT_DENSE), ref["dense"], gate, cos, f"DINOv2 ViT-g/14 L=40 {tag} dense")
+    check_parity(e.forward(x.cuda(), vdr.OUT_CLS), ref["cls"], f"DINOv2 ViT-g/14 L=40 {tag} cls", gate, cos=cos)
+    check_parity(e.forward(x.cuda(), vdr.OUT_DENSE), ref["dense"], f"DINOv2 ViT-g/14 L=40 {tag} dense", gate, cos=cos)
     # full per-GPU batch of config 5 (256 / 8 GPUs = 32 images)
     g = torch.Generator().manual_seed(2)
     xb = torch.rand(32, 3, cfg.img, cfg.img, generator=g).to(torch.bfloat16).cuda()
     xb[31] = xb[1]
-    out = _properties(e, xb, vdr.OUT_CLS, torch.float32)
+    out = check_batch_properties(lambda t: e.forward(t, vdr.OUT_CLS, torch.float32), xb)
     assert out.shape == (32, 1536)
 
 
@@ -119,10 +81,10 @@ def test_medsam_vit_b_1024_all_twelve_blocks(fp8):
     got = m.engine.forward(x.cuda(), vdr.OUT_ENCODER, torch.float32)
     assert got.shape == (1, 64, 64, 256)
     if fp8:
-        _check(got, ref, 4e-2 + 4e-2 * math.sqrt(12), 0.99, "MedSAM 1024^2 L=12 MX-fp8 neck output")
+        check_parity(got, ref, "MedSAM 1024^2 L=12 MX-fp8 neck output", gate_l2_fp8(12), cos=0.99)
     else:
         # the neck ends in a LayerNorm2d over 256 channels, which re-normalises the accumulated error: same gate
-        _check(got, ref, gate_l2(12), 0.999, "MedSAM 1024^2 L=12 neck output")
+        check_parity(got, ref, "MedSAM 1024^2 L=12 neck output", gate_l2(12))
     # batch of slices (what vdr.pipeline.generate_features feeds): rows do not depend on the batch
     xb = torch.cat([x, so.make_images(cfg, 2, seed=4)]).cuda()
     outb = m.engine.forward(xb, vdr.OUT_ENCODER, torch.float32)
@@ -138,16 +100,15 @@ def test_config5_massive_activation_channels_at_full_depth():
     5's output, so that switch is what `bench.py --fp8 --fp8-cls-bf16` times and what a massive-activation checkpoint
     should be loaded with.  Patch rows are dominated by the injected channels (cosine ~ 1 by construction)."""
     import vdr
-    from test_model_gpu import _inject_outlier_channels
     cfg = vo.CONFIGS["dinov2_giant14_224"]
-    w, _ = _inject_outlier_channels(vo.make_weights(cfg, seed=31), cfg.layers, cfg.dim, 32, "mlp.w12")
+    w, _ = inject_outlier_channels(vo.make_weights(cfg, seed=31), cfg.layers, cfg.dim, 32, "mlp.w12")
     x = vo.make_images(cfg, 2, seed=33)
     ref = vo.forward_images(cfg, w, x)["cls"]
 
     def cls_of(**kw):
         got = vdr.load_model("dinov2_giant14_224", weights=w, **kw).engine.forward(x.cuda(), vdr.OUT_CLS).float().cpu()
         assert torch.isfinite(got).all()
-        return _min_cos(got, ref), _rel_l2(got, ref)
+        return min_cos(got, ref), rel_l2(got, ref)
 
     c16, r16 = cls_of()
     c8, r8 = cls_of(fp8=1)
@@ -176,5 +137,5 @@ def test_resid_fp32_brings_the_deep_configs_to_the_survey_gate(name, layers, gat
     xd = x.cuda().to(torch.bfloat16) if name == "vit_large14_336" else x.cuda()
     if name == "vit_large14_336":
         ref = vo.forward_images(cfg, w, xd.float().cpu())
-    _check(e.forward(xd, vdr.OUT_CLS), ref["cls"], gate, 0.9995, f"{name} L={layers} resid_fp32 cls")
-    _check(e.forward(xd, vdr.OUT_DENSE), ref["dense"], gate, 0.9995, f"{name} L={layers} resid_fp32 dense (fp32 out)")
+    check_parity(e.forward(xd, vdr.OUT_CLS), ref["cls"], f"{name} L={layers} resid_fp32 cls", gate, cos=0.9995)
+    check_parity(e.forward(xd, vdr.OUT_DENSE), ref["dense"], f"{name} L={layers} resid_fp32 dense (fp32 out)", gate, cos=0.9995)

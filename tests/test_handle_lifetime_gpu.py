@@ -14,10 +14,9 @@ import ctypes as C
 import pytest
 import torch
 
+from handle_configs import P16, POSTLN, SAM, SWIGLU, reg_cfg, sam_config, sized_sam, vit_config
 from oracle import sam_oracle as so
 from oracle import vit_oracle as vo
-from handle_configs import reg_cfg, sam_config, sized_sam, vit_config
-from test_launch_ledger_gpu import P16, POSTLN, SAM, SWIGLU
 
 pytestmark = pytest.mark.gpu
 

@@ -10,25 +10,16 @@ import numpy as np
 import pytest
 import torch
 
+import handle_configs as hc
+from fixtures import ops  # noqa: F401
+from model_gates import check_parity, gate_l2, min_cos, rel_l2
+from ops_checks import BF16_EPS, assert_close, assert_unbiased, bf
 from oracle import attn_designs as ad
 from oracle import vit_oracle as vo
 
 pytestmark = pytest.mark.gpu
 
-BF16_EPS = 2.0 ** -8
 HEAD_DIMS = (32, 96, 128)
-
-
-@pytest.fixture(scope="module")
-def ops():
-    import vdr  # noqa: F401
-    from vdr import ops as _ops
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return _ops
-
-
-def _bf(x):
-    return x.to(torch.bfloat16)
 
 
 def _ref(qkv, B, N, H, dh):
@@ -38,38 +29,18 @@ def _ref(qkv, B, N, H, dh):
     return (p @ v).transpose(1, 2).reshape(B * N, H * dh).cpu()
 
 
-def _assert_unbiased(got, ref, what):
-    """|beta| <= 3e-4 from 30 k outputs on: see tests/test_ops_gpu.py _assert_unbiased"""
-    b = ad.check_unbiased(got.detach().double().cpu(), ref, what)
-    if b is not None:
-        print(f"beta {what}: {b:+.3e}")
-
-
-def _assert_close(got, ref, rtol, atol, what=""):
-    got = got.detach().float().cpu()
-    ref = ref.detach().float().cpu()
-    assert got.shape == ref.shape, (got.shape, ref.shape)
-    assert torch.isfinite(got).all(), f"{what}: non-finite output"
-    err = (got - ref).abs()
-    bad = err > atol + rtol * ref.abs()
-    if bad.any():
-        i = torch.nonzero(bad)[0].tolist()
-        raise AssertionError(f"{what}: {int(bad.sum())}/{bad.numel()} outside tol; first at {i}: got "
-                             f"{got[tuple(i)].item():.6g} ref {ref[tuple(i)].item():.6g}; max err {err.max().item():.4g}")
-
-
 # ---- the op ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dh", HEAD_DIMS)
 @pytest.mark.parametrize("N", [1, 5, 31, 32, 33, 127, 128, 129, 197, 288, 289, 577, 1024])
 def test_attention_hd_sequence_lengths(ops, dh, N):
     B, H = 2, 3
     g = torch.Generator().manual_seed(dh * 10000 + N)
-    qkv = _bf(torch.randn(B * N, 3 * H * dh, generator=g))
+    qkv = bf(torch.randn(B * N, 3 * H * dh, generator=g))
     o = ops.attention(qkv.cuda(), B, N, H, head_dim=dh)
     ref = _ref(qkv, B, N, H, dh)
     # P is rounded to bf16 before P.V and the output is stored as bf16: 2^-8 relative on O(1) values
-    _assert_close(o, ref, 2 * BF16_EPS, 6e-3, f"attention dh{dh} B{B} N{N} H{H}")
-    _assert_unbiased(o, ref, f"attention dh{dh} B{B} N{N} H{H}")
+    assert_close(o, ref, 2 * BF16_EPS, 6e-3, f"attention dh{dh} B{B} N{N} H{H}")
+    assert_unbiased(o, ref, f"attention dh{dh} B{B} N{N} H{H}")
 
 
 @pytest.mark.parametrize("dh", HEAD_DIMS)
@@ -77,11 +48,11 @@ def test_attention_hd_sequence_lengths(ops, dh, N):
 def test_attention_hd_batch_heads(ops, dh, B, N, H):
     """from one (sequence, head) item to more than 512"""
     g = torch.Generator().manual_seed(dh + B * 7 + N)
-    qkv = _bf(torch.randn(B * N, 3 * H * dh, generator=g))
+    qkv = bf(torch.randn(B * N, 3 * H * dh, generator=g))
     o = ops.attention(qkv.cuda(), B, N, H, head_dim=dh)
     ref = _ref(qkv, B, N, H, dh)
-    _assert_close(o, ref, 2 * BF16_EPS, 6e-3, f"attention dh{dh} B{B} N{N} H{H}")
-    _assert_unbiased(o, ref, f"attention dh{dh} B{B} N{N} H{H}")
+    assert_close(o, ref, 2 * BF16_EPS, 6e-3, f"attention dh{dh} B{B} N{N} H{H}")
+    assert_unbiased(o, ref, f"attention dh{dh} B{B} N{N} H{H}")
 
 
 @pytest.mark.parametrize("dh", HEAD_DIMS)
@@ -93,11 +64,11 @@ def test_attention_hd_rescale_branch_is_exercised(ops, dh):
     q = qkv[:, :dh]
     qkv[390, dh:2 * dh] = 4.0 * torch.sign(q[7])
     qkv[7, :dh] = 3.0 * torch.sign(q[7])
-    qkv = _bf(qkv)
+    qkv = bf(qkv)
     ref = _ref(qkv, B, N, H, dh)
     assert ref[7].abs().max() > 0  # (sanity)
     o = ops.attention(qkv.cuda(), B, N, H, head_dim=dh)
-    _assert_close(o, ref, 2 * BF16_EPS, 6e-3, f"attention rescale dh{dh}")
+    assert_close(o, ref, 2 * BF16_EPS, 6e-3, f"attention rescale dh{dh}")
 
 
 @pytest.mark.parametrize("dh", HEAD_DIMS)
@@ -107,8 +78,8 @@ def test_attention_hd_rows_sum_to_one(ops, dh):
     g = torch.Generator().manual_seed(9)
     qkv = torch.randn(B * N, 3 * H * dh, generator=g) * 2.0
     qkv[:, 2 * H * dh:] = 1.0
-    o = ops.attention(_bf(qkv).cuda(), B, N, H, head_dim=dh)
-    _assert_close(o, torch.ones(B * N, H * dh), 0.0, 4e-3, f"rows sum to one dh{dh}")
+    o = ops.attention(bf(qkv).cuda(), B, N, H, head_dim=dh)
+    assert_close(o, torch.ones(B * N, H * dh), 0.0, 4e-3, f"rows sum to one dh{dh}")
 
 
 @pytest.mark.parametrize("dh", HEAD_DIMS)
@@ -117,7 +88,7 @@ def test_attention_hd_sequence_output_does_not_depend_on_the_batch(ops, dh, N):
     H = 2
     B = 300  # 600 items
     g = torch.Generator().manual_seed(dh + N)
-    qkv = _bf(torch.randn(B * N, 3 * H * dh, generator=g)).cuda()
+    qkv = bf(torch.randn(B * N, 3 * H * dh, generator=g)).cuda()
     full = ops.attention(qkv, B, N, H, head_dim=dh)
     for b in (0, 1, 157, B - 1):
         alone = ops.attention(qkv[b * N:(b + 1) * N].contiguous(), 1, N, H, head_dim=dh)
@@ -134,7 +105,7 @@ def test_attention_hd_at_head_dim_64_is_vdr_op_attention(ops, B, N, H):
     from vdr.ops import _s
     lib = vdr.load()
     g = torch.Generator().manual_seed(B + N)
-    qkv = _bf(torch.randn(B * N, 3 * H * 64, generator=g)).cuda()
+    qkv = bf(torch.randn(B * N, 3 * H * 64, generator=g)).cuda()
     for variant in (0, 1, 3):
         a = torch.empty((B * N, H * 64), dtype=torch.bfloat16, device="cuda")
         b = torch.full_like(a, 5.0)
@@ -147,38 +118,6 @@ def test_attention_hd_at_head_dim_64_is_vdr_op_attention(ops, B, N, H):
 
 
 # ---- models ---------------------------------------------------------------------------------------------
-def _rel_l2(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def _min_cos(a, b):
-    a, b = a.double().reshape(-1, a.shape[-1]), b.double().reshape(-1, b.shape[-1])
-    return torch.nn.functional.cosine_similarity(a, b, dim=-1).min().item()
-
-
-def gate_l2(layers):
-    return 4e-3 + 3e-3 * math.sqrt(max(layers, 1))
-
-
-def _gate(got, ref, ref_emul, l2, what):
-    got = got.float().cpu()
-    assert torch.isfinite(got).all(), what
-    r32, re, c = _rel_l2(got, ref), _rel_l2(got, ref_emul), _min_cos(got, ref)
-    print(f"{what}: relL2 vs fp32 {r32:.3e}  vs bf16-emulated {re:.3e}  min cos {c:.6f}")
-    assert c >= 0.999 and r32 <= l2 and re <= l2, (what, r32, re, c)
-
-
-def _engine(cfg, w):
-    import vdr
-    vc = vdr.VdrConfig(img=cfg.img, patch=cfg.patch, in_chans=cfg.in_chans, dim=cfg.dim, heads=cfg.heads, layers=cfg.layers,
-                       mlp_hidden=cfg.mlp_hidden, act=cfg.act, pre_ln=cfg.pre_ln, layerscale=cfg.layerscale,
-                       has_cls=cfg.has_cls, has_pos=cfg.has_pos, input_ln=cfg.input_ln, ln_eps=cfg.ln_eps)
-    e = vdr.Engine(vc)
-    e.load_weights(w)
-    return e
-
-
 def _reference_state_dict(w, layers):
     sd = {"cls_token": w["cls_token"], "norm.weight": w["input_norm.weight"], "norm.bias": w["input_norm.bias"]}
     for i in range(layers):
@@ -214,7 +153,7 @@ def test_golden_reference_classifier_at_head_dim(golden_dir, tag):
     buf.seek(0)
     m.load_state_dict(torch.load(buf, map_location="cuda", weights_only=True))
     logits, cls = m(x.cuda())
-    _gate(cls, torch.from_numpy(g["cls"]), emu["cls"], gate_l2(layers), f"golden postln_{tag} cls")
+    check_parity(cls, torch.from_numpy(g["cls"]), f"golden postln_{tag} cls", gate_l2(layers), emu["cls"])
     err = (logits.cpu() - torch.from_numpy(g["logits"])).abs().max().item()
     assert err < 3e-2, f"logits max abs err {err}"
 
@@ -237,7 +176,7 @@ def test_golden_reference_bimodal_classifier_at_head_dims(golden_dir):
             want = torch.from_numpy(g[f"{mode}_{name}"])
             assert o.shape == want.shape, (mode, name)
             if name.startswith("cls"):
-                r, c = _rel_l2(o.cpu(), want), _min_cos(o.cpu(), want)
+                r, c = rel_l2(o.cpu(), want), min_cos(o.cpu(), want)
                 print(f"bimodal_hd {mode} {name}: relL2 {r:.3e} min cos {c:.6f}")
                 assert r <= gate_l2(L) and c >= 0.999, (mode, name, r, c)
             else:
@@ -256,7 +195,7 @@ def test_variable_length_sequences_at_head_dim_96():
     lens = [1, 37, 300, 129, 513, 64]
     cfg = vo.postln_cfg(dim, heads, layers, ffn)
     w = vo.make_weights(cfg, seed=13, scale=0.05)
-    e = _engine(cfg, w)
+    e = hc.engine(cfg, w)
     S = max(lens)
     seqs = [vo.make_tokens(1, n, dim, seed=200 + i)[0] for i, n in enumerate(lens)]
     pad = torch.full((len(lens), S, dim), 3.0)
@@ -266,7 +205,7 @@ def test_variable_length_sequences_at_head_dim_96():
     for i, t in enumerate(seqs):
         ref = vo.forward_tokens(cfg, w, t[None])["cls"][0]
         one = e.forward_tokens(t[None].cuda(), vdr.OUT_CLS).float().cpu()[0]
-        r_ref, r_one = _rel_l2(got[i][None], ref[None]), _rel_l2(got[i][None], one[None])
+        r_ref, r_one = rel_l2(got[i][None], ref[None]), rel_l2(got[i][None], one[None])
         assert r_ref <= gate_l2(layers) and r_one <= 4e-3, (i, lens[i], r_ref, r_one)
     pad2 = pad.clone()
     for i, t in enumerate(seqs):
@@ -290,7 +229,7 @@ def test_small_preln_vit_at_head_dim_96():
     x = vo.make_images(cfg, 5, seed=4)
     ref = vo.forward_images(cfg, w, x)
     emu = vo.forward_images(cfg, w, x, emulate_bf16=True)
-    e = _engine(cfg, w)
+    e = hc.engine(cfg, w)
     g = gate_l2(cfg.layers)
-    _gate(e.forward(x.cuda(), vdr.OUT_CLS), ref["cls"], emu["cls"], g, "vit dh96 cls")
-    _gate(e.forward(x.cuda(), vdr.OUT_DENSE), ref["dense"], emu["dense"], g, "vit dh96 dense")
+    check_parity(e.forward(x.cuda(), vdr.OUT_CLS), ref["cls"], "vit dh96 cls", g, emu["cls"])
+    check_parity(e.forward(x.cuda(), vdr.OUT_DENSE), ref["dense"], "vit dh96 dense", g, emu["dense"])

@@ -3,74 +3,27 @@
 The definition every check uses: the patch rows of the position table are F.interpolate(table.double(), size=(gh, gw),
 mode="bicubic", align_corners=False) rounded to fp32 once (vdr.weights.interpolate_pos_embed); the UNCHANGED oracle fed
 that table is the reference for the models (tests/test_input_size_cpu.py ties it to transformers).  Model gates are the
-project's own (tests/test_model_gpu.py): min row cosine >= 0.999 and rel-L2 <= 4e-3 + 3e-3 sqrt(L) against the fp32 and the
-bf16-emulating oracle; fp8 with _gate_fp8's levels."""
+project's own (tests/model_gates.py): min row cosine >= 0.999 and rel-L2 <= 4e-3 + 3e-3 sqrt(L) against the fp32 and the
+bf16-emulating oracle; fp8 with check_parity_fp8's levels."""
 import ctypes as C
-import math
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import handle_configs as hc
+from model_gates import check_batch_properties, check_parity, check_parity_fp8, gate_l2
 from oracle import vit_oracle as vo
 
 pytestmark = pytest.mark.gpu
 
 
-# ---- helpers (gates restated from tests/test_model_gpu.py) ------------------------------------------------
-def _rel_l2(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def _min_cos(a, b):
-    a, b = a.double().reshape(-1, a.shape[-1]), b.double().reshape(-1, b.shape[-1])
-    return torch.nn.functional.cosine_similarity(a, b, dim=-1).min().item()
-
-
-def gate_l2(layers):
-    return 4e-3 + 3e-3 * math.sqrt(max(layers, 1))
-
-
-def _gate(got, ref, ref_emul, l2_fp32, l2_emul, what):
-    got = got.float().cpu()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    assert torch.isfinite(got).all(), what
-    r32, re, c = _rel_l2(got, ref), _rel_l2(got, ref_emul), _min_cos(got, ref)
-    print(f"{what}: relL2 vs fp32 {r32:.3e}  vs bf16-emulated {re:.3e}  min cos {c:.6f}")
-    assert c >= 0.999, f"{what}: min cosine {c}"
-    assert r32 <= l2_fp32, f"{what}: rel L2 vs fp32 oracle {r32}"
-    assert re <= l2_emul, f"{what}: rel L2 vs bf16-emulating oracle {re}"
-
-
-def _gate_fp8(got, ref, ref_mx, layers, what):
-    got = got.float().cpu()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    assert torch.isfinite(got).all(), what
-    r32, rmx, c = _rel_l2(got, ref), _rel_l2(got, ref_mx), _min_cos(got, ref)
-    print(f"{what}: relL2 vs fp32 {r32:.3e}  vs MX-emulating oracle {rmx:.3e}  min cos {c:.6f}")
-    assert c >= 0.99, f"{what}: min cosine {c}"
-    gate = 4e-2 + 4e-2 * math.sqrt(layers)
-    assert r32 <= gate, f"{what}: rel L2 vs fp32 oracle {r32}"
-    assert rmx <= gate, f"{what}: rel L2 vs MX-emulating oracle {rmx}"
-
-
-def _vc(cfg: vo.VitCfg, layers=None, **kw):
-    import vdr
-    return vdr.VdrConfig(img=cfg.img, patch=cfg.patch, in_chans=cfg.in_chans, dim=cfg.dim, heads=cfg.heads,
-                         layers=cfg.layers if layers is None else layers, mlp_hidden=cfg.mlp_hidden, act=cfg.act,
-                         pre_ln=cfg.pre_ln, layerscale=cfg.layerscale, has_cls=cfg.has_cls, has_pos=cfg.has_pos,
-                         input_ln=cfg.input_ln, ln_eps=cfg.ln_eps, **kw)
-
-
+# ---- helpers ------------------------------------------------------------------------------------------------
 def _engine(cfg, w, size=None, layers=None, **kw):
     """An engine of cfg's weights (truncated to `layers` blocks), told `size` = (H, W) when given."""
-    import vdr
     L = cfg.layers if layers is None else layers
-    keep = {k: v for k, v in w.items() if not k.startswith("blocks.") or int(k.split(".")[1]) < L}
-    e = vdr.Engine(_vc(cfg, L, **kw))
-    e.load_weights(keep)
+    e = hc.engine(cfg, hc.first_blocks(w, L), layers=L, **kw)
     if size is not None:
         e.set_input_size(*size)
     return e
@@ -83,7 +36,7 @@ def _images(batch, H, W, seed, chans=3):
     return x.to(torch.bfloat16).float()
 
 
-def _sized(cfg, w, size):
+def _weights_at(cfg, w, size):
     """The weights the oracle gets at `size`: pos_embed resampled in float64, rounded once."""
     from vdr.weights import interpolate_pos_embed
     ws = dict(w)
@@ -99,7 +52,7 @@ def _sizes(cfg):
 
 
 SMALL = {  # tests/test_model_gpu.py
-    "tiny_p8": vo.VitCfg(32, 8, 3, 64, 1, 2, 128),
+    "tiny_p8": hc.TINY,
     "p16_d128": vo.VitCfg(64, 16, 3, 128, 2, 3, 512),
     "p14_d192": vo.VitCfg(56, 14, 3, 192, 3, 2, 768),
     "dinov2_swiglu_ls": vo.VitCfg(56, 14, 3, 128, 2, 2, 320 + 64, act="swiglu", layerscale=True),
@@ -207,7 +160,7 @@ def test_small_models_at_other_sizes(name, switch):
     B = 5
     for k, size in enumerate(_sizes(cfg)):
         x = _images(B, *size, seed=10 + k)
-        ws = _sized(cfg, w, size)
+        ws = _weights_at(cfg, w, size)
         ref = vo.forward_images(cfg, ws, x)
         emu = vo.forward_images(cfg, ws, x, emulate_bf16="mx" if fp8 else True)
         e.set_input_size(*size)
@@ -218,11 +171,11 @@ def test_small_models_at_other_sizes(name, switch):
             tag = f"{name} {switch} {size[0]}x{size[1]} {'bf16' if dt == torch.bfloat16 else 'fp32'} pixels"
             for mode, key in ((vdr.OUT_CLS, "cls"), (vdr.OUT_DENSE, "dense"), (vdr.OUT_TOKENS, "tokens")):
                 if fp8:
-                    _gate_fp8(e.forward(xd, mode), ref[key], emu[key], cfg.layers, f"{tag} {key}")
+                    check_parity_fp8(e.forward(xd, mode), ref[key], emu[key], cfg.layers, f"{tag} {key}")
                 else:
-                    _gate(e.forward(xd, mode), ref[key], emu[key], g, g, f"{tag} {key}")
+                    check_parity(e.forward(xd, mode), ref[key], f"{tag} {key}", g, emu[key])
             pe_emu = vo.forward_images(cfg, ws, x, emulate_bf16=True)["patch_embed"] if fp8 else emu["patch_embed"]
-            _gate(e.forward(xd, vdr.OUT_PATCH_EMBED), ref["patch_embed"], pe_emu, 4e-3, 4e-3, f"{tag} patch_embed")
+            check_parity(e.forward(xd, vdr.OUT_PATCH_EMBED), ref["patch_embed"], f"{tag} patch_embed", 4e-3, pe_emu)
 
 
 # ---- 4. token counts across the attention launcher's classes -----------------------------------------------------
@@ -233,7 +186,7 @@ def test_token_counts_across_the_attention_classes(size, N):
     cfg = vo.VitCfg(96, 16, 3, 128, 2, 2, 512)
     w = vo.make_weights(cfg, seed=8, scale=0.05)
     x = _images(3, *size, seed=9)
-    ws = _sized(cfg, w, size)
+    ws = _weights_at(cfg, w, size)
     assert ws["pos_embed"].shape[1] == N
     ref = vo.forward_images(cfg, ws, x)
     emu = vo.forward_images(cfg, ws, x, emulate_bf16=True)
@@ -242,7 +195,7 @@ def test_token_counts_across_the_attention_classes(size, N):
     g = gate_l2(cfg.layers)
     for dt in (torch.float32, torch.bfloat16):
         for mode, key in ((vdr.OUT_CLS, "cls"), (vdr.OUT_TOKENS, "tokens")):
-            _gate(e.forward(x.cuda().to(dt), mode), ref[key], emu[key], g, g, f"N={N} {size} {dt} {key}")
+            check_parity(e.forward(x.cuda().to(dt), mode), ref[key], f"N={N} {size} {dt} {key}", g, emu[key])
 
 
 # ---- 5. the transformers fixtures on the device -----------------------------------------------------------------
@@ -259,9 +212,9 @@ def test_transformers_fixtures_at_other_sizes(golden_dir, name):
     for k, (H, W) in enumerate([tuple(int(v) for v in s) for s in g["sizes"]]):
         x = torch.rand((int(g["batch"]), 3, H, W), generator=torch.Generator().manual_seed(int(g["xseed"]) + k), dtype=torch.float32)
         want = torch.from_numpy(g[f"tokens_{H}x{W}"])
-        emu = vo.forward_images(cfg, _sized(cfg, w, (H, W)), x, emulate_bf16=True)["tokens"]
+        emu = vo.forward_images(cfg, _weights_at(cfg, w, (H, W)), x, emulate_bf16=True)["tokens"]
         e.set_input_size(H, W)
-        _gate(e.forward(x.cuda(), vdr.OUT_TOKENS), want, emu, gl, gl, f"{name} {H}x{W} tokens")
+        check_parity(e.forward(x.cuda(), vdr.OUT_TOKENS), want, f"{name} {H}x{W} tokens", gl, emu)
 
 
 # ---- 6. the DINOv2-style outputs at a rectangular size ------------------------------------------------------------
@@ -284,8 +237,8 @@ def test_layers_maps_and_dynamic_size_at_a_rectangular_size():
                 assert torch.equal(t, trunc.forward(x, sp.mode, sp.dtype)), (i, sp.mode, sp.dtype)
     assert not torch.equal(got[0], got[6])
     # attention maps follow N' and (gh, gw); rows sum to 1 (tests/test_attn_maps_gpu.py: atol 1e-5)
-    static = VitDescriptorModel(_vc(cfg), w).set_input_size(*size)
-    dyn = VitDescriptorModel(_vc(cfg), w, dynamic_size=True)
+    static = VitDescriptorModel(hc.vit_config(cfg), w).set_input_size(*size)
+    dyn = VitDescriptorModel(hc.vit_config(cfg), w, dynamic_size=True)
     assert static.input_size == size and static.grid == (gh, gw) and dyn.input_size == (56, 56)
     last = static.get_last_selfattention(x)
     assert last.shape == (4, cfg.heads, N, N)
@@ -308,7 +261,7 @@ def test_layers_maps_and_dynamic_size_at_a_rectangular_size():
     assert vdr.extract_dense(dyn, x).shape == (4, gh, gw, cfg.dim)
     # ... and goes back to the native size on its own: bitwise a model that never moved
     x0 = vo.make_images(cfg, 3, seed=23).cuda()
-    assert torch.equal(dyn(x0), VitDescriptorModel(_vc(cfg), w)(x0)) and dyn.input_size == (56, 56)
+    assert torch.equal(dyn(x0), VitDescriptorModel(hc.vit_config(cfg), w)(x0)) and dyn.input_size == (56, 56)
     with pytest.raises(ValueError, match="images must be"):
         static(x0)  # without dynamic_size another shape is refused, as ever
 
@@ -316,7 +269,7 @@ def test_layers_maps_and_dynamic_size_at_a_rectangular_size():
 # ---- 7. batch properties at a new size ---------------------------------------------------------------------------
 @pytest.mark.parametrize("name,size", [("p16_d128", (160, 96)), ("p14_d192", (84, 126))])
 def test_batch_properties_at_a_new_size(name, size):
-    """tests/test_fullsize_gpu.py's _properties: duplicate images give bitwise equal rows, a batch permutation permutes
+    """tests/model_gates.py's check_batch_properties: duplicate images give bitwise equal rows, a batch permutation permutes
     the rows, a row does not depend on the batch it travels in."""
     import vdr
     cfg = SMALL[name]
@@ -327,12 +280,7 @@ def test_batch_properties_at_a_new_size(name, size):
     for dt in (torch.float32, torch.bfloat16):
         xd = x.cuda().to(dt)
         for mode in (vdr.OUT_CLS, vdr.OUT_DENSE):
-            out = e.forward(xd, mode)
-            assert torch.isfinite(out).all()
-            assert torch.equal(out[B - 1], out[1]), "duplicate images must give bitwise equal rows"
-            perm = torch.randperm(B, generator=torch.Generator().manual_seed(B)).cuda()
-            assert torch.equal(e.forward(xd[perm].contiguous(), mode), out[perm]), "batch permutation equivariance"
-            assert torch.equal(e.forward(xd[12:15].contiguous(), mode), out[12:15]), "a row depends on its batch"
+            check_batch_properties(lambda t: e.forward(t, mode), xd)
 
 
 # ---- 8. rectangular patch embedding, integer-exact ------------------------------------------------------------------
@@ -363,15 +311,6 @@ def test_rectangular_patch_embed_integer_exact(p, img, size, D, dt):
 
 
 # ---- 9. full size ---------------------------------------------------------------------------------------------------
-def _check(got, ref, gate, what):
-    got = got.float().cpu().reshape(ref.shape)
-    assert torch.isfinite(got).all(), what
-    r, c = _rel_l2(got, ref), _min_cos(got, ref)
-    print(f"{what}: relL2 vs fp32 oracle {r:.3e} (gate {gate:.3e})  min row cosine {c:.6f} (gate 0.999)")
-    assert c >= 0.999, f"{what}: min cosine {c}"
-    assert r <= gate, f"{what}: rel L2 {r} > {gate}"
-
-
 @pytest.mark.parametrize("size", [(224, 224), (448, 336)])
 def test_vit_small14_native_518_at_other_sizes_full_depth(size):
     """The geometry of a real dinov2_vits14 checkpoint: pos_embed [1, 1370, 384] (518^2, seeded), all 12 blocks, batch 4."""
@@ -382,13 +321,13 @@ def test_vit_small14_native_518_at_other_sizes_full_depth(size):
     w = vo.make_weights(cfg, seed=14)
     assert w["pos_embed"].shape == (1, 1370, 384)
     x = _images(4, *size, seed=15)
-    ref = vo.forward_images(cfg, _sized(cfg, w, size), x)
+    ref = vo.forward_images(cfg, _weights_at(cfg, w, size), x)
     m = vdr.load_model("dinov2_small14_518", weights=w, dynamic_size=True)
     n = (size[0] // 14) * (size[1] // 14)
     dense = m.dense_tokens(x.cuda(), torch.float32)
     assert dense.shape == (4, n, 384) and m.input_size == size
-    _check(dense, ref["dense"], gate_l2(12), f"ViT-S/14 (518 table) at {size} L=12 dense")
-    _check(m(x.cuda()), ref["cls"], gate_l2(12), f"ViT-S/14 (518 table) at {size} L=12 cls")
+    check_parity(dense, ref["dense"], f"ViT-S/14 (518 table) at {size} L=12 dense", gate_l2(12))
+    check_parity(m(x.cuda()), ref["cls"], f"ViT-S/14 (518 table) at {size} L=12 cls", gate_l2(12))
 
 
 def test_vit_base16_at_448_full_depth():
@@ -396,13 +335,13 @@ def test_vit_base16_at_448_full_depth():
     cfg = vo.VitCfg(224, 16, 3, 768, 12, 12, 3072)
     w = vo.make_weights(cfg, seed=16)
     x = _images(8, 448, 448, seed=17)
-    ref = vo.forward_images(cfg, _sized(cfg, w, (448, 448)), x)
+    ref = vo.forward_images(cfg, _weights_at(cfg, w, (448, 448)), x)
     m = vdr.load_model("vit_base16_224", weights=w).set_input_size(448, 448)
     xd = x.cuda().to(torch.bfloat16)
     dense = m.dense_tokens(xd, torch.float32)
     assert dense.shape == (8, 784, 768)
-    _check(dense, ref["dense"], gate_l2(12), "ViT-B/16 at 448^2 L=12 dense")
-    _check(m(xd), ref["cls"], gate_l2(12), "ViT-B/16 at 448^2 L=12 cls")
+    check_parity(dense, ref["dense"], "ViT-B/16 at 448^2 L=12 dense", gate_l2(12))
+    check_parity(m(xd), ref["cls"], "ViT-B/16 at 448^2 L=12 cls", gate_l2(12))
 
 
 # ---- 10. refusals on a live handle -------------------------------------------------------------------------------------
@@ -416,7 +355,7 @@ def test_refusals_on_a_live_handle():
     assert tok.lib.vdr_set_input_size(tok.h, 64, 64) == -7
     cfg = SMALL["p16_d128"]
     w = vo.make_weights(cfg, seed=3, scale=0.05)
-    blank = vdr.Engine(_vc(cfg))
+    blank = vdr.Engine(hc.vit_config(cfg))
     assert blank.lib.vdr_set_input_size(blank.h, 128, 128) == -6  # VDR_ERR_INCOMPLETE: not finalised
     e = _engine(cfg, w)
     lib = e.lib

@@ -12,15 +12,10 @@ import pytest
 import torch
 
 import kmeans_ref as kr
+from fixtures import lib  # noqa: F401
 
 GOLDENS = ("kmeans_sk_130x32", "kmeans_sk_333x96", "kmeans_sk_520x416")
 INERTIA_WORST = 1.42e-7  # README_kmeans.md: the worst relative distance of the fp32 emulation's inertia from sklearn's
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from vdr import _lib
-    return _lib.load()
 
 
 @pytest.mark.parametrize("name", GOLDENS)

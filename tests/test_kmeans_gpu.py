@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import kmeans_ref as kr
+from fixtures import ops  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -36,12 +37,6 @@ CASES = ((1,          1,    32,  1),
          (129,        5,    96,  3))
 GOLDENS = ("kmeans_sk_130x32", "kmeans_sk_333x96", "kmeans_sk_520x416")
 INERTIA_GATE = 4 * 1.42e-7  # README_kmeans.md: four times the worst relative distance the fp32 emulation measures against sklearn
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from vdr import ops
-    return ops
 
 
 @pytest.fixture(scope="module")

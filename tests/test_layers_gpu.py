@@ -6,11 +6,12 @@ normalised output bit for bit.  The mean-pooled output is gated against the floa
 the gate is tight enough to reject pooling that counts the CLS row, drops a patch row or divides by n + 1 (each an
 O(1/n) error), and the test shows that it does."""
 import ctypes as C
-import math
 
 import pytest
 import torch
 
+import handle_configs as hc
+from model_gates import check_parity, gate_l2
 from oracle import vit_oracle as vo
 
 pytestmark = pytest.mark.gpu
@@ -18,22 +19,10 @@ pytestmark = pytest.mark.gpu
 MODES = ("cls", "dense", "tokens")
 
 
-def _vc(cfg: vo.VitCfg, layers=None, **kw):
-    import vdr
-    return vdr.VdrConfig(img=cfg.img, patch=cfg.patch, in_chans=cfg.in_chans, dim=cfg.dim, heads=cfg.heads,
-                         layers=cfg.layers if layers is None else layers, mlp_hidden=cfg.mlp_hidden, act=cfg.act,
-                         pre_ln=cfg.pre_ln, layerscale=cfg.layerscale, has_cls=cfg.has_cls, has_pos=cfg.has_pos,
-                         input_ln=cfg.input_ln, ln_eps=cfg.ln_eps, **kw)
-
-
 def _engine(cfg, w, layers=None, **kw):
     """An engine of cfg's weights truncated to `layers` blocks (load_weights is strict: only blocks 0 .. layers-1)."""
-    import vdr
     L = cfg.layers if layers is None else layers
-    keep = {k: v for k, v in w.items() if not k.startswith("blocks.") or int(k.split(".")[1]) < L}
-    e = vdr.Engine(_vc(cfg, L, **kw))
-    e.load_weights(keep)
-    return e
+    return hc.engine(cfg, hc.first_blocks(w, L), layers=L, **kw)
 
 
 def _mode(name):
@@ -231,7 +220,7 @@ def test_refusals_with_a_real_handle_leave_the_output_untouched():
         return lib.vdr_forward_layers(eng.h, x.data_ptr(), 0, 2, C.byref(o), 1, ws.data_ptr(), ws.numel(), None)
     for kw in (dict(layer=2), dict(layer=-1), dict(ld=100), dict(ld=1)):
         assert call(e, **kw) == -1, kw
-    nocls = vdr.Engine(_vc(vo.VitCfg(64, 16, 3, 128, 2, 2, 512, has_cls=False)))
+    nocls = vdr.Engine(hc.vit_config(vo.VitCfg(64, 16, 3, 128, 2, 2, 512, has_cls=False)))
     assert call(nocls) == -1 and b"cls" in lib.vdr_last_error(nocls.h)
     for vc in (vdr.ARCHS["medsam"], vdr.VdrConfig(64, 16, 3, 128, 2, 0, 512),
                vdr.VdrConfig(img=0, patch=0, in_chans=0, dim=128, heads=2, layers=2, mlp_hidden=512, pre_ln=False, has_pos=False),
@@ -244,14 +233,6 @@ def test_refusals_with_a_real_handle_leave_the_output_untouched():
     assert not (out[:, :128] == 7.0).all() and (out[:, 128:] == 7.0).all()
 
 
-def _gate(got, ref, layers, what):
-    got, ref = got.double().cpu(), ref.double()
-    rel = ((got - ref).norm() / ref.norm()).item()
-    cos = torch.nn.functional.cosine_similarity(got.reshape(-1, got.shape[-1]), ref.reshape(-1, ref.shape[-1]), dim=-1).min().item()
-    print(f"{what}: relL2 {rel:.3e} min cos {cos:.6f}")
-    assert cos >= 0.999 and rel <= 4e-3 + 3e-3 * math.sqrt(max(layers, 1)), what
-
-
 def test_python_api_matches_dinov2_semantics_against_the_oracle():
     import dataclasses
 
@@ -259,7 +240,7 @@ def test_python_api_matches_dinov2_semantics_against_the_oracle():
     cfg = vo.VitCfg(112, 14, 3, 192, 3, 5, 512, act="swiglu", layerscale=True)
     w = vo.make_weights(cfg, seed=101, scale=0.05)
     x = vo.make_images(cfg, 3, seed=102)
-    model = vdr.VitDescriptorModel(_vc(cfg), w)
+    model = vdr.VitDescriptorModel(hc.vit_config(cfg), w)
     ref = {i: vo.forward_images(dataclasses.replace(cfg, layers=i + 1), w, x) for i in range(cfg.layers)}
     g, D, n = cfg.img // cfg.patch, cfg.dim, cfg.n_patches
     # n as an int: the last n blocks, patch tokens only
@@ -267,15 +248,15 @@ def test_python_api_matches_dinov2_semantics_against_the_oracle():
     assert isinstance(outs, tuple) and len(outs) == 2
     for t, i in zip(outs, (3, 4)):
         assert t.shape == (3, n, D) and t.dtype == torch.float32
-        _gate(t, ref[i]["dense"], i + 1, f"get_intermediate_layers block {i}")
+        check_parity(t, ref[i]["dense"], f"get_intermediate_layers block {i}", gate_l2(i + 1))
     # a list of blocks, reshaped, with class tokens: ((patch [B, D, h, w], cls [B, D]), ...) in block order
     outs = model.get_intermediate_layers(x.cuda(), [3, 0], reshape=True, return_class_token=True)
     assert len(outs) == 2 and all(len(p) == 2 for p in outs)
     for (patch, cls), i in zip(outs, (0, 3)):
         assert patch.shape == (3, D, g, g) and cls.shape == (3, D)
         assert patch.is_contiguous()  # DINOv2: reshape(B, h, w, D).permute(0, 3, 1, 2).contiguous()
-        _gate(patch.permute(0, 2, 3, 1).reshape(3, n, D), ref[i]["dense"], i + 1, f"reshaped block {i}")
-        _gate(cls, ref[i]["cls"], i + 1, f"class token block {i}")
+        check_parity(patch.permute(0, 2, 3, 1).reshape(3, n, D), ref[i]["dense"], f"reshaped block {i}", gate_l2(i + 1))
+        check_parity(cls, ref[i]["cls"], f"class token block {i}", gate_l2(i + 1))
     # norm=False: the raw stream (no final norm), against the oracle's stream before its final LayerNorm
     (raw,) = model.get_intermediate_layers(x.cuda(), [2], norm=False)
     normed = model.get_intermediate_layers(x.cuda(), [2])[0]
@@ -287,7 +268,7 @@ def test_python_api_matches_dinov2_semantics_against_the_oracle():
     assert feats.shape == (3, 5 * D) and feats.dtype == torch.float32
     want = torch.cat([ref[i]["cls"] for i in (1, 2, 3, 4)] + [ref[4]["dense"].mean(dim=1)], dim=-1)
     for k in range(5):
-        _gate(feats[:, k * D:(k + 1) * D], want[:, k * D:(k + 1) * D], cfg.layers, f"linear probe slice {k}")
+        check_parity(feats[:, k * D:(k + 1) * D], want[:, k * D:(k + 1) * D], f"linear probe slice {k}", gate_l2(cfg.layers))
     # ... and it is exactly what the DINOv2 recipe computes from this model's own intermediate layers
     li = model.get_intermediate_layers(x.cuda(), 4, return_class_token=True)
     recipe = torch.cat([c for _, c in li] + [li[-1][0].double().mean(dim=1).float()], dim=-1)

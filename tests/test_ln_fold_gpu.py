@@ -12,25 +12,14 @@ import math
 import pytest
 import torch
 
+from fixtures import ops  # noqa: F401
+from ops_checks import BF16_EPS, bf
 from oracle import attn_designs as ad
 from oracle import ln_fold_designs as lf
 
 pytestmark = pytest.mark.gpu
 
 EPS = lf.EPS
-BF16_EPS = 2.0 ** -8
-
-
-@pytest.fixture(scope="module")
-def ops():
-    import vdr  # noqa: F401
-    from vdr import ops as _ops
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return _ops
-
-
-def _bf(x):
-    return x.to(torch.bfloat16)
 
 
 def _nan_part(G, stride):
@@ -59,7 +48,7 @@ def _run_producer(ops, case, variant, resid32=False, stats=False, stride=None):
     if stats:
         kw["stats"] = torch.full((M, 2), float("nan"), device="cuda")
         kw["counters"] = torch.zeros((M + 63) // 64, dtype=torch.int32, device="cuda")
-    y = ops.linear_ln_stats(_bf(x).cuda(), _bf(W).cuda(), b.cuda(), None if resid32 else _bf(resid).cuda(), part, variant,
+    y = ops.linear_ln_stats(bf(x).cuda(), bf(W).cuda(), b.cuda(), None if resid32 else bf(resid).cuda(), part, variant,
                             gamma=None if gamma is None else gamma.cuda(), eps=EPS, **kw)
     return y, part, kw
 
@@ -129,10 +118,10 @@ def test_finalisers_equal_the_float64_formula_bit_for_bit(ops, M):
                 assert int(kw["counters"].abs().sum()) == 0, "counters not left zeroed"
     # the consumer fed the partials (finalised in the GEMM) is bitwise the consumer fed ln_finalize's statistics
     D = 768
-    xr = _bf(torch.randn(M, D, generator=g) + 3).cuda()
+    xr = bf(torch.randn(M, D, generator=g) + 3).cuda()
     part = _partials_of(ops, xr)
     st = ops.ln_finalize(part, M, EPS)
-    Wf = _bf(torch.randn(2304, D, generator=g) * 0.05).cuda()
+    Wf = bf(torch.randn(2304, D, generator=g) * 0.05).cuda()
     cs = Wf.float().sum(1)
     tb = torch.randn(2304, generator=g).cuda()
     for variant in (22, 23, 24, 26, 27, 28):
@@ -151,7 +140,7 @@ def _designed_consumer(ops, M, D, N, epi, variants, swiglu=False, seed=0, M_allo
     rows = M_alloc or M
     xa = torch.full((rows, D), float("nan"))
     xa[:M] = x
-    xg = _bf(xa).cuda()
+    xg = bf(xa).cuda()
     part = _partials_of(ops, xg[:M].contiguous(), stride=M + 64)
     st = torch.full((rows, 2), float("nan"), device="cuda")
     ops.ln_finalize(part, M, EPS, stats=st[:M])
@@ -252,7 +241,7 @@ def test_random_fold_against_float64(ops, name, D, N, epi):
     E = {"bias": EPI_BIAS, "gelu": EPI_BIAS_GELU, "swiglu": EPI_SWIGLU}[epi]
     g = torch.Generator().manual_seed(D + N)
     M = 1000
-    x = _bf(torch.randn(M, D, generator=g) * 1.5 + 0.5 * torch.randn(M, 1, generator=g))
+    x = bf(torch.randn(M, D, generator=g) * 1.5 + 0.5 * torch.randn(M, 1, generator=g))
     W = torch.randn(N, D, generator=g) * 0.05
     b = torch.randn(N, generator=g) * 0.1
     gamma = 1 + 0.2 * torch.randn(D, generator=g)

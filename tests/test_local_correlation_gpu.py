@@ -14,6 +14,7 @@ import torch
 
 import local_corr_ref as lref
 import nn_cosine_ref as nref
+from fixtures import ops  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -21,12 +22,6 @@ GRIDS = ((1, 1), (1, 5), (3, 3), (5, 7), (7, 15), (8, 16), (9, 17), (14, 14), (1
 RADII = (1, 2, 4, 8)
 DIMS = (32, 96, 448)
 PAIRS = 3
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from vdr import ops
-    return ops
 
 
 _CACHE = {}

@@ -11,18 +11,13 @@ import pytest
 import torch
 
 import descriptor_ref as dref
+from fixtures import ops  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 GRIDS = ((1, 1), (2, 3), (7, 5), (10, 11))
 HIERARCHIES = (1, 2, 3)
 WIDTHS = (8, 72, 384)
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from vdr import ops
-    return ops
 
 
 _CACHE = {}

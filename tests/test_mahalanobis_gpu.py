@@ -16,18 +16,13 @@ import pytest
 import torch
 
 import mahalanobis_ref as mr
+from fixtures import ops  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 RS = (1, 127, 128, 129, 300)
 KS = (1, 128, 129, 260)
 DS = (32, 96, 448)
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from vdr import ops
-    return ops
 
 
 _CACHE = {}

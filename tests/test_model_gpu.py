@@ -14,57 +14,21 @@ Stated tolerances (SURVEY.md §8d "Parity gate"), for a model of L layers:
     test_ops_gpu.py pin each kernel to one bf16 rounding of an fp32 reference);
   * golden vectors produced by the reference's own TransformerNoduleClassifier: same gates.
 """
-import math
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import handle_configs as hc
+from model_gates import check_parity, check_parity_fp8, gate_l2, gate_l2_fp8, inject_outlier_channels, min_cos, rel_l2
 from oracle import vit_oracle as vo
 
 pytestmark = pytest.mark.gpu
 
 
-def _rel_l2(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def _min_cos(a, b):
-    a, b = a.double().reshape(-1, a.shape[-1]), b.double().reshape(-1, b.shape[-1])
-    return torch.nn.functional.cosine_similarity(a, b, dim=-1).min().item()
-
-
-def _engine(cfg: vo.VitCfg, w, micro_batch=0, fp8=0, ln_fold=True, full_last_block=False, fp8_cls_bf16=False, resid_fp32=False,
-            ln_fin_fused=False):
-    import vdr
-    vc = vdr.VdrConfig(img=cfg.img, patch=cfg.patch, in_chans=cfg.in_chans, dim=cfg.dim, heads=cfg.heads, layers=cfg.layers,
-                       mlp_hidden=cfg.mlp_hidden, act=cfg.act, pre_ln=cfg.pre_ln, layerscale=cfg.layerscale,
-                       has_cls=cfg.has_cls, has_pos=cfg.has_pos, input_ln=cfg.input_ln, ln_eps=cfg.ln_eps,
-                       micro_batch=micro_batch, fp8=fp8, ln_fold=ln_fold, full_last_block=full_last_block,
-                       fp8_cls_bf16=fp8_cls_bf16, resid_fp32=resid_fp32, ln_fin_fused=ln_fin_fused)
-    e = vdr.Engine(vc)
-    e.load_weights(w)
-    return e
-
-
-def gate_l2(layers):
-    return 4e-3 + 3e-3 * math.sqrt(max(layers, 1))
-
-
-def _gate(got, ref, ref_emul, l2_fp32, l2_emul, what):
-    got = got.float().cpu()
-    assert torch.isfinite(got).all(), what
-    r32, re, c = _rel_l2(got, ref), _rel_l2(got, ref_emul), _min_cos(got, ref)
-    print(f"{what}: relL2 vs fp32 {r32:.3e}  vs bf16-emulated {re:.3e}  min cos {c:.6f}")
-    assert c >= 0.999, f"{what}: min cosine {c}"
-    assert r32 <= l2_fp32, f"{what}: rel L2 vs fp32 oracle {r32}"
-    assert re <= l2_emul, f"{what}: rel L2 vs bf16-emulating oracle {re}"
-
-
 SMALL = {
-    "tiny_p8": vo.VitCfg(32, 8, 3, 64, 1, 2, 128),
+    "tiny_p8": hc.TINY,
     "p16_d128": vo.VitCfg(64, 16, 3, 128, 2, 3, 512),
     "p14_d192": vo.VitCfg(56, 14, 3, 192, 3, 2, 768),
     "dinov2_swiglu_ls": vo.VitCfg(56, 14, 3, 128, 2, 2, 320 + 64, act="swiglu", layerscale=True),
@@ -79,16 +43,16 @@ def test_small_vit_all_outputs(name):
     x = vo.make_images(cfg, 5, seed=4)
     ref = vo.forward_images(cfg, w, x)
     emu = vo.forward_images(cfg, w, x, emulate_bf16=True)
-    e = _engine(cfg, w)
+    e = hc.engine(cfg, w)
     xd = x.cuda()
     g = gate_l2(cfg.layers)
-    _gate(e.forward(xd, vdr.OUT_CLS), ref["cls"], emu["cls"], g, g, f"{name} cls")
-    _gate(e.forward(xd, vdr.OUT_DENSE), ref["dense"], emu["dense"], g, g, f"{name} dense")
-    _gate(e.forward(xd, vdr.OUT_TOKENS), ref["tokens"], emu["tokens"], g, g, f"{name} tokens")
-    _gate(e.forward(xd, vdr.OUT_PATCH_EMBED), ref["patch_embed"], emu["patch_embed"], 4e-3, 4e-3, f"{name} patch_embed")
+    check_parity(e.forward(xd, vdr.OUT_CLS), ref["cls"], f"{name} cls", g, emu["cls"])
+    check_parity(e.forward(xd, vdr.OUT_DENSE), ref["dense"], f"{name} dense", g, emu["dense"])
+    check_parity(e.forward(xd, vdr.OUT_TOKENS), ref["tokens"], f"{name} tokens", g, emu["tokens"])
+    check_parity(e.forward(xd, vdr.OUT_PATCH_EMBED), ref["patch_embed"], f"{name} patch_embed", 4e-3, emu["patch_embed"])
     # bf16 input images and bf16 outputs take the same path
     d16 = e.forward(xd.to(torch.bfloat16), vdr.OUT_DENSE, torch.bfloat16)
-    assert d16.dtype == torch.bfloat16 and _rel_l2(d16.float().cpu(), ref["dense"]) < 3e-2
+    assert d16.dtype == torch.bfloat16 and rel_l2(d16.float().cpu(), ref["dense"]) < 3e-2
 
 
 def test_first_forward_after_finalize_is_graph_capturable():
@@ -127,10 +91,10 @@ def test_micro_batching_does_not_change_results():
     cfg = SMALL["p16_d128"]
     w = vo.make_weights(cfg, seed=5, scale=0.05)
     x = vo.make_images(cfg, 7, seed=6).cuda()
-    a = _engine(cfg, w).forward(x, vdr.OUT_CLS)
-    b = _engine(cfg, w, micro_batch=3).forward(x, vdr.OUT_CLS)
+    a = hc.engine(cfg, w).forward(x, vdr.OUT_CLS)
+    b = hc.engine(cfg, w, micro_batch=3).forward(x, vdr.OUT_CLS)
     assert torch.equal(a, b)
-    one = _engine(cfg, w).forward(x[2:3], vdr.OUT_CLS)
+    one = hc.engine(cfg, w).forward(x[2:3], vdr.OUT_CLS)
     assert torch.equal(a[2:3], one), "a row must not depend on what else is in the batch"
 
 
@@ -142,11 +106,11 @@ def test_vit_tiny16_224_config1():
     x = vo.make_images(cfg, 8, seed=0)
     ref = vo.forward_images(cfg, w, x)
     emu = vo.forward_images(cfg, w, x, emulate_bf16=True)
-    e = _engine(cfg, w)
+    e = hc.engine(cfg, w)
     got = e.forward(x.cuda(), vdr.OUT_CLS)
     assert got.shape == (8, 192) and got.dtype == torch.float32
-    _gate(got, ref["cls"], emu["cls"], gate_l2(12), gate_l2(12), "vit_tiny cls")
-    _gate(e.forward(x.cuda(), vdr.OUT_DENSE), ref["dense"], emu["dense"], gate_l2(12), gate_l2(12), "vit_tiny dense")
+    check_parity(got, ref["cls"], "vit_tiny cls", gate_l2(12), emu["cls"])
+    check_parity(e.forward(x.cuda(), vdr.OUT_DENSE), ref["dense"], "vit_tiny dense", gate_l2(12), emu["dense"])
 
 
 def test_vit_base16_224_headline_config():
@@ -157,10 +121,10 @@ def test_vit_base16_224_headline_config():
     x = vo.make_images(cfg, 4, seed=0)
     ref = vo.forward_images(cfg, w, x)
     emu = vo.forward_images(cfg, w, x, emulate_bf16=True)
-    e = _engine(cfg, w)
+    e = hc.engine(cfg, w)
     got = e.forward(x.cuda().to(torch.bfloat16), vdr.OUT_CLS)
     assert got.shape == (4, 768)
-    _gate(got, ref["cls"], emu["cls"], gate_l2(12), gate_l2(12), "vit_base cls")
+    check_parity(got, ref["cls"], "vit_base cls", gate_l2(12), emu["cls"])
 
 
 def test_vit_large14_336_geometry_dense_tokens():
@@ -173,11 +137,11 @@ def test_vit_large14_336_geometry_dense_tokens():
     x = vo.make_images(cfg, 2, seed=5)
     ref = vo.forward_images(cfg, w, x)
     emu = vo.forward_images(cfg, w, x, emulate_bf16=True)
-    e = _engine(cfg, w)
+    e = hc.engine(cfg, w)
     dense = e.forward(x.cuda().to(torch.bfloat16), vdr.OUT_DENSE, torch.bfloat16)
     assert dense.shape == (2, 576, 1024) and dense.dtype == torch.bfloat16
-    _gate(dense, ref["dense"], emu["dense"], gate_l2(2) + 2e-3, gate_l2(2) + 2e-3, "vit_large14 dense (bf16 out)")
-    _gate(e.forward(x.cuda(), vdr.OUT_CLS), ref["cls"], emu["cls"], gate_l2(2), gate_l2(2), "vit_large14 cls")
+    check_parity(dense, ref["dense"], "vit_large14 dense (bf16 out)", gate_l2(2) + 2e-3, emu["dense"])
+    check_parity(e.forward(x.cuda(), vdr.OUT_CLS), ref["cls"], "vit_large14 cls", gate_l2(2), emu["cls"])
 
 
 def test_dinov2_giant14_geometry_swiglu_layerscale():
@@ -190,27 +154,9 @@ def test_dinov2_giant14_geometry_swiglu_layerscale():
     x = vo.make_images(cfg, 3, seed=7)
     ref = vo.forward_images(cfg, w, x)
     emu = vo.forward_images(cfg, w, x, emulate_bf16=True)
-    e = _engine(cfg, w)
-    _gate(e.forward(x.cuda(), vdr.OUT_CLS), ref["cls"], emu["cls"], gate_l2(2), gate_l2(2), "dinov2_giant14 cls")
-    _gate(e.forward(x.cuda(), vdr.OUT_DENSE), ref["dense"], emu["dense"], gate_l2(2), gate_l2(2), "dinov2_giant14 dense")
-
-
-def _gate_fp8(got, ref, ref_mx, layers, what):
-    """fp8 gates: cosine >= 0.99 per row against the fp32 oracle (the reference has no fp8 path, so
-    this is parity with its fp32 arithmetic) and relative L2 <= 4e-2 + 4e-2 sqrt(L): an e4m3 element carries
-    ~2.5 % rms rounding error, a K-long dot product of two such operands ~3.5 %, diluted by the residual
-    stream, four quantised linears per block (measured 6.9e-2 .. 7.9e-2 at L = 2 .. 3).  The oracle that emulates the same MX-fp8 quantisation points is printed
-    and gated at the same level, not tighter: the quantiser itself is bit-exact (tests/test_ops_gpu.py), but any
-    bf16-level difference upstream moves elements across e4m3 rounding boundaries (6 % each), so two correct
-    runs decorrelate to roughly the quantisation noise itself."""
-    got = got.float().cpu()
-    assert torch.isfinite(got).all(), what
-    r32, rmx, c = _rel_l2(got, ref), _rel_l2(got, ref_mx), _min_cos(got, ref)
-    print(f"{what}: relL2 vs fp32 {r32:.3e}  vs MX-emulating oracle {rmx:.3e}  min cos {c:.6f}")
-    assert c >= 0.99, f"{what}: min cosine {c}"
-    gate = 4e-2 + 4e-2 * math.sqrt(layers)
-    assert r32 <= gate, f"{what}: rel L2 vs fp32 oracle {r32}"
-    assert rmx <= gate, f"{what}: rel L2 vs MX-emulating oracle {rmx}"
+    e = hc.engine(cfg, w)
+    check_parity(e.forward(x.cuda(), vdr.OUT_CLS), ref["cls"], "dinov2_giant14 cls", gate_l2(2), emu["cls"])
+    check_parity(e.forward(x.cuda(), vdr.OUT_DENSE), ref["dense"], "dinov2_giant14 dense", gate_l2(2), emu["dense"])
 
 
 @pytest.mark.parametrize("name", ["p16_d128", "p14_d192", "dinov2_swiglu_ls"])
@@ -224,9 +170,9 @@ def test_fp8_small_vit_all_outputs(name):
     xd = x.cuda()
     for level, mode in ((1, "mx"),):
         emx = vo.forward_images(cfg, w, x, emulate_bf16=mode)
-        e = _engine(cfg, w, fp8=level)
-        _gate_fp8(e.forward(xd, vdr.OUT_CLS), ref["cls"], emx["cls"], cfg.layers, f"{name} fp8={level} cls")
-        _gate_fp8(e.forward(xd, vdr.OUT_DENSE), ref["dense"], emx["dense"], cfg.layers, f"{name} fp8={level} dense")
+        e = hc.engine(cfg, w, fp8=level)
+        check_parity_fp8(e.forward(xd, vdr.OUT_CLS), ref["cls"], emx["cls"], cfg.layers, f"{name} fp8={level} cls")
+        check_parity_fp8(e.forward(xd, vdr.OUT_DENSE), ref["dense"], emx["dense"], cfg.layers, f"{name} fp8={level} dense")
     # the fp8 path is still batch-independent and deterministic
     a = e.forward(xd, vdr.OUT_CLS)
     b = e.forward(xd[[3, 1, 4, 0, 2]], vdr.OUT_CLS)
@@ -245,9 +191,10 @@ def test_fp8_dinov2_giant14_config5_geometry():
         ref = vo.forward_images(cfg, w, x)
         for level, mode in ((1, "mx"),):
             emx = vo.forward_images(cfg, w, x, emulate_bf16=mode)
-            e = _engine(cfg, w, fp8=level)
-            _gate_fp8(e.forward(x.cuda(), vdr.OUT_CLS), ref["cls"], emx["cls"], cfg.layers, f"{tag} fp8={level} cls")
-            _gate_fp8(e.forward(x.cuda(), vdr.OUT_DENSE), ref["dense"], emx["dense"], cfg.layers, f"{tag} fp8={level} dense")
+            e = hc.engine(cfg, w, fp8=level)
+            check_parity_fp8(e.forward(x.cuda(), vdr.OUT_CLS), ref["cls"], emx["cls"], cfg.layers, f"{tag} fp8={level} cls")
+            check_parity_fp8(e.forward(x.cuda(), vdr.OUT_DENSE), ref["dense"], emx["dense"], cfg.layers,
+                             f"{tag} fp8={level} dense")
 
 
 def test_fp8_is_refused_where_it_is_not_implemented():
@@ -268,42 +215,17 @@ def test_layernorm_folding_matches_the_explicit_layernorm_path():
     w["pos_embed"] = w["pos_embed"] + 1.5          # rows with |mean| >> their spread
     x = vo.make_images(cfg, 6, seed=13)
     ref = vo.forward_images(cfg, w, x)
-    fused = _engine(cfg, w).forward(x.cuda(), vdr.OUT_TOKENS)
-    plain = _engine(cfg, w, ln_fold=False).forward(x.cuda(), vdr.OUT_TOKENS)
+    fused = hc.engine(cfg, w).forward(x.cuda(), vdr.OUT_TOKENS)
+    plain = hc.engine(cfg, w, ln_fold=False).forward(x.cuda(), vdr.OUT_TOKENS)
     assert not torch.equal(fused, plain)  # two different code paths really ran
     # rows with mean 1.5 keep fewer bf16 bits for their spread: both paths sit ~1.5x above the usual gate
     g = 1.5 * gate_l2(cfg.layers)
-    r_f, r_p = _rel_l2(fused.cpu(), ref["tokens"]), _rel_l2(plain.cpu(), ref["tokens"])
-    print(f"LN fold: fused {r_f:.3e}  explicit {r_p:.3e}  fused-vs-explicit {_rel_l2(fused.cpu(), plain.cpu()):.3e}")
+    r_f, r_p = rel_l2(fused.cpu(), ref["tokens"]), rel_l2(plain.cpu(), ref["tokens"])
+    print(f"LN fold: fused {r_f:.3e}  explicit {r_p:.3e}  fused-vs-explicit {rel_l2(fused.cpu(), plain.cpu()):.3e}")
     assert r_f <= g and r_p <= g
     assert r_f <= 1.25 * r_p, "folding LayerNorm must not cost accuracy"
-    assert _rel_l2(fused.cpu(), plain.cpu()) <= g
-    assert _min_cos(fused.cpu(), ref["tokens"]) >= 0.999
-
-
-def _inject_outlier_channels(w, layers, dim, seed, fc1_key):
-    """What trained DINOv2-g / SAM checkpoints carry and seeded Gaussian weights do not ("massive activations"): a few
-    LayerNorm gains of 30-100x, and residual-stream channels that sit at 10^2..10^3 in every token.  The columns of the
-    linears that read those channels are scaled down by the same factors, as a trained model's are -- otherwise q.k^T
-    saturates every softmax and ANY bf16 implementation decorrelates from fp32 arithmetic by argmax flips, which would
-    test nothing of this library.  What is left is what the checkpoints stress here: row variances formed as
-    E[x^2] - mean^2 from fp32 partial sums with one term 10^4..10^5 x the others, bf16 rounding of rows whose mean is far
-    from 0, and MX blocks of 32 whose shared e8m0 scale is set by one outlier."""
-    g = torch.Generator().manual_seed(seed)
-    ch = torch.randperm(dim, generator=g)[:5].tolist()
-    gains = {ch[0]: 30.0, ch[1]: 60.0, ch[2]: 100.0}
-    w = {k: v.clone() for k, v in w.items()}
-    w["patch_embed.proj.bias"][ch[3]] += 300.0   # every token carries +300 / -120 in these channels into every block
-    w["patch_embed.proj.bias"][ch[4]] -= 120.0
-    for i in range(layers):
-        for norm, lin in (("norm1", "attn.qkv"), ("norm2", fc1_key)):
-            for c, gain in gains.items():
-                w[f"blocks.{i}.{norm}.weight"][c] *= gain
-                w[f"blocks.{i}.{lin}.weight"][:, c] /= gain
-            # the normalised value of a +300 channel is ~ 300 / sqrt(300^2 / D) = sqrt(D): keep its products ordinary
-            w[f"blocks.{i}.{lin}.weight"][:, ch[3]] /= math.sqrt(dim)
-            w[f"blocks.{i}.{lin}.weight"][:, ch[4]] /= math.sqrt(dim) * 0.4
-    return w, ch
+    assert rel_l2(fused.cpu(), plain.cpu()) <= g
+    assert min_cos(fused.cpu(), ref["tokens"]) >= 0.999
 
 
 def test_outlier_channels_vit_g_geometry():
@@ -312,19 +234,19 @@ def test_outlier_channels_vit_g_geometry():
     import vdr
     big = vo.CONFIGS["dinov2_giant14_224"]
     cfg = vo.VitCfg(big.img, big.patch, 3, big.dim, big.heads, 4, big.mlp_hidden, act=big.act, layerscale=True)
-    w, ch = _inject_outlier_channels(vo.make_weights(cfg, seed=31), cfg.layers, cfg.dim, 32, "mlp.w12")
+    w, ch = inject_outlier_channels(vo.make_weights(cfg, seed=31), cfg.layers, cfg.dim, 32, "mlp.w12")
     x = vo.make_images(cfg, 2, seed=33)
     ref = vo.forward_images(cfg, w, x)
     # the injection does what it says: the residual stream carries the two channels at 10^2..10^3 in every token
     assert ref["tokens"].shape[-1] == cfg.dim
     emu = vo.forward_images(cfg, w, x, emulate_bf16=True)
     g = gate_l2(cfg.layers)
-    fused = _engine(cfg, w).forward(x.cuda(), vdr.OUT_TOKENS)
-    plain = _engine(cfg, w, ln_fold=False).forward(x.cuda(), vdr.OUT_TOKENS)
+    fused = hc.engine(cfg, w).forward(x.cuda(), vdr.OUT_TOKENS)
+    plain = hc.engine(cfg, w, ln_fold=False).forward(x.cuda(), vdr.OUT_TOKENS)
     assert not torch.equal(fused, plain)
-    _gate(fused, ref["tokens"], emu["tokens"], g, g, "outliers ViT-g L4 bf16, LayerNorm folded")
-    _gate(plain, ref["tokens"], emu["tokens"], g, g, "outliers ViT-g L4 bf16, explicit LayerNorm")
-    assert _rel_l2(fused.cpu(), ref["tokens"]) <= 1.25 * _rel_l2(plain.cpu(), ref["tokens"]) + 1e-3, "the fold must not cost accuracy on outlier rows"
+    check_parity(fused, ref["tokens"], "outliers ViT-g L4 bf16, LayerNorm folded", g, emu["tokens"])
+    check_parity(plain, ref["tokens"], "outliers ViT-g L4 bf16, explicit LayerNorm", g, emu["tokens"])
+    assert rel_l2(fused.cpu(), ref["tokens"]) <= 1.25 * rel_l2(plain.cpu(), ref["tokens"]) + 1e-3, "the fold must not cost accuracy on outlier rows"
     # MX-fp8.  Analysed on the CPU with the MX-emulating oracle (the same quantisation points in plain torch fp32:
     # tools/fp8_outlier_analysis.py, profiles/r04_fp8_outlier_analysis.txt), which shows the same numbers as the kernels.
     # Gain outliers alone cost nothing (min cos 0.99724 with, 0.99731 without: e4m3 is a floating-point format).  Residual
@@ -338,17 +260,17 @@ def test_outlier_channels_vit_g_geometry():
     # MLP: vdr_config.fp8_cls_bf16 (below; emulation 0.9986 at 4 blocks, 0.9886 at 40).  Without it this stress case is
     # gated at 0.985 and on agreement with the emulating oracle (a stated deviation: include/vdr.h).
     emx = vo.forward_images(cfg, w, x, emulate_bf16="mx")
-    f8 = _engine(cfg, w, fp8=1).forward(x.cuda(), vdr.OUT_TOKENS).float().cpu()
+    f8 = hc.engine(cfg, w, fp8=1).forward(x.cuda(), vdr.OUT_TOKENS).float().cpu()
     assert torch.isfinite(f8).all()
-    r32, rmx = _rel_l2(f8, ref["tokens"]), _rel_l2(f8, emx["tokens"])
+    r32, rmx = rel_l2(f8, ref["tokens"]), rel_l2(f8, emx["tokens"])
     cos = torch.nn.functional.cosine_similarity(f8.double().reshape(-1, cfg.dim), ref["tokens"].double().reshape(-1, cfg.dim), dim=-1)
-    cos_emx = _min_cos(emx["tokens"], ref["tokens"])
+    cos_emx = min_cos(emx["tokens"], ref["tokens"])
     n_tok = ref["tokens"].shape[1]
     patch_rows = torch.ones(cos.numel(), dtype=torch.bool)
     patch_rows[::n_tok] = False  # row 0 of every image is its CLS token
     print(f"outliers ViT-g L4 MX-fp8: relL2 vs fp32 {r32:.3e}  vs MX-emulating oracle {rmx:.3e}  min cos CLS rows {cos[~patch_rows].min():.6f} "
           f"(MX-emulating oracle {cos_emx:.6f})  patch rows {cos[patch_rows].min():.6f}")
-    gate = 4e-2 + 4e-2 * math.sqrt(cfg.layers)
+    gate = gate_l2_fp8(cfg.layers)
     assert r32 <= gate and rmx <= gate
     assert cos[patch_rows].min() >= 0.99
     assert cos[~patch_rows].min() >= 0.985 and abs(cos[~patch_rows].min().item() - cos_emx) <= 5e-3
@@ -358,15 +280,15 @@ def test_outlier_channels_vit_g_geometry():
         emc = vo.forward_images(cfg, w, x, emulate_bf16="mx")
     finally:
         vo.MX_CLS_MLP_BF16 = False
-    f8c = _engine(cfg, w, fp8=1, fp8_cls_bf16=True).forward(x.cuda(), vdr.OUT_TOKENS).float().cpu()
+    f8c = hc.engine(cfg, w, fp8=1, fp8_cls_bf16=True).forward(x.cuda(), vdr.OUT_TOKENS).float().cpu()
     assert torch.isfinite(f8c).all()
     cosc = torch.nn.functional.cosine_similarity(f8c.double().reshape(-1, cfg.dim), ref["tokens"].double().reshape(-1, cfg.dim), dim=-1)
     cosc_emu = torch.nn.functional.cosine_similarity(emc["tokens"].double().reshape(-1, cfg.dim), ref["tokens"].double().reshape(-1, cfg.dim), dim=-1)
     print(f"outliers ViT-g L4 MX-fp8 + fp8_cls_bf16: min cos CLS rows {cosc[~patch_rows].min():.6f} (emulating oracle "
-          f"{cosc_emu[~patch_rows].min():.6f})  patch rows {cosc[patch_rows].min():.6f}  relL2 vs emulation {_rel_l2(f8c, emc['tokens']):.3e}")
+          f"{cosc_emu[~patch_rows].min():.6f})  patch rows {cosc[patch_rows].min():.6f}  relL2 vs emulation {rel_l2(f8c, emc['tokens']):.3e}")
     assert cosc[~patch_rows].min() >= 0.99 and cosc[patch_rows].min() >= 0.99
     assert abs(cosc[~patch_rows].min().item() - cosc_emu[~patch_rows].min().item()) <= 2e-3
-    assert _rel_l2(f8c, emc["tokens"]) <= gate
+    assert rel_l2(f8c, emc["tokens"]) <= gate
 
 
 def test_outlier_channels_medsam_geometry():
@@ -374,18 +296,18 @@ def test_outlier_channels_medsam_geometry():
     import vdr
     from oracle import sam_oracle as so
     cfg = so.SamCfg(layers=3, global_idx=(2,))
-    w, ch = _inject_outlier_channels(so.make_weights(cfg, seed=41), cfg.layers, cfg.dim, 42, "mlp.fc1")
+    w, ch = inject_outlier_channels(so.make_weights(cfg, seed=41), cfg.layers, cfg.dim, 42, "mlp.fc1")
     x = so.make_images(cfg, 1, seed=43)
     ref = so.sam_forward(cfg, w, x)
     emu = so.sam_forward(cfg, w, x, emulate_bf16=True)
     gr = cfg.grid
-    tok = _sam_engine(cfg, w).forward(x.cuda(), vdr.OUT_TOKENS)
-    _gate(tok, ref["tokens"].reshape(1, gr * gr, cfg.dim), emu["tokens"].reshape(1, gr * gr, cfg.dim), gate_l2(cfg.layers),
-          gate_l2(cfg.layers), "outliers MedSAM L3 bf16 tokens")
+    tok = hc.sam_engine(cfg, w).forward(x.cuda(), vdr.OUT_TOKENS)
+    check_parity(tok, ref["tokens"].reshape(1, gr * gr, cfg.dim), "outliers MedSAM L3 bf16 tokens", gate_l2(cfg.layers),
+                 emu["tokens"].reshape(1, gr * gr, cfg.dim))
     emx = so.sam_forward(cfg, w, x, emulate_bf16="mx")
-    t8 = _sam_engine(cfg, w, fp8=1).forward(x.cuda(), vdr.OUT_TOKENS)
-    _gate_fp8(t8, ref["tokens"].reshape(1, gr * gr, cfg.dim), emx["tokens"].reshape(1, gr * gr, cfg.dim), cfg.layers,
-              "outliers MedSAM L3 MX-fp8 tokens")
+    t8 = hc.sam_engine(cfg, w, fp8=1).forward(x.cuda(), vdr.OUT_TOKENS)
+    check_parity_fp8(t8, ref["tokens"].reshape(1, gr * gr, cfg.dim), emx["tokens"].reshape(1, gr * gr, cfg.dim), cfg.layers,
+                     "outliers MedSAM L3 MX-fp8 tokens")
 
 
 @pytest.mark.parametrize("name", ["p16_d128", "p14_d192", "dinov2_swiglu_ls"])
@@ -400,15 +322,15 @@ def test_cls_rows_only_last_block_bitwise_fp8(name, cls_bf16):
     cfg = SMALL[name]
     w = vo.make_weights(cfg, seed=23, scale=0.05)
     x = vo.make_images(cfg, 7, seed=24).cuda()
-    full = _engine(cfg, w, fp8=1, full_last_block=True, fp8_cls_bf16=cls_bf16)
+    full = hc.engine(cfg, w, fp8=1, full_last_block=True, fp8_cls_bf16=cls_bf16)
     ref_cls = full.forward(x, vdr.OUT_CLS)
     assert torch.equal(ref_cls, full.forward(x, vdr.OUT_TOKENS)[:, 0])
     for mb in (0, 3):
-        got = _engine(cfg, w, fp8=1, micro_batch=mb, fp8_cls_bf16=cls_bf16).forward(x, vdr.OUT_CLS)
+        got = hc.engine(cfg, w, fp8=1, micro_batch=mb, fp8_cls_bf16=cls_bf16).forward(x, vdr.OUT_CLS)
         assert torch.equal(got, ref_cls), f"micro_batch {mb}"
-    assert torch.equal(_engine(cfg, w, fp8=1, fp8_cls_bf16=cls_bf16).forward(x, vdr.OUT_DENSE), full.forward(x, vdr.OUT_DENSE))
+    assert torch.equal(hc.engine(cfg, w, fp8=1, fp8_cls_bf16=cls_bf16).forward(x, vdr.OUT_DENSE), full.forward(x, vdr.OUT_DENSE))
     if cls_bf16:
-        plain = _engine(cfg, w, fp8=1, full_last_block=True).forward(x, vdr.OUT_CLS)
+        plain = hc.engine(cfg, w, fp8=1, full_last_block=True).forward(x, vdr.OUT_CLS)
         assert not torch.equal(plain, ref_cls), "fp8_cls_bf16 changed nothing"
         # three forwards in a row through the side stream: same bits every time (the fork / join events are reused)
         for _ in range(3):
@@ -426,14 +348,14 @@ def test_cls_rows_only_last_block_bitwise(name, ln_fold):
     cfg = SMALL[name]
     w = vo.make_weights(cfg, seed=21, scale=0.05)
     x = vo.make_images(cfg, 7, seed=22).cuda()
-    full = _engine(cfg, w, ln_fold=ln_fold, full_last_block=True)
+    full = hc.engine(cfg, w, ln_fold=ln_fold, full_last_block=True)
     ref_cls = full.forward(x, vdr.OUT_CLS)
     assert torch.equal(ref_cls, full.forward(x, vdr.OUT_TOKENS)[:, 0])
     for mb in (0, 3):
-        got = _engine(cfg, w, ln_fold=ln_fold, micro_batch=mb).forward(x, vdr.OUT_CLS)
+        got = hc.engine(cfg, w, ln_fold=ln_fold, micro_batch=mb).forward(x, vdr.OUT_CLS)
         assert torch.equal(got, ref_cls), f"micro_batch {mb}"
     # the other outputs never take the short cut
-    pruned = _engine(cfg, w, ln_fold=ln_fold)
+    pruned = hc.engine(cfg, w, ln_fold=ln_fold)
     assert torch.equal(pruned.forward(x, vdr.OUT_TOKENS), full.forward(x, vdr.OUT_TOKENS))
     assert torch.equal(pruned.forward(x, vdr.OUT_DENSE), full.forward(x, vdr.OUT_DENSE))
 
@@ -443,7 +365,7 @@ def test_streams_and_micro_batches_do_not_change_results():
     cfg = SMALL["p14_d192"]
     w = vo.make_weights(cfg, seed=8, scale=0.05)
     x = vo.make_images(cfg, 9, seed=9).cuda()
-    a = _engine(cfg, w).forward(x, vdr.OUT_DENSE)
+    a = hc.engine(cfg, w).forward(x, vdr.OUT_DENSE)
     vc = vdr.VdrConfig(img=cfg.img, patch=cfg.patch, dim=cfg.dim, heads=cfg.heads, layers=cfg.layers,
                        mlp_hidden=cfg.mlp_hidden, streams=2, micro_batch=2)
     e2 = vdr.Engine(vc)
@@ -462,9 +384,9 @@ def test_golden_reference_class_tokens(golden_dir, tag):
     w = vo.make_weights(cfg, seed=int(g["wseed"]), scale=float(g["wscale"]))
     x = vo.make_tokens(int(g["batch"]), int(g["seq"]), dim, seed=int(g["xseed"]))
     emu = vo.forward_tokens(cfg, w, x, emulate_bf16=True)
-    e = _engine(cfg, w)
+    e = hc.engine(cfg, w)
     cls = e.forward_tokens(x.cuda(), vdr.OUT_CLS)
-    _gate(cls, torch.from_numpy(g["cls"]), emu["cls"], gate_l2(layers), gate_l2(layers), f"golden postln_{tag} cls")
+    check_parity(cls, torch.from_numpy(g["cls"]), f"golden postln_{tag} cls", gate_l2(layers), emu["cls"])
     # the drop-in class: (logits, cls) tuple, state_dict in the reference's own key names
     sd = {"cls_token": w["cls_token"], "norm.weight": w["input_norm.weight"], "norm.bias": w["input_norm.bias"]}
     for i in range(layers):
@@ -512,7 +434,7 @@ def test_variable_length_sequences_match_one_at_a_time(dims, lens):
     dim, heads, layers, ffn = dims
     cfg = vo.postln_cfg(dim, heads, layers, ffn)
     w = vo.make_weights(cfg, seed=13, scale=0.05)
-    e = _engine(cfg, w)
+    e = hc.engine(cfg, w)
     S = max(lens)
     seqs = [vo.make_tokens(1, n, dim, seed=100 + i)[0] for i, n in enumerate(lens)]
     pad = torch.full((len(lens), S, dim), 3.0)  # non-zero padding: it must not leak into any valid row
@@ -522,8 +444,8 @@ def test_variable_length_sequences_match_one_at_a_time(dims, lens):
     for i, t in enumerate(seqs):
         ref = vo.forward_tokens(cfg, w, t[None])["cls"][0]
         one = e.forward_tokens(t[None].cuda(), vdr.OUT_CLS).float().cpu()[0]
-        r_ref = _rel_l2(got[i][None], ref[None])
-        r_one = _rel_l2(got[i][None], one[None])
+        r_ref = rel_l2(got[i][None], ref[None])
+        r_one = rel_l2(got[i][None], one[None])
         assert r_ref <= gate_l2(layers) and r_one <= 4e-3, (i, lens[i], r_ref, r_one)
     # padding content is irrelevant, bitwise
     pad2 = pad.clone()
@@ -532,7 +454,7 @@ def test_variable_length_sequences_match_one_at_a_time(dims, lens):
     assert torch.equal(got, e.forward_tokens(pad2.cuda(), vdr.OUT_CLS, lengths=lens).float().cpu())
     # lengths == S everywhere is the fixed-length path
     full = e.forward_tokens(pad.cuda(), vdr.OUT_CLS, lengths=[S] * len(lens)).float().cpu()
-    assert _rel_l2(full, e.forward_tokens(pad.cuda(), vdr.OUT_CLS).float().cpu()) <= 4e-3
+    assert rel_l2(full, e.forward_tokens(pad.cuda(), vdr.OUT_CLS).float().cpu()) <= 4e-3
     with pytest.raises(ValueError):
         e.forward_tokens(pad.cuda(), vdr.OUT_CLS, lengths=[0] + lens[1:])
 
@@ -545,8 +467,8 @@ def test_golden_transformers_crosscheck(golden_dir, name):
     w = vo.make_weights(cfg, seed=int(g["wseed"]), scale=float(g["wscale"]))
     x = vo.make_images(cfg, int(g["batch"]), seed=int(g["xseed"]))
     emu = vo.forward_images(cfg, w, x, emulate_bf16=True)
-    got = _engine(cfg, w).forward(x.cuda(), vdr.OUT_TOKENS)
-    _gate(got, torch.from_numpy(g["tokens"]), emu["tokens"], gate_l2(cfg.layers), gate_l2(cfg.layers), name)
+    got = hc.engine(cfg, w).forward(x.cuda(), vdr.OUT_TOKENS)
+    check_parity(got, torch.from_numpy(g["tokens"]), name, gate_l2(cfg.layers), emu["tokens"])
 
 
 def test_reference_boundary_protocol():
@@ -568,11 +490,11 @@ def test_reference_boundary_protocol():
     model.model_name = "dinov2"   # the reference assigns the attribute after construction
     f = vdr.get_dense_descriptor(model, x[0].numpy())
     assert f.shape == (14, 14, 192) and f.dtype == np.float32
-    assert _rel_l2(torch.from_numpy(f).reshape(196, 192), ref["patch_embed"][0]) < 1e-2
+    assert rel_l2(torch.from_numpy(f).reshape(196, 192), ref["patch_embed"][0]) < 1e-2
     model.model_name = "medsam"
     f2 = vdr.get_dense_descriptor(model, x[0].numpy())
     assert f2.shape == (14, 14, 192)
-    assert _rel_l2(torch.from_numpy(f2).reshape(196, 192), ref["dense"][0]) < 2e-2
+    assert rel_l2(torch.from_numpy(f2).reshape(196, 192), ref["dense"][0]) < 2e-2
     d = vdr.extract_dense(model, x.cuda())
     assert d.shape == (2, 14, 14, 192)
     np.testing.assert_array_equal(d[0], f2)
@@ -629,7 +551,7 @@ def test_get_dense_descriptor_takes_the_raw_slice():
     want2 = np.transpose(m2.image_encoder(x2).cpu().numpy()[0], (1, 2, 0))
     np.testing.assert_array_equal(f2, want2)
     ref = vo.forward_images(cfg2, w2, x2.cpu())["dense"][0].reshape(16, 16, 64)
-    assert _rel_l2(torch.from_numpy(f2), ref) < 2e-2
+    assert rel_l2(torch.from_numpy(f2), ref) < 2e-2
 
 
 def test_dinov2_reference_mode_loads_a_real_checkpoint_layout():
@@ -657,7 +579,7 @@ def test_dinov2_reference_mode_loads_a_real_checkpoint_layout():
     assert pe.shape == (1, 4096, D) and pe.dtype == torch.float32
     ref = torch.nn.functional.conv2d(x.bfloat16().float(), sd["patch_embed.proj.weight"].bfloat16().float(),
                                      sd["patch_embed.proj.bias"], stride=14).flatten(2).transpose(1, 2)
-    assert _rel_l2(pe.cpu(), ref) < 4e-3
+    assert rel_l2(pe.cpu(), ref) < 4e-3
     f = vdr.get_dense_descriptor(model, x[0].numpy())      # :110-139 -> (64, 64, 384) float32
     assert f.shape == (64, 64, D) and f.dtype == np.float32
     np.testing.assert_array_equal(f.reshape(4096, D), pe[0].cpu().numpy())
@@ -672,7 +594,7 @@ def test_full_batch_properties_at_baseline_size():
     import vdr
     cfg = vo.CONFIGS["vit_base16_224"]
     w = vo.make_weights(cfg, seed=1)
-    e = _engine(cfg, w)
+    e = hc.engine(cfg, w)
     g = torch.Generator().manual_seed(0)
     x = torch.rand(256, 3, 224, 224, generator=g).to(torch.bfloat16).cuda()
     x[17] = x[3]
@@ -686,13 +608,13 @@ def test_full_batch_properties_at_baseline_size():
     assert torch.equal(small, out[100:103])
     # the LayerNorm statistics finalised inside the persistent residual GEMMs (1182 tiles on 512 workgroups, three tile
     # columns per block of rows) instead of by their own launches: the same bits
-    assert torch.equal(_engine(cfg, w, ln_fin_fused=True).forward(x, vdr.OUT_CLS), out)
+    assert torch.equal(hc.engine(cfg, w, ln_fin_fused=True).forward(x, vdr.OUT_CLS), out)
     # The qkv linears of these launches run on tile variant 31 (csrc/gemm_8p.hip: 256-row tiles, one workgroup per CU), those
     # of the 3-image run on the ring4 tiles: the comparison above is 8-phase == ring4 bit for bit, LayerNorm fold included.
     # A batch whose token count is NOT a multiple of 256 (100 images = 19700 rows: 693 tiles, the last row tile 244 rows):
     # the kernel reads the workspace's padding rows behind row M and stores none of them -- every token, fold on and off.
     for fold in (True, False):
-        ef = _engine(cfg, w, ln_fold=fold)
+        ef = hc.engine(cfg, w, ln_fold=fold)
         big = ef.forward(x[:100].contiguous(), vdr.OUT_TOKENS)
         assert torch.isfinite(big.float()).all()
         for lo in (0, 47, 97):
@@ -716,8 +638,8 @@ def test_layernorm_statistics_finalised_inside_the_residual_gemm(name, batch, re
     g = torch.Generator().manual_seed(72)
     x = torch.rand(batch, cfg.in_chans, cfg.img, cfg.img, generator=g).to(torch.bfloat16).cuda()
     for full in (False, True):
-        a = _engine(cfg, w, resid_fp32=resid_fp32, full_last_block=full, ln_fin_fused=True)
-        b = _engine(cfg, w, resid_fp32=resid_fp32, full_last_block=full)
+        a = hc.engine(cfg, w, resid_fp32=resid_fp32, full_last_block=full, ln_fin_fused=True)
+        b = hc.engine(cfg, w, resid_fp32=resid_fp32, full_last_block=full)
         for mode in (vdr.OUT_CLS, vdr.OUT_TOKENS):
             want = b.forward(x, mode)
             assert torch.isfinite(want.float()).all()
@@ -727,7 +649,7 @@ def test_layernorm_statistics_finalised_inside_the_residual_gemm(name, batch, re
         # the profiler sees the difference (launches large enough for the 8-phase qkv / fc1, which read finalised statistics):
         # one ln_finalize launch per forward -- the statistics of the assembled tokens -- instead of two per block
         counts = []
-        for e in (_engine(cfg, w, resid_fp32=resid_fp32, ln_fin_fused=True), _engine(cfg, w, resid_fp32=resid_fp32)):
+        for e in (hc.engine(cfg, w, resid_fp32=resid_fp32, ln_fin_fused=True), hc.engine(cfg, w, resid_fp32=resid_fp32)):
             e.profile(True)
             e.forward(x, vdr.OUT_TOKENS)
             counts.append(e.profile_read().get("layernorm", {}).get("launches", 0))
@@ -736,16 +658,6 @@ def test_layernorm_statistics_finalised_inside_the_residual_gemm(name, batch, re
 
 
 # ---- SAM / MedSAM image encoder (the reference's default backbone) ----------------
-def _sam_engine(cfg, w, fp8=0):
-    import vdr
-    vc = vdr.VdrConfig(img=cfg.img, patch=cfg.patch, in_chans=3, dim=cfg.dim, heads=cfg.heads, layers=cfg.layers,
-                       mlp_hidden=cfg.mlp_hidden, has_cls=False, has_pos=True, ln_eps=cfg.ln_eps, window=cfg.window,
-                       global_blocks=tuple(cfg.global_idx), neck_chans=cfg.out_chans, fp8=fp8)
-    e = vdr.Engine(vc)
-    e.load_weights(w)
-    return e
-
-
 @pytest.mark.parametrize("name,cfgargs,batch", [
     ("grid10_win4_padded", dict(img=160, patch=16, dim=64, heads=1, layers=3, mlp_hidden=128, window=4, global_idx=(1,), out_chans=64), 3),
     ("grid14_win7", dict(img=224, patch=16, dim=128, heads=2, layers=2, mlp_hidden=256, window=7, global_idx=(1,), out_chans=64), 2),
@@ -759,15 +671,15 @@ def test_sam_encoder_small(name, cfgargs, batch):
     x = so.make_images(cfg, batch, seed=22)
     ref = so.sam_forward(cfg, w, x)
     emu = so.sam_forward(cfg, w, x, emulate_bf16=True)
-    e = _sam_engine(cfg, w)
+    e = hc.sam_engine(cfg, w)
     tok = e.forward(x.cuda(), vdr.OUT_TOKENS)
     g = cfg.grid
-    _gate(tok, ref["tokens"].reshape(batch, g * g, cfg.dim), emu["tokens"].reshape(batch, g * g, cfg.dim),
-          gate_l2(cfg.layers), gate_l2(cfg.layers), f"sam {name} tokens")
+    check_parity(tok, ref["tokens"].reshape(batch, g * g, cfg.dim), f"sam {name} tokens", gate_l2(cfg.layers),
+                 emu["tokens"].reshape(batch, g * g, cfg.dim))
     out = e.forward(x.cuda(), vdr.OUT_ENCODER)  # [B, g, g, C] channel-last
     assert out.shape == (batch, g, g, cfg.out_chans)
-    _gate(out, ref["out"].permute(0, 2, 3, 1), emu["out"].permute(0, 2, 3, 1), gate_l2(cfg.layers) + 4e-3,
-          gate_l2(cfg.layers) + 4e-3, f"sam {name} neck output")
+    check_parity(out, ref["out"].permute(0, 2, 3, 1), f"sam {name} neck output", gate_l2(cfg.layers) + 4e-3,
+                 emu["out"].permute(0, 2, 3, 1))
 
 
 @pytest.mark.parametrize("cfgargs,batch", [
@@ -784,13 +696,13 @@ def test_sam_encoder_fp8(cfgargs, batch):
     x = so.make_images(cfg, batch, seed=22)
     ref = so.sam_forward(cfg, w, x)
     emx = so.sam_forward(cfg, w, x, emulate_bf16="mx")
-    e = _sam_engine(cfg, w, fp8=1)
+    e = hc.sam_engine(cfg, w, fp8=1)
     g = cfg.grid
     tok = e.forward(x.cuda(), vdr.OUT_TOKENS)
-    _gate_fp8(tok, ref["tokens"].reshape(batch, g * g, cfg.dim), emx["tokens"].reshape(batch, g * g, cfg.dim), cfg.layers,
-              "sam fp8 tokens")
+    check_parity_fp8(tok, ref["tokens"].reshape(batch, g * g, cfg.dim), emx["tokens"].reshape(batch, g * g, cfg.dim),
+                     cfg.layers, "sam fp8 tokens")
     out = e.forward(x.cuda(), vdr.OUT_ENCODER)
-    _gate_fp8(out, ref["out"].permute(0, 2, 3, 1), emx["out"].permute(0, 2, 3, 1), cfg.layers, "sam fp8 neck output")
+    check_parity_fp8(out, ref["out"].permute(0, 2, 3, 1), emx["out"].permute(0, 2, 3, 1), cfg.layers, "sam fp8 neck output")
     assert torch.equal(out, e.forward(x.cuda(), vdr.OUT_ENCODER))
 
 
@@ -802,10 +714,10 @@ def test_sam_golden_transformers_crosscheck(golden_dir):
                     int(g["window"]), tuple(int(i) for i in g["global_idx"]), int(g["out_chans"]), 1e-6)
     w = so.make_weights(cfg, seed=int(g["wseed"]), scale=float(g["wscale"]))
     x = so.make_images(cfg, int(g["batch"]), seed=int(g["xseed"]))
-    out = _sam_engine(cfg, w).forward(x.cuda(), vdr.OUT_ENCODER).permute(0, 3, 1, 2)
+    out = hc.sam_engine(cfg, w).forward(x.cuda(), vdr.OUT_ENCODER).permute(0, 3, 1, 2)
     want = torch.from_numpy(g["out"])
-    assert _rel_l2(out.cpu(), want) <= gate_l2(cfg.layers) + 4e-3
-    assert _min_cos(out.cpu().permute(0, 2, 3, 1), want.permute(0, 2, 3, 1)) >= 0.999
+    assert rel_l2(out.cpu(), want) <= gate_l2(cfg.layers) + 4e-3
+    assert min_cos(out.cpu().permute(0, 2, 3, 1), want.permute(0, 2, 3, 1)) >= 0.999
 
 
 def test_medsam_vit_b_1024_geometry_and_boundary():
@@ -823,8 +735,8 @@ def test_medsam_vit_b_1024_geometry_and_boundary():
     model = vdr.VitDescriptorModel(vc, w, "medsam")
     enc = model.image_encoder(x.cuda())
     assert enc.shape == (1, 256, 64, 64)
-    assert _rel_l2(enc.cpu(), ref["out"]) <= gate_l2(3) + 4e-3
-    assert _min_cos(enc.cpu().permute(0, 2, 3, 1), ref["out"].permute(0, 2, 3, 1)) >= 0.999
+    assert rel_l2(enc.cpu(), ref["out"]) <= gate_l2(3) + 4e-3
+    assert min_cos(enc.cpu().permute(0, 2, 3, 1), ref["out"].permute(0, 2, 3, 1)) >= 0.999
     f = vdr.get_dense_descriptor(model, x[0].numpy())
     assert f.shape == (64, 64, 256) and f.dtype == np.float32
     np.testing.assert_array_equal(f, np.transpose(enc[0].cpu().numpy(), (1, 2, 0)))
@@ -842,7 +754,7 @@ def test_batch_size_sweep_rows_do_not_depend_on_the_batch(fp8):
     import vdr
     cfg = SMALL["p14_d192"]
     w = vo.make_weights(cfg, seed=5, scale=0.05)
-    e = _engine(cfg, w, fp8=fp8)
+    e = hc.engine(cfg, w, fp8=fp8)
     x = vo.make_images(cfg, 65, seed=6).cuda()
     full_cls = e.forward(x, vdr.OUT_CLS)
     full_dense = e.forward(x, vdr.OUT_DENSE)
@@ -873,7 +785,7 @@ def test_golden_reference_bimodal_classifier(golden_dir, tag):
             want = torch.from_numpy(g[f"{mode}_{name}"])
             assert o.shape == want.shape and o.dtype == torch.float32 and o.is_cuda, (mode, name)
             if name.startswith("cls"):
-                r, c = _rel_l2(o.cpu(), want), _min_cos(o.cpu(), want)
+                r, c = rel_l2(o.cpu(), want), min_cos(o.cpu(), want)
                 print(f"bimodal_{tag} {mode} {name}: relL2 {r:.3e} min cos {c:.6f}")
                 assert r <= gate_l2(L) and c >= 0.999, (mode, name, r, c)
             else:
@@ -903,20 +815,20 @@ def test_resid_fp32_master_copy_of_the_residual_stream(name, ln_fold):
         emu = vo.forward_images(cfg, w, x, emulate_bf16=True)
     finally:
         vo.RESID_FP32 = False
-    e32 = _engine(cfg, w, ln_fold=ln_fold, resid_fp32=True)
-    e16 = _engine(cfg, w, ln_fold=ln_fold)
+    e32 = hc.engine(cfg, w, ln_fold=ln_fold, resid_fp32=True)
+    e16 = hc.engine(cfg, w, ln_fold=ln_fold)
     tok32 = e32.forward(x.cuda(), vdr.OUT_TOKENS).float().cpu()
     tok16 = e16.forward(x.cuda(), vdr.OUT_TOKENS).float().cpu()
-    r32, r16, remu = _rel_l2(tok32, ref["tokens"]), _rel_l2(tok16, ref["tokens"]), _rel_l2(tok32, emu["tokens"])
+    r32, r16, remu = rel_l2(tok32, ref["tokens"]), rel_l2(tok16, ref["tokens"]), rel_l2(tok32, emu["tokens"])
     print(f"{name} fold={ln_fold}: relL2 vs fp32 oracle: bf16 stream {r16:.3e}, fp32 stream {r32:.3e}; fp32 stream vs its emulation {remu:.3e}")
     assert torch.isfinite(tok32).all() and not torch.equal(tok32, tok16)
-    assert r32 <= gate_l2(cfg.layers) and r32 <= 1.05 * r16 and _min_cos(tok32, ref["tokens"]) >= 0.999
+    assert r32 <= gate_l2(cfg.layers) and r32 <= 1.05 * r16 and min_cos(tok32, ref["tokens"]) >= 0.999
     assert remu <= gate_l2(cfg.layers)
-    full = _engine(cfg, w, ln_fold=ln_fold, resid_fp32=True, full_last_block=True)
+    full = hc.engine(cfg, w, ln_fold=ln_fold, resid_fp32=True, full_last_block=True)
     ref_cls = full.forward(x.cuda(), vdr.OUT_CLS)
     assert torch.equal(ref_cls, full.forward(x.cuda(), vdr.OUT_TOKENS)[:, 0])
     for mb in (0, 2):
-        got = _engine(cfg, w, ln_fold=ln_fold, resid_fp32=True, micro_batch=mb).forward(x.cuda(), vdr.OUT_CLS)
+        got = hc.engine(cfg, w, ln_fold=ln_fold, resid_fp32=True, micro_batch=mb).forward(x.cuda(), vdr.OUT_CLS)
         assert torch.equal(got, ref_cls), f"micro_batch {mb}"
     assert torch.equal(e32.forward(x.cuda(), vdr.OUT_DENSE), full.forward(x.cuda(), vdr.OUT_DENSE))
 

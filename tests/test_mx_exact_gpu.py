@@ -16,6 +16,8 @@ import pytest
 import torch
 
 import sam_ops_ref as sr
+from fixtures import ops  # noqa: F401
+from ops_checks import bf
 from oracle import mx_designs as md
 from oracle import mx_oracle as mx
 
@@ -25,18 +27,6 @@ GUARD = 256      # guard bytes either side of a payload or a scale array (keeps 
 QFILL = 0xA5     # prefill of payloads and guards
 SENTINEL = 0x5A  # prefill of scale arrays: no test produces the scale 2^-37
 EPS = 1e-6
-
-
-@pytest.fixture(scope="module")
-def ops():
-    import vdr  # noqa: F401
-    from vdr import ops as _ops
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return _ops
-
-
-def _bf(x):
-    return x.to(torch.bfloat16)
 
 
 def _guarded_mx(ops, rows, K, sfill=SENTINEL):
@@ -68,7 +58,7 @@ def _raw(t):
 
 def _quant(ops, x, sfill=None):
     """x (float, bf16-exact) quantised on the GPU; sfill: the value of the scale bytes outside the valid rows"""
-    t = ops.mx_quantize(_bf(x).cuda())
+    t = ops.mx_quantize(bf(x).cuda())
     if sfill is not None:
         rest = md.unwritten_mask(*x.shape).cuda()
         t.scales[rest] = sfill
@@ -82,7 +72,7 @@ def test_quantiser_raw_bytes(ops, rows, K):
     for name, x in (("edge_blocks", md.edge_blocks(rows, K)), ("random", md.random_rows(rows, K, seed=rows + K))):
         what = f"{name} {rows}x{K}"
         t, qw, sw = _guarded_mx(ops, rows, K)
-        ops.mx_quantize(_bf(x).cuda(), out=t)
+        ops.mx_quantize(bf(x).cuda(), out=t)
         torch.cuda.synchronize()
         want_q, want_s = md.encode(x)
         md.check_bytes_equal(*_raw(t), want_q, want_s, what)
@@ -100,7 +90,7 @@ def test_quantiser_raw_bytes(ops, rows, K):
 def test_layernorm_mx_designed_rows(ops, rows, D):
     c = md.ln_mx_case(rows, D)
     t, qw, sw = _guarded_mx(ops, rows, D)
-    ops.layernorm_mx(_bf(c["x"]).cuda(), c["gamma"].cuda(), c["beta"].cuda(), EPS, out=t)
+    ops.layernorm_mx(bf(c["x"]).cuda(), c["gamma"].cuda(), c["beta"].cuda(), EPS, out=t)
     torch.cuda.synchronize()
     q, s = _raw(t)
     n = md.check_mx_bytes(q, s, c["ref"], md.ln_noise(c), f"layernorm_mx {rows}x{D}")
@@ -119,7 +109,7 @@ def test_layernorm_mx_window_designed_rows(ops, batch, g, ws, D):
     idx, valid = sr.window_index(batch, g, ws)
     rows, wrows = batch * g * g, sr.window_rows(batch, g, ws)
     c = md.ln_mx_case(rows, D)
-    x, gamma, beta = _bf(c["x"]).cuda(), c["gamma"].cuda(), c["beta"].cuda()
+    x, gamma, beta = bf(c["x"]).cuda(), c["gamma"].cuda(), c["beta"].cuda()
     q, s = _raw(ops.layernorm_mx(x, gamma, beta, EPS))
     n = md.check_mx_bytes(q, s, c["ref"], md.ln_noise(c), "layernorm_mx (token order)")
     print(f"layernorm_mx_window {rows}x{D}: {n} of {rows * D} elements excluded")
@@ -187,7 +177,7 @@ def test_linear_mx_bf16_epilogues_exact(ops, variant, kind):
         tail = y[neg].float()
         assert bool((tail == tail[0]).all()) and abs(float(tail[0]) / md.GELU_NEG_TAIL - 1.0) <= 2.0 ** -7, what
     else:
-        r = _bf(c["resid"]).cuda()
+        r = bf(c["resid"]).cuda()
         gam = None if kind == "resid" else c["gamma"].cuda()
         want = c["want_nogamma"] if kind == "resid" else c["want"]
         out = r.clone() if kind == "resid_in_place" else None
@@ -268,7 +258,7 @@ def test_nan_element_in_the_quantiser(ops):
     x = md.random_rows(5, 96, seed=3)
     x[2, 40] = float("nan")
     x[4, 64:] = float("nan")
-    t = ops.mx_quantize(_bf(x).cuda())
+    t = ops.mx_quantize(bf(x).cuda())
     q, s = _raw(t)
     want_q, want_s = md.encode(x, ignore_nan=True)
     nan = torch.isnan(x)
@@ -286,7 +276,7 @@ def test_inf_element_in_the_quantiser(ops):
     x = md.random_rows(5, 96, seed=4)
     x0 = x.clone()
     x[1, 7], x[3, 70] = float("inf"), float("-inf")
-    t = ops.mx_quantize(_bf(x).cuda())
+    t = ops.mx_quantize(bf(x).cuda())
     q, s = _raw(t)
     inf = torch.isinf(x)
     d = t.dequantize().cpu()
@@ -309,8 +299,8 @@ def test_nan_row_in_layernorm_mx(ops):
     x = c["x"].clone()
     x[2, 50] = float("nan")
     g, b = c["gamma"].cuda(), c["beta"].cuda()
-    q0, s0 = _raw(ops.layernorm_mx(_bf(c["x"]).cuda(), g, b, EPS))
-    q, s = _raw(ops.layernorm_mx(_bf(x).cuda(), g, b, EPS))
+    q0, s0 = _raw(ops.layernorm_mx(bf(c["x"]).cuda(), g, b, EPS))
+    q, s = _raw(ops.layernorm_mx(bf(x).cuda(), g, b, EPS))
     keep = torch.arange(5) != 2
     md.check_bytes_equal(q[keep], s[keep], q0[keep], s0[keep], "rows without the NaN")
     assert bool(((q[2] & 0x7F) == 0x7F).all()) and bool((s[2] == 1).all())

@@ -12,18 +12,13 @@ import pytest
 import torch
 
 import nn_cosine_ref as nref
+from fixtures import ops  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = ((1, 1), (5, 3), (127, 129), (128, 128), (130, 257))
 DIMS = (32, 96, 448)
 PAIRS = 3
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from vdr import ops
-    return ops
 
 
 _CACHE = {}

@@ -7,43 +7,14 @@ reference computed from the SAME bf16 inputs the error budget is one bf16 roundi
 """
 import math
 
-import numpy as np
 import pytest
 import torch
 
-from oracle import attn_designs as ad
+from fixtures import ops  # noqa: F401
+from ops_checks import BF16_EPS, assert_close, assert_unbiased, bf, relpos_attn_ref
 from oracle import vit_oracle as vo
 
 pytestmark = pytest.mark.gpu
-
-BF16_EPS = 2.0 ** -8
-
-
-@pytest.fixture(scope="module")
-def ops():
-    import vdr  # noqa: F401
-    from vdr import ops as _ops
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return _ops
-
-
-def _bf(x):
-    return x.to(torch.bfloat16)
-
-
-def _assert_close(got, ref, rtol, atol, what=""):
-    got = got.detach().float().cpu()
-    ref = ref.detach().float().cpu()
-    assert got.shape == ref.shape, (got.shape, ref.shape)
-    assert torch.isfinite(got).all(), f"{what}: non-finite output"
-    err = (got - ref).abs()
-    bound = atol + rtol * ref.abs()
-    bad = err > bound
-    if bad.any():
-        i = torch.nonzero(bad)[0].tolist()
-        raise AssertionError(f"{what}: {int(bad.sum())}/{bad.numel()} outside tol; first at {i}: got "
-                             f"{got[tuple(i)].item():.6g} ref {ref[tuple(i)].item():.6g}; max err {err.max().item():.4g}")
-
 
 # ---- LayerNorm ------------------------------------------------------------------------------------
 @pytest.mark.parametrize("D", [192, 256, 384, 768, 1024, 1536])
@@ -59,9 +30,9 @@ def test_layernorm(ops, D, in_dt, out_dt):
         y = ops.layernorm(x.cuda(), gamma.cuda(), beta.cuda(), eps, out_dt)
         ref = vo.layer_norm(x.float(), gamma, beta, eps)
         if out_dt == torch.float32:
-            _assert_close(y, ref, 2e-5, 2e-5, f"LN D={D}")
+            assert_close(y, ref, 2e-5, 2e-5, f"LN D={D}")
         else:
-            _assert_close(y, ref, BF16_EPS, 1e-3, f"LN D={D}")
+            assert_close(y, ref, BF16_EPS, 1e-3, f"LN D={D}")
 
 
 # ---- Linear (GEMM + epilogues) ----------------------------------------------------------------------
@@ -77,14 +48,14 @@ def test_linear_exact_integers_catches_layout_bugs(ops):
         b = torch.randint(-3, 4, (N,), generator=g).float()
         ref = x @ W.t() + b
         assert ref.abs().max() <= 256
-        y = ops.linear(_bf(x).cuda(), _bf(W).cuda(), b.cuda(), epilogue=EPI_BIAS)
+        y = ops.linear(bf(x).cuda(), bf(W).cuda(), b.cuda(), epilogue=EPI_BIAS)
         assert torch.equal(y.float().cpu(), ref), f"integer GEMM mismatch at {(M, N, K)}"
     # identity activation: y == W^T rows
     K = 128
     x = torch.eye(K)
     W = torch.arange(96 * K).reshape(96, K).float() % 251 - 125
-    y = ops.linear(_bf(x).cuda(), _bf(W).cuda(), None, epilogue=EPI_BIAS)
-    assert torch.equal(y.float().cpu(), _bf(W).float().t())
+    y = ops.linear(bf(x).cuda(), bf(W).cuda(), None, epilogue=EPI_BIAS)
+    assert torch.equal(y.float().cpu(), bf(W).float().t())
 
 
 @pytest.mark.parametrize("packed", [False, True])
@@ -102,14 +73,14 @@ def test_linear_every_tile_variant_exact(ops, variant, packed):
         b = torch.randint(-3, 4, (N,), generator=g).float()
         r = torch.randint(-4, 5, (M, N), generator=g).float()
         ref = x @ W.t() + b
-        Wd = _bf(W).cuda()
+        Wd = bf(W).cuda()
         if packed:
             Wd = ops.pack_linear_weight(Wd)
-        y = ops.linear(_bf(x).cuda(), Wd, b.cuda(), epilogue=EPI_BIAS, variant=variant, packed=packed)
+        y = ops.linear(bf(x).cuda(), Wd, b.cuda(), epilogue=EPI_BIAS, variant=variant, packed=packed)
         # integer sums are exact in fp32; the only rounding is the final one to bf16 (a no-op while |y| <= 256)
-        assert torch.equal(y.float().cpu(), _bf(ref).float()), f"variant {variant} bias {(M, N, K)}"
-        y = ops.linear(_bf(x).cuda(), Wd, b.cuda(), resid=_bf(r).cuda(), epilogue=EPI_BIAS_RESID, variant=variant, packed=packed)
-        assert torch.equal(y.float().cpu(), _bf(ref + r).float()), f"variant {variant} resid {(M, N, K)}"
+        assert torch.equal(y.float().cpu(), bf(ref).float()), f"variant {variant} bias {(M, N, K)}"
+        y = ops.linear(bf(x).cuda(), Wd, b.cuda(), resid=bf(r).cuda(), epilogue=EPI_BIAS_RESID, variant=variant, packed=packed)
+        assert torch.equal(y.float().cpu(), bf(ref + r).float()), f"variant {variant} resid {(M, N, K)}"
 
 
 def test_linear_rejects_unknown_and_ablation_variants(ops):
@@ -130,8 +101,8 @@ def test_linear_full_size_packed_equals_plain_bitwise(ops):
     g = torch.Generator().manual_seed(11)
     M = 50432
     for (N, K, epi) in [(768, 768, EPI_BIAS), (3072, 768, EPI_BIAS_GELU), (768, 3072, EPI_BIAS)]:
-        x = _bf(torch.randn(M, K, generator=g)).cuda()
-        W = _bf(torch.randn(N, K, generator=g) * 0.05).cuda()
+        x = bf(torch.randn(M, K, generator=g)).cuda()
+        W = bf(torch.randn(N, K, generator=g) * 0.05).cuda()
         b = torch.randn(N, generator=g).cuda()
         a = ops.linear(x, W, b, epilogue=epi, variant=22)
         Wp = ops.pack_linear_weight(W)
@@ -152,15 +123,15 @@ def test_linear_8phase_variant_exact_and_bitwise(ops):
         x = torch.randint(-2, 3, (M, K), generator=g).float()
         W = torch.randint(-2, 3, (N, K), generator=g).float()
         b = torch.randint(-3, 4, (N,), generator=g).float()
-        y = ops.linear(_bf(x).cuda(), _bf(W).cuda(), b.cuda(), epilogue=EPI_BIAS, variant=31)
+        y = ops.linear(bf(x).cuda(), bf(W).cuda(), b.cuda(), epilogue=EPI_BIAS, variant=31)
         ref = x.cuda() @ W.cuda().t() + b.cuda()
-        assert torch.equal(y.float(), _bf(ref.cpu()).cuda().float()), (M, N, K)
-        y0 = ops.linear(_bf(x).cuda(), _bf(W).cuda(), None, epilogue=EPI_BIAS, variant=31)  # no bias: the launcher's zeros
-        assert torch.equal(y0.float(), _bf((x.cuda() @ W.cuda().t()).cpu()).cuda().float()), (M, N, K, "no bias")
+        assert torch.equal(y.float(), bf(ref.cpu()).cuda().float()), (M, N, K)
+        y0 = ops.linear(bf(x).cuda(), bf(W).cuda(), None, epilogue=EPI_BIAS, variant=31)  # no bias: the launcher's zeros
+        assert torch.equal(y0.float(), bf((x.cuda() @ W.cuda().t()).cpu()).cuda().float()), (M, N, K, "no bias")
     M = 50432
     for (N, K, epi) in [(2304, 768, EPI_BIAS), (3072, 768, EPI_BIAS_GELU), (1536, 1536, EPI_BIAS), (3072, 768, EPI_BIAS)]:
-        x = _bf(torch.randn(M, K, generator=g)).cuda()
-        W = _bf(torch.randn(N, K, generator=g) * 0.05).cuda()
+        x = bf(torch.randn(M, K, generator=g)).cuda()
+        W = bf(torch.randn(N, K, generator=g) * 0.05).cuda()
         b = torch.randn(N, generator=g).cuda()
         a = ops.linear(x, W, b, epilogue=epi, variant=22)
         y = torch.full_like(a, 7.0)
@@ -168,17 +139,17 @@ def test_linear_8phase_variant_exact_and_bitwise(ops):
             ops.linear(x, W, b, epilogue=epi, variant=31, out=y)
             assert torch.equal(a, y), (N, K, epi)
         assert torch.equal(a, ops.linear(x, ops.pack_linear_weight(W), b, epilogue=epi, variant=26, packed=True)), (N, K, epi)
-    xs = _bf(torch.randn(4096, 768, generator=g)).cuda()
-    Ws = _bf(torch.randn(768, 768, generator=g)).cuda()
+    xs = bf(torch.randn(4096, 768, generator=g)).cuda()
+    Ws = bf(torch.randn(768, 768, generator=g)).cuda()
     for bad in (dict(x=xs, W=Ws),                                           # 48 tiles: not worth a persistent launch
-                dict(x=_bf(torch.randn(256 * 67, 768, generator=g)).cuda(), W=_bf(torch.randn(2304, 768, generator=g)).cuda()),  # 603 tiles = 2.4 rounds: the last one 35 % full
-                dict(x=_bf(torch.randn(50432 + 8, 768, generator=g)).cuda(), W=_bf(torch.randn(2304, 768, generator=g)).cuda()),   # M % 256
-                dict(x=_bf(torch.randn(50432, 768, generator=g)).cuda(), W=_bf(torch.randn(2304 + 64, 768, generator=g)).cuda())):  # N % 256
+                dict(x=bf(torch.randn(256 * 67, 768, generator=g)).cuda(), W=bf(torch.randn(2304, 768, generator=g)).cuda()),  # 603 tiles = 2.4 rounds: the last one 35 % full
+                dict(x=bf(torch.randn(50432 + 8, 768, generator=g)).cuda(), W=bf(torch.randn(2304, 768, generator=g)).cuda()),   # M % 256
+                dict(x=bf(torch.randn(50432, 768, generator=g)).cuda(), W=bf(torch.randn(2304 + 64, 768, generator=g)).cuda())):  # N % 256
         with pytest.raises(RuntimeError):
             ops.linear(bad["x"], bad["W"], None, variant=31)
     with pytest.raises(RuntimeError):
-        big = _bf(torch.randn(50432, 768, generator=g)).cuda()
-        ops.linear(big, _bf(torch.randn(768, 768, generator=g)).cuda(), None, resid=big, epilogue=EPI_BIAS_RESID, variant=31)
+        big = bf(torch.randn(50432, 768, generator=g)).cuda()
+        ops.linear(big, bf(torch.randn(768, 768, generator=g)).cuda(), None, resid=big, epilogue=EPI_BIAS_RESID, variant=31)
 
 
 def test_linear_many_tiles_exact(ops):
@@ -191,8 +162,8 @@ def test_linear_many_tiles_exact(ops):
         W = torch.randint(-2, 3, (N, K), generator=g).float()
         b = torch.randint(-3, 4, (N,), generator=g).float()
         for v, packed in ((0, False), (26, True), (27, True)):
-            Wd = _bf(W).cuda()
-            y = ops.linear(_bf(x).cuda(), ops.pack_linear_weight(Wd) if packed else Wd, b.cuda(), epilogue=EPI_BIAS, variant=v, packed=packed)
+            Wd = bf(W).cuda()
+            y = ops.linear(bf(x).cuda(), ops.pack_linear_weight(Wd) if packed else Wd, b.cuda(), epilogue=EPI_BIAS, variant=v, packed=packed)
             assert torch.equal(y.float().cpu(), x @ W.t() + b), (M, N, K, v)
 
 
@@ -208,10 +179,10 @@ def test_linear_persistent_residual_epilogue_exact(ops):
         W = torch.randint(-2, 3, (N, K), generator=g).float()
         b = torch.randint(-3, 4, (N,), generator=g).float()
         r = torch.randint(-4, 5, (M, N), generator=g).float()
-        Wd = _bf(W).cuda()
-        y = ops.linear(_bf(x).cuda(), ops.pack_linear_weight(Wd), b.cuda(), resid=_bf(r).cuda(), epilogue=EPI_BIAS_RESID, variant=26, packed=True)
+        Wd = bf(W).cuda()
+        y = ops.linear(bf(x).cuda(), ops.pack_linear_weight(Wd), b.cuda(), resid=bf(r).cuda(), epilogue=EPI_BIAS_RESID, variant=26, packed=True)
         assert torch.equal(y.float().cpu(), x @ W.t() + b + r), (M, N, K)
-        y3 = ops.linear(_bf(x).cuda(), Wd, b.cuda(), resid=_bf(r).cuda(), epilogue=EPI_BIAS_RESID, variant=22)
+        y3 = ops.linear(bf(x).cuda(), Wd, b.cuda(), resid=bf(r).cuda(), epilogue=EPI_BIAS_RESID, variant=22)
         assert torch.equal(y, y3)
 
 
@@ -223,27 +194,27 @@ SHAPES = [(197 * 3, 768, 768), (197 * 2 + 5, 2304, 768), (300, 3072, 768), (260,
 def test_linear_bias(ops, M, N, K):
     from vdr import EPI_BIAS
     g = torch.Generator().manual_seed(M + N + K)
-    x = _bf(torch.randn(M, K, generator=g))
-    W = _bf(torch.randn(N, K, generator=g) * 0.05)
+    x = bf(torch.randn(M, K, generator=g))
+    W = bf(torch.randn(N, K, generator=g) * 0.05)
     b = torch.randn(N, generator=g) * 0.1
     ref = x.float() @ W.float().t() + b
     y = ops.linear(x.cuda(), W.cuda(), b.cuda(), epilogue=EPI_BIAS)
-    _assert_close(y, ref, BF16_EPS, 2e-3 * math.sqrt(K / 768), f"linear {M}x{N}x{K}")
+    assert_close(y, ref, BF16_EPS, 2e-3 * math.sqrt(K / 768), f"linear {M}x{N}x{K}")
     y0 = ops.linear(x.cuda(), W.cuda(), None, epilogue=EPI_BIAS)
-    _assert_close(y0, ref - b, BF16_EPS, 2e-3 * math.sqrt(K / 768), "linear nobias")
+    assert_close(y0, ref - b, BF16_EPS, 2e-3 * math.sqrt(K / 768), "linear nobias")
 
 
 @pytest.mark.parametrize("M,N,K", [(197 * 2, 3072, 768), (130, 768, 192)])
 def test_linear_gelu(ops, M, N, K):
     from vdr import EPI_BIAS_GELU
     g = torch.Generator().manual_seed(7)
-    x = _bf(torch.randn(M, K, generator=g))
-    W = _bf(torch.randn(N, K, generator=g) * 0.08)
+    x = bf(torch.randn(M, K, generator=g))
+    W = bf(torch.randn(N, K, generator=g) * 0.08)
     b = torch.randn(N, generator=g) * 0.1
     ref = vo.gelu_erf(x.float() @ W.float().t() + b)
     assert torch.allclose(ref, torch.nn.functional.gelu(x.float() @ W.float().t() + b), atol=1e-5, rtol=1e-5)
     y = ops.linear(x.cuda(), W.cuda(), b.cuda(), epilogue=EPI_BIAS_GELU)
-    _assert_close(y, ref, BF16_EPS, 2e-3, "linear+gelu")
+    assert_close(y, ref, BF16_EPS, 2e-3, "linear+gelu")
 
 
 def test_gelu_tail_accuracy(ops):
@@ -255,25 +226,25 @@ def test_gelu_tail_accuracy(ops):
     # per-column bias sweep: column c gets pre-activation vals[c]
     N = vals.numel()
     Wz = torch.zeros(N, K)
-    y = ops.linear(_bf(torch.zeros(4, K)).cuda(), _bf(Wz).cuda(), vals.cuda(), epilogue=EPI_BIAS_GELU)
+    y = ops.linear(bf(torch.zeros(4, K)).cuda(), bf(Wz).cuda(), vals.cuda(), epilogue=EPI_BIAS_GELU)
     ref = torch.nn.functional.gelu(vals.double()).float().expand(4, N)
-    _assert_close(y, ref, BF16_EPS, 5e-7, "gelu sweep")
+    assert_close(y, ref, BF16_EPS, 5e-7, "gelu sweep")
 
 
 @pytest.mark.parametrize("M,N,K,ls", [(197 * 2, 768, 768, False), (333, 768, 3072, True), (70, 192, 768, False)])
 def test_linear_residual(ops, M, N, K, ls):
     from vdr import EPI_BIAS_RESID
     g = torch.Generator().manual_seed(11)
-    x = _bf(torch.randn(M, K, generator=g))
-    W = _bf(torch.randn(N, K, generator=g) * 0.05)
+    x = bf(torch.randn(M, K, generator=g))
+    W = bf(torch.randn(N, K, generator=g) * 0.05)
     b = torch.randn(N, generator=g) * 0.1
-    r = _bf(torch.randn(M, N, generator=g))
+    r = bf(torch.randn(M, N, generator=g))
     gamma = (1 + 0.2 * torch.randn(N, generator=g)) if ls else None
     lin = x.float() @ W.float().t() + b
     ref = r.float() + (gamma * lin if ls else lin)
     y = ops.linear(x.cuda(), W.cuda(), b.cuda(), resid=r.cuda(), gamma=gamma.cuda() if ls else None,
                    epilogue=EPI_BIAS_RESID)
-    _assert_close(y, ref, BF16_EPS, 3e-3 * math.sqrt(K / 768), "linear+resid")
+    assert_close(y, ref, BF16_EPS, 3e-3 * math.sqrt(K / 768), "linear+resid")
     # in place (y aliases resid), the way the forward uses it
     rr = r.cuda().clone()
     ops.linear(x.cuda(), W.cuda(), b.cuda(), resid=rr, gamma=gamma.cuda() if ls else None, epilogue=EPI_BIAS_RESID, out=rr)
@@ -284,8 +255,8 @@ def test_linear_swiglu(ops):
     from vdr import EPI_SWIGLU
     g = torch.Generator().manual_seed(13)
     M, D, F = 200, 384, 512
-    x = _bf(torch.randn(M, D, generator=g))
-    w12 = _bf(torch.randn(2 * F, D, generator=g) * 0.05)
+    x = bf(torch.randn(M, D, generator=g))
+    w12 = bf(torch.randn(2 * F, D, generator=g) * 0.05)
     b12 = torch.randn(2 * F, generator=g) * 0.1
     y12 = x.float() @ w12.float().t() + b12
     a, b = y12.chunk(2, dim=-1)
@@ -293,7 +264,7 @@ def test_linear_swiglu(ops):
     wp, bp = ops.pack_w12(w12, b12)
     y = ops.linear(x.cuda(), wp.cuda(), bp.cuda(), epilogue=EPI_SWIGLU)
     assert y.shape == (M, F)
-    _assert_close(y, ref, BF16_EPS, 2e-3, "swiglu")
+    assert_close(y, ref, BF16_EPS, 2e-3, "swiglu")
 
 
 # ---- attention ---------------------------------------------------------------------------------------
@@ -304,25 +275,16 @@ def _attn_ref(qkv, B, N, H):
     return o.transpose(1, 2).reshape(B * N, H * 64)
 
 
-def _assert_unbiased(got, ref, what):
-    """beta = <got - ref, ref> / <ref, ref> against the float64 reference, |beta| <= 3e-4 from 30 k outputs on
-    (oracle/attn_designs.py): rounding noise gives ~1e-5; a softmax temperature, P rounding or denominator error moves
-    every output the same way and gives 1e-3 and more, inside the elementwise tolerance"""
-    b = ad.check_unbiased(got.detach().double().cpu(), ref, what)
-    if b is not None:
-        print(f"beta {what}: {b:+.3e}")
-
-
 @pytest.mark.parametrize("B,N,H", [(2, 197, 3), (1, 197, 12), (3, 32, 2), (2, 33, 1), (1, 64, 2), (2, 100, 2),
                                    (1, 224, 1), (2, 257, 2), (1, 288, 1), (1, 5, 1), (2, 51, 4)])
 def test_attention_single_chunk(ops, B, N, H):
     g = torch.Generator().manual_seed(B * 1000 + N)
-    qkv = _bf(torch.randn(B * N, 3 * H * 64, generator=g))
+    qkv = bf(torch.randn(B * N, 3 * H * 64, generator=g))
     ref = _attn_ref(qkv, B, N, H)
     o = ops.attention(qkv.cuda(), B, N, H)
     # P is rounded to bf16 before P.V and the output is stored as bf16: 2^-8 relative on O(1) values
-    _assert_close(o, ref, 2 * BF16_EPS, 6e-3, f"attention B{B} N{N} H{H}")
-    _assert_unbiased(o, ref, f"attention B{B} N{N} H{H}")
+    assert_close(o, ref, 2 * BF16_EPS, 6e-3, f"attention B{B} N{N} H{H}")
+    assert_unbiased(o, ref, f"attention B{B} N{N} H{H}")
 
 
 @pytest.mark.parametrize("B,N,H", [(43, 197, 12), (2, 129, 3), (3, 224, 2), (5, 160, 1), (1, 193, 7)])
@@ -331,23 +293,23 @@ def test_attention_persistent_kernels_match_one_shot_bitwise(ops, B, N, H):
     persistent kernel (2) and the persistent kernel with its loader wave (4; the library's choice from 512 items on --
     (43, 197, 12) is 516).  Same arithmetic in the same order: bitwise equal, and within bf16 of the fp32 reference."""
     g = torch.Generator().manual_seed(B * 131 + N)
-    qkv = _bf(torch.randn(B * N, 3 * H * 64, generator=g))
+    qkv = bf(torch.randn(B * N, 3 * H * 64, generator=g))
     ref = _attn_ref(qkv, B, N, H)
     outs = {v: ops.attention(qkv.cuda(), B, N, H, variant=v) for v in (3, 2, 4, 0)}
     for v in (2, 4, 0):
         assert torch.equal(outs[v], outs[3]), f"variant {v} B{B} N{N} H{H}"
-    _assert_close(outs[0], ref, 2 * BF16_EPS, 6e-3, f"attention(persistent) B{B} N{N} H{H}")
-    _assert_unbiased(outs[0], ref, f"attention(persistent) B{B} N{N} H{H}")
+    assert_close(outs[0], ref, 2 * BF16_EPS, 6e-3, f"attention(persistent) B{B} N{N} H{H}")
+    assert_unbiased(outs[0], ref, f"attention(persistent) B{B} N{N} H{H}")
 
 
 @pytest.mark.parametrize("B,N,H", [(1, 577, 2), (2, 300, 1), (1, 1024, 1), (1, 197, 2), (1, 129, 1)])
 def test_attention_online_softmax_chunks(ops, B, N, H):
     g = torch.Generator().manual_seed(N)
-    qkv = _bf(torch.randn(B * N, 3 * H * 64, generator=g))
+    qkv = bf(torch.randn(B * N, 3 * H * 64, generator=g))
     ref = _attn_ref(qkv, B, N, H)
     o = ops.attention(qkv.cuda(), B, N, H, variant=1)
-    _assert_close(o, ref, 2 * BF16_EPS, 6e-3, f"attention(online) B{B} N{N} H{H}")
-    _assert_unbiased(o, ref, f"attention(online) B{B} N{N} H{H}")
+    assert_close(o, ref, 2 * BF16_EPS, 6e-3, f"attention(online) B{B} N{N} H{H}")
+    assert_unbiased(o, ref, f"attention(online) B{B} N{N} H{H}")
 
 
 def test_attention_rescale_branch_is_exercised(ops):
@@ -359,10 +321,10 @@ def test_attention_rescale_branch_is_exercised(ops):
     q = qkv[:, :64]
     qkv[390, 64:128] = q.mean(0) * 0 + 4.0 * torch.sign(q[7])  # key 390 (4th chunk) aligned with query 7
     qkv[7, :64] = 3.0 * torch.sign(q[7])
-    qkv = _bf(qkv)
+    qkv = bf(qkv)
     ref = _attn_ref(qkv, B, N, H)
     o = ops.attention(qkv.cuda(), B, N, H, variant=1)
-    _assert_close(o, ref, 2 * BF16_EPS, 6e-3, "attention rescale")
+    assert_close(o, ref, 2 * BF16_EPS, 6e-3, "attention rescale")
 
 
 def test_attention_softmax_is_shift_invariant_and_rows_sum_to_one(ops):
@@ -371,8 +333,8 @@ def test_attention_softmax_is_shift_invariant_and_rows_sum_to_one(ops):
     g = torch.Generator().manual_seed(9)
     qkv = torch.randn(B * N, 3 * H * 64, generator=g)
     qkv[:, 2 * H * 64:] = 1.0
-    o = ops.attention(_bf(qkv).cuda(), B, N, H)
-    _assert_close(o, torch.ones(B * N, H * 64), 0.0, 4e-3, "rows sum to one")
+    o = ops.attention(bf(qkv).cuda(), B, N, H)
+    assert_close(o, torch.ones(B * N, H * 64), 0.0, 4e-3, "rows sum to one")
 
 
 # ---- patch embed ---------------------------------------------------------------------------------------
@@ -385,18 +347,18 @@ def test_patch_embed(ops, img, p, D, dt):
     g = torch.Generator().manual_seed(img + D)
     B = 3
     x = torch.rand(B, 3, img, img, generator=g).to(dt)
-    W = _bf(torch.randn(D, 3, p, p, generator=g) * 0.05)
+    W = bf(torch.randn(D, 3, p, p, generator=g) * 0.05)
     b = torch.randn(D, generator=g) * 0.1
     n = (img // p) ** 2
-    ref = torch.nn.functional.conv2d(_bf(x).float(), W.float(), b, stride=p).flatten(2).transpose(1, 2).reshape(B * n, D)
+    ref = torch.nn.functional.conv2d(bf(x).float(), W.float(), b, stride=p).flatten(2).transpose(1, 2).reshape(B * n, D)
     y = ops.patch_embed(x.cuda(), W.cuda(), b.cuda(), p)
-    _assert_close(y, ref, BF16_EPS, 2e-3, f"patch_embed {img}/{p}")
+    assert_close(y, ref, BF16_EPS, 2e-3, f"patch_embed {img}/{p}")
     # with pos-embed and the CLS-row layout the full forward uses (row 0 of every image untouched)
     pos = torch.randn(n + 1, D, generator=g) * 0.02
     y2 = ops.patch_embed(x.cuda(), W.cuda(), b.cuda(), p, pos=pos.cuda(), row_stride=n + 1, row_offset=1)
     y2 = y2.float().cpu().reshape(B, n + 1, D)
     assert torch.equal(y2[:, 0], torch.zeros(B, D))
-    _assert_close(y2[:, 1:].reshape(B * n, D), ref + pos[1:].repeat(B, 1), BF16_EPS, 2e-3, "patch_embed+pos")
+    assert_close(y2[:, 1:].reshape(B * n, D), ref + pos[1:].repeat(B, 1), BF16_EPS, 2e-3, "patch_embed+pos")
 
 
 @pytest.mark.parametrize("img,p,D,B", [(224, 16, 768, 5), (64, 8, 192, 3), (96, 32, 256, 7), (224, 16, 200, 2)])
@@ -413,13 +375,13 @@ def test_patch_embed_gathered_from_images_exact(ops, img, p, D, B):
     ref = torch.nn.functional.conv2d(x, W, b, stride=p).flatten(2).transpose(1, 2).reshape(B * n, D)
     assert ref.abs().max() < 16384  # (bf16 output: compare after the same rounding)
     y = ops.patch_embed(x.bfloat16().cuda(), W.bfloat16().cuda(), b.cuda(), p)
-    assert torch.equal(y.float().cpu(), _bf(ref).float()), f"gathered patch embed {img}/{p}"
+    assert torch.equal(y.float().cpu(), bf(ref).float()), f"gathered patch embed {img}/{p}"
     y_col = ops.patch_embed(x.cuda(), W.bfloat16().cuda(), b.cuda(), p)  # fp32 images: im2col + GEMM
     assert torch.equal(y, y_col)
     pos = torch.randint(-2, 3, (n + 1, D), generator=g).float()
     y2 = ops.patch_embed(x.bfloat16().cuda(), W.bfloat16().cuda(), b.cuda(), p, pos=pos.cuda(), row_stride=n + 1, row_offset=1)
     y2 = y2.float().cpu().reshape(B, n + 1, D)
-    assert torch.equal(y2[:, 1:].reshape(B * n, D), _bf(ref + pos[1:].repeat(B, 1)).float())
+    assert torch.equal(y2[:, 1:].reshape(B * n, D), bf(ref + pos[1:].repeat(B, 1)).float())
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
@@ -435,34 +397,20 @@ def test_patch_embed_p14_exact(ops, dt):
     n = (img // p) ** 2
     ref = torch.nn.functional.conv2d(x, W, b, stride=p).flatten(2).transpose(1, 2).reshape(B * n, D)
     y = ops.patch_embed(x.to(dt).cuda(), W.bfloat16().cuda(), b.cuda(), p)
-    assert torch.equal(y.float().cpu(), _bf(ref).float())
+    assert torch.equal(y.float().cpu(), bf(ref).float())
 
 
 # ---- SAM / MedSAM attention with decomposed relative position bias ------------------------------------
-def _relpos_attn_ref(qkv, rel_h, rel_w, B, S, H):
-    """float64"""
-    from oracle import sam_oracle as so
-    q, k, v = qkv.double().reshape(B, S * S, 3, H, 64).permute(2, 0, 3, 1, 4)
-    attn = (q * 0.125) @ k.transpose(-1, -2)
-    Rh, Rw = so.rel_table(S, rel_h.double()), so.rel_table(S, rel_w.double())
-    rq = q.reshape(B, H, S, S, 64)
-    rh = torch.einsum("bnhwc,hkc->bnhwk", rq, Rh)
-    rw = torch.einsum("bnhwc,wkc->bnhwk", rq, Rw)
-    attn = (attn.view(B, H, S, S, S, S) + rh[..., :, None] + rw[..., None, :]).view(B, H, S * S, S * S)
-    o = torch.softmax(attn, dim=-1) @ v
-    return o.transpose(1, 2).reshape(B * S * S, H * 64)
-
-
 @pytest.mark.parametrize("B,S,H", [(3, 4, 2), (5, 7, 1), (2, 10, 2), (4, 14, 3), (25, 14, 12)])
 def test_attention_relpos_windows(ops, B, S, H):
     g = torch.Generator().manual_seed(S * 100 + B)
-    qkv = _bf(torch.randn(B * S * S, 3 * H * 64, generator=g))
+    qkv = bf(torch.randn(B * S * S, 3 * H * 64, generator=g))
     rel_h = torch.randn(2 * S - 1, 64, generator=g) * 0.1
     rel_w = torch.randn(2 * S - 1, 64, generator=g) * 0.1
-    ref = _relpos_attn_ref(qkv, rel_h, rel_w, B, S, H)
+    ref = relpos_attn_ref(qkv, rel_h, rel_w, B, S, H)
     out = ops.attention_relpos(qkv.cuda(), rel_h.cuda(), rel_w.cuda(), B, S, H)
-    _assert_close(out, ref, 2 * BF16_EPS, 6e-3, f"relpos attention B{B} S{S} H{H}")
-    _assert_unbiased(out, ref, f"relpos attention B{B} S{S} H{H}")
+    assert_close(out, ref, 2 * BF16_EPS, 6e-3, f"relpos attention B{B} S{S} H{H}")
+    assert_unbiased(out, ref, f"relpos attention B{B} S{S} H{H}")
 
 
 def test_attention_relpos_global_grid_64(ops):
@@ -470,13 +418,13 @@ def test_attention_relpos_global_grid_64(ops):
     (two grid rows per chunk) with the bias indexed from registers."""
     B, S, H = 1, 64, 2
     g = torch.Generator().manual_seed(64)
-    qkv = _bf(torch.randn(B * S * S, 3 * H * 64, generator=g))
+    qkv = bf(torch.randn(B * S * S, 3 * H * 64, generator=g))
     rel_h = torch.randn(2 * S - 1, 64, generator=g) * 0.1
     rel_w = torch.randn(2 * S - 1, 64, generator=g) * 0.1
-    ref = _relpos_attn_ref(qkv, rel_h, rel_w, B, S, H)
+    ref = relpos_attn_ref(qkv, rel_h, rel_w, B, S, H)
     out = ops.attention_relpos(qkv.cuda(), rel_h.cuda(), rel_w.cuda(), B, S, H)
-    _assert_close(out, ref, 2 * BF16_EPS, 6e-3, "relpos attention global 64x64")
-    _assert_unbiased(out, ref, "relpos attention global 64x64")
+    assert_close(out, ref, 2 * BF16_EPS, 6e-3, "relpos attention global 64x64")
+    assert_unbiased(out, ref, "relpos attention global 64x64")
 
 
 # ---- MX-fp8 (BASELINE config 5) -------------------------------------------------------------------

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import handle_configs as hc
 from oracle import vit_oracle as vo
 
 TOL = 2e-5
@@ -70,7 +71,7 @@ def test_sdpa_matches_torch():
 
 
 def test_emulated_bf16_close_to_fp32():
-    cfg = vo.VitCfg(32, 8, 3, 64, 1, 2, 128)
+    cfg = hc.TINY
     w = vo.make_weights(cfg, seed=2)
     x = vo.make_images(cfg, 2, seed=2)
     a = vo.forward_images(cfg, w, x)["cls"]

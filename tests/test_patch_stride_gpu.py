@@ -3,65 +3,28 @@
 The definition every model check uses is tests/stride_ref.py: F.conv2d(images, W, b, stride=s), pos_embed's patch rows
 resampled in float64 to the (gh, gw) grid and rounded once, then the UNCHANGED oracle's assemble_tokens / encoder
 (tests/test_patch_stride_cpu.py ties it to the oracle at s == p).  Model gates are the project's own
-(tests/test_input_size_gpu.py): min row cosine >= 0.999 and rel-L2 <= 4e-3 + 3e-3 sqrt(L) against the fp32 and the
+(tests/model_gates.py): min row cosine >= 0.999 and rel-L2 <= 4e-3 + 3e-3 sqrt(L) against the fp32 and the
 bf16-emulating restatement.  The kernel itself is pinned bit for bit: integer data through vdr_op_patch_embed_strided, and
 the shift property of the overlapping grid."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
 import torch
 
+import handle_configs as hc
 import stride_ref as sr
+from model_gates import check_batch_properties, check_parity, gate_l2, rel_l2
+from ops_checks import bf
 from oracle import vit_oracle as vo
 
 pytestmark = pytest.mark.gpu
 
 
-# ---- helpers (gates restated from tests/test_input_size_gpu.py, unchanged) -----------------------------------------
-def _rel_l2(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def _min_cos(a, b):
-    a, b = a.double().reshape(-1, a.shape[-1]), b.double().reshape(-1, b.shape[-1])
-    return torch.nn.functional.cosine_similarity(a, b, dim=-1).min().item()
-
-
-def gate_l2(layers):
-    return 4e-3 + 3e-3 * math.sqrt(max(layers, 1))
-
-
-def _gate(got, ref, ref_emul, l2_fp32, l2_emul, what):
-    got = got.float().cpu()
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    assert torch.isfinite(got).all(), what
-    r32, re, c = _rel_l2(got, ref), _rel_l2(got, ref_emul), _min_cos(got, ref)
-    print(f"{what}: relL2 vs fp32 {r32:.3e}  vs bf16-emulated {re:.3e}  min cos {c:.6f}")
-    assert c >= 0.999, f"{what}: min cosine {c}"
-    assert r32 <= l2_fp32, f"{what}: rel L2 vs fp32 oracle {r32}"
-    assert re <= l2_emul, f"{what}: rel L2 vs bf16-emulating oracle {re}"
-
-
-def _bf(t):
-    return t.to(torch.bfloat16)
-
-
-def _vc(cfg: vo.VitCfg, layers=None, **kw):
-    import vdr
-    return vdr.VdrConfig(img=cfg.img, patch=cfg.patch, in_chans=cfg.in_chans, dim=cfg.dim, heads=cfg.heads,
-                         layers=cfg.layers if layers is None else layers, mlp_hidden=cfg.mlp_hidden, act=cfg.act,
-                         pre_ln=cfg.pre_ln, layerscale=cfg.layerscale, has_cls=cfg.has_cls, has_pos=cfg.has_pos,
-                         input_ln=cfg.input_ln, ln_eps=cfg.ln_eps, **kw)
-
-
+# ---- helpers ---------------------------------------------------------------------------------------------------------
 def _engine(cfg, w, size=None, stride=None, **kw):
     """An engine of cfg's weights, told `size` = (H, W) and `stride` when given (size first)."""
-    import vdr
-    e = vdr.Engine(_vc(cfg, **kw))
-    e.load_weights(w)
+    e = hc.engine(cfg, w, **kw)
     if size is not None:
         e.set_input_size(*size)
     if stride is not None:
@@ -125,7 +88,7 @@ def test_strided_patch_embed_integer_exact(p, s, size, dt):
             ref = torch.nn.functional.conv2d(x, Wt, b, stride=s).flatten(2).transpose(1, 2)
             assert ref.shape == (B, n, D) and ref.abs().max() < 16384  # (exact in fp32; bf16 output: the same rounding)
             y, col = ops.patch_embed_strided(x.to(dt).cuda(), Wt.cuda(), b.cuda(), p, s, return_col=True)
-            assert torch.equal(y.float().cpu(), _bf(ref.reshape(B * n, D)).float()), (Cc, D)
+            assert torch.equal(y.float().cpu(), bf(ref.reshape(B * n, D)).float()), (Cc, D)
             K = Cc * p * p
             unfold = torch.nn.functional.unfold(x, kernel_size=p, stride=s).transpose(1, 2).reshape(B * n, K)
             colc = col.float().cpu()
@@ -135,7 +98,7 @@ def test_strided_patch_embed_integer_exact(p, s, size, dt):
             y2 = ops.patch_embed_strided(x.to(dt).cuda(), Wt.cuda(), b.cuda(), p, s, pos=pos.cuda(), row_stride=n + 1, row_offset=1)
             y2 = y2.float().cpu().reshape(B, n + 1, D)
             assert torch.equal(y2[:, 0], torch.zeros(B, D))
-            assert torch.equal(y2[:, 1:], _bf(ref + pos[1:]).float()), (Cc, D)
+            assert torch.equal(y2[:, 1:], bf(ref + pos[1:]).float()), (Cc, D)
 
 
 def test_strided_op_at_stride_p_and_plain_form():
@@ -150,7 +113,7 @@ def test_strided_op_at_stride_p_and_plain_form():
         ref = torch.nn.functional.conv2d(x, Wt, b, stride=s).flatten(2).transpose(1, 2).reshape(-1, 64)
         for dt in (torch.float32, torch.bfloat16):
             y = ops.patch_embed_strided(x.to(dt).cuda(), Wt.cuda(), b.cuda(), p, s)
-            assert torch.equal(y.float().cpu(), _bf(ref).float()), (p, s, size, dt)
+            assert torch.equal(y.float().cpu(), bf(ref).float()), (p, s, size, dt)
 
 
 # ---- 2. the shift property, bitwise ----------------------------------------------------------------------------------------
@@ -201,7 +164,7 @@ def test_small_models_at_a_finer_stride(name):
     from vdr.model import VitDescriptorModel
     cfg, w, wl, reg, kw = _small(name)
     e = _engine(cfg, wl, **kw)
-    m = VitDescriptorModel(_vc(cfg, **kw), wl)
+    m = VitDescriptorModel(hc.vit_config(cfg, **kw), wl)
     g = gate_l2(cfg.layers)
     B, P = 4, 1 + (0 if reg is None else reg.shape[1])
     for k, (size, s) in enumerate(_cases(name)):
@@ -220,10 +183,10 @@ def test_small_models_at_a_finer_stride(name):
             xd = x.cuda().to(dt)
             tag = f"{name} {size[0]}x{size[1]} stride {s} {'bf16' if dt == torch.bfloat16 else 'fp32'} pixels"
             for mode, key in ((vdr.OUT_CLS, "cls"), (vdr.OUT_DENSE, "dense"), (vdr.OUT_TOKENS, "tokens")):
-                _gate(e.forward(xd, mode), ref[key], emu[key], g, g, f"{tag} {key}")
+                check_parity(e.forward(xd, mode), ref[key], f"{tag} {key}", g, emu[key])
             pooled, = e.forward_layers(xd, [vdr.LayerOut(cfg.layers - 1, vdr.OUT_POOLED)])
-            _gate(pooled, ref["pooled"], emu["pooled"], g, g, f"{tag} pooled")
-            _gate(e.forward(xd, vdr.OUT_PATCH_EMBED), ref["patch_embed"], emu["patch_embed"], 4e-3, 4e-3, f"{tag} patch_embed")
+            check_parity(pooled, ref["pooled"], f"{tag} pooled", g, emu["pooled"])
+            check_parity(e.forward(xd, vdr.OUT_PATCH_EMBED), ref["patch_embed"], f"{tag} patch_embed", 4e-3, emu["patch_embed"])
         # the DINOv2-style outputs follow the grid
         m.set_input_size(*size).set_patch_stride(s)
         assert m.grid == (gh, gw) and m.patch_stride == s
@@ -249,7 +212,7 @@ def test_dynamic_size_keeps_the_stride():
     import vdr
     from vdr.model import VitDescriptorModel
     cfg, w, wl, reg, kw = _small("p16_d128")
-    dyn = VitDescriptorModel(_vc(cfg), w, dynamic_size=True).set_patch_stride(8)
+    dyn = VitDescriptorModel(hc.vit_config(cfg), w, dynamic_size=True).set_patch_stride(8)
     for size in ((64, 64), (96, 48), (64, 64)):
         x = _images(2, *size, seed=40).cuda()
         gh, gw = sr.grid(size, 16, 8)
@@ -312,12 +275,7 @@ def test_batch_properties_at_a_finer_stride(name, size):
     for dt in (torch.float32, torch.bfloat16):
         xd = x.cuda().to(dt)
         for mode in (vdr.OUT_CLS, vdr.OUT_DENSE):
-            out = e.forward(xd, mode)
-            assert torch.isfinite(out).all()
-            assert torch.equal(out[B - 1], out[1]), "duplicate images must give bitwise equal rows"
-            perm = torch.randperm(B, generator=torch.Generator().manual_seed(B)).cuda()
-            assert torch.equal(e.forward(xd[perm].contiguous(), mode), out[perm]), "batch permutation equivariance"
-            assert torch.equal(e.forward(xd[12:15].contiguous(), mode), out[12:15]), "a row depends on its batch"
+            check_batch_properties(lambda t: e.forward(t, mode), xd)
 
 
 # ---- 6. token counts across the attention launcher's classes -----------------------------------------------------------------------
@@ -338,7 +296,7 @@ def test_token_counts_across_the_attention_classes(size, s, N):
     g = gate_l2(cfg.layers)
     for dt in (torch.float32, torch.bfloat16):
         for mode, key in ((vdr.OUT_CLS, "cls"), (vdr.OUT_TOKENS, "tokens")):
-            _gate(e.forward(x.cuda().to(dt), mode), ref[key], emu[key], g, g, f"N={N} {size} stride {s} {dt} {key}")
+            check_parity(e.forward(x.cuda().to(dt), mode), ref[key], f"N={N} {size} stride {s} {dt} {key}", g, emu[key])
 
 
 # ---- 7. refusals on a live handle, workspace ------------------------------------------------------------------------------------------
@@ -362,7 +320,7 @@ def test_refusals_on_a_live_handle_and_workspace():
     for bad in (32, 5):
         assert sam.lib.vdr_set_patch_stride(sam.h, bad) == -1 and b"divide patch 16" in sam.lib.vdr_last_error(sam.h)
     cfg, w, wl, reg, kw = _small("p16_d128")
-    blank = vdr.Engine(_vc(cfg))
+    blank = vdr.Engine(hc.vit_config(cfg))
     assert blank.lib.vdr_set_patch_stride(blank.h, 8) == -6  # VDR_ERR_INCOMPLETE: not finalised
     st = C.c_int()
     assert blank.lib.vdr_get_patch_stride(blank.h, C.byref(st)) == 0 and st.value == 16  # patch until the first set
@@ -427,7 +385,7 @@ def test_python_surface(monkeypatch):
     d = vdr.get_dense_descriptor(model, x[0])
     assert d.shape == (11, 11, 128) and d.dtype == np.float32
     want = sr.forward_images(cfg, w, x, 8)["patch_embed"][0].reshape(11, 11, 128)
-    assert _rel_l2(torch.from_numpy(d), want) <= 4e-3
+    assert rel_l2(torch.from_numpy(d), want) <= 4e-3
     rng = np.random.default_rng(8)
     H, W, S = 72, 80, 2
     img = rng.random((H, W, S, 3)).astype(np.float32)

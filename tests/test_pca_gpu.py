@@ -14,18 +14,14 @@ import pytest
 import torch
 
 import pca_ref as pref
+from fixtures import ops  # noqa: F401
+from ops_checks import assert_same_bits
 
 pytestmark = pytest.mark.gpu
 
 ROWS = (2, 15, 16, 17, 1023, 1024, 1025, 2049)
 DIMS = (32, 96, 160, 288)
 PROBLEMS = 3
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from vdr import ops
-    return ops
 
 
 _CACHE = {}
@@ -39,14 +35,6 @@ def _designed(R, d):
     return _CACHE[key]
 
 
-def _bits(a, b, what):
-    a, b = a.detach().cpu(), b.detach().cpu()
-    assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.shape == b.shape, (what, a.dtype, a.shape, b.shape)
-    same = a.view(torch.int32) == b.view(torch.int32)
-    assert bool(same.all()), (what, int((~same).sum()), torch.nonzero(~same)[:4].tolist(),
-                              a[~same][:4].tolist(), b[~same][:4].tolist())
-
-
 @pytest.mark.parametrize("d", DIMS)
 @pytest.mark.parametrize("R", ROWS)
 def test_designed_covariance_is_exact_and_symmetric(ops, R, d):
@@ -55,11 +43,11 @@ def test_designed_covariance_is_exact_and_symmetric(ops, R, d):
     for dtype in (torch.bfloat16, torch.float32):
         xd = x.to(dtype).cuda()
         m, cov = ops.covariance(xd, mean.cuda())
-        _bits(m, mean, "mean is passed through")
-        _bits(cov, want, ("cov", R, d, dtype))
-        _bits(cov, cov.transpose(1, 2).contiguous(), "symmetry")
+        assert_same_bits(m, mean, "mean is passed through")
+        assert_same_bits(cov, want, ("cov", R, d, dtype))
+        assert_same_bits(cov, cov.transpose(1, 2).contiguous(), "symmetry")
         _, solo = ops.covariance(xd[1:2], mean[1:2].cuda())
-        _bits(solo, want[1:2], ("one problem", R, d, dtype))
+        assert_same_bits(solo, want[1:2], ("one problem", R, d, dtype))
 
 
 @pytest.mark.parametrize("d", DIMS)
@@ -69,8 +57,8 @@ def test_designed_col_mean_is_exact(ops, R, d):
     want = torch.stack([pref.exact_f32_div(x[p].double().sum(0), R) for p in range(PROBLEMS)])
     for dtype in (torch.bfloat16, torch.float32):
         xd = x.to(dtype).cuda()
-        _bits(ops.col_mean(xd), want, ("mean", R, d, dtype))
-        _bits(ops.col_mean(xd[2:3]), want[2:3], ("one problem", R, d, dtype))
+        assert_same_bits(ops.col_mean(xd), want, ("mean", R, d, dtype))
+        assert_same_bits(ops.col_mean(xd[2:3]), want[2:3], ("one problem", R, d, dtype))
 
 
 @pytest.mark.parametrize("k", (1, 3, 8))
@@ -85,11 +73,11 @@ def test_designed_projection_is_exact(ops, R, d, k):
     for dtype in (torch.bfloat16, torch.float32):
         xd = x.to(dtype).cuda()
         proj, mm = ops.pca_project(xd, mean.cuda(), comps.cuda())
-        _bits(proj, want.float(), ("proj", R, d, k, dtype))
-        _bits(mm, wmm, "minmax")
+        assert_same_bits(proj, want.float(), ("proj", R, d, k, dtype))
+        assert_same_bits(mm, wmm, "minmax")
         proj1, mm1 = ops.pca_project(xd[1:2], mean[1:2].cuda(), comps[1:2].cuda())
-        _bits(proj1, want[1:2].float(), "one problem")
-        _bits(mm1, wmm[1:2], "one problem's minmax")
+        assert_same_bits(proj1, want[1:2].float(), "one problem")
+        assert_same_bits(mm1, wmm[1:2], "one problem's minmax")
 
 
 @pytest.mark.parametrize("R,d", ((70, 2048), (1030, 1952)))
@@ -102,15 +90,15 @@ def test_wide_maps_are_exact(ops, R, d):
     wproj = torch.stack([pref.project(x[p], mean[p], comps[p])[0] for p in range(2)])
     assert bool((wproj == wproj.float().double()).all())
     xd = x.to(torch.bfloat16).cuda()
-    _bits(ops.col_mean(xd), wmean, ("mean", R, d))
+    assert_same_bits(ops.col_mean(xd), wmean, ("mean", R, d))
     _, cov = ops.covariance(xd, mean.cuda())
-    _bits(cov, wcov, ("cov", R, d))
-    _bits(cov, cov.transpose(1, 2).contiguous(), "symmetry")
+    assert_same_bits(cov, wcov, ("cov", R, d))
+    assert_same_bits(cov, cov.transpose(1, 2).contiguous(), "symmetry")
     proj, mm = ops.pca_project(xd, mean.cuda(), comps.cuda())
-    _bits(proj, wproj.float(), ("proj", R, d))
-    _bits(mm, torch.stack([wproj.amin(dim=(1, 2)), wproj.amax(dim=(1, 2))], dim=1).float(), "minmax")
+    assert_same_bits(proj, wproj.float(), ("proj", R, d))
+    assert_same_bits(mm, torch.stack([wproj.amin(dim=(1, 2)), wproj.amax(dim=(1, 2))], dim=1).float(), "minmax")
     proj3, _ = ops.pca_project(x.cuda(), mean.cuda(), comps[:, :3].contiguous().cuda())
-    _bits(proj3, wproj[:, :, :3].contiguous().float(), ("proj k = 3, fp32", R, d))
+    assert_same_bits(proj3, wproj[:, :, :3].contiguous().float(), ("proj k = 3, fp32", R, d))
 
 
 def test_centring_precedes_the_bf16_rounding(ops):
@@ -122,7 +110,7 @@ def test_centring_precedes_the_bf16_rounding(ops):
     mean = torch.full((2, d), 1000.0)
     want = torch.stack([pref.exact_f32_div((q[p].double() / 4).t() @ (q[p].double() / 4), R - 1) for p in range(2)])
     _, cov = ops.covariance(x.cuda(), mean.cuda())
-    _bits(cov, want, "centred covariance")
+    assert_same_bits(cov, want, "centred covariance")
     assert float(want.diagonal(dim1=1, dim2=2).min()) > 1.0  # (a rounding of x to bf16 first would leave multiples of 8: all wrong)
 
 
@@ -140,29 +128,29 @@ def test_layout_and_batch_independence_are_bitwise(ops):
     mv, cv = ops.covariance(view)
     pv, mmv = ops.pca_project(view, mean, comps, scale=True)
     for a, b, what in ((mv, mean, "mean"), (cv, cov, "cov"), (pv, proj, "proj"), (mmv, mm, "minmax")):
-        _bits(a, b, ("view", what))
+        assert_same_bits(a, b, ("view", what))
     # a problem inside a batch == its own run; two runs agree
     for p in range(3):
         m1, c1 = ops.covariance(x[p:p + 1])
         p1, mm1 = ops.pca_project(x[p:p + 1], m1, comps[p:p + 1], scale=True)
         for a, b, what in ((m1, mean[p:p + 1], "mean"), (c1, cov[p:p + 1], "cov"), (p1, proj[p:p + 1], "proj"), (mm1, mm[p:p + 1], "mm")):
-            _bits(a, b, ("solo", p, what))
+            assert_same_bits(a, b, ("solo", p, what))
     m2, c2 = ops.covariance(x)
-    _bits(m2, mean, "rerun mean")
-    _bits(c2, cov, "rerun cov")
-    _bits(ops.pca_project(x, mean, comps, scale=True)[0], proj, "rerun proj")
+    assert_same_bits(m2, mean, "rerun mean")
+    assert_same_bits(c2, cov, "rerun cov")
+    assert_same_bits(ops.pca_project(x, mean, comps, scale=True)[0], proj, "rerun proj")
     # joint over 3 strided images == the same rows concatenated
     cat = view.reshape(1, 3 * R, d).contiguous()
     mj, cj = ops.covariance(view, joint=True)
     mc, cc = ops.covariance(cat)
-    _bits(mj, mc, "joint mean")
-    _bits(cj, cc, "joint cov")
-    _bits(ops.col_mean(view, joint=True), mc, "joint col_mean")
+    assert_same_bits(mj, mc, "joint mean")
+    assert_same_bits(cj, cc, "joint cov")
+    assert_same_bits(ops.col_mean(view, joint=True), mc, "joint col_mean")
     pj, mmj = ops.pca_project(view, mj, comps[:1], scale=False)
     pc, mmc = ops.pca_project(cat, mc, comps[:1], scale=False)
     assert pj.shape == (1, 3 * R, 3)
-    _bits(pj, pc, "joint proj")
-    _bits(mmj, mmc, "joint minmax")
+    assert_same_bits(pj, pc, "joint proj")
+    assert_same_bits(mmj, mmc, "joint minmax")
 
 
 def test_scaling_is_one_subtraction_and_one_division(ops):
@@ -172,12 +160,12 @@ def test_scaling_is_one_subtraction_and_one_division(ops):
     mean = ops.col_mean(x)
     comps = torch.randn(2, k, d, generator=g).cuda()
     raw, mm = ops.pca_project(x, mean, comps, scale=False)
-    _bits(mm, torch.stack([raw.amin(dim=(1, 2)), raw.amax(dim=(1, 2))], dim=1), "minmax of the unscaled output")
+    assert_same_bits(mm, torch.stack([raw.amin(dim=(1, 2)), raw.amax(dim=(1, 2))], dim=1), "minmax of the unscaled output")
     scaled, mm2 = ops.pca_project(x, mean, comps, scale=True)
-    _bits(mm2, mm, "minmax is that of the unscaled projection")
+    assert_same_bits(mm2, mm, "minmax is that of the unscaled projection")
     raw, mm = raw.cpu(), mm.cpu()  # (the host's fp32 subtraction and division are the IEEE ones)
     lo, hi = mm[:, 0].view(2, 1, 1), mm[:, 1].view(2, 1, 1)
-    _bits(scaled, (raw - lo) / (hi - lo), "scaled")
+    assert_same_bits(scaled, (raw - lo) / (hi - lo), "scaled")
     assert float(scaled.min()) == 0.0 and float(scaled.max()) == 1.0
     # a constant map: max == min, returned as it is
     const = torch.full((1, 40, 32), 2.5).cuda()
@@ -186,7 +174,7 @@ def test_scaling_is_one_subtraction_and_one_division(ops):
     raw, mm = ops.pca_project(const, cm, cc, scale=False)
     sc, _ = ops.pca_project(const, cm, cc, scale=True)
     assert float(mm[0, 0]) == float(mm[0, 1]) == 64.0
-    _bits(sc, raw, "constant map")
+    assert_same_bits(sc, raw, "constant map")
 
 
 @pytest.mark.parametrize("R,d,dtype", ((300, 768, torch.bfloat16), (1100, 256, torch.float32)))

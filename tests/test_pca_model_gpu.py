@@ -11,22 +11,17 @@ import torch
 
 import handle_configs as hc
 import pca_ref as pref
+from handle_configs import TINY
+from ops_checks import assert_same_bits
 from oracle import vit_oracle as vo
 
 pytestmark = pytest.mark.gpu
 
-TINY = vo.VitCfg(32, 8, 3, 64, 1, 2, 128)
-
 
 @pytest.fixture(scope="module")
 def model():
-    import vdr
-    name = "_pca_tiny"
-    vdr.ARCHS[name] = hc.vit_config(TINY)
-    try:
-        yield vdr.load_model(name, weights=vo.make_weights(TINY, seed=21, scale=0.05))
-    finally:
-        del vdr.ARCHS[name]
+    with hc.registered_model("_pca_tiny") as m:
+        yield m
 
 
 @pytest.mark.parametrize("name", pref.SK_CASES)
@@ -68,11 +63,6 @@ def test_pca_colorize_against_the_references_maps(golden_dir):
         assert np.abs(out.reshape(64, 3) - g["rgb_default"]).max() <= pref.GATE_RGB
 
 
-def _same(a, b, what):
-    a, b = a.cpu(), b.cpu()
-    assert a.dtype == torch.float32 and a.shape == b.shape and bool((a.view(torch.int32) == b.view(torch.int32)).all()), what
-
-
 def _check(model, x, grid):
     import vdr
     gh, gw = grid
@@ -84,12 +74,12 @@ def _check(model, x, grid):
         got = model.pca_descriptors(x, **kw)
         assert got.shape == (B, gh, gw, 3) and got.dtype == torch.float32
         for b in range(B):
-            _same(got[b], vdr.pca_colorize(rows[b], (gh, gw)), ("per image", kw, b))
+            assert_same_bits(got[b], vdr.pca_colorize(rows[b], (gh, gw)), ("per image", kw, b))
         joint = model.pca_descriptors(x, joint=True, **kw)
-        _same(joint, vdr.pca_colorize(rows.reshape(B * gh * gw, -1), (B, gh, gw)), ("joint", kw))
+        assert_same_bits(joint, vdr.pca_colorize(rows.reshape(B * gh * gw, -1), (B, gh, gw)), ("joint", kw))
     bg = model.pca_descriptors(x, remove_bg=True)
     for b in range(B):
-        _same(bg[b], vdr.pca_colorize(dense[b], (gh, gw), remove_bg=True), ("remove_bg", b))
+        assert_same_bits(bg[b], vdr.pca_colorize(dense[b], (gh, gw), remove_bg=True), ("remove_bg", b))
     k5 = model.pca_descriptors(x, n_components=5)
     assert k5.shape == (B, gh, gw, 5) and float(k5.min()) == 0.0 and float(k5.max()) == 1.0
 
@@ -139,9 +129,9 @@ def test_pca_descriptors_of_a_sam_encoder_is_pca_colorize_of_its_neck_output():
     got = m.pca_descriptors(x)
     assert got.shape == (2, 14, 14, 3) and got.dtype == torch.float32
     for b in range(2):
-        _same(got[b], vdr.pca_colorize(rows[b], (14, 14)), ("per image", b))
-        _same(m.pca_descriptors(x, remove_bg=True)[b], vdr.pca_colorize(rows[b], (14, 14), remove_bg=True), ("remove_bg", b))
-    _same(m.pca_descriptors(x, joint=True), vdr.pca_colorize(rows.reshape(392, 64), (2, 14, 14)), "joint")
+        assert_same_bits(got[b], vdr.pca_colorize(rows[b], (14, 14)), ("per image", b))
+        assert_same_bits(m.pca_descriptors(x, remove_bg=True)[b], vdr.pca_colorize(rows[b], (14, 14), remove_bg=True), ("remove_bg", b))
+    assert_same_bits(m.pca_descriptors(x, joint=True), vdr.pca_colorize(rows.reshape(392, 64), (2, 14, 14)), "joint")
     with pytest.raises(ValueError):
         m.pca_descriptors(x, facet="key")  # (extract_descriptors' own refusal of SAM models)
 
@@ -156,7 +146,7 @@ def test_a_fit_does_not_depend_on_the_batch_it_came_in(d):
     whole = vdr.pca.fit(x, 3)
     for sl in (slice(0, 1), slice(1, 2), slice(2, 3), slice(1, 3)):
         part = vdr.pca.fit(x[sl], 3)
-        _same(part.components, whole.components[sl], ("components", sl))
-        _same(part.mean, whole.mean[sl], ("mean", sl))
+        assert_same_bits(part.components, whole.components[sl], ("components", sl))
+        assert_same_bits(part.mean, whole.mean[sl], ("mean", sl))
         assert torch.equal(part.explained_variance, whole.explained_variance[sl])
-        _same(part.transform(x[sl], scale=True), whole.transform(x, scale=True)[sl], ("transform", sl))
+        assert_same_bits(part.transform(x[sl], scale=True), whole.transform(x, scale=True)[sl], ("transform", sl))

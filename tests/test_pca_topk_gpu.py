@@ -17,6 +17,8 @@ import torch
 
 import pca_ref as pref
 import pca_topk_ref as tref
+from fixtures import ops  # noqa: F401
+from ops_checks import assert_same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -24,12 +26,6 @@ ROWS = (2, 15, 16, 17, 127, 128, 129, 300)
 DIMS = tuple(sorted({32, 96, 288, tref.GRAM_CHUNK - 32, tref.GRAM_CHUNK, tref.GRAM_CHUNK + 32}))
 PROBLEMS = 3
 U = pref.U
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from vdr import ops
-    return ops
 
 
 _CACHE = {}
@@ -52,13 +48,6 @@ def _planted(n, ratio):
     return _CACHE[key]
 
 
-def _bits(a, b, what):
-    a, b = a.detach().cpu(), b.detach().cpu()
-    assert a.dtype == b.dtype and a.shape == b.shape, (what, a.dtype, b.dtype, a.shape, b.shape)
-    same = a.view(torch.int32) == b.view(torch.int32)
-    assert bool(same.all()), (what, int((~same).sum()), torch.nonzero(~same)[:4].tolist(), a[~same][:4].tolist(), b[~same][:4].tolist())
-
-
 def _want_gram(x, mean):
     z = pref.centred_bf16(x, mean)
     return pref.exact_f32_div(z @ z.t(), x.shape[0] - 1)
@@ -73,11 +62,11 @@ def test_designed_gram_is_exact_and_symmetric(ops, t, d):
     for dtype in (torch.bfloat16, torch.float32):
         xd = x.to(dtype).cuda()
         m, g = ops.gram(xd, mean.cuda())
-        _bits(m, mean, "mean is passed through")
-        _bits(g, want, ("gram", t, d, dtype))
-        _bits(g, g.transpose(1, 2).contiguous(), "symmetry")
+        assert_same_bits(m, mean, "mean is passed through")
+        assert_same_bits(g, want, ("gram", t, d, dtype))
+        assert_same_bits(g, g.transpose(1, 2).contiguous(), "symmetry")
         _, solo = ops.gram(xd[1:2], mean[1:2].cuda())
-        _bits(solo, want[1:2], ("one problem", t, d, dtype))
+        assert_same_bits(solo, want[1:2], ("one problem", t, d, dtype))
 
 
 def test_designed_gram_and_mean_of_a_binned_width_are_exact(ops):
@@ -85,17 +74,17 @@ def test_designed_gram_and_mean_of_a_binned_width_are_exact(ops):
     x, mean = pref.designed(1, t, d, seed=7)
     xd = x.to(torch.bfloat16).cuda()
     _, g = ops.gram(xd, mean.cuda())
-    _bits(g, _want_gram(x[0], mean[0]).unsqueeze(0), "gram 196 x 13056")
-    _bits(g, g.transpose(1, 2).contiguous(), "symmetry")
-    _bits(ops.col_mean_any(xd), pref.exact_f32_div(x[0].double().sum(0), t).unsqueeze(0), "mean at d = 13056")
+    assert_same_bits(g, _want_gram(x[0], mean[0]).unsqueeze(0), "gram 196 x 13056")
+    assert_same_bits(g, g.transpose(1, 2).contiguous(), "symmetry")
+    assert_same_bits(ops.col_mean_any(xd), pref.exact_f32_div(x[0].double().sum(0), t).unsqueeze(0), "mean at d = 13056")
 
 
 def test_the_wide_mean_is_col_mean_bit_for_bit(ops):
     g = torch.Generator().manual_seed(2)
     for t, d in ((300, 160), (1030, 2048)):
         x = (torch.randn(3, t, d, generator=g) * 3 + 0.5).to(torch.bfloat16).cuda()
-        _bits(ops.col_mean_any(x), ops.col_mean(x), ("col_mean_any", t, d))
-        _bits(ops.col_mean_any(x.float()), ops.col_mean(x.float()), ("col_mean_any fp32", t, d))
+        assert_same_bits(ops.col_mean_any(x), ops.col_mean(x), ("col_mean_any", t, d))
+        assert_same_bits(ops.col_mean_any(x.float()), ops.col_mean(x.float()), ("col_mean_any fp32", t, d))
 
 
 def test_gram_centring_precedes_the_bf16_rounding(ops):
@@ -106,7 +95,7 @@ def test_gram_centring_precedes_the_bf16_rounding(ops):
     x = 1000.0 + q / 4
     want = torch.stack([pref.exact_f32_div((q[p].double() / 4) @ (q[p].double() / 4).t(), t - 1) for p in range(2)])
     _, got = ops.gram(x.cuda(), torch.full((2, d), 1000.0).cuda())
-    _bits(got, want, "centred gram")
+    assert_same_bits(got, want, "centred gram")
     assert float(want.diagonal(dim1=1, dim2=2).min()) > 1.0
 
 
@@ -118,15 +107,15 @@ def test_gram_layout_and_batch_independence_are_bitwise(ops):
     assert view.stride(1) == 3 * d and not view.is_contiguous()
     x = view.contiguous()
     mean, gram = ops.gram(x)
-    _bits(mean, ops.col_mean(x), "gram's own mean is col_mean")
+    assert_same_bits(mean, ops.col_mean(x), "gram's own mean is col_mean")
     mv, gv = ops.gram(view)
-    _bits(mv, mean, "view mean")
-    _bits(gv, gram, "view gram")
+    assert_same_bits(mv, mean, "view mean")
+    assert_same_bits(gv, gram, "view gram")
     for p in range(3):
         m1, g1 = ops.gram(x[p:p + 1])
-        _bits(m1, mean[p:p + 1], ("solo mean", p))
-        _bits(g1, gram[p:p + 1], ("solo gram", p))
-    _bits(ops.gram(x)[1], gram, "rerun")
+        assert_same_bits(m1, mean[p:p + 1], ("solo mean", p))
+        assert_same_bits(g1, gram[p:p + 1], ("solo gram", p))
+    assert_same_bits(ops.gram(x)[1], gram, "rerun")
     assert bool((gram == gram.transpose(1, 2)).all())
 
 
@@ -161,12 +150,12 @@ def test_designed_back_projection_is_exact(ops, t, d):
                            torch.zeros_like(raw)).float()
         for dtype in (torch.bfloat16, torch.float32):
             got = ops.pca_back_project(x.to(dtype).cuda(), mean.cuda(), u.cuda(), values.cuda())
-            _bits(got, want, ("back_project", t, d, k, dtype))
+            assert_same_bits(got, want, ("back_project", t, d, k, dtype))
             length = got.cpu().double().norm(dim=2)
             assert bool(((length - 1).abs() <= 4 * U)[(values > 0) & (norm[..., 0] > 0)].all())
             assert float(got[0, k - 1].abs().max()) == 0.0
         solo = ops.pca_back_project(x[1:2].cuda(), mean[1:2].cuda(), u[1:2].cuda(), values[1:2].cuda())
-        _bits(solo, want[1:2], ("one problem", t, d, k))
+        assert_same_bits(solo, want[1:2], ("one problem", t, d, k))
 
 
 def test_back_projection_at_a_binned_width(ops):
@@ -175,7 +164,7 @@ def test_back_projection_at_a_binned_width(ops):
     u = torch.randint(-2, 3, (1, k, t), generator=torch.Generator().manual_seed(1)).float()
     raw = tref.back_project(x[0], mean[0], u[0], torch.ones(k))[1]
     got = ops.pca_back_project(x.to(torch.bfloat16).cuda(), mean.cuda(), u.cuda(), torch.ones(1, k).cuda())
-    _bits(got, (raw / raw.pow(2).sum(1, keepdim=True).sqrt()).float().unsqueeze(0), "back_project 196 x 13056")
+    assert_same_bits(got, (raw / raw.pow(2).sum(1, keepdim=True).sqrt()).float().unsqueeze(0), "back_project 196 x 13056")
 
 
 # ---- sym_topk -------------------------------------------------------------------------------------------------------------
@@ -298,13 +287,13 @@ def test_sym_topk_is_bitwise_reproducible_and_batch_independent(ops):
     whole = ops.sym_topk(batch, 3)
     again = ops.sym_topk(batch, 3)
     for a, b, what in zip(whole, again, ("values", "vectors", "iters", "resid")):
-        _bits(a, b, ("rerun", what))
+        assert_same_bits(a, b, ("rerun", what), dtype=a.dtype)  # (iters is int32)
     for p in (0, 2):  # alone == first of 3 == last of 3 (rolled so that it is)
         alone = ops.sym_topk(batch[p:p + 1], 3)
         rolled = ops.sym_topk(torch.roll(batch, 2 - p, 0).contiguous(), 3)
         for a, b, c, what in zip(alone, whole, rolled, ("values", "vectors", "iters", "resid")):
-            _bits(a, b[p:p + 1], ("alone", p, what))
-            _bits(a, c[2:3], ("moved to the end", p, what))
+            assert_same_bits(a, b[p:p + 1], ("alone", p, what), dtype=a.dtype)
+            assert_same_bits(a, c[2:3], ("moved to the end", p, what), dtype=a.dtype)
     assert len(set(whole[2].tolist())) > 1  # (the problems stop at different iterations: the done flags are per problem)
 
 
@@ -413,10 +402,10 @@ def test_subspace_fit_does_not_depend_on_the_batch_it_came_in():
         whole = vdr.pca.fit(x, 3, solver="subspace")
         for sl in (slice(0, 1), slice(2, 3), slice(1, 3)):
             part = vdr.pca.fit(x[sl], 3, solver="subspace")
-            _bits(part.components, whole.components[sl], ("components", t, d, sl))
+            assert_same_bits(part.components, whole.components[sl], ("components", t, d, sl))
             assert torch.equal(part.explained_variance, whole.explained_variance[sl])
             if whole.scores is not None:
-                _bits(part.scores, whole.scores[sl], ("scores", sl))
+                assert_same_bits(part.scores, whole.scores[sl], ("scores", sl))
 
 
 def test_a_wide_map_is_fitted_and_transform_says_where_it_stops():

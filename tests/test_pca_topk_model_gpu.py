@@ -10,27 +10,17 @@ import torch
 
 import handle_configs as hc
 import pca_ref as pref
+from handle_configs import TINY
+from ops_checks import assert_same_bits
 from oracle import vit_oracle as vo
 
 pytestmark = pytest.mark.gpu
 
-TINY = vo.VitCfg(32, 8, 3, 64, 1, 2, 128)
-
 
 @pytest.fixture(scope="module")
 def model():
-    import vdr
-    name = "_pca_topk_tiny"
-    vdr.ARCHS[name] = hc.vit_config(TINY)
-    try:
-        yield vdr.load_model(name, weights=vo.make_weights(TINY, seed=21, scale=0.05))
-    finally:
-        del vdr.ARCHS[name]
-
-
-def _same(a, b, what):
-    a, b = a.cpu(), b.cpu()
-    assert a.dtype == torch.float32 and a.shape == b.shape and bool((a.view(torch.int32) == b.view(torch.int32)).all()), what
+    with hc.registered_model("_pca_topk_tiny") as m:
+        yield m
 
 
 def test_binned_pca_descriptors_is_colorize_of_the_binned_rows(model):
@@ -44,9 +34,9 @@ def test_binned_pca_descriptors_is_colorize_of_the_binned_rows(model):
         got = model.pca_descriptor_maps(x, facet="key", bin=True, hierarchy=hierarchy, solver="subspace")
         assert got.shape == (3, gh, gw, 3) and got.dtype == torch.float32 and float(got.min()) == 0.0 and float(got.max()) == 1.0
         for b in range(3):
-            _same(got[b], vdr.pca.colorize(rows[b].to(torch.bfloat16), (gh, gw), solver="subspace"), ("per image", hierarchy, b))
+            assert_same_bits(got[b], vdr.pca.colorize(rows[b].to(torch.bfloat16), (gh, gw), solver="subspace"), ("per image", hierarchy, b))
         bg = model.pca_descriptor_maps(x, facet="key", bin=True, hierarchy=hierarchy, remove_bg=True, solver="subspace")
-        _same(bg[1], vdr.pca.colorize(rows[1].to(torch.bfloat16), (gh, gw), remove_bg=True, solver="subspace"), ("remove_bg", hierarchy))
+        assert_same_bits(bg[1], vdr.pca.colorize(rows[1].to(torch.bfloat16), (gh, gw), remove_bg=True, solver="subspace"), ("remove_bg", hierarchy))
 
 
 def test_binned_pca_descriptors_follows_the_patch_stride_and_the_input_size(model):
@@ -60,7 +50,7 @@ def test_binned_pca_descriptors_follows_the_patch_stride_and_the_input_size(mode
         got = model.pca_descriptor_maps(x, facet="key", bin=True, solver="subspace")
         assert got.shape == (2, gh, gw, 3)
         for b in range(2):
-            _same(got[b], vdr.pca.colorize(rows[b].to(torch.bfloat16), (gh, gw), solver="subspace"), (grid, b))
+            assert_same_bits(got[b], vdr.pca.colorize(rows[b].to(torch.bfloat16), (gh, gw), solver="subspace"), (grid, b))
 
     model.set_patch_stride(4)
     try:
@@ -93,7 +83,7 @@ def test_the_default_solver_still_refuses_wide_binned_descriptors():
     rows = m.extract_descriptors(x, facet="key", bin=True)[:, 0]
     assert rows.shape == (2, 16, 4352) and got.shape == (2, 4, 4, 3)
     for b in range(2):
-        _same(got[b], vdr.pca.colorize(rows[b].to(torch.bfloat16), (4, 4), solver="subspace"), ("wide", b))
+        assert_same_bits(got[b], vdr.pca.colorize(rows[b].to(torch.bfloat16), (4, 4), solver="subspace"), ("wide", b))
     with pytest.raises(ValueError, match="at most 2048"):
         vdr.pca_colorize(rows[0], (4, 4))
 
@@ -105,7 +95,7 @@ def test_both_solvers_colour_an_unbinned_map_alike(model):
         for kw in ({}, dict(facet="key"), dict(joint=True)):
             a = model.pca_descriptors(x, **kw)
             b = model.pca_descriptor_maps(x, solver="subspace", **kw)
-            _same(model.pca_descriptor_maps(x, **kw), a, ("the defaults are pca_descriptors", kw))
+            assert_same_bits(model.pca_descriptor_maps(x, **kw), a, ("the defaults are pca_descriptors", kw))
             err = float((a - b).abs().max())
             print("eigh against subspace", kw, err)
             assert a.shape == b.shape == (3, 13, 13, 3) and err <= pref.GATE_RGB, (kw, err)

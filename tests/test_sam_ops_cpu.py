@@ -8,14 +8,9 @@ import pytest
 import torch
 
 import sam_ops_ref as sr
+from fixtures import lib  # noqa: F401
 
 INVALID, NO_DEVICE, UNSUPPORTED = -1, -2, -7
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from vdr import _lib
-    return _lib.load()
 
 
 @pytest.fixture(scope="module")

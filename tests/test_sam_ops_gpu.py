@@ -17,6 +17,8 @@ import pytest
 import torch
 
 import sam_ops_ref as sr
+from fixtures import ops  # noqa: F401
+from ops_checks import bf
 
 pytestmark = pytest.mark.gpu
 
@@ -24,18 +26,6 @@ CANARY = 0x5A5A  # int16 pattern of the prefilled outputs and guard rows (as bf1
 GUARD = 5        # guard rows before and after an output
 ALL_VARIANTS = (0, 22, 23, 24, 25, 26, 27, 28, 29)  # 0: what the forward picks for the out-projection; ring3, ring3k (25), ring4
 EPS = 1e-6
-
-
-@pytest.fixture(scope="module")
-def ops():
-    import vdr  # noqa: F401
-    from vdr import ops as _ops
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return _ops
-
-
-def _bf(x):
-    return x.to(torch.bfloat16)
 
 
 def _bits(t):
@@ -71,7 +61,7 @@ def _geo(batch, g, ws):
 def test_layernorm_window_is_layernorm_in_partition_order(ops, batch, g, ws, D):
     idx, valid, _ = _geo(batch, g, ws)
     gen = torch.Generator().manual_seed(1000 * g + 10 * ws + D)
-    x = _bf(torch.randn(batch * g * g, D, generator=gen) * 1.7 + 0.3).cuda()
+    x = bf(torch.randn(batch * g * g, D, generator=gen) * 1.7 + 0.3).cuda()
     gamma = (torch.randn(D, generator=gen) * 0.5 + 1.0).cuda()
     beta = (torch.randn(D, generator=gen) * 0.3).cuda()
     want = _bits(ops.layernorm(x, gamma, beta, EPS))
@@ -89,7 +79,7 @@ def test_layernorm_window_is_layernorm_in_partition_order(ops, batch, g, ws, D):
 def test_layernorm_window_rows_spell_their_token_number(ops, batch, g, ws, D):
     """Independent of vdr_op_layernorm: the signs of a normalised sam_ops_ref.token_code_rows row are its token number."""
     idx, valid, _ = _geo(batch, g, ws)
-    x = _bf(sr.token_code_rows(batch * g * g, D)).cuda()
+    x = bf(sr.token_code_rows(batch * g * g, D)).cuda()
     whole, body = _guarded(sr.window_rows(batch, g, ws), D)
     ops.layernorm_window(x, torch.ones(D, device="cuda"), torch.zeros(D, device="cuda"), EPS, batch, g, ws, out=body)
     torch.cuda.synchronize()
@@ -108,7 +98,7 @@ def test_layernorm_mx_window(ops, batch, g, ws, D):
     idx, valid, _ = _geo(batch, g, ws)
     rows = sr.window_rows(batch, g, ws)
     gen = torch.Generator().manual_seed(2000 * g + 10 * ws + D)
-    x = _bf(torch.randn(batch * g * g, D, generator=gen) * 1.7 + 0.3).cuda()
+    x = bf(torch.randn(batch * g * g, D, generator=gen) * 1.7 + 0.3).cuda()
     gamma = (torch.randn(D, generator=gen) * 0.5 + 1.0).cuda()
     beta = (torch.randn(D, generator=gen) * 0.3).cuda()
     want = _bits(ops.layernorm_mx(x, gamma, beta, EPS).dequantize())
@@ -163,14 +153,14 @@ def _run_window(ops, x, W, bias, resid, batch, g, ws, variant, in_place, part=No
 
 def _check_integer_case(ops, batch, g, ws, N, K, variants):
     x, W, bias, resid, ref = _integer_case(batch, g, ws, N, K, seed=g * 100 + ws + N)
-    want = _bits(_bf(ref.float()))
-    assert torch.equal(_bf(ref.float()).double(), ref)  # every expected output is a bf16 number
-    xd, Wd, bd, rd = _bf(x).cuda(), _bf(W).cuda(), bias.cuda(), _bf(resid).cuda()
+    want = _bits(bf(ref.float()))
+    assert torch.equal(bf(ref.float()).double(), ref)  # every expected output is a bf16 number
+    xd, Wd, bd, rd = bf(x).cuda(), bf(W).cuda(), bias.cuda(), bf(resid).cuda()
     for v in variants:
         out = _run_window(ops, xd, Wd, bd, rd, batch, g, ws, v, in_place=False)
         assert torch.equal(out, want), f"variant {v}: {int((out != want).any(1).sum())} of {want.shape[0]} rows differ"
         assert torch.equal(_run_window(ops, xd, Wd, bd, rd, batch, g, ws, v, in_place=True), out), f"variant {v} in place"
-    assert torch.equal(_bits(rd), _bits(_bf(resid)))  # the out-of-place launches left the residual alone
+    assert torch.equal(_bits(rd), _bits(bf(resid)))  # the out-of-place launches left the residual alone
 
 
 @pytest.mark.parametrize("N,K", [(64, 64), (768, 768), (200, 128)])
@@ -192,10 +182,10 @@ def test_linear_window_exact_integers_more_tiles_than_resident_workgroups(ops):
 def _real_case(batch, g, ws, N, K, seed):
     idx, valid, inv = _geo(batch, g, ws)
     gen = torch.Generator().manual_seed(seed)
-    x = _bf(torch.randn(sr.window_rows(batch, g, ws), K, generator=gen))
-    W = _bf(torch.randn(N, K, generator=gen) * 0.05)
+    x = bf(torch.randn(sr.window_rows(batch, g, ws), K, generator=gen))
+    W = bf(torch.randn(N, K, generator=gen) * 0.05)
     bias = torch.randn(N, generator=gen) * 0.2
-    resid = _bf(torch.randn(batch * g * g, N, generator=gen) * 1.5)
+    resid = bf(torch.randn(batch * g * g, N, generator=gen) * 1.5)
     return x, W, bias, resid, inv, valid
 
 
@@ -243,10 +233,10 @@ def test_linear_window_layernorm_partials(ops, batch, g, ws, N):
     for v in (22, 26, 28):
         # integer data: exact
         x, W, bias, resid, ref = _integer_case(batch, g, ws, N, N, seed=g * 100 + ws + N + 1)
-        xd, Wd, bd, rd = _bf(x).cuda(), _bf(W).cuda(), bias.cuda(), _bf(resid).cuda()
+        xd, Wd, bd, rd = bf(x).cuda(), bf(W).cuda(), bias.cuda(), bf(resid).cuda()
         part = _nan_part(N, tokens)
         out = _run_window(ops, xd, Wd, bd, rd, batch, g, ws, v, in_place=False, part=part)
-        assert torch.equal(out, _bits(_bf(ref.float())))
+        assert torch.equal(out, _bits(bf(ref.float())))
         _check_part(part, out, tokens, exact=True)
         # real-valued data: the summation bound, and the plain producer's bits
         x, W, bias, resid, inv, _ = _real_case(batch, g, ws, N, N, seed=g * 10 + ws + N)
@@ -294,7 +284,7 @@ IM2COL_GRIDS = [(1, 1), (3, 2), (2, 7), (3, 10), (1, 64)]
 @pytest.mark.parametrize("batch,g", IM2COL_GRIDS)
 def test_im2col3_is_unfold_in_tap_major_order(ops, batch, g, C):
     gen = torch.Generator().manual_seed(g * 10 + C)
-    x = _bf(torch.randn(batch * g * g, C, generator=gen) * 3.0)
+    x = bf(torch.randn(batch * g * g, C, generator=gen) * 3.0)
     flat = x.view(torch.int16).reshape(-1)
     n = flat.numel()
     flat[torch.randint(0, n, (n // 16 + 1,), generator=gen)] = -32768  # -0.0
@@ -312,7 +302,7 @@ def test_im2col3_never_reads_the_neighbouring_image(ops):
     batch, g, C = 3, 7, 64
     x = torch.full((batch, g * g, C), 7.0)
     x[1] = 1.0
-    col = ops.im2col3(_bf(x).reshape(-1, C).cuda(), batch, g).float().cpu().reshape(batch, g, g, 9, C)
+    col = ops.im2col3(bf(x).reshape(-1, C).cuda(), batch, g).float().cpu().reshape(batch, g, g, 9, C)
     mid = col[1]
     assert bool(((mid == 0) | (mid == 1)).all()), "image 1 holds a value of a neighbouring image"
     assert bool((mid[1:-1, 1:-1] == 1).all())
@@ -336,6 +326,6 @@ def test_neck_conv3x3_through_im2col3_exact_integers(ops, batch, g, C):
     ref = torch.nn.functional.conv2d(x.permute(0, 3, 1, 2).double(), Wc.double(), padding=1)
     ref = ref.permute(0, 2, 3, 1).reshape(batch * g * g, C)
     assert float(ref.abs().max()) <= 128
-    col = ops.im2col3(_bf(x).reshape(-1, C).cuda(), batch, g)
-    y = ops.linear(col, _bf(Wt).cuda(), None, epilogue=EPI_BIAS)
+    col = ops.im2col3(bf(x).reshape(-1, C).cuda(), batch, g)
+    y = ops.linear(col, bf(Wt).cuda(), None, epilogue=EPI_BIAS)
     assert torch.equal(y.double().cpu(), ref)

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from oracle import sam_oracle as so
+from sam_size_ref import golden_cases, linear_def, within_half_ulp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -20,19 +21,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _header():
     src = open(os.path.join(ROOT, "include", "vdr.h")).read()
     return re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
-
-
-def golden_cases(golden_dir):
-    """(native cfg, sized cfg, batch, wseed, xseed, wscale, expected out[:, :keep]) per case of sam_hf_resize.npz"""
-    g = np.load(os.path.join(golden_dir, "sam_hf_resize.npz"), allow_pickle=False)
-    out = []
-    for n in range(int(g["n_cases"])):
-        v = lambda k: g[f"c{n}_{k}"]  # noqa: E731
-        mk = lambda img: so.SamCfg(int(img), 16, 3, int(v("dim")), int(v("heads")), int(v("layers")), int(v("ffn")),  # noqa: E731
-                                   int(v("window")), tuple(int(i) for i in v("global_idx")), int(v("out_chans")), 1e-6)
-        out.append((mk(v("native")), mk(v("side")), int(v("batch")), int(v("wseed")), int(v("xseed")), float(g["wscale"]),
-                    torch.from_numpy(v("out"))))
-    return out
 
 
 def test_declarations_bindings_and_exports():
@@ -105,28 +93,6 @@ def test_host_refusals_without_an_engine():
         m.set_input_size(256, 256)
 
 
-def _linear_def(t, L):
-    """the definition written out in float64 numpy: src = max((i + 0.5) L0 / L - 0.5, 0), neighbours clamped at the last row"""
-    t = t.double().numpy()
-    L0 = t.shape[0]
-    out = np.empty((L, t.shape[1]), dtype=np.float64)
-    for i in range(L):
-        src = max((i + 0.5) * (L0 / L) - 0.5, 0.0)
-        i0 = min(int(src), L0 - 1)
-        i1 = min(i0 + 1, L0 - 1)
-        lam = src - i0
-        out[i] = (1.0 - lam) * t[i0] + lam * t[i1]
-    return out
-
-
-def within_half_ulp(got, want64):
-    """|got - want| <= half an fp32 ulp at want: got is the float64 value rounded to fp32 once.  (Two float64 evaluation
-    orders of the same blend differ by ~1e-16 relative: 2^-29 of an fp32 ulp, allowed for by the 1e-6.)"""
-    got = got.detach().cpu().double().numpy()
-    ulp = np.spacing(np.abs(want64).astype(np.float32)).astype(np.float64)
-    return bool((np.abs(got - want64) <= 0.5 * ulp * (1 + 1e-6)).all())
-
-
 def test_interpolate_rel_pos_host_definition():
     from vdr.weights import interpolate_rel_pos
     gen = torch.Generator().manual_seed(5)
@@ -134,7 +100,7 @@ def test_interpolate_rel_pos_host_definition():
     for L0, L in ((26, 13), (28, 7), (8, 16), (5, 20)):
         t = torch.randint(-64, 64, (L0, 8), generator=gen).float()
         got = interpolate_rel_pos(t, L)
-        want = _linear_def(t, L)
+        want = linear_def(t, L)
         assert got.dtype == torch.float32 and got.shape == (L, 8)
         assert np.array_equal(got.numpy().astype(np.float64), want), (L0, L)
     # downsampling by 2 averages neighbouring rows; upsampling keeps the end rows (clamped neighbours)
@@ -151,7 +117,7 @@ def test_interpolate_rel_pos_host_definition():
         # moves the weight by as much and the result by that times |t[i1] - t[i0]| <= 2 max|t|; plus the fp32 blend itself
         tmax, L0 = float(t.abs().max()), 2 * g0 - 1
         assert float((got - f32).abs().max()) <= (3 * 2.0 ** -24 * L0) * 2 * tmax + 4 * 2.0 ** -24 * tmax, (g0, g)
-        want = _linear_def(t, 2 * g - 1)
+        want = linear_def(t, 2 * g - 1)
         assert within_half_ulp(got, want), (g0, g)
     # identity at L == L0: the table itself
     t = torch.randn(27, 64, generator=gen)

@@ -7,47 +7,23 @@ References and gates are the existing ones: the float64 attention reference and 
 oracle fed tables resampled on the host in float64 (vdr.weights.sam_tables_at; checked against transformers on the CPU in
 tests/test_sam_size_cpu.py)."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
 import torch
 
+import handle_configs as hc
+from fixtures import ops  # noqa: F401
+from model_gates import check_batch_properties, check_parity, check_parity_fp8, gate_l2, gate_l2_fp8, min_cos, rel_l2
+from ops_checks import BF16_EPS, assert_close, assert_unbiased, bf, relpos_attn_ref
 from oracle import sam_oracle as so
+from sam_size_ref import golden_cases, linear_def, within_half_ulp
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def ops():
-    import vdr  # noqa: F401
-    from vdr import ops as _ops
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return _ops
-
-
-def _vc(cfg, **kw):
-    import vdr
-    return vdr.VdrConfig(img=cfg.img, patch=cfg.patch, in_chans=3, dim=cfg.dim, heads=cfg.heads, layers=cfg.layers,
-                         mlp_hidden=cfg.mlp_hidden, has_cls=False, has_pos=True, ln_eps=cfg.ln_eps, window=cfg.window,
-                         global_blocks=tuple(cfg.global_idx), neck_chans=cfg.out_chans, **kw)
-
-
-def _engine(cfg, w, **kw):
-    import vdr
-    e = vdr.Engine(_vc(cfg, **kw))
-    e.load_weights(w)
-    return e
-
-
-def _sized(cfg, side):
-    return so.SamCfg(side, cfg.patch, 3, cfg.dim, cfg.heads, cfg.layers, cfg.mlp_hidden, cfg.window, tuple(cfg.global_idx),
-                     cfg.out_chans, cfg.ln_eps)
-
-
 # ---- 1. the resampling kernel -----------------------------------------------------------------------------------
 def test_interpolate_rel_pos_kernel(ops):
-    from test_sam_size_cpu import _linear_def, within_half_ulp
     from vdr.weights import interpolate_rel_pos
     gen = torch.Generator().manual_seed(7)
     # integer tables, dyadic weights: exact
@@ -55,14 +31,14 @@ def test_interpolate_rel_pos_kernel(ops):
         t = torch.randint(-64, 64, (L0, 64), generator=gen).float()
         got = ops.interpolate_rel_pos(t.cuda(), L).cpu()
         assert got.shape == (L, 64) and got.dtype == torch.float32
-        assert np.array_equal(got.double().numpy(), _linear_def(t, L)), (L0, L)
+        assert np.array_equal(got.double().numpy(), linear_def(t, L)), (L0, L)
     # random tables at SAM lengths, channel counts that are no multiple of the workgroup: half an fp32 ulp of the float64
     # definition, and the host statement of it
     for g0, g, D in ((64, 32, 64), (64, 16, 64), (64, 48, 64), (14, 9, 64), (14, 20, 64), (10, 15, 64), (7, 64, 64), (64, 1, 64),
                      (1, 5, 64), (64, 33, 80), (14, 57, 3)):
         t = torch.randn(2 * g0 - 1, D, generator=gen)
         got = ops.interpolate_rel_pos(t.cuda(), 2 * g - 1).cpu()
-        assert within_half_ulp(got, _linear_def(t, 2 * g - 1)), (g0, g, D)
+        assert within_half_ulp(got, linear_def(t, 2 * g - 1)), (g0, g, D)
         host = interpolate_rel_pos(t, 2 * g - 1)
         assert float((got - host).abs().max()) <= float(np.spacing(np.float32(t.abs().max()))), (g0, g, D)
 
@@ -71,15 +47,14 @@ def test_interpolate_rel_pos_kernel(ops):
 @pytest.mark.parametrize("B,S,H", [(2, 5, 2), (3, 9, 1), (2, 12, 2), (2, 20, 3), (1, 33, 2), (1, 48, 1), (1, 57, 2), (2, 32, 12),
                                    (3, 1, 2), (2, 16, 2), (1, 63, 1)])
 def test_attention_relpos_any_grid_side(ops, B, S, H):
-    from test_ops_gpu import BF16_EPS, _assert_close, _assert_unbiased, _bf, _relpos_attn_ref
     g = torch.Generator().manual_seed(S * 100 + B)
-    qkv = _bf(torch.randn(B * S * S, 3 * H * 64, generator=g))
+    qkv = bf(torch.randn(B * S * S, 3 * H * 64, generator=g))
     rel_h = torch.randn(2 * S - 1, 64, generator=g) * 0.1
     rel_w = torch.randn(2 * S - 1, 64, generator=g) * 0.1
-    ref = _relpos_attn_ref(qkv, rel_h, rel_w, B, S, H)
+    ref = relpos_attn_ref(qkv, rel_h, rel_w, B, S, H)
     out = ops.attention_relpos(qkv.cuda(), rel_h.cuda(), rel_w.cuda(), B, S, H)
-    _assert_close(out, ref, 2 * BF16_EPS, 6e-3, f"relpos attention B{B} S{S} H{H}")
-    _assert_unbiased(out, ref, f"relpos attention B{B} S{S} H{H}")
+    assert_close(out, ref, 2 * BF16_EPS, 6e-3, f"relpos attention B{B} S{S} H{H}")
+    assert_unbiased(out, ref, f"relpos attention B{B} S{S} H{H}")
 
 
 # ---- 3. a designed input that must come out bit for bit ------------------------------------------------------------
@@ -110,63 +85,57 @@ def test_attention_relpos_designed_shift_is_exact(ops, g, s, t):
 
 
 # ---- 4. small models at other sizes ---------------------------------------------------------------------------------
-def _golden(golden_dir):
-    from test_sam_size_cpu import golden_cases
-    return golden_cases(golden_dir)
-
-
 @pytest.mark.parametrize("n", range(7))
 def test_sam_small_models_at_other_sizes(golden_dir, n):
     """The transformers fixtures' models, native tables loaded as they are into an encoder built at another size: tokens and
     neck output against the fp32 and the bf16-emulating oracle (host-resampled tables) at test_sam_encoder_small's gates,
     and the neck output against transformers at test_sam_golden_transformers_crosscheck's."""
     import vdr
-    from test_model_gpu import _gate, _min_cos, _rel_l2, gate_l2
     from vdr.weights import sam_tables_at
-    cn, cs, batch, wseed, xseed, wscale, want = _golden(golden_dir)[n]
+    cn, cs, batch, wseed, xseed, wscale, want = golden_cases(golden_dir)[n]
     w0 = so.make_weights(cn, seed=wseed, scale=wscale)
     ws = sam_tables_at(w0, cs.grid, cs.global_idx)
     x = so.make_images(cs, batch, seed=xseed)
     ref = so.sam_forward(cs, ws, x)
     emu = so.sam_forward(cs, ws, x, emulate_bf16=True)
-    e = _engine(cs, w0)  # NATIVE tables: pos_embed [1, g0, g0, D], rel_pos [2 g0 - 1, 64] in the global blocks
+    e = hc.sam_engine(cs, w0)  # NATIVE tables: pos_embed [1, g0, g0, D], rel_pos [2 g0 - 1, 64] in the global blocks
     g = cs.grid
     name = f"{cn.img} -> {cs.img}"
     tok = e.forward(x.cuda(), vdr.OUT_TOKENS)
-    _gate(tok, ref["tokens"].reshape(batch, g * g, cs.dim), emu["tokens"].reshape(batch, g * g, cs.dim), gate_l2(cs.layers),
-          gate_l2(cs.layers), f"sam {name} tokens")
+    check_parity(tok, ref["tokens"].reshape(batch, g * g, cs.dim), f"sam {name} tokens", gate_l2(cs.layers),
+                 emu["tokens"].reshape(batch, g * g, cs.dim))
     out = e.forward(x.cuda(), vdr.OUT_ENCODER)
     assert out.shape == (batch, g, g, cs.out_chans)
-    _gate(out, ref["out"].permute(0, 2, 3, 1), emu["out"].permute(0, 2, 3, 1), gate_l2(cs.layers) + 4e-3,
-          gate_l2(cs.layers) + 4e-3, f"sam {name} neck output")
+    check_parity(out, ref["out"].permute(0, 2, 3, 1), f"sam {name} neck output", gate_l2(cs.layers) + 4e-3,
+                 emu["out"].permute(0, 2, 3, 1))
     got = out.permute(0, 3, 1, 2)[:, :want.shape[1]].cpu()
-    r, c = _rel_l2(got, want), _min_cos(got.permute(0, 2, 3, 1), want.permute(0, 2, 3, 1))
+    r, c = rel_l2(got, want), min_cos(got.permute(0, 2, 3, 1), want.permute(0, 2, 3, 1))
     print(f"sam {name} vs transformers: relL2 {r:.3e} min cos {c:.6f}")
     assert r <= gate_l2(cs.layers) + 4e-3
     assert c >= 0.999
     # the device resampling is the host definition: a handle given the host-resampled tables computes the same bits
-    assert torch.equal(out, _engine(cs, ws).forward(x.cuda(), vdr.OUT_ENCODER))
+    assert torch.equal(out, hc.sam_engine(cs, ws).forward(x.cuda(), vdr.OUT_ENCODER))
 
 
 @pytest.mark.parametrize("n", [2, 4])
 def test_sam_small_models_at_other_sizes_fp8(golden_dir, n):
     import vdr
-    from test_model_gpu import _gate_fp8
     from vdr.weights import sam_tables_at
-    cn, cs, _, wseed, xseed, wscale, _ = _golden(golden_dir)[n]
+    cn, cs, _, wseed, xseed, wscale, _ = golden_cases(golden_dir)[n]
     batch = 2
     w0 = so.make_weights(cn, seed=wseed, scale=wscale)
     ws = sam_tables_at(w0, cs.grid, cs.global_idx)
     x = so.make_images(cs, batch, seed=xseed)
     ref = so.sam_forward(cs, ws, x)
     emx = so.sam_forward(cs, ws, x, emulate_bf16="mx")
-    e = _engine(cs, w0, fp8=1)
+    e = hc.sam_engine(cs, w0, fp8=1)
     g = cs.grid
     tok = e.forward(x.cuda(), vdr.OUT_TOKENS)
-    _gate_fp8(tok, ref["tokens"].reshape(batch, g * g, cs.dim), emx["tokens"].reshape(batch, g * g, cs.dim), cs.layers,
-              f"sam fp8 {cn.img} -> {cs.img} tokens")
+    check_parity_fp8(tok, ref["tokens"].reshape(batch, g * g, cs.dim), emx["tokens"].reshape(batch, g * g, cs.dim), cs.layers,
+                     f"sam fp8 {cn.img} -> {cs.img} tokens")
     out = e.forward(x.cuda(), vdr.OUT_ENCODER)
-    _gate_fp8(out, ref["out"].permute(0, 2, 3, 1), emx["out"].permute(0, 2, 3, 1), cs.layers, f"sam fp8 {cn.img} -> {cs.img} neck output")
+    check_parity_fp8(out, ref["out"].permute(0, 2, 3, 1), emx["out"].permute(0, 2, 3, 1), cs.layers,
+                     f"sam fp8 {cn.img} -> {cs.img} neck output")
     assert torch.equal(out, e.forward(x.cuda(), vdr.OUT_ENCODER))
 
 
@@ -176,11 +145,11 @@ def test_native_checkpoint_at_its_native_size_is_bitwise_unchanged():
     cfg = so.SamCfg(img=224, patch=16, dim=128, heads=2, layers=2, mlp_hidden=256, window=7, global_idx=(1,), out_chans=64)
     w = so.make_weights(cfg, seed=21, scale=0.05)
     x = so.make_images(cfg, 2, seed=22).cuda()
-    plain = _engine(cfg, w).forward(x, vdr.OUT_ENCODER)
+    plain = hc.sam_engine(cfg, w).forward(x, vdr.OUT_ENCODER)
     # a handle that was first given tables of ANOTHER native grid (kept for resampling), then the ones of its own shape:
     # the loaded tables themselves are used, no resampling step
-    other = so.make_weights(_sized(cfg, 320), seed=5, scale=0.05)
-    e = vdr.Engine(_vc(cfg))
+    other = so.make_weights(hc.sized_sam(cfg, 320), seed=5, scale=0.05)
+    e = vdr.Engine(hc.sam_config(cfg))
     e.load_weights({**w, "pos_embed": other["pos_embed"], "blocks.1.attn.rel_pos_h": other["blocks.1.attn.rel_pos_h"],
                     "blocks.1.attn.rel_pos_w": other["blocks.1.attn.rel_pos_w"]})
     assert not torch.equal(plain, e.forward(x, vdr.OUT_ENCODER))
@@ -195,10 +164,9 @@ def test_medsam_vit_b_geometry_at_other_sizes(side):
     -- pos_embed [1, 64, 64, 768], rel_pos [127, 64] -- loaded into an encoder built at 256^2 / 512^2 / 768^2, the depth cut
     to (window, window, global) so that the CPU oracle stays in seconds."""
     import vdr
-    from test_model_gpu import _gate, gate_l2
     from vdr.weights import sam_tables_at
     cn = so.SamCfg(layers=3, global_idx=(2,))
-    cs = _sized(cn, side)
+    cs = hc.sized_sam(cn, side)
     g = cs.grid
     w0 = so.make_weights(cn, seed=23)
     assert tuple(w0["pos_embed"].shape) == (1, 64, 64, 768) and tuple(w0["blocks.2.attn.rel_pos_h"].shape) == (127, 64)
@@ -211,11 +179,11 @@ def test_medsam_vit_b_geometry_at_other_sizes(side):
     model = vdr.VitDescriptorModel(vc, w0, "medsam", sized=True)
     enc = model.image_encoder(x.cuda())
     assert enc.shape == (B, 256, g, g)
-    _gate(enc.permute(0, 2, 3, 1), ref["out"].permute(0, 2, 3, 1), emu["out"].permute(0, 2, 3, 1), gate_l2(3) + 4e-3,
-          gate_l2(3) + 4e-3, f"ViT-B geometry at {side}^2 neck output")
+    check_parity(enc.permute(0, 2, 3, 1), ref["out"].permute(0, 2, 3, 1), f"ViT-B geometry at {side}^2 neck output",
+                 gate_l2(3) + 4e-3, emu["out"].permute(0, 2, 3, 1))
     tok = model.engine.forward(x.cuda(), vdr.OUT_TOKENS)
-    _gate(tok, ref["tokens"].reshape(B, g * g, 768), emu["tokens"].reshape(B, g * g, 768), gate_l2(3), gate_l2(3),
-          f"ViT-B geometry at {side}^2 tokens")
+    check_parity(tok, ref["tokens"].reshape(B, g * g, 768), f"ViT-B geometry at {side}^2 tokens", gate_l2(3),
+                 emu["tokens"].reshape(B, g * g, 768))
     # a raw gray slice goes straight to the model's side (one skimage-semantics resize, not 1024 first)
     from oracle import prep_oracle as po
     raw = np.random.default_rng(side).random((300, 280)).astype(np.float32)
@@ -223,7 +191,7 @@ def test_medsam_vit_b_geometry_at_other_sizes(side):
     assert f.shape == (g, g, 256) and f.dtype == np.float32
     direct = torch.from_numpy(po.prepare_image(raw, side=side))[None]
     want = so.sam_forward(cs, ws, direct)["out"][0].permute(1, 2, 0)
-    _gate(torch.from_numpy(f), want, want, gate_l2(3) + 4e-3, gate_l2(3) + 4e-3, f"get_dense_descriptor at {side}^2")
+    check_parity(torch.from_numpy(f), want, f"get_dense_descriptor at {side}^2", gate_l2(3) + 4e-3, want)
     # a prepared image of the model's side is taken as it is
     np.testing.assert_array_equal(vdr.get_dense_descriptor(model, x[0].numpy()), np.transpose(enc[0].cpu().numpy(), (1, 2, 0)))
 
@@ -233,11 +201,9 @@ def test_medsam_vit_b_512_all_twelve_blocks(fp8):
     """load_model('medsam', img_size=512): the whole SAM ViT-B image encoder (12 blocks, global blocks 2 / 5 / 8 / 11 over
     32 x 32 tokens) with the native 1024^2 tables, at test_medsam_vit_b_1024_all_twelve_blocks's gates."""
     import vdr
-    from test_fullsize_gpu import _check
-    from test_model_gpu import gate_l2
     from vdr.weights import sam_tables_at
     cn = so.SAM_VIT_B
-    cs = _sized(cn, 512)
+    cs = hc.sized_sam(cn, 512)
     w0 = so.make_weights(cn, seed=1)
     x = so.make_images(cs, 1, seed=3)
     ref = so.sam_forward(cs, sam_tables_at(w0, 32, cs.global_idx), x)["out"].permute(0, 2, 3, 1)
@@ -246,9 +212,9 @@ def test_medsam_vit_b_512_all_twelve_blocks(fp8):
     got = m.engine.forward(x.cuda(), vdr.OUT_ENCODER, torch.float32)
     assert got.shape == (1, 32, 32, 256)
     if fp8:
-        _check(got, ref, 4e-2 + 4e-2 * math.sqrt(12), 0.99, "MedSAM 512^2 L=12 MX-fp8 neck output")
+        check_parity(got, ref, "MedSAM 512^2 L=12 MX-fp8 neck output", gate_l2_fp8(12), cos=0.99)
     else:
-        _check(got, ref, gate_l2(12), 0.999, "MedSAM 512^2 L=12 neck output")
+        check_parity(got, ref, "MedSAM 512^2 L=12 neck output", gate_l2(12))
     xb = torch.cat([x, so.make_images(cs, 2, seed=4)]).cuda()
     outb = m.engine.forward(xb, vdr.OUT_ENCODER, torch.float32)
     assert torch.equal(outb[0], got[0])
@@ -261,19 +227,14 @@ def test_medsam_vit_b_512_all_twelve_blocks(fp8):
 def test_batch_properties_at_a_new_size(fp8):
     import vdr
     cn = so.SamCfg(img=224, patch=16, dim=128, heads=2, layers=3, mlp_hidden=256, window=7, global_idx=(0, 2), out_chans=64)
-    cs = _sized(cn, 288)  # grid 18: padded windows, 324 tokens = 2 full key chunks + a ragged one
+    cs = hc.sized_sam(cn, 288)  # grid 18: padded windows, 324 tokens = 2 full key chunks + a ragged one
     w0 = so.make_weights(cn, seed=31, scale=0.05)
-    e = _engine(cs, w0, fp8=fp8)
+    e = hc.sam_engine(cs, w0, fp8=fp8)
     x = so.make_images(cs, 6, seed=32)
     x[5] = x[1]
     x = x.cuda()
-    out = e.forward(x, vdr.OUT_ENCODER)
-    assert torch.isfinite(out).all()
-    assert torch.equal(out[5], out[1]), "duplicate rows"
-    perm = torch.tensor([3, 0, 5, 2, 4, 1])
-    assert torch.equal(e.forward(x[perm.cuda()], vdr.OUT_ENCODER), out[perm.cuda()]), "a permutation permutes the rows"
-    assert torch.equal(e.forward(x[2:3], vdr.OUT_ENCODER), out[2:3]), "a row does not depend on its batch"
-    assert torch.equal(_engine(cs, w0, fp8=fp8, micro_batch=4).forward(x, vdr.OUT_ENCODER), out)
+    out = check_batch_properties(lambda t: e.forward(t, vdr.OUT_ENCODER), x, small=1, perm=[3, 0, 5, 2, 4, 1], lo=2)
+    assert torch.equal(hc.sam_engine(cs, w0, fp8=fp8, micro_batch=4).forward(x, vdr.OUT_ENCODER), out)
 
 
 # ---- 8. graph capture -----------------------------------------------------------------------------------------------------
@@ -282,10 +243,10 @@ def test_forward_at_a_new_size_is_graph_capturable():
     synchronises, and its replay reproduces an eager forward bit for bit."""
     import vdr
     cn = so.SamCfg(img=224, patch=16, dim=128, heads=2, layers=2, mlp_hidden=256, window=7, global_idx=(1,), out_chans=64)
-    cs = _sized(cn, 176)
+    cs = hc.sized_sam(cn, 176)
     w0 = so.make_weights(cn, seed=41, scale=0.05)
     x = so.make_images(cs, 3, seed=42).cuda()
-    e = _engine(cs, w0)
+    e = hc.sam_engine(cs, w0)
     out = torch.empty((3, 11, 11, 64), dtype=torch.float32, device="cuda")
     e._workspace(3)
     graph = torch.cuda.CUDAGraph()
@@ -298,7 +259,7 @@ def test_forward_at_a_new_size_is_graph_capturable():
     out.zero_()
     graph.replay()
     torch.cuda.synchronize()
-    assert torch.equal(out, _engine(cs, w0).forward(x, vdr.OUT_ENCODER))
+    assert torch.equal(out, hc.sam_engine(cs, w0).forward(x, vdr.OUT_ENCODER))
 
 
 # ---- 9. generate_features takes the side and the grid from the model -----------------------------------------------------------
@@ -308,9 +269,9 @@ def test_generate_features_at_a_reduced_geometry():
     from vdr import pipeline, prep
     from vdr.weights import sam_tables_at
     cn = so.SamCfg(img=224, patch=16, dim=128, heads=2, layers=2, mlp_hidden=256, window=7, global_idx=(1,), out_chans=64)
-    cs = _sized(cn, 144)
+    cs = hc.sized_sam(cn, 144)
     w0 = so.make_weights(cn, seed=21)
-    model = vdr.VitDescriptorModel(_vc(cs), w0, "medsam", torch.device("cuda"), sized=True)
+    model = vdr.VitDescriptorModel(hc.sam_config(cs), w0, "medsam", torch.device("cuda"), sized=True)
     rng = np.random.default_rng(8)
     H, W, S = 72, 80, 5
     img = rng.random((H, W, S)).astype(np.float32)

@@ -13,12 +13,12 @@ import torch
 
 import handle_configs as hc
 import spectral_ref as sref
+from handle_configs import TINY
 from oracle import vit_oracle as vo
 from spectral_ref import NAMES, labels_agree, load_golden
 
 pytestmark = pytest.mark.gpu
 
-TINY = vo.VitCfg(32, 8, 3, 64, 1, 2, 128)
 
 # name: (|lambda - golden|, 1 - |cos|) as first measured on the device
 MEASURED = {"130x32": (1.063e-08, 9.548e-15), "333x96": (3.743e-09, 7.772e-16), "520x416": (1.540e-08, 9.659e-15)}
@@ -26,13 +26,8 @@ MEASURED = {"130x32": (1.063e-08, 9.548e-15), "333x96": (3.743e-09, 7.772e-16), 
 
 @pytest.fixture(scope="module")
 def model():
-    import vdr
-    name = "_spectral_tiny"
-    vdr.ARCHS[name] = hc.vit_config(TINY)
-    try:
-        yield vdr.load_model(name, weights=vo.make_weights(TINY, seed=21, scale=0.05))
-    finally:
-        del vdr.ARCHS[name]
+    with hc.registered_model("_spectral_tiny") as m:
+        yield m
 
 
 @pytest.fixture(scope="module")

@@ -12,15 +12,10 @@ import pytest
 import torch
 
 import upsample_ref as ur
+from fixtures import lib  # noqa: F401
 
 PS = ((16, 16), (14, 14), (16, 8), (14, 7), (16, 4), (8, 8))
 INVALID, NO_DEVICE, UNSUPPORTED = -1, -2, -7
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from vdr import _lib
-    return _lib.load()
 
 
 def _aligned(n=4096):

@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import upsample_ref as ur
+from fixtures import ops  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -26,12 +27,6 @@ GRIDS = ((1, 1), (2, 3), (5, 4), (9, 11))
 RS = (1, 2, 3)
 CS = (8, 32, 136, 264)
 DEV = "cuda"
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from vdr import ops
-    return ops
 
 
 def _cases():

@@ -25,8 +25,7 @@ if __name__ == "__main__":  # (--record: the paths tests/conftest.py sets up und
         if _p not in sys.path:
             sys.path.insert(0, _p)
 
-from handle_configs import reg_cfg, sam_config, vit_config  # noqa: E402
-from test_launch_ledger_gpu import P16, POSTLN, SAM, SWIGLU  # noqa: E402
+from handle_configs import P16, POSTLN, SAM, SWIGLU, reg_cfg, sam_config, vit_config  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 

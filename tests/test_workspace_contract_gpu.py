@@ -27,8 +27,11 @@ import os
 import pytest
 import torch
 
+import clip_ref as cr
+import forward_cases as fc
+import handle_configs as hc
 import memguard as mg
-import test_launch_ledger_gpu as ledger
+from handle_configs import P16, POSTLN, SAM
 from oracle import sam_oracle as so
 from oracle import vit_oracle as vo
 
@@ -76,13 +79,13 @@ class Workspaces:
 
 # ---- cases the ledger does not have -----------------------------------------------------------------------------------------
 def _p16(**kw):
-    return ledger._vit_engine(ledger.P16, vo.make_weights(ledger.P16, seed=3, scale=0.05), **kw)
+    return hc.engine(P16, vo.make_weights(P16, seed=3, scale=0.05), **kw)
 
 
 def _facets():
     import vdr
     e = _p16()
-    x = vo.make_images(ledger.P16, 3, seed=4).cuda()
+    x = vo.make_images(P16, 3, seed=4).cuda()
 
     def run():
         f, feats, maps = e.forward_descriptors(x, [vdr.FacetOut(1, "key", hierarchy=2), vdr.FacetOut(2, "token", all_rows=True),
@@ -95,8 +98,8 @@ def _facets():
 def _half_stride():
     import vdr
     e = _p16()
-    e.set_patch_stride(ledger.P16.patch // 2)  # 7 x 7 overlapping patches: the col buffer grows
-    x = vo.make_images(ledger.P16, 3, seed=4).cuda()
+    e.set_patch_stride(P16.patch // 2)  # 7 x 7 overlapping patches: the col buffer grows
+    x = vo.make_images(P16, 3, seed=4).cuda()
     return e, lambda: [e.forward(x, vdr.OUT_DENSE), e.forward(x, vdr.OUT_CLS)]
 
 
@@ -110,8 +113,7 @@ def _other_size():
 
 def _tower(family):
     def make():
-        from test_clip_model_gpu import _tiny
-        g, cfg, w, model = _tiny(os.path.join(ledger.HERE, "golden"), family)
+        g, cfg, w, model = cr.tiny_model(os.path.join(hc.HERE, "golden"), family)
         x = vo.make_images(cfg, 3, seed=8).cuda()
         return model.engine, lambda: [model.get_image_features(x)]
     return make
@@ -119,9 +121,8 @@ def _tower(family):
 
 def _sam_resized():
     import vdr
-    from test_sam_size_gpu import _engine, _sized
-    cs = _sized(ledger.SAM, 112)  # native 160: a 7 x 7 grid, ragged 4 x 4 windows, resampled position tables
-    e = _engine(cs, so.make_weights(ledger.SAM, seed=21, scale=0.05))
+    cs = hc.sized_sam(SAM, 112)  # native 160: a 7 x 7 grid, ragged 4 x 4 windows, resampled position tables
+    e = hc.sam_engine(cs, so.make_weights(SAM, seed=21, scale=0.05))
     x = so.make_images(cs, 2, seed=22).cuda()
     return e, lambda: [e.forward(x, vdr.OUT_ENCODER)]
 
@@ -131,9 +132,9 @@ VARLEN = [5, 1, 17, 9]
 
 def _postln_varlen_tokens():
     import vdr
-    e = ledger._vit_engine(ledger.POSTLN, vo.make_weights(ledger.POSTLN, seed=13, scale=0.05))
-    x = vo.make_tokens(4, 17, ledger.POSTLN.dim, seed=14).cuda()
-    c = 1 if ledger.POSTLN.has_cls else 0
+    e = hc.engine(POSTLN, vo.make_weights(POSTLN, seed=13, scale=0.05))
+    x = vo.make_tokens(4, 17, POSTLN.dim, seed=14).cuda()
+    c = 1 if POSTLN.has_cls else 0
 
     def run():  # rows past a sequence's length are undefined (vdr.h): the defined rows only
         t = e.forward_tokens(x, vdr.OUT_TOKENS, lengths=VARLEN)
@@ -144,12 +145,12 @@ def _postln_varlen_tokens():
 
 EXTRA = {"facets-binned": _facets, "patch_stride-half": _half_stride, "input_size-96x48": _other_size, "clip-tower": _tower("clip"),
          "siglip-tower": _tower("siglip"), "sam-resized-112": _sam_resized, "postln-varlen-all_rows": _postln_varlen_tokens}
-CASES = list(ledger.CASE_IDS) + list(EXTRA)
-TWO_STREAMS = [c for c in ledger.CASE_IDS if "mb2_streams2" in c]
+CASES = list(fc.CASE_IDS) + list(EXTRA)
+TWO_STREAMS = [c for c in fc.CASE_IDS if "mb2_streams2" in c]
 
 
 def _maker(case):
-    return EXTRA[case] if case in EXTRA else ledger._cases()[case]
+    return EXTRA[case] if case in EXTRA else fc.cases()[case]
 
 
 def _snapshot(outs):
@@ -230,8 +231,8 @@ def test_short_workspace_refused_by_every_entry_point_outputs_untouched():
     e = _p16()
     ws = Workspaces(e)
     ws.fill, ws.short = None, 256
-    B, D, N, n, H = 3, ledger.P16.dim, e.n_tokens, e.n_patches, ledger.P16.heads
-    x = vo.make_images(ledger.P16, B, seed=4).cuda()
+    B, D, N, n, H = 3, P16.dim, e.n_tokens, e.n_patches, P16.heads
+    x = vo.make_images(P16, B, seed=4).cuda()
     outs = {k: _canary(s, torch.float32) for k, s in dict(cls=(B, D), tokens=(B, N, D), map=(B, H, 1, N), facet=(B, n, D)).items()}
     lo = lambda: vdr.LayerOut(1, vdr.OUT_CLS, out=outs["cls"])  # noqa: E731
     calls = {
@@ -246,10 +247,10 @@ def test_short_workspace_refused_by_every_entry_point_outputs_untouched():
             call()
         assert err.value.code == VDR_ERR_WORKSPACE, (name, err.value)
     # the token entry points: Engine.forward_tokens allocates its output itself, so the C calls are made here
-    t = ledger._vit_engine(ledger.POSTLN, vo.make_weights(ledger.POSTLN, seed=13, scale=0.05))
+    t = hc.engine(POSTLN, vo.make_weights(POSTLN, seed=13, scale=0.05))
     tws = Workspaces(t)
     tws.fill, tws.short = None, 256
-    Bt, S, Dt = 4, 17, ledger.POSTLN.dim
+    Bt, S, Dt = 4, 17, POSTLN.dim
     tok = vo.make_tokens(Bt, S, Dt, seed=14).float().cuda().contiguous()
     tout = _canary((Bt, Dt), torch.float32)
     lens = torch.tensor(VARLEN, dtype=torch.int32, device="cuda")
