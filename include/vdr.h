@@ -811,6 +811,47 @@ int vdr_op_local_correlation(const void* x, int64_t ldx, int64_t x_stride, const
                              int pairs, int gh, int gw, int d, int radius, int transposed, void* work,
                              float* cost, float* best_sim, int32_t* best_idx, void* stream);
 
+/* Multi-source soft window vote (csrc/window_vote.hip): DINO's label propagation step for one target map against S source
+ * maps -- the annotated slice and the last few propagated ones --, soft labels in and out.  For each of `problems` problems
+ * on one gh x gw grid, t = gh * gw, W = 2 * radius + 1:
+ *   cost [problems, sources, t, W * W] fp32: the S cost volumes of the target against its sources, as
+ *     vdr_op_local_correlation writes them (slot w = (dy + radius) * W + (dx + radius)); one call of it with pairs = S, the
+ *     target at x_stride = 0 and the sources y_stride apart writes a problem's block.
+ *   src  [problems, sources, t, n_classes] fp32: the class scores of the source patches, finite and non-negative by
+ *     contract; one-hot rows are hard labels.
+ * Definition, for query i = (qy, qx) of problem p:
+ *   candidates  the pairs (s, w) whose position (qy + dy, qx + dx) is inside the grid -- decided from (gh, gw, radius); the
+ *               values of the other slots are never read.  Candidate (s, w) has the patch index j = (qy + dy) * gw + (qx + dx)
+ *               and the value cost[p, s, i, w].
+ *   order       greater value first, then lower s, then lower w: total.  The neighbours m = 0 .. k-1 are the first k
+ *               candidates under it (exact fp32 comparisons; nothing is rounded).
+ *   weights     VDR_VOTE_SOFTMAX: e_m = expf((v_m - v_0) * inv_t), inv_t = 1.0f / temperature rounded once, the subtraction
+ *               and the multiplication one fp32 rounding each; expf is the device math library's, whose error is at most
+ *               1 ulp (a relative error of at most 2^-23; results below 2^-126 may be flushed to 0), and expf(0) = 1
+ *               exactly, so e_0 is 1.0f.  VDR_VOTE_UNIFORM: e_m = 1 (temperature is checked all the same).
+ *   scores[p, i, c] = (sum_m e_m * src[p, s_m, j_m, c]) / (sum_m e_m): every product rounded before it is added, both sums
+ *               in fp32 ascending in m starting from the first term, one IEEE division per class.  ([problems, t, n_classes])
+ *   labels[p, i] = the lowest c that attains the largest scores[p, i, c]                              ([problems, t] int32)
+ *   idx[p, i, m] = s_m * t + j_m, a row of the problem's [sources * t, n_classes] src; val[p, i, m] = v_m  ([problems, t, k])
+ * labels may be NULL; idx and val may be NULL, but only together.  No atomics; every entry has exactly one writer; a
+ * problem's bits depend on (gh, gw, radius, sources, k, n_classes, weights, temperature, inputs) only -- not on `problems`,
+ * on its position in the batch or on a launch heuristic.  No scratch memory is needed.
+ * Refused before the device is touched, in this order: VDR_ERR_INVALID for a null cost, src or scores, non-positive
+ * problems, sources, gh, gw or n_classes, pointers that are not 16-byte aligned, problems * sources * gh * gw above
+ * 2^31 - 1; VDR_ERR_UNSUPPORTED for sources above VDR_WINDOW_VOTE_MAX_SOURCES, a radius outside 1 ..
+ * VDR_LOCAL_CORR_MAX_RADIUS, k outside 1 .. VDR_WINDOW_VOTE_MAX_K, n_classes above VDR_WINDOW_VOTE_MAX_CLASSES;
+ * VDR_ERR_INVALID for k above sources * min(gh, radius + 1) * min(gw, radius + 1) (the candidates of a corner patch: a slot
+ * outside the grid is never selected), weights that are neither constant, a temperature that is not positive or not finite,
+ * exactly one of idx / val null, an element count of cost or src above 2^31 - 1 (idx and val have fewer than cost). */
+#define VDR_WINDOW_VOTE_MAX_SOURCES 8
+#define VDR_WINDOW_VOTE_MAX_K 16
+#define VDR_WINDOW_VOTE_MAX_CLASSES 64
+#define VDR_VOTE_SOFTMAX 0
+#define VDR_VOTE_UNIFORM 1
+int vdr_op_window_vote(const float* cost, const float* src, int problems, int sources, int gh, int gw, int radius, int k,
+                       int n_classes, int weights, float temperature, float* scores, int32_t* labels, int32_t* idx, float* val,
+                       void* stream);
+
 /* Thresholded affinity graph of a descriptor map, one bit per pair (csrc/affinity.hip): for each of `pairs` problems the
  * graph B[i, j] = cos(x_i, x_j) > tau over the rows of X_p, without the t x t matrix of scores ever being written.
  *   X_p = [t, d] bf16, rows ldx elements apart, starting at x + p * x_stride (0 allowed).

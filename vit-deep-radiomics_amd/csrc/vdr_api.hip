@@ -2240,11 +2240,14 @@ static int refuse(const char* op, int code, const std::string& what) { return fa
 // A descriptor map as the descriptor ops take it (include/vdr.h): `problems` problems of `imgs` images of `t` rows of `d`
 // channels, the rows `ld`, the images `image_stride`, the problems `problem_stride` elements apart.  An op without an image
 // level passes imgs = 1 and image_stride = 0, one without a problem stride 0, a bf16-only op in_dtype = VDR_BF16.
+// `packed`: a dense tensor that is read element by element and is no MFMA operand (window_vote's class scores): d is any
+// positive count, and of the rows and strides nothing is asked -- only the base pointers are 16-byte aligned.
 struct DescOperand {
   const void* x;
   int in_dtype;
   int64_t ld, image_stride, problem_stride;
   int problems, imgs, t, d;
+  bool packed = false;
 };
 // what the op's signature calls the sizes, the row stride, the other strides and the row count of all problems
 struct DescNames {
@@ -2255,11 +2258,14 @@ static const DescNames GRAM_NAMES = {"problems, t and d", "ld", "image_stride", 
 static const DescNames KMEANS_NAMES = {"problems, imgs, t and d", "ld", "the strides", "problems * R"};
 static const DescNames NN_NAMES = {"pairs, tx, ty and d", "ldx and ldy", "the pair strides", "pairs * max(tx, ty)"};
 static const DescNames LOCAL_NAMES = {"pairs, gh, gw and d", "ldx and ldy", "the pair strides", "pairs * gh * gw"};
+static const DescNames WINDOW_VOTE_NAMES = {"problems, sources, gh, gw and n_classes", "n_classes", "the strides",
+                                            "problems * sources * gh * gw"};
 static const DescNames AFFINITY_NAMES = {"pairs, t and d", "ldx", "x_stride", "pairs * t"};
 
 // THE operand check of the descriptor ops, in one fixed order: dtype, null pointers, positive sizes, d % 32 (and d <= max_d
-// where max_d > 0), ld >= d and strides >= 0, 16-byte alignment of x, of `required16` (the op's other pointers that must be
-// non-null and 16-byte aligned), of the rows and of both strides, problems * imgs * t <= 2^31 - 1.  What only one op asks
+// where max_d > 0; not of a packed operand), ld >= d and strides >= 0, 16-byte alignment of x, of `required16` (the op's other
+// pointers that must be non-null and 16-byte aligned), of the rows and of both strides (a packed operand: of the pointers
+// alone), problems * imgs * t <= 2^31 - 1.  What only one op asks
 // (k ranges, optional or 4-byte pointers, pitch, ...) stays in that op, after this.
 static int check_desc_operand(const char* op, const DescOperand& o, const DescNames& n, int max_d,
                               std::initializer_list<const void*> required16) {
@@ -2268,11 +2274,12 @@ static int check_desc_operand(const char* op, const DescOperand& o, const DescNa
   for (const void* q : required16) null = null || !q;
   if (null) return refuse(op, VDR_ERR_INVALID, "null pointer");
   if (o.problems <= 0 || o.imgs <= 0 || o.t <= 0 || o.d <= 0) return refuse(op, VDR_ERR_INVALID, std::string(n.sizes) + " must be positive");
-  if (o.d % 32 != 0 || (max_d > 0 && o.d > max_d))
+  if (!o.packed && (o.d % 32 != 0 || (max_d > 0 && o.d > max_d)))
     return refuse(op, VDR_ERR_UNSUPPORTED, "d must be a multiple of 32" + (max_d > 0 ? ", at most " + std::to_string(max_d) : std::string()));
   if (o.ld < o.d || o.image_stride < 0 || o.problem_stride < 0) return refuse(op, VDR_ERR_INVALID, std::string(n.ld) + " must be >= d, " + n.strides + " >= 0");
   const int64_t per16 = o.in_dtype == VDR_BF16 ? 8 : 4;  // elements of a 16-byte chunk
-  if (!aligned16({o.x}) || !aligned16(required16) || o.ld % per16 || o.image_stride % per16 || o.problem_stride % per16)
+  if (o.packed && (!aligned16({o.x}) || !aligned16(required16))) return refuse(op, VDR_ERR_INVALID, "pointers must be 16-byte aligned");
+  if (!o.packed && (!aligned16({o.x}) || !aligned16(required16) || o.ld % per16 || o.image_stride % per16 || o.problem_stride % per16))
     return refuse(op, VDR_ERR_INVALID, std::string("pointers, rows (") + n.ld + ") and " + n.strides + " must be 16-byte aligned");
   const int64_t R = (int64_t)o.imgs * o.t;  // (each factor is a positive int: no overflow; R is bounded before the next product)
   if (R > INT32_MAX || R * o.problems > INT32_MAX) return refuse(op, VDR_ERR_INVALID, std::string(n.rows) + " exceeds 2^31 - 1");
@@ -2801,6 +2808,41 @@ int vdr_op_local_correlation(const void* x, int64_t ldx, int64_t x_stride, const
   RUN_OP(launch_local_correlation(x, ldx, x_stride, y, ldy, y_stride, pairs, gh, gw, d, radius, transposed, work, cost, best_sim,
                                   best_idx, (hipStream_t)stream),
          "local_correlation");
+}
+
+int vdr_op_window_vote(const float* cost, const float* src, int problems, int sources, int gh, int gw, int radius, int k,
+                       int n_classes, int weights, float temperature, float* scores, int32_t* labels, int32_t* idx, float* val,
+                       void* stream) {
+  const char* op = "window_vote";
+  // t as in vdr_op_local_correlation: 0 for a grid that is not positive, capped where gh * gw overflows (refused below)
+  const int64_t t64 = gh > 0 && gw > 0 ? (int64_t)gh * gw : 0;
+  const int t = (int)(t64 > INT32_MAX ? INT32_MAX : t64);
+  if (int rc = check_desc_operand(op, {src, VDR_F32, n_classes, 0, 0, problems, sources, t, n_classes, true}, WINDOW_VOTE_NAMES, 0,
+                                  {cost, scores}))
+    return rc;
+  if (t64 > INT32_MAX) return refuse(op, VDR_ERR_INVALID, "gh * gw exceeds 2^31 - 1");
+  if (sources > VDR_WINDOW_VOTE_MAX_SOURCES)
+    return refuse(op, VDR_ERR_UNSUPPORTED, "sources must be 1 .. " + std::to_string(VDR_WINDOW_VOTE_MAX_SOURCES));
+  if (radius < 1 || radius > VDR_LOCAL_CORR_MAX_RADIUS)
+    return refuse(op, VDR_ERR_UNSUPPORTED, "radius must be 1 .. " + std::to_string(VDR_LOCAL_CORR_MAX_RADIUS));
+  if (k < 1 || k > VDR_WINDOW_VOTE_MAX_K) return refuse(op, VDR_ERR_UNSUPPORTED, "k must be 1 .. " + std::to_string(VDR_WINDOW_VOTE_MAX_K));
+  if (n_classes > VDR_WINDOW_VOTE_MAX_CLASSES)
+    return refuse(op, VDR_ERR_UNSUPPORTED, "n_classes must be 1 .. " + std::to_string(VDR_WINDOW_VOTE_MAX_CLASSES));
+  const int corner = sources * std::min(gh, radius + 1) * std::min(gw, radius + 1);
+  if (k > corner)
+    return refuse(op, VDR_ERR_INVALID, "k exceeds the " + std::to_string(corner) + " in-grid candidates of a corner patch, sources * min(gh, radius + 1) * min(gw, radius + 1)");
+  if (weights != VDR_VOTE_SOFTMAX && weights != VDR_VOTE_UNIFORM)
+    return refuse(op, VDR_ERR_INVALID, "weights must be VDR_VOTE_SOFTMAX or VDR_VOTE_UNIFORM");
+  if (!(temperature > 0.f) || !std::isfinite(temperature)) return refuse(op, VDR_ERR_INVALID, "temperature must be positive and finite");
+  if (!idx != !val) return refuse(op, VDR_ERR_INVALID, "idx and val must both be given or both be null");
+  if (!aligned16({labels, idx, val})) return refuse(op, VDR_ERR_INVALID, "labels, idx and val must be 16-byte aligned");
+  const int64_t rows = (int64_t)problems * sources * t, WW = (int64_t)(2 * radius + 1) * (2 * radius + 1);
+  if (rows > INT32_MAX / WW) return refuse(op, VDR_ERR_INVALID, "problems * sources * gh * gw * (2 radius + 1)^2 exceeds 2^31 - 1");
+  if (rows > INT32_MAX / n_classes) return refuse(op, VDR_ERR_INVALID, "problems * sources * gh * gw * n_classes exceeds 2^31 - 1");
+  // (idx and val have fewer elements than cost: k <= sources * (radius + 1)^2 < sources * (2 radius + 1)^2)
+  RUN_OP(launch_window_vote(cost, src, problems, sources, gh, gw, radius, k, n_classes, weights, temperature, scores, labels, idx, val,
+                            (hipStream_t)stream),
+         "window_vote");
 }
 
 size_t vdr_affinity_work_bytes(int pairs, int t) { return affinity_work_bytes(pairs, t); }

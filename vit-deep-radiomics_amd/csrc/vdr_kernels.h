@@ -337,6 +337,13 @@ hipError_t launch_local_correlation(const void* x, int64_t ldx, int64_t x_stride
                                     int pairs, int gh, int gw, int d, int radius, int transposed, void* work, float* cost,
                                     float* best_sim, int32_t* best_idx, hipStream_t st);
 
+// Multi-source soft window vote (window_vote.hip; the definition is vdr_op_window_vote's in include/vdr.h): cost
+// [problems][sources][t][(2r+1)^2] and src [problems][sources][t][n_classes] fp32 -> scores [problems][t][n_classes], and
+// optionally labels [problems][t], (idx, val) [problems][t][k].  One launch, a wave per query, no scratch memory.
+hipError_t launch_window_vote(const float* cost, const float* src, int problems, int sources, int gh, int gw, int radius, int k,
+                              int n_classes, int weights, float temperature, float* scores, int32_t* labels, int32_t* idx,
+                              float* val, hipStream_t st);
+
 // Thresholded affinity graphs of descriptor maps, one bit per pair (affinity.hip; the definitions are vdr_op_affinity_bits' and
 // vdr_op_bits_matvec's in include/vdr.h): X_p [t, d] bf16, rows ldx elements apart, problems x_stride apart (0 allowed);
 // d % 32 == 0; pointers and strides 16-byte aligned; work: affinity_work_bytes(pairs, t) bytes; bits [pairs][t][pitch] with

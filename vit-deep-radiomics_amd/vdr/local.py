@@ -1,6 +1,7 @@
 """What is done with the cost volume of a windowed correlation (vdr.ops.local_correlation, csrc/local_corr.hip): the k best
 candidates of every patch inside its window -- the (idx, val) lists vdr.knn.vote takes, which is DINO's label propagation
-between slices --, and a soft displacement field.
+between slices --, a soft displacement field, and vote_window: the multi-source soft vote of vdr.ops.window_vote
+(csrc/window_vote.hip) restated in torch, which is what VitDescriptorModel.propagate_volume's kernel is read against.
 
 Plain torch: no kernel is involved, CPU and device tensors both work.  A cost volume is [P, t, W * W] fp32 on a gh x gw grid,
 t = gh * gw, W = 2 * radius + 1; slot (dy + radius) * W + (dx + radius) of row i = qy * gw + qx holds the similarity of patch
@@ -74,3 +75,41 @@ def soft_displacement(cost: torch.Tensor, radius: int, temperature: float = 0.1)
     for s in range(1, off.shape[0]):  # (the sum spelled out in slot order: torch's sum() fixes no order)
         flow = flow + w[..., s, None] * off[s]
     return flow, w.max(dim=-1).values
+
+
+def vote_window(cost: torch.Tensor, src: torch.Tensor, grid, k: int, weights: str = "softmax", temperature: float = 0.1,
+                labels: bool = True, neighbours: bool = True):
+    """vdr.ops.window_vote in plain torch (CPU or device): the statement the kernel is read against, and what runs where there
+    is no device.  cost [P, S, t, W * W] fp32, src [P, S, t, C] fp32 -> (scores [P, t, C] fp32, labels [P, t] int32, idx
+    [P, t, k] int32 holding s * t + j, val [P, t, k] fp32), the op's arguments, refusals and definition (include/vdr.h):
+    the slots outside the grid -- known from the grid, whatever they hold -- are no candidates; a stable descending sort of
+    the concatenated [S * W * W] rows is the order (greater value, then lower source, then lower slot); e_m =
+    exp((v_m - v_0) * (1 / T)) with 1 / T rounded once to fp32, or 1; both sums are spelled out in neighbour order from the
+    first term, and there is one division per class.  Only the exponential may differ from the kernel's, by its error."""
+    from .knn import lowest_argmax
+    from .ops import check_window_vote
+    P, S, gh, gw, r, k, C = check_window_vote("vote_window", cost, src, grid, k, weights, temperature)
+    dev, t, WW = cost.device, gh * gw, (2 * r + 1) ** 2
+    off = offsets(r, dev)
+    i = torch.arange(t, device=dev).unsqueeze(1)
+    cy, cx = torch.div(i, gw, rounding_mode="floor") + off[:, 0], i % gw + off[:, 1]  # [t, W * W]
+    inside = (cy >= 0) & (cy < gh) & (cx >= 0) & (cx < gw)
+    j = cy * gw + cx
+    rows = torch.where(inside, cost, float("-inf")).permute(0, 2, 1, 3).reshape(P, t, S * WW)
+    order = torch.sort(rows, dim=-1, descending=True, stable=True)
+    e, val = order.indices[..., :k], order.values[..., :k].contiguous()
+    s, w = torch.div(e, WW, rounding_mode="floor"), e % WW
+    idx = s * t + torch.gather(j.unsqueeze(0).expand(P, t, WW), 2, w)  # [P, t, k]
+    near = src.reshape(P, S * t, C)[torch.arange(P, device=dev).view(P, 1, 1), idx]  # [P, t, k, C]
+    if weights == "uniform":
+        em = torch.ones_like(val)
+    else:
+        inv_t = float(torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(temperature), dtype=torch.float32))
+        em = torch.exp((val - val[..., :1]) * inv_t)  # (a Python scalar that fp32 holds exactly: one fp32 multiplication)
+    num, den = em[..., 0, None] * near[..., 0, :], em[..., 0]
+    for m in range(1, k):  # (the sums spelled out in neighbour order: torch's sum() fixes no order)
+        num = num + em[..., m, None] * near[..., m, :]
+        den = den + em[..., m]
+    scores = num / den.unsqueeze(-1)
+    return (scores, lowest_argmax(scores).to(torch.int32) if labels else None, idx.to(torch.int32) if neighbours else None,
+            val if neighbours else None)

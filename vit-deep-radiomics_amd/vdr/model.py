@@ -254,6 +254,32 @@ class Propagation:
 
 
 @dataclass
+class VolumePropagation:
+    """Result of VitDescriptorModel.propagate_volume for the Z slices of a volume on a gh x gw grid.  scores [Z, gh, gw, C]
+    fp32: every patch's soft class scores (slice `index`: what was given, a hard map as one-hot; a propagated slice: rows that
+    sum to 1 up to rounding); labels [Z, gh, gw] int64: the class of the largest score, the lowest on a tie.  A slice the sweep
+    did not visit (below `index` with direction="up", above it with "down") has scores 0 and labels -1.  grid = (gh, gw);
+    stride and patch place a grid index in the image."""
+    scores: torch.Tensor
+    labels: torch.Tensor
+    grid: "tuple[int, int]"
+    radius: int
+    index: int
+    stride: int
+    patch: int
+
+    def upsample_guided(self, x: torch.Tensor, box=None, **kwargs) -> torch.Tensor:
+        """The labels at pixel resolution, [Z, h, w] int64 over `box` (None: the whole image): the soft scores through
+        vdr.upsample.guided with the slices x [Z, 3, H, W] themselves as the guide (fp32 out; kwargs: its radius and sigmas),
+        then the lowest arg-max.  An unvisited slice comes out as class 0."""
+        from . import knn, upsample
+        guide = x if x.dtype in (torch.float32, torch.bfloat16) else x.float()
+        up = upsample.guided(self.scores, guide.to(self.scores.device), self.patch, self.stride, box=box, out_dtype=torch.float32,
+                             **kwargs)
+        return knn.lowest_argmax(up)
+
+
+@dataclass
 class Cosegmentation:
     """Result of VitDescriptorModel.cosegment for B images on a gh x gw grid.  labels [B, gh, gw] int32: every patch's cluster
     of the one joint k-means over all B maps; salient [k] bool: the clusters voted salient; masks [B, gh, gw] bool: the
@@ -605,7 +631,7 @@ class VitDescriptorModel:
         candidates writes the [B, t, (2 radius + 1)^2] cost volume -- never a t x t matrix --; vdr.local.topk and
         vdr.knn.vote(weights="softmax") do the rest.  A volume is swept by looping over this, the result's labels becoming
         the next call's labels_src.  No saliency is involved, so the model needs no CLS token.  Several source slices per
-        target and soft (probability) labels are not supported.  The input size, patch stride and dynamic_size in force
+        target and soft (probability) labels are propagate_volume's.  The input size, patch stride and dynamic_size in force
         apply.  Refusals (ValueError, before any device work): extract_descriptors' own, shapes of x_src / x_dst / labels_src
         that do not agree with each other or with the grid in force, a radius outside 1..8, k above vdr.local.max_k(grid,
         radius), labels outside 0..n_classes-1, a temperature that is not positive."""
@@ -620,13 +646,7 @@ class VitDescriptorModel:
             raise ValueError(f"propagate_labels: n_classes must be positive, got {n_classes}")
         if not float(temperature) > 0:
             raise ValueError(f"propagate_labels: temperature must be positive, got {temperature}")
-        B, (gh, gw) = x_src.shape[0], self.engine.grid
-        if getattr(self, "dynamic_size", False):  # (the grid the forward will adopt, without adopting it here)
-            p, s = int(self.cfg.patch), int(self.engine.patch_stride)
-            gh, gw = (int(x_src.shape[-2]) - p) // s + 1, (int(x_src.shape[-1]) - p) // s + 1
-        elif tuple(x_src.shape[-2:]) != tuple(self.engine.input_size):
-            raise ValueError(f"propagate_labels: the images are {tuple(x_src.shape[-2:])}, the input size in force "
-                             f"{tuple(self.engine.input_size)}")
+        B, (gh, gw) = x_src.shape[0], self._grid_of("propagate_labels", x_src)
         if not isinstance(labels_src, torch.Tensor) or labels_src.dtype.is_floating_point or labels_src.dtype == torch.bool or \
                 tuple(labels_src.shape) != (B, gh, gw):
             raise ValueError(f"propagate_labels: labels_src must be an integer tensor of shape {(B, gh, gw)} (the grid in force), got "
@@ -643,6 +663,107 @@ class VitDescriptorModel:
                           temperature=float(temperature))
         return Propagation(scores.reshape(B, gh, gw, int(n_classes)), knn.lowest_argmax(scores).reshape(B, gh, gw), idx, val,
                            (int(gh), int(gw)), radius)
+
+    def _grid_of(self, what: str, x) -> "tuple[int, int]":
+        """The grid the forward of the [B, 3, H, W] batch x will run on, without adopting anything: the grid in force, or with
+        dynamic_size the one of x's size; another size is refused (ValueError)."""
+        if getattr(self, "dynamic_size", False):
+            p, s = int(self.cfg.patch), int(self.engine.patch_stride)
+            return (int(x.shape[-2]) - p) // s + 1, (int(x.shape[-1]) - p) // s + 1
+        if tuple(x.shape[-2:]) != tuple(self.engine.input_size):
+            raise ValueError(f"{what}: the images are {tuple(x.shape[-2:])}, the input size in force {tuple(self.engine.input_size)}")
+        gh, gw = self.engine.grid
+        return int(gh), int(gw)
+
+    def propagate_volume(self, x: torch.Tensor, labels: torch.Tensor, n_classes: int, index: int = 0, radius: int = 4, k: int = 5,
+                         temperature: float = 0.1, n_context: int = 7, direction: str = "both", layer=None, facet: str = "key",
+                         bin: bool = False, hierarchy: int = 2, max_batch: int = 16) -> VolumePropagation:
+        """DINO's label propagation through a volume: x [Z, 3, H, W] holds the slices in order, `labels` annotates slice
+        `index` -- [gh, gw] integer classes in 0..n_classes-1, or [gh, gw, n_classes] float soft scores (finite,
+        non-negative) -- and every other slice gets soft scores from the multi-source window vote (vdr.ops.window_vote):
+        each patch takes the k most similar source patches at most `radius` grid steps from its own position, over ALL its
+        source slices at once, and averages their soft scores with weights exp((sim - best sim) / temperature).
+        The sweep runs upwards from index + 1, then downwards from index - 1 with a fresh context (direction: "up" | "down" |
+        "both").  The sources of a slice are, IN THIS SLOT ORDER, the annotated slice (slot 0, kept for the whole sweep), then
+        the min(n_context, steps so far) most recently propagated slices, nearest first, with the soft scores they received;
+        n_context = 0 propagates from the annotated slice alone.  The slot order is part of the result: of two candidates
+        with the same similarity the one in the lower slot is taken first.  Slice `index` returns what it was given (hard
+        labels as one-hot); a slice the chosen direction does not reach keeps scores 0 and labels -1.
+        Device work per slice: one vdr.ops.local_correlation call (pairs = sources, the target expand()ed) and one
+        window_vote; no host synchronisation inside the sweep.  The descriptors (extract_descriptors' arguments) come from
+        forward_descriptors in chunks of max_batch slices; resident at any time are the annotated slice's map, n_context
+        context maps and one chunk, never the volume's.  The input size, patch stride and dynamic_size in force apply.
+        Deviations from DINO's eval_video_segmentation: exactly k neighbours (upstream keeps everything tied with the
+        k-th), a square window of radius <= 8 patches (upstream: a 12-patch disc), no per-class min-max normalisation of
+        the result.  Refusals (ValueError, before any device work): propagate_labels' own, an index outside 0..Z-1,
+        n_context outside 0..7, an unknown direction, max_batch < 1, labels whose shape or values do not fit the grid and
+        n_classes (1..64), k above 16 or above vdr.local.max_k(grid, radius) -- the candidates of a corner patch in the
+        first step, which has one source."""
+        from . import knn, local, ops
+        what = "propagate_volume"
+        h = self._descriptor_args(layer, facet, bin, False, hierarchy)
+        check_batch(what, x)
+        radius = ops.check_local_radius(what, radius)
+        C = int(n_classes)
+        if not 1 <= C <= ops.WINDOW_VOTE_MAX_CLASSES:
+            raise ValueError(f"{what}: n_classes must be 1..{ops.WINDOW_VOTE_MAX_CLASSES}, got {n_classes}")
+        if not float(temperature) > 0 or float(temperature) == float("inf"):
+            raise ValueError(f"{what}: temperature must be positive and finite, got {temperature}")
+        Z, (gh, gw) = int(x.shape[0]), self._grid_of(what, x)
+        if isinstance(index, bool) or int(index) != index or not 0 <= int(index) < Z:
+            raise ValueError(f"{what}: index must be an integer in 0..{Z - 1} (the slices of x), got {index!r}")
+        if isinstance(n_context, bool) or int(n_context) != n_context or not 0 <= int(n_context) < ops.WINDOW_VOTE_MAX_SOURCES:
+            raise ValueError(f"{what}: n_context must be an integer in 0..{ops.WINDOW_VOTE_MAX_SOURCES - 1}, got {n_context!r}")
+        if direction not in ("up", "down", "both"):
+            raise ValueError(f"{what}: direction must be 'up', 'down' or 'both', got {direction!r}")
+        if isinstance(max_batch, bool) or int(max_batch) != max_batch or int(max_batch) < 1:
+            raise ValueError(f"{what}: max_batch must be a positive integer, got {max_batch!r}")
+        hard = isinstance(labels, torch.Tensor) and not labels.dtype.is_floating_point and labels.dtype != torch.bool
+        if not isinstance(labels, torch.Tensor) or labels.dtype == torch.bool or \
+                tuple(labels.shape) != ((gh, gw) if hard else (gh, gw, C)):
+            raise ValueError(f"{what}: labels must be an integer tensor of shape {(gh, gw)} or a float tensor of shape {(gh, gw, C)} "
+                             f"(the grid in force and n_classes), got {getattr(labels, 'dtype', type(labels).__name__)} "
+                             f"{tuple(getattr(labels, 'shape', ()))}")
+        k_max = min(local.max_k((gh, gw), radius), ops.WINDOW_VOTE_MAX_K)
+        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= k_max:
+            raise ValueError(f"{what}: k must be 1..{k_max} (at most {ops.WINDOW_VOTE_MAX_K}, and the in-grid candidates of a corner "
+                             f"patch of a {gh} x {gw} grid at radius {radius} in the first step), got {k!r}")
+        if hard and labels.numel() and (int(labels.min()) < 0 or int(labels.max()) >= C):
+            raise ValueError(f"{what}: labels must lie in 0..{C - 1}")
+        if not hard and not bool((torch.isfinite(labels) & (labels >= 0)).all()):
+            raise ValueError(f"{what}: soft labels must be finite and non-negative")
+        index, n_context, k, step = int(index), int(n_context), int(k), int(max_batch)
+
+        dev, t = self.device, gh * gw
+        given = torch.nn.functional.one_hot(labels.long(), C) if hard else labels
+        given = given.to(device=dev, dtype=torch.float32).reshape(t, C)
+        scores = torch.zeros((Z, t, C), dtype=torch.float32, device=dev)
+        visited = torch.zeros(Z, dtype=torch.bool)
+        scores[index], visited[index] = given, True
+        anchor = self._descriptors(x[index:index + 1].to(dev), layer, facet, h)[0]
+        # the sources in slot order: [0] the annotated slice, [1 ..] the context, nearest first
+        bank = torch.empty((1 + n_context,) + tuple(anchor.shape), dtype=anchor.dtype, device=dev)
+        soft = torch.empty((1 + n_context, t, C), dtype=torch.float32, device=dev)
+        bank[0], soft[0] = anchor, given
+        sweeps = ([range(index + 1, Z)] if direction != "down" else []) + ([range(index - 1, -1, -1)] if direction != "up" else [])
+        for order in sweeps:
+            for c0 in range(0, len(order), step):
+                zs = list(order[c0:c0 + step])
+                desc = self._descriptors(x[min(zs):max(zs) + 1].to(dev), layer, facet, h)
+                for n, z in enumerate(zs, start=c0):  # n: the steps so far in this direction
+                    d = desc[z - min(zs)]
+                    S = 1 + min(n, n_context)
+                    cost, _, _ = ops.local_correlation(d.unsqueeze(0).expand(S, -1, -1), bank[:S], (gh, gw), radius, best=False)
+                    got = ops.window_vote(cost.unsqueeze(0), soft[:S].unsqueeze(0), (gh, gw), k, "softmax", float(temperature),
+                                          labels=False, neighbours=False)[0][0]
+                    scores[z], visited[z] = got, True
+                    if n_context:  # the new slice becomes slot 1; the others move up by one and the oldest drops out
+                        keep = min(n, n_context - 1)
+                        bank[2:2 + keep], soft[2:2 + keep] = bank[1:1 + keep].clone(), soft[1:1 + keep].clone()
+                        bank[1], soft[1] = d, got
+        lab = torch.where(visited.to(dev).unsqueeze(1), knn.lowest_argmax(scores), -1)
+        return VolumePropagation(scores.reshape(Z, gh, gw, C), lab.reshape(Z, gh, gw), (gh, gw), radius, index,
+                                 int(self.engine.patch_stride), int(self.cfg.patch))
 
     def cosegment(self, x: torch.Tensor, k=None, layer=None, facet: str = "key", bin: bool = False, hierarchy: int = 2,
                   thresh: float = 0.065, votes_percentage: float = 75, elbow: float = 0.975, **fit_kwargs) -> Cosegmentation:

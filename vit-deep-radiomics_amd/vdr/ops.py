@@ -431,6 +431,80 @@ def local_correlation(x: torch.Tensor, y: torch.Tensor, grid, radius: int, cost:
     return c, best_sim, best_idx
 
 
+WINDOW_VOTE_MAX_SOURCES, WINDOW_VOTE_MAX_K, WINDOW_VOTE_MAX_CLASSES = 8, 16, 64  # VDR_WINDOW_VOTE_MAX_* (include/vdr.h)
+VOTE_WEIGHTS = ("softmax", "uniform")  # VDR_VOTE_SOFTMAX, VDR_VOTE_UNIFORM
+
+
+def check_window_vote(op: str, cost, src, grid, k, weights, temperature):
+    """The refusals of the window vote (ValueError), shared by vdr.ops.window_vote and its torch statement
+    vdr.local.vote_window -- vdr_op_window_vote's, in its order.  Returns (P, S, gh, gw, radius, k, C)."""
+    if not isinstance(cost, torch.Tensor) or cost.dim() != 4 or cost.dtype != torch.float32:
+        raise ValueError(f"{op}: cost must be a [P, S, t, W * W] float32 tensor")
+    if not isinstance(src, torch.Tensor) or src.dim() != 4 or src.dtype != torch.float32:
+        raise ValueError(f"{op}: src must be a [P, S, t, C] float32 tensor")
+    if cost.device != src.device:
+        raise ValueError(f"{op}: cost and src must be on the same device")
+    if tuple(cost.shape[:3]) != tuple(src.shape[:3]):
+        raise ValueError(f"{op}: cost {tuple(cost.shape)} and src {tuple(src.shape)} must agree in P, S and t")
+    P, S, t, WW = (int(v) for v in cost.shape)
+    C = int(src.shape[3])
+    gh, gw = (int(v) for v in grid)
+    if min(P, S, gh, gw, C) <= 0:
+        raise ValueError(f"{op}: problems, sources, gh, gw and n_classes must be positive")
+    if gh * gw != t:
+        raise ValueError(f"{op}: cost has {t} rows, the grid {gh} x {gw}")
+    if P * S * t > 2 ** 31 - 1:
+        raise ValueError(f"{op}: problems * sources * gh * gw exceeds 2^31 - 1")
+    if S > WINDOW_VOTE_MAX_SOURCES:
+        raise ValueError(f"{op}: sources must be 1 .. {WINDOW_VOTE_MAX_SOURCES}, got {S}")
+    r = next((r for r in range(1, LOCAL_CORR_MAX_RADIUS + 1) if (2 * r + 1) ** 2 == WW), None)
+    if r is None:
+        raise ValueError(f"{op}: cost has {WW} slots, which is (2 r + 1)^2 for no radius in 1..{LOCAL_CORR_MAX_RADIUS}")
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= WINDOW_VOTE_MAX_K:
+        raise ValueError(f"{op}: k must be an integer in 1 .. {WINDOW_VOTE_MAX_K}, got {k!r}")
+    if C > WINDOW_VOTE_MAX_CLASSES:
+        raise ValueError(f"{op}: n_classes must be 1 .. {WINDOW_VOTE_MAX_CLASSES}, got {C}")
+    corner = S * min(gh, r + 1) * min(gw, r + 1)
+    if int(k) > corner:
+        raise ValueError(f"{op}: k exceeds the {corner} in-grid candidates of a corner patch, sources * min(gh, radius + 1) * "
+                         f"min(gw, radius + 1), got {k}")
+    if weights not in VOTE_WEIGHTS:
+        raise ValueError(f"{op}: weights must be one of {VOTE_WEIGHTS}, got {weights!r}")
+    T = torch.tensor(float(temperature), dtype=torch.float32)  # (what the op sees: the fp32 value)
+    if not float(T) > 0 or not bool(torch.isfinite(T)):
+        raise ValueError(f"{op}: temperature must be positive and finite, got {temperature!r}")
+    if P * S * t * max(WW, C) > 2 ** 31 - 1:
+        raise ValueError(f"{op}: an element count (cost or src) exceeds 2^31 - 1")
+    return P, S, gh, gw, r, int(k), C
+
+
+def window_vote(cost: torch.Tensor, src: torch.Tensor, grid, k: int, weights: str = "softmax", temperature: float = 0.1,
+                labels: bool = True, neighbours: bool = True):
+    """The multi-source soft window vote (vdr_op_window_vote): cost [P, S, t, W * W] fp32 -- per problem the S cost volumes of
+    one target map against S source maps on grid = (gh, gw), as local_correlation writes them (one call with the target
+    expand()ed over the S sources gives a problem's block) --, src [P, S, t, C] fp32 the sources' class scores (finite,
+    non-negative; one-hot rows are hard labels).  Every patch takes the k best candidates inside the grid over all S windows
+    -- greater value first, then lower source, then lower slot -- and votes their src rows with weights
+    exp((v_m - v_0) / temperature) ("softmax") or 1 ("uniform"), normalised.  Returns (scores [P, t, C] fp32, labels [P, t]
+    int32: the lowest class of the largest score, idx [P, t, k] int32: s * t + j of the neighbours, best first, val [P, t, k]
+    fp32: their values); labels=False / neighbours=False skip those outputs (None in their place).  The radius is the one
+    whose (2 r + 1)^2 is cost's last dimension.  S <= 8, k <= 16 and at most the in-grid candidates of a corner patch, C <= 64.
+    vdr.local.vote_window is the same in plain torch; the exact arithmetic is stated in include/vdr.h."""
+    P, S, gh, gw, r, k, C = check_window_vote("window_vote", cost, src, grid, k, weights, temperature)
+    if cost.device.type != "cuda":
+        raise ValueError("window_vote: cost and src must be on the device (vdr.local.vote_window runs on any)")
+    cost, src = cost.contiguous(), src.contiguous()
+    lib = L.load()
+    dev, t = cost.device, gh * gw
+    scores = torch.empty((P, t, C), dtype=torch.float32, device=dev)
+    lab = torch.empty((P, t), dtype=torch.int32, device=dev) if labels else None
+    idx = torch.empty((P, t, k), dtype=torch.int32, device=dev) if neighbours else None
+    val = torch.empty((P, t, k), dtype=torch.float32, device=dev) if neighbours else None
+    L.check(lib.vdr_op_window_vote(cost.data_ptr(), src.data_ptr(), P, S, gh, gw, r, k, C, VOTE_WEIGHTS.index(weights),
+                                   float(temperature), scores.data_ptr(), _p(lab), _p(idx), _p(val), _s(cost)))
+    return scores, lab, idx, val
+
+
 def bits_pitch(t: int) -> int:
     """int32 words per row of a bit-packed [t, t] graph: ceil(t / 32) rounded up to a multiple of 4 (16-byte rows)"""
     return (int(t) + 127) // 128 * 4
