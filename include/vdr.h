@@ -774,6 +774,39 @@ int vdr_op_nn_cosine(const void* x, int64_t ldx, int64_t x_stride, int tx,
                      int pairs, int d, void* work,
                      float* row_sim, int32_t* row_idx, float* col_sim, int32_t* col_idx, void* stream);
 
+/* k nearest neighbours between two descriptor maps (csrc/knn.hip): for each of `pairs` problems, the k best candidates of
+ * every query over ALL candidates, without the tq x tc score matrix ever being written.
+ *   X_p = [tq, d] bf16 (the queries), rows ldx elements apart, starting at x + p * x_stride; Y_p = [tc, d] bf16 (the
+ *   candidates) with ldy and y_stride likewise.  A stride of 0 is allowed (many query sets against one bank).  The operand
+ *   rules are vdr_op_nn_cosine's.
+ * Definition, one fp32 rounding per step, in this order:
+ *   ss(v), rn(v), dot = vdr_op_nn_cosine's: ss(v) = sum_c v_c^2 in fp32 in its fixed order, rn(v) = 1.0f / fmaxf(sqrtf(ss(v)),
+ *               1e-8f) with correctly rounded sqrtf and division, dot accumulated in fp32 by bf16 MFMAs in ascending k;
+ *   metric VDR_KNN_COSINE: s(i, j) = (dot(x_i, y_j) * rn(x_i)) * rn(y_j): two multiplications, in this association -- the bits
+ *               of vdr_op_nn_cosine's sim(i, j).  Better means greater s, then lower j;
+ *   metric VDR_KNN_L2:     s(i, j) = fmaxf(fmaf(-2.0f, dot(x_i, y_j), ss(x_i) + ss(y_j)), 0.0f): one addition, one fused
+ *               multiply-add, the clamp -- the SQUARED distance; the square root is the caller's.  Better means smaller s, then
+ *               lower j.  The value returned is s itself, never -0;
+ *   exclude_diag != 0: candidate j == i is not eligible for query i (the k-NN graph of one map against itself);
+ *   val[p, i, m], idx[p, i, m] = s and j of the m-th best eligible candidate of query i, m = 0 .. k - 1   ([pairs, tq, k]
+ *               fp32 / int32), best first.
+ * The order is total on pairs with distinct indices, so a problem's bits depend on (tq, tc, d, k, metric, exclude_diag,
+ * inputs) only -- not on `pairs`, on its position in the batch or on how the launch cuts the candidates into runs.  Inputs are
+ * finite by contract.  No atomics; every output element has exactly one writer.  With k = 1 and the cosine metric val / idx
+ * equal vdr_op_nn_cosine's row_sim / row_idx bit for bit.
+ * work: vdr_knn_work_bytes(pairs, tq, tc, k) bytes of device scratch (the row norms and the partial lists), 16-byte aligned;
+ * it is written before it is read.
+ * Refused before the device is touched, in this order: VDR_ERR_INVALID for a null x, y, work, val or idx, non-positive
+ * pairs, tq, tc or d; VDR_ERR_UNSUPPORTED for d % 32 != 0; VDR_ERR_INVALID for ldx < d or ldy < d, negative strides,
+ * pointers or strides that are not 16-byte aligned, pairs * max(tq, tc) above 2^31 - 1; VDR_ERR_UNSUPPORTED for k outside
+ * 1 .. VDR_KNN_MAX_K; VDR_ERR_INVALID for an unknown metric, for tc - (exclude_diag ? 1 : 0) < k (so no padding entry is ever
+ * returned: exactly k neighbours, always), for pairs * tq * k above 2^31 - 1. */
+#define VDR_KNN_MAX_K 16
+enum vdr_knn_metric { VDR_KNN_COSINE = 0, VDR_KNN_L2 = 1 };
+size_t vdr_knn_work_bytes(int pairs, int tq, int tc, int k);
+int vdr_op_knn(const void* x, int64_t ldx, int64_t x_stride, int tq, const void* y, int64_t ldy, int64_t y_stride, int tc,
+               int pairs, int d, int k, int metric, int exclude_diag, void* work, float* val, int32_t* idx, void* stream);
+
 /* Windowed correlation of two descriptor maps that live on ONE gh x gw grid (csrc/local_corr.hip): for each of `pairs`
  * problems, every patch of X_p against the patches of Y_p at most `radius` grid steps away in y and in x -- the search for
  * adjacent slices or a follow-up scan, where a structure moves by a few patches.  t = gh * gw, row i = qy * gw + qx.

@@ -254,8 +254,8 @@ VDR_DEV void raw_fill(RawChunk<BF16>& c, bool ok, const void* x, int64_t off) {
 }
 
 // ---- staging by LDS-DMA: the cosine kernels ---------------------------------------------------------------
-// nn_cosine.hip, affinity.hip and local_corr.hip multiply raw bf16 rows, so their operands go global -> LDS directly.  All
-// three take dma_wait and t128_dma_chunk; local_corr_kernel runs on t128_dma_stage and dma_steps, nn_cosine_kernel and
+// nn_cosine.hip, knn.hip, affinity.hip and local_corr.hip multiply raw bf16 rows, so their operands go global -> LDS directly.
+// All take dma_wait and t128_dma_chunk; local_corr_kernel and knn_kernel run on t128_dma_stage and dma_steps, nn_cosine_kernel and
 // affinity_bits_kernel keep spelled-out copies of those two (1 - 3 % slower through them: DESIGN 4.6t) -- a change to either
 // is a change to all three, and a new kernel starts from the helpers.
 // the staged step has landed, for every wave: the DMAs are opaque to hipcc, so the wait is spelled out

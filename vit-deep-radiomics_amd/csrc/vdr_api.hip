@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/vdr.h"
+#include "knn_map.h"
 #include "local_corr_map.h"
 #include "vdr_kernels.h"
 
@@ -2257,6 +2258,7 @@ static const DescNames PCA_NAMES = {"problems, imgs, t and d", "ld", "image_stri
 static const DescNames GRAM_NAMES = {"problems, t and d", "ld", "image_stride", "problems * t"};
 static const DescNames KMEANS_NAMES = {"problems, imgs, t and d", "ld", "the strides", "problems * R"};
 static const DescNames NN_NAMES = {"pairs, tx, ty and d", "ldx and ldy", "the pair strides", "pairs * max(tx, ty)"};
+static const DescNames KNN_NAMES = {"pairs, tq, tc and d", "ldx and ldy", "the pair strides", "pairs * max(tq, tc)"};
 static const DescNames LOCAL_NAMES = {"pairs, gh, gw and d", "ldx and ldy", "the pair strides", "pairs * gh * gw"};
 static const DescNames WINDOW_VOTE_NAMES = {"problems, sources, gh, gw and n_classes", "n_classes", "the strides",
                                             "problems * sources * gh * gw"};
@@ -2781,6 +2783,24 @@ int vdr_op_nn_cosine(const void* x, int64_t ldx, int64_t x_stride, int tx, const
   RUN_OP(launch_nn_cosine(x, ldx, x_stride, tx, y, ldy, y_stride, ty, pairs, d, work, row_sim, row_idx, col_sim, col_idx,
                           (hipStream_t)stream),
          "nn_cosine");
+}
+
+size_t vdr_knn_work_bytes(int pairs, int tq, int tc, int k) { return knn_work_bytes(pairs, tq, tc, k); }
+
+int vdr_op_knn(const void* x, int64_t ldx, int64_t x_stride, int tq, const void* y, int64_t ldy, int64_t y_stride, int tc, int pairs,
+               int d, int k, int metric, int exclude_diag, void* work, float* val, int32_t* idx, void* stream) {
+  static_assert(VDR_KNN_MAX_K == KNN_MAX_K, "include/vdr.h and knn_map.h");
+  const char* op = "knn";
+  if (int rc = check_desc_operand(op, {x, VDR_BF16, ldx, 0, x_stride, pairs, 1, tq, d}, KNN_NAMES, 0, {work, val, idx})) return rc;
+  if (int rc = check_desc_operand(op, {y, VDR_BF16, ldy, 0, y_stride, pairs, 1, tc, d}, KNN_NAMES, 0, {})) return rc;
+  if (k < 1 || k > VDR_KNN_MAX_K)
+    return refuse(op, VDR_ERR_UNSUPPORTED, "k must be 1 .. " + std::to_string(VDR_KNN_MAX_K) + " (larger lists are out of scope)");
+  if (metric != VDR_KNN_COSINE && metric != VDR_KNN_L2) return refuse(op, VDR_ERR_INVALID, "metric must be VDR_KNN_COSINE or VDR_KNN_L2");
+  if ((int64_t)tc - (exclude_diag ? 1 : 0) < k) return refuse(op, VDR_ERR_INVALID, "fewer than k eligible candidates (tc - exclude_diag < k)");
+  if ((int64_t)pairs * tq > INT32_MAX / k) return refuse(op, VDR_ERR_INVALID, "pairs * tq * k exceeds 2^31 - 1");
+  RUN_OP(launch_knn(x, ldx, x_stride, tq, y, ldy, y_stride, tc, pairs, d, k, metric == VDR_KNN_L2, exclude_diag, work, val, idx,
+                    (hipStream_t)stream),
+         "knn");
 }
 
 size_t vdr_local_correlation_work_bytes(int pairs, int gh, int gw, int radius) {

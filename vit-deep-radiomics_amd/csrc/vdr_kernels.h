@@ -328,6 +328,15 @@ hipError_t launch_nn_cosine(const void* x, int64_t ldx, int64_t x_stride, int tx
                             int ty, int pairs, int d, void* work, float* row_sim, int32_t* row_idx, float* col_sim,
                             int32_t* col_idx, hipStream_t st);
 
+// k nearest neighbours of two descriptor maps (knn.hip; the definition is vdr_op_knn's in include/vdr.h): operands as
+// launch_nn_cosine's, X the queries and Y the candidates; k 1 .. 16, l2 != 0: squared distances instead of cosines;
+// exclude_diag: candidate i is not eligible for query i; tc - exclude_diag >= k.  val / idx [pairs][tq][k], best first; work:
+// knn_work_bytes(pairs, tq, tc, k) bytes.  Three launches (row norms or sums of squares, the fused tile kernel, the merge of
+// the partial lists); every index is knn_map.h's.
+size_t knn_work_bytes(int pairs, int tq, int tc, int k);
+hipError_t launch_knn(const void* x, int64_t ldx, int64_t x_stride, int tq, const void* y, int64_t ldy, int64_t y_stride, int tc,
+                      int pairs, int d, int k, int l2, int exclude_diag, void* work, float* val, int32_t* idx, hipStream_t st);
+
 // Windowed correlation of two descriptor maps on one gh x gw grid (local_corr.hip; the definition is
 // vdr_op_local_correlation's in include/vdr.h): operands as launch_nn_cosine's with tx = ty = gh * gw; radius 1 .. 8.
 // cost [pairs][t][(2r+1)^2] fp32 and / or (best_sim, best_idx) [pairs][t]; work: local_correlation_work_bytes(...) bytes.

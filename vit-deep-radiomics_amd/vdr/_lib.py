@@ -123,6 +123,8 @@ SYMBOLS = {
     "vdr_op_log_bin": (_I, [_P, _I, _L, _L, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "vdr_nn_cosine_work_bytes": (C.c_size_t, [_I, _I, _I]),
     "vdr_op_nn_cosine": (_I, [_P, _L, _L, _I, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "vdr_knn_work_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "vdr_op_knn": (_I, [_P, _L, _L, _I, _P, _L, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vdr_local_correlation_work_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "vdr_op_local_correlation": (_I, [_P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vdr_op_window_vote": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),

@@ -139,18 +139,34 @@ def fit_gaussian(x: torch.Tensor, per_position: bool = False, shrinkage: float =
 
 class MemoryBank:
     """A bank of m normal descriptors [m, d] (kept in bf16); score(x [B, t, d]) -> [B, t] fp32 = 1 - the cosine to the
-    nearest bank row, by vdr.ops.nn_cosine with the bank under every map at stride 0 (no new kernel)."""
+    nearest bank row, by vdr.ops.nn_cosine with the bank under every map at stride 0.  score(x, k) with k > 1: the mean of the
+    k smallest distances 1 - cos (vdr.ops.knn), added nearest first and divided once.  reweight=True is PatchCore's
+    re-weighting of the nearest distance d_1 by the neighbourhood: (1 - softmax(d)[0]) * d_1 over the k distances d (k >= 2),
+    which lowers the score of a patch whose nearest bank rows are all about equally far."""
 
     def __init__(self, bank: torch.Tensor):
         if not isinstance(bank, torch.Tensor) or bank.dim() != 2 or bank.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError("MemoryBank: bank must be a [m, d] float32 or bfloat16 tensor")
         self.bank = bank.to(torch.bfloat16).contiguous()
 
-    def score(self, x: torch.Tensor) -> torch.Tensor:
+    def score(self, x: torch.Tensor, k: int = 1, reweight: bool = False) -> torch.Tensor:
         if not isinstance(x, torch.Tensor) or x.dim() != 3:
             raise TypeError("MemoryBank.score: x must be a [B, t, d] float32 or bfloat16 tensor")
         m, d = self.bank.shape
-        return 1.0 - ops.nn_cosine(x, self.bank.unsqueeze(0).expand(x.shape[0], m, d), mutual=False)[0]
+        bank = self.bank.unsqueeze(0).expand(x.shape[0], m, d)
+        if isinstance(k, bool) or int(k) != k or int(k) < 1:
+            raise ValueError(f"MemoryBank.score: k must be a positive integer, got {k!r}")
+        if reweight and int(k) < 2:
+            raise ValueError("MemoryBank.score: reweight=True needs k >= 2")
+        if int(k) == 1:
+            return 1.0 - ops.nn_cosine(x, bank, mutual=False)[0]
+        dist = 1.0 - ops.knn(x, bank, int(k))[0]  # [B, t, k], nearest first
+        if reweight:
+            return (1.0 - torch.softmax(dist, dim=-1)[..., 0]) * dist[..., 0]
+        total = dist[..., 0]
+        for j in range(1, int(k)):
+            total = total + dist[..., j]
+        return total / float(int(k))
 
     @classmethod
     def coreset(cls, x: torch.Tensor, m: int) -> "MemoryBank":

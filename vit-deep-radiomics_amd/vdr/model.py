@@ -244,7 +244,8 @@ class Propagation:
     """Result of VitDescriptorModel.propagate_labels for B (source, target) slice pairs on a gh x gw grid.  scores
     [B, gh, gw, n_classes] fp32: every target patch's class scores, the softmax-weighted vote of its k best source patches
     inside the window (they sum to 1); labels [B, gh, gw] int64: the class of the largest score, the lowest on a tie;
-    idx [B, t, k] int32 / val [B, t, k] fp32: those source patches and their similarities, best first."""
+    idx [B, t, k] int32 / val [B, t, k] fp32: those source patches and their similarities, best first.  radius is None when
+    the search was global (transfer_labels)."""
     scores: torch.Tensor
     labels: torch.Tensor
     idx: torch.Tensor
@@ -663,6 +664,61 @@ class VitDescriptorModel:
                           temperature=float(temperature))
         return Propagation(scores.reshape(B, gh, gw, int(n_classes)), knn.lowest_argmax(scores).reshape(B, gh, gw), idx, val,
                            (int(gh), int(gw)), radius)
+
+    def transfer_labels(self, x_src: torch.Tensor, labels_src: torch.Tensor, x_dst: torch.Tensor, n_classes: int, k: int = 5,
+                        temperature: float = 0.1, layer=None, facet: str = "key", bin: bool = False,
+                        hierarchy: int = 2) -> Propagation:
+        """propagate_labels with the GLOBAL search in place of the window: every patch of x_dst[b] takes the softmax-weighted
+        vote of its k most similar patches of x_src[b] wherever they lie -- for slices that are not registered to each
+        other (another patient, another orientation), where a window around the own position means nothing.  One forward
+        over cat([x_dst, x_src]) writes the bf16 `facet` descriptors; one vdr.ops.knn call with the target patches as queries
+        and the source patches as candidates returns the (val, idx) lists -- the t x t similarity matrix is never written --
+        and vdr.knn.vote(weights="softmax") votes.  The result is a Propagation with radius None.  Refusals (ValueError,
+        before any device work): propagate_labels' own, with k in 1..min(16, t) instead of the window's bound."""
+        from . import knn, ops
+        h = self._descriptor_args(layer, facet, bin, False, hierarchy)
+        check_batch("transfer_labels", x_src)
+        if not isinstance(x_dst, torch.Tensor) or tuple(x_src.shape) != tuple(x_dst.shape):
+            raise ValueError(f"transfer_labels: x_src and x_dst must be [B, 3, H, W] of the same shape, got {tuple(x_src.shape)} "
+                             f"and {tuple(getattr(x_dst, 'shape', ()))}")
+        if int(n_classes) < 1:
+            raise ValueError(f"transfer_labels: n_classes must be positive, got {n_classes}")
+        if not float(temperature) > 0:
+            raise ValueError(f"transfer_labels: temperature must be positive, got {temperature}")
+        B, (gh, gw) = x_src.shape[0], self._grid_of("transfer_labels", x_src)
+        if not isinstance(labels_src, torch.Tensor) or labels_src.dtype.is_floating_point or labels_src.dtype == torch.bool or \
+                tuple(labels_src.shape) != (B, gh, gw):
+            raise ValueError(f"transfer_labels: labels_src must be an integer tensor of shape {(B, gh, gw)} (the grid in force), got "
+                             f"{getattr(labels_src, 'dtype', type(labels_src).__name__)} {tuple(getattr(labels_src, 'shape', ()))}")
+        k = ops.check_knn("transfer_labels", k, "cosine", gh * gw, False)
+        if labels_src.numel() and (int(labels_src.min()) < 0 or int(labels_src.max()) >= int(n_classes)):
+            raise ValueError(f"transfer_labels: labels_src must lie in 0..{int(n_classes) - 1}")
+        desc = self._descriptors(torch.cat([x_dst.to(self.device), x_src.to(self.device)]), layer, facet, h)
+        val, idx = ops.knn(desc[:B], desc[B:], k)
+        scores = knn.vote(idx, val, labels_src.to(self.device).reshape(B, gh * gw), int(n_classes), weights="softmax",
+                          temperature=float(temperature))
+        return Propagation(scores.reshape(B, gh, gw, int(n_classes)), knn.lowest_argmax(scores).reshape(B, gh, gw), idx, val,
+                           (int(gh), int(gw)), None)
+
+    def fit_knn(self, batches, labels: torch.Tensor, n_classes: int, n_last_blocks: int = 1, avgpool: bool = False, **classifier_kw):
+        """The k-NN classifier of this model's frozen features: the bank is linear_probe_features(batch, n_last_blocks, avgpool)
+        of every batch of `batches` (an iterable of [B, 3, H, W] tensors, or one such tensor), row after row; labels [N] integer
+        classes of those rows.  classifier_kw goes to vdr.knn.KnnClassifier (k, weights, temperature, metric, bank_chunk).
+        DINO's evaluation is the defaults: the normalised CLS token of the last block, cosine, softmax votes at T = 0.07."""
+        from . import knn
+        if isinstance(batches, torch.Tensor):
+            batches = [batches]
+        feats = [self.linear_probe_features(b.to(self.device), n_last_blocks, avgpool) for b in batches]
+        if not feats:
+            raise ValueError("fit_knn: no batch was given")
+        clf = knn.KnnClassifier(torch.cat(feats), labels, n_classes, **classifier_kw)
+        clf.n_last_blocks, clf.avgpool = int(n_last_blocks), bool(avgpool)
+        return clf
+
+    def knn_predict(self, x: torch.Tensor, clf):
+        """(scores [B, n_classes] fp32, labels [B] int64) of the images x [B, 3, H, W] under a classifier of fit_knn: the same
+        features, clf.predict."""
+        return clf.predict(self.linear_probe_features(x.to(self.device), clf.n_last_blocks, clf.avgpool))
 
     def _grid_of(self, what: str, x) -> "tuple[int, int]":
         """The grid the forward of the [B, 3, H, W] batch x will run on, without adopting anything: the grid in force, or with

@@ -382,6 +382,52 @@ def nn_cosine(x: torch.Tensor, y: torch.Tensor, mutual: bool = True):
     return row_sim, row_idx, col_sim, col_idx
 
 
+KNN_MAX_K = 16  # VDR_KNN_MAX_K (include/vdr.h)
+KNN_METRICS = ("cosine", "l2")  # VDR_KNN_COSINE, VDR_KNN_L2
+
+
+def check_knn(op: str, k, metric: str, tc: int, exclude_diag: bool) -> int:
+    """The one wording of "no such neighbour list" (ValueError); returns k as an int."""
+    if metric not in KNN_METRICS:
+        raise ValueError(f"{op}: metric must be one of {KNN_METRICS}, got {metric!r}")
+    if isinstance(k, bool) or int(k) != k or int(k) < 1:
+        raise ValueError(f"{op}: k must be a positive integer, got {k!r}")
+    if int(k) > KNN_MAX_K:
+        raise ValueError(f"{op}: k must be at most {KNN_MAX_K}, got {k} (longer lists, such as DINO's 20 / 200, are out of scope)")
+    if tc - int(bool(exclude_diag)) < int(k):
+        raise ValueError(f"{op}: {tc} candidates{' without the own row' if exclude_diag else ''} are fewer than k = {k}")
+    return int(k)
+
+
+def knn(x: torch.Tensor, y: torch.Tensor, k: int, metric: str = "cosine", exclude_diag: bool = False):
+    """The k nearest candidates of every query over ALL candidates (vdr_op_knn): x [P, tq, d] the queries, y [P, tc, d] the
+    candidates; operands as nn_cosine takes them (bf16 read in place through views with contiguous channels, a batch stride
+    of 0 from expand() -- many query sets against one bank --, fp32 rounded once to bf16; d a multiple of 32).  Returns
+    (val [P, tq, k] fp32, idx [P, tq, k] int32), best first: metric="cosine" the cosine similarity with nn_cosine's bits,
+    greater is better; metric="l2" the SQUARED distance, smaller is better; equal values in ascending index order.
+    exclude_diag=True: candidate i is not eligible for query i (the k-NN graph of a map against itself).  k is 1..16 and at
+    most the number of eligible candidates, so exactly k real neighbours come back.  The [tq, tc] score matrix is never
+    materialised.  The exact arithmetic is stated in include/vdr.h."""
+    ox = desc_operand(x, "knn", "x", refuse_strided_channels=True)
+    oy = desc_operand(y, "knn", "y", refuse_strided_channels=True)
+    if ox.x.device != oy.x.device:
+        raise ValueError("knn: x and y must be on the same device")
+    if ox.problems != oy.problems or ox.d != oy.d:
+        raise ValueError(f"knn: x {tuple(x.shape)} and y {tuple(y.shape)} must agree in P and d")
+    P, tq, tc, d = ox.problems, ox.t, oy.t, ox.d
+    k = check_knn("knn", k, metric, tc, exclude_diag)
+    if P * tq * k > 2 ** 31 - 1:
+        raise ValueError("knn: P * tq * k exceeds 2^31 - 1")
+    lib = L.load()
+    dev = ox.x.device
+    work = torch.empty((lib.vdr_knn_work_bytes(P, tq, tc, k),), dtype=torch.uint8, device=dev)
+    val = torch.empty((P, tq, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((P, tq, k), dtype=torch.int32, device=dev)
+    L.check(lib.vdr_op_knn(ox.x.data_ptr(), ox.ld, ox.stride, tq, oy.x.data_ptr(), oy.ld, oy.stride, tc, P, d, k,
+                           KNN_METRICS.index(metric), int(bool(exclude_diag)), work.data_ptr(), val.data_ptr(), idx.data_ptr(), _s(ox.x)))
+    return val, idx
+
+
 LOCAL_CORR_MAX_RADIUS = 8  # VDR_LOCAL_CORR_MAX_RADIUS (include/vdr.h)
 
 
