@@ -106,10 +106,20 @@ typedef struct {
                       /*    0's row statistics)                                               */
   float ln_eps;       /* 1e-6 timm/DINOv2/SAM, 1e-5 torch default (models_archs.py:136)       */
   int32_t micro_batch;/* images per internal pass (0 = library default: the whole batch, split   */
-                      /* evenly over `streams`); results do not depend on it                    */
-  int32_t streams;    /* internal HIP streams the micro-batches are spread over (0/1 = the caller's   */
-                      /* stream only); >1 lets kernels of independent micro-batches overlap, e.g. one */
-                      /* GEMM's store-bound epilogue under another's MFMA main loop                   */
+                      /* evenly over `streams`; with streams == 0 too, the default split below); */
+                      /* results do not depend on it                                             */
+  int32_t streams;    /* internal HIP streams the micro-batches are spread over; >1 lets kernels of   */
+                      /* independent micro-batches overlap, e.g. one part's launch gaps and small     */
+                      /* kernels under the other's GEMMs.  1 = the caller's stream only.  0 with an   */
+                      /* explicit micro_batch: the same.  0 with micro_batch == 0 = the default split,*/
+                      /* decided per call from the batch: the whole batch on the caller's stream, or, */
+                      /* where it costs the 8-phase qkv / fc1 GEMMs no extra round of tiles and the   */
+                      /* whole batch's last rounds leave 3/4 of a round of the chip idle, two unequal */
+                      /* parts on two internal streams (ViT-B/16 at batch 256: 146 + 110; 384 stays   */
+                      /* whole; vdr_batch_plan reports it).  Never on a stream that is being */
+                      /* captured (a captured forward stays a linear graph), never for fp8 models or  */
+                      /* SAM encoders.  streams = 1 forces one stream.  Results do not depend on any  */
+                      /* of it: every row is the same bits however the batch is cut                   */
   /* SAM / MedSAM image encoder (segment_anything ImageEncoderViT, tfds_dense_descriptor.py:104,123):   */
   int32_t window;     /* > 0: windowed attention of this side (14) with decomposed relative position   */
                       /* bias in every block; needs has_cls = 0, has_pos = 1, pre_ln = 1               */
@@ -308,6 +318,13 @@ const char* vdr_weight_name(vdr_handle h, int i);
  *     written.
  * tests/test_workspace_contract_gpu.py holds every kind of forward to this between canary guards. */
 int vdr_workspace_bytes(vdr_handle h, int batch, int seq, size_t* out);
+
+/* How a forward of `batch` images (token models: sequences of `seq` tokens) is cut into micro-batches: `parts` passes of
+ * `micro_batch` images, the last one the rest, pass k on internal stream k % streams (streams == 1: the caller's stream).
+ * It is what vdr_config.micro_batch / streams ask for; with both 0 it is the library's default split (vdr_config.streams):
+ * (batch, 1, 1), or two parts on two streams.  On a stream that is being captured the default is always (batch, 1, 1).
+ * vdr_workspace_bytes covers the plan reported here and the captured form. */
+int vdr_batch_plan(vdr_handle h, int batch, int seq, int32_t* micro_batch, int32_t* parts, int32_t* streams);
 
 /* Replaces: model.image_encoder(x) / model.patch_embed(x)
  * (tfds_dense_descriptor.py:123,128) followed by the CLS / patch-token slice

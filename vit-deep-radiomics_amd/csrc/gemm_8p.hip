@@ -47,15 +47,22 @@ hipError_t launch_gemm_8p_act(const G8& g, int epi, bool fold, int grid, int dev
 // (a 2.3-round launch runs 3 rounds long: measured on ViT-g/14's qkv, 594 tiles: 114 us against ring4's 107; a launch of
 // less than one round -- one MedSAM slice, M = 4096: 144 / 192 tiles -- pays the pipeline fill and the four epilogue slots once
 // per 12 K-tiles: qkv 27.1 -> 28.9 us, fc1 31.4 -> 32.4 against the 128-row ring4 tiles)
-bool gemm_8p_shape_ok(int64_t M, int N) {
-  if (M <= 0 || (N & 255)) return false;
+// gemm_8p_rounds: the rounds such a launch runs, 0 where the rule refuses the shape, and (idle) the part of a round its
+// last round leaves the chip empty, 0 .. 0.15 x rounds (the forward's split policy counts both)
+int64_t gemm_8p_rounds(int64_t M, int N, double* idle) {
+  if (idle) *idle = 0.0;
+  if (M <= 0 || (N & 255)) return 0;
   int n_cu = device_cu_count(current_device_index());
   if (n_cu <= 0) n_cu = 256;
   const int64_t tiles = ((M + 255) / 256) * (int64_t)(N / 256), slots = n_cu & ~7;
-  if (tiles < 2 * slots) return false;
+  if (tiles < 2 * slots) return 0;
   const int64_t rounds = (tiles + slots - 1) / slots;
-  return (double)tiles >= 0.85 * (double)(rounds * slots);
+  if ((double)tiles < 0.85 * (double)(rounds * slots)) return 0;
+  if (idle) *idle = (double)(rounds * slots - tiles) / (double)slots;
+  return rounds;
 }
+
+bool gemm_8p_shape_ok(int64_t M, int N) { return gemm_8p_rounds(M, N, nullptr) > 0; }
 
 bool gemm_8p_eligible(const GemmArgs& a, int epi) {
   if (epi != EPI_BIAS && !epi_is_act(epi)) return false;

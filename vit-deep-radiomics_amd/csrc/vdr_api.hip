@@ -196,10 +196,13 @@ struct vdr_model {
   // device copy they were packed from; built by resolve()
   std::map<const void*, DevBuf> w_il;
   std::string err;
-  // internal streams (cfg.streams > 1)
+  // internal streams (cfg.streams > 1, or the default split of batch_plan), created by the first forward that forks
   std::vector<Stream> streams;
   Event ev_fork;
   std::vector<Event> ev_join;
+  // the default split last worked out (default_split: first part of split_first images, 0 = none, for split_batch images
+  // of split_ntok tokens)
+  int split_batch = 0, split_ntok = 0, split_first = 0;
   // fp8_cls_bf16: one side stream (+ fork / join events) per stream a forward can run on, created by vdr_finalize; the CLS
   // rows' bf16 MLP of a block runs there under the MX-fp8 GEMMs of the other rows
   std::vector<Stream> aux;
@@ -498,7 +501,8 @@ int change_geometry(vdr_model* m, int height, int width, int stride) {
   return VDR_OK;
 }
 
-int num_streams(const vdr_model* m) { return m->cfg.streams > 1 ? (m->cfg.streams > 8 ? 8 : m->cfg.streams) : 1; }
+// the internal streams vdr_config.streams asks for (what a forward of a given batch runs on: batch_plan)
+int configured_streams(const vdr_model* m) { return m->cfg.streams > 1 ? (m->cfg.streams > 8 ? 8 : m->cfg.streams) : 1; }
 
 // the pair-interleaved copy of GEMM weight w [N][K] bf16 (whole-line operand loads, gemm_kernels.h), kept in w_il under w
 int interleave(vdr_model* m, const void* w, int N, int K, const char* what_buf, const char* what_launch) {
@@ -597,7 +601,7 @@ int resolve(vdr_model* m) {
     if (c.fp8 && c.fp8_cls_bf16 && c.has_cls) {  // the CLS rows' MLP runs on the bf16 weights
       for (int i = 0; i < c.layers; ++i)
         if ((rc = pack(m->layers[i].w1, N1, D)) || (rc = pack(m->layers[i].w2, D, F))) return rc;
-      while (m->aux.size() < (size_t)num_streams(m)) {
+      while (m->aux.size() < (size_t)configured_streams(m)) {  // (the default split leaves fp8 models alone: default_split)
         Stream st;
         Event ea, eb;
         VDR_TRY(make_stream(st), "hipStreamCreate(CLS side stream)");
@@ -733,34 +737,26 @@ Carve carve(const vdr_model* m, char* base, int mb, int ntok) {
   return w;
 }
 
-int default_micro_batch(const vdr_model* m, int batch) {
-  if (m->cfg.micro_batch > 0) return m->cfg.micro_batch < batch ? m->cfg.micro_batch : batch;
-  const int ns = num_streams(m);
-  return (batch + ns - 1) / ns;
-}
-
-// fork: the internal streams wait for everything already enqueued on the caller's stream
-int fork_streams(vdr_model* m, hipStream_t caller) {
-  const int ns = num_streams(m);
+// fork: the first ns internal streams wait for everything already enqueued on the caller's stream
+int fork_streams(vdr_model* m, hipStream_t caller, int ns) {
   if (ns == 1) return VDR_OK;
-  if (m->streams.empty()) {
-    m->streams.resize(ns);
-    m->ev_join.resize(ns);
-    for (int i = 0; i < ns; ++i) {
-      if (make_stream(m->streams[i]) != hipSuccess) return VDR_ERR_HIP;
-      if (make_event(m->ev_join[i], hipEventDisableTiming) != hipSuccess) return VDR_ERR_HIP;
-    }
-    if (make_event(m->ev_fork, hipEventDisableTiming) != hipSuccess) return VDR_ERR_HIP;
+  while ((int)m->streams.size() < ns) {
+    Stream st;
+    Event ev;
+    if (make_stream(st) != hipSuccess) return VDR_ERR_HIP;
+    if (make_event(ev, hipEventDisableTiming) != hipSuccess) return VDR_ERR_HIP;
+    m->streams.push_back(std::move(st));
+    m->ev_join.push_back(std::move(ev));
   }
+  if (!m->ev_fork && make_event(m->ev_fork, hipEventDisableTiming) != hipSuccess) return VDR_ERR_HIP;
   if (hipEventRecord(m->ev_fork.get(), caller) != hipSuccess) return VDR_ERR_HIP;
   for (int i = 0; i < ns; ++i)
     if (hipStreamWaitEvent(m->streams[i].get(), m->ev_fork.get(), 0) != hipSuccess) return VDR_ERR_HIP;
   return VDR_OK;
 }
 
-// join: the caller's stream waits for every internal stream
-int join_streams(vdr_model* m, hipStream_t caller) {
-  const int ns = num_streams(m);
+// join: the caller's stream waits for the first ns internal streams
+int join_streams(vdr_model* m, hipStream_t caller, int ns) {
   if (ns == 1) return VDR_OK;
   for (int i = 0; i < ns; ++i) {
     if (hipEventRecord(m->ev_join[i].get(), m->streams[i].get()) != hipSuccess) return VDR_ERR_HIP;
@@ -918,6 +914,12 @@ bool use_8p(int cls) {
 // launch itself; ln_stats_in_gemm asks this alone
 bool wants_8p(int cls, int64_t M, int N) { return use_8p(cls) && gemm_8p_shape_ok(M, N); }
 
+// Tile variant 31 (gemm_8p.hip) for the write-once linears of large launches (plain weight layout).  The workspace
+// buffers A points into hold Mp >= M + 256 rows, so a ragged last 256-row tile reads rows that exist; they are never stored.
+bool takes_8p(int cls, const GemmArgs& g, int epi) {
+  return g.lda == g.K && g.a_rows > 0 && wants_8p(cls, g.M, g.N) && gemm_8p_eligible(g, epi);
+}
+
 // Where the (sum, sumsq) partials of the residual stream become (mean, rstd): inside the consuming GEMM when it runs
 // a ring3 variant (22-24; every workgroup finalises its own rows in LDS while its ring fills: no launch), otherwise by
 // ln_finalize_kernel ahead of it.  Same arithmetic either way: results are bitwise equal.  Measured (same box,
@@ -974,9 +976,7 @@ int gemm(vdr_model* m, hipStream_t s, int cls, GemmArgs g, int epi, const LnFold
   const double outw = epi == EPI_SWIGLU ? g.N / 2 : g.N;
   Scope sc(m, s, cls, 2.0 * g.M * g.N * g.K,
            2.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * outw * (g.resid32 ? 5 : g.resid ? 2 : 1)));  // (fp32 in + fp32 out + bf16 out)
-  // Tile variant 31 (gemm_8p.hip) for the write-once linears of large launches (plain weight layout).  The workspace
-  // buffers A points into hold Mp >= M + 256 rows, so a ragged last 256-row tile reads rows that exist; they are never stored.
-  if (g.lda == g.K && g.a_rows > 0 && wants_8p(cls, g.M, g.N) && gemm_8p_eligible(g, epi))
+  if (takes_8p(cls, g, epi))
     VDR_TRY(launch_gemm(g, epi, VARIANT_8P, s), "gemm_8p");
   else
     VDR_TRY(launch_gemm_w(m, g, epi, variant, s), "gemm");
@@ -1623,9 +1623,106 @@ int check_device(vdr_handle h) {
   return VDR_OK;
 }
 
-// The rest of every forward once its arguments are checked: the device, the workspace, then micro-batches of at most
-// default_micro_batch images, micro-batch k on internal stream k % streams (the caller's stream with one) in its own
-// slice of the workspace.  body(s, w, b0, mb) enqueues the micro-batch of images b0 .. b0 + mb - 1.
+// ---- micro-batches ------------------------------------------------------------------------------------------------------
+// The 8-phase rounds of the block loop's qkv / fc1 launch over `images` images; 0 where gemm() gives the launch to another
+// tile variant.  gemm()'s own test (takes_8p) on the launch as BlockSteps::norm_linear describes it: dense operands, the
+// workspace rows readable past the last tile.
+int64_t block_linear_rounds(const vdr_model* m, bool fc1, int images, int ntok, double* idle = nullptr) {
+  const vdr_config& c = m->cfg;
+  if (idle) *idle = 0.0;
+  if (c.fp8) return 0;  // (PATH_MX: gemm_mx)
+  const int epi = fc1 ? fc1_epilogue(c) : EPI_BIAS;
+  const int N = !fc1 ? 3 * c.dim : epi == EPI_SWIGLU ? 2 * c.mlp_hidden : c.mlp_hidden;
+  GemmArgs g = linear(nullptr, nullptr, nullptr, (int64_t)images * ntok, N, c.dim, epi);
+  g.a_rows = (g.M + 255) / 256 * 256 + 256;  // (carve: Mp of a slice that holds at least these images)
+  return takes_8p(fc1 ? VDR_K_GEMM_FC1 : VDR_K_GEMM_QKV, g, epi) ? gemm_8p_rounds(g.M, g.N, idle) : 0;
+}
+
+// The default split (vdr_config.micro_batch == 0 and streams == 0): two parts on two internal streams, so that the idle
+// time between one part's launches -- per-launch intercepts, ln_finalize, the CLS tail: 6-7 % of the ViT-B batch-256 step --
+// runs under the other part's kernels.  The 8-phase GEMMs run whole rounds of one workgroup per CU, so a split
+// pays only where it adds no round: a candidate (b1, batch - b1) is admissible when every qkv / fc1 launch that takes tile
+// variant 31 for the whole batch takes it for both parts and the parts' summed rounds do not exceed the whole batch's
+// (ViT-B at 256: 7 + 10 whole, 18 for 128 + 128, 17 for 146 + 110).  Fewest summed rounds win, then the most even pair.
+// The summed rounds never fall below the whole batch's, so what the second stream recovers inside these GEMMs is the part
+// of a round that the whole batch's last rounds leave the chip empty; the split itself costs about 0.2 ms of a ViT-B step
+// (the ramps of twice the launches), which is 3/4 of a round per block there: a batch whose qkv and fc1 launches leave less
+// than SPLIT_MIN_IDLE of a round idle between them stays whole (ViT-B: 320, 384, 512; measured at 384: 12.87 -> 13.04 ms).
+// Returns the larger, first part; 0: no admissible pair, the forward runs the whole batch on the caller's stream.  Left
+// alone, for want of a measurement: batches no launch of which takes variant 31, fp8 models and SAM encoders.
+constexpr double SPLIT_MIN_IDLE = 0.75;
+int default_split(vdr_model* m, int batch, int ntok) {
+  const vdr_config& c = m->cfg;
+  if (c.fp8 || c.window > 0 || c.layers <= 0 || batch < 2) return 0;
+  if (m->split_batch == batch && m->split_ntok == ntok) return m->split_first;
+  double idle[2];
+  const int64_t whole[2] = {block_linear_rounds(m, false, batch, ntok, &idle[0]), block_linear_rounds(m, true, batch, ntok, &idle[1])};
+  int first = 0;
+  int64_t best = whole[0] + whole[1] + 1;
+  for (int b1 = (batch + 1) / 2; b1 < batch && idle[0] + idle[1] >= SPLIT_MIN_IDLE; ++b1) {
+    int64_t sum = 0;
+    bool kept = true;
+    for (int fc1 = 0; fc1 < 2; ++fc1) {
+      const int64_t r1 = block_linear_rounds(m, fc1, b1, ntok), r2 = block_linear_rounds(m, fc1, batch - b1, ntok);
+      kept = kept && (!whole[fc1] || (r1 && r2));
+      sum += r1 + r2;
+    }
+    if (kept && sum < best) {  // (b1 ascending: of equal sums the most even pair stays)
+      best = sum;
+      first = b1;
+    }
+  }
+  m->split_batch = batch;
+  m->split_ntok = ntok;
+  m->split_first = first;
+  return first;
+}
+
+// How a forward cuts its batch: `parts` micro-batches of mb images (the last one the rest), part k on internal stream
+// k % streams (streams == 1: the caller's) in workspace slice k % streams, each of `slice` bytes and carved for mb images.
+struct BatchPlan {
+  int mb, parts, streams;
+  bool by_default;  // default_split chose it (not vdr_config.micro_batch / streams)
+  size_t slice;
+  size_t bytes;     // the workspace of the call: what vdr_workspace_bytes reports and every forward asks for
+};
+
+// The one place that decides it, for vdr_workspace_bytes, the forwards and the workspace carve alike.  linear_only: the
+// caller's stream is being captured -- the default split stays out, so that a captured forward is a linear graph; `bytes` is
+// the same either way and covers both forms.
+BatchPlan batch_plan(vdr_model* m, int batch, int ntok, bool linear_only = false) {
+  const vdr_config& c = m->cfg;
+  BatchPlan p{};
+  p.streams = configured_streams(m);
+  p.mb = c.micro_batch > 0 ? (c.micro_batch < batch ? c.micro_batch : batch) : (batch + p.streams - 1) / p.streams;
+  const int first = c.micro_batch == 0 && c.streams == 0 ? default_split(m, batch, ntok) : 0;
+  p.by_default = first > 0;
+  if (first && !linear_only) {
+    p.mb = first;
+    p.streams = 2;
+  }
+  p.parts = (batch + p.mb - 1) / p.mb;
+  p.slice = carve(m, nullptr, p.mb, ntok).total;
+  p.bytes = p.slice * p.streams;
+  if (first) {  // (two slices for the larger part, or the whole batch in one)
+    const size_t two = 2 * carve(m, nullptr, first, ntok).total, whole = carve(m, nullptr, batch, ntok).total;
+    p.bytes = two > whole ? two : whole;
+  }
+  return p;
+}
+
+bool being_captured(hipStream_t s) {
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &st) != hipSuccess) {  // (the legacy stream while another thread captures: stay linear)
+    (void)hipGetLastError();
+    return true;
+  }
+  return st != hipStreamCaptureStatusNone;
+}
+
+// The rest of every forward once its arguments are checked: the device, the workspace, then the micro-batches of
+// batch_plan, each in its stream's slice of the workspace.  body(s, w, b0, mb) enqueues the micro-batch of images
+// b0 .. b0 + mb - 1.
 template <class Body>
 int run_micro_batches(vdr_model* m, int batch, int ntok, void* workspace, size_t workspace_bytes, void* stream, Body body) {
   int rc = check_device(m);
@@ -1633,24 +1730,24 @@ int run_micro_batches(vdr_model* m, int batch, int ntok, void* workspace, size_t
   if (!m->resolved) return fail(m, VDR_ERR_INCOMPLETE, "vdr_finalize has not run since the last vdr_set_weight");
   DeviceGuard dg(m->device);
   if (!dg.ok) return fail(m, VDR_ERR_HIP, "hipSetDevice failed");
-  const int mb_max = default_micro_batch(m, batch);
-  const int ns = num_streams(m);
-  const size_t per_ws = carve(m, nullptr, mb_max, ntok).total;
-  if (per_ws * ns > workspace_bytes)
-    return fail(m, VDR_ERR_WORKSPACE, "workspace too small: need " + std::to_string(per_ws * ns) + " bytes");
   hipStream_t caller = (hipStream_t)stream;
-  if (fork_streams(m, caller)) return fail(m, VDR_ERR_HIP, "internal stream setup failed");
+  BatchPlan p = batch_plan(m, batch, ntok);
+  if (p.bytes > workspace_bytes)
+    return fail(m, VDR_ERR_WORKSPACE, "workspace too small: need " + std::to_string(p.bytes) + " bytes");
+  if (p.by_default && being_captured(caller)) p = batch_plan(m, batch, ntok, true);
+  const int ns = p.streams;
+  if (fork_streams(m, caller, ns)) return fail(m, VDR_ERR_HIP, "internal stream setup failed");
   int chunk = 0;
-  for (int b0 = 0; b0 < batch; b0 += mb_max, ++chunk) {
-    const int mb = batch - b0 < mb_max ? batch - b0 : mb_max;
+  for (int b0 = 0; b0 < batch; b0 += p.mb, ++chunk) {
+    const int mb = batch - b0 < p.mb ? batch - b0 : p.mb;
     const int si = chunk % ns;
     m->cur_aux = si;
     m->stats_fresh = false;  // (nothing has finalised the statistics of this micro-batch yet)
     hipStream_t s = ns == 1 ? caller : m->streams[si].get();
-    const Carve w = carve(m, (char*)workspace + si * per_ws, mb_max, ntok);
+    const Carve w = carve(m, (char*)workspace + si * p.slice, p.mb, ntok);
     if ((rc = body(s, w, b0, mb))) return rc;
   }
-  if (join_streams(m, caller)) return fail(m, VDR_ERR_HIP, "internal stream join failed");
+  if (join_streams(m, caller, ns)) return fail(m, VDR_ERR_HIP, "internal stream join failed");
   return VDR_OK;
 }
 
@@ -1964,8 +2061,20 @@ int vdr_workspace_bytes(vdr_handle m, int batch, int seq, size_t* out) {
   if (!m || !out || batch <= 0) return fail(m, VDR_ERR_INVALID, "bad argument");
   const int ntok = m->cfg.patch ? m->n_tokens : seq + (m->cfg.has_cls ? 1 : 0);
   if (ntok <= 0) return fail(m, VDR_ERR_INVALID, "seq must be positive for a token model");
-  const int mb = default_micro_batch(m, batch);
-  *out = carve(m, nullptr, mb, ntok).total * num_streams(m);
+  DeviceGuard dg(m->device);  // (the default split counts rounds on the handle's device, as the forward will)
+  *out = batch_plan(m, batch, ntok).bytes;
+  return VDR_OK;
+}
+
+int vdr_batch_plan(vdr_handle m, int batch, int seq, int32_t* micro_batch, int32_t* parts, int32_t* streams) {
+  if (!m || !micro_batch || !parts || !streams || batch <= 0) return fail(m, VDR_ERR_INVALID, "bad argument");
+  const int ntok = m->cfg.patch ? m->n_tokens : seq + (m->cfg.has_cls ? 1 : 0);
+  if (ntok <= 0) return fail(m, VDR_ERR_INVALID, "seq must be positive for a token model");
+  DeviceGuard dg(m->device);
+  const BatchPlan p = batch_plan(m, batch, ntok);
+  *micro_batch = p.mb;
+  *parts = p.parts;
+  *streams = p.streams;
   return VDR_OK;
 }
 
@@ -2064,8 +2173,10 @@ static int forward_layers_impl(const char* fn, vdr_handle m, const void* images,
   }
   // binned facets, before anything is launched: 16-byte chunks of D channels, and the level means of the largest
   // micro-batch -- (h - 1) * mb * n * D fp32 -- inside the fc1 activation buffer (carve: Mp * mlp_hidden bf16)
-  {
-    const int mb = default_micro_batch(m, batch);
+  // (in either form of the forward: split by default, or whole on a stream that is being captured)
+  for (const bool linear_only : {false, true}) {
+    DeviceGuard dg(m->device);
+    const int mb = batch_plan(m, batch, m->n_tokens, linear_only).mb;
     const size_t u_bytes = (size_t)carve(m, nullptr, mb, m->n_tokens).Mp * c.mlp_hidden * 2;
     for (int k = 0; k < n_facets; ++k) {
       const int h = facets[k].hierarchy;

@@ -198,6 +198,8 @@ hipError_t launch_gemm(const GemmArgs& a, int epilogue, int variant, hipStream_t
 // last 256-row tile, at least 2 tiles per CU with the last round of workgroups at least 85 % full
 bool gemm_8p_eligible(const GemmArgs& a, int epilogue);
 bool gemm_8p_shape_ok(int64_t M, int N);  // its tile-count rule alone
+// rounds of one workgroup per CU such a launch runs (0: the rule refuses the shape); idle: the fraction of a round its last one leaves empty
+int64_t gemm_8p_rounds(int64_t M, int N, double* idle = nullptr);
 // [N][K] bf16 (row stride ld elements) -> the pair-interleaved weight layout (N even, K % 32 == 0)
 hipError_t launch_w_interleave(const void* src, void* dst, int N, int K, int64_t ld, hipStream_t s);
 

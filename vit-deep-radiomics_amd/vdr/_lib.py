@@ -75,6 +75,7 @@ SYMBOLS = {
     "vdr_num_weights": (_I, [_P]),
     "vdr_weight_name": (C.c_char_p, [_P, _I]),
     "vdr_workspace_bytes": (_I, [_P, _I, _I, C.POINTER(C.c_size_t)]),
+    "vdr_batch_plan": (_I, [_P, _I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "vdr_forward": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, C.c_size_t, _P]),
     "vdr_forward_layers": (_I, [_P, _P, _I, _I, C.POINTER(vdr_layer_out), _I, _P, C.c_size_t, _P]),
     "vdr_forward_attn_maps": (_I, [_P, _P, _I, _I, C.POINTER(vdr_layer_out), _I, C.POINTER(vdr_attn_map), _I, _P, C.c_size_t,

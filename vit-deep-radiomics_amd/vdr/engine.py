@@ -321,6 +321,13 @@ class Engine:
             self._ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
         return self._ws
 
+    def batch_plan(self, batch: int, seq: int = 0) -> "tuple[int, int, int]":
+        """vdr_batch_plan: (micro_batch, parts, streams) a forward of `batch` images (sequences of `seq` tokens) runs as --
+        the configured micro_batch / streams, or with both 0 the library's default split for this batch."""
+        mb, parts, streams = C.c_int32(), C.c_int32(), C.c_int32()
+        L.check(self.lib.vdr_batch_plan(self.h, batch, seq, C.byref(mb), C.byref(parts), C.byref(streams)), self.h)
+        return mb.value, parts.value, streams.value
+
     def _run(self, entry, x: torch.Tensor, *args, seq: int = 0):
         """The tail of every forward: entry(handle, x, its dtype, batch, *args, workspace, its size, the current stream),
         checked.  args: what the C entry point takes between `batch` and `workspace`."""
