@@ -645,6 +645,101 @@ int vdr_op_attention_probs(const void* qkv, void* out, int batch, int seq, int h
 int vdr_op_attention_pool(const float* q, const void* kv, int64_t ldkv, void* out, int batch, int n, int heads, int head_dim,
                           void* stream);
 
+/* ---- mask decoder ops: the kernels of SAM's box-prompt mask decoder (csrc/mask_decoder.hip; the decoder object below
+ * composes them with the GEMM and LayerNorm of the forward).  A "problem" is one (image, box) pair.  All three are compiled without floating-point
+ * contraction: every multiply and add below is rounded once unless written fma().
+ *
+ * Cross attention with a handful of rows on one side (segment_anything Attention inside TwoWayAttentionBlock):
+ *   out[p, i, h*dh + d] = sum_j softmax_j(Q[p,i,h] . K[p,j,h] dh^-0.5) v[p, j, h*dh + d]
+ *   Q[p,i,c] = float(q[p,i,c]) + q_add[i,c],  K[p,j,c] = float(k[p,j,c]) + k_add[j,c]   (one fp32 addition; no table: the float)
+ *   q    device bf16, row p * tq + i, ldq elements apart;  k, v  device bf16, row p * tk + j, ldk / ldv apart;  out  bf16, row
+ *        p * tq + i, ldo apart.  Each is read in place: a column slice of a wider buffer (a stacked projection) is fine.
+ *   q_add / k_add  device fp32 [tq, heads*dh] / [tk, heads*dh], dense, shared by every problem, or NULL: the positional-encoding
+ *        term pe W^T + b of a projection whose input is x + pe.
+ * head_dim 16 or 32, heads * head_dim <= 256, one of tq, tk at most 16.  s = the fma chain over d ascending from 0 (tk <= 16) or
+ * over the 8 columns of each 16-byte chunk followed by the chunks added in a tree (tk > 16); t = s * fp32(dh^-0.5 log2 e);
+ * p = 2^(t - m) on v_exp_f32.
+ *   tk <= 16 ("few keys"): K and v of the problem are held in LDS as fp32, one lane per (query row, head); m = max_j t_j,
+ *        L = p_0 + p_1 + ..., A_d = fma(p_j, v_jd, A_d) for j ascending, out = bf16(A_d / L): one IEEE division, one rounding.
+ *   tk > 16, tq <= 16 ("few queries"): one workgroup of 4 waves per (problem, head); key j goes to wave (j / KPW) % 4, slot
+ *        j % KPW (KPW = 512 / dh keys per wave and step), every (wave, slot) runs an online softmax per query (running maximum
+ *        m, l = fma(l, 2^(m - m'), p), acc likewise); the slots of a wave are rescaled to the wave's maximum and added in a
+ *        butterfly tree, the 4 waves in ascending order through LDS; out = bf16(A / L).  Every k / v byte is read once, 16 bytes
+ *        per lane.  Any summation order obeys |A_d - exact| <= gamma(tk + 2) sum_j p_j |v_jd| (tests/sam_decoder_ref.py).
+ * No atomics; which lane sums what depends on (tq, tk, dh) only, so a problem's bits do not depend on `problems` or its position.
+ * Refused before the device is touched: null q / k / v / out, non-positive sizes, problems > 65535, a leading dimension below
+ * heads*dh or no multiple of 8, a pointer off 16 bytes (VDR_ERR_INVALID); head_dim not 16 or 32, heads*dh > 256, tq and tk both
+ * above 16 (VDR_ERR_UNSUPPORTED). */
+int vdr_op_cross_attention(const void* q, int64_t ldq, const float* q_add, const void* k, int64_t ldk, const float* k_add,
+                           const void* v, int64_t ldv, void* out, int64_t ldo, int problems, int tq, int tk, int heads,
+                           int head_dim, void* stream);
+
+/* The token-side linear of the mask decoder (M = a few rows per problem, where a tile GEMM would be one ragged tile):
+ *   y[r, n] = [max(., 0)](sum_k X[r,k] W[g][n,k] + bias[g][n]) [+ float(resid[r, n])],   g = r % groups
+ *   X[r,k] = float(x[r,k]), or with x_add float(bf16(float(x[r,k]) + float(x_add[r,k])))  (torch's bf16 `x + pe`)
+ *   x, x_add, resid  device bf16, rows ldx / ldxa / ldr elements apart (x_add, resid may be NULL; resid may be y);
+ *   W  device bf16 [groups, N, K] (PyTorch layout per group), 16-byte aligned; bias fp32 [groups, N] or NULL;
+ *   y  bf16 or fp32 (out_dtype), rows ldy apart.
+ * The sum: 16 partial sums, partial q over the 8-element chunks q, q + 16, q + 32, .. of the row (k = 8 chunk .. 8 chunk + 7), each
+ * one fp32 fma chain in ascending k from 0; the partials added in ascending q; then + bias, the ReLU, + resid, each one rounding,
+ * then the rounding to out_dtype.  So relu = 1 gives max(., 0) of the bits relu = 0 gives.  `groups` > 1: the four hypernetwork MLPs of the decoder in
+ * one launch (row r = problem * 4 + mask token).  K % 8 == 0, K <= 2048 (VDR_ERR_UNSUPPORTED); anything else VDR_ERR_INVALID. */
+int vdr_op_token_linear(const void* x, int64_t ldx, const void* x_add, int64_t ldxa, const void* W, const float* bias,
+                        const void* resid, int64_t ldr, void* y, int out_dtype, int64_t ldy, int M, int N, int K, int groups,
+                        int relu, void* stream);
+
+/* The fused tail of the mask decoder's upscaling: GELU -> ConvTranspose2d(64, 32, kernel 2, stride 2) -> GELU -> the product
+ * with the problem's hypernetwork outputs -> low-resolution logits.  The 32-channel 4g x 4g map is never written.
+ *   x      device bf16 [problems*g*g*4, 64]: row (p*g*g + cy*g + cx)*4 + dy1*2 + dx1 is pixel (2cy+dy1, 2cx+dx1) of the 2g x 2g
+ *          map after LayerNorm2d (the first transposed convolution as a linear on the weight reshaped to [4*64, C], then
+ *          vdr_op_layernorm at D = 64).  gelu_in = 1: a = bf16(gelu(float(x))) is applied on load (the library's device
+ *          polynomial, csrc/vdr_dev.h gelu_erf; pinned by the GELU tests of the GEMM epilogue); 0: a = x
+ *   W      device bf16 [4*32, 64]: row (dy2*2+dx2)*32 + c = ConvTranspose2d.weight[:, c, dy2, dx2];  bias fp32 [32]
+ *   hyper  device fp32 [problems, 4, 32]
+ *   out    device fp32 [problems, 4, 4g, 4g]:
+ *          u_c = gelu(sum_k a_k W[s2*32+c, k] + bias[c])   (fp32 MFMA accumulation over k, one addition, the polynomial)
+ *          out[p, m, 2(2cy+dy1)+dy2, 2(2cx+dx1)+dx2] = (sum over c in C0 of hyper[p,m,c] u_c) + (sum over c in C1), each an fma
+ *          chain from 0 in ascending c; C0 = channels with (c & 4) == 0, C1 the others (the two half-waves of the MFMA tile).
+ * g in [1, 64] (VDR_ERR_UNSUPPORTED); null or misaligned (16 bytes) pointers, problems <= 0: VDR_ERR_INVALID. */
+int vdr_op_mask_upscale(const void* x, const void* W, const float* bias, const float* hyper, float* out, int problems, int g,
+                        int gelu_in, void* stream);
+
+/* ---- the mask decoder object: SAM's box-prompt encoder and mask decoder as ONE call on the neck output of the image encoder.
+ * A handle of its own: the vdr_weight_name enumeration, the workspace size and the launches of a vdr_handle do not change.
+ * The arithmetic is the composition of the ops above with vdr_op_linear and vdr_op_layernorm (csrc/vdr_api.hip vdr_mask_decode;
+ * DESIGN 4.3c); a "problem" is one (image, box) pair, P = batch * boxes_per_image.
+ *   config: what segment_anything's MaskDecoder / TwoWayTransformer are built with.  The kernels cover channels 256, heads 8,
+ *   depth 2, attention_downsample_rate 2, mask_tokens 4, upscale channels 64 / 32, iou_head_depth 3, mlp_dim any multiple of 64 up
+ *   to 2048, grid 1 .. 64 (anything else: VDR_ERR_UNSUPPORTED).  img: the side of the input image the boxes are given in.
+ *   ln_eps: the four LayerNorms of each two-way block (segment_anything 1e-5; transformers.SamModel applies 1e-6);
+ *   final_ln_eps: norm_final_attn (1e-5 in both); ln2d_eps: the upscaling's LayerNorm2d (1e-6 in both).
+ *   weights: segment_anything's names (vdr_mask_decoder_weight_name enumerates them, vdr_mask_decoder_num_weights counts), host
+ *   fp32, any shape with the right element count; VDR_ERR_UNKNOWN_NAME otherwise.  vdr_mask_decoder_finalize rounds the GEMM
+ *   weights to bf16, stacks the projections, builds the positional-encoding tables in float64 (VDR_ERR_INCOMPLETE: a weight is
+ *   missing) and frees the host copies.
+ *   vdr_mask_decode: emb device fp32 [batch, 256, g, g] (channels_last = 0) or [batch, g, g, 256] (1: the encoder's own
+ *   VDR_OUT_ENCODER layout); boxes device fp32 [batch, boxes_per_image, 4] (x0, y0, x1, y1) in pixels of the img x img input;
+ *   logits device fp32 [P, 4, 4g, 4g] and iou device fp32 [P, 4], all four mask tokens (token 0: the single-mask output, 1 .. 3:
+ *   the multi-mask ones).  50 launches + 2 of set-up on `stream`, whatever batch and boxes_per_image; no host synchronisation, no
+ *   allocation, no atomics; a problem's bits depend neither on P nor on its position.  Every refusal comes before the device is
+ *   touched; a workspace smaller than vdr_mask_decoder_workspace_bytes(P) is VDR_ERR_WORKSPACE before anything is written, and
+ *   nothing past that size is. */
+typedef struct {
+  int32_t grid, img, channels, heads, depth, mlp_dim, attention_downsample_rate, mask_tokens, upscale_channels_1, upscale_channels_2,
+      iou_head_depth;
+  float ln_eps, final_ln_eps, ln2d_eps;
+} vdr_mask_decoder_config;
+typedef struct vdr_mask_decoder* vdr_mask_decoder_handle;
+int vdr_mask_decoder_create(const vdr_mask_decoder_config* cfg, int device, vdr_mask_decoder_handle* out);
+void vdr_mask_decoder_destroy(vdr_mask_decoder_handle d);
+int vdr_mask_decoder_num_weights(vdr_mask_decoder_handle d);
+const char* vdr_mask_decoder_weight_name(vdr_mask_decoder_handle d, int i);
+int vdr_mask_decoder_set_weight(vdr_mask_decoder_handle d, const char* name, const float* host, const int64_t* shape, int ndim);
+int vdr_mask_decoder_finalize(vdr_mask_decoder_handle d);
+int vdr_mask_decoder_workspace_bytes(vdr_mask_decoder_handle d, int problems, size_t* out);
+int vdr_mask_decode(vdr_mask_decoder_handle d, const float* emb, int channels_last, const float* boxes, int batch, int boxes_per_image,
+                    void* workspace, size_t workspace_bytes, float* logits, float* iou, void* stream);
+
 /* SAM / MedSAM Attention.forward with use_rel_pos (third-party segment_anything ImageEncoderViT, called at
  * tfds_dense_descriptor.py:123): per (window, head) softmax(q k^T dh^-0.5 + q.Rh[qh-kh] + q.Rw[qw-kw]) v.
  *   qkv   [batch*S*S, 3*H*64] bf16, `batch` windows (or whole grids) of S x S tokens, row-major (h, w)

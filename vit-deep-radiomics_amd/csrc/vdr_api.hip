@@ -2702,6 +2702,55 @@ int vdr_op_attention_pool(const float* q, const void* kv, int64_t ldkv, void* ou
          "attention_pool");
 }
 
+// ---- the mask decoder ops (csrc/mask_decoder.hip) ----
+int vdr_op_cross_attention(const void* q, int64_t ldq, const float* q_add, const void* k, int64_t ldk, const float* k_add,
+                           const void* v, int64_t ldv, void* out, int64_t ldo, int problems, int tq, int tk, int heads,
+                           int head_dim, void* stream) {
+  const char* op = "vdr_op_cross_attention";
+  if (!q || !k || !v || !out) return refuse(op, VDR_ERR_INVALID, "null pointer");
+  if (head_dim != 16 && head_dim != 32) return refuse(op, VDR_ERR_UNSUPPORTED, "head dim must be 16 or 32");
+  if (problems <= 0 || tq <= 0 || tk <= 0 || heads <= 0) return refuse(op, VDR_ERR_INVALID, "problems, tq, tk and heads must be positive");
+  if (problems > 65535) return refuse(op, VDR_ERR_INVALID, "at most 65535 problems");
+  if (tq > 16 && tk > 16) return refuse(op, VDR_ERR_UNSUPPORTED, "one of tq and tk must be at most 16");
+  const int64_t HD = (int64_t)heads * head_dim;
+  if (HD > 256) return refuse(op, VDR_ERR_UNSUPPORTED, "heads * head_dim must be at most 256");
+  if (ldq < HD || ldk < HD || ldv < HD || ldo < HD || ((ldq | ldk | ldv | ldo) & 7))
+    return refuse(op, VDR_ERR_INVALID, "ldq, ldk, ldv and ldo must be multiples of 8, at least heads * head_dim");
+  if (!aligned16({q, q_add, k, k_add, v, out})) return refuse(op, VDR_ERR_INVALID, "pointers must be 16-byte aligned");
+  RUN_OP(launch_cross_attention(q, ldq, q_add, k, ldk, k_add, v, ldv, out, ldo, problems, tq, tk, heads, head_dim, (hipStream_t)stream),
+         "cross_attention");
+}
+
+int vdr_op_token_linear(const void* x, int64_t ldx, const void* x_add, int64_t ldxa, const void* W, const float* bias,
+                        const void* resid, int64_t ldr, void* y, int out_dtype, int64_t ldy, int M, int N, int K, int groups,
+                        int relu, void* stream) {
+  const char* op = "vdr_op_token_linear";
+  if (!x || !W || !y) return refuse(op, VDR_ERR_INVALID, "null pointer");
+  if (out_dtype != VDR_F32 && out_dtype != VDR_BF16) return refuse(op, VDR_ERR_INVALID, "out_dtype must be VDR_F32 or VDR_BF16");
+  if (M <= 0 || N <= 0 || K <= 0 || groups <= 0 || groups > M) return refuse(op, VDR_ERR_INVALID, "M, N, K must be positive, groups in [1, M]");
+  if ((K & 7) || K > 2048) return refuse(op, VDR_ERR_UNSUPPORTED, "K must be a multiple of 8, at most 2048");
+  if ((int64_t)((M + groups - 1) / groups + 7) / 8 * groups > 65535) return refuse(op, VDR_ERR_UNSUPPORTED, "too many rows");
+  if (relu != 0 && relu != 1) return refuse(op, VDR_ERR_INVALID, "relu must be 0 or 1");
+  if (ldx < K || (x_add && ldxa < K) || (resid && ldr < N) || ldy < N) return refuse(op, VDR_ERR_INVALID, "a leading dimension is shorter than its row");
+  if (!aligned16({W}) || ((uintptr_t)x & 1) || ((uintptr_t)y & (out_dtype == VDR_F32 ? 3 : 1)) || ((uintptr_t)bias & 3))
+    return refuse(op, VDR_ERR_INVALID, "W must be 16-byte aligned, the others to their element");
+  RUN_OP(launch_token_linear(x, ldx, x_add, ldxa, W, bias, resid, ldr, y, out_dtype == VDR_F32, ldy, M, N, K, groups, relu,
+                             (hipStream_t)stream),
+         "token_linear");
+}
+
+int vdr_op_mask_upscale(const void* x, const void* W, const float* bias, const float* hyper, float* out, int problems, int g,
+                        int gelu_in, void* stream) {
+  const char* op = "vdr_op_mask_upscale";
+  if (!x || !W || !bias || !hyper || !out) return refuse(op, VDR_ERR_INVALID, "null pointer");
+  if (problems <= 0) return refuse(op, VDR_ERR_INVALID, "problems must be positive");
+  if (g < 1 || g > 64) return refuse(op, VDR_ERR_UNSUPPORTED, "g must be in [1, 64]");
+  if ((int64_t)problems * g * g * 4 > INT32_MAX) return refuse(op, VDR_ERR_INVALID, "problems * g * g * 4 exceeds 2^31 - 1");
+  if (gelu_in != 0 && gelu_in != 1) return refuse(op, VDR_ERR_INVALID, "gelu_in must be 0 or 1");
+  if (!aligned16({x, W, bias, hyper, out})) return refuse(op, VDR_ERR_INVALID, "pointers must be 16-byte aligned");
+  RUN_OP(launch_mask_upscale(x, W, bias, hyper, out, problems, g, gelu_in, (hipStream_t)stream), "mask_upscale");
+}
+
 int vdr_op_attention_relpos(const void* qkv, const float* rel_pos_h, const float* rel_pos_w, float* rel, void* out,
                             int batch, int S, int heads, void* stream) {
   if (!qkv || !rel_pos_h || !rel_pos_w || !rel || !out) return fail(nullptr, VDR_ERR_INVALID, "null argument");
@@ -3209,6 +3258,452 @@ int vdr_profile_read(vdr_handle m, double* ms, int64_t* launches, double* flops,
     m->p_flops[k] = 0;
     m->p_bytes[k] = 0;
   }
+  return VDR_OK;
+}
+
+}  // extern "C"
+
+// ---- the mask decoder object (include/vdr.h "mask decoder"; kernels: csrc/mask_decoder.hip) -------------------------------------
+struct vdr_mask_decoder {
+  vdr_mask_decoder_config cfg;
+  std::vector<std::string> names;
+  std::vector<std::vector<int64_t>> shapes;
+  std::map<std::string, std::vector<float>> host;   // what vdr_mask_decoder_set_weight was given
+  std::map<std::string, void*> dev;                 // what vdr_mask_decoder_finalize built (owned)
+  bool finalized = false;
+  ~vdr_mask_decoder() {
+    for (auto& kv : dev) (void)hipFree(kv.second);
+  }
+};
+
+namespace {
+
+using MD = vdr_mask_decoder;
+constexpr int MD_C = 256, MD_T = 7, MD_IN = 128;
+
+void md_names(MD* d) {
+  auto add = [&](const std::string& n, std::vector<int64_t> shp) {
+    d->names.push_back(n);
+    d->shapes.push_back(std::move(shp));
+  };
+  const int64_t C = MD_C, F = d->cfg.mlp_dim;
+  auto attn = [&](const std::string& p, int64_t inner) {
+    for (const char* n : {"q_proj", "k_proj", "v_proj"}) {
+      add(p + n + ".weight", {inner, C});
+      add(p + n + ".bias", {inner});
+    }
+    add(p + "out_proj.weight", {C, inner});
+    add(p + "out_proj.bias", {C});
+  };
+  auto ln = [&](const std::string& p, int64_t n) {
+    add(p + ".weight", {n});
+    add(p + ".bias", {n});
+  };
+  add("prompt_encoder.pe_layer.positional_encoding_gaussian_matrix", {2, C / 2});
+  add("prompt_encoder.point_embeddings.2.weight", {1, C});
+  add("prompt_encoder.point_embeddings.3.weight", {1, C});
+  add("prompt_encoder.no_mask_embed.weight", {1, C});
+  add("mask_decoder.iou_token.weight", {1, C});
+  add("mask_decoder.mask_tokens.weight", {4, C});
+  for (int i = 0; i < 2; ++i) {
+    const std::string p = "mask_decoder.transformer.layers." + std::to_string(i) + ".";
+    attn(p + "self_attn.", C);
+    ln(p + "norm1", C);
+    attn(p + "cross_attn_token_to_image.", MD_IN);
+    ln(p + "norm2", C);
+    add(p + "mlp.lin1.weight", {F, C});
+    add(p + "mlp.lin1.bias", {F});
+    add(p + "mlp.lin2.weight", {C, F});
+    add(p + "mlp.lin2.bias", {C});
+    ln(p + "norm3", C);
+    ln(p + "norm4", C);
+    attn(p + "cross_attn_image_to_token.", MD_IN);
+  }
+  attn("mask_decoder.transformer.final_attn_token_to_image.", MD_IN);
+  ln("mask_decoder.transformer.norm_final_attn", C);
+  add("mask_decoder.output_upscaling.0.weight", {C, 64, 2, 2});
+  add("mask_decoder.output_upscaling.0.bias", {64});
+  ln("mask_decoder.output_upscaling.1", 64);
+  add("mask_decoder.output_upscaling.3.weight", {64, 32, 2, 2});
+  add("mask_decoder.output_upscaling.3.bias", {32});
+  for (int m = 0; m < 4; ++m)
+    for (int j = 0; j < 3; ++j) {
+      const std::string p = "mask_decoder.output_hypernetworks_mlps." + std::to_string(m) + ".layers." + std::to_string(j);
+      add(p + ".weight", {j == 2 ? 32 : C, C});
+      add(p + ".bias", {j == 2 ? 32 : C});
+    }
+  for (int j = 0; j < 3; ++j) {
+    const std::string p = "mask_decoder.iou_prediction_head.layers." + std::to_string(j);
+    add(p + ".weight", {j == 2 ? 4 : C, C});
+    add(p + ".bias", {j == 2 ? 4 : C});
+  }
+}
+
+float md_bf16_round(float f) {
+  const uint32_t u = (uint32_t)f32_to_bf16(f) << 16;
+  float r;
+  memcpy(&r, &u, 4);
+  return r;
+}
+
+// the decode's workspace: every buffer 256-byte aligned, in this order
+struct MdCarve {
+  size_t pe, tok, tmp, qkv, att, q, kv2, h, keys, keys2, img, atti, up, up2, hx1, hx2, hyper, ix1, ix2, total;
+};
+MdCarve md_carve(const MD* d, int64_t P) {
+  const int64_t n = (int64_t)d->cfg.grid * d->cfg.grid, T = MD_T * P;
+  MdCarve c{};
+  size_t off = 0;
+  auto take = [&](int64_t bytes) {
+    const size_t o = off;
+    off += ((size_t)bytes + 255) / 256 * 256;
+    return o;
+  };
+  c.pe = take(T * MD_C * 2);
+  c.tok = take(T * MD_C * 2);
+  c.tmp = take(T * MD_C * 2);
+  c.qkv = take(T * 3 * MD_C * 2);
+  c.att = take(T * MD_C * 2);
+  c.q = take(T * MD_IN * 2);
+  c.kv2 = take(T * 2 * MD_IN * 2);
+  c.h = take(T * (int64_t)d->cfg.mlp_dim * 2);
+  c.keys = take(P * n * MD_C * 2);
+  c.keys2 = take(P * n * MD_C * 2);
+  c.img = take(P * n * 3 * MD_IN * 2);
+  c.atti = take(P * n * MD_IN * 2);
+  c.up = take(P * n * MD_C * 2);
+  c.up2 = take(P * n * MD_C * 2);
+  c.hx1 = take(4 * P * MD_C * 2);
+  c.hx2 = take(4 * P * MD_C * 2);
+  c.hyper = take(4 * P * 32 * 4);
+  c.ix1 = take(P * MD_C * 2);
+  c.ix2 = take(P * MD_C * 2);
+  c.total = off;
+  return c;
+}
+
+int md_upload(MD* d, const std::string& label, const void* src, size_t bytes) {
+  void* p = nullptr;
+  OP_TRY(hipMalloc(&p, bytes), "hipMalloc(mask decoder weight)");
+  d->dev[label] = p;
+  OP_TRY(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice), "hipMemcpy(mask decoder weight)");
+  return VDR_OK;
+}
+int md_up_bf(MD* d, const std::string& label, const std::vector<float>& v) {
+  std::vector<uint16_t> b(v.size());
+  for (size_t i = 0; i < v.size(); ++i) b[i] = f32_to_bf16(v[i]);
+  return md_upload(d, label, b.data(), b.size() * 2);
+}
+int md_up_f32(MD* d, const std::string& label, const std::vector<float>& v) { return md_upload(d, label, v.data(), v.size() * 4); }
+
+std::vector<float> md_cat(std::initializer_list<const std::vector<float>*> parts) {
+  std::vector<float> o;
+  for (auto* p : parts) o.insert(o.end(), p->begin(), p->end());
+  return o;
+}
+
+int md_ln(const void* x, void* y, const float* gamma, const float* beta, int64_t rows, int D, float eps, hipStream_t s) {
+  LnArgs a{};
+  a.x = x;
+  a.in_bf16 = 1;
+  a.y = y;
+  a.out_bf16 = 1;
+  a.gamma = gamma;
+  a.beta = beta;
+  a.rows = rows;
+  a.D = D;
+  a.eps = eps;
+  a.imap = identity_map();
+  a.omap = identity_map();
+  OP_TRY(launch_layernorm(a, s), "layernorm");
+  return VDR_OK;
+}
+
+int md_gemm(const void* x, const void* W, const float* bias, const void* resid, void* y, int64_t M, int N, int K, hipStream_t s) {
+  const int epi = resid ? EPI_BIAS_RESID : EPI_BIAS;
+  GemmArgs g = linear(x, W, y, M, N, K, epi);
+  g.bias = bias;
+  g.resid = resid;
+  return op_gemm(g, epi, gemm_variant_for(VDR_K_GEMM_FC1, M, N), (void*)s, "mask decoder gemm: unsupported shape");
+}
+
+}  // namespace
+
+extern "C" {
+
+int vdr_mask_decoder_create(const vdr_mask_decoder_config* cfg, int device, vdr_mask_decoder_handle* out) {
+  const char* op = "vdr_mask_decoder_create";
+  if (!cfg || !out) return refuse(op, VDR_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (device < 0) return refuse(op, VDR_ERR_INVALID, "device must be >= 0");
+  if (cfg->grid < 1 || cfg->grid > 64) return refuse(op, VDR_ERR_UNSUPPORTED, "grid must be 1 .. 64");
+  if (cfg->img <= 0) return refuse(op, VDR_ERR_INVALID, "img (the input side the boxes are given in) must be positive");
+  if (cfg->channels != 256 || cfg->heads != 8 || cfg->depth != 2 || cfg->attention_downsample_rate != 2 || cfg->mask_tokens != 4 ||
+      cfg->upscale_channels_1 != 64 || cfg->upscale_channels_2 != 32 || cfg->iou_head_depth != 3)
+    return refuse(op, VDR_ERR_UNSUPPORTED, "channels 256, heads 8, depth 2, attention downsample rate 2, 4 mask tokens, upscale channels 64 / 32, IoU head depth 3");
+  if (cfg->mlp_dim <= 0 || cfg->mlp_dim % 64 || cfg->mlp_dim > 2048) return refuse(op, VDR_ERR_UNSUPPORTED, "mlp_dim must be a multiple of 64, at most 2048");
+  if (!(cfg->ln_eps > 0.0f) || !(cfg->final_ln_eps > 0.0f) || !(cfg->ln2d_eps > 0.0f)) return refuse(op, VDR_ERR_INVALID, "the eps fields must be positive");
+  if (int rc = check_device(nullptr)) return rc;
+  OP_TRY(hipSetDevice(device), "hipSetDevice");
+  MD* d = new MD();
+  d->cfg = *cfg;
+  md_names(d);
+  *out = d;
+  return VDR_OK;
+}
+
+void vdr_mask_decoder_destroy(vdr_mask_decoder_handle d) { delete d; }
+
+int vdr_mask_decoder_num_weights(vdr_mask_decoder_handle d) { return d ? (int)d->names.size() : 0; }
+
+const char* vdr_mask_decoder_weight_name(vdr_mask_decoder_handle d, int i) {
+  return d && i >= 0 && i < (int)d->names.size() ? d->names[i].c_str() : nullptr;
+}
+
+int vdr_mask_decoder_set_weight(vdr_mask_decoder_handle d, const char* name, const float* host, const int64_t* shape, int ndim) {
+  const char* op = "vdr_mask_decoder_set_weight";
+  if (!d || !name || !host || !shape || ndim < 1 || ndim > 4) return refuse(op, VDR_ERR_INVALID, "null or malformed argument");
+  if (d->finalized) return refuse(op, VDR_ERR_INVALID, "the decoder is finalized");
+  for (size_t i = 0; i < d->names.size(); ++i)
+    if (d->names[i] == name) {
+      int64_t want = 1, got = 1;
+      for (int64_t v : d->shapes[i]) want *= v;
+      for (int k = 0; k < ndim; ++k) got *= shape[k];
+      if (got != want) return refuse(op, VDR_ERR_INVALID, std::string(name) + ": element count mismatch");
+      d->host[name].assign(host, host + want);
+      return VDR_OK;
+    }
+  return refuse(op, VDR_ERR_UNKNOWN_NAME, std::string("unknown weight ") + name);
+}
+
+int vdr_mask_decoder_finalize(vdr_mask_decoder_handle d) {
+  const char* op = "vdr_mask_decoder_finalize";
+  if (!d) return refuse(op, VDR_ERR_INVALID, "null handle");
+  if (d->finalized) return VDR_OK;
+  for (auto& n : d->names)
+    if (!d->host.count(n)) return refuse(op, VDR_ERR_INCOMPLETE, "missing weight " + n);
+  auto& H = d->host;
+  const int g = d->cfg.grid, n = g * g;
+  // the Fourier features of the cell centres, float64: [n, 256]
+  const std::vector<float>& G = H["prompt_encoder.pe_layer.positional_encoding_gaussian_matrix"];
+  std::vector<double> kpe((size_t)n * MD_C);
+  for (int y = 0; y < g; ++y)
+    for (int x = 0; x < g; ++x)
+      for (int f = 0; f < 128; ++f) {
+        const double cx = 2.0 * ((x + 0.5) / g) - 1.0, cy = 2.0 * ((y + 0.5) / g) - 1.0;
+        const double ph = 6.283185307179586476925286766559 * (cx * (double)G[f] + cy * (double)G[128 + f]);
+        kpe[(size_t)(y * g + x) * MD_C + f] = sin(ph);
+        kpe[(size_t)(y * g + x) * MD_C + 128 + f] = cos(ph);
+      }
+  // pe W^T + b on the bf16-rounded weight the GEMM multiplies with: fp32 [n, 128]
+  auto table = [&](const std::string& p) {
+    const std::vector<float>&W = H[p + ".weight"], &b = H[p + ".bias"];
+    std::vector<double> Wr(W.size());
+    for (size_t i = 0; i < W.size(); ++i) Wr[i] = (double)md_bf16_round(W[i]);
+    std::vector<float> t((size_t)n * MD_IN);
+    for (int r = 0; r < n; ++r)
+      for (int o = 0; o < MD_IN; ++o) {
+        double a = 0.0;
+        for (int k = 0; k < MD_C; ++k) a += kpe[(size_t)r * MD_C + k] * Wr[(size_t)o * MD_C + k];
+        t[(size_t)r * MD_IN + o] = (float)(a + (double)b[o]);
+      }
+    return t;
+  };
+  // ConvTranspose2d weight [Cin, Cout, 2, 2] -> [(dy, dx, Cout), Cin]
+  auto convt = [&](const std::vector<float>& W, int Cin, int Cout) {
+    std::vector<float> o((size_t)4 * Cout * Cin);
+    for (int ci = 0; ci < Cin; ++ci)
+      for (int co = 0; co < Cout; ++co)
+        for (int s = 0; s < 4; ++s) o[((size_t)s * Cout + co) * Cin + ci] = W[((size_t)ci * Cout + co) * 4 + s];
+    return o;
+  };
+  const std::vector<float> z128(MD_IN, 0.0f);
+#define MD_UP(call)            \
+  do {                         \
+    if (int rc = (call)) return rc; \
+  } while (0)
+  MD_UP(md_up_f32(d, "gauss", G));
+  MD_UP(md_up_f32(d, "corner", md_cat({&H["prompt_encoder.point_embeddings.2.weight"], &H["prompt_encoder.point_embeddings.3.weight"]})));
+  MD_UP(md_up_f32(d, "fixed", md_cat({&H["mask_decoder.iou_token.weight"], &H["mask_decoder.mask_tokens.weight"]})));
+  MD_UP(md_up_f32(d, "no_mask", H["prompt_encoder.no_mask_embed.weight"]));
+  auto attn = [&](const std::string& L, const std::string& p) -> int {
+    MD_UP(md_up_bf(d, L + "wq", H[p + "q_proj.weight"]));
+    MD_UP(md_up_f32(d, L + "bq", H[p + "q_proj.bias"]));
+    MD_UP(md_up_bf(d, L + "wo", H[p + "out_proj.weight"]));
+    MD_UP(md_up_f32(d, L + "bo", H[p + "out_proj.bias"]));
+    return VDR_OK;
+  };
+  auto norm = [&](const std::string& L, const std::string& p) -> int {
+    MD_UP(md_up_f32(d, L + "g", H[p + ".weight"]));
+    MD_UP(md_up_f32(d, L + "b", H[p + ".bias"]));
+    return VDR_OK;
+  };
+  for (int i = 0; i < 2; ++i) {
+    const std::string L = "l" + std::to_string(i) + ".", p = "mask_decoder.transformer.layers." + std::to_string(i) + ".";
+    const std::string s = p + "self_attn.", a = p + "cross_attn_token_to_image.", b = p + "cross_attn_image_to_token.";
+    MD_UP(md_up_bf(d, L + "wqk", md_cat({&H[s + "q_proj.weight"], &H[s + "k_proj.weight"]})));
+    MD_UP(md_up_f32(d, L + "bqk", md_cat({&H[s + "q_proj.bias"], &H[s + "k_proj.bias"]})));
+    MD_UP(md_up_bf(d, L + "wv", H[s + "v_proj.weight"]));
+    MD_UP(md_up_f32(d, L + "bv", H[s + "v_proj.bias"]));
+    MD_UP(md_up_bf(d, L + "wo", H[s + "out_proj.weight"]));
+    MD_UP(md_up_f32(d, L + "bo", H[s + "out_proj.bias"]));
+    MD_UP(attn(L + "t2i.", a));
+    // the image side of the block in one GEMM: columns [k of token-to-image | v of token-to-image | q of image-to-token]
+    MD_UP(md_up_bf(d, L + "t2i.wimg", md_cat({&H[a + "k_proj.weight"], &H[a + "v_proj.weight"], &H[b + "q_proj.weight"]})));
+    MD_UP(md_up_f32(d, L + "t2i.bimg", md_cat({&z128, &H[a + "v_proj.bias"], &z128})));
+    MD_UP(md_up_f32(d, L + "t2i.ktab", table(a + "k_proj")));
+    MD_UP(md_up_f32(d, L + "qtab", table(b + "q_proj")));
+    MD_UP(md_up_bf(d, L + "w1", H[p + "mlp.lin1.weight"]));
+    MD_UP(md_up_f32(d, L + "b1", H[p + "mlp.lin1.bias"]));
+    MD_UP(md_up_bf(d, L + "w2", H[p + "mlp.lin2.weight"]));
+    MD_UP(md_up_f32(d, L + "b2", H[p + "mlp.lin2.bias"]));
+    MD_UP(md_up_bf(d, L + "wk2", H[b + "k_proj.weight"]));
+    MD_UP(md_up_f32(d, L + "bk2", H[b + "k_proj.bias"]));
+    MD_UP(md_up_bf(d, L + "wv2", H[b + "v_proj.weight"]));
+    MD_UP(md_up_f32(d, L + "bv2", H[b + "v_proj.bias"]));
+    MD_UP(md_up_bf(d, L + "wo2", H[b + "out_proj.weight"]));
+    MD_UP(md_up_f32(d, L + "bo2", H[b + "out_proj.bias"]));
+    for (int j = 1; j <= 4; ++j) MD_UP(norm(L + "n" + std::to_string(j), p + "norm" + std::to_string(j)));
+  }
+  {
+    const std::string f = "mask_decoder.transformer.final_attn_token_to_image.";
+    MD_UP(attn("f.", f));
+    MD_UP(md_up_bf(d, "f.wimg", md_cat({&H[f + "k_proj.weight"], &H[f + "v_proj.weight"]})));
+    MD_UP(md_up_f32(d, "f.bimg", md_cat({&z128, &H[f + "v_proj.bias"]})));
+    MD_UP(md_up_f32(d, "f.ktab", table(f + "k_proj")));
+    MD_UP(norm("f.n", "mask_decoder.transformer.norm_final_attn"));
+  }
+  {
+    const std::string U = "mask_decoder.output_upscaling.";
+    MD_UP(md_up_bf(d, "up1.w", convt(H[U + "0.weight"], MD_C, 64)));
+    const std::vector<float>& b1 = H[U + "0.bias"];
+    MD_UP(md_up_f32(d, "up1.b", md_cat({&b1, &b1, &b1, &b1})));
+    MD_UP(norm("up.n", U + "1"));
+    MD_UP(md_up_bf(d, "up2.w", convt(H[U + "3.weight"], 64, 32)));
+    MD_UP(md_up_f32(d, "up2.b", H[U + "3.bias"]));
+  }
+  for (int j = 0; j < 3; ++j) {
+    std::vector<float> w, b;
+    for (int m = 0; m < 4; ++m) {
+      const std::string p = "mask_decoder.output_hypernetworks_mlps." + std::to_string(m) + ".layers." + std::to_string(j);
+      w.insert(w.end(), H[p + ".weight"].begin(), H[p + ".weight"].end());
+      b.insert(b.end(), H[p + ".bias"].begin(), H[p + ".bias"].end());
+    }
+    MD_UP(md_up_bf(d, "hy" + std::to_string(j) + ".w", w));
+    MD_UP(md_up_f32(d, "hy" + std::to_string(j) + ".b", b));
+    const std::string p = "mask_decoder.iou_prediction_head.layers." + std::to_string(j);
+    MD_UP(md_up_bf(d, "iou" + std::to_string(j) + ".w", H[p + ".weight"]));
+    MD_UP(md_up_f32(d, "iou" + std::to_string(j) + ".b", H[p + ".bias"]));
+  }
+#undef MD_UP
+  d->host.clear();
+  d->finalized = true;
+  return VDR_OK;
+}
+
+int vdr_mask_decoder_workspace_bytes(vdr_mask_decoder_handle d, int problems, size_t* out) {
+  const char* op = "vdr_mask_decoder_workspace_bytes";
+  if (!d || !out) return refuse(op, VDR_ERR_INVALID, "null argument");
+  if (problems <= 0 || problems > 65535) return refuse(op, VDR_ERR_INVALID, "problems must be 1 .. 65535");
+  *out = md_carve(d, problems).total;
+  return VDR_OK;
+}
+
+int vdr_mask_decode(vdr_mask_decoder_handle d, const float* emb, int channels_last, const float* boxes, int batch, int boxes_per_image,
+                    void* workspace, size_t workspace_bytes, float* logits, float* iou, void* stream) {
+  const char* op = "vdr_mask_decode";
+  if (!d || !emb || !boxes || !workspace || !logits || !iou) return refuse(op, VDR_ERR_INVALID, "null argument");
+  if (channels_last != 0 && channels_last != 1) return refuse(op, VDR_ERR_INVALID, "channels_last must be 0 or 1");
+  if (batch <= 0 || boxes_per_image <= 0 || (int64_t)batch * boxes_per_image > 65535)
+    return refuse(op, VDR_ERR_INVALID, "batch and boxes_per_image must be positive, at most 65535 problems");
+  if (!aligned16({emb, boxes, workspace, logits, iou})) return refuse(op, VDR_ERR_INVALID, "pointers must be 16-byte aligned");
+  if (!d->finalized) return refuse(op, VDR_ERR_INCOMPLETE, "vdr_mask_decoder_finalize has not run");
+  const int P = batch * boxes_per_image, g = d->cfg.grid, n = g * g, T = MD_T, C = MD_C, F = d->cfg.mlp_dim;
+  const MdCarve c = md_carve(d, P);
+  if (workspace_bytes < c.total) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(c.total) + " bytes needed");
+  if (int rc = check_device(nullptr)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  bool missing = false;  // (a label finalize did not build: an internal error, reported instead of thrown across the C boundary)
+  auto W = [&](const std::string& k) {
+    auto it = d->dev.find(k);
+    if (it == d->dev.end()) missing = true;
+    return it == d->dev.end() ? (const void*)nullptr : (const void*)it->second;
+  };
+  auto Fp = [&](const std::string& k) { return (const float*)W(k); };
+  for (const char* k : {"fixed", "gauss", "corner", "no_mask", "up1.w", "up1.b", "up.ng", "up.nb", "up2.w", "up2.b", "f.wq", "f.bq", "f.wo", "f.bo", "f.wimg",
+                        "f.bimg", "f.ktab", "f.ng", "f.nb"})
+    (void)W(k);
+  for (int i = 0; i < 2; ++i) {
+    const std::string L = "l" + std::to_string(i) + ".";
+    for (const char* k : {"wqk", "bqk", "wv", "bv", "wo", "bo", "t2i.wq", "t2i.bq", "t2i.wo", "t2i.bo", "t2i.wimg", "t2i.bimg", "t2i.ktab", "qtab", "w1", "b1",
+                          "w2", "b2", "wk2", "bk2", "wv2", "bv2", "wo2", "bo2", "n1g", "n1b", "n2g", "n2b", "n3g", "n3b", "n4g", "n4b"})
+      (void)W(L + k);
+  }
+  for (int j = 0; j < 3; ++j)
+    for (const char* k : {"hy", "iou"})
+      for (const char* t : {".w", ".b"}) (void)W(std::string(k) + std::to_string(j) + t);
+  if (missing) return refuse(op, VDR_ERR_INCOMPLETE, "internal: a finalized buffer is missing");
+  void *pe = ws + c.pe, *tok = ws + c.tok, *tmp = ws + c.tmp, *qkv = ws + c.qkv, *att = ws + c.att, *q = ws + c.q, *kv2 = ws + c.kv2, *h = ws + c.h;
+  void *keys = ws + c.keys, *keys2 = ws + c.keys2, *img = ws + c.img, *atti = ws + c.atti, *up = ws + c.up, *up2 = ws + c.up2;
+  auto bfp = [](void* p, int64_t off) { return (void*)((char*)p + 2 * off); };
+#define MD_L(expr, what) OP_TRY(expr, what)
+#define MD_R(call)                  \
+  do {                              \
+    if (int rc = (call)) return rc; \
+  } while (0)
+  // tokens (also the query pe) and keys
+  MD_L(launch_decoder_setup(boxes, Fp("fixed"), Fp("gauss"), Fp("corner"), emb, channels_last, Fp("no_mask"), pe, keys, batch, boxes_per_image, g,
+                            (float)d->cfg.img, s), "decoder_setup");
+  const void* cur = pe;  // the tokens of layer 0 are the initial ones
+  auto tl = [&](const void* x, int64_t ldx, const void* xadd, const std::string& w, const std::string& b, const void* resid, void* y, int f32out,
+                int64_t ldy, int M, int N, int K, int groups, int relu, int rpg = 0, int64_t gs = 0) {
+    return launch_token_linear(x, ldx, xadd, C, W(w), Fp(b), resid, C, y, f32out, ldy, M, N, K, groups, relu, s, rpg, gs);
+  };
+  // token -> image attention with its out-projection, residual and norm; leaves the new tokens in `tok`
+  auto t2i = [&](const std::string& L, int ncols, const std::string& ng, const std::string& nbeta, float eps) -> int {
+    MD_L(tl(cur, C, pe, L + "wq", L + "bq", nullptr, q, 0, MD_IN, T * P, MD_IN, C, 1, 0), "token_linear");
+    MD_R(md_gemm(keys, W(L + "wimg"), Fp(L + "bimg"), nullptr, img, (int64_t)P * n, ncols, C, s));
+    MD_L(launch_cross_attention(q, MD_IN, nullptr, img, ncols, Fp(L + "ktab"), bfp(img, MD_IN), ncols, att, MD_IN, P, T, n, 8, 16, s), "cross_attention");
+    MD_L(tl(att, MD_IN, nullptr, L + "wo", L + "bo", cur, tmp, 0, C, T * P, C, MD_IN, 1, 0), "token_linear");
+    MD_R(md_ln(tmp, tok, Fp(ng), Fp(nbeta), (int64_t)T * P, C, eps, s));
+    cur = tok;
+    return VDR_OK;
+  };
+  for (int i = 0; i < 2; ++i) {
+    const std::string L = "l" + std::to_string(i) + ".";
+    MD_L(tl(cur, C, i ? pe : nullptr, L + "wqk", L + "bqk", nullptr, qkv, 0, 3 * C, T * P, 2 * C, C, 1, 0), "token_linear");
+    MD_L(tl(cur, C, nullptr, L + "wv", L + "bv", nullptr, bfp(qkv, 2 * C), 0, 3 * C, T * P, C, C, 1, 0), "token_linear");
+    MD_L(launch_cross_attention(qkv, 3 * C, nullptr, bfp(qkv, C), 3 * C, nullptr, bfp(qkv, 2 * C), 3 * C, att, C, P, T, T, 8, 32, s), "cross_attention");
+    MD_L(tl(att, C, nullptr, L + "wo", L + "bo", i ? cur : nullptr, tmp, 0, C, T * P, C, C, 1, 0), "token_linear");
+    MD_R(md_ln(tmp, tok, Fp(L + "n1g"), Fp(L + "n1b"), (int64_t)T * P, C, d->cfg.ln_eps, s));
+    cur = tok;
+    MD_R(t2i(L + "t2i.", 3 * MD_IN, L + "n2g", L + "n2b", d->cfg.ln_eps));
+    MD_L(tl(tok, C, nullptr, L + "w1", L + "b1", nullptr, h, 0, F, T * P, F, C, 1, 1), "token_linear");
+    MD_L(tl(h, F, nullptr, L + "w2", L + "b2", tok, tmp, 0, C, T * P, C, F, 1, 0), "token_linear");
+    MD_R(md_ln(tmp, tok, Fp(L + "n3g"), Fp(L + "n3b"), (int64_t)T * P, C, d->cfg.ln_eps, s));
+    MD_L(tl(tok, C, pe, L + "wk2", L + "bk2", nullptr, kv2, 0, 2 * MD_IN, T * P, MD_IN, C, 1, 0), "token_linear");
+    MD_L(tl(tok, C, nullptr, L + "wv2", L + "bv2", nullptr, bfp(kv2, MD_IN), 0, 2 * MD_IN, T * P, MD_IN, C, 1, 0), "token_linear");
+    MD_L(launch_cross_attention(bfp(img, 2 * MD_IN), 3 * MD_IN, Fp(L + "qtab"), kv2, 2 * MD_IN, nullptr, bfp(kv2, MD_IN), 2 * MD_IN, atti, MD_IN, P, n, T,
+                                8, 16, s), "cross_attention");
+    MD_R(md_gemm(atti, W(L + "wo2"), Fp(L + "bo2"), keys, keys2, (int64_t)P * n, C, MD_IN, s));
+    MD_R(md_ln(keys2, keys, Fp(L + "n4g"), Fp(L + "n4b"), (int64_t)P * n, C, d->cfg.ln_eps, s));
+  }
+  MD_R(t2i("f.", 2 * MD_IN, "f.ng", "f.nb", d->cfg.final_ln_eps));
+  // upscaling: the first transposed convolution as a linear, LayerNorm2d over the 64 channels of each of its 4 sub-pixels
+  MD_R(md_gemm(keys, W("up1.w"), Fp("up1.b"), nullptr, up, (int64_t)P * n, C, C, s));
+  MD_R(md_ln(up, up2, Fp("up.ng"), Fp("up.nb"), (int64_t)P * n * 4, 64, d->cfg.ln2d_eps, s));
+  // the hypernetworks on the mask tokens (rows p * 7 + 1 + m of tok), the IoU head on the IoU token (row p * 7)
+  void *hx1 = ws + c.hx1, *hx2 = ws + c.hx2, *hyper = ws + c.hyper, *ix1 = ws + c.ix1, *ix2 = ws + c.ix2;
+  MD_L(tl(bfp(tok, C), C, nullptr, "hy0.w", "hy0.b", nullptr, hx1, 0, C, 4 * P, C, C, 4, 1, 4, (int64_t)T * C), "token_linear");
+  MD_L(tl(hx1, C, nullptr, "hy1.w", "hy1.b", nullptr, hx2, 0, C, 4 * P, C, C, 4, 1), "token_linear");
+  MD_L(tl(hx2, C, nullptr, "hy2.w", "hy2.b", nullptr, hyper, 1, 32, 4 * P, 32, C, 4, 0), "token_linear");
+  MD_L(tl(tok, (int64_t)T * C, nullptr, "iou0.w", "iou0.b", nullptr, ix1, 0, C, P, C, C, 1, 1), "token_linear");
+  MD_L(tl(ix1, C, nullptr, "iou1.w", "iou1.b", nullptr, ix2, 0, C, P, C, C, 1, 1), "token_linear");
+  MD_L(tl(ix2, C, nullptr, "iou2.w", "iou2.b", nullptr, iou, 1, 4, P, 4, C, 1, 0), "token_linear");
+  MD_L(launch_mask_upscale(up2, W("up2.w"), Fp("up2.b"), (const float*)hyper, logits, P, g, 1, s), "mask_upscale");
+#undef MD_L
+#undef MD_R
   return VDR_OK;
 }
 

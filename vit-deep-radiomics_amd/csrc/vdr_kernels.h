@@ -243,6 +243,17 @@ hipError_t launch_attention_probs(const void* qkv, void* out, int batch, int seq
 // one-query attention pooling (attention_pool.hip): out[b, h*dh + d] = sum_j softmax_j(q_h . k[b, j, h] dh^-1/2) v[b, j, h, d];
 // q fp32 [heads * head_dim] (one probe for the whole batch), kv bf16 rows b * n + j of ldkv elements, [k | v] columns,
 // out bf16 [batch, heads * head_dim].  head_dim 32 / 64 / 96 / 128, n >= 1, ldkv % 8 == 0, kv 16-byte aligned
+// csrc/mask_decoder.hip: the kernels of SAM's mask decoder (include/vdr.h)
+hipError_t launch_cross_attention(const void* q, int64_t ldq, const float* q_add, const void* k, int64_t ldk, const float* k_add,
+                                  const void* v, int64_t ldv, void* out, int64_t ldo, int problems, int tq, int tk, int heads,
+                                  int head_dim, hipStream_t s);
+hipError_t launch_token_linear(const void* x, int64_t ldx, const void* x_add, int64_t ldxa, const void* W, const float* bias,
+                               const void* resid, int64_t ldr, void* y, int out_f32, int64_t ldy, int M, int N, int K, int groups,
+                               int relu, hipStream_t s, int x_rpg = 0, int64_t x_gs = 0);
+hipError_t launch_decoder_setup(const float* boxes, const float* fixed, const float* gauss, const float* corner, const float* emb,
+                                int channels_last, const float* no_mask, void* tok, void* keys, int B, int nb, int g, float img, hipStream_t s);
+hipError_t launch_mask_upscale(const void* x, const void* W, const float* bias, const float* hyper, float* out, int problems,
+                               int g, int gelu_in, hipStream_t s);
 hipError_t launch_attention_pool(const float* q, const void* kv, int64_t ldkv, void* out, int batch, int n, int heads,
                                  int head_dim, hipStream_t s);
 

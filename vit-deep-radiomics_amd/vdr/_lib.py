@@ -37,6 +37,12 @@ class vdr_config_ext(C.Structure):
     _fields_ = [("size", C.c_int32), ("n_register", C.c_int32), ("rope", C.c_int32), ("rope_theta", C.c_float)]
 
 
+class vdr_mask_decoder_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("grid", "img", "channels", "heads", "depth", "mlp_dim", "attention_downsample_rate", "mask_tokens",
+                                          "upscale_channels_1", "upscale_channels_2", "iou_head_depth")] + \
+               [(n, C.c_float) for n in ("ln_eps", "final_ln_eps", "ln2d_eps")]
+
+
 class vdr_layer_out(C.Structure):
     _fields_ = [("layer", C.c_int32), ("out_mode", C.c_int32), ("out_dtype", C.c_int32), ("norm", C.c_int32),
                 ("ld", C.c_int64), ("out", C.c_void_p)]
@@ -110,6 +116,17 @@ SYMBOLS = {
     "vdr_op_attention_varlen": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
     "vdr_op_attention_probs": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vdr_op_attention_pool": (_I, [_P, _P, _L, _P, _I, _I, _I, _I, _P]),
+    "vdr_op_cross_attention": (_I, [_P, _L, _P, _P, _L, _P, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P]),
+    "vdr_op_token_linear": (_I, [_P, _L, _P, _L, _P, _P, _P, _L, _P, _I, _L, _I, _I, _I, _I, _I, _P]),
+    "vdr_op_mask_upscale": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "vdr_mask_decoder_create": (_I, [C.POINTER(vdr_mask_decoder_config), _I, C.POINTER(_P)]),
+    "vdr_mask_decoder_destroy": (None, [_P]),
+    "vdr_mask_decoder_num_weights": (_I, [_P]),
+    "vdr_mask_decoder_weight_name": (C.c_char_p, [_P, _I]),
+    "vdr_mask_decoder_set_weight": (_I, [_P, C.c_char_p, _P, C.POINTER(_L), _I]),
+    "vdr_mask_decoder_finalize": (_I, [_P]),
+    "vdr_mask_decoder_workspace_bytes": (_I, [_P, _I, C.POINTER(C.c_size_t)]),
+    "vdr_mask_decode": (_I, [_P, _P, _I, _P, _I, _I, _P, C.c_size_t, _P, _P, _P]),
     "vdr_op_attention_relpos": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "vdr_op_layernorm_window": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "vdr_op_layernorm_mx_window": (_I, [_P, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P]),

@@ -303,8 +303,11 @@ class VitDescriptorModel:
     """Frozen-ViT feature extractor with the attributes the reference's hot loop dispatches on."""
 
     def __init__(self, cfg: VdrConfig, weights: "dict[str, torch.Tensor]", model_name: str = "vit", device=None,
-                 dynamic_size: bool = False, sized: bool = False):
-        """sized=True (SAM encoders built at another side than the reference's 1024, load_model's img_size):
+                 dynamic_size: bool = False, sized: bool = False, decoder_weights=None, decoder_eps=None):
+        """decoder_weights (SAM models): the checkpoint's prompt_encoder.* / mask_decoder.* tensors under their segment_anything
+        names (vdr.weights.split_sam_decoder_weights) -- the handle then segments: segment / decode_masks (vdr/segment.py).
+        decoder_eps: the three LayerNorm eps of the decoder (vdr.segment.SA_EPS by default, HF_EPS for transformers' values).
+        sized=True (SAM encoders built at another side than the reference's 1024, load_model's img_size):
         get_dense_descriptor prepares a raw slice at cfg.img in one resize.  dynamic_size=True: every image method first adopts the size of the images it is given (x.shape[-2:]), as
         DINOv2 and transformers do with interpolate_pos_encoding; the position table is rebuilt only when the size
         changes.  False (default): other sizes are refused until set_input_size names one."""
@@ -326,6 +329,40 @@ class VitDescriptorModel:
             self.head = _ClipProjection(head, self.device)
         elif "head.probe" in head:
             self.head = _SiglipPoolHead(head, cfg, self.device)
+        self.mask_decoder = None
+        if decoder_weights is not None:
+            if cfg.window <= 0:
+                raise ValueError("decoder_weights: the mask decoder belongs to SAM / MedSAM models")
+            from .segment import SA_EPS, MaskDecoder
+            self.mask_decoder = MaskDecoder(decoder_weights, cfg.img // cfg.patch, cfg.img, self.device, **(decoder_eps or SA_EPS))
+
+    # -- box prompt -> mask (SAM / MedSAM with decoder weights; vdr/segment.py) ------------------
+    @property
+    def has_mask_decoder(self) -> bool:
+        return getattr(self, "mask_decoder", None) is not None
+
+    def decode_masks(self, emb: torch.Tensor, boxes, multimask: bool = False):
+        """The prompt encoder and mask decoder alone, on an embedding the caller holds: emb [B, 256, g, g] (what image_encoder
+        returns), boxes [B, nb, 4] (x0, y0, x1, y1) in pixels of the input image -> vdr.Segmentation."""
+        from . import segment as sg
+        sg._require(self, "decode_masks")
+        g = self.mask_decoder.g
+        if not isinstance(emb, torch.Tensor) or emb.dim() != 4 or tuple(emb.shape[1:]) != (256, g, g):
+            raise ValueError(f"decode_masks: emb must be [B, 256, {g}, {g}] (the model's grid), got "
+                             f"{tuple(emb.shape) if isinstance(emb, torch.Tensor) else type(emb).__name__}")
+        boxes = sg.check_boxes("decode_masks", boxes, emb.shape[0])
+        logits, iou = sg.select_masks(*self.mask_decoder.decode(emb.to(self.device), boxes), multimask)
+        return sg.Segmentation(logits, iou, (self.cfg.img, self.cfg.img))
+
+    def segment(self, x: torch.Tensor, boxes, multimask: bool = False):
+        """x [B, 3, S, S], boxes [B, nb, 4] (x0, y0, x1, y1) in pixels of x -> vdr.Segmentation: image_encoder followed by
+        decode_masks, bit for bit."""
+        from . import segment as sg
+        sg._require(self, "segment")
+        check_batch("segment", x)
+        boxes = sg.check_boxes("segment", boxes, x.shape[0])   # (before the encoder runs)
+        logits, iou = sg.select_masks(*self.mask_decoder.decode(self.image_encoder(x), boxes), multimask)
+        return sg.Segmentation(logits, iou, (self.cfg.img, self.cfg.img))
 
     # -- input size ------------------------------------------------------------------------------
     def set_input_size(self, height: int, width: int):
@@ -1092,7 +1129,7 @@ class _SiglipPoolHead:
 def load_model(model_name: str, model_path=None, weights=None, device=None, micro_batch: int = 0, streams: int = 0,
                fp8: int = 0, full_last_block: bool = False, ln_fold: bool = True, fp8_cls_bf16: bool = False,
                resid_fp32: bool = False, ln_fin_fused: bool = False, dynamic_size: bool = False, img_size=None,
-               stride=None):
+               stride=None, decoder_eps=None):
     """R1.  model_name: 'dinov2' | 'medsam' (reference names) or any key of ARCHS.
     model_path: a PyTorch state_dict file with the canonical key names; loaded with
     torch.load(weights_only=True).  weights: the same dict passed directly.  A transformers CLIPVisionModel
@@ -1114,6 +1151,10 @@ def load_model(model_name: str, model_path=None, weights=None, device=None, micr
     side -- and load the checkpoint's native tables into it: pos_embed [1, 64, 64, D] and the global blocks' rel_pos_h / w
     [127, 64] are resampled once on the device (bicubic / get_rel_pos's linear rule).  get_dense_descriptor and
     generate_features then prepare raw slices at that side.
+    A SAM / MedSAM checkpoint that also holds prompt_encoder.* / mask_decoder.* (segment_anything's spelling or
+    transformers.SamModel's) keeps them: model.has_mask_decoder, model.segment(x, boxes), model.decode_masks(emb, boxes)
+    (vdr/segment.py).  decoder_eps: the decoder's three LayerNorm eps (default vdr.segment.SA_EPS, segment_anything's values;
+    vdr.segment.HF_EPS is what transformers 5.15 applies).
     stride (default None = the patch side): run the patch convolution at this stride, a divisor of the patch side, for a
     finer dense grid (VitDescriptorModel.set_patch_stride); not for SAM / MedSAM and DINOv3 models."""
     if model_name not in ARCHS:
@@ -1132,6 +1173,13 @@ def load_model(model_name: str, model_path=None, weights=None, device=None, micr
         if model_path is None:
             raise ValueError("load_model needs model_path or weights (no network: nothing is downloaded)")
         weights = torch.load(model_path, map_location="cpu", weights_only=True)
+    decoder = None
+    if arch.window > 0:  # a whole SAM checkpoint: the box-prompt encoder and mask decoder come along (either key spelling)
+        from .weights import split_sam_decoder_weights
+        weights, decoder = split_sam_decoder_weights(weights)
+    if arch.window > 0 and any(k.startswith("vision_encoder.") for k in weights):  # transformers.SamModel's encoder spelling
+        from .weights import from_sam_hf_vision_state_dict
+        weights = from_sam_hf_vision_state_dict(weights)
     if model_name == "medsam" and any(k.startswith("image_encoder.") for k in weights):
         weights = from_sam_state_dict(weights)
     # transformers CLIPVisionModel[WithProjection] / SiglipVisionModel keys (with or without the vision_model. prefix)
@@ -1147,7 +1195,8 @@ def load_model(model_name: str, model_path=None, weights=None, device=None, micr
     elif "embeddings.patch_embeddings.projection.weight" in weights and any(".layer_scale1.lambda1" in k for k in weights):
         from .weights import from_dinov2_hf_state_dict
         weights = from_dinov2_hf_state_dict(weights)
-    model = VitDescriptorModel(cfg, weights, model_name, device, dynamic_size=dynamic_size, sized=img_size is not None)
+    model = VitDescriptorModel(cfg, weights, model_name, device, dynamic_size=dynamic_size, sized=img_size is not None,
+                               decoder_weights=decoder, decoder_eps=decoder_eps)
     model.model_name = model_name
     if stride is not None:
         model.set_patch_stride(stride)

@@ -256,6 +256,81 @@ def attention_probs(qkv: torch.Tensor, batch: int, seq: int, heads: int, head_di
     return out
 
 
+def _rows2d(t, name, cols=None):
+    if not (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2 and (t.shape[1] == 1 or t.stride(1) == 1)):
+        raise TypeError(f"{name} must be a 2-D bfloat16 tensor on the HIP device with contiguous columns")
+    if cols is not None and t.shape[1] != cols:
+        raise ValueError(f"{name} has {t.shape[1]} columns, expected {cols}")
+    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0))
+
+
+def cross_attention(q, k, v, problems: int, tq: int, tk: int, heads: int, head_dim: int, q_add=None, k_add=None, out=None):
+    """softmax(Q K^T / sqrt(head_dim)) v per (problem, head) with a handful of rows on one side (vdr_op_cross_attention): q
+    [problems*tq, heads*head_dim], k and v [problems*tk, heads*head_dim] bf16, each contiguous or a column slice of a wider
+    buffer (read in place); q_add [tq, heads*head_dim] / k_add [tk, heads*head_dim] fp32 tables added to every problem's q / k
+    rows in fp32.  head_dim 16 or 32; tq <= 16 or tk <= 16.  Returns bf16 [problems*tq, heads*head_dim]."""
+    lib = L.load()
+    HD = heads * head_dim
+    ldq, ldk, ldv = _rows2d(q, "q", HD), _rows2d(k, "k", HD), _rows2d(v, "v", HD)
+    if q.shape[0] != problems * tq or k.shape[0] != problems * tk or v.shape[0] != problems * tk:
+        raise ValueError("cross_attention: q must hold problems * tq rows, k and v problems * tk")
+    for t, rows, name in ((q_add, tq, "q_add"), (k_add, tk, "k_add")):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, HD)):
+            raise ValueError(f"cross_attention: {name} must be a contiguous float32 [{rows}, {HD}] tensor on the device")
+    if out is None:
+        out = torch.empty((problems * tq, HD), dtype=torch.bfloat16, device=q.device)
+    ldo = _rows2d(out, "out", HD)
+    L.check(lib.vdr_op_cross_attention(q.data_ptr(), ldq, _p(q_add), k.data_ptr(), ldk, _p(k_add), v.data_ptr(), ldv,
+                                       out.data_ptr(), ldo, problems, tq, tk, heads, head_dim, _s(q)))
+    return out
+
+
+def token_linear(x, W, bias=None, x_add=None, resid=None, relu=False, out=None, out_dtype=torch.bfloat16):
+    """The token-side linear of the mask decoder (vdr_op_token_linear): x [M, K] bf16 (rows may be strided), W [N, K] or
+    [groups, N, K] bf16 (row r uses group r % groups), bias fp32 [N] / [groups, N]; x_add: bf16(x + x_add) is the input;
+    resid bf16 [M, N] is added after the ReLU.  One fp32 fma chain over k.  Returns [M, N] bf16 or fp32 (or writes `out`,
+    which may be a column slice)."""
+    lib = L.load()
+    ldx = _rows2d(x, "x")
+    M, K = x.shape
+    if not (W.is_cuda and W.dtype == torch.bfloat16 and W.is_contiguous() and W.dim() in (2, 3) and W.shape[-1] == K):
+        raise ValueError("token_linear: W must be a contiguous bfloat16 [N, K] or [groups, N, K] tensor")
+    groups = W.shape[0] if W.dim() == 3 else 1
+    N = W.shape[-2]
+    if bias is not None and not (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == groups * N):
+        raise ValueError("token_linear: bias must be contiguous float32 [groups, N]")
+    ldxa = _rows2d(x_add, "x_add", K) if x_add is not None else 0
+    ldr = _rows2d(resid, "resid", N) if resid is not None else 0
+    if out is None:
+        out = torch.empty((M, N), dtype=out_dtype, device=x.device)
+    if not (out.dim() == 2 and tuple(out.shape) == (M, N) and out.dtype in (torch.float32, torch.bfloat16) and (N == 1 or out.stride(1) == 1)):
+        raise ValueError("token_linear: out must be [M, N] float32 or bfloat16 with contiguous columns")
+    ldy = out.stride(0) if M > 1 else max(N, out.stride(0))
+    L.check(lib.vdr_op_token_linear(x.data_ptr(), ldx, _p(x_add), ldxa, W.data_ptr(), _p(bias), _p(resid), ldr, out.data_ptr(),
+                                    L.VDR_BF16 if out.dtype == torch.bfloat16 else L.VDR_F32, ldy, M, N, K, groups, int(bool(relu)),
+                                    _s(x)))
+    return out
+
+
+def mask_upscale(x, W, bias, hyper, problems: int, g: int, gelu_in: bool = True, out=None):
+    """The fused tail of the mask decoder (vdr_op_mask_upscale): x [problems*g*g*4, 64] bf16 LayerNorm2d rows, W [128, 64] bf16
+    (row (dy*2+dx)*32 + c), bias fp32 [32], hyper fp32 [problems, 4, 32] -> low-resolution logits fp32 [problems, 4, 4g, 4g]."""
+    lib = L.load()
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and tuple(x.shape) == (problems * g * g * 4, 64)):
+        raise ValueError("mask_upscale: x must be a contiguous bfloat16 [problems*g*g*4, 64] tensor on the device")
+    if not (W.dtype == torch.bfloat16 and W.is_contiguous() and tuple(W.shape) == (128, 64)):
+        raise ValueError("mask_upscale: W must be contiguous bfloat16 [128, 64]")
+    if not (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == 32):
+        raise ValueError("mask_upscale: bias must be float32 [32]")
+    if not (hyper.dtype == torch.float32 and hyper.is_contiguous() and tuple(hyper.shape) == (problems, 4, 32)):
+        raise ValueError("mask_upscale: hyper must be contiguous float32 [problems, 4, 32]")
+    if out is None:
+        out = torch.empty((problems, 4, 4 * g, 4 * g), dtype=torch.float32, device=x.device)
+    L.check(lib.vdr_op_mask_upscale(x.data_ptr(), W.data_ptr(), bias.data_ptr(), hyper.data_ptr(), out.data_ptr(), problems, g,
+                                    int(bool(gelu_in)), _s(x)))
+    return out
+
+
 def log_bin(x: torch.Tensor, gh: int, gw: int, hierarchy: int = 2, out_dtype=torch.float32, out=None) -> torch.Tensor:
     """Log-binning of a dense descriptor map (vdr_op_log_bin): x [B, gh*gw, C] bf16 or fp32 -- contiguous, or a view whose
     last dimension is contiguous, such as the key columns and patch rows buf[:, P:, C:2*C] of a [B, P + n, 3C] qkv

@@ -186,6 +186,36 @@ def generate_features(model, img_3d, mask_3d, flip=None, max_batch=16, descripto
     return features_list, mask_list
 
 
+def segment_volume(model, img_3d, boxes, max_batch=16, threshold=0.0):
+    """The mask generate_features takes as mask_3d, from box prompts: img_3d (H, W, S) gray volume in [0, 1] (or (H, W, S, 3)),
+    boxes [S, 4] (x0, y0, x1, y1) in slice pixels, one per slice, or one box [4] for every slice -> (H, W, S) bool numpy.
+    The slices run in chunks of `max_batch` through prepare -> model.segment (mask token 0) -> bilinear logits at slice
+    resolution > threshold; one synchronisation per volume.  SAM / MedSAM models loaded with their decoder weights."""
+    from . import segment as sg
+    sg._require(model, "segment_volume")
+    vol = torch.as_tensor(img_3d)
+    if vol.dim() not in (3, 4) or (vol.dim() == 4 and vol.shape[3] != 3):
+        raise ValueError(f"segment_volume: img_3d must be (H, W, S) or (H, W, S, 3), got {tuple(vol.shape)}")
+    H, W, S = (int(v) for v in vol.shape[:3])
+    b = torch.as_tensor(boxes)
+    if tuple(b.shape) not in ((4,), (S, 4)):
+        raise ValueError(f"segment_volume: boxes must be [4] or [{S}, 4], got {tuple(b.shape)}")
+    sg.check_boxes("segment_volume", b.reshape(-1, 1, 4))
+    b = b.double().reshape(-1, 4).expand(S, 4)
+    side = model.cfg.img
+    scaled = b * torch.tensor([side / W, side / H, side / W, side / H], dtype=torch.float64)   # (segment.scale_box, per slice)
+    vol = vol.to(model.device)
+    if vol.dtype not in (torch.float32, torch.float64):
+        vol = vol.to(torch.float32)
+    out = torch.empty((S, H, W), dtype=torch.bool, device=model.device)
+    for s0 in range(0, S, max_batch):
+        s1 = min(S, s0 + max_batch)
+        x = prep.prepare_slices(vol[:, :, s0:s1], side=side, device=model.device)
+        seg = model.segment(x, scaled[s0:s1].reshape(s1 - s0, 1, 4))
+        out[s0:s1] = seg.masks(size=(H, W), threshold=threshold)[:, 0, 0]
+    return out.permute(1, 2, 0).cpu().numpy()
+
+
 # ---- tfds_dense_descriptor.py:142-165 -----------------------------------------------------------------------
 from .h5store import read_features, save_features  # noqa: E402,F401  (torch-free module: also runs where only h5py is)
 

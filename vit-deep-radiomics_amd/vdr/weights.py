@@ -283,3 +283,92 @@ def sam_tables_at(weights, grid: int, global_blocks) -> dict:
             k = f"blocks.{i}.attn.rel_pos_{ax}"
             out[k] = interpolate_rel_pos(weights[k], 2 * g - 1)
     return out
+
+
+# ---- SAM prompt encoder / mask decoder: the two spellings of one set of tensors -----------------------------------------
+# (segment_anything, transformers.SamModel); "{i}" is a transformer layer, "{m}" one of the 4 point embeddings / hypernetworks.
+# A name is spelled the same in both unless it matches a row here.  The hypernetwork and IoU-head MLPs are the one ambiguous
+# spot: `layers.0` is the FIRST linear for segment_anything and the MIDDLE one for transformers (proj_in, layers.0, proj_out).
+_SAM_DECODER_SPELLINGS = (
+    ("prompt_encoder.pe_layer.positional_encoding_gaussian_matrix", "shared_image_embedding.positional_embedding"),
+    ("prompt_encoder.point_embeddings.{m}.", "prompt_encoder.point_embed.{m}."),
+    ("prompt_encoder.mask_downscaling.0.", "prompt_encoder.mask_embed.conv1."),
+    ("prompt_encoder.mask_downscaling.1.", "prompt_encoder.mask_embed.layer_norm1."),
+    ("prompt_encoder.mask_downscaling.3.", "prompt_encoder.mask_embed.conv2."),
+    ("prompt_encoder.mask_downscaling.4.", "prompt_encoder.mask_embed.layer_norm2."),
+    ("prompt_encoder.mask_downscaling.6.", "prompt_encoder.mask_embed.conv3."),
+    ("mask_decoder.transformer.layers.{i}.norm1.", "mask_decoder.transformer.layers.{i}.layer_norm1."),
+    ("mask_decoder.transformer.layers.{i}.norm2.", "mask_decoder.transformer.layers.{i}.layer_norm2."),
+    ("mask_decoder.transformer.layers.{i}.norm3.", "mask_decoder.transformer.layers.{i}.layer_norm3."),
+    ("mask_decoder.transformer.layers.{i}.norm4.", "mask_decoder.transformer.layers.{i}.layer_norm4."),
+    ("mask_decoder.transformer.norm_final_attn.", "mask_decoder.transformer.layer_norm_final_attn."),
+    ("mask_decoder.output_upscaling.0.", "mask_decoder.upscale_conv1."),
+    ("mask_decoder.output_upscaling.1.", "mask_decoder.upscale_layer_norm."),
+    ("mask_decoder.output_upscaling.3.", "mask_decoder.upscale_conv2."),
+    ("mask_decoder.output_hypernetworks_mlps.{m}.layers.0.", "mask_decoder.output_hypernetworks_mlps.{m}.proj_in."),
+    ("mask_decoder.output_hypernetworks_mlps.{m}.layers.1.", "mask_decoder.output_hypernetworks_mlps.{m}.layers.0."),
+    ("mask_decoder.output_hypernetworks_mlps.{m}.layers.2.", "mask_decoder.output_hypernetworks_mlps.{m}.proj_out."),
+    ("mask_decoder.iou_prediction_head.layers.0.", "mask_decoder.iou_prediction_head.proj_in."),
+    ("mask_decoder.iou_prediction_head.layers.1.", "mask_decoder.iou_prediction_head.layers.0."),
+    ("mask_decoder.iou_prediction_head.layers.2.", "mask_decoder.iou_prediction_head.proj_out."),
+)
+SAM_DECODER_PREFIXES = ("prompt_encoder.", "mask_decoder.", "shared_image_embedding.")
+
+
+def sam_decoder_name(name: str, to: str) -> str:
+    """One prompt-encoder / mask-decoder tensor name in the other spelling: to="hf" takes a segment_anything name to
+    transformers.SamModel's, to="sa" the reverse.  Names the two libraries share come back unchanged."""
+    import re
+    if to not in ("hf", "sa"):
+        raise ValueError(f"to must be 'hf' or 'sa', got {to!r}")
+    for sa, hf in _SAM_DECODER_SPELLINGS:
+        src, dst = (sa, hf) if to == "hf" else (hf, sa)
+        pat = "^" + re.escape(src).replace(r"\{i\}", r"(?P<i>\d+)").replace(r"\{m\}", r"(?P<m>\d+)")
+        mt = re.match(pat, name)
+        if mt:
+            return dst.format(**mt.groupdict()) + name[mt.end():]
+    return name
+
+
+def split_sam_decoder_weights(sd):
+    """A SAM state dict in either spelling -> (everything else, the prompt-encoder / mask-decoder tensors under their
+    segment_anything names as fp32, or None when the checkpoint has none).  transformers' spelling is recognised by a name
+    only it uses (proj_in, upscale_conv1, shared_image_embedding)."""
+    dec = {k: v for k, v in sd.items() if k.startswith(SAM_DECODER_PREFIXES)}
+    if not dec:
+        return sd, None
+    rest = {k: v for k, v in sd.items() if k not in dec}
+    hf = any(".proj_in." in k or ".upscale_conv1." in k or k.startswith("shared_image_embedding.") for k in dec)
+    out = {}
+    for k, v in dec.items():
+        if hf and k == "prompt_encoder.shared_embedding.positional_embedding":
+            continue  # (tied to shared_image_embedding.positional_embedding)
+        out[sam_decoder_name(k, "sa") if hf else k] = torch.as_tensor(v).detach().to(torch.float32).contiguous()
+    return rest, out
+
+
+_SAM_HF_ENCODER = (("patch_embed.projection.", "patch_embed.proj."), (".layer_norm1.", ".norm1."), (".layer_norm2.", ".norm2."),
+                   (".mlp.lin1.", ".mlp.fc1."), (".mlp.lin2.", ".mlp.fc2."))
+_SAM_HF_NECK = {"neck.conv1.": "neck.0.", "neck.layer_norm1.": "neck.1.", "neck.conv2.": "neck.2.", "neck.layer_norm2.": "neck.3."}
+
+
+def from_sam_hf_vision_state_dict(sd):
+    """The vision_encoder.* tensors of a transformers.SamModel / SamVisionModel state dict -> the canonical encoder names
+    vdr_set_weight understands (layers.{i} -> blocks.{i}, layer_norm{1,2} -> norm{1,2}, mlp.lin{1,2} -> mlp.fc{1,2},
+    patch_embed.projection -> patch_embed.proj, neck.conv1 / layer_norm1 / conv2 / layer_norm2 -> neck.0 .. neck.3); every
+    other key is passed through."""
+    out = {}
+    for k, v in sd.items():
+        if not k.startswith("vision_encoder."):
+            out[k] = v
+            continue
+        k = k[len("vision_encoder."):]
+        if k.startswith("layers."):
+            k = "blocks." + k[len("layers."):]
+        for a, b in _SAM_HF_NECK.items():
+            if k.startswith(a):
+                k = b + k[len(a):]
+        for a, b in _SAM_HF_ENCODER:
+            k = k.replace(a, b)
+        out[k] = v
+    return out
