@@ -740,6 +740,83 @@ int vdr_mask_decoder_workspace_bytes(vdr_mask_decoder_handle d, int problems, si
 int vdr_mask_decode(vdr_mask_decoder_handle d, const float* emb, int channels_last, const float* boxes, int batch, int boxes_per_image,
                     void* workspace, size_t workspace_bytes, float* logits, float* iou, void* stream);
 
+/* ---- point and mask prompts (csrc/mask_prompt.hip).  Everything here is additive: the entry points above keep
+ * their behaviour, their bits and their launches.
+ *
+ * Optional prompt weights.  vdr_mask_decoder_set_weight also accepts, before finalize, the names the second enumeration
+ * (vdr_mask_decoder_num_prompt_weights / vdr_mask_decoder_prompt_weight_name) lists:
+ *   points  prompt_encoder.point_embeddings.{0,1}.weight [1, 256], prompt_encoder.not_a_point_embed.weight [1, 256]
+ *   mask    prompt_encoder.mask_downscaling.0.{weight [4,1,2,2], bias [4]}, .1.{weight, bias} [4], .3.{weight [16,4,2,2], bias [16]},
+ *           .4.{weight, bias} [16], .6.{weight [256,16,1,1], bias [256]}   (mask_in_chans = 16)
+ * finalize succeeds without them; a group given in part is VDR_ERR_INCOMPLETE naming the missing tensor.
+ * vdr_mask_decoder_prompt_support: VDR_PROMPT_POINTS | VDR_PROMPT_MASK of a finalized handle.  The mask-prompt weights stay fp32.
+ *
+ * vdr_mask_prompts: device pointers.  boxes [batch, nb, 4] or NULL; points [batch, nb, np, 2] (x, y) in input pixels or NULL, labels
+ * int32 [batch, nb, np], np = points_per_problem; mask_input fp32 [P, 4g, 4g], or [batch, 4g, 4g] with mask_per_image = 1 (shared by
+ * the image's nb problems: transformers' form), or NULL.  At least one of boxes / points (VDR_ERR_INVALID).
+ * Tokens per problem, segment_anything's layout: [iou; 4 mask tokens; np points; one padding point if boxes is NULL; the 2 box
+ * corners otherwise], T = 5 + np + (boxes ? 2 : 1) <= 16 (more: VDR_ERR_UNSUPPORTED).
+ * A point row: the Fourier features of ((x + 0.5) / img, (y + 0.5) / img), float64, as the box corners get them; label 1 / 0:
+ * float(pe + point_embeddings[label]); -1: not_a_point_embed alone; -10: a zero row (transformers' padding); any other value: float(pe)
+ * (transformers' behaviour; labels are not validated on the device).  The padding point is a label -1 row.  One rounding to bf16.
+ * Keys: with mask_input bf16(emb + dense) by vdr_op_mask_embed (eps = ln2d_eps), else bf16(emb + no_mask_embed) as vdr_mask_decode.
+ * vdr_mask_decode_prompts: vdr_mask_decode's contract -- 52 launches whatever the prompts, no host synchronisation, no allocation, no
+ * atomics, a problem's bits depend neither on P nor on its position; every refusal before the device is touched; a workspace
+ * below vdr_mask_decoder_workspace_bytes_prompts(P, T) is VDR_ERR_WORKSPACE with nothing written (equal to
+ * vdr_mask_decoder_workspace_bytes at T = 7).  Points (or no boxes: the padding point) / a mask on a handle without their weights:
+ * VDR_ERR_UNSUPPORTED.  With boxes only it gives vdr_mask_decode's bits.  The prompts themselves (none given, T > 16) are checked
+ * first of all.  The workspace begins with the tokens as set up, bf16 [P, T, 256] (they double as the query positional encoding and
+ * are not written again): the tests read the point rows there. */
+#define VDR_PROMPT_POINTS 1
+#define VDR_PROMPT_MASK 2
+typedef struct {
+  const float* boxes;
+  const float* points;
+  const int32_t* labels;
+  int32_t points_per_problem;
+  const float* mask_input;
+  int32_t mask_per_image;
+} vdr_mask_prompts;
+int vdr_mask_decoder_num_prompt_weights(vdr_mask_decoder_handle d);
+const char* vdr_mask_decoder_prompt_weight_name(vdr_mask_decoder_handle d, int i);
+int vdr_mask_decoder_prompt_support(vdr_mask_decoder_handle d);
+int vdr_mask_decoder_workspace_bytes_prompts(vdr_mask_decoder_handle d, int problems, int tokens, size_t* out);
+int vdr_mask_decode_prompts(vdr_mask_decoder_handle d, const float* emb, int channels_last, const vdr_mask_prompts* prompts, int batch,
+                            int boxes_per_image, void* workspace, size_t workspace_bytes, float* logits, float* iou, void* stream);
+
+/* The fused keys of a decode with a mask prompt: keys[p * n + cell, c] = bf16(emb[p / nb, c, cell] + dense[c]), dense never written.
+ *   emb      device fp32 [B, 256, g, g] (channels_last = 0) or [B, g, g, 256] (1); problem p reads image p / problems_per_image
+ *   mask     device fp32 [problems, 4g, 4g], or [B, 4g, 4g] with mask_per_image = 1 (problem p reads mask p / problems_per_image)
+ *   weights  device fp32 [VDR_MASK_EMBED_WEIGHTS]: mask_downscaling's 0.weight [4,1,2,2], 0.bias, 1.weight, 1.bias [4], 3.weight
+ *            [16,4,2,2], 3.bias, 4.weight, 4.bias [16], 6.weight [256,16], 6.bias [256], back to back
+ *   keys     device bf16 [problems * g * g, 256]
+ * Per cell (cy, cx), every operation fp32 and rounded once unless written fma (the file is compiled without contraction):
+ *   x[by,bx][dy,dx] = mask[4cy + 2by + dy, 4cx + 2bx + dx]
+ *   c1[ch]  = the fma chain from b1[ch] over k = 2dy + dx ascending: acc = fma(w1[ch][k], x[k], acc)          (per 2 x 2 block)
+ *   LayerNorm over the 4 channels, two-pass: mean = (((c0 + c1) + c2) + c3) / 4; d = c - mean; var = (d0 d0 + d1 d1 + ..) / 4 in
+ *           ascending order from 0; rstd = 1 / sqrt(var + eps) (IEEE); y = (d * rstd) * gamma + beta
+ *   a1      = gelu(y): the library's device polynomial (csrc/vdr_dev.h gelu_erf)
+ *   c2[co]  = the fma chain from b2[co] over k = 4 ci + 2 by + bx ascending: acc = fma(w2[co][k], a1[k], acc)
+ *   LayerNorm over the 16 channels (sum ascending from 0, / 16, as above), a2 = gelu(.)
+ *   dense[c] = the fma chain from b3[c] over k ascending: acc = fma(w3[c][k], a2[k], acc)
+ *   keys    = bf16(dense[c] + emb): one addition, one rounding.  So w3 = 0 gives bf16(emb + b3) exactly.
+ * Fixed order everywhere, no atomics: a problem's bits depend neither on `problems` nor on its position nor on the layout.
+ * g in [1, 64] (VDR_ERR_UNSUPPORTED); null or misaligned (16 bytes) pointers, problems outside 1 .. 65535 or no multiple of
+ * problems_per_image, eps <= 0: VDR_ERR_INVALID. */
+#define VDR_MASK_EMBED_WEIGHTS 4684
+int vdr_op_mask_embed(const float* emb, int channels_last, const float* mask, int mask_per_image, const float* weights, void* keys,
+                      int problems, int problems_per_image, int g, float eps, void* stream);
+
+/* The box of a logit map, for the next slice of a volume sweep: over the pixels with logit > threshold of plane p (H x W fp32 at
+ * logits + p * plane_stride elements: token 0 of [P, 4, H, W] is read in place with plane_stride = 4 H W),
+ *   x0 = minX * sx - margin, x1 = (maxX + 1) * sx + margin, sx = float(img) / float(W); y likewise with sy = float(img) / float(H);
+ *   each one fp32 multiplication and one addition, then clamped to [0, img].  boxes [P, 4] fp32 (x0, y0, x1, y1), area [P] int32 the
+ *   pixel count.  An empty mask returns prev[p] (fp32 [P, 4]) and area 0.  Integer reductions: exact, one workgroup per problem, one launch,
+ *   no atomics.  Refused: null pointers, non-positive sizes, problems > 65535, a plane_stride below H W, margin < 0 or NaN
+ *   (VDR_ERR_INVALID); H W > 2^31 - 1, img > 2^24 (VDR_ERR_UNSUPPORTED). */
+int vdr_op_mask_box(const float* logits, int64_t plane_stride, const float* prev, float* boxes, int32_t* area, int problems, int H, int W,
+                    int img, float margin, float threshold, void* stream);
+
 /* SAM / MedSAM Attention.forward with use_rel_pos (third-party segment_anything ImageEncoderViT, called at
  * tfds_dense_descriptor.py:123): per (window, head) softmax(q k^T dh^-0.5 + q.Rh[qh-kh] + q.Rw[qw-kw]) v.
  *   qkv   [batch*S*S, 3*H*64] bf16, `batch` windows (or whole grids) of S x S tokens, row-major (h, w)

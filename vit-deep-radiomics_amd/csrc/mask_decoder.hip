@@ -461,6 +461,15 @@ hipError_t launch_decoder_setup(const float* boxes, const float* fixed, const fl
   return hipGetLastError();
 }
 
+// the keys alone (decoder_keys_kernel): what a decode with prompts but without a mask prompt launches next to its own tokens kernel
+hipError_t launch_decoder_keys(const float* emb, int channels_last, const float* no_mask, void* keys, int B, int nb, int g, hipStream_t s) {
+  const int P = B * nb, n = g * g;
+  if (B <= 0 || nb <= 0 || g <= 0 || (int64_t)P * n * 256 > ((int64_t)1 << 40)) return hipErrorInvalidValue;
+  const int64_t total = (int64_t)P * n * 256;
+  hipLaunchKernelGGL(decoder_keys_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, emb, no_mask, (bf16_t*)keys, total, n, nb, channels_last);
+  return hipGetLastError();
+}
+
 hipError_t launch_cross_attention(const void* q, int64_t ldq, const float* q_add, const void* k, int64_t ldk, const float* k_add,
                                   const void* v, int64_t ldv, void* out, int64_t ldo, int problems, int tq, int tk, int heads,
                                   int head_dim, hipStream_t s) {

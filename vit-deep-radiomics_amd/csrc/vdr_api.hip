@@ -2751,6 +2751,36 @@ int vdr_op_mask_upscale(const void* x, const void* W, const float* bias, const f
   RUN_OP(launch_mask_upscale(x, W, bias, hyper, out, problems, g, gelu_in, (hipStream_t)stream), "mask_upscale");
 }
 
+// ---- the mask prompt ops (csrc/mask_prompt.hip) ----
+int vdr_op_mask_embed(const float* emb, int channels_last, const float* mask, int mask_per_image, const float* weights, void* keys,
+                      int problems, int problems_per_image, int g, float eps, void* stream) {
+  const char* op = "vdr_op_mask_embed";
+  if (!emb || !mask || !weights || !keys) return refuse(op, VDR_ERR_INVALID, "null pointer");
+  if ((channels_last != 0 && channels_last != 1) || (mask_per_image != 0 && mask_per_image != 1))
+    return refuse(op, VDR_ERR_INVALID, "channels_last and mask_per_image must be 0 or 1");
+  if (problems <= 0 || problems > 65535 || problems_per_image <= 0 || problems % problems_per_image)
+    return refuse(op, VDR_ERR_INVALID, "problems must be 1 .. 65535 and a multiple of problems_per_image");
+  if (g < 1 || g > 64) return refuse(op, VDR_ERR_UNSUPPORTED, "g must be in [1, 64]");
+  if (!(eps > 0.0f)) return refuse(op, VDR_ERR_INVALID, "eps must be positive");
+  if (!aligned16({emb, mask, weights, keys})) return refuse(op, VDR_ERR_INVALID, "pointers must be 16-byte aligned");
+  RUN_OP(launch_mask_embed(emb, channels_last, mask, mask_per_image, weights, weights + MASK_EMBED_SMALL, weights + MASK_EMBED_SMALL + 16 * 256,
+                           keys, problems, problems_per_image, g, eps, (hipStream_t)stream),
+         "mask_embed");
+}
+
+int vdr_op_mask_box(const float* logits, int64_t plane_stride, const float* prev, float* boxes, int32_t* area, int problems, int H, int W,
+                    int img, float margin, float threshold, void* stream) {
+  const char* op = "vdr_op_mask_box";
+  if (!logits || !prev || !boxes || !area) return refuse(op, VDR_ERR_INVALID, "null pointer");
+  if (problems <= 0 || problems > 65535 || H <= 0 || W <= 0 || img <= 0) return refuse(op, VDR_ERR_INVALID, "problems (at most 65535), H, W and img must be positive");
+  if ((int64_t)H * W > INT32_MAX) return refuse(op, VDR_ERR_UNSUPPORTED, "H * W exceeds 2^31 - 1");
+  if (img > (1 << 24)) return refuse(op, VDR_ERR_UNSUPPORTED, "img must be exact in fp32: at most 2^24");
+  if (plane_stride < (int64_t)H * W) return refuse(op, VDR_ERR_INVALID, "plane_stride is shorter than a plane");
+  if (!(margin >= 0.0f) || threshold != threshold) return refuse(op, VDR_ERR_INVALID, "margin must be >= 0, threshold a number");
+  if (((uintptr_t)logits & 3) || ((uintptr_t)area & 3) || !aligned16({prev, boxes})) return refuse(op, VDR_ERR_INVALID, "prev and boxes must be 16-byte aligned, the others to their element");
+  RUN_OP(launch_mask_box(logits, plane_stride, prev, boxes, area, problems, H, W, (float)img, margin, threshold, (hipStream_t)stream), "mask_box");
+}
+
 int vdr_op_attention_relpos(const void* qkv, const float* rel_pos_h, const float* rel_pos_w, float* rel, void* out,
                             int batch, int S, int heads, void* stream) {
   if (!qkv || !rel_pos_h || !rel_pos_w || !rel || !out) return fail(nullptr, VDR_ERR_INVALID, "null argument");
@@ -3268,6 +3298,9 @@ struct vdr_mask_decoder {
   vdr_mask_decoder_config cfg;
   std::vector<std::string> names;
   std::vector<std::vector<int64_t>> shapes;
+  std::vector<std::string> pnames;                  // the optional prompt weights: 3 of the point prompts, then 10 of the mask prompt
+  std::vector<std::vector<int64_t>> pshapes;
+  int support = 0;                                  // VDR_PROMPT_POINTS | VDR_PROMPT_MASK: what finalize found complete
   std::map<std::string, std::vector<float>> host;   // what vdr_mask_decoder_set_weight was given
   std::map<std::string, void*> dev;                 // what vdr_mask_decoder_finalize built (owned)
   bool finalized = false;
@@ -3279,7 +3312,7 @@ struct vdr_mask_decoder {
 namespace {
 
 using MD = vdr_mask_decoder;
-constexpr int MD_C = 256, MD_T = 7, MD_IN = 128;
+constexpr int MD_C = 256, MD_T = 7, MD_IN = 128, MD_MAX_T = 16, MD_POINT_WEIGHTS = 3;
 
 void md_names(MD* d) {
   auto add = [&](const std::string& n, std::vector<int64_t> shp) {
@@ -3337,6 +3370,25 @@ void md_names(MD* d) {
     add(p + ".weight", {j == 2 ? 4 : C, C});
     add(p + ".bias", {j == 2 ? 4 : C});
   }
+  // optional: the first MD_POINT_WEIGHTS are the point prompts' group, the rest the mask prompt's (mask_in_chans = 16)
+  auto padd = [&](const std::string& n, std::vector<int64_t> shp) {
+    d->pnames.push_back(n);
+    d->pshapes.push_back(std::move(shp));
+  };
+  padd("prompt_encoder.point_embeddings.0.weight", {1, C});
+  padd("prompt_encoder.point_embeddings.1.weight", {1, C});
+  padd("prompt_encoder.not_a_point_embed.weight", {1, C});
+  const std::string m = "prompt_encoder.mask_downscaling.";
+  padd(m + "0.weight", {4, 1, 2, 2});
+  padd(m + "0.bias", {4});
+  padd(m + "1.weight", {4});
+  padd(m + "1.bias", {4});
+  padd(m + "3.weight", {16, 4, 2, 2});
+  padd(m + "3.bias", {16});
+  padd(m + "4.weight", {16});
+  padd(m + "4.bias", {16});
+  padd(m + "6.weight", {C, 16, 1, 1});
+  padd(m + "6.bias", {C});
 }
 
 float md_bf16_round(float f) {
@@ -3350,8 +3402,8 @@ float md_bf16_round(float f) {
 struct MdCarve {
   size_t pe, tok, tmp, qkv, att, q, kv2, h, keys, keys2, img, atti, up, up2, hx1, hx2, hyper, ix1, ix2, total;
 };
-MdCarve md_carve(const MD* d, int64_t P) {
-  const int64_t n = (int64_t)d->cfg.grid * d->cfg.grid, T = MD_T * P;
+MdCarve md_carve(const MD* d, int64_t P, int tokens = MD_T) {
+  const int64_t n = (int64_t)d->cfg.grid * d->cfg.grid, T = tokens * P;
   MdCarve c{};
   size_t off = 0;
   auto take = [&](int64_t bytes) {
@@ -3473,6 +3525,15 @@ int vdr_mask_decoder_set_weight(vdr_mask_decoder_handle d, const char* name, con
       d->host[name].assign(host, host + want);
       return VDR_OK;
     }
+  for (size_t i = 0; i < d->pnames.size(); ++i)
+    if (d->pnames[i] == name) {
+      int64_t want = 1, got = 1;
+      for (int64_t v : d->pshapes[i]) want *= v;
+      for (int k = 0; k < ndim; ++k) got *= shape[k];
+      if (got != want) return refuse(op, VDR_ERR_INVALID, std::string(name) + ": element count mismatch");
+      d->host[name].assign(host, host + want);
+      return VDR_OK;
+    }
   return refuse(op, VDR_ERR_UNKNOWN_NAME, std::string("unknown weight ") + name);
 }
 
@@ -3482,6 +3543,18 @@ int vdr_mask_decoder_finalize(vdr_mask_decoder_handle d) {
   if (d->finalized) return VDR_OK;
   for (auto& n : d->names)
     if (!d->host.count(n)) return refuse(op, VDR_ERR_INCOMPLETE, "missing weight " + n);
+  // the optional groups: all of a group or none of it
+  int support = 0;
+  for (int grp = 0; grp < 2; ++grp) {
+    const size_t lo = grp ? MD_POINT_WEIGHTS : 0, hi = grp ? d->pnames.size() : MD_POINT_WEIGHTS;
+    size_t have = 0;
+    for (size_t i = lo; i < hi; ++i) have += d->host.count(d->pnames[i]);
+    if (have == hi - lo) support |= grp ? VDR_PROMPT_MASK : VDR_PROMPT_POINTS;
+    else if (have)
+      for (size_t i = lo; i < hi; ++i)
+        if (!d->host.count(d->pnames[i]))
+          return refuse(op, VDR_ERR_INCOMPLETE, std::string(grp ? "the mask prompt's" : "the point prompts'") + " weights are given in part: missing weight " + d->pnames[i]);
+  }
   auto& H = d->host;
   const int g = d->cfg.grid, n = g * g;
   // the Fourier features of the cell centres, float64: [n, 256]
@@ -3595,7 +3668,19 @@ int vdr_mask_decoder_finalize(vdr_mask_decoder_handle d) {
     MD_UP(md_up_bf(d, "iou" + std::to_string(j) + ".w", H[p + ".weight"]));
     MD_UP(md_up_f32(d, "iou" + std::to_string(j) + ".b", H[p + ".bias"]));
   }
+  if (support & VDR_PROMPT_POINTS) {
+    MD_UP(md_up_f32(d, "pt_emb", md_cat({&H["prompt_encoder.point_embeddings.0.weight"], &H["prompt_encoder.point_embeddings.1.weight"]})));
+    MD_UP(md_up_f32(d, "nap", H["prompt_encoder.not_a_point_embed.weight"]));
+  }
+  if (support & VDR_PROMPT_MASK) {  // fp32 on the device: 4.4 K values
+    const std::string m = "prompt_encoder.mask_downscaling.";
+    const std::vector<float> w = md_cat({&H[m + "0.weight"], &H[m + "0.bias"], &H[m + "1.weight"], &H[m + "1.bias"], &H[m + "3.weight"],
+                                         &H[m + "3.bias"], &H[m + "4.weight"], &H[m + "4.bias"], &H[m + "6.weight"], &H[m + "6.bias"]});
+    if ((int)w.size() != VDR_MASK_EMBED_WEIGHTS) return refuse(op, VDR_ERR_INCOMPLETE, "internal: the packed mask-prompt weights");
+    MD_UP(md_up_f32(d, "md.w", w));  // vdr_op_mask_embed's `weights`
+  }
 #undef MD_UP
+  d->support = support;
   d->host.clear();
   d->finalized = true;
   return VDR_OK;
@@ -3609,18 +3694,15 @@ int vdr_mask_decoder_workspace_bytes(vdr_mask_decoder_handle d, int problems, si
   return VDR_OK;
 }
 
-int vdr_mask_decode(vdr_mask_decoder_handle d, const float* emb, int channels_last, const float* boxes, int batch, int boxes_per_image,
-                    void* workspace, size_t workspace_bytes, float* logits, float* iou, void* stream) {
-  const char* op = "vdr_mask_decode";
-  if (!d || !emb || !boxes || !workspace || !logits || !iou) return refuse(op, VDR_ERR_INVALID, "null argument");
-  if (channels_last != 0 && channels_last != 1) return refuse(op, VDR_ERR_INVALID, "channels_last must be 0 or 1");
-  if (batch <= 0 || boxes_per_image <= 0 || (int64_t)batch * boxes_per_image > 65535)
-    return refuse(op, VDR_ERR_INVALID, "batch and boxes_per_image must be positive, at most 65535 problems");
-  if (!aligned16({emb, boxes, workspace, logits, iou})) return refuse(op, VDR_ERR_INVALID, "pointers must be 16-byte aligned");
-  if (!d->finalized) return refuse(op, VDR_ERR_INCOMPLETE, "vdr_mask_decoder_finalize has not run");
-  const int P = batch * boxes_per_image, g = d->cfg.grid, n = g * g, T = MD_T, C = MD_C, F = d->cfg.mlp_dim;
-  const MdCarve c = md_carve(d, P);
-  if (workspace_bytes < c.total) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(c.total) + " bytes needed");
+}  // extern "C"
+
+namespace {
+
+// the chain of launches both decode entry points run; pr == nullptr: vdr_mask_decode's own set-up (boxes, T = 7)
+int md_run(const char* op, MD* d, const float* emb, int channels_last, const float* boxes, const vdr_mask_prompts* pr, int T, int batch,
+           int boxes_per_image, void* workspace, float* logits, float* iou, void* stream) {
+  const int P = batch * boxes_per_image, g = d->cfg.grid, n = g * g, C = MD_C, F = d->cfg.mlp_dim;
+  const MdCarve c = md_carve(d, P, T);
   if (int rc = check_device(nullptr)) return rc;
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
@@ -3631,6 +3713,8 @@ int vdr_mask_decode(vdr_mask_decoder_handle d, const float* emb, int channels_la
     return it == d->dev.end() ? (const void*)nullptr : (const void*)it->second;
   };
   auto Fp = [&](const std::string& k) { return (const float*)W(k); };
+  if (pr && (pr->points || !pr->boxes)) (void)W("pt_emb"), (void)W("nap");
+  if (pr && pr->mask_input) (void)W("md.w");
   for (const char* k : {"fixed", "gauss", "corner", "no_mask", "up1.w", "up1.b", "up.ng", "up.nb", "up2.w", "up2.b", "f.wq", "f.bq", "f.wo", "f.bo", "f.wimg",
                         "f.bimg", "f.ktab", "f.ng", "f.nb"})
     (void)W(k);
@@ -3653,8 +3737,19 @@ int vdr_mask_decode(vdr_mask_decoder_handle d, const float* emb, int channels_la
     if (int rc = (call)) return rc; \
   } while (0)
   // tokens (also the query pe) and keys
-  MD_L(launch_decoder_setup(boxes, Fp("fixed"), Fp("gauss"), Fp("corner"), emb, channels_last, Fp("no_mask"), pe, keys, batch, boxes_per_image, g,
-                            (float)d->cfg.img, s), "decoder_setup");
+  if (!pr) {
+    MD_L(launch_decoder_setup(boxes, Fp("fixed"), Fp("gauss"), Fp("corner"), emb, channels_last, Fp("no_mask"), pe, keys, batch, boxes_per_image, g,
+                              (float)d->cfg.img, s), "decoder_setup");
+  } else {
+    const bool pts = pr->points || !pr->boxes;
+    MD_L(launch_prompt_tokens(pr->boxes, pr->points, pr->labels, pr->points ? pr->points_per_problem : 0, Fp("fixed"), Fp("gauss"), Fp("corner"),
+                              pts ? Fp("pt_emb") : nullptr, pts ? Fp("nap") : nullptr, pe, P, T, (float)d->cfg.img, s), "prompt_tokens");
+    if (pr->mask_input)
+      MD_L(launch_mask_embed(emb, channels_last, pr->mask_input, pr->mask_per_image, Fp("md.w"), Fp("md.w") + MASK_EMBED_SMALL, Fp("md.w") + MASK_EMBED_SMALL + 16 * MD_C, keys, P,
+                             boxes_per_image, g, d->cfg.ln2d_eps, s), "mask_embed");
+    else
+      MD_L(launch_decoder_keys(emb, channels_last, Fp("no_mask"), keys, batch, boxes_per_image, g, s), "decoder_keys");
+  }
   const void* cur = pe;  // the tokens of layer 0 are the initial ones
   auto tl = [&](const void* x, int64_t ldx, const void* xadd, const std::string& w, const std::string& b, const void* resid, void* y, int f32out,
                 int64_t ldy, int M, int N, int K, int groups, int relu, int rpg = 0, int64_t gs = 0) {
@@ -3705,6 +3800,78 @@ int vdr_mask_decode(vdr_mask_decoder_handle d, const float* emb, int channels_la
 #undef MD_L
 #undef MD_R
   return VDR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vdr_mask_decode(vdr_mask_decoder_handle d, const float* emb, int channels_last, const float* boxes, int batch, int boxes_per_image,
+                    void* workspace, size_t workspace_bytes, float* logits, float* iou, void* stream) {
+  const char* op = "vdr_mask_decode";
+  if (!d || !emb || !boxes || !workspace || !logits || !iou) return refuse(op, VDR_ERR_INVALID, "null argument");
+  if (channels_last != 0 && channels_last != 1) return refuse(op, VDR_ERR_INVALID, "channels_last must be 0 or 1");
+  if (batch <= 0 || boxes_per_image <= 0 || (int64_t)batch * boxes_per_image > 65535)
+    return refuse(op, VDR_ERR_INVALID, "batch and boxes_per_image must be positive, at most 65535 problems");
+  if (!aligned16({emb, boxes, workspace, logits, iou})) return refuse(op, VDR_ERR_INVALID, "pointers must be 16-byte aligned");
+  if (!d->finalized) return refuse(op, VDR_ERR_INCOMPLETE, "vdr_mask_decoder_finalize has not run");
+  const MdCarve c = md_carve(d, (int64_t)batch * boxes_per_image);
+  if (workspace_bytes < c.total) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(c.total) + " bytes needed");
+  return md_run(op, d, emb, channels_last, boxes, nullptr, MD_T, batch, boxes_per_image, workspace, logits, iou, stream);
+}
+
+int vdr_mask_decoder_num_prompt_weights(vdr_mask_decoder_handle d) { return d ? (int)d->pnames.size() : 0; }
+
+const char* vdr_mask_decoder_prompt_weight_name(vdr_mask_decoder_handle d, int i) {
+  return d && i >= 0 && i < (int)d->pnames.size() ? d->pnames[i].c_str() : nullptr;
+}
+
+int vdr_mask_decoder_prompt_support(vdr_mask_decoder_handle d) { return d && d->finalized ? d->support : 0; }
+
+// the prompts alone: what can be refused without a handle comes first (tests/test_sam_prompts_cpu.py has no device to make one with)
+static int md_check_prompts(const char* op, const vdr_mask_prompts* pr, int* tokens) {
+  if (!pr) return refuse(op, VDR_ERR_INVALID, "null prompts");
+  if (!pr->boxes && !pr->points) return refuse(op, VDR_ERR_INVALID, "at least one of boxes and points must be given");
+  if (pr->points && (!pr->labels || pr->points_per_problem <= 0))
+    return refuse(op, VDR_ERR_INVALID, "points need labels and a positive points_per_problem");
+  if (pr->mask_per_image != 0 && pr->mask_per_image != 1) return refuse(op, VDR_ERR_INVALID, "mask_per_image must be 0 or 1");
+  const int64_t T = 5 + (pr->points ? (int64_t)pr->points_per_problem : 0) + (pr->boxes ? 2 : 1);
+  if (T > MD_MAX_T)
+    return refuse(op, VDR_ERR_UNSUPPORTED, "at most " + std::to_string(MD_MAX_T) + " tokens per problem (5 + points + 2 with a box, + 1 without); got " + std::to_string(T));
+  *tokens = (int)T;
+  return VDR_OK;
+}
+
+int vdr_mask_decoder_workspace_bytes_prompts(vdr_mask_decoder_handle d, int problems, int tokens, size_t* out) {
+  const char* op = "vdr_mask_decoder_workspace_bytes_prompts";
+  if (!out) return refuse(op, VDR_ERR_INVALID, "null argument");
+  if (tokens < 6) return refuse(op, VDR_ERR_INVALID, "a decode has at least 6 tokens per problem");
+  if (tokens > MD_MAX_T) return refuse(op, VDR_ERR_UNSUPPORTED, "at most " + std::to_string(MD_MAX_T) + " tokens per problem");
+  if (!d) return refuse(op, VDR_ERR_INVALID, "null handle");
+  if (problems <= 0 || problems > 65535) return refuse(op, VDR_ERR_INVALID, "problems must be 1 .. 65535");
+  *out = md_carve(d, problems, tokens).total;
+  return VDR_OK;
+}
+
+int vdr_mask_decode_prompts(vdr_mask_decoder_handle d, const float* emb, int channels_last, const vdr_mask_prompts* prompts, int batch,
+                            int boxes_per_image, void* workspace, size_t workspace_bytes, float* logits, float* iou, void* stream) {
+  const char* op = "vdr_mask_decode_prompts";
+  int T = 0;
+  if (int rc = md_check_prompts(op, prompts, &T)) return rc;
+  if (!d || !emb || !workspace || !logits || !iou) return refuse(op, VDR_ERR_INVALID, "null argument");
+  if (channels_last != 0 && channels_last != 1) return refuse(op, VDR_ERR_INVALID, "channels_last must be 0 or 1");
+  if (batch <= 0 || boxes_per_image <= 0 || (int64_t)batch * boxes_per_image > 65535)
+    return refuse(op, VDR_ERR_INVALID, "batch and boxes_per_image must be positive, at most 65535 problems");
+  if (!aligned16({emb, prompts->boxes, prompts->points, prompts->labels, prompts->mask_input, workspace, logits, iou}))
+    return refuse(op, VDR_ERR_INVALID, "pointers must be 16-byte aligned");
+  if (!d->finalized) return refuse(op, VDR_ERR_INCOMPLETE, "vdr_mask_decoder_finalize has not run");
+  if ((prompts->points || !prompts->boxes) && !(d->support & VDR_PROMPT_POINTS))
+    return refuse(op, VDR_ERR_UNSUPPORTED, "point prompts (and the padding point of a decode without boxes) need point_embeddings.{0,1} and not_a_point_embed");
+  if (prompts->mask_input && !(d->support & VDR_PROMPT_MASK))
+    return refuse(op, VDR_ERR_UNSUPPORTED, "a mask prompt needs the mask_downscaling weights");
+  const MdCarve c = md_carve(d, (int64_t)batch * boxes_per_image, T);
+  if (workspace_bytes < c.total) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(c.total) + " bytes needed");
+  return md_run(op, d, emb, channels_last, nullptr, prompts, T, batch, boxes_per_image, workspace, logits, iou, stream);
 }
 
 }  // extern "C"

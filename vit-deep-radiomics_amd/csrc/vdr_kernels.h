@@ -254,6 +254,16 @@ hipError_t launch_decoder_setup(const float* boxes, const float* fixed, const fl
                                 int channels_last, const float* no_mask, void* tok, void* keys, int B, int nb, int g, float img, hipStream_t s);
 hipError_t launch_mask_upscale(const void* x, const void* W, const float* bias, const float* hyper, float* out, int problems,
                                int g, int gelu_in, hipStream_t s);
+hipError_t launch_decoder_keys(const float* emb, int channels_last, const float* no_mask, void* keys, int B, int nb, int g, hipStream_t s);
+// csrc/mask_prompt.hip: point / mask prompts and the box of a mask (include/vdr.h "mask prompt ops")
+constexpr int MASK_EMBED_SMALL = 332;  // the packed fp32 weights of mask_downscaling.{0,1,3,4}: w1 [4,4] b1 g1 e1 [4] w2 [16,16] b2 g2 e2 [16]
+hipError_t launch_mask_embed(const float* emb, int channels_last, const float* mask, int mask_per_image, const float* small,
+                             const float* w3, const float* b3, void* keys, int P, int nb, int g, float eps, hipStream_t s);
+hipError_t launch_prompt_tokens(const float* boxes, const float* points, const int32_t* labels, int np, const float* fixed,
+                                const float* gauss, const float* corner, const float* pt_emb, const float* nap, void* tok, int P,
+                                int T, float img, hipStream_t s);
+hipError_t launch_mask_box(const float* logits, int64_t plane_stride, const float* prev, float* boxes, int32_t* area, int P, int H,
+                           int W, float img, float margin, float threshold, hipStream_t s);
 hipError_t launch_attention_pool(const float* q, const void* kv, int64_t ldkv, void* out, int batch, int n, int heads,
                                  int head_dim, hipStream_t s);
 

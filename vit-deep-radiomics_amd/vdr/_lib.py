@@ -43,6 +43,15 @@ class vdr_mask_decoder_config(C.Structure):
                [(n, C.c_float) for n in ("ln_eps", "final_ln_eps", "ln2d_eps")]
 
 
+class vdr_mask_prompts(C.Structure):
+    _fields_ = [("boxes", C.c_void_p), ("points", C.c_void_p), ("labels", C.c_void_p), ("points_per_problem", C.c_int32),
+                ("mask_input", C.c_void_p), ("mask_per_image", C.c_int32)]
+
+
+PROMPT_POINTS, PROMPT_MASK = 1, 2
+MASK_EMBED_WEIGHTS = 4684
+
+
 class vdr_layer_out(C.Structure):
     _fields_ = [("layer", C.c_int32), ("out_mode", C.c_int32), ("out_dtype", C.c_int32), ("norm", C.c_int32),
                 ("ld", C.c_int64), ("out", C.c_void_p)]
@@ -127,6 +136,13 @@ SYMBOLS = {
     "vdr_mask_decoder_finalize": (_I, [_P]),
     "vdr_mask_decoder_workspace_bytes": (_I, [_P, _I, C.POINTER(C.c_size_t)]),
     "vdr_mask_decode": (_I, [_P, _P, _I, _P, _I, _I, _P, C.c_size_t, _P, _P, _P]),
+    "vdr_mask_decoder_num_prompt_weights": (_I, [_P]),
+    "vdr_mask_decoder_prompt_weight_name": (C.c_char_p, [_P, _I]),
+    "vdr_mask_decoder_prompt_support": (_I, [_P]),
+    "vdr_mask_decoder_workspace_bytes_prompts": (_I, [_P, _I, _I, C.POINTER(C.c_size_t)]),
+    "vdr_mask_decode_prompts": (_I, [_P, _P, _I, C.POINTER(vdr_mask_prompts), _I, _I, _P, C.c_size_t, _P, _P, _P]),
+    "vdr_op_mask_embed": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _F, _P]),
+    "vdr_op_mask_box": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P]),
     "vdr_op_attention_relpos": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "vdr_op_layernorm_window": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "vdr_op_layernorm_mx_window": (_I, [_P, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P]),

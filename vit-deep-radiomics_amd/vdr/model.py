@@ -336,33 +336,105 @@ class VitDescriptorModel:
             from .segment import SA_EPS, MaskDecoder
             self.mask_decoder = MaskDecoder(decoder_weights, cfg.img // cfg.patch, cfg.img, self.device, **(decoder_eps or SA_EPS))
 
-    # -- box prompt -> mask (SAM / MedSAM with decoder weights; vdr/segment.py) ------------------
+    # -- prompt -> mask (SAM / MedSAM with decoder weights; vdr/segment.py) ----------------------
     @property
     def has_mask_decoder(self) -> bool:
         return getattr(self, "mask_decoder", None) is not None
 
-    def decode_masks(self, emb: torch.Tensor, boxes, multimask: bool = False):
+    def decode_masks(self, emb: torch.Tensor, boxes=None, points=None, point_labels=None, mask_input=None, multimask: bool = False):
         """The prompt encoder and mask decoder alone, on an embedding the caller holds: emb [B, 256, g, g] (what image_encoder
-        returns), boxes [B, nb, 4] (x0, y0, x1, y1) in pixels of the input image -> vdr.Segmentation."""
+        returns), boxes [B, nb, 4] (x0, y0, x1, y1) and / or points [B, nb, np, 2] (x, y) with point_labels [B, nb, np] (1 foreground,
+        0 background, -1 not a point, -10 padding), all in pixels of the input image; mask_input [B, nb, 4g, 4g] (or one per image:
+        [B, 1, 4g, 4g] / [B, 4g, 4g]), a decode's own low-resolution logits (Segmentation.as_mask_input) -> vdr.Segmentation."""
         from . import segment as sg
         sg._require(self, "decode_masks")
         g = self.mask_decoder.g
         if not isinstance(emb, torch.Tensor) or emb.dim() != 4 or tuple(emb.shape[1:]) != (256, g, g):
             raise ValueError(f"decode_masks: emb must be [B, 256, {g}, {g}] (the model's grid), got "
                              f"{tuple(emb.shape) if isinstance(emb, torch.Tensor) else type(emb).__name__}")
-        boxes = sg.check_boxes("decode_masks", boxes, emb.shape[0])
-        logits, iou = sg.select_masks(*self.mask_decoder.decode(emb.to(self.device), boxes), multimask)
+        prompts = sg.check_prompts("decode_masks", boxes, points, point_labels, mask_input, emb.shape[0], g, self.mask_decoder)
+        logits, iou = sg.select_masks(*self.mask_decoder.decode(emb.to(self.device), *prompts), multimask)
         return sg.Segmentation(logits, iou, (self.cfg.img, self.cfg.img))
 
-    def segment(self, x: torch.Tensor, boxes, multimask: bool = False):
-        """x [B, 3, S, S], boxes [B, nb, 4] (x0, y0, x1, y1) in pixels of x -> vdr.Segmentation: image_encoder followed by
+    def segment(self, x: torch.Tensor, boxes=None, points=None, point_labels=None, mask_input=None, multimask: bool = False):
+        """x [B, 3, S, S] and the prompts of decode_masks, in pixels of x -> vdr.Segmentation: image_encoder followed by
         decode_masks, bit for bit."""
         from . import segment as sg
         sg._require(self, "segment")
         check_batch("segment", x)
-        boxes = sg.check_boxes("segment", boxes, x.shape[0])   # (before the encoder runs)
-        logits, iou = sg.select_masks(*self.mask_decoder.decode(self.image_encoder(x), boxes), multimask)
+        prompts = sg.check_prompts("segment", boxes, points, point_labels, mask_input, x.shape[0], self.mask_decoder.g, self.mask_decoder)   # (before the encoder runs)
+        logits, iou = sg.select_masks(*self.mask_decoder.decode(self.image_encoder(x), *prompts), multimask)
         return sg.Segmentation(logits, iou, (self.cfg.img, self.cfg.img))
+
+    def propagate_masks(self, x: torch.Tensor, box, index: int, direction: str = "both", margin: float = 8, use_mask_prompt: bool = True,
+                        multimask: bool = False, max_batch: int = 16):
+        """A mask for a whole volume from ONE annotated slice: x [Z, 3, S, S] prepared slices, box (x0, y0, x1, y1) on slice
+        `index` in pixels of x -> vdr.VolumeSegmentation.  Slice `index` is decoded from `box`; every further slice gets
+        vdr.ops.mask_box of its neighbour's single-mask (token 0) logits, grown by `margin` pixels, as its box and -- with
+        use_mask_prompt -- those logits as its mask prompt (False: box-only propagation, the MedSAM way; it needs no
+        mask-prompt weights).  An empty mask hands its own box on.  direction: "up" (index + 1 ..), "down" (index - 1 ..) or
+        "both": step k then decodes slices index + k and index - k as ONE two-problem call while both exist (a problem's bits
+        do not depend on the problem count).  multimask: the stored logits / iou are the highest-IoU of tokens 1..3 instead of
+        token 0; the sweep itself always hands token 0 on.  Embeddings come from image_encoder in chunks of max_batch; nothing
+        in the sweep synchronises with the host."""
+        from . import ops
+        from . import segment as sg
+        sg._require(self, "propagate_masks")
+        check_batch("propagate_masks", x)
+        Z = int(x.shape[0])
+        if isinstance(index, bool) or not isinstance(index, int) or not 0 <= index < Z:
+            raise ValueError(f"propagate_masks: index must be a slice number in [0, {Z}), got {index!r}")
+        if direction not in ("both", "up", "down"):
+            raise ValueError(f"propagate_masks: direction must be 'both', 'up' or 'down', got {direction!r}")
+        if not (isinstance(margin, (int, float)) and margin >= 0):
+            raise ValueError(f"propagate_masks: margin must be a number >= 0, got {margin!r}")
+        if isinstance(max_batch, bool) or not isinstance(max_batch, int) or max_batch < 1:
+            raise ValueError(f"propagate_masks: max_batch must be a positive integer, got {max_batch!r}")
+        b = torch.as_tensor(box)
+        if tuple(b.shape) != (4,):
+            raise ValueError(f"propagate_masks: box must be (x0, y0, x1, y1), got {tuple(b.shape)}")
+        sg.check_boxes("propagate_masks", b.reshape(1, 1, 4))
+        dec = self.mask_decoder
+        if use_mask_prompt and not dec.has_mask_prompt:
+            raise ValueError("propagate_masks: use_mask_prompt needs the checkpoint's prompt_encoder.mask_downscaling.* weights: weights absent "
+                             "(use_mask_prompt=False propagates the box alone)")
+        g, img, dev = dec.g, self.cfg.img, self.device
+        emb = torch.cat([self.image_encoder(x[s0:s0 + max_batch]) for s0 in range(0, Z, max_batch)], dim=0)
+        logits = torch.empty((Z, 4 * g, 4 * g), dtype=torch.float32, device=dev)
+        iou = torch.empty((Z,), dtype=torch.float32, device=dev)
+        boxes = torch.empty((Z, 4), dtype=torch.float32, device=dev)
+        area = torch.empty((Z,), dtype=torch.int32, device=dev)
+
+        def step(slices, bx, prev_logits):
+            """decode `slices` from boxes bx [k, 4] (and the neighbours' token-0 logits) -> (their token-0 logits, their next boxes)"""
+            k = len(slices)
+            e = emb[slices[0]:slices[0] + 1] if k == 1 else torch.stack([emb[z] for z in slices])
+            lg4, iou4 = dec.decode(e, bx.reshape(k, 1, 4), mask_input=prev_logits.reshape(k, 1, 4 * g, 4 * g) if prev_logits is not None else None)
+            lg4, iou4 = lg4[:, 0], iou4[:, 0]                                     # [k, 4, 4g, 4g], [k, 4]
+            nxt, ar = ops.mask_box(lg4[:, 0], bx, img, margin=margin, threshold=0.0)
+            if multimask:
+                j = iou4[:, 1:].argmax(dim=1, keepdim=True)                       # (a device gather: no synchronisation)
+                keep = torch.gather(lg4[:, 1:], 1, j[:, :, None, None].expand(-1, 1, 4 * g, 4 * g))[:, 0]
+                kiou = torch.gather(iou4[:, 1:], 1, j)[:, 0]
+            else:
+                keep, kiou = lg4[:, 0], iou4[:, 0]
+            for i, z in enumerate(slices):
+                logits[z], iou[z], boxes[z], area[z] = keep[i], kiou[i], bx[i], ar[i]
+            return lg4[:, 0], nxt
+
+        seed = b.to(dev, torch.float32).reshape(1, 4)
+        lg0, nx0 = step([index], seed, None)
+        state = {"up": (lg0[0], nx0[0]), "down": (lg0[0], nx0[0])}
+        for k in range(1, Z):
+            todo = [(d, z) for d, z in (("up", index + k), ("down", index - k)) if direction in ("both", d) and 0 <= z < Z]
+            if not todo:
+                break
+            bx = torch.stack([state[d][1] for d, _ in todo])
+            prev = torch.stack([state[d][0] for d, _ in todo]) if use_mask_prompt else None
+            lg, nxt = step([z for _, z in todo], bx, prev)
+            for i, (d, _) in enumerate(todo):
+                state[d] = (lg[i], nxt[i])
+        return sg.VolumeSegmentation(logits, iou, boxes, area, (img, img))
 
     # -- input size ------------------------------------------------------------------------------
     def set_input_size(self, height: int, width: int):

@@ -331,6 +331,57 @@ def mask_upscale(x, W, bias, hyper, problems: int, g: int, gelu_in: bool = True,
     return out
 
 
+def mask_embed(emb, mask, weights, problems_per_image: int = 1, eps: float = 1e-6, out=None):
+    """The fused keys of a decode with a mask prompt (vdr_op_mask_embed): emb fp32 [B, 256, g, g] (a channel-first view of a
+    [B, g, g, 256] tensor is read in place), mask fp32 [B * problems_per_image, 4g, 4g], or [B, 4g, 4g] shared by the image's
+    problems; weights fp32 [4684], mask_downscaling's ten tensors back to back (0.weight, 0.bias, 1.weight, 1.bias, 3.weight,
+    3.bias, 4.weight, 4.bias, 6.weight, 6.bias) -> keys bf16 [B * problems_per_image * g * g, 256] = bf16(emb + dense)."""
+    lib = L.load()
+    if not (emb.is_cuda and emb.dtype == torch.float32 and emb.dim() == 4 and emb.shape[1] == 256 and emb.shape[2] == emb.shape[3]):
+        raise ValueError("mask_embed: emb must be a float32 [B, 256, g, g] tensor on the device")
+    B, g, nb = int(emb.shape[0]), int(emb.shape[2]), int(problems_per_image)
+    if emb.permute(0, 2, 3, 1).is_contiguous():
+        channels_last = 1
+    else:
+        emb, channels_last = emb.contiguous(), 0
+    P = B * nb
+    if not (mask.is_cuda and mask.dtype == torch.float32 and mask.is_contiguous() and mask.dim() == 3 and tuple(mask.shape[1:]) == (4 * g, 4 * g)
+            and mask.shape[0] in (P, B)):
+        raise ValueError(f"mask_embed: mask must be a contiguous float32 [{P} or {B}, {4 * g}, {4 * g}] tensor on the device")
+    per_image = int(mask.shape[0] != P)
+    if not (weights.is_cuda and weights.dtype == torch.float32 and weights.is_contiguous() and weights.numel() == L.MASK_EMBED_WEIGHTS):
+        raise ValueError(f"mask_embed: weights must be a contiguous float32 tensor of {L.MASK_EMBED_WEIGHTS} values on the device")
+    if out is None:
+        out = torch.empty((P * g * g, 256), dtype=torch.bfloat16, device=emb.device)
+    if not (out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and out.numel() == P * g * g * 256):
+        raise ValueError("mask_embed: out must be a contiguous bfloat16 [P * g * g, 256] tensor")
+    L.check(lib.vdr_op_mask_embed(emb.data_ptr(), channels_last, mask.data_ptr(), per_image, weights.data_ptr(), out.data_ptr(), P, nb, g,
+                                  float(eps), _s(emb)))
+    return out
+
+
+def mask_box(logits, prev, img: int, margin: float = 0.0, threshold: float = 0.0):
+    """The box of each logit map (vdr_op_mask_box): logits fp32 [P, H, W] -- contiguous planes, the planes themselves may be
+    strided, as token 0 of a [P, 4, H, W] tensor -- and prev fp32 [P, 4] -> (boxes fp32 [P, 4] (x0, y0, x1, y1) in pixels of the
+    img x img input, grown by `margin` and clamped to [0, img]; area int32 [P]).  An empty mask returns prev's box and area 0."""
+    lib = L.load()
+    if not (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 3):
+        raise ValueError("mask_box: logits must be a float32 [P, H, W] tensor on the device")
+    P, H, W = (int(v) for v in logits.shape)
+    if not ((W == 1 or logits.stride(2) == 1) and (H == 1 or logits.stride(1) == W)):
+        logits = logits.contiguous()
+    stride = logits.stride(0) if P > 1 else H * W
+    if stride < H * W:
+        logits, stride = logits.contiguous(), H * W
+    if not (prev.is_cuda and prev.dtype == torch.float32 and prev.is_contiguous() and tuple(prev.shape) == (P, 4)):
+        raise ValueError(f"mask_box: prev must be a contiguous float32 [{P}, 4] tensor on the device")
+    boxes = torch.empty((P, 4), dtype=torch.float32, device=logits.device)
+    area = torch.empty((P,), dtype=torch.int32, device=logits.device)
+    L.check(lib.vdr_op_mask_box(logits.data_ptr(), stride, prev.data_ptr(), boxes.data_ptr(), area.data_ptr(), P, H, W, int(img), float(margin),
+                                float(threshold), _s(logits)))
+    return boxes, area
+
+
 def log_bin(x: torch.Tensor, gh: int, gw: int, hierarchy: int = 2, out_dtype=torch.float32, out=None) -> torch.Tensor:
     """Log-binning of a dense descriptor map (vdr_op_log_bin): x [B, gh*gw, C] bf16 or fp32 -- contiguous, or a view whose
     last dimension is contiguous, such as the key columns and patch rows buf[:, P:, C:2*C] of a [B, P + n, 3C] qkv

@@ -216,6 +216,33 @@ def segment_volume(model, img_3d, boxes, max_batch=16, threshold=0.0):
     return out.permute(1, 2, 0).cpu().numpy()
 
 
+def propagate_segmentation(model, img_3d, box, index, direction="both", margin=8, use_mask_prompt=True, max_batch=16, threshold=0.0):
+    """segment_volume from ONE annotation: img_3d (H, W, S) gray volume in [0, 1] (or (H, W, S, 3)), box (x0, y0, x1, y1) in
+    slice pixels on slice `index` -> (H, W, S) bool numpy, the array generate_features takes as mask_3d.  The slices are
+    prepared in chunks of max_batch, model.propagate_masks carries the mask through the volume (margin in pixels of the
+    prepared input), the logits are resampled to slice resolution; one synchronisation per volume."""
+    from . import segment as sg
+    sg._require(model, "propagate_segmentation")
+    vol = torch.as_tensor(img_3d)
+    if vol.dim() not in (3, 4) or (vol.dim() == 4 and vol.shape[3] != 3):
+        raise ValueError(f"propagate_segmentation: img_3d must be (H, W, S) or (H, W, S, 3), got {tuple(vol.shape)}")
+    H, W, S = (int(v) for v in vol.shape[:3])
+    b = torch.as_tensor(box)
+    if tuple(b.shape) != (4,):
+        raise ValueError(f"propagate_segmentation: box must be (x0, y0, x1, y1), got {tuple(b.shape)}")
+    sg.check_boxes("propagate_segmentation", b.reshape(1, 1, 4))
+    if isinstance(index, bool) or not isinstance(index, int) or not 0 <= index < S:
+        raise ValueError(f"propagate_segmentation: index must be a slice number in [0, {S}), got {index!r}")
+    side = model.cfg.img
+    scaled = torch.tensor(sg.scale_box(b.tolist(), H, W, side), dtype=torch.float64)
+    vol = vol.to(model.device)
+    if vol.dtype not in (torch.float32, torch.float64):
+        vol = vol.to(torch.float32)
+    x = torch.cat([prep.prepare_slices(vol[:, :, s0:s0 + max_batch], side=side, device=model.device) for s0 in range(0, S, max_batch)], dim=0)
+    seg = model.propagate_masks(x, scaled, index, direction=direction, margin=margin, use_mask_prompt=use_mask_prompt, max_batch=max_batch)
+    return seg.masks(size=(H, W), threshold=threshold).permute(1, 2, 0).cpu().numpy()
+
+
 # ---- tfds_dense_descriptor.py:142-165 -----------------------------------------------------------------------
 from .h5store import read_features, save_features  # noqa: E402,F401  (torch-free module: also runs where only h5py is)
 

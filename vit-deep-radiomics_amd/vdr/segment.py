@@ -1,5 +1,5 @@
-"""Box prompt in, mask out: SAM's prompt encoder (boxes only) and mask decoder on the neck output of the library's SAM /
-MedSAM encoder (segment_anything's PromptEncoder + MaskDecoder; parity pinned against transformers.SamModel).
+"""Prompt in, mask out: SAM's prompt encoder (boxes, points, a dense mask prompt) and mask decoder on the neck output of the
+library's SAM / MedSAM encoder (segment_anything's PromptEncoder + MaskDecoder; parity pinned against transformers.SamModel).
 
 A "problem" is one (image, box) pair; P = B * nb, n = g * g cells.  The decode is ONE call of the library's decoder object
 (vdr_mask_decode, include/vdr.h): a fixed chain of launches on the caller's stream -- the same number for every B and nb
@@ -9,7 +9,13 @@ image-side linears and LayerNorm, in a workspace the caller owns.  Per block the
 pe W^T + b of k and q are fp32 tables of n rows, computed once per decoder in float64 and added inside the attention kernel's
 loads.
 
-Out of scope: point and mask prompts, the automatic mask generator, the not_a_point padding path, fp8."""
+Points and the mask prompt go through vdr_mask_decode_prompts (the same 52 launches): tokens [iou; 4 mask tokens; np points;
+one padding point if there is no box; 2 box corners if there is one], at most 16 per problem; with a mask prompt the keys
+are bf16(emb + mask_downscaling(mask)) from ONE fused kernel (vdr_op_mask_embed).  propagate_masks (vdr/model.py) carries a
+mask through a volume from one annotated slice: each slice's box is vdr_op_mask_box of its neighbour's logits.
+
+Out of scope: the automatic mask generator, per-problem point counts other than by label -1 padding, fp8.  MedSAM fine-tuned
+the decoder with box prompts only: its point / mask-prompt weights are SAM's, nothing is claimed about their masks."""
 from __future__ import annotations
 
 import math
@@ -38,6 +44,99 @@ class Segmentation:
 
     def masks(self, size=None, threshold: float = 0.0) -> torch.Tensor:
         return self.logits(size) > threshold
+
+    def best(self) -> "Segmentation":
+        """the highest-IoU mask of every problem (M = 1): a device gather, no synchronisation; ties go to the lowest index"""
+        idx = self.iou.argmax(dim=2, keepdim=True)                                  # [B, nb, 1]
+        lg = torch.gather(self.low_res_logits, 2, idx[..., None, None].expand(-1, -1, 1, *self.low_res_logits.shape[3:]))
+        return Segmentation(lg, torch.gather(self.iou, 2, idx), self.input_size)
+
+    def as_mask_input(self, select="best") -> torch.Tensor:
+        """[B, nb, 4g, 4g] fp32: one mask's low-resolution logits per problem, to feed back as `mask_input` (SAM's refinement
+        loop).  select: "best" (highest predicted IoU) or the index of a mask."""
+        if select == "best":
+            return self.best().low_res_logits[:, :, 0]
+        if isinstance(select, bool) or not isinstance(select, int) or not 0 <= select < self.low_res_logits.shape[2]:
+            raise ValueError(f"as_mask_input: select must be 'best' or an index below {self.low_res_logits.shape[2]}, got {select!r}")
+        return self.low_res_logits[:, :, select]
+
+
+class VolumeSegmentation:
+    """What propagate_masks returns: low_res_logits [Z, 4g, 4g] fp32, iou [Z], boxes [Z, 4] fp32 (the box each slice was decoded
+    with, in pixels of the prepared input), area [Z] int32 (pixels of the slice's low-resolution mask), all on the device."""
+
+    def __init__(self, low_res_logits, iou, boxes, area, input_size):
+        self.low_res_logits, self.iou, self.boxes, self.area = low_res_logits, iou, boxes, area
+        self.input_size = tuple(int(v) for v in input_size)
+
+    def logits(self, size=None) -> torch.Tensor:
+        size = self.input_size if size is None else tuple(int(v) for v in size)
+        return torch.nn.functional.interpolate(self.low_res_logits[:, None], size=size, mode="bilinear", align_corners=False)[:, 0]
+
+    def masks(self, size=None, threshold: float = 0.0) -> torch.Tensor:
+        """[Z, h, w] bool at the input size or `size`"""
+        return self.logits(size) > threshold
+
+
+MAX_TOKENS = 16                     # per problem (include/vdr.h): 5 + points + (2 with a box, 1 without)
+POINT_LABELS = (1, 0, -1, -10)      # foreground, background, not a point, transformers' padding
+
+
+def _real(what, name, t):
+    if isinstance(t, np.ndarray):
+        t = torch.from_numpy(t)
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{what}: {name} must be a tensor or array, got {type(t).__name__}")
+    if t.dtype == torch.bool or t.is_complex():
+        raise ValueError(f"{what}: {name} must hold real numbers, got {t.dtype}")
+    return t
+
+
+def check_prompts(what: str, boxes, points, labels, mask_input, batch, g=None, decoder=None):
+    """Every prompt of one decode, before any device work -> (boxes, points, labels, mask_input) as tensors or None.  points
+    [B, nb, np, 2] (x, y) with labels [B, nb, np]; mask_input [B, nb, 4g, 4g] or [B, 1, 4g, 4g] / [B, 4g, 4g] (one per image)."""
+    if boxes is None and points is None:
+        raise ValueError(f"{what}: no prompt: give boxes, points or both")
+    if boxes is not None:
+        boxes = check_boxes(what, boxes, batch)
+    nb = None if boxes is None else int(boxes.shape[1])
+    if (points is None) != (labels is None):
+        raise ValueError(f"{what}: points and point_labels go together")
+    if points is not None:
+        points, labels = _real(what, "points", points), _real(what, "point_labels", labels)
+        if points.dim() != 4 or points.shape[-1] != 2 or points.shape[1] < 1 or points.shape[2] < 1:
+            raise ValueError(f"{what}: points must be [B, nb, np, 2] (x, y), got {tuple(points.shape)}")
+        if tuple(labels.shape) != tuple(points.shape[:3]):
+            raise ValueError(f"{what}: point_labels must be {tuple(points.shape[:3])}, got {tuple(labels.shape)}")
+        if labels.is_floating_point():
+            raise ValueError(f"{what}: point_labels must be integers, got {labels.dtype}")
+        if batch is not None and points.shape[0] != batch:
+            raise ValueError(f"{what}: {points.shape[0]} point sets for {batch} images")
+        if nb is not None and points.shape[1] != nb:
+            raise ValueError(f"{what}: nb mismatch: {nb} boxes per image, {points.shape[1]} point sets per image")
+        nb = int(points.shape[1])
+        T = 5 + int(points.shape[2]) + (2 if boxes is not None else 1)
+        if T > MAX_TOKENS:
+            raise ValueError(f"{what}: {T} tokens per problem (5 + {points.shape[2]} points + {2 if boxes is not None else 1}); at most {MAX_TOKENS}")
+        if not labels.is_cuda and not bool(torch.isin(labels, torch.tensor(POINT_LABELS, dtype=labels.dtype)).all()):
+            raise ValueError(f"{what}: point_labels must be 1 (foreground), 0 (background), -1 (not a point) or -10 (padding)")
+    if decoder is not None and (points is not None or boxes is None) and not decoder.has_point_prompts:
+        raise ValueError(f"{what}: the checkpoint has no point-prompt weights (point_embeddings.0/1, not_a_point_embed): weights absent")
+    if mask_input is not None:
+        mask_input = _real(what, "mask_input", mask_input)
+        B = int(points.shape[0] if boxes is None else boxes.shape[0])
+        ok = mask_input.is_floating_point() and mask_input.dim() in (3, 4) and mask_input.shape[0] == B
+        if ok and g is not None:
+            ok = tuple(mask_input.shape[-2:]) == (4 * g, 4 * g)
+        if ok and mask_input.dim() == 4:
+            ok = mask_input.shape[1] in (1, nb)
+        if not ok:
+            side = "4g" if g is None else str(4 * g)
+            raise ValueError(f"{what}: wrong mask shape: mask_input must be floating [{B}, {nb}, {side}, {side}], or [{B}, 1, {side}, {side}] / "
+                             f"[{B}, {side}, {side}] (one per image), got {tuple(mask_input.shape)} {mask_input.dtype}")
+        if decoder is not None and not decoder.has_mask_prompt:
+            raise ValueError(f"{what}: the checkpoint has no mask-prompt weights (prompt_encoder.mask_downscaling.*): weights absent")
+    return boxes, points, labels, mask_input
 
 
 def check_boxes(what: str, boxes, batch=None) -> torch.Tensor:
@@ -91,38 +190,73 @@ class MaskDecoder:
             t = torch.as_tensor(weights[name]).detach().to(torch.float32).contiguous().cpu()
             shape = (C.c_int64 * t.dim())(*t.shape)
             L.check(self.lib.vdr_mask_decoder_set_weight(h, name.encode(), t.data_ptr(), shape, t.dim()))
+        # the optional prompt weights: a group is set when the checkpoint holds all of it
+        opt = [self.lib.vdr_mask_decoder_prompt_weight_name(h, i).decode() for i in range(self.lib.vdr_mask_decoder_num_prompt_weights(h))]
+        for group in (opt[:3], opt[3:]):
+            if all(n in weights for n in group):
+                for name in group:
+                    t = torch.as_tensor(weights[name]).detach().to(torch.float32).contiguous().cpu()
+                    shape = (C.c_int64 * t.dim())(*t.shape)
+                    L.check(self.lib.vdr_mask_decoder_set_weight(h, name.encode(), t.data_ptr(), shape, t.dim()))
         L.check(self.lib.vdr_mask_decoder_finalize(h))
+        support = self.lib.vdr_mask_decoder_prompt_support(h)
+        self.has_point_prompts, self.has_mask_prompt = bool(support & L.PROMPT_POINTS), bool(support & L.PROMPT_MASK)
 
     def __del__(self):
         h, self.h = getattr(self, "h", None), None
         if h:
             self.lib.vdr_mask_decoder_destroy(h)
 
-    def workspace_bytes(self, problems: int) -> int:
+    def workspace_bytes(self, problems: int, tokens: int = 7) -> int:
         import ctypes as C
         n = C.c_size_t()
-        L.check(self.lib.vdr_mask_decoder_workspace_bytes(self.h, int(problems), C.byref(n)))
+        if tokens == 7:
+            L.check(self.lib.vdr_mask_decoder_workspace_bytes(self.h, int(problems), C.byref(n)))
+        else:
+            L.check(self.lib.vdr_mask_decoder_workspace_bytes_prompts(self.h, int(problems), int(tokens), C.byref(n)))
         return int(n.value)
 
-    def decode(self, emb: torch.Tensor, boxes: torch.Tensor, workspace=None):
+    def decode(self, emb: torch.Tensor, boxes=None, points=None, labels=None, mask_input=None, workspace=None):
         """emb [B, 256, g, g] on the device (a channel-first view of the encoder's [B, g, g, 256] output is read in place), boxes
-        [B, nb, 4] -> (low_res_logits [B, nb, 4, 4g, 4g] fp32, iou [B, nb, 4] fp32) of all four mask tokens: ONE vdr_mask_decode
-        call on the current stream.  workspace: a uint8 device tensor of at least workspace_bytes(B * nb), else allocated here."""
-        B, nb = int(boxes.shape[0]), int(boxes.shape[1])
+        [B, nb, 4] and / or points [B, nb, np, 2] with labels [B, nb, np], mask_input [B, nb, 4g, 4g] or one per image ([B, 1, 4g, 4g]
+        / [B, 4g, 4g]) -> (low_res_logits [B, nb, 4, 4g, 4g] fp32, iou [B, nb, 4] fp32) of all four mask tokens: ONE vdr_mask_decode
+        (boxes alone) or vdr_mask_decode_prompts call on the current stream.  workspace: a uint8 device tensor of at least
+        workspace_bytes(B * nb, tokens), else allocated here."""
+        import ctypes as C
+        boxes, points, labels, mask_input = check_prompts("decode", boxes, points, labels, mask_input, int(emb.shape[0]), self.g, self)
+        lead = boxes if boxes is not None else points
+        B, nb = int(lead.shape[0]), int(lead.shape[1])
         P = B * nb
+        npts = 0 if points is None else int(points.shape[2])
+        T = 5 + npts + (2 if boxes is not None else 1)
         emb = emb.to(self.device, torch.float32)
         if emb.permute(0, 2, 3, 1).is_contiguous():
             channels_last = 1
         else:
             emb, channels_last = emb.contiguous(), 0
-        bx = boxes.to(self.device, torch.float32).contiguous()
-        need = self.workspace_bytes(P)
+        bx = None if boxes is None else boxes.to(self.device, torch.float32).contiguous()
+        need = self.workspace_bytes(P, T)
         if workspace is None:
             workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
         logits = torch.empty((B, nb, 4, 4 * self.g, 4 * self.g), dtype=torch.float32, device=self.device)
         iou = torch.empty((B, nb, 4), dtype=torch.float32, device=self.device)
-        L.check(self.lib.vdr_mask_decode(self.h, emb.data_ptr(), channels_last, bx.data_ptr(), B, nb, workspace.data_ptr(), workspace.numel(),
-                                         logits.data_ptr(), iou.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if points is None and mask_input is None:
+            L.check(self.lib.vdr_mask_decode(self.h, emb.data_ptr(), channels_last, bx.data_ptr(), B, nb, workspace.data_ptr(), workspace.numel(),
+                                             logits.data_ptr(), iou.data_ptr(), stream))
+            return logits, iou
+        pr = L.vdr_mask_prompts(boxes=None if bx is None else bx.data_ptr())
+        if points is not None:
+            pt = points.to(self.device, torch.float32).contiguous()
+            lb = labels.to(self.device, torch.int32).contiguous()
+            pr.points, pr.labels, pr.points_per_problem = pt.data_ptr(), lb.data_ptr(), npts
+        if mask_input is not None:
+            mk = mask_input.to(self.device, torch.float32)
+            per_image = mk.dim() == 3 or (mk.shape[1] == 1 and nb != 1)
+            mk = mk.reshape(-1, 4 * self.g, 4 * self.g).contiguous()
+            pr.mask_input, pr.mask_per_image = mk.data_ptr(), int(per_image)
+        L.check(self.lib.vdr_mask_decode_prompts(self.h, emb.data_ptr(), channels_last, C.byref(pr), B, nb, workspace.data_ptr(), workspace.numel(),
+                                                 logits.data_ptr(), iou.data_ptr(), stream))
         return logits, iou
 
 
@@ -141,27 +275,38 @@ def scale_box(box, h: int, w: int, side: int) -> "tuple[float, float, float, flo
 def _require(model, what):
     cfg = getattr(model, "cfg", None)
     if cfg is None or getattr(cfg, "window", 0) <= 0:
-        raise ValueError(f"{what}: box-prompt segmentation needs a SAM / MedSAM model, got '{getattr(model, 'model_name', type(model).__name__)}'")
+        raise ValueError(f"{what}: prompted segmentation needs a SAM / MedSAM model, got '{getattr(model, 'model_name', type(model).__name__)}'")
     if not getattr(model, "has_mask_decoder", False):
         raise ValueError(f"{what}: the model was loaded without prompt_encoder.* / mask_decoder.* weights (an encoder-only checkpoint)")
 
 
-def segment_slice(model, img, box, multimask: bool = False, threshold: float = 0.0) -> np.ndarray:
+def segment_slice(model, img, box=None, multimask: bool = False, threshold: float = 0.0, points=None, point_labels=None) -> np.ndarray:
     """get_dense_descriptor's sibling: a RAW (h, w) gray or (h, w, 3) colour slice in [0, 1] and one box (x0, y0, x1, y1) in slice
-    pixels -> the (h, w) bool mask at slice resolution ((M, h, w) with multimask).  The slice is prepared as prepare_image
-    does, the box scaled by the same factors."""
+    pixels and / or points [np, 2] (x, y) in slice pixels with point_labels [np] -> the (h, w) bool mask at slice resolution
+    ((M, h, w) with multimask).  The slice is prepared as prepare_image does, the box and the points scaled by the same factors."""
     from . import prep
     _require(model, "segment_slice")
     t = torch.as_tensor(img)
     if t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[2] != 3):
         raise ValueError(f"segment_slice: a raw (h, w) / (h, w, 3) slice, got {tuple(t.shape)}")
-    b = torch.as_tensor(box)
-    if b.shape != (4,):
-        raise ValueError(f"segment_slice: box must be (x0, y0, x1, y1), got {tuple(b.shape)}")
-    check_boxes("segment_slice", b.reshape(1, 1, 4))
     h, w = int(t.shape[0]), int(t.shape[1])
     side = model.cfg.img
-    boxes = torch.tensor([[scale_box(b.tolist(), h, w, side)]], dtype=torch.float64)
+    boxes = pts = lbl = None
+    if box is not None:
+        b = torch.as_tensor(box)
+        if b.shape != (4,):
+            raise ValueError(f"segment_slice: box must be (x0, y0, x1, y1), got {tuple(b.shape)}")
+        check_boxes("segment_slice", b.reshape(1, 1, 4))
+        boxes = torch.tensor([[scale_box(b.tolist(), h, w, side)]], dtype=torch.float64)
+    if points is not None or point_labels is not None:
+        if points is None or point_labels is None:
+            raise ValueError("segment_slice: points and point_labels go together")
+        p, lbl = torch.as_tensor(points), torch.as_tensor(point_labels)
+        if p.dim() != 2 or p.shape[1] != 2 or tuple(lbl.shape) != (p.shape[0],):
+            raise ValueError(f"segment_slice: points must be [np, 2] (x, y) with point_labels [np], got {tuple(p.shape)} and {tuple(lbl.shape)}")
+        pts = (p.double() * torch.tensor([side / float(w), side / float(h)], dtype=torch.float64))[None, None]
+        lbl = lbl[None, None]
+    check_prompts("segment_slice", boxes, pts, lbl, None, 1, decoder=model.mask_decoder)
     x = prep.prepare_image(t, side=side, device=model.device)
-    m = model.segment(x, boxes, multimask=multimask).masks(size=(h, w), threshold=threshold)[0, 0]
+    m = model.segment(x, boxes, points=pts, point_labels=lbl, multimask=multimask).masks(size=(h, w), threshold=threshold)[0, 0]
     return (m if multimask else m[0]).cpu().numpy()
