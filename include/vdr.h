@@ -817,6 +817,62 @@ int vdr_op_mask_embed(const float* emb, int channels_last, const float* mask, in
 int vdr_op_mask_box(const float* logits, int64_t plane_stride, const float* prev, float* boxes, int32_t* area, int problems, int H, int W,
                     int img, float margin, float threshold, void* stream);
 
+/* ---- automatic mask generation: the statistics of candidate masks and box NMS (csrc/mask_stats.hip, csrc/nms.hip).
+ *
+ * vdr_op_mask_stats: for each of `planes` planes of fp32 logits H x W, the bilinear up-sampling to oh x ow is evaluated and
+ * reduced to seven integers; the up-sampled plane is never written.  Plane p starts at
+ *   logits + (p / planes_per_group) * group_stride + (p % planes_per_group) * plane_stride   (elements),
+ * so with planes_per_group = 1 plane p starts at logits + p * group_stride (one token of [P, 4, H, W] read in place, as
+ * vdr_op_mask_box takes it), with planes_per_group = planes at logits + p * plane_stride (group_stride is then not read), and
+ * tokens 1 .. 3 of [P, 4, H, W] are planes_per_group = 3, plane_stride = H W, group_stride = 4 H W from logits + H W.
+ * The arithmetic is torch's upsample_bilinear2d(align_corners=False) on the CPU, every operation fp32 and rounded once, no fma
+ * (the file is compiled without contraction):
+ *   sy  = float(H) / float(oh)                                   one IEEE division; sx = float(W) / float(ow)
+ *   src = (float(oy) + 0.5f) * sy - 0.5f, then src < 0 ? 0 : src  an addition, a multiplication, a subtraction
+ *   y0  = (int)src;  l1 = src - float(y0);  l0 = 1.0f - l1;  y1 = y0 + (y0 < H - 1);   the same in x
+ *   v   = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * c + lx1 * d)   a = in[y0][x0], b = in[y0][x1], c = in[y1][x0], d = in[y1][x1];
+ *                                                                 each product and each sum rounded
+ *   t_hi = threshold + offset, t_lo = threshold - offset          each computed once
+ *   counts int32 [planes, 3]: the pixels with v > t_hi, v > threshold, v > t_lo (a NaN counts nowhere)
+ *   box    int32 [planes, 4]: min x, min y, max x, max y (inclusive) over v > threshold; an empty mask gives 0, 0, 0, 0
+ *                             (transformers' _batched_mask_to_box)
+ * Integer reductions only: exact and independent of order.  Two launches (a partial slot per band of at most 32 output rows, then a
+ * finish of one wave per plane in fixed order), no atomics, one writer per output; a plane's outputs depend neither on `planes` nor
+ * on its position.  workspace: the partial slots, vdr_mask_stats_workspace_bytes (0 for a shape the op refuses); fewer bytes:
+ * VDR_ERR_WORKSPACE, nothing written.  Refused before the device is touched (VDR_ERR_INVALID): null pointers; workspace, counts or
+ * box not 16-byte aligned, logits not 4-byte aligned; H, W outside 1 .. 256; oh, ow outside 1 .. 4096; planes outside 1 .. 65535 or
+ * no multiple of planes_per_group; plane_stride < H W; a group_stride that lets a group's planes overlap the next group; offset < 0
+ * or NaN. */
+#define VDR_MASK_STATS_MAX_SIDE 256
+#define VDR_MASK_STATS_MAX_OUT 4096
+size_t vdr_mask_stats_workspace_bytes(int planes, int H, int W, int oh, int ow);
+int vdr_op_mask_stats(const float* logits, int64_t plane_stride, int planes_per_group, int64_t group_stride, int planes, int H, int W, int oh,
+                      int ow, float threshold, float offset, void* workspace, size_t workspace_bytes, int32_t* counts, int32_t* box,
+                      void* stream);
+
+/* vdr_op_nms: greedy non-maximum suppression of n boxes, torchvision's definition.
+ *   boxes   device fp32 [n, 4] (x0, y0, x1, y1)
+ *   order   device int32 [n]: a permutation of 0 .. n - 1 listing the boxes best first (a stable descending sort of the scores).  An
+ *           entry outside 0 .. n - 1 is never used as an address; the outputs are then unspecified
+ *   keep    device uint8 [n]: keep[i] = 1 if box i is kept, else 0
+ *   kept    device int32 [n]: the kept box indices in `order`'s sequence, then -1 up to n
+ *   count   device int32 [1]: the number of kept boxes
+ * Every operation fp32 and rounded once (no contraction):
+ *   area  = (x1 - x0) * (y1 - y0)
+ *   w     = min(x1_i, x1_j) - max(x0_i, x0_j), w < 0 ? 0 : w;  h likewise;  inter = w * h
+ *   iou   = inter / ((area_i + area_j) - inter)                   IEEE division
+ * Walking `order`, a box is kept unless an EARLIER KEPT box has iou > iou_threshold with it: the comparison is strict, and the NaN of
+ * two zero-area boxes does not suppress.  Two launches: the n x ceil(n / 64) matrix of 64-bit suppression words (on and above the
+ * diagonal) into the workspace, then ONE wave that walks it 64 positions at a time (the rows of a block are loaded together and the rows
+ * that are not kept masked out: measured faster than loading kept rows one after the other).  No atomics, bitwise reproducible.
+ * workspace: vdr_nms_workspace_bytes(n) = 8 n ceil(n / 64) bytes (0 for an n the op refuses); fewer: VDR_ERR_WORKSPACE, nothing
+ * written.  Refused before the device is touched (VDR_ERR_INVALID): null pointers; boxes or workspace not 16-byte aligned, order,
+ * kept or count not 4-byte aligned; n outside 1 .. 4096; a NaN iou_threshold. */
+#define VDR_NMS_MAX_BOXES 4096
+size_t vdr_nms_workspace_bytes(int n);
+int vdr_op_nms(const float* boxes, const int32_t* order, int n, float iou_threshold, void* workspace, size_t workspace_bytes, uint8_t* keep,
+               int32_t* kept, int32_t* count, void* stream);
+
 /* SAM / MedSAM Attention.forward with use_rel_pos (third-party segment_anything ImageEncoderViT, called at
  * tfds_dense_descriptor.py:123): per (window, head) softmax(q k^T dh^-0.5 + q.Rh[qh-kh] + q.Rw[qw-kw]) v.
  *   qkv   [batch*S*S, 3*H*64] bf16, `batch` windows (or whole grids) of S x S tokens, row-major (h, w)

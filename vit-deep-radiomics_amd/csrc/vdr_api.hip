@@ -18,6 +18,7 @@
 
 #include "../../include/vdr.h"
 #include "knn_map.h"
+#include "mask_stats_map.h"
 #include "local_corr_map.h"
 #include "vdr_kernels.h"
 
@@ -2779,6 +2780,47 @@ int vdr_op_mask_box(const float* logits, int64_t plane_stride, const float* prev
   if (!(margin >= 0.0f) || threshold != threshold) return refuse(op, VDR_ERR_INVALID, "margin must be >= 0, threshold a number");
   if (((uintptr_t)logits & 3) || ((uintptr_t)area & 3) || !aligned16({prev, boxes})) return refuse(op, VDR_ERR_INVALID, "prev and boxes must be 16-byte aligned, the others to their element");
   RUN_OP(launch_mask_box(logits, plane_stride, prev, boxes, area, problems, H, W, (float)img, margin, threshold, (hipStream_t)stream), "mask_box");
+}
+
+// ---- the automatic mask generator's post-processing (csrc/mask_stats.hip, csrc/nms.hip) ----
+size_t vdr_mask_stats_workspace_bytes(int planes, int H, int W, int oh, int ow) { return mask_stats_workspace_bytes(planes, H, W, oh, ow); }
+
+int vdr_op_mask_stats(const float* logits, int64_t plane_stride, int planes_per_group, int64_t group_stride, int planes, int H, int W, int oh,
+                      int ow, float threshold, float offset, void* workspace, size_t workspace_bytes, int32_t* counts, int32_t* box,
+                      void* stream) {
+  static_assert(VDR_MASK_STATS_MAX_SIDE == MS_MAX_SIDE && VDR_MASK_STATS_MAX_OUT == MS_MAX_OUT, "include/vdr.h and mask_stats_map.h");
+  const char* op = "vdr_op_mask_stats";
+  if (!logits || !workspace || !counts || !box) return refuse(op, VDR_ERR_INVALID, "null pointer");
+  if (planes < 1 || planes > 65535) return refuse(op, VDR_ERR_INVALID, "planes must be 1 .. 65535");
+  if (H < 1 || H > MS_MAX_SIDE || W < 1 || W > MS_MAX_SIDE) return refuse(op, VDR_ERR_INVALID, "H and W must be 1 .. " + std::to_string(MS_MAX_SIDE));
+  if (oh < 1 || oh > MS_MAX_OUT || ow < 1 || ow > MS_MAX_OUT) return refuse(op, VDR_ERR_INVALID, "oh and ow must be 1 .. " + std::to_string(MS_MAX_OUT));
+  if (plane_stride < (int64_t)H * W) return refuse(op, VDR_ERR_INVALID, "plane_stride is shorter than a plane");
+  if (planes_per_group < 1 || planes % planes_per_group) return refuse(op, VDR_ERR_INVALID, "planes must be a multiple of planes_per_group >= 1");
+  if (planes_per_group < planes && group_stride < (planes_per_group - 1) * plane_stride + (int64_t)H * W)
+    return refuse(op, VDR_ERR_INVALID, "group_stride is shorter than a group's planes");
+  if (!(offset >= 0.0f)) return refuse(op, VDR_ERR_INVALID, "offset must be >= 0");
+  if (((uintptr_t)logits & 3) || !aligned16({workspace, counts, box})) return refuse(op, VDR_ERR_INVALID, "workspace, counts and box must be 16-byte aligned, logits to its element");
+  const size_t need = mask_stats_workspace_bytes(planes, H, W, oh, ow);
+  if (workspace_bytes < need) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(need) + " bytes needed");
+  RUN_OP(launch_mask_stats(logits, plane_stride, planes_per_group, group_stride, planes, H, W, oh, ow, threshold, offset, workspace, counts, box,
+                           (hipStream_t)stream),
+         "mask_stats");
+}
+
+size_t vdr_nms_workspace_bytes(int n) { return nms_workspace_bytes(n); }
+
+int vdr_op_nms(const float* boxes, const int32_t* order, int n, float iou_threshold, void* workspace, size_t workspace_bytes, uint8_t* keep,
+               int32_t* kept, int32_t* count, void* stream) {
+  static_assert(VDR_NMS_MAX_BOXES == NMS_MAX_BOXES, "include/vdr.h and vdr_kernels.h");
+  const char* op = "vdr_op_nms";
+  if (!boxes || !order || !workspace || !keep || !kept || !count) return refuse(op, VDR_ERR_INVALID, "null pointer");
+  if (n < 1 || n > NMS_MAX_BOXES) return refuse(op, VDR_ERR_INVALID, "n must be 1 .. " + std::to_string(NMS_MAX_BOXES));
+  if (iou_threshold != iou_threshold) return refuse(op, VDR_ERR_INVALID, "iou_threshold must be a number");
+  if (!aligned16({boxes, workspace}) || (((uintptr_t)order | (uintptr_t)kept | (uintptr_t)count) & 3))
+    return refuse(op, VDR_ERR_INVALID, "boxes and workspace must be 16-byte aligned, order, kept and count to their element");
+  const size_t need = nms_workspace_bytes(n);
+  if (workspace_bytes < need) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(need) + " bytes needed");
+  RUN_OP(launch_nms(boxes, order, n, iou_threshold, workspace, keep, kept, count, (hipStream_t)stream), "nms");
 }
 
 int vdr_op_attention_relpos(const void* qkv, const float* rel_pos_h, const float* rel_pos_w, float* rel, void* out,

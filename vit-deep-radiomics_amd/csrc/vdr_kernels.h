@@ -264,6 +264,14 @@ hipError_t launch_prompt_tokens(const float* boxes, const float* points, const i
                                 int T, float img, hipStream_t s);
 hipError_t launch_mask_box(const float* logits, int64_t plane_stride, const float* prev, float* boxes, int32_t* area, int P, int H,
                            int W, float img, float margin, float threshold, hipStream_t s);
+// csrc/mask_stats.hip, csrc/nms.hip: the post-processing of the automatic mask generator (include/vdr.h "automatic mask generation")
+size_t mask_stats_workspace_bytes(int P, int H, int W, int oh, int ow);  // 0: a shape the op refuses
+hipError_t launch_mask_stats(const float* logits, int64_t plane_stride, int group, int64_t group_stride, int P, int H, int W, int oh, int ow,
+                             float threshold, float offset, void* work, int32_t* counts, int32_t* box, hipStream_t s);
+constexpr int NMS_MAX_BOXES = 4096;  // 64 words of 64 bits: one lane of the walking wave per word
+size_t nms_workspace_bytes(int n);
+hipError_t launch_nms(const float* boxes, const int32_t* order, int n, float iou_threshold, void* work, uint8_t* keep, int32_t* kept,
+                      int32_t* count, hipStream_t s);
 hipError_t launch_attention_pool(const float* q, const void* kv, int64_t ldkv, void* out, int batch, int n, int heads,
                                  int head_dim, hipStream_t s);
 

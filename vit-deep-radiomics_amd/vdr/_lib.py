@@ -143,6 +143,10 @@ SYMBOLS = {
     "vdr_mask_decode_prompts": (_I, [_P, _P, _I, C.POINTER(vdr_mask_prompts), _I, _I, _P, C.c_size_t, _P, _P, _P]),
     "vdr_op_mask_embed": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _F, _P]),
     "vdr_op_mask_box": (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P]),
+    "vdr_mask_stats_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
+    "vdr_op_mask_stats": (_I, [_P, _L, _I, _L, _I, _I, _I, _I, _I, _F, _F, _P, C.c_size_t, _P, _P, _P]),
+    "vdr_nms_workspace_bytes": (C.c_size_t, [_I]),
+    "vdr_op_nms": (_I, [_P, _P, _I, _F, _P, C.c_size_t, _P, _P, _P, _P]),
     "vdr_op_attention_relpos": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "vdr_op_layernorm_window": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "vdr_op_layernorm_mx_window": (_I, [_P, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P]),

@@ -366,6 +366,20 @@ class VitDescriptorModel:
         logits, iou = sg.select_masks(*self.mask_decoder.decode(self.image_encoder(x), *prompts), multimask)
         return sg.Segmentation(logits, iou, (self.cfg.img, self.cfg.img))
 
+    def generate_masks(self, x: torch.Tensor, points_per_side: int = 32, points_per_batch: int = 64, pred_iou_thresh: float = 0.88,
+                       stability_score_thresh: float = 0.95, stability_score_offset: float = 1.0, mask_threshold: float = 0.0,
+                       box_nms_thresh: float = 0.7, size=None):
+        """Segment everything: SAM's automatic mask generator on ONE image x [1, 3, S, S] (or [3, S, S]) -> vdr.MaskSet (vdr/amg.py).
+        A points_per_side x points_per_side grid of one-point prompts is decoded points_per_batch at a time into three masks a
+        point; every candidate's stability score, area and box at `size` (the input size by default) come from vdr.ops.mask_stats;
+        candidates with predicted IoU > pred_iou_thresh and stability > stability_score_thresh (both strict) go through greedy box
+        NMS at box_nms_thresh (vdr.ops.nms, best predicted IoU first), and the kept points are decoded once more for their
+        logits.  Two host reads in all: the filter flags and the NMS count.  More than 4096 candidates after the filter is a
+        ValueError.  Crop layers, small-region removal and mask-level NMS are out of scope."""
+        from . import amg
+        return amg.generate(self, x, points_per_side, points_per_batch, pred_iou_thresh, stability_score_thresh, stability_score_offset,
+                            mask_threshold, box_nms_thresh, size)
+
     def propagate_masks(self, x: torch.Tensor, box, index: int, direction: str = "both", margin: float = 8, use_mask_prompt: bool = True,
                         multimask: bool = False, max_batch: int = 16):
         """A mask for a whole volume from ONE annotated slice: x [Z, 3, S, S] prepared slices, box (x0, y0, x1, y1) on slice

@@ -382,6 +382,96 @@ def mask_box(logits, prev, img: int, margin: float = 0.0, threshold: float = 0.0
     return boxes, area
 
 
+MASK_STATS_MAX_SIDE, MASK_STATS_MAX_OUT, NMS_MAX_BOXES = 256, 4096, 4096  # VDR_MASK_STATS_MAX_SIDE, .._MAX_OUT, VDR_NMS_MAX_BOXES (include/vdr.h)
+
+
+class PlaneOperand:
+    """Planes of fp32 logits as vdr_op_mask_stats reads them (the operand builder of mask_stats): the tensor kept alive and
+    (planes, planes_per_group, plane_stride, group_stride, H, W).  [P, H, W] or [G, M, H, W] on the device; a plane must be
+    contiguous, the planes and groups may be strided (one token, or tokens 1 .. 3, of a [P, 4, H, W] tensor are read in place);
+    anything else is copied once."""
+
+    def __init__(self, x, op: str, name: str = "logits"):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() not in (3, 4):
+            raise ValueError(f"{op}: {name} must be a float32 [P, H, W] or [G, M, H, W] tensor")
+        if not x.is_cuda:
+            raise ValueError(f"{op}: {name} must live on the HIP device")
+        if x.dim() == 3:
+            x = x.unsqueeze(1)
+        G, M, H, W = (int(v) for v in x.shape)
+        if min(G, M) < 1 or not (1 <= H <= MASK_STATS_MAX_SIDE and 1 <= W <= MASK_STATS_MAX_SIDE):
+            raise ValueError(f"{op}: {name} needs at least one plane of 1 .. {MASK_STATS_MAX_SIDE} rows and columns, got {tuple(x.shape)}")
+        if G * M > 65535:
+            raise ValueError(f"{op}: at most 65535 planes a call, got {G * M}")
+        ps, gs = (x.stride(1) if M > 1 else H * W), (x.stride(0) if G > 1 else M * H * W)
+        ok = (W == 1 or x.stride(3) == 1) and (H == 1 or x.stride(2) == W) and ps >= H * W and gs >= (M - 1) * ps + H * W
+        if not ok:
+            x = x.contiguous()
+            ps, gs = H * W, M * H * W
+        self.x, self.planes, self.group, self.plane_stride, self.group_stride, self.H, self.W = x, G * M, M, ps, gs, H, W
+        self.shape = (G, M)
+
+
+def check_out_size(op: str, size) -> "tuple[int, int]":
+    try:
+        oh, ow = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"{op}: size must be (height, width), got {size!r}") from None
+    if not (1 <= oh <= MASK_STATS_MAX_OUT and 1 <= ow <= MASK_STATS_MAX_OUT):
+        raise ValueError(f"{op}: size must be 1 .. {MASK_STATS_MAX_OUT} in both directions, got {size!r}")
+    return oh, ow
+
+
+def mask_stats(logits, size, threshold: float = 0.0, offset: float = 1.0, workspace=None):
+    """The statistics of candidate masks at image resolution (vdr_op_mask_stats): logits fp32 [P, H, W] or [G, M, H, W] on the
+    device (PlaneOperand: strided planes are read in place) -> (counts int32 [.., 3], box int32 [.., 4]) of the bilinear
+    (align_corners=False) up-sampling to size = (oh, ow), which is never written: the pixel counts above threshold + offset,
+    threshold and threshold - offset, and (min x, min y, max x, max y) of the pixels above threshold (0, 0, 0, 0 for none).
+    Bit for bit vdr.amg.mask_stats_torch.  workspace: a uint8 device tensor of at least vdr_mask_stats_workspace_bytes."""
+    o = PlaneOperand(logits, "mask_stats")
+    oh, ow = check_out_size("mask_stats", size)
+    if not float(offset) >= 0.0:
+        raise ValueError(f"mask_stats: offset must be >= 0, got {offset!r}")
+    lib = L.load()
+    dev = o.x.device
+    need = lib.vdr_mask_stats_workspace_bytes(o.planes, o.H, o.W, oh, ow)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    lead = (o.planes,) if logits.dim() == 3 else o.shape
+    counts = torch.empty((*lead, 3), dtype=torch.int32, device=dev)
+    box = torch.empty((*lead, 4), dtype=torch.int32, device=dev)
+    L.check(lib.vdr_op_mask_stats(o.x.data_ptr(), o.plane_stride, o.group, o.group_stride, o.planes, o.H, o.W, oh, ow, float(threshold),
+                                  float(offset), workspace.data_ptr(), workspace.numel(), counts.data_ptr(), box.data_ptr(), _s(o.x)))
+    return counts, box
+
+
+def nms(boxes, scores, iou_threshold: float, workspace=None):
+    """Greedy box non-maximum suppression (vdr_op_nms; torchvision's definition, bit for bit vdr.amg.nms_torch): boxes [N, 4]
+    (x0, y0, x1, y1) and scores [N] on the device, N in 1 .. 4096 -> (kept int32 [N]: the kept box indices best first, then -1;
+    count int32 [1]), both on the device: nothing here synchronises.  Boxes are visited in the order of a stable descending
+    sort of the scores (equal scores: the lower index first); a box goes when an earlier kept box has IoU > iou_threshold."""
+    if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda and boxes.dim() == 2 and boxes.shape[1] == 4 and 1 <= boxes.shape[0] <= NMS_MAX_BOXES):
+        raise ValueError(f"nms: boxes must be an [N, 4] tensor on the device, N in 1 .. {NMS_MAX_BOXES}")
+    N = int(boxes.shape[0])
+    if not (isinstance(scores, torch.Tensor) and scores.device == boxes.device and tuple(scores.shape) == (N,)):
+        raise ValueError(f"nms: scores must be [{N}] on the boxes' device")
+    if float(iou_threshold) != float(iou_threshold):
+        raise ValueError("nms: iou_threshold must be a number")
+    lib = L.load()
+    dev = boxes.device
+    bx = boxes.to(torch.float32).contiguous()
+    order = torch.sort(scores, descending=True, stable=True).indices.to(torch.int32)
+    need = lib.vdr_nms_workspace_bytes(N)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    keep = torch.empty((N,), dtype=torch.uint8, device=dev)
+    kept = torch.empty((N,), dtype=torch.int32, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    L.check(lib.vdr_op_nms(bx.data_ptr(), order.data_ptr(), N, float(iou_threshold), workspace.data_ptr(), workspace.numel(), keep.data_ptr(),
+                           kept.data_ptr(), count.data_ptr(), _s(bx)))
+    return kept, count
+
+
 def log_bin(x: torch.Tensor, gh: int, gw: int, hierarchy: int = 2, out_dtype=torch.float32, out=None) -> torch.Tensor:
     """Log-binning of a dense descriptor map (vdr_op_log_bin): x [B, gh*gw, C] bf16 or fp32 -- contiguous, or a view whose
     last dimension is contiguous, such as the key columns and patch rows buf[:, P:, C:2*C] of a [B, P + n, 3C] qkv

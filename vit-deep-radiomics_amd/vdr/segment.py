@@ -14,7 +14,9 @@ one padding point if there is no box; 2 box corners if there is one], at most 16
 are bf16(emb + mask_downscaling(mask)) from ONE fused kernel (vdr_op_mask_embed).  propagate_masks (vdr/model.py) carries a
 mask through a volume from one annotated slice: each slice's box is vdr_op_mask_box of its neighbour's logits.
 
-Out of scope: the automatic mask generator, per-problem point counts other than by label -1 padding, fp8.  MedSAM fine-tuned
+The automatic mask generator (a grid of point prompts, fused mask statistics, box NMS) is vdr/amg.py.
+
+Out of scope: per-problem point counts other than by label -1 padding, fp8.  MedSAM fine-tuned
 the decoder with box prompts only: its point / mask-prompt weights are SAM's, nothing is claimed about their masks."""
 from __future__ import annotations
 
@@ -44,6 +46,18 @@ class Segmentation:
 
     def masks(self, size=None, threshold: float = 0.0) -> torch.Tensor:
         return self.logits(size) > threshold
+
+    def stats(self, size=None, threshold: float = 0.0, offset: float = 1.0):
+        """(counts int32 [B, nb, M, 3], boxes int32 [B, nb, M, 4], stability fp32 [B, nb, M]) of every mask at the input size or
+        `size`: the pixels above threshold + offset, threshold and threshold - offset, the box (min x, min y, max x, max y) of
+        those above threshold, and SAM's stability score float(n_hi) / float(n_lo).  ONE vdr.ops.mask_stats call that reads
+        low_res_logits in place (tokens 1 .. 3 of the decode's four included); the up-sampled masks are never written."""
+        from . import amg, ops
+        size = self.input_size if size is None else size
+        B, nb, M = (int(v) for v in self.low_res_logits.shape[:3])
+        counts, box = ops.mask_stats(self.low_res_logits.flatten(0, 1), size, threshold, offset)
+        counts, box = counts.reshape(B, nb, M, 3), box.reshape(B, nb, M, 4)
+        return counts, box, amg.stability(counts)
 
     def best(self) -> "Segmentation":
         """the highest-IoU mask of every problem (M = 1): a device gather, no synchronisation; ties go to the lowest index"""
