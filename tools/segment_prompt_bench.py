@@ -2,14 +2,16 @@
 """Point / mask prompts and the volume sweep on one MI355X: what they cost next to the box decode.
 
    python tools/segment_prompt_bench.py [--rounds 9] [--steps 20] [--out profiles/segment_prompts_bench.txt] [--no-sweep]
-                                        [--parent-lib PATH --parent-copy PATH]
+                                        [--parent-lib PATH --parent-copy PATH] [--lib PATH]
    python tools/segment_prompt_bench.py --one-step      (one sweep step and nothing else: the program to put behind
                                                          `rocprofv3 --kernel-trace --stats --`, no counters in the same run)
 
 * decode at g = 64, P = 1: vdr_mask_decode (T = 7), vdr_mask_decode_prompts with boxes only (T = 7: checked bitwise equal
   first), with a box and nine points (T = 16) and with a box and a mask prompt; interleaved medians with min and max.
   --parent-lib / --parent-copy: the parent commit's library and a second copy of it, dlopen'ed next to this one: its
-  vdr_mask_decode must give this library's bits, and the time difference is read against parent / parent-copy.
+  vdr_mask_decode must give this library's bits at P = 1 and P = 16, and the time difference is read against parent /
+  parent-copy; then the time to build a decoder (create, set every weight, finalize), alternating between the two libraries.
+  --lib: run everything on that libvdr.so instead of the package's own (the sweep of a parent build, in a process of its own).
 * mask_embed alone at P = 1, 16, 64 in algorithmic TB/s (embedding 1 KB + mask 64 B in, keys 512 B out per cell) against
   the eager torch convolution chain.  decoder_keys_kernel cannot be launched alone through the ABI: its time is read from the
   kernel trace of a box-only sweep step (--one-step --no-mask-prompt).
@@ -75,8 +77,9 @@ def torch_mask_box(lg, prev, img, margin):
     return torch.where((area > 0)[:, None], box, prev), area
 
 
-def foreign_decoder(path, w, g, img, mlp_dim=2048):
-    """a box-prompt decoder handle on the library at `path` (one built before the prompt entry points existed lacks them)"""
+def foreign_decoder(path, w, g, img, mlp_dim=2048, problems=1):
+    """a box-prompt decoder handle on the library at `path` (one built before the prompt entry points existed lacks them);
+    decode(emb [1, 256, g, g], boxes [problems, 4], lg, iou), .close()"""
     lib = _lib.bind(ctypes.CDLL(path), skip_missing=True)
     cfg = _lib.vdr_mask_decoder_config(grid=g, img=img, channels=256, heads=8, depth=2, mlp_dim=mlp_dim, attention_downsample_rate=2, mask_tokens=4,
                                        upscale_channels_1=64, upscale_channels_2=32, iou_head_depth=3, **SA_EPS)
@@ -88,12 +91,13 @@ def foreign_decoder(path, w, g, img, mlp_dim=2048):
         assert lib.vdr_mask_decoder_set_weight(h, name.encode(), t.data_ptr(), (ctypes.c_int64 * t.dim())(*t.shape), t.dim()) == 0
     assert lib.vdr_mask_decoder_finalize(h) == 0
     n = ctypes.c_size_t()
-    assert lib.vdr_mask_decoder_workspace_bytes(h, 1, ctypes.byref(n)) == 0
+    assert lib.vdr_mask_decoder_workspace_bytes(h, problems, ctypes.byref(n)) == 0
     ws = torch.empty(n.value, dtype=torch.uint8, device="cuda")
 
     def decode(emb, boxes, lg, iou):
-        assert lib.vdr_mask_decode(h, emb.data_ptr(), 0, boxes.data_ptr(), 1, 1, ws.data_ptr(), ws.numel(), lg.data_ptr(), iou.data_ptr(),
+        assert lib.vdr_mask_decode(h, emb.data_ptr(), 0, boxes.data_ptr(), 1, problems, ws.data_ptr(), ws.numel(), lg.data_ptr(), iou.data_ptr(),
                                    torch.cuda.current_stream().cuda_stream) == 0
+    decode.close = lambda: lib.vdr_mask_decoder_destroy(h)
     return decode
 
 
@@ -113,9 +117,12 @@ def main():
     ap.add_argument("--slices", type=int, default=64)
     ap.add_argument("--parent-lib")
     ap.add_argument("--parent-copy")
+    ap.add_argument("--lib")
     ap.add_argument("--one-step", action="store_true")
     ap.add_argument("--no-mask-prompt", action="store_true")
     a = ap.parse_args()
+    if a.lib:
+        _lib.LIB_PATH = os.path.abspath(a.lib)  # before the first load()
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
     w = decoder_weights(7)
@@ -140,8 +147,8 @@ def main():
 
     def fmt(t):
         return f"{t[0]:7.3f} [{t[1]:.3f} .. {t[2]:.3f}]"
-    emit(f"segment_prompt_bench: {torch.cuda.get_device_name(0)}, kernels {vdr.source_id()}, {a.rounds} interleaved rounds of {a.steps} steps, "
-         "median ms [min .. max]")
+    emit(f"segment_prompt_bench: {torch.cuda.get_device_name(0)}, kernels {vdr.source_id()}, library {os.path.relpath(_lib.LIB_PATH, ROOT)}, "
+         f"{a.rounds} interleaved rounds of {a.steps} steps, median ms [min .. max]")
     dec = MaskDecoder(w, g, img, dev, **SA_EPS)
     emb = torch.randn((1, 256, g, g), device=dev)
     boxes = torch.tensor([[[200.0, 220.0, 800.0, 790.0]]], device=dev)
@@ -169,19 +176,40 @@ def main():
         emit(f"  {nm:44s} {fmt(t)}  {d:+.3f} ms against the yardstick" + ("" if d <= max(res[0][2] - res[0][1], 0.0) or nm.startswith("vdr_mask_decode,")
                                                                           else "  **outside the yardstick's own min .. max**"))
     if a.parent_lib:
-        pa, pb = foreign_decoder(a.parent_lib, w, g, img), foreign_decoder(a.parent_copy or a.parent_lib, w, g, img)
-        la, ia, lb_, ib = torch.empty_like(lg0), torch.empty_like(iou0), torch.empty_like(lg0), torch.empty_like(iou0)
-        pa(emb, boxes[0], la, ia)
-        pb(emb, boxes[0], lb_, ib)
-        torch.cuda.synchronize()
-        emit(f"the parent's library on the same weights: vdr_mask_decode bitwise equal to this library's: {torch.equal(la, lg0) and torch.equal(ia, iou0)}")
-        assert torch.equal(la, lg0) and torch.equal(ia, iou0) and torch.equal(lb_, lg0)
-        r = interleaved([lambda: pa(emb, boxes[0], la, ia), lambda: pb(emb, boxes[0], lb_, ib), new_entry, lambda: dec.decode(emb, boxes)], a.rounds, a.steps)
-        spread = abs(r[0][0] - r[1][0])
-        emit(f"  parent {fmt(r[0])}  parent copy {fmt(r[1])}  (difference of two parents {spread:.4f} ms)")
-        emit(f"  this library: vdr_mask_decode_prompts {fmt(r[2])}  vdr_mask_decode via MaskDecoder.decode (with its allocations) {fmt(r[3])}")
-        d = r[2][0] - r[0][0]
-        emit(f"  this - parent = {d:+.4f} ms: " + ("inside" if abs(d) <= max(spread, r[0][2] - r[0][1]) else "**OUTSIDE**") + " the parents' spread / min .. max")
+        import time
+        this = os.path.abspath(_lib.LIB_PATH)
+        for P in (1, 16):   # vdr_mask_decode on the three libraries, raw ctypes calls with preallocated outputs on each
+            bx = (boxes[0] + torch.arange(P, device=dev)[:, None] * torch.tensor([3.0, 2.0, -2.0, -3.0], device=dev)).contiguous()
+            decs = [foreign_decoder(p, w, g, img, problems=P) for p in (a.parent_lib, a.parent_copy or a.parent_lib, this)]
+            outs = [(torch.empty((1, P, 4, 4 * g, 4 * g), device=dev), torch.empty((1, P, 4), device=dev)) for _ in decs]
+            for dc, (lg, iou) in zip(decs, outs):
+                dc(emb, bx, lg, iou)
+            torch.cuda.synchronize()
+            same = all(torch.equal(lg, outs[2][0]) and torch.equal(iou, outs[2][1]) for lg, iou in outs[:2])
+            emit(f"the parent's library on the same weights, P {P}: vdr_mask_decode bitwise equal to this library's: {same}")
+            assert same
+            r = interleaved([lambda dc=dc, o=o: dc(emb, bx, *o) for dc, o in zip(decs, outs)], a.rounds, a.steps)
+            spread = abs(r[0][0] - r[1][0])
+            emit(f"  parent {fmt(r[0])}  parent copy {fmt(r[1])}  (difference of two parents {spread:.4f} ms)  this library {fmt(r[2])}")
+            d = r[2][0] - r[0][0]
+            emit(f"  this - parent = {d:+.4f} ms: " + ("inside" if d <= max(spread, r[0][2] - r[0][1]) else "**SLOWER, OUTSIDE**") + " the parents' spread / min .. max")
+            for dc in decs:
+                dc.close()
+        ms = {p: [] for p in (a.parent_lib, this)}   # load time: create, set every weight, finalize (g 64: the float64 tables dominate)
+        for _ in range(5):
+            for p in ms:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                dc = foreign_decoder(p, w, g, img)
+                torch.cuda.synchronize()
+                ms[p].append((time.perf_counter() - t0) * 1e3)
+                dc.close()
+        emit("building a decoder at g 64, mlp_dim 2048 (create, set every weight, finalize): 5 per library, alternating, wall clock (ms)")
+        for p, v in ms.items():
+            emit(f"  {os.path.relpath(p, ROOT):40s} median {sorted(v)[2]:8.1f}  min {min(v):8.1f}  max {max(v):8.1f}   " + " ".join(f"{x:.1f}" for x in v))
+        d = sorted(ms[this])[2] - sorted(ms[a.parent_lib])[2]
+        rng = max(ms[a.parent_lib]) - min(ms[a.parent_lib])
+        emit(f"  median this - parent = {d:+.1f} ms; range of the parent {rng:.1f} ms -> " + ("not slower beyond the parent's range" if d <= rng else "**SLOWER**"))
     emit("mask_embed alone at g 64, algorithmic bytes (embedding 1 KB + mask 64 B in, keys 512 B out per cell) / time; im2col of this library: 4.3 TB/s")
     packed = pack(w).to(dev)
     wd = {k: v.to(dev) for k, v in w.items() if k.startswith(MD)}

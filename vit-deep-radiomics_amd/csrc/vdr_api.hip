@@ -18,6 +18,7 @@
 
 #include "../../include/vdr.h"
 #include "knn_map.h"
+#include "mask_decoder_pack.h"
 #include "mask_stats_map.h"
 #include "local_corr_map.h"
 #include "vdr_kernels.h"
@@ -27,13 +28,6 @@ using namespace vdr;
 namespace {
 
 thread_local std::string g_err;
-
-uint16_t f32_to_bf16(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // keep NaN a NaN
-  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);                  // round to nearest even
-}
 
 int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
@@ -3336,109 +3330,23 @@ int vdr_profile_read(vdr_handle m, double* ms, int64_t* launches, double* flops,
 }  // extern "C"
 
 // ---- the mask decoder object (include/vdr.h "mask decoder"; kernels: csrc/mask_decoder.hip) -------------------------------------
+// The load-time rules of this file hold here too: the device copies live in ONE DevBuf that frees itself with the handle, and a
+// name is spelled once -- a checkpoint name in md_names, a derived buffer as a field of MdWeights (both mask_decoder_pack.h).
 struct vdr_mask_decoder {
   vdr_mask_decoder_config cfg;
-  std::vector<std::string> names;
-  std::vector<std::vector<int64_t>> shapes;
-  std::vector<std::string> pnames;                  // the optional prompt weights: 3 of the point prompts, then 10 of the mask prompt
-  std::vector<std::vector<int64_t>> pshapes;
-  int support = 0;                                  // VDR_PROMPT_POINTS | VDR_PROMPT_MASK: what finalize found complete
-  std::map<std::string, std::vector<float>> host;   // what vdr_mask_decoder_set_weight was given
-  std::map<std::string, void*> dev;                 // what vdr_mask_decoder_finalize built (owned)
+  int device = 0;
+  std::vector<MdWeightDef> table;  // md_names: the n_required required weights, then the optional prompt weights
+  int n_required = 0;
+  int support = 0;  // VDR_PROMPT_POINTS | VDR_PROMPT_MASK: what finalize found complete
+  MdHost host;      // what vdr_mask_decoder_set_weight was given
+  DevBuf arena;     // what vdr_mask_decoder_finalize built: md_pack's bytes ...
+  MdWeights w;      // ... and its fields, pointing into the arena
   bool finalized = false;
-  ~vdr_mask_decoder() {
-    for (auto& kv : dev) (void)hipFree(kv.second);
-  }
 };
 
 namespace {
 
 using MD = vdr_mask_decoder;
-constexpr int MD_C = 256, MD_T = 7, MD_IN = 128, MD_MAX_T = 16, MD_POINT_WEIGHTS = 3;
-
-void md_names(MD* d) {
-  auto add = [&](const std::string& n, std::vector<int64_t> shp) {
-    d->names.push_back(n);
-    d->shapes.push_back(std::move(shp));
-  };
-  const int64_t C = MD_C, F = d->cfg.mlp_dim;
-  auto attn = [&](const std::string& p, int64_t inner) {
-    for (const char* n : {"q_proj", "k_proj", "v_proj"}) {
-      add(p + n + ".weight", {inner, C});
-      add(p + n + ".bias", {inner});
-    }
-    add(p + "out_proj.weight", {C, inner});
-    add(p + "out_proj.bias", {C});
-  };
-  auto ln = [&](const std::string& p, int64_t n) {
-    add(p + ".weight", {n});
-    add(p + ".bias", {n});
-  };
-  add("prompt_encoder.pe_layer.positional_encoding_gaussian_matrix", {2, C / 2});
-  add("prompt_encoder.point_embeddings.2.weight", {1, C});
-  add("prompt_encoder.point_embeddings.3.weight", {1, C});
-  add("prompt_encoder.no_mask_embed.weight", {1, C});
-  add("mask_decoder.iou_token.weight", {1, C});
-  add("mask_decoder.mask_tokens.weight", {4, C});
-  for (int i = 0; i < 2; ++i) {
-    const std::string p = "mask_decoder.transformer.layers." + std::to_string(i) + ".";
-    attn(p + "self_attn.", C);
-    ln(p + "norm1", C);
-    attn(p + "cross_attn_token_to_image.", MD_IN);
-    ln(p + "norm2", C);
-    add(p + "mlp.lin1.weight", {F, C});
-    add(p + "mlp.lin1.bias", {F});
-    add(p + "mlp.lin2.weight", {C, F});
-    add(p + "mlp.lin2.bias", {C});
-    ln(p + "norm3", C);
-    ln(p + "norm4", C);
-    attn(p + "cross_attn_image_to_token.", MD_IN);
-  }
-  attn("mask_decoder.transformer.final_attn_token_to_image.", MD_IN);
-  ln("mask_decoder.transformer.norm_final_attn", C);
-  add("mask_decoder.output_upscaling.0.weight", {C, 64, 2, 2});
-  add("mask_decoder.output_upscaling.0.bias", {64});
-  ln("mask_decoder.output_upscaling.1", 64);
-  add("mask_decoder.output_upscaling.3.weight", {64, 32, 2, 2});
-  add("mask_decoder.output_upscaling.3.bias", {32});
-  for (int m = 0; m < 4; ++m)
-    for (int j = 0; j < 3; ++j) {
-      const std::string p = "mask_decoder.output_hypernetworks_mlps." + std::to_string(m) + ".layers." + std::to_string(j);
-      add(p + ".weight", {j == 2 ? 32 : C, C});
-      add(p + ".bias", {j == 2 ? 32 : C});
-    }
-  for (int j = 0; j < 3; ++j) {
-    const std::string p = "mask_decoder.iou_prediction_head.layers." + std::to_string(j);
-    add(p + ".weight", {j == 2 ? 4 : C, C});
-    add(p + ".bias", {j == 2 ? 4 : C});
-  }
-  // optional: the first MD_POINT_WEIGHTS are the point prompts' group, the rest the mask prompt's (mask_in_chans = 16)
-  auto padd = [&](const std::string& n, std::vector<int64_t> shp) {
-    d->pnames.push_back(n);
-    d->pshapes.push_back(std::move(shp));
-  };
-  padd("prompt_encoder.point_embeddings.0.weight", {1, C});
-  padd("prompt_encoder.point_embeddings.1.weight", {1, C});
-  padd("prompt_encoder.not_a_point_embed.weight", {1, C});
-  const std::string m = "prompt_encoder.mask_downscaling.";
-  padd(m + "0.weight", {4, 1, 2, 2});
-  padd(m + "0.bias", {4});
-  padd(m + "1.weight", {4});
-  padd(m + "1.bias", {4});
-  padd(m + "3.weight", {16, 4, 2, 2});
-  padd(m + "3.bias", {16});
-  padd(m + "4.weight", {16});
-  padd(m + "4.bias", {16});
-  padd(m + "6.weight", {C, 16, 1, 1});
-  padd(m + "6.bias", {C});
-}
-
-float md_bf16_round(float f) {
-  const uint32_t u = (uint32_t)f32_to_bf16(f) << 16;
-  float r;
-  memcpy(&r, &u, 4);
-  return r;
-}
 
 // the decode's workspace: every buffer 256-byte aligned, in this order
 struct MdCarve {
@@ -3476,34 +3384,14 @@ MdCarve md_carve(const MD* d, int64_t P, int tokens = MD_T) {
   return c;
 }
 
-int md_upload(MD* d, const std::string& label, const void* src, size_t bytes) {
-  void* p = nullptr;
-  OP_TRY(hipMalloc(&p, bytes), "hipMalloc(mask decoder weight)");
-  d->dev[label] = p;
-  OP_TRY(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice), "hipMemcpy(mask decoder weight)");
-  return VDR_OK;
-}
-int md_up_bf(MD* d, const std::string& label, const std::vector<float>& v) {
-  std::vector<uint16_t> b(v.size());
-  for (size_t i = 0; i < v.size(); ++i) b[i] = f32_to_bf16(v[i]);
-  return md_upload(d, label, b.data(), b.size() * 2);
-}
-int md_up_f32(MD* d, const std::string& label, const std::vector<float>& v) { return md_upload(d, label, v.data(), v.size() * 4); }
-
-std::vector<float> md_cat(std::initializer_list<const std::vector<float>*> parts) {
-  std::vector<float> o;
-  for (auto* p : parts) o.insert(o.end(), p->begin(), p->end());
-  return o;
-}
-
-int md_ln(const void* x, void* y, const float* gamma, const float* beta, int64_t rows, int D, float eps, hipStream_t s) {
+int md_ln(const void* x, void* y, const MdNormW& w, int64_t rows, int D, float eps, hipStream_t s) {
   LnArgs a{};
   a.x = x;
   a.in_bf16 = 1;
   a.y = y;
   a.out_bf16 = 1;
-  a.gamma = gamma;
-  a.beta = beta;
+  a.gamma = w.g;
+  a.beta = w.b;
   a.rows = rows;
   a.D = D;
   a.eps = eps;
@@ -3513,10 +3401,10 @@ int md_ln(const void* x, void* y, const float* gamma, const float* beta, int64_t
   return VDR_OK;
 }
 
-int md_gemm(const void* x, const void* W, const float* bias, const void* resid, void* y, int64_t M, int N, int K, hipStream_t s) {
+int md_gemm(const void* x, const MdLinW& w, const void* resid, void* y, int64_t M, int N, int K, hipStream_t s) {
   const int epi = resid ? EPI_BIAS_RESID : EPI_BIAS;
-  GemmArgs g = linear(x, W, y, M, N, K, epi);
-  g.bias = bias;
+  GemmArgs g = linear(x, w.w, y, M, N, K, epi);
+  g.bias = w.b;
   g.resid = resid;
   return op_gemm(g, epi, gemm_variant_for(VDR_K_GEMM_FC1, M, N), (void*)s, "mask decoder gemm: unsupported shape");
 }
@@ -3538,39 +3426,45 @@ int vdr_mask_decoder_create(const vdr_mask_decoder_config* cfg, int device, vdr_
   if (cfg->mlp_dim <= 0 || cfg->mlp_dim % 64 || cfg->mlp_dim > 2048) return refuse(op, VDR_ERR_UNSUPPORTED, "mlp_dim must be a multiple of 64, at most 2048");
   if (!(cfg->ln_eps > 0.0f) || !(cfg->final_ln_eps > 0.0f) || !(cfg->ln2d_eps > 0.0f)) return refuse(op, VDR_ERR_INVALID, "the eps fields must be positive");
   if (int rc = check_device(nullptr)) return rc;
-  OP_TRY(hipSetDevice(device), "hipSetDevice");
+  DeviceGuard dg(device);  // (only to learn that the device exists)
+  if (!dg.ok) return refuse(op, VDR_ERR_HIP, "hipSetDevice failed");
   MD* d = new MD();
   d->cfg = *cfg;
-  md_names(d);
+  d->device = device;
+  d->table = md_names(cfg->mlp_dim);
+  for (const MdWeightDef& w : d->table) d->n_required += w.group == MD_REQUIRED;
   *out = d;
   return VDR_OK;
 }
 
-void vdr_mask_decoder_destroy(vdr_mask_decoder_handle d) { delete d; }
+void vdr_mask_decoder_destroy(vdr_mask_decoder_handle d) {
+  if (!d) return;
+  DeviceGuard dg(d->device);
+  delete d;  // (the arena frees itself)
+}
 
-int vdr_mask_decoder_num_weights(vdr_mask_decoder_handle d) { return d ? (int)d->names.size() : 0; }
+int vdr_mask_decoder_num_weights(vdr_mask_decoder_handle d) { return d ? d->n_required : 0; }
 
 const char* vdr_mask_decoder_weight_name(vdr_mask_decoder_handle d, int i) {
-  return d && i >= 0 && i < (int)d->names.size() ? d->names[i].c_str() : nullptr;
+  return d && i >= 0 && i < d->n_required ? d->table[i].name.c_str() : nullptr;
 }
+
+int vdr_mask_decoder_num_prompt_weights(vdr_mask_decoder_handle d) { return d ? (int)d->table.size() - d->n_required : 0; }
+
+const char* vdr_mask_decoder_prompt_weight_name(vdr_mask_decoder_handle d, int i) {
+  return i >= 0 && i < vdr_mask_decoder_num_prompt_weights(d) ? d->table[d->n_required + i].name.c_str() : nullptr;
+}
+
+int vdr_mask_decoder_prompt_support(vdr_mask_decoder_handle d) { return d && d->finalized ? d->support : 0; }
 
 int vdr_mask_decoder_set_weight(vdr_mask_decoder_handle d, const char* name, const float* host, const int64_t* shape, int ndim) {
   const char* op = "vdr_mask_decoder_set_weight";
   if (!d || !name || !host || !shape || ndim < 1 || ndim > 4) return refuse(op, VDR_ERR_INVALID, "null or malformed argument");
   if (d->finalized) return refuse(op, VDR_ERR_INVALID, "the decoder is finalized");
-  for (size_t i = 0; i < d->names.size(); ++i)
-    if (d->names[i] == name) {
+  for (const MdWeightDef& w : d->table)
+    if (w.name == name) {
       int64_t want = 1, got = 1;
-      for (int64_t v : d->shapes[i]) want *= v;
-      for (int k = 0; k < ndim; ++k) got *= shape[k];
-      if (got != want) return refuse(op, VDR_ERR_INVALID, std::string(name) + ": element count mismatch");
-      d->host[name].assign(host, host + want);
-      return VDR_OK;
-    }
-  for (size_t i = 0; i < d->pnames.size(); ++i)
-    if (d->pnames[i] == name) {
-      int64_t want = 1, got = 1;
-      for (int64_t v : d->pshapes[i]) want *= v;
+      for (int64_t v : w.shape) want *= v;
       for (int k = 0; k < ndim; ++k) got *= shape[k];
       if (got != want) return refuse(op, VDR_ERR_INVALID, std::string(name) + ": element count mismatch");
       d->host[name].assign(host, host + want);
@@ -3583,145 +3477,30 @@ int vdr_mask_decoder_finalize(vdr_mask_decoder_handle d) {
   const char* op = "vdr_mask_decoder_finalize";
   if (!d) return refuse(op, VDR_ERR_INVALID, "null handle");
   if (d->finalized) return VDR_OK;
-  for (auto& n : d->names)
-    if (!d->host.count(n)) return refuse(op, VDR_ERR_INCOMPLETE, "missing weight " + n);
-  // the optional groups: all of a group or none of it
+  // the required weights, then the optional groups: all of a group or none of it
   int support = 0;
-  for (int grp = 0; grp < 2; ++grp) {
-    const size_t lo = grp ? MD_POINT_WEIGHTS : 0, hi = grp ? d->pnames.size() : MD_POINT_WEIGHTS;
+  for (MdGroup grp : {MD_REQUIRED, MD_POINTS, MD_MASK}) {
     size_t have = 0;
-    for (size_t i = lo; i < hi; ++i) have += d->host.count(d->pnames[i]);
-    if (have == hi - lo) support |= grp ? VDR_PROMPT_MASK : VDR_PROMPT_POINTS;
-    else if (have)
-      for (size_t i = lo; i < hi; ++i)
-        if (!d->host.count(d->pnames[i]))
-          return refuse(op, VDR_ERR_INCOMPLETE, std::string(grp ? "the mask prompt's" : "the point prompts'") + " weights are given in part: missing weight " + d->pnames[i]);
-  }
-  auto& H = d->host;
-  const int g = d->cfg.grid, n = g * g;
-  // the Fourier features of the cell centres, float64: [n, 256]
-  const std::vector<float>& G = H["prompt_encoder.pe_layer.positional_encoding_gaussian_matrix"];
-  std::vector<double> kpe((size_t)n * MD_C);
-  for (int y = 0; y < g; ++y)
-    for (int x = 0; x < g; ++x)
-      for (int f = 0; f < 128; ++f) {
-        const double cx = 2.0 * ((x + 0.5) / g) - 1.0, cy = 2.0 * ((y + 0.5) / g) - 1.0;
-        const double ph = 6.283185307179586476925286766559 * (cx * (double)G[f] + cy * (double)G[128 + f]);
-        kpe[(size_t)(y * g + x) * MD_C + f] = sin(ph);
-        kpe[(size_t)(y * g + x) * MD_C + 128 + f] = cos(ph);
+    const MdWeightDef* missing = nullptr;  // the group's first
+    for (const MdWeightDef& w : d->table)
+      if (w.group == grp) {
+        if (d->host.count(w.name)) ++have;
+        else if (!missing) missing = &w;
       }
-  // pe W^T + b on the bf16-rounded weight the GEMM multiplies with: fp32 [n, 128]
-  auto table = [&](const std::string& p) {
-    const std::vector<float>&W = H[p + ".weight"], &b = H[p + ".bias"];
-    std::vector<double> Wr(W.size());
-    for (size_t i = 0; i < W.size(); ++i) Wr[i] = (double)md_bf16_round(W[i]);
-    std::vector<float> t((size_t)n * MD_IN);
-    for (int r = 0; r < n; ++r)
-      for (int o = 0; o < MD_IN; ++o) {
-        double a = 0.0;
-        for (int k = 0; k < MD_C; ++k) a += kpe[(size_t)r * MD_C + k] * Wr[(size_t)o * MD_C + k];
-        t[(size_t)r * MD_IN + o] = (float)(a + (double)b[o]);
-      }
-    return t;
-  };
-  // ConvTranspose2d weight [Cin, Cout, 2, 2] -> [(dy, dx, Cout), Cin]
-  auto convt = [&](const std::vector<float>& W, int Cin, int Cout) {
-    std::vector<float> o((size_t)4 * Cout * Cin);
-    for (int ci = 0; ci < Cin; ++ci)
-      for (int co = 0; co < Cout; ++co)
-        for (int s = 0; s < 4; ++s) o[((size_t)s * Cout + co) * Cin + ci] = W[((size_t)ci * Cout + co) * 4 + s];
-    return o;
-  };
-  const std::vector<float> z128(MD_IN, 0.0f);
-#define MD_UP(call)            \
-  do {                         \
-    if (int rc = (call)) return rc; \
-  } while (0)
-  MD_UP(md_up_f32(d, "gauss", G));
-  MD_UP(md_up_f32(d, "corner", md_cat({&H["prompt_encoder.point_embeddings.2.weight"], &H["prompt_encoder.point_embeddings.3.weight"]})));
-  MD_UP(md_up_f32(d, "fixed", md_cat({&H["mask_decoder.iou_token.weight"], &H["mask_decoder.mask_tokens.weight"]})));
-  MD_UP(md_up_f32(d, "no_mask", H["prompt_encoder.no_mask_embed.weight"]));
-  auto attn = [&](const std::string& L, const std::string& p) -> int {
-    MD_UP(md_up_bf(d, L + "wq", H[p + "q_proj.weight"]));
-    MD_UP(md_up_f32(d, L + "bq", H[p + "q_proj.bias"]));
-    MD_UP(md_up_bf(d, L + "wo", H[p + "out_proj.weight"]));
-    MD_UP(md_up_f32(d, L + "bo", H[p + "out_proj.bias"]));
-    return VDR_OK;
-  };
-  auto norm = [&](const std::string& L, const std::string& p) -> int {
-    MD_UP(md_up_f32(d, L + "g", H[p + ".weight"]));
-    MD_UP(md_up_f32(d, L + "b", H[p + ".bias"]));
-    return VDR_OK;
-  };
-  for (int i = 0; i < 2; ++i) {
-    const std::string L = "l" + std::to_string(i) + ".", p = "mask_decoder.transformer.layers." + std::to_string(i) + ".";
-    const std::string s = p + "self_attn.", a = p + "cross_attn_token_to_image.", b = p + "cross_attn_image_to_token.";
-    MD_UP(md_up_bf(d, L + "wqk", md_cat({&H[s + "q_proj.weight"], &H[s + "k_proj.weight"]})));
-    MD_UP(md_up_f32(d, L + "bqk", md_cat({&H[s + "q_proj.bias"], &H[s + "k_proj.bias"]})));
-    MD_UP(md_up_bf(d, L + "wv", H[s + "v_proj.weight"]));
-    MD_UP(md_up_f32(d, L + "bv", H[s + "v_proj.bias"]));
-    MD_UP(md_up_bf(d, L + "wo", H[s + "out_proj.weight"]));
-    MD_UP(md_up_f32(d, L + "bo", H[s + "out_proj.bias"]));
-    MD_UP(attn(L + "t2i.", a));
-    // the image side of the block in one GEMM: columns [k of token-to-image | v of token-to-image | q of image-to-token]
-    MD_UP(md_up_bf(d, L + "t2i.wimg", md_cat({&H[a + "k_proj.weight"], &H[a + "v_proj.weight"], &H[b + "q_proj.weight"]})));
-    MD_UP(md_up_f32(d, L + "t2i.bimg", md_cat({&z128, &H[a + "v_proj.bias"], &z128})));
-    MD_UP(md_up_f32(d, L + "t2i.ktab", table(a + "k_proj")));
-    MD_UP(md_up_f32(d, L + "qtab", table(b + "q_proj")));
-    MD_UP(md_up_bf(d, L + "w1", H[p + "mlp.lin1.weight"]));
-    MD_UP(md_up_f32(d, L + "b1", H[p + "mlp.lin1.bias"]));
-    MD_UP(md_up_bf(d, L + "w2", H[p + "mlp.lin2.weight"]));
-    MD_UP(md_up_f32(d, L + "b2", H[p + "mlp.lin2.bias"]));
-    MD_UP(md_up_bf(d, L + "wk2", H[b + "k_proj.weight"]));
-    MD_UP(md_up_f32(d, L + "bk2", H[b + "k_proj.bias"]));
-    MD_UP(md_up_bf(d, L + "wv2", H[b + "v_proj.weight"]));
-    MD_UP(md_up_f32(d, L + "bv2", H[b + "v_proj.bias"]));
-    MD_UP(md_up_bf(d, L + "wo2", H[b + "out_proj.weight"]));
-    MD_UP(md_up_f32(d, L + "bo2", H[b + "out_proj.bias"]));
-    for (int j = 1; j <= 4; ++j) MD_UP(norm(L + "n" + std::to_string(j), p + "norm" + std::to_string(j)));
+    if (grp == MD_REQUIRED && missing) return refuse(op, VDR_ERR_INCOMPLETE, "missing weight " + missing->name);
+    if (grp != MD_REQUIRED && !missing) support |= grp == MD_MASK ? VDR_PROMPT_MASK : VDR_PROMPT_POINTS;
+    if (grp != MD_REQUIRED && missing && have)
+      return refuse(op, VDR_ERR_INCOMPLETE, std::string(grp == MD_MASK ? "the mask prompt's" : "the point prompts'") + " weights are given in part: missing weight " + missing->name);
   }
-  {
-    const std::string f = "mask_decoder.transformer.final_attn_token_to_image.";
-    MD_UP(attn("f.", f));
-    MD_UP(md_up_bf(d, "f.wimg", md_cat({&H[f + "k_proj.weight"], &H[f + "v_proj.weight"]})));
-    MD_UP(md_up_f32(d, "f.bimg", md_cat({&z128, &H[f + "v_proj.bias"]})));
-    MD_UP(md_up_f32(d, "f.ktab", table(f + "k_proj")));
-    MD_UP(norm("f.n", "mask_decoder.transformer.norm_final_attn"));
-  }
-  {
-    const std::string U = "mask_decoder.output_upscaling.";
-    MD_UP(md_up_bf(d, "up1.w", convt(H[U + "0.weight"], MD_C, 64)));
-    const std::vector<float>& b1 = H[U + "0.bias"];
-    MD_UP(md_up_f32(d, "up1.b", md_cat({&b1, &b1, &b1, &b1})));
-    MD_UP(norm("up.n", U + "1"));
-    MD_UP(md_up_bf(d, "up2.w", convt(H[U + "3.weight"], 64, 32)));
-    MD_UP(md_up_f32(d, "up2.b", H[U + "3.bias"]));
-  }
-  for (int j = 0; j < 3; ++j) {
-    std::vector<float> w, b;
-    for (int m = 0; m < 4; ++m) {
-      const std::string p = "mask_decoder.output_hypernetworks_mlps." + std::to_string(m) + ".layers." + std::to_string(j);
-      w.insert(w.end(), H[p + ".weight"].begin(), H[p + ".weight"].end());
-      b.insert(b.end(), H[p + ".bias"].begin(), H[p + ".bias"].end());
-    }
-    MD_UP(md_up_bf(d, "hy" + std::to_string(j) + ".w", w));
-    MD_UP(md_up_f32(d, "hy" + std::to_string(j) + ".b", b));
-    const std::string p = "mask_decoder.iou_prediction_head.layers." + std::to_string(j);
-    MD_UP(md_up_bf(d, "iou" + std::to_string(j) + ".w", H[p + ".weight"]));
-    MD_UP(md_up_f32(d, "iou" + std::to_string(j) + ".b", H[p + ".bias"]));
-  }
-  if (support & VDR_PROMPT_POINTS) {
-    MD_UP(md_up_f32(d, "pt_emb", md_cat({&H["prompt_encoder.point_embeddings.0.weight"], &H["prompt_encoder.point_embeddings.1.weight"]})));
-    MD_UP(md_up_f32(d, "nap", H["prompt_encoder.not_a_point_embed.weight"]));
-  }
-  if (support & VDR_PROMPT_MASK) {  // fp32 on the device: 4.4 K values
-    const std::string m = "prompt_encoder.mask_downscaling.";
-    const std::vector<float> w = md_cat({&H[m + "0.weight"], &H[m + "0.bias"], &H[m + "1.weight"], &H[m + "1.bias"], &H[m + "3.weight"],
-                                         &H[m + "3.bias"], &H[m + "4.weight"], &H[m + "4.bias"], &H[m + "6.weight"], &H[m + "6.bias"]});
-    if ((int)w.size() != VDR_MASK_EMBED_WEIGHTS) return refuse(op, VDR_ERR_INCOMPLETE, "internal: the packed mask-prompt weights");
-    MD_UP(md_up_f32(d, "md.w", w));  // vdr_op_mask_embed's `weights`
-  }
-#undef MD_UP
+  DeviceGuard dg(d->device);
+  if (!dg.ok) return refuse(op, VDR_ERR_HIP, "hipSetDevice failed");
+  // one staging vector, one allocation, one copy; then every field of d->w is pointed at its offset
+  const MdPacked pk = md_pack(d->cfg, d->host, support, d->w);
+  DevBuf arena;
+  OP_TRY(arena.alloc(pk.bytes.size()), "hipMalloc(mask decoder weights)");
+  OP_TRY(hipMemcpy(arena.get(), pk.bytes.data(), pk.bytes.size(), hipMemcpyHostToDevice), "hipMemcpy(mask decoder weights)");
+  pk.publish(arena.get());
+  d->arena = std::move(arena);
   d->support = support;
   d->host.clear();
   d->finalized = true;
@@ -3736,40 +3515,53 @@ int vdr_mask_decoder_workspace_bytes(vdr_mask_decoder_handle d, int problems, si
   return VDR_OK;
 }
 
+int vdr_mask_decoder_workspace_bytes_prompts(vdr_mask_decoder_handle d, int problems, int tokens, size_t* out) {
+  const char* op = "vdr_mask_decoder_workspace_bytes_prompts";
+  if (!out) return refuse(op, VDR_ERR_INVALID, "null argument");
+  if (tokens < 6) return refuse(op, VDR_ERR_INVALID, "a decode has at least 6 tokens per problem");
+  if (tokens > MD_MAX_T) return refuse(op, VDR_ERR_UNSUPPORTED, "at most " + std::to_string(MD_MAX_T) + " tokens per problem");
+  if (!d) return refuse(op, VDR_ERR_INVALID, "null handle");
+  if (problems <= 0 || problems > 65535) return refuse(op, VDR_ERR_INVALID, "problems must be 1 .. 65535");
+  *out = md_carve(d, problems, tokens).total;
+  return VDR_OK;
+}
+
 }  // extern "C"
 
 namespace {
 
-// the chain of launches both decode entry points run; pr == nullptr: vdr_mask_decode's own set-up (boxes, T = 7)
+// What both decode entry points ask of their common arguments, refused in this order before the device is touched; pr ==
+// nullptr: vdr_mask_decode (boxes alone, T = 7)
+int md_check(const char* op, const MD* d, const float* emb, int channels_last, const float* boxes, const vdr_mask_prompts* pr, int T, int batch,
+             int boxes_per_image, const void* workspace, size_t workspace_bytes, const float* logits, const float* iou) {
+  if (!d || !emb || (!pr && !boxes) || !workspace || !logits || !iou) return refuse(op, VDR_ERR_INVALID, "null argument");
+  if (channels_last != 0 && channels_last != 1) return refuse(op, VDR_ERR_INVALID, "channels_last must be 0 or 1");
+  if (batch <= 0 || boxes_per_image <= 0 || (int64_t)batch * boxes_per_image > 65535)
+    return refuse(op, VDR_ERR_INVALID, "batch and boxes_per_image must be positive, at most 65535 problems");
+  if (pr) boxes = pr->boxes;
+  if (!aligned16({emb, boxes, pr ? pr->points : nullptr, pr ? pr->labels : nullptr, pr ? pr->mask_input : nullptr, workspace, logits, iou}))
+    return refuse(op, VDR_ERR_INVALID, "pointers must be 16-byte aligned");
+  if (!d->finalized) return refuse(op, VDR_ERR_INCOMPLETE, "vdr_mask_decoder_finalize has not run");
+  if (pr && (pr->points || !pr->boxes) && !(d->support & VDR_PROMPT_POINTS))
+    return refuse(op, VDR_ERR_UNSUPPORTED, "point prompts (and the padding point of a decode without boxes) need point_embeddings.{0,1} and not_a_point_embed");
+  if (pr && pr->mask_input && !(d->support & VDR_PROMPT_MASK)) return refuse(op, VDR_ERR_UNSUPPORTED, "a mask prompt needs the mask_downscaling weights");
+  const MdCarve c = md_carve(d, (int64_t)batch * boxes_per_image, T);
+  if (workspace_bytes < c.total) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(c.total) + " bytes needed");
+  return VDR_OK;
+}
+
+// the chain of launches both decode entry points run, on the handle's device; pr == nullptr: vdr_mask_decode's own set-up
 int md_run(const char* op, MD* d, const float* emb, int channels_last, const float* boxes, const vdr_mask_prompts* pr, int T, int batch,
            int boxes_per_image, void* workspace, float* logits, float* iou, void* stream) {
   const int P = batch * boxes_per_image, g = d->cfg.grid, n = g * g, C = MD_C, F = d->cfg.mlp_dim;
   const MdCarve c = md_carve(d, P, T);
   if (int rc = check_device(nullptr)) return rc;
+  DeviceGuard dg(d->device);
+  if (!dg.ok) return refuse(op, VDR_ERR_HIP, "hipSetDevice failed");
+  const bool pts = pr && (pr->points || !pr->boxes);  // (a decode without boxes carries a padding point)
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
-  bool missing = false;  // (a label finalize did not build: an internal error, reported instead of thrown across the C boundary)
-  auto W = [&](const std::string& k) {
-    auto it = d->dev.find(k);
-    if (it == d->dev.end()) missing = true;
-    return it == d->dev.end() ? (const void*)nullptr : (const void*)it->second;
-  };
-  auto Fp = [&](const std::string& k) { return (const float*)W(k); };
-  if (pr && (pr->points || !pr->boxes)) (void)W("pt_emb"), (void)W("nap");
-  if (pr && pr->mask_input) (void)W("md.w");
-  for (const char* k : {"fixed", "gauss", "corner", "no_mask", "up1.w", "up1.b", "up.ng", "up.nb", "up2.w", "up2.b", "f.wq", "f.bq", "f.wo", "f.bo", "f.wimg",
-                        "f.bimg", "f.ktab", "f.ng", "f.nb"})
-    (void)W(k);
-  for (int i = 0; i < 2; ++i) {
-    const std::string L = "l" + std::to_string(i) + ".";
-    for (const char* k : {"wqk", "bqk", "wv", "bv", "wo", "bo", "t2i.wq", "t2i.bq", "t2i.wo", "t2i.bo", "t2i.wimg", "t2i.bimg", "t2i.ktab", "qtab", "w1", "b1",
-                          "w2", "b2", "wk2", "bk2", "wv2", "bv2", "wo2", "bo2", "n1g", "n1b", "n2g", "n2b", "n3g", "n3b", "n4g", "n4b"})
-      (void)W(L + k);
-  }
-  for (int j = 0; j < 3; ++j)
-    for (const char* k : {"hy", "iou"})
-      for (const char* t : {".w", ".b"}) (void)W(std::string(k) + std::to_string(j) + t);
-  if (missing) return refuse(op, VDR_ERR_INCOMPLETE, "internal: a finalized buffer is missing");
+  const MdWeights& w = d->w;
   void *pe = ws + c.pe, *tok = ws + c.tok, *tmp = ws + c.tmp, *qkv = ws + c.qkv, *att = ws + c.att, *q = ws + c.q, *kv2 = ws + c.kv2, *h = ws + c.h;
   void *keys = ws + c.keys, *keys2 = ws + c.keys2, *img = ws + c.img, *atti = ws + c.atti, *up = ws + c.up, *up2 = ws + c.up2;
   auto bfp = [](void* p, int64_t off) { return (void*)((char*)p + 2 * off); };
@@ -3780,98 +3572,71 @@ int md_run(const char* op, MD* d, const float* emb, int channels_last, const flo
   } while (0)
   // tokens (also the query pe) and keys
   if (!pr) {
-    MD_L(launch_decoder_setup(boxes, Fp("fixed"), Fp("gauss"), Fp("corner"), emb, channels_last, Fp("no_mask"), pe, keys, batch, boxes_per_image, g,
-                              (float)d->cfg.img, s), "decoder_setup");
+    MD_L(launch_decoder_setup(boxes, w.fixed, w.gauss, w.corner, emb, channels_last, w.no_mask, pe, keys, batch, boxes_per_image, g, (float)d->cfg.img, s),
+         "decoder_setup");
   } else {
-    const bool pts = pr->points || !pr->boxes;
-    MD_L(launch_prompt_tokens(pr->boxes, pr->points, pr->labels, pr->points ? pr->points_per_problem : 0, Fp("fixed"), Fp("gauss"), Fp("corner"),
-                              pts ? Fp("pt_emb") : nullptr, pts ? Fp("nap") : nullptr, pe, P, T, (float)d->cfg.img, s), "prompt_tokens");
+    MD_L(launch_prompt_tokens(pr->boxes, pr->points, pr->labels, pr->points ? pr->points_per_problem : 0, w.fixed, w.gauss, w.corner,
+                              pts ? w.pt_emb : nullptr, pts ? w.nap : nullptr, pe, P, T, (float)d->cfg.img, s), "prompt_tokens");
     if (pr->mask_input)
-      MD_L(launch_mask_embed(emb, channels_last, pr->mask_input, pr->mask_per_image, Fp("md.w"), Fp("md.w") + MASK_EMBED_SMALL, Fp("md.w") + MASK_EMBED_SMALL + 16 * MD_C, keys, P,
+      MD_L(launch_mask_embed(emb, channels_last, pr->mask_input, pr->mask_per_image, w.mask_w, w.mask_w + MASK_EMBED_SMALL, w.mask_w + MASK_EMBED_SMALL + 16 * MD_C, keys, P,
                              boxes_per_image, g, d->cfg.ln2d_eps, s), "mask_embed");
     else
-      MD_L(launch_decoder_keys(emb, channels_last, Fp("no_mask"), keys, batch, boxes_per_image, g, s), "decoder_keys");
+      MD_L(launch_decoder_keys(emb, channels_last, w.no_mask, keys, batch, boxes_per_image, g, s), "decoder_keys");
   }
   const void* cur = pe;  // the tokens of layer 0 are the initial ones
-  auto tl = [&](const void* x, int64_t ldx, const void* xadd, const std::string& w, const std::string& b, const void* resid, void* y, int f32out,
-                int64_t ldy, int M, int N, int K, int groups, int relu, int rpg = 0, int64_t gs = 0) {
-    return launch_token_linear(x, ldx, xadd, C, W(w), Fp(b), resid, C, y, f32out, ldy, M, N, K, groups, relu, s, rpg, gs);
+  auto tl = [&](const void* x, int64_t ldx, const void* xadd, const MdLinW& l, const void* resid, void* y, int f32out, int64_t ldy, int M, int N, int K,
+                int groups, int relu, int rpg = 0, int64_t gs = 0) {
+    return launch_token_linear(x, ldx, xadd, C, l.w, l.b, resid, C, y, f32out, ldy, M, N, K, groups, relu, s, rpg, gs);
   };
   // token -> image attention with its out-projection, residual and norm; leaves the new tokens in `tok`
-  auto t2i = [&](const std::string& L, int ncols, const std::string& ng, const std::string& nbeta, float eps) -> int {
-    MD_L(tl(cur, C, pe, L + "wq", L + "bq", nullptr, q, 0, MD_IN, T * P, MD_IN, C, 1, 0), "token_linear");
-    MD_R(md_gemm(keys, W(L + "wimg"), Fp(L + "bimg"), nullptr, img, (int64_t)P * n, ncols, C, s));
-    MD_L(launch_cross_attention(q, MD_IN, nullptr, img, ncols, Fp(L + "ktab"), bfp(img, MD_IN), ncols, att, MD_IN, P, T, n, 8, 16, s), "cross_attention");
-    MD_L(tl(att, MD_IN, nullptr, L + "wo", L + "bo", cur, tmp, 0, C, T * P, C, MD_IN, 1, 0), "token_linear");
-    MD_R(md_ln(tmp, tok, Fp(ng), Fp(nbeta), (int64_t)T * P, C, eps, s));
+  auto t2i = [&](const MdAttnW& a, int ncols, const MdNormW& norm, float eps) -> int {
+    MD_L(tl(cur, C, pe, a.q, nullptr, q, 0, MD_IN, T * P, MD_IN, C, 1, 0), "token_linear");
+    MD_R(md_gemm(keys, a.img, nullptr, img, (int64_t)P * n, ncols, C, s));
+    MD_L(launch_cross_attention(q, MD_IN, nullptr, img, ncols, a.ktab, bfp(img, MD_IN), ncols, att, MD_IN, P, T, n, 8, 16, s), "cross_attention");
+    MD_L(tl(att, MD_IN, nullptr, a.o, cur, tmp, 0, C, T * P, C, MD_IN, 1, 0), "token_linear");
+    MD_R(md_ln(tmp, tok, norm, (int64_t)T * P, C, eps, s));
     cur = tok;
     return VDR_OK;
   };
   for (int i = 0; i < 2; ++i) {
-    const std::string L = "l" + std::to_string(i) + ".";
-    MD_L(tl(cur, C, i ? pe : nullptr, L + "wqk", L + "bqk", nullptr, qkv, 0, 3 * C, T * P, 2 * C, C, 1, 0), "token_linear");
-    MD_L(tl(cur, C, nullptr, L + "wv", L + "bv", nullptr, bfp(qkv, 2 * C), 0, 3 * C, T * P, C, C, 1, 0), "token_linear");
+    const MdBlockW& L = w.l[i];
+    MD_L(tl(cur, C, i ? pe : nullptr, L.qk, nullptr, qkv, 0, 3 * C, T * P, 2 * C, C, 1, 0), "token_linear");
+    MD_L(tl(cur, C, nullptr, L.v, nullptr, bfp(qkv, 2 * C), 0, 3 * C, T * P, C, C, 1, 0), "token_linear");
     MD_L(launch_cross_attention(qkv, 3 * C, nullptr, bfp(qkv, C), 3 * C, nullptr, bfp(qkv, 2 * C), 3 * C, att, C, P, T, T, 8, 32, s), "cross_attention");
-    MD_L(tl(att, C, nullptr, L + "wo", L + "bo", i ? cur : nullptr, tmp, 0, C, T * P, C, C, 1, 0), "token_linear");
-    MD_R(md_ln(tmp, tok, Fp(L + "n1g"), Fp(L + "n1b"), (int64_t)T * P, C, d->cfg.ln_eps, s));
+    MD_L(tl(att, C, nullptr, L.o, i ? cur : nullptr, tmp, 0, C, T * P, C, C, 1, 0), "token_linear");
+    MD_R(md_ln(tmp, tok, L.n1, (int64_t)T * P, C, d->cfg.ln_eps, s));
     cur = tok;
-    MD_R(t2i(L + "t2i.", 3 * MD_IN, L + "n2g", L + "n2b", d->cfg.ln_eps));
-    MD_L(tl(tok, C, nullptr, L + "w1", L + "b1", nullptr, h, 0, F, T * P, F, C, 1, 1), "token_linear");
-    MD_L(tl(h, F, nullptr, L + "w2", L + "b2", tok, tmp, 0, C, T * P, C, F, 1, 0), "token_linear");
-    MD_R(md_ln(tmp, tok, Fp(L + "n3g"), Fp(L + "n3b"), (int64_t)T * P, C, d->cfg.ln_eps, s));
-    MD_L(tl(tok, C, pe, L + "wk2", L + "bk2", nullptr, kv2, 0, 2 * MD_IN, T * P, MD_IN, C, 1, 0), "token_linear");
-    MD_L(tl(tok, C, nullptr, L + "wv2", L + "bv2", nullptr, bfp(kv2, MD_IN), 0, 2 * MD_IN, T * P, MD_IN, C, 1, 0), "token_linear");
-    MD_L(launch_cross_attention(bfp(img, 2 * MD_IN), 3 * MD_IN, Fp(L + "qtab"), kv2, 2 * MD_IN, nullptr, bfp(kv2, MD_IN), 2 * MD_IN, atti, MD_IN, P, n, T,
-                                8, 16, s), "cross_attention");
-    MD_R(md_gemm(atti, W(L + "wo2"), Fp(L + "bo2"), keys, keys2, (int64_t)P * n, C, MD_IN, s));
-    MD_R(md_ln(keys2, keys, Fp(L + "n4g"), Fp(L + "n4b"), (int64_t)P * n, C, d->cfg.ln_eps, s));
+    MD_R(t2i(L.t2i, 3 * MD_IN, L.n2, d->cfg.ln_eps));
+    MD_L(tl(tok, C, nullptr, L.fc1, nullptr, h, 0, F, T * P, F, C, 1, 1), "token_linear");
+    MD_L(tl(h, F, nullptr, L.fc2, tok, tmp, 0, C, T * P, C, F, 1, 0), "token_linear");
+    MD_R(md_ln(tmp, tok, L.n3, (int64_t)T * P, C, d->cfg.ln_eps, s));
+    MD_L(tl(tok, C, pe, L.k2, nullptr, kv2, 0, 2 * MD_IN, T * P, MD_IN, C, 1, 0), "token_linear");
+    MD_L(tl(tok, C, nullptr, L.v2, nullptr, bfp(kv2, MD_IN), 0, 2 * MD_IN, T * P, MD_IN, C, 1, 0), "token_linear");
+    MD_L(launch_cross_attention(bfp(img, 2 * MD_IN), 3 * MD_IN, L.qtab, kv2, 2 * MD_IN, nullptr, bfp(kv2, MD_IN), 2 * MD_IN, atti, MD_IN, P, n, T, 8, 16, s),
+         "cross_attention");
+    MD_R(md_gemm(atti, L.o2, keys, keys2, (int64_t)P * n, C, MD_IN, s));
+    MD_R(md_ln(keys2, keys, L.n4, (int64_t)P * n, C, d->cfg.ln_eps, s));
   }
-  MD_R(t2i("f.", 2 * MD_IN, "f.ng", "f.nb", d->cfg.final_ln_eps));
+  MD_R(t2i(w.f, 2 * MD_IN, w.fn, d->cfg.final_ln_eps));
   // upscaling: the first transposed convolution as a linear, LayerNorm2d over the 64 channels of each of its 4 sub-pixels
-  MD_R(md_gemm(keys, W("up1.w"), Fp("up1.b"), nullptr, up, (int64_t)P * n, C, C, s));
-  MD_R(md_ln(up, up2, Fp("up.ng"), Fp("up.nb"), (int64_t)P * n * 4, 64, d->cfg.ln2d_eps, s));
+  MD_R(md_gemm(keys, w.up1, nullptr, up, (int64_t)P * n, C, C, s));
+  MD_R(md_ln(up, up2, w.up_n, (int64_t)P * n * 4, 64, d->cfg.ln2d_eps, s));
   // the hypernetworks on the mask tokens (rows p * 7 + 1 + m of tok), the IoU head on the IoU token (row p * 7)
   void *hx1 = ws + c.hx1, *hx2 = ws + c.hx2, *hyper = ws + c.hyper, *ix1 = ws + c.ix1, *ix2 = ws + c.ix2;
-  MD_L(tl(bfp(tok, C), C, nullptr, "hy0.w", "hy0.b", nullptr, hx1, 0, C, 4 * P, C, C, 4, 1, 4, (int64_t)T * C), "token_linear");
-  MD_L(tl(hx1, C, nullptr, "hy1.w", "hy1.b", nullptr, hx2, 0, C, 4 * P, C, C, 4, 1), "token_linear");
-  MD_L(tl(hx2, C, nullptr, "hy2.w", "hy2.b", nullptr, hyper, 1, 32, 4 * P, 32, C, 4, 0), "token_linear");
-  MD_L(tl(tok, (int64_t)T * C, nullptr, "iou0.w", "iou0.b", nullptr, ix1, 0, C, P, C, C, 1, 1), "token_linear");
-  MD_L(tl(ix1, C, nullptr, "iou1.w", "iou1.b", nullptr, ix2, 0, C, P, C, C, 1, 1), "token_linear");
-  MD_L(tl(ix2, C, nullptr, "iou2.w", "iou2.b", nullptr, iou, 1, 4, P, 4, C, 1, 0), "token_linear");
-  MD_L(launch_mask_upscale(up2, W("up2.w"), Fp("up2.b"), (const float*)hyper, logits, P, g, 1, s), "mask_upscale");
+  MD_L(tl(bfp(tok, C), C, nullptr, w.hy[0], nullptr, hx1, 0, C, 4 * P, C, C, 4, 1, 4, (int64_t)T * C), "token_linear");
+  MD_L(tl(hx1, C, nullptr, w.hy[1], nullptr, hx2, 0, C, 4 * P, C, C, 4, 1), "token_linear");
+  MD_L(tl(hx2, C, nullptr, w.hy[2], nullptr, hyper, 1, 32, 4 * P, 32, C, 4, 0), "token_linear");
+  MD_L(tl(tok, (int64_t)T * C, nullptr, w.iou[0], nullptr, ix1, 0, C, P, C, C, 1, 1), "token_linear");
+  MD_L(tl(ix1, C, nullptr, w.iou[1], nullptr, ix2, 0, C, P, C, C, 1, 1), "token_linear");
+  MD_L(tl(ix2, C, nullptr, w.iou[2], nullptr, iou, 1, 4, P, 4, C, 1, 0), "token_linear");
+  MD_L(launch_mask_upscale(up2, w.up2.w, w.up2.b, (const float*)hyper, logits, P, g, 1, s), "mask_upscale");
 #undef MD_L
 #undef MD_R
   return VDR_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int vdr_mask_decode(vdr_mask_decoder_handle d, const float* emb, int channels_last, const float* boxes, int batch, int boxes_per_image,
-                    void* workspace, size_t workspace_bytes, float* logits, float* iou, void* stream) {
-  const char* op = "vdr_mask_decode";
-  if (!d || !emb || !boxes || !workspace || !logits || !iou) return refuse(op, VDR_ERR_INVALID, "null argument");
-  if (channels_last != 0 && channels_last != 1) return refuse(op, VDR_ERR_INVALID, "channels_last must be 0 or 1");
-  if (batch <= 0 || boxes_per_image <= 0 || (int64_t)batch * boxes_per_image > 65535)
-    return refuse(op, VDR_ERR_INVALID, "batch and boxes_per_image must be positive, at most 65535 problems");
-  if (!aligned16({emb, boxes, workspace, logits, iou})) return refuse(op, VDR_ERR_INVALID, "pointers must be 16-byte aligned");
-  if (!d->finalized) return refuse(op, VDR_ERR_INCOMPLETE, "vdr_mask_decoder_finalize has not run");
-  const MdCarve c = md_carve(d, (int64_t)batch * boxes_per_image);
-  if (workspace_bytes < c.total) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(c.total) + " bytes needed");
-  return md_run(op, d, emb, channels_last, boxes, nullptr, MD_T, batch, boxes_per_image, workspace, logits, iou, stream);
-}
-
-int vdr_mask_decoder_num_prompt_weights(vdr_mask_decoder_handle d) { return d ? (int)d->pnames.size() : 0; }
-
-const char* vdr_mask_decoder_prompt_weight_name(vdr_mask_decoder_handle d, int i) {
-  return d && i >= 0 && i < (int)d->pnames.size() ? d->pnames[i].c_str() : nullptr;
-}
-
-int vdr_mask_decoder_prompt_support(vdr_mask_decoder_handle d) { return d && d->finalized ? d->support : 0; }
-
 // the prompts alone: what can be refused without a handle comes first (tests/test_sam_prompts_cpu.py has no device to make one with)
-static int md_check_prompts(const char* op, const vdr_mask_prompts* pr, int* tokens) {
+int md_check_prompts(const char* op, const vdr_mask_prompts* pr, int* tokens) {
   if (!pr) return refuse(op, VDR_ERR_INVALID, "null prompts");
   if (!pr->boxes && !pr->points) return refuse(op, VDR_ERR_INVALID, "at least one of boxes and points must be given");
   if (pr->points && (!pr->labels || pr->points_per_problem <= 0))
@@ -3884,15 +3649,15 @@ static int md_check_prompts(const char* op, const vdr_mask_prompts* pr, int* tok
   return VDR_OK;
 }
 
-int vdr_mask_decoder_workspace_bytes_prompts(vdr_mask_decoder_handle d, int problems, int tokens, size_t* out) {
-  const char* op = "vdr_mask_decoder_workspace_bytes_prompts";
-  if (!out) return refuse(op, VDR_ERR_INVALID, "null argument");
-  if (tokens < 6) return refuse(op, VDR_ERR_INVALID, "a decode has at least 6 tokens per problem");
-  if (tokens > MD_MAX_T) return refuse(op, VDR_ERR_UNSUPPORTED, "at most " + std::to_string(MD_MAX_T) + " tokens per problem");
-  if (!d) return refuse(op, VDR_ERR_INVALID, "null handle");
-  if (problems <= 0 || problems > 65535) return refuse(op, VDR_ERR_INVALID, "problems must be 1 .. 65535");
-  *out = md_carve(d, problems, tokens).total;
-  return VDR_OK;
+}  // namespace
+
+extern "C" {
+
+int vdr_mask_decode(vdr_mask_decoder_handle d, const float* emb, int channels_last, const float* boxes, int batch, int boxes_per_image,
+                    void* workspace, size_t workspace_bytes, float* logits, float* iou, void* stream) {
+  const char* op = "vdr_mask_decode";
+  if (int rc = md_check(op, d, emb, channels_last, boxes, nullptr, MD_T, batch, boxes_per_image, workspace, workspace_bytes, logits, iou)) return rc;
+  return md_run(op, d, emb, channels_last, boxes, nullptr, MD_T, batch, boxes_per_image, workspace, logits, iou, stream);
 }
 
 int vdr_mask_decode_prompts(vdr_mask_decoder_handle d, const float* emb, int channels_last, const vdr_mask_prompts* prompts, int batch,
@@ -3900,20 +3665,9 @@ int vdr_mask_decode_prompts(vdr_mask_decoder_handle d, const float* emb, int cha
   const char* op = "vdr_mask_decode_prompts";
   int T = 0;
   if (int rc = md_check_prompts(op, prompts, &T)) return rc;
-  if (!d || !emb || !workspace || !logits || !iou) return refuse(op, VDR_ERR_INVALID, "null argument");
-  if (channels_last != 0 && channels_last != 1) return refuse(op, VDR_ERR_INVALID, "channels_last must be 0 or 1");
-  if (batch <= 0 || boxes_per_image <= 0 || (int64_t)batch * boxes_per_image > 65535)
-    return refuse(op, VDR_ERR_INVALID, "batch and boxes_per_image must be positive, at most 65535 problems");
-  if (!aligned16({emb, prompts->boxes, prompts->points, prompts->labels, prompts->mask_input, workspace, logits, iou}))
-    return refuse(op, VDR_ERR_INVALID, "pointers must be 16-byte aligned");
-  if (!d->finalized) return refuse(op, VDR_ERR_INCOMPLETE, "vdr_mask_decoder_finalize has not run");
-  if ((prompts->points || !prompts->boxes) && !(d->support & VDR_PROMPT_POINTS))
-    return refuse(op, VDR_ERR_UNSUPPORTED, "point prompts (and the padding point of a decode without boxes) need point_embeddings.{0,1} and not_a_point_embed");
-  if (prompts->mask_input && !(d->support & VDR_PROMPT_MASK))
-    return refuse(op, VDR_ERR_UNSUPPORTED, "a mask prompt needs the mask_downscaling weights");
-  const MdCarve c = md_carve(d, (int64_t)batch * boxes_per_image, T);
-  if (workspace_bytes < c.total) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(c.total) + " bytes needed");
+  if (int rc = md_check(op, d, emb, channels_last, nullptr, prompts, T, batch, boxes_per_image, workspace, workspace_bytes, logits, iou)) return rc;
   return md_run(op, d, emb, channels_last, nullptr, prompts, T, batch, boxes_per_image, workspace, logits, iou, stream);
 }
 
 }  // extern "C"
+

@@ -197,21 +197,23 @@ class MaskDecoder:
         h = C.c_void_p()
         L.check(self.lib.vdr_mask_decoder_create(C.byref(cfg), self.device.index or 0, C.byref(h)))
         self.h = h
+
+        def set_weight(name):
+            t = torch.as_tensor(weights[name]).detach().to(torch.float32).contiguous().cpu()
+            shape = (C.c_int64 * t.dim())(*t.shape)
+            L.check(self.lib.vdr_mask_decoder_set_weight(h, name.encode(), t.data_ptr(), shape, t.dim()))
+
         for i in range(self.lib.vdr_mask_decoder_num_weights(h)):
             name = self.lib.vdr_mask_decoder_weight_name(h, i).decode()
             if name not in weights:
                 raise ValueError(f"mask decoder: the checkpoint has no {name}")
-            t = torch.as_tensor(weights[name]).detach().to(torch.float32).contiguous().cpu()
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            L.check(self.lib.vdr_mask_decoder_set_weight(h, name.encode(), t.data_ptr(), shape, t.dim()))
+            set_weight(name)
         # the optional prompt weights: a group is set when the checkpoint holds all of it
         opt = [self.lib.vdr_mask_decoder_prompt_weight_name(h, i).decode() for i in range(self.lib.vdr_mask_decoder_num_prompt_weights(h))]
         for group in (opt[:3], opt[3:]):
             if all(n in weights for n in group):
                 for name in group:
-                    t = torch.as_tensor(weights[name]).detach().to(torch.float32).contiguous().cpu()
-                    shape = (C.c_int64 * t.dim())(*t.shape)
-                    L.check(self.lib.vdr_mask_decoder_set_weight(h, name.encode(), t.data_ptr(), shape, t.dim()))
+                    set_weight(name)
         L.check(self.lib.vdr_mask_decoder_finalize(h))
         support = self.lib.vdr_mask_decoder_prompt_support(h)
         self.has_point_prompts, self.has_mask_prompt = bool(support & L.PROMPT_POINTS), bool(support & L.PROMPT_MASK)
