@@ -873,6 +873,71 @@ size_t vdr_nms_workspace_bytes(int n);
 int vdr_op_nms(const float* boxes, const int32_t* order, int n, float iou_threshold, void* workspace, size_t workspace_bytes, uint8_t* keep,
                int32_t* kept, int32_t* count, void* stream);
 
+/* ---- connected components of mask planes (csrc/components.hip, csrc/components_map.h).
+ *
+ * A plane is H x W uint8, nonzero = set, H and W in 1 .. 4096, pixel index i = y * W + x.  connectivity is 4 (edge neighbours) or
+ * 8 (edge and corner neighbours).  value selects the pixels whose components are taken: 1 the set pixels, 0 the clear pixels
+ * (the complement: holes and background).  The ROOT of a selected pixel is the lowest pixel index of its component; a pixel that
+ * is not selected has root -1.  The AREA of a component is its pixel count.  Both are functions of the partition alone: every
+ * correct algorithm, and every order in which workgroups run, gives the same integers.  Labels 1, 2, .. in the order of the
+ * components' first pixels (scipy.ndimage.label's numbering) are the rank of the root among the roots (vdr.components.relabel).
+ *
+ * vdr_op_mask_binarize: planes of fp32 logits H x W, addressed as vdr_op_mask_stats addresses them (plane_stride,
+ *   planes_per_group, group_stride), -> out uint8 [planes, oh, ow]: 1 where the bilinear align_corners=False up-sampling is
+ *   > threshold, else 0 (a NaN gives 0).  The arithmetic is vdr_op_mask_stats', operation for operation (the same ms_axis, the same
+ *   blend order, no contraction): the set pixels are exactly the ones mask_stats counts as v > threshold and boxes.  One launch.
+ *   It accepts the shapes vdr_mask_stats_workspace_bytes accepts; the workspace is never read or written -- pointer and size are only
+ *   checked, so that the call has the shape of the other ops (vdr_mask_binarize_workspace_bytes
+ *   is 16 for an accepted shape, 0 for a refused one; fewer bytes: VDR_ERR_WORKSPACE).  Refused (VDR_ERR_INVALID): null pointers,
+ *   logits not 4-byte aligned, H, W outside 1 .. 256, oh, ow outside 1 .. 4096, planes outside 1 .. 65535 or no multiple of
+ *   planes_per_group, plane_stride < H W, overlapping groups, a NaN threshold.
+ *
+ * vdr_op_connected_components: mask uint8 [planes, H, W] ->
+ *   root   int32 [planes, H, W]   the root of each pixel (-1: not selected)
+ *   area   int32 [planes, H, W]   the component's area at its root pixel, 0 everywhere else
+ *   count  int32 [planes]         the number of components
+ *   Three launches: 64 x 64 tiles labelled in LDS by union-find; unions across the seams between tiles (find + integer atomicMin
+ *   on the label plane); every pixel follows its chain to the root, tile areas are added to their root's (integer atomicAdd).
+ *   workspace: vdr_connected_components_workspace_bytes = 4 bytes per pixel (the label plane).
+ *
+ * vdr_op_mask_clean: mask uint8 [planes, H, W], min_area >= 0, connectivity, mode = a set of VDR_CLEAN_* bits ->
+ *   out      uint8 [planes, H, W]  0 / 1; it may not overlap mask (refused)
+ *   changed  int32 [planes]        bit 0: the hole step changed the plane; bit 1: the island / largest step did
+ *   stats    int32 [planes, 5]     the area of out, then its inclusive box x0, y0, x1, y1; 0, 0, 0, 0 for an empty plane
+ *                                  (vdr_op_mask_stats' box convention)
+ *   The steps run in this order, each on the result of the one before:
+ *     VDR_CLEAN_HOLES    every component of the CLEAR pixels with area < min_area becomes set (segment_anything's rule: a
+ *                        component that touches the border is not spared)
+ *     VDR_CLEAN_ISLANDS  every component of the SET pixels with area < min_area is cleared; if all of them are below it the
+ *                        largest stays, ties going to the lowest root
+ *     VDR_CLEAN_LARGEST  only the largest component of the set pixels stays, ties going to the lowest root (min_area is not read)
+ *   ISLANDS together with LARGEST is refused.  mode 0 copies (nonzero -> 1) and gives the statistics.  An empty plane, or one
+ *   with nothing to remove, comes back unchanged with changed 0.  Launches, fixed for a mode: 4 for HOLES, 5 for ISLANDS or
+ *   LARGEST (else 1 copy), 1 finish.  workspace: vdr_mask_clean_workspace_bytes = 8 bytes per pixel (label and area planes) +
+ *   16 bytes per plane (rounded up to 8) + 64 bytes per 4096 pixels of a plane (partial slots of changed / stats).  The slots
+ *   scale with the pixels: 8 + 1 / 64 bytes a pixel in all, not 8 plus a per-plane part only -- the price of one writer per
+ *   statistic instead of per-plane atomics.
+ *
+ * The library's usual contract: plain device pointers, the caller's stream, no host synchronisation, no allocation; a plane's
+ * outputs depend neither on `planes` nor on its position.  The integer atomics (minimum, sum) are order-independent: the outputs
+ * are bitwise reproducible.  A workspace below the *_workspace_bytes (0 for a shape the op refuses): VDR_ERR_WORKSPACE, nothing
+ * written.  Refused before the device is touched (VDR_ERR_INVALID): null pointers; H, W outside 1 .. 4096; planes outside
+ * 1 .. 65535; a connectivity other than 4 and 8; a value other than 0 and 1; min_area < 0; unknown mode bits; ISLANDS | LARGEST;
+ * out overlapping mask; a workspace not 16-byte aligned, int32 outputs not 4-byte aligned. */
+#define VDR_COMPONENTS_MAX_SIDE 4096
+#define VDR_CLEAN_HOLES 1
+#define VDR_CLEAN_ISLANDS 2
+#define VDR_CLEAN_LARGEST 4
+size_t vdr_mask_binarize_workspace_bytes(int planes, int H, int W, int oh, int ow);
+int vdr_op_mask_binarize(const float* logits, int64_t plane_stride, int planes_per_group, int64_t group_stride, int planes, int H, int W, int oh,
+                         int ow, float threshold, void* workspace, size_t workspace_bytes, uint8_t* out, void* stream);
+size_t vdr_connected_components_workspace_bytes(int planes, int H, int W);
+int vdr_op_connected_components(const uint8_t* mask, int planes, int H, int W, int connectivity, int value, void* workspace, size_t workspace_bytes,
+                                int32_t* root, int32_t* area, int32_t* count, void* stream);
+size_t vdr_mask_clean_workspace_bytes(int planes, int H, int W);
+int vdr_op_mask_clean(const uint8_t* mask, int planes, int H, int W, int min_area, int connectivity, int mode, void* workspace,
+                      size_t workspace_bytes, uint8_t* out, int32_t* changed, int32_t* stats, void* stream);
+
 /* SAM / MedSAM Attention.forward with use_rel_pos (third-party segment_anything ImageEncoderViT, called at
  * tfds_dense_descriptor.py:123): per (window, head) softmax(q k^T dh^-0.5 + q.Rh[qh-kh] + q.Rw[qw-kw]) v.
  *   qkv   [batch*S*S, 3*H*64] bf16, `batch` windows (or whole grids) of S x S tokens, row-major (h, w)

@@ -20,6 +20,7 @@
 #include "knn_map.h"
 #include "mask_decoder_pack.h"
 #include "mask_stats_map.h"
+#include "components_map.h"
 #include "local_corr_map.h"
 #include "vdr_kernels.h"
 
@@ -2815,6 +2816,74 @@ int vdr_op_nms(const float* boxes, const int32_t* order, int n, float iou_thresh
   const size_t need = nms_workspace_bytes(n);
   if (workspace_bytes < need) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(need) + " bytes needed");
   RUN_OP(launch_nms(boxes, order, n, iou_threshold, workspace, keep, kept, count, (hipStream_t)stream), "nms");
+}
+
+// ---- connected components of mask planes (csrc/components.hip) ----
+size_t vdr_mask_binarize_workspace_bytes(int planes, int H, int W, int oh, int ow) { return mask_stats_workspace_bytes(planes, H, W, oh, ow) ? 16 : 0; }
+
+int vdr_op_mask_binarize(const float* logits, int64_t plane_stride, int planes_per_group, int64_t group_stride, int planes, int H, int W, int oh,
+                         int ow, float threshold, void* workspace, size_t workspace_bytes, uint8_t* out, void* stream) {
+  const char* op = "vdr_op_mask_binarize";
+  if (!logits || !workspace || !out) return refuse(op, VDR_ERR_INVALID, "null pointer");
+  if (planes < 1 || planes > 65535) return refuse(op, VDR_ERR_INVALID, "planes must be 1 .. 65535");
+  if (H < 1 || H > MS_MAX_SIDE || W < 1 || W > MS_MAX_SIDE) return refuse(op, VDR_ERR_INVALID, "H and W must be 1 .. " + std::to_string(MS_MAX_SIDE));
+  if (oh < 1 || oh > MS_MAX_OUT || ow < 1 || ow > MS_MAX_OUT) return refuse(op, VDR_ERR_INVALID, "oh and ow must be 1 .. " + std::to_string(MS_MAX_OUT));
+  if (plane_stride < (int64_t)H * W) return refuse(op, VDR_ERR_INVALID, "plane_stride is shorter than a plane");
+  if (planes_per_group < 1 || planes % planes_per_group) return refuse(op, VDR_ERR_INVALID, "planes must be a multiple of planes_per_group >= 1");
+  if (planes_per_group < planes && group_stride < (planes_per_group - 1) * plane_stride + (int64_t)H * W)
+    return refuse(op, VDR_ERR_INVALID, "group_stride is shorter than a group's planes");
+  if (threshold != threshold) return refuse(op, VDR_ERR_INVALID, "threshold must be a number");
+  if ((uintptr_t)logits & 3) return refuse(op, VDR_ERR_INVALID, "logits must be aligned to its element");
+  const size_t need = vdr_mask_binarize_workspace_bytes(planes, H, W, oh, ow);
+  if (workspace_bytes < need) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(need) + " bytes needed");
+  RUN_OP(launch_mask_binarize(logits, plane_stride, planes_per_group, group_stride, planes, H, W, oh, ow, threshold, out, (hipStream_t)stream),
+         "mask_binarize");
+}
+
+size_t vdr_connected_components_workspace_bytes(int planes, int H, int W) { return components_workspace_bytes(planes, H, W, 0); }
+
+// the checks the two labelling ops share; 0: fine
+static int components_refusal(const char* op, int planes, int H, int W, int connectivity) {
+  static_assert(VDR_COMPONENTS_MAX_SIDE == CC_MAX_SIDE, "include/vdr.h and components_map.h");
+  if (planes < 1 || planes > CC_MAX_PLANES) return refuse(op, VDR_ERR_INVALID, "planes must be 1 .. 65535");
+  if (H < 1 || H > CC_MAX_SIDE || W < 1 || W > CC_MAX_SIDE) return refuse(op, VDR_ERR_INVALID, "H and W must be 1 .. " + std::to_string(CC_MAX_SIDE));
+  if (connectivity != 4 && connectivity != 8) return refuse(op, VDR_ERR_INVALID, "connectivity must be 4 or 8");
+  return 0;
+}
+
+int vdr_op_connected_components(const uint8_t* mask, int planes, int H, int W, int connectivity, int value, void* workspace, size_t workspace_bytes,
+                                int32_t* root, int32_t* area, int32_t* count, void* stream) {
+  const char* op = "vdr_op_connected_components";
+  if (!mask || !workspace || !root || !area || !count) return refuse(op, VDR_ERR_INVALID, "null pointer");
+  if (int rc = components_refusal(op, planes, H, W, connectivity)) return rc;
+  if (value != 0 && value != 1) return refuse(op, VDR_ERR_INVALID, "value must be 0 or 1");
+  if (!aligned16({workspace}) || (((uintptr_t)root | (uintptr_t)area | (uintptr_t)count) & 3))
+    return refuse(op, VDR_ERR_INVALID, "workspace must be 16-byte aligned, root, area and count to their element");
+  const size_t need = components_workspace_bytes(planes, H, W, 0);
+  if (workspace_bytes < need) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(need) + " bytes needed");
+  RUN_OP(launch_connected_components(mask, planes, H, W, connectivity, value, workspace, root, area, count, (hipStream_t)stream),
+         "connected_components");
+}
+
+size_t vdr_mask_clean_workspace_bytes(int planes, int H, int W) { return components_workspace_bytes(planes, H, W, 1); }
+
+int vdr_op_mask_clean(const uint8_t* mask, int planes, int H, int W, int min_area, int connectivity, int mode, void* workspace,
+                      size_t workspace_bytes, uint8_t* out, int32_t* changed, int32_t* stats, void* stream) {
+  const char* op = "vdr_op_mask_clean";
+  if (!mask || !workspace || !out || !changed || !stats) return refuse(op, VDR_ERR_INVALID, "null pointer");
+  if (int rc = components_refusal(op, planes, H, W, connectivity)) return rc;
+  if (min_area < 0) return refuse(op, VDR_ERR_INVALID, "min_area must be >= 0");
+  if (mode & ~(VDR_CLEAN_HOLES | VDR_CLEAN_ISLANDS | VDR_CLEAN_LARGEST)) return refuse(op, VDR_ERR_INVALID, "unknown mode bit");
+  if ((mode & VDR_CLEAN_ISLANDS) && (mode & VDR_CLEAN_LARGEST)) return refuse(op, VDR_ERR_INVALID, "VDR_CLEAN_ISLANDS and VDR_CLEAN_LARGEST exclude each other");
+  {
+    const uintptr_t a = (uintptr_t)mask, b = (uintptr_t)out, n = (uintptr_t)planes * H * W;
+    if (a < b + n && b < a + n) return refuse(op, VDR_ERR_INVALID, "out may not overlap mask");
+  }
+  if (!aligned16({workspace}) || (((uintptr_t)changed | (uintptr_t)stats) & 3))
+    return refuse(op, VDR_ERR_INVALID, "workspace must be 16-byte aligned, changed and stats to their element");
+  const size_t need = components_workspace_bytes(planes, H, W, 1);
+  if (workspace_bytes < need) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(need) + " bytes needed");
+  RUN_OP(launch_mask_clean(mask, planes, H, W, min_area, connectivity, mode, workspace, out, changed, stats, (hipStream_t)stream), "mask_clean");
 }
 
 int vdr_op_attention_relpos(const void* qkv, const float* rel_pos_h, const float* rel_pos_w, float* rel, void* out,

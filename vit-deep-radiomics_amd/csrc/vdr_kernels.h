@@ -272,6 +272,14 @@ constexpr int NMS_MAX_BOXES = 4096;  // 64 words of 64 bits: one lane of the wal
 size_t nms_workspace_bytes(int n);
 hipError_t launch_nms(const float* boxes, const int32_t* order, int n, float iou_threshold, void* work, uint8_t* keep, int32_t* kept,
                       int32_t* count, hipStream_t s);
+// csrc/components.hip: connected components of mask planes (include/vdr.h "connected components"; the mapping is components_map.h)
+size_t components_workspace_bytes(int P, int H, int W, int clean);  // 0: a shape the ops refuse; clean: vdr_op_mask_clean's
+hipError_t launch_connected_components(const uint8_t* mask, int P, int H, int W, int connectivity, int value, void* work, int32_t* root,
+                                       int32_t* area, int32_t* count, hipStream_t s);
+hipError_t launch_mask_clean(const uint8_t* mask, int P, int H, int W, int min_area, int connectivity, int mode, void* work, uint8_t* out,
+                             int32_t* changed, int32_t* stats, hipStream_t s);
+hipError_t launch_mask_binarize(const float* logits, int64_t plane_stride, int group, int64_t group_stride, int P, int H, int W, int oh, int ow,
+                                float threshold, uint8_t* out, hipStream_t s);
 hipError_t launch_attention_pool(const float* q, const void* kv, int64_t ldkv, void* out, int batch, int n, int heads,
                                  int head_dim, hipStream_t s);
 

@@ -146,6 +146,12 @@ SYMBOLS = {
     "vdr_mask_stats_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
     "vdr_op_mask_stats": (_I, [_P, _L, _I, _L, _I, _I, _I, _I, _I, _F, _F, _P, C.c_size_t, _P, _P, _P]),
     "vdr_nms_workspace_bytes": (C.c_size_t, [_I]),
+    "vdr_mask_binarize_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
+    "vdr_op_mask_binarize": (_I, [_P, _L, _I, _L, _I, _I, _I, _I, _I, _F, _P, C.c_size_t, _P, _P]),
+    "vdr_connected_components_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+    "vdr_op_connected_components": (_I, [_P, _I, _I, _I, _I, _I, _P, C.c_size_t, _P, _P, _P, _P]),
+    "vdr_mask_clean_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+    "vdr_op_mask_clean": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, C.c_size_t, _P, _P, _P, _P]),
     "vdr_op_nms": (_I, [_P, _P, _I, _F, _P, C.c_size_t, _P, _P, _P, _P]),
     "vdr_op_attention_relpos": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "vdr_op_layernorm_window": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),

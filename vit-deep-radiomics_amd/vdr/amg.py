@@ -8,8 +8,14 @@ candidate's logits come back bit for bit and memory stays at one batch.  model.g
 mask_stats_torch and nms_torch state the two kernels in plain torch on the CPU, operation by operation: the kernels are read
 against them bit for bit.
 
-Out of scope: crop layers (crop_n_layers > 0, and with them the near-crop-edge filter), small-region removal
-(min_mask_region_area), several images per call, mask-level NMS, fp8."""
+Small-region removal (min_mask_region_area > 0, segment_anything's postprocess_small_regions) runs after the NMS on the device:
+the kept masks are binarised at `size` (vdr.ops.mask_binarize, mask_stats' arithmetic), holes and then islands below the area
+are removed at 8-connectivity (vdr.ops.mask_clean: connected components, csrc/components.hip), and a second box NMS prefers the
+masks that needed no change.  Deviations there: "largest" ties go to the lowest root; parity with OpenCV's
+connectedComponentsWithStats, which segment_anything calls, is unpinned (the rule is restated on scipy.ndimage.label).
+
+Out of scope: crop layers (crop_n_layers > 0, and with them the near-crop-edge filter), several images per call, mask-level NMS,
+fp8."""
 from __future__ import annotations
 
 import numpy as np
@@ -128,10 +134,15 @@ class MaskSet:
     """What generate_masks returns, K masks in NMS order (best predicted IoU first), all on the device:
     low_res_logits [K, 4g, 4g] fp32; iou, stability fp32 [K]; area int32 [K] (pixels above the threshold at `size`); boxes int32
     [K, 4] XYXY, inclusive, at `size`; points fp32 [K, 2] (x, y), the prompt of each mask in input pixels; point_index int64 [K]
-    (into the grid), mask_index int64 [K] (0 .. 2: which of the point's three masks)."""
+    (into the grid), mask_index int64 [K] (0 .. 2: which of the point's three masks).  After small-region removal
+    (min_mask_region_area > 0) the set also carries cleaned uint8 [K, h, w], the cleaned masks at `size`, and changed int32 [K]
+    (bit 0: holes were filled, bit 1: islands were removed); area and boxes are then the cleaned masks', and masks(), label_map()
+    and rle() give the cleaned planes -- at `size` only."""
 
-    def __init__(self, low_res_logits, iou, stability, area, boxes, points, point_index, mask_index, input_size, size, mask_threshold):
+    def __init__(self, low_res_logits, iou, stability, area, boxes, points, point_index, mask_index, input_size, size, mask_threshold,
+                 cleaned=None, changed=None):
         self.low_res_logits, self.iou, self.stability, self.area, self.boxes = low_res_logits, iou, stability, area, boxes
+        self.cleaned, self.changed = cleaned, changed
         self.points, self.point_index, self.mask_index = points, point_index, mask_index
         self.input_size, self.size, self.mask_threshold = tuple(int(v) for v in input_size), tuple(int(v) for v in size), float(mask_threshold)
 
@@ -141,6 +152,10 @@ class MaskSet:
     def masks(self, size=None) -> torch.Tensor:
         """[K, h, w] bool at the statistics' size or `size`: bilinear (align_corners=False) > mask_threshold; plain torch"""
         size = self.size if size is None else tuple(int(v) for v in size)
+        if self.cleaned is not None:
+            if size != self.size:
+                raise ValueError(f"MaskSet.masks: the set was cleaned at {self.size} (min_mask_region_area); another size, {size}, would need cleaning again")
+            return self.cleaned != 0
         if len(self) == 0:
             return torch.zeros((0, *size), dtype=torch.bool, device=self.low_res_logits.device)
         up = torch.nn.functional.interpolate(self.low_res_logits[:, None], size=size, mode="bilinear", align_corners=False)[:, 0]
@@ -164,9 +179,11 @@ class MaskSet:
         return mask_to_rle(self.masks(size))
 
 
-def check_generate(model, x, points_per_side, points_per_batch, thresholds: dict):
+def check_generate(model, x, points_per_side, points_per_batch, thresholds: dict, min_mask_region_area=0):
     """Every refusal of generate_masks, before any device work -> x as [1, 3, S, S]"""
     from . import segment as sg
+    if isinstance(min_mask_region_area, bool) or not isinstance(min_mask_region_area, int) or min_mask_region_area < 0:
+        raise ValueError(f"generate_masks: min_mask_region_area must be an integer >= 0, got {min_mask_region_area!r}")
     sg._require(model, "generate_masks")
     if not isinstance(x, torch.Tensor) or x.dim() not in (3, 4):
         raise ValueError(f"generate_masks: one image [1, 3, S, S] or [3, S, S], got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
@@ -190,11 +207,11 @@ def check_generate(model, x, points_per_side, points_per_batch, thresholds: dict
 
 
 def generate(model, x, points_per_side, points_per_batch, pred_iou_thresh, stability_score_thresh, stability_score_offset, mask_threshold,
-             box_nms_thresh, size) -> MaskSet:
+             box_nms_thresh, size, min_mask_region_area=0) -> MaskSet:
     from . import ops
     x = check_generate(model, x, points_per_side, points_per_batch, dict(
         pred_iou_thresh=pred_iou_thresh, stability_score_thresh=stability_score_thresh, stability_score_offset=stability_score_offset,
-        mask_threshold=mask_threshold, box_nms_thresh=box_nms_thresh))
+        mask_threshold=mask_threshold, box_nms_thresh=box_nms_thresh), min_mask_region_area)
     img, dev = model.cfg.img, model.device
     size = (img, img) if size is None else ops.check_out_size("generate_masks", size)
     grid = point_grid(points_per_side, img).to(dev)
@@ -220,7 +237,10 @@ def generate(model, x, points_per_side, points_per_batch, pred_iou_thresh, stabi
     def result(sel, logits):
         return MaskSet(logits, iou[sel], stab[sel], counts[sel, 1], boxes[sel], grid[sel // 3], sel // 3, sel % 3, (img, img), size, mask_threshold)
     if cand.numel() == 0:
-        return result(cand, torch.zeros((0, g4, g4), dtype=torch.float32, device=dev))
+        ms = result(cand, torch.zeros((0, g4, g4), dtype=torch.float32, device=dev))
+        if min_mask_region_area > 0:
+            ms.cleaned, ms.changed = torch.zeros((0, *size), dtype=torch.uint8, device=dev), torch.zeros((0,), dtype=torch.int32, device=dev)
+        return ms
     if cand.numel() > MAX_CANDIDATES:
         raise ValueError(f"generate_masks: {cand.numel()} candidates pass the filters, NMS takes at most {MAX_CANDIDATES}: raise pred_iou_thresh "
                          "or stability_score_thresh, or lower points_per_side")
@@ -231,4 +251,21 @@ def generate(model, x, points_per_side, points_per_batch, pred_iou_thresh, stabi
         part = sel[s0:s0 + points_per_batch]
         lg = decode(grid[part // 3]).low_res_logits[0]                   # [k, 3, 4g, 4g]
         logits.append(torch.gather(lg, 1, (part % 3)[:, None, None, None].expand(-1, 1, g4, g4))[:, 0])
-    return result(sel, torch.cat(logits))
+    ms = result(sel, torch.cat(logits))
+    return remove_small_regions(ms, min_mask_region_area, box_nms_thresh) if min_mask_region_area > 0 else ms
+
+
+def remove_small_regions(ms: MaskSet, min_area: int, box_nms_thresh: float) -> MaskSet:
+    """segment_anything's postprocess_small_regions on a MaskSet of K >= 1 masks: the masks binarised at ms.size; holes, then islands,
+    below min_area removed at 8-connectivity; boxes from the cleaned masks; a second box NMS whose score is 1 for a mask that
+    needed no change and 0 for one that did (visited in a stable order: unchanged masks first, each class in rank order), so
+    that a changed mask goes when it now overlaps an unchanged one.  The survivors stay in their rank order (best predicted IoU
+    first); a changed mask takes its new area and box.  One more host read: the second NMS count."""
+    from . import ops, segment as sg
+    cleaned, changed, stats = sg.clean_planes("generate_masks", ms.low_res_logits, ms.size, ms.mask_threshold, min_area, holes=True, islands=True,
+                                              largest=False, connectivity=8)
+    score = (changed == 0).to(torch.float32)
+    kept, count = ops.nms(stats[:, 1:].to(torch.float32), score, box_nms_thresh)
+    keep = torch.sort(kept[:int(count.cpu())].long()).values
+    return MaskSet(ms.low_res_logits[keep], ms.iou[keep], ms.stability[keep], stats[keep, 0], stats[keep, 1:], ms.points[keep], ms.point_index[keep],
+                   ms.mask_index[keep], ms.input_size, ms.size, ms.mask_threshold, cleaned=cleaned[keep].view(torch.uint8), changed=changed[keep])

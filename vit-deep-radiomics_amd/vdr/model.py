@@ -368,17 +368,20 @@ class VitDescriptorModel:
 
     def generate_masks(self, x: torch.Tensor, points_per_side: int = 32, points_per_batch: int = 64, pred_iou_thresh: float = 0.88,
                        stability_score_thresh: float = 0.95, stability_score_offset: float = 1.0, mask_threshold: float = 0.0,
-                       box_nms_thresh: float = 0.7, size=None):
+                       box_nms_thresh: float = 0.7, size=None, min_mask_region_area: int = 0):
         """Segment everything: SAM's automatic mask generator on ONE image x [1, 3, S, S] (or [3, S, S]) -> vdr.MaskSet (vdr/amg.py).
         A points_per_side x points_per_side grid of one-point prompts is decoded points_per_batch at a time into three masks a
         point; every candidate's stability score, area and box at `size` (the input size by default) come from vdr.ops.mask_stats;
         candidates with predicted IoU > pred_iou_thresh and stability > stability_score_thresh (both strict) go through greedy box
         NMS at box_nms_thresh (vdr.ops.nms, best predicted IoU first), and the kept points are decoded once more for their
         logits.  Two host reads in all: the filter flags and the NMS count.  More than 4096 candidates after the filter is a
-        ValueError.  Crop layers, small-region removal and mask-level NMS are out of scope."""
+        ValueError.  min_mask_region_area > 0: segment_anything's small-region removal after the NMS (holes, then islands, below
+        that many pixels at `size`, connected components on the device; a second box NMS that prefers unchanged masks; one more
+        host read); the MaskSet then carries the cleaned planes.  0 is the path without it: no further launch, the same bits.
+        Crop layers and mask-level NMS are out of scope."""
         from . import amg
         return amg.generate(self, x, points_per_side, points_per_batch, pred_iou_thresh, stability_score_thresh, stability_score_offset,
-                            mask_threshold, box_nms_thresh, size)
+                            mask_threshold, box_nms_thresh, size, min_mask_region_area)
 
     def propagate_masks(self, x: torch.Tensor, box, index: int, direction: str = "both", margin: float = 8, use_mask_prompt: bool = True,
                         multimask: bool = False, max_batch: int = 16):
@@ -990,33 +993,38 @@ class VitDescriptorModel:
         return ops.affinity_bits(self._descriptors(x, layer, facet, h), tau=tau)
 
     def tokencut(self, x: torch.Tensor, layer=None, facet: str = "key", bin: bool = False, tau: float = 0.2, eps: float = 1e-5,
-                 hierarchy: int = 2):
+                 hierarchy: int = 2, labelling: str = "host"):
         """TokenCut (Wang et al., CVPR 2022) on every image of x [B, 3, H, W]: one forward (vdr_forward_facets) writes the bf16
         `facet` descriptors of block `layer` (None: the last block), log-binned at `hierarchy` when bin;
         vdr.ops.affinity_bits builds the graph cos > tau of each map from that buffer in place, one bit per pair;
         vdr.spectral.tokencut takes the Fiedler vector of (D - W) y = lambda D y, W = eps + (1 - eps) B, splits it at its
         mean and returns the seed's connected component and box (vdr.TokenCut, with the graph in .bits; pixel_box() for pixels).  No mask, no second
         image, no k.  The input size, patch stride and dynamic_size in force apply.  Written from the paper as remembered;
-        parity with its code is not pinned.  Refusals (ValueError, before any device work): extract_descriptors', a NaN tau."""
+        parity with its code is not pinned.  labelling: "host" (the seed's component by a numpy flood fill per map) or "device" (one
+        vdr.ops.connected_components call for all maps; the same masks and boxes).  Refusals (ValueError, before any device work):
+        extract_descriptors', a NaN tau, an unknown labelling."""
         from . import spectral
+        spectral.check_labelling("tokencut", labelling)
         bits = self._affinity_graph(x, "tokencut", layer, facet, bin, hierarchy, float(tau))
         return spectral.tokencut(bits, tuple(self.engine.grid), eps=float(eps), stride=int(self.engine.patch_stride),
-                                 patch=int(self.cfg.patch))
+                                 patch=int(self.cfg.patch), **({} if labelling == "host" else {"labelling": labelling}))
 
     def lost(self, x: torch.Tensor, layer=None, facet: str = "key", k: int = 100, bin: bool = False, hierarchy: int = 2,
-             tau: float = 0.0):
+             tau: float = 0.0, labelling: str = "host"):
         """LOST (Simeoni et al., BMVC 2021) on every image of x [B, 3, H, W]: the graph cos > 0 of the bf16 `facet` descriptors
         (one forward, vdr.ops.affinity_bits in place), the lowest-degree patch as the seed, the k lowest-degree patches
         adjacent to it as the expansion set, the seed's connected component of that set and its box (vdr.Lost).  tau: the
         threshold of the graph, LOST's 0 by default; descriptors that share a large common component (every cosine positive:
         a complete graph, every degree equal) need a higher one to say anything.  Deviation: LOST compares raw dot products
-        with >= 0; here it is cosines > tau.  Refusals as
+        with >= 0; here it is cosines > tau.  labelling as tokencut's.  Refusals as
         tokencut's, and k < 1."""
         from . import spectral
+        spectral.check_labelling("lost", labelling)
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or int(k) < 1:
             raise ValueError(f"lost: k must be a positive integer, got {k!r}")
         bits = self._affinity_graph(x, "lost", layer, facet, bin, hierarchy, float(tau))
-        return spectral.lost(bits, tuple(self.engine.grid), k=int(k), stride=int(self.engine.patch_stride), patch=int(self.cfg.patch))
+        return spectral.lost(bits, tuple(self.engine.grid), k=int(k), stride=int(self.engine.patch_stride), patch=int(self.cfg.patch),
+                            **({} if labelling == "host" else {"labelling": labelling}))
 
     def _anomaly_args(self, what, layer, facet, bin, hierarchy):
         """the device-free refusals shared by fit_anomaly and anomaly_map; returns (hierarchy to ask for, channels)"""

@@ -472,6 +472,91 @@ def nms(boxes, scores, iou_threshold: float, workspace=None):
     return kept, count
 
 
+def mask_binarize(logits, size, threshold: float = 0.0, out=None):
+    """Candidate masks at image resolution (vdr_op_mask_binarize): logits fp32 [P, H, W] or [G, M, H, W] on the device
+    (PlaneOperand: strided planes are read in place) -> uint8 [.., oh, ow], 1 where the bilinear (align_corners=False)
+    up-sampling to size = (oh, ow) is > threshold.  The arithmetic is mask_stats': the set pixels are the ones it counts and
+    boxes; bit for bit vdr.amg.upsample_torch(logits, size) > threshold."""
+    o = PlaneOperand(logits, "mask_binarize")
+    oh, ow = check_out_size("mask_binarize", size)
+    if float(threshold) != float(threshold):
+        raise ValueError("mask_binarize: threshold must be a number")
+    lib = L.load()
+    dev = o.x.device
+    lead = (o.planes,) if logits.dim() == 3 else o.shape
+    if out is None:
+        out = torch.empty((*lead, oh, ow), dtype=torch.uint8, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (*lead, oh, ow)):
+        raise ValueError(f"mask_binarize: out must be a contiguous uint8 {(*lead, oh, ow)} tensor on the device")
+    workspace = torch.empty((lib.vdr_mask_binarize_workspace_bytes(o.planes, o.H, o.W, oh, ow),), dtype=torch.uint8, device=dev)
+    L.check(lib.vdr_op_mask_binarize(o.x.data_ptr(), o.plane_stride, o.group, o.group_stride, o.planes, o.H, o.W, oh, ow, float(threshold),
+                                     workspace.data_ptr(), workspace.numel(), out.data_ptr(), _s(o.x)))
+    return out
+
+
+def _mask_planes(mask, op: str):
+    from . import components as cc
+    m, single = cc.as_planes(mask, op)
+    if not m.is_cuda:
+        raise ValueError(f"{op}: mask must live on the HIP device")
+    return m, single
+
+
+def connected_components(mask, connectivity: int = 8, value: int = 1, workspace=None):
+    """Connected components of mask planes (vdr_op_connected_components): mask bool or uint8 [P, H, W] or [H, W] on the device
+    (nonzero = set), connectivity 4 or 8, value 1 (components of the set pixels) or 0 (of the clear pixels) -> (root int32
+    like mask: the lowest pixel index y * W + x of each pixel's component, -1 where not selected; area int32 like mask: the
+    component's pixel count at its root, 0 elsewhere; count int32 [P]).  Bit for bit vdr.components.label_torch; nothing here
+    synchronises."""
+    from . import components as cc
+    m, single = _mask_planes(mask, "connected_components")
+    cc.check_connectivity("connected_components", connectivity)
+    if isinstance(value, bool) or value not in (0, 1):
+        raise ValueError(f"connected_components: value must be 0 or 1, got {value!r}")
+    lib = L.load()
+    P, H, W = (int(v) for v in m.shape)
+    need = lib.vdr_connected_components_workspace_bytes(P, H, W)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=m.device)
+    root = torch.empty((P, H, W), dtype=torch.int32, device=m.device)
+    area = torch.empty((P, H, W), dtype=torch.int32, device=m.device)
+    count = torch.empty((P,), dtype=torch.int32, device=m.device)
+    L.check(lib.vdr_op_connected_components(m.data_ptr(), P, H, W, int(connectivity), int(value), workspace.data_ptr(), workspace.numel(),
+                                            root.data_ptr(), area.data_ptr(), count.data_ptr(), _s(m)))
+    return (root[0], area[0], count) if single else (root, area, count)
+
+
+def mask_clean(mask, min_area: int = 0, holes: bool = False, islands: bool = False, largest: bool = False, connectivity: int = 8, workspace=None,
+               out=None, changed=None, stats=None):
+    """Small-region removal / keep-largest on mask planes (vdr_op_mask_clean): mask bool or uint8 [P, H, W] or [H, W] on the
+    device -> (out uint8 like mask, 0 / 1; changed int32 [P]: bit 0 the hole step changed the plane, bit 1 the island / largest
+    step; stats int32 [P, 5]: area and inclusive box x0, y0, x1, y1 of out, zeros for an empty plane).  holes: components of
+    the clear pixels below min_area become set; then islands: components of the set pixels below min_area are cleared (the
+    largest stays if all are below); or largest: only the largest component stays (ties: the lowest root).  Bit for bit
+    vdr.components.clean_torch; nothing here synchronises.  out / changed / stats: contiguous device tensors of those shapes and
+    types to write into (a slice of a larger result, say) instead of fresh ones; out may not share memory with mask."""
+    from . import components as cc
+    m, single = _mask_planes(mask, "mask_clean")
+    min_area, mode, connectivity = cc.check_clean("mask_clean", min_area, holes, islands, largest, connectivity)
+    lib = L.load()
+    P, H, W = (int(v) for v in m.shape)
+    need = lib.vdr_mask_clean_workspace_bytes(P, H, W)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=m.device)
+    def given(t, shape, dtype, name):
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=m.device)
+        if not (isinstance(t, torch.Tensor) and t.device == m.device and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"mask_clean: {name} must be a contiguous {dtype} tensor of shape {shape} on the mask's device")
+        return t
+    out = given(out, (P, H, W), torch.uint8, "out")
+    changed = given(changed, (P,), torch.int32, "changed")
+    stats = given(stats, (P, 5), torch.int32, "stats")
+    L.check(lib.vdr_op_mask_clean(m.data_ptr(), P, H, W, min_area, connectivity, mode, workspace.data_ptr(), workspace.numel(), out.data_ptr(),
+                                  changed.data_ptr(), stats.data_ptr(), _s(m)))
+    return (out[0] if single else out), changed, stats
+
+
 def log_bin(x: torch.Tensor, gh: int, gw: int, hierarchy: int = 2, out_dtype=torch.float32, out=None) -> torch.Tensor:
     """Log-binning of a dense descriptor map (vdr_op_log_bin): x [B, gh*gw, C] bf16 or fp32 -- contiguous, or a view whose
     last dimension is contiguous, such as the key columns and patch rows buf[:, P:, C:2*C] of a [B, P + n, 3C] qkv

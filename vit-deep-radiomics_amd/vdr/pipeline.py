@@ -186,12 +186,32 @@ def generate_features(model, img_3d, mask_3d, flip=None, max_batch=16, descripto
     return features_list, mask_list
 
 
-def segment_volume(model, img_3d, boxes, max_batch=16, threshold=0.0):
+def _check_regions(what, min_region_area, fill_holes, keep_largest):
+    """The region keywords of segment_volume / propagate_segmentation -> whether any is on; ValueError before any device work"""
+    if isinstance(min_region_area, bool) or not isinstance(min_region_area, int) or min_region_area < 0:
+        raise ValueError(f"{what}: min_region_area must be an integer >= 0, got {min_region_area!r}")
+    if not isinstance(fill_holes, bool) or not isinstance(keep_largest, bool):
+        raise ValueError(f"{what}: fill_holes and keep_largest must be True or False, got {fill_holes!r}, {keep_largest!r}")
+    if fill_holes and min_region_area == 0:
+        raise ValueError(f"{what}: fill_holes fills the holes below min_region_area pixels: give a positive min_region_area")
+    return min_region_area > 0 or keep_largest
+
+
+def _region_kwargs(min_region_area, fill_holes, keep_largest):
+    """the clean() keywords: holes below the area filled when asked; islands below it removed, or only the largest part kept"""
+    return dict(min_area=min_region_area, holes=fill_holes, islands=min_region_area > 0 and not keep_largest, largest=keep_largest)
+
+
+def segment_volume(model, img_3d, boxes, max_batch=16, threshold=0.0, min_region_area=0, fill_holes=False, keep_largest=False):
     """The mask generate_features takes as mask_3d, from box prompts: img_3d (H, W, S) gray volume in [0, 1] (or (H, W, S, 3)),
     boxes [S, 4] (x0, y0, x1, y1) in slice pixels, one per slice, or one box [4] for every slice -> (H, W, S) bool numpy.
     The slices run in chunks of `max_batch` through prepare -> model.segment (mask token 0) -> bilinear logits at slice
-    resolution > threshold; one synchronisation per volume.  SAM / MedSAM models loaded with their decoder weights."""
+    resolution > threshold; one synchronisation per volume.  SAM / MedSAM models loaded with their decoder weights.
+    min_region_area > 0 removes, slice by slice, the islands below that many pixels (the largest stays when all are), fill_holes
+    also fills the holes below it, keep_largest keeps only each slice's largest component (Segmentation.clean: connected
+    components on the device, 8-connected, 2-D).  All three off is the path without them, bit for bit."""
     from . import segment as sg
+    regions = _check_regions("segment_volume", min_region_area, fill_holes, keep_largest)
     sg._require(model, "segment_volume")
     vol = torch.as_tensor(img_3d)
     if vol.dim() not in (3, 4) or (vol.dim() == 4 and vol.shape[3] != 3):
@@ -212,16 +232,22 @@ def segment_volume(model, img_3d, boxes, max_batch=16, threshold=0.0):
         s1 = min(S, s0 + max_batch)
         x = prep.prepare_slices(vol[:, :, s0:s1], side=side, device=model.device)
         seg = model.segment(x, scaled[s0:s1].reshape(s1 - s0, 1, 4))
-        out[s0:s1] = seg.masks(size=(H, W), threshold=threshold)[:, 0, 0]
+        if regions:
+            out[s0:s1] = seg.clean(size=(H, W), threshold=threshold, **_region_kwargs(min_region_area, fill_holes, keep_largest))[0][:, 0, 0]
+        else:
+            out[s0:s1] = seg.masks(size=(H, W), threshold=threshold)[:, 0, 0]
     return out.permute(1, 2, 0).cpu().numpy()
 
 
-def propagate_segmentation(model, img_3d, box, index, direction="both", margin=8, use_mask_prompt=True, max_batch=16, threshold=0.0):
+def propagate_segmentation(model, img_3d, box, index, direction="both", margin=8, use_mask_prompt=True, max_batch=16, threshold=0.0,
+                           min_region_area=0, fill_holes=False, keep_largest=False):
     """segment_volume from ONE annotation: img_3d (H, W, S) gray volume in [0, 1] (or (H, W, S, 3)), box (x0, y0, x1, y1) in
     slice pixels on slice `index` -> (H, W, S) bool numpy, the array generate_features takes as mask_3d.  The slices are
     prepared in chunks of max_batch, model.propagate_masks carries the mask through the volume (margin in pixels of the
-    prepared input), the logits are resampled to slice resolution; one synchronisation per volume."""
+    prepared input), the logits are resampled to slice resolution; one synchronisation per volume.  min_region_area, fill_holes and
+    keep_largest as segment_volume's: they clean the RETURNED masks slice by slice, the propagation itself is untouched."""
     from . import segment as sg
+    regions = _check_regions("propagate_segmentation", min_region_area, fill_holes, keep_largest)
     sg._require(model, "propagate_segmentation")
     vol = torch.as_tensor(img_3d)
     if vol.dim() not in (3, 4) or (vol.dim() == 4 and vol.shape[3] != 3):
@@ -240,6 +266,8 @@ def propagate_segmentation(model, img_3d, box, index, direction="both", margin=8
         vol = vol.to(torch.float32)
     x = torch.cat([prep.prepare_slices(vol[:, :, s0:s0 + max_batch], side=side, device=model.device) for s0 in range(0, S, max_batch)], dim=0)
     seg = model.propagate_masks(x, scaled, index, direction=direction, margin=margin, use_mask_prompt=use_mask_prompt, max_batch=max_batch)
+    if regions:
+        return seg.clean(size=(H, W), threshold=threshold, **_region_kwargs(min_region_area, fill_holes, keep_largest))[0].permute(1, 2, 0).cpu().numpy()
     return seg.masks(size=(H, W), threshold=threshold).permute(1, 2, 0).cpu().numpy()
 
 

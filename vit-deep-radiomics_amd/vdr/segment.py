@@ -31,6 +31,35 @@ SA_EPS = dict(ln_eps=1e-5, final_ln_eps=1e-5, ln2d_eps=1e-6)   # segment_anythin
 HF_EPS = dict(ln_eps=1e-6, final_ln_eps=1e-5, ln2d_eps=1e-6)   # transformers.SamModel applies its config's layer_norm_eps
 
 
+def clean_planes(what: str, logits, size, threshold=0.0, min_area=0, holes=True, islands=True, largest=False, connectivity=8, max_planes=64,
+                 lead=None):
+    """Binarise planes of low-resolution logits at `size` and clean them: logits fp32 [P, h, w] or [G, M, h, w] on the device
+    (read in place) -> (masks bool [.., oh, ow], changed int32 [..], stats int32 [.., 5]).  ONE vdr.ops.mask_binarize and ONE
+    vdr.ops.mask_clean per chunk of at most max_planes planes, so that the label workspace stays bounded (8 bytes a pixel);
+    every refusal comes before any device work.  lead: the leading shape of the results when it is
+    not the logits' own (a [B, nb, M, h, w] decode passed as [B nb, M, h, w])."""
+    from . import components as cc, ops
+    oh, ow = ops.check_out_size(what, size)
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or threshold != threshold:
+        raise ValueError(f"{what}: threshold must be a number, got {threshold!r}")
+    min_area, mode, connectivity = cc.check_clean(what, min_area, holes, islands, largest, connectivity)
+    if isinstance(max_planes, bool) or not isinstance(max_planes, int) or not 1 <= max_planes <= 65535:
+        raise ValueError(f"{what}: max_planes must be an integer in 1 .. 65535, got {max_planes!r}")
+    lead = tuple(int(v) for v in (logits.shape[:-2] if lead is None else lead))
+    groups = logits if logits.dim() == 4 else logits[:, None]          # [G, M, h, w]: chunks of whole groups stay views, read in place
+    G, M = int(groups.shape[0]), int(groups.shape[1])
+    P, dev, step = G * M, logits.device, max(1, max_planes // M)
+    masks = torch.empty((P, oh, ow), dtype=torch.uint8, device=dev)
+    changed = torch.empty((P,), dtype=torch.int32, device=dev)
+    stats = torch.empty((P, 5), dtype=torch.int32, device=dev)
+    for g0 in range(0, G, step):
+        raw = ops.mask_binarize(groups[g0:g0 + step], (oh, ow), float(threshold)).reshape(-1, oh, ow)
+        p0, p1 = g0 * M, g0 * M + int(raw.shape[0])
+        ops.mask_clean(raw, min_area, holes=bool(mode & cc.HOLES), islands=bool(mode & cc.ISLANDS), largest=bool(mode & cc.LARGEST),
+                       connectivity=connectivity, out=masks[p0:p1], changed=changed[p0:p1], stats=stats[p0:p1])   # written in place: no copy
+    return masks.view(torch.bool).reshape(*lead, oh, ow), changed.reshape(lead), stats.reshape(*lead, 5)
+
+
 class Segmentation:
     """low_res_logits [B, nb, M, 4g, 4g] fp32 and iou [B, nb, M] fp32 of one decode; M = 1 (mask token 0) or 3 (tokens 1..3)."""
 
@@ -58,6 +87,16 @@ class Segmentation:
         counts, box = ops.mask_stats(self.low_res_logits.flatten(0, 1), size, threshold, offset)
         counts, box = counts.reshape(B, nb, M, 3), box.reshape(B, nb, M, 4)
         return counts, box, amg.stability(counts)
+
+    def clean(self, size=None, threshold: float = 0.0, min_area: int = 0, holes: bool = True, islands: bool = True, largest: bool = False,
+              connectivity: int = 8, max_planes: int = 64):
+        """(masks bool [B, nb, M, h, w], changed int32 [B, nb, M], stats int32 [B, nb, M, 5]) at the input size or `size`: the masks
+        of masks(size, threshold) with holes below min_area filled and islands below it removed (segment_anything's
+        remove_small_regions, both passes), or only the largest component kept; changed bit 0 / 1: the hole / island step changed
+        the mask; stats: area and inclusive box x0, y0, x1, y1.  One vdr.ops.mask_binarize that reads low_res_logits in place and
+        one vdr.ops.mask_clean per chunk of max_planes planes (clean_planes); the binarisation is mask_stats' arithmetic."""
+        return clean_planes("Segmentation.clean", self.low_res_logits.flatten(0, 1), self.input_size if size is None else size, threshold, min_area,
+                            holes, islands, largest, connectivity, max_planes, lead=tuple(self.low_res_logits.shape[:3]))
 
     def best(self) -> "Segmentation":
         """the highest-IoU mask of every problem (M = 1): a device gather, no synchronisation; ties go to the lowest index"""
@@ -90,6 +129,13 @@ class VolumeSegmentation:
     def masks(self, size=None, threshold: float = 0.0) -> torch.Tensor:
         """[Z, h, w] bool at the input size or `size`"""
         return self.logits(size) > threshold
+
+    def clean(self, size=None, threshold: float = 0.0, min_area: int = 0, holes: bool = True, islands: bool = True, largest: bool = False,
+              connectivity: int = 8, max_planes: int = 64):
+        """(masks bool [Z, h, w], changed int32 [Z], stats int32 [Z, 5]): Segmentation.clean for the slices of a volume, slice by
+        slice (2-D components; 3-D ones are out of scope)"""
+        return clean_planes("VolumeSegmentation.clean", self.low_res_logits, self.input_size if size is None else size, threshold, min_area, holes,
+                            islands, largest, connectivity, max_planes)
 
 
 MAX_TOKENS = 16                     # per problem (include/vdr.h): 5 + points + (2 with a box, 1 without)

@@ -227,6 +227,27 @@ def _masks_and_boxes(parts, seeds, grid, dev):
     return as_dev(parts), torch.tensor(seeds, dtype=torch.int64, device=dev), as_dev(masks), boxes
 
 
+def check_labelling(what: str, labelling):
+    if labelling not in ("host", "device"):
+        raise ValueError(f"{what}: labelling must be 'host' or 'device', got {labelling!r}")
+
+
+def _masks_and_boxes_device(parts, seeds, grid, dev):
+    """device labelling: ONE vdr.ops.connected_components call (connectivity 4) labels every map, the seed's component is
+    root == root[seed], the box comes from the first and last set row and column; the same tensors as _masks_and_boxes, and
+    there is no device-to-host read (the bipartitions and seeds go up as ordinary blocking copies)"""
+    from . import components as cc
+    gh, gw = grid
+    part = torch.from_numpy(np.stack(parts)).to(dev).reshape(-1, gh, gw)
+    seed = torch.tensor(seeds, dtype=torch.int64, device=dev)
+    root, _, _ = ops.connected_components(part, connectivity=4)
+    mask = cc.seed_component(root, seed)
+    rows, cols = mask.any(dim=2).to(torch.uint8), mask.any(dim=1).to(torch.uint8)
+    first = lambda v: v.argmax(dim=1)                                    # noqa: E731  (the first maximum: the first set row / column)
+    last = lambda v: v.shape[1] - 1 - v.flip(1).argmax(dim=1)            # noqa: E731
+    return part, seed, mask, torch.stack([first(rows), first(cols), last(rows), last(cols)], dim=1)
+
+
 def _check_grid(bits, grid, what):
     gh, gw = int(grid[0]), int(grid[1])
     if bits.dim() != 3 or gh <= 0 or gw <= 0 or gh * gw != bits.shape[1]:
@@ -234,22 +255,27 @@ def _check_grid(bits, grid, what):
     return gh, gw
 
 
-def tokencut(bits: torch.Tensor, grid, eps: float = 1e-5, stride: int = 1, patch: int = 1, **fiedler_kwargs) -> TokenCut:
+def tokencut(bits: torch.Tensor, grid, eps: float = 1e-5, stride: int = 1, patch: int = 1, labelling: str = "host", **fiedler_kwargs) -> TokenCut:
     """TokenCut on the graphs bits [P, t, pitch] of maps on the grid (gh, gw), t = gh * gw: the Fiedler vector (`fiedler`),
-    bipartition_rule per map, the seed's 4-connected component, its bounding box.  The labelling runs on the host."""
+    bipartition_rule per map, the seed's 4-connected component, its bounding box.  labelling "host": a numpy flood fill per map;
+    "device": one vdr.ops.connected_components call for all maps (the same masks and boxes)."""
+    check_labelling("tokencut", labelling)
     gh, gw = _check_grid(bits, grid, "tokencut")
     vec, val, resid, steps = fiedler(bits, eps=eps, **fiedler_kwargs)
     v = vec.cpu().numpy()
     rules = [bipartition_rule(v[p]) for p in range(v.shape[0])]
-    parts, seeds, masks, boxes = _masks_and_boxes([r[0] for r in rules], [r[1] for r in rules], (gh, gw), bits.device)
+    label = _masks_and_boxes_device if labelling == "device" else _masks_and_boxes
+    parts, seeds, masks, boxes = label([r[0] for r in rules], [r[1] for r in rules], (gh, gw), bits.device)
     return TokenCut(vec.reshape(-1, gh, gw), parts, seeds, masks, boxes, (gh, gw), int(stride), int(patch), val, resid, steps, bits)
 
 
-def lost(bits: torch.Tensor, grid, k: int = 100, stride: int = 1, patch: int = 1) -> Lost:
+def lost(bits: torch.Tensor, grid, k: int = 100, stride: int = 1, patch: int = 1, labelling: str = "host") -> Lost:
     """LOST on the graphs bits [P, t, pitch] (built at tau = 0) of maps on the grid (gh, gw): lost_rule per map, the seed's
     4-connected component of the expansion set, its bounding box.  Host work per call: the degrees come from one bits_matvec
     launch on a zero vector (`degree`: the popcounts ride on the product kernel, there is no kernel of their own), and the seed's
-    row of every problem is one small device-to-host copy (pitch words): fine for the tens of maps of a batch, not for thousands."""
+    row of every problem is one small device-to-host copy (pitch words): fine for the tens of maps of a batch, not for thousands.
+    labelling as tokencut's."""
+    check_labelling("lost", labelling)
     gh, gw = _check_grid(bits, grid, "lost")
     if int(k) < 1:
         raise ValueError(f"lost: k must be positive, got {k}")
@@ -262,5 +288,6 @@ def lost(bits: torch.Tensor, grid, k: int = 100, stride: int = 1, patch: int = 1
         s, chosen = lost_rule(row, deg_h[p], k)
         seeds.append(s)
         sets.append(chosen)
-    parts, seeds, masks, boxes = _masks_and_boxes(sets, seeds, (gh, gw), bits.device)
+    label = _masks_and_boxes_device if labelling == "device" else _masks_and_boxes
+    parts, seeds, masks, boxes = label(sets, seeds, (gh, gw), bits.device)
     return Lost(deg.reshape(-1, gh, gw), parts, seeds, masks, boxes, (gh, gw), int(stride), int(patch), bits)
