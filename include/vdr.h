@@ -938,6 +938,50 @@ size_t vdr_mask_clean_workspace_bytes(int planes, int H, int W);
 int vdr_op_mask_clean(const uint8_t* mask, int planes, int H, int W, int min_area, int connectivity, int mode, void* workspace,
                       size_t workspace_bytes, uint8_t* out, int32_t* changed, int32_t* stats, void* stream);
 
+/* ---- exact Euclidean distance transform of mask planes (csrc/edt.hip, csrc/edt_map.h).
+ *
+ * A plane is H x W uint8, nonzero = set, H and W in 1 .. 4096 (a zero-area plane is refused), planes in 1 .. 65535, pixel index
+ * i = y * W + x.  value selects the pixels that are measured: 1 the set pixels, 0 the clear ones (vdr_op_connected_components'
+ * convention).  Everything is an integer and a function of the mask alone: the outputs are bit for bit
+ * rint(scipy.ndimage.distance_transform_edt(selected) ^ 2) and its indices under the tie rule below.
+ *
+ * vdr_op_distance_transform: mask uint8 [planes, H, W], value, outside, r2 -> four outputs, EACH OPTIONAL (null: not computed,
+ * not touched), at least one of them given:
+ *   d2       int32 [planes, H, W]  for a selected pixel (y, x): min (y - y')^2 + (x - x')^2 over the pixels (y', x') that are NOT
+ *                                  selected; 0 on a pixel that is not selected.  outside = 1: everything beyond the plane counts as
+ *                                  not selected, so the minimum also runs over (y + 1)^2, (H - y)^2, (x + 1)^2 and (W - x)^2.
+ *                                  A selected pixel with no candidate at all (every pixel of the plane selected, outside = 0) gets
+ *                                  VDR_EDT_NONE = 2^31 - 1.  The largest real value is 2 * 4095^2.
+ *   nearest  int32 [planes, H, W]  the LOWEST pixel index among the non-selected pixels that attain the minimum; -1 on a pixel that
+ *                                  is not selected and where there is none.  Refused together with outside = 1 (the nearest point
+ *                                  may lie beyond the plane).  The tie rule is the separable form's own: within a row the nearest
+ *                                  non-selected pixel with the lower x, across rows the lowest y'.
+ *   peak     int32 [planes, 2]     the maximum of d2 over the plane and the lowest pixel index that attains it; (0, -1) for a plane
+ *                                  with nothing selected.  VDR_EDT_NONE counts as a value: a full plane gives (VDR_EDT_NONE, 0).
+ *   within   uint8 [planes, H, W]  1 where d2 <= r2, else 0, for r2 >= 0 (r2 is read only when within is given; a pixel that is not
+ *                                  selected has d2 = 0 and is always 1).  Given WITHOUT d2 it takes d2's place: the int32 plane is
+ *                                  never written -- Euclidean dilation and erosion by a radius r are this output at r2 = floor(r^2).
+ *   The signature chosen for the thresholded plane is "a nullable d2 plus this output", not a mode flag: both may be asked at once.
+ *
+ * Two launches, three with peak: a row pass (per pixel the signed offset to the nearest non-selected pixel of its own row, 16 bits,
+ * -32768 for "none in this row", which is tested for and never squared); a column pass that searches outwards from each pixel's own
+ * row and stops when k^2 reaches the best so far (integer only; at most max(y, H - 1 - y) steps); with peak, one partial slot per
+ * tile of the column pass and one wave per plane that reduces them.  No atomics.  No intermediate exceeds 2 * 4099^2 < 2^26.
+ * workspace: vdr_distance_transform_workspace_bytes = 2 bytes a pixel (the row offsets; the total rounded up to 16) + 8 bytes per
+ * 64 x 16 tile of a plane (the peak's slots): 2 + 1 / 128 bytes a pixel on large planes, not 2 plus a per-plane part only -- the
+ * price of one writer per slot instead of a per-plane atomic maximum, as in vdr_op_mask_clean.
+ *
+ * The library's usual contract: plain device pointers, the caller's stream, no host synchronisation, no allocation; a plane's
+ * outputs depend neither on `planes` nor on its position.  A workspace below the size (0 for a shape the op refuses):
+ * VDR_ERR_WORKSPACE, nothing written.  Refused before the device is touched (VDR_ERR_INVALID): a null mask or workspace; all four
+ * outputs null; H, W outside 1 .. 4096; planes outside 1 .. 65535; a value or an outside other than 0 and 1; nearest with
+ * outside = 1; within with r2 < 0; a workspace not 16-byte aligned, int32 outputs not 4-byte aligned. */
+#define VDR_EDT_MAX_SIDE 4096
+#define VDR_EDT_NONE 2147483647
+size_t vdr_distance_transform_workspace_bytes(int planes, int H, int W);
+int vdr_op_distance_transform(const uint8_t* mask, int planes, int H, int W, int value, int outside, int r2, void* workspace, size_t workspace_bytes,
+                              int32_t* d2, int32_t* nearest, int32_t* peak, uint8_t* within, void* stream);
+
 /* SAM / MedSAM Attention.forward with use_rel_pos (third-party segment_anything ImageEncoderViT, called at
  * tfds_dense_descriptor.py:123): per (window, head) softmax(q k^T dh^-0.5 + q.Rh[qh-kh] + q.Rw[qw-kw]) v.
  *   qkv   [batch*S*S, 3*H*64] bf16, `batch` windows (or whole grids) of S x S tokens, row-major (h, w)

@@ -21,6 +21,7 @@
 #include "mask_decoder_pack.h"
 #include "mask_stats_map.h"
 #include "components_map.h"
+#include "edt_map.h"
 #include "local_corr_map.h"
 #include "vdr_kernels.h"
 
@@ -2884,6 +2885,29 @@ int vdr_op_mask_clean(const uint8_t* mask, int planes, int H, int W, int min_are
   const size_t need = components_workspace_bytes(planes, H, W, 1);
   if (workspace_bytes < need) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(need) + " bytes needed");
   RUN_OP(launch_mask_clean(mask, planes, H, W, min_area, connectivity, mode, workspace, out, changed, stats, (hipStream_t)stream), "mask_clean");
+}
+
+// ---- exact Euclidean distance transform of mask planes (csrc/edt.hip) ----
+size_t vdr_distance_transform_workspace_bytes(int planes, int H, int W) { return distance_transform_workspace_bytes(planes, H, W); }
+
+int vdr_op_distance_transform(const uint8_t* mask, int planes, int H, int W, int value, int outside, int r2, void* workspace, size_t workspace_bytes,
+                              int32_t* d2, int32_t* nearest, int32_t* peak, uint8_t* within, void* stream) {
+  static_assert(VDR_EDT_MAX_SIDE == EDT_MAX_SIDE && VDR_EDT_NONE == EDT_NONE, "include/vdr.h and edt_map.h");
+  const char* op = "vdr_op_distance_transform";
+  if (!mask || !workspace) return refuse(op, VDR_ERR_INVALID, "null pointer");
+  if (!d2 && !nearest && !peak && !within) return refuse(op, VDR_ERR_INVALID, "no output: d2, nearest, peak and within are all null");
+  if (planes < 1 || planes > EDT_MAX_PLANES) return refuse(op, VDR_ERR_INVALID, "planes must be 1 .. 65535");
+  if (H < 1 || H > EDT_MAX_SIDE || W < 1 || W > EDT_MAX_SIDE) return refuse(op, VDR_ERR_INVALID, "H and W must be 1 .. " + std::to_string(EDT_MAX_SIDE));
+  if (value != 0 && value != 1) return refuse(op, VDR_ERR_INVALID, "value must be 0 or 1");
+  if (outside != 0 && outside != 1) return refuse(op, VDR_ERR_INVALID, "outside must be 0 or 1");
+  if (nearest && outside) return refuse(op, VDR_ERR_INVALID, "nearest is not defined with outside = 1 (the nearest point may lie beyond the plane)");
+  if (within && r2 < 0) return refuse(op, VDR_ERR_INVALID, "r2 must be >= 0");
+  if (!aligned16({workspace}) || (((uintptr_t)d2 | (uintptr_t)nearest | (uintptr_t)peak) & 3))
+    return refuse(op, VDR_ERR_INVALID, "workspace must be 16-byte aligned, d2, nearest and peak to their element");
+  const size_t need = distance_transform_workspace_bytes(planes, H, W);
+  if (workspace_bytes < need) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(need) + " bytes needed");
+  RUN_OP(launch_distance_transform(mask, planes, H, W, value, outside, r2, workspace, d2, nearest, peak, within, (hipStream_t)stream),
+         "distance_transform");
 }
 
 int vdr_op_attention_relpos(const void* qkv, const float* rel_pos_h, const float* rel_pos_w, float* rel, void* out,

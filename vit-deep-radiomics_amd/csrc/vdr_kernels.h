@@ -280,6 +280,10 @@ hipError_t launch_mask_clean(const uint8_t* mask, int P, int H, int W, int min_a
                              int32_t* changed, int32_t* stats, hipStream_t s);
 hipError_t launch_mask_binarize(const float* logits, int64_t plane_stride, int group, int64_t group_stride, int P, int H, int W, int oh, int ow,
                                 float threshold, uint8_t* out, hipStream_t s);
+// csrc/edt.hip: exact Euclidean distance transform of mask planes (include/vdr.h "distance transform"; the mapping is edt_map.h)
+size_t distance_transform_workspace_bytes(int P, int H, int W);  // 0: a shape the op refuses
+hipError_t launch_distance_transform(const uint8_t* mask, int P, int H, int W, int value, int outside, int r2, void* work, int32_t* d2,
+                                     int32_t* nearest, int32_t* peak, uint8_t* within, hipStream_t s);
 hipError_t launch_attention_pool(const float* q, const void* kv, int64_t ldkv, void* out, int batch, int n, int heads,
                                  int head_dim, hipStream_t s);
 

@@ -8,7 +8,7 @@ from ._lib import (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GELU_TANH, EPI_BIAS_QUICK_G
 from .engine import AttnMap, Engine, FacetOut, LayerOut, VdrConfig  # noqa: F401
 from .model import (ARCHS, Correspondences, Cosegmentation, Propagation, TransformerNoduleBimodalClassifier, TransformerNoduleClassifier, VitDescriptorModel, VolumePropagation, extract_dense, get_dense_descriptor,  # noqa: F401
                     load_model)
-from . import amg, anomaly, components, kmeans, knn, local, pca, pipeline, prep, segment, spectral, upsample  # noqa: F401,E402
+from . import amg, anomaly, components, kmeans, knn, local, metrics, morphology, pca, pipeline, prep, segment, spectral, upsample  # noqa: F401,E402
 from .segment import Segmentation, VolumeSegmentation, segment_slice  # noqa: F401,E402
 from .amg import MaskSet  # noqa: F401,E402
 from .anomaly import AnomalyMap, Gaussian, GaussianAccumulator, MemoryBank, fit_gaussian  # noqa: F401,E402

@@ -384,7 +384,7 @@ class VitDescriptorModel:
                             mask_threshold, box_nms_thresh, size, min_mask_region_area)
 
     def propagate_masks(self, x: torch.Tensor, box, index: int, direction: str = "both", margin: float = 8, use_mask_prompt: bool = True,
-                        multimask: bool = False, max_batch: int = 16):
+                        multimask: bool = False, max_batch: int = 16, point_prompt=None):
         """A mask for a whole volume from ONE annotated slice: x [Z, 3, S, S] prepared slices, box (x0, y0, x1, y1) on slice
         `index` in pixels of x -> vdr.VolumeSegmentation.  Slice `index` is decoded from `box`; every further slice gets
         vdr.ops.mask_box of its neighbour's single-mask (token 0) logits, grown by `margin` pixels, as its box and -- with
@@ -393,10 +393,17 @@ class VitDescriptorModel:
         "both": step k then decodes slices index + k and index - k as ONE two-problem call while both exist (a problem's bits
         do not depend on the problem count).  multimask: the stored logits / iou are the highest-IoU of tokens 1..3 instead of
         token 0; the sweep itself always hands token 0 on.  Embeddings come from image_encoder in chunks of max_batch; nothing
-        in the sweep synchronises with the host."""
+        in the sweep synchronises with the host.  point_prompt="inner": every slice after the first also gets ONE positive click,
+        vdr.morphology.inner_point of its neighbour's token-0 low-resolution mask (logits > 0, the plane's outside counted as
+        clear): the most interior pixel, which keeps a sweep on a thin or concave structure; the label is -1 ("not a point")
+        when that mask is empty.  It is computed on the device (vdr_op_distance_transform), needs the point-prompt weights, and
+        the sweep still never synchronises.  None (the default) is the sweep without it, bit for bit."""
+        from . import morphology as mo
         from . import ops
         from . import segment as sg
         sg._require(self, "propagate_masks")
+        if point_prompt not in (None, "inner"):
+            raise ValueError(f"propagate_masks: point_prompt must be None or 'inner', got {point_prompt!r}")
         check_batch("propagate_masks", x)
         Z = int(x.shape[0])
         if isinstance(index, bool) or not isinstance(index, int) or not 0 <= index < Z:
@@ -415,6 +422,8 @@ class VitDescriptorModel:
         if use_mask_prompt and not dec.has_mask_prompt:
             raise ValueError("propagate_masks: use_mask_prompt needs the checkpoint's prompt_encoder.mask_downscaling.* weights: weights absent "
                              "(use_mask_prompt=False propagates the box alone)")
+        if point_prompt is not None and not dec.has_point_prompts:
+            raise ValueError("propagate_masks: the checkpoint has no point-prompt weights (point_embeddings.0/1, not_a_point_embed): weights absent")
         g, img, dev = dec.g, self.cfg.img, self.device
         emb = torch.cat([self.image_encoder(x[s0:s0 + max_batch]) for s0 in range(0, Z, max_batch)], dim=0)
         logits = torch.empty((Z, 4 * g, 4 * g), dtype=torch.float32, device=dev)
@@ -422,11 +431,14 @@ class VitDescriptorModel:
         boxes = torch.empty((Z, 4), dtype=torch.float32, device=dev)
         area = torch.empty((Z,), dtype=torch.int32, device=dev)
 
-        def step(slices, bx, prev_logits):
-            """decode `slices` from boxes bx [k, 4] (and the neighbours' token-0 logits) -> (their token-0 logits, their next boxes)"""
+        def step(slices, bx, prev_logits, click=None):
+            """decode `slices` from boxes bx [k, 4] (the neighbours' token-0 logits, the neighbours' clicks) -> (their token-0 logits,
+            their next boxes, their clicks for the next slice or None)"""
             k = len(slices)
             e = emb[slices[0]:slices[0] + 1] if k == 1 else torch.stack([emb[z] for z in slices])
-            lg4, iou4 = dec.decode(e, bx.reshape(k, 1, 4), mask_input=prev_logits.reshape(k, 1, 4 * g, 4 * g) if prev_logits is not None else None)
+            lg4, iou4 = dec.decode(e, bx.reshape(k, 1, 4), points=None if click is None else click[0].reshape(k, 1, 1, 2),
+                                   labels=None if click is None else click[1].reshape(k, 1, 1),
+                                   mask_input=prev_logits.reshape(k, 1, 4 * g, 4 * g) if prev_logits is not None else None)
             lg4, iou4 = lg4[:, 0], iou4[:, 0]                                     # [k, 4, 4g, 4g], [k, 4]
             nxt, ar = ops.mask_box(lg4[:, 0], bx, img, margin=margin, threshold=0.0)
             if multimask:
@@ -437,20 +449,22 @@ class VitDescriptorModel:
                 keep, kiou = lg4[:, 0], iou4[:, 0]
             for i, z in enumerate(slices):
                 logits[z], iou[z], boxes[z], area[z] = keep[i], kiou[i], bx[i], ar[i]
-            return lg4[:, 0], nxt
+            return lg4[:, 0], nxt, (mo.inner_point(lg4[:, 0] > 0, img, outside=True) if point_prompt else None)
 
         seed = b.to(dev, torch.float32).reshape(1, 4)
-        lg0, nx0 = step([index], seed, None)
-        state = {"up": (lg0[0], nx0[0]), "down": (lg0[0], nx0[0])}
+        lg0, nx0, ck0 = step([index], seed, None)
+        first = (lg0[0], nx0[0], None if ck0 is None else (ck0[0][0], ck0[1][0]))
+        state = {"up": first, "down": first}
         for k in range(1, Z):
             todo = [(d, z) for d, z in (("up", index + k), ("down", index - k)) if direction in ("both", d) and 0 <= z < Z]
             if not todo:
                 break
             bx = torch.stack([state[d][1] for d, _ in todo])
             prev = torch.stack([state[d][0] for d, _ in todo]) if use_mask_prompt else None
-            lg, nxt = step([z for _, z in todo], bx, prev)
+            click = (torch.stack([state[d][2][0] for d, _ in todo]), torch.stack([state[d][2][1] for d, _ in todo])) if point_prompt else None
+            lg, nxt, ck = step([z for _, z in todo], bx, prev, click)
             for i, (d, _) in enumerate(todo):
-                state[d] = (lg[i], nxt[i])
+                state[d] = (lg[i], nxt[i], None if ck is None else (ck[0][i], ck[1][i]))
         return sg.VolumeSegmentation(logits, iou, boxes, area, (img, img))
 
     # -- input size ------------------------------------------------------------------------------

@@ -557,6 +557,45 @@ def mask_clean(mask, min_area: int = 0, holes: bool = False, islands: bool = Fal
     return (out[0] if single else out), changed, stats
 
 
+def distance_transform(mask, value: int = 1, outside: bool = False, return_nearest: bool = False, return_peak: bool = False, threshold=None,
+                       workspace=None, return_d2: bool = True):
+    """Exact Euclidean distance transform of mask planes (vdr_op_distance_transform): mask bool or uint8 [P, H, W] or [H, W] on
+    the device (nonzero = set), value 1 (the set pixels are measured) or 0 (the clear ones) -> d2 int32 like mask: the squared
+    distance to the nearest pixel that is not selected, 0 where not selected, 2^31 - 1 where there is none; outside=True counts
+    everything beyond the plane as not selected.  return_nearest adds nearest int32 like mask (the lowest index y * W + x of a
+    nearest non-selected pixel, -1 where there is none; not with outside), return_peak adds peak int32 [P, 2] (the largest d2
+    and the lowest index that attains it, (0, -1) for a plane with nothing selected); with either the result is a tuple in
+    that order.  threshold = r2 (an integer >= 0): the first result is the uint8 plane d2 <= r2 INSTEAD of d2, and the int32
+    plane is never written.  return_d2=False leaves the first result out altogether (no plane of the mask's size is allocated
+    or written; not together with threshold, and something else must be asked for): vdr.morphology.inner_point asks for the
+    peak alone.  Bit for bit vdr.morphology.edt_torch; nothing here synchronises.  Every refusal of an argument comes before
+    the device is asked for."""
+    from . import components as cc
+    from . import morphology as mo
+    cc.as_planes(mask, "distance_transform")
+    value, outside, r2 = mo.check_edt("distance_transform", value, outside, return_nearest, threshold)
+    if not return_d2 and (r2 is not None or not (return_nearest or return_peak)):
+        raise ValueError("distance_transform: return_d2=False goes with return_nearest or return_peak and without threshold")
+    m, single = _mask_planes(mask, "distance_transform")
+    lib = L.load()
+    P, H, W = (int(v) for v in m.shape)
+    need = lib.vdr_distance_transform_workspace_bytes(P, H, W)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=m.device)
+    first = torch.empty((P, H, W), dtype=torch.int32 if r2 is None else torch.uint8, device=m.device) if return_d2 else None
+    nearest = torch.empty((P, H, W), dtype=torch.int32, device=m.device) if return_nearest else None
+    peak = torch.empty((P, 2), dtype=torch.int32, device=m.device) if return_peak else None
+    L.check(lib.vdr_op_distance_transform(m.data_ptr(), P, H, W, value, outside, 0 if r2 is None else r2, workspace.data_ptr(), workspace.numel(),
+                                          _p(first) if r2 is None else None, _p(nearest), _p(peak),
+                                          _p(first) if r2 is not None else None, _s(m)))
+    out = [first[0] if single else first] if return_d2 else []
+    if return_nearest:
+        out.append(nearest[0] if single else nearest)
+    if return_peak:
+        out.append(peak)
+    return out[0] if len(out) == 1 else tuple(out)
+
+
 def log_bin(x: torch.Tensor, gh: int, gw: int, hierarchy: int = 2, out_dtype=torch.float32, out=None) -> torch.Tensor:
     """Log-binning of a dense descriptor map (vdr_op_log_bin): x [B, gh*gw, C] bf16 or fp32 -- contiguous, or a view whose
     last dimension is contiguous, such as the key columns and patch rows buf[:, P:, C:2*C] of a [B, P + n, 3C] qkv

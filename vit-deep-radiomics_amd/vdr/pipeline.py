@@ -202,16 +202,26 @@ def _region_kwargs(min_region_area, fill_holes, keep_largest):
     return dict(min_area=min_region_area, holes=fill_holes, islands=min_region_area > 0 and not keep_largest, largest=keep_largest)
 
 
-def segment_volume(model, img_3d, boxes, max_batch=16, threshold=0.0, min_region_area=0, fill_holes=False, keep_largest=False):
+def _grow(what, masks, grow):
+    """Euclidean dilation of finished bool masks [S, H, W] on the device by `grow` pixels (vdr.morphology.dilate); 0: the masks"""
+    from . import morphology as mo
+    return masks if mo.check_radius(what, grow) == 0 else mo.dilate(masks, grow)
+
+
+def segment_volume(model, img_3d, boxes, max_batch=16, threshold=0.0, min_region_area=0, fill_holes=False, keep_largest=False, grow=0.0):
     """The mask generate_features takes as mask_3d, from box prompts: img_3d (H, W, S) gray volume in [0, 1] (or (H, W, S, 3)),
     boxes [S, 4] (x0, y0, x1, y1) in slice pixels, one per slice, or one box [4] for every slice -> (H, W, S) bool numpy.
     The slices run in chunks of `max_batch` through prepare -> model.segment (mask token 0) -> bilinear logits at slice
     resolution > threshold; one synchronisation per volume.  SAM / MedSAM models loaded with their decoder weights.
     min_region_area > 0 removes, slice by slice, the islands below that many pixels (the largest stays when all are), fill_holes
     also fills the holes below it, keep_largest keeps only each slice's largest component (Segmentation.clean: connected
-    components on the device, 8-connected, 2-D).  All three off is the path without them, bit for bit."""
+    components on the device, 8-connected, 2-D).  All three off is the path without them, bit for bit.  grow > 0 dilates the
+    finished mask of every slice, after any cleaning, by the Euclidean disc of that radius in slice pixels (compared as
+    floor(grow^2); one distance transform on the device); 0 is the path without it."""
+    from . import morphology as mo
     from . import segment as sg
     regions = _check_regions("segment_volume", min_region_area, fill_holes, keep_largest)
+    mo.check_radius("segment_volume: grow", grow)
     sg._require(model, "segment_volume")
     vol = torch.as_tensor(img_3d)
     if vol.dim() not in (3, 4) or (vol.dim() == 4 and vol.shape[3] != 3):
@@ -236,18 +246,24 @@ def segment_volume(model, img_3d, boxes, max_batch=16, threshold=0.0, min_region
             out[s0:s1] = seg.clean(size=(H, W), threshold=threshold, **_region_kwargs(min_region_area, fill_holes, keep_largest))[0][:, 0, 0]
         else:
             out[s0:s1] = seg.masks(size=(H, W), threshold=threshold)[:, 0, 0]
-    return out.permute(1, 2, 0).cpu().numpy()
+    return _grow("segment_volume: grow", out, grow).permute(1, 2, 0).cpu().numpy()
 
 
 def propagate_segmentation(model, img_3d, box, index, direction="both", margin=8, use_mask_prompt=True, max_batch=16, threshold=0.0,
-                           min_region_area=0, fill_holes=False, keep_largest=False):
+                           min_region_area=0, fill_holes=False, keep_largest=False, grow=0.0, point_prompt=None):
     """segment_volume from ONE annotation: img_3d (H, W, S) gray volume in [0, 1] (or (H, W, S, 3)), box (x0, y0, x1, y1) in
     slice pixels on slice `index` -> (H, W, S) bool numpy, the array generate_features takes as mask_3d.  The slices are
     prepared in chunks of max_batch, model.propagate_masks carries the mask through the volume (margin in pixels of the
     prepared input), the logits are resampled to slice resolution; one synchronisation per volume.  min_region_area, fill_holes and
-    keep_largest as segment_volume's: they clean the RETURNED masks slice by slice, the propagation itself is untouched."""
+    keep_largest as segment_volume's: they clean the RETURNED masks slice by slice, the propagation itself is untouched; grow as
+    segment_volume's, after the cleaning.  point_prompt: model.propagate_masks' (None, or "inner" for the neighbour's most
+    interior pixel as a positive click on every further slice)."""
+    from . import morphology as mo
     from . import segment as sg
     regions = _check_regions("propagate_segmentation", min_region_area, fill_holes, keep_largest)
+    mo.check_radius("propagate_segmentation: grow", grow)
+    if point_prompt not in (None, "inner"):
+        raise ValueError(f"propagate_segmentation: point_prompt must be None or 'inner', got {point_prompt!r}")
     sg._require(model, "propagate_segmentation")
     vol = torch.as_tensor(img_3d)
     if vol.dim() not in (3, 4) or (vol.dim() == 4 and vol.shape[3] != 3):
@@ -265,10 +281,13 @@ def propagate_segmentation(model, img_3d, box, index, direction="both", margin=8
     if vol.dtype not in (torch.float32, torch.float64):
         vol = vol.to(torch.float32)
     x = torch.cat([prep.prepare_slices(vol[:, :, s0:s0 + max_batch], side=side, device=model.device) for s0 in range(0, S, max_batch)], dim=0)
-    seg = model.propagate_masks(x, scaled, index, direction=direction, margin=margin, use_mask_prompt=use_mask_prompt, max_batch=max_batch)
+    kw = {} if point_prompt is None else dict(point_prompt=point_prompt)
+    seg = model.propagate_masks(x, scaled, index, direction=direction, margin=margin, use_mask_prompt=use_mask_prompt, max_batch=max_batch, **kw)
     if regions:
-        return seg.clean(size=(H, W), threshold=threshold, **_region_kwargs(min_region_area, fill_holes, keep_largest))[0].permute(1, 2, 0).cpu().numpy()
-    return seg.masks(size=(H, W), threshold=threshold).permute(1, 2, 0).cpu().numpy()
+        masks = seg.clean(size=(H, W), threshold=threshold, **_region_kwargs(min_region_area, fill_holes, keep_largest))[0]
+    else:
+        masks = seg.masks(size=(H, W), threshold=threshold)
+    return _grow("propagate_segmentation: grow", masks, grow).permute(1, 2, 0).cpu().numpy()
 
 
 # ---- tfds_dense_descriptor.py:142-165 -----------------------------------------------------------------------

@@ -98,6 +98,22 @@ class Segmentation:
         return clean_planes("Segmentation.clean", self.low_res_logits.flatten(0, 1), self.input_size if size is None else size, threshold, min_area,
                             holes, islands, largest, connectivity, max_planes, lead=tuple(self.low_res_logits.shape[:3]))
 
+    def distance(self, size=None, threshold: float = 0.0) -> torch.Tensor:
+        """int32 [B, nb, M, h, w]: the squared Euclidean distance of every mask pixel to the nearest pixel outside its mask (0
+        outside the mask, 2^31 - 1 on a mask that fills the plane), at the input size or `size`: ONE vdr.ops.mask_binarize that
+        reads low_res_logits in place (the pixels mask_stats counts) and ONE vdr.ops.distance_transform."""
+        return distance_planes("Segmentation.distance", self.low_res_logits.flatten(0, 1), self.input_size if size is None else size, threshold,
+                               tuple(self.low_res_logits.shape[:3]))
+
+    def inner_points(self):
+        """(points fp32 [B, nb, M, 2] (x, y) in pixels of the input, labels int32 [B, nb, M]): the most interior pixel of every
+        low-resolution mask (logits > 0; vdr.morphology.inner_point with the plane's outside counted as clear), ready to go
+        back in as a positive click; label -1 and point (0, 0) for an empty mask.  No synchronisation."""
+        from . import morphology as mo
+        lead = tuple(self.low_res_logits.shape[:3])
+        pts, lab = mo.inner_point((self.low_res_logits > 0).flatten(0, 2), self.input_size, outside=True)
+        return pts.reshape(*lead, 2), lab.reshape(lead)
+
     def best(self) -> "Segmentation":
         """the highest-IoU mask of every problem (M = 1): a device gather, no synchronisation; ties go to the lowest index"""
         idx = self.iou.argmax(dim=2, keepdim=True)                                  # [B, nb, 1]
@@ -136,6 +152,42 @@ class VolumeSegmentation:
         slice (2-D components; 3-D ones are out of scope)"""
         return clean_planes("VolumeSegmentation.clean", self.low_res_logits, self.input_size if size is None else size, threshold, min_area, holes,
                             islands, largest, connectivity, max_planes)
+
+    def distance(self, size=None, threshold: float = 0.0) -> torch.Tensor:
+        """int32 [Z, h, w]: Segmentation.distance for the slices of a volume, slice by slice (2-D distances)"""
+        return distance_planes("VolumeSegmentation.distance", self.low_res_logits, self.input_size if size is None else size, threshold,
+                               (int(self.low_res_logits.shape[0]),))
+
+    def inner_points(self):
+        """(points fp32 [Z, 2] (x, y) in pixels of the input, labels int32 [Z]): Segmentation.inner_points slice by slice"""
+        from . import morphology as mo
+        return mo.inner_point(self.low_res_logits > 0, self.input_size, outside=True)
+
+    def compare(self, other, size=None, threshold: float = 0.0, spacing: float = 1.0, tolerance: float = 1.0) -> dict:
+        """This volume's masks against `other` -- another VolumeSegmentation or a bool / uint8 mask tensor [Z, h, w] on the same
+        device -- slice by slice at the input size or `size`: vdr.metrics.overlap (dice, iou, intersection, a, b) and
+        vdr.metrics.surface (hd, hd95, assd, nsd) in one dict of [Z] tensors.  The distance transforms run on the device; the
+        surface measures synchronise once per slice."""
+        from . import metrics
+        size = self.input_size if size is None else tuple(int(v) for v in size)
+        a = self.masks(size, threshold)
+        b = other.masks(size, threshold) if isinstance(other, VolumeSegmentation) else other
+        if not isinstance(b, torch.Tensor) or tuple(b.shape) != tuple(a.shape):
+            raise ValueError(f"VolumeSegmentation.compare: other must be a VolumeSegmentation or a mask tensor {tuple(a.shape)}, got "
+                             f"{tuple(b.shape) if isinstance(b, torch.Tensor) else type(b).__name__}")
+        out = metrics.overlap(a, b)
+        out.update(metrics.surface(a, b, spacing=spacing, tolerance=tolerance))
+        return out
+
+
+def distance_planes(what: str, logits, size, threshold, lead):
+    """planes of low-resolution logits [P, h, w] or [G, M, h, w] on the device -> d2 int32 [*lead, oh, ow] of their masks at `size`"""
+    from . import ops
+    oh, ow = ops.check_out_size(what, size)
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or threshold != threshold:
+        raise ValueError(f"{what}: threshold must be a number, got {threshold!r}")
+    raw = ops.mask_binarize(logits, (oh, ow), float(threshold)).reshape(-1, oh, ow)
+    return ops.distance_transform(raw).reshape(*lead, oh, ow)
 
 
 MAX_TOKENS = 16                     # per problem (include/vdr.h): 5 + points + (2 with a box, 1 without)
