@@ -5,8 +5,6 @@ the device is touched; the mapping of the statistics kernel walked by a host pro
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 import types
 
 import pytest
@@ -14,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 import amg_ref as AR
+import host_program
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -266,16 +265,7 @@ def test_mask_set_methods_on_designed_logits():
 def test_the_mask_stats_mapping_stages_in_bounds_and_owns_every_pixel_once(tmp_path, sanitize):
     """tests/mask_stats_map_cases.cpp, a host program with its own main, over the header the kernels include; the second build
     runs it under the address and undefined-behaviour sanitizers (host code, stand-alone)"""
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++") or os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    exe = os.path.join(str(tmp_path), "mask_stats_map_cases")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", *flags, "-I", CSRC, os.path.join(HERE, "mask_stats_map_cases.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    r = subprocess.run([exe], capture_output=True, text=True)
-    print(r.stdout[-3000:])
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    lines = r.stdout.splitlines()
+    lines = host_program.run("mask_stats_map_cases", tmp_path, sanitize).splitlines()
     assert lines[-1] == "cases 48 fails 0"
     assert sum("unowned 0 twice 0" in ln and ln.endswith(")") and " bad 0 " in ln for ln in lines) == 48
     # the generator's shape (32 bands of 32 rows, 10 staged rows), a down-sampling that fills the stage, oh = 4096, sides of 1 and 256
@@ -283,3 +273,16 @@ def test_the_mask_stats_mapping_stages_in_bounds_and_owns_every_pixel_once(tmp_p
     assert any(ln.startswith("P 3 H 256 W 256 oh 255 ow 257 layout 0: rows 28 bands 10 stage 29 ") for ln in lines)
     assert any(ln.startswith("P 6 H 256 W 8 oh 4096 ow 5 layout 1: rows 32 bands 128 stage 4 ") for ln in lines)
     assert any(ln.startswith("P 3 H 1 W 256 oh 7 ow 4096 layout 2: rows 32 bands 1 stage 1 ") for ln in lines)
+
+
+# ---- the plane reduction the mask-plane kernels share ------------------------------------------------------------------------------
+@pytest.mark.parametrize("sanitize", [False, True])
+def test_the_plane_reduction_gives_brute_force_integers_in_every_order(tmp_path, sanitize):
+    """tests/plane_reduce_cases.cpp, a host program with its own main, over csrc/plane_reduce.h: the identity is neutral, combine is
+    commutative and associative on designed values, a slot round-trips, and a plane's pixels reduced forwards, reversed, as a tree
+    and wave by wave give the brute-force counts and box; the second build runs it under the address and undefined-behaviour
+    sanitizers (host code, stand-alone)"""
+    lines = host_program.run("plane_reduce_cases", tmp_path, sanitize).splitlines()
+    assert lines[-1] == "cases 24 fails 0"
+    assert sum(ln.startswith("NS ") and ln.endswith(" designed 8 fails 0") for ln in lines) == 24
+    assert all(f"NS {ns} W 517 H 300: " in "\n".join(lines) and f"NS {ns} W 1 H 1: " in "\n".join(lines) for ns in (1, 2, 3))

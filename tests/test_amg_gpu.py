@@ -76,6 +76,23 @@ def test_mask_stats_on_designed_planes(H, W, oh, ow):
     assert bool(amg.stability(c)[0].isnan())
 
 
+def test_mask_stats_reduces_128_bands_from_the_last_one():
+    """(5, 7) -> (4096, 33) is 128 bands a plane, two trips of the finish kernel's loop over the slots.  Plane 0: only the last source
+    pixel is above the threshold, so every count and the box's minima and maxima come from the last bands and the last columns while
+    all other slots hold the identity; plane 1: everything below, box 0, 0, 0, 0.  Exact against vdr.amg.mask_stats_torch."""
+    from vdr import amg, ops
+    H, W, oh, ow = 5, 7, 4096, 33
+    lg = torch.full((2, H, W), -2.0)
+    lg[0, H - 1, W - 1] = 5.0
+    for thr, off in THRESHOLDS:
+        want_c, want_b = amg.mask_stats_torch(lg, (oh, ow), thr, off)
+        c, b = ops.mask_stats(lg.to(DEV), (oh, ow), thr, off)
+        assert _same(c, want_c) and _same(b, want_b), (thr, off)
+        x0, y0, x1, y1 = b[0].tolist()
+        assert c[0, 1].item() > 0 and (x1, y1) == (ow - 1, oh - 1) and y0 > oh - 2 * oh // H and x0 > ow - 2 * ow // W   # inside the last source pixel's reach
+        assert c[1].tolist() == [0, 0, 0] and b[1].tolist() == [0, 0, 0, 0]
+
+
 def test_mask_stats_memory_contract():
     """outputs and workspace of exactly the promised size between canaries; a workspace one byte short is VDR_ERR_WORKSPACE with
     nothing written"""

@@ -7,8 +7,6 @@ import ctypes as C
 import glob
 import os
 import re
-import shutil
-import subprocess
 import types
 
 import numpy as np
@@ -16,6 +14,7 @@ import pytest
 import torch
 
 import components_ref as CR
+import host_program
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -134,17 +133,9 @@ def test_the_kernels_passes_run_on_the_host_in_both_orders(tmp_path, sanitize):
     once, the seam pass enumerates every straddling pair, every index stays in bounds, and the passes themselves, run tile by
     tile forward and reversed under a step cap, give the breadth-first search's roots and areas; the second build runs it under
     the address and undefined-behaviour sanitizers (host code, stand-alone)"""
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++") or os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    exe = os.path.join(str(tmp_path), "components_map_cases")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", *flags, "-I", CSRC, os.path.join(HERE, "components_map_cases.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    r = subprocess.run([exe], capture_output=True, text=True)
-    print(r.stdout[-3000:])
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    lines = r.stdout.splitlines()
-    assert lines[-1] == "cases 38 fails 0" and "FAIL" not in r.stdout
+    out = host_program.run("components_map_cases", tmp_path, sanitize)
+    lines = out.splitlines()
+    assert lines[-1] == "cases 38 fails 0" and "FAIL" not in out
     assert sum(ln.endswith(" fails 0") and ln.startswith("H ") for ln in lines) == 38
     assert any(ln.startswith("H 300 W 517: tiles 45 seam items 4468 chunks 38 ") for ln in lines)
     assert any(ln.startswith(f"H {2 * T + 1} W {2 * T + 1}: tiles 9 ") for ln in lines) and any(ln.startswith("H 1 W 1: tiles 1 seam items 0 ") for ln in lines)

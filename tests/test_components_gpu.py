@@ -199,6 +199,30 @@ def test_mask_clean_on_the_designs_made_for_it():
     assert changed.tolist() == [2, 0, 0] and stats[0].tolist() == [8, 0, 0, W - 1, H - 1]      # only the single pixel goes
 
 
+def test_mask_clean_reduces_more_than_64_chunks_a_plane():
+    """513 x 513 is 65 chunks of 4096 pixels, the smallest square at which the finish kernel's loop over a plane's slots makes a
+    second trip (lane 0 takes chunks 0 and 64).  Plane 0: 3 x 3 blobs in the first and the last corner and a single pixel at
+    (y 512, x 0), so islands below 2 drops one pixel and the box spans the plane; plane 1: set pixels in chunk 64 alone, so its
+    area and box come from the second trip only; plane 2: all clear.  Exact against vdr.components.clean_torch."""
+    from vdr import components as cc
+    from vdr import ops
+    S = 513
+    assert (S * S + 4095) // 4096 == 65 and 511 * S + 508 >= 64 * 4096
+    m = torch.zeros((3, S, S), dtype=torch.uint8)
+    m[0, :3, :3] = m[0, S - 3:, S - 3:] = 1
+    m[0, 512, 0] = 1
+    m[1, 511:513, 508:513] = 1
+    for kw in (dict(min_area=2, islands=True), dict(largest=True)):
+        wo, wc, ws = cc.clean_torch(m, **kw)
+        out, changed, stats = ops.mask_clean(m.to(DEV), **kw)
+        assert out.dtype == torch.uint8 and torch.equal(out.cpu(), wo) and _eq(changed, wc.numpy()) and _eq(stats, ws.numpy()), kw
+        assert changed[2].item() == 0 and stats[2].tolist() == [0, 0, 0, 0, 0]                 # the all-clear plane
+        if "islands" in kw:
+            assert changed.tolist() == [2, 0, 0] and stats[:2].tolist() == [[18, 0, 0, 512, 512], [10, 508, 511, 512, 512]]
+        else:
+            assert changed.tolist() == [2, 0, 0] and stats[:2].tolist() == [[9, 0, 0, 2, 2], [10, 508, 511, 512, 512]]
+
+
 def test_mask_clean_memory_contract():
     from vdr import _lib
     lib = _lib.load()

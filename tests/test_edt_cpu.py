@@ -9,8 +9,6 @@ import ctypes as C
 import glob
 import os
 import re
-import shutil
-import subprocess
 import types
 
 import numpy as np
@@ -18,6 +16,7 @@ import pytest
 import torch
 
 import edt_ref as ER
+import host_program
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -203,17 +202,9 @@ def test_the_kernels_passes_run_on_the_host_in_both_orders(tmp_path, sanitize):
     once, every index stays inside the promised extents, and the passes themselves, run thread by thread forward and reversed
     with every search under its step cap, give the brute-force d2, nearest and peak; the second build runs it under the address
     and undefined-behaviour sanitizers (host code, stand-alone)"""
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++") or os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    exe = os.path.join(str(tmp_path), "edt_map_cases")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", *flags, "-I", CSRC, os.path.join(HERE, "edt_map_cases.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    r = subprocess.run([exe], capture_output=True, text=True)
-    print(r.stdout[-3000:])
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    lines = r.stdout.splitlines()
-    assert lines[-1] == "cases 57 fails 0" and "FAIL" not in r.stdout
+    out = host_program.run("edt_map_cases", tmp_path, sanitize)
+    lines = out.splitlines()
+    assert lines[-1] == "cases 57 fails 0" and "FAIL" not in out
     assert sum(ln.endswith(" fails 0") and ln.startswith("H ") for ln in lines) == 57
     assert any(ln.startswith("H 300 W 517: seg 9 pitch 10 rblocks 75 ctiles 171 ") for ln in lines)
     assert any(ln.startswith("H 1 W 4096: seg 64 pitch 66 rblocks 1 ctiles 64 ") for ln in lines) and any(ln.startswith("H 4096 W 1: seg 1 pitch 2 ") for ln in lines)
@@ -240,8 +231,9 @@ def test_new_symbols_are_declared_bound_and_listed_in_the_makefile():
     assert lib.vdr_distance_transform_workspace_bytes(64, 1024, 1024) == (2 + 1 / 128) * 64 * 1024 * 1024
     for bad in ((0, 4, 4), (65536, 4, 4), (1, 0, 4), (1, 4, 0), (1, 4, 4097), (1, 4097, 4)):
         assert lib.vdr_distance_transform_workspace_bytes(*bad) == 0
-    # no atomics in the new file; components.hip stays the only kernel source with any
-    text = open(os.path.join(CSRC, "edt.hip")).read() + open(os.path.join(CSRC, "edt_map.h")).read()
+    # no atomics in the new file nor in the reduction it shares; components.hip stays the only kernel source with any
+    text = "".join(open(os.path.join(CSRC, f)).read() for f in ("edt.hip", "edt_map.h", "plane_reduce.h"))
+    assert "plane_reduce.h" in mk
     assert not re.search(r"\batomic(Add|Min|Max|CAS|Or)\b|__hip_atomic", text)
     assert "INTEGER ATOMICS live in this file and only here" in open(os.path.join(CSRC, "components.hip")).read()
 

@@ -130,6 +130,24 @@ def test_designed_planes_have_their_closed_forms(H, W):
             assert int(nearest[k, 1, xm]) == 0 and int(nearest[k, H - 2, xm]) == (H - 1) * W
 
 
+def test_the_peak_reduces_171_tiles_from_the_first_and_the_last():
+    """300 x 517 is 171 tiles a plane (19 x 9 of 16 x 64), three trips of the peak kernel's loop over the slots.  Plane 0: 3 x 3 blocks
+    in the first and in the last tile and single pixels between them: two equal maxima, the lowest index wins; plane 1: the block
+    of the last tile alone is the unique maximum; plane 2: nothing selected, (0, -1).  Exact against vdr.morphology.edt_torch."""
+    from vdr import morphology as mo
+    from vdr import ops
+    H, W = 300, 517
+    m = torch.zeros((3, H, W), dtype=torch.uint8)
+    m[:2, 296:299, 513:516] = 1                                                # rows 288 .. 299, columns 512 .. 516: the last tile
+    m[0, 1:4, 1:4] = 1
+    m[:2, 150, ::7] = 1
+    want_d2, want_peak = mo.edt_torch(m, return_peak=True)
+    assert want_peak.tolist() == [[4, 2 * W + 2], [4, 297 * W + 514], [0, -1]]
+    d2, peak = ops.distance_transform(m.to(DEV), return_peak=True)
+    assert _eq(d2, want_d2.numpy()) and _eq(peak, want_peak.numpy())
+    assert _eq(ops.distance_transform(m.to(DEV), return_peak=True, return_d2=False), want_peak.numpy())   # the peak alone
+
+
 def test_distance_transform_memory_contract():
     """outputs and workspace of exactly the promised size between canaries; a workspace one byte short is VDR_ERR_WORKSPACE with
     the canary-filled outputs untouched; null optional outputs are not touched (whatever is not asked for stays canary)"""

@@ -5,13 +5,12 @@ the golden files; chunked search equals the unchunked one; vdr.ops.knn refuses o
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import host_program
 import knn_ref as kr
 import nn_cosine_ref as nref
 
@@ -98,15 +97,7 @@ def test_work_bytes_is_what_the_plan_says():
 
 def test_the_map_walk_finds_every_address_inside_its_extent(tmp_path):
     """tests/knn_map_cases.cpp, a host program with its own main, over the header the kernels include"""
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++") or os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    exe = os.path.join(str(tmp_path), "knn_map_cases")
-    r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-I", CSRC, os.path.join(HERE, "knn_map_cases.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    r = subprocess.run([exe], capture_output=True, text=True)
-    print(r.stdout)
-    assert r.returncode == 0, r.stdout[-2000:]
-    lines = r.stdout.splitlines()
+    lines = host_program.run("knn_map_cases", tmp_path).splitlines()
     assert lines[-1] == f"cases {len(lines) - 1}" and len(lines) > 100 and all(line.startswith("ok ") for line in lines[:-1])
     for shape in ("8x3969x3969 d=768 k=16 ", "8x3969x3969 d=768 k=1 ", "64x196x196 d=768 ", "32x729x729 d=768 ", "1x3969x3969 d=768 ",
                   "1x1024x65536 d=768 ", "1x8192x8192 d=384 ", "3x300x700 d=64 k=5 ld=64/64 stride=19200/0:",

@@ -7,14 +7,13 @@ propagate_labels and find_correspondences(radius=)."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 import types
 
 import numpy as np
 import pytest
 import torch
 
+import host_program
 import local_corr_ref as lref
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -103,15 +102,7 @@ def test_work_bytes_is_positive_granular_and_monotone():
 
 def test_the_mapping_covers_every_query_slot_once(tmp_path):
     """tests/local_corr_map_cases.cpp, a host program with its own main, over the header the kernel includes"""
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++") or os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    exe = os.path.join(str(tmp_path), "local_corr_map_cases")
-    r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-I", CSRC, os.path.join(HERE, "local_corr_map_cases.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    r = subprocess.run([exe], capture_output=True, text=True)
-    print(r.stdout)
-    assert r.returncode == 0, r.stdout[-2000:]
-    lines = r.stdout.splitlines()
+    lines = host_program.run("local_corr_map_cases", tmp_path).splitlines()
     assert len(lines) == 17 * 4 and all(line.startswith("ok ") for line in lines)
     assert any(line.startswith("ok 1x1 r=8 ") for line in lines) and any(line.startswith("ok 9x17 r=4 ") for line in lines)
 

@@ -5,14 +5,13 @@ Python refusals, torch mask_box on designed masks, and the mapping of the fused 
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 import types
 
 import numpy as np
 import pytest
 import torch
 
+import host_program
 import sam_decoder_ref as R
 import sam_prompt_ref as PR
 
@@ -278,16 +277,7 @@ def test_best_and_as_mask_input_select_per_problem():
 def test_the_mask_embed_mapping_reads_in_bounds_and_writes_every_key_once(tmp_path, sanitize):
     """tests/mask_embed_map_cases.cpp, a host program with its own main, over the header the kernel includes; the second build
     runs it under the address and undefined-behaviour sanitizers (host code, stand-alone)"""
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++") or os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    exe = os.path.join(str(tmp_path), "mask_embed_map_cases")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", *flags, "-I", CSRC, os.path.join(HERE, "mask_embed_map_cases.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    r = subprocess.run([exe], capture_output=True, text=True)
-    print(r.stdout[-3000:])
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    lines = r.stdout.splitlines()
+    lines = host_program.run("mask_embed_map_cases", tmp_path, sanitize).splitlines()
     assert lines[-1] == "cases 64 fails 0"
     assert sum("unwritten 0 twice 0" in ln for ln in lines) == 64
     # ragged last tile (g 3, P 3: 27 rows), tiles that span two problems (g 10: 100 rows a problem), the largest grid

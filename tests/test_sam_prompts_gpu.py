@@ -108,6 +108,32 @@ def test_mask_box_equals_its_torch_statement_bit_for_bit(S):
     assert box[1].tolist() == [0.0, 0.0, img / S + 8.0, img / S + 8.0] and box[5].tolist() == [0.0, 0.0, float(img), float(img)]
 
 
+@pytest.mark.parametrize("H,W,last,pair", [(256, 256, (3, 255), ((0, 1), (3, 200))),   # 4 pixels a load: thread 255 owns pixels 1020 .. 1023
+                                           (40, 7, (36, 3), ((0, 2), (28, 4)))])       # W = 7, one pixel a load: thread 255 owns pixel 255
+def test_mask_box_reduces_the_last_thread_and_the_outer_waves(H, W, last, pair):
+    """the workgroup's reduction at its edges: the only pixel above threshold belongs to thread 255 (the last lane of the last
+    wave); a pair that waves 0 and 3 own; an empty plane, which returns prev.  (y, x) pixels; the other threads stay at the
+    identity"""
+    from vdr import ops
+    lg = torch.full((3, H, W), -1.0)
+    lg[0, last[0], last[1]] = 2.0
+    for y, x in pair:
+        lg[1, y, x] = 2.0
+    lg = lg.to(DEV)
+    prev = _randn((3, 4), 17, 50.0).abs().to(DEV)
+    for margin in (0.0, 3.5):
+        box, area = ops.mask_box(lg, prev, 1024, margin=margin)
+        want_box, want_area = PR.mask_box_ref(lg, prev, 1024, margin, 0.0)
+        torch.cuda.synchronize()
+        assert torch.equal(box.view(torch.int32), want_box.view(torch.int32)) and torch.equal(area, want_area), margin
+        assert area.tolist() == [1, 2, 0] and torch.equal(box[2], prev[2])
+    box, _ = ops.mask_box(lg, prev, 1024)
+    sx, sy = 1024 / W, 1024 / H                                                                   # (exact in fp32 for 256; the reference holds W = 7)
+    if W == 256:
+        assert box[0].tolist() == [last[1] * sx, last[0] * sy, (last[1] + 1) * sx, (last[0] + 1) * sy]
+        assert box[1].tolist() == [1 * sx, 0.0, 201 * sx, 4 * sy]
+
+
 # ---- the decode ------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def goldens(golden_dir):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel-level A/B of two builds of libvdr.so in ONE process, interleaved rounds (guide rule 24): both libraries are
 dlopen'ed side by side and the attention ops / vdr_op_linear_packed are called through ctypes on the same tensors.
-   python tools/ab_libs.py path/to/libA.so[:variant] path/to/libB.so[:variant] [attention|gemm|descriptors]
+   python tools/ab_libs.py path/to/libA.so[:variant] path/to/libB.so[:variant] [attention|gemm|descriptors|masks]
 (":variant" = the tile variant handed to vdr_op_linear_packed by that side, e.g. the same library twice as lib.so:0 lib.so:31)
 attention: first a bitwise pass (torch.equal of the two libraries' outputs) over the smallest shapes that reach every
 instantiation of the fused attention kernels, then the timing; exit status 1 if any output differs.  For the spread of
@@ -9,7 +9,10 @@ the timing run a copy of library A against it (a second path: the same path is t
 descriptors: the same two passes for the descriptor-analysis ops (nn_cosine, affinity_bits, local_correlation, the PCA ops, the
 Gram side, k-means, mahalanobis): bitwise on the smallest shapes that reach every path (the shapes of the exact tests), every element of
 every output compared; timed on the shapes of tools/correspondence_bench.py, spectral_bench.py (the affinity shapes),
-local_correlation_bench.py, pca_bench.py, pca_topk_bench.py and kmeans_bench.py."""
+local_correlation_bench.py, pca_bench.py, pca_topk_bench.py and kmeans_bench.py.
+masks: the same two passes for the mask-plane ops (mask_stats, mask_binarize, connected_components, mask_clean in every mode,
+distance_transform in every output combination, mask_box where both libraries export it): bitwise on the shapes of their exact
+tests, int32 and uint8 planes included; timed on the shapes of tools/amg_bench.py, components_bench.py and edt_bench.py."""
 import ctypes as C
 import os
 import sys
@@ -282,15 +285,23 @@ def descriptors_equal(libs, st):
               for imgs in (1, 2)]
     cases += [gram_case(st, 2, t, d, bf16, pad=32) for t in (17, 129, 300) for d in (96, GRAM_CHUNK + 32) for bf16 in (True, False)]
     cases += [kmeans_case(st, 2, 1, R, d, k) for R in (1, 129, 300) for k in (1, 127, 130) if k <= R for d in (96, 416)]
+    return cases_equal(libs, cases)
+
+
+def cases_equal(libs, cases, u8_fill=None):
+    """every element of every output of every case, library A against library B; u8_fill: the value no uint8 output may keep"""
+    def undefined(t):
+        if t.dtype == torch.uint8:  # (without u8_fill: the affinity words as bytes -- in a bit field every pattern is a value, the fill included)
+            return 0 if u8_fill is None else int((t == u8_fill).sum())
+        return int((torch.isnan(t) if t.dtype.is_floating_point else t == _INT_FILL).sum())
     bad = 0
     for name, run in cases:
         outs = [run(lib) for lib in libs]
         torch.cuda.synchronize()
         notes = []  # per output that fails: its index, elements left undefined by A / B, elements whose bits differ
         for i, (a, b) in enumerate(zip(*outs)):
-            # (uint8: the affinity words as bytes -- in a bit field every pattern is a value, the fill included)
-            undef = [0 if t.dtype == torch.uint8 else int((torch.isnan(t) if t.dtype.is_floating_point else t == _INT_FILL).sum()) for t in (a, b)]
-            diff = int((a.view(torch.int32) != b.view(torch.int32)).sum())
+            undef = [undefined(t) for t in (a, b)]
+            diff = int((a != b).sum()) if a.dtype == torch.uint8 else int((a.view(torch.int32) != b.view(torch.int32)).sum())
             if undef[0] or undef[1] or diff:
                 notes.append(f"out{i} undefined {undef[0]}/{undef[1]} differ {diff} of {a.numel()}")
         same = len(outs[0]) == len(outs[1]) and not notes
@@ -316,8 +327,135 @@ def descriptors_timed(st):
     return timed
 
 
+# ---- mask-plane ops ---------------------------------------------------------------------------------------------------
+# Every output is an integer (mask_box: floats from integers by a fixed chain), so "equal" is the whole requirement.  uint8 outputs
+# are prefilled with _U8_FILL, which no op writes (they write 0 / 1).
+_U8_FILL = 255
+
+
+def _blobs(P, H, W, seed):
+    """uint8 [P, H, W]: smooth blobs with holes and specks (a coarse random field up-sampled, a little salt on top)"""
+    g = torch.Generator().manual_seed(seed)
+    low = torch.randn((P, 1, max(H // 16, 1) + 1, max(W // 16, 1) + 1), generator=g)
+    m = torch.nn.functional.interpolate(low, size=(H, W), mode="bilinear", align_corners=False)[:, 0] > 0.1
+    return (m ^ (torch.rand((P, H, W), generator=g) < 0.02)).to(torch.uint8).cuda()
+
+
+def logits_case(st, H, W, oh, ow, P, tokens=None):
+    """mask_stats and mask_binarize on [P, 4, H, W] logits: one token in place, tokens 1 .. 3 in place (groups), or dense"""
+    lg = (torch.randn((P, 4, H, W), generator=torch.Generator().manual_seed(H + W + oh)) * 3).cuda()
+    if tokens is None:
+        a = (lg.data_ptr(), H * W, 4 * P, 0, 4 * P)
+    elif tokens == 1:
+        a = (lg[:, 2].data_ptr(), H * W, 1, 4 * H * W, P)
+    else:
+        a = (lg[:, 1:].data_ptr(), H * W, 3, 4 * H * W, 3 * P)
+    n = a[4]
+
+    def run(lib, keep=None):
+        o = _Bufs(keep)
+        work = o.work(lib.vdr_mask_stats_workspace_bytes(n, H, W, oh, ow))
+        counts, box = o.out(n, 3, dtype=torch.int32), o.out(n, 4, dtype=torch.int32)
+        assert lib.vdr_op_mask_stats(*a, H, W, oh, ow, 0.25, 0.75, work.data_ptr(), work.numel(), counts.data_ptr(), box.data_ptr(), st) == 0
+        plane = o.out(n, oh, ow, dtype=torch.uint8, value=_U8_FILL)
+        assert lib.vdr_op_mask_binarize(*a, H, W, oh, ow, 0.25, work.data_ptr(), work.numel(), plane.data_ptr(), st) == 0
+        return [counts, box, plane]
+    return f"mask_stats+binarize {H}x{W}->{oh}x{ow} P{n} {'dense' if tokens is None else 'token' if tokens == 1 else 'groups'}", run
+
+
+def components_case(st, P, H, W, ops=("label", 0, 1, 2, 3, 4, 5)):
+    """connected_components (conn 8, value 1) and mask_clean in every mode (0: the copy; 1 holes, 2 islands, 4 largest)"""
+    m = _blobs(P, H, W, H + 3 * W)
+
+    def run(lib, keep=None):
+        o = _Bufs(keep)
+        outs = []
+        if "label" in ops:
+            work = o.work(lib.vdr_connected_components_workspace_bytes(P, H, W))
+            root, area, count = o.out(P, H, W, dtype=torch.int32), o.out(P, H, W, dtype=torch.int32), o.out(P, dtype=torch.int32)
+            assert lib.vdr_op_connected_components(m.data_ptr(), P, H, W, 8, 1, work.data_ptr(), work.numel(), root.data_ptr(), area.data_ptr(),
+                                                   count.data_ptr(), st) == 0
+            outs += [root, area, count]
+        work = o.work(lib.vdr_mask_clean_workspace_bytes(P, H, W))
+        for mode in (v for v in ops if v != "label"):
+            out = o.out(P, H, W, dtype=torch.uint8, value=_U8_FILL)
+            changed, stats = o.out(P, dtype=torch.int32), o.out(P, 5, dtype=torch.int32)
+            assert lib.vdr_op_mask_clean(m.data_ptr(), P, H, W, 9, 4 if mode & 1 else 8, mode, work.data_ptr(), work.numel(), out.data_ptr(),
+                                         changed.data_ptr(), stats.data_ptr(), st) == 0
+            outs += [out, changed, stats]
+        return outs
+    return f"components {'+'.join(str(v) for v in ops)} P{P} {H}x{W}", run
+
+
+EDT_OUTPUTS = ("d2", "nearest", "peak", "within", "d2+nearest+peak", "within+peak", "d2+peak")
+
+
+def edt_case(st, P, H, W, outputs, value=1, outside=0):
+    """distance_transform with one combination of its outputs (the peak alone included)"""
+    m = _blobs(P, H, W, 5 * H + W)
+    if P > 1:
+        m[0] = 0  # a plane with nothing selected (value 1): peak (0, -1)
+    want = outputs.split("+")
+
+    def run(lib, keep=None):
+        o = _Bufs(keep)
+        work = o.work(lib.vdr_distance_transform_workspace_bytes(P, H, W))
+        d2 = o.out(P, H, W, dtype=torch.int32) if "d2" in want else None
+        nearest = o.out(P, H, W, dtype=torch.int32) if "nearest" in want else None
+        peak = o.out(P, 2, dtype=torch.int32) if "peak" in want else None
+        within = o.out(P, H, W, dtype=torch.uint8, value=_U8_FILL) if "within" in want else None
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        assert lib.vdr_op_distance_transform(m.data_ptr(), P, H, W, value, outside, 10, work.data_ptr(), work.numel(), ptr(d2), ptr(nearest), ptr(peak),
+                                             ptr(within), st) == 0
+        return [t for t in (d2, nearest, peak, within) if t is not None]
+    return f"edt {outputs} P{P} {H}x{W} v{value} o{outside}", run
+
+
+def box_case(st, P, H, W):
+    """mask_box: random planes, one empty plane (prev comes back), one plane whose only pixel is the last"""
+    lg = torch.randn((P, H, W), generator=torch.Generator().manual_seed(H * W)).cuda() - 1.5
+    lg[0] = -1.0
+    if P > 1:
+        lg[1] = -1.0
+        lg[1, H - 1, W - 1] = 1.0
+    prev = torch.rand((P, 4), generator=torch.Generator().manual_seed(P)).cuda() * 100
+
+    def run(lib, keep=None):
+        o = _Bufs(keep)
+        boxes, area = o.out(P, 4), o.out(P, dtype=torch.int32)
+        assert lib.vdr_op_mask_box(lg.data_ptr(), H * W, prev.data_ptr(), boxes.data_ptr(), area.data_ptr(), P, H, W, 1024, 2.5, 0.0, st) == 0
+        return [boxes, area]
+    return f"mask_box P{P} {H}x{W}", run
+
+
+def masks_equal(libs, st):
+    """the shapes of the exact tests (tests/test_amg_gpu.py, test_components_gpu.py, test_edt_gpu.py, the mask_box cases of
+    test_sam_prompts_gpu.py), the 65-chunk plane of mask_clean and the 128-band plane of mask_stats included"""
+    cases = [logits_case(st, H, W, oh, ow, P, tok) for (H, W, oh, ow, P) in ((1, 1, 3, 5, 3), (8, 8, 32, 32, 130), (12, 20, 50, 75, 130), (17, 3, 9, 2, 3),
+                                                                             (64, 64, 256, 256, 3), (256, 256, 1024, 1024, 1), (5, 7, 4096, 33, 3))
+             for tok in (None, 1, 3)]
+    planes = ((1, 1), (1, 129), (2, 64), (63, 65), (64, 64), (65, 129), (129, 129), (129, 257), (300, 517), (513, 513))
+    cases += [components_case(st, 3, H, W) for (H, W) in planes]
+    cases += [edt_case(st, 3, H, W, outputs) for (H, W) in planes + ((1, 4096), (4096, 1)) for outputs in EDT_OUTPUTS]
+    cases += [edt_case(st, 3, 300, 517, "d2+peak", value, outside) for value in (0, 1) for outside in (0, 1)]
+    if all(hasattr(lib, "vdr_op_mask_box") for lib in libs):
+        cases += [box_case(st, 3, H, W) for (H, W) in ((1, 1), (5, 7), (16, 16), (33, 7), (256, 256), (64, 1028))]
+    return cases_equal(libs, cases, u8_fill=_U8_FILL)
+
+
+def masks_timed(libs, st):
+    """the shapes of tools/amg_bench.py, components_bench.py and edt_bench.py; mask_box on 256 x 256 planes"""
+    timed = [logits_case(st, 256, 256, 1024, 1024, 64, 3), logits_case(st, 256, 256, 1024, 1024, 1, 1)]
+    for P, side in ((1, 1024), (64, 1024), (192, 256)):
+        timed += [components_case(st, P, side, side, ("label",)), components_case(st, P, side, side, (3,)), components_case(st, P, side, side, (4,))]
+        timed += [edt_case(st, P, side, side, "d2"), edt_case(st, P, side, side, "peak"), edt_case(st, P, side, side, "d2+nearest+peak")]
+    if all(hasattr(lib, "vdr_op_mask_box") for lib in libs):
+        timed += [box_case(st, 1, 256, 256), box_case(st, 64, 256, 256)]
+    return timed
+
+
 def main():
-    specs = [a.split(":") for a in sys.argv[1:3]]
+    specs =[a.split(":") for a in sys.argv[1:3]]
     libs = [load(sp[0]) for sp in specs]
     variants = [int(sp[1]) if len(sp) > 1 else 0 for sp in specs]
     what = sys.argv[3] if len(sys.argv) > 3 else "attention"
@@ -332,9 +470,9 @@ def main():
             out = torch.empty(shape, device="cuda", dtype=torch.bfloat16)
             for li, lib in enumerate(libs):
                 cases.append((f"{name} lib{'AB'[li]}", lambda lib=lib, call=call, out=out: call(lib, out)))
-    elif what == "descriptors":
-        bad = descriptors_equal(libs, st)
-        for name, run in descriptors_timed(st):
+    elif what in ("descriptors", "masks"):
+        bad = descriptors_equal(libs, st) if what == "descriptors" else masks_equal(libs, st)
+        for name, run in (descriptors_timed(st) if what == "descriptors" else masks_timed(libs, st)):
             keep = []
             for li, lib in enumerate(libs):
                 cases.append((f"{name} lib{'AB'[li]}", lambda lib=lib, run=run, keep=keep: 0 if run(lib, keep) is not None else 1))

@@ -9,9 +9,10 @@
 //                       the label plane in global memory (find + atomicMin).
 //   cc_flatten_kernel   every pixel follows its chain to the root and stores it; a tile root that is no plane root adds its
 //                       count to the plane root's (one atomicAdd per (tile, component)); plane roots are counted.
-//   cc_best_kernel      the per-plane minimum of the key (2^31 - 1 - area, root): the largest component, lowest root on a tie.
-//   cc_apply_kernel     one step of mask_clean per pixel from area[root]; the chunk's changed flag, area and box of the result
-//                       go to ONE partial slot (shuffles, then LDS), which cc_finish_kernel (one wave per plane) reduces.
+//   cc_best_kernel      the per-plane minimum of the key (2^31 - 1 - area, root): the largest component, lowest root on a tie
+//                       (the wave's minimum by plane_reduce.h, then one atomicMin per wave).
+//   cc_apply_kernel     one step of mask_clean per pixel from area[root]; the chunk's changed count, area and box of the result
+//                       go to ONE partial slot, which cc_finish_kernel (one wave per plane) reduces: plane_reduce.h, both.
 //   mask_binarize_kernel  mask_stats' up-sampling, written instead of counted: ms_axis and the blend order of mask_stats.hip.
 //
 // INTEGER ATOMICS live in this file and only here: atomicMin on labels and on the best key, atomicAdd on pixel counts.  The
@@ -25,6 +26,7 @@
 #include "vdr_kernels.h"
 #include "mask_stats_map.h"
 #include "components_map.h"
+#include "plane_reduce.h"
 
 namespace vdr {
 
@@ -77,12 +79,6 @@ __global__ __launch_bounds__(CC_THREADS) void cc_seam_kernel(CcGeom q, int conn8
   cc_seam_unions<CcGlobal>(q, s, conn8, L + (int64_t)blockIdx.y * q.H * q.W);
 }
 
-__device__ inline int cc_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);  // fixed trip count: six halvings
-  return v;
-}
-
 // root may be L itself (mask_clean flattens in place): no __restrict__ on the two
 __global__ __launch_bounds__(CC_THREADS) void cc_flatten_kernel(CcGeom q, int* L, int* area, int* root, int* __restrict__ count) {
   const int plane = blockIdx.y, HW = q.H * q.W;
@@ -92,7 +88,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_flatten_kernel(CcGeom q, int* L
     const int i = blockIdx.x * CC_CHUNK + k * CC_THREADS + threadIdx.x;
     if (i < HW) roots += cc_flatten_pixel<CcGlobal>(i, L + off, area + off, root + off);
   }
-  roots = cc_wave_sum(roots);
+  roots = pr_wave_sum(roots);
   if ((threadIdx.x & 63) == 0 && roots) atomicAdd(count + plane, roots);
 }
 
@@ -107,84 +103,57 @@ __global__ __launch_bounds__(CC_THREADS) void cc_best_kernel(CcGeom q, const int
       key = u < key ? u : key;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {  // fixed trip count: six halvings
-    const unsigned hi = __shfl_xor((unsigned)(key >> 32), o), lo = __shfl_xor((unsigned)key, o);
-    const unsigned long long u = ((unsigned long long)hi << 32) | lo;
-    key = u < key ? u : key;
-  }
+  key = pr_wave_min_key(key);
   if ((threadIdx.x & 63) == 0 && key != CC_NO_BEST) atomicMin(best + plane, key);
 }
+
+using CcAcc = PlaneAcc<2>;  // sums: pixels the step changed (a flag: tested against 0), area of the result (plane_reduce.h)
+constexpr int CC_CHANGED = 0, CC_AREA = 1;
+static_assert(CC_SLOT == PR_SLOT, "the partial slot");
 
 // src may be out itself (the second step reads the first step's result): a pixel is read and written by its own thread only
 __global__ __launch_bounds__(CC_THREADS) void cc_apply_kernel(CcGeom q, int step, int min_area, const uint8_t* src, const int* __restrict__ L,
                                                               const int* __restrict__ area, const unsigned long long* __restrict__ best,
                                                               uint8_t* out, int32_t* __restrict__ slots) {
-  __shared__ int wred[CC_THREADS / 64][6];
+  __shared__ int wred[CC_THREADS / 64][PR_SLOT];
   const int plane = blockIdx.y, HW = q.H * q.W, tid = threadIdx.x;
   const int64_t off = (int64_t)plane * HW;
   const int broot = step >= CC_STEP_ISLANDS ? cc_best_root(best[plane]) : -1;
-  int acc[6] = {0, 0, q.W, q.H, -1, -1};  // changed, area, min x, min y, max x, max y
+  CcAcc acc = pr_identity<2>(q.W, q.H);
   for (int k = 0; k < CC_PER_THREAD; ++k) {  // fixed trip count
     const int i = blockIdx.x * CC_CHUNK + k * CC_THREADS + tid;
     if (i >= HW) continue;
     const int set = src[off + i] != 0;
     const int o = cc_apply_pixel(step, set, i, L + off, area + off, broot, min_area);
     out[off + i] = (uint8_t)o;
-    acc[0] |= o != set;
+    acc.sum(CC_CHANGED) += o != set;
     if (o) {
-      const int y = i / q.W, x = i - y * q.W;
-      ++acc[1];
-      acc[2] = x < acc[2] ? x : acc[2], acc[3] = y < acc[3] ? y : acc[3];
-      acc[4] = x > acc[4] ? x : acc[4], acc[5] = y > acc[5] ? y : acc[5];
+      const int y = i / q.W;
+      ++acc.sum(CC_AREA);
+      acc.take(i - y * q.W, y);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {  // fixed trip count: six halvings
-    const int b0 = __shfl_xor(acc[0], o), b1 = __shfl_xor(acc[1], o), b2 = __shfl_xor(acc[2], o), b3 = __shfl_xor(acc[3], o),
-              b4 = __shfl_xor(acc[4], o), b5 = __shfl_xor(acc[5], o);
-    acc[0] |= b0, acc[1] += b1;
-    acc[2] = b2 < acc[2] ? b2 : acc[2], acc[3] = b3 < acc[3] ? b3 : acc[3];
-    acc[4] = b4 > acc[4] ? b4 : acc[4], acc[5] = b5 > acc[5] ? b5 : acc[5];
-  }
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) wred[tid >> 6][k] = acc[k];
-  }
-  __syncthreads();
-  if (tid < 6) {
-    int v = wred[0][tid];
-    for (int w = 1; w < CC_THREADS / 64; ++w) {  // fixed trip count
-      const int u = wred[w][tid];
-      v = tid == 0 ? (v | u) : tid == 1 ? v + u : tid < 4 ? (u < v ? u : v) : (u > v ? u : v);
-    }
-    slots[((int64_t)plane * q.chunks + blockIdx.x) * CC_SLOT + tid] = v;
-  }
+  pr_block_store<2, CC_THREADS / 64>(acc, wred, slots + ((int64_t)plane * q.chunks + blockIdx.x) * CC_SLOT);
 }
 
 // one wave per plane: slots_a (the hole step's, may be null) gives bit 0 of changed, slots_b bit 1 and the statistics
 __global__ __launch_bounds__(64) void cc_finish_kernel(CcGeom q, const int32_t* __restrict__ slots_a, const int32_t* __restrict__ slots_b,
                                                        int32_t* __restrict__ changed, int32_t* __restrict__ stats) {
   const int plane = blockIdx.x, lane = threadIdx.x;
-  int ca = 0, acc[6] = {0, 0, q.W, q.H, -1, -1};
+  int ca = 0;
+  CcAcc acc = pr_identity<2>(q.W, q.H);
   for (int c = lane; c < q.chunks; c += 64) {  // chunks is finite and c grows by 64
     const int64_t s = ((int64_t)plane * q.chunks + c) * CC_SLOT;
-    if (slots_a) ca |= slots_a[s];
-    acc[0] |= slots_b[s], acc[1] += slots_b[s + 1];
-    acc[2] = slots_b[s + 2] < acc[2] ? slots_b[s + 2] : acc[2], acc[3] = slots_b[s + 3] < acc[3] ? slots_b[s + 3] : acc[3];
-    acc[4] = slots_b[s + 4] > acc[4] ? slots_b[s + 4] : acc[4], acc[5] = slots_b[s + 5] > acc[5] ? slots_b[s + 5] : acc[5];
+    if (slots_a) ca += slots_a[s + CC_CHANGED];
+    acc = pr_combine(acc, pr_load<2>(slots_b + s));
   }
+  ca = pr_wave_sum(ca);
+  acc = pr_wave_reduce(acc);
+  if (lane) return;  // every lane holds the plane's integers; one writes them
+  changed[plane] = (ca ? 1 : 0) | (acc.sum(CC_CHANGED) ? 2 : 0);
+  stats[plane * 5] = acc.sum(CC_AREA);
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {  // fixed trip count: six halvings
-    const int a0 = __shfl_xor(ca, o), b0 = __shfl_xor(acc[0], o), b1 = __shfl_xor(acc[1], o), b2 = __shfl_xor(acc[2], o),
-              b3 = __shfl_xor(acc[3], o), b4 = __shfl_xor(acc[4], o), b5 = __shfl_xor(acc[5], o);
-    ca |= a0, acc[0] |= b0, acc[1] += b1;
-    acc[2] = b2 < acc[2] ? b2 : acc[2], acc[3] = b3 < acc[3] ? b3 : acc[3];
-    acc[4] = b4 > acc[4] ? b4 : acc[4], acc[5] = b5 > acc[5] ? b5 : acc[5];
-  }
-  if (lane == 0) changed[plane] = (ca ? 1 : 0) | (acc[0] ? 2 : 0);
-  if (lane == 1) stats[plane * 5] = acc[1];
-  if (lane >= 2 && lane < 6) stats[plane * 5 + lane - 1] = acc[1] > 0 ? acc[lane] : 0;  // an empty plane: 0, 0, 0, 0
+  for (int k = 0; k < 4; ++k) stats[plane * 5 + 1 + k] = acc.sum(CC_AREA) > 0 ? acc.box(k) : 0;  // an empty plane: 0, 0, 0, 0
 }
 
 // one thread per output pixel; the arithmetic of mask_stats_kernel: horizontal blends of the two source rows, then the vertical one

@@ -8,8 +8,9 @@
 //                      the row, the lower column on a tie) goes to the workspace, lane-contiguous.
 //   edt_col_kernel     a thread per pixel, lanes along x: d2 = min over y' of (y - y')^2 + g(y', x)^2 by edt_search, outwards from
 //                      y' = y until k^2 reaches the best so far; g rows are read through the cache, coalesced.  It writes d2,
-//                      nearest, the thresholded plane (each optional) and, for the peak, ONE partial slot per tile.
-//   edt_peak_kernel    one wave per plane reduces the plane's slots to (largest d2, lowest index that attains it).
+//                      nearest, the thresholded plane (each optional) and, for the peak, ONE partial slot per tile: the
+//                      largest key of the workgroup (edt_peak_key; the key reduction of plane_reduce.h).
+//   edt_peak_kernel    one wave per plane reduces the plane's slots to (largest d2, lowest index that attains it), likewise.
 //
 // No atomics: every output and every slot has one writer (components.hip stays the only file with integer atomics).
 // Every loop carries its termination argument beside it (here or in edt_map.h); the same code runs on the host first, thread by
@@ -18,6 +19,7 @@
 #include "vdr_dev.h"
 #include "vdr_kernels.h"
 #include "edt_map.h"
+#include "plane_reduce.h"
 
 namespace vdr {
 
@@ -37,16 +39,6 @@ __global__ __launch_bounds__(EDT_THREADS) void edt_row_kernel(const uint8_t* __r
   edt_row_scan(q, rb, outside, tid, row, sl, sr);
   __syncthreads();
   edt_row_store(q, rb, tid, row, g + off);
-}
-
-__device__ inline unsigned long long edt_wave_max(unsigned long long key) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {  // fixed trip count: six halvings
-    const unsigned hi = __shfl_xor((unsigned)(key >> 32), o), lo = __shfl_xor((unsigned)key, o);
-    const unsigned long long u = ((unsigned long long)hi << 32) | lo;
-    key = u > key ? u : key;
-  }
-  return key;
 }
 
 __global__ __launch_bounds__(EDT_THREADS) void edt_col_kernel(const short* __restrict__ g, EdtGeom q, int outside, int r2,
@@ -70,11 +62,8 @@ __global__ __launch_bounds__(EDT_THREADS) void edt_col_kernel(const short* __res
     key = u > key ? u : key;
   }
   if (!slots) return;  // the same in every thread
-  key = edt_wave_max(key);
-  if ((tid & 63) == 0) wred[tid >> 6] = key;
-  __syncthreads();
+  key = pr_block_max_key<EDT_THREADS / 64>(key, wred);
   if (tid == 0) {
-    for (int w = 1; w < EDT_RROWS; ++w) key = wred[w] > key ? wred[w] : key;  // fixed trip count
     const int64_t s = edt_slot(q, plane, t);
     slots[s] = edt_peak_d2(key), slots[s + 1] = edt_peak_index(key);
   }
@@ -89,7 +78,7 @@ __global__ __launch_bounds__(64) void edt_peak_kernel(EdtGeom q, const int32_t* 
     const unsigned long long u = slots[s + 1] < 0 ? 0ull : edt_peak_key(slots[s], slots[s + 1]);
     key = u > key ? u : key;
   }
-  key = edt_wave_max(key);
+  key = pr_wave_max_key(key);
   if (lane == 0) peak[2 * plane] = edt_peak_d2(key), peak[2 * plane + 1] = edt_peak_index(key);
 }
 

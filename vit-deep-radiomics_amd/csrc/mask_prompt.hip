@@ -11,13 +11,14 @@
 //   prompt_tokens   decoder_tokens_kernel's sibling for segment_anything's layout [iou; 4 mask tokens; np points; one padding
 //                   point if there is no box; 2 box corners if there is one].  Trigonometry in double, once per decode; with
 //                   boxes only it computes decoder_tokens_kernel's bits.
-//   mask_box        the box of a logit map (> threshold) for the next slice of a volume: one workgroup per problem, integer
-//                   min / max / count, a fixed tree through LDS, no atomics.
+//   mask_box        the box of a logit map (> threshold) for the next slice of a volume: one workgroup per problem, a count
+//                   and a box by the plane reduction of plane_reduce.h, no atomics.
 //
 // Built with -ffp-contract=off (Makefile): every multiply and add outside the explicit fmaf calls is rounded once.
 #include "vdr_dev.h"
 #include "vdr_kernels.h"
 #include "mask_embed_map.h"
+#include "plane_reduce.h"
 
 namespace vdr {
 
@@ -215,17 +216,14 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void mask_box_kernel(const float* __restrict__ logits, int64_t plane_stride, const float* __restrict__ prev,
                                                        float* __restrict__ boxes, int32_t* __restrict__ area, int H, int W, float img,
                                                        float margin, float threshold) {
-  __shared__ int red[5][256];
+  __shared__ int wred[4][PR_SLOT];
   const int p = blockIdx.x, tid = threadIdx.x;
   const float* lg = logits + (int64_t)p * plane_stride;
-  int x0 = W, x1 = -1, y0 = H, y1 = -1, cnt = 0;
+  PlaneAcc<1> acc = pr_identity<1>(W, H);  // the one sum: the count
   const int total = H * W;
   auto take = [&](int x, int y) {
-    x0 = x < x0 ? x : x0;
-    x1 = x > x1 ? x : x1;
-    y0 = y < y0 ? y : y0;
-    y1 = y > y1 ? y : y1;
-    ++cnt;
+    acc.take(x, y);
+    ++acc.sum(0);
   };
   if (VEC) {
     for (int idx = 4 * tid; idx < total; idx += 4 * 256) {
@@ -243,27 +241,17 @@ __global__ __launch_bounds__(256) void mask_box_kernel(const float* __restrict__
       }
     }
   }
-  red[0][tid] = x0, red[1][tid] = x1, red[2][tid] = y0, red[3][tid] = y1, red[4][tid] = cnt;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) {
-      red[0][tid] = red[0][tid + o] < red[0][tid] ? red[0][tid + o] : red[0][tid];
-      red[1][tid] = red[1][tid + o] > red[1][tid] ? red[1][tid + o] : red[1][tid];
-      red[2][tid] = red[2][tid + o] < red[2][tid] ? red[2][tid + o] : red[2][tid];
-      red[3][tid] = red[3][tid + o] > red[3][tid] ? red[3][tid + o] : red[3][tid];
-      red[4][tid] = red[4][tid] + red[4][tid + o];
-    }
-    __syncthreads();
-  }
+  pr_block_reduce<1, 4>(acc, wred);
   if (tid >= 4) return;
-  const int n = red[4][0];
+  const int n = pr_waves_value<1, 4>(wred, 0);
   if (tid == 0) area[p] = n;
   float v;
   if (n == 0) {
     v = prev[p * 4 + tid];
   } else {
     const float s = (tid & 1) ? img / (float)H : img / (float)W;
-    v = tid < 2 ? (float)red[2 * tid][0] * s - margin : (float)(red[2 * (tid - 2) + 1][0] + 1) * s + margin;
+    const int b = pr_waves_value<1, 4>(wred, 1 + tid);  // thread 0 .. 3: min x, min y, max x, max y
+    v = tid < 2 ? (float)b * s - margin : (float)(b + 1) * s + margin;
     v = v < 0.0f ? 0.0f : v > img ? img : v;
   }
   boxes[p * 4 + tid] = v;

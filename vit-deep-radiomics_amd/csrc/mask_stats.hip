@@ -7,53 +7,31 @@
 //                       columns: the horizontal blends of the two source rows of an output row depend on the column and the
 //                       source row alone, so the thread keeps them while the source rows stay the same -- at 4 x that is 1 LDS read
 //                       per 2 pixels instead of 4 per pixel -- and the rows' indices and weights come from a table in LDS
-//                       (one broadcast read per row).  Integer counts and min / max: shuffles inside the wave, the four waves
-//                       through LDS, ONE partial slot per band.
-//   mask_stats_finish   one wave per plane reduces the plane's slots and writes its seven integers.
+//                       (one broadcast read per row).  Three counts and a box: the plane reduction of plane_reduce.h, ONE
+//                       partial slot per band.
+//   mask_stats_finish   one wave per plane reduces the plane's slots (plane_reduce.h again) and writes its seven integers.
 //
 // No atomics, one writer per output, integer reductions only: a plane's outputs depend neither on P nor on its position.
 // Built with -ffp-contract=off (Makefile): every multiply and add of the interpolation is rounded once.
 #include "vdr_dev.h"
 #include "vdr_kernels.h"
 #include "mask_stats_map.h"
+#include "plane_reduce.h"
 
 namespace vdr {
 
 namespace {
 
-struct MsAcc {
-  int n_hi, n_mid, n_lo, x0, y0, x1, y1;
-};
-
-__device__ inline MsAcc ms_combine(const MsAcc& a, const MsAcc& b) {
-  MsAcc r;
-  r.n_hi = a.n_hi + b.n_hi, r.n_mid = a.n_mid + b.n_mid, r.n_lo = a.n_lo + b.n_lo;
-  r.x0 = a.x0 < b.x0 ? a.x0 : b.x0, r.y0 = a.y0 < b.y0 ? a.y0 : b.y0;
-  r.x1 = a.x1 > b.x1 ? a.x1 : b.x1, r.y1 = a.y1 > b.y1 ? a.y1 : b.y1;
-  return r;
-}
-
-__device__ inline MsAcc ms_wave_reduce(MsAcc a) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    MsAcc b;
-    b.n_hi = __shfl_xor(a.n_hi, o), b.n_mid = __shfl_xor(a.n_mid, o), b.n_lo = __shfl_xor(a.n_lo, o);
-    b.x0 = __shfl_xor(a.x0, o), b.y0 = __shfl_xor(a.y0, o), b.x1 = __shfl_xor(a.x1, o), b.y1 = __shfl_xor(a.y1, o);
-    a = ms_combine(a, b);
-  }
-  return a;
-}
-
-__device__ inline int ms_get(const MsAcc& a, int k) {
-  return k == 0 ? a.n_hi : k == 1 ? a.n_mid : k == 2 ? a.n_lo : k == 3 ? a.x0 : k == 4 ? a.y0 : k == 5 ? a.x1 : a.y1;
-}
+using MsAcc = PlaneAcc<3>;  // sums: n_hi, n_mid, n_lo (plane_reduce.h)
+constexpr int MS_HI = 0, MS_MID = 1, MS_LO = 2;
+static_assert(MS_SLOT == PR_SLOT, "the partial slot");
 
 __global__ __launch_bounds__(MS_THREADS) void mask_stats_kernel(const float* __restrict__ logits, int64_t plane_stride, int group,
                                                                 int64_t group_stride, MsGeom q, float t_hi, float thr, float t_lo,
                                                                 int vec, int32_t* __restrict__ part) {
   __shared__ __attribute__((aligned(16))) float stage[MS_STAGE_ROWS * MS_MAX_SIDE];
   __shared__ MsAxis rowtab[MS_BAND];
-  __shared__ int wred[MS_THREADS / 64][MS_SLOT];
+  __shared__ int wred[MS_THREADS / 64][PR_SLOT];
   const int tid = threadIdx.x;
   const int plane = blockIdx.x / q.bands, band = blockIdx.x - plane * q.bands;
   const MsBand b = ms_band(q, band);
@@ -71,13 +49,13 @@ __global__ __launch_bounds__(MS_THREADS) void mask_stats_kernel(const float* __r
     rowtab[tid] = a;
   }
   __syncthreads();
-  MsAcc acc{0, 0, 0, q.ow, q.oh, -1, -1};
+  MsAcc acc = pr_identity<3>(q.ow, q.oh);
   for (int ox = tid; ox < q.ow; ox += MS_THREADS) {
     const MsAxis cx = ms_axis(ox, q.sx, W);
     auto blend = [&](int row) { return cx.l0 * stage[row + cx.i0] + cx.l1 * stage[row + cx.i1]; };
     int c0 = -1, c1 = -1;
     float top = 0.0f, bot = 0.0f;
-    bool any = false;
+    int y0 = q.oh, y1 = -1;  // the column's rows above thr
     for (int r = 0; r < nrows; ++r) {
       const MsAxis ry = rowtab[r];
       if (ry.i0 != c0 || ry.i1 != c1) {  // (uniform in the workgroup)
@@ -86,48 +64,31 @@ __global__ __launch_bounds__(MS_THREADS) void mask_stats_kernel(const float* __r
         c0 = ry.i0, c1 = ry.i1;
       }
       const float v = ry.l0 * top + ry.l1 * bot;
-      acc.n_hi += v > t_hi;
-      acc.n_lo += v > t_lo;
+      acc.sum(MS_HI) += v > t_hi;
+      acc.sum(MS_LO) += v > t_lo;
       if (v > thr) {
         const int oy = b.r0 + r;
-        ++acc.n_mid;
-        any = true;
-        acc.y0 = oy < acc.y0 ? oy : acc.y0;
-        acc.y1 = oy > acc.y1 ? oy : acc.y1;
+        ++acc.sum(MS_MID);
+        y0 = oy < y0 ? oy : y0;
+        y1 = oy > y1 ? oy : y1;
       }
     }
-    if (any) {
-      acc.x0 = ox < acc.x0 ? ox : acc.x0;
-      acc.x1 = ox > acc.x1 ? ox : acc.x1;
-    }
+    if (y1 >= 0) acc.take(ox, y0), acc.take(ox, y1);
   }
-  acc = ms_wave_reduce(acc);
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < 7; ++k) wred[tid >> 6][k] = ms_get(acc, k);
-  }
-  __syncthreads();
-  if (tid < 7) {
-    int v = wred[0][tid];
-    for (int w = 1; w < MS_THREADS / 64; ++w) {
-      const int u = wred[w][tid];
-      v = tid < 3 ? v + u : tid < 5 ? (u < v ? u : v) : (u > v ? u : v);
-    }
-    part[ms_slot(q, plane, band, tid)] = v;
-  }
+  pr_block_store<3, MS_THREADS / 64>(acc, wred, part + ms_slot(q, plane, band, 0));
 }
 
 __global__ __launch_bounds__(64) void mask_stats_finish_kernel(const int32_t* __restrict__ part, MsGeom q, int32_t* __restrict__ counts,
                                                                int32_t* __restrict__ box) {
   const int plane = blockIdx.x, lane = threadIdx.x;
-  MsAcc acc{0, 0, 0, q.ow, q.oh, -1, -1};
-  for (int band = lane; band < q.bands; band += 64) {
-    const int32_t* s = part + ms_slot(q, plane, band, 0);
-    acc = ms_combine(acc, MsAcc{s[0], s[1], s[2], s[3], s[4], s[5], s[6]});
-  }
-  acc = ms_wave_reduce(acc);
-  if (lane < 3) counts[plane * 3 + lane] = ms_get(acc, lane);
-  else if (lane < 7) box[plane * 4 + lane - 3] = acc.n_mid > 0 ? ms_get(acc, lane) : 0;   // an empty mask: 0, 0, 0, 0
+  MsAcc acc = pr_identity<3>(q.ow, q.oh);
+  for (int band = lane; band < q.bands; band += 64) acc = pr_combine(acc, pr_load<3>(part + ms_slot(q, plane, band, 0)));
+  acc = pr_wave_reduce(acc);
+  if (lane) return;  // every lane holds the plane's seven integers; one writes them
+#pragma unroll
+  for (int k = 0; k < 3; ++k) counts[plane * 3 + k] = acc.sum(k);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) box[plane * 4 + k] = acc.sum(MS_MID) > 0 ? acc.box(k) : 0;  // an empty mask: 0, 0, 0, 0
 }
 
 }  // namespace

@@ -2346,6 +2346,30 @@ static bool aligned16(std::initializer_list<const void*> ps) {
 // an op's refusal "<op>: <what>" as its return value
 static int refuse(const char* op, int code, const std::string& what) { return fail(nullptr, code, std::string(op) + ": " + what); }
 
+// The refusals the workspace ops and the mask-plane ops share, one per fact; each returns 0 when there is nothing to refuse.
+static int refuse_workspace(const char* op, size_t have, size_t need) {
+  return have < need ? refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(need) + " bytes needed") : 0;
+}
+
+// the plane count and the sides of a plane
+static int refuse_planes(const char* op, int planes, int H, int W, int max_side) {
+  if (planes < 1 || planes > 65535) return refuse(op, VDR_ERR_INVALID, "planes must be 1 .. 65535");
+  if (H < 1 || H > max_side || W < 1 || W > max_side) return refuse(op, VDR_ERR_INVALID, "H and W must be 1 .. " + std::to_string(max_side));
+  return 0;
+}
+
+// the logit planes of mask_stats and mask_binarize (include/vdr.h): sides, output size, the two strides
+static int refuse_logit_planes(const char* op, int64_t plane_stride, int planes_per_group, int64_t group_stride, int planes, int H, int W, int oh,
+                               int ow) {
+  if (int rc = refuse_planes(op, planes, H, W, MS_MAX_SIDE)) return rc;
+  if (oh < 1 || oh > MS_MAX_OUT || ow < 1 || ow > MS_MAX_OUT) return refuse(op, VDR_ERR_INVALID, "oh and ow must be 1 .. " + std::to_string(MS_MAX_OUT));
+  if (plane_stride < (int64_t)H * W) return refuse(op, VDR_ERR_INVALID, "plane_stride is shorter than a plane");
+  if (planes_per_group < 1 || planes % planes_per_group) return refuse(op, VDR_ERR_INVALID, "planes must be a multiple of planes_per_group >= 1");
+  if (planes_per_group < planes && group_stride < (planes_per_group - 1) * plane_stride + (int64_t)H * W)
+    return refuse(op, VDR_ERR_INVALID, "group_stride is shorter than a group's planes");
+  return 0;
+}
+
 // A descriptor map as the descriptor ops take it (include/vdr.h): `problems` problems of `imgs` images of `t` rows of `d`
 // channels, the rows `ld`, the images `image_stride`, the problems `problem_stride` elements apart.  An op without an image
 // level passes imgs = 1 and image_stride = 0, one without a problem stride 0, a bf16-only op in_dtype = VDR_BF16.
@@ -2787,17 +2811,10 @@ int vdr_op_mask_stats(const float* logits, int64_t plane_stride, int planes_per_
   static_assert(VDR_MASK_STATS_MAX_SIDE == MS_MAX_SIDE && VDR_MASK_STATS_MAX_OUT == MS_MAX_OUT, "include/vdr.h and mask_stats_map.h");
   const char* op = "vdr_op_mask_stats";
   if (!logits || !workspace || !counts || !box) return refuse(op, VDR_ERR_INVALID, "null pointer");
-  if (planes < 1 || planes > 65535) return refuse(op, VDR_ERR_INVALID, "planes must be 1 .. 65535");
-  if (H < 1 || H > MS_MAX_SIDE || W < 1 || W > MS_MAX_SIDE) return refuse(op, VDR_ERR_INVALID, "H and W must be 1 .. " + std::to_string(MS_MAX_SIDE));
-  if (oh < 1 || oh > MS_MAX_OUT || ow < 1 || ow > MS_MAX_OUT) return refuse(op, VDR_ERR_INVALID, "oh and ow must be 1 .. " + std::to_string(MS_MAX_OUT));
-  if (plane_stride < (int64_t)H * W) return refuse(op, VDR_ERR_INVALID, "plane_stride is shorter than a plane");
-  if (planes_per_group < 1 || planes % planes_per_group) return refuse(op, VDR_ERR_INVALID, "planes must be a multiple of planes_per_group >= 1");
-  if (planes_per_group < planes && group_stride < (planes_per_group - 1) * plane_stride + (int64_t)H * W)
-    return refuse(op, VDR_ERR_INVALID, "group_stride is shorter than a group's planes");
+  if (int rc = refuse_logit_planes(op, plane_stride, planes_per_group, group_stride, planes, H, W, oh, ow)) return rc;
   if (!(offset >= 0.0f)) return refuse(op, VDR_ERR_INVALID, "offset must be >= 0");
   if (((uintptr_t)logits & 3) || !aligned16({workspace, counts, box})) return refuse(op, VDR_ERR_INVALID, "workspace, counts and box must be 16-byte aligned, logits to its element");
-  const size_t need = mask_stats_workspace_bytes(planes, H, W, oh, ow);
-  if (workspace_bytes < need) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(need) + " bytes needed");
+  if (int rc = refuse_workspace(op, workspace_bytes, mask_stats_workspace_bytes(planes, H, W, oh, ow))) return rc;
   RUN_OP(launch_mask_stats(logits, plane_stride, planes_per_group, group_stride, planes, H, W, oh, ow, threshold, offset, workspace, counts, box,
                            (hipStream_t)stream),
          "mask_stats");
@@ -2814,8 +2831,7 @@ int vdr_op_nms(const float* boxes, const int32_t* order, int n, float iou_thresh
   if (iou_threshold != iou_threshold) return refuse(op, VDR_ERR_INVALID, "iou_threshold must be a number");
   if (!aligned16({boxes, workspace}) || (((uintptr_t)order | (uintptr_t)kept | (uintptr_t)count) & 3))
     return refuse(op, VDR_ERR_INVALID, "boxes and workspace must be 16-byte aligned, order, kept and count to their element");
-  const size_t need = nms_workspace_bytes(n);
-  if (workspace_bytes < need) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(need) + " bytes needed");
+  if (int rc = refuse_workspace(op, workspace_bytes, nms_workspace_bytes(n))) return rc;
   RUN_OP(launch_nms(boxes, order, n, iou_threshold, workspace, keep, kept, count, (hipStream_t)stream), "nms");
 }
 
@@ -2826,42 +2842,27 @@ int vdr_op_mask_binarize(const float* logits, int64_t plane_stride, int planes_p
                          int ow, float threshold, void* workspace, size_t workspace_bytes, uint8_t* out, void* stream) {
   const char* op = "vdr_op_mask_binarize";
   if (!logits || !workspace || !out) return refuse(op, VDR_ERR_INVALID, "null pointer");
-  if (planes < 1 || planes > 65535) return refuse(op, VDR_ERR_INVALID, "planes must be 1 .. 65535");
-  if (H < 1 || H > MS_MAX_SIDE || W < 1 || W > MS_MAX_SIDE) return refuse(op, VDR_ERR_INVALID, "H and W must be 1 .. " + std::to_string(MS_MAX_SIDE));
-  if (oh < 1 || oh > MS_MAX_OUT || ow < 1 || ow > MS_MAX_OUT) return refuse(op, VDR_ERR_INVALID, "oh and ow must be 1 .. " + std::to_string(MS_MAX_OUT));
-  if (plane_stride < (int64_t)H * W) return refuse(op, VDR_ERR_INVALID, "plane_stride is shorter than a plane");
-  if (planes_per_group < 1 || planes % planes_per_group) return refuse(op, VDR_ERR_INVALID, "planes must be a multiple of planes_per_group >= 1");
-  if (planes_per_group < planes && group_stride < (planes_per_group - 1) * plane_stride + (int64_t)H * W)
-    return refuse(op, VDR_ERR_INVALID, "group_stride is shorter than a group's planes");
+  if (int rc = refuse_logit_planes(op, plane_stride, planes_per_group, group_stride, planes, H, W, oh, ow)) return rc;
   if (threshold != threshold) return refuse(op, VDR_ERR_INVALID, "threshold must be a number");
   if ((uintptr_t)logits & 3) return refuse(op, VDR_ERR_INVALID, "logits must be aligned to its element");
-  const size_t need = vdr_mask_binarize_workspace_bytes(planes, H, W, oh, ow);
-  if (workspace_bytes < need) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(need) + " bytes needed");
+  if (int rc = refuse_workspace(op, workspace_bytes, vdr_mask_binarize_workspace_bytes(planes, H, W, oh, ow))) return rc;
   RUN_OP(launch_mask_binarize(logits, plane_stride, planes_per_group, group_stride, planes, H, W, oh, ow, threshold, out, (hipStream_t)stream),
          "mask_binarize");
 }
 
 size_t vdr_connected_components_workspace_bytes(int planes, int H, int W) { return components_workspace_bytes(planes, H, W, 0); }
 
-// the checks the two labelling ops share; 0: fine
-static int components_refusal(const char* op, int planes, int H, int W, int connectivity) {
-  static_assert(VDR_COMPONENTS_MAX_SIDE == CC_MAX_SIDE, "include/vdr.h and components_map.h");
-  if (planes < 1 || planes > CC_MAX_PLANES) return refuse(op, VDR_ERR_INVALID, "planes must be 1 .. 65535");
-  if (H < 1 || H > CC_MAX_SIDE || W < 1 || W > CC_MAX_SIDE) return refuse(op, VDR_ERR_INVALID, "H and W must be 1 .. " + std::to_string(CC_MAX_SIDE));
-  if (connectivity != 4 && connectivity != 8) return refuse(op, VDR_ERR_INVALID, "connectivity must be 4 or 8");
-  return 0;
-}
-
 int vdr_op_connected_components(const uint8_t* mask, int planes, int H, int W, int connectivity, int value, void* workspace, size_t workspace_bytes,
                                 int32_t* root, int32_t* area, int32_t* count, void* stream) {
+  static_assert(VDR_COMPONENTS_MAX_SIDE == CC_MAX_SIDE && CC_MAX_PLANES == 65535, "include/vdr.h and components_map.h");
   const char* op = "vdr_op_connected_components";
   if (!mask || !workspace || !root || !area || !count) return refuse(op, VDR_ERR_INVALID, "null pointer");
-  if (int rc = components_refusal(op, planes, H, W, connectivity)) return rc;
+  if (int rc = refuse_planes(op, planes, H, W, CC_MAX_SIDE)) return rc;
+  if (connectivity != 4 && connectivity != 8) return refuse(op, VDR_ERR_INVALID, "connectivity must be 4 or 8");
   if (value != 0 && value != 1) return refuse(op, VDR_ERR_INVALID, "value must be 0 or 1");
   if (!aligned16({workspace}) || (((uintptr_t)root | (uintptr_t)area | (uintptr_t)count) & 3))
     return refuse(op, VDR_ERR_INVALID, "workspace must be 16-byte aligned, root, area and count to their element");
-  const size_t need = components_workspace_bytes(planes, H, W, 0);
-  if (workspace_bytes < need) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(need) + " bytes needed");
+  if (int rc = refuse_workspace(op, workspace_bytes, components_workspace_bytes(planes, H, W, 0))) return rc;
   RUN_OP(launch_connected_components(mask, planes, H, W, connectivity, value, workspace, root, area, count, (hipStream_t)stream),
          "connected_components");
 }
@@ -2872,7 +2873,8 @@ int vdr_op_mask_clean(const uint8_t* mask, int planes, int H, int W, int min_are
                       size_t workspace_bytes, uint8_t* out, int32_t* changed, int32_t* stats, void* stream) {
   const char* op = "vdr_op_mask_clean";
   if (!mask || !workspace || !out || !changed || !stats) return refuse(op, VDR_ERR_INVALID, "null pointer");
-  if (int rc = components_refusal(op, planes, H, W, connectivity)) return rc;
+  if (int rc = refuse_planes(op, planes, H, W, CC_MAX_SIDE)) return rc;
+  if (connectivity != 4 && connectivity != 8) return refuse(op, VDR_ERR_INVALID, "connectivity must be 4 or 8");
   if (min_area < 0) return refuse(op, VDR_ERR_INVALID, "min_area must be >= 0");
   if (mode & ~(VDR_CLEAN_HOLES | VDR_CLEAN_ISLANDS | VDR_CLEAN_LARGEST)) return refuse(op, VDR_ERR_INVALID, "unknown mode bit");
   if ((mode & VDR_CLEAN_ISLANDS) && (mode & VDR_CLEAN_LARGEST)) return refuse(op, VDR_ERR_INVALID, "VDR_CLEAN_ISLANDS and VDR_CLEAN_LARGEST exclude each other");
@@ -2882,8 +2884,7 @@ int vdr_op_mask_clean(const uint8_t* mask, int planes, int H, int W, int min_are
   }
   if (!aligned16({workspace}) || (((uintptr_t)changed | (uintptr_t)stats) & 3))
     return refuse(op, VDR_ERR_INVALID, "workspace must be 16-byte aligned, changed and stats to their element");
-  const size_t need = components_workspace_bytes(planes, H, W, 1);
-  if (workspace_bytes < need) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(need) + " bytes needed");
+  if (int rc = refuse_workspace(op, workspace_bytes, components_workspace_bytes(planes, H, W, 1))) return rc;
   RUN_OP(launch_mask_clean(mask, planes, H, W, min_area, connectivity, mode, workspace, out, changed, stats, (hipStream_t)stream), "mask_clean");
 }
 
@@ -2892,20 +2893,18 @@ size_t vdr_distance_transform_workspace_bytes(int planes, int H, int W) { return
 
 int vdr_op_distance_transform(const uint8_t* mask, int planes, int H, int W, int value, int outside, int r2, void* workspace, size_t workspace_bytes,
                               int32_t* d2, int32_t* nearest, int32_t* peak, uint8_t* within, void* stream) {
-  static_assert(VDR_EDT_MAX_SIDE == EDT_MAX_SIDE && VDR_EDT_NONE == EDT_NONE, "include/vdr.h and edt_map.h");
+  static_assert(VDR_EDT_MAX_SIDE == EDT_MAX_SIDE && VDR_EDT_NONE == EDT_NONE && EDT_MAX_PLANES == 65535, "include/vdr.h and edt_map.h");
   const char* op = "vdr_op_distance_transform";
   if (!mask || !workspace) return refuse(op, VDR_ERR_INVALID, "null pointer");
   if (!d2 && !nearest && !peak && !within) return refuse(op, VDR_ERR_INVALID, "no output: d2, nearest, peak and within are all null");
-  if (planes < 1 || planes > EDT_MAX_PLANES) return refuse(op, VDR_ERR_INVALID, "planes must be 1 .. 65535");
-  if (H < 1 || H > EDT_MAX_SIDE || W < 1 || W > EDT_MAX_SIDE) return refuse(op, VDR_ERR_INVALID, "H and W must be 1 .. " + std::to_string(EDT_MAX_SIDE));
+  if (int rc = refuse_planes(op, planes, H, W, EDT_MAX_SIDE)) return rc;
   if (value != 0 && value != 1) return refuse(op, VDR_ERR_INVALID, "value must be 0 or 1");
   if (outside != 0 && outside != 1) return refuse(op, VDR_ERR_INVALID, "outside must be 0 or 1");
   if (nearest && outside) return refuse(op, VDR_ERR_INVALID, "nearest is not defined with outside = 1 (the nearest point may lie beyond the plane)");
   if (within && r2 < 0) return refuse(op, VDR_ERR_INVALID, "r2 must be >= 0");
   if (!aligned16({workspace}) || (((uintptr_t)d2 | (uintptr_t)nearest | (uintptr_t)peak) & 3))
     return refuse(op, VDR_ERR_INVALID, "workspace must be 16-byte aligned, d2, nearest and peak to their element");
-  const size_t need = distance_transform_workspace_bytes(planes, H, W);
-  if (workspace_bytes < need) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(need) + " bytes needed");
+  if (int rc = refuse_workspace(op, workspace_bytes, distance_transform_workspace_bytes(planes, H, W))) return rc;
   RUN_OP(launch_distance_transform(mask, planes, H, W, value, outside, r2, workspace, d2, nearest, peak, within, (hipStream_t)stream),
          "distance_transform");
 }
@@ -3639,7 +3638,7 @@ int md_check(const char* op, const MD* d, const float* emb, int channels_last, c
     return refuse(op, VDR_ERR_UNSUPPORTED, "point prompts (and the padding point of a decode without boxes) need point_embeddings.{0,1} and not_a_point_embed");
   if (pr && pr->mask_input && !(d->support & VDR_PROMPT_MASK)) return refuse(op, VDR_ERR_UNSUPPORTED, "a mask prompt needs the mask_downscaling weights");
   const MdCarve c = md_carve(d, (int64_t)batch * boxes_per_image, T);
-  if (workspace_bytes < c.total) return refuse(op, VDR_ERR_WORKSPACE, "workspace too small: " + std::to_string(c.total) + " bytes needed");
+  if (int rc = refuse_workspace(op, workspace_bytes, c.total)) return rc;
   return VDR_OK;
 }
 

@@ -396,6 +396,7 @@ class PlaneOperand:
             raise ValueError(f"{op}: {name} must be a float32 [P, H, W] or [G, M, H, W] tensor")
         if not x.is_cuda:
             raise ValueError(f"{op}: {name} must live on the HIP device")
+        self.lead = tuple(int(v) for v in x.shape[:-2])  # the leading shape of every result: (P,) or (G, M)
         if x.dim() == 3:
             x = x.unsqueeze(1)
         G, M, H, W = (int(v) for v in x.shape)
@@ -409,7 +410,20 @@ class PlaneOperand:
             x = x.contiguous()
             ps, gs = H * W, M * H * W
         self.x, self.planes, self.group, self.plane_stride, self.group_stride, self.H, self.W = x, G * M, M, ps, gs, H, W
-        self.shape = (G, M)
+
+
+def _workspace(workspace, need: int, device):
+    """the caller's workspace, or a fresh one of the library's byte count (the C entry point checks a given one's size)"""
+    return torch.empty((need,), dtype=torch.uint8, device=device) if workspace is None else workspace
+
+
+def _result(op: str, name: str, t, shape, dtype, device):
+    """the caller's tensor to write `name` into, checked, or a fresh one"""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if not (isinstance(t, torch.Tensor) and t.device == device and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise ValueError(f"{op}: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on the operand's device")
+    return t
 
 
 def check_out_size(op: str, size) -> "tuple[int, int]":
@@ -434,12 +448,9 @@ def mask_stats(logits, size, threshold: float = 0.0, offset: float = 1.0, worksp
         raise ValueError(f"mask_stats: offset must be >= 0, got {offset!r}")
     lib = L.load()
     dev = o.x.device
-    need = lib.vdr_mask_stats_workspace_bytes(o.planes, o.H, o.W, oh, ow)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
-    lead = (o.planes,) if logits.dim() == 3 else o.shape
-    counts = torch.empty((*lead, 3), dtype=torch.int32, device=dev)
-    box = torch.empty((*lead, 4), dtype=torch.int32, device=dev)
+    workspace = _workspace(workspace, lib.vdr_mask_stats_workspace_bytes(o.planes, o.H, o.W, oh, ow), dev)
+    counts = torch.empty((*o.lead, 3), dtype=torch.int32, device=dev)
+    box = torch.empty((*o.lead, 4), dtype=torch.int32, device=dev)
     L.check(lib.vdr_op_mask_stats(o.x.data_ptr(), o.plane_stride, o.group, o.group_stride, o.planes, o.H, o.W, oh, ow, float(threshold),
                                   float(offset), workspace.data_ptr(), workspace.numel(), counts.data_ptr(), box.data_ptr(), _s(o.x)))
     return counts, box
@@ -461,9 +472,7 @@ def nms(boxes, scores, iou_threshold: float, workspace=None):
     dev = boxes.device
     bx = boxes.to(torch.float32).contiguous()
     order = torch.sort(scores, descending=True, stable=True).indices.to(torch.int32)
-    need = lib.vdr_nms_workspace_bytes(N)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    workspace = _workspace(workspace, lib.vdr_nms_workspace_bytes(N), dev)
     keep = torch.empty((N,), dtype=torch.uint8, device=dev)
     kept = torch.empty((N,), dtype=torch.int32, device=dev)
     count = torch.empty((1,), dtype=torch.int32, device=dev)
@@ -483,12 +492,8 @@ def mask_binarize(logits, size, threshold: float = 0.0, out=None):
         raise ValueError("mask_binarize: threshold must be a number")
     lib = L.load()
     dev = o.x.device
-    lead = (o.planes,) if logits.dim() == 3 else o.shape
-    if out is None:
-        out = torch.empty((*lead, oh, ow), dtype=torch.uint8, device=dev)
-    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (*lead, oh, ow)):
-        raise ValueError(f"mask_binarize: out must be a contiguous uint8 {(*lead, oh, ow)} tensor on the device")
-    workspace = torch.empty((lib.vdr_mask_binarize_workspace_bytes(o.planes, o.H, o.W, oh, ow),), dtype=torch.uint8, device=dev)
+    out = _result("mask_binarize", "out", out, (*o.lead, oh, ow), torch.uint8, dev)
+    workspace = _workspace(None, lib.vdr_mask_binarize_workspace_bytes(o.planes, o.H, o.W, oh, ow), dev)
     L.check(lib.vdr_op_mask_binarize(o.x.data_ptr(), o.plane_stride, o.group, o.group_stride, o.planes, o.H, o.W, oh, ow, float(threshold),
                                      workspace.data_ptr(), workspace.numel(), out.data_ptr(), _s(o.x)))
     return out
@@ -515,9 +520,7 @@ def connected_components(mask, connectivity: int = 8, value: int = 1, workspace=
         raise ValueError(f"connected_components: value must be 0 or 1, got {value!r}")
     lib = L.load()
     P, H, W = (int(v) for v in m.shape)
-    need = lib.vdr_connected_components_workspace_bytes(P, H, W)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=m.device)
+    workspace = _workspace(workspace, lib.vdr_connected_components_workspace_bytes(P, H, W), m.device)
     root = torch.empty((P, H, W), dtype=torch.int32, device=m.device)
     area = torch.empty((P, H, W), dtype=torch.int32, device=m.device)
     count = torch.empty((P,), dtype=torch.int32, device=m.device)
@@ -540,18 +543,10 @@ def mask_clean(mask, min_area: int = 0, holes: bool = False, islands: bool = Fal
     min_area, mode, connectivity = cc.check_clean("mask_clean", min_area, holes, islands, largest, connectivity)
     lib = L.load()
     P, H, W = (int(v) for v in m.shape)
-    need = lib.vdr_mask_clean_workspace_bytes(P, H, W)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=m.device)
-    def given(t, shape, dtype, name):
-        if t is None:
-            return torch.empty(shape, dtype=dtype, device=m.device)
-        if not (isinstance(t, torch.Tensor) and t.device == m.device and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
-            raise ValueError(f"mask_clean: {name} must be a contiguous {dtype} tensor of shape {shape} on the mask's device")
-        return t
-    out = given(out, (P, H, W), torch.uint8, "out")
-    changed = given(changed, (P,), torch.int32, "changed")
-    stats = given(stats, (P, 5), torch.int32, "stats")
+    workspace = _workspace(workspace, lib.vdr_mask_clean_workspace_bytes(P, H, W), m.device)
+    out = _result("mask_clean", "out", out, (P, H, W), torch.uint8, m.device)
+    changed = _result("mask_clean", "changed", changed, (P,), torch.int32, m.device)
+    stats = _result("mask_clean", "stats", stats, (P, 5), torch.int32, m.device)
     L.check(lib.vdr_op_mask_clean(m.data_ptr(), P, H, W, min_area, connectivity, mode, workspace.data_ptr(), workspace.numel(), out.data_ptr(),
                                   changed.data_ptr(), stats.data_ptr(), _s(m)))
     return (out[0] if single else out), changed, stats
@@ -579,9 +574,7 @@ def distance_transform(mask, value: int = 1, outside: bool = False, return_neare
     m, single = _mask_planes(mask, "distance_transform")
     lib = L.load()
     P, H, W = (int(v) for v in m.shape)
-    need = lib.vdr_distance_transform_workspace_bytes(P, H, W)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=m.device)
+    workspace = _workspace(workspace, lib.vdr_distance_transform_workspace_bytes(P, H, W), m.device)
     first = torch.empty((P, H, W), dtype=torch.int32 if r2 is None else torch.uint8, device=m.device) if return_d2 else None
     nearest = torch.empty((P, H, W), dtype=torch.int32, device=m.device) if return_nearest else None
     peak = torch.empty((P, 2), dtype=torch.int32, device=m.device) if return_peak else None
