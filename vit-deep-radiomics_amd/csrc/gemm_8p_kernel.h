@@ -1,6 +1,10 @@
 // The 8-phase GEMM kernel of tile variant 31 (description: gemm_8p.hip).  A header so that its instantiations can live in
 // two translation units: gemm_8p.hip (EPI_BIAS, EPI_BIAS_GELU; the launcher and the shape rules) and gemm_8p_act.hip
 // (EPI_BIAS_QGELU, EPI_BIAS_TGELU).  Everything here has internal linkage.
+// The epilogue (epi_tiles) is written for its issue slots -- both waves of a SIMD run it with the matrix pipe idle: per site
+// 303 vector instructions and 18 s_nop with erf-GELU and the fold (before: 335 and 40), 88 and 9 bias-only with the fold
+// (123 and 11); fc1 245 -> 239 us, qkv 158 -> 157 us per launch at ViT-B/16 batch 256 (profiles/gemm8p_epilogue_isa.txt,
+// profiles/gemm8p_epilogue_ab.txt).
 #pragma once
 #include <utility>
 
@@ -134,82 +138,173 @@ __global__ __launch_bounds__(512) void gemm_8p_kernel(G8 p) {
     __builtin_amdgcn_s_setprio(0);
   };
 
-  // Epilogue of two m-tiles (i0, i0 + 1) of one M half, both n halves.  The arithmetic is epilogue_bf16's (gemm_epi.h), in
-  // the accumulator layout:  v = fma(rs, acc, fma(-rs mu, csum, bias)), erf-GELU, one bf16 rounding.  A lane holds 16 B of
-  // output row r in each 32-column block (p = 0, 1); lanes r and r ^ 8 exchange one block so that a store instruction
-  // covers 8 rows x 128 B instead of 16 rows x 64 B.
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+  using I2 = std::integral_constant<int, 2>;
+  using I3 = std::integral_constant<int, 3>;
+  using T = std::true_type;
+  using F = std::false_type;
+
+  // Epilogue of two m-tiles (i0, i0 + 1) of one M half, both n halves: one "site", expanded 10 times in the kernel.  The
+  // arithmetic is epilogue_bf16's (gemm_epi.h), in the accumulator layout:  v = fma(rs, acc, fma(-rs mu, csum, bias)), the
+  // activation, one bf16 rounding.  A lane holds 16 B of output row r in each 32-column block (p = 0, 1); lanes r and r ^ 8
+  // exchange one block so that a store instruction covers 8 rows x 128 B instead of 16 rows x 64 B.
+  // Both waves of a SIMD run their sites side by side with the matrix pipe idle, so every issue slot here is paid in full:
+  // what the ISA of a site holds, and what was taken out of it (hazard no-ops behind transcendentals and between dependent
+  // packed instructions, the 4-instruction exchange, per-m-tile reads of the constants, a quarter-rate multiply in the
+  // addresses), is counted in profiles/gemm8p_epilogue_isa.txt; the times are in profiles/gemm8p_epilogue_ab.txt.
   // (the descriptor ends after the last valid row: the rows of a ragged last tile past M are dropped by the range check)
   const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc((void*)p.C, (short)0, p.M * p.ldc * 2, 0x00020000);
+  const uint32_t ldc2 = (uint32_t)p.ldc * 2;  // bytes per output row (below 2^24: M ldc 2 fits the 32-bit range of the descriptor)
   auto epi_tiles = [&](auto mh_, auto i0_, int m0, int n0, int par) {
     constexpr int mh = decltype(mh_)::value, i0 = decltype(i0_)::value;
-    // (the lane-derived addresses are rebuilt from an opaque copy of the lane id at every site: hoisted out of the K loop by
-    // hipcc they are long-lived registers of a kernel at its 256-register cap -- spilt, and a scratch reload inside the loop
-    // would count in vmcnt next to the LDS-DMA pieces)
-    int lane_ = lane;
+    // Addresses: everything that is the same in all 64 lanes (tile, wave, M half, m-tile, constant buffer) is scalar
+    // arithmetic, added to the lane term by one instruction.  (The offset of a store stays a vector operand: the rows of a
+    // ragged last tile are dropped by the descriptor's range check, which this code relies on for the vector offset only.)
+    // The lane terms are rebuilt from an opaque copy of the lane id at every site, about 14 vector instructions: hoisted out
+    // of the K loop by hipcc they are long-lived registers of a kernel at its 256-register cap -- spilt, and a scratch
+    // reload inside the loop would count in vmcnt next to the LDS-DMA pieces.
+    uint32_t lane_ = (uint32_t)lane;
     asm volatile("" : "+v"(lane_));
-    const int r = lane_ & 15, q = lane_ >> 4;
+    const uint32_t q16 = lane_ & 0x30;  // 16 q: this lane's 16 bytes of a 64-byte output block, 8 q floats of the constants
     const uint32_t cb = lds0 + LDS_CONST + par * 4096;
-    const uint32_t baddr = cb + (wc * 64 + 8 * q) * 4;
+    const uint32_t baddr = (cb + wc * 256) + q16 * 2;
+    const uint32_t saddr = (cb + 2048 + (wr * 128 + 64 * mh + 16 * i0) * 8) + (lane_ & 15) * 8;
     typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
     typedef __attribute__((address_space(3))) f32x2 lds_f32x2;
-    const bool lower = (r & 8) == 0;
-    const int lane_off = ((m0 + wr * 128 + 64 * mh + (r & 7)) * p.ldc + n0 + wc * 64 + (lower ? 0 : 32) + 8 * q) * 2;
-    sfor<2>([&](auto di) {
-      constexpr int i = i0 + di, ii = 4 * mh + i;
-      float rs = 1.0f, nrm = 0.0f;
-      if constexpr (FOLD) {
-        const f32x2 st = *reinterpret_cast<const lds_f32x2*>((uintptr_t)(cb + 2048 + (wr * 128 + 64 * mh + 16 * i + r) * 8));
-        rs = st[1];
-        nrm = -st[1] * st[0];
-      }
-      bf16x8 ob[2];
-      // (one 32-column block at a time: its 4 constant vectors are 16 live registers, both blocks' would be 32 and spill)
-      sfor<2>([&](auto pb) {
-        const f32x4 b0 = *reinterpret_cast<const lds_f32x4*>((uintptr_t)(baddr + pb * 128));
-        const f32x4 b1 = *reinterpret_cast<const lds_f32x4*>((uintptr_t)(baddr + pb * 128 + 16));
-        f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (FOLD) {
-          c0 = *reinterpret_cast<const lds_f32x4*>((uintptr_t)(baddr + 1024 + pb * 128));
-          c1 = *reinterpret_cast<const lds_f32x4*>((uintptr_t)(baddr + 1024 + pb * 128 + 16));
-        }
-#pragma unroll
-        for (int e = 0; e < 4; e += 2) {
-          // epilogue_bf16's formula: two fused multiply-adds (without the fold rs = 1, nrm = 0, csum = 0: acc + bias exactly),
-          // on pairs of neighbouring accumulator registers: v_pk_fma_f32, bit for bit the scalar operations, two per issue slot
-          const f32x2 rs2 = {rs, rs}, nrm2 = {nrm, nrm};
-          f32x2 v0 = __builtin_elementwise_fma(rs2, f32x2{acc[ii][2 * pb][e], acc[ii][2 * pb][e + 1]},
-                                               __builtin_elementwise_fma(nrm2, f32x2{c0[e], c0[e + 1]}, f32x2{b0[e], b0[e + 1]}));
-          f32x2 v1 = __builtin_elementwise_fma(rs2, f32x2{acc[ii][2 * pb + 1][e], acc[ii][2 * pb + 1][e + 1]},
-                                               __builtin_elementwise_fma(nrm2, f32x2{c1[e], c1[e + 1]}, f32x2{b1[e], b1[e + 1]}));
-          if constexpr (epi_is_act(EPI)) {
-            v0 = epi_act2<EPI>(v0);
-            v1 = epi_act2<EPI>(v1);
-          }
-          ob[pb][e] = (bf16_t)v0[0];
-          ob[pb][e + 1] = (bf16_t)v0[1];
-          ob[pb][4 + e] = (bf16_t)v1[0];
-          ob[pb][4 + e + 1] = (bf16_t)v1[1];
-        }
-        __builtin_amdgcn_sched_barrier(0);  // (keeps hipcc from fetching the next block's constants ahead: VGPR cap)
+    // store: row (r & 7) of an 8-row group, block 0 in lanes r < 8 and block 1 (+ 64 bytes) in lanes r >= 8
+    const uint32_t voff = __umul24(lane_ & 7, ldc2) + (q16 + ((lane_ & 8) << 3));  // (v_mad_u32_u24: full rate)
+    const uint32_t soff = (uint32_t)(m0 + wr * 128 + 64 * mh + 16 * i0) * ldc2 + (uint32_t)(n0 + wc * 64) * 2;
+    // (mean, rstd) of this lane's row in both m-tiles
+    f32x2 rs2[2] = {{1.0f, 1.0f}, {1.0f, 1.0f}}, nrm2[2] = {{0.0f, 0.0f}, {0.0f, 0.0f}};
+    if constexpr (FOLD) {
+      sfor<2>([&](auto di) {
+        const f32x2 st = *reinterpret_cast<const lds_f32x2*>((uintptr_t)(saddr + di * 128));
+        const float nrm = -st[1] * st[0];
+        rs2[di] = f32x2{st[1], st[1]};
+        nrm2[di] = f32x2{nrm, nrm};
       });
-      const bf16x8 o0 = ob[0], o1 = ob[1];
-      const u32x4 w0 = __builtin_bit_cast(u32x4, o0), w1 = __builtin_bit_cast(u32x4, o1);
-      u32x4 da, db;
-#pragma unroll
-      for (int d = 0; d < 4; ++d) {
-        const uint32_t send = lower ? w1[d] : w0[d];
-        const uint32_t recv = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)send, 0x128 /* row_ror:8 */, 0xf, 0xf, false);
-        da[d] = lower ? w0[d] : recv;  // rows 0-7 of the m-tile: own block 0 | row r-8's block 1
-        db[d] = lower ? recv : w1[d];  // rows 8-15:             row r+8's block 0 | own block 1
+    }
+    // One 32-column block at a time, both m-tiles on it: its 4 constant vectors (16 live registers; both blocks' would be
+    // 32 and spill) are read from LDS once per site and block, not once per m-tile.  Block 0 of the two m-tiles waits in
+    // ob0 (8 registers) for block 1; an m-tile leaves as soon as its block 1 is rounded.
+    bf16x8 ob0[2];
+    sfor<2>([&](auto pb) {
+      const f32x4 b0 = *reinterpret_cast<const lds_f32x4*>((uintptr_t)(baddr + pb * 128));
+      const f32x4 b1 = *reinterpret_cast<const lds_f32x4*>((uintptr_t)(baddr + pb * 128 + 16));
+      f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
+      if constexpr (FOLD) {
+        c0 = *reinterpret_cast<const lds_f32x4*>((uintptr_t)(baddr + 1024 + pb * 128));
+        c1 = *reinterpret_cast<const lds_f32x4*>((uintptr_t)(baddr + 1024 + pb * 128 + 16));
       }
-      const int o_a = lane_off + (16 * i) * p.ldc * 2, o_b = lane_off + (16 * i + 8) * p.ldc * 2;
-      if (p.nt_store) {
-        __builtin_amdgcn_raw_buffer_store_b128(da, crs, o_a, 0, 2 /* nt */);
-        __builtin_amdgcn_raw_buffer_store_b128(db, crs, o_b, 0, 2);
-      } else {
-        __builtin_amdgcn_raw_buffer_store_b128(da, crs, o_a, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(db, crs, o_b, 0, 0);
-      }
+      sfor<2>([&](auto di) {
+        constexpr int i = i0 + di, ii = 4 * mh + i;
+        bf16x8 ob;
+        // The block's 8 values per accumulator tile are 4 pairs of neighbouring registers: pair k is elements e, e + 1
+        // (e = 2 (k >> 1)) of tile 2 pb + (k & 1).  fold: epilogue_bf16's formula, two fused multiply-adds (without the
+        // fold rs = 1, nrm = 0, csum = 0: acc + bias exactly) as v_pk_fma_f32, bit for bit the scalar operations, two per
+        // issue slot.  put: one bf16 rounding (v_cvt_pk_bf16_f32) into the pair's place of the 16 output bytes.
+        auto fold = [&](auto k_) -> f32x2 {
+          constexpr int k = decltype(k_)::value, t = 2 * pb + (k & 1), e = 2 * (k >> 1);
+          const f32x4& bb = (k & 1) ? b1 : b0;
+          const f32x4& cc = (k & 1) ? c1 : c0;
+          return __builtin_elementwise_fma(rs2[di], f32x2{acc[ii][t][e], acc[ii][t][e + 1]},
+                                           __builtin_elementwise_fma(nrm2[di], f32x2{cc[e], cc[e + 1]}, f32x2{bb[e], bb[e + 1]}));
+        };
+        auto put = [&](auto k_, f32x2 v) {
+          constexpr int k = decltype(k_)::value, o = 4 * (k & 1) + 2 * (k >> 1);
+          ob[o] = (bf16_t)v[0];
+          ob[o + 1] = (bf16_t)v[1];
+        };
+        // The activations run on two pairs at a time, in the order written (a sched_barrier between the steps holds hipcc
+        // to it).  Two hazards cost an s_nop each, issue cycles that compute nothing, when a result is read in the slot right
+        // behind its instruction: that of a v_exp_f32 / v_rcp_f32, and that of a packed instruction (v_pk_fma_f32 ...).
+        // So the packed chains of the two pairs are left to hipcc to interleave, the four transcendentals are issued
+        // together and their two consumers follow in the same order: each reads a result that is at least two slots old.
+        // Every value goes through the operations of epi_act2 (vdr_dev.h) in their order.
+        auto B = [] { __builtin_amdgcn_sched_barrier(0); };
+        [[maybe_unused]] f32x2 x[4], a[4], u[4], g[4];
+        sfor<2>([&](auto h) {
+          using K0 = std::integral_constant<int, 2 * h>;
+          using K1 = std::integral_constant<int, 2 * h + 1>;
+          if constexpr (EPI == EPI_BIAS_GELU) {
+            // H: a = min(|x|, 5.7), u = max(x, 0);  P: g = Q(a);  E: g = 2^g;  M: g = u - a g;  then the rounding.  (H and P
+            // apart: the clamps are asm statements, which hipcc does not count as the wait state between two dependent
+            // packed instructions)
+            auto H = [&](auto k) { gelu_erf2_clamp(fold(k), a[k], u[k]); };
+            auto P = [&](auto k) { g[k] = gelu_erf2_poly(a[k]); };
+            auto E = [&](auto k) { g[k] = fast_exp2_2(g[k]); };
+            auto M = [&](auto k) { g[k] = gelu_erf2_tail(a[k], g[k], u[k]); };
+            H(K0{}); H(K1{}); B();
+            P(K0{}); P(K1{}); B();
+            E(K0{}); B(); E(K1{}); B();
+            M(K0{}); B(); M(K1{}); B();
+            put(K0{}, g[K0::value]); B(); put(K1{}, g[K1::value]);
+          } else if constexpr (epi_is_act(EPI)) {
+            // H: the exponent g = -t log2 e;  E: g = 2^g;  D: g = g + 1;  R: g = 1 / g;  M: g = x g;  C: round
+            auto H = [&](auto k) {
+              x[k] = fold(k);
+              if constexpr (EPI == EPI_BIAS_QGELU) g[k] = quick_gelu2_e2(x[k]);
+              else g[k] = gelu_tanh2_e2(x[k]);
+            };
+            auto E = [&](auto k) { g[k] = fast_exp2_2(g[k]); };
+            auto D = [&](auto k) { g[k] = g[k] + f32x2{1.0f, 1.0f}; };
+            auto R = [&](auto k) { g[k] = fast_rcp_2(g[k]); };
+            auto M = [&](auto k) { g[k] = x[k] * g[k]; };
+            H(K0{}); H(K1{}); B();
+            E(K0{}); B(); E(K1{}); B();
+            D(K0{}); B(); D(K1{}); B();
+            R(K0{}); B(); R(K1{}); B();
+            M(K0{}); B(); M(K1{}); B();
+            put(K0{}, g[K0::value]); B(); put(K1{}, g[K1::value]);
+          } else {
+            put(K0{}, fold(K0{}));
+            put(K1{}, fold(K1{}));
+          }
+        });
+        B();  // (also keeps hipcc from fetching the next block's constants ahead: VGPR cap)
+        if constexpr (pb == 0) {
+          ob0[di] = ob;
+        } else {
+          // Lanes r and r ^ 8 exchange one block: rows 0-7 of the m-tile take [own block 0 | row r - 8's block 1], rows 8-15
+          // [row r + 8's block 0 | own block 1].  Two instructions per dword: a select whose second source comes through DPP
+          // row_ror:8 (lane predicate r < 8 in VCC), and a DPP move that only writes the lanes r < 8 (bank mask 0x3: banks are
+          // 4 lanes of a 16-lane row).  Written as asm: select + __builtin_amdgcn_update_dpp + two selects compile to select,
+          // move, DPP move, select, select per dword.  hipcc pads no hazard inside an asm statement: a DPP source needs 2 wait states behind the vector
+          // instruction that wrote it -- here a v_cvt_pk_bf16_f32 above, or a copy hipcc makes to place the operands -- so the
+          // statement opens with s_nop 1; inside it no DPP source is written before it is read.
+          const u32x4 w0 = __builtin_bit_cast(u32x4, ob0[di]), w1 = __builtin_bit_cast(u32x4, ob);
+          uint32_t a0 = w0[0], a1 = w0[1], a2 = w0[2], a3 = w0[3], b0 = w1[0], b1 = w1[1], b2 = w1[2], b3 = w1[3];
+          uint32_t d0, d1, d2, d3;
+          asm volatile(
+              "s_nop 1\n\t"
+              "s_mov_b32 vcc_lo, 0x00ff00ff\n\t"  // lanes with (lane & 8) == 0
+              "s_mov_b32 vcc_hi, 0x00ff00ff\n\t"
+              "v_cndmask_b32_dpp %[d0], %[b0], %[a0], vcc row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+              "v_cndmask_b32_dpp %[d1], %[b1], %[a1], vcc row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+              "v_cndmask_b32_dpp %[d2], %[b2], %[a2], vcc row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+              "v_cndmask_b32_dpp %[d3], %[b3], %[a3], vcc row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+              "v_mov_b32_dpp %[b0], %[a0] row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+              "v_mov_b32_dpp %[b1], %[a1] row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+              "v_mov_b32_dpp %[b2], %[a2] row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+              "v_mov_b32_dpp %[b3], %[a3] row_ror:8 row_mask:0xf bank_mask:0x3"
+              : [d0] "=&v"(d0), [d1] "=&v"(d1), [d2] "=&v"(d2), [d3] "=&v"(d3), [b0] "+v"(b0), [b1] "+v"(b1), [b2] "+v"(b2), [b3] "+v"(b3)
+              : [a0] "v"(a0), [a1] "v"(a1), [a2] "v"(a2), [a3] "v"(a3)
+              : "vcc");
+          const u32x4 da = {d0, d1, d2, d3}, db = {b0, b1, b2, b3};
+          const uint32_t s_a = soff + (16 * di) * ldc2, s_b = soff + (16 * di + 8) * ldc2;
+          // (opaque: as a hoisted condition hipcc keeps it as a lane mask and rebuilds it with two vector instructions per site)
+          int nt = p.nt_store;
+          asm volatile("" : "+s"(nt));
+          if (nt) {
+            __builtin_amdgcn_raw_buffer_store_b128(da, crs, voff + s_a, 0, 2 /* nt */);
+            __builtin_amdgcn_raw_buffer_store_b128(db, crs, voff + s_b, 0, 2);
+          } else {
+            __builtin_amdgcn_raw_buffer_store_b128(da, crs, voff + s_a, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(db, crs, voff + s_b, 0, 0);
+          }
+        }
+      });
     });
   };
   auto seg_sync_a = [&]() {  // end of a load segment: own LDS reads retired, then the rendezvous
@@ -242,13 +337,6 @@ __global__ __launch_bounds__(512) void gemm_8p_kernel(G8 p) {
       if (wave == 3) dma16((const char*)p.stats + (size_t)(m0_ + 128) * 8, (uint32_t)lane * 16, cb + 3072);
     }
   };
-
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>;
-  using I3 = std::integral_constant<int, 3>;
-  using T = std::true_type;
-  using F = std::false_type;
 
   // ---- prologue: K-tile 0 complete, A0 of K-tile 1 in flight ----
   stage(I0{}, ca, cw, 0, 0);

@@ -95,21 +95,31 @@ VDR_DEV float gelu_erf(float x) {
 // the last multiply-add as v_pk_fma_f32 -- two values per issue slot at the scalar instruction's rate
 // (profiles/r03_valu_rate_micro.txt) -- so a pair costs 2 min + 2 max + 7 packed + 2 exp slots instead of 18 + 2 exp.  The
 // GELU epilogues are bound by vector issue.
-VDR_DEV f32x2 gelu_erf2(f32x2 x) {
-  f32x2 a, relu;
+// In steps (clamp, polynomial, exponential, last multiply-add) so that a caller that is bound by vector issue can put
+// independent work between the v_exp_f32 and the multiply-add that reads it (a vector instruction that reads a
+// transcendental's result in the very next slot costs a 4-cycle s_nop: the 8-phase epilogue, gemm_8p_kernel.h).
+VDR_DEV void gelu_erf2_clamp(f32x2 x, f32x2& a, f32x2& relu) {
   asm("v_min_f32_e64 %0, |%1|, %2" : "=v"(a[0]) : "v"(x[0]), "v"(5.7f));
   asm("v_min_f32_e64 %0, |%1|, %2" : "=v"(a[1]) : "v"(x[1]), "v"(5.7f));
   asm("v_max_f32_e32 %0, 0, %1" : "=v"(relu[0]) : "v"(x[0]));
   asm("v_max_f32_e32 %0, 0, %1" : "=v"(relu[1]) : "v"(x[1]));
+}
+VDR_DEV f32x2 gelu_erf2_poly(f32x2 a) {
   const auto k = [](float c) { return f32x2{c, c}; };
   f32x2 q = __builtin_elementwise_fma(k(2.480073296e-05f), a, k(-6.399250922e-04f));
   q = __builtin_elementwise_fma(q, a, k(7.365777341e-03f));
   q = __builtin_elementwise_fma(q, a, k(-5.164207073e-02f));
   q = __builtin_elementwise_fma(q, a, k(-4.607286841e-01f));
   q = __builtin_elementwise_fma(q, a, k(-1.150403490e+00f));
-  q = __builtin_elementwise_fma(q, a, k(-1.000050145e+00f));
-  const f32x2 e = {fast_exp2(q[0]), fast_exp2(q[1])};
-  return __builtin_elementwise_fma(-a, e, relu);
+  return __builtin_elementwise_fma(q, a, k(-1.000050145e+00f));
+}
+VDR_DEV f32x2 fast_exp2_2(f32x2 q) { return f32x2{fast_exp2(q[0]), fast_exp2(q[1])}; }
+VDR_DEV f32x2 fast_rcp_2(f32x2 d) { return f32x2{fast_rcp(d[0]), fast_rcp(d[1])}; }
+VDR_DEV f32x2 gelu_erf2_tail(f32x2 a, f32x2 e, f32x2 relu) { return __builtin_elementwise_fma(-a, e, relu); }
+VDR_DEV f32x2 gelu_erf2(f32x2 x) {
+  f32x2 a, relu;
+  gelu_erf2_clamp(x, a, relu);
+  return gelu_erf2_tail(a, fast_exp2_2(gelu_erf2_poly(a)), relu);
 }
 
 // The sigmoid-gated activations of the language-supervised towers, both  x sigmoid(t) = x / (1 + 2^(-t log2 e)):
@@ -131,14 +141,19 @@ VDR_DEV float gelu_tanh(float x) { return x_sigmoid(x, x * fmaf(x * x, TGELU_E2B
 // The same on pairs, bit for bit (every step is the IEEE operation of the scalar form; the transcendentals are per
 // value): QuickGELU 3 packed (v_pk_mul, v_pk_add, v_pk_mul) + 2 v_exp + 2 v_rcp slots per pair, tanh-GELU 5 packed
 // (v_pk_mul, v_pk_fma, v_pk_mul, v_pk_add, v_pk_mul) + 2 + 2, against erf-GELU's 2 min + 2 max + 7 packed + 2 v_exp.
+// The exponent of a pair is its own step (quick_gelu2_e2, gelu_tanh2_e2) for the callers that interleave the v_exp_f32 and
+// v_rcp_f32 of one pair with the packed steps of the next (gemm_8p_kernel.h): x_sigmoid2 is
+// x * fast_rcp_2(fast_exp2_2(e2) + 1), step by step.
+VDR_DEV f32x2 quick_gelu2_e2(f32x2 x) { return x * f32x2{QGELU_E2, QGELU_E2}; }
+VDR_DEV f32x2 gelu_tanh2_e2(f32x2 x) {
+  return x * __builtin_elementwise_fma(x * x, f32x2{TGELU_E2B, TGELU_E2B}, f32x2{TGELU_E2A, TGELU_E2A});
+}
 VDR_DEV f32x2 x_sigmoid2(f32x2 x, f32x2 e2) {
-  const f32x2 d = f32x2{fast_exp2(e2[0]), fast_exp2(e2[1])} + f32x2{1.0f, 1.0f};
-  return x * f32x2{fast_rcp(d[0]), fast_rcp(d[1])};
+  const f32x2 d = fast_exp2_2(e2) + f32x2{1.0f, 1.0f};
+  return x * fast_rcp_2(d);
 }
-VDR_DEV f32x2 quick_gelu2(f32x2 x) { return x_sigmoid2(x, x * f32x2{QGELU_E2, QGELU_E2}); }
-VDR_DEV f32x2 gelu_tanh2(f32x2 x) {
-  return x_sigmoid2(x, x * __builtin_elementwise_fma(x * x, f32x2{TGELU_E2B, TGELU_E2B}, f32x2{TGELU_E2A, TGELU_E2A}));
-}
+VDR_DEV f32x2 quick_gelu2(f32x2 x) { return x_sigmoid2(x, quick_gelu2_e2(x)); }
+VDR_DEV f32x2 gelu_tanh2(f32x2 x) { return x_sigmoid2(x, gelu_tanh2_e2(x)); }
 
 // One 16-key slice of a softmax row held in the S^T accumulator layout: P = 2^(s * sc + nmb) for the 8 scores of this
 // lane, their sum added to `lsum2`, P rounded to bf16 as the B operand of O^T += V^T . P^T.  Written on PAIRS of
