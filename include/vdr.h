@@ -982,6 +982,58 @@ size_t vdr_distance_transform_workspace_bytes(int planes, int H, int W);
 int vdr_op_distance_transform(const uint8_t* mask, int planes, int H, int W, int value, int outside, int r2, void* workspace, size_t workspace_bytes,
                               int32_t* d2, int32_t* nearest, int32_t* peak, uint8_t* within, void* stream);
 
+/* ---- exact 3-D Euclidean distance transform of mask volumes with voxel spacing (csrc/edt3d.hip, csrc/edt3d_map.h).
+ *
+ * A volume is Z x H x W uint8, nonzero = set, every side in 1 .. 4096, voxel index i = (z H + y) W + x; there are `volumes` of
+ * them, back to back.  value selects the voxels that are measured: 1 the set voxels, 0 the clear ones.  spacing is three INTEGERS
+ * (qz, qy, qx), each in 1 .. 65535, in a unit the caller chooses (vdr.morphology.quantize_spacing: millimetres / 2^-10, say); the
+ * squared distance between two voxels (dz, dy, dx) apart is (qz dz)^2 + (qy dy)^2 + (qx dx)^2.  Everything is an integer and a
+ * function of the mask and the spacing alone.  The bound (qz Z)^2 + (qy H)^2 + (qx W)^2 <= 2^53 makes every value exact both in
+ * int64 and in float64, so the outputs are bit for bit rint(scipy.ndimage.distance_transform_edt(selected, sampling=(qz, qy, qx)) ^ 2),
+ * and scipy's float64 result is exactly sqrt(d2).
+ *
+ * vdr_op_distance_transform_3d: vol uint8 [volumes, Z, H, W], spacing, value, outside, r2 -> three outputs, EACH OPTIONAL (null: not
+ * computed, not touched), at least one of them given:
+ *   d2      int64 [volumes, Z, H, W]  for a selected voxel: min (qz dz)^2 + (qy dy)^2 + (qx dx)^2 over the voxels that are NOT selected;
+ *                                     0 on a voxel that is not selected; VDR_EDT3_NONE = 2^63 - 1 on a selected voxel with no
+ *                                     candidate at all.  The largest real value is at most 2^53.
+ *   peak    int64 [volumes, 2]        the largest d2 of a volume and the lowest voxel index that attains it; (0, -1) for a volume with
+ *                                     nothing selected.  VDR_EDT3_NONE counts as a value: a full volume with outside = 0 gives
+ *                                     (VDR_EDT3_NONE, 0).
+ *   within  uint8 [volumes, Z, H, W]  1 where d2 <= r2, else 0, for r2 >= 0 (read only when within is given; a voxel that is not
+ *                                     selected has d2 = 0 and is always 1).  Given WITHOUT d2 it takes d2's place and no int64 volume
+ *                                     is written: Euclidean dilation and erosion by the ellipsoid of a radius r are this output at
+ *                                     r2 = floor(r^2 / unit^2).
+ *   outside 0 .. 7, one bit an axis: bit 2 = z, bit 1 = y, bit 0 = x.  On a set axis everything beyond the volume's two faces counts
+ *           as not selected: the minimum also runs over (q (c + 1))^2 and (q (side - c))^2 of that axis.  Scan volumes are routinely
+ *           cropped along z only, which is why this is per axis.
+ *   Out of scope: `nearest` in 3-D (it needs a tie rule of its own); spacing that differs per volume of one call.
+ *
+ * Three launches, four with peak: the x pass is vdr_op_distance_transform's row pass over the volumes * Z planes (the signed 16-bit
+ * row offset); the y pass searches outwards along y with the weights (qy, qx), stops when (qy k)^2 reaches the best so far, and leaves
+ * per voxel the in-plane VECTOR (oy, ox) as two int16 (4 bytes, not the 8 of the value); the z pass searches outwards over the slices
+ * z +- k, recomputing the in-plane value from the vector, and stops when (qz k)^2 reaches the best so far (at most max(z, Z - 1 - z)
+ * steps); with peak, one partial slot per tile of the z pass and one wave per volume that reduces them.  No atomics.  A weighted
+ * step q k is below 2^32 and its square is one 32 x 32 -> 64 multiply; sums stay below 2^60; compares are int64.
+ * When within is asked for ALONE (no d2, no peak) the searches also end early: the y search when (qy k)^2 > r2, the z search when
+ * best <= r2 or (qz k)^2 > r2 -- nothing further out can change d2 <= r2.  This changes no output bit and bounds a dilation or an
+ * erosion by a small radius to O(r) steps.  (The y search may NOT stop at best <= r2: a row further out can still be nearer in the
+ * plane, and a voxel some slices away may need exactly that difference.)
+ * workspace: vdr_distance_transform_3d_workspace_bytes = 2 bytes a voxel (row offsets) + 4 bytes a voxel (vectors), each section
+ * rounded up to 16, + 16 bytes per 64 x 16 tile of a slice (the peak's slots); 0 for a shape the op refuses.
+ *
+ * The library's usual contract: plain device pointers, the caller's stream, no host synchronisation, no allocation; a volume's
+ * outputs depend neither on `volumes` nor on its position.  A workspace below the size: VDR_ERR_WORKSPACE, nothing written.  Refused
+ * before the device is touched (VDR_ERR_INVALID): a null vol or workspace; all three outputs null; volumes < 1; Z, H, W outside
+ * 1 .. 4096; volumes * Z above 65535; Z * H * W above 2^30; a spacing outside 1 .. 65535; (qz Z)^2 + (qy H)^2 + (qx W)^2 > 2^53; a
+ * value other than 0 and 1; outside outside 0 .. 7; within with r2 < 0; a workspace not 16-byte aligned, int64 outputs not 8-byte
+ * aligned. */
+#define VDR_EDT3_NONE 9223372036854775807ll
+#define VDR_EDT3_MAX_SPACING 65535
+size_t vdr_distance_transform_3d_workspace_bytes(int volumes, int Z, int H, int W);
+int vdr_op_distance_transform_3d(const uint8_t* vol, int volumes, int Z, int H, int W, int qz, int qy, int qx, int value, int outside, int64_t r2,
+                                 void* workspace, size_t workspace_bytes, int64_t* d2, int64_t* peak, uint8_t* within, void* stream);
+
 /* SAM / MedSAM Attention.forward with use_rel_pos (third-party segment_anything ImageEncoderViT, called at
  * tfds_dense_descriptor.py:123): per (window, head) softmax(q k^T dh^-0.5 + q.Rh[qh-kh] + q.Rw[qw-kw]) v.
  *   qkv   [batch*S*S, 3*H*64] bf16, `batch` windows (or whole grids) of S x S tokens, row-major (h, w)

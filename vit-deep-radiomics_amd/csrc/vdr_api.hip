@@ -22,6 +22,7 @@
 #include "mask_stats_map.h"
 #include "components_map.h"
 #include "edt_map.h"
+#include "edt3d_map.h"
 #include "local_corr_map.h"
 #include "vdr_kernels.h"
 
@@ -2907,6 +2908,33 @@ int vdr_op_distance_transform(const uint8_t* mask, int planes, int H, int W, int
   if (int rc = refuse_workspace(op, workspace_bytes, distance_transform_workspace_bytes(planes, H, W))) return rc;
   RUN_OP(launch_distance_transform(mask, planes, H, W, value, outside, r2, workspace, d2, nearest, peak, within, (hipStream_t)stream),
          "distance_transform");
+}
+
+// ---- exact 3-D Euclidean distance transform with integer voxel spacing (csrc/edt3d.hip) ----
+size_t vdr_distance_transform_3d_workspace_bytes(int volumes, int Z, int H, int W) { return distance_transform_3d_workspace_bytes(volumes, Z, H, W); }
+
+int vdr_op_distance_transform_3d(const uint8_t* vol, int volumes, int Z, int H, int W, int qz, int qy, int qx, int value, int outside, int64_t r2,
+                                 void* workspace, size_t workspace_bytes, int64_t* d2, int64_t* peak, uint8_t* within, void* stream) {
+  static_assert(VDR_EDT3_NONE == EDT3_NONE && VDR_EDT3_MAX_SPACING == EDT3_MAX_Q && VDR_EDT_MAX_SIDE == EDT_MAX_SIDE, "include/vdr.h and edt3d_map.h");
+  const char* op = "vdr_op_distance_transform_3d";
+  if (!vol || !workspace) return refuse(op, VDR_ERR_INVALID, "null pointer");
+  if (!d2 && !peak && !within) return refuse(op, VDR_ERR_INVALID, "no output: d2, peak and within are all null");
+  if (volumes < 1 || Z < 1 || Z > EDT_MAX_SIDE || H < 1 || H > EDT_MAX_SIDE || W < 1 || W > EDT_MAX_SIDE)
+    return refuse(op, VDR_ERR_INVALID, "volumes must be >= 1, Z, H and W 1 .. " + std::to_string(EDT_MAX_SIDE));
+  if ((int64_t)volumes * Z > EDT_MAX_PLANES) return refuse(op, VDR_ERR_INVALID, "volumes * Z must be at most 65535");
+  if ((int64_t)Z * H * W > EDT3_MAX_VOXELS) return refuse(op, VDR_ERR_INVALID, "Z * H * W must be at most 2^30");
+  if (qz < 1 || qz > EDT3_MAX_Q || qy < 1 || qy > EDT3_MAX_Q || qx < 1 || qx > EDT3_MAX_Q)
+    return refuse(op, VDR_ERR_INVALID, "spacing must be three integers in 1 .. 65535");
+  if (!edt3_spacing_ok(Z, H, W, qz, qy, qx))
+    return refuse(op, VDR_ERR_INVALID, "(qz Z)^2 + (qy H)^2 + (qx W)^2 exceeds 2^53: distances would not be exact; use a coarser quantum");
+  if (value != 0 && value != 1) return refuse(op, VDR_ERR_INVALID, "value must be 0 or 1");
+  if (outside < 0 || outside > 7) return refuse(op, VDR_ERR_INVALID, "outside must be 0 .. 7 (bit 2 = z, bit 1 = y, bit 0 = x)");
+  if (within && r2 < 0) return refuse(op, VDR_ERR_INVALID, "r2 must be >= 0");
+  if (!aligned16({workspace}) || (((uintptr_t)d2 | (uintptr_t)peak) & 7))
+    return refuse(op, VDR_ERR_INVALID, "workspace must be 16-byte aligned, d2 and peak to their element");
+  if (int rc = refuse_workspace(op, workspace_bytes, distance_transform_3d_workspace_bytes(volumes, Z, H, W))) return rc;
+  RUN_OP(launch_distance_transform_3d(vol, volumes, Z, H, W, qz, qy, qx, value, outside, r2, workspace, d2, peak, within, (hipStream_t)stream),
+         "distance_transform_3d");
 }
 
 int vdr_op_attention_relpos(const void* qkv, const float* rel_pos_h, const float* rel_pos_w, float* rel, void* out,

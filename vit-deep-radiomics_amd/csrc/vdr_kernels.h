@@ -284,6 +284,10 @@ hipError_t launch_mask_binarize(const float* logits, int64_t plane_stride, int g
 size_t distance_transform_workspace_bytes(int P, int H, int W);  // 0: a shape the op refuses
 hipError_t launch_distance_transform(const uint8_t* mask, int P, int H, int W, int value, int outside, int r2, void* work, int32_t* d2,
                                      int32_t* nearest, int32_t* peak, uint8_t* within, hipStream_t s);
+// csrc/edt3d.hip: exact 3-D Euclidean distance transform with integer voxel spacing (include/vdr.h; the mapping is edt3d_map.h)
+size_t distance_transform_3d_workspace_bytes(int P, int Z, int H, int W);  // 0: a shape the op refuses
+hipError_t launch_distance_transform_3d(const uint8_t* vol, int P, int Z, int H, int W, int qz, int qy, int qx, int value, int outside,
+                                        int64_t r2, void* work, int64_t* d2, int64_t* peak, uint8_t* within, hipStream_t s);
 hipError_t launch_attention_pool(const float* q, const void* kv, int64_t ldkv, void* out, int batch, int n, int heads,
                                  int head_dim, hipStream_t s);
 

@@ -154,6 +154,8 @@ SYMBOLS = {
     "vdr_op_mask_clean": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, C.c_size_t, _P, _P, _P, _P]),
     "vdr_distance_transform_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "vdr_op_distance_transform": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, C.c_size_t, _P, _P, _P, _P, _P]),
+    "vdr_distance_transform_3d_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "vdr_op_distance_transform_3d": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.c_int64, _P, C.c_size_t, _P, _P, _P, _P]),
     "vdr_op_nms": (_I, [_P, _P, _I, _F, _P, C.c_size_t, _P, _P, _P, _P]),
     "vdr_op_attention_relpos": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "vdr_op_layernorm_window": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),

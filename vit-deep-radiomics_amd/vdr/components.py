@@ -34,6 +34,21 @@ def as_planes(mask, what: str):
     return (m.view(torch.uint8) if m.dtype == torch.bool else m), single
 
 
+def as_volumes(vol, what: str):
+    """A bool / uint8 mask of 3 or 4 dimensions, the last three one volume -> ([P, Z, H, W] uint8 contiguous, whether a volume
+    dimension was added).  The P Z slices go through as_planes, the one operand check of the mask-plane ops; a volume has at most
+    2^30 voxels."""
+    if not isinstance(vol, torch.Tensor) or vol.dtype not in (torch.bool, torch.uint8) or vol.dim() not in (3, 4):
+        raise ValueError(f"{what}: mask must be a bool or uint8 tensor [Z, H, W] or [P, Z, H, W]")
+    single = vol.dim() == 3
+    v = vol[None] if single else vol
+    P, Z, H, W = (int(n) for n in v.shape)
+    if not (P >= 1 and 1 <= Z <= MAX_SIDE and Z * H * W <= 2**30):
+        raise ValueError(f"{what}: volumes of 1 .. {MAX_SIDE} slices and at most 2^30 voxels, got {tuple(vol.shape)}")
+    planes, _ = as_planes(v.reshape(P * Z, H, W), what)
+    return planes.reshape(P, Z, H, W), single
+
+
 def check_connectivity(what: str, connectivity):
     if isinstance(connectivity, bool) or connectivity not in (4, 8):
         raise ValueError(f"{what}: connectivity must be 4 or 8, got {connectivity!r}")

@@ -589,6 +589,41 @@ def distance_transform(mask, value: int = 1, outside: bool = False, return_neare
     return out[0] if len(out) == 1 else tuple(out)
 
 
+def distance_transform_3d(vol, spacing=(1, 1, 1), value: int = 1, outside=False, return_peak: bool = False, threshold=None, return_d2: bool = True,
+                          workspace=None):
+    """Exact 3-D Euclidean distance transform of mask volumes under integer voxel spacing (vdr_op_distance_transform_3d): vol bool
+    or uint8 [Z, H, W] or [P, Z, H, W] on the device (nonzero = set), spacing three integers (qz, qy, qx) in 1 .. 65535
+    (vdr.morphology.quantize_spacing makes them from millimetres), value 1 (the set voxels are measured) or 0 (the clear ones) ->
+    d2 int64 like vol: min (qz dz)^2 + (qy dy)^2 + (qx dx)^2 over the voxels that are not selected, 0 where not selected, 2^63 - 1
+    where there is none.  outside: False, True or three bools (z, y, x) -- on a set axis everything beyond the volume's two faces
+    counts as not selected.  return_peak adds peak int64 [P, 2] (the largest d2 and the lowest voxel index (z H + y) W + x that
+    attains it, (0, -1) for a volume with nothing selected).  threshold = r2 (an integer >= 0): the first result is the uint8
+    volume d2 <= r2 INSTEAD of d2; no int64 volume is written, and asked for alone it lets the searches end after O(r) steps.
+    return_d2=False leaves the first result out (with return_peak, without threshold).  Bit for bit
+    vdr.morphology.edt3d_torch and rint(scipy.ndimage.distance_transform_edt(selected, sampling=spacing) ^ 2); nothing here
+    synchronises.  Every refusal of an argument comes before the device is asked for."""
+    from . import components as cc
+    from . import morphology as mo
+    v, single = cc.as_volumes(vol, "distance_transform_3d")
+    q, value, bits, r2 = mo.check_edt3("distance_transform_3d", spacing, value, outside, threshold, v.shape[1:])
+    if not return_d2 and (r2 is not None or not return_peak):
+        raise ValueError("distance_transform_3d: return_d2=False goes with return_peak and without threshold")
+    P, Z, H, W = (int(n) for n in v.shape)
+    if not v.is_cuda:
+        raise ValueError("distance_transform_3d: mask must live on the HIP device")
+    lib = L.load()
+    workspace = _workspace(workspace, lib.vdr_distance_transform_3d_workspace_bytes(P, Z, H, W), v.device)
+    first = torch.empty((P, Z, H, W), dtype=torch.int64 if r2 is None else torch.uint8, device=v.device) if return_d2 else None
+    peak = torch.empty((P, 2), dtype=torch.int64, device=v.device) if return_peak else None
+    L.check(lib.vdr_op_distance_transform_3d(v.data_ptr(), P, Z, H, W, q[0], q[1], q[2], value, bits, 0 if r2 is None else r2, workspace.data_ptr(),
+                                             workspace.numel(), _p(first) if r2 is None else None, _p(peak),
+                                             _p(first) if r2 is not None else None, _s(v)))
+    out = [first[0] if single else first] if return_d2 else []
+    if return_peak:
+        out.append(peak)
+    return out[0] if len(out) == 1 else tuple(out)
+
+
 def log_bin(x: torch.Tensor, gh: int, gw: int, hierarchy: int = 2, out_dtype=torch.float32, out=None) -> torch.Tensor:
     """Log-binning of a dense descriptor map (vdr_op_log_bin): x [B, gh*gw, C] bf16 or fp32 -- contiguous, or a view whose
     last dimension is contiguous, such as the key columns and patch rows buf[:, P:, C:2*C] of a [B, P + n, 3C] qkv

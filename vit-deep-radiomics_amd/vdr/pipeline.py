@@ -202,13 +202,38 @@ def _region_kwargs(min_region_area, fill_holes, keep_largest):
     return dict(min_area=min_region_area, holes=fill_holes, islands=min_region_area > 0 and not keep_largest, largest=keep_largest)
 
 
-def _grow(what, masks, grow):
-    """Euclidean dilation of finished bool masks [S, H, W] on the device by `grow` pixels (vdr.morphology.dilate); 0: the masks"""
+def _check_grow(what, grow, spatial_res):
+    """the checks of grow / spatial_res before any device work -> the spacing (sz, sy, sx) of the [S, H, W] mask volume, or None.
+    spatial_res is in the reference's (x, y, z) order, as tfds2voxels returns it."""
     from . import morphology as mo
+    if spatial_res is None:
+        mo.check_radius(what + ": grow", grow)
+        return None
+    try:
+        res = tuple(float(v) for v in spatial_res)
+    except (TypeError, ValueError):
+        res = ()
+    if len(res) != 3:
+        raise ValueError(f"{what}: spatial_res must be the voxel size (x, y, z), got {spatial_res!r}")
+    spacing = (res[2], res[1], res[0])
+    try:
+        _, quantum = mo.quantize_spacing(spacing)
+    except ValueError as e:
+        raise ValueError(f"{what}: spatial_res: {e}") from None
+    mo.radius_squared(what + ": grow", grow, quantum)
+    return spacing
+
+
+def _grow(what, masks, grow, spacing=None):
+    """Euclidean dilation of finished bool masks [S, H, W] on the device by `grow` (vdr.morphology.dilate): slice by slice by the
+    disc of that many pixels, or, with the spacing (sz, sy, sx) of the volume, by the 3-D ellipsoid of that length; 0: the masks"""
+    from . import morphology as mo
+    if spacing is not None:
+        return mo.dilate(masks, grow, spacing=spacing)
     return masks if mo.check_radius(what, grow) == 0 else mo.dilate(masks, grow)
 
 
-def segment_volume(model, img_3d, boxes, max_batch=16, threshold=0.0, min_region_area=0, fill_holes=False, keep_largest=False, grow=0.0):
+def segment_volume(model, img_3d, boxes, max_batch=16, threshold=0.0, min_region_area=0, fill_holes=False, keep_largest=False, grow=0.0, spatial_res=None):
     """The mask generate_features takes as mask_3d, from box prompts: img_3d (H, W, S) gray volume in [0, 1] (or (H, W, S, 3)),
     boxes [S, 4] (x0, y0, x1, y1) in slice pixels, one per slice, or one box [4] for every slice -> (H, W, S) bool numpy.
     The slices run in chunks of `max_batch` through prepare -> model.segment (mask token 0) -> bilinear logits at slice
@@ -217,11 +242,13 @@ def segment_volume(model, img_3d, boxes, max_batch=16, threshold=0.0, min_region
     also fills the holes below it, keep_largest keeps only each slice's largest component (Segmentation.clean: connected
     components on the device, 8-connected, 2-D).  All three off is the path without them, bit for bit.  grow > 0 dilates the
     finished mask of every slice, after any cleaning, by the Euclidean disc of that radius in slice pixels (compared as
-    floor(grow^2); one distance transform on the device); 0 is the path without it."""
-    from . import morphology as mo
+    floor(grow^2); one distance transform on the device); 0 is the path without it.  spatial_res = the voxel size (x, y, z) as
+    tfds2voxels returns it: grow is then a LENGTH in that unit and the dilation is the 3-D ellipsoid over the finished volume
+    (vdr.morphology.dilate with spacing: one thresholded 3-D transform, the spacing rounded to 2^-10 of its unit); None is the
+    slice-by-slice path, bit for bit."""
     from . import segment as sg
     regions = _check_regions("segment_volume", min_region_area, fill_holes, keep_largest)
-    mo.check_radius("segment_volume: grow", grow)
+    spacing = _check_grow("segment_volume", grow, spatial_res)
     sg._require(model, "segment_volume")
     vol = torch.as_tensor(img_3d)
     if vol.dim() not in (3, 4) or (vol.dim() == 4 and vol.shape[3] != 3):
@@ -246,22 +273,22 @@ def segment_volume(model, img_3d, boxes, max_batch=16, threshold=0.0, min_region
             out[s0:s1] = seg.clean(size=(H, W), threshold=threshold, **_region_kwargs(min_region_area, fill_holes, keep_largest))[0][:, 0, 0]
         else:
             out[s0:s1] = seg.masks(size=(H, W), threshold=threshold)[:, 0, 0]
-    return _grow("segment_volume: grow", out, grow).permute(1, 2, 0).cpu().numpy()
+    return _grow("segment_volume: grow", out, grow, spacing).permute(1, 2, 0).cpu().numpy()
 
 
 def propagate_segmentation(model, img_3d, box, index, direction="both", margin=8, use_mask_prompt=True, max_batch=16, threshold=0.0,
-                           min_region_area=0, fill_holes=False, keep_largest=False, grow=0.0, point_prompt=None):
+                           min_region_area=0, fill_holes=False, keep_largest=False, grow=0.0, point_prompt=None, spatial_res=None):
     """segment_volume from ONE annotation: img_3d (H, W, S) gray volume in [0, 1] (or (H, W, S, 3)), box (x0, y0, x1, y1) in
     slice pixels on slice `index` -> (H, W, S) bool numpy, the array generate_features takes as mask_3d.  The slices are
     prepared in chunks of max_batch, model.propagate_masks carries the mask through the volume (margin in pixels of the
     prepared input), the logits are resampled to slice resolution; one synchronisation per volume.  min_region_area, fill_holes and
     keep_largest as segment_volume's: they clean the RETURNED masks slice by slice, the propagation itself is untouched; grow as
     segment_volume's, after the cleaning.  point_prompt: model.propagate_masks' (None, or "inner" for the neighbour's most
-    interior pixel as a positive click on every further slice)."""
-    from . import morphology as mo
+    interior pixel as a positive click on every further slice).  spatial_res: segment_volume's (grow as a length, the 3-D
+    ellipsoid over the finished volume); None is the slice-by-slice path, bit for bit."""
     from . import segment as sg
     regions = _check_regions("propagate_segmentation", min_region_area, fill_holes, keep_largest)
-    mo.check_radius("propagate_segmentation: grow", grow)
+    spacing = _check_grow("propagate_segmentation", grow, spatial_res)
     if point_prompt not in (None, "inner"):
         raise ValueError(f"propagate_segmentation: point_prompt must be None or 'inner', got {point_prompt!r}")
     sg._require(model, "propagate_segmentation")
@@ -287,7 +314,7 @@ def propagate_segmentation(model, img_3d, box, index, direction="both", margin=8
         masks = seg.clean(size=(H, W), threshold=threshold, **_region_kwargs(min_region_area, fill_holes, keep_largest))[0]
     else:
         masks = seg.masks(size=(H, W), threshold=threshold)
-    return _grow("propagate_segmentation: grow", masks, grow).permute(1, 2, 0).cpu().numpy()
+    return _grow("propagate_segmentation: grow", masks, grow, spacing).permute(1, 2, 0).cpu().numpy()
 
 
 # ---- tfds_dense_descriptor.py:142-165 -----------------------------------------------------------------------

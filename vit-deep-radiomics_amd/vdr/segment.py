@@ -153,8 +153,20 @@ class VolumeSegmentation:
         return clean_planes("VolumeSegmentation.clean", self.low_res_logits, self.input_size if size is None else size, threshold, min_area, holes,
                             islands, largest, connectivity, max_planes)
 
-    def distance(self, size=None, threshold: float = 0.0) -> torch.Tensor:
-        """int32 [Z, h, w]: Segmentation.distance for the slices of a volume, slice by slice (2-D distances)"""
+    def distance(self, size=None, threshold: float = 0.0, spacing=None) -> torch.Tensor:
+        """int32 [Z, h, w]: Segmentation.distance for the slices of a volume, slice by slice (2-D distances).  spacing=(sz, sy, sx),
+        the voxel size at `size`: int64 [Z, h, w], the 3-D squared distances of the whole volume in units of the quantum squared
+        (vdr.morphology.quantize_spacing; sqrt(d2) * 2^-10 is the distance in spacing's unit)"""
+        if spacing is not None:
+            from . import morphology as mo
+            from . import ops
+            what = "VolumeSegmentation.distance"
+            q, _ = mo.quantize_spacing(spacing)
+            oh, ow = ops.check_out_size(what, self.input_size if size is None else size)
+            if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or threshold != threshold:
+                raise ValueError(f"{what}: threshold must be a number, got {threshold!r}")
+            mo.check_edt3(what, q, 1, False, None, (int(self.low_res_logits.shape[0]), oh, ow))
+            return mo._edt3(ops.mask_binarize(self.low_res_logits, (oh, ow), float(threshold)), q, 1, 0)
         return distance_planes("VolumeSegmentation.distance", self.low_res_logits, self.input_size if size is None else size, threshold,
                                (int(self.low_res_logits.shape[0]),))
 
@@ -163,18 +175,26 @@ class VolumeSegmentation:
         from . import morphology as mo
         return mo.inner_point(self.low_res_logits > 0, self.input_size, outside=True)
 
-    def compare(self, other, size=None, threshold: float = 0.0, spacing: float = 1.0, tolerance: float = 1.0) -> dict:
+    def compare(self, other, size=None, threshold: float = 0.0, spacing=1.0, tolerance: float = 1.0) -> dict:
         """This volume's masks against `other` -- another VolumeSegmentation or a bool / uint8 mask tensor [Z, h, w] on the same
         device -- slice by slice at the input size or `size`: vdr.metrics.overlap (dice, iou, intersection, a, b) and
         vdr.metrics.surface (hd, hd95, assd, nsd) in one dict of [Z] tensors.  The distance transforms run on the device; the
-        surface measures synchronise once per slice."""
+        surface measures synchronise once per slice.  spacing=(sz, sy, sx), the voxel size at `size`: the two VOLUMES are compared
+        as wholes, in 3-D and in spacing's unit -- every entry is a [1] tensor (vdr.metrics.surface with a 3-sequence)."""
         from . import metrics
+        if not isinstance(spacing, (int, float)):
+            from . import morphology as mo
+            mo.quantize_spacing(spacing)
         size = self.input_size if size is None else tuple(int(v) for v in size)
         a = self.masks(size, threshold)
         b = other.masks(size, threshold) if isinstance(other, VolumeSegmentation) else other
         if not isinstance(b, torch.Tensor) or tuple(b.shape) != tuple(a.shape):
             raise ValueError(f"VolumeSegmentation.compare: other must be a VolumeSegmentation or a mask tensor {tuple(a.shape)}, got "
                              f"{tuple(b.shape) if isinstance(b, torch.Tensor) else type(b).__name__}")
+        if not isinstance(spacing, (int, float)):
+            out = metrics.overlap(a, b, volumes=True)
+            out.update(metrics.surface(a, b, spacing=spacing, tolerance=tolerance))
+            return out
         out = metrics.overlap(a, b)
         out.update(metrics.surface(a, b, spacing=spacing, tolerance=tolerance))
         return out
